@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """NNUE training throughput on MI355X  (metric: BASELINE.json -- images/sec of the full training step).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c1|c3|c4]      (N > 1: starts its own N ranks)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c1|c3|c4] [--full] [--dump-outputs DIR]
+                                                                                      (N > 1: starts its own N ranks)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one pass of the hot path over one batch of synthetic input already resident in HBM:
@@ -11,11 +12,15 @@ train.py:359-366 does per batch.  Default workload = BASELINE configs[1]: CIFAR-
 GPU, 800 -> 1024/128/32 -> 10, fp32, SGD(lr 0.01, momentum 0.9, wd 2e-4), clip 1.0 (config/train_nnue.py).
 Weak scaling: every GPU keeps batch 512 (N=8 is BASELINE configs[4], global batch 4096).
 
-Rank 0 prints ONE JSON line.  Beyond the contract fields it carries
+Rank 0 prints ONE JSON line: images/s and ms_per_step of the K timed steps, and the workload's configuration.  A plain run
+sets up, warms up, times the K steps and (with --dump-outputs) writes what the last timed step computed, nothing else.
+With --full the line also carries
   roofline      dominant kernel: algorithmic bytes per launch (one gathered / accumulated table
                 row = L1*4 bytes) / its average duration, measured here with HIP events on the launch
                 stream in an instrumented pass that follows the timed region (same buffers, same process);
   kernels       the same figure for every C entry point of the step;
+  gather_path   the same step with the LDS-staged gather kernels (N=1, where the product form is the default);
+  config.single_bucket  the bucketed workload (c3) on plain randn images, where one layer stack takes the whole batch;
   cpu_baseline  the oracle's loop-form port of the reference CPU path (N=1 only) on a bounded sample.
 """
 import argparse
@@ -68,6 +73,13 @@ def parse():
                          "steps left over after the whole groups run as single-step graphs; 1 = one graph launch per step; "
                          "0 (default) = the group size in 5..32 that leaves the fewest single steps for --steps")
     ap.add_argument("--no-graph", action="store_true", help="launch kernels eagerly instead of replaying a hipGraph")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the instrumented pass (per-kernel durations, "
+                         "roofline), the single-bucket run of the bucketed workload, the gather-kernel form and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed -- its mean loss, its logits and the "
+                         "parameters after its update -- as DIR/<name>.npy in float32; an array of more than 2^22 elements is "
+                         "written as a fixed seeded sample of its elements (the same positions in every run)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-gather-compare", action="store_true",
                     help="skip the second pass with the LDS-staged gather kernels (NNUE_FT_PATH=bits) and its HBM-roofline object")
@@ -75,7 +87,10 @@ def parse():
     ap.add_argument("--launcher-selftest", action="store_true",
                     help="rehearse the self-launch path without a GPU: the ranks rendezvous over gloo, all-reduce a small flat "
                          "buffer through the trainer's DataParallel plumbing and rank 0 prints the JSON line (tests/test_bench_launcher.py)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def self_launch(args) -> int:
@@ -158,6 +173,31 @@ def cpu_baseline(cfg, budget_s):
     return {"value": round(batch * steps / dt, 1), "unit": "images/sec", "cores": cores, "of": os.cpu_count(), "kind": "port",
             "sample": f"{steps} full training steps of batch {batch} after 1 warm-up ({dt:.1f} s), "
                       f"oracle loop form (per-sample Python loops + autograd, as nnue.py:601-633/:694-708), torch CPU fp32"}
+
+
+DUMP_MAX_ELEMS = 1 << 22  # per array (16 MB of float32); the 224x224 table (67 M elements) is dumped as a sample
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: Path, trainer, last_loss) -> None:
+    """--dump-outputs: what the last timed step computed, as a caller of the trainer receives it -- its mean loss, its logits
+    and every trained parameter after its update -- one DIR/<name>.npy each, float32.  Inputs and initial parameters are
+    seeded, so two builds run with the same arguments can be compared array by array.  An array of more than DUMP_MAX_ELEMS
+    elements is written as the elements at DUMP_MAX_ELEMS positions drawn once from a generator seeded with 0 (ascending)."""
+    import numpy as np
+    arrays = {"loss": last_loss.reshape(1), "logits": trainer.logits, **{k: trainer.p[k] for k in trainer.layout.names}}
+    out_dir.mkdir(parents=True, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMS:
+            pos = torch.randint(0, t.numel(), (DUMP_MAX_ELEMS,), generator=torch.Generator().manual_seed(0)).sort().values
+            t = t.reshape(-1)[pos.to(t.device)]
+        a = t.float().cpu().numpy()
+        total += a.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise SystemExit(f"--dump-outputs: more than {DUMP_MAX_BYTES >> 20} MB at {name}")
+        np.save(out_dir / f"{name}.npy", a)
 
 
 def main():
@@ -268,296 +308,301 @@ def main():
     n_mean, n_max = trainer.active_stats()
     bucket_hist = (torch.bincount(trainer.bucket_plan.bucket.long(), minlength=trainer.K).tolist()
                    if trainer.bucket_plan is not None else None)
+    if args.dump_outputs and rank == 0:  # before --full trains on: the state the last timed step left
+        dump_outputs(Path(args.dump_outputs), trainer, last_loss)
 
-    # ---- instrumented pass: per-entry-point durations from HIP events on the launch stream
-    # FeatureTransformer kernel family: dense MFMA products, bit-mask/LDS-staged gather kernels or id-list kernels
-    ftp = {"mfma": "nnue_ftm", "bits": "nnue_ftb", "list": "nnue_ft"}[trainer.ft_path]
-    names = (["nnue_ftm_conv_binarize"] if trainer.use_mfma else
-             ["nnue_conv3x3_forward", {"bits": "nnue_binarize_bits", "list": "nnue_binarize_features"}[trainer.ft_path]])
-    fwd_entry = f"{ftp}_forward_l1" if getattr(trainer, "fuse_l1", False) else f"{ftp}_forward"  # fused: + layer-1 slabs in the epilogue
-    if trainer.K > 1 and trainer.use_mfma:
-        fwd_entry = f"{ftp}_forward_grouping"  # + the bucket grouping as one extra workgroup of the launch
-    names += [fwd_entry] + (["nnue_classifier_train_step_bucketed"] if trainer.K > 1 else ["nnue_classifier_train_step"])
-    # weight + value gradient (+ tail rows) go through one C call; it is one launch at launch-sized shapes and the two
-    # separate launches at the 224x224 shapes (policy in nnue_ftm_backward)
-    merged = trainer.use_mfma and trainer.merge_backward
-    val_entry = "nnue_ftm_backward_values_ws" if trainer.use_mfma else f"{ftp}_backward_values"  # (the product form takes a workspace)
-    bwd_entry = f"{ftp}_backward_bucketed" if (merged and trainer.K > 1) else f"{ftp}_backward"
-    names += [bwd_entry] if merged else [f"{ftp}_backward_weight", val_entry]
-    factor_exchange = bool(getattr(trainer, "factor_exchange", False))  # data parallel: the gradient's factors are gathered, same fused update
-    fused_update = bool(getattr(trainer, "fuse_table_update", False)) or factor_exchange
-    if fused_update:  # weight gradient formed and consumed in the update (no d_weight)
-        names = [n for n in names if n not in (f"{ftp}_backward", f"{ftp}_backward_bucketed", f"{ftp}_backward_weight")]
-        names += [val_entry, f"{ftp}_backward_tail_rows"] + (["nnue_dp_factor_pack", "nnue_dp_factor_unpack"] if factor_exchange else [])
-        names += [f"{ftp}_gram_sqnorm", f"{ftp}_gram_sqnorm_tail", f"{ftp}_backward_weight_update"]
-        names = list(dict.fromkeys(names))
-        merged = False
-    names += ["nnue_ste_conv_backward", "nnue_sgd_step"]
-    # big table inside a step group: the update of a step also forms the next step's forward (one pass over the table); the
-    # instrumented pass then issues the group's launches eagerly (step_many(timers=...)) instead of single steps
-    group_fused = bool(getattr(trainer, "fuse_next_forward", False)) and S > 1
-    upd_fwd = f"{ftp}_backward_weight_update_forward"
-    if group_fused:
-        names += [upd_fwd]
-    timers = {k: [] for k in names}
-    isteps = max(5, min(50, args.steps))
-    if group_fused:
-        isteps = max(S, isteps // S * S)
-        group = lambda i0: tuple((i0 + j) % SLOTS for j in range(S))  # noqa: E731
-        trainer.step_many(group(0), timers={k: [] for k in names})
-    else:
-        for i in range(3):
-            trainer.step(slot=i % SLOTS, timers={k: [] for k in names})  # settle into eager mode
-    torch.cuda.synchronize(dev)
-    t1 = time.perf_counter()
-    if group_fused:
-        for i0 in range(0, isteps, S):
-            trainer.step_many(group(i0), timers=timers)
-    else:
-        for i in range(isteps):
-            trainer.step(slot=i % SLOTS, timers=timers)
-    torch.cuda.synchronize(dev)
-    eager_ms = (time.perf_counter() - t1) * 1e3 / isteps
-    dur_us = {}
-    for k, pairs in timers.items():
-        # an entry point may be called more than once per step (stages / phases): report its time per step
-        dur_us[k] = sum(a.elapsed_time(b) * 1e3 for a, b in pairs) / isteps if pairs else 0.0
-    if group_fused:  # these run once per group / S-1 times per group: report them per launch
-        for k in (upd_fwd, f"{ftp}_backward_weight_update", fwd_entry):
-            if timers[k]:
-                dur_us[k] = sum(a.elapsed_time(b) * 1e3 for a, b in timers[k]) / len(timers[k])
-
-    row = cfg["l1"] * 4  # bytes of one gathered / accumulated table row
-    alg = {  # algorithmic bytes per launch: fwd (n+1), value grad (n+1), weight grad n rows per image
-        f"{ftp}_forward": (n_mean + 1) * row * B,
-        val_entry: (n_mean + 1) * row * B,
-        f"{ftp}_backward_weight": n_mean * row * B,
-    }
-    if merged:
-        alg = {f"{ftp}_forward": alg[f"{ftp}_forward"], f"{ftp}_backward": alg[val_entry] + alg[f"{ftp}_backward_weight"]}
-    if fwd_entry != f"{ftp}_forward":
-        alg[fwd_entry] = alg.pop(f"{ftp}_forward")
-    if merged and bwd_entry != f"{ftp}_backward":
-        alg[bwd_entry] = alg.pop(f"{ftp}_backward")
-    if fused_update:  # value gradient as its own launch; the weight gradient is formed inside the update product
-        alg = {fwd_entry: (n_mean + 1) * row * B, val_entry: (n_mean + 1) * row * B,
-               f"{ftp}_backward_weight_update": n_mean * row * B * (world if factor_exchange else 1)}
-        if group_fused:  # + the next forward's gathered rows
-            alg[upd_fwd] = n_mean * row * B + (n_mean + 1) * row * B
-    kernels = {k: {"avg_us": round(dur_us[k], 2), **({"alg_GBps": round(alg[k] / dur_us[k] * 1e-3, 1)} if k in alg and dur_us[k] > 0 else {})}
-               for k in names}
-    KERNEL_OF = {  # C entry point -> (kernel name prefix, substring) in rocprof / PMC summaries
-        "nnue_ftm_forward": ("ftm_gemm", "FwdEpi"), "nnue_ftm_forward_grouping": ("ftm_gemm", "FwdEpi"), "nnue_ftm_forward_l1": ("ftm_forward_l1", ""),
-        "nnue_ftm_backward": ("ftm_backward", ""), "nnue_ftm_backward_bucketed": ("ftm_backward", ""),
-        "nnue_ftm_backward_weight": ("ftm_gemm", "BwwEpi"), "nnue_ftm_backward_values": ("ftm_gemm", "ValEpi"), "nnue_ftm_backward_values_ws": ("ftm_gemm", "ValEpi"),
-        "nnue_ftm_backward_weight_update": ("ftm_gemm", "BwwSgdEpi"), "nnue_ftm_backward_weight_update_forward": ("ftm_update_forward_kernel", ""),
-        "nnue_ftb_forward": ("ftb_gather_kernel", ", 0,"), "nnue_ftb_backward_weight": ("ftb_gather_kernel", ", 1,"),
-        "nnue_ftb_backward_values": ("ftb_values_kernel", ""), "nnue_ft_forward": ("ft_forward_wide", ""),
-        "nnue_ft_backward_weight": ("ft_backward_weight_wide", ""), "nnue_ft_backward_values": ("ft_backward_values_wide", "")}
-
-    def match_kernel(entry, name):
-        want = KERNEL_OF.get(entry)
-        if not want:
-            return False
-        name = name.replace("(anonymous namespace)::", "").replace("void ", "")
-        if want[1] == "BwwEpi" and "BwwSgdEpi" in name:
-            return False
-        return name.startswith(want[0]) and want[1] in name
-
-    def pmc_traffic(entry):
-        """HBM-side bytes per launch of the kernel behind a C entry point, from the committed rocprofv3 --pmc passes
-        (profiles/*pmc_traffic.json, FETCH_SIZE doubled per the gfx950 correction + WRITE_SIZE; separate passes per
-        counter group).  Counters cannot be read inside this process, so workloads without a committed pass report null."""
-        files = sorted((ROOT / "profiles").glob("*pmc_traffic.json"))
-        if not files:
-            return None
-        data = json.loads(files[-1].read_text())
-        kernels = data.get("workloads", {}).get(args.workload.replace("c3k1", "c3")) or (data.get("kernels") if args.workload == "c2" else None)
-        if not kernels:
-            return None
-        for name, v in kernels.items():
-            if match_kernel(entry, name):
-                return {"bytes": v["hbm_bytes_corrected"], "l2_hit_rate": v["l2_hit_rate"], "kernel": name,
-                        "source": f"profiles/{files[-1].name} (committed counter passes of the eager step; not collected in this run)"}
-        return None
-
-    def rocprof_avg_us(entry):
-        """Average duration of that kernel in the latest committed `rocprofv3 --kernel-trace --stats` summary of this
-        workload's bench command (profiles/*kernel_stats_<workload>.csv)."""
-        files = sorted((ROOT / "profiles").glob(f"*kernel_stats_{args.workload.replace('c3k1', 'c3')}.csv"))
-        if not files:
-            return None
-        import csv
-        with open(files[-1]) as fh:
-            for rec in csv.DictReader(fh):
-                if match_kernel(entry, rec["Name"]) and int(rec["Calls"]) >= 10:
-                    return {"us": round(float(rec["AverageNs"]) / 1e3, 2), "source": f"profiles/{files[-1].name}"}
-        return None
-
-    dom = max(alg, key=lambda k: dur_us[k])
-    table_mb = model.input.weight.numel() * 4 / 1e6
-    alg_rate = alg[dom] / (dur_us[dom] * 1e-6) / 1e9 if dur_us[dom] > 0 else 0.0
-    if trainer.ft_path == "mfma":
-        # Products over the whole map (active and inactive positions).  Each product is priced on the unit it runs on
-        # (nnue_ftm_uses_bf16): the f32-input MFMA (157.3 TF) or, for the two products whose A operand is the binary map,
-        # three bf16 MFMAs per logical product (2.5 PF dense; 3x the flops as matrix work).  Beside it the compulsory HBM
-        # bytes of the launch; the bound reported is whichever ideal time is longer.
-        from nnue_hip import lib as _lib
-        direct = min(trainer.F - 1, trainer.P)
-        L1, L2, F, P = cfg["l1"], cfg["l2"], trainer.F, trainer.P
-        uses = lambda which: bool(_lib.load().nnue_ftm_uses_bf16(which, B, F, P, L1))  # noqa: E731
-        f_fwd, f_w, f_v, f_l1 = 2.0 * B * direct * L1, 2.0 * B * direct * L1, 2.0 * B * P * L1, 2.0 * B * L1 * L2
-        tbl, mp, act = direct * L1 * 4.0, float(B * P), B * L1 * 4.0
-        work = {  # entry -> ([(unit, useful flops)], compulsory bytes)
-            f"{ftp}_forward": ([("bf16" if uses(0) else "f32", f_fwd)], tbl + mp + act),
-            f"{ftp}_forward_grouping": ([("bf16" if uses(0) else "f32", f_fwd)], tbl + mp + act),
-            f"{ftp}_forward_l1": ([("bf16" if uses(0) else "f32", f_fwd), ("f32", f_l1)], tbl + mp + act + (L1 // 64) * B * L2 * 4.0),
-            f"{ftp}_backward_weight": ([("bf16" if uses(1) else "f32", f_w)], mp + act + tbl),
-            val_entry: ([("bf16x6" if uses(4) else "f32", f_v)], act + F * L1 * 4.0 + mp + B * P * 4.0),
-            # (under the factor exchange the product contracts the GLOBAL batch: world x the flops, map and d_ft rows)
-            f"{ftp}_backward_weight_update": ([("bf16", f_w * (world if factor_exchange else 1))],
-                                              (mp + act) * (world if factor_exchange else 1) + 2 * tbl + (2 * tbl if OPT["momentum"] else 0)),
-        }
-        # the update of step t + the forward of step t+1 in one pass: both products, the table and its momentum read and written
-        # once, both maps (the forward's own read of the table is what the fusion removes)
-        work[upd_fwd] = ([("bf16", f_w), ("bf16", f_fwd)], 2 * mp + 2 * act + 2 * tbl + (2 * tbl if OPT["momentum"] else 0))
-        bw = [("bf16" if uses(2) else "f32", f_w), ("bf16x6" if uses(5) else "f32", f_v)] + ([("f32", f_l1)] if getattr(trainer, "ride_dw1", False) else [])
-        work[f"{ftp}_backward"] = (bw, 2 * mp + act + F * L1 * 4.0 + tbl + B * P * 4.0)
-        work[f"{ftp}_backward_bucketed"] = work[f"{ftp}_backward"]
-        PEAK = {"f32": MFMA_F32_PEAK_TFLOPS, "bf16": MFMA_BF16_PEAK_TFLOPS, "bf16x6": MFMA_BF16_PEAK_TFLOPS}
-        PASSES = {"f32": 1, "bf16": 3, "bf16x6": 6}  # bf16 MFMAs per logical product: exact split of one operand / six plane products of two
-        units, comp_bytes = work[dom]
-        useful = sum(f for _, f in units)
-        t_mfma = sum(f * PASSES[u] / (PEAK[u] * 1e12) for u, f in units)  # seconds at the units' peaks
-        t_hbm = comp_bytes / (HBM_PEAK_GBS * 1e9)
-        dur = dur_us[dom] * 1e-6
-        rp = rocprof_avg_us(dom)
-        common = {"kernel": dom, "traffic": (pmc_traffic(dom) or {}).get("bytes"), "traffic_detail": pmc_traffic(dom),
-                  "compulsory_bytes": int(comp_bytes), "flops_per_launch": int(useful),
-                  "matrix_work": [{"unit": u, "useful_flops": int(f), "peak_TFLOPs": PEAK[u], "mfma_flops": int(f * PASSES[u])}
-                                  for u, f in units],
-                  "ideal_us": {"mfma": round(t_mfma * 1e6, 2), "hbm": round(t_hbm * 1e6, 2)},
-                  "avg_launch_us": round(dur_us[dom], 2), "rocprof_avg_us": rp["us"] if rp else None, "rocprof_source": rp["source"] if rp else None,
-                  "alg_bytes_per_launch": int(alg[dom]), "alg_GBps": round(alg_rate, 1),
-                  # SURVEY 8d's "one table row per gathered id" prices a gather; a product re-uses a staged row across the
-                  # samples of a tile, so for this path the algorithmic-byte rate is NOT a lower bound on traffic (it exceeds
-                  # the HBM peak while the table is cache-resident) -- the bound is the one reported in bound/peak/frac
-                  "alg_is_bound": False}
-        if t_hbm >= t_mfma:
-            rate = comp_bytes / dur / 1e9 if dur > 0 else 0.0
-            roofline = {"bound": "hbm", "achieved": round(rate, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(rate / HBM_PEAK_GBS, 4),
-                        # the same fraction with the kernel's average duration in the committed rocprofv3 summary instead of this run's events
-                        "frac_rocprof": round(comp_bytes / (rp["us"] * 1e-6) / 1e9 / HBM_PEAK_GBS, 4) if rp else None, **common,
-                        "regime": "compulsory bytes of the launch (table %.1f MB streamed once, parameters and momentum read and written where the "
-                                  "update is fused) / HIP-event duration; the matrix work of the launch would take %.1f us at its units' peaks"
-                                  % (table_mb, t_mfma * 1e6)}
+    # ---- everything below measures beside the headline figure and runs only with --full
+    eager_ms = roofline = kernels = single_bucket = gather = None
+    if args.full:
+        # ---- instrumented pass: per-entry-point durations from HIP events on the launch stream
+        # FeatureTransformer kernel family: dense MFMA products, bit-mask/LDS-staged gather kernels or id-list kernels
+        ftp = {"mfma": "nnue_ftm", "bits": "nnue_ftb", "list": "nnue_ft"}[trainer.ft_path]
+        names = (["nnue_ftm_conv_binarize"] if trainer.use_mfma else
+                 ["nnue_conv3x3_forward", {"bits": "nnue_binarize_bits", "list": "nnue_binarize_features"}[trainer.ft_path]])
+        fwd_entry = f"{ftp}_forward_l1" if getattr(trainer, "fuse_l1", False) else f"{ftp}_forward"  # fused: + layer-1 slabs in the epilogue
+        if trainer.K > 1 and trainer.use_mfma:
+            fwd_entry = f"{ftp}_forward_grouping"  # + the bucket grouping as one extra workgroup of the launch
+        names += [fwd_entry] + (["nnue_classifier_train_step_bucketed"] if trainer.K > 1 else ["nnue_classifier_train_step"])
+        # weight + value gradient (+ tail rows) go through one C call; it is one launch at launch-sized shapes and the two
+        # separate launches at the 224x224 shapes (policy in nnue_ftm_backward)
+        merged = trainer.use_mfma and trainer.merge_backward
+        val_entry = "nnue_ftm_backward_values_ws" if trainer.use_mfma else f"{ftp}_backward_values"  # (the product form takes a workspace)
+        bwd_entry = f"{ftp}_backward_bucketed" if (merged and trainer.K > 1) else f"{ftp}_backward"
+        names += [bwd_entry] if merged else [f"{ftp}_backward_weight", val_entry]
+        factor_exchange = bool(getattr(trainer, "factor_exchange", False))  # data parallel: the gradient's factors are gathered, same fused update
+        fused_update = bool(getattr(trainer, "fuse_table_update", False)) or factor_exchange
+        if fused_update:  # weight gradient formed and consumed in the update (no d_weight)
+            names = [n for n in names if n not in (f"{ftp}_backward", f"{ftp}_backward_bucketed", f"{ftp}_backward_weight")]
+            names += [val_entry, f"{ftp}_backward_tail_rows"] + (["nnue_dp_factor_pack", "nnue_dp_factor_unpack"] if factor_exchange else [])
+            names += [f"{ftp}_gram_sqnorm", f"{ftp}_gram_sqnorm_tail", f"{ftp}_backward_weight_update"]
+            names = list(dict.fromkeys(names))
+            merged = False
+        names += ["nnue_ste_conv_backward", "nnue_sgd_step"]
+        # big table inside a step group: the update of a step also forms the next step's forward (one pass over the table); the
+        # instrumented pass then issues the group's launches eagerly (step_many(timers=...)) instead of single steps
+        group_fused = bool(getattr(trainer, "fuse_next_forward", False)) and S > 1
+        upd_fwd = f"{ftp}_backward_weight_update_forward"
+        if group_fused:
+            names += [upd_fwd]
+        timers = {k: [] for k in names}
+        isteps = max(5, min(50, args.steps))
+        if group_fused:
+            isteps = max(S, isteps // S * S)
+            group = lambda i0: tuple((i0 + j) % SLOTS for j in range(S))  # noqa: E731
+            trainer.step_many(group(0), timers={k: [] for k in names})
         else:
-            blended = useful / t_mfma / 1e12  # the peak this launch could reach given which unit each product runs on
-            achieved = useful / dur / 1e12 if dur > 0 else 0.0
-            roofline = {"bound": "mfma", "achieved": round(achieved, 2), "peak": round(blended, 1), "unit": "TFLOP/s",
-                        "frac": round(achieved / blended, 4),
-                        "frac_rocprof": round(useful / (rp["us"] * 1e-6) / 1e12 / blended, 4) if rp else None,
-                        "frac_of_f32_mfma_peak": round(achieved / MFMA_F32_PEAK_TFLOPS, 4),  # round 1's pricing of the same launch, for comparison
-                        **common,
-                        "regime": "useful flops of the products in the launch (2 M N K over the whole map) / HIP-event duration, against the "
-                                  "peak of the unit each product runs on (f32-input MFMA 157.3 TF; bf16 MFMA 2.5 PF at three MFMAs per "
-                                  "product for the exact split of one operand, six for the plane products of two f32 operands); table %.1f MB" % table_mb}
-    else:
-        roofline = {"bound": "hbm", "kernel": dom, "achieved": round(alg_rate, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": round(alg_rate / HBM_PEAK_GBS, 4), "traffic": (pmc_traffic(dom) or {}).get("bytes"),
-                    "traffic_detail": pmc_traffic(dom), "alg_is_bound": True,
-                    "alg_bytes_per_launch": int(alg[dom]), "avg_launch_us": round(dur_us[dom], 2),
-                    "regime": ("table %.1f MB is L2/Infinity-Cache resident: algorithmic rate is cache bandwidth and may exceed the HBM peak"
-                               % table_mb) if table_mb < 200 else "table %.0f MB exceeds the Infinity Cache: HBM-bound" % table_mb}
-
-    # ---- the same step with the LDS-staged gather kernels (the form SURVEY 8d prices against the HBM roofline), same
-    # process, same synthetic batches: images/s and the algorithmic-byte rate of its dominant FT kernel
-    # ---- bucketed workload: the same step on plain randn images (every sample lands in ONE layer stack), same process
-    single_bucket = None
-    if world == 1 and args.spread and cfg.get("buckets", 1) > 1 and args.density is None:
-        torch.manual_seed(0)
-        model_s = nnue.NNUE(nnue.GridFeatureSet(cfg["grid"], cfg["fps"]), cfg["l1"], cfg["l2"], cfg["l3"], num_classes=cfg["classes"],
-                            input_size=cfg["image"], num_ls_buckets=cfg["buckets"], clip_activations=cfg.get("clip")).to(dev)
-        ts = NnueTrainer(model_s, B, (cfg["image"], cfg["image"]), group=None, use_graph=not args.no_graph, input_slots=SLOTS, **OPT)
-        gs = torch.Generator().manual_seed(1234)
-        for images, labels in ts.inputs:
-            images.copy_(torch.randn(B, 3, cfg["image"], cfg["image"], generator=gs))
-            labels.copy_(torch.randint(0, cfg["classes"], (B,), generator=gs))
-        set_up(ts)
-        run_steps(ts, max(5, min(args.warmup, 30)))
+            for i in range(3):
+                trainer.step(slot=i % SLOTS, timers={k: [] for k in names})  # settle into eager mode
         torch.cuda.synchronize(dev)
-        ts0 = time.perf_counter()
-        run_steps(ts, args.steps)
+        t1 = time.perf_counter()
+        if group_fused:
+            for i0 in range(0, isteps, S):
+                trainer.step_many(group(i0), timers=timers)
+        else:
+            for i in range(isteps):
+                trainer.step(slot=i % SLOTS, timers=timers)
         torch.cuda.synchronize(dev)
-        s_elapsed = time.perf_counter() - ts0
-        single_bucket = {"images_per_sec": round(B * args.steps / s_elapsed, 1), "ms_per_step": round(s_elapsed * 1e3 / args.steps, 4),
-                         "samples_per_bucket_last_batch": torch.bincount(ts.bucket_plan.bucket.long(), minlength=ts.K).tolist()}
-        del ts, model_s
+        eager_ms = (time.perf_counter() - t1) * 1e3 / isteps
+        dur_us = {}
+        for k, pairs in timers.items():
+            # an entry point may be called more than once per step (stages / phases): report its time per step
+            dur_us[k] = sum(a.elapsed_time(b) * 1e3 for a, b in pairs) / isteps if pairs else 0.0
+        if group_fused:  # these run once per group / S-1 times per group: report them per launch
+            for k in (upd_fwd, f"{ftp}_backward_weight_update", fwd_entry):
+                if timers[k]:
+                    dur_us[k] = sum(a.elapsed_time(b) * 1e3 for a, b in timers[k]) / len(timers[k])
 
-    gather = None
-    if world == 1 and trainer.ft_path == "mfma" and not args.no_gather_compare and os.environ.get("NNUE_FT_PATH", "auto") == "auto":
-        os.environ["NNUE_FT_PATH"] = "bits"
-        try:
+        row = cfg["l1"] * 4  # bytes of one gathered / accumulated table row
+        alg = {  # algorithmic bytes per launch: fwd (n+1), value grad (n+1), weight grad n rows per image
+            f"{ftp}_forward": (n_mean + 1) * row * B,
+            val_entry: (n_mean + 1) * row * B,
+            f"{ftp}_backward_weight": n_mean * row * B,
+        }
+        if merged:
+            alg = {f"{ftp}_forward": alg[f"{ftp}_forward"], f"{ftp}_backward": alg[val_entry] + alg[f"{ftp}_backward_weight"]}
+        if fwd_entry != f"{ftp}_forward":
+            alg[fwd_entry] = alg.pop(f"{ftp}_forward")
+        if merged and bwd_entry != f"{ftp}_backward":
+            alg[bwd_entry] = alg.pop(f"{ftp}_backward")
+        if fused_update:  # value gradient as its own launch; the weight gradient is formed inside the update product
+            alg = {fwd_entry: (n_mean + 1) * row * B, val_entry: (n_mean + 1) * row * B,
+                   f"{ftp}_backward_weight_update": n_mean * row * B * (world if factor_exchange else 1)}
+            if group_fused:  # + the next forward's gathered rows
+                alg[upd_fwd] = n_mean * row * B + (n_mean + 1) * row * B
+        kernels = {k: {"avg_us": round(dur_us[k], 2), **({"alg_GBps": round(alg[k] / dur_us[k] * 1e-3, 1)} if k in alg and dur_us[k] > 0 else {})}
+                   for k in names}
+        KERNEL_OF = {  # C entry point -> (kernel name prefix, substring) in rocprof / PMC summaries
+            "nnue_ftm_forward": ("ftm_gemm", "FwdEpi"), "nnue_ftm_forward_grouping": ("ftm_gemm", "FwdEpi"), "nnue_ftm_forward_l1": ("ftm_forward_l1", ""),
+            "nnue_ftm_backward": ("ftm_backward", ""), "nnue_ftm_backward_bucketed": ("ftm_backward", ""),
+            "nnue_ftm_backward_weight": ("ftm_gemm", "BwwEpi"), "nnue_ftm_backward_values": ("ftm_gemm", "ValEpi"), "nnue_ftm_backward_values_ws": ("ftm_gemm", "ValEpi"),
+            "nnue_ftm_backward_weight_update": ("ftm_gemm", "BwwSgdEpi"), "nnue_ftm_backward_weight_update_forward": ("ftm_update_forward_kernel", ""),
+            "nnue_ftb_forward": ("ftb_gather_kernel", ", 0,"), "nnue_ftb_backward_weight": ("ftb_gather_kernel", ", 1,"),
+            "nnue_ftb_backward_values": ("ftb_values_kernel", ""), "nnue_ft_forward": ("ft_forward_wide", ""),
+            "nnue_ft_backward_weight": ("ft_backward_weight_wide", ""), "nnue_ft_backward_values": ("ft_backward_values_wide", "")}
+
+        def match_kernel(entry, name):
+            want = KERNEL_OF.get(entry)
+            if not want:
+                return False
+            name = name.replace("(anonymous namespace)::", "").replace("void ", "")
+            if want[1] == "BwwEpi" and "BwwSgdEpi" in name:
+                return False
+            return name.startswith(want[0]) and want[1] in name
+
+        def pmc_traffic(entry):
+            """HBM-side bytes per launch of the kernel behind a C entry point, from the committed rocprofv3 --pmc passes
+            (profiles/*pmc_traffic.json, FETCH_SIZE doubled per the gfx950 correction + WRITE_SIZE; separate passes per
+            counter group).  Counters cannot be read inside this process, so workloads without a committed pass report null."""
+            files = sorted((ROOT / "profiles").glob("*pmc_traffic.json"))
+            if not files:
+                return None
+            data = json.loads(files[-1].read_text())
+            kernels = data.get("workloads", {}).get(args.workload.replace("c3k1", "c3")) or (data.get("kernels") if args.workload == "c2" else None)
+            if not kernels:
+                return None
+            for name, v in kernels.items():
+                if match_kernel(entry, name):
+                    return {"bytes": v["hbm_bytes_corrected"], "l2_hit_rate": v["l2_hit_rate"], "kernel": name,
+                            "source": f"profiles/{files[-1].name} (committed counter passes of the eager step; not collected in this run)"}
+            return None
+
+        def rocprof_avg_us(entry):
+            """Average duration of that kernel in the latest committed `rocprofv3 --kernel-trace --stats` summary of this
+            workload's bench command (profiles/*kernel_stats_<workload>.csv)."""
+            files = sorted((ROOT / "profiles").glob(f"*kernel_stats_{args.workload.replace('c3k1', 'c3')}.csv"))
+            if not files:
+                return None
+            import csv
+            with open(files[-1]) as fh:
+                for rec in csv.DictReader(fh):
+                    if match_kernel(entry, rec["Name"]) and int(rec["Calls"]) >= 10:
+                        return {"us": round(float(rec["AverageNs"]) / 1e3, 2), "source": f"profiles/{files[-1].name}"}
+            return None
+
+        dom = max(alg, key=lambda k: dur_us[k])
+        table_mb = model.input.weight.numel() * 4 / 1e6
+        alg_rate = alg[dom] / (dur_us[dom] * 1e-6) / 1e9 if dur_us[dom] > 0 else 0.0
+        if trainer.ft_path == "mfma":
+            # Products over the whole map (active and inactive positions).  Each product is priced on the unit it runs on
+            # (nnue_ftm_uses_bf16): the f32-input MFMA (157.3 TF) or, for the two products whose A operand is the binary map,
+            # three bf16 MFMAs per logical product (2.5 PF dense; 3x the flops as matrix work).  Beside it the compulsory HBM
+            # bytes of the launch; the bound reported is whichever ideal time is longer.
+            from nnue_hip import lib as _lib
+            direct = min(trainer.F - 1, trainer.P)
+            L1, L2, F, P = cfg["l1"], cfg["l2"], trainer.F, trainer.P
+            uses = lambda which: bool(_lib.load().nnue_ftm_uses_bf16(which, B, F, P, L1))  # noqa: E731
+            f_fwd, f_w, f_v, f_l1 = 2.0 * B * direct * L1, 2.0 * B * direct * L1, 2.0 * B * P * L1, 2.0 * B * L1 * L2
+            tbl, mp, act = direct * L1 * 4.0, float(B * P), B * L1 * 4.0
+            work = {  # entry -> ([(unit, useful flops)], compulsory bytes)
+                f"{ftp}_forward": ([("bf16" if uses(0) else "f32", f_fwd)], tbl + mp + act),
+                f"{ftp}_forward_grouping": ([("bf16" if uses(0) else "f32", f_fwd)], tbl + mp + act),
+                f"{ftp}_forward_l1": ([("bf16" if uses(0) else "f32", f_fwd), ("f32", f_l1)], tbl + mp + act + (L1 // 64) * B * L2 * 4.0),
+                f"{ftp}_backward_weight": ([("bf16" if uses(1) else "f32", f_w)], mp + act + tbl),
+                val_entry: ([("bf16x6" if uses(4) else "f32", f_v)], act + F * L1 * 4.0 + mp + B * P * 4.0),
+                # (under the factor exchange the product contracts the GLOBAL batch: world x the flops, map and d_ft rows)
+                f"{ftp}_backward_weight_update": ([("bf16", f_w * (world if factor_exchange else 1))],
+                                                  (mp + act) * (world if factor_exchange else 1) + 2 * tbl + (2 * tbl if OPT["momentum"] else 0)),
+            }
+            # the update of step t + the forward of step t+1 in one pass: both products, the table and its momentum read and written
+            # once, both maps (the forward's own read of the table is what the fusion removes)
+            work[upd_fwd] = ([("bf16", f_w), ("bf16", f_fwd)], 2 * mp + 2 * act + 2 * tbl + (2 * tbl if OPT["momentum"] else 0))
+            bw = [("bf16" if uses(2) else "f32", f_w), ("bf16x6" if uses(5) else "f32", f_v)] + ([("f32", f_l1)] if getattr(trainer, "ride_dw1", False) else [])
+            work[f"{ftp}_backward"] = (bw, 2 * mp + act + F * L1 * 4.0 + tbl + B * P * 4.0)
+            work[f"{ftp}_backward_bucketed"] = work[f"{ftp}_backward"]
+            PEAK = {"f32": MFMA_F32_PEAK_TFLOPS, "bf16": MFMA_BF16_PEAK_TFLOPS, "bf16x6": MFMA_BF16_PEAK_TFLOPS}
+            PASSES = {"f32": 1, "bf16": 3, "bf16x6": 6}  # bf16 MFMAs per logical product: exact split of one operand / six plane products of two
+            units, comp_bytes = work[dom]
+            useful = sum(f for _, f in units)
+            t_mfma = sum(f * PASSES[u] / (PEAK[u] * 1e12) for u, f in units)  # seconds at the units' peaks
+            t_hbm = comp_bytes / (HBM_PEAK_GBS * 1e9)
+            dur = dur_us[dom] * 1e-6
+            rp = rocprof_avg_us(dom)
+            common = {"kernel": dom, "traffic": (pmc_traffic(dom) or {}).get("bytes"), "traffic_detail": pmc_traffic(dom),
+                      "compulsory_bytes": int(comp_bytes), "flops_per_launch": int(useful),
+                      "matrix_work": [{"unit": u, "useful_flops": int(f), "peak_TFLOPs": PEAK[u], "mfma_flops": int(f * PASSES[u])}
+                                      for u, f in units],
+                      "ideal_us": {"mfma": round(t_mfma * 1e6, 2), "hbm": round(t_hbm * 1e6, 2)},
+                      "avg_launch_us": round(dur_us[dom], 2), "rocprof_avg_us": rp["us"] if rp else None, "rocprof_source": rp["source"] if rp else None,
+                      "alg_bytes_per_launch": int(alg[dom]), "alg_GBps": round(alg_rate, 1),
+                      # SURVEY 8d's "one table row per gathered id" prices a gather; a product re-uses a staged row across the
+                      # samples of a tile, so for this path the algorithmic-byte rate is NOT a lower bound on traffic (it exceeds
+                      # the HBM peak while the table is cache-resident) -- the bound is the one reported in bound/peak/frac
+                      "alg_is_bound": False}
+            if t_hbm >= t_mfma:
+                rate = comp_bytes / dur / 1e9 if dur > 0 else 0.0
+                roofline = {"bound": "hbm", "achieved": round(rate, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(rate / HBM_PEAK_GBS, 4),
+                            # the same fraction with the kernel's average duration in the committed rocprofv3 summary instead of this run's events
+                            "frac_rocprof": round(comp_bytes / (rp["us"] * 1e-6) / 1e9 / HBM_PEAK_GBS, 4) if rp else None, **common,
+                            "regime": "compulsory bytes of the launch (table %.1f MB streamed once, parameters and momentum read and written where the "
+                                      "update is fused) / HIP-event duration; the matrix work of the launch would take %.1f us at its units' peaks"
+                                      % (table_mb, t_mfma * 1e6)}
+            else:
+                blended = useful / t_mfma / 1e12  # the peak this launch could reach given which unit each product runs on
+                achieved = useful / dur / 1e12 if dur > 0 else 0.0
+                roofline = {"bound": "mfma", "achieved": round(achieved, 2), "peak": round(blended, 1), "unit": "TFLOP/s",
+                            "frac": round(achieved / blended, 4),
+                            "frac_rocprof": round(useful / (rp["us"] * 1e-6) / 1e12 / blended, 4) if rp else None,
+                            "frac_of_f32_mfma_peak": round(achieved / MFMA_F32_PEAK_TFLOPS, 4),  # round 1's pricing of the same launch, for comparison
+                            **common,
+                            "regime": "useful flops of the products in the launch (2 M N K over the whole map) / HIP-event duration, against the "
+                                      "peak of the unit each product runs on (f32-input MFMA 157.3 TF; bf16 MFMA 2.5 PF at three MFMAs per "
+                                      "product for the exact split of one operand, six for the plane products of two f32 operands); table %.1f MB" % table_mb}
+        else:
+            roofline = {"bound": "hbm", "kernel": dom, "achieved": round(alg_rate, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": round(alg_rate / HBM_PEAK_GBS, 4), "traffic": (pmc_traffic(dom) or {}).get("bytes"),
+                        "traffic_detail": pmc_traffic(dom), "alg_is_bound": True,
+                        "alg_bytes_per_launch": int(alg[dom]), "avg_launch_us": round(dur_us[dom], 2),
+                        "regime": ("table %.1f MB is L2/Infinity-Cache resident: algorithmic rate is cache bandwidth and may exceed the HBM peak"
+                                   % table_mb) if table_mb < 200 else "table %.0f MB exceeds the Infinity Cache: HBM-bound" % table_mb}
+
+        # ---- the same step with the LDS-staged gather kernels (the form SURVEY 8d prices against the HBM roofline), same
+        # process, same synthetic batches: images/s and the algorithmic-byte rate of its dominant FT kernel
+        # ---- bucketed workload: the same step on plain randn images (every sample lands in ONE layer stack), same process
+        single_bucket = None
+        if world == 1 and args.spread and cfg.get("buckets", 1) > 1 and args.density is None:
             torch.manual_seed(0)
-            model_g = nnue.NNUE(nnue.GridFeatureSet(cfg["grid"], cfg["fps"]), cfg["l1"], cfg["l2"], cfg["l3"],
-                                num_classes=cfg["classes"], input_size=cfg["image"], num_ls_buckets=cfg.get("buckets", 1),
-                                clip_activations=cfg.get("clip")).to(dev)
-            if args.spread:
-                with torch.no_grad():
-                    model_g.conv.weight.abs_()
-            if args.density is not None:
-                with torch.no_grad():
-                    model_g.visual_threshold.copy_(model.visual_threshold)
-            tg = NnueTrainer(model_g, B, (cfg["image"], cfg["image"]), group=None, use_graph=not args.no_graph, input_slots=SLOTS, **OPT)
-            if args.density is not None:
-                tg.lr = 0.0
-            if tg.ft_path == "bits":
-                for (gi, gl), (si, sl) in zip(tg.inputs, trainer.inputs):
-                    gi.copy_(si)
-                    gl.copy_(sl)
-                gsteps = max(10, min(args.steps, 100))
-                set_up(tg)
-                run_steps(tg, max(5, min(args.warmup, 20)))
-                torch.cuda.synchronize(dev)
-                tg0 = time.perf_counter()
-                run_steps(tg, gsteps)
-                torch.cuda.synchronize(dev)
-                g_elapsed = time.perf_counter() - tg0
-                gn_mean, _ = tg.active_stats()
-                gnames = ["nnue_ftb_forward", "nnue_ftb_backward_weight", "nnue_ftb_backward_values"]
-                gt = {k: [] for k in gnames}
-                for i in range(3):
-                    tg.step(slot=i % SLOTS, timers={k: [] for k in gnames})
-                gi_steps = max(5, min(30, gsteps))
-                for i in range(gi_steps):
-                    tg.step(slot=i % SLOTS, timers=gt)
-                torch.cuda.synchronize(dev)
-                gdur = {k: sum(a.elapsed_time(b) * 1e3 for a, b in v) / gi_steps for k, v in gt.items()}
-                galg = {"nnue_ftb_forward": (gn_mean + 1) * row * B, "nnue_ftb_backward_values": (gn_mean + 1) * row * B,
-                        "nnue_ftb_backward_weight": gn_mean * row * B}
-                gdom = max(galg, key=lambda k: gdur[k])
-                grate = galg[gdom] / (gdur[gdom] * 1e-6) / 1e9 if gdur[gdom] > 0 else 0.0
-                old = sorted((ROOT / "profiles").glob("r01g_pmc_traffic.json"))
-                gtraffic = None
-                if old and args.workload == "c2":
-                    kk = json.loads(old[-1].read_text())["kernels"]
-                    pat = {"nnue_ftb_forward": ("ftb_gather_kernel", ", 0,"), "nnue_ftb_backward_weight": ("ftb_gather_kernel", ", 1,"),
-                           "nnue_ftb_backward_values": ("ftb_values_kernel", "")}[gdom]
-                    for name, v in kk.items():
-                        if name.startswith(pat[0]) and pat[1] in name:
-                            gtraffic = v["hbm_bytes_corrected"]
-                gather = {"path": "NNUE_FT_PATH=bits (LDS-staged gather kernels, ftb_kernels.hip)",
-                          "images_per_sec": round(B * gsteps / g_elapsed, 1), "ms_per_step": round(g_elapsed * 1e3 / gsteps, 4),
-                          "roofline": {"bound": "hbm", "kernel": gdom, "achieved": round(grate, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                       "frac": round(grate / HBM_PEAK_GBS, 4), "traffic": gtraffic,
-                                       "alg_bytes_per_launch": int(galg[gdom]), "avg_launch_us": round(gdur[gdom], 2),
-                                       "regime": ("table %.1f MB is L2/Infinity-Cache resident: algorithmic rate is cache bandwidth and may "
-                                                  "exceed the HBM peak" % table_mb) if table_mb < 200 else
-                                                 "table %.0f MB exceeds the Infinity Cache: HBM-bound" % table_mb},
-                          "kernels_us": {k: round(v, 2) for k, v in gdur.items()}}
-            del tg, model_g
-        finally:
-            os.environ["NNUE_FT_PATH"] = "auto"
+            model_s = nnue.NNUE(nnue.GridFeatureSet(cfg["grid"], cfg["fps"]), cfg["l1"], cfg["l2"], cfg["l3"], num_classes=cfg["classes"],
+                                input_size=cfg["image"], num_ls_buckets=cfg["buckets"], clip_activations=cfg.get("clip")).to(dev)
+            ts = NnueTrainer(model_s, B, (cfg["image"], cfg["image"]), group=None, use_graph=not args.no_graph, input_slots=SLOTS, **OPT)
+            gs = torch.Generator().manual_seed(1234)
+            for images, labels in ts.inputs:
+                images.copy_(torch.randn(B, 3, cfg["image"], cfg["image"], generator=gs))
+                labels.copy_(torch.randint(0, cfg["classes"], (B,), generator=gs))
+            set_up(ts)
+            run_steps(ts, max(5, min(args.warmup, 30)))
+            torch.cuda.synchronize(dev)
+            ts0 = time.perf_counter()
+            run_steps(ts, args.steps)
+            torch.cuda.synchronize(dev)
+            s_elapsed = time.perf_counter() - ts0
+            single_bucket = {"images_per_sec": round(B * args.steps / s_elapsed, 1), "ms_per_step": round(s_elapsed * 1e3 / args.steps, 4),
+                             "samples_per_bucket_last_batch": torch.bincount(ts.bucket_plan.bucket.long(), minlength=ts.K).tolist()}
+            del ts, model_s
+
+        gather = None
+        if world == 1 and trainer.ft_path == "mfma" and not args.no_gather_compare and os.environ.get("NNUE_FT_PATH", "auto") == "auto":
+            os.environ["NNUE_FT_PATH"] = "bits"
+            try:
+                torch.manual_seed(0)
+                model_g = nnue.NNUE(nnue.GridFeatureSet(cfg["grid"], cfg["fps"]), cfg["l1"], cfg["l2"], cfg["l3"],
+                                    num_classes=cfg["classes"], input_size=cfg["image"], num_ls_buckets=cfg.get("buckets", 1),
+                                    clip_activations=cfg.get("clip")).to(dev)
+                if args.spread:
+                    with torch.no_grad():
+                        model_g.conv.weight.abs_()
+                if args.density is not None:
+                    with torch.no_grad():
+                        model_g.visual_threshold.copy_(model.visual_threshold)
+                tg = NnueTrainer(model_g, B, (cfg["image"], cfg["image"]), group=None, use_graph=not args.no_graph, input_slots=SLOTS, **OPT)
+                if args.density is not None:
+                    tg.lr = 0.0
+                if tg.ft_path == "bits":
+                    for (gi, gl), (si, sl) in zip(tg.inputs, trainer.inputs):
+                        gi.copy_(si)
+                        gl.copy_(sl)
+                    gsteps = max(10, min(args.steps, 100))
+                    set_up(tg)
+                    run_steps(tg, max(5, min(args.warmup, 20)))
+                    torch.cuda.synchronize(dev)
+                    tg0 = time.perf_counter()
+                    run_steps(tg, gsteps)
+                    torch.cuda.synchronize(dev)
+                    g_elapsed = time.perf_counter() - tg0
+                    gn_mean, _ = tg.active_stats()
+                    gnames = ["nnue_ftb_forward", "nnue_ftb_backward_weight", "nnue_ftb_backward_values"]
+                    gt = {k: [] for k in gnames}
+                    for i in range(3):
+                        tg.step(slot=i % SLOTS, timers={k: [] for k in gnames})
+                    gi_steps = max(5, min(30, gsteps))
+                    for i in range(gi_steps):
+                        tg.step(slot=i % SLOTS, timers=gt)
+                    torch.cuda.synchronize(dev)
+                    gdur = {k: sum(a.elapsed_time(b) * 1e3 for a, b in v) / gi_steps for k, v in gt.items()}
+                    galg = {"nnue_ftb_forward": (gn_mean + 1) * row * B, "nnue_ftb_backward_values": (gn_mean + 1) * row * B,
+                            "nnue_ftb_backward_weight": gn_mean * row * B}
+                    gdom = max(galg, key=lambda k: gdur[k])
+                    grate = galg[gdom] / (gdur[gdom] * 1e-6) / 1e9 if gdur[gdom] > 0 else 0.0
+                    old = sorted((ROOT / "profiles").glob("r01g_pmc_traffic.json"))
+                    gtraffic = None
+                    if old and args.workload == "c2":
+                        kk = json.loads(old[-1].read_text())["kernels"]
+                        pat = {"nnue_ftb_forward": ("ftb_gather_kernel", ", 0,"), "nnue_ftb_backward_weight": ("ftb_gather_kernel", ", 1,"),
+                               "nnue_ftb_backward_values": ("ftb_values_kernel", "")}[gdom]
+                        for name, v in kk.items():
+                            if name.startswith(pat[0]) and pat[1] in name:
+                                gtraffic = v["hbm_bytes_corrected"]
+                    gather = {"path": "NNUE_FT_PATH=bits (LDS-staged gather kernels, ftb_kernels.hip)",
+                              "images_per_sec": round(B * gsteps / g_elapsed, 1), "ms_per_step": round(g_elapsed * 1e3 / gsteps, 4),
+                              "roofline": {"bound": "hbm", "kernel": gdom, "achieved": round(grate, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                           "frac": round(grate / HBM_PEAK_GBS, 4), "traffic": gtraffic,
+                                           "alg_bytes_per_launch": int(galg[gdom]), "avg_launch_us": round(gdur[gdom], 2),
+                                           "regime": ("table %.1f MB is L2/Infinity-Cache resident: algorithmic rate is cache bandwidth and may "
+                                                      "exceed the HBM peak" % table_mb) if table_mb < 200 else
+                                                     "table %.0f MB exceeds the Infinity Cache: HBM-bound" % table_mb},
+                              "kernels_us": {k: round(v, 2) for k, v in gdur.items()}}
+                del tg, model_g
+            finally:
+                os.environ["NNUE_FT_PATH"] = "auto"
 
     if rank == 0:
         out = {
@@ -584,17 +629,19 @@ def main():
                        "global_batch": B * world, "parallelism": f"dp{world}", "launch": "eager" if args.no_graph else "hipGraph", "steps_per_graph": S,
                        "mean_active_features": round(n_mean, 1), "max_active_features": n_max,
                        "active_density": round(n_mean / ((cfg["image"] - 1) // max(1, (cfg["image"] - 1) // (cfg["grid"] - 1)) + 1) ** 2 / cfg["fps"], 4),
-                       "eager_ms_per_step_instrumented": round(eager_ms, 4), "loss_after": round(loss_after, 4),
+                       **({"eager_ms_per_step_instrumented": round(eager_ms, 4)} if eager_ms is not None else {}),
+                       "loss_after": round(loss_after, 4),
                        **({"num_ls_buckets": trainer.K, "samples_per_bucket_last_batch": bucket_hist} if bucket_hist is not None else {}),
                        # the same 8-stack model on plain randn images, where one stack takes the whole batch
                        **({"single_bucket_images_per_sec": single_bucket["images_per_sec"], "single_bucket": single_bucket}
                           if single_bucket is not None else {})},
-            "roofline": roofline,
-            "kernels": kernels,
         }
+        if args.full:
+            out["roofline"] = roofline
+            out["kernels"] = kernels
         if gather is not None:
             out["gather_path"] = gather
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg, args.cpu_seconds)
         sys.stdout.flush()
         os.dup2(real_stdout, 1)

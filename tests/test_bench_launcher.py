@@ -21,6 +21,12 @@ def test_bench_starts_its_own_ranks():
     assert rec["n_gpus"] == 2 and rec["n_ranks"] == 2 and rec["steps"] == 3 and rec["allreduce_ok"]
 
 
+def test_bench_refuses_fewer_than_one_timed_step():
+    out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "0"], stdout=subprocess.PIPE,
+                         stderr=subprocess.PIPE, text=True, timeout=120)
+    assert out.returncode != 0 and "--steps must be at least 1" in out.stderr
+
+
 def test_bench_refuses_a_world_size_mismatch():
     env = dict(os.environ, WORLD_SIZE="3", RANK="0", LOCAL_RANK="0")
     out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2"], env=env, stdout=subprocess.PIPE,

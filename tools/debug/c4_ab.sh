@@ -7,7 +7,7 @@ R=$PWD; mkdir -p $O; cd /tmp; export TMPDIR=/tmp
 for spec in "$@"; do
   set -- $spec; n=$1; shift
   ( for kv in "$@"; do export "$kv"; done
-    rocprofv3 --kernel-trace --stats --output-format csv -d $O/$n -- python3 $R/bench.py --workload $W --steps 50 --warmup 10 --no-gather-compare --no-cpu-baseline > $O/$n.json 2> $O/$n.err || echo "$n failed: $(tail -3 $O/$n.err)" )
+    rocprofv3 --kernel-trace --stats --output-format csv -d $O/$n -- python3 $R/bench.py --workload $W --steps 50 --warmup 10 --full --no-gather-compare --no-cpu-baseline > $O/$n.json 2> $O/$n.err || echo "$n failed: $(tail -3 $O/$n.err)" )
   python3 - $O/$n $n $O/$n.json <<'PY'
 import csv, glob, json, sys
 try:

@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage: quick_stats.sh OUTDIR workload...   -- rocprofv3 kernel stats of bench.py per workload (top kernels printed)
 O=$PWD/$1; shift; R=$PWD; mkdir -p $O
-B="--steps 200 --warmup 16 --no-cpu-baseline --no-gather-compare"
+B="--steps 200 --warmup 16 --full --no-cpu-baseline --no-gather-compare"
 cd /tmp; export TMPDIR=/tmp
 for w in "$@"; do
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_$w -- python3 $R/bench.py --workload $w $B > $O/$w.json 2>$O/err_$w || exit 1
