@@ -40,7 +40,7 @@
 extern "C" {
 #endif
 
-#define NNUE_HIP_ABI_VERSION 30
+#define NNUE_HIP_ABI_VERSION 31
 
 #define NNUE_OK 0
 #define NNUE_E_ARG (-1)     /* null pointer, non-positive size, bad alignment */
@@ -550,6 +550,25 @@ int64_t nnue_engine_scratch(const nnue_engine_model* m, int B);
 int nnue_engine_evaluate_logits(const nnue_engine_model* m, const float* images, int B, int H, int W,
                                 float* logits, float* density, void* scratch, int64_t scratch_bytes,
                                 nnue_stream_t stream);
+
+/* NNUEEvaluator::evaluate_incremental (engine/src/nnue_engine.cpp:739-786) for S independent streams at once (video: one
+ * stream per camera, one call per frame), returning the multiclass logits of evaluate_logits as its consumer reads them
+ * (evaluate.py:143-176).  Every stream keeps its wrapped int16 accumulator and its last active-feature set in `state`; a
+ * step adds the table rows of the features that turned on and subtracts those that turned off
+ * (FeatureTransformer::update_accumulator, nnue_engine.cpp:257-267), or refreshes from the bias (refresh_accumulator,
+ * :806-816) when the stream is not valid or when that reads fewer rows.  The accumulator wraps mod 2^16, so every step's
+ * logits and density are bit-identical to nnue_engine_evaluate_logits on the same frame, whatever the history.
+ * Exactly one input: images (S flat buffers of 3*H*W floats, as nnue_engine_evaluate_logits; H x W may change between
+ * steps; scratch >= nnue_engine_scratch(m, S) bytes) or active (uint8 [S][num_features], non-zero = on, every id counts;
+ * scratch unused).  Outputs: logits [S][classes], density [S], changed [S] = features that differ from the stream's
+ * previous set (all active features for a stream that was not valid).
+ * state: 16-byte aligned, >= nnue_engine_stream_state_bytes(m, S) bytes; zero-filled = every stream fresh.  Its first S
+ * int32 are the valid flags: writing 0 to one makes that stream refresh on its next step (the step sets it to 1).
+ * NNUE_E_SCRATCH for too small a state or scratch; NNUE_E_SHAPE where num_features needs more LDS than a workgroup has. */
+int64_t nnue_engine_stream_state_bytes(const nnue_engine_model* m, int S);
+int nnue_engine_stream_step(const nnue_engine_model* m, const float* images, const uint8_t* active, int S, int H, int W,
+                            void* state, int64_t state_bytes, float* logits, float* density, int32_t* changed,
+                            void* scratch, int64_t scratch_bytes, nnue_stream_t stream);
 
 /* Data parallel for bandwidth-sized tables ("exchange only touched rows"; the reference itself is single-device,
  * train.py:263).  The table's weight gradient of the GLOBAL batch is d_W = A^T D with A the {0,1} map [world*B][P] and

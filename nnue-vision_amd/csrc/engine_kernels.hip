@@ -42,58 +42,14 @@ __global__ __launch_bounds__(256) void engine_conv_kernel(const float* __restric
 
 __device__ __forceinline__ int32_t clamp_i(int32_t v, int32_t lo, int32_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
-// One workgroup per image: feature grid + FeatureTransformer (int16 wrap-around) + clipped ReLU + forward_multiclass
-// (nnue_engine.h:236-283, simd_scalar.cpp:78-96, nnue_engine.cpp:726-729, :480-539).
-// dynamic LDS: ft [L1] i32 | pair [L1] i32 | h1 [L2] i32 | h2 [L3] i32 | counts [4] i32
-__global__ __launch_bounds__(256) void engine_stack_kernel(const int8_t* __restrict__ conv, float threshold, int F, int oc,
-                                                           const int16_t* __restrict__ ft_w, const int32_t* __restrict__ ft_b,
-                                                           int quantized_one, const int8_t* __restrict__ l1_w,
-                                                           const int32_t* __restrict__ l1_b, float l1_scale,
-                                                           const int8_t* __restrict__ l2_w, const int32_t* __restrict__ l2_b,
-                                                           int l2_scale, const int8_t* __restrict__ out_w,
-                                                           const int32_t* __restrict__ out_b, float out_scale, int L1, int L2,
-                                                           int L3, int C, float* __restrict__ logits, float* __restrict__ density) {
-  extern __shared__ int32_t lds[];
-  int32_t* ft = lds;
-  int32_t* pair = ft + L1;
-  int32_t* h1 = pair + L1;
-  int32_t* h2 = h1 + L2;
-  int32_t* counts = h2 + L3;
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int8_t* __restrict__ cv = conv + (size_t)b * F;
-
-  // active features, ascending: every wave forms the same ballots and adds the rows to its own columns
-  int32_t acc[kMaxColsPerThread];
-#pragma unroll
-  for (int j = 0; j < kMaxColsPerThread; ++j) acc[j] = 0;
-  int count = 0;
-  for (int f0 = 0; f0 < F; f0 += 64) {
-    const int f = f0 + lane;
-    const bool on = f < F && (float)cv[f] > threshold && (f % oc) < 64;  // 64 channels per cell are bit-packed
-    unsigned long long mask = __ballot(on);
-    count += __popcll(mask);
-    while (mask) {
-      const int row = f0 + __builtin_ctzll(mask);
-      mask &= mask - 1;
-      const int16_t* __restrict__ wr = ft_w + (size_t)row * L1;
-#pragma unroll
-      for (int j = 0; j < kMaxColsPerThread; ++j) {
-        const int col = tid + 256 * j;
-        if (col < L1) acc[j] += (int32_t)wr[col];
-      }
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < kMaxColsPerThread; ++j) {
-    const int col = tid + 256 * j;
-    if (col < L1) {
-      const int16_t v = (int16_t)((int32_t)(int16_t)ft_b[col] + acc[j]);  // int16 accumulator wraps
-      ft[col] = clamp_i((int32_t)v, 0, quantized_one);
-    }
-  }
-  if (tid == 0) density[b] = (float)count / (float)F;
-  __syncthreads();
-
+// LayerStack::forward_multiclass (nnue_engine.cpp:480-539) of one image, from the clipped accumulator ft [L1] (LDS) to its
+// logits row; shared by the batched and the per-stream kernels.  The caller synchronises after writing ft.
+__device__ __forceinline__ void engine_tail(const int32_t* ft, int32_t* pair, int32_t* h1, int32_t* h2,
+                                            const int8_t* __restrict__ l1_w, const int32_t* __restrict__ l1_b, float l1_scale,
+                                            const int8_t* __restrict__ l2_w, const int32_t* __restrict__ l2_b, int l2_scale,
+                                            const int8_t* __restrict__ out_w, const int32_t* __restrict__ out_b, float out_scale,
+                                            int L1, int L2, int L3, int C, float* __restrict__ logits_row) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   // pairwise: (a * b) / 128 clamped to [0, 127] | a clamped to [0, 127]
   const int half = L1 / 2;
   for (int i = tid; i < L1; i += 256) {
@@ -132,9 +88,207 @@ __global__ __launch_bounds__(256) void engine_stack_kernel(const int8_t* __restr
     const int8_t* __restrict__ wr = out_w + (size_t)c * L3;
     int32_t s = out_b[c];
     for (int j = 0; j < L3; ++j) s += h2[j] * (int32_t)wr[j];
-    logits[(size_t)b * C + c] = (float)s / out_scale;
+    logits_row[c] = (float)s / out_scale;
   }
+}
+
+// One workgroup per image: feature grid + FeatureTransformer (int16 wrap-around) + clipped ReLU + forward_multiclass
+// (nnue_engine.h:236-283, simd_scalar.cpp:78-96, nnue_engine.cpp:726-729, :480-539).
+// dynamic LDS: ft [L1] i32 | pair [L1] i32 | h1 [L2] i32 | h2 [L3] i32 | counts [4] i32
+__global__ __launch_bounds__(256) void engine_stack_kernel(const int8_t* __restrict__ conv, float threshold, int F, int oc,
+                                                           const int16_t* __restrict__ ft_w, const int32_t* __restrict__ ft_b,
+                                                           int quantized_one, const int8_t* __restrict__ l1_w,
+                                                           const int32_t* __restrict__ l1_b, float l1_scale,
+                                                           const int8_t* __restrict__ l2_w, const int32_t* __restrict__ l2_b,
+                                                           int l2_scale, const int8_t* __restrict__ out_w,
+                                                           const int32_t* __restrict__ out_b, float out_scale, int L1, int L2,
+                                                           int L3, int C, float* __restrict__ logits, float* __restrict__ density) {
+  extern __shared__ int32_t lds[];
+  int32_t* ft = lds;
+  int32_t* pair = ft + L1;
+  int32_t* h1 = pair + L1;
+  int32_t* h2 = h1 + L2;
+  int32_t* counts = h2 + L3;
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+  const int8_t* __restrict__ cv = conv + (size_t)b * F;
+
+  // active features, ascending: every wave forms the same ballots and adds the rows to its own columns
+  int32_t acc[kMaxColsPerThread];
+#pragma unroll
+  for (int j = 0; j < kMaxColsPerThread; ++j) acc[j] = 0;
+  int count = 0;
+  for (int f0 = 0; f0 < F; f0 += 64) {
+    const int f = f0 + lane;
+    const bool on = f < F && (float)cv[f] > threshold && (f % oc) < 64;  // 64 channels per cell are bit-packed
+    unsigned long long mask = __ballot(on);
+    count += __popcll(mask);
+    while (mask) {
+      const int row = f0 + __builtin_ctzll(mask);
+      mask &= mask - 1;
+      const int16_t* __restrict__ wr = ft_w + (size_t)row * L1;
+#pragma unroll
+      for (int j = 0; j < kMaxColsPerThread; ++j) {
+        const int col = tid + 256 * j;
+        if (col < L1) acc[j] += (int32_t)wr[col];
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < kMaxColsPerThread; ++j) {
+    const int col = tid + 256 * j;
+    if (col < L1) {
+      const int16_t v = (int16_t)((int32_t)(int16_t)ft_b[col] + acc[j]);  // int16 accumulator wraps
+      ft[col] = clamp_i((int32_t)v, 0, quantized_one);
+    }
+  }
+  if (tid == 0) density[b] = (float)count / (float)F;
+  __syncthreads();
+
+  engine_tail(ft, pair, h1, h2, l1_w, l1_b, l1_scale, l2_w, l2_b, l2_scale, out_w, out_b, out_scale, L1, L2, L3, C,
+              logits + (size_t)b * C);
   (void)counts;
+}
+
+
+// Per-stream state of nnue_engine_stream_step, one device buffer (offsets in bytes; W64 = ceil(F / 64)):
+//   valid  [S] i32  at 0              0 = refresh the stream from the bias on its next step (a zero-filled state is fresh)
+//   parity [S] i32  at 4 S            which of the two bit-word slots holds the stream's current feature set
+//   bits   [2][S][W64] u64            at align16(8 S): the active-feature sets, ping-pong
+//   acc    [S][L1] i16                after bits: the wrapped accumulator, bias included, BEFORE the clipped ReLU
+struct StreamLayout {
+  int64_t parity, bits, acc, total;
+};
+
+__host__ __device__ inline StreamLayout stream_layout(int64_t S, int64_t F, int64_t L1) {
+  StreamLayout l;
+  const int64_t w64 = (F + 63) / 64;
+  l.parity = 4 * S;
+  l.bits = (8 * S + 15) / 16 * 16;
+  l.acc = l.bits + 2 * S * w64 * 8;
+  l.total = (l.acc + 2 * S * L1 + 15) / 16 * 16;
+  return l;
+}
+
+// NNUEEvaluator::evaluate_incremental (nnue_engine.cpp:739-786) for S independent streams, one workgroup per stream: the new
+// feature set, the difference to the stream's previous one, and FeatureTransformer::update_accumulator (:257-267) on the
+// stored int16 accumulator -- or refresh_accumulator (:806-816) from the bias when the stream is not valid, or when the
+// difference holds more features than the new set (then a refresh reads fewer table rows).  Both give the same bits: the
+// accumulator is int16 and wraps, and addition mod 2^16 does not depend on the order or the history of the terms.
+// Then the clipped ReLU and engine_tail, as engine_stack_kernel.
+// kFeatures: the set is given as a uint8 map active [S][F] (non-zero = on, every id counts: the reference's entry that takes
+// feature indices applies no per-cell channel mask); otherwise it is formed from the conv bytes with engine_stack_kernel's
+// predicate.
+// Read/write hazard on the bit words: they ping-pong between two slots ([2][S][W64] + a per-stream parity that flips at the
+// end of the step).  Every wave may read the old words at any time during the step while the new ones are stored into the
+// other slot, so no barrier has to order those reads before the stores, and a launch never reads a word it writes.
+// dynamic LDS: ft [L1] i32 | pair [L1] i32 | h1 [L2] i32 | h2 [L3] i32 | counts [8] i32 | (8-byte aligned) new [W64] u64 |
+// old [W64] u64
+template <bool kFeatures>
+__global__ __launch_bounds__(256) void engine_stream_kernel(const int8_t* __restrict__ conv, const uint8_t* __restrict__ active,
+                                                            float threshold, int F, int oc, int S, const int16_t* __restrict__ ft_w,
+                                                            const int32_t* __restrict__ ft_b, int quantized_one,
+                                                            const int8_t* __restrict__ l1_w, const int32_t* __restrict__ l1_b,
+                                                            float l1_scale, const int8_t* __restrict__ l2_w,
+                                                            const int32_t* __restrict__ l2_b, int l2_scale,
+                                                            const int8_t* __restrict__ out_w, const int32_t* __restrict__ out_b,
+                                                            float out_scale, int L1, int L2, int L3, int C, uint8_t* __restrict__ state,
+                                                            float* __restrict__ logits, float* __restrict__ density,
+                                                            int32_t* __restrict__ changed) {
+  extern __shared__ int32_t lds[];
+  int32_t* ft = lds;
+  int32_t* pair = ft + L1;
+  int32_t* h1 = pair + L1;
+  int32_t* h2 = h1 + L2;
+  int32_t* counts = h2 + L3;  // [wave] new, [4 + wave] difference
+  const int W64 = (F + 63) / 64;
+  unsigned long long* new_s = reinterpret_cast<unsigned long long*>(lds + ((2 * L1 + L2 + L3 + 8 + 1) & ~1));
+  unsigned long long* old_s = new_s + W64;
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+
+  const StreamLayout lay = stream_layout(S, F, L1);
+  int32_t* __restrict__ valid = reinterpret_cast<int32_t*>(state);
+  int32_t* __restrict__ parity = reinterpret_cast<int32_t*>(state + lay.parity);
+  unsigned long long* __restrict__ bits = reinterpret_cast<unsigned long long*>(state + lay.bits);
+  int16_t* __restrict__ accs = reinterpret_cast<int16_t*>(state + lay.acc) + (size_t)b * L1;
+  const bool was_valid = valid[b] != 0;
+  const int par = parity[b] & 1;
+  const unsigned long long* __restrict__ old_w = bits + ((size_t)par * S + b) * W64;
+  unsigned long long* __restrict__ new_w = bits + ((size_t)(par ^ 1) * S + b) * W64;
+
+  // pass 1: wave w forms the ballots of chunks w, w + 4, ...: new set -> its slot and LDS, old set -> LDS, both popcounts
+  int n_new = 0, n_diff = 0;
+  for (int c = wave; c < W64; c += 4) {
+    const int f = c * 64 + lane;
+    bool on;
+    if constexpr (kFeatures) on = f < F && active[(size_t)b * F + f] != 0;
+    else on = f < F && (float)conv[(size_t)b * F + f] > threshold && (f % oc) < 64;  // 64 channels per cell are bit-packed
+    const unsigned long long m = __ballot(on);
+    const unsigned long long o = was_valid ? old_w[c] : 0ull;
+    n_new += __popcll(m);
+    n_diff += __popcll(m ^ o);
+    if (lane == 0) {
+      new_w[c] = m;
+      new_s[c] = m;
+      old_s[c] = o;
+    }
+  }
+  if (lane == 0) {
+    counts[wave] = n_new;
+    counts[4 + wave] = n_diff;
+  }
+  __syncthreads();
+  n_new = counts[0] + counts[1] + counts[2] + counts[3];
+  n_diff = counts[4] + counts[5] + counts[6] + counts[7];
+  const bool refresh = !was_valid || n_diff > n_new;
+
+  // pass 2: every wave walks the same words and updates its own columns in int32 registers seeded from the state or the bias
+  int32_t acc[kMaxColsPerThread];
+#pragma unroll
+  for (int j = 0; j < kMaxColsPerThread; ++j) {
+    const int col = tid + 256 * j;
+    acc[j] = col < L1 ? (refresh ? (int32_t)(int16_t)ft_b[col] : (int32_t)accs[col]) : 0;
+  }
+  for (int c = 0; c < W64; ++c) {
+    const unsigned long long m = new_s[c], o = refresh ? 0ull : old_s[c];
+    unsigned long long add = m & ~o, sub = o & ~m;
+    while (add) {
+      const int16_t* __restrict__ wr = ft_w + (size_t)(c * 64 + __builtin_ctzll(add)) * L1;
+      add &= add - 1;
+#pragma unroll
+      for (int j = 0; j < kMaxColsPerThread; ++j) {
+        const int col = tid + 256 * j;
+        if (col < L1) acc[j] += (int32_t)wr[col];
+      }
+    }
+    while (sub) {
+      const int16_t* __restrict__ wr = ft_w + (size_t)(c * 64 + __builtin_ctzll(sub)) * L1;
+      sub &= sub - 1;
+#pragma unroll
+      for (int j = 0; j < kMaxColsPerThread; ++j) {
+        const int col = tid + 256 * j;
+        if (col < L1) acc[j] -= (int32_t)wr[col];
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < kMaxColsPerThread; ++j) {
+    const int col = tid + 256 * j;
+    if (col < L1) {
+      const int16_t v = (int16_t)acc[j];  // int16 accumulator wraps
+      accs[col] = v;
+      ft[col] = clamp_i((int32_t)v, 0, quantized_one);
+    }
+  }
+  if (tid == 0) {
+    density[b] = (float)n_new / (float)F;
+    changed[b] = was_valid ? n_diff : n_new;
+    valid[b] = 1;
+    parity[b] = par ^ 1;
+  }
+  __syncthreads();
+
+  engine_tail(ft, pair, h1, h2, l1_w, l1_b, l1_scale, l2_w, l2_b, l2_scale, out_w, out_b, out_scale, L1, L2, L3, C,
+              logits + (size_t)b * C);
 }
 
 }  // namespace
@@ -144,25 +298,46 @@ extern "C" int64_t nnue_engine_scratch(const nnue_engine_model* m, int B) {
   return (int64_t)B * m->num_features;
 }
 
-extern "C" int nnue_engine_evaluate_logits(const nnue_engine_model* m, const float* images, int B, int H, int W, float* logits,
-                                           float* density, void* scratch, int64_t scratch_bytes, nnue_stream_t stream) {
-  NNUE_REQUIRE(m && images && logits && density && scratch, NNUE_E_ARG, "nnue_engine_evaluate_logits: null pointer");
-  NNUE_REQUIRE(m->conv_w && m->conv_b && m->ft_w && m->ft_b && m->l1_w && m->l1_b && m->l2_w && m->l2_b && m->out_w && m->out_b,
-               NNUE_E_ARG, "nnue_engine_evaluate_logits: model tensor missing");
-  NNUE_REQUIRE(B > 0 && H > 0 && W > 0, NNUE_E_ARG, "nnue_engine_evaluate_logits: B=%d H=%d W=%d must be positive", B, H, W);
+static bool engine_has_tensors(const nnue_engine_model* m) {
+  return m->conv_w && m->conv_b && m->ft_w && m->ft_b && m->l1_w && m->l1_b && m->l2_w && m->l2_b && m->out_w && m->out_b;
+}
+
+// Shape and scale checks shared by the engine's entry points (fn names the caller in the message).
+static int engine_check_model(const nnue_engine_model* m, const char* fn) {
   const int g = m->grid, oc = m->oc, F = m->num_features;
-  NNUE_REQUIRE(g > 0 && oc > 0 && F == g * g * oc, NNUE_E_SHAPE, "nnue_engine_evaluate_logits: num_features %d != %d*%d*%d", F, g, g, oc);
+  NNUE_REQUIRE(g > 0 && oc > 0 && F == g * g * oc, NNUE_E_SHAPE, "%s: num_features %d != %d*%d*%d", fn, F, g, g, oc);
   NNUE_REQUIRE(m->l1 >= 2 && m->l1 <= 256 * kMaxColsPerThread && m->l2 >= 1 && m->l3 >= 1 && m->classes >= 1, NNUE_E_SHAPE,
-               "nnue_engine_evaluate_logits: L1=%d (2..%d) L2=%d L3=%d C=%d", m->l1, 256 * kMaxColsPerThread, m->l2, m->l3, m->classes);
+               "%s: L1=%d (2..%d) L2=%d L3=%d C=%d", fn, m->l1, 256 * kMaxColsPerThread, m->l2, m->l3, m->classes);
   NNUE_REQUIRE(m->conv_scale >= 1.0f && m->l2_scale >= 1.0f && m->l1_scale > 0.0f && m->out_scale > 0.0f, NNUE_E_ARG,
-               "nnue_engine_evaluate_logits: scales must be positive (integer scales >= 1)");
-  // the engine's own stride rule, ceil((H-1)/(g-1)) (nnue_engine.cpp:710-718) -- not the training stride
+               "%s: scales must be positive (integer scales >= 1)", fn);
+  return NNUE_OK;
+}
+
+// The engine's own stride rule, ceil((H-1)/(g-1)) (nnue_engine.cpp:710-718) -- not the training stride -- and the
+// rejection of an image whose conv map would overrun the engine's grid buffer.
+static int engine_conv_geometry(const nnue_engine_model* m, int H, int W, const char* fn, int* stride_out, int* oh_out, int* ow_out) {
+  const int g = m->grid, oc = m->oc, F = m->num_features;
   int stride = g > 1 ? (H - 1 + g - 2) / (g - 1) : (H > 1 ? H : 1);
   if (stride < 1) stride = 1;
   const int OH = (H + 2 - 3) / stride + 1, OW = (W + 2 - 3) / stride + 1;
   NNUE_REQUIRE(OH > 0 && OW > 0 && (long long)OH * OW * oc <= F, NNUE_E_SHAPE,
-               "nnue_engine_evaluate_logits: a %dx%d image gives a %dx%d map that overruns the engine's %dx%d grid buffer", H, W, OH,
-               OW, g, g);
+               "%s: a %dx%d image gives a %dx%d map that overruns the engine's %dx%d grid buffer", fn, H, W, OH, OW, g, g);
+  *stride_out = stride;
+  *oh_out = OH;
+  *ow_out = OW;
+  return NNUE_OK;
+}
+
+extern "C" int nnue_engine_evaluate_logits(const nnue_engine_model* m, const float* images, int B, int H, int W, float* logits,
+                                           float* density, void* scratch, int64_t scratch_bytes, nnue_stream_t stream) {
+  static const char* fn = "nnue_engine_evaluate_logits";
+  NNUE_REQUIRE(m && images && logits && density && scratch, NNUE_E_ARG, "nnue_engine_evaluate_logits: null pointer");
+  NNUE_REQUIRE(engine_has_tensors(m), NNUE_E_ARG, "nnue_engine_evaluate_logits: model tensor missing");
+  NNUE_REQUIRE(B > 0 && H > 0 && W > 0, NNUE_E_ARG, "nnue_engine_evaluate_logits: B=%d H=%d W=%d must be positive", B, H, W);
+  if (int rc = engine_check_model(m, fn)) return rc;
+  const int oc = m->oc, F = m->num_features;
+  int stride, OH, OW;
+  if (int rc = engine_conv_geometry(m, H, W, fn, &stride, &OH, &OW)) return rc;
   NNUE_REQUIRE(scratch_bytes >= (int64_t)B * F, NNUE_E_SCRATCH, "nnue_engine_evaluate_logits: scratch %lld < %lld bytes",
                (long long)scratch_bytes, (long long)B * F);
   NNUE_REQUIRE((long long)B * H * W * 3 < (1ll << 40), NNUE_E_SHAPE, "nnue_engine_evaluate_logits: batch too large");
@@ -176,4 +351,51 @@ extern "C" int nnue_engine_evaluate_logits(const nnue_engine_model* m, const flo
                      (int)(int16_t)m->quantized_one, m->l1_w, m->l1_b, m->l1_scale, m->l2_w, m->l2_b, (int)m->l2_scale, m->out_w,
                      m->out_b, m->out_scale, m->l1, m->l2, m->l3, m->classes, logits, density);
   return nnue_launch_status("nnue_engine_evaluate_logits");
+}
+
+extern "C" int64_t nnue_engine_stream_state_bytes(const nnue_engine_model* m, int S) {
+  if (!m || S <= 0 || m->num_features <= 0 || m->l1 <= 0) return 0;
+  return stream_layout(S, m->num_features, m->l1).total;
+}
+
+extern "C" int nnue_engine_stream_step(const nnue_engine_model* m, const float* images, const uint8_t* active, int S, int H, int W,
+                                       void* state, int64_t state_bytes, float* logits, float* density, int32_t* changed,
+                                       void* scratch, int64_t scratch_bytes, nnue_stream_t stream) {
+  static const char* fn = "nnue_engine_stream_step";
+  NNUE_REQUIRE(m && state && logits && density && changed, NNUE_E_ARG, "%s: null pointer", fn);
+  NNUE_REQUIRE((images != nullptr) != (active != nullptr), NNUE_E_ARG, "%s: pass exactly one of images and active", fn);
+  NNUE_REQUIRE(nnue_aligned16(state), NNUE_E_ARG, "%s: state must be 16-byte aligned", fn);
+  NNUE_REQUIRE(engine_has_tensors(m), NNUE_E_ARG, "%s: model tensor missing", fn);
+  NNUE_REQUIRE(S > 0, NNUE_E_ARG, "%s: S=%d must be positive", fn, S);
+  if (int rc = engine_check_model(m, fn)) return rc;
+  const int oc = m->oc, F = m->num_features, L1 = m->l1, W64 = (F + 63) / 64;
+  const int64_t need = nnue_engine_stream_state_bytes(m, S);
+  NNUE_REQUIRE(state_bytes >= need, NNUE_E_SCRATCH, "%s: state %lld < %lld bytes", fn, (long long)state_bytes, (long long)need);
+  const size_t lds = (size_t)((2 * L1 + m->l2 + m->l3 + 8 + 1) & ~1) * sizeof(int32_t) + (size_t)2 * W64 * sizeof(uint64_t);
+  NNUE_REQUIRE(lds <= 64 * 1024, NNUE_E_SHAPE, "%s: layer and feature sizes need %zu bytes of LDS", fn, lds);
+  int stride = 1, OH = 0, OW = 0;
+  if (images) {
+    NNUE_REQUIRE(H > 0 && W > 0, NNUE_E_ARG, "%s: H=%d W=%d must be positive", fn, H, W);
+    if (int rc = engine_conv_geometry(m, H, W, fn, &stride, &OH, &OW)) return rc;
+    NNUE_REQUIRE(scratch, NNUE_E_ARG, "%s: images need scratch", fn);
+    NNUE_REQUIRE(scratch_bytes >= (int64_t)S * F, NNUE_E_SCRATCH, "%s: scratch %lld < %lld bytes", fn, (long long)scratch_bytes,
+                 (long long)S * F);
+    NNUE_REQUIRE((long long)S * H * W * 3 < (1ll << 40), NNUE_E_SHAPE, "%s: batch too large", fn);
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  uint8_t* st = static_cast<uint8_t*>(state);
+  const int q1 = (int)(int16_t)m->quantized_one, l2s = (int)m->l2_scale;
+  if (images) {
+    int8_t* conv = static_cast<int8_t*>(scratch);
+    hipLaunchKernelGGL(engine_conv_kernel, dim3((F + 255) / 256, S), dim3(256), 0, s, images, m->conv_w, m->conv_b, m->conv_scale, H,
+                       W, stride, OH, OW, oc, F, conv);
+    hipLaunchKernelGGL(engine_stream_kernel<false>, dim3(S), dim3(256), lds, s, conv, nullptr, m->threshold, F, oc, S, m->ft_w,
+                       m->ft_b, q1, m->l1_w, m->l1_b, m->l1_scale, m->l2_w, m->l2_b, l2s, m->out_w, m->out_b, m->out_scale, L1,
+                       m->l2, m->l3, m->classes, st, logits, density, changed);
+  } else {
+    hipLaunchKernelGGL(engine_stream_kernel<true>, dim3(S), dim3(256), lds, s, nullptr, active, m->threshold, F, oc, S, m->ft_w,
+                       m->ft_b, q1, m->l1_w, m->l1_b, m->l1_scale, m->l2_w, m->l2_b, l2s, m->out_w, m->out_b, m->out_scale, L1,
+                       m->l2, m->l3, m->classes, st, logits, density, changed);
+  }
+  return nnue_launch_status(fn);
 }

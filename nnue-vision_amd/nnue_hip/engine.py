@@ -4,13 +4,15 @@
 (engine/src/nnue_engine.cpp:544-657; same rejections) and keeps its quantised tensors in device memory;
 ``evaluate_logits(images)`` is ``NNUEEvaluator::evaluate_logits`` (nnue_engine.cpp:704-734) for a whole batch --
 bit-identical to the C++ engine (tests/golden/engine_cases.npz holds outputs of the real engine).
+``stream(S)`` is ``NNUEEvaluator::evaluate_incremental`` (nnue_engine.cpp:739-786) for S independent frame sequences: each
+step updates a stored int16 accumulator by the features that changed, with the same bits as ``evaluate_logits``.
 """
 from __future__ import annotations
 
 import ctypes
 import struct
 from pathlib import Path
-from typing import Optional, Tuple
+from typing import Iterable, Optional, Tuple
 
 import numpy as np
 import torch
@@ -136,12 +138,11 @@ class EngineModel:
                 t.update(l1_w=l1_w, l1_b=l1_b, l2_w=l2_w, l2_b=l2_b, out_w=out_w, out_b=out_b)
         return EngineModel(h, t, device)
 
-    def evaluate_logits(self, images: torch.Tensor, height: Optional[int] = None, width: Optional[int] = None
-                        ) -> Tuple[torch.Tensor, torch.Tensor]:
-        """(logits [B, C] float32, density [B] float32).  ``images`` is what the reference hands the engine: per sample
-        a flat buffer of 3*H*W floats which the engine indexes as HWC -- for a [B,3,H,W] tensor that is its memory as
-        it stands (evaluate.py:150-161 passes shape[1], shape[2] as H, W), which is reproduced, not corrected."""
-        images = lib._need(images, torch.float32, "images")
+    def stream(self, num_streams: int) -> "EngineStream":
+        """Incremental evaluation of ``num_streams`` frame sequences (see EngineStream)."""
+        return EngineStream(self, num_streams)
+
+    def _frames(self, images: torch.Tensor, height: Optional[int], width: Optional[int]) -> Tuple[int, int, int]:
         if images.dim() == 4:
             b, h, w = images.shape[0], images.shape[2], images.shape[3]
             if images.shape[1] != 3:
@@ -150,11 +151,97 @@ class EngineModel:
             b, h, w = images.shape[0], height, width
         else:
             raise ValueError("images: expected [B,3,H,W], or [B,3*H*W] with height and width")
+        return b, h, w
+
+    def _scratch_for(self, b: int) -> torch.Tensor:
         need = int(lib.load().nnue_engine_scratch(ctypes.byref(self._c), b))
         if self._scratch is None or self._scratch.numel() < need:
             self._scratch = torch.empty((max(16, need),), dtype=torch.uint8, device=self.device)
+        return self._scratch
+
+    def evaluate_logits(self, images: torch.Tensor, height: Optional[int] = None, width: Optional[int] = None
+                        ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(logits [B, C] float32, density [B] float32).  ``images`` is what the reference hands the engine: per sample
+        a flat buffer of 3*H*W floats which the engine indexes as HWC -- for a [B,3,H,W] tensor that is its memory as
+        it stands (evaluate.py:150-161 passes shape[1], shape[2] as H, W), which is reproduced, not corrected."""
+        images = lib._need(images, torch.float32, "images")
+        b, h, w = self._frames(images, height, width)
+        self._scratch_for(b)
         logits = torch.empty((b, self.num_classes), dtype=torch.float32, device=self.device)
         density = torch.empty((b,), dtype=torch.float32, device=self.device)
         lib._call("nnue_engine_evaluate_logits", ctypes.addressof(self._c), images.data_ptr(), b, h, w, logits.data_ptr(),
                   density.data_ptr(), self._scratch.data_ptr(), self._scratch.numel(), lib._stream(images))
         return logits, density
+
+
+class EngineStream:
+    """S independent frame sequences (for example one per camera) evaluated incrementally on the device: every stream keeps
+    the engine's wrapped int16 accumulator and its last active-feature set, and a step applies only the features that
+    turned on or off (FeatureTransformer::update_accumulator, nnue_engine.cpp:257-267).  Every step's logits and density
+    are bit-identical to ``EngineModel.evaluate_logits`` on the same frames, whatever came before: int16 addition wraps,
+    so the order and history of the terms do not matter.  A new stream, and one passed to ``reset``, is refreshed from
+    the bias on its next step.  ``step`` (images) and ``step_features`` (feature maps) may be mixed on one stream."""
+
+    def __init__(self, model: EngineModel, num_streams: int):
+        s = int(num_streams)
+        if s <= 0:
+            raise ValueError(f"num_streams must be positive, got {num_streams}")
+        self.model, self.num_streams = model, s
+        self.num_features = int(model.header["num_features"])
+        nbytes = int(lib.load().nnue_engine_stream_state_bytes(ctypes.byref(model._c), s))
+        # zero-filled = every stream invalid; the first S int32 of the state are the valid flags (include/nnue_hip.h)
+        self.state = torch.zeros((nbytes,), dtype=torch.uint8, device=model.device)
+        self._valid = self.state[:4 * s].view(torch.int32)
+
+    def reset(self, streams: Optional[Iterable[int]] = None) -> None:
+        """Marks all streams, or the given indices, for a refresh from the bias on the next step."""
+        if streams is None:
+            self._valid.fill_(0)
+            return
+        idx = sorted({int(i) for i in streams})
+        if idx and (idx[0] < 0 or idx[-1] >= self.num_streams):
+            raise ValueError(f"reset: stream indices must lie in [0, {self.num_streams})")
+        for i in idx:
+            self._valid[i:i + 1].fill_(0)
+
+    def _check(self, t, what: str, dtypes) -> None:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{what}: expected a tensor, got {type(t).__name__}")
+        if t.dtype not in dtypes:
+            raise ValueError(f"{what}: expected dtype {' or '.join(str(d) for d in dtypes)}, got {t.dtype}")
+        dev = self.model.device
+        if not t.is_cuda or (dev.index is not None and t.device.index != dev.index):
+            raise ValueError(f"{what}: tensor is on {t.device}, the stream's state on {self.model.device} "
+                             "(no CPU fallback in this build)")
+        if t.dim() < 1 or t.shape[0] != self.num_streams:
+            raise ValueError(f"{what}: expected {self.num_streams} streams in dim 0, got shape {tuple(t.shape)}")
+
+    def _run(self, images: Optional[torch.Tensor], active: Optional[torch.Tensor], h: int, w: int
+             ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        m, s = self.model, self.num_streams
+        logits = torch.empty((s, m.num_classes), dtype=torch.float32, device=m.device)
+        density = torch.empty((s,), dtype=torch.float32, device=m.device)
+        changed = torch.empty((s,), dtype=torch.int32, device=m.device)
+        scratch = m._scratch_for(s) if images is not None else None
+        src = images if images is not None else active
+        lib._call("nnue_engine_stream_step", ctypes.addressof(m._c), lib._ptr(images), lib._ptr(active), s, h, w,
+                  self.state.data_ptr(), self.state.numel(), logits.data_ptr(), density.data_ptr(), changed.data_ptr(),
+                  lib._ptr(scratch), 0 if scratch is None else scratch.numel(), lib._stream(src))
+        return logits, density, changed
+
+    def step(self, frames: torch.Tensor, height: Optional[int] = None, width: Optional[int] = None
+             ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """One frame per stream, in the forms ``evaluate_logits`` takes ([S,3,H,W], or [S,3*H*W] with height and width;
+        H x W may change between steps).  Returns (logits [S, C] float32, density [S] float32, changed [S] int32): changed
+        = features that differ from the stream's previous set, or all active ones on a refresh."""
+        self._check(frames, "frames", (torch.float32,))
+        _, h, w = self.model._frames(frames, height, width)
+        return self._run(frames.contiguous(), None, h, w)
+
+    def step_features(self, active: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """One active-feature map per stream: bool or uint8 [S, num_features] on the device, non-zero = on.  Every id
+        counts (the reference's evaluate_incremental(current_features) takes the indices as given)."""
+        self._check(active, "active", (torch.bool, torch.uint8))
+        if tuple(active.shape) != (self.num_streams, self.num_features):
+            raise ValueError(f"active: expected shape {(self.num_streams, self.num_features)}, got {tuple(active.shape)}")
+        return self._run(None, active.contiguous(), 0, 0)

@@ -16,7 +16,7 @@ import torch
 
 _HERE = Path(__file__).resolve().parent
 LIB_PATH = _HERE / "libnnue_hip.so"
-ABI_VERSION = 30
+ABI_VERSION = 31
 
 _c_int, _c_i64, _c_f, _c_p = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
 
@@ -127,6 +127,8 @@ SIGNATURES = {
                                  _c_p, _c_p, _c_p]),
     "nnue_engine_scratch": (_c_i64, [_c_p, _c_int]),
     "nnue_engine_evaluate_logits": (_c_int, [_c_p, _c_p, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p, _c_i64, _c_p]),
+    "nnue_engine_stream_state_bytes": (_c_i64, [_c_p, _c_int]),
+    "nnue_engine_stream_step": (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p]),
     "nnue_sgd_scratch": (_c_i64, [_c_i64]),
     "nnue_adam_step": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f,
                                 _c_p, _c_p, _c_i64, _c_p, _c_p]),
