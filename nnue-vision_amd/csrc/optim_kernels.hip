@@ -35,8 +35,8 @@ __global__ __launch_bounds__(256) void cross_entropy_kernel(const float* __restr
   se = wave_sum(se);
   const int64_t y = labels[b];
   const bool ok = y >= 0 && y < C;
-  const float lse = mx + logf(se);
-  if (lane == 0) sample_loss[b] = ok ? lse - z[y] : 0.0f;
+  // (max - z_y) + log(se): exact to a few ulp of the loss itself; (max + log(se)) - z_y rounds at the scale of the logits
+  if (lane == 0) sample_loss[b] = ok ? (mx - z[y]) + logf(se) : 0.0f;
   if (d_logits) {
     const float inv = 1.0f / se;
     for (int c = lane; c < C; c += 64) {
@@ -57,7 +57,8 @@ __global__ __launch_bounds__(256) void mean_kernel(const float* __restrict__ v, 
   if (threadIdx.x == 0) *out = ((red[0] + red[1]) + (red[2] + red[3])) / (float)n;
 }
 
-// evaluation: argmax (first maximum, as numpy) and one integer atomic per sample into the confusion matrix;
+// evaluation: argmax (first maximum, as numpy: a NaN beats every number and the first NaN wins) and one integer atomic per
+// sample into the confusion matrix;
 // C == 1 is the reference's binary rule (output > 0.5 vs target > 0.5)
 __global__ __launch_bounds__(256) void confusion_kernel(const float* __restrict__ logits,
                                                         const int64_t* __restrict__ labels, int B, int C, int K,
@@ -72,8 +73,8 @@ __global__ __launch_bounds__(256) void confusion_kernel(const float* __restrict_
   } else {
     pred = 0;
     float best = z[0];
-    for (int c = 1; c < C; ++c)
-      if (z[c] > best) {
+    for (int c = 1; c < C && best == best; ++c)
+      if (!(z[c] <= best)) {  // greater, or NaN
         best = z[c];
         pred = c;
       }
@@ -85,6 +86,15 @@ __global__ __launch_bounds__(256) void confusion_kernel(const float* __restrict_
 }
 
 constexpr int kNormBlocks = 1024;
+
+// clip_grad_norm_'s coefficient, clamp(max_norm / (norm + 1e-6), max=1) as torch forms it: a NaN norm gives a NaN
+// coefficient (every gradient becomes NaN, as in the reference), where fminf would drop the NaN and apply 1.
+// max_norm <= 0: no clipping.
+__device__ __forceinline__ float clip_coefficient(float norm, float max_norm) {
+  if (!(max_norm > 0.0f)) return 1.0f;
+  const float c = max_norm / (norm + 1e-6f);
+  return c > 1.0f ? 1.0f : c;
+}
 
 // Block partial of sum (g * scale)^2: 16-byte loads, four independent chains per thread (the 268 MB gradient of
 // the 224x224 configuration is one streaming read; a dependent scalar chain reached only 1.25 TB/s).
@@ -192,14 +202,15 @@ __global__ __launch_bounds__(256) void sgd_apply_kernel(float* __restrict__ p, c
   if (lr_dev) lr = lr_dev[0];  // the learning rate as a device scalar: a scheduler changes it without re-capturing the step
   // The first kPre passes of this thread's share are requested BEFORE the norm is re-derived: after a kernel boundary
   // both the partials and the parameters are first touches (~2 us each from a cold L2), and the two waits would
-  // otherwise run one after the other.  Unconditional loads from clamped indices; results used only where valid.
+  // otherwise run one after the other.  Unconditional loads from clamped indices; results used only where valid.  (live == 0,
+  // the hole is the whole buffer: no index is valid and nothing is read; the launch still writes norm_out / coef_out.)
   constexpr int kPre = 4;
   const int64_t stride = (int64_t)gridDim.x * 256;
   const int64_t hole = skip_hi - skip_lo;  // 0: everything is updated here
   const int64_t live = count - hole, j0 = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  float pw[kPre], pg[kPre], pm[kPre];
+  float pw[kPre] = {}, pg[kPre] = {}, pm[kPre] = {};
 #pragma unroll
-  for (int u = 0; u < kPre; ++u) {
+  for (int u = 0; u < kPre && live > 0; ++u) {
     const int64_t j = j0 + u * stride < live ? j0 + u * stride : 0;
     const int64_t i = j < skip_lo ? j : j + hole;
     pw[u] = p[i];
@@ -221,7 +232,7 @@ __global__ __launch_bounds__(256) void sgd_apply_kernel(float* __restrict__ p, c
     if (threadIdx.x == 0) {
       const float norm = (float)sqrt((red[0] + red[1]) + (red[2] + red[3]));
       if (norm_out && blockIdx.x == 0) *norm_out = norm;
-      coef_s = max_norm > 0.0f ? fminf(max_norm / (norm + 1e-6f), 1.0f) : 1.0f;
+      coef_s = clip_coefficient(norm, max_norm);
       if (coef_out && blockIdx.x == 0) *coef_out = coef_s;  // for the producer that applies [skip_lo, skip_hi) itself
     }
     __syncthreads();
@@ -272,9 +283,9 @@ __global__ __launch_bounds__(256) void sgd_apply_vec_kernel(float* __restrict__ 
   const float4* __restrict__ p4 = reinterpret_cast<const float4*>(p);
   const float4* __restrict__ g4 = reinterpret_cast<const float4*>(g);
   const float4* __restrict__ m4 = reinterpret_cast<const float4*>(m);
-  float4 pw[kPre], pg[kPre], pm[kPre];
+  float4 pw[kPre] = {}, pg[kPre] = {}, pm[kPre] = {};
 #pragma unroll
-  for (int u = 0; u < kPre; ++u) {
+  for (int u = 0; u < kPre && live4 > 0; ++u) {  // live4 == 0: nothing to read (see sgd_apply_kernel)
     const int64_t j = j0 + u * stride < live4 ? j0 + u * stride : 0;
     const int64_t i = j < lo4 ? j : j + hole4;
     pw[u] = p4[i];
@@ -296,7 +307,7 @@ __global__ __launch_bounds__(256) void sgd_apply_vec_kernel(float* __restrict__ 
     if (threadIdx.x == 0) {
       const float norm = (float)sqrt((red[0] + red[1]) + (red[2] + red[3]));
       if (norm_out && blockIdx.x == 0) *norm_out = norm;
-      coef_s = max_norm > 0.0f ? fminf(max_norm / (norm + 1e-6f), 1.0f) : 1.0f;
+      coef_s = clip_coefficient(norm, max_norm);
       if (coef_out && blockIdx.x == 0) *coef_out = coef_s;
     }
     __syncthreads();
@@ -356,7 +367,7 @@ __global__ __launch_bounds__(256) void adam_apply_kernel(float* __restrict__ p, 
   if (threadIdx.x == 0) {
     const float norm = (float)sqrt((red[0] + red[1]) + (red[2] + red[3]));
     if (norm_out && blockIdx.x == 0) *norm_out = norm;
-    coef_s = max_norm > 0.0f ? fminf(max_norm / (norm + 1e-6f), 1.0f) : 1.0f;
+    coef_s = clip_coefficient(norm, max_norm);
   }
   __syncthreads();
   const float gs = coef_s * scale;
@@ -441,6 +452,8 @@ extern "C" int nnue_sgd_step(float* params, float* grads, float* momentum_buf, i
   int nb = (int)((count + 4095) / 4096);
   nb = nb < 64 ? 64 : (nb > kNormBlocks ? kNormBlocks : nb);
   int nparts = nb;
+  NNUE_REQUIRE(!ext_applied_elsewhere || (ext_partial && coef_out), NNUE_E_ARG,
+               "nnue_sgd_step: ext_applied_elsewhere needs the producer's partials and coef_out");
   if (ext_partial) {
     NNUE_REQUIRE(ext_count > 0 && ext_count <= 65536 && ext_lo >= 0 && ext_lo < ext_hi && ext_hi <= count && ext_lo % 4 == 0 &&
                      (ext_hi % 4 == 0 || ext_hi == count),
@@ -469,8 +482,6 @@ extern "C" int nnue_sgd_step(float* params, float* grads, float* momentum_buf, i
   } else if (max_norm > 0.0f || norm_out || coef_out) {
     hipLaunchKernelGGL(sqnorm_stage1, dim3(nb), dim3(256), 0, s, grads, count, grad_scale, partial, ext_lo, ext_hi);
   }
-  NNUE_REQUIRE(!ext_applied_elsewhere || (ext_partial && coef_out), NNUE_E_ARG,
-               "nnue_sgd_step: ext_applied_elsewhere needs the producer's partials and coef_out");
   const int64_t live = ext_applied_elsewhere ? count - (ext_hi - ext_lo) : count;
   int blocks = (int)((live + 1023) / 1024);
   blocks = blocks < 1 ? 1 : blocks;
