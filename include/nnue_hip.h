@@ -40,7 +40,7 @@
 extern "C" {
 #endif
 
-#define NNUE_HIP_ABI_VERSION 31
+#define NNUE_HIP_ABI_VERSION 32
 
 #define NNUE_OK 0
 #define NNUE_E_ARG (-1)     /* null pointer, non-positive size, bad alignment */
@@ -650,6 +650,35 @@ int nnue_adam_step(float* params, float* grads, float* exp_avg, float* exp_avg_s
                    int64_t count, float lr, float beta1, float beta2, float eps, float weight_decay,
                    float max_norm, float grad_scale, float* norm_out,
                    void* scratch, int64_t scratch_bytes, const float* lr_dev, nnue_stream_t stream);
+
+/* clip_grad_norm_ + SGD(momentum, weight_decay) over a LIST of n separate tensors -- torch.optim's parameter list with its
+ * param groups, as the reference's loop steps it (train.py:363-366; the optimizer of create_optimizer, train.py:455-471):
+ * segment i is params[i] / grads[i] / momentum_bufs[i], counts[i] > 0 elements, with its own lr[i], momentum[i],
+ * weight_decay[i] and first_step[i] (no momentum buffer yet: it is written, not read).  The norm is the global one over all
+ * segments; per element the arithmetic of nnue_sgd_step (grad_scale 1):
+ *   c = min(1, max_norm/(norm+1e-6)) if max_norm > 0 else 1 ; g <- c*g + wd*p ; m <- first ? g : momentum*m + g ; p <- p - lr*m
+ * momentum[i] == 0: momentum_bufs may be NULL or hold NULL there, and nothing is written to it.
+ * The arrays are HOST arrays (pointers to device memory, counts and hyperparameters); the call packs them into kernel-argument
+ * tables of 50 segments, so a step has no host-to-device copy and launches 2 kernels per 50 segments (1 without a norm).
+ * Any sizes, any 4-byte-aligned views: 16-byte accesses where the segment's pointers share their offset within 16 bytes.
+ * The norm is summed in fixed-size chunks in list order and re-derived in double: two runs give the same bits whatever the
+ * pointers.  scratch >= nnue_multi_optim_scratch(counts, n) bytes (0 on invalid arguments).  norm_out (device float, may be
+ * NULL) receives the pre-clip norm -- what clip_grad_norm_ returns.  lr_dev (may be NULL): n device floats that replace lr[]. */
+int64_t nnue_multi_optim_scratch(const int64_t* counts, int n);
+int nnue_multi_sgd_step(float* const* params, float* const* grads, float* const* momentum_bufs, const int64_t* counts, int n,
+                        const float* lr, const float* momentum, const float* weight_decay, const int32_t* first_step,
+                        float max_norm, float* norm_out, void* scratch, int64_t scratch_bytes, const float* lr_dev,
+                        nnue_stream_t stream);
+
+/* clip_grad_norm_ + Adam(lr, betas, eps, weight_decay) over a list of n separate tensors (train.py:363-366, :455-471; torch's
+ * L2 weight decay, no amsgrad): segment i carries exp_avgs[i], exp_avg_sqs[i] and its own step counter step_counters[i]
+ * (one device int32 per tensor, so a tensor that skips a step keeps its own count), with lr[i], beta1[i], beta2[i], eps[i],
+ * weight_decay[i].  The norm launch advances every listed counter by one; per element the arithmetic of nnue_adam_step at
+ * that segment's t.  Tables, alignment, scratch, norm_out and lr_dev as nnue_multi_sgd_step. */
+int nnue_multi_adam_step(float* const* params, float* const* grads, float* const* exp_avgs, float* const* exp_avg_sqs,
+                         int32_t* const* step_counters, const int64_t* counts, int n, const float* lr, const float* beta1,
+                         const float* beta2, const float* eps, const float* weight_decay, float max_norm, float* norm_out,
+                         void* scratch, int64_t scratch_bytes, const float* lr_dev, nnue_stream_t stream);
 
 #ifdef __cplusplus
 }

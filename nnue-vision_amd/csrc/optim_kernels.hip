@@ -1,5 +1,6 @@
 // Loss and step tail on gfx950: mean cross-entropy with its gradient (train.py:250-254) and
-// clip_grad_norm_ + SGD(momentum, weight_decay) on one flat buffer (train.py:363-366, :457-464).
+// clip_grad_norm_ + SGD(momentum, weight_decay) / Adam on one flat buffer or on a list of separate tensors
+// (train.py:363-366, :457-471).
 // Both are small streaming kernels; sums are staged so results are bitwise reproducible.
 #include "common.h"
 
@@ -94,6 +95,33 @@ __device__ __forceinline__ float clip_coefficient(float norm, float max_norm) {
   if (!(max_norm > 0.0f)) return 1.0f;
   const float c = max_norm / (norm + 1e-6f);
   return c > 1.0f ? 1.0f : c;
+}
+
+// The per-element arithmetic of clip_grad_norm_ + SGD (train.py:363-366, :457-464), shared by the flat and the multi-tensor
+// kernels: g <- gs*g + wd*w; m <- first ? g : momentum*m + g (has_m: momentum != 0); returns w - lr*m.
+__device__ __forceinline__ float sgd_update(float w, float g, float m_old, float& m_new, float gs, float lr, float momentum,
+                                            float wd, bool has_m, bool first) {
+  float gi = fmaf(wd, w, g * gs);
+  if (has_m) gi = first ? gi : fmaf(momentum, m_old, gi);
+  m_new = gi;
+  return w - lr * gi;
+}
+
+// ... and of clip_grad_norm_ + Adam (train.py:363-366, :465-470): L2 weight decay folded into the gradient, the moments
+// updated in place, the bias corrections of step t precomputed by adam_bias_correction.
+struct AdamBias {
+  float step_size, inv_sqrt_bc2;
+};
+__device__ __forceinline__ AdamBias adam_bias_correction(float lr, float beta1, float beta2, int t) {
+  const double bc1 = 1.0 - pow((double)beta1, (double)t), bc2 = 1.0 - pow((double)beta2, (double)t);
+  return {(float)((double)lr / bc1), (float)(1.0 / sqrt(bc2))};
+}
+__device__ __forceinline__ float adam_update(float w, float g, float& m, float& v, float gs, AdamBias bc, float beta1, float beta2,
+                                             float eps, float wd) {
+  const float gi = fmaf(wd, w, g * gs);
+  m = beta1 * m + (1.0f - beta1) * gi;
+  v = beta2 * v + (1.0f - beta2) * gi * gi;
+  return w - bc.step_size * (m / (sqrtf(v) * bc.inv_sqrt_bc2 + eps));
 }
 
 // Block partial of sum (g * scale)^2: 16-byte loads, four independent chains per thread (the 268 MB gradient of
@@ -244,23 +272,16 @@ __global__ __launch_bounds__(256) void sgd_apply_kernel(float* __restrict__ p, c
     const int64_t j = j0 + u * stride;
     if (j < live) {
       const int64_t i = j < skip_lo ? j : j + hole;
-      float gi = fmaf(wd, pw[u], pg[u] * gs);
-      if (m) {
-        gi = first_step ? gi : fmaf(momentum, pm[u], gi);
-        m[i] = gi;
-      }
-      p[i] = pw[u] - lr * gi;
+      float mn;
+      p[i] = sgd_update(pw[u], pg[u], pm[u], mn, gs, lr, momentum, wd, m != nullptr, first_step);
+      if (m) m[i] = mn;
     }
   }
   for (int64_t j = j0 + kPre * stride; j < live; j += stride) {
     const int64_t i = j < skip_lo ? j : j + hole;
-    const float w = p[i];
-    float gi = fmaf(wd, w, g[i] * gs);
-    if (m) {
-      gi = first_step ? gi : fmaf(momentum, m[i], gi);
-      m[i] = gi;
-    }
-    p[i] = w - lr * gi;
+    float mn;
+    p[i] = sgd_update(p[i], g[i], (m && !first_step) ? m[i] : 0.0f, mn, gs, lr, momentum, wd, m != nullptr, first_step);
+    if (m) m[i] = mn;
   }
 }
 
@@ -314,11 +335,8 @@ __global__ __launch_bounds__(256) void sgd_apply_vec_kernel(float* __restrict__ 
     clip = coef_s;
   }
   const float gs = clip * scale;
-  auto one = [&](float w, float gv, float mv, float& m_new) {  // the arithmetic of sgd_apply_kernel, element by element
-    float gi = fmaf(wd, w, gv * gs);
-    if (m) gi = first_step ? gi : fmaf(momentum, mv, gi);
-    m_new = gi;
-    return w - lr * gi;
+  auto one = [&](float w, float gv, float mv, float& m_new) {
+    return sgd_update(w, gv, mv, m_new, gs, lr, momentum, wd, m != nullptr, first_step);
   };
   auto apply = [&](int64_t i, const float4& w, const float4& gv, const float4& mv) {
     float4 mn, wn;
@@ -371,19 +389,274 @@ __global__ __launch_bounds__(256) void adam_apply_kernel(float* __restrict__ p, 
   }
   __syncthreads();
   const float gs = coef_s * scale;
-  const int t = step_counter[0];
-  const double bc1 = 1.0 - pow((double)beta1, (double)t), bc2 = 1.0 - pow((double)beta2, (double)t);
-  const float step_size = (float)((double)lr / bc1);
-  const float inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+  const AdamBias bc = adam_bias_correction(lr, beta1, beta2, step_counter[0]);
   const int64_t stride = (int64_t)gridDim.x * 256;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < count; i += stride) {
-    const float w = p[i];
-    const float gi = fmaf(wd, w, g[i] * gs);
-    const float mi = beta1 * m[i] + (1.0f - beta1) * gi;
-    const float vi = beta2 * v[i] + (1.0f - beta2) * gi * gi;
+    float mi = m[i], vi = v[i];
+    p[i] = adam_update(p[i], g[i], mi, vi, gs, bc, beta1, beta2, eps, wd);
     m[i] = mi;
     v[i] = vi;
-    p[i] = w - step_size * (mi / (sqrtf(vi) * inv_sqrt_bc2 + eps));
+  }
+}
+
+
+// ---- the multi-tensor form: torch.optim's list of separate parameters (one segment per tensor, any sizes, any views) ----
+// Stage 1 writes one sum-of-squares partial per kMultiChunk elements of each segment, segments in list order; stage 2's
+// workgroups re-derive the global norm from all partials (fixed order, double) and stream kMultiUnit-element units of the
+// update through the per-element helpers above.  The segment table rides in the kernel arguments, so a step has no host-to-
+// device copy; a list longer than one table is split over several launches that write disjoint ranges of the partials.
+constexpr int kMultiChunk = 16384;       // elements per norm partial (4096 partials for the 268 MB table of the 224x224 model)
+constexpr int kMultiUnit = 4096;         // elements per apply unit: 256 threads x 4 float4
+constexpr int kMultiApplyBlocks = 2048;  // apply grid cap: each workgroup then streams >= 8 units of a big table per re-reduction
+constexpr int kMultiSegs = 50;
+
+struct MultiSeg {
+  float* p;
+  const float* g;
+  float* m;       // SGD momentum buffer (NULL: momentum 0) / Adam exp_avg
+  float* v;       // Adam exp_avg_sq
+  int32_t* step;  // Adam step counter (device)
+  int64_t count;
+  int32_t chunk0, unit0;  // this segment's first norm chunk / apply unit within the launch
+  float lr, a, b, wd, eps;  // a: momentum or beta1; b: beta2
+  int32_t first;            // SGD: no momentum buffer yet (the update writes it without reading)
+};
+
+struct MultiArgs {
+  float* partial;      // all partials of the list (the apply reads [0, nparts))
+  float* norm_out;     // pre-clip norm (first apply launch only), may be NULL
+  const float* lr_dev; // n device floats replacing lr, indexed by seg_base + segment; may be NULL
+  int32_t nparts, part_base, seg_base, n, chunks, units, need_norm;
+  float max_norm;
+  MultiSeg seg[kMultiSegs];
+};
+static_assert(sizeof(MultiArgs) <= 4096, "the segment table must fit the 4 KiB kernel-argument budget");
+
+// the last segment whose first chunk (by_unit: unit) is <= x; x is wave-uniform, so these are scalar loads of the arguments
+__device__ __forceinline__ int multi_find(const MultiArgs& A, int x, bool by_unit) {
+  int lo = 0, hi = A.n - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if ((by_unit ? A.seg[mid].unit0 : A.seg[mid].chunk0) <= x) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+
+__device__ __forceinline__ float sq4(float4 x, float a) { return fmaf(x.w, x.w, fmaf(x.z, x.z, fmaf(x.y, x.y, fmaf(x.x, x.x, a)))); }
+
+// Stage 1.  Element e0 + it*4096 + j*1024 + 4*thread + k of a chunk always enters chain j in the same position, whether it
+// arrives in a 16-byte load (g aligned, whole chunk in range) or in guarded scalar loads (a misaligned view, the ragged
+// last chunk): the partial does not depend on where the gradient happens to lie.  Adam: the first workgroup also
+// advances the segments' step counters (as sqnorm_stage1_count does).
+__global__ __launch_bounds__(256) void multi_sqnorm_kernel(const MultiArgs A) {
+  __shared__ float red[4];
+  if (blockIdx.x == 0 && (int)threadIdx.x < A.n && A.seg[threadIdx.x].step) A.seg[threadIdx.x].step[0] += 1;
+  if (!A.need_norm) return;
+  const int c = blockIdx.x;
+  const MultiSeg& S = A.seg[multi_find(A, c, false)];
+  const float* __restrict__ g = S.g;
+  const int64_t e0 = (int64_t)(c - S.chunk0) * kMultiChunk + 4 * threadIdx.x;
+  constexpr int kIt = kMultiChunk / kMultiUnit;
+  float a[4] = {0.f, 0.f, 0.f, 0.f};
+  if ((reinterpret_cast<uintptr_t>(g) & 15) == 0 && (int64_t)(c - S.chunk0 + 1) * kMultiChunk <= S.count) {
+    float4 x[kIt][4];
+#pragma unroll
+    for (int it = 0; it < kIt; ++it)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) x[it][j] = *reinterpret_cast<const float4*>(g + e0 + it * kMultiUnit + j * 1024);
+#pragma unroll
+    for (int it = 0; it < kIt; ++it)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) a[j] = sq4(x[it][j], a[j]);
+  } else {
+    for (int it = 0; it < kIt; ++it)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int64_t i = e0 + it * kMultiUnit + j * 1024;
+        float4 x;
+        x.x = i < S.count ? g[i] : 0.0f;
+        x.y = i + 1 < S.count ? g[i + 1] : 0.0f;
+        x.z = i + 2 < S.count ? g[i + 2] : 0.0f;
+        x.w = i + 3 < S.count ? g[i + 3] : 0.0f;
+        a[j] = sq4(x, a[j]);
+      }
+  }
+  const float acc = wave_sum((a[0] + a[1]) + (a[2] + a[3]));
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) A.partial[A.part_base + c] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// One apply unit in registers.  Vector form (p, g and the state share their offset within 16 bytes): float4 q of the
+// segment starts at element head + 4q, and unit k holds float4s k*1024 + j*256 + thread; the < 4 elements before the first
+// aligned one (head) go with unit 0, those after the last whole float4 (tail) with the segment's last unit.  Scalar form
+// (mixed offsets): unit k holds elements k*4096 + r*256 + thread.
+template <bool kAdam>
+struct MultiUnit {
+  float4 w[4], g[4], m[4], v[4];
+  int64_t base;  // vector form: element of the unit's first float4; scalar form: first element of the unit
+  int lim;       // elements of the segment from base on, capped at one unit
+  bool vec;
+
+  // component c of quad j: vector form element 4*(j*256 + thread) + c; scalar form element (4*j + c)*256 + thread.  The
+  // wave-uniform base pointer keeps the per-thread offset 32-bit and shared by all quads.
+  __device__ __forceinline__ int offset(int j, int c) const {
+    return vec ? 4 * (j * 256 + (int)threadIdx.x) + c : (4 * j + c) * 256 + (int)threadIdx.x;
+  }
+
+  __device__ __forceinline__ void load(const MultiSeg& S, int k, bool read_m) {
+    const uintptr_t off = reinterpret_cast<uintptr_t>(S.p) & 15;
+    vec = (reinterpret_cast<uintptr_t>(S.g) & 15) == off && (!S.m || (reinterpret_cast<uintptr_t>(S.m) & 15) == off) &&
+          (!kAdam || (reinterpret_cast<uintptr_t>(S.v) & 15) == off);
+    base = (int64_t)k * kMultiUnit + (vec ? (int64_t)((16 - off) & 15) / 4 : 0);
+    lim = S.count - base < kMultiUnit + 16 ? (int)(S.count - base) : kMultiUnit + 16;
+    const float* __restrict__ P = S.p + base;
+    const float* __restrict__ G = S.g + base;
+    const float* __restrict__ M = S.m + base;
+    const float* __restrict__ V = S.v + base;
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      w[j] = g[j] = m[j] = v[j] = z;
+      if (vec) {
+        const int o = offset(j, 0);
+        if (o + 4 <= lim) {
+          w[j] = *reinterpret_cast<const float4*>(P + o);
+          g[j] = *reinterpret_cast<const float4*>(G + o);
+          if (read_m) m[j] = *reinterpret_cast<const float4*>(M + o);
+          if (kAdam) v[j] = *reinterpret_cast<const float4*>(V + o);
+        }
+      } else {
+        auto one = [&](int c, float& wc, float& gc, float& mc, float& vc) {
+          const int o = offset(j, c);
+          if (o >= lim) return;
+          wc = P[o];
+          gc = G[o];
+          if (read_m) mc = M[o];
+          if (kAdam) vc = V[o];
+        };
+        one(0, w[j].x, g[j].x, m[j].x, v[j].x);
+        one(1, w[j].y, g[j].y, m[j].y, v[j].y);
+        one(2, w[j].z, g[j].z, m[j].z, v[j].z);
+        one(3, w[j].w, g[j].w, m[j].w, v[j].w);
+      }
+    }
+  }
+
+  __device__ __forceinline__ void store(const MultiSeg& S) const {
+    float* __restrict__ P = S.p + base;
+    float* __restrict__ M = S.m + base;
+    float* __restrict__ V = S.v + base;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (vec) {
+        const int o = offset(j, 0);
+        if (o + 4 > lim) continue;
+        *reinterpret_cast<float4*>(P + o) = w[j];
+        if (S.m) *reinterpret_cast<float4*>(M + o) = m[j];
+        if (kAdam) *reinterpret_cast<float4*>(V + o) = v[j];
+      } else {
+        auto one = [&](int c, float wc, float mc, float vc) {
+          const int o = offset(j, c);
+          if (o >= lim) return;
+          P[o] = wc;
+          if (S.m) M[o] = mc;
+          if (kAdam) V[o] = vc;
+        };
+        one(0, w[j].x, m[j].x, v[j].x);
+        one(1, w[j].y, m[j].y, v[j].y);
+        one(2, w[j].z, m[j].z, v[j].z);
+        one(3, w[j].w, m[j].w, v[j].w);
+      }
+    }
+  }
+};
+
+// the per-segment constants of the update: learning rate (lr_dev wins) and, for Adam, the bias corrections of the step
+// stage 1 has just counted
+struct MultiHyper {
+  float lr;
+  AdamBias bc;
+};
+template <bool kAdam>
+__device__ __forceinline__ MultiHyper multi_hyper(const MultiArgs& A, int s) {
+  const MultiSeg& S = A.seg[s];
+  MultiHyper h;
+  h.lr = A.lr_dev ? A.lr_dev[A.seg_base + s] : S.lr;
+  h.bc = kAdam ? adam_bias_correction(h.lr, S.a, S.b, S.step[0]) : AdamBias{0.f, 0.f};
+  return h;
+}
+
+template <bool kAdam>
+__device__ __forceinline__ float multi_update(const MultiSeg& S, const MultiHyper& h, float w, float g, float& m, float& v, float gs) {
+  if (kAdam) return adam_update(w, g, m, v, gs, h.bc, S.a, S.b, S.eps, S.wd);
+  float mn;
+  const float out = sgd_update(w, g, m, mn, gs, h.lr, S.a, S.wd, S.m != nullptr, S.first != 0);
+  m = mn;
+  return out;
+}
+
+// Stage 2.  The first unit is requested before the norm is re-derived (both are first touches after the kernel boundary).
+template <bool kAdam>
+__global__ __launch_bounds__(256) void multi_apply_kernel(const MultiArgs A) {
+  __shared__ double red[4];
+  __shared__ float coef_s;
+  int u = blockIdx.x;
+  int s = multi_find(A, u, true);
+  MultiUnit<kAdam> U;
+  U.load(A.seg[s], u - A.seg[s].unit0, A.seg[s].m && (kAdam || !A.seg[s].first));
+  float clip = 1.0f;
+  if (A.need_norm) {
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < A.nparts; i += 256) acc += (double)A.partial[i];
+#pragma unroll
+    for (int k = 32; k >= 1; k >>= 1) acc += __shfl_xor(acc, k);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const float norm = (float)sqrt((red[0] + red[1]) + (red[2] + red[3]));
+      if (A.norm_out && blockIdx.x == 0) *A.norm_out = norm;
+      coef_s = clip_coefficient(norm, A.max_norm);
+    }
+    __syncthreads();
+    clip = coef_s;
+  }
+  int hs = s;
+  MultiHyper h = multi_hyper<kAdam>(A, s);
+  while (true) {
+    const MultiSeg& S = A.seg[s];
+    if (hs != s) {
+      h = multi_hyper<kAdam>(A, s);
+      hs = s;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      U.w[j].x = multi_update<kAdam>(S, h, U.w[j].x, U.g[j].x, U.m[j].x, U.v[j].x, clip);
+      U.w[j].y = multi_update<kAdam>(S, h, U.w[j].y, U.g[j].y, U.m[j].y, U.v[j].y, clip);
+      U.w[j].z = multi_update<kAdam>(S, h, U.w[j].z, U.g[j].z, U.m[j].z, U.v[j].z, clip);
+      U.w[j].w = multi_update<kAdam>(S, h, U.w[j].w, U.g[j].w, U.m[j].w, U.v[j].w, clip);
+    }
+    U.store(S);
+    // vector form: the head (unit 0) and the tail (last unit) elements, one per thread (tiny segments have both)
+    const int k = u - S.unit0;
+    if (U.vec) {
+      const int64_t head = U.base - (int64_t)k * kMultiUnit, t = threadIdx.x;  // head < 4
+      const int64_t tail0 = S.count <= head ? S.count : head + ((S.count - head) & ~(int64_t)3);
+      const bool last = (int64_t)(k + 1) * kMultiUnit >= S.count;
+      for (int pass = 0; pass < 2; ++pass) {
+        const int64_t e = pass == 0 ? (k == 0 && t < head && t < S.count ? t : -1) : (last && tail0 + t < S.count ? tail0 + t : -1);
+        if (e < 0) continue;
+        float mv = (S.m && (kAdam || !S.first)) ? S.m[e] : 0.0f, vv = kAdam ? S.v[e] : 0.0f;
+        S.p[e] = multi_update<kAdam>(S, h, S.p[e], S.g[e], mv, vv, clip);
+        if (S.m) S.m[e] = mv;
+        if (kAdam) S.v[e] = vv;
+      }
+    }
+    u += gridDim.x;
+    if (u >= A.units) break;
+    while (s + 1 < A.n && A.seg[s + 1].unit0 <= u) ++s;
+    U.load(A.seg[s], u - A.seg[s].unit0, A.seg[s].m && (kAdam || !A.seg[s].first));
   }
 }
 
@@ -511,4 +784,100 @@ extern "C" int nnue_confusion_accumulate(const float* logits, const int64_t* lab
   hipLaunchKernelGGL(confusion_kernel, dim3((B + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), logits, labels, B, C, K,
                      reinterpret_cast<unsigned long long*>(confusion));
   return nnue_launch_status("nnue_confusion_accumulate");
+}
+
+// ---- multi-tensor entry points ----
+namespace {
+
+int64_t multi_chunks(int64_t count) { return (count + kMultiChunk - 1) / kMultiChunk; }
+
+// Validates every segment, then packs the tables (kMultiSegs segments per launch) and launches all norm launches before
+// all apply launches on `stream`.  m / v / steps / first / a / b / eps may be NULL where the form does not use them.
+template <bool kAdam>
+int multi_step(const char* what, float* const* params, float* const* grads, float* const* m, float* const* v, int32_t* const* steps,
+               const int64_t* counts, int n, const float* lr, const float* a, const float* b, const float* eps, const float* wd,
+               const int32_t* first, float max_norm, float* norm_out, void* scratch, int64_t scratch_bytes, const float* lr_dev,
+               nnue_stream_t stream) {
+  NNUE_REQUIRE(n > 0, NNUE_E_ARG, "%s: n = %d must be positive", what, n);
+  NNUE_REQUIRE(params && grads && counts && lr && a && wd && scratch && (kAdam ? (m && v && steps && b && eps) : first != nullptr),
+               NNUE_E_ARG, "%s: null pointer", what);
+  int64_t nparts = 0;
+  for (int i = 0; i < n; ++i) {
+    NNUE_REQUIRE(params[i] && grads[i], NNUE_E_ARG, "%s: null pointer (segment %d)", what, i);
+    NNUE_REQUIRE(counts[i] > 0 && counts[i] <= ((int64_t)1 << 40), NNUE_E_ARG, "%s: count %lld of segment %d out of range", what,
+                 (long long)counts[i], i);
+    if (kAdam) {
+      NNUE_REQUIRE(m[i] && v[i] && steps[i], NNUE_E_ARG, "%s: null pointer (segment %d)", what, i);
+      NNUE_REQUIRE(a[i] >= 0.f && a[i] < 1.f && b[i] >= 0.f && b[i] < 1.f && eps[i] > 0.f, NNUE_E_ARG,
+                   "%s: betas must be in [0,1) and eps > 0 (segment %d)", what, i);
+    } else {
+      NNUE_REQUIRE(a[i] == 0.0f || (m && m[i]), NNUE_E_ARG, "%s: momentum %g needs a momentum buffer (segment %d)", what, a[i], i);
+    }
+    nparts += multi_chunks(counts[i]);
+  }
+  NNUE_REQUIRE(nparts < ((int64_t)1 << 28), NNUE_E_ARG, "%s: %lld elements in all: too many", what, (long long)nparts * kMultiChunk);
+  NNUE_REQUIRE(scratch_bytes >= nnue_multi_optim_scratch(counts, n), NNUE_E_SCRATCH, "%s: scratch %lld < %lld bytes", what,
+               (long long)scratch_bytes, (long long)nnue_multi_optim_scratch(counts, n));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const bool need_norm = max_norm > 0.0f || norm_out;
+  MultiArgs A{};
+  A.partial = static_cast<float*>(scratch);
+  A.lr_dev = lr_dev;
+  A.nparts = (int32_t)nparts;
+  A.need_norm = need_norm;
+  A.max_norm = max_norm;
+  auto pack = [&](int base, int part_base) {  // segments [base, base + kMultiSegs) into A
+    A.seg_base = base;
+    A.part_base = part_base;
+    A.n = n - base < kMultiSegs ? n - base : kMultiSegs;
+    A.chunks = A.units = 0;
+    for (int i = 0; i < A.n; ++i) {
+      const int j = base + i;
+      MultiSeg& S = A.seg[i];
+      const bool has_m = kAdam || a[j] != 0.0f;
+      S = MultiSeg{params[j], grads[j], has_m ? m[j] : nullptr, kAdam ? v[j] : nullptr, kAdam ? steps[j] : nullptr, counts[j],
+                   A.chunks, A.units, lr[j], a[j], kAdam ? b[j] : 0.0f, wd[j], kAdam ? eps[j] : 0.0f, kAdam ? 0 : first[j]};
+      A.chunks += (int32_t)multi_chunks(counts[j]);
+      A.units += (int32_t)((counts[j] + kMultiUnit - 1) / kMultiUnit);
+    }
+  };
+  if (need_norm || kAdam) {
+    for (int base = 0, part = 0; base < n; base += kMultiSegs) {
+      pack(base, part);
+      part += A.chunks;
+      A.norm_out = nullptr;
+      hipLaunchKernelGGL(multi_sqnorm_kernel, dim3(need_norm ? A.chunks : 1), dim3(256), 0, s, A);
+    }
+  }
+  for (int base = 0; base < n; base += kMultiSegs) {
+    pack(base, 0);
+    A.norm_out = base == 0 ? norm_out : nullptr;
+    hipLaunchKernelGGL(multi_apply_kernel<kAdam>, dim3(A.units < kMultiApplyBlocks ? A.units : kMultiApplyBlocks), dim3(256), 0, s, A);
+  }
+  return nnue_launch_status(what);
+}
+
+}  // namespace
+
+extern "C" int64_t nnue_multi_optim_scratch(const int64_t* counts, int n) {
+  if (!counts || n <= 0) return 0;
+  int64_t parts = 0;
+  for (int i = 0; i < n; ++i) parts += counts[i] > 0 ? multi_chunks(counts[i]) : 0;
+  return nnue_round_up(parts * (int64_t)sizeof(float), 256);
+}
+
+extern "C" int nnue_multi_sgd_step(float* const* params, float* const* grads, float* const* momentum_bufs, const int64_t* counts, int n,
+                                   const float* lr, const float* momentum, const float* weight_decay, const int32_t* first_step,
+                                   float max_norm, float* norm_out, void* scratch, int64_t scratch_bytes, const float* lr_dev,
+                                   nnue_stream_t stream) {
+  return multi_step<false>("nnue_multi_sgd_step", params, grads, momentum_bufs, nullptr, nullptr, counts, n, lr, momentum, nullptr,
+                           nullptr, weight_decay, first_step, max_norm, norm_out, scratch, scratch_bytes, lr_dev, stream);
+}
+
+extern "C" int nnue_multi_adam_step(float* const* params, float* const* grads, float* const* exp_avgs, float* const* exp_avg_sqs,
+                                    int32_t* const* step_counters, const int64_t* counts, int n, const float* lr, const float* beta1,
+                                    const float* beta2, const float* eps, const float* weight_decay, float max_norm, float* norm_out,
+                                    void* scratch, int64_t scratch_bytes, const float* lr_dev, nnue_stream_t stream) {
+  return multi_step<true>("nnue_multi_adam_step", params, grads, exp_avgs, exp_avg_sqs, step_counters, counts, n, lr, beta1, beta2, eps,
+                          weight_decay, nullptr, max_norm, norm_out, scratch, scratch_bytes, lr_dev, stream);
 }
