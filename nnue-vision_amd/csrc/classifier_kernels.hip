@@ -19,12 +19,17 @@ namespace {
 
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
+// ReLU, or clamp(0, clip) when clip > 0, keeping a NaN as torch.relu / torch.clamp do (fmaxf / fminf would drop it)
 __device__ __forceinline__ float act_fn(float z, float clip) {
-  const float r = fmaxf(z, 0.0f);
-  return clip > 0.0f ? fminf(r, clip) : r;
+  const float r = z <= 0.0f ? 0.0f : z;
+  return (clip > 0.0f && r > clip) ? clip : r;
 }
-__device__ __forceinline__ float gate_fn(float h, float clip) {
-  return (h > 0.0f && (clip <= 0.0f || h < clip)) ? 1.0f : 0.0f;
+// d passed back through act_fn where it produced h, as torch's autograd does: relu's gradient is blocked only where
+// h <= 0 (a NaN h passes it), clamp's is kept only inside the range (a NaN h blocks it).  A select, not a product, so a
+// blocked NaN gradient becomes 0 as in torch.  (torch's clamp also passes the gradient at z == 0 and z == clip.)
+__device__ __forceinline__ float gate_fn(float d, float h, float clip) {
+  if (clip > 0.0f) return (h > 0.0f && h < clip) ? d : 0.0f;
+  return h <= 0.0f ? 0.0f : d;
 }
 
 // element k of the (virtual) l0 row built from x row `xr`
@@ -475,7 +480,7 @@ __global__ __launch_bounds__(128) void tail_backward_kernel(const float* __restr
   for (int j = tid; j < L3; j += 128) {
     float s = 0.f;
     for (int c = 0; c < C; ++c) s = fmaf(dls[c], w3[(size_t)c * L3 + j], s);
-    const float v = s * gate_fn(h2[(size_t)b * L3 + j], clip);
+    const float v = gate_fn(s, h2[(size_t)b * L3 + j], clip);
     dz2s[j] = v;
     d_z2[(size_t)b * L3 + j] = v;
   }
@@ -483,7 +488,7 @@ __global__ __launch_bounds__(128) void tail_backward_kernel(const float* __restr
   for (int k = tid; k < L2; k += 128) {
     float s = 0.f;
     for (int j = 0; j < L3; ++j) s = fmaf(dz2s[j], w2[(size_t)j * L2 + k], s);
-    d_z1[(size_t)b * L2 + k] = s * gate_fn(h1[(size_t)b * L2 + k], clip);
+    d_z1[(size_t)b * L2 + k] = gate_fn(s, h1[(size_t)b * L2 + k], clip);
   }
 }
 
@@ -667,7 +672,7 @@ __global__ __launch_bounds__(NT) void tail_train_kernel(const float* __restrict_
     se = block_reduce_nt<NT>(se, false, red);
   }
   const bool ok = y >= 0 && y < C;
-  if (tid == 0) sample_loss[b] = ok ? (mx + logf(se)) - lgs[y] : 0.0f;
+  if (tid == 0) sample_loss[b] = ok ? nnue_ce_sample_loss(mx, lgs[y], se) : 0.0f;
   const float inv = 1.0f / se;
   __syncthreads();  // every thread has read lgs[y] / the logits it needs before they are overwritten
   for (int c = tid; c < C; c += NT) {
@@ -702,7 +707,7 @@ __global__ __launch_bounds__(NT) void tail_train_kernel(const float* __restrict_
       for (int w = 1; w < S; w *= 2)  // fixed pairwise tree: (p0 + p1) + (p2 + p3) ...
 #pragma unroll
         for (int i = 0; i + w < S; i += 2 * w) q[i] += q[i + w];
-      const float v = q[0] * gate_fn(h2s[j], clip);
+      const float v = gate_fn(q[0], h2s[j], clip);
       dz2s[j] = v;
       d_z2[(size_t)b * L3 + j] = v;
     }
@@ -719,7 +724,7 @@ __global__ __launch_bounds__(NT) void tail_train_kernel(const float* __restrict_
       for (int u = 0; u < 16; ++u) s = fmaf(dz2s[j + u], w[u], s);
     }
     for (; j < L3; ++j) s = fmaf(dz2s[j], w2[(size_t)j * L2 + k], s);
-    const float v = s * gate_fn(h1s[k], clip);
+    const float v = gate_fn(s, h1s[k], clip);
     d_z1[(size_t)b * L2 + k] = v;
     if (d_z1_g) d_z1_g[(size_t)g * L2 + k] = v;
   }

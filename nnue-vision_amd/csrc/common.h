@@ -33,6 +33,11 @@ constexpr int kWave = 64;  // CDNA4 wavefront
 // accumulates into the same buffer was observed not to be ordered reliably before that kernel on this stack (ROCm 7.0:
 // replayed training steps of the id-list path read stale values), so nothing in a capturable path uses memset nodes.
 #ifdef __HIPCC__
+// Per-sample softmax cross-entropy from the row maximum mx, the label's logit z_y and se = sum exp(z - mx).  Formed as
+// (mx - z_y) + log(se): exact to a few ulp of the loss itself, where (mx + log(se)) - z_y rounds at the scale of the
+// logits.  Shared by the stand-alone loss (optim_kernels.hip) and the fused classifier step (classifier_kernels.hip).
+__device__ __forceinline__ float nnue_ce_sample_loss(float mx, float z_y, float se) { return (mx - z_y) + logf(se); }
+
 namespace {
 __global__ __launch_bounds__(256) void nnue_zero_floats_kernel(float* __restrict__ dst, size_t count) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;

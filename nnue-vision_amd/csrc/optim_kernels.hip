@@ -36,8 +36,7 @@ __global__ __launch_bounds__(256) void cross_entropy_kernel(const float* __restr
   se = wave_sum(se);
   const int64_t y = labels[b];
   const bool ok = y >= 0 && y < C;
-  // (max - z_y) + log(se): exact to a few ulp of the loss itself; (max + log(se)) - z_y rounds at the scale of the logits
-  if (lane == 0) sample_loss[b] = ok ? (mx - z[y]) + logf(se) : 0.0f;
+  if (lane == 0) sample_loss[b] = ok ? nnue_ce_sample_loss(mx, z[y], se) : 0.0f;
   if (d_logits) {
     const float inv = 1.0f / se;
     for (int c = lane; c < C; c += 64) {
