@@ -40,7 +40,7 @@
 extern "C" {
 #endif
 
-#define NNUE_HIP_ABI_VERSION 32
+#define NNUE_HIP_ABI_VERSION 33
 
 #define NNUE_OK 0
 #define NNUE_E_ARG (-1)     /* null pointer, non-positive size, bad alignment */
@@ -115,10 +115,9 @@ int nnue_ste_conv_backward(const float* images, const float* conv_out, const flo
                            int stages, nnue_stream_t stream);
 /* The same sums (nnue.py:28-54; autograd of the conv at nnue.py:640) from the im2col form of the images that
  * nnue_ftm_conv_binarize_patches leaves: patches [27][B*Gh*Gw] f32, term-major, read coalesced along positions instead of pixels
- * gathered at the conv stride.  conv_out (needed only inside the threshold term's sigmoid) is read when given; with conv_out NULL
- * it is re-formed from the patches and `weight` [fps][27] with the forward's own fmaf chain.  Either way d_thr, d_weight and the
- * stage-1 partials are BITWISE those of nnue_ste_conv_backward.  fps <= 64. */
-int nnue_ste_conv_backward_patches(const float* patches, const float* weight, const float* conv_out, const float* thr,
+ * gathered at the conv stride, and conv_out (required).  d_thr, d_weight and the stage-1 partials are BITWISE those of
+ * nnue_ste_conv_backward.  fps <= 64. */
+int nnue_ste_conv_backward_patches(const float* patches, const float* conv_out, const float* thr,
                                    const float* d_conv_out, int B, int fps, int Gh, int Gw,
                                    float* d_thr, float* d_weight, void* scratch, int64_t scratch_bytes,
                                    int stages, nnue_stream_t stream);
@@ -228,9 +227,8 @@ int nnue_ftm_conv_binarize(const float* images, const float* weight, const float
                            nnue_stream_t stream);
 /* The same launch (nnue.py:640, :646-647, :19-25) also leaving the im2col form of the images for the backward:
  * patches[q][b*Gh*Gw + hw] = the pixel under tap q = ci*9 + kh*3 + kw of position hw (0 where the tap falls off the image),
- * 27*B*Gh*Gw floats.  conv_out may be NULL (not written): with a stride above 3 the taps of neighbouring positions do not
- * overlap, the patches are a fraction of the images (0.18 at 224x224, stride 7) and the training step needs conv_out only
- * where nnue_ste_conv_backward_patches re-forms it.  bits, n, sink (and conv_out when given) are bitwise nnue_ftm_conv_binarize's. */
+ * 27*B*Gh*Gw floats: with a stride above 3 the taps of neighbouring positions do not overlap and the patches are a fraction of
+ * the images (0.18 at 224x224, stride 7).  conv_out is required.  conv_out, bits, n and sink are bitwise nnue_ftm_conv_binarize's. */
 int nnue_ftm_conv_binarize_patches(const float* images, const float* weight, const float* thr, int B, int H, int W,
                                    int fps, int stride, int F, float* patches, float* conv_out, uint8_t* bits,
                                    int32_t* n, float* sink, nnue_stream_t stream);
@@ -261,11 +259,9 @@ int nnue_ftm_backward_weight(const uint8_t* bits, const float* sink, const float
  *   d_conv_out[b,p] = active(b,p) ? < d_out[b,:], weight[min(p,F-1),:] > : 0     for every p < P */
 int nnue_ftm_backward_values(const uint8_t* bits, const float* d_out, const float* weight,
                              int B, int F, int P, int L1, float* d_conv_out, nnue_stream_t stream);
-/* nnue_ftm_backward_values with a workspace (same result contract: autograd of nnue.py:702-708 and :628-633 -- the gradient
- * reaches the map at active positions only).  For big maps the workspace lets d_out be split ONCE per launch into its three
- * bf16 planes, staged by LDS-DMA, while the table's fragments go straight to registers (csrc/ftv_kernels.hip);
- * nnue_ftm_backward_values_scratch returns the bytes needed (0: this shape runs the workspace-free kernels, scratch may be
- * NULL).  Too little workspace for a shape that needs one: NNUE_E_SCRATCH. */
+/* nnue_ftm_backward_values (autograd of nnue.py:702-708 and :628-633), argument checks and result included, under a
+ * workspace-taking signature.  No shape needs a workspace: nnue_ftm_backward_values_scratch returns 0 and scratch may be
+ * NULL.  The entry point exists because callers time the value gradient by this name. */
 int64_t nnue_ftm_backward_values_scratch(int B, int F, int P, int L1);
 int nnue_ftm_backward_values_ws(const uint8_t* bits, const float* d_out, const float* weight, int B, int F, int P, int L1,
                                 float* d_conv_out, void* scratch, int64_t scratch_bytes, nnue_stream_t stream);

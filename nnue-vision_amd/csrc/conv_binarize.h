@@ -28,11 +28,10 @@ struct ConvParamsPlain {
 // the few-channel maps whose workgroups are latency-bound anyway); otherwise nine taps per unrolled pass (60 registers: the
 // 64-channel map of the 224x224 shape is occupancy-bound, 28.9 -> 26.4 us).
 // `patches` (or NULL): the im2col form of the images, [27][B * G] f32 term-major (patches[q][b * G + hw] = the pixel under tap q of
-// position hw, 0 where the tap falls off the image) -- what nnue_ste_conv_backward_patches reads instead of the images and of
-// conv_out; `out` may then be NULL (conv_out is not written: at stride 7 a 224x224 image is 5.4x its patches, and conv_out is
-// 2.4x them again).
-// (kPatch / kOut are compile-time: as runtime pointers tests they cost the few-channel variant 7.6 -> 12.7 us at batch 1024.)
-template <bool kFullUnroll, bool kPatch, bool kOut, class Params, class Staged>
+// position hw, 0 where the tap falls off the image) -- what nnue_ste_conv_backward_patches reads instead of the images (at stride
+// 7 a 224x224 image is 5.4x its patches).
+// (kPatch is compile-time: as a runtime pointer test it costs the few-channel variant 7.6 -> 12.7 us at batch 1024.)
+template <bool kFullUnroll, bool kPatch, class Params, class Staged>
 __device__ __forceinline__ void conv_binarize_body(const float* __restrict__ img, Params& prm, float* __restrict__ out,
                                                    uint8_t* __restrict__ bits, int* __restrict__ n, float* __restrict__ sink, int H, int W,
                                                    int fps, int stride, int Gh, int Gw, int F, int slices, int bx, int by,
@@ -109,7 +108,7 @@ __device__ __forceinline__ void conv_binarize_body(const float* __restrict__ img
           const int p = (c0 + u) * G + hw;
           const size_t o = (size_t)b * fps * G + p;
           const bool on = acc[u] > thr_lds[c0 + u];
-          if constexpr (kOut) out[o] = acc[u];
+          out[o] = acc[u];
           bits[o] = on ? 1 : 0;
           cnt += on;
           snk += on && p >= F - 1;

@@ -60,7 +60,7 @@ __global__ __launch_bounds__(256) void conv3x3_forward_kernel(const float* __res
 // MFMA FeatureTransformer path): conv_binarize.h.  grid (B, slices).
 #include "conv_binarize.h"
 
-template <bool kFullUnroll, bool kPatch = false, bool kOut = true>
+template <bool kFullUnroll, bool kPatch = false>
 __global__ __launch_bounds__(256) void conv_binarize_kernel(const float* __restrict__ img, const float* __restrict__ w,
                                                             const float* __restrict__ thr, float* __restrict__ out,
                                                             uint8_t* __restrict__ bits, int* __restrict__ n,
@@ -68,8 +68,8 @@ __global__ __launch_bounds__(256) void conv_binarize_kernel(const float* __restr
                                                             int Gh, int Gw, int F, int slices, float* __restrict__ patches) {
   extern __shared__ __attribute__((aligned(16))) float w_lds[];
   ConvParamsPlain prm{w, thr};
-  conv_binarize_body<kFullUnroll, kPatch, kOut>(img, prm, out, bits, n, sink, H, W, fps, stride, Gh, Gw, F, slices, (int)blockIdx.x, (int)blockIdx.y,
-                                                w_lds, [] {}, patches, (size_t)gridDim.x * Gh * Gw);
+  conv_binarize_body<kFullUnroll, kPatch>(img, prm, out, bits, n, sink, H, W, fps, stride, Gh, Gw, F, slices, (int)blockIdx.x, (int)blockIdx.y,
+                                          w_lds, [] {}, patches, (size_t)gridDim.x * Gh * Gw);
 }
 
 // ------------------------------------------------------------------ binarise + compact
@@ -214,10 +214,8 @@ constexpr int kSteLd = 68;      // LDS row stride in floats: 16 B aligned, rows 
 constexpr int kSteMaxBlocks = 1024;
 
 // kPatch: the patch terms come from the im2col buffer nnue_ftm_conv_binarize_patches wrote (`img` = patches [27][B * G], coalesced
-// along positions, instead of pixels gathered at the conv stride) and conv_out -- needed only inside the threshold term's
-// sigmoid -- is re-formed from the staged patch tile with the forward's own fmaf chain (`conv_out` = the conv weights [fps][27]):
-// bitwise the same numbers, 48 MB read per launch at the 224x224 shape instead of 160 MB.
-template <int MT, bool kPatch = false, bool kReform = false>  // 16-channel tiles, fps <= 16 * MT; kReform: conv_out = the conv weights
+// along positions, instead of pixels gathered at the conv stride): bitwise the same numbers.
+template <int MT, bool kPatch = false>  // 16-channel tiles, fps <= 16 * MT
 __global__ __launch_bounds__(256) void ste_conv_backward_mfma(const float* __restrict__ img,
                                                               const float* __restrict__ conv_out,
                                                               const float* __restrict__ thr,
@@ -252,7 +250,7 @@ __global__ __launch_bounds__(256) void ste_conv_backward_mfma(const float* __res
       if (abl & 2) { dv[j] = 1.0f; cvv[j] = 0.5f; continue; }
 #endif
       dv[j] = (ok && c < fps) ? d_conv_out[o] : 0.0f;
-      if constexpr (!kReform) cvv[j] = (ok && c < fps) ? conv_out[o] : 0.0f;
+      cvv[j] = (ok && c < fps) ? conv_out[o] : 0.0f;
     }
     const int h = hw / Gw, x = hw - h * Gw;
 #pragma unroll
@@ -289,10 +287,8 @@ __global__ __launch_bounds__(256) void ste_conv_backward_mfma(const float* __res
     for (int j = 0; j < MT * 4; ++j) {
       const int c = wave + 4 * j;
       if (c < fps) {
-        if constexpr (!kReform) {
-          const float s = 1.0f / (1.0f + __expf(-kSteSharpness * (cvv[j] - thr[c])));  // scalar load, cached
-          tacc[j] = fmaf(dv[j], (kSteSharpness * s) * (1.0f - s), tacc[j]);
-        }
+        const float s = 1.0f / (1.0f + __expf(-kSteSharpness * (cvv[j] - thr[c])));  // scalar load, cached
+        tacc[j] = fmaf(dv[j], (kSteSharpness * s) * (1.0f - s), tacc[j]);
         d_lds[c][lane] = dv[j];
       }
     }
@@ -302,25 +298,6 @@ __global__ __launch_bounds__(256) void ste_conv_backward_mfma(const float* __res
       if (qq < 27) p_lds[qq][lane] = pv[rr];
     }
     __syncthreads();
-    if constexpr (kReform) {
-      // conv_out of this lane's position for the wave's channels: conv3x3's fmaf chain (q ascending from zero) over the staged
-      // patch column; the weights are wave-uniform (scalar loads)
-      float pq[27];
-#pragma unroll
-      for (int qq = 0; qq < 27; ++qq) pq[qq] = p_lds[qq][lane];
-#pragma unroll
-      for (int j = 0; j < MT * 4; ++j) {
-        const int c = wave + 4 * j;
-        if (c < fps) {
-          const float* __restrict__ wc = conv_out + c * 27;
-          float cv = 0.0f;
-#pragma unroll
-          for (int qq = 0; qq < 27; ++qq) cv = fmaf(pq[qq], wc[qq], cv);
-          const float s = 1.0f / (1.0f + __expf(-kSteSharpness * (cv - thr[c])));
-          tacc[j] = fmaf(dv[j], (kSteSharpness * s) * (1.0f - s), tacc[j]);
-        }
-      }
-    }
     const int k0 = 16 * wave + 4 * q;
     const float4 b0 = *reinterpret_cast<const float4*>(&p_lds[r][k0]);
     const float4 b1 = *reinterpret_cast<const float4*>(&p_lds[16 + r][k0]);
@@ -512,7 +489,7 @@ extern "C" int nnue_conv3x3_forward(const float* images, const float* weight, fl
 namespace {
 int conv_binarize_impl(const char* who, const float* images, const float* weight, const float* thr, int B, int H, int W, int fps, int stride, int F,
                        float* conv_out, float* patches, uint8_t* bits, int32_t* n, float* sink, nnue_stream_t stream) {
-  NNUE_REQUIRE(images && weight && thr && (conv_out || patches) && bits && n && sink, NNUE_E_ARG, "%s: null pointer", who);
+  NNUE_REQUIRE(images && weight && thr && conv_out && bits && n && sink, NNUE_E_ARG, "%s: null pointer", who);
   NNUE_REQUIRE(B > 0 && H > 0 && W > 0 && fps > 0 && stride > 0 && F > 0, NNUE_E_ARG, "%s: B=%d H=%d W=%d fps=%d stride=%d F=%d must be positive", who,
                B, H, W, fps, stride, F);
   NNUE_REQUIRE(((fps + 7) & ~7) * 28 * 4 <= 64 * 1024, NNUE_E_SHAPE, "%s: fps=%d too large for the LDS weight tile", who, fps);
@@ -529,17 +506,15 @@ int conv_binarize_impl(const char* who, const float* images, const float* weight
   slices = slices < 1 ? 1 : (slices > 16 ? 16 : slices);
   if (slices > 1) nnue_zero_counters(n, sink, B, s);  // a kernel, not a memset node (common.h)
   const size_t lds = (size_t)(((fps + 7) & ~7) * 28) * sizeof(float);
-#define NNUE_CONV_LAUNCH(FULL, PATCH, OUT)                                                                                                      \
-  hipLaunchKernelGGL((conv_binarize_kernel<FULL, PATCH, OUT>), dim3(B, slices), dim3(threads), lds, s, images, weight, thr, conv_out, bits, n, sink, H, \
+#define NNUE_CONV_LAUNCH(FULL, PATCH)                                                                                                           \
+  hipLaunchKernelGGL((conv_binarize_kernel<FULL, PATCH>), dim3(B, slices), dim3(threads), lds, s, images, weight, thr, conv_out, bits, n, sink, H, \
                      W, fps, stride, Gh, Gw, F, slices, patches)
   if (fps <= 16) {
-    if (!patches) NNUE_CONV_LAUNCH(true, false, true);
-    else if (conv_out) NNUE_CONV_LAUNCH(true, true, true);
-    else NNUE_CONV_LAUNCH(true, true, false);
+    if (!patches) NNUE_CONV_LAUNCH(true, false);
+    else NNUE_CONV_LAUNCH(true, true);
   } else {
-    if (!patches) NNUE_CONV_LAUNCH(false, false, true);
-    else if (conv_out) NNUE_CONV_LAUNCH(false, true, true);
-    else NNUE_CONV_LAUNCH(false, true, false);
+    if (!patches) NNUE_CONV_LAUNCH(false, false);
+    else NNUE_CONV_LAUNCH(false, true);
   }
 #undef NNUE_CONV_LAUNCH
   return nnue_launch_status(who);
@@ -549,7 +524,6 @@ int conv_binarize_impl(const char* who, const float* images, const float* weight
 extern "C" int nnue_ftm_conv_binarize(const float* images, const float* weight, const float* thr, int B, int H, int W, int fps,
                                       int stride, int F, float* conv_out, uint8_t* bits, int32_t* n, float* sink,
                                       nnue_stream_t stream) {
-  NNUE_REQUIRE(conv_out, NNUE_E_ARG, "nnue_ftm_conv_binarize: null pointer");
   return conv_binarize_impl("nnue_ftm_conv_binarize", images, weight, thr, B, H, W, fps, stride, F, conv_out, nullptr, bits, n, sink, stream);
 }
 
@@ -592,8 +566,8 @@ extern "C" int64_t nnue_ste_conv_backward_chunks(int B, int fps, int Gh, int Gw)
 }
 
 namespace {
-// patches != NULL: the im2col form (images unused, `weight` needed to re-form conv_out); else pixels + conv_out
-int ste_impl(const char* who, const float* images, const float* conv_out, const float* patches, const float* weight, const float* thr,
+// patches != NULL: the im2col form (images unused); else pixels
+int ste_impl(const char* who, const float* images, const float* conv_out, const float* patches, const float* thr,
              const float* d_conv_out, int B, int H, int W, int fps, int stride, int Gh, int Gw, float* d_thr, float* d_weight, void* scratch,
              int64_t scratch_bytes, int stages, nnue_stream_t stream) {
   NNUE_REQUIRE(d_thr || d_weight, NNUE_E_ARG, "%s: both outputs are null", who);
@@ -613,12 +587,9 @@ int ste_impl(const char* who, const float* images, const float* conv_out, const 
     if (stages & 1) {
 #define NNUE_STE_LAUNCH(MT)                                                                                                          \
   do {                                                                                                                               \
-    if (patches && conv_out)                                                                                                         \
-      hipLaunchKernelGGL((ste_conv_backward_mfma<MT, true, false>), dim3(chunks), dim3(256), 0, s, patches, conv_out, thr, d_conv_out, B, H, W, \
+    if (patches)                                                                                                                     \
+      hipLaunchKernelGGL((ste_conv_backward_mfma<MT, true>), dim3(chunks), dim3(256), 0, s, patches, conv_out, thr, d_conv_out, B, H, W,  \
                          fps, stride, Gh, Gw, tiles, partial, abl);                                                                  \
-    else if (patches)                                                                                                                \
-      hipLaunchKernelGGL((ste_conv_backward_mfma<MT, true, true>), dim3(chunks), dim3(256), 0, s, patches, weight, thr, d_conv_out, B, H, W, fps, \
-                         stride, Gh, Gw, tiles, partial, abl);                                                                       \
     else                                                                                                                             \
       hipLaunchKernelGGL((ste_conv_backward_mfma<MT, false>), dim3(chunks), dim3(256), 0, s, images, conv_out, thr, d_conv_out, B, H, W, \
                          fps, stride, Gh, Gw, tiles, partial, abl);                                                                  \
@@ -653,17 +624,17 @@ extern "C" int nnue_ste_conv_backward(const float* images, const float* conv_out
   NNUE_REQUIRE(B > 0 && H > 0 && W > 0 && fps > 0 && stride > 0, NNUE_E_ARG,
                "nnue_ste_conv_backward: B=%d H=%d W=%d fps=%d stride=%d must be positive", B, H, W, fps, stride);
   const int Gh = (H - 1) / stride + 1, Gw = (W - 1) / stride + 1;
-  return ste_impl("nnue_ste_conv_backward", images, conv_out, nullptr, nullptr, thr, d_conv_out, B, H, W, fps, stride, Gh, Gw, d_thr, d_weight,
+  return ste_impl("nnue_ste_conv_backward", images, conv_out, nullptr, thr, d_conv_out, B, H, W, fps, stride, Gh, Gw, d_thr, d_weight,
                   scratch, scratch_bytes, stages, stream);
 }
 
-extern "C" int nnue_ste_conv_backward_patches(const float* patches, const float* weight, const float* conv_out, const float* thr,
+extern "C" int nnue_ste_conv_backward_patches(const float* patches, const float* conv_out, const float* thr,
                                               const float* d_conv_out, int B, int fps, int Gh, int Gw, float* d_thr, float* d_weight,
                                               void* scratch, int64_t scratch_bytes, int stages, nnue_stream_t stream) {
-  NNUE_REQUIRE(patches && (weight || conv_out) && thr && d_conv_out && scratch, NNUE_E_ARG, "nnue_ste_conv_backward_patches: null pointer");
+  NNUE_REQUIRE(patches && conv_out && thr && d_conv_out && scratch, NNUE_E_ARG, "nnue_ste_conv_backward_patches: null pointer");
   NNUE_REQUIRE(B > 0 && fps > 0 && Gh > 0 && Gw > 0, NNUE_E_ARG, "nnue_ste_conv_backward_patches: B=%d fps=%d Gh=%d Gw=%d must be positive", B, fps,
                Gh, Gw);
-  return ste_impl("nnue_ste_conv_backward_patches", nullptr, conv_out, patches, weight, thr, d_conv_out, B, 0, 0, fps, 1, Gh, Gw, d_thr, d_weight,
+  return ste_impl("nnue_ste_conv_backward_patches", nullptr, conv_out, patches, thr, d_conv_out, B, 0, 0, fps, 1, Gh, Gw, d_thr, d_weight,
                   scratch, scratch_bytes, stages, stream);
 }
 

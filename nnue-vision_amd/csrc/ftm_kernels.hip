@@ -22,7 +22,6 @@
 // block; MFMA step t takes element t), which a sum does not care about.  The next K tile's global loads are
 // issued right after the barrier that publishes the current one and stay in flight during its MFMAs.
 #include "common.h"
-#include "ftv_kernels.h"
 #include "small_wgrad.h"
 
 #include <cstdlib>
@@ -1012,10 +1011,7 @@ __device__ __forceinline__ void split8(const u32x4& v0, const u32x4& v1, u32x4& 
 
 // ABL: timing-only ablations for tools/debug (results are WRONG unless 0): 1 no split of A (raw words stored), 2 no split at
 // all, 3 no MFMAs (fragments still read), 4 no staging (no split, no LDS stores), 5 no global loads
-// APL: operand A arrives already split -- ma.p = K-tile-major planes [K / 32][3][M][32] bf16 (hi, mid, lo; ftv_split_planes), KT = 32: three 16-byte loads per 8-k
-// run and no split VALU for it (the d_out planes of nnue_ftm_backward_values_ws).  This kernel is issue-bound (MFMA and VALU issue
-// add up on a SIMD, tools/micro/mfma_bf16_tile.hip), and two thirds of its split work is the same d_out rows in every workgroup.
-template <int BM, int BN, class Epi, int KT = kBf6K, int ABL = 0, bool APL = false>
+template <int BM, int BN, class Epi, int KT = kBf6K, int ABL = 0>
 __device__ __forceinline__ void gemm_tile_bf6(unsigned char* __restrict__ smem, const Mat& ma, const Mat& mb, const Epi& epi, int M, int N,
                                               int k_lo, int k_hi, int tiles_n, int tile, int ks) {
   static_assert((BM == 32 || BM == 64 || BM == 128) && (BN == 64 || BN == 128), "tile shapes");
@@ -1035,7 +1031,7 @@ __device__ __forceinline__ void gemm_tile_bf6(unsigned char* __restrict__ smem, 
   constexpr int GA = BM * RUNS / 256, GB = BN * RUNS / 256;  // 8-k runs per thread
   static_assert(GA >= 1 && GB >= 1, "every thread stages at least one run of each operand");
   const bool stream_b = mb.bytes > (64u << 20);        // uniform: a table larger than the caches is read non-temporally
-  u32x4 ra[GA][APL ? 3 : 2], rb[GB][2];
+  u32x4 ra[GA][2], rb[GB][2];
   auto fetch = [&](int k0) {
     if constexpr (ABL == 5) {
       if (k0 != k_lo) return;
@@ -1043,15 +1039,8 @@ __device__ __forceinline__ void gemm_tile_bf6(unsigned char* __restrict__ smem, 
 #pragma unroll
     for (int i = 0; i < GA; ++i) {
       const int g = tid + 256 * i, row = g / RUNS, k = k0 + (g % RUNS) * 8;
-      if constexpr (APL) {  // rows past M re-read row M - 1: their accumulators are never stored
-        const int rr = m_base + row < M ? m_base + row : M - 1;
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl)
-          ra[i][pl] = __builtin_amdgcn_raw_buffer_load_b128(rsa, ((((k >> 5) * 3 + pl) * M + rr) * 32 + (k & 31)) * 2, 0, 0);
-      } else {
-        ra[i][0] = mat_load<false>(rsa, ma, m_base + row, k);
-        ra[i][1] = mat_load<false>(rsa, ma, m_base + row, k + 4);
-      }
+      ra[i][0] = mat_load<false>(rsa, ma, m_base + row, k);
+      ra[i][1] = mat_load<false>(rsa, ma, m_base + row, k + 4);
     }
 #pragma unroll
     for (int i = 0; i < GB; ++i) {
@@ -1073,8 +1062,7 @@ __device__ __forceinline__ void gemm_tile_bf6(unsigned char* __restrict__ smem, 
     for (int i = 0; i < GA; ++i) {
       const int g = tid + 256 * i, row = g / RUNS, c = g % RUNS;
       u32x4 hi, mid, lo;
-      if constexpr (APL) { hi = ra[i][0]; mid = ra[i][1]; lo = ra[i][2]; }
-      else if constexpr (ABL == 1 || ABL == 2) { hi = ra[i][0]; mid = ra[i][1]; lo = ra[i][0] ^ ra[i][1]; }
+      if constexpr (ABL == 1 || ABL == 2) { hi = ra[i][0]; mid = ra[i][1]; lo = ra[i][0] ^ ra[i][1]; }
       else split8(ra[i][0], ra[i][1], hi, mid, lo);
       *reinterpret_cast<u32x4*>(As + bf6_img<KT>(row, c)) = hi;
       *reinterpret_cast<u32x4*>(As + PA + bf6_img<KT>(row, c)) = mid;
@@ -1138,10 +1126,10 @@ __device__ __forceinline__ void gemm_tile_bf6(unsigned char* __restrict__ smem, 
   store_tile<BM, BN, Epi>(reinterpret_cast<float*>(smem), epi, acc, M, N, m_base, n_base, m0, n0, tile, ks);
 }
 
-template <int BM, int BN, class Epi, int KT, int ABL = 0, bool APL = false>
+template <int BM, int BN, class Epi, int KT, int ABL = 0>
 __global__ __launch_bounds__(256) void ftm_gemm_bf6_kernel(Mat ma, Mat mb, Epi epi, int M, int N, int K, int tiles_n) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[gemm_bf6_lds_bytes<BM, BN, KT>()];
-  gemm_tile_bf6<BM, BN, Epi, KT, ABL, APL>(smem, ma, mb, epi, M, N, 0, K, tiles_n, blockIdx.x, 0);
+  gemm_tile_bf6<BM, BN, Epi, KT, ABL>(smem, ma, mb, epi, M, N, 0, K, tiles_n, blockIdx.x, 0);
 }
 
 template <int BM, int BN, bool AKC, class Epi>
@@ -1842,7 +1830,6 @@ extern "C" int nnue_ftm_backward_values(const uint8_t* bits, const float* d_out,
   if (values_bf6(B, P, L1)) {  // the big-map shape: 128 x 64 tiles, six bf16 plane products (147 -> 117 us at the 224x224 shape)
     // K tiles of 32: six images of a 128 x 64 tile are 36 KB and 120 registers -- four workgroups per CU -- 100 us against
     // 115 us with K tiles of 64 (72 KB, two per CU) and 147 us on the f32 MFMA at the 224x224 shape
-    static const int kt = env_int("NNUE_FTM_BF6_KT", 32);  // developer knob
     const dim3 grid((unsigned)(s.tiles_m * s.tiles_n));
 #ifdef NNUE_ABLATIONS  // timing-only ablations (WRONG results), tools/debug: compiled only with NNUE_BUILD_ABLATIONS=1 (csrc/build.py)
     static const int abl = env_int("NNUE_FTM_BF6_ABL", 0);
@@ -1850,62 +1837,20 @@ extern "C" int nnue_ftm_backward_values(const uint8_t* bits, const float* d_out,
     NNUE_ABL(1) NNUE_ABL(2) NNUE_ABL(3) NNUE_ABL(4) NNUE_ABL(5)
 #undef NNUE_ABL
 #endif
-    static const int bn = env_int("NNUE_FTM_BF6_BN", 64);  // developer knob: 128-column tiles stage d_out half as often
-    if (bn == 128) {
-      const int tn = (P + 127) / 128;
-      hipLaunchKernelGGL((ftm_gemm_bf6_kernel<128, 128, ValEpi, 32>), dim3((unsigned)(s.tiles_m * tn)), dim3(256), 0, st, ma, mb, epi, B, P, L1, tn);
-      return nnue_launch_status("nnue_ftm_backward_values");
-    }
-    if (kt == 64) hipLaunchKernelGGL((ftm_gemm_bf6_kernel<128, 64, ValEpi, 64>), grid, dim3(256), 0, st, ma, mb, epi, B, P, L1, s.tiles_n);
-    else hipLaunchKernelGGL((ftm_gemm_bf6_kernel<128, 64, ValEpi, 32>), grid, dim3(256), 0, st, ma, mb, epi, B, P, L1, s.tiles_n);
+    hipLaunchKernelGGL((ftm_gemm_bf6_kernel<128, 64, ValEpi, 32>), grid, dim3(256), 0, st, ma, mb, epi, B, P, L1, s.tiles_n);
     return nnue_launch_status("nnue_ftm_backward_values");
   }
   launch<true, true>(st, s, ma, mb, epi, B, P, L1);
   return nnue_launch_status("nnue_ftm_backward_values");
 }
 
-// The same value gradient with a workspace: big maps take ftv_kernels.hip (d_out split once into bf16 planes in the
-// workspace and staged by LDS-DMA, table fragments straight into registers); every other shape, or a call without enough
-// workspace for it, runs nnue_ftm_backward_values unchanged.
-namespace {
-// the six-plane tile kernel fed with d_out planes from the workspace (K in whole tiles of 32; offsets fit 31 bits)
-bool values_planes(int B, int P, int L1) {
-  // Off by default: measured in the 224x224 step this is SLOWER than splitting d_out in every workgroup (125.6 vs 98.8 us): three
-  // 16-byte plane loads per run instead of two float loads put 1.36x the bytes through the CUs' load path, which is what the tile
-  // kernel waits for -- not its split VALU.  Read per call (tests switch it).
-  const char* e = getenv("NNUE_FTM_VAL_PLANES");
-  return (e ? atoi(e) : 0) && values_bf6(B, P, L1) && L1 % 32 == 0 && (long long)3 * B * L1 * 2 < (1ll << 31);
-}
-}  // namespace
-
-extern "C" int64_t nnue_ftm_backward_values_scratch(int B, int F, int P, int L1) {
-  if (!nnue_ftm_supported(F, P, L1) || !shape_ok(B, F, P, L1)) return 0;
-  if (values_bf6(B, P, L1) && ftv_supported(B, F, P, L1)) return ftv_scratch_bytes(B, L1);
-  return values_planes(B, P, L1) ? ftv_scratch_bytes(B, L1) : 0;
-}
+// The same value gradient, argument checks included, under its workspace-taking name: no shape needs a workspace; the entry
+// point stays because callers time the value gradient by this name.
+extern "C" int64_t nnue_ftm_backward_values_scratch(int /*B*/, int /*F*/, int /*P*/, int /*L1*/) { return 0; }
 
 extern "C" int nnue_ftm_backward_values_ws(const uint8_t* bits, const float* d_out, const float* weight, int B, int F, int P, int L1,
-                                           float* d_conv_out, void* scratch, int64_t scratch_bytes, nnue_stream_t stream) {
-  const int64_t need = nnue_ftm_backward_values_scratch(B, F, P, L1);
-  if (need == 0) return nnue_ftm_backward_values(bits, d_out, weight, B, F, P, L1, d_conv_out, stream);
-  NNUE_REQUIRE(bits && d_out && weight && d_conv_out, NNUE_E_ARG, "nnue_ftm_backward_values_ws: null pointer");
-  NNUE_REQUIRE(scratch && scratch_bytes >= need, NNUE_E_SCRATCH, "nnue_ftm_backward_values_ws: workspace of %lld bytes needed, %lld given",
-               (long long)need, (long long)scratch_bytes);
-  NNUE_REQUIRE(nnue_aligned16(d_out) && nnue_aligned16(weight) && nnue_aligned16(scratch), NNUE_E_ARG,
-               "nnue_ftm_backward_values_ws: pointers must be 16-byte aligned");
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (values_bf6(B, P, L1) && ftv_supported(B, F, P, L1)) {
-    ftv_launch(bits, d_out, weight, B, F, P, L1, d_conv_out, scratch, st);
-    return nnue_launch_status("nnue_ftm_backward_values_ws");
-  }
-  // d_out split once per launch; the 128 x 64 x 32 six-plane tiles take its planes as they are (no split VALU for operand A)
-  ftv_split_planes(d_out, B, L1, scratch, st);
-  const Shape s = plan(B, P, L1, true, false);
-  const Mat ma{scratch, (unsigned)((size_t)3 * B * L1 * 2), L1, kIntMax, L1}, mb{weight, (unsigned)((size_t)F * L1 * 4), L1, F - 1, kIntMax};
-  const ValEpi epi{bits, d_conv_out, P};
-  hipLaunchKernelGGL((ftm_gemm_bf6_kernel<128, 64, ValEpi, 32, 0, true>), dim3((unsigned)(s.tiles_m * s.tiles_n)), dim3(256), 0, st, ma, mb, epi, B, P,
-                     L1, s.tiles_n);
-  return nnue_launch_status("nnue_ftm_backward_values_ws");
+                                           float* d_conv_out, void* /*scratch*/, int64_t /*scratch_bytes*/, nnue_stream_t stream) {
+  return nnue_ftm_backward_values(bits, d_out, weight, B, F, P, L1, d_conv_out, stream);
 }
 
 // Both gradients of the binary-map FeatureTransformer in one launch (see ftm_backward_kernel); falls back to the two

@@ -16,7 +16,7 @@ import torch
 
 _HERE = Path(__file__).resolve().parent
 LIB_PATH = _HERE / "libnnue_hip.so"
-ABI_VERSION = 32
+ABI_VERSION = 33
 
 _c_int, _c_i64, _c_f, _c_p = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
 
@@ -73,8 +73,7 @@ SIGNATURES = {
     "nnue_ftm_conv_binarize": (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p]),
     "nnue_ftm_conv_binarize_patches": (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p,
                                                 _c_p]),
-    "nnue_ste_conv_backward_patches": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p, _c_i64, _c_int,
-                                                _c_p]),
+    "nnue_ste_conv_backward_patches": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p, _c_i64, _c_int, _c_p]),
     "nnue_ftm_forward": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p, _c_i64, _c_p]),
     "nnue_ftm_forward_grouping": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p, _c_i64, _c_p, _c_int,
                                            _c_p, _c_p, _c_p, _c_p, _c_p]),
@@ -415,14 +414,13 @@ def ste_conv_backward(images, conv_out, thr, d_conv_out, stride: int,
     return d_thr, d_weight
 
 
-def ste_conv_backward_patches(patches, weight, thr, d_conv_out, gh: int, gw: int,
+def ste_conv_backward_patches(patches, conv_out, thr, d_conv_out, gh: int, gw: int,
                               d_thr: Optional[torch.Tensor] = None, d_weight: Optional[torch.Tensor] = None,
-                              scratch: Optional[torch.Tensor] = None, stages: int = 3, conv_out: Optional[torch.Tensor] = None):
-    """ste_conv_backward from the im2col form ftm_conv_binarize(patches=...) left (no images; conv_out is read when given,
-    else re-formed from the patches and the conv weights); bitwise the same d_thr / d_weight / partials."""
-    weight = _need(weight, torch.float32, "conv.weight")
-    fps = weight.shape[0]
-    b = d_conv_out.numel() // (fps * gh * gw)
+                              scratch: Optional[torch.Tensor] = None, stages: int = 3):
+    """ste_conv_backward from the im2col form ftm_conv_binarize(patches=...) left in place of the images; bitwise the same
+    d_thr / d_weight / partials."""
+    b, fps = conv_out.shape[:2]
+    conv_out = _need(conv_out, torch.float32, "conv_out", (b, fps, gh, gw))
     patches = _need(patches, torch.float32, "patches", (27, b * gh * gw))
     d_conv_out = _need(d_conv_out, torch.float32, "d_conv_out").view(b, fps, gh, gw)
     thr = _need(thr.reshape(-1), torch.float32, "threshold", (fps,))
@@ -434,9 +432,7 @@ def ste_conv_backward_patches(patches, weight, thr, d_conv_out, gh: int, gw: int
     need = load().nnue_ste_conv_backward_scratch(b, fps, gh, gw)
     if scratch is None:
         scratch = torch.empty((need,), dtype=torch.uint8, device=dev)
-    if conv_out is not None:
-        conv_out = _need(conv_out, torch.float32, "conv_out", (b, fps, gh, gw))
-    _call("nnue_ste_conv_backward_patches", patches.data_ptr(), weight.data_ptr(), _ptr(conv_out), thr.data_ptr(), d_conv_out.data_ptr(), b, fps, gh, gw,
+    _call("nnue_ste_conv_backward_patches", patches.data_ptr(), conv_out.data_ptr(), thr.data_ptr(), d_conv_out.data_ptr(), b, fps, gh, gw,
           d_thr.data_ptr(), d_weight.data_ptr(), scratch.data_ptr(), scratch.numel(), int(stages), _stream(patches))
     return d_thr, d_weight
 
@@ -666,9 +662,7 @@ class FeatureMatrix:
         return FeatureMatrix(torch.empty((batch, positions), dtype=torch.uint8, device=device),
                              torch.empty((batch,), dtype=torch.int32, device=device),
                              torch.empty((batch,), dtype=torch.float32, device=device),
-                             torch.empty((max(16, ftm_scratch_bytes(batch, num_rows, positions, l1),
-                                              int(load().nnue_ftm_backward_values_scratch(batch, num_rows, positions, l1))),),
-                                         dtype=torch.uint8, device=device),
+                             torch.empty((max(16, ftm_scratch_bytes(batch, num_rows, positions, l1)),), dtype=torch.uint8, device=device),
                              positions, num_rows)
 
 
@@ -690,10 +684,10 @@ def ftm_binarize(conv_out: torch.Tensor, thr: torch.Tensor, num_rows: int, l1: i
 
 def ftm_conv_binarize(images: torch.Tensor, weight: torch.Tensor, thr: torch.Tensor, stride: int, num_rows: int, l1: int,
                       conv_out: Optional[torch.Tensor] = None, fm: Optional[FeatureMatrix] = None,
-                      patches: Optional[torch.Tensor] = None, write_conv_out: bool = True):
+                      patches: Optional[torch.Tensor] = None):
     """conv3x3_forward + ftm_binarize in one launch; returns (conv_out, fm), bitwise the two separate calls.
     patches (float32 [27, B*Gh*Gw]): the launch also leaves the im2col form of the images (ste_conv_backward_patches reads
-    it); with write_conv_out=False conv_out is then not written (and None is returned in its place)."""
+    it)."""
     images = _need(images, torch.float32, "images")
     if images.dim() != 4 or images.shape[1] != 3:
         raise ValueError(f"images: expected [B,3,H,W], got {tuple(images.shape)}")
@@ -704,11 +698,7 @@ def ftm_conv_binarize(images: torch.Tensor, weight: torch.Tensor, thr: torch.Ten
         raise ValueError("conv.weight: expected [fps,3,3,3]")
     thr = _need(thr.reshape(-1), torch.float32, "threshold", (fps,))
     gh, gw = conv_out_hw(h, w, stride)
-    if patches is None and not write_conv_out:
-        raise ValueError("ftm_conv_binarize: without conv_out the patches are needed")
-    if not write_conv_out:
-        conv_out = None
-    elif conv_out is None:
+    if conv_out is None:
         conv_out = torch.empty((b, fps, gh, gw), dtype=torch.float32, device=images.device)
     elif tuple(conv_out.shape) != (b, fps, gh, gw):
         raise ValueError("ftm_conv_binarize: conv_out has the wrong shape")
@@ -719,7 +709,7 @@ def ftm_conv_binarize(images: torch.Tensor, weight: torch.Tensor, thr: torch.Ten
     if patches is not None:
         patches = _need(patches, torch.float32, "patches", (27, b * gh * gw))
         _call("nnue_ftm_conv_binarize_patches", images.data_ptr(), weight.data_ptr(), thr.data_ptr(), b, h, w, fps, int(stride), int(num_rows),
-              patches.data_ptr(), _ptr(conv_out), fm.bits.data_ptr(), fm.n.data_ptr(), fm.sink.data_ptr(), _stream(images))
+              patches.data_ptr(), conv_out.data_ptr(), fm.bits.data_ptr(), fm.n.data_ptr(), fm.sink.data_ptr(), _stream(images))
         return conv_out, fm
     _call("nnue_ftm_conv_binarize", images.data_ptr(), weight.data_ptr(), thr.data_ptr(), b, h, w, fps, int(stride), int(num_rows),
           conv_out.data_ptr(), fm.bits.data_ptr(), fm.n.data_ptr(), fm.sink.data_ptr(), _stream(images))
@@ -798,14 +788,9 @@ def ftm_backward_values(d_out: torch.Tensor, weight: torch.Tensor, fm: FeatureMa
         dst = torch.empty((b, fm.positions), dtype=torch.float32, device=d_out.device)
     elif dst.numel() != b * fm.positions:
         raise ValueError("ftm_backward_values: dst has the wrong size")
-    # big maps: d_out is split once into bf16 planes in a workspace (csrc/ftv_kernels.hip) -- the forward's split-K scratch,
-    # free at this point of a step, serves when it is large enough
-    need = int(load().nnue_ftm_backward_values_scratch(b, fm.num_rows, fm.positions, l1))
-    ws = fm.scratch if (need and fm.scratch is not None and fm.scratch.numel() >= need) else None
-    if need and ws is None:
-        ws = fm.scratch = torch.empty((need,), dtype=torch.uint8, device=d_out.device)
+    # the workspace-taking name (no shape needs a workspace): the name the value gradient is timed by
     _call("nnue_ftm_backward_values_ws", fm.bits.data_ptr(), d_out.data_ptr(), weight.data_ptr(), b, fm.num_rows, fm.positions,
-          l1, dst.data_ptr(), _ptr(ws) if need else None, need, _stream(d_out))
+          l1, dst.data_ptr(), None, 0, _stream(d_out))
     return dst
 
 

@@ -218,11 +218,10 @@ class NnueTrainer:
         self.use_mfma, self.use_bits = self.ft_path == "mfma", self.ft_path == "bits"
         self.fm = lib.FeatureMatrix.empty(B, self.P, self.F, self.L1, self.dev) if self.use_mfma else None
         # Large strides (the taps of neighbouring positions do not overlap: 224x224 at stride 7 reads 3 of every 7 rows and the
-        # backward would gather them again): the conv launch leaves the im2col form of the images -- 27 floats per position, 0.18
-        # of the image bytes -- and does not write conv_out; the STE backward reads the patches and re-forms conv_out with the
-        # forward's fmaf chain (bitwise).  NNUE_CONV_PATCHES=0|1|auto (auto: images more than twice their patches).
+        # backward would gather them again): the conv launch also leaves the im2col form of the images -- 27 floats per position,
+        # 0.18 of the image bytes -- and the STE backward reads the patches instead of the images (bitwise).
+        # NNUE_CONV_PATCHES=0|1|auto (auto: images more than twice their patches).
         pm = os.environ.get("NNUE_CONV_PATCHES", "auto")
-        self.reform_conv_out = os.environ.get("NNUE_CONV_REFORM", "0") == "1"  # conv_out not written; the backward re-forms it
         self.use_patches = (self.use_mfma and self.fps <= 64 and pm != "0"
                             and (pm == "1" or 3 * self.H * self.W > 2 * 27 * self.gh * self.gw))
         if self.use_patches:
@@ -302,14 +301,7 @@ class NnueTrainer:
         self._plan_local = self._plan_seg = self._plan_update_first = self._plan_update = None
         self._plan_slot = 0
         self._side = torch.cuda.Stream(device=self.dev) if use_graph else None
-        self._s1 = torch.cuda.Stream(device=self.dev) if use_graph else None
-        self._s2 = torch.cuda.Stream(device=self.dev) if use_graph else None
-        # NNUE_GRAPH_BRANCHES=1 captures the off-critical-path segments on side streams.  Measured on MI355X /
-        # ROCm 7.0 (C2): 0.230 ms/step forked vs 0.175 ms/step as one chain -- the graph's fork/join edges cost
-        # more than the overlap returns, so the default is the linear chain.
-        self.branch = os.environ.get("NNUE_GRAPH_BRANCHES", "0") == "1"
-        # forked capture runs "ft_wgrad" beside "tail", which then must not depend on it
-        self.merge_backward = not self.branch and os.environ.get("NNUE_FTM_SPLIT_BACKWARD", "0") != "1"
+        self.merge_backward = os.environ.get("NNUE_FTM_SPLIT_BACKWARD", "0") != "1"
         # the classifier's first-layer weight gradient rides in the merged FeatureTransformer backward launch (a third
         # tile family reading d_z1 out of the classifier's scratch) where that launch is used
         self.ride_dw1 = (self.use_mfma and self.merge_backward and os.environ.get("NNUE_FTM_RIDE_DW1", "1") != "0"
@@ -446,7 +438,7 @@ class NnueTrainer:
         if name == "front":
             if self.use_mfma:  # conv + {0,1} map + counts in one launch
                 lib.ftm_conv_binarize(self.images, p["conv.weight"], p["visual_threshold"], self.stride, self.F, self.L1,
-                                      conv_out=self.conv_out, fm=self.fm, patches=self.patches, write_conv_out=not (self.use_patches and self.reform_conv_out))
+                                      conv_out=self.conv_out, fm=self.fm, patches=self.patches)
                 return
             lib.conv3x3_forward(self.images, p["conv.weight"], self.stride, out=self.conv_out)
             if self.use_bits:
@@ -509,9 +501,9 @@ class NnueTrainer:
             else:
                 lib.ft_backward_values(self.d_ft, p["input.weight"], self.act, self.P, dst=self.d_conv_out)
             if self.use_patches:
-                lib.ste_conv_backward_patches(self.patches, p["conv.weight"], p["visual_threshold"], self.d_conv_out, self.gh, self.gw,
+                lib.ste_conv_backward_patches(self.patches, self.conv_out, p["visual_threshold"], self.d_conv_out, self.gh, self.gw,
                                               d_thr=g["visual_threshold"], d_weight=g["conv.weight"], scratch=self.ste_scratch,
-                                              stages=1 if self.defer_ste else 3, conv_out=None if self.reform_conv_out else self.conv_out)
+                                              stages=1 if self.defer_ste else 3)
             else:
                 lib.ste_conv_backward(self.images, self.conv_out, p["visual_threshold"], self.d_conv_out, self.stride,
                                       d_thr=g["visual_threshold"], d_weight=g["conv.weight"], scratch=self.ste_scratch,
@@ -567,8 +559,7 @@ class NnueTrainer:
             if next_slot is not None:
                 nxt = self.fm if alt else self.fm_alt
                 lib.ftm_conv_binarize(self.inputs[next_slot][0], self.p["conv.weight"], self.p["visual_threshold"], self.stride, self.F, self.L1,
-                                      conv_out=self.conv_out, fm=nxt, patches=self.patches,
-                                      write_conv_out=not (self.use_patches and self.reform_conv_out))
+                                      conv_out=self.conv_out, fm=nxt, patches=self.patches)
                 lib.ftm_backward_weight_update_forward(fx.g_dft, fx.g_fm, self.p["input.weight"], mom, self.clip_coef, self.lr, self.momentum,
                                                        self.weight_decay, scale, first, nxt, self.p["input.bias"], self.ft, lr_dev=self.lr_dev)
                 return
@@ -603,7 +594,7 @@ class NnueTrainer:
         return [t for t in (self.flat_momentum, self.flat_exp_avg, self.flat_exp_avg_sq, self.adam_step_count) if t is not None]
 
     def _capture(self, fn) -> torch.cuda.CUDAGraph:
-        """Captures fn(main_stream) into a graph; fn may fork work onto self._s1 / self._s2 with events."""
+        """Captures fn(main_stream) into a graph."""
         graph = torch.cuda.CUDAGraph()
         self._side.wait_stream(torch.cuda.current_stream(self.dev))
         with torch.cuda.stream(self._side):
@@ -613,18 +604,16 @@ class NnueTrainer:
         torch.cuda.current_stream(self.dev).wait_stream(self._side)
         return graph
 
-    def _run_local(self, slot: int, part: str, main: torch.cuda.Stream, branch: bool, timers=None, loss=None, alt: bool = False,
+    def _run_local(self, slot: int, part: str, main: torch.cuda.Stream, timers=None, loss=None, alt: bool = False,
                    forward_done: bool = False) -> None:
-        """Launches the local segments of `part` ("all" | "a" | "b").  With `branch` (graph capture) the transposed
-        lists, the FT weight gradient and the classifier weight gradients go to side streams and are joined at
-        the end; otherwise everything is issued in order on `main`.  `loss`: a device scalar that receives the mean loss
-        instead of ``self.loss`` (step_many's per-step results)."""
+        """Launches the local segments of `part` ("all" | "a" | "b") in order on `main`.  `loss`: a device scalar that
+        receives the mean loss instead of ``self.loss`` (step_many's per-step results)."""
         seg = lambda name: self._seg_plan(slot, name, loss, alt)  # noqa: E731
         m = main.cuda_stream
         if forward_done:
             # step_many with the next forward fused into the previous step's table update: this step's map and FeatureTransformer
             # output already exist (alt: in the second map)
-            assert part == "all" and not branch
+            assert part == "all"
             lib.run_plan([c for c in seg("forward") if c[0] != "nnue_ftm_forward"], m, timers)
             for name in ("ft_wgrad", "cls_wgrad", "tail"):
                 lib.run_plan(seg(name), m, timers)
@@ -632,29 +621,10 @@ class NnueTrainer:
         if part == "b":
             lib.run_plan(seg("tail"), m, timers)
             return
-        if not branch:
-            for name in ("front", "transpose", "forward", "ft_wgrad", "cls_wgrad"):
-                lib.run_plan(seg(name), m, timers)
-            if part == "all":
-                lib.run_plan(seg("tail"), m, timers)
-            return
-        s1, s2 = self._s1, self._s2
-        lib.run_plan(seg("front"), m)
-        e0 = torch.cuda.Event()
-        e0.record(main)
-        s1.wait_event(e0)
-        lib.run_plan(seg("transpose"), s1.cuda_stream)
-        lib.run_plan(seg("forward"), m)
-        e1 = torch.cuda.Event()
-        e1.record(main)
-        s1.wait_event(e1)
-        lib.run_plan(seg("ft_wgrad"), s1.cuda_stream)
-        s2.wait_event(e1)
-        lib.run_plan(seg("cls_wgrad"), s2.cuda_stream)
+        for name in ("front", "transpose", "forward", "ft_wgrad", "cls_wgrad"):
+            lib.run_plan(seg(name), m, timers)
         if part == "all":
-            lib.run_plan(seg("tail"), m)
-        main.wait_stream(s1)
-        main.wait_stream(s2)
+            lib.run_plan(seg("tail"), m, timers)
 
     def _plans(self, slot: int = 0):
         """Records the three fixed call sequences once (this also executes them once; the update plans are
@@ -765,7 +735,7 @@ class NnueTrainer:
             for part in parts:
                 if (slot, part) not in self._g_local:
                     self._g_local[(slot, part)] = self._capture(
-                        lambda st, part=part: self._run_local(slot, part, st, branch=self.branch))
+                        lambda st, part=part: self._run_local(slot, part, st))
             if self._g_update is None and upd:
                 self._g_update = self._capture(lambda st: lib.run_plan(upd, st.cuda_stream))
 
@@ -773,13 +743,13 @@ class NnueTrainer:
             if graphs:
                 self._g_local[(slot, part)].replay()
             else:
-                self._run_local(slot, part, main, branch=False, timers=timers)
+                self._run_local(slot, part, main, timers=timers)
 
         if graphs and self.capture_collectives and not first and ragged is None:
             # data parallel, steady state: local kernels + exchange + update are ONE graph
             if (slot, "full_dp") not in self._g_local:
                 def full_dp(st):
-                    self._run_local(slot, "all", st, branch=False)
+                    self._run_local(slot, "all", st)
                     self._exchange_and_update(False)
                 captured = True
                 try:
@@ -800,7 +770,7 @@ class NnueTrainer:
             # single rank, steady state: local step + update are ONE graph (one replay per step)
             if (slot, "full") not in self._g_local:
                 def full(st):
-                    self._run_local(slot, "all", st, branch=self.branch)
+                    self._run_local(slot, "all", st)
                     lib.run_plan(upd, st.cuda_stream)
                 self._g_local[(slot, "full")] = self._capture(full)
             self._g_local[(slot, "full")].replay()
@@ -851,7 +821,7 @@ class NnueTrainer:
         fuse = self.fuse_next_forward and len(slots) > 1 and (not self.dp.collectives or self.factor_exchange)
         for i, s in enumerate(slots):
             alt = fuse and i % 2 == 1
-            self._run_local(s, "all", st, branch=False, timers=timers, loss=ring[i], alt=alt, forward_done=fuse and i > 0)
+            self._run_local(s, "all", st, timers=timers, loss=ring[i], alt=alt, forward_done=fuse and i > 0)
             if self.dp.collectives:
                 with lib.time_calls(timers):
                     self._exchange_and_update(False, alt=alt, next_slot=slots[i + 1] if fuse and i + 1 < len(slots) else None)
@@ -864,8 +834,7 @@ class NnueTrainer:
                 mom = self.flat_momentum[lo:hi] if self.flat_momentum is not None else None
                 with lib.time_calls(timers):
                     lib.ftm_conv_binarize(self.inputs[slots[i + 1]][0], self.p["conv.weight"], self.p["visual_threshold"], self.stride,
-                                          self.F, self.L1, conv_out=self.conv_out, fm=nxt, patches=self.patches,
-                                          write_conv_out=not (self.use_patches and self.reform_conv_out))
+                                          self.F, self.L1, conv_out=self.conv_out, fm=nxt, patches=self.patches)
                     lib.ftm_backward_weight_update_forward(self.d_ft, cur, self.p["input.weight"], mom, self.clip_coef, self.lr, self.momentum,
                                                            self.weight_decay, self.dp.grad_scale, False, nxt, self.p["input.bias"], self.ft,
                                                            lr_dev=self.lr_dev)

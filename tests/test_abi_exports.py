@@ -61,6 +61,11 @@ def test_argument_validation_returns_codes_without_launching():
     assert L.nnue_classifier_forward(p, 1, p, p, p, p, p, p, 0.0, 2, 7, 4, 4, 3, p, p, p, p, 1 << 20, None) == -2
     # momentum without a buffer
     assert L.nnue_sgd_step(p, p, 0, 10, 0.1, 0.9, 0.0, 1.0, 1.0, 1, None, p, 1 << 20, None, 0, 0, None, None, None, 0, 0, 0, None, 0, None, None) == -1
+    # the patch form reads and writes conv_out: NULL is refused
+    assert L.nnue_ftm_conv_binarize_patches(p, p, p, 2, 8, 8, 4, 1, 100, p, None, p, p, p, None) == -1
+    assert b"null pointer" in L.nnue_hip_last_error()
+    assert L.nnue_ste_conv_backward_patches(p, None, p, p, 2, 4, 8, 8, p, p, p, 1 << 20, 3, None) == -1
+    assert b"null pointer" in L.nnue_hip_last_error()
 
 
 def test_scratch_queries():

@@ -40,7 +40,7 @@ SHAPES = [  # B, fps, Gh, Gw, F, L1: the CIFAR map (clamp sink), exact-fit map, 
     (512, 8, 11, 11, 800, 1024), (64, 8, 11, 11, 800, 256), (37, 4, 8, 8, 256, 64), (5, 4, 3, 3, 100, 36),
     (16, 64, 8, 8, 4096, 128), (3, 2, 2, 1, 3, 4), (130, 8, 10, 10, 800, 200), (33, 12, 5, 5, 150, 72), (1, 4, 1, 1, 4, 8),
     (24, 64, 32, 32, 65536, 256), (140, 64, 24, 24, 30000, 136),  # big maps: bf16-split tiles incl. the six-product value gradient
-    (130, 64, 24, 24, 30000, 128), (128, 64, 32, 32, 65536, 64),  # ... and the LDS-DMA value gradient (ftv_kernels.hip): row tail, clamp, two row tiles
+    (130, 64, 24, 24, 30000, 128), (128, 64, 32, 32, 65536, 64),  # ... and the value gradient's row tail, clamp, two row tiles
 ]
 
 
@@ -81,15 +81,11 @@ def test_ftm_kernels_against_float64(hip, shape, density):
 
 
 @pytest.mark.parametrize("shape", [(24, 64, 32, 32, 65536, 256), (130, 64, 24, 24, 30000, 128), (128, 64, 32, 32, 65536, 512)])
-def test_value_gradient_by_lds_dma_against_float64(hip, shape, monkeypatch):
-    """The optional big-map value gradient of csrc/ftv_kernels.hip (NNUE_FTM_VAL_DMA=1: d_out split once into bf16 planes in a
-    workspace and staged by LDS-DMA, table fragments straight to registers): row tail, two row tiles, the F-1 clamp, and bitwise
-    equality with the default six-plane tile kernel's term order is NOT expected -- both are held to the float64 value."""
+def test_big_map_value_gradient_against_float64(hip, shape):
+    """The big-map value gradient (six bf16 plane products on 128 x 64 tiles, d_out split in every workgroup, no workspace): row
+    tail, two row tiles and the F-1 clamp, held to the float64 value."""
     b, fps, gh, gw, f, l1 = shape
-    monkeypatch.setenv("NNUE_FTM_VAL_DMA", "1")
-    if int(hip.load().nnue_ftm_backward_values_scratch(b, f, fps * gh * gw, l1)) == 0:
-        pytest.skip("the six-plane products are switched off (NNUE_FTM_BF16 / NNUE_FTM_VAL_BF6): this shape takes the f32 kernels")
-    assert int(hip.load().nnue_ftm_backward_values_scratch(b, f, fps * gh * gw, l1)) == 3 * b * l1 * 2
+    assert int(hip.load().nnue_ftm_backward_values_scratch(b, f, fps * gh * gw, l1)) == 0
     gen = torch.Generator().manual_seed(b + f)
     conv_out = torch.randn(b, fps, gh, gw, generator=gen)
     thr = torch.full((fps,), 0.17)
@@ -99,22 +95,11 @@ def test_value_gradient_by_lds_dma_against_float64(hip, shape, monkeypatch):
     g = lambda t: t.to(DEV)
     fm = hip.ftm_binarize(g(conv_out), g(thr), f, l1)
     d_val = hip.ftm_backward_values(g(d_out), g(weight), fm)
-    assert_close_grad(d_val.view(conv_out.shape), ref_dval, "d_conv_out (LDS-DMA kernel)", rtol=2e-5)
+    assert_close_grad(d_val.view(conv_out.shape), ref_dval, "d_conv_out", rtol=2e-5)
     active = (conv_out > 0.17).reshape(b, -1)
     assert not bool(d_val.view(b, -1)[~active.to(DEV)].any())
-    for _ in range(8):  # fixed order: reproducible (and a guard against the intermittent early read this kernel once had)
+    for _ in range(8):  # fixed order: reproducible
         assert torch.equal(hip.ftm_backward_values(g(d_out), g(weight), fm), d_val)
-    # the default: the six-plane tile kernel, d_out split in every workgroup, no workspace
-    monkeypatch.setenv("NNUE_FTM_VAL_DMA", "0")
-    monkeypatch.setenv("NNUE_FTM_VAL_PLANES", "0")
-    assert int(hip.load().nnue_ftm_backward_values_scratch(b, f, fps * gh * gw, l1)) == 0
-    d_tile = hip.ftm_backward_values(g(d_out), g(weight), fm)
-    assert_close_grad(d_tile.view(conv_out.shape), ref_dval, "d_conv_out (tile kernel)", rtol=2e-5)
-    # ... and the same kernel fed with the d_out planes from the workspace (NNUE_FTM_VAL_PLANES=1; measured slower, kept as a
-    # knob): the same terms in the same order, bit for bit
-    monkeypatch.setenv("NNUE_FTM_VAL_PLANES", "1")
-    assert int(hip.load().nnue_ftm_backward_values_scratch(b, f, fps * gh * gw, l1)) == (3 * b * l1 * 2 if l1 % 32 == 0 else 0)
-    assert torch.equal(hip.ftm_backward_values(g(d_out), g(weight), fm), d_tile)
 
 
 @pytest.mark.parametrize("name", MODEL_CASES)

@@ -1,7 +1,6 @@
 """The im2col form of the conv front for large strides (include/nnue_hip.h: nnue_ftm_conv_binarize_patches,
 nnue_ste_conv_backward_patches; self.conv of nnue.py:640 and StraightThroughBinary.backward, nnue.py:28-54): the forward launch
-leaves patches[27][B*G] and the backward reads them instead of the strided pixels and of conv_out, which it re-forms with the
-forward's own fmaf chain.  Contract: BITWISE the pixel form (itself held to the oracle by tests/test_gpu_kernels.py and the
+leaves patches[27][B*G] and the backward reads them instead of the strided pixels.  Contract: BITWISE the pixel form (itself held to the oracle by tests/test_gpu_kernels.py and the
 whole-step tests).  ``-m gpu``."""
 import pytest
 import torch
@@ -18,7 +17,7 @@ SHAPES = [(4, 32, 32, 3, 8, 800), (2, 224, 224, 7, 64, 65536), (3, 40, 56, 5, 20
 
 
 @pytest.mark.parametrize("b,h,w,stride,fps,f", SHAPES)
-def test_forward_leaves_the_im2col_form_and_the_same_map(b, h, w, stride, fps, f):
+def test_forward_leaves_the_im2col_form_beside_conv_out(b, h, w, stride, fps, f):
     from nnue_hip import lib
     lib.load()
     gen = torch.Generator().manual_seed(h * 13 + fps)
@@ -29,11 +28,8 @@ def test_forward_leaves_the_im2col_form_and_the_same_map(b, h, w, stride, fps, f
     conv_ref, fm_ref = lib.ftm_conv_binarize(images, weight, thr, stride, f, 64)
     patches = torch.full((27, b * gh * gw), float("nan"), device=DEV)
     conv_got, fm_got = lib.ftm_conv_binarize(images, weight, thr, stride, f, 64, patches=patches)
-    none, fm_only = lib.ftm_conv_binarize(images, weight, thr, stride, f, 64, patches=torch.empty_like(patches), write_conv_out=False)
     torch.cuda.synchronize()
-    assert none is None
-    for fm in (fm_got, fm_only):
-        assert torch.equal(fm.bits, fm_ref.bits) and torch.equal(fm.n, fm_ref.n) and torch.equal(fm.sink, fm_ref.sink)
+    assert torch.equal(fm_got.bits, fm_ref.bits) and torch.equal(fm_got.n, fm_ref.n) and torch.equal(fm_got.sink, fm_ref.sink)
     assert torch.equal(conv_got, conv_ref)
     # the pixels themselves, zero where a tap falls off the image: exactly torch's unfold
     cols = F.unfold(images, kernel_size=3, padding=1, stride=stride)  # [B, 27, G], term = ci*9 + kh*3 + kw
@@ -43,7 +39,7 @@ def test_forward_leaves_the_im2col_form_and_the_same_map(b, h, w, stride, fps, f
 
 @pytest.mark.parametrize("b,h,w,stride,fps,f", SHAPES)
 @pytest.mark.parametrize("stages", (3, 1))
-def test_backward_from_the_patches_is_bitwise_the_pixel_form(b, h, w, stride, fps, f, stages):
+def test_backward_from_patches_and_conv_out_is_bitwise_the_pixel_form(b, h, w, stride, fps, f, stages):
     from nnue_hip import lib
     lib.load()
     gen = torch.Generator().manual_seed(h * 17 + fps)
@@ -57,22 +53,19 @@ def test_backward_from_the_patches_is_bitwise_the_pixel_form(b, h, w, stride, fp
     need = int(lib.load().nnue_ste_conv_backward_scratch(b, fps, gh, gw))
     s_ref, s_got = torch.zeros(need, dtype=torch.uint8, device=DEV), torch.zeros(need, dtype=torch.uint8, device=DEV)
     t_ref, w_ref = lib.ste_conv_backward(images, conv_out, thr, d, stride, scratch=s_ref, stages=stages)
-    for given in (None, conv_out):  # conv_out re-formed from the patches / read
-        s_got.zero_()
-        t_got, w_got = lib.ste_conv_backward_patches(patches, weight, thr, d, gh, gw, scratch=s_got, stages=stages, conv_out=given)
-        torch.cuda.synchronize()
-        assert torch.equal(s_got, s_ref), "stage-1 partials differ"
-        if stages == 3:
-            assert torch.equal(t_got, t_ref) and torch.equal(w_got, w_ref)
-            assert float(w_ref.abs().max()) > 0 and float(t_ref.abs().max()) > 0
+    t_got, w_got = lib.ste_conv_backward_patches(patches, conv_out, thr, d, gh, gw, scratch=s_got, stages=stages)
+    torch.cuda.synchronize()
+    assert torch.equal(s_got, s_ref), "stage-1 partials differ"
+    if stages == 3:
+        assert torch.equal(t_got, t_ref) and torch.equal(w_got, w_ref)
+        assert float(w_ref.abs().max()) > 0 and float(t_ref.abs().max()) > 0
 
 
 def test_trainer_with_and_without_patches_is_bitwise_the_same(monkeypatch):
     """Three steps of the trainer at a stride-4 shape with the patch form forced on and off: identical parameters."""
     out = []
-    for mode, reform in (("1", "0"), ("1", "1"), ("0", "0")):
+    for mode in ("1", "0"):
         monkeypatch.setenv("NNUE_CONV_PATCHES", mode)
-        monkeypatch.setenv("NNUE_CONV_REFORM", reform)
         torch.manual_seed(0)
         model = nnue.NNUE(nnue.GridFeatureSet(16, 8), 256, 32, 16, num_classes=10, input_size=64).to(DEV)
         tr = NnueTrainer(model, 32, (64, 64), lr=0.05, momentum=0.9, weight_decay=1e-4, max_grad_norm=1.0, use_graph=True, input_slots=2)

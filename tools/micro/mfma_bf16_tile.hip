@@ -1,5 +1,5 @@
 // Microbenchmark: what v_mfma_f32_16x16x32_bf16 sustains on RANDOM operands in the instruction pattern of the 224x224 value
-// gradient (ftv_kernels.hip): per "row block" 12 MFMAs over 3 A fragments x 6 B fragments into 2 accumulators, 8 row blocks =
+// gradient: per "row block" 12 MFMAs over 3 A fragments x 6 B fragments into 2 accumulators, 8 row blocks =
 // 96 MFMAs per "K tile", operands in registers only (no memory in the loop).  Variants: wave count per SIMD (1, 2, 4) and a
 // register-only VALU block of V instructions per tile in front of the MFMAs (the split).  Prints ns per MFMA per SIMD, the
 // in-kernel clock (s_memtime over s_memrealtime) and cycles per MFMA.
