@@ -40,7 +40,7 @@
 extern "C" {
 #endif
 
-#define NNUE_HIP_ABI_VERSION 33
+#define NNUE_HIP_ABI_VERSION 34
 
 #define NNUE_OK 0
 #define NNUE_E_ARG (-1)     /* null pointer, non-positive size, bad alignment */
@@ -268,6 +268,9 @@ int nnue_ftm_backward_values_ws(const uint8_t* bits, const float* d_out, const f
 
 int nnue_ftm_backward_cw_supported(int B, int F, int P, int L1, int L2); /* shapes whose nnue_ftm_backward takes d_w1 */
 int64_t nnue_ftm_backward_sq_count(int B, int F, int P, int L1); /* floats nnue_ftm_backward's sq_partial receives; 0: none */
+/* runs of STE partials nnue_ftm_backward's ste_partial receives (fps == 8 image grids of the merged launch); 0: not taken */
+int64_t nnue_ftm_backward_ste_chunks(int B, int F, int P, int L1, int H, int W, int stride);
+int nnue_ftm_backward_ste_supported(int B, int F, int P, int L1, int H, int W, int stride); /* nnue_ftm_backward_ste_chunks > 0 */
 
 /* nnue_ftm_backward_weight + nnue_ftm_backward_values as ONE launch (autograd of nnue.py:702-708, :628-633): the
  * two products and the tail rows are independent, so their workgroups share the chip.  Same results, bit for bit,
@@ -283,11 +286,19 @@ int64_t nnue_ftm_backward_sq_count(int B, int F, int P, int L1); /* floats nnue_
  * small != NULL (filled by nnue_classifier_train_rider; merged-launch shapes only): the classifier's small batch-reduced
  * gradients (d_w3, d_w2, the three bias gradients; autograd of nnue.py:728-734) and the mean loss (train.py:250-254) run as
  * one more tile family of this launch -- ~30 workgroups beside a few hundred -- instead of beside the classifier's d_x tiles
- * (nnue_classifier_train_step phases bit 32). */
+ * (nnue_classifier_train_step phases bit 32).
+ * ste_partial != NULL (shapes with nnue_ftm_backward_ste_chunks > 0): the value-gradient tiles also reduce d_conv_out into the
+ * partial sums of the threshold and conv-weight gradients -- stage 1 of nnue_ste_conv_backward (the straight-through
+ * threshold nnue.py:28-54 and the conv's autograd at nnue.py:640) -- from ste_images [B][3][H][W] (or, when ste_patches !=
+ * NULL, the im2col patches [27][B * Gh * Gw] of nnue_ftm_conv_binarize_patches: the same bits), ste_conv_out [B][P] and
+ * ste_thr [fps]: [fps * 28][chunks] floats (ste_partial_bytes >= 4 * fps * 28 * chunks), whose second stage is
+ * nnue_sgd_step's ste argument (clip_grad_norm_ + SGD, train.py:363-366).  d_conv_out may then be NULL (not stored). */
 int nnue_ftm_backward(const uint8_t* bits, const float* sink, const float* d_out, const float* weight,
                       int B, int F, int P, int L1, float* d_weight, float* d_bias, float* d_conv_out,
                       const float* ft, const float* d_z1, int L2, float* d_w1, float* sq_partial,
-                      const nnue_cls_rider* small, nnue_stream_t stream);
+                      const nnue_cls_rider* small, const float* ste_images, const float* ste_patches, const float* ste_conv_out,
+                      const float* ste_thr, int H, int W, int stride, float* ste_partial, int64_t ste_partial_bytes,
+                      nnue_stream_t stream);
 
 /* ---- pairwise product + SimpleClassifier -------------------------------------- */
 
@@ -496,7 +507,9 @@ int nnue_ftm_backward_bucketed(const uint8_t* bits, const float* sink, const flo
                                int B, int F, int P, int L1, float* d_weight, float* d_bias, float* d_conv_out,
                                const float* ft_grouped, const float* d_z1_grouped, int L2, float* d_w1,
                                float* sq_partial, int K, const int32_t* seg, int grouped_rows,
-                               const nnue_cls_rider* small, nnue_stream_t stream);
+                               const nnue_cls_rider* small, const float* ste_images, const float* ste_patches, const float* ste_conv_out,
+                               const float* ste_thr, int H, int W, int stride, float* ste_partial, int64_t ste_partial_bytes,
+                               nnue_stream_t stream);
 
 /* ---- loss + step tail ---------------------------------------------------------- */
 

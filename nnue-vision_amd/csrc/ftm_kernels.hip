@@ -148,6 +148,159 @@ struct ValEpi {  // d_conv_out = acc where the position is active, else 0
   }
 };
 
+// The value gradient whose epilogue also reduces its tile into the partial sums of the threshold and conv-weight gradients
+// (stage 1 of ste_conv_backward_mfma, feature_kernels.hip: nnue.py:28-54 and the conv's autograd), so that d_conv_out need not
+// cross a kernel boundary.  fps == 8: a tile's 64 columns are the 8 channels of 8 consecutive grid positions (column j: channel
+// j / 8, position 8 tile_n + j % 8), so the 27 pixels of a position are gathered once per tile and shared by all its channels.
+// d_conv_out is stored only when the pointer is set.  Partials: [fps * 28][n_tiles] (term 27 = the threshold term), one slot
+// per tile, the slots of one XCD consecutive (see ste_conv_backward_mfma).  The pixel terms come from the images or, where the
+// conv launch left them, from the im2col patches -- the same values, so both forms give the same bits (as the STE kernel's do).
+struct ValSteEpi {
+  static constexpr bool kAU8 = false;
+  static constexpr bool kFusedL1 = false;
+  static constexpr bool kBPair = false;
+  static constexpr bool kSte = true;
+  const uint8_t* __restrict__ bits;
+  float* __restrict__ d_conv_out;  // NULL: not stored
+  int P;
+  const float* __restrict__ img;       // [B][3][H][W] (unused when patches != NULL)
+  const float* __restrict__ patches;   // NULL or [27][B * G] (nnue_ftm_conv_binarize_patches)
+  const float* __restrict__ conv_out;  // [B][P]
+  const float* __restrict__ thr;       // [fps]
+  int H, W, stride, Gw, G;
+  float* __restrict__ partial;
+  int n_tiles;
+  // table row (= map position) of tile-local column j; columns past the grid read a real row, their results are dropped
+  __device__ __forceinline__ int prow(int tile_n, int j) const {
+    const int hw = tile_n * 8 + (j & 7);
+    return (j >> 3) * G + (hw < G ? hw : G - 1);
+  }
+};
+constexpr float kFtmSteSharpness = 10.0f;  // k, nnue.py:41 (the STE kernel's constant)
+
+template <class Epi, class = void>
+struct is_ste { static constexpr bool value = false; };
+template <class Epi>
+struct is_ste<Epi, decltype((void)Epi::kSte)> { static constexpr bool value = Epi::kSte; };
+
+// The pixel operand of the tile's STE contraction, dW[c][q] = sum over the tile's (sample, position) pairs k of
+// d[c][k] * patch[k][q] on v_mfma_f32_16x16x4_f32: wave w takes pairs [2 BM w, 2 BM (w + 1)), MFMA step (g, e) pair
+// 2 BM w + 16 g + 4 q + e, lane (r, q) supplies patch terms r and 16 + r (term 27 is 1: it sums the threshold rows).
+template <int BM>
+struct SteFrag {
+  float pv[BM / 8][4][2];
+};
+template <int BM>
+__device__ __forceinline__ void ste_pixels(const ValSteEpi& e, SteFrag<BM>& f, int M, int m_base, int tile_n, int wave, int r, int q) {
+#pragma unroll
+  for (int g = 0; g < BM / 8; ++g)
+#pragma unroll
+    for (int t4 = 0; t4 < 4; ++t4) {
+      const int k = wave * 2 * BM + 16 * g + 4 * q + t4;
+      const int m = m_base + (k >> 3), hw = tile_n * 8 + (k & 7);
+      const bool ok = m < M && hw < e.G;
+      const int h = hw / e.Gw, x = hw - h * e.Gw;
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        const int qq = r + 16 * s;
+        const int qc = qq < 27 ? qq : 26;
+        bool in;
+        float v;
+        if (e.patches) {  // uniform
+          in = ok && qq < 27;
+          v = e.patches[in ? ((size_t)qc * M + m) * e.G + hw : 0];
+        } else {
+          const int ci = qc / 9, kh = (qc - ci * 9) / 3, kw = qc - ci * 9 - kh * 3;
+          const int iy = h * e.stride + kh - 1, ix = x * e.stride + kw - 1;
+          in = ok && qq < 27 && iy >= 0 && iy < e.H && ix >= 0 && ix < e.W;
+          v = e.img[in ? (((size_t)m * 3 + ci) * e.H + iy) * e.W + ix : 0];
+        }
+        f.pv[g][t4][s] = in ? v : (qq == 27 ? 1.0f : 0.0f);
+      }
+    }
+}
+
+// Epilogue of a ValSteEpi tile (BN = 64, waves 2 x 2, accumulator register e of lane 16 q + r = C[row 4 q + e][col r]):
+// the masked d tile and its threshold terms d k s (1 - s) go to LDS as the rows 0..7 / 8..15 of a [16][8 BM] operand, the
+// pixel fragments are the other one, and one 16 x 32 MFMA tile per wave contracts its quarter of the pairs; the four waves'
+// tiles are summed in wave order.  `smem` is free (the K loop ended with a barrier) and holds >= 16 (8 BM + 4) + 2048 floats.
+template <int BM, int BN>
+__device__ __forceinline__ void ste_tile(float* __restrict__ smem, const ValSteEpi& e, const f32x4 (&acc)[BM / 32][BN / 32], const SteFrag<BM>& f,
+                                         int M, int m_base, int tile_n, int m0, int n0, int tile) {
+  static_assert(BN == 64, "a tile holds the 8 channels of 8 positions");
+  constexpr int TM = BM / 32, TN = BN / 32, LDA = 8 * BM + 4;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int r = lane & 15, q = lane >> 4;
+  float bit[TM][TN][4], cv[TM][TN][4], th[TN];
+#pragma unroll
+  for (int t = 0; t < TN; ++t) {
+    const int j = n0 + 16 * t + r, c = j >> 3, hw = tile_n * 8 + (j & 7);
+    const int p = c * e.G + (hw < e.G ? hw : 0);
+    th[t] = e.thr[c];
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int ee = 0; ee < 4; ++ee) {
+        const int m = m_base + m0 + 16 * i + 4 * q + ee;
+        const bool ok = m < M && hw < e.G;
+        bit[i][t][ee] = ok ? (float)e.bits[(size_t)m * e.P + p] : 0.0f;
+        cv[i][t][ee] = ok ? e.conv_out[(size_t)m * e.P + p] : 0.0f;
+      }
+  }
+  float* __restrict__ A = smem;
+  float* __restrict__ red = smem + 16 * LDA;  // [4 waves][8 registers][64 lanes]
+#pragma unroll
+  for (int t = 0; t < TN; ++t) {
+    const int j = n0 + 16 * t + r, c = j >> 3, hw = tile_n * 8 + (j & 7);
+    const int p = c * e.G + (hw < e.G ? hw : 0);
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int ee = 0; ee < 4; ++ee) {
+        const int m_loc = m0 + 16 * i + 4 * q + ee, m = m_base + m_loc;
+        const float d = bit[i][t][ee] != 0.0f ? acc[i][t][ee] : 0.0f;  // bit is 0 outside the tile's valid range
+        if (e.d_conv_out && m < M && hw < e.G) e.d_conv_out[(size_t)m * e.P + p] = d;
+        const float s = 1.0f / (1.0f + __expf(-kFtmSteSharpness * (cv[i][t][ee] - th[t])));
+        const int k = m_loc * 8 + (j & 7);
+        A[c * LDA + k] = d;
+        A[(8 + c) * LDA + k] = d * ((kFtmSteSharpness * s) * (1.0f - s));
+      }
+  }
+  __syncthreads();
+  f32x4 c0 = {0.f, 0.f, 0.f, 0.f}, c1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int g = 0; g < BM / 8; ++g) {
+    const float4 a = *reinterpret_cast<const float4*>(&A[r * LDA + wave * 2 * BM + 16 * g + 4 * q]);
+    c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, f.pv[g][0][0], c0, 0, 0, 0);
+    c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, f.pv[g][0][1], c1, 0, 0, 0);
+    c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, f.pv[g][1][0], c0, 0, 0, 0);
+    c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, f.pv[g][1][1], c1, 0, 0, 0);
+    c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, f.pv[g][2][0], c0, 0, 0, 0);
+    c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, f.pv[g][2][1], c1, 0, 0, 0);
+    c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, f.pv[g][3][0], c0, 0, 0, 0);
+    c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, f.pv[g][3][1], c1, 0, 0, 0);
+  }
+#pragma unroll
+  for (int ee = 0; ee < 4; ++ee) {
+    red[(wave * 8 + ee) * 64 + lane] = c0[ee];
+    red[(wave * 8 + 4 + ee) * 64 + lane] = c1[ee];
+  }
+  __syncthreads();
+  int slot;  // XCD-major slots (the value tiles are the launch's first workgroups: tile % 8 is the XCD)
+  {
+    const int nwg = e.n_tiles, xcd = tile & 7, q8 = nwg >> 3, r8 = nwg & 7;
+    slot = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (tile >> 3);
+  }
+  for (int o = tid; o < 8 * 28; o += 256) {
+    const int c = o / 28, qq = o - c * 28;
+    const int row = qq < 27 ? c : 8 + c, col = qq;  // C[c][q] = sum d * pixel q; C[8 + c][27] = sum of the threshold terms
+    const int s = (col >> 4) * 4 + (row & 3), ln = (row >> 2) * 16 + (col & 15);
+    e.partial[(size_t)o * e.n_tiles + slot] =
+        (red[(0 * 8 + s) * 64 + ln] + red[(1 * 8 + s) * 64 + ln]) + (red[(2 * 8 + s) * 64 + ln] + red[(3 * 8 + s) * 64 + ln]);
+  }
+}
+
 // Weight gradient of the classifier's first Linear, d_w1 = d_z1^T l0 (autograd of nnue.py:728-730 through the pairwise
 // block nnue.py:660-666), as a third tile family of the merged backward launch: A = d_z1^T, B = l0 formed from ft while
 // its tile is stored to LDS (l0[:, c] = ft[:, c] * ft[:, c + L1/2] for c < L1/2, ft[:, c - L1/2] above; a 64-column tile
@@ -465,6 +618,10 @@ __device__ __forceinline__ void gemm_tile(float* __restrict__ smem, const Mat& m
     b_prod = n_base < epi.half;
     b_shift = b_prod ? 0 : epi.half;
   }
+  auto b_outer = [&](int row) {  // B row of tile-local row `row` (ValSteEpi: the channel-interleaved columns)
+    if constexpr (is_ste<Epi>::value) return epi.prow(tile_n, row);
+    else return n_base + row;
+  };
   u32x4 ra[AG], rb[BG], rb2[Epi::kBPair ? BG : 1];
   auto fetch = [&](int k0) {
 #pragma unroll
@@ -473,7 +630,7 @@ __device__ __forceinline__ void gemm_tile(float* __restrict__ smem, const Mat& m
 #pragma unroll
     for (int i = 0; i < BG; ++i)
     {
-      rb[i] = BKC ? mat_load<false>(rsb, mb, n_base + b_row(i), k0 + b_k(i))
+      rb[i] = BKC ? mat_load<false>(rsb, mb, b_outer(b_row(i)), k0 + b_k(i))
                   : mat_load<false>(rsb, mb, k0 + b_k(i), b_col(n_base + b_row(i)) - b_shift);
       if constexpr (Epi::kBPair)
         if (b_prod) rb2[i] = mat_load<false>(rsb, mb, k0 + b_k(i), n_base + b_row(i) + epi.half);
@@ -504,6 +661,9 @@ __device__ __forceinline__ void gemm_tile(float* __restrict__ smem, const Mat& m
 
   FusedL1Pre<Epi::kFusedL1 ? BM : 32> l1pre;
   if constexpr (Epi::kFusedL1) fused_l1_prefetch<BM>(epi, l1pre, m_base, tile_n, m0, n0, r, q, wave);
+  // the STE epilogue's pixels are requested before the K loop (32 registers at BM = 32)
+  SteFrag<is_ste<Epi>::value ? BM : 8> stef;
+  if constexpr (is_ste<Epi>::value) ste_pixels<BM>(epi, stef, M, m_base, tile_n, wave, r, q);
   // (Two K tiles of loads in flight -- two register sets, the loop written out twice, every load unconditional with a dead request's
   // offset outside its window, no branch between the halves, scheduling barriers between the sets' requests: each of these was
   // needed before the compiler's waits became vmcnt(12) instead of vmcnt(0), which round 2's attempt never reached -- was measured at
@@ -560,6 +720,8 @@ __device__ __forceinline__ void gemm_tile(float* __restrict__ smem, const Mat& m
   if constexpr (Epi::kFusedL1) {
     fused_l1_epilogue<BM>(epi, l1pre, smem, acc, m_base, tile_n, m0, n0, r, q, wave, tid);
     return;
+  } else if constexpr (is_ste<Epi>::value) {
+    ste_tile<BM, BN>(smem, epi, acc, stef, M, m_base, tile_n, m0, n0, tile);
   } else {
     store_tile<BM, BN, Epi>(smem, epi, acc, M, N, m_base, n_base, m0, n0, tile, ks);
   }
@@ -1045,7 +1207,9 @@ __device__ __forceinline__ void gemm_tile_bf6(unsigned char* __restrict__ smem, 
 #pragma unroll
     for (int i = 0; i < GB; ++i) {
       const int g = tid + 256 * i, row = g / RUNS, k = k0 + (g % RUNS) * 8;
-      const int rr = n_base + row < mb.clamp ? n_base + row : mb.clamp;
+      int nr = n_base + row;
+      if constexpr (is_ste<Epi>::value) nr = epi.prow(tile_n, row);
+      const int rr = nr < mb.clamp ? nr : mb.clamp;
       const int off0 = k < mb.inner_k ? (rr * mb.ld + k) * 4 : 0x7ffffff0, off1 = k + 4 < mb.inner_k ? (rr * mb.ld + k + 4) * 4 : 0x7ffffff0;
       if (stream_b) {
         rb[i][0] = __builtin_amdgcn_raw_buffer_load_b128(rsb, off0, 0, 2);
@@ -1123,7 +1287,13 @@ __device__ __forceinline__ void gemm_tile_bf6(unsigned char* __restrict__ smem, 
     contract();
     __syncthreads();
   }
-  store_tile<BM, BN, Epi>(reinterpret_cast<float*>(smem), epi, acc, M, N, m_base, n_base, m0, n0, tile, ks);
+  if constexpr (is_ste<Epi>::value) {  // (64 pixel registers at BM = 64: requested here, not across the K loop)
+    SteFrag<BM> stef;
+    ste_pixels<BM>(epi, stef, M, m_base, tile_n, wave, r, q);
+    ste_tile<BM, BN>(reinterpret_cast<float*>(smem), epi, acc, stef, M, m_base, tile_n, m0, n0, tile);
+  } else {
+    store_tile<BM, BN, Epi>(reinterpret_cast<float*>(smem), epi, acc, M, N, m_base, n_base, m0, n0, tile, ks);
+  }
 }
 
 template <int BM, int BN, class Epi, int KT, int ABL = 0>
@@ -1331,20 +1501,22 @@ __global__ __launch_bounds__(256) void ftm_backward_kernel(Mat wa, Mat wb, BwwEp
 }
 
 // The same launch with the weight-gradient tiles on the bf16 matrix unit (gemm_tile_bf, WM x 64 x 128); value-gradient
-// tiles (both operands f32) and the rider keep the f32 MFMA.
-template <int WM, int VM, int VN, int VK, bool V6 = false, bool W64 = false>
+// tiles (both operands f32) and the rider keep the f32 MFMA.  VE = ValSteEpi: the value tiles also leave the STE partials.
+template <int WM, int VM, int VN, int VK, bool V6 = false, bool W64 = false, class VE = ValEpi>
 __global__ __launch_bounds__(256) void ftm_backward_bf_kernel(Mat wa, Mat wb, BwwEpi we, int wM, int wN, int wK, int w_tiles_n, int n_w,
-                                                              Mat va, Mat vb, ValEpi ve, int vM, int vN, int vK, int v_tiles_n, int n_v,
+                                                              Mat va, Mat vb, VE ve, int vM, int vN, int vK, int v_tiles_n, int n_v,
                                                               CwArgs c, TailRows t, SmallWgrad sw) {
   constexpr int kW = W64 ? gemm_bf64_lds_bytes<WM>() : gemm_bf_lds_bytes<WM, 64>(), kV = V6 ? gemm_bf6_lds_bytes<VM, VN>() : gemm_lds_floats<VM, VN, VK, true, true>() * 4;
   constexpr int kC = gemm_lds_floats<32, 64, 128, false, false>() * 4;
   constexpr int kWV = kW > kV ? kW : kV;
-  __shared__ __attribute__((aligned(16))) unsigned char smem_b[kWV > kC ? kWV : kC];
+  constexpr int kLds = kWV > kC ? kWV : kC;
+  static_assert(!is_ste<VE>::value || (16 * (8 * VM + 4) + 2048) * 4 <= kLds, "the STE epilogue borrows the tile's LDS");
+  __shared__ __attribute__((aligned(16))) unsigned char smem_b[kLds];
   float* smem = reinterpret_cast<float*>(smem_b);
   const int blk = blockIdx.x;
   if (blk < n_v) {
-    if constexpr (V6) gemm_tile_bf6<VM, VN, ValEpi>(smem_b, va, vb, ve, vM, vN, 0, vK, v_tiles_n, blk, 0);
-    else gemm_tile<VM, VN, VK, true, true, ValEpi>(smem, va, vb, ve, vM, vN, 0, vK, v_tiles_n, blk, 0);
+    if constexpr (V6) gemm_tile_bf6<VM, VN, VE>(smem_b, va, vb, ve, vM, vN, 0, vK, v_tiles_n, blk, 0);
+    else gemm_tile<VM, VN, VK, true, true, VE>(smem, va, vb, ve, vM, vN, 0, vK, v_tiles_n, blk, 0);
   } else if (blk < n_v + n_w) {
     if constexpr (W64) gemm_tile_bf64<WM, false, BwwEpi>(smem_b, wa, wb, we, wM, wN, 0, wK, w_tiles_n, blk - n_v, 0);
     else gemm_tile_bf<WM, 64, false, BwwEpi>(smem_b, wa, wb, we, wM, wN, 0, wK, w_tiles_n, blk - n_v, 0);
@@ -1876,6 +2048,11 @@ bool merged_backward_shape(int B, int F, int P, int L1, bool* big) {
 }
 // value tiles of the merged launch as six bf16 plane products: for the 64 x 64 tiles (C3 shapes: 43.5 vs 46.0 us for the
 // launch); the 32 x 64 tiles of the batch-512 shape are latency-bound per K tile and lose with the 64-deep bf16 tiles (27.2 vs 26.3 us)
+// weight tiles with K tiles of 64 (gemm_tile_bf64) in the merged launch
+bool merged_w64() {
+  static const int w64 = env_int("NNUE_FTM_BWD_W64", 1);  // developer knob
+  return w64 != 0;
+}
 bool merged_values_bf6(int B, int F, int P, int L1) {
   static const int bf6 = env_int("NNUE_FTM_BWD_BF6", 1);  // developer knob
   bool big = false;
@@ -1884,6 +2061,42 @@ bool merged_values_bf6(int B, int F, int P, int L1) {
   return bf6 && !v_small && L1 % 8 == 0;
 }
 }  // namespace
+
+namespace {
+struct SteArgs {  // the STE stage 1 riding in the value tiles (nnue_ftm_backward's ste_* arguments)
+  const float* img;
+  const float* patches;
+  const float* conv_out;
+  const float* thr;
+  int H, W, stride;
+  float* partial;
+  int64_t partial_bytes;
+};
+
+// Value tiles of the merged launch when they carry the STE partials (= the partials' run length), 0 where the shape is not taken:
+// 8 channels (fps * G == P with G the grid of an H x W image at `stride`), the merged launch with its default bf16 weight tiles
+// and 32 x 64 value tiles (the batch-512 CIFAR shape: 0.0830 -> 0.0801 ms per step).  The 64 x 64 bf16-plane value tiles of the
+// batch-1024 shapes also take the epilogue (ftm_backward_bf_kernel<.., ValSteEpi>) but lose there -- C3 0.1266 -> 0.1312 ms:
+// their 64 pixel registers are requested after the K loop -- so they keep the STE launch.
+int64_t ste_ride_tiles(int B, int F, int P, int L1, int H, int W, int stride) {
+  if (!nnue_ftm_supported(F, P, L1) || !shape_ok(B, F, P, L1) || H <= 0 || W <= 0 || stride <= 0) return 0;
+  const long long Gh = (H - 1) / stride + 1, Gw = (W - 1) / stride + 1;
+  if (8 * Gh * Gw != P || (long long)B * 3 * H * W >= (1ll << 40)) return 0;
+  bool big = false;
+  if (!merged_backward_shape(B, F, P, L1, &big) || merged_bf_wm() != 64 || !merged_w64()) return 0;
+  static const int wide = env_int("NNUE_FTM_RIDE_STE_V64", 0);  // developer knob: 1 also rides in the 64 x 64 value tiles
+  const int vm = (!big && plan(B, P, L1, true, false).cfg == 0) ? 32 : 64;
+  if (vm != 32 && !wide) return 0;
+  return (int64_t)((B + vm - 1) / vm) * ((Gh * Gw + 7) / 8);
+}
+}  // namespace
+
+extern "C" int64_t nnue_ftm_backward_ste_chunks(int B, int F, int P, int L1, int H, int W, int stride) {
+  return ste_ride_tiles(B, F, P, L1, H, W, stride);
+}
+extern "C" int nnue_ftm_backward_ste_supported(int B, int F, int P, int L1, int H, int W, int stride) {
+  return ste_ride_tiles(B, F, P, L1, H, W, stride) > 0;
+}
 
 // Number of squared-norm partials nnue_ftm_backward leaves (one per weight-gradient tile), 0 when the product is split
 // along K (never for this operand order today) or the shape is not taken.
@@ -1911,29 +2124,43 @@ extern "C" int nnue_ftm_backward_cw_supported(int B, int F, int P, int L1, int L
 namespace {
 int ftm_backward_impl(const uint8_t* bits, const float* sink, const float* d_out, const float* weight, int B, int F, int P, int L1,
                       float* d_weight, float* d_bias, float* d_conv_out, const float* ft, const float* d_z1, int L2, float* d_w1,
-                      float* sq_partial, int K, const int32_t* seg, int grouped_rows, const nnue_cls_rider* small, nnue_stream_t stream);
+                      float* sq_partial, int K, const int32_t* seg, int grouped_rows, const nnue_cls_rider* small, const SteArgs* ste,
+                      nnue_stream_t stream);
 }
 extern "C" int nnue_ftm_backward(const uint8_t* bits, const float* sink, const float* d_out, const float* weight, int B, int F, int P,
                                  int L1, float* d_weight, float* d_bias, float* d_conv_out, const float* ft, const float* d_z1, int L2,
-                                 float* d_w1, float* sq_partial, const nnue_cls_rider* small, nnue_stream_t stream) {
+                                 float* d_w1, float* sq_partial, const nnue_cls_rider* small, const float* ste_images, const float* ste_patches, const float* ste_conv_out,
+                                 const float* ste_thr, int H, int W, int stride, float* ste_partial, int64_t ste_partial_bytes, nnue_stream_t stream) {
+  const SteArgs sa{ste_images, ste_patches, ste_conv_out, ste_thr, H, W, stride, ste_partial, ste_partial_bytes};
   return ftm_backward_impl(bits, sink, d_out, weight, B, F, P, L1, d_weight, d_bias, d_conv_out, ft, d_z1, L2, d_w1, sq_partial, 1, nullptr, 0,
-                           small, stream);
+                           small, ste_partial ? &sa : nullptr, stream);
 }
 extern "C" int nnue_ftm_backward_bucketed(const uint8_t* bits, const float* sink, const float* d_out, const float* weight, int B, int F,
                                           int P, int L1, float* d_weight, float* d_bias, float* d_conv_out, const float* ft_grouped,
                                           const float* d_z1_grouped, int L2, float* d_w1, float* sq_partial, int K, const int32_t* seg,
-                                          int grouped_rows, const nnue_cls_rider* small, nnue_stream_t stream) {
+                                          int grouped_rows, const nnue_cls_rider* small, const float* ste_images, const float* ste_patches, const float* ste_conv_out,
+                                          const float* ste_thr, int H, int W, int stride, float* ste_partial, int64_t ste_partial_bytes,
+                                          nnue_stream_t stream) {
   NNUE_REQUIRE(K >= 1 && K <= 64, NNUE_E_ARG, "nnue_ftm_backward_bucketed: K=%d out of range", K);
   NNUE_REQUIRE(K == 1 || !d_w1 || (seg && grouped_rows >= B && grouped_rows % 16 == 0), NNUE_E_ARG,
                "nnue_ftm_backward_bucketed: d_w1 for K > 1 needs seg and the grouped row count (a multiple of 16, >= B)");
+  const SteArgs sa{ste_images, ste_patches, ste_conv_out, ste_thr, H, W, stride, ste_partial, ste_partial_bytes};
   return ftm_backward_impl(bits, sink, d_out, weight, B, F, P, L1, d_weight, d_bias, d_conv_out, ft_grouped, d_z1_grouped, L2, d_w1, sq_partial,
-                           K, K > 1 ? seg : nullptr, K > 1 ? grouped_rows : 0, small, stream);
+                           K, K > 1 ? seg : nullptr, K > 1 ? grouped_rows : 0, small, ste_partial ? &sa : nullptr, stream);
 }
 namespace {
 int ftm_backward_impl(const uint8_t* bits, const float* sink, const float* d_out, const float* weight, int B, int F, int P, int L1,
                       float* d_weight, float* d_bias, float* d_conv_out, const float* ft, const float* d_z1, int L2, float* d_w1,
-                      float* sq_partial, int K, const int32_t* seg, int grouped_rows, const nnue_cls_rider* small, nnue_stream_t stream) {
-  NNUE_REQUIRE(bits && sink && d_out && weight && d_weight && d_bias && d_conv_out, NNUE_E_ARG, "nnue_ftm_backward: null pointer");
+                      float* sq_partial, int K, const int32_t* seg, int grouped_rows, const nnue_cls_rider* small, const SteArgs* ste,
+                      nnue_stream_t stream) {
+  NNUE_REQUIRE(bits && sink && d_out && weight && d_weight && d_bias && (d_conv_out || ste), NNUE_E_ARG, "nnue_ftm_backward: null pointer");
+  const int64_t ste_tiles = ste ? ste_ride_tiles(B, F, P, L1, ste->H, ste->W, ste->stride) : 0;
+  NNUE_REQUIRE(!ste || ((ste->img || ste->patches) && ste->conv_out && ste->thr && ste->partial), NNUE_E_ARG,
+               "nnue_ftm_backward: null STE pointer");
+  NNUE_REQUIRE(!ste || ste_tiles > 0, NNUE_E_SHAPE, "nnue_ftm_backward: STE partials requested for a shape the merged launch does not take "
+               "(nnue_ftm_backward_ste_chunks)");
+  NNUE_REQUIRE(!ste || ste->partial_bytes >= ste_tiles * 8 * 28 * (int64_t)sizeof(float), NNUE_E_SCRATCH, "nnue_ftm_backward: STE partials %lld < %lld bytes",
+               ste ? (long long)ste->partial_bytes : 0ll, (long long)ste_tiles * 8 * 28 * 4);
   const bool want_cw = d_w1 != nullptr;
   NNUE_REQUIRE(!want_cw || (ft && d_z1 && nnue_ftm_backward_cw_supported(B, F, P, L1, L2) && nnue_aligned16(ft) && nnue_aligned16(d_z1)),
                NNUE_E_SHAPE, "nnue_ftm_backward: d_w1 requested for a shape / pointers the merged launch does not take (nnue_ftm_backward_cw_supported)");
@@ -1971,7 +2198,14 @@ int ftm_backward_impl(const uint8_t* bits, const float* sink, const float* d_out
   // (value-gradient tiles of 32 x 32 x 128 -- twice the workgroups, two resident per CU -- were measured at the CIFAR
   // batch-512 shape and lose: 30.5 vs 28.9 us for the launch)
   const Shape& svr = big_pair ? sv2 : sv;
-  const int n_w = swr.tiles_m * swr.tiles_n, n_v = svr.tiles_m * svr.tiles_n, n_t = t.col_blocks * (1 + t.zero_slices);
+  // STE ride: the value tiles' columns are the 8 channels of 8 grid positions (ValSteEpi), ceil(G / 8) tiles along N
+  const int G = P / 8, v_tiles_n = ste ? (G + 7) / 8 : svr.tiles_n;
+  const int n_w = swr.tiles_m * swr.tiles_n, n_v = svr.tiles_m * v_tiles_n, n_t = t.col_blocks * (1 + t.zero_slices);
+  ValSteEpi vs{};
+  if (ste) {
+    const int Gw = (ste->W - 1) / ste->stride + 1;
+    vs = ValSteEpi{bits, d_conv_out, P, ste->img, ste->patches, ste->conv_out, ste->thr, ste->H, ste->W, ste->stride, Gw, G, ste->partial, n_v};
+  }
   CwArgs cw{};
   if (want_cw) {  // d_w1 [L2][L1] = d_z1^T [L2 x B] l0 [B x L1]   (per bucket over its own grouped rows when seg != NULL)
     const int rows = seg ? grouped_rows : B;
@@ -2008,7 +2242,19 @@ int ftm_backward_impl(const uint8_t* bits, const float* sink, const float* d_out
   const bool v6 = merged_values_bf6(B, F, P, L1);
   // weight tiles with K tiles of 64 (gemm_tile_bf64): the launch's LDS drops from 64 KB to the rider's 52 KB -- three
   // workgroups per CU instead of two (the 168 registers allow exactly that): 43.5 -> 37.7 us at the C3 shapes, 26.2 -> 25.1 us at C2
-  static const int w64 = env_int("NNUE_FTM_BWD_W64", 1);  // developer knob
+  const bool w64 = merged_w64();
+  if (ste) {  // the value tiles leave the STE partials (ValSteEpi; nnue_ftm_backward_ste_chunks said the shape is taken)
+    if (v_small)
+      hipLaunchKernelGGL((ftm_backward_bf_kernel<64, 32, 64, 128, false, true, ValSteEpi>), grid, dim3(256), 0, st, wa, wb, we, direct, L1, B,
+                         swr.tiles_n, n_w, va, vb, vs, B, P, L1, v_tiles_n, n_v, cw, t, sgw);
+    else if (v6)
+      hipLaunchKernelGGL((ftm_backward_bf_kernel<64, 64, 64, 64, true, true, ValSteEpi>), grid, dim3(256), 0, st, wa, wb, we, direct, L1, B,
+                         swr.tiles_n, n_w, va, vb, vs, B, P, L1, v_tiles_n, n_v, cw, t, sgw);
+    else
+      hipLaunchKernelGGL((ftm_backward_bf_kernel<64, 64, 64, 64, false, true, ValSteEpi>), grid, dim3(256), 0, st, wa, wb, we, direct, L1, B,
+                         swr.tiles_n, n_w, va, vb, vs, B, P, L1, v_tiles_n, n_v, cw, t, sgw);
+    return nnue_launch_status("nnue_ftm_backward");
+  }
   if (bf_wm == 64) { if (v_small) NNUE_FTM_BWD_BF(64, 32, 64, 128); else NNUE_FTM_BWD_BF(64, 64, 64, 64); }
   else if (bf_wm == 32) { if (v_small) NNUE_FTM_BWD_BF(32, 32, 64, 128); else NNUE_FTM_BWD_BF(32, 64, 64, 64); }
   else if (big_pair) NNUE_FTM_BWD(64, 64, 64, 64, 64, 64);

@@ -16,7 +16,7 @@ import torch
 
 _HERE = Path(__file__).resolve().parent
 LIB_PATH = _HERE / "libnnue_hip.so"
-ABI_VERSION = 33
+ABI_VERSION = 34
 
 _c_int, _c_i64, _c_f, _c_p = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
 
@@ -85,10 +85,14 @@ SIGNATURES = {
     "nnue_ftm_backward_values_ws": (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p, _c_i64, _c_p]),
     "nnue_ftm_backward_cw_supported": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int]),
     "nnue_ftm_backward_sq_count": (_c_i64, [_c_int, _c_int, _c_int, _c_int]),
+    "nnue_ftm_backward_ste_chunks": (_c_i64, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int]),
+    "nnue_ftm_backward_ste_supported": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int]),
     "nnue_ftm_backward": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p,
-                                   _c_p, _c_p, _c_int, _c_p, _c_p, _c_rider, _c_p]),
+                                   _c_p, _c_p, _c_int, _c_p, _c_p, _c_rider, _c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_int,
+                                   _c_p, _c_i64, _c_p]),
     "nnue_ftm_backward_bucketed": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p,
-                                            _c_p, _c_p, _c_int, _c_p, _c_p, _c_int, _c_p, _c_int, _c_rider, _c_p]),
+                                            _c_p, _c_p, _c_int, _c_p, _c_p, _c_int, _c_p, _c_int, _c_rider, _c_p, _c_p, _c_p,
+                                            _c_p, _c_int, _c_int, _c_int, _c_p, _c_i64, _c_p]),
     "nnue_classifier_train_rider": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p,
                                              _c_p, _c_p, _c_p, _c_i64, _c_bk, _c_rider]),
     "nnue_classifier_train_dz1_grouped_offset": (_c_i64, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int]),
@@ -804,11 +808,20 @@ def ftm_backward_cw_supported(b: int, f: int, p: int, l1: int, l2: int) -> bool:
     return bool(load().nnue_ftm_backward_cw_supported(b, f, p, l1, l2))
 
 
+def ftm_backward_ste_chunks(b: int, f: int, p: int, l1: int, h: int, w: int, stride: int) -> int:
+    """Runs of STE partials the merged backward's value tiles leave for this shape (ftm_backward(ste=...)); 0: not taken."""
+    return int(load().nnue_ftm_backward_ste_chunks(b, f, p, l1, h, w, stride))
+
+
 def ftm_backward(d_out: torch.Tensor, weight: torch.Tensor, fm: FeatureMatrix, d_weight: Optional[torch.Tensor] = None,
                  d_bias: Optional[torch.Tensor] = None, dst: Optional[torch.Tensor] = None, ft: Optional[torch.Tensor] = None,
                  d_z1: Optional[torch.Tensor] = None, d_w1: Optional[torch.Tensor] = None,
-                 sq_partial: Optional[torch.Tensor] = None, buckets=None, small: Optional["NnueClsRider"] = None):
+                 sq_partial: Optional[torch.Tensor] = None, buckets=None, small: Optional["NnueClsRider"] = None, ste=None):
     """(d_weight, d_bias, d_conv_out) in one launch; bitwise the results of ftm_backward_weight + ftm_backward_values.
+    ste = (images [B, 3, H, W], conv_out, thr, stride, partial[, patches]): the value tiles also leave stage 1 of ste_conv_backward
+    as [fps * 28][ftm_backward_ste_chunks(...)] floats in `partial` (its second stage: sgd_step(ste=...)); with the im2col
+    `patches` [27, B * Gh * Gw] (ftm_conv_binarize(patches=...)) the pixel terms are read from them (the same bits);
+    d_conv_out is then stored only when `dst` is given (the third result is None otherwise).
     small (classifier_train_rider(...)): the classifier's small gradients + mean loss run as one more tile family of the launch.
     With ft [B, L1], d_z1 [B, L2] and d_w1 [L2, L1] the launch also writes d_w1 = d_z1^T l0 (the pairwise block of ft).
     buckets (a BucketPlan): d_w1 [K, L2, L1]; ft / d_z1 are then the GROUPED-row copies [tiles*16, .] the bucketed
@@ -822,10 +835,25 @@ def ftm_backward(d_out: torch.Tensor, weight: torch.Tensor, fm: FeatureMatrix, d
         d_weight = torch.empty((fm.num_rows, l1), dtype=torch.float32, device=d_out.device)
     if d_bias is None:
         d_bias = torch.empty((l1,), dtype=torch.float32, device=d_out.device)
-    if dst is None:
+    if dst is None and ste is None:
         dst = torch.empty((b, fm.positions), dtype=torch.float32, device=d_out.device)
-    elif dst.numel() != b * fm.positions:
+    elif dst is not None and dst.numel() != b * fm.positions:
         raise ValueError("ftm_backward: dst has the wrong size")
+    ste_args = (None, None, None, None, 0, 0, 0, None, 0)
+    if ste is not None:
+        images, conv_out, thr, stride, part = ste[:5]
+        patches = ste[5] if len(ste) > 5 else None
+        images = _need(images, torch.float32, "images")
+        conv_out = _need(conv_out, torch.float32, "conv_out")
+        thr = _need(thr, torch.float32, "visual_threshold")
+        if images.dim() != 4 or images.shape[:2] != (b, 3) or conv_out.numel() != b * fm.positions or part.device != d_out.device:
+            raise ValueError("ftm_backward: STE operands have the wrong shape")
+        h, w = images.shape[2], images.shape[3]
+        if patches is not None:
+            gh, gw = conv_out_hw(h, w, stride)
+            patches = _need(patches, torch.float32, "patches", (27, b * gh * gw))
+        ste_args = (images.data_ptr(), _ptr(patches), conv_out.data_ptr(), thr.data_ptr(), h, w, int(stride), part.data_ptr(),
+                    part.numel() * part.element_size())
     l2 = 0
     rows = b if buckets is None else buckets.tiles * 16
     if d_w1 is not None:
@@ -836,13 +864,13 @@ def ftm_backward(d_out: torch.Tensor, weight: torch.Tensor, fm: FeatureMatrix, d
         if ft.shape != (rows, l1) or d_z1.numel() != rows * l2 or tuple(d_w1.shape) != want or not d_w1.is_contiguous():
             raise ValueError("ftm_backward: ft / d_z1 / d_w1 shape mismatch")
     args = (fm.bits.data_ptr(), fm.sink.data_ptr(), d_out.data_ptr(), weight.data_ptr(), b, fm.num_rows,
-            fm.positions, l1, d_weight.data_ptr(), d_bias.data_ptr(), dst.data_ptr(),
+            fm.positions, l1, d_weight.data_ptr(), d_bias.data_ptr(), _ptr(dst),
             _ptr(ft if d_w1 is not None else None), _ptr(d_z1 if d_w1 is not None else None), l2, _ptr(d_w1), _ptr(sq_partial))
     rider = ctypes.pointer(small) if small is not None else None
     if buckets is None:
-        _call("nnue_ftm_backward", *args, rider, _stream(d_out))
+        _call("nnue_ftm_backward", *args, rider, *ste_args, _stream(d_out))
     else:
-        _call("nnue_ftm_backward_bucketed", *args, buckets.K, buckets.seg.data_ptr(), rows, rider, _stream(d_out))
+        _call("nnue_ftm_backward_bucketed", *args, buckets.K, buckets.seg.data_ptr(), rows, rider, *ste_args, _stream(d_out))
     return d_weight, d_bias, dst
 
 

@@ -340,6 +340,18 @@ class NnueTrainer:
             self.gram = torch.zeros((lib.ftm_gram_scratch(self.fx.g_fm),), **f32)
             self.clip_coef = torch.ones((), **f32)
         self.grads_materialised = not (self.fuse_table_update or self.factor_exchange)
+        # Single rank + SGD with the merged FeatureTransformer backward: its value-gradient tiles also reduce d_conv_out into the
+        # STE partials (stage 1 of ste_conv_backward) in their epilogue, so the STE launch disappears and d_conv_out is not
+        # stored; the second stage stays in the norm launch.  With the im2col patches the epilogue reads them instead of the images
+        # (the same bits, as the STE kernel's two forms).  NNUE_FTM_RIDE_STE=0 keeps the STE launch.
+        ste_chunks = lib.ftm_backward_ste_chunks(B, self.F, self.P, self.L1, self.H, self.W, self.stride) if self.use_mfma else 0
+        self.ride_ste = (self.defer_ste and self.merge_backward and not self.fuse_table_update
+                         and not self.factor_exchange and ste_chunks > 0 and os.environ.get("NNUE_FTM_RIDE_STE", "1") != "0")
+        if self.ride_ste:
+            self.ste_chunks = ste_chunks
+            need = self.fps * 28 * ste_chunks * 4
+            if self.ste_scratch.numel() < need:
+                self.ste_scratch = torch.empty((need,), **u8)
         # Inside a step group (step_many) the table's update of step t and the FeatureTransformer forward of step t+1 are ONE
         # pass over the table (nnue_ftm_backward_weight_update_forward: the next batch is resident, its map only needs the conv
         # weights the small tensors' update has just written, and the update leaves every new table tile in registers) -- the
@@ -479,9 +491,11 @@ class NnueTrainer:
             elif self.use_mfma and self.merge_backward:
                 # weight gradient, value gradient and tail rows share one launch (independent work, all read d_ft)
                 lib.ftm_backward(self.d_ft, p["input.weight"], self.fm, d_weight=g["input.weight"], d_bias=g["input.bias"],
-                                 dst=self.d_conv_out, ft=self.ft_rider, d_z1=self.d_z1,
+                                 dst=None if self.ride_ste else self.d_conv_out, ft=self.ft_rider, d_z1=self.d_z1,
                                  d_w1=g["classifier.classifier.0.weight"] if self.ride_dw1 else None, sq_partial=self.sq_partial,
-                                 buckets=self.bucket_plan, small=self._rider(self.loss) if self.ride_small else None)
+                                 buckets=self.bucket_plan, small=self._rider(self.loss) if self.ride_small else None,
+                                 ste=((self.images, self.conv_out, p["visual_threshold"], self.stride, self.ste_scratch, self.patches)
+                                      if self.ride_ste else None))
             elif self.use_mfma:
                 lib.ftm_backward_weight(self.d_ft, self.fm, d_weight=g["input.weight"], d_bias=g["input.bias"])
             elif self.use_bits:
@@ -500,6 +514,8 @@ class NnueTrainer:
                 lib.ftb_backward_values(self.d_ft, p["input.weight"], self.bits, dst=self.d_conv_out)
             else:
                 lib.ft_backward_values(self.d_ft, p["input.weight"], self.act, self.P, dst=self.d_conv_out)
+            if self.ride_ste:
+                return  # stage 1 rode in the merged launch ("ft_wgrad"), stage 2 rides in the norm launch
             if self.use_patches:
                 lib.ste_conv_backward_patches(self.patches, self.conv_out, p["visual_threshold"], self.d_conv_out, self.gh, self.gw,
                                               d_thr=g["visual_threshold"], d_weight=g["conv.weight"], scratch=self.ste_scratch,
