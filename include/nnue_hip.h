@@ -40,7 +40,7 @@
 extern "C" {
 #endif
 
-#define NNUE_HIP_ABI_VERSION 34
+#define NNUE_HIP_ABI_VERSION 35
 
 #define NNUE_OK 0
 #define NNUE_E_ARG (-1)     /* null pointer, non-positive size, bad alignment */
@@ -341,7 +341,11 @@ int nnue_classifier_backward(const float* x, int pairwise,
  * product and no slab sum are launched here, d_w1 is not written; with both phases in the one call (19, 27) the
  * small weight/bias gradients and the mean loss share the d_x launch -- unless 32 is added as well (51, 59): then they
  * are left to nnue_ftm_backward's launch too (its `small` argument, filled by nnue_classifier_train_rider with the same
- * tensors and scratch), and the d_x launch holds only d_x tiles.
+ * tensors and scratch), and the d_x launch holds only d_x tiles.  Adding 64 exists in that one combination only
+ * (123 = 59 + 64; any other use of bit 64 is refused as a bad phases value): the per-sample tail runs inside the d_x
+ * launch -- each d_x row tile recomputes the tail of its own 16 rows, so phase 1 is one launch -- with outputs bitwise
+ * those of 59.  It needs nnue_classifier_train_fused_tail_supported(B, L1, L2, L3, C, 1, pairwise) (else NNUE_E_SHAPE)
+ * and 16-byte aligned w2 and w3.
  * scratch >= nnue_classifier_train_scratch(B, L1, L2, L3, C) bytes. */
 int64_t nnue_classifier_train_scratch(int B, int L1, int L2, int L3, int C);
 int64_t nnue_classifier_train_dz1_offset(int B, int L1, int L2, int L3, int C, int pairwise);
@@ -354,6 +358,10 @@ int nnue_classifier_train_step(const float* x, int pairwise,
                                float* d_x, float* d_w1, float* d_b1, float* d_w2, float* d_b2,
                                float* d_w3, float* d_b3,
                                void* scratch, int64_t scratch_bytes, int phases, nnue_stream_t stream);
+/* 1 when nnue_classifier_train_step takes phases 123 at this shape (K layer stacks), 0 otherwise: K == 1, the pairwise
+ * block (nnue.py:660-666), C <= 64, L1 % 128 == 0, and L2 = 128, L3 = 32 (the widths the fused kernel is built for;
+ * nnue.py:713-738).  Other shapes keep phases 59's two launches. */
+int nnue_classifier_train_fused_tail_supported(int B, int L1, int L2, int L3, int C, int K, int pairwise);
 /* A host-side call (no launch) that fills `out` with the arguments of the small-gradient tile family for a step run with
  * phases bit 32 -- d_w3, d_w2, d_b3, d_b2, d_b1 (autograd of nnue.py:728-734) and the mean loss (train.py:250-254) then run
  * inside nnue_ftm_backward's launch (its `small` argument).  Same tensors and scratch as the train step; buckets = NULL

@@ -321,6 +321,105 @@ __global__ __launch_bounds__(256) void slab_sum_kernel(const float* __restrict__
 // d_x = (d_z1 W1) through the pairwise block ("NN": A contiguous along K = L2, B along N).  A wave
 // owns 16 samples x two 16-column tiles: columns j and j + L1/2 when pairwise (the pairwise backward
 // needs both), adjacent tiles otherwise.
+//
+// The tile's pieces are shared with tail_dx_train_kernel (which reads d_z1 out of LDS and requests its W1
+// operands before the per-sample tail runs): same operands, same MFMA order, so d_x is bitwise the same.
+// K is walked in chunks of up to 4 blocks of 16; every load of a chunk is issued before its MFMAs, so a
+// wave pays one L2 round trip per chunk (L2 = 128: two) instead of one per block
+constexpr int kBwxKC = 4;
+struct BwxChunk {
+  float4 a[kBwxKC];
+  float b0[kBwxKC][4], b1[kBwxKC][4];
+};
+
+// B operand of one 16-column tile (columns c..c+15)
+__device__ __forceinline__ void bwx_load_b_tile(float (&b)[kBwxKC][4], const float* __restrict__ w1, int kb0, int L1, int L2, int c,
+                                                int r, int q) {
+#pragma unroll
+  for (int u = 0; u < kBwxKC; ++u) {
+    const int kb = kb0 + 16 * u;
+    const bool in = kb < L2;  // wave-uniform
+    const int k = (in ? kb : 0) + 4 * q;
+    const float* __restrict__ wk = w1 + (size_t)k * L1 + r;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) b[u][e] = in ? wk[(size_t)e * L1 + c] : 0.f;
+  }
+}
+
+__device__ __forceinline__ void bwx_load_b(BwxChunk& ch, const float* __restrict__ w1, int kb0, int L1, int L2, int c0, int c1,
+                                           int r, int q) {
+  bwx_load_b_tile(ch.b0, w1, kb0, L1, L2, c0, r, q);
+  bwx_load_b_tile(ch.b1, w1, kb0, L1, L2, c1, r, q);
+}
+
+// dz: this lane's d_z1 row (global or LDS)
+__device__ __forceinline__ void bwx_load_a(BwxChunk& ch, const float* dz, bool row_ok, int kb0, int L2, int q) {
+#pragma unroll
+  for (int u = 0; u < kBwxKC; ++u) {
+    const int kb = kb0 + 16 * u;
+    const bool in = kb < L2;
+    const int k = (in ? kb : 0) + 4 * q;
+    const float4 v = *reinterpret_cast<const float4*>(dz + k);  // in bounds for every lane (a padding row reads row 0 / its own)
+    ch.a[u] = (row_ok && in) ? v : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+}
+
+__device__ __forceinline__ void bwx_mma(const BwxChunk& ch, f32x4& acc0, f32x4& acc1) {
+#pragma unroll
+  for (int u = 0; u < kBwxKC; ++u) {
+    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(ch.a[u].x, ch.b0[u][0], acc0, 0, 0, 0);
+    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(ch.a[u].x, ch.b1[u][0], acc1, 0, 0, 0);
+    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(ch.a[u].y, ch.b0[u][1], acc0, 0, 0, 0);
+    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(ch.a[u].y, ch.b1[u][1], acc1, 0, 0, 0);
+    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(ch.a[u].z, ch.b0[u][2], acc0, 0, 0, 0);
+    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(ch.a[u].z, ch.b1[u][2], acc1, 0, 0, 0);
+    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(ch.a[u].w, ch.b0[u][3], acc0, 0, 0, 0);
+    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(ch.a[u].w, ch.b1[u][3], acc1, 0, 0, 0);
+  }
+}
+
+// the MFMAs of one of the two tiles, in the order bwx_mma gives that tile's accumulator
+__device__ __forceinline__ void bwx_mma_tile(const float4 (&a)[kBwxKC], const float (&b)[kBwxKC][4], f32x4& acc) {
+#pragma unroll
+  for (int u = 0; u < kBwxKC; ++u) {
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u].x, b[u][0], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u].y, b[u][1], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u].z, b[u][2], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u].w, b[u][3], acc, 0, 0, 0);
+  }
+}
+
+// the x values the pairwise epilogue multiplies by (accumulator register e = sample orows[e])
+__device__ __forceinline__ void bwx_load_x(float (&xv0)[4], float (&xv1)[4], const float* __restrict__ x, const int (&orows)[4], int B,
+                                           int L1, int c0, int c1, int r) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const bool ok = orows[e] >= 0 && orows[e] < B;
+    const float* __restrict__ xr = x + (size_t)(ok ? orows[e] : 0) * L1;
+    const float a = xr[c0 + r], b = xr[c1 + r];  // unconditional (row 0 for a padding row): no branch per load
+    xv0[e] = ok ? a : 0.f;
+    xv1[e] = ok ? b : 0.f;
+  }
+}
+
+__device__ __forceinline__ void bwx_store(const f32x4& acc0, const f32x4& acc1, const float (&xv0)[4], const float (&xv1)[4],
+                                          const int (&orows)[4], int pairwise, int B, int L1, int c0, int c1, int r,
+                                          float* __restrict__ d_x) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int orow = orows[e];
+    if (orow < 0 || orow >= B) continue;
+    float* __restrict__ o = d_x + (size_t)orow * L1;
+    if (pairwise) {
+      o[c0 + r] = fmaf(acc0[e], xv1[e], acc1[e]);
+      o[c1 + r] = acc0[e] * xv0[e];
+    } else {
+      o[c0 + r] = acc0[e];
+      o[c1 + r] = acc1[e];
+    }
+  }
+}
+
 __device__ __forceinline__ void l1_backward_x_body(const float* __restrict__ x, int pairwise, const float* __restrict__ w1,
                                                    const float* __restrict__ d_z1, int B, int L1, int L2,
                                                    float* __restrict__ d_x, long long block, const Buckets& bk) {
@@ -351,51 +450,15 @@ __device__ __forceinline__ void l1_backward_x_body(const float* __restrict__ x, 
   const bool row_ok = row >= 0 && row < B;
   const float* __restrict__ dz = d_z1 + (size_t)(row_ok ? row : 0) * L2;
   f32x4 acc0 = (f32x4){0.f, 0.f, 0.f, 0.f}, acc1 = acc0;
-  // K is walked in chunks of up to 4 blocks of 16; every load of a chunk is issued before its MFMAs, so a
-  // wave pays one L2 round trip per chunk (L2 = 128: two) instead of one per block
-  constexpr int KC = 4;
-  for (int kb0 = 0; kb0 < L2; kb0 += 16 * KC) {  // L2 % 16 == 0
-    float4 a[KC];
-    float b0v[KC][4], b1v[KC][4];
-#pragma unroll
-    for (int u = 0; u < KC; ++u) {
-      const int kb = kb0 + 16 * u;
-      const bool in = kb < L2;  // wave-uniform
-      const int k = (in ? kb : 0) + 4 * q;
-      a[u] = (row_ok && in) ? *reinterpret_cast<const float4*>(dz + k) : make_float4(0.f, 0.f, 0.f, 0.f);
-      const float* __restrict__ wk = w1 + (size_t)k * L1 + r;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        b0v[u][e] = in ? wk[(size_t)e * L1 + c0] : 0.f;
-        b1v[u][e] = in ? wk[(size_t)e * L1 + c1] : 0.f;
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < KC; ++u) {
-      acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u].x, b0v[u][0], acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u].x, b1v[u][0], acc1, 0, 0, 0);
-      acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u].y, b0v[u][1], acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u].y, b1v[u][1], acc1, 0, 0, 0);
-      acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u].z, b0v[u][2], acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u].z, b1v[u][2], acc1, 0, 0, 0);
-      acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u].w, b0v[u][3], acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u].w, b1v[u][3], acc1, 0, 0, 0);
-    }
+  for (int kb0 = 0; kb0 < L2; kb0 += 16 * kBwxKC) {  // L2 % 16 == 0
+    BwxChunk ch;
+    bwx_load_a(ch, dz, row_ok, kb0, L2, q);
+    bwx_load_b(ch, w1, kb0, L1, L2, c0, c1, r, q);
+    bwx_mma(ch, acc0, acc1);
   }
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const int orow = orows[e];
-    if (orow < 0 || orow >= B) continue;
-    float* __restrict__ o = d_x + (size_t)orow * L1;
-    if (pairwise) {
-      const float* __restrict__ xr = x + (size_t)orow * L1;
-      o[c0 + r] = fmaf(acc0[e], xr[c1 + r], acc1[e]);
-      o[c1 + r] = acc0[e] * xr[c0 + r];
-    } else {
-      o[c0 + r] = acc0[e];
-      o[c1 + r] = acc1[e];
-    }
-  }
+  float xv0[4] = {0.f, 0.f, 0.f, 0.f}, xv1[4] = {0.f, 0.f, 0.f, 0.f};
+  if (pairwise) bwx_load_x(xv0, xv1, x, orows, B, L1, c0, c1, r);
+  bwx_store(acc0, acc1, xv0, xv1, orows, pairwise, B, L1, c0, c1, r, d_x);
 }
 
 __global__ __launch_bounds__(256) void l1_backward_w_mfma(const float* __restrict__ x, int pairwise,
@@ -518,6 +581,87 @@ __device__ __forceinline__ float block_reduce_nt(float v, bool is_max, float* re
   return r;
 }
 
+// Per-output arithmetic of the tail, shared with tail_dx_train_kernel so that both form every value with the same
+// expression (same operation order, same fma contractions) whatever the thread mapping around it.
+// One of four chains of a layer-2 / logit dot product: z += w . h over one float4 run
+__device__ __forceinline__ float tail_dot4(const float4& w, const float4& h, float z) {
+  return fmaf(w.w, h.w, fmaf(w.z, h.z, fmaf(w.y, h.y, fmaf(w.x, h.x, z))));
+}
+
+// max and sum of exp over the C <= 64 logits of N samples (lane c holds logit c of each): the same 64-lane butterflies
+// in every wave, lanes >= C add 0 / max -inf; the N samples' chains are interleaved
+template <int N>
+__device__ __forceinline__ void ce_wave_stats(const float (&v)[N], bool in, float (&mx)[N], float (&se)[N]) {
+#pragma unroll
+  for (int n = 0; n < N; ++n) mx[n] = in ? v[n] : -INFINITY;
+#pragma unroll
+  for (int sh = 32; sh >= 1; sh >>= 1)
+#pragma unroll
+    for (int n = 0; n < N; ++n) mx[n] = fmaxf(mx[n], __shfl_xor(mx[n], sh));
+#pragma unroll
+  for (int n = 0; n < N; ++n) se[n] = in ? expf(v[n] - mx[n]) : 0.0f;
+#pragma unroll
+  for (int sh = 32; sh >= 1; sh >>= 1)
+#pragma unroll
+    for (int n = 0; n < N; ++n) se[n] += __shfl_xor(se[n], sh);
+}
+
+// v of lane (lane ^ SH): the same value __shfl_xor(v, SH) gives, through DPP (SH 1, 2) or ds_swizzle (4 .. 16) instead
+// of an LDS round trip through ds_bpermute
+template <int SH>
+__device__ __forceinline__ float lane_xor(float v) {
+  const int i = __float_as_int(v);
+  if constexpr (SH == 1) return __int_as_float(__builtin_amdgcn_update_dpp(i, i, 0xB1, 0xF, 0xF, false));  // quad_perm 1,0,3,2
+  else if constexpr (SH == 2) return __int_as_float(__builtin_amdgcn_update_dpp(i, i, 0x4E, 0xF, 0xF, false));  // quad_perm 2,3,0,1
+  else if constexpr (SH < 32) return __int_as_float(__builtin_amdgcn_ds_swizzle(i, 0x1F | (SH << 10)));  // bit mode: lane ^ SH
+  else return __shfl_xor(v, SH);
+}
+
+// ce_wave_stats with lane_xor: the same butterflies (same operands, same order), cheaper exchanges
+template <int N>
+__device__ __forceinline__ void ce_wave_stats_fast(const float (&v)[N], bool in, float (&mx)[N], float (&se)[N]) {
+#pragma unroll
+  for (int n = 0; n < N; ++n) mx[n] = in ? v[n] : -INFINITY;
+#define NNUE_MAX_STEP(SH) _Pragma("unroll") for (int n = 0; n < N; ++n) mx[n] = fmaxf(mx[n], lane_xor<SH>(mx[n]));
+  NNUE_MAX_STEP(32) NNUE_MAX_STEP(16) NNUE_MAX_STEP(8) NNUE_MAX_STEP(4) NNUE_MAX_STEP(2) NNUE_MAX_STEP(1)
+#undef NNUE_MAX_STEP
+#pragma unroll
+  for (int n = 0; n < N; ++n) se[n] = in ? expf(v[n] - mx[n]) : 0.0f;
+#define NNUE_SUM_STEP(SH) _Pragma("unroll") for (int n = 0; n < N; ++n) se[n] += lane_xor<SH>(se[n]);
+  NNUE_SUM_STEP(32) NNUE_SUM_STEP(16) NNUE_SUM_STEP(8) NNUE_SUM_STEP(4) NNUE_SUM_STEP(2) NNUE_SUM_STEP(1)
+#undef NNUE_SUM_STEP
+}
+
+// d loss / d logit z of a sample with a valid label
+__device__ __forceinline__ float ce_dlogit(float z, float mx, float inv, bool is_y, float scale_over_b) {
+  return (expf(z - mx) * inv - (is_y ? 1.0f : 0.0f)) * scale_over_b;
+}
+
+// class slice cp (of S) of d_z2[j] = sum_c d_logits[c] w3[c][j]: four chains over c = cp, cp + S, ...  (w3j = w3 + j)
+template <int S>
+__device__ __forceinline__ float dz2_slice(const float* dl, const float* w3j, int cp, int C, int L3) {
+  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+  int c = cp;
+  for (; c + 3 * S < C; c += 4 * S) {
+    s0 = fmaf(dl[c], w3j[(size_t)c * L3], s0);
+    s1 = fmaf(dl[c + S], w3j[(size_t)(c + S) * L3], s1);
+    s2 = fmaf(dl[c + 2 * S], w3j[(size_t)(c + 2 * S) * L3], s2);
+    s3 = fmaf(dl[c + 3 * S], w3j[(size_t)(c + 3 * S) * L3], s3);
+  }
+  for (; c < C; c += S) s0 = fmaf(dl[c], w3j[(size_t)c * L3], s0);
+  return (s0 + s1) + (s2 + s3);
+}
+
+// the S slices of one d_z2 value in a fixed pairwise tree: (p0 + p1) + (p2 + p3) ...
+template <int S>
+__device__ __forceinline__ float slice_tree(float (&q)[S]) {
+#pragma unroll
+  for (int w = 1; w < S; w *= 2)
+#pragma unroll
+    for (int i = 0; i + w < S; i += 2 * w) q[i] += q[i + w];
+  return q[0];
+}
+
 // NT threads per sample: 128 for the usual class counts, 512 when C is large (1000 classes at 224x224: the logits,
 // the softmax and the d_z2 sum are then 4x wider per pass).
 template <int NT, bool VEC>
@@ -595,7 +739,6 @@ __global__ __launch_bounds__(NT) void tail_train_kernel(const float* __restrict_
     h1[(size_t)b * L2 + j] = h;
   }
   __syncthreads();
-  auto dot4 = [](const float4& w, const float4& h, float z) { return fmaf(w.w, h.w, fmaf(w.z, h.z, fmaf(w.y, h.y, fmaf(w.x, h.x, z)))); };
   for (int j0 = 0; j0 < L3; j0 += NT / 4) {
     const int j = j0 + og;
     float z = 0.f;
@@ -607,11 +750,11 @@ __global__ __launch_bounds__(NT) void tail_train_kernel(const float* __restrict_
 #pragma unroll
           for (int i = 0; i < kPre2; ++i) {
             const int kk = 4 * (part4 + 4 * i);
-            if (kk < L2) z = dot4(w2v[i], *reinterpret_cast<const float4*>(h1s + kk), z);
+            if (kk < L2) z = tail_dot4(w2v[i], *reinterpret_cast<const float4*>(h1s + kk), z);
           }
           k += 16 * kPre2;
         }
-        for (; k < L2; k += 16) z = dot4(*reinterpret_cast<const float4*>(wr + k), *reinterpret_cast<const float4*>(h1s + k), z);
+        for (; k < L2; k += 16) z = tail_dot4(*reinterpret_cast<const float4*>(wr + k), *reinterpret_cast<const float4*>(h1s + k), z);
       } else {
         for (int k = part4; k < L2; k += 4) z = fmaf(wr[k], h1s[k], z);
       }
@@ -636,11 +779,11 @@ __global__ __launch_bounds__(NT) void tail_train_kernel(const float* __restrict_
 #pragma unroll
           for (int i = 0; i < kPre3; ++i) {
             const int kk = 4 * (part4 + 4 * i);
-            if (kk < L3) z = dot4(w3v[i], *reinterpret_cast<const float4*>(h2s + kk), z);
+            if (kk < L3) z = tail_dot4(w3v[i], *reinterpret_cast<const float4*>(h2s + kk), z);
           }
           k += 16 * kPre3;
         }
-        for (; k < L3; k += 16) z = dot4(*reinterpret_cast<const float4*>(wr + k), *reinterpret_cast<const float4*>(h2s + k), z);
+        for (; k < L3; k += 16) z = tail_dot4(*reinterpret_cast<const float4*>(wr + k), *reinterpret_cast<const float4*>(h2s + k), z);
       } else {
         for (int k = part4; k < L3; k += 4) z = fmaf(wr[k], h2s[k], z);
       }
@@ -658,13 +801,11 @@ __global__ __launch_bounds__(NT) void tail_train_kernel(const float* __restrict_
   float mx = -INFINITY, se = 0.f;
   if (C <= 64) {  // every wave forms the same two reductions by itself: no block barriers
     const int lane = tid & 63;
-    const float v = lane < C ? lgs[lane] : -INFINITY;
-    mx = v;
-#pragma unroll
-    for (int sh = 32; sh >= 1; sh >>= 1) mx = fmaxf(mx, __shfl_xor(mx, sh));
-    se = lane < C ? expf(v - mx) : 0.0f;
-#pragma unroll
-    for (int sh = 32; sh >= 1; sh >>= 1) se += __shfl_xor(se, sh);
+    const float v[1] = {lane < C ? lgs[lane] : -INFINITY};
+    float m1[1], s1[1];
+    ce_wave_stats<1>(v, lane < C, m1, s1);
+    mx = m1[0];
+    se = s1[0];
   } else {
     for (int c = tid; c < C; c += NT) mx = fmaxf(mx, lgs[c]);
     mx = block_reduce_nt<NT>(mx, true, red);
@@ -676,7 +817,7 @@ __global__ __launch_bounds__(NT) void tail_train_kernel(const float* __restrict_
   const float inv = 1.0f / se;
   __syncthreads();  // every thread has read lgs[y] / the logits it needs before they are overwritten
   for (int c = tid; c < C; c += NT) {
-    const float g = ok ? (expf(lgs[c] - mx) * inv - (c == y ? 1.0f : 0.0f)) * scale_over_b : 0.0f;
+    const float g = ok ? ce_dlogit(lgs[c], mx, inv, c == y, scale_over_b) : 0.0f;
     lgs[c] = g;
     d_logits[(size_t)b * C + c] = g;
   }
@@ -685,29 +826,13 @@ __global__ __launch_bounds__(NT) void tail_train_kernel(const float* __restrict_
   // (a single serial chain over C = 1000 classes cost 60 us of the 224x224 configuration's step)
   for (int j0 = 0; j0 < L3; j0 += 32) {
     const int j = j0 + (tid & 31), cp = tid >> 5;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    if (j < L3) {
-      const float* __restrict__ wc = w3 + j;
-      int c = cp;
-      for (; c + 3 * S < C; c += 4 * S) {
-        s0 = fmaf(lgs[c], wc[(size_t)c * L3], s0);
-        s1 = fmaf(lgs[c + S], wc[(size_t)(c + S) * L3], s1);
-        s2 = fmaf(lgs[c + 2 * S], wc[(size_t)(c + 2 * S) * L3], s2);
-        s3 = fmaf(lgs[c + 3 * S], wc[(size_t)(c + 3 * S) * L3], s3);
-      }
-      for (; c < C; c += S) s0 = fmaf(lgs[c], wc[(size_t)c * L3], s0);
-    }
-    part_s[cp][tid & 31] = (s0 + s1) + (s2 + s3);
+    part_s[cp][tid & 31] = j < L3 ? dz2_slice<S>(lgs, w3 + j, cp, C, L3) : 0.0f;
     __syncthreads();
     if (cp == 0 && j < L3) {
       float q[S];
 #pragma unroll
       for (int i = 0; i < S; ++i) q[i] = part_s[i][tid];
-#pragma unroll
-      for (int w = 1; w < S; w *= 2)  // fixed pairwise tree: (p0 + p1) + (p2 + p3) ...
-#pragma unroll
-        for (int i = 0; i + w < S; i += 2 * w) q[i] += q[i + w];
-      const float v = gate_fn(q[0], h2s[j], clip);
+      const float v = gate_fn(slice_tree<S>(q), h2s[j], clip);
       dz2s[j] = v;
       d_z2[(size_t)b * L3 + j] = v;
     }
@@ -731,6 +856,306 @@ __global__ __launch_bounds__(NT) void tail_train_kernel(const float* __restrict_
   __syncthreads();
 }
 
+// ------------------------------------------------------------------ fused tail + d_x (training, phases bit 64)
+// The per-sample tail above and the d_x product in ONE launch.  A d_x tile of 16 rows only needs d_z1 of those rows,
+// and d_z1 only needs their layer-1 slabs, the small weights and the labels, so the workgroup that forms a d_x tile
+// runs the tail for its own 16 rows first instead of waiting for a separate launch.  Workgroup = one 16-row tile x one
+// column group of 4 pairs of 16-column tiles (c0, c0 + L1/2), one tile per wave.  Every workgroup of a row tile runs
+// the same tail; the one of column group 0 writes its outputs (h1, h2, logits, sample_loss, d_logits, d_z2, d_z1 --
+// what the merged FeatureTransformer backward's riders read), the others keep d_z1 in LDS only.
+//
+// Each output is formed by the expressions tail_train_kernel<128, true> uses, in its order: slab sum in slab order,
+// four tail_dot4 chains combined by xor 1 then xor 2, the 64-lane softmax butterflies, dz2_slice<4> + slice_tree<4>,
+// d_z1 serially in row order -- and d_x by the l1_backward_x_body pieces: bitwise the two launches.
+//
+// Loads: the W1 column slice, the x values of the pairwise epilogue, the small weights, biases, labels and the tile's
+// first 16 slabs are all requested at entry (one dependent load level).  Placement: blocks are numbered so that all
+// column groups of a row tile share blockIdx % 8 (round-robin dispatch puts them on one XCD, whose L2 then serves the 7
+// repeated reads of the tile's 128 KB of slabs); results do not depend on it.
+constexpr int kTdxRows = 16, kTdxThreads = 512, kTdxMaxC = 64;
+
+// dz2_slice<S> for C <= kTdxMaxC with its tail loop unrolled and predicated (same fmas in the same order): the
+// per-lane trip counts of the loop form made every thread wait out one LDS round trip per class
+template <int S>
+__device__ __forceinline__ float dz2_slice_small(const float* dl, const float* w3j, int cp, int C, int L3) {
+  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+  int c = cp;
+  for (int m = 0, mu = C > 3 * S ? (C - 3 * S + 4 * S - 1) / (4 * S) : 0; m < mu; ++m) {  // uniform bound (cp = 0)
+    const bool act = c + 3 * S < C;
+    const int cc = act ? c : 0;
+    const float f0 = fmaf(dl[cc], w3j[(size_t)cc * L3], s0), f1 = fmaf(dl[cc + S], w3j[(size_t)(cc + S) * L3], s1);
+    const float f2 = fmaf(dl[cc + 2 * S], w3j[(size_t)(cc + 2 * S) * L3], s2), f3 = fmaf(dl[cc + 3 * S], w3j[(size_t)(cc + 3 * S) * L3], s3);
+    s0 = act ? f0 : s0; s1 = act ? f1 : s1; s2 = act ? f2 : s2; s3 = act ? f3 : s3;
+    c = act ? c + 4 * S : c;
+  }
+#pragma unroll
+  for (int t = 0; t < 3; ++t) {  // c + 3S >= C here: at most three classes are left
+    const bool act = c + S * t < C;
+    const int cc = act ? c + S * t : 0;
+    const float f = fmaf(dl[cc], w3j[(size_t)cc * L3], s0);
+    s0 = act ? f : s0;
+  }
+  return (s0 + s1) + (s2 + s3);
+}
+
+template <int L2, int L3>
+__global__ __launch_bounds__(kTdxThreads) void tail_dx_train_kernel(
+    const float* __restrict__ part, int ksplit, const float* __restrict__ b1, const float* __restrict__ w2,
+    const float* __restrict__ b2, const float* __restrict__ w3, const float* __restrict__ b3, float clip,
+    const int64_t* __restrict__ labels, float scale_over_b, int B, int C, float* __restrict__ h1, float* __restrict__ h2,
+    float* __restrict__ logits, float* __restrict__ sample_loss, float* __restrict__ d_logits, float* __restrict__ d_z1,
+    float* __restrict__ d_z2, const float* __restrict__ x, const float* __restrict__ w1, int L1, float* __restrict__ d_x,
+    int m_tiles, int n_cg) {
+  constexpr int T = kTdxRows, NT = kTdxThreads, NWAVE = NT / 64;
+  constexpr int NI = T * L2 / 4 / NT;       // float4 slots of the tile's slab rows per thread
+  constexpr int NCH = L2 / (16 * kBwxKC);   // K chunks of the d_x product
+  constexpr int RP = NT / 4 / L3;           // rows per pass of the four-thread dot products
+  static_assert(NI >= 1 && NI * NT * 4 == T * L2 && NT % L2 == 0 && L3 % 16 == 0 && (NT / 4) % L3 == 0 && T % RP == 0,
+                "tail_dx_train_kernel: unsupported layer widths");
+  __shared__ float4 w2s4[L3 * L2 / 4];  // w2 [L3][L2]
+  __shared__ float4 w3s4[kTdxMaxC * L3 / 4];  // w3 [C][L3]
+  __shared__ __attribute__((aligned(16))) float h1s[T][L2];
+  __shared__ __attribute__((aligned(16))) float dz1s[T][L2];
+  __shared__ __attribute__((aligned(16))) float h2s[T][L3];
+  __shared__ float dz2s[T][L3];
+  __shared__ float ps[T][4][L3];
+  __shared__ float lgs[T][kTdxMaxC];  // logits, then d_logits
+  __shared__ float b2s[L3], b3s[kTdxMaxC];
+  __shared__ int64_t ys[T];
+  __shared__ f32x4 xch[NWAVE][64];  // d_x accumulators swapped between the two waves of a pair
+  const float* w2s = reinterpret_cast<const float*>(w2s4);
+  const float* w3s = reinterpret_cast<const float*>(w3s4);
+
+  const int blk = blockIdx.x, slot = blk >> 3;
+  const int mt = (slot / n_cg) * 8 + (blk & 7), cg = slot % n_cg;
+  if (mt >= m_tiles) return;  // whole workgroup (the numbering rounds the tile count up to a multiple of 8)
+  const bool writer = cg == 0;
+  const int row0 = mt * T;
+  const int tid = threadIdx.x;
+
+  // ---- the d_x operands: a pair of 16-column tiles (c0, c0 + L1/2) per two waves, one tile per wave; this wave's W1
+  // column slice and the x values of its epilogue are requested first and used after the tail
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int lane = tid & 63;
+  const int r = lane & 15, q = lane >> 4;
+  const int half = L1 / 2;
+  const int hi = wave & 1;  // 0: tile c0 (acc0 of l1_backward_x_body), 1: tile c1 (acc1)
+  const int c0 = (cg * (NWAVE / 2) + (wave >> 1)) * 16, c1 = c0 + half, cm = hi ? c1 : c0;
+  int orows[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) orows[e] = row0 + 4 * q + e;
+  float bw[NCH][kBwxKC][4];
+#pragma unroll
+  for (int n = 0; n < NCH; ++n) bwx_load_b_tile(bw[n], w1, n * 16 * kBwxKC, L1, L2, cm, r, q);
+  float xv[4];  // the c1 tile's wave multiplies by x[c0], the c0 tile's by x[c1]
+#pragma unroll
+  for (int e = 0; e < 4; ++e) xv[e] = x[(size_t)min(orows[e], B - 1) * L1 + (hi ? c0 : c1) + r];  // a padding row stores nothing
+
+  // ---- then the small weights, biases, labels and the slabs.  Every load is unconditional from an in-bounds
+  // address and masked afterwards: a guarded load becomes a branch with a wait of its own.
+  constexpr int NW2 = L3 * L2 / 4 / NT;  // float4 of w2 per thread
+  constexpr int NW3 = kTdxMaxC * L3 / 4 / NT;
+  static_assert(NW2 >= 1 && NW2 * NT * 4 == L3 * L2 && NW3 >= 1 && NW3 * NT * 4 == kTdxMaxC * L3, "tail_dx_train_kernel: staging shape");
+  float4 w2v[NW2], w3v[NW3];
+#pragma unroll
+  for (int i = 0; i < NW2; ++i) w2v[i] = reinterpret_cast<const float4*>(w2)[tid + NT * i];
+  const int n_w3 = C * L3 / 4;
+#pragma unroll
+  for (int i = 0; i < NW3; ++i) w3v[i] = reinterpret_cast<const float4*>(w3)[min(tid + NT * i, n_w3 - 1)];
+  const float b2v = b2[tid % L3];
+  const float b3v = b3[min(tid, C - 1)];
+  const int64_t yv = labels[min(row0 + (tid % T), B - 1)];
+  int srow[NI], scol[NI];
+  float4 z4[NI];
+  const float* prow[NI];  // this thread's slab row (a padding row of the last tile reads row B - 1: it feeds no output)
+#pragma unroll
+  for (int i = 0; i < NI; ++i) {
+    const int f = tid + NT * i;
+    srow[i] = f / (L2 / 4);
+    scol[i] = 4 * (f % (L2 / 4));
+    prow[i] = part + (size_t)min(row0 + srow[i], B - 1) * L2 + scol[i];
+    z4[i] = make_float4(b1[scol[i]], b1[scol[i] + 1], b1[scol[i] + 2], b1[scol[i] + 3]);
+  }
+  // z = b1[j] + part[0] + part[1] + ... in slab order, in batches of 16 slabs whose loads are all in flight together (a
+  // slab past the end re-reads the last one and is not added -- skipped, not added as 0, which would turn a -0 into +0)
+  const size_t slab = (size_t)B * L2;
+  auto load_batch = [&](int s0, float4 (&v)[NI][16]) {
+#pragma unroll
+    for (int i = 0; i < NI; ++i)
+#pragma unroll
+      for (int u = 0; u < 16; ++u) v[i][u] = *reinterpret_cast<const float4*>(prow[i] + (size_t)min(s0 + u, ksplit - 1) * slab);
+  };
+  auto sum_batch = [&](int s0, const float4 (&v)[NI][16]) {
+#pragma unroll
+    for (int i = 0; i < NI; ++i)
+#pragma unroll
+      for (int u = 0; u < 16; ++u) {
+        const bool add = s0 + u < ksplit;  // uniform
+        z4[i].x = add ? z4[i].x + v[i][u].x : z4[i].x;
+        z4[i].y = add ? z4[i].y + v[i][u].y : z4[i].y;
+        z4[i].z = add ? z4[i].z + v[i][u].z : z4[i].z;
+        z4[i].w = add ? z4[i].w + v[i][u].w : z4[i].w;
+      }
+  };
+  {
+    float4 v[NI][16];
+    load_batch(0, v);
+    // the staged weights go to LDS while the first batch is in flight (their loads were issued before it)
+#pragma unroll
+    for (int i = 0; i < NW2; ++i) w2s4[tid + NT * i] = w2v[i];
+#pragma unroll
+    for (int i = 0; i < NW3; ++i)
+      if (tid + NT * i < n_w3) w3s4[tid + NT * i] = w3v[i];
+    if (tid < L3) b2s[tid] = b2v;
+    if (tid < C) b3s[tid] = b3v;
+    if (tid < T) ys[tid] = row0 + tid < B ? yv : -1;
+    sum_batch(0, v);
+  }
+  for (int s0 = 16; s0 < ksplit; s0 += 16) {
+    float4 v[NI][16];
+    load_batch(s0, v);
+    sum_batch(s0, v);
+  }
+
+  // ---- h1 = act(z)
+#pragma unroll
+  for (int i = 0; i < NI; ++i) {
+    float4 h;
+    h.x = act_fn(z4[i].x, clip); h.y = act_fn(z4[i].y, clip); h.z = act_fn(z4[i].z, clip); h.w = act_fn(z4[i].w, clip);
+    *reinterpret_cast<float4*>(&h1s[srow[i]][scol[i]]) = h;
+    if (writer && row0 + srow[i] < B) *reinterpret_cast<float4*>(h1 + (size_t)(row0 + srow[i]) * L2 + scol[i]) = h;
+  }
+  __syncthreads();
+
+  const int part4 = tid & 3, og = tid >> 2;  // four threads per dot product
+  // ---- h2 = act(w2 h1 + b2): unit j = og % L3 (its w2 row held in registers), RP rows per pass
+  {
+    const int j = og % L3;
+    float4 wf[L2 / 16];
+#pragma unroll
+    for (int m = 0; m < L2 / 16; ++m) wf[m] = w2s4[(j * L2 + 4 * part4 + 16 * m) / 4];
+    const float bj = b2s[j];
+#pragma unroll
+    for (int it = 0; it < T / RP; ++it) {  // compile-time trip count: the rows' chains interleave
+      const int rr = og / L3 + RP * it;
+      float z = 0.f;
+#pragma unroll
+      for (int m = 0; m < L2 / 16; ++m) z = tail_dot4(wf[m], *reinterpret_cast<const float4*>(&h1s[rr][4 * part4 + 16 * m]), z);
+      z += lane_xor<1>(z);
+      z += lane_xor<2>(z);
+      if (part4 == 0) {
+        const float h = act_fn(z + bj, clip);
+        h2s[rr][j] = h;
+        if (writer && row0 + rr < B) h2[(size_t)(row0 + rr) * L3 + j] = h;
+      }
+    }
+  }
+  __syncthreads();
+  // ---- logits = w3 h2 + b3
+  for (int o0 = 0; o0 < T * C; o0 += NT / 4) {  // uniform trip count: the shuffles need every lane
+    const int o = o0 + og;
+    const bool v = o < T * C;
+    const int rr = v ? o / C : 0, c = v ? o - rr * C : 0;
+    float z = 0.f;
+#pragma unroll
+    for (int k = 4 * part4; k < L3; k += 16)
+      z = tail_dot4(*reinterpret_cast<const float4*>(w3s + c * L3 + k), *reinterpret_cast<const float4*>(&h2s[rr][k]), z);
+    z = v ? z : 0.f;
+    z += lane_xor<1>(z);
+    z += lane_xor<2>(z);
+    if (v && part4 == 0) {
+      z += b3s[c];
+      lgs[rr][c] = z;
+      if (writer && row0 + rr < B) logits[(size_t)(row0 + rr) * C + c] = z;
+    }
+  }
+  __syncthreads();
+  // ---- softmax cross-entropy and d_logits: rows wave, wave + NWAVE, ... of the tile (interleaved), lane = class
+  {
+    constexpr int RW = T / NWAVE;
+    const bool in = lane < C;
+    float v[RW], mx[RW], se[RW];
+#pragma unroll
+    for (int it = 0; it < RW; ++it) v[it] = in ? lgs[wave + NWAVE * it][lane] : -INFINITY;
+    ce_wave_stats_fast<RW>(v, in, mx, se);
+#pragma unroll
+    for (int it = 0; it < RW; ++it) {
+      const int rr = wave + NWAVE * it;
+      const int64_t y = ys[rr];
+      const bool ok = y >= 0 && y < C;
+      const float zy = ok ? lgs[rr][y] : 0.f;  // read by every lane before any lane overwrites its logit
+      if (writer && lane == 0 && row0 + rr < B) sample_loss[row0 + rr] = ok ? nnue_ce_sample_loss(mx[it], zy, se[it]) : 0.0f;
+      const float inv = 1.0f / se[it];
+      if (in) {
+        const float g = ok ? ce_dlogit(v[it], mx[it], inv, lane == y, scale_over_b) : 0.0f;
+        lgs[rr][lane] = g;
+        if (writer && row0 + rr < B) d_logits[(size_t)(row0 + rr) * C + lane] = g;
+      }
+    }
+  }
+  __syncthreads();
+  // ---- d_z2 = gate(w3^T d_logits): four class slices per value, then the fixed tree
+#pragma unroll
+  for (int it = 0; it < T * 4 * L3 / NT; ++it) {
+    const int i = tid + NT * it;
+    const int j = i % L3, cp = (i / L3) & 3, rr = i / (4 * L3);
+    ps[rr][cp][j] = dz2_slice_small<4>(lgs[rr], w3s + j, cp, C, L3);
+  }
+  __syncthreads();
+#pragma unroll
+  for (int it = 0; it < (T * L3 + NT - 1) / NT; ++it) {
+    const int i = tid + NT * it, rr = i / L3, j = i % L3;
+    if (i < T * L3) {
+      float qv[4] = {ps[rr][0][j], ps[rr][1][j], ps[rr][2][j], ps[rr][3][j]};
+      const float v = gate_fn(slice_tree<4>(qv), h2s[rr][j], clip);
+      dz2s[rr][j] = v;
+      if (writer && row0 + rr < B) d_z2[(size_t)(row0 + rr) * L3 + j] = v;
+    }
+  }
+  __syncthreads();
+  // ---- d_z1 = gate(w2^T d_z2): unit k = tid % L2 (its w2 column in registers), serial in row order
+  {
+    const int k = tid % L2;
+    float wc[L3];
+#pragma unroll
+    for (int j = 0; j < L3; ++j) wc[j] = w2s[j * L2 + k];
+#pragma unroll
+    for (int it = 0; it < T * L2 / NT; ++it) {
+      const int rr = tid / L2 + (NT / L2) * it;
+      float s = 0.f;
+#pragma unroll
+      for (int j = 0; j < L3; ++j) s = fmaf(dz2s[rr][j], wc[j], s);
+      const float v = gate_fn(s, h1s[rr][k], clip);
+      dz1s[rr][k] = v;
+      if (writer && row0 + rr < B) d_z1[(size_t)(row0 + rr) * L2 + k] = v;
+    }
+  }
+  __syncthreads();
+  // ---- d_x: this wave's tile with l1_backward_x_body's operands and MFMA order, then the pairwise epilogue with the
+  // partner wave's accumulator
+  {
+    const bool row_ok = row0 + r < B;
+    f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int n = 0; n < NCH; ++n) {
+      BwxChunk ch;
+      bwx_load_a(ch, &dz1s[r][0], row_ok, n * 16 * kBwxKC, L2, q);
+      bwx_mma_tile(ch.a, bw[n], acc);
+    }
+    xch[wave][lane] = acc;
+    __syncthreads();
+    const f32x4 other = xch[wave ^ 1][lane];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int orow = orows[e];
+      if (orow >= B) continue;
+      float* __restrict__ o = d_x + (size_t)orow * L1;
+      if (hi) o[c1 + r] = other[e] * xv[e];           // acc0 * x[c0]
+      else o[c0 + r] = fmaf(acc[e], xv[e], other[e]);  // fma(acc0, x[c1], acc1)
+    }
+  }
+}
+
 // ------------------------------------------------------------------ shape policy (shared by scratch + launch)
 struct ClsPlan {
   bool fwd_mfma, bww_mfma, bwx_mfma;
@@ -739,6 +1164,12 @@ struct ClsPlan {
 };
 
 int bucket_tiles(int B, int K) { return (B + 15) / 16 + K; }  // sum_k ceil(c_k / 16) <= B / 16 + K
+
+// tail_dx_train_kernel's shapes: one layer stack, the pairwise block, whole 4-wave column groups, a wave per row of
+// logits, and the layer widths it is instantiated for (those of every shipped configuration)
+bool tail_dx_supported(int B, int L1, int L2, int L3, int C, int K, int pairwise) {
+  return B > 0 && K == 1 && pairwise && L1 > 0 && L1 % 128 == 0 && C >= 1 && C <= kTdxMaxC && L2 == 128 && L3 == 32;
+}
 
 ClsPlan make_plan(int B, int L1, int L2, int pairwise, int K = 1) {
   ClsPlan p{};
@@ -1004,10 +1435,14 @@ int train_step_impl(const float* x, int pairwise, const float* w1, const float* 
                     nnue_stream_t stream) {
   NNUE_REQUIRE(x && w1 && b1 && w2 && b2 && w3 && b3 && labels && h1 && h2 && logits && sample_loss && loss && scratch,
                NNUE_E_ARG, "nnue_classifier_train_step: null pointer");
+  // bit 64 exists in one combination only: 123 = 59 + the per-sample tail inside the d_x launch
+  const bool fuse_tail = phases == 123;
+  if (fuse_tail) phases = 59;
   NNUE_REQUIRE(phases >= 1 && phases <= 63 && (phases & 3) && (phases & 20) != 20 && (!(phases & 32) || (phases & 19) == 19), NNUE_E_ARG,
                "nnue_classifier_train_step: phases = 1 (activations + d_x) | 2 (weight gradients + loss) [| 4: first-layer weight product beside "
                "d_x] [| 8: layer-1 slabs already at the start of scratch] [| 16 (not with 4): d_w1 comes from nnue_ftm_backward] [| 32 (with 1, 2 "
-               "and 16): the small gradients and the mean loss ride in nnue_ftm_backward's launch as well]");
+               "and 16): the small gradients and the mean loss ride in nnue_ftm_backward's launch as well] [| 64 (only as 123 = 59 + 64): the "
+               "per-sample tail runs in the d_x launch]");
   const bool ext_dw1 = (phases & 16) != 0;
   const bool ext_small = (phases & 32) != 0;
   const bool ext_slabs = (phases & 8) != 0;
@@ -1055,6 +1490,18 @@ int train_step_impl(const float* x, int pairwise, const float* w1, const float* 
   const bool wgrad_rides = (phases & 3) == 3 && ext_dw1 && p.bwx_mfma && d_x != nullptr;
   NNUE_REQUIRE(!ext_small || wgrad_rides, NNUE_E_SHAPE,
                "nnue_classifier_train_step: phases bit 32 needs the d_x launch the small gradients otherwise ride in (MFMA shapes, d_x requested)");
+  NNUE_REQUIRE(!fuse_tail || tail_dx_supported(B, L1, L2, L3, C, K, pairwise), NNUE_E_SHAPE,
+               "nnue_classifier_train_step: phases 123 (tail inside the d_x launch) needs nnue_classifier_train_fused_tail_supported "
+               "(B=%d L1=%d L2=%d L3=%d C=%d K=%d pairwise=%d)", B, L1, L2, L3, C, K, pairwise);
+  NNUE_REQUIRE(!fuse_tail || (nnue_aligned16(w2) && nnue_aligned16(w3)), NNUE_E_ARG,
+               "nnue_classifier_train_step: phases 123 needs 16-byte aligned w2 and w3");
+  if (fuse_tail) {  // phases 123: the slabs are in scratch, d_w1 and the small gradients ride in nnue_ftm_backward's launch
+    const int n_cg = L1 / 32 / (kTdxThreads / 128);  // pairs of 16-column tiles / pairs per workgroup
+    hipLaunchKernelGGL((tail_dx_train_kernel<128, 32>), dim3((m_tiles + 7) / 8 * 8 * n_cg), dim3(kTdxThreads), 0, s, part, L1 / 64, b1, w2, b2,
+                       w3, b3, clip, labels, grad_scale / (float)B, B, C, h1, h2, logits, sample_loss, d_logits, d_z1, d_z2, x, w1, L1, d_x,
+                       m_tiles, n_cg);
+    return nnue_launch_status("nnue_classifier_train_step");
+  }
   if (phases & 1) {
     if (ext_slabs) {
       // part[L1/64][B][L2] was written by nnue_ftm_forward_l1 (the FeatureTransformer forward's epilogue)
@@ -1125,6 +1572,10 @@ extern "C" int64_t nnue_classifier_train_scratch_bucketed(int B, int L1, int L2,
   const int64_t a = train_layout(make_plan(B, L1, L2, 0, K), B, L1, L2, L3, C, K).total;
   const int64_t b = train_layout(make_plan(B, L1, L2, 1, K), B, L1, L2, L3, C, K).total;
   return (a > b ? a : b) * (int64_t)sizeof(float);
+}
+
+extern "C" int nnue_classifier_train_fused_tail_supported(int B, int L1, int L2, int L3, int C, int K, int pairwise) {
+  return tail_dx_supported(B, L1, L2, L3, C, K, pairwise) ? 1 : 0;
 }
 
 extern "C" int64_t nnue_classifier_train_dz1_offset(int B, int L1, int L2, int L3, int C, int pairwise) {

@@ -16,7 +16,7 @@ import torch
 
 _HERE = Path(__file__).resolve().parent
 LIB_PATH = _HERE / "libnnue_hip.so"
-ABI_VERSION = 34
+ABI_VERSION = 35
 
 _c_int, _c_i64, _c_f, _c_p = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
 
@@ -106,6 +106,7 @@ SIGNATURES = {
                                           _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p]),
     "nnue_classifier_train_scratch": (_c_i64, [_c_int, _c_int, _c_int, _c_int, _c_int]),
     "nnue_classifier_train_dz1_offset": (_c_i64, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int]),
+    "nnue_classifier_train_fused_tail_supported": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int]),
     "nnue_classifier_train_step": (_c_int, [_c_p, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_f, _c_p, _c_f,
                                             _c_int, _c_int, _c_int, _c_int, _c_int,
                                             _c_p, _c_p, _c_p, _c_p, _c_p,
@@ -1008,6 +1009,12 @@ def classifier_train_scratch_bytes(b: int, l1: int, l2: int, l3: int, c: int, bu
 def classifier_train_dz1_offset(b: int, l1: int, l2: int, l3: int, c: int, pairwise: bool) -> int:
     """Byte offset of d_z1 [B, L2] inside the classifier's training scratch (valid after phase 1)."""
     return int(load().nnue_classifier_train_dz1_offset(b, l1, l2, l3, c, int(bool(pairwise))))
+
+
+def classifier_train_fused_tail_supported(b: int, l1: int, l2: int, l3: int, c: int, buckets: int = 1, pairwise: bool = True) -> bool:
+    """Whether classifier_train_step accepts phases 123 (59 with the per-sample tail inside the d_x launch) at this shape."""
+    return bool(load().nnue_classifier_train_fused_tail_supported(int(b), int(l1), int(l2), int(l3), int(c), int(buckets),
+                                                                  int(bool(pairwise))))
 
 
 def classifier_train_grouped_offsets(b: int, l1: int, l2: int, l3: int, c: int, buckets: int):

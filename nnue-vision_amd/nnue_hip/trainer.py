@@ -380,6 +380,10 @@ class NnueTrainer:
         # ... and so do the classifier's small gradients + mean loss (one more tile family of that launch; the classifier's d_x
         # launch then holds only d_x tiles).  NNUE_CLS_RIDE_SMALL=0 keeps them beside d_x.
         self.ride_small = self.ride_dw1 and os.environ.get("NNUE_CLS_RIDE_SMALL", "1") != "0"
+        # ... and then the classifier's per-sample tail runs inside its d_x launch (phases 123: each d_x row tile recomputes the
+        # tail of its own 16 rows; bitwise the two launches).  NNUE_CLS_FUSE_TAIL_DX=0 keeps the two launches.
+        self.fuse_tail_dx = (self.fuse_l1 and self.ride_small and os.environ.get("NNUE_CLS_FUSE_TAIL_DX", "1") != "0"
+                             and lib.classifier_train_fused_tail_supported(B, self.L1, self.L2, self.L3, self.C, self.K))
         self._riders = {}  # mean-loss destination -> host struct (kept alive: recorded plans hold pointers to them)
 
     # ------------------------------------------------------------------ hyper-parameters
@@ -469,7 +473,8 @@ class NnueTrainer:
                 # the forward's epilogue also forms the classifier's layer-1 slabs (start of its scratch)
                 lib.ftm_forward_l1(p["input.weight"], p["input.bias"], self.fm, p["classifier.classifier.0.weight"], self.cls_scratch,
                                    out=self.ft)
-                self._cls_step((59 if self.ride_small else 27) if self.ride_dw1 else 13)  # 27: both phases, d_w1 left to the merged backward; + 32: the small gradients too
+                # 27: both phases, d_w1 left to the merged backward; + 32: the small gradients too; + 64: the tail in the d_x launch
+                self._cls_step((123 if self.fuse_tail_dx else 59 if self.ride_small else 27) if self.ride_dw1 else 13)
                 return
             if self.use_mfma:
                 lib.ftm_forward(p["input.weight"], p["input.bias"], self.fm, out=self.ft, group=self.bucket_plan)
