@@ -40,7 +40,7 @@
 extern "C" {
 #endif
 
-#define NNUE_HIP_ABI_VERSION 35
+#define NNUE_HIP_ABI_VERSION 36
 
 #define NNUE_OK 0
 #define NNUE_E_ARG (-1)     /* null pointer, non-positive size, bad alignment */
@@ -500,6 +500,29 @@ int nnue_ftm_backward_weight_update_forward(const uint8_t* bits, const float* d_
                                             const uint8_t* bits_next, const float* sink_next, int B_next, const float* bias,
                                             float* out_next, void* scratch, int64_t scratch_bytes, nnue_stream_t stream);
 
+/* The same two passes for the reference's other optimizer, torch.optim.Adam (create_optimizer, train.py:465-471): the product
+ * d_W = A^T d_out (autograd of nnue.py:702-708) and, element by element in its epilogue, clip_grad_norm_ + Adam
+ *     g = coef[0]*grad_scale*d_W + wd*w ;  m = b1 m + (1-b1) g ;  v = b2 v + (1-b2) g^2
+ *     w -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps)                                  (train.py:363-366, :465-470)
+ * on table rows [0, direct) and the matching rows of exp_avg / exp_avg_sq (16-byte aligned) -- the arithmetic of
+ * nnue_adam_step -- so d_weight is never written or read back.  t = step_counter[0] is read, not advanced: run it after
+ * nnue_adam_step_ext(ext_applied_elsewhere = 1) of the same step, which advances the counter and leaves coef.  lr_dev as in
+ * nnue_sgd_step.  Rejected like nnue_adam_step: betas outside [0,1), eps <= 0; B*L1 > 2^24 (the Gram norm's limit): NNUE_E_SHAPE. */
+int nnue_ftm_backward_weight_update_adam(const uint8_t* bits, const float* d_out, int B, int F, int P, int L1,
+                                         float* weight, float* exp_avg_rows, float* exp_avg_sq_rows, const float* coef,
+                                         const int32_t* step_counter, float lr, float beta1, float beta2, float eps,
+                                         float weight_decay, float grad_scale, const float* lr_dev, nnue_stream_t stream);
+/* nnue_ftm_backward_weight_update_adam of step t and nnue_ftm_forward of step t+1 in ONE pass over the table (train.py:465-470 +
+ * FeatureTransformer.forward, nnue.py:686-710, of the next loop iteration): arguments and shapes as
+ * nnue_ftm_backward_weight_update_forward (nnue_ftm_update_forward_supported is the shape query for both); table, both moments
+ * and out_next are BITWISE what the two separate calls produce. */
+int nnue_ftm_backward_weight_update_forward_adam(const uint8_t* bits, const float* d_out, int B, int F, int P, int L1,
+                                                 float* weight, float* exp_avg_rows, float* exp_avg_sq_rows, const float* coef,
+                                                 const int32_t* step_counter, float lr, float beta1, float beta2, float eps,
+                                                 float weight_decay, float grad_scale, const float* lr_dev,
+                                                 const uint8_t* bits_next, const float* sink_next, int B_next, const float* bias,
+                                                 float* out_next, void* scratch, int64_t scratch_bytes, nnue_stream_t stream);
+
 /* Reporting only: 1 when the product of this shape runs on the bf16 matrix unit (exact three-way split of the f32
  * operand), 0 on the f32 MFMA.  which: 0 forward, 1 stand-alone weight gradient, 2 weight-gradient tiles of the merged
  * backward launch, 3 weight gradient with the update in its epilogue; 4 stand-alone value gradient, 5 value-gradient tiles
@@ -667,6 +690,18 @@ int nnue_adam_step(float* params, float* grads, float* exp_avg, float* exp_avg_s
                    int64_t count, float lr, float beta1, float beta2, float eps, float weight_decay,
                    float max_norm, float grad_scale, float* norm_out,
                    void* scratch, int64_t scratch_bytes, const float* lr_dev, nnue_stream_t stream);
+
+/* nnue_adam_step with what nnue_sgd_step offers a producer of part of the gradient (clip_grad_norm_ + Adam, train.py:363-366,
+ * :465-470; the arithmetic and the step counter of nnue_adam_step): ext_partial / ext_count / ext_lo / ext_hi / coef_out /
+ * ext_applied_elsewhere exactly as there -- the norm launch skips grads[ext_lo, ext_hi) and takes that range's share from the
+ * producer's partials (nnue_ftm_gram_sqnorm), the clip coefficient is left in coef_out, and with ext_applied_elsewhere the
+ * apply pass touches neither params nor the moments in that range (nnue_ftm_backward_weight_update_adam applies it, reading
+ * coef_out and step_counter).  The counter is advanced once, by the norm launch. */
+int nnue_adam_step_ext(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int32_t* step_counter,
+                       int64_t count, float lr, float beta1, float beta2, float eps, float weight_decay,
+                       float max_norm, float grad_scale, float* norm_out, void* scratch, int64_t scratch_bytes,
+                       const float* ext_partial, int ext_count, int64_t ext_lo, int64_t ext_hi,
+                       float* coef_out, int ext_applied_elsewhere, const float* lr_dev, nnue_stream_t stream);
 
 /* clip_grad_norm_ + SGD(momentum, weight_decay) over a LIST of n separate tensors -- torch.optim's parameter list with its
  * param groups, as the reference's loop steps it (train.py:363-366; the optimizer of create_optimizer, train.py:455-471):

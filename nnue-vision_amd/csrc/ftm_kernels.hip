@@ -33,6 +33,7 @@ namespace {
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 #include "bucket_group.h"  // the bucketed stacks' selector + grouping: rides as one extra workgroup of the forward launch
+#include "optim_update.h"  // adam_update_fused and the bias corrections: one header with the optimizer kernels (optim_kernels.hip)
 
 // Row-major matrix seen as (outer, inner), read through a buffer descriptor: 16-byte loads at (outer, inner..inner+3),
 // hardware range check instead of branches -- rows past the end of the `bytes` window read as zero (that is how K
@@ -131,6 +132,26 @@ struct BwwSgdEpi {
     }
     weight[i] = w - (lr_dev ? lr_dev[0] : lr) * gi;
   }
+};
+
+// The same for the reference's other optimizer: clip_grad_norm_ + torch.optim.Adam (train.py:363-366, :465-470) applied to
+// the table rows and their two moments in place, element by element adam_apply_kernel's arithmetic with its fused multiply-adds
+// pinned (adam_update_fused: bitwise the fused update + forward pass, within a rounding per term of adam_update).  The
+// step number is the device counter the optimizer's norm launch has already advanced (nnue_adam_step_ext), so nothing in
+// the launch changes from step to step.  Only the bf16-split tiles take it (rmw_tile_adam).
+struct BwwAdamEpi {
+  static constexpr bool kFusedL1 = false;
+  static constexpr bool kRmw = true;
+  static constexpr bool kAdam = true;
+  float* __restrict__ weight;      // table rows [0, direct), updated in place
+  float* __restrict__ exp_avg;     // matching first-moment rows
+  float* __restrict__ exp_avg_sq;  // matching second-moment rows
+  const float* __restrict__ coef;  // clip coefficient (device scalar)
+  const int* __restrict__ step_counter;  // step_counter[0] = t of this step
+  int L1;
+  float lr, beta1, beta2, eps, wd, scale;
+  int xcd_remap;
+  const float* __restrict__ lr_dev;
 };
 
 struct ValEpi {  // d_conv_out = acc where the position is active, else 0
@@ -580,6 +601,72 @@ __device__ __forceinline__ void rmw_tile(float* __restrict__ smem, const Epi& ep
   }
 }
 
+template <class Epi, class = void>
+struct is_adam { static constexpr bool value = false; };
+template <class Epi>
+struct is_adam<Epi, decltype((void)Epi::kAdam)> { static constexpr bool value = Epi::kAdam; };
+
+// rmw_tile for BwwAdamEpi: three streams read and three written per tile (parameters, exp_avg, exp_avg_sq), 96 KB in flight
+// per workgroup at 128 x 64.  As there: every load of the tile is requested after the K loop and before the first result is
+// combined; here they go through buffer descriptors whose window ends at table row M, so no load or store sits behind a
+// branch (an element past the tile's rows or columns gets an offset outside the window: it reads zero and its stores are
+// dropped) and one s_waitcnt covers them; non-temporal, touched once per step.  The bias corrections (two double-precision
+// pow) are formed once per workgroup -- a workgroup owns one tile -- BEFORE the loads are requested: formed while the 96
+// registers of the three streams are in flight, pow's temporaries take the 128 x 64 kernel from 136 to 147 VGPRs (+ 32 AGPRs)
+// and from three waves per SIMD to two.
+template <int BM, int BN, class Epi>
+__device__ __forceinline__ void rmw_tile_adam(float* __restrict__ smem, const Epi& epi, const f32x4 (&acc)[BM / 32][BN / 32], int M, int N,
+                                              int m_base, int n_base, int m0, int n0) {
+  constexpr int TM = BM / 32, TN = BN / 32, LD = BN + 4, PER = BM * BN / 4 / 256;
+  constexpr int kOut = 0x7ff00000;  // a byte offset outside every window (the entry point checks the table against it)
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int r = lane & 15, q = lane >> 4;
+  const unsigned bytes = (unsigned)((size_t)M * epi.L1 * 4);
+  const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc(epi.weight, 0, bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsm = __builtin_amdgcn_make_buffer_rsrc(epi.exp_avg, 0, bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsv = __builtin_amdgcn_make_buffer_rsrc(epi.exp_avg_sq, 0, bytes, 0x00020000);
+  auto off_of = [&](int u) {
+    const int idx = tid + 256 * u, row = idx / (BN / 4), c4 = idx % (BN / 4);
+    const int m = m_base + row, n = n_base + 4 * c4;
+    return (m < M && n < N) ? (m * epi.L1 + n) * 4 : kOut;
+  };
+  const float gs = epi.coef[0] * epi.scale;
+  const float lr = epi.lr_dev ? epi.lr_dev[0] : epi.lr;
+  const AdamBias bc = adam_bias_correction(lr, epi.beta1, epi.beta2, epi.step_counter[0]);
+  u32x4 w[PER], mo[PER], vv[PER];
+#pragma unroll
+  for (int u = 0; u < PER; ++u) w[u] = __builtin_amdgcn_raw_buffer_load_b128(rsw, off_of(u), 0, 2);
+#pragma unroll
+  for (int u = 0; u < PER; ++u) mo[u] = __builtin_amdgcn_raw_buffer_load_b128(rsm, off_of(u), 0, 2);
+#pragma unroll
+  for (int u = 0; u < PER; ++u) vv[u] = __builtin_amdgcn_raw_buffer_load_b128(rsv, off_of(u), 0, 2);
+#pragma unroll
+  for (int i = 0; i < TM; ++i)
+#pragma unroll
+    for (int t = 0; t < TN; ++t)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) smem[(m0 + 16 * i + 4 * q + e) * LD + n0 + 16 * t + r] = acc[i][t][e];
+  __syncthreads();
+#pragma unroll
+  for (int u = 0; u < PER; ++u) {
+    const int idx = tid + 256 * u, row = idx / (BN / 4), c4 = idx % (BN / 4);
+    const float4 g = *reinterpret_cast<const float4*>(smem + row * LD + 4 * c4);
+    const float gv[4] = {g.x, g.y, g.z, g.w};
+    u32x4 wn, mn, vn;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {  // the arithmetic of adam_apply_kernel, element by element (fused multiply-adds pinned)
+      float mi = __uint_as_float(mo[u][e]), vi = __uint_as_float(vv[u][e]);
+      wn[e] = __float_as_uint(adam_update_fused(__uint_as_float(w[u][e]), gv[e], mi, vi, gs, bc, epi.beta1, epi.beta2, epi.eps, epi.wd));
+      mn[e] = __float_as_uint(mi);
+      vn[e] = __float_as_uint(vi);
+    }
+    const int off = off_of(u);
+    __builtin_amdgcn_raw_buffer_store_b128(mn, rsm, off, 0, 2);
+    __builtin_amdgcn_raw_buffer_store_b128(vn, rsv, off, 0, 2);
+    __builtin_amdgcn_raw_buffer_store_b128(wn, rsw, off, 0, 2);
+  }
+}
+
 // One BM x BN output tile (linear tile index `tile`, K slab `ks`) by the 256 threads of a workgroup; `smem` is the
 // workgroup's LDS (gemm_lds_floats() floats, 16-byte aligned).
 // The tile contracts k in [k_lo, k_hi); `ks` only names the split-K slab the epilogue stores to.
@@ -941,7 +1028,8 @@ __device__ __forceinline__ void gemm_tile_bf(unsigned char* __restrict__ smem, c
   if constexpr (Epi::kFusedL1) {
     fused_l1_epilogue<BM>(epi, l1pre, reinterpret_cast<float*>(smem), acc, m_base, tile_n, m0, n0, r, q, wave, tid);
   } else if constexpr (is_rmw<Epi>::value) {
-    rmw_tile<BM, BN, Epi>(reinterpret_cast<float*>(smem), epi, acc, M, N, m_base, n_base, m0, n0);
+    if constexpr (is_adam<Epi>::value) rmw_tile_adam<BM, BN, Epi>(reinterpret_cast<float*>(smem), epi, acc, M, N, m_base, n_base, m0, n0);
+    else rmw_tile<BM, BN, Epi>(reinterpret_cast<float*>(smem), epi, acc, M, N, m_base, n_base, m0, n0);
   } else {
     store_tile<BM, BN, Epi>(reinterpret_cast<float*>(smem), epi, acc, M, N, m_base, n_base, m0, n0, tile, ks);
   }
@@ -1106,7 +1194,8 @@ __device__ __forceinline__ void gemm_tile_bf64(unsigned char* __restrict__ smem,
     contract();
     __syncthreads();
   }
-  if constexpr (is_rmw<Epi>::value) rmw_tile<BM, BN, Epi>(reinterpret_cast<float*>(smem), epi, acc, M, N, m_base, n_base, m0, n0);
+  if constexpr (is_adam<Epi>::value) rmw_tile_adam<BM, BN, Epi>(reinterpret_cast<float*>(smem), epi, acc, M, N, m_base, n_base, m0, n0);
+  else if constexpr (is_rmw<Epi>::value) rmw_tile<BM, BN, Epi>(reinterpret_cast<float*>(smem), epi, acc, M, N, m_base, n_base, m0, n0);
   else store_tile<BM, BN, Epi>(reinterpret_cast<float*>(smem), epi, acc, M, N, m_base, n_base, m0, n0, tile, ks);
 }
 
@@ -2459,6 +2548,93 @@ extern "C" int nnue_ftm_backward_weight_update_forward(const uint8_t* bits, cons
   hipLaunchKernelGGL(ftm_finish_kernel, dim3((unsigned)((count4 + 255) / 256)), dim3(256), 0, st, static_cast<const float*>(scratch), s.ksplit, count4,
                      bias, weight + (size_t)(F - 1) * L1, sink_next, L1, out_next);
   return nnue_launch_status("nnue_ftm_backward_weight_update_forward");
+}
+
+// ---- ... and with Adam (train.py:465-470): BwwAdamEpi / the kAdam form of the fused pass -----------------------------------------
+namespace {
+// what nnue_adam_step rejects, and the tables the branch-free epilogue can address
+int adam_table_args_ok(const char* who, const void* exp_avg_rows, const void* exp_avg_sq_rows, const void* step_counter, int B, int F, int P,
+                       int L1, float beta1, float beta2, float eps) {
+  NNUE_REQUIRE(exp_avg_rows && exp_avg_sq_rows && step_counter, NNUE_E_ARG, "%s: null pointer", who);
+  NNUE_REQUIRE(nnue_aligned16(exp_avg_rows) && nnue_aligned16(exp_avg_sq_rows), NNUE_E_ARG, "%s: the moment rows must be 16-byte aligned", who);
+  NNUE_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps > 0.f, NNUE_E_ARG, "%s: betas must be in [0,1) and eps > 0", who);
+  NNUE_REQUIRE(shape_ok(B, F, P, L1), NNUE_E_ARG, "%s: B=%d F=%d P=%d L1=%d out of range", who, B, F, P, L1);
+  NNUE_REQUIRE(nnue_ftm_supported(F, P, L1), NNUE_E_SHAPE, "%s: P=%d and L1=%d must be multiples of 4", who, P, L1);
+  NNUE_REQUIRE((int64_t)B * L1 <= (1 << 24), NNUE_E_SHAPE, "%s: B=%d x L1=%d exceeds 2^24 (the Gram form of the clip norm)", who, B, L1);
+  NNUE_REQUIRE((int64_t)F * L1 * 4 <= 0x7ff00000ll, NNUE_E_SHAPE, "%s: table of %d x %d floats is too large", who, F, L1);
+  return NNUE_OK;
+}
+}  // namespace
+
+extern "C" int nnue_ftm_backward_weight_update_adam(const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight,
+                                                    float* exp_avg_rows, float* exp_avg_sq_rows, const float* coef,
+                                                    const int32_t* step_counter, float lr, float beta1, float beta2, float eps,
+                                                    float weight_decay, float grad_scale, const float* lr_dev, nnue_stream_t stream) {
+  const char* who = "nnue_ftm_backward_weight_update_adam";
+  NNUE_REQUIRE(bits && d_out && weight && coef, NNUE_E_ARG, "%s: null pointer", who);
+  if (const int rc = adam_table_args_ok(who, exp_avg_rows, exp_avg_sq_rows, step_counter, B, F, P, L1, beta1, beta2, eps)) return rc;
+  NNUE_REQUIRE(nnue_aligned16(bits) && nnue_aligned16(d_out) && nnue_aligned16(weight), NNUE_E_ARG, "%s: pointers must be 16-byte aligned", who);
+  const int direct = (F - 1 < P) ? F - 1 : P;
+  if (direct <= 0) return NNUE_OK;
+  Shape s = plan(direct, L1, B, false, false, true);
+  if (s.cfg < 6) {  // launch-sized product: a 64-row bf16 tile (the in-place epilogue lives in the bf16 tile)
+    s.cfg = 7; s.bm = 64; s.bn = 64; s.bk = kBfK;
+    s.tiles_m = (direct + 63) / 64; s.tiles_n = (L1 + 63) / 64; s.ksplit = 1; s.klen = (B + kBfK - 1) / kBfK * kBfK;
+  }
+  NNUE_REQUIRE(s.ksplit == 1, NNUE_E_SHAPE, "%s: the product must not be split along K", who);
+  static const int xcd = env_int("NNUE_FTM_XCD_REMAP", 1);   // developer knobs, as nnue_ftm_backward_weight_update
+  static const int kt64 = env_int("NNUE_FTM_BF_KT64", 1);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const Mat ma{bits, (unsigned)((size_t)B * P), P, kIntMax, kIntMax}, mb{d_out, (unsigned)((size_t)B * L1 * 4), L1, kIntMax, kIntMax};
+  const BwwAdamEpi epi{weight, exp_avg_rows, exp_avg_sq_rows, coef, step_counter, L1, lr, beta1, beta2, eps, weight_decay, grad_scale, xcd, lr_dev};
+  const dim3 grid((unsigned)(s.tiles_m * s.tiles_n), 1u);
+  // only the bf16-split tiles carry the in-place epilogue (launch<>'s default branch without the f32 tiles)
+  if (s.cfg == 6) hipLaunchKernelGGL((ftm_gemm_bf_kernel<32, 64, false, BwwAdamEpi>), grid, dim3(256), 0, st, ma, mb, epi, direct, L1, B, s.klen, s.tiles_n, GroupArgs{});
+  else if (s.cfg == 7) hipLaunchKernelGGL((ftm_gemm_bf_kernel<64, 64, false, BwwAdamEpi>), grid, dim3(256), 0, st, ma, mb, epi, direct, L1, B, s.klen, s.tiles_n, GroupArgs{});
+  else if (kt64) hipLaunchKernelGGL((ftm_gemm_bf64_kernel<false, BwwAdamEpi>), grid, dim3(256), 0, st, ma, mb, epi, direct, L1, B, s.klen, s.tiles_n);
+  else hipLaunchKernelGGL((ftm_gemm_bf_kernel<128, 64, false, BwwAdamEpi>), grid, dim3(256), 0, st, ma, mb, epi, direct, L1, B, s.klen, s.tiles_n, GroupArgs{});
+  return nnue_launch_status(who);
+}
+
+extern "C" int nnue_ftm_backward_weight_update_forward_adam(const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight,
+                                                            float* exp_avg_rows, float* exp_avg_sq_rows, const float* coef,
+                                                            const int32_t* step_counter, float lr, float beta1, float beta2, float eps,
+                                                            float weight_decay, float grad_scale, const float* lr_dev,
+                                                            const uint8_t* bits_next, const float* sink_next, int B_next, const float* bias,
+                                                            float* out_next, void* scratch, int64_t scratch_bytes, nnue_stream_t stream) {
+  const char* who = "nnue_ftm_backward_weight_update_forward_adam";
+  NNUE_REQUIRE(bits && d_out && weight && coef && bits_next && sink_next && bias && out_next && scratch, NNUE_E_ARG, "%s: null pointer", who);
+  if (const int rc = adam_table_args_ok(who, exp_avg_rows, exp_avg_sq_rows, step_counter, B, F, P, L1, beta1, beta2, eps)) return rc;
+  NNUE_REQUIRE(nnue_ftm_update_forward_supported(B, B_next, F, P, L1), NNUE_E_SHAPE,
+               "%s: B=%d B_next=%d F=%d P=%d L1=%d is not a split-K forward over a big table (use the two separate calls)", who, B, B_next, F, P, L1);
+  NNUE_REQUIRE(nnue_aligned16(bits) && nnue_aligned16(bits_next) && nnue_aligned16(d_out) && nnue_aligned16(weight) && nnue_aligned16(bias) &&
+                   nnue_aligned16(out_next) && nnue_aligned16(scratch),
+               NNUE_E_ARG, "%s: pointers must be 16-byte aligned", who);
+  NNUE_REQUIRE(bits != bits_next, NNUE_E_ARG, "%s: the two maps must be different buffers", who);
+  const int direct = (F - 1 < P) ? F - 1 : P;
+  const Shape s = plan(B_next, L1, direct, true, true, true);
+  const int64_t need = (int64_t)s.ksplit * B_next * L1 * (int64_t)sizeof(float);
+  NNUE_REQUIRE(scratch_bytes >= need, NNUE_E_SCRATCH, "%s: scratch %lld < %lld bytes", who, (long long)scratch_bytes, (long long)need);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  static const int xcd = env_int("NNUE_FTM_XCD_REMAP", 1);  // developer knob
+  const int blocks = s.tiles_n * s.ksplit;
+  UpdFwdAdam a{};
+  static_cast<UpdFwd&>(a) = UpdFwd{bits, bits_next, d_out, weight, exp_avg_rows, coef, lr_dev, static_cast<float*>(scratch), B, B_next, P, L1, direct, s.klen,
+                                   s.tiles_n, (xcd && s.ksplit % 8 == 0) ? 1 : 0, lr, 0.0f, weight_decay, grad_scale, env_int("NNUE_FTM_UF_ABL", 0)};
+  a.exp_avg_sq = exp_avg_sq_rows;
+  a.step_counter = step_counter;
+  a.beta1 = beta1; a.beta2 = beta2; a.eps = eps;
+  switch ((B + 63) / 64) {
+    case 1: hipLaunchKernelGGL((ftm_update_forward_kernel<1, true, false, true>), dim3((unsigned)blocks), dim3(256), 0, st, a); break;
+    case 2: hipLaunchKernelGGL((ftm_update_forward_kernel<2, true, false, true>), dim3((unsigned)blocks), dim3(256), 0, st, a); break;
+    case 4: hipLaunchKernelGGL((ftm_update_forward_kernel<4, true, false, true>), dim3((unsigned)blocks), dim3(256), 0, st, a); break;
+    case 8: hipLaunchKernelGGL((ftm_update_forward_kernel<8, true, false, true>), dim3((unsigned)blocks), dim3(256), 0, st, a); break;
+    default: hipLaunchKernelGGL((ftm_update_forward_kernel<16, true, false, true>), dim3((unsigned)blocks), dim3(256), 0, st, a); break;
+  }
+  const int64_t count4 = (int64_t)B_next * L1 / 4;
+  hipLaunchKernelGGL(ftm_finish_kernel, dim3((unsigned)((count4 + 255) / 256)), dim3(256), 0, st, static_cast<const float*>(scratch), s.ksplit, count4,
+                     bias, weight + (size_t)(F - 1) * L1, sink_next, L1, out_next);
+  return nnue_launch_status(who);
 }
 
 // Which matrix unit a product of this shape runs on (the launch policy above, for reporting: bench.py prices a kernel

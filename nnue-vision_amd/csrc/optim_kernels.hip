@@ -96,32 +96,7 @@ __device__ __forceinline__ float clip_coefficient(float norm, float max_norm) {
   return c > 1.0f ? 1.0f : c;
 }
 
-// The per-element arithmetic of clip_grad_norm_ + SGD (train.py:363-366, :457-464), shared by the flat and the multi-tensor
-// kernels: g <- gs*g + wd*w; m <- first ? g : momentum*m + g (has_m: momentum != 0); returns w - lr*m.
-__device__ __forceinline__ float sgd_update(float w, float g, float m_old, float& m_new, float gs, float lr, float momentum,
-                                            float wd, bool has_m, bool first) {
-  float gi = fmaf(wd, w, g * gs);
-  if (has_m) gi = first ? gi : fmaf(momentum, m_old, gi);
-  m_new = gi;
-  return w - lr * gi;
-}
-
-// ... and of clip_grad_norm_ + Adam (train.py:363-366, :465-470): L2 weight decay folded into the gradient, the moments
-// updated in place, the bias corrections of step t precomputed by adam_bias_correction.
-struct AdamBias {
-  float step_size, inv_sqrt_bc2;
-};
-__device__ __forceinline__ AdamBias adam_bias_correction(float lr, float beta1, float beta2, int t) {
-  const double bc1 = 1.0 - pow((double)beta1, (double)t), bc2 = 1.0 - pow((double)beta2, (double)t);
-  return {(float)((double)lr / bc1), (float)(1.0 / sqrt(bc2))};
-}
-__device__ __forceinline__ float adam_update(float w, float g, float& m, float& v, float gs, AdamBias bc, float beta1, float beta2,
-                                             float eps, float wd) {
-  const float gi = fmaf(wd, w, g * gs);
-  m = beta1 * m + (1.0f - beta1) * gi;
-  v = beta2 * v + (1.0f - beta2) * gi * gi;
-  return w - bc.step_size * (m / (sqrtf(v) * bc.inv_sqrt_bc2 + eps));
-}
+#include "optim_update.h"  // sgd_update, AdamBias, adam_bias_correction, adam_update: shared with the product epilogues
 
 // Block partial of sum (g * scale)^2: 16-byte loads, four independent chains per thread (the 268 MB gradient of
 // the 224x224 configuration is one streaming read; a dependent scalar chain reached only 1.25 TB/s).
@@ -391,6 +366,59 @@ __global__ __launch_bounds__(256) void adam_apply_kernel(float* __restrict__ p, 
   const AdamBias bc = adam_bias_correction(lr, beta1, beta2, step_counter[0]);
   const int64_t stride = (int64_t)gridDim.x * 256;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < count; i += stride) {
+    float mi = m[i], vi = v[i];
+    p[i] = adam_update(p[i], g[i], mi, vi, gs, bc, beta1, beta2, eps, wd);
+    m[i] = mi;
+    v[i] = vi;
+  }
+}
+
+// The two launches of nnue_adam_step_ext: the norm launch skips [lo, hi) of the gradient (a producer left that range's sums of
+// squares), the apply pass adds the producer's partials to the norm, leaves the clip coefficient in coef_out and -- with
+// skip_lo < skip_hi -- does not touch that range (its producer applies the update itself).  Otherwise adam_apply_kernel.
+__global__ __launch_bounds__(256) void sqnorm_stage1_count_skip(const float* __restrict__ g, int64_t count, float scale,
+                                                                float* __restrict__ partial, int* __restrict__ step_counter, int64_t lo,
+                                                                int64_t hi) {
+  __shared__ float red[4];
+  if (blockIdx.x == 0 && threadIdx.x == 0) step_counter[0] += 1;
+  const float v = sqnorm_block_partial_skip(g, count, scale, red, blockIdx.x, gridDim.x, lo, hi);
+  if (threadIdx.x == 0) partial[blockIdx.x] = v;
+}
+
+__global__ __launch_bounds__(256) void adam_apply_ext_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                             float* __restrict__ v, int64_t count, float lr, float beta1, float beta2,
+                                                             float eps, float wd, float max_norm, float scale,
+                                                             const int* __restrict__ step_counter, const float* __restrict__ partial,
+                                                             int nparts, float* __restrict__ norm_out,
+                                                             const float* __restrict__ ext_partial, int ext_count,
+                                                             float* __restrict__ coef_out, int64_t skip_lo, int64_t skip_hi,
+                                                             const float* __restrict__ lr_dev) {
+  __shared__ double red[4];
+  __shared__ float coef_s;
+  if (lr_dev) lr = lr_dev[0];
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < nparts; i += 256) acc += (double)partial[i];
+  if (ext_partial) {  // a producer's sums of squares (unscaled) of the range the norm launch skipped
+    const double s2 = (double)scale * (double)scale;
+    for (int i = threadIdx.x; i < ext_count; i += 256) acc += (double)ext_partial[i] * s2;
+  }
+#pragma unroll
+  for (int s = 32; s >= 1; s >>= 1) acc += __shfl_xor(acc, s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const float norm = (float)sqrt((red[0] + red[1]) + (red[2] + red[3]));
+    if (norm_out && blockIdx.x == 0) *norm_out = norm;
+    coef_s = clip_coefficient(norm, max_norm);
+    if (coef_out && blockIdx.x == 0) *coef_out = coef_s;  // for the producer that applies [skip_lo, skip_hi) itself
+  }
+  __syncthreads();
+  const float gs = coef_s * scale;
+  const AdamBias bc = adam_bias_correction(lr, beta1, beta2, step_counter[0]);
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  const int64_t hole = skip_hi - skip_lo, live = count - hole;  // hole 0: everything is updated here
+  for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < live; j += stride) {
+    const int64_t i = j < skip_lo ? j : j + hole;
     float mi = m[i], vi = v[i];
     p[i] = adam_update(p[i], g[i], mi, vi, gs, bc, beta1, beta2, eps, wd);
     m[i] = mi;
@@ -773,6 +801,43 @@ extern "C" int nnue_sgd_step(float* params, float* grads, float* momentum_buf, i
   hipLaunchKernelGGL(sgd_apply_kernel, dim3(blocks), dim3(256), 0, s, params, grads, mom, count, lr, momentum, weight_decay, max_norm, grad_scale,
                      first_step, partial, nparts, norm_out, ext_partial, ext_count, coef_out, skip_lo, skip_hi, lr_dev);
   return nnue_launch_status("nnue_sgd_step");
+}
+
+extern "C" int nnue_adam_step_ext(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int32_t* step_counter, int64_t count,
+                                  float lr, float beta1, float beta2, float eps, float weight_decay, float max_norm, float grad_scale,
+                                  float* norm_out, void* scratch, int64_t scratch_bytes, const float* ext_partial, int ext_count,
+                                  int64_t ext_lo, int64_t ext_hi, float* coef_out, int ext_applied_elsewhere, const float* lr_dev,
+                                  nnue_stream_t stream) {
+  NNUE_REQUIRE(params && grads && exp_avg && exp_avg_sq && step_counter && scratch, NNUE_E_ARG, "nnue_adam_step_ext: null pointer");
+  NNUE_REQUIRE(count > 0, NNUE_E_ARG, "nnue_adam_step_ext: count must be positive");
+  NNUE_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps > 0.f, NNUE_E_ARG,
+               "nnue_adam_step_ext: betas must be in [0,1) and eps > 0");
+  NNUE_REQUIRE(scratch_bytes >= nnue_sgd_scratch(count), NNUE_E_SCRATCH, "nnue_adam_step_ext: scratch %lld < %lld bytes",
+               (long long)scratch_bytes, (long long)nnue_sgd_scratch(count));
+  NNUE_REQUIRE(!ext_applied_elsewhere || (ext_partial && coef_out), NNUE_E_ARG,
+               "nnue_adam_step_ext: ext_applied_elsewhere needs the producer's partials and coef_out");
+  if (ext_partial) {
+    NNUE_REQUIRE(ext_count > 0 && ext_count <= 65536 && ext_lo >= 0 && ext_lo < ext_hi && ext_hi <= count && ext_lo % 4 == 0 &&
+                     (ext_hi % 4 == 0 || ext_hi == count),
+                 NNUE_E_ARG, "nnue_adam_step_ext: producer partials need 0 < count <= 65536 and a range [lo, hi) of multiples of 4 inside grads");
+  } else {
+    ext_lo = ext_hi = 0;
+    ext_count = 0;
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  float* partial = static_cast<float*>(scratch);
+  int nb = (int)((count + 4095) / 4096);  // as nnue_sgd_step: 16 floats per thread, 64 .. kNormBlocks workgroups
+  nb = nb < 64 ? 64 : (nb > kNormBlocks ? kNormBlocks : nb);
+  // (always launched: it also advances the step counter)
+  hipLaunchKernelGGL(sqnorm_stage1_count_skip, dim3(nb), dim3(256), 0, s, grads, count, grad_scale, partial, step_counter, ext_lo, ext_hi);
+  const int64_t live = ext_applied_elsewhere ? count - (ext_hi - ext_lo) : count;
+  int blocks = (int)((live + 1023) / 1024);
+  blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
+  const int64_t skip_lo = ext_applied_elsewhere ? ext_lo : 0, skip_hi = ext_applied_elsewhere ? ext_hi : 0;
+  hipLaunchKernelGGL(adam_apply_ext_kernel, dim3(blocks), dim3(256), 0, s, params, grads, exp_avg, exp_avg_sq, count, lr, beta1, beta2, eps,
+                     weight_decay, max_norm, grad_scale, step_counter, partial, nb, norm_out, ext_partial, ext_count, coef_out, skip_lo, skip_hi,
+                     lr_dev);
+  return nnue_launch_status("nnue_adam_step_ext");
 }
 
 extern "C" int nnue_confusion_accumulate(const float* logits, const int64_t* labels, int B, int C, uint64_t* confusion,

@@ -1,4 +1,4 @@
-// The big table's SGD update of step t and the FeatureTransformer forward of step t+1 in ONE pass over the table
+// The big table's SGD (or Adam: kAdam below) update of step t and the FeatureTransformer forward of step t+1 in ONE pass over the table
 // (include inside ftm_kernels.hip's anonymous namespace, after gemm_tile_bf64 and its helpers).
 //
 // At the 224x224 shape the table (65 536 x 1024 f32, 268 MB) is streamed three times per step: by the forward, by the value
@@ -34,6 +34,13 @@ struct UpdFwd {
   float lr, mom, wd, scale;
   int abl;  // timing-only ablations (NNUE_ABLATIONS builds): 1 no parameter/momentum loads, 2 no stores, 4 no forward phase, 8 no d_W MFMAs
 };
+// The Adam form (torch.optim.Adam, train.py:465-470): `momentum` holds the exp_avg rows; the step number is the device counter
+// the optimizer's norm launch has already advanced, so the launch replays from a graph.
+struct UpdFwdAdam : UpdFwd {
+  float* __restrict__ exp_avg_sq;           // second-moment rows matching `momentum` (= exp_avg)
+  const int* __restrict__ step_counter;     // step_counter[0] = t of this step
+  float beta1, beta2, eps;
+};
 
 constexpr int kUfLds = 64 * 1024;
 // Images (byte offsets in the workgroup's LDS); the phases of a tile alias each other:
@@ -57,8 +64,16 @@ __device__ __forceinline__ int uf_wp_img(int row, int chunk) { return row * 256 
 // memory instruction makes the compiler's wait counts the minimum over both paths: with such branches the waits for the map
 // tiles also drained the parameter and momentum loads that had been requested after them, i.e. the HBM latency was exposed
 // once per tile.
-template <int kNK, bool kMom, bool kFirst>
-__global__ __launch_bounds__(256, 2) void ftm_update_forward_kernel(UpdFwd a) {
+//
+// kAdam (the argument is UpdFwdAdam; kMom = true, kFirst = false): phase 2 applies adam_update_fused instead, with a third
+// table-sized stream, the second moment.  Held like the other two from one tile's phase 3 to the next tile's phase 2 it would be 32 more registers
+// on the 226 of the momentum form -- more than a wave has at two workgroups per CU -- so it is requested later, after the
+// LAST stage1() of the tile's phase 1: the 24 registers of the staged factors (rat, rb) and the plane temporaries are dead
+// from there on, and the final contract1(), the barrier, the accumulators' trip through LDS and stage3() lie between the
+// request and its first use.  Compiled: 226-235 VGPRs over the kNK forms (230 at kNK = 2), no scratch, 64 KB LDS, two workgroups
+// per CU as the SGD forms.  The bias corrections (two double-precision pow) are formed once, at entry.
+template <int kNK, bool kMom, bool kFirst, bool kAdam = false>
+__global__ __launch_bounds__(256, 2) void ftm_update_forward_kernel(std::conditional_t<kAdam, UpdFwdAdam, UpdFwd> a) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[kUfLds];
   constexpr int KT = kBf64K, PB = 64 * KT * 2;
   constexpr int kOut = 0x7ff00000;  // a byte offset outside every buffer window
@@ -93,6 +108,8 @@ __global__ __launch_bounds__(256, 2) void ftm_update_forward_kernel(UpdFwd a) {
   const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc(a.weight, 0, (unsigned)((size_t)a.direct * L1 * 4), 0x00020000);
   const __amdgpu_buffer_rsrc_t rsm = __builtin_amdgcn_make_buffer_rsrc(kMom ? a.momentum : a.weight, 0, kMom ? (unsigned)((size_t)a.direct * L1 * 4) : 0u,
                                                                        0x00020000);
+  __amdgpu_buffer_rsrc_t rsv = rsm;  // second moment (Adam only)
+  if constexpr (kAdam) rsv = __builtin_amdgcn_make_buffer_rsrc(a.exp_avg_sq, 0, (unsigned)((size_t)a.direct * L1 * 4), 0x00020000);
   const int m0 = (wave >> 1) * 64, n0 = (wave & 1) * 32;
   // Per-thread coordinates behind global offsets.  They are re-derived from an opaque copy of the thread index at the top of
   // every tile: loop-invariant offsets (about forty of them) would otherwise be held -- and spilled -- across the loop beside the
@@ -233,7 +250,7 @@ __global__ __launch_bounds__(256, 2) void ftm_update_forward_kernel(UpdFwd a) {
       }
     }
   };
-  float4 w[8], mo[8];
+  float4 w[8], mo[8], vv[8];  // (vv: Adam only)
   int wm0 = 0;  // byte offset of the thread's first parameter of the tile (one multiply per tile)
   auto wm_off = [&](int u) { return wm0 + u * (L1 * 4); };
   auto fetch2 = [&](int m_base, bool live) {
@@ -261,8 +278,25 @@ __global__ __launch_bounds__(256, 2) void ftm_update_forward_kernel(UpdFwd a) {
       }
     }
   };
+  // the second moment of the tile whose parameters fetch2 requested (wm0 is that tile's offset)
+  auto fetch2v = [&]() {
+#ifdef NNUE_ABLATIONS
+    if (a.abl & 1) {
+#pragma unroll
+      for (int u = 0; u < 8; ++u) vv[u] = make_float4(0.5f, 0.25f, 0.125f, 1.f);
+      return;
+    }
+#endif
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const u32x4 x = __builtin_amdgcn_raw_buffer_load_b128(rsv, wm_off(u), 0, 2);
+      vv[u] = make_float4(__uint_as_float(x[0]), __uint_as_float(x[1]), __uint_as_float(x[2]), __uint_as_float(x[3]));
+    }
+  };
   const float gs = a.coef[0] * a.scale;
   const float lr = a.lr_dev ? a.lr_dev[0] : a.lr;
+  AdamBias bc{0.f, 0.f};
+  if constexpr (kAdam) bc = adam_bias_correction(lr, a.beta1, a.beta2, a.step_counter[0]);
 
   fetch1(p_lo, 0, p_lo < p_hi);
   fetch2(p_lo, p_lo < p_hi);
@@ -289,12 +323,13 @@ __global__ __launch_bounds__(256, 2) void ftm_update_forward_kernel(UpdFwd a) {
       stage1();
       __syncthreads();
     }
+    if constexpr (kAdam) fetch2v();  // after the last stage1(): see above
 #ifdef NNUE_ABLATIONS
     if (!(a.abl & 8))
 #endif
     contract1();
     __syncthreads();
-    // ---------------- phase 2: accumulators -> LDS -> 8 rows x 4 columns per thread, SGD
+    // ---------------- phase 2: accumulators -> LDS -> 8 rows x 4 columns per thread, SGD / Adam
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -307,6 +342,26 @@ __global__ __launch_bounds__(256, 2) void ftm_update_forward_kernel(UpdFwd a) {
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
       const float4 v = *reinterpret_cast<const float4*>(Ct + (8 * g8 + u) * 68 + 4 * c4);
+      if constexpr (kAdam) {  // the arithmetic of rmw_tile_adam, element by element
+        float4 wn;
+        wn.x = adam_update_fused(w[u].x, v.x, mo[u].x, vv[u].x, gs, bc, a.beta1, a.beta2, a.eps, a.wd);
+        wn.y = adam_update_fused(w[u].y, v.y, mo[u].y, vv[u].y, gs, bc, a.beta1, a.beta2, a.eps, a.wd);
+        wn.z = adam_update_fused(w[u].z, v.z, mo[u].z, vv[u].z, gs, bc, a.beta1, a.beta2, a.eps, a.wd);
+        wn.w = adam_update_fused(w[u].w, v.w, mo[u].w, vv[u].w, gs, bc, a.beta1, a.beta2, a.eps, a.wd);
+#ifdef NNUE_ABLATIONS
+        if (!(a.abl & 2))
+#endif
+        {
+          __builtin_amdgcn_raw_buffer_store_b128((u32x4){__float_as_uint(mo[u].x), __float_as_uint(mo[u].y), __float_as_uint(mo[u].z), __float_as_uint(mo[u].w)},
+                                                 rsm, wm_off(u), 0, 2);
+          __builtin_amdgcn_raw_buffer_store_b128((u32x4){__float_as_uint(vv[u].x), __float_as_uint(vv[u].y), __float_as_uint(vv[u].z), __float_as_uint(vv[u].w)},
+                                                 rsv, wm_off(u), 0, 2);
+          __builtin_amdgcn_raw_buffer_store_b128((u32x4){__float_as_uint(wn.x), __float_as_uint(wn.y), __float_as_uint(wn.z), __float_as_uint(wn.w)}, rsw,
+                                                 wm_off(u), 0, 2);
+        }
+        w[u] = m_base + 8 * g8 + u < a.direct ? wn : make_float4(0.f, 0.f, 0.f, 0.f);
+        continue;
+      }
       float4 g;  // the arithmetic of sgd_apply_kernel / rmw_tile, element by element
       g.x = fmaf(a.wd, w[u].x, v.x * gs); g.y = fmaf(a.wd, w[u].y, v.y * gs);
       g.z = fmaf(a.wd, w[u].z, v.z * gs); g.w = fmaf(a.wd, w[u].w, v.w * gs);

@@ -16,7 +16,7 @@ import torch
 
 _HERE = Path(__file__).resolve().parent
 LIB_PATH = _HERE / "libnnue_hip.so"
-ABI_VERSION = 35
+ABI_VERSION = 36
 
 _c_int, _c_i64, _c_f, _c_p = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
 
@@ -158,6 +158,13 @@ SIGNATURES = {
     "nnue_ftm_update_forward_supported": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int]),
     "nnue_ftm_backward_weight_update_forward": (_c_int, [_c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p, _c_f, _c_f, _c_f, _c_f,
                                                          _c_int, _c_p, _c_p, _c_p, _c_int, _c_p, _c_p, _c_p, _c_i64, _c_p]),
+    "nnue_adam_step_ext": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f,
+                                    _c_p, _c_p, _c_i64, _c_p, _c_int, _c_i64, _c_i64, _c_p, _c_int, _c_p, _c_p]),
+    "nnue_ftm_backward_weight_update_adam": (_c_int, [_c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p,
+                                                      _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_p, _c_p]),
+    "nnue_ftm_backward_weight_update_forward_adam": (_c_int, [_c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p,
+                                                              _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_p,
+                                                              _c_p, _c_p, _c_int, _c_p, _c_p, _c_p, _c_i64, _c_p]),
 }
 
 _lib: Optional[ctypes.CDLL] = None
@@ -1170,6 +1177,49 @@ def ftm_backward_weight_update_forward(d_out: torch.Tensor, fm: "FeatureMatrix",
           fm_next.scratch.data_ptr(), fm_next.scratch.numel(), _stream(d_out))
 
 
+def ftm_backward_weight_update_adam(d_out: torch.Tensor, fm: "FeatureMatrix", weight: torch.Tensor, exp_avg_rows: torch.Tensor,
+                                    exp_avg_sq_rows: torch.Tensor, coef: torch.Tensor, step_counter: torch.Tensor, lr: float,
+                                    betas, eps: float, weight_decay: float, grad_scale: float,
+                                    lr_dev: Optional[torch.Tensor] = None) -> None:
+    """weight rows [0, direct) and the matching moment rows <- Adam update with d_W = A^T d_out formed and consumed in the
+    product's epilogue.  ``step_counter`` (device int32) is read, not advanced: adam_step(ext_applied_elsewhere=True) of the
+    same step advances it and leaves ``coef``."""
+    d_out = _need(d_out, torch.float32, "d_out")
+    b, l1 = d_out.shape
+    weight = _need(weight, torch.float32, "input.weight", (fm.num_rows, l1))
+    _need(exp_avg_rows, torch.float32, "exp_avg rows")
+    _need(exp_avg_sq_rows, torch.float32, "exp_avg_sq rows")
+    _need(coef, torch.float32, "clip coefficient")
+    _need(step_counter, torch.int32, "step counter", (1,))
+    _call("nnue_ftm_backward_weight_update_adam", fm.bits.data_ptr(), d_out.data_ptr(), b, fm.num_rows, fm.positions, l1, weight.data_ptr(),
+          exp_avg_rows.data_ptr(), exp_avg_sq_rows.data_ptr(), coef.data_ptr(), step_counter.data_ptr(), float(lr), float(betas[0]),
+          float(betas[1]), float(eps), float(weight_decay), float(grad_scale), _ptr(lr_dev), _stream(d_out))
+
+
+def ftm_backward_weight_update_forward_adam(d_out: torch.Tensor, fm: "FeatureMatrix", weight: torch.Tensor, exp_avg_rows: torch.Tensor,
+                                            exp_avg_sq_rows: torch.Tensor, coef: torch.Tensor, step_counter: torch.Tensor, lr: float,
+                                            betas, eps: float, weight_decay: float, grad_scale: float, fm_next: "FeatureMatrix",
+                                            bias: torch.Tensor, out_next: torch.Tensor, lr_dev: Optional[torch.Tensor] = None) -> None:
+    """ftm_backward_weight_update_adam(d_out, fm, ...) and ftm_forward(weight, bias, fm_next, out=out_next) in one pass over the
+    table (bitwise the two calls).  `bias` and table row F-1 must already be updated (adam_step)."""
+    d_out = _need(d_out, torch.float32, "d_out")
+    b, l1 = d_out.shape
+    weight = _need(weight, torch.float32, "input.weight", (fm.num_rows, l1))
+    bias = _need(bias, torch.float32, "input.bias", (l1,))
+    out_next = _need(out_next, torch.float32, "out_next", (fm_next.batch, l1))
+    _need(exp_avg_rows, torch.float32, "exp_avg rows")
+    _need(exp_avg_sq_rows, torch.float32, "exp_avg_sq rows")
+    _need(coef, torch.float32, "clip coefficient")
+    _need(step_counter, torch.int32, "step counter", (1,))
+    if fm.batch != b or fm_next.positions != fm.positions or fm_next.num_rows != fm.num_rows:
+        raise ValueError("ftm_backward_weight_update_forward_adam: the maps do not match d_out / each other")
+    _call("nnue_ftm_backward_weight_update_forward_adam", fm.bits.data_ptr(), d_out.data_ptr(), b, fm.num_rows, fm.positions, l1,
+          weight.data_ptr(), exp_avg_rows.data_ptr(), exp_avg_sq_rows.data_ptr(), coef.data_ptr(), step_counter.data_ptr(), float(lr),
+          float(betas[0]), float(betas[1]), float(eps), float(weight_decay), float(grad_scale), _ptr(lr_dev), fm_next.bits.data_ptr(),
+          fm_next.sink.data_ptr(), fm_next.batch, bias.data_ptr(), out_next.data_ptr(), fm_next.scratch.data_ptr(), fm_next.scratch.numel(),
+          _stream(d_out))
+
+
 class FactorExchange:
     """Buffers of the factor exchange (include/nnue_hip.h, nnue_dp_factor_*): ``chunks`` uint8 [world][chunk_bytes] is the
     all-gather's receive buffer, ``own`` this rank's slice of it (sent in place); ``d_ft`` / ``sink`` are float views of the
@@ -1237,7 +1287,10 @@ def sgd_step(params: torch.Tensor, grads: torch.Tensor, momentum_buf: Optional[t
 def adam_step(params: torch.Tensor, grads: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor,
               step_counter: torch.Tensor, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
               max_norm: float = 0.0, grad_scale: float = 1.0, norm_out: Optional[torch.Tensor] = None,
-              scratch: Optional[torch.Tensor] = None, lr_dev: Optional[torch.Tensor] = None) -> None:
+              scratch: Optional[torch.Tensor] = None, lr_dev: Optional[torch.Tensor] = None, ext=None,
+              coef_out: Optional[torch.Tensor] = None, ext_applied_elsewhere: bool = False) -> None:
+    """ext / coef_out / ext_applied_elsewhere as in sgd_step (nnue_adam_step_ext): ext = (partials, lo, hi), a producer's sums of
+    squares for grads[lo:hi]; with ext_applied_elsewhere that range of params and moments is left to the producer."""
     params = _need(params, torch.float32, "flat params")
     shape = tuple(params.shape)
     grads = _need(grads, torch.float32, "flat grads", shape)
@@ -1246,6 +1299,13 @@ def adam_step(params: torch.Tensor, grads: torch.Tensor, exp_avg: torch.Tensor, 
     _need(step_counter, torch.int32, "step counter", (1,))
     if scratch is None:
         scratch = torch.empty((sgd_scratch_bytes(params.numel()),), dtype=torch.uint8, device=params.device)
+    if ext is not None or coef_out is not None or ext_applied_elsewhere:
+        ext_args = (ext[0].data_ptr(), ext[0].numel(), int(ext[1]), int(ext[2])) if ext is not None else (None, 0, 0, 0)
+        _call("nnue_adam_step_ext", params.data_ptr(), grads.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(),
+              step_counter.data_ptr(), params.numel(), float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
+              float(max_norm), float(grad_scale), _ptr(norm_out), scratch.data_ptr(), scratch.numel(), *ext_args, _ptr(coef_out),
+              int(bool(ext_applied_elsewhere)), _ptr(lr_dev), _stream(params))
+        return
     _call("nnue_adam_step", params.data_ptr(), grads.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(),
           step_counter.data_ptr(), params.numel(), float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
           float(max_norm), float(grad_scale), _ptr(norm_out), scratch.data_ptr(), scratch.numel(), _ptr(lr_dev), _stream(params))

@@ -313,16 +313,17 @@ class NnueTrainer:
             if off % 4 == 0 and (rows * self.L1) % 4 == 0:
                 self.sq_partial = torch.empty((n_sq,), **f32)
                 self.sq_range = (off, off + rows * self.L1)
-        # Big tables on a single rank with SGD: the FeatureTransformer weight gradient is never materialised.  Its squared
+        # Big tables on a single rank (SGD or Adam): the FeatureTransformer weight gradient is never materialised.  Its squared
         # norm comes from two B x B Gram matrices (nnue_ftm_gram_sqnorm), the optimizer's norm/apply pass skips those rows
         # and leaves the clip coefficient in a device scalar, and the product d_W = A^T d_out runs LAST, applying the update
-        # to the table in its epilogue (nnue_ftm_backward_weight_update): no 268 MB write + read at the 224x224 shape.
+        # to the table (Adam: and to its two moments) in its epilogue (nnue_ftm_backward_weight_update[_adam]): no 268 MB write
+        # + read at the 224x224 shape.
         self.fuse_table_update = False
         rows = min(self.F - 1, self.P)
         off = self.layout.offsets[self.layout.names.index("input.weight")]
         big_table = self.F * self.L1 * 4 >= (32 << 20)
         want = os.environ.get("NNUE_FUSE_TABLE_UPDATE", "auto")
-        if (self.use_mfma and not self.dp.collectives and optimizer == "sgd" and rows > 0 and B * self.L1 <= (1 << 24) and off % 4 == 0
+        if (self.use_mfma and not self.dp.collectives and rows > 0 and B * self.L1 <= (1 << 24) and off % 4 == 0
                 and (rows * self.L1) % 4 == 0 and want != "0" and (big_table or want == "1")):
             self.fuse_table_update = True
             self.ride_dw1 = False  # the rider lives in the merged launch, which this path does not use
@@ -543,7 +544,18 @@ class NnueTrainer:
 
     def _update(self, first: bool, grad_scale: Optional[float] = None) -> None:
         scale = self.dp.grad_scale if grad_scale is None else grad_scale
-        if self.optimizer == "adam":
+        if self.optimizer == "adam" and self.fuse_table_update:
+            # small tensors + norm (the table's share from the Gram partials) + step counter, then the product with the Adam
+            # epilogue on the table's rows of the three flat buffers
+            lib.adam_step(self.flat_params, self.flat_grads, self.flat_exp_avg, self.flat_exp_avg_sq, self.adam_step_count,
+                          self.lr, self.betas, self.eps, self.weight_decay, self.max_grad_norm, scale, self.grad_norm,
+                          self.sgd_scratch, lr_dev=self.lr_dev, ext=(self.sq_partial, *self.sq_range), coef_out=self.clip_coef,
+                          ext_applied_elsewhere=True)
+            lo, hi = self.sq_range
+            lib.ftm_backward_weight_update_adam(self.d_ft, self.fm, self.p["input.weight"], self.flat_exp_avg[lo:hi],
+                                                self.flat_exp_avg_sq[lo:hi], self.clip_coef, self.adam_step_count, self.lr, self.betas,
+                                                self.eps, self.weight_decay, scale, lr_dev=self.lr_dev)
+        elif self.optimizer == "adam":
             lib.adam_step(self.flat_params, self.flat_grads, self.flat_exp_avg, self.flat_exp_avg_sq, self.adam_step_count,
                           self.lr, self.betas, self.eps, self.weight_decay, self.max_grad_norm, scale, self.grad_norm,
                           self.sgd_scratch, lr_dev=self.lr_dev)
@@ -849,16 +861,22 @@ class NnueTrainer:
             elif fuse and i + 1 < len(slots):
                 # small tensors (and the clip coefficient) first: the next map needs the updated conv weights and thresholds,
                 # the next forward's finish the updated bias and table row F-1
-                lib.run_plan([c for c in upd if c[0] == "nnue_sgd_step"], st.cuda_stream, timers)
+                lib.run_plan([c for c in upd if c[0] in ("nnue_sgd_step", "nnue_adam_step_ext")], st.cuda_stream, timers)
                 cur, nxt = (self.fm_alt, self.fm) if alt else (self.fm, self.fm_alt)
                 lo, hi = self.sq_range
                 mom = self.flat_momentum[lo:hi] if self.flat_momentum is not None else None
                 with lib.time_calls(timers):
                     lib.ftm_conv_binarize(self.inputs[slots[i + 1]][0], self.p["conv.weight"], self.p["visual_threshold"], self.stride,
                                           self.F, self.L1, conv_out=self.conv_out, fm=nxt, patches=self.patches)
-                    lib.ftm_backward_weight_update_forward(self.d_ft, cur, self.p["input.weight"], mom, self.clip_coef, self.lr, self.momentum,
-                                                           self.weight_decay, self.dp.grad_scale, False, nxt, self.p["input.bias"], self.ft,
-                                                           lr_dev=self.lr_dev)
+                    if self.optimizer == "adam":
+                        lib.ftm_backward_weight_update_forward_adam(self.d_ft, cur, self.p["input.weight"], self.flat_exp_avg[lo:hi],
+                                                                    self.flat_exp_avg_sq[lo:hi], self.clip_coef, self.adam_step_count,
+                                                                    self.lr, self.betas, self.eps, self.weight_decay, self.dp.grad_scale,
+                                                                    nxt, self.p["input.bias"], self.ft, lr_dev=self.lr_dev)
+                    else:
+                        lib.ftm_backward_weight_update_forward(self.d_ft, cur, self.p["input.weight"], mom, self.clip_coef, self.lr,
+                                                               self.momentum, self.weight_decay, self.dp.grad_scale, False, nxt,
+                                                               self.p["input.bias"], self.ft, lr_dev=self.lr_dev)
             elif alt:
                 swap = self._alt_swap()
                 lib.run_plan([(nm, fn, tuple(swap.get(a, a) if isinstance(a, int) else a for a in args)) for nm, fn, args in upd],
