@@ -207,12 +207,18 @@ struct is_ste<Epi, decltype((void)Epi::kSte)> { static constexpr bool value = Ep
 // The pixel operand of the tile's STE contraction, dW[c][q] = sum over the tile's (sample, position) pairs k of
 // d[c][k] * patch[k][q] on v_mfma_f32_16x16x4_f32: wave w takes pairs [2 BM w, 2 BM (w + 1)), MFMA step (g, e) pair
 // 2 BM w + 16 g + 4 q + e, lane (r, q) supplies patch terms r and 16 + r (term 27 is 1: it sums the threshold rows).
+// ste_pixels only REQUESTS the pixels (unconditional loads from clamped addresses) and notes in a bit mask which of them are
+// real; ste_pixels_select replaces the others once the loads are back.  Selecting at the request puts a full wait, a
+// first-touch round trip of its own, between the gather and whatever is requested next.
 template <int BM>
 struct SteFrag {
   float pv[BM / 8][4][2];
+  unsigned in[(BM + 31) / 32];  // bit 8 (g % 4) + 2 t4 + s of word g / 4: pv[g][t4][s] is a pixel inside the image
 };
 template <int BM>
 __device__ __forceinline__ void ste_pixels(const ValSteEpi& e, SteFrag<BM>& f, int M, int m_base, int tile_n, int wave, int r, int q) {
+#pragma unroll
+  for (int w = 0; w < (BM + 31) / 32; ++w) f.in[w] = 0u;
 #pragma unroll
   for (int g = 0; g < BM / 8; ++g)
 #pragma unroll
@@ -236,9 +242,48 @@ __device__ __forceinline__ void ste_pixels(const ValSteEpi& e, SteFrag<BM>& f, i
           in = ok && qq < 27 && iy >= 0 && iy < e.H && ix >= 0 && ix < e.W;
           v = e.img[in ? (((size_t)m * 3 + ci) * e.H + iy) * e.W + ix : 0];
         }
-        f.pv[g][t4][s] = in ? v : (qq == 27 ? 1.0f : 0.0f);
+        f.pv[g][t4][s] = v;
+        f.in[g >> 2] |= (in ? 1u : 0u) << (8 * (g & 3) + 2 * t4 + s);
       }
     }
+}
+template <int BM>
+__device__ __forceinline__ void ste_pixels_select(SteFrag<BM>& f, int r) {
+#pragma unroll
+  for (int g = 0; g < BM / 8; ++g)
+#pragma unroll
+    for (int t4 = 0; t4 < 4; ++t4)
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        const bool in = (f.in[g >> 2] >> (8 * (g & 3) + 2 * t4 + s)) & 1u;
+        f.pv[g][t4][s] = in ? f.pv[g][t4][s] : (r + 16 * s == 27 ? 1.0f : 0.0f);
+      }
+}
+
+// What the epilogue of a ValSteEpi tile reads from memory: the map bytes and conv outputs under the lane's accumulator
+// registers and its columns' thresholds, as loaded (unconditionally, rows and positions clamped into range; ste_tile applies
+// the guards).  Requested in the last K tile, where the staging registers are free and the MFMAs of that tile hide the trip.
+template <int BM>
+struct StePre {
+  uint8_t bit[BM / 32][2][4];
+  float cv[BM / 32][2][4], th[2];
+};
+template <int BM>
+__device__ __forceinline__ void ste_prefetch(const ValSteEpi& e, StePre<BM>& p, int M, int m_base, int tile_n, int m0, int n0, int r, int q) {
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    const int j = n0 + 16 * t + r, c = j >> 3, hw = tile_n * 8 + (j & 7);
+    const int pp = c * e.G + (hw < e.G ? hw : 0);
+    p.th[t] = e.thr[c];
+#pragma unroll
+    for (int i = 0; i < BM / 32; ++i)
+#pragma unroll
+      for (int ee = 0; ee < 4; ++ee) {
+        const int m = min(m_base + m0 + 16 * i + 4 * q + ee, M - 1);
+        p.bit[i][t][ee] = e.bits[(size_t)m * e.P + pp];
+        p.cv[i][t][ee] = e.conv_out[(size_t)m * e.P + pp];
+      }
+  }
 }
 
 // Epilogue of a ValSteEpi tile (BN = 64, waves 2 x 2, accumulator register e of lane 16 q + r = C[row 4 q + e][col r]):
@@ -247,26 +292,27 @@ __device__ __forceinline__ void ste_pixels(const ValSteEpi& e, SteFrag<BM>& f, i
 // tiles are summed in wave order.  `smem` is free (the K loop ended with a barrier) and holds >= 16 (8 BM + 4) + 2048 floats.
 template <int BM, int BN>
 __device__ __forceinline__ void ste_tile(float* __restrict__ smem, const ValSteEpi& e, const f32x4 (&acc)[BM / 32][BN / 32], const SteFrag<BM>& f,
-                                         int M, int m_base, int tile_n, int m0, int n0, int tile) {
+                                         const StePre<BM>& pre, int M, int m_base, int tile_n, int m0, int n0, int tile) {
   static_assert(BN == 64, "a tile holds the 8 channels of 8 positions");
   constexpr int TM = BM / 32, TN = BN / 32, LDA = 8 * BM + 4;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = lane & 15, q = lane >> 4;
-  float bit[TM][TN][4], cv[TM][TN][4], th[TN];
+  // the guards on what ste_prefetch loaded, and the sigmoid's slope k s (1 - s): neither needs the accumulators
+  float bit[TM][TN][4], slope[TM][TN][4];
 #pragma unroll
   for (int t = 0; t < TN; ++t) {
-    const int j = n0 + 16 * t + r, c = j >> 3, hw = tile_n * 8 + (j & 7);
-    const int p = c * e.G + (hw < e.G ? hw : 0);
-    th[t] = e.thr[c];
+    const int hw = tile_n * 8 + ((n0 + 16 * t + r) & 7);
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
       for (int ee = 0; ee < 4; ++ee) {
         const int m = m_base + m0 + 16 * i + 4 * q + ee;
         const bool ok = m < M && hw < e.G;
-        bit[i][t][ee] = ok ? (float)e.bits[(size_t)m * e.P + p] : 0.0f;
-        cv[i][t][ee] = ok ? e.conv_out[(size_t)m * e.P + p] : 0.0f;
+        bit[i][t][ee] = ok ? (float)pre.bit[i][t][ee] : 0.0f;
+        const float cv = ok ? pre.cv[i][t][ee] : 0.0f;
+        const float s = 1.0f / (1.0f + __expf(-kFtmSteSharpness * (cv - pre.th[t])));
+        slope[i][t][ee] = (kFtmSteSharpness * s) * (1.0f - s);
       }
   }
   float* __restrict__ A = smem;
@@ -282,10 +328,9 @@ __device__ __forceinline__ void ste_tile(float* __restrict__ smem, const ValSteE
         const int m_loc = m0 + 16 * i + 4 * q + ee, m = m_base + m_loc;
         const float d = bit[i][t][ee] != 0.0f ? acc[i][t][ee] : 0.0f;  // bit is 0 outside the tile's valid range
         if (e.d_conv_out && m < M && hw < e.G) e.d_conv_out[(size_t)m * e.P + p] = d;
-        const float s = 1.0f / (1.0f + __expf(-kFtmSteSharpness * (cv[i][t][ee] - th[t])));
         const int k = m_loc * 8 + (j & 7);
         A[c * LDA + k] = d;
-        A[(8 + c) * LDA + k] = d * ((kFtmSteSharpness * s) * (1.0f - s));
+        A[(8 + c) * LDA + k] = d * slope[i][t][ee];
       }
   }
   __syncthreads();
@@ -748,9 +793,8 @@ __device__ __forceinline__ void gemm_tile(float* __restrict__ smem, const Mat& m
 
   FusedL1Pre<Epi::kFusedL1 ? BM : 32> l1pre;
   if constexpr (Epi::kFusedL1) fused_l1_prefetch<BM>(epi, l1pre, m_base, tile_n, m0, n0, r, q, wave);
-  // the STE epilogue's pixels are requested before the K loop (32 registers at BM = 32)
   SteFrag<is_ste<Epi>::value ? BM : 8> stef;
-  if constexpr (is_ste<Epi>::value) ste_pixels<BM>(epi, stef, M, m_base, tile_n, wave, r, q);
+  StePre<is_ste<Epi>::value ? BM : 32> stepre;
   // (Two K tiles of loads in flight -- two register sets, the loop written out twice, every load unconditional with a dead request's
   // offset outside its window, no branch between the halves, scheduling barriers between the sets' requests: each of these was
   // needed before the compiler's waits became vmcnt(12) instead of vmcnt(0), which round 2's attempt never reached -- was measured at
@@ -760,6 +804,58 @@ __device__ __forceinline__ void gemm_tile(float* __restrict__ smem, const Mat& m
   // walk the same 256-byte columns of the shared operands at the same time -- was measured at the CIFAR shapes and changes nothing:
   // forward 18.1 vs 18.2 us, merged backward 25.7 vs 25.4 us; profiles/r03n_krot_ab.txt.)
   fetch(k_lo);
+  if constexpr (is_ste<Epi>::value) {
+    // The same loop with its last tile (there is at least one) written out behind it, so that the staging registers are dead
+    // in it: that tile requests everything the epilogue reads -- the pixels (32 registers at BM = 32), the map bytes, conv
+    // outputs and thresholds -- in their place, and the trip runs under its MFMAs.  (A copy of the loop below rather than a
+    // change to it: every other instantiation keeps the instruction stream it had.)
+    auto stage_tile = [&]() {
+#pragma unroll
+      for (int i = 0; i < AG; ++i) *reinterpret_cast<float4*>(&As[kc(a_row(i), a_k(i))]) = widen<AU8>(ra[i]);
+#pragma unroll
+      for (int i = 0; i < BG; ++i) *reinterpret_cast<float4*>(&Bs[kc(b_row(i), b_k(i))]) = widen<false>(rb[i]);
+      __syncthreads();
+    };
+    auto contract_tile = [&]() {
+      float4 a[2][TM], b[2][TN];
+      frags(0, a[0], b[0]);
+#pragma unroll
+      for (int kb = 0; kb < BK; kb += 16) {
+        const int cur = (kb >> 4) & 1;
+        if (kb + 16 < BK) frags(kb + 16, a[cur ^ 1], b[cur ^ 1]);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+          for (int t = 0; t < TN; ++t) acc[i][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[cur][i].x, b[cur][t].x, acc[i][t], 0, 0, 0);
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+          for (int t = 0; t < TN; ++t) acc[i][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[cur][i].y, b[cur][t].y, acc[i][t], 0, 0, 0);
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+          for (int t = 0; t < TN; ++t) acc[i][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[cur][i].z, b[cur][t].z, acc[i][t], 0, 0, 0);
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+          for (int t = 0; t < TN; ++t) acc[i][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[cur][i].w, b[cur][t].w, acc[i][t], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      __syncthreads();
+    };
+    static_assert(AKC && BKC && !Epi::kBPair, "the value gradient's operand forms");
+    for (int k0 = k_lo; k0 + BK < k_hi; k0 += BK) {
+      stage_tile();
+      fetch(k0 + BK);
+      contract_tile();
+    }
+    stage_tile();
+    ste_pixels<BM>(epi, stef, M, m_base, tile_n, wave, r, q);
+    ste_prefetch<BM>(epi, stepre, M, m_base, tile_n, m0, n0, r, q);
+    contract_tile();
+    ste_pixels_select<BM>(stef, r);
+  } else
   for (int k0 = k_lo; k0 < k_hi; k0 += BK) {
 #pragma unroll
     for (int i = 0; i < AG; ++i) *reinterpret_cast<float4*>(&As[AKC ? kc(a_row(i), a_k(i)) : a_k(i) * LDA + a_row(i)]) = widen<AU8>(ra[i]);
@@ -808,7 +904,7 @@ __device__ __forceinline__ void gemm_tile(float* __restrict__ smem, const Mat& m
     fused_l1_epilogue<BM>(epi, l1pre, smem, acc, m_base, tile_n, m0, n0, r, q, wave, tid);
     return;
   } else if constexpr (is_ste<Epi>::value) {
-    ste_tile<BM, BN>(smem, epi, acc, stef, M, m_base, tile_n, m0, n0, tile);
+    ste_tile<BM, BN>(smem, epi, acc, stef, stepre, M, m_base, tile_n, m0, n0, tile);
   } else {
     store_tile<BM, BN, Epi>(smem, epi, acc, M, N, m_base, n_base, m0, n0, tile, ks);
   }
@@ -1378,8 +1474,11 @@ __device__ __forceinline__ void gemm_tile_bf6(unsigned char* __restrict__ smem, 
   }
   if constexpr (is_ste<Epi>::value) {  // (64 pixel registers at BM = 64: requested here, not across the K loop)
     SteFrag<BM> stef;
+    StePre<BM> stepre;
+    ste_prefetch<BM>(epi, stepre, M, m_base, tile_n, m0, n0, r, q);
     ste_pixels<BM>(epi, stef, M, m_base, tile_n, wave, r, q);
-    ste_tile<BM, BN>(reinterpret_cast<float*>(smem), epi, acc, stef, M, m_base, tile_n, m0, n0, tile);
+    ste_pixels_select<BM>(stef, r);
+    ste_tile<BM, BN>(reinterpret_cast<float*>(smem), epi, acc, stef, stepre, M, m_base, tile_n, m0, n0, tile);
   } else {
     store_tile<BM, BN, Epi>(reinterpret_cast<float*>(smem), epi, acc, M, N, m_base, n_base, m0, n0, tile, ks);
   }
