@@ -71,6 +71,14 @@ __device__ __forceinline__ float4 widen(const u32x4& raw) {
   return make_float4(__uint_as_float(raw[0]), __uint_as_float(raw[1]), __uint_as_float(raw[2]), __uint_as_float(raw[3]));
 }
 
+// Blocks are dealt round-robin over the 8 XCDs (observed, never relied on for results): block `tile` of `nwg` -> the index under
+// which the blocks of one XCD (equal tile % 8) hold a contiguous run of indices.  Bijective for any grid size
+// (cdna_hip_programming.md, XCD swizzle).
+__device__ __forceinline__ int xcd_contiguous_tile(int tile, int nwg) {
+  const int xcd = tile & 7, q8 = nwg >> 3, r8 = nwg & 7;
+  return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (tile >> 3);
+}
+
 // ---- epilogues: col(n) gives per-column values, pre(m, n) a per-element operand loaded before any store ---------
 struct FwdEpi {  // out = acc + bias + sink[b] * weight[F-1]   (or a split-K slab, finished by ftm_finish_kernel)
   static constexpr bool kAU8 = true;  // operand A is the byte map
@@ -140,6 +148,7 @@ struct BwwSgdEpi {
 // step number is the device counter the optimizer's norm launch has already advanced (nnue_adam_step_ext), so nothing in
 // the launch changes from step to step.  Only the bf16-split tiles take it (rmw_tile_adam).
 struct BwwAdamEpi {
+  static constexpr bool kAU8 = true;
   static constexpr bool kFusedL1 = false;
   static constexpr bool kRmw = true;
   static constexpr bool kAdam = true;
@@ -353,11 +362,7 @@ __device__ __forceinline__ void ste_tile(float* __restrict__ smem, const ValSteE
     red[(wave * 8 + 4 + ee) * 64 + lane] = c1[ee];
   }
   __syncthreads();
-  int slot;  // XCD-major slots (the value tiles are the launch's first workgroups: tile % 8 is the XCD)
-  {
-    const int nwg = e.n_tiles, xcd = tile & 7, q8 = nwg >> 3, r8 = nwg & 7;
-    slot = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (tile >> 3);
-  }
+  const int slot = xcd_contiguous_tile(tile, e.n_tiles);  // XCD-major slots (the value tiles are the launch's first workgroups)
   for (int o = tid; o < 8 * 28; o += 256) {
     const int c = o / 28, qq = o - c * 28;
     const int row = qq < 27 ? c : 8 + c, col = qq;  // C[c][q] = sum d * pixel q; C[8 + c][27] = sum of the threshold terms
@@ -926,18 +931,19 @@ __device__ __forceinline__ void gemm_tile(float* __restrict__ smem, const Mat& m
 // 8 k x 4 n block (eight 16-byte loads), splits it in registers and writes, per n, one 16-byte chunk of 8 k per plane.
 // The split is 4 VALU per value + 1.5 for packing; it is amortised over the BM rows of the tile, so tall tiles matter
 // more here than for the f32 kernel.
-using bf16x8 = __attribute__((__vector_size__(8 * sizeof(__bf16)))) __bf16;
-constexpr int kBfK = 128;  // K tile
-template <int BM, int BN>
-constexpr int gemm_bf_lds_bytes() { return (BM + 3 * BN) * kBfK * 2; }
+constexpr int kBfK = 128, kBf64K = 64;  // K tile depths: gemm_tile_bf / gemm_tile_bf64
+template <int BM, int BN, int KT>
+constexpr int gemm_bf_lds_bytes() { return (BM + 3 * BN) * KT * 2; }
 
-__device__ __forceinline__ int bf_img(int row, int chunk) { return row * (kBfK * 2) + ((chunk ^ (row & 15)) << 4); }  // byte offset
+// byte offset of 16-byte chunk `chunk` of image row `row`
+__device__ __forceinline__ int bf_img(int row, int chunk) { return row * (kBfK * 2) + ((chunk ^ (row & 15)) << 4); }
+__device__ __forceinline__ int bf64_img(int row, int chunk) { return row * (kBf64K * 2) + ((chunk ^ ((row >> 1) & 7)) << 4); }
+template <int KT>
+struct BfImg {  // the image of a K tile of depth KT
+  __device__ __forceinline__ int operator()(int row, int chunk) const { return KT == kBfK ? bf_img(row, chunk) : bf64_img(row, chunk); }
+};
 
-// four {0,1} bytes -> four bf16 (two words)
-__device__ __forceinline__ void bytes_to_bf16(unsigned x, unsigned& w0, unsigned& w1) {
-  w0 = ((x & 0xffu) | ((x & 0xff00u) << 8)) * 0x3f80u;
-  w1 = (((x >> 16) & 0xffu) | ((x >> 8) & 0xff0000u)) * 0x3f80u;
-}
+#include "bf16_split.h"  // split3 / split_block / split8, stage_map_k / stage_map_m
 
 template <int BM, int BN, bool AKC, class Epi>
 __device__ __forceinline__ void gemm_tile_bf(unsigned char* __restrict__ smem, const Mat& ma, const Mat& mb, const Epi& epi, int M, int N,
@@ -1026,58 +1032,21 @@ __device__ __forceinline__ void gemm_tile_bf(unsigned char* __restrict__ smem, c
     if constexpr (AKC) {
 #pragma unroll
       for (int i = 0; i < AGK; ++i) {
-        const int g = tid + 256 * i, row = akc_row(g), c = akc_grp(g) * 2;
-        u32x4 lo, hi;
-        unsigned a, b;
-        bytes_to_bf16(ra[i][0], a, b); lo[0] = a; lo[1] = b;
-        bytes_to_bf16(ra[i][1], a, b); lo[2] = a; lo[3] = b;
-        bytes_to_bf16(ra[i][2], a, b); hi[0] = a; hi[1] = b;
-        bytes_to_bf16(ra[i][3], a, b); hi[2] = a; hi[3] = b;
-        *reinterpret_cast<u32x4*>(As + bf_img(row, c)) = lo;
-        *reinterpret_cast<u32x4*>(As + bf_img(row, c + 1)) = hi;
+        const int g = tid + 256 * i;
+        stage_map_k(As, BfImg<kBfK>{}, akc_row(g), akc_grp(g) * 2, ra[i]);
       }
     } else {
 #pragma unroll
       for (int i = 0; i < AGR; ++i) {
         const int g = a_block(tid + 256 * i);
         if (g < (BM / 4) * 16) {
-          const int m4 = (g % (BM / 4)) * 4, c = g / (BM / 4);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {  // byte e of the eight words = 8 consecutive k of row m4 + e
-            u32x4 v;
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-              const unsigned sel = 0x0c000c00u | (unsigned)e | ((unsigned)(4 + e) << 16);  // [lo.byte e, 0, hi.byte e, 0]
-              v[t] = __builtin_amdgcn_perm(rat[i][2 * t + 1], rat[i][2 * t], sel) * 0x3f80u;
-            }
-            *reinterpret_cast<u32x4*>(As + bf_img(m4 + e, c)) = v;
-          }
+          stage_map_m(As, BfImg<kBfK>{}, (g % (BM / 4)) * 4, g / (BM / 4), rat[i]);
         }
       }
     }
     // exact three-way split of the 8 k x 4 n block, packed along k
     u32x4 pl[3][4];  // [plane][n]: 8 bf16
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      unsigned h[2][4], m[2][4], l[2][4];
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float x = __uint_as_float(rb[2 * t + u][e]);
-          const unsigned hb = __float_as_uint(x) & 0xffff0000u;
-          const float r1 = x - __uint_as_float(hb);
-          const unsigned mb_ = __float_as_uint(r1) & 0xffff0000u;
-          const float r2 = r1 - __uint_as_float(mb_);
-          h[u][e] = hb; m[u][e] = mb_; l[u][e] = __float_as_uint(r2);
-        }
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {  // word t of column e: k = 2 t (low half) and 2 t + 1 (high half)
-        pl[0][e][t] = __builtin_amdgcn_perm(h[1][e], h[0][e], 0x07060302u);
-        pl[1][e][t] = __builtin_amdgcn_perm(m[1][e], m[0][e], 0x07060302u);
-        pl[2][e][t] = __builtin_amdgcn_perm(l[1][e], l[0][e], 0x07060302u);
-      }
-    }
+    split_block<4>(rb, pl);
 #pragma unroll
     for (int pnum = 0; pnum < 3; ++pnum)
 #pragma unroll
@@ -1134,12 +1103,10 @@ __device__ __forceinline__ void gemm_tile_bf(unsigned char* __restrict__ smem, c
 // ---- gemm_tile_bf with K tiles of 64 (BM = 128 or 64, BN = 64): half the LDS and fewer live registers, for the kernels
 // whose occupancy is what they wait for -- the two big-table kernels (two workgroups per CU at 80 KB / ~200 registers) and
 // the merged backward launch (its 64 KB were these tiles').  Same arithmetic as gemm_tile_bf; the f32 operand is staged in
-// 4 k x 4 n blocks (four 16-byte loads, 8-byte LDS stores).
-constexpr int kBf64K = 64;
-__device__ __forceinline__ int bf64_img(int row, int chunk) { return row * (kBf64K * 2) + ((chunk ^ ((row >> 1) & 7)) << 4); }
-template <int BM>
-constexpr int gemm_bf64_lds_bytes() { return (BM + 3 * 64) * kBf64K * 2; }
-
+// 4 k x 4 n blocks (four 16-byte loads, 8-byte LDS stores).  Both tile functions split and stage through bf16_split.h and
+// differ in the staging geometry that follows from the K-tile depth; a single function over the depth, and the contraction as
+// one shared function, were tried and change the kernels' listings (a single function: one more VGPR in the BwwEpi forms,
+// other wait placement): profiles/bf16_tile_helpers.md.
 template <int BM, bool AKC, class Epi>
 __device__ __forceinline__ void gemm_tile_bf64(unsigned char* __restrict__ smem, const Mat& ma, const Mat& mb, const Epi& epi, int M, int N,
                                                int k_lo, int k_hi, int tiles_n, int tile, int ks) {
@@ -1163,7 +1130,7 @@ __device__ __forceinline__ void gemm_tile_bf64(unsigned char* __restrict__ smem,
   const bool stream_b = mb.bytes > (64u << 20);  // uniform
   // A, forward (bytes contiguous along k): 16-byte groups (row, 16 k): 4 per row, two per thread
   // A, weight gradient (bytes contiguous along m): one 8 k x 4 m block per thread (8 x 32 blocks)
-  auto a_block = [&](int g) {  // as in gemm_tile_bf: 16 consecutive blocks = 4 m blocks x 4 k blocks
+  auto a_block = [&](int g) {  // 16 consecutive blocks = 4 m blocks x 4 k blocks
     constexpr int MB = BM / 4;
     const int grp = g >> 4, l = g & 15;
     const int groups_m = MB / 4;
@@ -1204,54 +1171,16 @@ __device__ __forceinline__ void gemm_tile_bf64(unsigned char* __restrict__ smem,
     if constexpr (AKC) {
 #pragma unroll
       for (int i = 0; i < AGK; ++i) {
-        const int g = tid + 256 * i, row = a_row_of(g), c = (g & 3) * 2;
-        u32x4 lo, hi;
-        unsigned a, b;
-        bytes_to_bf16(ra[i][0], a, b); lo[0] = a; lo[1] = b;
-        bytes_to_bf16(ra[i][1], a, b); lo[2] = a; lo[3] = b;
-        bytes_to_bf16(ra[i][2], a, b); hi[0] = a; hi[1] = b;
-        bytes_to_bf16(ra[i][3], a, b); hi[2] = a; hi[3] = b;
-        *reinterpret_cast<u32x4*>(As + bf64_img(row, c)) = lo;
-        *reinterpret_cast<u32x4*>(As + bf64_img(row, c + 1)) = hi;
+        const int g = tid + 256 * i;
+        stage_map_k(As, BfImg<kBf64K>{}, a_row_of(g), (g & 3) * 2, ra[i]);
       }
     } else if (tid < ABLK) {
       const int g = a_block(tid);
-      const int m4 = (g % (BM / 4)) * 4, c = g / (BM / 4);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {  // byte e of the eight words = 8 consecutive k of row m4 + e
-        u32x4 v;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-          const unsigned sel = 0x0c000c00u | (unsigned)e | ((unsigned)(4 + e) << 16);
-          v[t] = __builtin_amdgcn_perm(rat[2 * t + 1], rat[2 * t], sel) * 0x3f80u;
-        }
-        *reinterpret_cast<u32x4*>(As + bf64_img(m4 + e, c)) = v;
-      }
+      stage_map_m(As, BfImg<kBf64K>{}, (g % (BM / 4)) * 4, g / (BM / 4), rat);
     }
     // exact three-way split of the 4 k x 4 n block, packed along k: per n and plane one 8-byte half chunk
-    using u32x2 = __attribute__((__vector_size__(2 * sizeof(unsigned)))) unsigned;
     u32x2 pl[3][4];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      unsigned h[2][4], m[2][4], l[2][4];
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float x = __uint_as_float(rb[2 * t + u][e]);
-          const unsigned hb = __float_as_uint(x) & 0xffff0000u;
-          const float r1 = x - __uint_as_float(hb);
-          const unsigned mb_ = __float_as_uint(r1) & 0xffff0000u;
-          const float r2 = r1 - __uint_as_float(mb_);
-          h[u][e] = hb; m[u][e] = mb_; l[u][e] = __float_as_uint(r2);
-        }
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        pl[0][e][t] = __builtin_amdgcn_perm(h[1][e], h[0][e], 0x07060302u);
-        pl[1][e][t] = __builtin_amdgcn_perm(m[1][e], m[0][e], 0x07060302u);
-        pl[2][e][t] = __builtin_amdgcn_perm(l[1][e], l[0][e], 0x07060302u);
-      }
-    }
+    split_block<2>(rb, pl);
     const int half = (bk4 & 4) ? 8 : 0;
 #pragma unroll
     for (int pnum = 0; pnum < 3; ++pnum)
@@ -1297,14 +1226,11 @@ __device__ __forceinline__ void gemm_tile_bf64(unsigned char* __restrict__ smem,
 
 template <bool AKC, class Epi>
 __global__ __launch_bounds__(256) void ftm_gemm_bf64_kernel(Mat ma, Mat mb, Epi epi, int M, int N, int K, int klen, int tiles_n) {
-  __shared__ __attribute__((aligned(16))) unsigned char smem[gemm_bf64_lds_bytes<128>()];
+  __shared__ __attribute__((aligned(16))) unsigned char smem[gemm_bf_lds_bytes<128, 64, kBf64K>()];
   const int ks = blockIdx.y, k_lo = ks * klen;
   int tile = blockIdx.x;
   if constexpr (is_rmw<Epi>::value) {
-    if (epi.xcd_remap) {  // see ftm_gemm_bf_kernel
-      const int nwg = gridDim.x, xcd = tile & 7, q8 = nwg >> 3, r8 = nwg & 7;
-      tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (tile >> 3);
-    }
+    if (epi.xcd_remap) tile = xcd_contiguous_tile(tile, gridDim.x);
   }
   gemm_tile_bf64<128, AKC, Epi>(smem, ma, mb, epi, M, N, k_lo, (k_lo + klen < K) ? k_lo + klen : K, tiles_n, tile, ks);
 }
@@ -1333,27 +1259,6 @@ __device__ __forceinline__ int bf6_img(int row, int chunk) {
   // groups are {0-3, 12-15, 20-27}, ...), and four 64-byte rows share a 256-byte bank row, so the XOR term per block of four
   // rows is {0, 3, 2, 1} -- with the obvious {0, 1, 2, 3} a third of the kernel's LDS cycles were conflicts (SQ_LDS_BANK_CONFLICT)
   return row * (KT * 2) + ((chunk ^ (KT == 64 ? (row >> 1) & 7 : (4 - (row >> 2)) & 3)) << 4);
-}
-
-// 8 consecutive k (two float4) -> one 16-byte chunk of 8 bf16 per plane
-__device__ __forceinline__ void split8(const u32x4& v0, const u32x4& v1, u32x4& hi, u32x4& mid, u32x4& lo) {
-  unsigned h[8], m[8], l[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const unsigned xb = e < 4 ? v0[e] : v1[e - 4];
-    const float x = __uint_as_float(xb);
-    const unsigned hb = xb & 0xffff0000u;
-    const float r1 = x - __uint_as_float(hb);
-    const unsigned mb_ = __float_as_uint(r1) & 0xffff0000u;
-    const float r2 = r1 - __uint_as_float(mb_);
-    h[e] = hb; m[e] = mb_; l[e] = __float_as_uint(r2);
-  }
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {  // word t: k = 2 t (low half), 2 t + 1 (high half)
-    hi[t] = __builtin_amdgcn_perm(h[2 * t + 1], h[2 * t], 0x07060302u);
-    mid[t] = __builtin_amdgcn_perm(m[2 * t + 1], m[2 * t], 0x07060302u);
-    lo[t] = __builtin_amdgcn_perm(l[2 * t + 1], l[2 * t], 0x07060302u);
-  }
 }
 
 // ABL: timing-only ablations for tools/debug (results are WRONG unless 0): 1 no split of A (raw words stored), 2 no split at
@@ -1492,7 +1397,7 @@ __global__ __launch_bounds__(256) void ftm_gemm_bf6_kernel(Mat ma, Mat mb, Epi e
 
 template <int BM, int BN, bool AKC, class Epi>
 __global__ __launch_bounds__(256) void ftm_gemm_bf_kernel(Mat ma, Mat mb, Epi epi, int M, int N, int K, int klen, int tiles_n, GroupArgs ga) {
-  __shared__ __attribute__((aligned(16))) unsigned char smem[gemm_bf_lds_bytes<BM, BN>()];
+  __shared__ __attribute__((aligned(16))) unsigned char smem[gemm_bf_lds_bytes<BM, BN, kBfK>()];
   if (ga.n && blockIdx.x == gridDim.x - 1) {  // see ftm_gemm_kernel
     if (blockIdx.y == 0) bucket_group_body<256>(ga, reinterpret_cast<int*>(smem));
     return;
@@ -1502,20 +1407,15 @@ __global__ __launch_bounds__(256) void ftm_gemm_bf_kernel(Mat ma, Mat mb, Epi ep
   // (dealing the K slices of the split-K forward to the XCDs instead of its column tiles -- one L2 per map slice -- was
   // measured at the 224x224 shape and changes nothing: 68.7 vs 69.1 us)
   if constexpr (is_rmw<Epi>::value) {
-    // Blocks are dealt round-robin over the 8 XCDs (observed, never relied on for results): with this remap the blocks of one
-    // XCD walk a contiguous run of tiles, so the 16 column tiles that share a map tile meet in ONE L2 instead of eight.
-    // Bijective for any grid size (cdna_hip_programming.md, XCD swizzle).
-    if (epi.xcd_remap) {
-      const int nwg = gridDim.x, xcd = tile & 7, q8 = nwg >> 3, r8 = nwg & 7;
-      tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (tile >> 3);
-    }
+    // the blocks of one XCD walk a contiguous run of tiles, so the 16 column tiles that share a map tile meet in ONE L2 instead of eight
+    if (epi.xcd_remap) tile = xcd_contiguous_tile(tile, gridDim.x);
   }
   gemm_tile_bf<BM, BN, AKC, Epi>(smem, ma, mb, epi, M, N, k_lo, (k_lo + klen < K) ? k_lo + klen : K, tiles_n, tile, ks);
 }
 
 template <int BM>
 __global__ __launch_bounds__(256) void ftm_forward_l1_bf_kernel(Mat ma, Mat mb, FwdL1Epi epi, int M, int N, int K, int tiles_n) {
-  constexpr int kGemm = gemm_bf_lds_bytes<BM, 64>(), kEpi = 2 * BM * kL1Ld * 4;
+  constexpr int kGemm = gemm_bf_lds_bytes<BM, 64, kBfK>(), kEpi = 2 * BM * kL1Ld * 4;
   __shared__ __attribute__((aligned(16))) unsigned char smem[kGemm > kEpi ? kGemm : kEpi];
   gemm_tile_bf<BM, 64, true, FwdL1Epi>(smem, ma, mb, epi, M, N, 0, K, tiles_n, blockIdx.x, 0);
 }
@@ -1694,7 +1594,7 @@ template <int WM, int VM, int VN, int VK, bool V6 = false, bool W64 = false, cla
 __global__ __launch_bounds__(256) void ftm_backward_bf_kernel(Mat wa, Mat wb, BwwEpi we, int wM, int wN, int wK, int w_tiles_n, int n_w,
                                                               Mat va, Mat vb, VE ve, int vM, int vN, int vK, int v_tiles_n, int n_v,
                                                               CwArgs c, TailRows t, SmallWgrad sw) {
-  constexpr int kW = W64 ? gemm_bf64_lds_bytes<WM>() : gemm_bf_lds_bytes<WM, 64>(), kV = V6 ? gemm_bf6_lds_bytes<VM, VN>() : gemm_lds_floats<VM, VN, VK, true, true>() * 4;
+  constexpr int kW = gemm_bf_lds_bytes<WM, 64, W64 ? kBf64K : kBfK>(), kV = V6 ? gemm_bf6_lds_bytes<VM, VN>() : gemm_lds_floats<VM, VN, VK, true, true>() * 4;
   constexpr int kC = gemm_lds_floats<32, 64, 128, false, false>() * 4;
   constexpr int kWV = kW > kV ? kW : kV;
   constexpr int kLds = kWV > kC ? kWV : kC;
@@ -1947,7 +1847,7 @@ int env_int(const char* name, int fallback) {
 
 // Tile shapes (BM, BN, BK).  BK grows as the tile shrinks so that a K tile always carries >= 2048 MFMA cycles/wave.
 struct Shape {
-  int cfg;  // 0: 32x64x128   1: 64x64x64   2: 128x64x32   3: 64x128x32
+  int cfg;  // row of kCfg: 0-5 the f32 tiles, 6-8 the bf16-split tiles of 32 / 64 / 128 rows
   int bm, bn, bk, tiles_m, tiles_n, ksplit, klen;
 };
 constexpr int kCfg[9][3] = {{32, 64, 128}, {64, 64, 64}, {128, 64, 32}, {64, 128, 32}, {128, 64, 64}, {64, 128, 64},
@@ -2008,33 +1908,36 @@ Shape plan(int M, int N, int K, bool prefer_m, bool allow_split, bool bf_ok = fa
 template <bool AKC, bool BKC, class Epi>
 void launch(hipStream_t st, const Shape& s, Mat ma, Mat mb, Epi epi, int M, int N, int K, GroupArgs ga = GroupArgs{}) {
   const dim3 grid((unsigned)(s.tiles_m * s.tiles_n) + (ga.n ? 1u : 0u), (unsigned)s.ksplit);
-#define NNUE_FTM_LAUNCH(BM, BN, BK)                                                                                           \
+  if (s.cfg < 6) {
+    if constexpr (!is_adam<Epi>::value) {  // (the f32 tiles have no Adam epilogue: rmw_tile_adam is the bf16-split tiles')
+#define NNUE_FTM_LAUNCH(BM, BN, BK) \
   hipLaunchKernelGGL((ftm_gemm_kernel<BM, BN, BK, AKC, BKC, Epi>), grid, dim3(256), 0, st, ma, mb, epi, M, N, K, s.klen, s.tiles_n, ga)
-  switch (s.cfg) {
-    case 0: NNUE_FTM_LAUNCH(32, 64, 128); break;
-    case 1: NNUE_FTM_LAUNCH(64, 64, 64); break;
-    case 2: NNUE_FTM_LAUNCH(128, 64, 32); break;
-    case 3: NNUE_FTM_LAUNCH(64, 128, 32); break;
-    case 4: NNUE_FTM_LAUNCH(128, 64, 64); break;
-    case 5: NNUE_FTM_LAUNCH(64, 128, 64); break;
-    default:
-      if constexpr (!BKC && Epi::kAU8) {  // bf16-split tiles: the map times an f32 operand that is contiguous along its rows
+      switch (s.cfg) {
+        case 0: NNUE_FTM_LAUNCH(32, 64, 128); break;
+        case 1: NNUE_FTM_LAUNCH(64, 64, 64); break;
+        case 2: NNUE_FTM_LAUNCH(128, 64, 32); break;
+        case 3: NNUE_FTM_LAUNCH(64, 128, 32); break;
+        case 4: NNUE_FTM_LAUNCH(128, 64, 64); break;
+        default: NNUE_FTM_LAUNCH(64, 128, 64); break;
+      }
+#undef NNUE_FTM_LAUNCH
+    }
+    return;
+  }
+  if constexpr (!BKC && Epi::kAU8) {  // bf16-split tiles: the map times an f32 operand that is contiguous along its rows
 #define NNUE_FTM_LAUNCH_BF(BM) \
   hipLaunchKernelGGL((ftm_gemm_bf_kernel<BM, 64, AKC, Epi>), grid, dim3(256), 0, st, ma, mb, epi, M, N, K, s.klen, s.tiles_n, ga)
-        // 128-row tiles of the big-table kernels (split-K forward, update in the epilogue) with K tiles of 64: 40 KB and
-        // 124 / 152 registers instead of 80 KB and ~190 / 200 -- four / three workgroups per CU instead of two: forward 67.5 -> 64 us,
-        // update 192.5 -> 184 us at the 224x224 shape (A/B in one run)
-        static const int kt64 = env_int("NNUE_FTM_BF_KT64", 1);  // developer knob
-        if (s.cfg == 6) NNUE_FTM_LAUNCH_BF(32);
-        else if (s.cfg == 7) NNUE_FTM_LAUNCH_BF(64);
-        else if (kt64 && !ga.n && (std::is_same<Epi, FwdEpi>::value || is_rmw<Epi>::value))
-          hipLaunchKernelGGL((ftm_gemm_bf64_kernel<AKC, Epi>), grid, dim3(256), 0, st, ma, mb, epi, M, N, K, s.klen, s.tiles_n);
-        else NNUE_FTM_LAUNCH_BF(128);
+    // 128-row tiles of the big-table kernels (split-K forward, update in the epilogue) with K tiles of 64: 40 KB and
+    // 124 / 152 registers instead of 80 KB and ~190 / 200 -- four / three workgroups per CU instead of two: forward 67.5 -> 64 us,
+    // update 192.5 -> 184 us at the 224x224 shape (A/B in one run)
+    static const int kt64 = env_int("NNUE_FTM_BF_KT64", 1);  // developer knob
+    if (s.cfg == 6) NNUE_FTM_LAUNCH_BF(32);
+    else if (s.cfg == 7) NNUE_FTM_LAUNCH_BF(64);
+    else if (kt64 && !ga.n && (std::is_same<Epi, FwdEpi>::value || is_rmw<Epi>::value))
+      hipLaunchKernelGGL((ftm_gemm_bf64_kernel<AKC, Epi>), grid, dim3(256), 0, st, ma, mb, epi, M, N, K, s.klen, s.tiles_n);
+    else NNUE_FTM_LAUNCH_BF(128);
 #undef NNUE_FTM_LAUNCH_BF
-      }
-      break;
   }
-#undef NNUE_FTM_LAUNCH
 }
 
 // every operand is addressed with 32-bit byte offsets (tile overhang included)
@@ -2564,29 +2467,133 @@ extern "C" int nnue_ftm_backward_tail_rows(const float* sink, const float* d_out
   return nnue_launch_status("nnue_ftm_backward_tail_rows");
 }
 
-extern "C" int nnue_ftm_backward_weight_update(const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight,
-                                               float* momentum_rows, const float* coef, float lr, float momentum, float weight_decay,
-                                               float grad_scale, int first_step, const float* lr_dev, nnue_stream_t stream) {
-  NNUE_REQUIRE(bits && d_out && weight && coef, NNUE_E_ARG, "nnue_ftm_backward_weight_update: null pointer");
-  NNUE_REQUIRE(momentum == 0.0f || momentum_rows, NNUE_E_ARG, "nnue_ftm_backward_weight_update: momentum %g needs the momentum rows", momentum);
-  NNUE_REQUIRE(shape_ok(B, F, P, L1), NNUE_E_ARG, "nnue_ftm_backward_weight_update: B=%d F=%d P=%d L1=%d out of range", B, F, P, L1);
-  NNUE_REQUIRE(nnue_ftm_supported(F, P, L1), NNUE_E_SHAPE, "nnue_ftm_backward_weight_update: P=%d and L1=%d must be multiples of 4", P, L1);
-  NNUE_REQUIRE(nnue_aligned16(bits) && nnue_aligned16(d_out) && nnue_aligned16(weight), NNUE_E_ARG,
-               "nnue_ftm_backward_weight_update: pointers must be 16-byte aligned");
-  const int direct = (F - 1 < P) ? F - 1 : P;
-  if (direct <= 0) return NNUE_OK;
+// ---- the weight gradient with the optimizer's update in its epilogue, and that + the next forward in one pass ---------------
+namespace {
+// the forward of the NEXT step's map that the fused pass (update_forward.h) appends to the update
+struct NextFwd {
+  const uint8_t* bits_next;
+  const float* sink_next;
+  const float* bias;
+  float* out_next;
+  void* scratch;
+  int64_t scratch_bytes;
+};
+
+// pointer checks of the four update entry points (nx: the fused pass's further arguments, or NULL)
+int update_ptrs_nonnull(const char* who, const void* bits, const void* d_out, const void* weight, const void* coef, const NextFwd* nx) {
+  NNUE_REQUIRE(bits && d_out && weight && coef && (!nx || (nx->bits_next && nx->sink_next && nx->bias && nx->out_next && nx->scratch)), NNUE_E_ARG,
+               "%s: null pointer", who);
+  return NNUE_OK;
+}
+int update_ptrs_aligned(const char* who, const void* bits, const void* d_out, const void* weight, const void* momentum_rows, const NextFwd* nx) {
+  NNUE_REQUIRE(nnue_aligned16(bits) && nnue_aligned16(d_out) && nnue_aligned16(weight) &&
+                   (!nx || (nnue_aligned16(nx->bits_next) && nnue_aligned16(nx->bias) && nnue_aligned16(nx->out_next) && nnue_aligned16(nx->scratch) &&
+                            (!momentum_rows || nnue_aligned16(momentum_rows)))),
+               NNUE_E_ARG, "%s: pointers must be 16-byte aligned", who);
+  NNUE_REQUIRE(!nx || bits != nx->bits_next, NNUE_E_ARG, "%s: the two maps must be different buffers", who);
+  return NNUE_OK;
+}
+
+// Shape of the product d_W = A^T d_out whose epilogue applies the update (BwwSgdEpi / BwwAdamEpi): always a bf16-split tile --
+// the in-place epilogues live there -- and never split along K
+int update_product_shape(const char* who, int direct, int L1, int B, Shape* out) {
   Shape s = plan(direct, L1, B, false, false, true);
-  if (s.cfg < 6) {  // launch-sized product: a 64-row bf16 tile (the in-place epilogue lives in the bf16 tile)
+  if (s.cfg < 6) {  // launch-sized product: a 64-row bf16 tile
     s.cfg = 7; s.bm = 64; s.bn = 64; s.bk = kBfK;
     s.tiles_m = (direct + 63) / 64; s.tiles_n = (L1 + 63) / 64; s.ksplit = 1; s.klen = (B + kBfK - 1) / kBfK * kBfK;
   }
-  NNUE_REQUIRE(s.ksplit == 1, NNUE_E_SHAPE, "nnue_ftm_backward_weight_update: the product must not be split along K");
-  static const int xcd = env_int("NNUE_FTM_XCD_REMAP", 1);  // developer knob
+  NNUE_REQUIRE(s.ksplit == 1, NNUE_E_SHAPE, "%s: the product must not be split along K", who);
+  *out = s;
+  return NNUE_OK;
+}
+
+template <class Epi>
+int update_launch(const char* who, const uint8_t* bits, const float* d_out, int B, int P, int L1, int direct, const Epi& epi, nnue_stream_t stream) {
+  Shape s;
+  if (const int rc = update_product_shape(who, direct, L1, B, &s)) return rc;
   launch<false, false>(static_cast<hipStream_t>(stream), s, Mat{bits, (unsigned)((size_t)B * P), P, kIntMax, kIntMax},
-                       Mat{d_out, (unsigned)((size_t)B * L1 * 4), L1, kIntMax, kIntMax},
+                       Mat{d_out, (unsigned)((size_t)B * L1 * 4), L1, kIntMax, kIntMax}, epi, direct, L1, B);
+  return nnue_launch_status(who);
+}
+
+// What an entry point of the fused pass fills of its arguments: the operands, shapes and the hyper-parameters both optimizers
+// have (Adam: `state_rows` = exp_avg, mom = 0, and its own three fields on top).  slabs, klen, tiles_n, xcd_remap and abl stay
+// zero: update_forward_launch fills them from the forward's plan.
+template <class Args>
+Args make_upd_fwd(const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight, float* state_rows, const float* coef,
+                  const float* lr_dev, float lr, float mom, float wd, float scale, const uint8_t* bits_next, int B_next) {
+  Args a{};
+  a.bits = bits;
+  a.bits_next = bits_next;
+  a.d_out = d_out;
+  a.weight = weight;
+  a.momentum = state_rows;
+  a.coef = coef;
+  a.lr_dev = lr_dev;
+  a.B = B;
+  a.Bn = B_next;
+  a.P = P;
+  a.L1 = L1;
+  a.direct = (F - 1 < P) ? F - 1 : P;
+  a.lr = lr;
+  a.mom = mom;
+  a.wd = wd;
+  a.scale = scale;
+  return a;
+}
+
+// The fused pass's launch: the scratch check, the forward's plan (slabs, slab length, column tiles, XCD remap) into `a`, the kernel
+// of the product's K-tile count, ftm_finish_kernel.  first: first step of an SGD momentum buffer (written, not read).
+template <bool kAdam>
+int update_forward_launch(const char* who, std::conditional_t<kAdam, UpdFwdAdam, UpdFwd> a, int F, bool first, const NextFwd& nx, nnue_stream_t stream) {
+  const Shape s = plan(a.Bn, a.L1, a.direct, true, true, true);
+  const int64_t need = (int64_t)s.ksplit * a.Bn * a.L1 * (int64_t)sizeof(float);
+  NNUE_REQUIRE(nx.scratch_bytes >= need, NNUE_E_SCRATCH, "%s: scratch %lld < %lld bytes", who, (long long)nx.scratch_bytes, (long long)need);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  static const int xcd = env_int("NNUE_FTM_XCD_REMAP", 1);  // developer knob
+  a.slabs = static_cast<float*>(nx.scratch);
+  a.klen = s.klen;
+  a.tiles_n = s.tiles_n;
+  a.xcd_remap = (xcd && s.ksplit % 8 == 0) ? 1 : 0;
+  a.abl = env_int("NNUE_FTM_UF_ABL", 0);
+  const dim3 grid((unsigned)(s.tiles_n * s.ksplit));
+  const bool mom = a.momentum != nullptr;
+  auto go = [&](auto nk) {
+    constexpr int NK = decltype(nk)::value;
+    if constexpr (kAdam) hipLaunchKernelGGL((ftm_update_forward_kernel<NK, true, false, true>), grid, dim3(256), 0, st, a);
+    else if (!mom) hipLaunchKernelGGL((ftm_update_forward_kernel<NK, false, false>), grid, dim3(256), 0, st, a);
+    else if (first) hipLaunchKernelGGL((ftm_update_forward_kernel<NK, true, true>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((ftm_update_forward_kernel<NK, true, false>), grid, dim3(256), 0, st, a);
+  };
+  switch ((a.B + 63) / 64) {  // K tiles of the weight-gradient product (nnue_ftm_update_forward_supported: 1, 2, 4, 8 or 16)
+    case 1: go(std::integral_constant<int, 1>{}); break;
+    case 2: go(std::integral_constant<int, 2>{}); break;
+    case 4: go(std::integral_constant<int, 4>{}); break;
+    case 8: go(std::integral_constant<int, 8>{}); break;
+    default: go(std::integral_constant<int, 16>{}); break;
+  }
+  const int64_t count4 = (int64_t)a.Bn * a.L1 / 4;
+  hipLaunchKernelGGL(ftm_finish_kernel, dim3((unsigned)((count4 + 255) / 256)), dim3(256), 0, st, static_cast<const float*>(nx.scratch), s.ksplit, count4,
+                     nx.bias, a.weight + (size_t)(F - 1) * a.L1, nx.sink_next, a.L1, nx.out_next);
+  return nnue_launch_status(who);
+}
+}  // namespace
+
+extern "C" int nnue_ftm_backward_weight_update(const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight,
+                                               float* momentum_rows, const float* coef, float lr, float momentum, float weight_decay,
+                                               float grad_scale, int first_step, const float* lr_dev, nnue_stream_t stream) {
+  const char* who = "nnue_ftm_backward_weight_update";
+  if (const int rc = update_ptrs_nonnull(who, bits, d_out, weight, coef, nullptr)) return rc;
+  NNUE_REQUIRE(momentum == 0.0f || momentum_rows, NNUE_E_ARG, "%s: momentum %g needs the momentum rows", who, momentum);
+  NNUE_REQUIRE(shape_ok(B, F, P, L1), NNUE_E_ARG, "%s: B=%d F=%d P=%d L1=%d out of range", who, B, F, P, L1);
+  NNUE_REQUIRE(nnue_ftm_supported(F, P, L1), NNUE_E_SHAPE, "%s: P=%d and L1=%d must be multiples of 4", who, P, L1);
+  if (const int rc = update_ptrs_aligned(who, bits, d_out, weight, nullptr, nullptr)) return rc;
+  const int direct = (F - 1 < P) ? F - 1 : P;
+  if (direct <= 0) return NNUE_OK;
+  static const int xcd = env_int("NNUE_FTM_XCD_REMAP", 1);  // developer knob
+  return update_launch(who, bits, d_out, B, P, L1, direct,
                        BwwSgdEpi{weight, momentum == 0.0f ? nullptr : momentum_rows, coef, L1, lr, momentum, weight_decay, grad_scale, first_step, xcd, lr_dev},
-                       direct, L1, B);
-  return nnue_launch_status("nnue_ftm_backward_weight_update");
+                       stream);
 }
 
 // nnue_ftm_backward_weight_update + nnue_ftm_forward of the NEXT step's map in one pass over the table (update_forward.h).
@@ -2608,45 +2615,16 @@ extern "C" int nnue_ftm_backward_weight_update_forward(const uint8_t* bits, cons
                                                        float grad_scale, int first_step, const float* lr_dev, const uint8_t* bits_next,
                                                        const float* sink_next, int B_next, const float* bias, float* out_next, void* scratch,
                                                        int64_t scratch_bytes, nnue_stream_t stream) {
-  NNUE_REQUIRE(bits && d_out && weight && coef && bits_next && sink_next && bias && out_next && scratch, NNUE_E_ARG,
-               "nnue_ftm_backward_weight_update_forward: null pointer");
-  NNUE_REQUIRE(momentum == 0.0f || momentum_rows, NNUE_E_ARG, "nnue_ftm_backward_weight_update_forward: momentum %g needs the momentum rows", momentum);
+  const char* who = "nnue_ftm_backward_weight_update_forward";
+  const NextFwd nx{bits_next, sink_next, bias, out_next, scratch, scratch_bytes};
+  if (const int rc = update_ptrs_nonnull(who, bits, d_out, weight, coef, &nx)) return rc;
+  NNUE_REQUIRE(momentum == 0.0f || momentum_rows, NNUE_E_ARG, "%s: momentum %g needs the momentum rows", who, momentum);
   NNUE_REQUIRE(nnue_ftm_update_forward_supported(B, B_next, F, P, L1), NNUE_E_SHAPE,
-               "nnue_ftm_backward_weight_update_forward: B=%d B_next=%d F=%d P=%d L1=%d is not a split-K forward over a big table (use the two separate "
-               "calls)", B, B_next, F, P, L1);
-  NNUE_REQUIRE(nnue_aligned16(bits) && nnue_aligned16(bits_next) && nnue_aligned16(d_out) && nnue_aligned16(weight) && nnue_aligned16(bias) &&
-                   nnue_aligned16(out_next) && nnue_aligned16(scratch) && (!momentum_rows || nnue_aligned16(momentum_rows)),
-               NNUE_E_ARG, "nnue_ftm_backward_weight_update_forward: pointers must be 16-byte aligned");
-  NNUE_REQUIRE(bits != bits_next, NNUE_E_ARG, "nnue_ftm_backward_weight_update_forward: the two maps must be different buffers");
-  const int direct = (F - 1 < P) ? F - 1 : P;
-  const Shape s = plan(B_next, L1, direct, true, true, true);
-  const int64_t need = (int64_t)s.ksplit * B_next * L1 * (int64_t)sizeof(float);
-  NNUE_REQUIRE(scratch_bytes >= need, NNUE_E_SCRATCH, "nnue_ftm_backward_weight_update_forward: scratch %lld < %lld bytes", (long long)scratch_bytes,
-               (long long)need);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  static const int xcd = env_int("NNUE_FTM_XCD_REMAP", 1);  // developer knob
-  const int blocks = s.tiles_n * s.ksplit;
-  UpdFwd a{bits, bits_next, d_out, weight, momentum == 0.0f ? nullptr : momentum_rows, coef, lr_dev, static_cast<float*>(scratch),
-           B, B_next, P, L1, direct, s.klen, s.tiles_n, (xcd && s.ksplit % 8 == 0) ? 1 : 0, lr, momentum, weight_decay, grad_scale, env_int("NNUE_FTM_UF_ABL", 0)};
-  const bool mom = a.momentum != nullptr, first = mom && first_step;
-#define NNUE_UF_LAUNCH(NK)                                                                                                         \
-  do {                                                                                                                             \
-    if (!mom) hipLaunchKernelGGL((ftm_update_forward_kernel<NK, false, false>), dim3((unsigned)blocks), dim3(256), 0, st, a);      \
-    else if (first) hipLaunchKernelGGL((ftm_update_forward_kernel<NK, true, true>), dim3((unsigned)blocks), dim3(256), 0, st, a);  \
-    else hipLaunchKernelGGL((ftm_update_forward_kernel<NK, true, false>), dim3((unsigned)blocks), dim3(256), 0, st, a);            \
-  } while (0)
-  switch ((B + 63) / 64) {
-    case 1: NNUE_UF_LAUNCH(1); break;
-    case 2: NNUE_UF_LAUNCH(2); break;
-    case 4: NNUE_UF_LAUNCH(4); break;
-    case 8: NNUE_UF_LAUNCH(8); break;
-    default: NNUE_UF_LAUNCH(16); break;
-  }
-#undef NNUE_UF_LAUNCH
-  const int64_t count4 = (int64_t)B_next * L1 / 4;
-  hipLaunchKernelGGL(ftm_finish_kernel, dim3((unsigned)((count4 + 255) / 256)), dim3(256), 0, st, static_cast<const float*>(scratch), s.ksplit, count4,
-                     bias, weight + (size_t)(F - 1) * L1, sink_next, L1, out_next);
-  return nnue_launch_status("nnue_ftm_backward_weight_update_forward");
+               "%s: B=%d B_next=%d F=%d P=%d L1=%d is not a split-K forward over a big table (use the two separate calls)", who, B, B_next, F, P, L1);
+  if (const int rc = update_ptrs_aligned(who, bits, d_out, weight, momentum_rows, &nx)) return rc;
+  const UpdFwd a = make_upd_fwd<UpdFwd>(bits, d_out, B, F, P, L1, weight, momentum == 0.0f ? nullptr : momentum_rows, coef, lr_dev, lr, momentum,
+                                        weight_decay, grad_scale, bits_next, B_next);
+  return update_forward_launch<false>(who, a, F, a.momentum && first_step, nx, stream);
 }
 
 // ---- ... and with Adam (train.py:465-470): BwwAdamEpi / the kAdam form of the fused pass -----------------------------------------
@@ -2670,29 +2648,15 @@ extern "C" int nnue_ftm_backward_weight_update_adam(const uint8_t* bits, const f
                                                     const int32_t* step_counter, float lr, float beta1, float beta2, float eps,
                                                     float weight_decay, float grad_scale, const float* lr_dev, nnue_stream_t stream) {
   const char* who = "nnue_ftm_backward_weight_update_adam";
-  NNUE_REQUIRE(bits && d_out && weight && coef, NNUE_E_ARG, "%s: null pointer", who);
+  if (const int rc = update_ptrs_nonnull(who, bits, d_out, weight, coef, nullptr)) return rc;
   if (const int rc = adam_table_args_ok(who, exp_avg_rows, exp_avg_sq_rows, step_counter, B, F, P, L1, beta1, beta2, eps)) return rc;
-  NNUE_REQUIRE(nnue_aligned16(bits) && nnue_aligned16(d_out) && nnue_aligned16(weight), NNUE_E_ARG, "%s: pointers must be 16-byte aligned", who);
+  if (const int rc = update_ptrs_aligned(who, bits, d_out, weight, nullptr, nullptr)) return rc;
   const int direct = (F - 1 < P) ? F - 1 : P;
   if (direct <= 0) return NNUE_OK;
-  Shape s = plan(direct, L1, B, false, false, true);
-  if (s.cfg < 6) {  // launch-sized product: a 64-row bf16 tile (the in-place epilogue lives in the bf16 tile)
-    s.cfg = 7; s.bm = 64; s.bn = 64; s.bk = kBfK;
-    s.tiles_m = (direct + 63) / 64; s.tiles_n = (L1 + 63) / 64; s.ksplit = 1; s.klen = (B + kBfK - 1) / kBfK * kBfK;
-  }
-  NNUE_REQUIRE(s.ksplit == 1, NNUE_E_SHAPE, "%s: the product must not be split along K", who);
-  static const int xcd = env_int("NNUE_FTM_XCD_REMAP", 1);   // developer knobs, as nnue_ftm_backward_weight_update
-  static const int kt64 = env_int("NNUE_FTM_BF_KT64", 1);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const Mat ma{bits, (unsigned)((size_t)B * P), P, kIntMax, kIntMax}, mb{d_out, (unsigned)((size_t)B * L1 * 4), L1, kIntMax, kIntMax};
-  const BwwAdamEpi epi{weight, exp_avg_rows, exp_avg_sq_rows, coef, step_counter, L1, lr, beta1, beta2, eps, weight_decay, grad_scale, xcd, lr_dev};
-  const dim3 grid((unsigned)(s.tiles_m * s.tiles_n), 1u);
-  // only the bf16-split tiles carry the in-place epilogue (launch<>'s default branch without the f32 tiles)
-  if (s.cfg == 6) hipLaunchKernelGGL((ftm_gemm_bf_kernel<32, 64, false, BwwAdamEpi>), grid, dim3(256), 0, st, ma, mb, epi, direct, L1, B, s.klen, s.tiles_n, GroupArgs{});
-  else if (s.cfg == 7) hipLaunchKernelGGL((ftm_gemm_bf_kernel<64, 64, false, BwwAdamEpi>), grid, dim3(256), 0, st, ma, mb, epi, direct, L1, B, s.klen, s.tiles_n, GroupArgs{});
-  else if (kt64) hipLaunchKernelGGL((ftm_gemm_bf64_kernel<false, BwwAdamEpi>), grid, dim3(256), 0, st, ma, mb, epi, direct, L1, B, s.klen, s.tiles_n);
-  else hipLaunchKernelGGL((ftm_gemm_bf_kernel<128, 64, false, BwwAdamEpi>), grid, dim3(256), 0, st, ma, mb, epi, direct, L1, B, s.klen, s.tiles_n, GroupArgs{});
-  return nnue_launch_status(who);
+  static const int xcd = env_int("NNUE_FTM_XCD_REMAP", 1);  // developer knob
+  return update_launch(who, bits, d_out, B, P, L1, direct,
+                       BwwAdamEpi{weight, exp_avg_rows, exp_avg_sq_rows, coef, step_counter, L1, lr, beta1, beta2, eps, weight_decay, grad_scale, xcd, lr_dev},
+                       stream);
 }
 
 extern "C" int nnue_ftm_backward_weight_update_forward_adam(const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight,
@@ -2702,38 +2666,20 @@ extern "C" int nnue_ftm_backward_weight_update_forward_adam(const uint8_t* bits,
                                                             const uint8_t* bits_next, const float* sink_next, int B_next, const float* bias,
                                                             float* out_next, void* scratch, int64_t scratch_bytes, nnue_stream_t stream) {
   const char* who = "nnue_ftm_backward_weight_update_forward_adam";
-  NNUE_REQUIRE(bits && d_out && weight && coef && bits_next && sink_next && bias && out_next && scratch, NNUE_E_ARG, "%s: null pointer", who);
+  const NextFwd nx{bits_next, sink_next, bias, out_next, scratch, scratch_bytes};
+  if (const int rc = update_ptrs_nonnull(who, bits, d_out, weight, coef, &nx)) return rc;
   if (const int rc = adam_table_args_ok(who, exp_avg_rows, exp_avg_sq_rows, step_counter, B, F, P, L1, beta1, beta2, eps)) return rc;
   NNUE_REQUIRE(nnue_ftm_update_forward_supported(B, B_next, F, P, L1), NNUE_E_SHAPE,
                "%s: B=%d B_next=%d F=%d P=%d L1=%d is not a split-K forward over a big table (use the two separate calls)", who, B, B_next, F, P, L1);
-  NNUE_REQUIRE(nnue_aligned16(bits) && nnue_aligned16(bits_next) && nnue_aligned16(d_out) && nnue_aligned16(weight) && nnue_aligned16(bias) &&
-                   nnue_aligned16(out_next) && nnue_aligned16(scratch),
-               NNUE_E_ARG, "%s: pointers must be 16-byte aligned", who);
-  NNUE_REQUIRE(bits != bits_next, NNUE_E_ARG, "%s: the two maps must be different buffers", who);
-  const int direct = (F - 1 < P) ? F - 1 : P;
-  const Shape s = plan(B_next, L1, direct, true, true, true);
-  const int64_t need = (int64_t)s.ksplit * B_next * L1 * (int64_t)sizeof(float);
-  NNUE_REQUIRE(scratch_bytes >= need, NNUE_E_SCRATCH, "%s: scratch %lld < %lld bytes", who, (long long)scratch_bytes, (long long)need);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  static const int xcd = env_int("NNUE_FTM_XCD_REMAP", 1);  // developer knob
-  const int blocks = s.tiles_n * s.ksplit;
-  UpdFwdAdam a{};
-  static_cast<UpdFwd&>(a) = UpdFwd{bits, bits_next, d_out, weight, exp_avg_rows, coef, lr_dev, static_cast<float*>(scratch), B, B_next, P, L1, direct, s.klen,
-                                   s.tiles_n, (xcd && s.ksplit % 8 == 0) ? 1 : 0, lr, 0.0f, weight_decay, grad_scale, env_int("NNUE_FTM_UF_ABL", 0)};
+  if (const int rc = update_ptrs_aligned(who, bits, d_out, weight, nullptr, &nx)) return rc;
+  UpdFwdAdam a = make_upd_fwd<UpdFwdAdam>(bits, d_out, B, F, P, L1, weight, exp_avg_rows, coef, lr_dev, lr, 0.0f, weight_decay, grad_scale,
+                                          bits_next, B_next);
   a.exp_avg_sq = exp_avg_sq_rows;
   a.step_counter = step_counter;
-  a.beta1 = beta1; a.beta2 = beta2; a.eps = eps;
-  switch ((B + 63) / 64) {
-    case 1: hipLaunchKernelGGL((ftm_update_forward_kernel<1, true, false, true>), dim3((unsigned)blocks), dim3(256), 0, st, a); break;
-    case 2: hipLaunchKernelGGL((ftm_update_forward_kernel<2, true, false, true>), dim3((unsigned)blocks), dim3(256), 0, st, a); break;
-    case 4: hipLaunchKernelGGL((ftm_update_forward_kernel<4, true, false, true>), dim3((unsigned)blocks), dim3(256), 0, st, a); break;
-    case 8: hipLaunchKernelGGL((ftm_update_forward_kernel<8, true, false, true>), dim3((unsigned)blocks), dim3(256), 0, st, a); break;
-    default: hipLaunchKernelGGL((ftm_update_forward_kernel<16, true, false, true>), dim3((unsigned)blocks), dim3(256), 0, st, a); break;
-  }
-  const int64_t count4 = (int64_t)B_next * L1 / 4;
-  hipLaunchKernelGGL(ftm_finish_kernel, dim3((unsigned)((count4 + 255) / 256)), dim3(256), 0, st, static_cast<const float*>(scratch), s.ksplit, count4,
-                     bias, weight + (size_t)(F - 1) * L1, sink_next, L1, out_next);
-  return nnue_launch_status(who);
+  a.beta1 = beta1;
+  a.beta2 = beta2;
+  a.eps = eps;
+  return update_forward_launch<true>(who, a, F, false, nx, stream);
 }
 
 // Which matrix unit a product of this shape runs on (the launch policy above, for reporting: bench.py prices a kernel

@@ -143,40 +143,10 @@ __global__ __launch_bounds__(256, 2) void ftm_update_forward_kernel(std::conditi
 #pragma unroll
     for (int i = 0; i < 4; ++i) rb[i] = __builtin_amdgcn_raw_buffer_load_b128(rsb, bb + i * (L1 * 4), 0, 0);
   };
-  using u32x2 = __attribute__((__vector_size__(2 * sizeof(unsigned)))) unsigned;
   auto stage1 = [&]() {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {  // byte e of the eight words = 8 consecutive k of table row am4 + e
-      u32x4 v;
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const unsigned sel = 0x0c000c00u | (unsigned)e | ((unsigned)(4 + e) << 16);
-        v[t] = __builtin_amdgcn_perm(rat[2 * t + 1], rat[2 * t], sel) * 0x3f80u;
-      }
-      *reinterpret_cast<u32x4*>(As + bf64_img(am4 + e, ak8 >> 3)) = v;
-    }
+    stage_map_m(As, BfImg<kBf64K>{}, am4, ak8 >> 3, rat);
     u32x2 pl[3][4];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      unsigned h[2][4], m[2][4], l[2][4];
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float x = __uint_as_float(rb[2 * t + u][e]);
-          const unsigned hb = __float_as_uint(x) & 0xffff0000u;
-          const float r1 = x - __uint_as_float(hb);
-          const unsigned mb_ = __float_as_uint(r1) & 0xffff0000u;
-          const float r2 = r1 - __uint_as_float(mb_);
-          h[u][e] = hb; m[u][e] = mb_; l[u][e] = __float_as_uint(r2);
-        }
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        pl[0][e][t] = __builtin_amdgcn_perm(h[1][e], h[0][e], 0x07060302u);
-        pl[1][e][t] = __builtin_amdgcn_perm(m[1][e], m[0][e], 0x07060302u);
-        pl[2][e][t] = __builtin_amdgcn_perm(l[1][e], l[0][e], 0x07060302u);
-      }
-    }
+    split_block<2>(rb, pl);
     const int half = (bk4 & 4) ? 8 : 0;
 #pragma unroll
     for (int pnum = 0; pnum < 3; ++pnum)
@@ -196,15 +166,8 @@ __global__ __launch_bounds__(256, 2) void ftm_update_forward_kernel(std::conditi
   auto stage3 = [&]() {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-      const int g = tid0 + 256 * i, row = an_row_of(g), c = (g & 3) * 2;
-      u32x4 lo, hi;
-      unsigned x, y;
-      bytes_to_bf16(ran[i][0], x, y); lo[0] = x; lo[1] = y;
-      bytes_to_bf16(ran[i][1], x, y); lo[2] = x; lo[3] = y;
-      bytes_to_bf16(ran[i][2], x, y); hi[0] = x; hi[1] = y;
-      bytes_to_bf16(ran[i][3], x, y); hi[2] = x; hi[3] = y;
-      *reinterpret_cast<u32x4*>(An + bf64_img(row, c)) = lo;
-      *reinterpret_cast<u32x4*>(An + bf64_img(row, c + 1)) = hi;
+      const int g = tid0 + 256 * i;
+      stage_map_k(An, BfImg<kBf64K>{}, an_row_of(g), (g & 3) * 2, ran[i]);
     }
   };
   f32x4 accw[4][2], accf[4][2];
@@ -395,29 +358,7 @@ __global__ __launch_bounds__(256, 2) void ftm_update_forward_kernel(std::conditi
     // ---------------- phase 3: W_new planes + forward
     {
       u32x4 pl[3][4];  // [plane][column e]: 8 bf16 along k (the thread's eight table rows)
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        unsigned h[2][4], m[2][4], l[2][4];
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-          const float xs[4] = {w[2 * t + u].x, w[2 * t + u].y, w[2 * t + u].z, w[2 * t + u].w};
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const float x = xs[e];
-            const unsigned hb = __float_as_uint(x) & 0xffff0000u;
-            const float r1 = x - __uint_as_float(hb);
-            const unsigned mb_ = __float_as_uint(r1) & 0xffff0000u;
-            const float r2 = r1 - __uint_as_float(mb_);
-            h[u][e] = hb; m[u][e] = mb_; l[u][e] = __float_as_uint(r2);
-          }
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          pl[0][e][t] = __builtin_amdgcn_perm(h[1][e], h[0][e], 0x07060302u);
-          pl[1][e][t] = __builtin_amdgcn_perm(m[1][e], m[0][e], 0x07060302u);
-          pl[2][e][t] = __builtin_amdgcn_perm(l[1][e], l[0][e], 0x07060302u);
-        }
-      }
+      split_block<4>(w, pl);
 #pragma unroll
       for (int pnum = 0; pnum < 3; ++pnum)
 #pragma unroll
