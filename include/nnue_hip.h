@@ -40,7 +40,7 @@
 extern "C" {
 #endif
 
-#define NNUE_HIP_ABI_VERSION 36
+#define NNUE_HIP_ABI_VERSION 37
 
 #define NNUE_OK 0
 #define NNUE_E_ARG (-1)     /* null pointer, non-positive size, bad alignment */
@@ -609,6 +609,47 @@ int64_t nnue_engine_stream_state_bytes(const nnue_engine_model* m, int S);
 int nnue_engine_stream_step(const nnue_engine_model* m, const float* images, const uint8_t* active, int S, int H, int W,
                             void* state, int64_t state_bytes, float* logits, float* density, int32_t* changed,
                             void* scratch, int64_t scratch_bytes, nnue_stream_t stream);
+
+/* ---- the engine's integer inference with the layer stack chosen per image -------------------------------------
+ *
+ * A `.nnue` file holds K layer stacks (serialize.py:394-491; loader engine/src/nnue_engine.cpp:619-635) and the engine takes a
+ * layer_stack_index per call (nnue_engine.cpp:704-707; an index outside [0, K) means stack 0).  The calls below take all K
+ * stacks, packed stack-major, and choose one per image: stack_in[b] when stack_in != NULL (outside [0, K) = stack 0), else
+ *     stack[b] = min(K-1, n[b] * K / (num_features + 1)),   n[b] = the features the kernel counts as active
+ * (the numerator of density[b]) -- the rule the bucketed model is trained with (nnue.bucket_of), applied to the engine's own
+ * map, which is not the training map (ceil stride, HWC read, quantised conv), so the index may differ from the training one.
+ * The struct is read on the host; `scales` is a HOST array (the scales reach the kernel by value in its arguments), every
+ * other pointer is device memory.  No call copies between host and device or synchronises. */
+typedef struct nnue_engine_stacks {
+  int32_t count;        /* K, 1..64 (the range NNUE accepts) */
+  const float* scales;  /* HOST [K][3]: l1_scale, l2_scale, out_scale -- validated like the single-stack scalars */
+  const int8_t* l1_w;   /* stack-major: [K][(l2+1)*l1] */
+  const int32_t* l1_b;  /* [K][l2+1] */
+  const int8_t* l2_w;   /* [K][l3*2*l2] */
+  const int32_t* l2_b;  /* [K][l3] */
+  const int8_t* out_w;  /* [K][classes*l3] */
+  const int32_t* out_b; /* [K][classes] */
+} nnue_engine_stacks;
+
+/* NNUEEvaluator::evaluate_logits with its layer_stack_index (engine/src/nnue_engine.cpp:704-734) for B images at once, the
+ * index chosen per image as above -- what evaluate_compiled_model's per-image engine call (evaluate.py:143-176) would obtain
+ * with that index.  Arguments, checks and results as nnue_engine_evaluate_logits, bit-identical to the engine stack by stack;
+ * m supplies the conv, the table and the sizes, its own stack pointers and stack scales are not read.  stack_out [B] (device,
+ * required) receives the stack each image used.  NNUE_E_ARG also for a null st, a count outside 1..64, a missing stack tensor
+ * or a scale the single-stack call would refuse. */
+int nnue_engine_evaluate_logits_stacks(const nnue_engine_model* m, const nnue_engine_stacks* st, const float* images,
+                                       int B, int H, int W, const int32_t* stack_in, float* logits, float* density,
+                                       int32_t* stack_out, void* scratch, int64_t scratch_bytes, nnue_stream_t stream);
+
+/* NNUEEvaluator::evaluate_incremental (engine/src/nnue_engine.cpp:739-786) for S streams with the stack of every stream chosen
+ * per step as above (from the step's new feature set; the logits are those its consumer reads, evaluate.py:143-176).
+ * Arguments, checks and results as nnue_engine_stream_step; the state has the same layout and holds nothing about stacks, so
+ * one state buffer may pass between the two calls from step to step.  stack_out [S] (device, required) receives the stack
+ * each stream used.  NNUE_E_ARG also as nnue_engine_evaluate_logits_stacks. */
+int nnue_engine_stream_step_stacks(const nnue_engine_model* m, const nnue_engine_stacks* st, const float* images,
+                                   const uint8_t* active, int S, int H, int W, const int32_t* stack_in, void* state,
+                                   int64_t state_bytes, float* logits, float* density, int32_t* changed, int32_t* stack_out,
+                                   void* scratch, int64_t scratch_bytes, nnue_stream_t stream);
 
 /* Data parallel for bandwidth-sized tables ("exchange only touched rows"; the reference itself is single-device,
  * train.py:263).  The table's weight gradient of the GLOBAL batch is d_W = A^T D with A the {0,1} map [world*B][P] and

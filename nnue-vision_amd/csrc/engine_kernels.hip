@@ -92,9 +92,60 @@ __device__ __forceinline__ void engine_tail(const int32_t* ft, int32_t* pair, in
   }
 }
 
+// Which layer stack a workgroup's image goes through.  NoStackSel: the one stack of the kernel's own arguments (the plain
+// entry points; nothing is added to the kernel).  StackSel: K stacks packed stack-major behind those same pointers, chosen per
+// image -- stack_in[b] when given (outside [0, K) = stack 0, nnue_engine.cpp:705-707), else the training rule on the engine's own
+// count, min(K-1, n*K / (F+1)) (nnue.bucket_of).  The three scales of every stack travel by value in the kernel arguments.
+constexpr int kMaxStacks = 64;
+
+struct NoStackSel {
+  static constexpr bool kSelect = false;
+};
+
+struct StackSel {
+  static constexpr bool kSelect = true;
+  int K;
+  const int32_t* stack_in;
+  int32_t* stack_out;
+  float l1_scale[kMaxStacks];
+  int l2_scale[kMaxStacks];
+  float out_scale[kMaxStacks];
+};
+
+// Resolves the stack of image b from its active-feature count n (uniform over the workgroup), records it, and moves the tail's
+// weights, biases and scales to that stack.
+__device__ __forceinline__ void engine_select_stack(const StackSel& sel, int b, int n, int F, int L1, int L2, int L3, int C,
+                                                    const int8_t* __restrict__& l1_w, const int32_t* __restrict__& l1_b,
+                                                    float& l1_scale, const int8_t* __restrict__& l2_w,
+                                                    const int32_t* __restrict__& l2_b, int& l2_scale,
+                                                    const int8_t* __restrict__& out_w, const int32_t* __restrict__& out_b,
+                                                    float& out_scale) {
+  int k;
+  if (sel.stack_in) {
+    k = sel.stack_in[b];
+    if (k < 0 || k >= sel.K) k = 0;
+  } else {
+    k = (int)((unsigned)(n * sel.K) / (unsigned)(F + 1));  // n <= F and F * K < 2^31 (checked on the host)
+    if (k > sel.K - 1) k = sel.K - 1;
+  }
+  k = __builtin_amdgcn_readfirstlane(k);
+  if (threadIdx.x == 0) sel.stack_out[b] = k;
+  l1_w += (size_t)k * (L2 + 1) * L1;
+  l1_b += (size_t)k * (L2 + 1);
+  l2_w += (size_t)k * L3 * 2 * L2;
+  l2_b += (size_t)k * L3;
+  out_w += (size_t)k * C * L3;
+  out_b += (size_t)k * C;
+  l1_scale = sel.l1_scale[k];
+  l2_scale = sel.l2_scale[k];
+  out_scale = sel.out_scale[k];
+}
+
 // One workgroup per image: feature grid + FeatureTransformer (int16 wrap-around) + clipped ReLU + forward_multiclass
 // (nnue_engine.h:236-283, simd_scalar.cpp:78-96, nnue_engine.cpp:726-729, :480-539).
 // dynamic LDS: ft [L1] i32 | pair [L1] i32 | h1 [L2] i32 | h2 [L3] i32 | counts [4] i32
+// Sel = StackSel: the image's stack is resolved from `count` before the tail (see engine_select_stack).
+template <class Sel>
 __global__ __launch_bounds__(256) void engine_stack_kernel(const int8_t* __restrict__ conv, float threshold, int F, int oc,
                                                            const int16_t* __restrict__ ft_w, const int32_t* __restrict__ ft_b,
                                                            int quantized_one, const int8_t* __restrict__ l1_w,
@@ -102,7 +153,7 @@ __global__ __launch_bounds__(256) void engine_stack_kernel(const int8_t* __restr
                                                            const int8_t* __restrict__ l2_w, const int32_t* __restrict__ l2_b,
                                                            int l2_scale, const int8_t* __restrict__ out_w,
                                                            const int32_t* __restrict__ out_b, float out_scale, int L1, int L2,
-                                                           int L3, int C, float* __restrict__ logits, float* __restrict__ density) {
+                                                           int L3, int C, float* __restrict__ logits, float* __restrict__ density, Sel sel) {
   extern __shared__ int32_t lds[];
   int32_t* ft = lds;
   int32_t* pair = ft + L1;
@@ -144,6 +195,8 @@ __global__ __launch_bounds__(256) void engine_stack_kernel(const int8_t* __restr
   if (tid == 0) density[b] = (float)count / (float)F;
   __syncthreads();
 
+  if constexpr (Sel::kSelect)
+    engine_select_stack(sel, b, count, F, L1, L2, L3, C, l1_w, l1_b, l1_scale, l2_w, l2_b, l2_scale, out_w, out_b, out_scale);
   engine_tail(ft, pair, h1, h2, l1_w, l1_b, l1_scale, l2_w, l2_b, l2_scale, out_w, out_b, out_scale, L1, L2, L3, C,
               logits + (size_t)b * C);
   (void)counts;
@@ -183,7 +236,8 @@ __host__ __device__ inline StreamLayout stream_layout(int64_t S, int64_t F, int6
 // other slot, so no barrier has to order those reads before the stores, and a launch never reads a word it writes.
 // dynamic LDS: ft [L1] i32 | pair [L1] i32 | h1 [L2] i32 | h2 [L3] i32 | counts [8] i32 | (8-byte aligned) new [W64] u64 |
 // old [W64] u64
-template <bool kFeatures>
+// Sel = StackSel: the stream's stack is resolved from `n_new` before the tail (see engine_select_stack); the state is the same.
+template <bool kFeatures, class Sel>
 __global__ __launch_bounds__(256) void engine_stream_kernel(const int8_t* __restrict__ conv, const uint8_t* __restrict__ active,
                                                             float threshold, int F, int oc, int S, const int16_t* __restrict__ ft_w,
                                                             const int32_t* __restrict__ ft_b, int quantized_one,
@@ -193,7 +247,7 @@ __global__ __launch_bounds__(256) void engine_stream_kernel(const int8_t* __rest
                                                             const int8_t* __restrict__ out_w, const int32_t* __restrict__ out_b,
                                                             float out_scale, int L1, int L2, int L3, int C, uint8_t* __restrict__ state,
                                                             float* __restrict__ logits, float* __restrict__ density,
-                                                            int32_t* __restrict__ changed) {
+                                                            int32_t* __restrict__ changed, Sel sel) {
   extern __shared__ int32_t lds[];
   int32_t* ft = lds;
   int32_t* pair = ft + L1;
@@ -287,6 +341,8 @@ __global__ __launch_bounds__(256) void engine_stream_kernel(const int8_t* __rest
   }
   __syncthreads();
 
+  if constexpr (Sel::kSelect)
+    engine_select_stack(sel, b, n_new, F, L1, L2, L3, C, l1_w, l1_b, l1_scale, l2_w, l2_b, l2_scale, out_w, out_b, out_scale);
   engine_tail(ft, pair, h1, h2, l1_w, l1_b, l1_scale, l2_w, l2_b, l2_scale, out_w, out_b, out_scale, L1, L2, L3, C,
               logits + (size_t)b * C);
 }
@@ -298,18 +354,38 @@ extern "C" int64_t nnue_engine_scratch(const nnue_engine_model* m, int B) {
   return (int64_t)B * m->num_features;
 }
 
-static bool engine_has_tensors(const nnue_engine_model* m) {
-  return m->conv_w && m->conv_b && m->ft_w && m->ft_b && m->l1_w && m->l1_b && m->l2_w && m->l2_b && m->out_w && m->out_b;
+// A call runs the model's own stack (st == nullptr: the plain entry points) or the K packed stacks of an nnue_engine_stacks,
+// in which case the model's stack pointers and stack scales are not read.
+static bool engine_has_tensors(const nnue_engine_model* m, const nnue_engine_stacks* st) {
+  if (!(m->conv_w && m->conv_b && m->ft_w && m->ft_b)) return false;
+  if (st) return st->l1_w && st->l1_b && st->l2_w && st->l2_b && st->out_w && st->out_b;
+  return m->l1_w && m->l1_b && m->l2_w && m->l2_b && m->out_w && m->out_b;
+}
+
+// What the stack-selecting entry points check before they read anything behind st.
+static int engine_check_stacks(const nnue_engine_stacks* st, const void* stack_out, const char* fn) {
+  NNUE_REQUIRE(st && stack_out, NNUE_E_ARG, "%s: null pointer", fn);
+  NNUE_REQUIRE(st->count >= 1 && st->count <= kMaxStacks, NNUE_E_ARG, "%s: %d layer stacks (1..%d)", fn, st->count, kMaxStacks);
+  NNUE_REQUIRE(st->scales, NNUE_E_ARG, "%s: null pointer", fn);
+  return NNUE_OK;
 }
 
 // Shape and scale checks shared by the engine's entry points (fn names the caller in the message).
-static int engine_check_model(const nnue_engine_model* m, const char* fn) {
+static int engine_check_model(const nnue_engine_model* m, const nnue_engine_stacks* st, const char* fn) {
   const int g = m->grid, oc = m->oc, F = m->num_features;
   NNUE_REQUIRE(g > 0 && oc > 0 && F == g * g * oc, NNUE_E_SHAPE, "%s: num_features %d != %d*%d*%d", fn, F, g, g, oc);
   NNUE_REQUIRE(m->l1 >= 2 && m->l1 <= 256 * kMaxColsPerThread && m->l2 >= 1 && m->l3 >= 1 && m->classes >= 1, NNUE_E_SHAPE,
                "%s: L1=%d (2..%d) L2=%d L3=%d C=%d", fn, m->l1, 256 * kMaxColsPerThread, m->l2, m->l3, m->classes);
-  NNUE_REQUIRE(m->conv_scale >= 1.0f && m->l2_scale >= 1.0f && m->l1_scale > 0.0f && m->out_scale > 0.0f, NNUE_E_ARG,
-               "%s: scales must be positive (integer scales >= 1)", fn);
+  bool scales_ok = m->conv_scale >= 1.0f;
+  if (st) {
+    for (int k = 0; k < st->count; ++k)
+      scales_ok = scales_ok && st->scales[3 * k + 1] >= 1.0f && st->scales[3 * k] > 0.0f && st->scales[3 * k + 2] > 0.0f;
+    // the selector's n * K (n <= F) stays inside 32 bits
+    NNUE_REQUIRE(F <= INT32_MAX / kMaxStacks, NNUE_E_SHAPE, "%s: num_features %d too large for stack selection", fn, F);
+  } else {
+    scales_ok = scales_ok && m->l2_scale >= 1.0f && m->l1_scale > 0.0f && m->out_scale > 0.0f;
+  }
+  NNUE_REQUIRE(scales_ok, NNUE_E_ARG, "%s: scales must be positive (integer scales >= 1)", fn);
   return NNUE_OK;
 }
 
@@ -328,29 +404,85 @@ static int engine_conv_geometry(const nnue_engine_model* m, int H, int W, const 
   return NNUE_OK;
 }
 
-extern "C" int nnue_engine_evaluate_logits(const nnue_engine_model* m, const float* images, int B, int H, int W, float* logits,
-                                           float* density, void* scratch, int64_t scratch_bytes, nnue_stream_t stream) {
-  static const char* fn = "nnue_engine_evaluate_logits";
-  NNUE_REQUIRE(m && images && logits && density && scratch, NNUE_E_ARG, "nnue_engine_evaluate_logits: null pointer");
-  NNUE_REQUIRE(engine_has_tensors(m), NNUE_E_ARG, "nnue_engine_evaluate_logits: model tensor missing");
-  NNUE_REQUIRE(B > 0 && H > 0 && W > 0, NNUE_E_ARG, "nnue_engine_evaluate_logits: B=%d H=%d W=%d must be positive", B, H, W);
-  if (int rc = engine_check_model(m, fn)) return rc;
+// The tail's tensors as the kernels take them: the model's stack, or the base of the packed stacks (their scales travel in
+// the StackSel instead).
+struct EngineTailArgs {
+  const int8_t* l1_w;
+  const int32_t* l1_b;
+  float l1_scale;
+  const int8_t* l2_w;
+  const int32_t* l2_b;
+  int l2_scale;
+  const int8_t* out_w;
+  const int32_t* out_b;
+  float out_scale;
+};
+
+static EngineTailArgs engine_tail_args(const nnue_engine_model* m, const nnue_engine_stacks* st) {
+  if (st) return {st->l1_w, st->l1_b, 0.0f, st->l2_w, st->l2_b, 1, st->out_w, st->out_b, 0.0f};
+  return {m->l1_w, m->l1_b, m->l1_scale, m->l2_w, m->l2_b, (int)m->l2_scale, m->out_w, m->out_b, m->out_scale};
+}
+
+static StackSel engine_stack_sel(const nnue_engine_stacks* st, const int32_t* stack_in, int32_t* stack_out) {
+  StackSel sel{};
+  sel.K = st->count;
+  sel.stack_in = stack_in;
+  sel.stack_out = stack_out;
+  for (int k = 0; k < st->count; ++k) {
+    sel.l1_scale[k] = st->scales[3 * k];
+    sel.l2_scale[k] = (int)st->scales[3 * k + 1];
+    sel.out_scale[k] = st->scales[3 * k + 2];
+  }
+  return sel;
+}
+
+template <class Sel>
+static void engine_launch_stack(const nnue_engine_model* m, const EngineTailArgs& t, const int8_t* conv, int B, size_t lds,
+                                float* logits, float* density, Sel sel, hipStream_t s) {
+  hipLaunchKernelGGL((engine_stack_kernel<Sel>), dim3(B), dim3(256), lds, s, conv, m->threshold, m->num_features, m->oc, m->ft_w,
+                     m->ft_b, (int)(int16_t)m->quantized_one, t.l1_w, t.l1_b, t.l1_scale, t.l2_w, t.l2_b, t.l2_scale, t.out_w,
+                     t.out_b, t.out_scale, m->l1, m->l2, m->l3, m->classes, logits, density, sel);
+}
+
+// nnue_engine_evaluate_logits (select == false; st, stack_in and stack_out unused) and nnue_engine_evaluate_logits_stacks.
+static int engine_evaluate(const char* fn, const nnue_engine_model* m, bool select, const nnue_engine_stacks* st,
+                           const float* images, int B, int H, int W, const int32_t* stack_in, float* logits, float* density,
+                           int32_t* stack_out, void* scratch, int64_t scratch_bytes, nnue_stream_t stream) {
+  NNUE_REQUIRE(m && images && logits && density && scratch, NNUE_E_ARG, "%s: null pointer", fn);
+  if (select)
+    if (int rc = engine_check_stacks(st, stack_out, fn)) return rc;
+  NNUE_REQUIRE(engine_has_tensors(m, st), NNUE_E_ARG, "%s: model tensor missing", fn);
+  NNUE_REQUIRE(B > 0 && H > 0 && W > 0, NNUE_E_ARG, "%s: B=%d H=%d W=%d must be positive", fn, B, H, W);
+  if (int rc = engine_check_model(m, st, fn)) return rc;
   const int oc = m->oc, F = m->num_features;
   int stride, OH, OW;
   if (int rc = engine_conv_geometry(m, H, W, fn, &stride, &OH, &OW)) return rc;
-  NNUE_REQUIRE(scratch_bytes >= (int64_t)B * F, NNUE_E_SCRATCH, "nnue_engine_evaluate_logits: scratch %lld < %lld bytes",
-               (long long)scratch_bytes, (long long)B * F);
-  NNUE_REQUIRE((long long)B * H * W * 3 < (1ll << 40), NNUE_E_SHAPE, "nnue_engine_evaluate_logits: batch too large");
+  NNUE_REQUIRE(scratch_bytes >= (int64_t)B * F, NNUE_E_SCRATCH, "%s: scratch %lld < %lld bytes", fn, (long long)scratch_bytes,
+               (long long)B * F);
+  NNUE_REQUIRE((long long)B * H * W * 3 < (1ll << 40), NNUE_E_SHAPE, "%s: batch too large", fn);
+  const size_t lds = (size_t)(2 * m->l1 + m->l2 + m->l3 + 4) * sizeof(int32_t);
+  NNUE_REQUIRE(lds <= 64 * 1024, NNUE_E_SHAPE, "%s: layer sizes need %zu bytes of LDS", fn, lds);
   hipStream_t s = static_cast<hipStream_t>(stream);
   int8_t* conv = static_cast<int8_t*>(scratch);
   hipLaunchKernelGGL(engine_conv_kernel, dim3((F + 255) / 256, B), dim3(256), 0, s, images, m->conv_w, m->conv_b, m->conv_scale, H, W,
                      stride, OH, OW, oc, F, conv);
-  const size_t lds = (size_t)(2 * m->l1 + m->l2 + m->l3 + 4) * sizeof(int32_t);
-  NNUE_REQUIRE(lds <= 64 * 1024, NNUE_E_SHAPE, "nnue_engine_evaluate_logits: layer sizes need %zu bytes of LDS", lds);
-  hipLaunchKernelGGL(engine_stack_kernel, dim3(B), dim3(256), lds, s, conv, m->threshold, F, oc, m->ft_w, m->ft_b,
-                     (int)(int16_t)m->quantized_one, m->l1_w, m->l1_b, m->l1_scale, m->l2_w, m->l2_b, (int)m->l2_scale, m->out_w,
-                     m->out_b, m->out_scale, m->l1, m->l2, m->l3, m->classes, logits, density);
-  return nnue_launch_status("nnue_engine_evaluate_logits");
+  const EngineTailArgs t = engine_tail_args(m, st);
+  if (select) engine_launch_stack(m, t, conv, B, lds, logits, density, engine_stack_sel(st, stack_in, stack_out), s);
+  else engine_launch_stack(m, t, conv, B, lds, logits, density, NoStackSel{}, s);
+  return nnue_launch_status(fn);
+}
+
+extern "C" int nnue_engine_evaluate_logits(const nnue_engine_model* m, const float* images, int B, int H, int W, float* logits,
+                                           float* density, void* scratch, int64_t scratch_bytes, nnue_stream_t stream) {
+  return engine_evaluate("nnue_engine_evaluate_logits", m, false, nullptr, images, B, H, W, nullptr, logits, density, nullptr, scratch,
+                         scratch_bytes, stream);
+}
+
+extern "C" int nnue_engine_evaluate_logits_stacks(const nnue_engine_model* m, const nnue_engine_stacks* st, const float* images,
+                                                  int B, int H, int W, const int32_t* stack_in, float* logits, float* density,
+                                                  int32_t* stack_out, void* scratch, int64_t scratch_bytes, nnue_stream_t stream) {
+  return engine_evaluate("nnue_engine_evaluate_logits_stacks", m, true, st, images, B, H, W, stack_in, logits, density, stack_out,
+                         scratch, scratch_bytes, stream);
 }
 
 extern "C" int64_t nnue_engine_stream_state_bytes(const nnue_engine_model* m, int S) {
@@ -358,16 +490,28 @@ extern "C" int64_t nnue_engine_stream_state_bytes(const nnue_engine_model* m, in
   return stream_layout(S, m->num_features, m->l1).total;
 }
 
-extern "C" int nnue_engine_stream_step(const nnue_engine_model* m, const float* images, const uint8_t* active, int S, int H, int W,
-                                       void* state, int64_t state_bytes, float* logits, float* density, int32_t* changed,
-                                       void* scratch, int64_t scratch_bytes, nnue_stream_t stream) {
-  static const char* fn = "nnue_engine_stream_step";
+template <bool kFeatures, class Sel>
+static void engine_launch_stream(const nnue_engine_model* m, const EngineTailArgs& t, const int8_t* conv, const uint8_t* active,
+                                 int S, size_t lds, uint8_t* state, float* logits, float* density, int32_t* changed, Sel sel,
+                                 hipStream_t s) {
+  hipLaunchKernelGGL((engine_stream_kernel<kFeatures, Sel>), dim3(S), dim3(256), lds, s, conv, active, m->threshold, m->num_features,
+                     m->oc, S, m->ft_w, m->ft_b, (int)(int16_t)m->quantized_one, t.l1_w, t.l1_b, t.l1_scale, t.l2_w, t.l2_b,
+                     t.l2_scale, t.out_w, t.out_b, t.out_scale, m->l1, m->l2, m->l3, m->classes, state, logits, density, changed, sel);
+}
+
+// nnue_engine_stream_step (select == false; st, stack_in and stack_out unused) and nnue_engine_stream_step_stacks.
+static int engine_stream_step(const char* fn, const nnue_engine_model* m, bool select, const nnue_engine_stacks* st,
+                              const float* images, const uint8_t* active, int S, int H, int W, const int32_t* stack_in, void* state,
+                              int64_t state_bytes, float* logits, float* density, int32_t* changed, int32_t* stack_out,
+                              void* scratch, int64_t scratch_bytes, nnue_stream_t stream) {
   NNUE_REQUIRE(m && state && logits && density && changed, NNUE_E_ARG, "%s: null pointer", fn);
+  if (select)
+    if (int rc = engine_check_stacks(st, stack_out, fn)) return rc;
   NNUE_REQUIRE((images != nullptr) != (active != nullptr), NNUE_E_ARG, "%s: pass exactly one of images and active", fn);
   NNUE_REQUIRE(nnue_aligned16(state), NNUE_E_ARG, "%s: state must be 16-byte aligned", fn);
-  NNUE_REQUIRE(engine_has_tensors(m), NNUE_E_ARG, "%s: model tensor missing", fn);
+  NNUE_REQUIRE(engine_has_tensors(m, st), NNUE_E_ARG, "%s: model tensor missing", fn);
   NNUE_REQUIRE(S > 0, NNUE_E_ARG, "%s: S=%d must be positive", fn, S);
-  if (int rc = engine_check_model(m, fn)) return rc;
+  if (int rc = engine_check_model(m, st, fn)) return rc;
   const int oc = m->oc, F = m->num_features, L1 = m->l1, W64 = (F + 63) / 64;
   const int64_t need = nnue_engine_stream_state_bytes(m, S);
   NNUE_REQUIRE(state_bytes >= need, NNUE_E_SCRATCH, "%s: state %lld < %lld bytes", fn, (long long)state_bytes, (long long)need);
@@ -383,19 +527,34 @@ extern "C" int nnue_engine_stream_step(const nnue_engine_model* m, const float* 
     NNUE_REQUIRE((long long)S * H * W * 3 < (1ll << 40), NNUE_E_SHAPE, "%s: batch too large", fn);
   }
   hipStream_t s = static_cast<hipStream_t>(stream);
-  uint8_t* st = static_cast<uint8_t*>(state);
-  const int q1 = (int)(int16_t)m->quantized_one, l2s = (int)m->l2_scale;
+  uint8_t* sp = static_cast<uint8_t*>(state);
+  const EngineTailArgs t = engine_tail_args(m, st);
   if (images) {
     int8_t* conv = static_cast<int8_t*>(scratch);
     hipLaunchKernelGGL(engine_conv_kernel, dim3((F + 255) / 256, S), dim3(256), 0, s, images, m->conv_w, m->conv_b, m->conv_scale, H,
                        W, stride, OH, OW, oc, F, conv);
-    hipLaunchKernelGGL(engine_stream_kernel<false>, dim3(S), dim3(256), lds, s, conv, nullptr, m->threshold, F, oc, S, m->ft_w,
-                       m->ft_b, q1, m->l1_w, m->l1_b, m->l1_scale, m->l2_w, m->l2_b, l2s, m->out_w, m->out_b, m->out_scale, L1,
-                       m->l2, m->l3, m->classes, st, logits, density, changed);
+    if (select)
+      engine_launch_stream<false>(m, t, conv, nullptr, S, lds, sp, logits, density, changed, engine_stack_sel(st, stack_in, stack_out), s);
+    else engine_launch_stream<false>(m, t, conv, nullptr, S, lds, sp, logits, density, changed, NoStackSel{}, s);
   } else {
-    hipLaunchKernelGGL(engine_stream_kernel<true>, dim3(S), dim3(256), lds, s, nullptr, active, m->threshold, F, oc, S, m->ft_w,
-                       m->ft_b, q1, m->l1_w, m->l1_b, m->l1_scale, m->l2_w, m->l2_b, l2s, m->out_w, m->out_b, m->out_scale, L1,
-                       m->l2, m->l3, m->classes, st, logits, density, changed);
+    if (select)
+      engine_launch_stream<true>(m, t, nullptr, active, S, lds, sp, logits, density, changed, engine_stack_sel(st, stack_in, stack_out), s);
+    else engine_launch_stream<true>(m, t, nullptr, active, S, lds, sp, logits, density, changed, NoStackSel{}, s);
   }
   return nnue_launch_status(fn);
+}
+
+extern "C" int nnue_engine_stream_step(const nnue_engine_model* m, const float* images, const uint8_t* active, int S, int H, int W,
+                                       void* state, int64_t state_bytes, float* logits, float* density, int32_t* changed,
+                                       void* scratch, int64_t scratch_bytes, nnue_stream_t stream) {
+  return engine_stream_step("nnue_engine_stream_step", m, false, nullptr, images, active, S, H, W, nullptr, state, state_bytes, logits,
+                            density, changed, nullptr, scratch, scratch_bytes, stream);
+}
+
+extern "C" int nnue_engine_stream_step_stacks(const nnue_engine_model* m, const nnue_engine_stacks* st, const float* images,
+                                              const uint8_t* active, int S, int H, int W, const int32_t* stack_in, void* state,
+                                              int64_t state_bytes, float* logits, float* density, int32_t* changed,
+                                              int32_t* stack_out, void* scratch, int64_t scratch_bytes, nnue_stream_t stream) {
+  return engine_stream_step("nnue_engine_stream_step_stacks", m, true, st, images, active, S, H, W, stack_in, state, state_bytes, logits,
+                            density, changed, stack_out, scratch, scratch_bytes, stream);
 }

@@ -8,8 +8,9 @@ atomics) on the GPU; the per-batch mean losses and the K x K matrix stay on the 
 once.  Accuracy and the support-weighted precision / recall / F1 (``zero_division=0``) are then formed from
 the matrix in float64 -- the same numbers sklearn produces, without sklearn.
 
-``evaluate_compiled_model`` (one subprocess of the C++ engine per image) is out of scope and stays with the
-reference.
+``evaluate_compiled_model`` (the reference runs one subprocess of the C++ engine per image) serialises the model and runs
+the engine's integer inference for whole batches on the GPU (nnue_hip/engine.py), the layer stack chosen per image when
+the model has several.
 """
 from __future__ import annotations
 
@@ -136,7 +137,10 @@ def evaluate_compiled_model(model: torch.nn.Module, loader, model_type: str) -> 
     serialised to a temporary `.nnue` file exactly as there, the file is loaded the way the C++ engine loads it, and
     the engine's integer `evaluate_logits` runs for whole batches on the GPU (bit-identical logits and densities,
     include/nnue_hip.h: nnue_engine_evaluate_logits).  Returns the reference's keys: the compute_metrics dict plus
-    `ms_per_sample` (GPU time of the engine call per sample) and `latent_density` (mean active fraction)."""
+    `ms_per_sample` (GPU time of the engine call per sample) and `latent_density` (mean active fraction).
+    A model with ``num_ls_buckets`` K > 1 is loaded with all K layer stacks and every image goes through the stack its own
+    active-feature count selects (``engine.stack_of``: the training rule on the engine's map), so the metrics describe the
+    network that was trained; earlier versions of this function pushed every image through stack 0.  K = 1 is unchanged."""
     import tempfile
     import time
     from pathlib import Path
@@ -150,7 +154,7 @@ def evaluate_compiled_model(model: torch.nn.Module, loader, model_type: str) -> 
     with tempfile.TemporaryDirectory() as tmp:
         path = Path(tmp) / "model.nnue"
         serialize_model(model, path)
-        engine = EngineModel.load(path)
+        engine = EngineModel.load(path, bucket="auto" if int(getattr(model, "num_ls_buckets", 1)) > 1 else 0)
     outputs, targets, densities = [], [], []
     seconds, samples = 0.0, 0
     for images, labels in loader:

@@ -6,18 +6,24 @@
 bit-identical to the C++ engine (tests/golden/engine_cases.npz holds outputs of the real engine).
 ``stream(S)`` is ``NNUEEvaluator::evaluate_incremental`` (nnue_engine.cpp:739-786) for S independent frame sequences: each
 step updates a stored int16 accumulator by the features that changed, with the same bits as ``evaluate_logits``.
+``EngineModel.load(path, bucket="auto")`` keeps all K layer stacks of the file; both calls then choose the stack of every image
+from its own active-feature count (``stack_of``, the rule a ``num_ls_buckets=K`` model is trained with) or take it from the
+caller -- the engine's ``layer_stack_index`` (nnue_engine.cpp:704-707), bit-identical to the engine stack by stack.
 """
 from __future__ import annotations
 
 import ctypes
 import struct
 from pathlib import Path
-from typing import Iterable, Optional, Tuple
+from typing import Iterable, Optional, Tuple, Union
 
 import numpy as np
 import torch
 
 from . import lib
+
+
+_STACK_TENSORS = ("l1_w", "l1_b", "l2_w", "l2_b", "out_w", "out_b")
 
 
 class _CModel(ctypes.Structure):  # include/nnue_hip.h: nnue_engine_model
@@ -26,8 +32,20 @@ class _CModel(ctypes.Structure):  # include/nnue_hip.h: nnue_engine_model
                 + [(n, ctypes.c_void_p) for n in ("conv_w", "conv_b", "ft_w", "ft_b", "l1_w", "l1_b", "l2_w", "l2_b", "out_w", "out_b")])
 
 
+class _CStacks(ctypes.Structure):  # include/nnue_hip.h: nnue_engine_stacks
+    _fields_ = ([("count", ctypes.c_int32), ("scales", ctypes.POINTER(ctypes.c_float))]
+                + [(n, ctypes.c_void_p) for n in _STACK_TENSORS])
+
+
 class EngineFormatError(ValueError):
     pass
+
+
+def stack_of(active_counts: torch.Tensor, num_stacks: int, num_features: int) -> torch.Tensor:
+    """The layer stack of an image with ``active_counts`` active features: min(K-1, n*K // (num_features+1)), the training
+    rule (``nnue.bucket_of``) on the engine's feature count -- density * num_features of the engine calls."""
+    from nnue import bucket_of
+    return bucket_of(active_counts, num_stacks, num_features)
 
 
 class _Reader:
@@ -52,9 +70,10 @@ class _Reader:
 
 
 class EngineModel:
-    """Quantised tensors of one `.nnue` file on the device + the scalars of its header."""
+    """Quantised tensors of one `.nnue` file on the device + the scalars of its header.  ``stack_scales`` (loaded with
+    bucket="auto"): the six stack tensors hold all K stacks, stack-major, and every call selects a stack per image."""
 
-    def __init__(self, header: dict, tensors: dict, device):
+    def __init__(self, header: dict, tensors: dict, device, stack_scales: Optional[np.ndarray] = None):
         self.header = header
         self.device = torch.device(device)
         self.tensors = {k: torch.from_numpy(v).to(self.device) for k, v in tensors.items()}
@@ -65,15 +84,48 @@ class EngineModel:
             setattr(c, k, float(header[k]))
         for k, t in self.tensors.items():
             setattr(c, k, t.data_ptr())
-        self._c = c
+        self._c = c  # of a stack-selecting model: its stack 0 (the packed tensors begin with it)
         self._scratch: Optional[torch.Tensor] = None
+        self._stacks: Optional[_CStacks] = None
+        if stack_scales is not None:
+            self._scales = np.ascontiguousarray(stack_scales, dtype=np.float32)  # host [K][3], read by every call
+            st = _CStacks()
+            st.count = int(self._scales.shape[0])
+            st.scales = self._scales.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+            for k in _STACK_TENSORS:
+                setattr(st, k, self.tensors[k].data_ptr())
+            self._stacks = st
 
     @property
     def num_classes(self) -> int:
         return int(self.header["classes"])
 
+    @property
+    def num_stacks(self) -> int:
+        """Layer stacks the model selects among: K after load(bucket="auto"), else 1."""
+        return 1 if self._stacks is None else int(self._stacks.count)
+
+    def _stack_arg(self, stacks: Optional[torch.Tensor], n: int, what: str) -> Optional[torch.Tensor]:
+        """The caller's stack indices as the int32 [n] device tensor the C call takes (outside [0, K) = stack 0)."""
+        if stacks is None:
+            return None
+        if self._stacks is None:
+            raise ValueError(f"{what}: stacks= needs a model loaded with bucket=\"auto\" (this one holds a single stack)")
+        if not isinstance(stacks, torch.Tensor) or stacks.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"{what}: stacks must be an int32 or int64 tensor")
+        if not stacks.is_cuda or tuple(stacks.shape) != (n,):
+            raise ValueError(f"{what}: stacks must be a device tensor of shape ({n},), got {tuple(stacks.shape)} on {stacks.device}")
+        if stacks.dtype == torch.int64:  # an index beyond int32 must not wrap into the range
+            stacks = torch.where((stacks >= 0) & (stacks < self.num_stacks), stacks, torch.zeros_like(stacks)).to(torch.int32)
+        return stacks.contiguous()
+
     @staticmethod
-    def load(path, device=None, bucket: int = 0) -> "EngineModel":
+    def load(path, device=None, bucket: Union[int, str] = 0) -> "EngineModel":
+        """bucket: the one layer stack to keep (an index the file lacks means stack 0, nnue_engine.cpp:705-707), or "auto":
+        all of them, packed for per-image selection (their class counts and bias lengths must agree)."""
+        auto = isinstance(bucket, str)
+        if auto and bucket != "auto":
+            raise ValueError(f"bucket: expected an index or \"auto\", got {bucket!r}")
         if not torch.cuda.is_available():
             raise lib.NnueHipError("the engine restatement runs on the GPU only (no CPU fallback in this build)")
         device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
@@ -112,7 +164,8 @@ class EngineModel:
         t["ft_b"] = r.array(np.int32, l1)
         if h["buckets"] < 1:
             raise EngineFormatError("no layer stack in the file")
-        chosen = bucket if bucket < h["buckets"] else 0  # nnue_engine.cpp:705-707
+        chosen = 0 if auto or bucket >= h["buckets"] else bucket  # nnue_engine.cpp:705-707
+        packed = []
         for i in range(h["buckets"]):
             scales = r.take("4f")
             o, n = r.take("2I")
@@ -136,7 +189,20 @@ class EngineModel:
                 h["l1_scale"], h["l2_scale"], h["out_scale"], _ = scales
                 h["classes"] = o
                 t.update(l1_w=l1_w, l1_b=l1_b, l2_w=l2_w, l2_b=l2_b, out_w=out_w, out_b=out_b)
-        return EngineModel(h, t, device)
+            if auto:
+                if o != h["classes"]:
+                    raise EngineFormatError(f"layer stack {i} has {o} classes, stack 0 has {h['classes']}")
+                if (l1_b.size, l2_b.size, out_b.size) != (h["l2"] + 1, h["l3"], o):
+                    raise EngineFormatError(f"layer stack {i}: bias lengths {(l1_b.size, l2_b.size, out_b.size)} != "
+                                            f"{(h['l2'] + 1, h['l3'], o)}")
+                packed.append((scales[:3], dict(l1_w=l1_w, l1_b=l1_b, l2_w=l2_w, l2_b=l2_b, out_w=out_w, out_b=out_b)))
+        if not auto:
+            return EngineModel(h, t, device)
+        if len(packed) > 64:
+            raise EngineFormatError(f"{len(packed)} layer stacks: per-image selection takes at most 64")
+        for k in _STACK_TENSORS:
+            t[k] = np.stack([tensors[k] for _, tensors in packed])
+        return EngineModel(h, t, device, np.array([sc for sc, _ in packed], dtype=np.float32))
 
     def stream(self, num_streams: int) -> "EngineStream":
         """Incremental evaluation of ``num_streams`` frame sequences (see EngineStream)."""
@@ -159,19 +225,30 @@ class EngineModel:
             self._scratch = torch.empty((max(16, need),), dtype=torch.uint8, device=self.device)
         return self._scratch
 
-    def evaluate_logits(self, images: torch.Tensor, height: Optional[int] = None, width: Optional[int] = None
-                        ) -> Tuple[torch.Tensor, torch.Tensor]:
+    def evaluate_logits(self, images: torch.Tensor, height: Optional[int] = None, width: Optional[int] = None,
+                        stacks: Optional[torch.Tensor] = None, return_stacks: bool = False):
         """(logits [B, C] float32, density [B] float32).  ``images`` is what the reference hands the engine: per sample
         a flat buffer of 3*H*W floats which the engine indexes as HWC -- for a [B,3,H,W] tensor that is its memory as
-        it stands (evaluate.py:150-161 passes shape[1], shape[2] as H, W), which is reproduced, not corrected."""
+        it stands (evaluate.py:150-161 passes shape[1], shape[2] as H, W), which is reproduced, not corrected.
+        A model loaded with bucket="auto" puts every image through the stack ``stack_of`` gives for its active-feature
+        count, or through ``stacks`` (device int32/int64 [B]; outside [0, K) = stack 0).  return_stacks: also return the
+        stack every image used, int32 [B] (zeros for a single-stack model)."""
         images = lib._need(images, torch.float32, "images")
         b, h, w = self._frames(images, height, width)
+        stacks = self._stack_arg(stacks, b, "evaluate_logits")
         self._scratch_for(b)
         logits = torch.empty((b, self.num_classes), dtype=torch.float32, device=self.device)
         density = torch.empty((b,), dtype=torch.float32, device=self.device)
-        lib._call("nnue_engine_evaluate_logits", ctypes.addressof(self._c), images.data_ptr(), b, h, w, logits.data_ptr(),
-                  density.data_ptr(), self._scratch.data_ptr(), self._scratch.numel(), lib._stream(images))
-        return logits, density
+        if self._stacks is None:
+            lib._call("nnue_engine_evaluate_logits", ctypes.addressof(self._c), images.data_ptr(), b, h, w, logits.data_ptr(),
+                      density.data_ptr(), self._scratch.data_ptr(), self._scratch.numel(), lib._stream(images))
+            used = torch.zeros((b,), dtype=torch.int32, device=self.device) if return_stacks else None
+        else:
+            used = torch.empty((b,), dtype=torch.int32, device=self.device)
+            lib._call("nnue_engine_evaluate_logits_stacks", ctypes.addressof(self._c), ctypes.addressof(self._stacks),
+                      images.data_ptr(), b, h, w, lib._ptr(stacks), logits.data_ptr(), density.data_ptr(), used.data_ptr(),
+                      self._scratch.data_ptr(), self._scratch.numel(), lib._stream(images))
+        return (logits, density, used) if return_stacks else (logits, density)
 
 
 class EngineStream:
@@ -180,7 +257,9 @@ class EngineStream:
     turned on or off (FeatureTransformer::update_accumulator, nnue_engine.cpp:257-267).  Every step's logits and density
     are bit-identical to ``EngineModel.evaluate_logits`` on the same frames, whatever came before: int16 addition wraps,
     so the order and history of the terms do not matter.  A new stream, and one passed to ``reset``, is refreshed from
-    the bias on its next step.  ``step`` (images) and ``step_features`` (feature maps) may be mixed on one stream."""
+    the bias on its next step.  ``step`` (images) and ``step_features`` (feature maps) may be mixed on one stream.
+    On a model loaded with bucket="auto" every step chooses each stream's layer stack from the step's own feature count
+    (or takes ``stacks=``, as ``evaluate_logits``); ``stacks`` holds the stacks of the last step, int32 [S]."""
 
     def __init__(self, model: EngineModel, num_streams: int):
         s = int(num_streams)
@@ -192,6 +271,7 @@ class EngineStream:
         # zero-filled = every stream invalid; the first S int32 of the state are the valid flags (include/nnue_hip.h)
         self.state = torch.zeros((nbytes,), dtype=torch.uint8, device=model.device)
         self._valid = self.state[:4 * s].view(torch.int32)
+        self.stacks = torch.zeros((s,), dtype=torch.int32, device=model.device)
 
     def reset(self, streams: Optional[Iterable[int]] = None) -> None:
         """Marks all streams, or the given indices, for a refresh from the bias on the next step."""
@@ -216,32 +296,42 @@ class EngineStream:
         if t.dim() < 1 or t.shape[0] != self.num_streams:
             raise ValueError(f"{what}: expected {self.num_streams} streams in dim 0, got shape {tuple(t.shape)}")
 
-    def _run(self, images: Optional[torch.Tensor], active: Optional[torch.Tensor], h: int, w: int
-             ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    def _run(self, images: Optional[torch.Tensor], active: Optional[torch.Tensor], h: int, w: int,
+             stacks: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         m, s = self.model, self.num_streams
+        stacks = m._stack_arg(stacks, s, "EngineStream")
         logits = torch.empty((s, m.num_classes), dtype=torch.float32, device=m.device)
         density = torch.empty((s,), dtype=torch.float32, device=m.device)
         changed = torch.empty((s,), dtype=torch.int32, device=m.device)
         scratch = m._scratch_for(s) if images is not None else None
         src = images if images is not None else active
-        lib._call("nnue_engine_stream_step", ctypes.addressof(m._c), lib._ptr(images), lib._ptr(active), s, h, w,
-                  self.state.data_ptr(), self.state.numel(), logits.data_ptr(), density.data_ptr(), changed.data_ptr(),
-                  lib._ptr(scratch), 0 if scratch is None else scratch.numel(), lib._stream(src))
+        if m._stacks is None:
+            lib._call("nnue_engine_stream_step", ctypes.addressof(m._c), lib._ptr(images), lib._ptr(active), s, h, w,
+                      self.state.data_ptr(), self.state.numel(), logits.data_ptr(), density.data_ptr(), changed.data_ptr(),
+                      lib._ptr(scratch), 0 if scratch is None else scratch.numel(), lib._stream(src))
+        else:
+            used = torch.empty((s,), dtype=torch.int32, device=m.device)
+            lib._call("nnue_engine_stream_step_stacks", ctypes.addressof(m._c), ctypes.addressof(m._stacks), lib._ptr(images),
+                      lib._ptr(active), s, h, w, lib._ptr(stacks), self.state.data_ptr(), self.state.numel(), logits.data_ptr(),
+                      density.data_ptr(), changed.data_ptr(), used.data_ptr(), lib._ptr(scratch),
+                      0 if scratch is None else scratch.numel(), lib._stream(src))
+            self.stacks = used
         return logits, density, changed
 
-    def step(self, frames: torch.Tensor, height: Optional[int] = None, width: Optional[int] = None
-             ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    def step(self, frames: torch.Tensor, height: Optional[int] = None, width: Optional[int] = None,
+             stacks: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """One frame per stream, in the forms ``evaluate_logits`` takes ([S,3,H,W], or [S,3*H*W] with height and width;
         H x W may change between steps).  Returns (logits [S, C] float32, density [S] float32, changed [S] int32): changed
         = features that differ from the stream's previous set, or all active ones on a refresh."""
         self._check(frames, "frames", (torch.float32,))
         _, h, w = self.model._frames(frames, height, width)
-        return self._run(frames.contiguous(), None, h, w)
+        return self._run(frames.contiguous(), None, h, w, stacks)
 
-    def step_features(self, active: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    def step_features(self, active: torch.Tensor, stacks: Optional[torch.Tensor] = None
+                      ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """One active-feature map per stream: bool or uint8 [S, num_features] on the device, non-zero = on.  Every id
         counts (the reference's evaluate_incremental(current_features) takes the indices as given)."""
         self._check(active, "active", (torch.bool, torch.uint8))
         if tuple(active.shape) != (self.num_streams, self.num_features):
             raise ValueError(f"active: expected shape {(self.num_streams, self.num_features)}, got {tuple(active.shape)}")
-        return self._run(None, active.contiguous(), 0, 0)
+        return self._run(None, active.contiguous(), 0, 0, stacks)

@@ -1,8 +1,11 @@
 """Throughput of the engine's integer inference on the GPU beside the reference's way of getting the
 same numbers: one `nnue_inference` subprocess per image (evaluate.py:143-176), timed on this host with oracle/_ref.
 Prints one JSON object:  python tools/bench_engine.py > gpurun_out/engine_bench.json"""
+import argparse
+import contextlib
 import json
 import os
+import statistics
 import subprocess
 import sys
 import tempfile
@@ -20,7 +23,88 @@ import serialize  # noqa: E402
 from nnue_hip.engine import EngineModel  # noqa: E402
 
 
+STACK_SHAPES = [
+    {"name": "cifar_32x32", "g": 10, "fps": 8, "l1": 1024, "l2": 128, "l3": 32, "classes": 10, "size": 32, "batch": 4096},
+    {"name": "224x224", "g": 32, "fps": 64, "l1": 512, "l2": 32, "l3": 32, "classes": 10, "size": 224, "batch": 1024},
+]
+
+
+def _median_ms(pairs):
+    torch.cuda.synchronize()
+    return statistics.median(a.elapsed_time(b) for a, b in pairs)
+
+
+def _alternate(calls, warmup, repeats):
+    """Runs the calls in turn, warmup + repeats rounds; median event time of each over the timed rounds."""
+    times = [[] for _ in calls]
+    for t in range(warmup + repeats):
+        for i, fn in enumerate(calls):
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            fn(t)
+            t1.record()
+            if t >= warmup:
+                times[i].append((t0, t1))
+    return [_median_ms(ts) for ts in times]
+
+
+def bench_stacks(K, warmup, repeats):
+    """--stacks K: per-image layer-stack selection (EngineModel.load(bucket="auto")) against the plain single-stack call, in
+    this process, on the same K-stack file and the same images, at the CIFAR shape (10x10x8, 1024/128/32, batch 4096) and the
+    224x224 shape (32x32x64, 512/32/32, batch 1024).  The conv weights are made non-negative and image b is dark noise with a
+    bright prefix of b/(B-1) of its floats, so the active-feature counts spread over the stacks (`stack_counts`).  The two calls
+    alternate inside one loop; times are medians of device-event-timed calls after warm-up, for evaluate_logits and for
+    stream(B).step on frames that alternate between the batch and the batch rolled by one image.
+        python tools/bench_engine.py --stacks 8 > profiles/engine_stacks.json"""
+    res = {"device": torch.cuda.get_device_name(0), "stacks": K, "warmup": warmup, "repeats": repeats,
+           "timing": "median of device-event-timed calls, plain and selected alternating in one loop", "cases": []}
+    for shape in STACK_SHAPES:
+        torch.manual_seed(0)
+        size, B = shape["size"], shape["batch"]
+        model = nnue.NNUE(nnue.GridFeatureSet(shape["g"], shape["fps"]), shape["l1"], shape["l2"], shape["l3"],
+                          num_classes=shape["classes"], input_size=size, num_ls_buckets=K)
+        with torch.no_grad():
+            model.conv.weight.abs_()
+        with tempfile.TemporaryDirectory() as tmp:
+            path = Path(tmp) / "m.nnue"
+            with contextlib.redirect_stdout(sys.stderr):  # keep stdout to the one JSON object
+                serialize.serialize_model(model, path)
+            plain, auto = EngineModel.load(path), EngineModel.load(path, bucket="auto")
+        n = 3 * size * size
+        x = torch.randn(B, n, device="cuda") * 0.3 - 1.5
+        bright = torch.arange(n, device="cuda")[None, :] < (torch.arange(B, device="cuda") * n // (B - 1))[:, None]
+        x = (x + 3.0 * bright).view(B, 3, size, size).contiguous()
+        del bright
+        frames = (x, x.roll(1, 0).contiguous())
+        logits, density, stack = auto.evaluate_logits(x, return_stacks=True)
+        same = stack == 0  # rows of stack 0 must be the plain call's, bit for bit
+        assert torch.equal(logits[same], plain.evaluate_logits(x)[0][same]) and bool((~same).any())
+        row = {"shape": shape["name"], "batch": B, "F": int(auto.header["num_features"]), "L1": shape["l1"],
+               "stack_counts": torch.bincount(stack.long(), minlength=K).tolist(),
+               "mean_density": float(density.double().mean())}
+        row["plain_ms"], row["selected_ms"] = _alternate([lambda t: plain.evaluate_logits(x), lambda t: auto.evaluate_logits(x)],
+                                                         warmup, repeats)
+        row["selected_over_plain"] = row["selected_ms"] / row["plain_ms"]
+        sp, sa = plain.stream(B), auto.stream(B)
+        row["stream_plain_ms"], row["stream_selected_ms"] = _alternate(
+            [lambda t: sp.step(frames[t & 1]), lambda t: sa.step(frames[t & 1])], warmup, repeats)
+        row["stream_selected_over_plain"] = row["stream_selected_ms"] / row["stream_plain_ms"]
+        print(json.dumps(row), file=sys.stderr)
+        res["cases"].append(row)
+        del x, frames, sp, sa
+    print(json.dumps(res))
+
+
 def main():
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("--stacks", type=int, default=0, help="K: time per-image stack selection against the plain call instead")
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--repeats", type=int, default=50)
+    args = ap.parse_args()
+    if args.stacks:
+        if not torch.cuda.is_available():
+            raise SystemExit("bench_engine: needs a GPU")
+        return bench_stacks(args.stacks, args.warmup, args.repeats)
     torch.manual_seed(0)
     model = nnue.NNUE(nnue.GridFeatureSet(10, 8), 1024, 128, 32, num_classes=10)
     res = {"model": "C2 architecture (800 -> 1024/128/32 -> 10), 32x32 images"}
