@@ -40,7 +40,7 @@
 extern "C" {
 #endif
 
-#define NNUE_HIP_ABI_VERSION 37
+#define NNUE_HIP_ABI_VERSION 38
 
 #define NNUE_OK 0
 #define NNUE_E_ARG (-1)     /* null pointer, non-positive size, bad alignment */
@@ -650,6 +650,31 @@ int nnue_engine_stream_step_stacks(const nnue_engine_model* m, const nnue_engine
                                    const uint8_t* active, int S, int H, int W, const int32_t* stack_in, void* state,
                                    int64_t state_bytes, float* logits, float* density, int32_t* changed, int32_t* stack_out,
                                    void* scratch, int64_t scratch_bytes, nnue_stream_t stream);
+
+/* ---- the engine's tensors from a live model ------------------------------------------------------------------------
+ *
+ * What serialize_model followed by a load of the file leaves in device memory, formed from the model's float32 parameters in
+ * ONE launch, without the file, a host copy or a change to the parameters (the reference's training loop quantises through the
+ * file after every epoch: train.py:389-421).  Sources (device float32, any 4-byte aligned view): conv_w [oc][3][3][3], ft_w
+ * [F][L1], ft_b [L1], and the classifier's w1 [K][L2][L1], b1 [K][L2], w2 [K][L3][L2], b2 [K][L3], w3 [K][C][L3], b3 [K][C]
+ * (K = 1: the reference's SimpleClassifier).  Destination: the tensors of `dst` -- conv_w in the source's flat order, ft_w int16
+ * [F][L1] (16-byte aligned), ft_b -- and the six stack tensors with the engine's padding (serialize.py:423-491): l1_w
+ * [L2+1][L1] with a zero last row, l1_b [L2+1] with a zero last element, l2_w [L3][2*L2] with a zero second half of every row,
+ * l2_b, out_w [C][L3], out_b.  dst_stacks != NULL (count == K): all K stacks, stack-major, into its tensors; dst's own stack
+ * pointers are not read.  dst_stacks == NULL: stack `stack` (in [0, K)) into dst's own stack tensors.  conv_b and every scalar of
+ * the structs are the caller's (the reference's conv has no bias: its quantised bias is zero).
+ * Arithmetic, element for element the serialiser's (serialize.py:218-222, :234-237 after the clamp of nnue.py:528-539):
+ *     weight: clamp(round_half_even(w * 64), -127, 127) with w first clamped to [-1, 1] -- in registers, the source is never
+ *             written -- except the conv's, which is not clamped;      bias: round_half_even(b * 64) as int32, unclamped;
+ * w * 64 is the float32 product, the rounding rintf.  A source element that is not finite, and a bias whose scaled value int32
+ * cannot hold, is written as 0 and ADDED to bad_count[0] (device int32; the caller zeroes it), one atomic per wave that saw any.
+ * NNUE_E_ARG: null pointer, K outside 1..64, a non-positive size, stack outside [0, K), a missing destination tensor, a
+ * misaligned pointer; NNUE_E_SHAPE: odd L1, sizes of dst (or the count of dst_stacks) that differ from the arguments. */
+int nnue_engine_quantize_model(const float* conv_w, const float* ft_w, const float* ft_b, const float* w1, const float* b1,
+                               const float* w2, const float* b2, const float* w3, const float* b3,
+                               int oc, int F, int L1, int L2, int L3, int C, int K, int stack,
+                               const nnue_engine_model* dst, const nnue_engine_stacks* dst_stacks,
+                               int32_t* bad_count, nnue_stream_t stream);
 
 /* Data parallel for bandwidth-sized tables ("exchange only touched rows"; the reference itself is single-device,
  * train.py:263).  The table's weight gradient of the GLOBAL batch is d_W = A^T D with A the {0,1} map [world*B][P] and

@@ -10,7 +10,9 @@ the matrix in float64 -- the same numbers sklearn produces, without sklearn.
 
 ``evaluate_compiled_model`` (the reference runs one subprocess of the C++ engine per image) serialises the model and runs
 the engine's integer inference for whole batches on the GPU (nnue_hip/engine.py), the layer stack chosen per image when
-the model has several.
+the model has several.  ``evaluate_engine`` is the same evaluation for an engine that already exists -- one built from the live
+parameters with ``EngineModel.from_model`` and refreshed with ``requantize`` -- with every sum kept on the device and one
+read-back: what a training loop runs after each epoch (train.py:389-421).
 """
 from __future__ import annotations
 
@@ -177,4 +179,36 @@ def evaluate_compiled_model(model: torch.nn.Module, loader, model_type: str) -> 
     metrics = compute_metrics(outputs, targets)
     metrics["ms_per_sample"] = seconds / samples * 1000.0 if samples else 0.0
     metrics["latent_density"] = float(torch.cat(densities).double().mean().item())
+    return metrics
+
+
+def evaluate_engine(engine, loader) -> Dict[str, float]:
+    """``evaluate_compiled_model``'s metrics (evaluate.py:88-385; same keys) for an ``EngineModel`` that is already on the
+    device, with ``evaluate_model``'s label handling.  Every batch's logits go straight into the confusion kernel and the
+    densities into a float64 device sum; an event pair brackets each engine call, and the only synchronisation is the one
+    read-back at the end, where the event times are summed into ``ms_per_sample`` (GPU time of the engine call per sample)."""
+    device = engine.device
+    confusion, density_sum = None, torch.zeros((1,), dtype=torch.float64, device=device)
+    events, samples = [], 0
+    for images, labels in loader:
+        images = images.to(device, non_blocking=True).float().contiguous()
+        labels = labels.to(device, non_blocking=True).long().reshape(-1)
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        logits, density = engine.evaluate_logits(images)
+        t1.record()
+        events.append((t0, t1))
+        samples += int(images.shape[0])
+        if logits.shape[1] == 1:
+            labels = (labels > 0).long()
+        confusion = _lib.confusion_accumulate(logits, labels, confusion)
+        density_sum += density.double().sum()
+    if not events:
+        raise ValueError("evaluate_engine: empty loader")
+    # the single read-back: the matrix (its int64 bits carried as float64) and the density sum in one buffer
+    host = torch.cat([confusion.reshape(-1).view(torch.float64), density_sum]).cpu()
+    matrix = host[:-1].view(torch.int64).numpy().reshape(tuple(confusion.shape))
+    metrics = metrics_from_confusion(_checked(matrix, samples))
+    metrics["ms_per_sample"] = sum(t0.elapsed_time(t1) for t0, t1 in events) / samples
+    metrics["latent_density"] = float(host[-1].item()) / samples
     return metrics

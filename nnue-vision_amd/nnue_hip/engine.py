@@ -9,6 +9,9 @@ step updates a stored int16 accumulator by the features that changed, with the s
 ``EngineModel.load(path, bucket="auto")`` keeps all K layer stacks of the file; both calls then choose the stack of every image
 from its own active-feature count (``stack_of``, the rule a ``num_ls_buckets=K`` model is trained with) or take it from the
 caller -- the engine's ``layer_stack_index`` (nnue_engine.cpp:704-707), bit-identical to the engine stack by stack.
+``EngineModel.from_model(model)`` builds the same tensors from a live ``nnue.NNUE`` on the device, without the file and without
+touching the model (one launch, include/nnue_hip.h: nnue_engine_quantize_model); ``requantize(model)`` repeats that launch into
+the tensors the engine already holds -- what a training loop does after every epoch.
 """
 from __future__ import annotations
 
@@ -76,7 +79,7 @@ class EngineModel:
     def __init__(self, header: dict, tensors: dict, device, stack_scales: Optional[np.ndarray] = None):
         self.header = header
         self.device = torch.device(device)
-        self.tensors = {k: torch.from_numpy(v).to(self.device) for k, v in tensors.items()}
+        self.tensors = {k: (v if torch.is_tensor(v) else torch.from_numpy(v)).to(self.device) for k, v in tensors.items()}
         c = _CModel()
         for k in ("num_features", "l1", "l2", "l3", "classes", "grid", "oc"):
             setattr(c, k, int(header[k]))
@@ -87,6 +90,10 @@ class EngineModel:
         self._c = c  # of a stack-selecting model: its stack 0 (the packed tensors begin with it)
         self._scratch: Optional[torch.Tensor] = None
         self._stacks: Optional[_CStacks] = None
+        self.generation = 0  # advanced by requantize: an EngineStream's accumulators are sums over the table of one generation
+        self._stack_index = 0  # of a single-stack model built by from_model: the source stack requantize reads
+        self._bad: Optional[torch.Tensor] = None  # device int32: elements the last quantise launches could not represent
+        self._bad_known_zero = False
         if stack_scales is not None:
             self._scales = np.ascontiguousarray(stack_scales, dtype=np.float32)  # host [K][3], read by every call
             st = _CStacks()
@@ -204,6 +211,102 @@ class EngineModel:
             t[k] = np.stack([tensors[k] for _, tensors in packed])
         return EngineModel(h, t, device, np.array([sc for sc, _ in packed], dtype=np.float32))
 
+    # ---- from a live model ---------------------------------------------------------------------
+    @staticmethod
+    def _arch(model) -> dict:
+        """Sizes of an ``nnue.NNUE`` under the header's names (what ``load`` reads from the file ``serialize_model`` writes)."""
+        w = model.input.weight
+        return {"num_features": int(w.shape[0]), "l1": int(w.shape[1]), "l2": int(model.l2_size), "l3": int(model.l3_size),
+                "buckets": int(model.num_ls_buckets), "oc": int(model.conv.weight.shape[0]), "classes": int(model.num_classes)}
+
+    @staticmethod
+    def _scalars(model) -> dict:
+        """The header scalars, formed with the expressions of ``NNUE.get_quantized_model_data`` (nnue.py:541-588) on the
+        model's own device: the threshold's float32 mean is the one the file would carry."""
+        from serialize import QUANT_SCALE
+        return {"nnue2score": model.nnue2score.item(), "quantized_one": 127.0,
+                "threshold": float(model.visual_threshold.detach().mean().cpu().item()), "conv_scale": QUANT_SCALE,
+                "l1_scale": QUANT_SCALE, "l2_scale": QUANT_SCALE, "out_scale": QUANT_SCALE}
+
+    def _quantize_from(self, model, check: bool) -> None:
+        """The one launch: every engine tensor from the model's parameters (padding included; conv_b stays zero)."""
+        a, b, c = model.classifier._linears()
+        src = [lib._need(p.detach(), torch.float32, name) for name, p in (
+            ("conv.weight", model.conv.weight), ("input.weight", model.input.weight), ("input.bias", model.input.bias),
+            ("classifier.0.weight", a.weight), ("classifier.0.bias", a.bias), ("classifier.2.weight", b.weight),
+            ("classifier.2.bias", b.bias), ("classifier.4.weight", c.weight), ("classifier.4.bias", c.bias))]
+        h = self.header
+        if not self._bad_known_zero:  # after an unchecked call, or one that raised
+            self._bad.zero_()
+        self._bad_known_zero = False
+        lib._call("nnue_engine_quantize_model", *[t.data_ptr() for t in src], h["oc"], h["num_features"], h["l1"], h["l2"], h["l3"],
+                  h["classes"], h["buckets"], self._stack_index, ctypes.addressof(self._c),
+                  None if self._stacks is None else ctypes.addressof(self._stacks), self._bad.data_ptr(), lib._stream(src[1]))
+        if check:
+            bad = int(self._bad.item())  # one scalar, once per call
+            if bad:
+                raise ValueError(f"{bad} parameter(s) are not finite or do not fit the engine's integers (written as 0)")
+            self._bad_known_zero = True
+
+    @classmethod
+    def from_model(cls, model, bucket: Union[int, str, None] = None, check: bool = True) -> "EngineModel":
+        """What ``EngineModel.load`` returns for the file ``serialize_model`` would write for ``model`` (an ``nnue.NNUE`` on the
+        GPU), built on the device in one launch; the model -- parameters, ``training`` flag, gradients -- is not changed.
+        bucket: None = "auto" for a model with several layer stacks, else 0; an index keeps that stack (``load``'s rule for
+        one the model lacks).  check: read back the count of parameters that are not finite (or biases beyond int32 once
+        scaled; both are written as 0) and raise ValueError when it is not zero."""
+        if isinstance(bucket, str) and bucket != "auto":
+            raise ValueError(f"bucket: expected an index, None or \"auto\", got {bucket!r}")
+        if not torch.cuda.is_available():
+            raise lib.NnueHipError("the engine restatement runs on the GPU only (no CPU fallback in this build)")
+        import nnue
+        if not isinstance(model, nnue.NNUE):
+            raise TypeError(f"from_model: expected an nnue.NNUE, got {type(model).__name__}")
+        device = lib._need(model.input.weight.detach(), torch.float32, "input.weight").device
+        h = cls._arch(model)
+        k = h["buckets"]
+        auto = bucket == "auto" or (bucket is None and k > 1)
+        if not auto and bucket is not None and bucket < 0:
+            raise ValueError(f"bucket: expected a non-negative index, got {bucket}")
+        if h["num_features"] % h["oc"]:
+            raise EngineFormatError("Invalid feature/channel configuration")
+        g = int(np.sqrt(h["num_features"] // h["oc"]))
+        if g * g * h["oc"] != h["num_features"]:
+            raise EngineFormatError("Invalid feature grid calculation")
+        h["grid"] = g
+        h.update(cls._scalars(model))
+        f, l1, l2, l3, c, oc = h["num_features"], h["l1"], h["l2"], h["l3"], h["classes"], h["oc"]
+        lead = (k,) if auto else ()
+        shapes = {"conv_w": ((oc * 27,), torch.int8), "conv_b": ((oc,), torch.int32), "ft_w": ((f * l1,), torch.int16),
+                  "ft_b": ((l1,), torch.int32), "l1_w": (lead + ((l2 + 1) * l1,), torch.int8), "l1_b": (lead + (l2 + 1,), torch.int32),
+                  "l2_w": (lead + (l3 * 2 * l2,), torch.int8), "l2_b": (lead + (l3,), torch.int32),
+                  "out_w": (lead + (c * l3,), torch.int8), "out_b": (lead + (c,), torch.int32)}
+        tensors = {name: torch.zeros(shape, dtype=dtype, device=device) for name, (shape, dtype) in shapes.items()}
+        scales = np.full((k, 3), h["conv_scale"], dtype=np.float32) if auto else None
+        engine = cls(h, tensors, device, scales)
+        engine._stack_index = 0 if auto or bucket is None or bucket >= k else int(bucket)  # nnue_engine.cpp:705-707
+        engine._bad = torch.zeros((1,), dtype=torch.int32, device=device)
+        engine._bad_known_zero = True
+        engine._quantize_from(model, check)
+        return engine
+
+    def requantize(self, model, check: bool = True) -> None:
+        """``from_model`` again, into the tensors this engine already holds: no allocation, every ``data_ptr()`` unchanged (a
+        captured graph over ``evaluate_logits`` stays valid), the by-value scalars refreshed.  Streams of this model refresh
+        their accumulators on their next step.  A model of another architecture or stack count is refused."""
+        if self._bad is None:
+            raise ValueError("requantize: this engine was loaded from a file; build it with EngineModel.from_model")
+        arch = self._arch(model)
+        mine = {k: self.header[k] for k in arch}
+        if arch != mine:
+            raise ValueError(f"requantize: the model is {arch}, this engine {mine}")
+        lib._need(model.input.weight.detach(), torch.float32, "input.weight")
+        scalars = self._scalars(model)
+        self.header.update(scalars)
+        self._c.threshold = scalars["threshold"]
+        self.generation += 1
+        self._quantize_from(model, check)
+
     def stream(self, num_streams: int) -> "EngineStream":
         """Incremental evaluation of ``num_streams`` frame sequences (see EngineStream)."""
         return EngineStream(self, num_streams)
@@ -256,8 +359,8 @@ class EngineStream:
     the engine's wrapped int16 accumulator and its last active-feature set, and a step applies only the features that
     turned on or off (FeatureTransformer::update_accumulator, nnue_engine.cpp:257-267).  Every step's logits and density
     are bit-identical to ``EngineModel.evaluate_logits`` on the same frames, whatever came before: int16 addition wraps,
-    so the order and history of the terms do not matter.  A new stream, and one passed to ``reset``, is refreshed from
-    the bias on its next step.  ``step`` (images) and ``step_features`` (feature maps) may be mixed on one stream.
+    so the order and history of the terms do not matter.  A new stream, one passed to ``reset``, and every stream after the
+    model's ``requantize``, is refreshed from the bias on its next step.  ``step`` (images) and ``step_features`` (feature maps) may be mixed on one stream.
     On a model loaded with bucket="auto" every step chooses each stream's layer stack from the step's own feature count
     (or takes ``stacks=``, as ``evaluate_logits``); ``stacks`` holds the stacks of the last step, int32 [S]."""
 
@@ -272,6 +375,7 @@ class EngineStream:
         self.state = torch.zeros((nbytes,), dtype=torch.uint8, device=model.device)
         self._valid = self.state[:4 * s].view(torch.int32)
         self.stacks = torch.zeros((s,), dtype=torch.int32, device=model.device)
+        self._generation = model.generation
 
     def reset(self, streams: Optional[Iterable[int]] = None) -> None:
         """Marks all streams, or the given indices, for a refresh from the bias on the next step."""
@@ -299,6 +403,9 @@ class EngineStream:
     def _run(self, images: Optional[torch.Tensor], active: Optional[torch.Tensor], h: int, w: int,
              stacks: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         m, s = self.model, self.num_streams
+        if self._generation != m.generation:  # the model was requantised: the accumulators are sums over the old table
+            self._valid.fill_(0)
+            self._generation = m.generation
         stacks = m._stack_arg(stacks, s, "EngineStream")
         logits = torch.empty((s, m.num_classes), dtype=torch.float32, device=m.device)
         density = torch.empty((s,), dtype=torch.float32, device=m.device)

@@ -16,7 +16,7 @@ import torch
 
 _HERE = Path(__file__).resolve().parent
 LIB_PATH = _HERE / "libnnue_hip.so"
-ABI_VERSION = 37
+ABI_VERSION = 38
 
 _c_int, _c_i64, _c_f, _c_p = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
 
@@ -137,6 +137,8 @@ SIGNATURES = {
                                                     _c_p]),
     "nnue_engine_stream_step_stacks": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_p,
                                                 _c_p, _c_p, _c_i64, _c_p]),
+    "nnue_engine_quantize_model": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int,
+                                            _c_int, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p, _c_p]),
     "nnue_sgd_scratch": (_c_i64, [_c_i64]),
     "nnue_multi_optim_scratch": (_c_i64, [_c_p, _c_int]),
     "nnue_multi_sgd_step": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_int, _c_p, _c_p, _c_p, _c_p, _c_f, _c_p, _c_p, _c_i64, _c_p, _c_p]),

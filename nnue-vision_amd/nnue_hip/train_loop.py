@@ -1,6 +1,5 @@
 """The training driver around the fused step: what ``train.py:257-454`` does for the
-NNUE model, minus the parts that are out of scope here (W&B, RunPod, dataset download, C++-engine compile and
-per-image compiled evaluation).
+NNUE model, minus the parts that are out of scope here (W&B, RunPod, dataset download and the C++-engine compile).
 
 * ``load_config`` executes a Python file as the config module (config/config_loader.py:16-50) -- the same
   ``config/train_*.py`` files work unchanged; only the attributes ``train_model`` reads are used.
@@ -12,6 +11,12 @@ per-image compiled evaluation).
   ``{"epoch", "model_state_dict", "optimizer_state_dict", "metrics", "config_name"}``.
   (serialize.py:536 expects "state_dict" or a bare state dict instead -- the reference's own inconsistency is
   kept: pass ``ckpt["model_state_dict"]`` to it.)
+* ``compiled_eval`` (argument, or the config attribute of that name; off by default) adds the reference's per-epoch compiled
+  evaluation (train.py:389-427): the integer engine is requantised from the live parameters on the device
+  (``EngineModel.requantize``) and run over the validation loader (``evaluate.evaluate_engine``); the row gains
+  ``compiled/f1``, ``compiled/accuracy``, ``compiled/ms_per_sample`` and ``compiled/latent_density``.  Unlike the reference,
+  whose call clamps the live weights through ``serialize_model``, this leaves the parameters alone: a run with the metrics on
+  is bitwise the run with them off.
 
 Loaders are any iterables of ``(images float32 [b,3,H,W], labels int [b])`` batches; the data pipeline itself
 (torchvision / albumentations) is out of scope.
@@ -77,8 +82,11 @@ def build_model(config, device):
 
 
 def run_training(config, train_loader: Iterable, val_loader: Iterable, test_loader: Optional[Iterable] = None, model=None,
-                 checkpoint_dir=None, log: Callable[[str], None] = print, use_graph: bool = True) -> TrainResult:
+                 checkpoint_dir=None, log: Callable[[str], None] = print, use_graph: bool = True,
+                 compiled_eval: Optional[bool] = None) -> TrainResult:
     import evaluate
+    if compiled_eval is None:
+        compiled_eval = bool(getattr(config, "compiled_eval", False))
     if not torch.cuda.is_available():
         raise lib.NnueHipError("training runs on the GPU only (no CPU fallback in this build)")
     device = torch.device("cuda", torch.cuda.current_device())
@@ -99,6 +107,10 @@ def run_training(config, train_loader: Iterable, val_loader: Iterable, test_load
                           max_grad_norm=clip, use_graph=use_graph, input_slots=8 if in_place else 1, **opt)
     result = TrainResult()
     ckpt_dir = Path(checkpoint_dir) if checkpoint_dir is not None else None
+    engine = None
+    if compiled_eval:
+        from .engine import EngineModel
+        engine = EngineModel.from_model(model)
     for epoch in range(int(config.max_epochs)):
         model.train()
         if in_place:
@@ -115,10 +127,18 @@ def run_training(config, train_loader: Iterable, val_loader: Iterable, test_load
         row = {"epoch": epoch, "train/epoch_loss": train_loss, "train/epoch_f1": train_metrics["f1"],
                "train/epoch_accuracy": train_metrics["acc"], "val/loss": val_loss, "val/f1": val_metrics["f1"],
                "val/accuracy": val_metrics["acc"]}
+        line = (f"Epoch {epoch + 1}/{config.max_epochs} - Train Loss: {train_loss:.4f}, Train F1: {train_metrics['f1']:.4f}, "
+                f"Train Acc: {train_metrics['acc']:.4f} | Val Loss: {val_loss:.4f}, Val F1: {val_metrics['f1']:.4f}, "
+                f"Val Acc: {val_metrics['acc']:.4f}")
+        if engine is not None:  # train.py:389-427
+            engine.requantize(model)
+            compiled = evaluate.evaluate_engine(engine, val_loader)
+            row.update({"compiled/f1": compiled["f1"], "compiled/accuracy": compiled["acc"],
+                        "compiled/ms_per_sample": compiled["ms_per_sample"], "compiled/latent_density": compiled["latent_density"]})
+            line += (f" | Compiled F1: {compiled['f1']:.4f}, Compiled Acc: {compiled['acc']:.4f}, "
+                     f"Speed: {compiled['ms_per_sample']:.2f}ms/sample, Density: {compiled['latent_density']:.4f}")
         result.history.append(row)
-        log(f"Epoch {epoch + 1}/{config.max_epochs} - Train Loss: {train_loss:.4f}, Train F1: {train_metrics['f1']:.4f}, "
-            f"Train Acc: {train_metrics['acc']:.4f} | Val Loss: {val_loss:.4f}, Val F1: {val_metrics['f1']:.4f}, "
-            f"Val Acc: {val_metrics['acc']:.4f}")
+        log(line)
         if val_metrics["f1"] > result.best_val_f1:
             result.best_val_f1, result.best_epoch = val_metrics["f1"], epoch
             if ckpt_dir is not None:
