@@ -40,7 +40,7 @@
 extern "C" {
 #endif
 
-#define NNUE_HIP_ABI_VERSION 38
+#define NNUE_HIP_ABI_VERSION 39
 
 #define NNUE_OK 0
 #define NNUE_E_ARG (-1)     /* null pointer, non-positive size, bad alignment */
@@ -248,6 +248,33 @@ int nnue_ftm_forward_l1_supported(int B, int F, int P, int L1, int L2); /* shape
 int nnue_ftm_forward_l1(const uint8_t* bits, const float* sink, const float* weight, const float* bias,
                         const float* w1, int B, int F, int P, int L1, int L2, float* out, float* part,
                         nnue_stream_t stream);
+
+/* The table of nnue_ftm_forward_l1 as pre-split bf16 planes, written once per step by rider workgroups of the conv launch and
+ * read by the 32-row bf16 fused forward in place of the table (every row tile of nnue_ftm_forward_l1's bf16 form splits its own
+ * slab of the table again).  Plane buffer: one 48 KB block per (64-column tile t, 128-row K tile kt), block t * ktiles + kt
+ * (ktiles = ceil(min(F-1, P) / 128)); inside a block, plane p (0 hi, 1 mid, 2 lo: weight = hi + mid + lo exactly, each a bf16)
+ * of table column c(n) = 32 t + (n & 31) + (n & 32 ? L1/2 : 0), n < 64, rows k = 128 kt + 8 ch .. + 7 as eight bf16 at byte
+ *     p * 16384 + n * 256 + ((ch ^ (n & 15)) << 4);          rows k >= min(F-1, P) are zeros.
+ * _supported: nnue_ftm_forward_l1_supported shapes whose 32-row tiles fill the chip (>= 256 workgroups) where 64-row ones do not,
+ * with a table of at most 64 MB.  _bytes: the size of the plane buffer (0 for sizes no such buffer exists for). */
+int nnue_ftm_forward_l1_planes_supported(int B, int F, int P, int L1, int L2);
+int64_t nnue_ftm_forward_planes_bytes(int B, int F, int P, int L1);
+
+/* nnue_ftm_conv_binarize (self.conv + StraightThroughBinary.forward, nnue.py:640, :646-647, :19-25) whose launch also writes the
+ * planes of `table` (input.weight [F][L1], the operand of nnue.py:702-708) into `planes`: conv_out, bits, n and sink are bitwise
+ * nnue_ftm_conv_binarize's.  Shapes: nnue_ftm_forward_l1_planes_supported with P = fps * Gh * Gw.  There is no form that also
+ * leaves the im2col patches (nnue_ftm_conv_binarize_patches): a caller that wants those keeps the two plain calls. */
+int nnue_ftm_conv_binarize_planes(const float* images, const float* weight, const float* thr, int B, int H, int W,
+                                  int fps, int stride, int F, const float* table, int L1, int L2, void* planes,
+                                  int64_t planes_bytes, float* conv_out, uint8_t* bits, int32_t* n, float* sink,
+                                  nnue_stream_t stream);
+
+/* nnue_ftm_forward_l1 (nnue.py:686-710 + :660-666, :728-730) reading the planes nnue_ftm_conv_binarize_planes wrote from the
+ * same `weight`; weight itself is read for the clamp-sink row F-1 only.  out and part are bitwise what nnue_ftm_forward_l1
+ * gives with its 32-row bf16 tiles (NNUE_FTM_BF_BM=32). */
+int nnue_ftm_forward_l1_planes(const uint8_t* bits, const float* sink, const void* planes, int64_t planes_bytes,
+                               const float* weight, const float* bias, const float* w1, int B, int F, int P, int L1,
+                               int L2, float* out, float* part, nnue_stream_t stream);
 
 /* Its weight/bias gradient (autograd of nnue.py:702-708); fixed summation order, no atomics.  Rows the map
  * cannot reach are written as zero.  Either output may be NULL. */

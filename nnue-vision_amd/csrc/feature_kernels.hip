@@ -72,6 +72,32 @@ __global__ __launch_bounds__(256) void conv_binarize_kernel(const float* __restr
                                           w_lds, [] {}, patches, (size_t)gridDim.x * Gh * Gw);
 }
 
+// The same launch with rider workgroups that leave the FeatureTransformer table as the pre-split bf16 planes of the 32-row
+// fused forward (forward_planes.h): the conv workgroups are latency-bound and run every step right in front of that forward,
+// so the split -- which every one of the forward's row tiles would otherwise repeat on its own slab -- is done once per step
+// and can never be stale.  A kernel of its own beside conv_binarize_kernel (one body, conv_binarize_body), so that kernel's
+// instantiations keep their arguments and instruction streams.  Flat grid: the B * slices conv workgroups, then `riders` rider
+// workgroups (riders dispatched first were measured too and are the slower order: the conv workgroups are the launch's long
+// pole, §4a''' of DESIGN.md); a rider uses no LDS and does no conv work.  No im2col (`patches`) form: the shapes that take the
+// planes have strides whose patches do not pay, and the trainer keeps the two plain calls where it wants patches.
+#include "forward_planes.h"
+
+template <bool kFullUnroll>
+__global__ __launch_bounds__(256) void conv_binarize_planes_kernel(const float* __restrict__ img, const float* __restrict__ w,
+                                                                   const float* __restrict__ thr, float* __restrict__ out,
+                                                                   uint8_t* __restrict__ bits, int* __restrict__ n,
+                                                                   float* __restrict__ sink, int B, int H, int W, int fps, int stride,
+                                                                   int Gh, int Gw, int F, int slices, FwdPlaneArgs pa) {
+  extern __shared__ __attribute__((aligned(16))) float w_lds[];
+  const int id = (int)blockIdx.x;
+  if (id >= B * slices) {
+    forward_planes_write(pa, id - B * slices);
+    return;
+  }
+  ConvParamsPlain prm{w, thr};
+  conv_binarize_body<kFullUnroll, false>(img, prm, out, bits, n, sink, H, W, fps, stride, Gh, Gw, F, slices, id % B, id / B, w_lds, [] {});
+}
+
 // ------------------------------------------------------------------ binarise + compact
 // One workgroup per sample walks the flat ids p = c*G + hw in ascending order, 256 at a time:
 // bit = conv_out > thr[c]; wave ballots + a 4-entry LDS scan give each active id its slot, so the
@@ -487,8 +513,16 @@ extern "C" int nnue_conv3x3_forward(const float* images, const float* weight, fl
 }
 
 namespace {
+struct PlaneRide {  // nnue_ftm_conv_binarize_planes: the table and its plane buffer (table == NULL: no riders)
+  const float* table;
+  int L1, L2;
+  void* planes;
+  int64_t planes_bytes;
+};
+
 int conv_binarize_impl(const char* who, const float* images, const float* weight, const float* thr, int B, int H, int W, int fps, int stride, int F,
-                       float* conv_out, float* patches, uint8_t* bits, int32_t* n, float* sink, nnue_stream_t stream) {
+                       float* conv_out, float* patches, uint8_t* bits, int32_t* n, float* sink, nnue_stream_t stream,
+                       const PlaneRide& ride = PlaneRide{}) {
   NNUE_REQUIRE(images && weight && thr && conv_out && bits && n && sink, NNUE_E_ARG, "%s: null pointer", who);
   NNUE_REQUIRE(B > 0 && H > 0 && W > 0 && fps > 0 && stride > 0 && F > 0, NNUE_E_ARG, "%s: B=%d H=%d W=%d fps=%d stride=%d F=%d must be positive", who,
                B, H, W, fps, stride, F);
@@ -497,6 +531,16 @@ int conv_binarize_impl(const char* who, const float* images, const float* weight
   const long long G = (long long)Gh * Gw;
   NNUE_REQUIRE(G * fps < (1ll << 30) && (long long)B * G * fps < (1ll << 40), NNUE_E_SHAPE, "%s: map too large", who);
   NNUE_REQUIRE(!patches || 27ll * B * G * 4 < (1ll << 31), NNUE_E_SHAPE, "%s: the im2col buffer must stay below 2 GiB", who);
+  const int P = (int)(G * fps);
+  if (ride.table) {  // every check before the first launch (the counters' zero fill below)
+    NNUE_REQUIRE(ride.planes, NNUE_E_ARG, "%s: null pointer", who);
+    NNUE_REQUIRE(nnue_ftm_forward_l1_planes_supported(B, F, P, ride.L1, ride.L2), NNUE_E_SHAPE,
+                 "%s: B=%d F=%d P=%d L1=%d L2=%d is not a planes-fed forward shape (nnue_ftm_forward_l1_planes_supported)", who, B, F, P, ride.L1,
+                 ride.L2);
+    NNUE_REQUIRE(nnue_aligned16(ride.table) && nnue_aligned16(ride.planes), NNUE_E_ARG, "%s: pointers must be 16-byte aligned", who);
+    NNUE_REQUIRE(ride.planes_bytes >= nnue_ftm_forward_planes_bytes(B, F, P, ride.L1), NNUE_E_SCRATCH, "%s: plane buffer of %lld bytes, needs %lld", who,
+                 (long long)ride.planes_bytes, (long long)nnue_ftm_forward_planes_bytes(B, F, P, ride.L1));
+  }
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int threads = G <= 64 ? 64 : (G <= 128 ? 128 : 256);
   // one workgroup per sample when the batch alone fills the chip; otherwise split samples (at least one position per
@@ -506,6 +550,19 @@ int conv_binarize_impl(const char* who, const float* images, const float* weight
   slices = slices < 1 ? 1 : (slices > 16 ? 16 : slices);
   if (slices > 1) nnue_zero_counters(n, sink, B, s);  // a kernel, not a memset node (common.h)
   const size_t lds = (size_t)(((fps + 7) & ~7) * 28) * sizeof(float);
+  if (ride.table) {
+    const int direct = (F - 1 < P) ? F - 1 : P, ktiles = (direct + kBfK - 1) / kBfK, parts = 256 / threads;
+    const FwdPlaneArgs pa{ride.table, static_cast<unsigned char*>(ride.planes), (unsigned)((size_t)direct * ride.L1 * 4), ride.L1, ktiles, parts};
+    const int riders = (ride.L1 / 64) * ktiles * parts;
+    const dim3 grid((unsigned)(B * slices + riders));
+    if (fps <= 16)
+      hipLaunchKernelGGL((conv_binarize_planes_kernel<true>), grid, dim3(threads), lds, s, images, weight, thr, conv_out, bits, n, sink, B, H, W, fps,
+                         stride, Gh, Gw, F, slices, pa);
+    else
+      hipLaunchKernelGGL((conv_binarize_planes_kernel<false>), grid, dim3(threads), lds, s, images, weight, thr, conv_out, bits, n, sink, B, H, W, fps,
+                         stride, Gh, Gw, F, slices, pa);
+    return nnue_launch_status(who);
+  }
 #define NNUE_CONV_LAUNCH(FULL, PATCH)                                                                                                           \
   hipLaunchKernelGGL((conv_binarize_kernel<FULL, PATCH>), dim3(B, slices), dim3(threads), lds, s, images, weight, thr, conv_out, bits, n, sink, H, \
                      W, fps, stride, Gh, Gw, F, slices, patches)
@@ -532,6 +589,14 @@ extern "C" int nnue_ftm_conv_binarize_patches(const float* images, const float* 
                                               nnue_stream_t stream) {
   NNUE_REQUIRE(patches, NNUE_E_ARG, "nnue_ftm_conv_binarize_patches: null pointer");
   return conv_binarize_impl("nnue_ftm_conv_binarize_patches", images, weight, thr, B, H, W, fps, stride, F, conv_out, patches, bits, n, sink, stream);
+}
+
+extern "C" int nnue_ftm_conv_binarize_planes(const float* images, const float* weight, const float* thr, int B, int H, int W, int fps,
+                                             int stride, int F, const float* table, int L1, int L2, void* planes, int64_t planes_bytes,
+                                             float* conv_out, uint8_t* bits, int32_t* n, float* sink, nnue_stream_t stream) {
+  NNUE_REQUIRE(table && planes, NNUE_E_ARG, "nnue_ftm_conv_binarize_planes: null pointer");
+  return conv_binarize_impl("nnue_ftm_conv_binarize_planes", images, weight, thr, B, H, W, fps, stride, F, conv_out, nullptr, bits, n, sink, stream,
+                            PlaneRide{table, L1, L2, planes, planes_bytes});
 }
 
 extern "C" int nnue_binarize_features(const float* conv_out, const float* thr, int B, int fps, int Gh, int Gw, int F,

@@ -46,6 +46,7 @@ struct Mat {
   int ld, clamp, inner_k;
 };
 using u32x4 = __attribute__((__vector_size__(4 * sizeof(unsigned)))) unsigned;
+#include "forward_planes.h"  // kBfK, bf_img, bf16_split.h (split3 / split_block / split8, stage_map_k / stage_map_m), the plane buffer
 
 // The raw 16 bytes (float operand) or 4 bytes (byte operand, in .x) of (outer, inner .. inner+3).  Nothing is done to
 // the value here: widening / splitting happens when the registers are stored to LDS, one K tile later, so the load
@@ -405,7 +406,7 @@ struct FwdL1Epi {
   float* __restrict__ part;  // [L1/64][B][L2]
   int B, L1, L2, half;
   // table / ft column of tile-local column index n_abs = 64 * tile + n_local
-  __device__ __forceinline__ int col(int n_abs) const { return ((n_abs >> 6) << 5) + (n_abs & 31) + ((n_abs & 32) ? half : 0); }
+  __device__ __forceinline__ int col(int n_abs) const { return NNUE_FWD_L1_COL(n_abs, half); }
 };
 
 // LDS floats one tile needs (both staged operands)
@@ -931,24 +932,25 @@ __device__ __forceinline__ void gemm_tile(float* __restrict__ smem, const Mat& m
 // 8 k x 4 n block (eight 16-byte loads), splits it in registers and writes, per n, one 16-byte chunk of 8 k per plane.
 // The split is 4 VALU per value + 1.5 for packing; it is amortised over the BM rows of the tile, so tall tiles matter
 // more here than for the f32 kernel.
-constexpr int kBfK = 128, kBf64K = 64;  // K tile depths: gemm_tile_bf / gemm_tile_bf64
+constexpr int kBf64K = 64;  // K tile depths: gemm_tile_bf (kBfK) / gemm_tile_bf64
 template <int BM, int BN, int KT>
 constexpr int gemm_bf_lds_bytes() { return (BM + 3 * BN) * KT * 2; }
 
-// byte offset of 16-byte chunk `chunk` of image row `row`
-__device__ __forceinline__ int bf_img(int row, int chunk) { return row * (kBfK * 2) + ((chunk ^ (row & 15)) << 4); }
+// byte offset of 16-byte chunk `chunk` of image row `row` (bf_img: forward_planes.h)
 __device__ __forceinline__ int bf64_img(int row, int chunk) { return row * (kBf64K * 2) + ((chunk ^ ((row >> 1) & 7)) << 4); }
 template <int KT>
 struct BfImg {  // the image of a K tile of depth KT
   __device__ __forceinline__ int operator()(int row, int chunk) const { return KT == kBfK ? bf_img(row, chunk) : bf64_img(row, chunk); }
 };
 
-#include "bf16_split.h"  // split3 / split_block / split8, stage_map_k / stage_map_m
-
-template <int BM, int BN, bool AKC, class Epi>
+// PL (the fused-L1 forward at 32 rows): mb is not the table but its pre-split planes (forward_planes.h), one 48 KB block per
+// (column tile, K tile) that already is the three B images -- fetch / stage of B become 12 plain 16-byte loads and 12 linear,
+// conflict-free ds_write_b128 with no VALU; A, contract and the epilogue are the same code, so the sums are bitwise the same.
+template <int BM, int BN, bool AKC, class Epi, bool PL = false>
 __device__ __forceinline__ void gemm_tile_bf(unsigned char* __restrict__ smem, const Mat& ma, const Mat& mb, const Epi& epi, int M, int N,
                                              int k_lo, int k_hi, int tiles_n, int tile, int ks) {
   static_assert(BN == 64, "the f32 operand's staging assigns one 8 k x 4 n block per thread: 128 x 64 per K tile");
+  static_assert(!PL || (BM == 32 && AKC && Epi::kFusedL1), "the planes are laid out for the 32-row fused forward");
   static_assert(BM == 32 || BM == 64 || BM == 128, "tile heights");
   constexpr int TM = BM / 32, TN = BN / 32;
   unsigned char* __restrict__ As = smem;
@@ -977,7 +979,7 @@ __device__ __forceinline__ void gemm_tile_bf(unsigned char* __restrict__ smem, c
   const int b_off = b_col(n_base + bn4) * 4;  // byte offset inside a row
   // A, forward (bytes contiguous along k): 16-byte groups, (row, 16 k); BM * 8 groups
   // A, weight gradient (bytes contiguous along m): thread = (k block of 8, m block of 4); BM / 4 x 16 blocks
-  const bool stream_b = mb.bytes > (64u << 20);  // uniform
+  const bool stream_b = mb.bytes > kStreamTableBytes;  // uniform
   // (same 4 x 4 arrangement inside a 16-lane group as for the f32 operand: block index -> (m block, k block))
   auto a_block = [&](int g) {
     constexpr int MB = BM / 4;  // m blocks per k block
@@ -995,9 +997,10 @@ __device__ __forceinline__ void gemm_tile_bf(unsigned char* __restrict__ smem, c
   struct Regs {
     u32x4 ra[AKC ? AGK : 1];
     unsigned rat[AKC ? 1 : AGR][8];
-    u32x4 rb[8];
+    u32x4 rb[PL ? 12 : 8];
   };
   Regs set0;
+  [[maybe_unused]] const int pl_ktiles = (k_hi - k_lo + kBfK - 1) / kBfK;
   auto fetch = [&](int k0, Regs& R) {
     auto& ra = R.ra; auto& rat = R.rat; auto& rb = R.rb;
     if constexpr (AKC) {
@@ -1016,6 +1019,12 @@ __device__ __forceinline__ void gemm_tile_bf(unsigned char* __restrict__ smem, c
         for (int j = 0; j < 8; ++j)
           rat[i][j] = __builtin_amdgcn_raw_buffer_load_b32(rsa, on ? (k0 + k8 + j) * ma.ld + m_base + m4 : 0x7ffffff0, 0, 0);
       }
+    }
+    if constexpr (PL) {  // this (column tile, K tile)'s block: the block is a scalar offset, the thread's 16 bytes a lane offset
+      const int blk = (tile_n * pl_ktiles + (k0 - k_lo) / kBfK) * kFwdPlaneBlock;
+#pragma unroll
+      for (int j = 0; j < 12; ++j) rb[j] = __builtin_amdgcn_raw_buffer_load_b128(rsb, (tid + 256 * j) * 16, blk, 0);
+      return;
     }
     // a table larger than the caches is streamed once per launch: non-temporal, so that it does not displace the map,
     // d_out and the split-K slabs in L2
@@ -1044,13 +1053,18 @@ __device__ __forceinline__ void gemm_tile_bf(unsigned char* __restrict__ smem, c
         }
       }
     }
-    // exact three-way split of the 8 k x 4 n block, packed along k
-    u32x4 pl[3][4];  // [plane][n]: 8 bf16
-    split_block<4>(rb, pl);
+    if constexpr (PL) {
 #pragma unroll
-    for (int pnum = 0; pnum < 3; ++pnum)
+      for (int j = 0; j < 12; ++j) *reinterpret_cast<u32x4*>(Bs + (tid + 256 * j) * 16) = rb[j];
+    } else {
+      // exact three-way split of the 8 k x 4 n block, packed along k
+      u32x4 pl[3][4];  // [plane][n]: 8 bf16
+      split_block<4>(rb, pl);
 #pragma unroll
-      for (int e = 0; e < 4; ++e) *reinterpret_cast<u32x4*>(Bs + pnum * (BN * kBfK * 2) + bf_img(bn4 + e, bk8 >> 3)) = pl[pnum][e];
+      for (int pnum = 0; pnum < 3; ++pnum)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) *reinterpret_cast<u32x4*>(Bs + pnum * (BN * kBfK * 2) + bf_img(bn4 + e, bk8 >> 3)) = pl[pnum][e];
+    }
   };
   f32x4 acc[TM][TN];
 #pragma unroll
@@ -1082,13 +1096,51 @@ __device__ __forceinline__ void gemm_tile_bf(unsigned char* __restrict__ smem, c
   };
   // (two register sets with the loads of tile t+2 in flight were measured and lose: 83 -> 108 us for the 224x224 forward,
   // 109 -> 193 us for its weight gradient, whose K = batch is a single tile; nothing at the CIFAR shapes)
-  fetch(k_lo, set0);
-  for (int k0 = k_lo; k0 < k_hi; k0 += kBfK) {
-    stage(set0);
-    __syncthreads();
-    if (k0 + kBfK < k_hi) fetch(k0 + kBfK, set0);
-    contract();
-    __syncthreads();
+  if constexpr (PL) {
+    // Without the split a K tile is 24 MFMAs and 14 LDS stores: what is left per tile is the latency of its loads, so two
+    // tiles are kept in flight (two register sets of 13 loads; one workgroup per CU has the registers).  The tiles are staged
+    // and contracted in the same order, so the sums keep their bits.  Every fetch of the steady loop is unconditional and the
+    // last one to three tiles are straight-line code per case: a fetch under a condition makes the wait in front of the next
+    // stage cover both cases, i.e. every load in flight (vmcnt(0)), and the second set buys nothing.
+    Regs set1;
+    auto tile = [&](Regs& R, int next) {  // next < 0: no further tile for this register set
+      stage(R);
+      __syncthreads();
+      if (next >= 0) fetch(next, R);
+      contract();
+      __syncthreads();
+    };
+    const int k_last = k_lo + (pl_ktiles - 1) * kBfK;
+    fetch(k_lo, set0);
+    // (the scheduler must not interleave the two sets' loads: the loop's waits count on set0's being the older ones, as they are
+    // on its back edge -- interleaved, the first stage of every iteration drains set1 as well)
+    __builtin_amdgcn_sched_barrier(0);
+    fetch(k_lo + kBfK < k_hi ? k_lo + kBfK : k_last, set1);  // (a single K tile: read again, never staged)
+    __builtin_amdgcn_sched_barrier(0);
+    int k0 = k_lo;
+    for (; k0 + 3 * kBfK < k_hi; k0 += 2 * kBfK) {
+      tile(set0, k0 + 2 * kBfK);
+      tile(set1, k0 + 3 * kBfK);
+    }
+    if (k0 + 2 * kBfK < k_hi) {
+      tile(set0, k0 + 2 * kBfK);
+      tile(set1, -1);
+      tile(set0, -1);
+    } else if (k0 + kBfK < k_hi) {
+      tile(set0, -1);
+      tile(set1, -1);
+    } else {
+      tile(set0, -1);
+    }
+  } else {
+    fetch(k_lo, set0);
+    for (int k0 = k_lo; k0 < k_hi; k0 += kBfK) {
+      stage(set0);
+      __syncthreads();
+      if (k0 + kBfK < k_hi) fetch(k0 + kBfK, set0);
+      contract();
+      __syncthreads();
+    }
   }
   if constexpr (Epi::kFusedL1) {
     fused_l1_epilogue<BM>(epi, l1pre, reinterpret_cast<float*>(smem), acc, m_base, tile_n, m0, n0, r, q, wave, tid);
@@ -1127,7 +1179,7 @@ __device__ __forceinline__ void gemm_tile_bf64(unsigned char* __restrict__ smem,
   // f32 operand: thread = (k block of 4: 16 of them, n block of 4: 16 of them); lanes of a 16-lane group take 4 n x 4 k blocks
   const int bn4 = (((lane & 3) | ((lane >> 4) << 2))) * 4, bk4 = (((lane >> 2) & 3) | (wave << 2)) * 4;
   const int b_off = (n_base + bn4) * 4;
-  const bool stream_b = mb.bytes > (64u << 20);  // uniform
+  const bool stream_b = mb.bytes > kStreamTableBytes;  // uniform
   // A, forward (bytes contiguous along k): 16-byte groups (row, 16 k): 4 per row, two per thread
   // A, weight gradient (bytes contiguous along m): one 8 k x 4 m block per thread (8 x 32 blocks)
   auto a_block = [&](int g) {  // 16 consecutive blocks = 4 m blocks x 4 k blocks
@@ -1282,7 +1334,7 @@ __device__ __forceinline__ void gemm_tile_bf6(unsigned char* __restrict__ smem, 
   const int m0 = (wave >> 1) * (BM / 2), n0 = (wave & 1) * (BN / 2);
   constexpr int GA = BM * RUNS / 256, GB = BN * RUNS / 256;  // 8-k runs per thread
   static_assert(GA >= 1 && GB >= 1, "every thread stages at least one run of each operand");
-  const bool stream_b = mb.bytes > (64u << 20);        // uniform: a table larger than the caches is read non-temporally
+  const bool stream_b = mb.bytes > kStreamTableBytes;        // uniform: a table larger than the caches is read non-temporally
   u32x4 ra[GA][2], rb[GB][2];
   auto fetch = [&](int k0) {
     if constexpr (ABL == 5) {
@@ -1418,6 +1470,13 @@ __global__ __launch_bounds__(256) void ftm_forward_l1_bf_kernel(Mat ma, Mat mb, 
   constexpr int kGemm = gemm_bf_lds_bytes<BM, 64, kBfK>(), kEpi = 2 * BM * kL1Ld * 4;
   __shared__ __attribute__((aligned(16))) unsigned char smem[kGemm > kEpi ? kGemm : kEpi];
   gemm_tile_bf<BM, 64, true, FwdL1Epi>(smem, ma, mb, epi, M, N, 0, K, tiles_n, blockIdx.x, 0);
+}
+
+// The 32-row bf16 fused forward fed the table's planes (mp: the plane buffer nnue_ftm_conv_binarize_planes wrote this step)
+__global__ __launch_bounds__(256) void ftm_forward_l1_planes_kernel(Mat ma, Mat mp, FwdL1Epi epi, int M, int N, int K, int tiles_n) {
+  constexpr int kGemm = gemm_bf_lds_bytes<32, 64, kBfK>(), kEpi = 2 * 32 * kL1Ld * 4;
+  __shared__ __attribute__((aligned(16))) unsigned char smem[kGemm > kEpi ? kGemm : kEpi];
+  gemm_tile_bf<32, 64, true, FwdL1Epi, true>(smem, ma, mp, epi, M, N, 0, K, tiles_n, blockIdx.x, 0);
 }
 
 // ga.n != NULL: the launch has one workgroup more than tiles (grid.x - 1 tiles); it groups the batch by layer-stack bucket
@@ -2386,6 +2445,46 @@ extern "C" int nnue_ftm_forward_l1(const uint8_t* bits, const float* sink, const
   else if (s.cfg == 6) hipLaunchKernelGGL((ftm_forward_l1_bf_kernel<32>), grid, dim3(256), 0, st, ma, mb, epi, B, L1, direct, s.tiles_n);
   else hipLaunchKernelGGL((ftm_forward_l1_bf_kernel<64>), grid, dim3(256), 0, st, ma, mb, epi, B, L1, direct, s.tiles_n);
   return nnue_launch_status("nnue_ftm_forward_l1");
+}
+
+// The fused forward fed the table as pre-split bf16 planes (forward_planes.h; written once per step by the riders of
+// nnue_ftm_conv_binarize_planes).  Taken where nnue_ftm_forward_l1 runs 32-row tiles on the f32 MFMA today: 32-row tiles
+// fill the chip (>= 256 workgroups; NNUE_FTM_FWD_PLANES_MIN_WG, read per call, lowers that floor so that tests reach the
+// kernel at small shapes) while 64-row ones -- whose own split is amortised over twice the rows -- do not, and the table
+// is launch-sized (a table beyond the caches is streamed once per launch; planes would be 1.5x its bytes, written and read).
+extern "C" int nnue_ftm_forward_l1_planes_supported(int B, int F, int P, int L1, int L2) {
+  if (!nnue_ftm_forward_l1_supported(B, F, P, L1, L2)) return 0;
+  const int direct = (F - 1 < P) ? F - 1 : P;
+  if ((long long)direct * L1 * 4 > (long long)kStreamTableBytes) return 0;  // a streamed table
+  const long long t32 = (long long)((B + 31) / 32) * (L1 / 64), t64 = (long long)((B + 63) / 64) * (L1 / 64);
+  return t32 >= env_int("NNUE_FTM_FWD_PLANES_MIN_WG", 256) && t64 < 256;
+}
+
+extern "C" int64_t nnue_ftm_forward_planes_bytes(int B, int F, int P, int L1) {
+  if (B <= 0 || F <= 1 || P <= 0 || L1 <= 0 || L1 % 64 != 0) return 0;
+  const int direct = (F - 1 < P) ? F - 1 : P;
+  return (int64_t)(L1 / 64) * ((direct + kBfK - 1) / kBfK) * kFwdPlaneBlock;
+}
+
+extern "C" int nnue_ftm_forward_l1_planes(const uint8_t* bits, const float* sink, const void* planes, int64_t planes_bytes, const float* weight,
+                                          const float* bias, const float* w1, int B, int F, int P, int L1, int L2, float* out, float* part,
+                                          nnue_stream_t stream) {
+  NNUE_REQUIRE(bits && sink && planes && weight && bias && w1 && out && part, NNUE_E_ARG, "nnue_ftm_forward_l1_planes: null pointer");
+  NNUE_REQUIRE(nnue_ftm_forward_l1_planes_supported(B, F, P, L1, L2), NNUE_E_SHAPE,
+               "nnue_ftm_forward_l1_planes: B=%d F=%d P=%d L1=%d L2=%d is not a planes-fed forward shape (nnue_ftm_forward_l1_planes_supported)", B, F,
+               P, L1, L2);
+  NNUE_REQUIRE(nnue_aligned16(bits) && nnue_aligned16(planes) && nnue_aligned16(weight) && nnue_aligned16(bias) && nnue_aligned16(out) &&
+                   nnue_aligned16(w1),
+               NNUE_E_ARG, "nnue_ftm_forward_l1_planes: pointers must be 16-byte aligned");
+  const int64_t need = nnue_ftm_forward_planes_bytes(B, F, P, L1);
+  NNUE_REQUIRE(planes_bytes >= need && need < (1ll << 31), NNUE_E_SCRATCH, "nnue_ftm_forward_l1_planes: plane buffer of %lld bytes, needs %lld",
+               (long long)planes_bytes, (long long)need);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int direct = (F - 1 < P) ? F - 1 : P, tiles_n = L1 / 64;
+  const Mat ma{bits, (unsigned)((size_t)B * P), P, kIntMax, kIntMax}, mp{planes, (unsigned)need, L1, kIntMax, kIntMax};
+  const FwdL1Epi epi{bias, weight + (size_t)(F - 1) * L1, sink, out, w1, part, B, L1, L2, L1 / 2};
+  hipLaunchKernelGGL(ftm_forward_l1_planes_kernel, dim3((unsigned)(((B + 31) / 32) * tiles_n)), dim3(256), 0, st, ma, mp, epi, B, L1, direct, tiles_n);
+  return nnue_launch_status("nnue_ftm_forward_l1_planes");
 }
 
 

@@ -16,7 +16,7 @@ import torch
 
 _HERE = Path(__file__).resolve().parent
 LIB_PATH = _HERE / "libnnue_hip.so"
-ABI_VERSION = 38
+ABI_VERSION = 39
 
 _c_int, _c_i64, _c_f, _c_p = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
 
@@ -79,6 +79,11 @@ SIGNATURES = {
                                            _c_p, _c_p, _c_p, _c_p, _c_p]),
     "nnue_ftm_forward_l1_supported": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int]),
     "nnue_ftm_forward_l1": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p]),
+    "nnue_ftm_forward_l1_planes_supported": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int]),
+    "nnue_ftm_forward_planes_bytes": (_c_i64, [_c_int, _c_int, _c_int, _c_int]),
+    "nnue_ftm_conv_binarize_planes": (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_p, _c_int, _c_int, _c_p, _c_i64,
+                                               _c_p, _c_p, _c_p, _c_p, _c_p]),
+    "nnue_ftm_forward_l1_planes": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p]),
     "nnue_ftm_backward_weight": (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p]),
     "nnue_ftm_backward_values": (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p]),
     "nnue_ftm_backward_values_scratch": (_c_i64, [_c_int, _c_int, _c_int, _c_int]),
@@ -241,15 +246,20 @@ class time_calls:
         return False
 
 
+# entry points timed under the name of the call they replace (a caller's timer keys name the plain forms)
+_TIMED_AS = {"nnue_ftm_conv_binarize_planes": "nnue_ftm_conv_binarize", "nnue_ftm_forward_l1_planes": "nnue_ftm_forward_l1"}
+
+
 def _call(name: str, *args) -> None:
     lib = load()
     fn = getattr(lib, name)
-    if _timing is not None and name in _timing:
+    key = _TIMED_AS.get(name, name)
+    if _timing is not None and key in _timing:
         t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         t0.record()
         rc = fn(*args)
         t1.record()
-        _timing[name].append((t0, t1))
+        _timing[key].append((t0, t1))
     else:
         rc = fn(*args)
     if rc != 0:
@@ -262,12 +272,13 @@ def run_plan(plan, stream_ptr: int, timers=None) -> None:
     """Replays recorded calls on `stream_ptr`.  timers: {entry-point name: list} -- a (start, end) pair of
     torch events is recorded around each matching call on the current stream and appended to the list."""
     for name, fn, args in plan:
-        if timers is not None and name in timers:
+        key = _TIMED_AS.get(name, name)
+        if timers is not None and key in timers:
             t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             t0.record()
             rc = fn(*args, stream_ptr)
             t1.record()
-            timers[name].append((t0, t1))
+            timers[key].append((t0, t1))
         else:
             rc = fn(*args, stream_ptr)
         if rc != 0:
@@ -777,6 +788,65 @@ def ftm_forward_l1(weight: torch.Tensor, bias: torch.Tensor, fm: FeatureMatrix, 
         out = torch.empty((fm.batch, l1), dtype=torch.float32, device=weight.device)
     _call("nnue_ftm_forward_l1", fm.bits.data_ptr(), fm.sink.data_ptr(), weight.data_ptr(), bias.data_ptr(), w1.data_ptr(),
           fm.batch, f, fm.positions, l1, l2, out.data_ptr(), part.data_ptr(), _stream(weight))
+    return out
+
+
+def ftm_forward_l1_planes_supported(batch: int, num_rows: int, positions: int, l1: int, l2: int) -> bool:
+    return bool(load().nnue_ftm_forward_l1_planes_supported(int(batch), int(num_rows), int(positions), int(l1), int(l2)))
+
+
+def ftm_forward_planes_bytes(batch: int, num_rows: int, positions: int, l1: int) -> int:
+    return int(load().nnue_ftm_forward_planes_bytes(int(batch), int(num_rows), int(positions), int(l1)))
+
+
+def ftm_conv_binarize_planes(images: torch.Tensor, weight: torch.Tensor, thr: torch.Tensor, stride: int, table: torch.Tensor, l2: int,
+                             planes: torch.Tensor, conv_out: Optional[torch.Tensor] = None, fm: Optional[FeatureMatrix] = None):
+    """ftm_conv_binarize whose launch also leaves `table` (input.weight) as the bf16 planes ftm_forward_l1_planes reads
+    (`planes`: a uint8 buffer of ftm_forward_planes_bytes); returns (conv_out, fm), bitwise ftm_conv_binarize's."""
+    images = _need(images, torch.float32, "images")
+    if images.dim() != 4 or images.shape[1] != 3:
+        raise ValueError(f"images: expected [B,3,H,W], got {tuple(images.shape)}")
+    b, _, h, w = images.shape
+    weight = _need(weight, torch.float32, "conv.weight")
+    fps = weight.shape[0]
+    if tuple(weight.shape) != (fps, 3, 3, 3):
+        raise ValueError("conv.weight: expected [fps,3,3,3]")
+    thr = _need(thr.reshape(-1), torch.float32, "threshold", (fps,))
+    table = _need(table, torch.float32, "input.weight")
+    f, l1 = table.shape
+    planes = _need(planes, torch.uint8, "planes")
+    gh, gw = conv_out_hw(h, w, stride)
+    if conv_out is None:
+        conv_out = torch.empty((b, fps, gh, gw), dtype=torch.float32, device=images.device)
+    elif tuple(conv_out.shape) != (b, fps, gh, gw):
+        raise ValueError("ftm_conv_binarize_planes: conv_out has the wrong shape")
+    if fm is None:
+        fm = FeatureMatrix.empty(b, fps * gh * gw, f, l1, images.device)
+    elif fm.batch != b or fm.positions != fps * gh * gw or fm.num_rows != f:
+        raise ValueError("ftm_conv_binarize_planes: buffers do not match the map")
+    _call("nnue_ftm_conv_binarize_planes", images.data_ptr(), weight.data_ptr(), thr.data_ptr(), b, h, w, fps, int(stride), f,
+          table.data_ptr(), l1, int(l2), planes.data_ptr(), planes.numel(), conv_out.data_ptr(), fm.bits.data_ptr(), fm.n.data_ptr(),
+          fm.sink.data_ptr(), _stream(images))
+    return conv_out, fm
+
+
+def ftm_forward_l1_planes(weight: torch.Tensor, bias: torch.Tensor, fm: FeatureMatrix, planes: torch.Tensor, w1: torch.Tensor,
+                          part: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ftm_forward_l1 reading the planes ftm_conv_binarize_planes wrote from `weight` (bitwise its 32-row bf16 form)."""
+    weight = _need(weight, torch.float32, "input.weight")
+    f, l1 = weight.shape
+    bias = _need(bias, torch.float32, "input.bias", (l1,))
+    l2 = w1.shape[0]
+    w1 = _need(w1, torch.float32, "classifier.0.weight", (l2, l1))
+    planes = _need(planes, torch.uint8, "planes")
+    if f != fm.num_rows:
+        raise ValueError("ftm_forward_l1_planes: the map was built for a different table")
+    if not part.is_cuda or part.numel() * part.element_size() < (l1 // 64) * fm.batch * l2 * 4:
+        raise ValueError("ftm_forward_l1_planes: part buffer too small for [L1/64][B][L2] floats")
+    if out is None:
+        out = torch.empty((fm.batch, l1), dtype=torch.float32, device=weight.device)
+    _call("nnue_ftm_forward_l1_planes", fm.bits.data_ptr(), fm.sink.data_ptr(), planes.data_ptr(), planes.numel(), weight.data_ptr(),
+          bias.data_ptr(), w1.data_ptr(), fm.batch, f, fm.positions, l1, l2, out.data_ptr(), part.data_ptr(), _stream(weight))
     return out
 
 

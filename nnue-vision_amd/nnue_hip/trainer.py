@@ -277,6 +277,12 @@ class NnueTrainer:
         # (bucket-homogeneous MFMA tiles) instead of the FeatureTransformer forward's epilogue / backward rider
         self.fuse_l1 = (self.K == 1 and self.use_mfma and os.environ.get("NNUE_FUSE_L1", "1") != "0"
                         and lib.ftm_forward_l1_supported(B, self.F, self.P, self.L1, self.L2))
+        # Where that forward runs 32-row tiles (the CIFAR batch-512 shape), the conv launch's rider workgroups leave the table as
+        # pre-split bf16 planes once per step and the forward reads those on the bf16 matrix unit (nnue_ftm_conv_binarize_planes
+        # -> nnue_ftm_forward_l1_planes) instead of the table on the f32 one.  NNUE_FTM_FWD_PLANES=0 keeps the two plain calls.
+        self.fwd_planes = (self.fuse_l1 and not self.use_patches and os.environ.get("NNUE_FTM_FWD_PLANES", "1") != "0"
+                           and lib.ftm_forward_l1_planes_supported(B, self.F, self.P, self.L1, self.L2))
+        self.planes = (torch.empty((lib.ftm_forward_planes_bytes(B, self.F, self.P, self.L1),), **u8) if self.fwd_planes else None)
         # Sharded update for bandwidth-sized flat buffers under collectives (SGD): reduce-scatter, per-shard clip + SGD with
         # the norm assembled from all-gathered block partials, all-gather of the parameters.  NNUE_DP_SHARDED_UPDATE=0|1|auto
         mode = os.environ.get("NNUE_DP_SHARDED_UPDATE", "auto")
@@ -453,6 +459,10 @@ class NnueTrainer:
     def _segment(self, name: str) -> None:
         p, g = self.p, self.g
         if name == "front":
+            if self.fwd_planes:  # conv + {0,1} map + counts, and the table's bf16 planes from the same launch's riders
+                lib.ftm_conv_binarize_planes(self.images, p["conv.weight"], p["visual_threshold"], self.stride, p["input.weight"], self.L2,
+                                             self.planes, conv_out=self.conv_out, fm=self.fm)
+                return
             if self.use_mfma:  # conv + {0,1} map + counts in one launch
                 lib.ftm_conv_binarize(self.images, p["conv.weight"], p["visual_threshold"], self.stride, self.F, self.L1,
                                       conv_out=self.conv_out, fm=self.fm, patches=self.patches)
@@ -472,8 +482,12 @@ class NnueTrainer:
             # (product form: the grouping rides in the FeatureTransformer forward launch as one extra workgroup)
             if self.use_mfma and self.fuse_l1:
                 # the forward's epilogue also forms the classifier's layer-1 slabs (start of its scratch)
-                lib.ftm_forward_l1(p["input.weight"], p["input.bias"], self.fm, p["classifier.classifier.0.weight"], self.cls_scratch,
-                                   out=self.ft)
+                if self.fwd_planes:
+                    lib.ftm_forward_l1_planes(p["input.weight"], p["input.bias"], self.fm, self.planes, p["classifier.classifier.0.weight"],
+                                              self.cls_scratch, out=self.ft)
+                else:
+                    lib.ftm_forward_l1(p["input.weight"], p["input.bias"], self.fm, p["classifier.classifier.0.weight"], self.cls_scratch,
+                                       out=self.ft)
                 # 27: both phases, d_w1 left to the merged backward; + 32: the small gradients too; + 64: the tail in the d_x launch
                 self._cls_step((123 if self.fuse_tail_dx else 59 if self.ride_small else 27) if self.ride_dw1 else 13)
                 return
