@@ -1213,18 +1213,43 @@ def ftm_backward_tail_rows(d_out: torch.Tensor, fm: "FeatureMatrix", d_weight: t
           d_bias.data_ptr(), _stream(d_out))
 
 
+def _ftm_weight_update(name: str, d_out, fm, weight, coef, lr_dev, scalars, momentum_rows=None, adam=None, nxt=None) -> None:
+    """The one body of ftm_backward_weight_update{,_forward}{,_adam}; `name`: the public function, "nnue_" + name its C entry
+    point.  scalars: the optimizer's C arguments between the state pointers and lr_dev; adam = (exp_avg_rows, exp_avg_sq_rows,
+    step_counter), else SGD on momentum_rows; nxt = (fm_next, bias, out_next): the pass also forms that map's forward."""
+    d_out = _need(d_out, torch.float32, "d_out")
+    b, l1 = d_out.shape
+    weight = _need(weight, torch.float32, "input.weight", (fm.num_rows, l1))
+    if nxt is not None:
+        fm_next, bias, out_next = nxt
+        bias = _need(bias, torch.float32, "input.bias", (l1,))
+        out_next = _need(out_next, torch.float32, "out_next", (fm_next.batch, l1))
+    if adam is not None:
+        _need(adam[0], torch.float32, "exp_avg rows")
+        _need(adam[1], torch.float32, "exp_avg_sq rows")
+    _need(coef, torch.float32, "clip coefficient")
+    if adam is not None:
+        _need(adam[2], torch.int32, "step counter", (1,))
+        state = (adam[0].data_ptr(), adam[1].data_ptr(), coef.data_ptr(), adam[2].data_ptr())
+    else:
+        state = (_ptr(momentum_rows), coef.data_ptr())
+    forward = ()
+    if nxt is not None:
+        if fm.batch != b or fm_next.positions != fm.positions or fm_next.num_rows != fm.num_rows:
+            raise ValueError(f"{name}: the maps do not match d_out / each other")
+        forward = (fm_next.bits.data_ptr(), fm_next.sink.data_ptr(), fm_next.batch, bias.data_ptr(), out_next.data_ptr(),
+                   fm_next.scratch.data_ptr(), fm_next.scratch.numel())
+    _call("nnue_" + name, fm.bits.data_ptr(), d_out.data_ptr(), b, fm.num_rows, fm.positions, l1, weight.data_ptr(), *state, *scalars,
+          _ptr(lr_dev), *forward, _stream(d_out))
+
+
 def ftm_backward_weight_update(d_out: torch.Tensor, fm: "FeatureMatrix", weight: torch.Tensor, momentum_rows: Optional[torch.Tensor],
                                coef: torch.Tensor, lr: float, momentum: float, weight_decay: float, grad_scale: float,
                                first_step: bool, lr_dev: Optional[torch.Tensor] = None) -> None:
     """weight rows [0, direct) <- SGD update with d_W = A^T d_out formed and consumed in the product's epilogue.
     lr_dev (device float32 scalar): the learning rate is read from it instead of `lr`."""
-    d_out = _need(d_out, torch.float32, "d_out")
-    b, l1 = d_out.shape
-    weight = _need(weight, torch.float32, "input.weight", (fm.num_rows, l1))
-    _need(coef, torch.float32, "clip coefficient")
-    _call("nnue_ftm_backward_weight_update", fm.bits.data_ptr(), d_out.data_ptr(), b, fm.num_rows, fm.positions, l1, weight.data_ptr(),
-          _ptr(momentum_rows), coef.data_ptr(), float(lr), float(momentum), float(weight_decay), float(grad_scale),
-          int(bool(first_step)), _ptr(lr_dev), _stream(d_out))
+    _ftm_weight_update("ftm_backward_weight_update", d_out, fm, weight, coef, lr_dev, momentum_rows=momentum_rows,
+                       scalars=(float(lr), float(momentum), float(weight_decay), float(grad_scale), int(bool(first_step))))
 
 
 def ftm_update_forward_supported(batch: int, num_rows: int, positions: int, l1: int, batch_next: Optional[int] = None) -> bool:
@@ -1239,18 +1264,8 @@ def ftm_backward_weight_update_forward(d_out: torch.Tensor, fm: "FeatureMatrix",
                                        bias: torch.Tensor, out_next: torch.Tensor, lr_dev: Optional[torch.Tensor] = None) -> None:
     """ftm_backward_weight_update(d_out, fm, ...) and ftm_forward(weight, bias, fm_next, out=out_next) in one pass over the
     table (bitwise the two calls).  `bias` and table row F-1 must already be updated (sgd_step)."""
-    d_out = _need(d_out, torch.float32, "d_out")
-    b, l1 = d_out.shape
-    weight = _need(weight, torch.float32, "input.weight", (fm.num_rows, l1))
-    bias = _need(bias, torch.float32, "input.bias", (l1,))
-    out_next = _need(out_next, torch.float32, "out_next", (fm_next.batch, l1))
-    _need(coef, torch.float32, "clip coefficient")
-    if fm.batch != b or fm_next.positions != fm.positions or fm_next.num_rows != fm.num_rows:
-        raise ValueError("ftm_backward_weight_update_forward: the maps do not match d_out / each other")
-    _call("nnue_ftm_backward_weight_update_forward", fm.bits.data_ptr(), d_out.data_ptr(), b, fm.num_rows, fm.positions, l1,
-          weight.data_ptr(), _ptr(momentum_rows), coef.data_ptr(), float(lr), float(momentum), float(weight_decay), float(grad_scale),
-          int(bool(first_step)), _ptr(lr_dev), fm_next.bits.data_ptr(), fm_next.sink.data_ptr(), fm_next.batch, bias.data_ptr(), out_next.data_ptr(),
-          fm_next.scratch.data_ptr(), fm_next.scratch.numel(), _stream(d_out))
+    _ftm_weight_update("ftm_backward_weight_update_forward", d_out, fm, weight, coef, lr_dev, momentum_rows=momentum_rows,
+                       nxt=(fm_next, bias, out_next), scalars=(float(lr), float(momentum), float(weight_decay), float(grad_scale), int(bool(first_step))))
 
 
 def ftm_backward_weight_update_adam(d_out: torch.Tensor, fm: "FeatureMatrix", weight: torch.Tensor, exp_avg_rows: torch.Tensor,
@@ -1260,16 +1275,8 @@ def ftm_backward_weight_update_adam(d_out: torch.Tensor, fm: "FeatureMatrix", we
     """weight rows [0, direct) and the matching moment rows <- Adam update with d_W = A^T d_out formed and consumed in the
     product's epilogue.  ``step_counter`` (device int32) is read, not advanced: adam_step(ext_applied_elsewhere=True) of the
     same step advances it and leaves ``coef``."""
-    d_out = _need(d_out, torch.float32, "d_out")
-    b, l1 = d_out.shape
-    weight = _need(weight, torch.float32, "input.weight", (fm.num_rows, l1))
-    _need(exp_avg_rows, torch.float32, "exp_avg rows")
-    _need(exp_avg_sq_rows, torch.float32, "exp_avg_sq rows")
-    _need(coef, torch.float32, "clip coefficient")
-    _need(step_counter, torch.int32, "step counter", (1,))
-    _call("nnue_ftm_backward_weight_update_adam", fm.bits.data_ptr(), d_out.data_ptr(), b, fm.num_rows, fm.positions, l1, weight.data_ptr(),
-          exp_avg_rows.data_ptr(), exp_avg_sq_rows.data_ptr(), coef.data_ptr(), step_counter.data_ptr(), float(lr), float(betas[0]),
-          float(betas[1]), float(eps), float(weight_decay), float(grad_scale), _ptr(lr_dev), _stream(d_out))
+    _ftm_weight_update("ftm_backward_weight_update_adam", d_out, fm, weight, coef, lr_dev, adam=(exp_avg_rows, exp_avg_sq_rows, step_counter),
+                       scalars=(float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay), float(grad_scale)))
 
 
 def ftm_backward_weight_update_forward_adam(d_out: torch.Tensor, fm: "FeatureMatrix", weight: torch.Tensor, exp_avg_rows: torch.Tensor,
@@ -1278,22 +1285,9 @@ def ftm_backward_weight_update_forward_adam(d_out: torch.Tensor, fm: "FeatureMat
                                             bias: torch.Tensor, out_next: torch.Tensor, lr_dev: Optional[torch.Tensor] = None) -> None:
     """ftm_backward_weight_update_adam(d_out, fm, ...) and ftm_forward(weight, bias, fm_next, out=out_next) in one pass over the
     table (bitwise the two calls).  `bias` and table row F-1 must already be updated (adam_step)."""
-    d_out = _need(d_out, torch.float32, "d_out")
-    b, l1 = d_out.shape
-    weight = _need(weight, torch.float32, "input.weight", (fm.num_rows, l1))
-    bias = _need(bias, torch.float32, "input.bias", (l1,))
-    out_next = _need(out_next, torch.float32, "out_next", (fm_next.batch, l1))
-    _need(exp_avg_rows, torch.float32, "exp_avg rows")
-    _need(exp_avg_sq_rows, torch.float32, "exp_avg_sq rows")
-    _need(coef, torch.float32, "clip coefficient")
-    _need(step_counter, torch.int32, "step counter", (1,))
-    if fm.batch != b or fm_next.positions != fm.positions or fm_next.num_rows != fm.num_rows:
-        raise ValueError("ftm_backward_weight_update_forward_adam: the maps do not match d_out / each other")
-    _call("nnue_ftm_backward_weight_update_forward_adam", fm.bits.data_ptr(), d_out.data_ptr(), b, fm.num_rows, fm.positions, l1,
-          weight.data_ptr(), exp_avg_rows.data_ptr(), exp_avg_sq_rows.data_ptr(), coef.data_ptr(), step_counter.data_ptr(), float(lr),
-          float(betas[0]), float(betas[1]), float(eps), float(weight_decay), float(grad_scale), _ptr(lr_dev), fm_next.bits.data_ptr(),
-          fm_next.sink.data_ptr(), fm_next.batch, bias.data_ptr(), out_next.data_ptr(), fm_next.scratch.data_ptr(), fm_next.scratch.numel(),
-          _stream(d_out))
+    _ftm_weight_update("ftm_backward_weight_update_forward_adam", d_out, fm, weight, coef, lr_dev,
+                       adam=(exp_avg_rows, exp_avg_sq_rows, step_counter), nxt=(fm_next, bias, out_next),
+                       scalars=(float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay), float(grad_scale)))
 
 
 class FactorExchange:

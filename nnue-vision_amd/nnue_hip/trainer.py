@@ -232,19 +232,21 @@ class NnueTrainer:
         # materialised d_W, bitwise identical replicas.  The other gradients travel in the same all-gather and are summed in
         # rank order (lib.FactorExchange).  NNUE_DP_FACTOR_EXCHANGE=auto|1|0; auto = tables of 32 MB or more.
         fx_mode = os.environ.get("NNUE_DP_FACTOR_EXCHANGE", "auto")
-        fx_rows = min(self.F - 1, self.P)
-        fx_off = self.layout.offsets[self.layout.names.index("input.weight")]
+        # the table rows the product d_W = A^T d_out covers, as a range of the flat buffers; every form that leaves those rows to
+        # the product's launch (their sums of squares, their update) needs the range non-empty and float4-aligned
+        tbl_lo = self.layout.offsets[self.layout.names.index("input.weight")]
+        tbl_hi = tbl_lo + min(self.F - 1, self.P) * self.L1
+        tbl_ok = tbl_hi > tbl_lo and tbl_lo % 4 == 0 and tbl_hi % 4 == 0
+        big_table = self.F * self.L1 * 4 >= (32 << 20)
         gb = B * self.dp.world
-        self.factor_exchange = (self.dp.collectives and self.use_mfma and optimizer == "sgd" and self.dp.buckets == 1 and fx_rows > 0
+        self.factor_exchange = (self.dp.collectives and self.use_mfma and optimizer == "sgd" and self.dp.buckets == 1 and tbl_ok
                                 and self.layout.names[:3] == ["visual_threshold", "conv.weight", "input.weight"]
                                 and gb * self.L1 <= (1 << 24) and ((gb + 15) // 16) * ((self.L1 + 15) // 16) <= 65536
-                                and fx_off % 4 == 0 and (fx_rows * self.L1) % 4 == 0 and fx_mode != "0"
-                                and (fx_mode == "1" or self.F * self.L1 * 4 >= (32 << 20)))
+                                and fx_mode != "0" and (fx_mode == "1" or big_table))
         self.fx = None
         if self.factor_exchange:
-            tail_lo = fx_off + fx_rows * self.L1
-            self.fx = lib.FactorExchange(self.dp.world, self.dp.rank, B, self.P, self.F, self.L1, head=fx_off, tail_lo=tail_lo,
-                                         tail=self.layout.count - tail_lo, device=self.dev)
+            self.fx = lib.FactorExchange(self.dp.world, self.dp.rank, B, self.P, self.F, self.L1, head=tbl_lo, tail_lo=tbl_hi,
+                                         tail=self.layout.count - tbl_hi, device=self.dev)
             self.fm.sink = self.fx.sink  # written by the binarise kernel straight into this rank's chunk
         self.bits = lib.FeatureBits.empty(B, self.P, self.F, self.L1, self.dev) if self.use_bits else None
         self.act = lib.ActList.empty(B, self.P, self.F, self.dev) if self.ft_path == "list" else None
@@ -270,9 +272,6 @@ class NnueTrainer:
         self.defer_ste = (not self.dp.collectives and optimizer == "sgd" and os.environ.get("NNUE_DEFER_STE", "1") != "0"
                           and self.fps * 28 <= 4096 and self.layout.names[:2] == ["visual_threshold", "conv.weight"])
         self.ste_chunks = lib.ste_conv_backward_chunks(B, self.fps, self.gh, self.gw)
-        # single rank + SGD: the FT weight-gradient tiles leave their sums of squares, so the clip norm does not read
-        # those rows of the flat gradient buffer again (268 MB at the 224x224 configuration)
-        self.sq_partial, self.sq_range = None, None
         # K > 1: the first layer's weights differ per sample, so its product is the classifier's own grouped launch
         # (bucket-homogeneous MFMA tiles) instead of the FeatureTransformer forward's epilogue / backward rider
         self.fuse_l1 = (self.K == 1 and self.use_mfma and os.environ.get("NNUE_FUSE_L1", "1") != "0"
@@ -312,41 +311,32 @@ class NnueTrainer:
         # tile family reading d_z1 out of the classifier's scratch) where that launch is used
         self.ride_dw1 = (self.use_mfma and self.merge_backward and os.environ.get("NNUE_FTM_RIDE_DW1", "1") != "0"
                          and lib.ftm_backward_cw_supported(B, self.F, self.P, self.L1, self.L2))
-        n_sq = lib.ftm_backward_sq_count(B, self.F, self.P, self.L1) if (self.use_mfma and self.merge_backward) else 0
-        if (n_sq > 0 and not self.dp.collectives and optimizer == "sgd" and os.environ.get("NNUE_NORM_PARTIALS", "1") != "0"):
-            off = self.layout.offsets[self.layout.names.index("input.weight")]
-            rows = min(self.F - 1, self.P)
-            if off % 4 == 0 and (rows * self.L1) % 4 == 0:
-                self.sq_partial = torch.empty((n_sq,), **f32)
-                self.sq_range = (off, off + rows * self.L1)
         # Big tables on a single rank (SGD or Adam): the FeatureTransformer weight gradient is never materialised.  Its squared
         # norm comes from two B x B Gram matrices (nnue_ftm_gram_sqnorm), the optimizer's norm/apply pass skips those rows
         # and leaves the clip coefficient in a device scalar, and the product d_W = A^T d_out runs LAST, applying the update
         # to the table (Adam: and to its two moments) in its epilogue (nnue_ftm_backward_weight_update[_adam]): no 268 MB write
         # + read at the 224x224 shape.
-        self.fuse_table_update = False
-        rows = min(self.F - 1, self.P)
-        off = self.layout.offsets[self.layout.names.index("input.weight")]
-        big_table = self.F * self.L1 * 4 >= (32 << 20)
         want = os.environ.get("NNUE_FUSE_TABLE_UPDATE", "auto")
-        if (self.use_mfma and not self.dp.collectives and rows > 0 and B * self.L1 <= (1 << 24) and off % 4 == 0
-                and (rows * self.L1) % 4 == 0 and want != "0" and (big_table or want == "1")):
-            self.fuse_table_update = True
-            self.ride_dw1 = False  # the rider lives in the merged launch, which this path does not use
-            self.sq_partial = torch.empty((int(lib.load().nnue_ftm_gram_sq_count(B, self.L1)),), **f32)
-            self.sq_range = (off, off + rows * self.L1)
-            self.gram = torch.zeros((lib.ftm_gram_scratch(self.fm),), **f32)
-            self.clip_coef = torch.ones((), **f32)
+        self.fuse_table_update = (self.use_mfma and not self.dp.collectives and tbl_ok and B * self.L1 <= (1 << 24) and want != "0"
+                                  and (big_table or want == "1"))
         # With the fused table update ``model.input.weight.grad`` (a view of flat_grads) is never written: rows the product
         # covers stay at the zeros they were allocated with.  ``grads_materialised`` says so; callers that want the table's
         # gradient for logging or custom clipping set NNUE_FUSE_TABLE_UPDATE=0.
-        if self.factor_exchange:  # the same fused update, on the global factors (B * world rows)
-            self.ride_dw1 = False
-            self.sq_partial = torch.empty((int(lib.load().nnue_ftm_gram_sq_count(gb, self.L1)),), **f32)
-            self.sq_range = (fx_off, fx_off + fx_rows * self.L1)
-            self.gram = torch.zeros((lib.ftm_gram_scratch(self.fx.g_fm),), **f32)
-            self.clip_coef = torch.ones((), **f32)
         self.grads_materialised = not (self.fuse_table_update or self.factor_exchange)
+        # sq_partial: the sums of squares of the table's share (flat_grads[sq_range]) of the clip norm, left by its producer
+        self.sq_partial = self.sq_range = self.gram = self.clip_coef = None
+        n_sq = lib.ftm_backward_sq_count(B, self.F, self.P, self.L1) if (self.use_mfma and self.merge_backward) else 0
+        if not self.grads_materialised:  # the Gram form; under the factor exchange on the global factors (B * world rows)
+            self.ride_dw1 = False  # the rider lives in the merged launch, which this path does not use
+            self.sq_partial = torch.empty((int(lib.load().nnue_ftm_gram_sq_count(gb, self.L1)),), **f32)
+            self.sq_range = (tbl_lo, tbl_hi)
+            self.gram = torch.zeros((lib.ftm_gram_scratch(self.fx.g_fm if self.factor_exchange else self.fm),), **f32)
+            self.clip_coef = torch.ones((), **f32)
+        elif n_sq > 0 and not self.dp.collectives and optimizer == "sgd" and tbl_ok and os.environ.get("NNUE_NORM_PARTIALS", "1") != "0":
+            # single rank + SGD: the FT weight-gradient tiles leave their sums of squares, so the clip norm does not read
+            # those rows of the flat gradient buffer again (268 MB at the 224x224 configuration)
+            self.sq_partial = torch.empty((n_sq,), **f32)
+            self.sq_range = (tbl_lo, tbl_hi)
         # Single rank + SGD with the merged FeatureTransformer backward: its value-gradient tiles also reduce d_conv_out into the
         # STE partials (stage 1 of ste_conv_backward) in their epilogue, so the STE launch disappears and d_conv_out is not
         # stored; the second stage stays in the norm launch.  With the im2col patches the epilogue reads them instead of the images
@@ -556,36 +546,50 @@ class NnueTrainer:
         for name in self.SEGMENTS:
             self._segment(name)
 
+    def _small_update(self, first: bool, scale: float) -> None:
+        """The optimizer's launch on the flat buffers: clip norm + update of every tensor.  Where the table's gradient is never
+        materialised (fuse_table_update, factor_exchange) it takes the table's share of the norm from the Gram partials, leaves
+        the table's rows alone and the clip coefficient in ``clip_coef`` for _table_update."""
+        ext = (self.sq_partial, *self.sq_range) if self.sq_partial is not None else None
+        elsewhere = not self.grads_materialised
+        if self.optimizer == "adam":
+            lib.adam_step(self.flat_params, self.flat_grads, self.flat_exp_avg, self.flat_exp_avg_sq, self.adam_step_count,
+                          self.lr, self.betas, self.eps, self.weight_decay, self.max_grad_norm, scale, self.grad_norm,
+                          self.sgd_scratch, lr_dev=self.lr_dev, ext=ext, coef_out=self.clip_coef, ext_applied_elsewhere=elsewhere)
+            return
+        ste = ((self.ste_scratch, self.ste_chunks, self.fps, self.g["visual_threshold"], self.g["conv.weight"])
+               if self.defer_ste else None)
+        lib.sgd_step(self.flat_params, self.flat_grads, self.flat_momentum, self.lr, self.momentum, self.weight_decay,
+                     self.max_grad_norm, scale, first, self.grad_norm, self.sgd_scratch, ste=ste, ext=ext,
+                     coef_out=self.clip_coef, ext_applied_elsewhere=elsewhere, lr_dev=self.lr_dev)
+
+    def _table_update(self, first: bool, scale: float, d_ft: torch.Tensor, fm, nxt=None) -> None:
+        """The product d_W = A^T d_ft (A: map `fm`) with the table's update in its epilogue, after _small_update: SGD on the
+        momentum's rows or Adam on the two moments' rows.  nxt: the same pass over the table also forms the FeatureTransformer
+        forward of map `nxt` into ``self.ft`` (_next_map has written it; the small update the bias and table row F-1)."""
+        lo, hi = self.sq_range
+        forward = () if nxt is None else (nxt, self.p["input.bias"], self.ft)
+        if self.optimizer == "adam":
+            fn = lib.ftm_backward_weight_update_adam if nxt is None else lib.ftm_backward_weight_update_forward_adam
+            opt = (self.flat_exp_avg[lo:hi], self.flat_exp_avg_sq[lo:hi], self.clip_coef, self.adam_step_count, self.lr, self.betas,
+                   self.eps, self.weight_decay, scale)
+        else:
+            fn = lib.ftm_backward_weight_update if nxt is None else lib.ftm_backward_weight_update_forward
+            mom = self.flat_momentum[lo:hi] if self.flat_momentum is not None else None
+            opt = (mom, self.clip_coef, self.lr, self.momentum, self.weight_decay, scale, first)
+        fn(d_ft, fm, self.p["input.weight"], *opt, *forward, lr_dev=self.lr_dev)
+
+    def _next_map(self, slot: int, nxt) -> None:
+        """conv + {0,1} map of input slot `slot` into map `nxt`, between the two halves of an update that forms the next step's
+        forward: it needs the conv weights and thresholds the small update has just written."""
+        lib.ftm_conv_binarize(self.inputs[slot][0], self.p["conv.weight"], self.p["visual_threshold"], self.stride, self.F, self.L1,
+                              conv_out=self.conv_out, fm=nxt, patches=self.patches)
+
     def _update(self, first: bool, grad_scale: Optional[float] = None) -> None:
         scale = self.dp.grad_scale if grad_scale is None else grad_scale
-        if self.optimizer == "adam" and self.fuse_table_update:
-            # small tensors + norm (the table's share from the Gram partials) + step counter, then the product with the Adam
-            # epilogue on the table's rows of the three flat buffers
-            lib.adam_step(self.flat_params, self.flat_grads, self.flat_exp_avg, self.flat_exp_avg_sq, self.adam_step_count,
-                          self.lr, self.betas, self.eps, self.weight_decay, self.max_grad_norm, scale, self.grad_norm,
-                          self.sgd_scratch, lr_dev=self.lr_dev, ext=(self.sq_partial, *self.sq_range), coef_out=self.clip_coef,
-                          ext_applied_elsewhere=True)
-            lo, hi = self.sq_range
-            lib.ftm_backward_weight_update_adam(self.d_ft, self.fm, self.p["input.weight"], self.flat_exp_avg[lo:hi],
-                                                self.flat_exp_avg_sq[lo:hi], self.clip_coef, self.adam_step_count, self.lr, self.betas,
-                                                self.eps, self.weight_decay, scale, lr_dev=self.lr_dev)
-        elif self.optimizer == "adam":
-            lib.adam_step(self.flat_params, self.flat_grads, self.flat_exp_avg, self.flat_exp_avg_sq, self.adam_step_count,
-                          self.lr, self.betas, self.eps, self.weight_decay, self.max_grad_norm, scale, self.grad_norm,
-                          self.sgd_scratch, lr_dev=self.lr_dev)
-        else:
-            ste = ((self.ste_scratch, self.ste_chunks, self.fps, self.g["visual_threshold"], self.g["conv.weight"])
-                   if self.defer_ste else None)
-            lib.sgd_step(self.flat_params, self.flat_grads, self.flat_momentum, self.lr, self.momentum, self.weight_decay,
-                         self.max_grad_norm, scale, first, self.grad_norm, self.sgd_scratch, ste=ste,
-                         ext=(self.sq_partial, *self.sq_range) if self.sq_partial is not None else None,
-                         coef_out=self.clip_coef if self.fuse_table_update else None,
-                         ext_applied_elsewhere=self.fuse_table_update, lr_dev=self.lr_dev)
-            if self.fuse_table_update:
-                lo, hi = self.sq_range
-                mom = self.flat_momentum[lo:hi] if self.flat_momentum is not None else None
-                lib.ftm_backward_weight_update(self.d_ft, self.fm, self.p["input.weight"], mom, self.clip_coef, self.lr, self.momentum,
-                                               self.weight_decay, scale, first, lr_dev=self.lr_dev)
+        self._small_update(first, scale)
+        if self.fuse_table_update:  # the product runs LAST and applies the table's share
+            self._table_update(first, scale, self.d_ft, self.fm)
 
     def _exchange_and_update(self, first: bool, grad_scale: Optional[float] = None, alt: bool = False,
                              next_slot: Optional[int] = None) -> None:
@@ -598,20 +602,11 @@ class NnueTrainer:
             self.dp.all_gather_chunks(fx.chunks)  # the step's one collective
             fx.unpack(self.flat_grads)
             lib.ftm_gram_sqnorm(fx.g_fm, fx.g_dft, self.gram, self.sq_partial)
-            lib.sgd_step(self.flat_params, self.flat_grads, self.flat_momentum, self.lr, self.momentum, self.weight_decay,
-                         self.max_grad_norm, scale, first, self.grad_norm, self.sgd_scratch, ext=(self.sq_partial, *self.sq_range),
-                         coef_out=self.clip_coef, ext_applied_elsewhere=True, lr_dev=self.lr_dev)
-            lo, hi = self.sq_range
-            mom = self.flat_momentum[lo:hi] if self.flat_momentum is not None else None
-            if next_slot is not None:
-                nxt = self.fm if alt else self.fm_alt
-                lib.ftm_conv_binarize(self.inputs[next_slot][0], self.p["conv.weight"], self.p["visual_threshold"], self.stride, self.F, self.L1,
-                                      conv_out=self.conv_out, fm=nxt, patches=self.patches)
-                lib.ftm_backward_weight_update_forward(fx.g_dft, fx.g_fm, self.p["input.weight"], mom, self.clip_coef, self.lr, self.momentum,
-                                                       self.weight_decay, scale, first, nxt, self.p["input.bias"], self.ft, lr_dev=self.lr_dev)
-                return
-            lib.ftm_backward_weight_update(fx.g_dft, fx.g_fm, self.p["input.weight"], mom, self.clip_coef, self.lr, self.momentum,
-                                           self.weight_decay, scale, first, lr_dev=self.lr_dev)
+            self._small_update(first, scale)
+            nxt = None if next_slot is None else (self.fm if alt else self.fm_alt)
+            if nxt is not None:
+                self._next_map(next_slot, nxt)
+            self._table_update(first, scale, fx.g_dft, fx.g_fm, nxt)
             return
         if not self.sharded_update:
             self.dp.allreduce_sum(self.flat_grads, async_op=False)
@@ -865,7 +860,7 @@ class NnueTrainer:
     def _run_many(self, st: torch.cuda.Stream, slots, ring: torch.Tensor, upd, timers=None) -> None:
         """The launches of ``len(slots)`` consecutive steps on stream `st` (the current stream): what step_many captures, and
         -- with `timers` -- what it runs eagerly with HIP events around the named entry points."""
-        fuse = self.fuse_next_forward and len(slots) > 1 and (not self.dp.collectives or self.factor_exchange)
+        fuse = self._group_fuses(slots)
         for i, s in enumerate(slots):
             alt = fuse and i % 2 == 1
             self._run_local(s, "all", st, timers=timers, loss=ring[i], alt=alt, forward_done=fuse and i > 0)
@@ -875,28 +870,31 @@ class NnueTrainer:
             elif fuse and i + 1 < len(slots):
                 # small tensors (and the clip coefficient) first: the next map needs the updated conv weights and thresholds,
                 # the next forward's finish the updated bias and table row F-1
-                lib.run_plan([c for c in upd if c[0] in ("nnue_sgd_step", "nnue_adam_step_ext")], st.cuda_stream, timers)
                 cur, nxt = (self.fm_alt, self.fm) if alt else (self.fm, self.fm_alt)
-                lo, hi = self.sq_range
-                mom = self.flat_momentum[lo:hi] if self.flat_momentum is not None else None
                 with lib.time_calls(timers):
-                    lib.ftm_conv_binarize(self.inputs[slots[i + 1]][0], self.p["conv.weight"], self.p["visual_threshold"], self.stride,
-                                          self.F, self.L1, conv_out=self.conv_out, fm=nxt, patches=self.patches)
-                    if self.optimizer == "adam":
-                        lib.ftm_backward_weight_update_forward_adam(self.d_ft, cur, self.p["input.weight"], self.flat_exp_avg[lo:hi],
-                                                                    self.flat_exp_avg_sq[lo:hi], self.clip_coef, self.adam_step_count,
-                                                                    self.lr, self.betas, self.eps, self.weight_decay, self.dp.grad_scale,
-                                                                    nxt, self.p["input.bias"], self.ft, lr_dev=self.lr_dev)
-                    else:
-                        lib.ftm_backward_weight_update_forward(self.d_ft, cur, self.p["input.weight"], mom, self.clip_coef, self.lr,
-                                                               self.momentum, self.weight_decay, self.dp.grad_scale, False, nxt,
-                                                               self.p["input.bias"], self.ft, lr_dev=self.lr_dev)
+                    self._small_update(False, self.dp.grad_scale)
+                    self._next_map(slots[i + 1], nxt)
+                    self._table_update(False, self.dp.grad_scale, self.d_ft, cur, nxt)
             elif alt:
                 swap = self._alt_swap()
                 lib.run_plan([(nm, fn, tuple(swap.get(a, a) if isinstance(a, int) else a for a in args)) for nm, fn, args in upd],
                              st.cuda_stream, timers)
             else:
                 lib.run_plan(upd, st.cuda_stream, timers)
+
+    def _group_fuses(self, slots) -> bool:
+        """In a group on `slots` the table update of every step but the last also forms the next step's forward."""
+        return self.fuse_next_forward and len(slots) > 1 and (not self.dp.collectives or self.factor_exchange)
+
+    def _ends_on_alt(self, slots) -> bool:
+        """The last step of a group on `slots` leaves its map in the second one (the maps alternate within a fused group)."""
+        return self._group_fuses(slots) and len(slots) % 2 == 0
+
+    def _ring(self, n: int) -> torch.Tensor:
+        """The ring of per-step mean losses, grown to at least n entries."""
+        if self.loss_ring.numel() < n:
+            self.loss_ring = torch.zeros((n,), dtype=torch.float32, device=self.dev)
+        return self.loss_ring
 
     def step_many(self, slots, timers=None) -> torch.Tensor:
         """``len(slots)`` consecutive optimizer steps on what the named input slots already hold (fill
@@ -914,19 +912,16 @@ class NnueTrainer:
         if timers is not None and self.steps_done > 0 and self._plan_local is not None:
             # (with ranks: the collectives are issued eagerly, in the same order on every rank)
             _, _, upd = self._plans(slots[0])
-            if self.loss_ring.numel() < len(slots):
-                self.loss_ring = torch.zeros((len(slots),), dtype=torch.float32, device=self.dev)
-            self._run_many(torch.cuda.current_stream(self.dev), slots, self.loss_ring, upd, timers)
-            self._last_alt = self.fuse_next_forward and len(slots) % 2 == 0 and (not self.dp.collectives or self.factor_exchange)
+            ring = self._ring(len(slots))
+            self._run_many(torch.cuda.current_stream(self.dev), slots, ring, upd, timers)
+            self._last_alt = self._ends_on_alt(slots)
             self.steps_done += len(slots)
-            return self.loss_ring[:len(slots)]
+            return ring[:len(slots)]
         one_graph = (self.use_graph and self.steps_done > 0 and self._plan_local is not None
                      and (not self.dp.collectives or self.capture_collectives))
         if one_graph and (slots, "many") not in self._g_local:
             _, _, upd = self._plans(slots[0])
-            if self.loss_ring.numel() < len(slots):
-                self.loss_ring = torch.zeros((len(slots),), dtype=torch.float32, device=self.dev)
-            ring = self.loss_ring
+            ring = self._ring(len(slots))
             captured = True
             try:
                 self._g_local[(slots, "many")] = (self._capture(lambda st: self._run_many(st, slots, ring, upd)), ring)
@@ -942,14 +937,13 @@ class NnueTrainer:
                 self.capture_collectives = False
                 one_graph = False
         if not one_graph:
-            if self.loss_ring.numel() < len(slots):
-                self.loss_ring = torch.zeros((len(slots),), dtype=torch.float32, device=self.dev)
+            ring = self._ring(len(slots))
             for i, s in enumerate(slots):
-                self.loss_ring[i].copy_(self.step(slot=s), non_blocking=True)
-            return self.loss_ring[:len(slots)]
+                ring[i].copy_(self.step(slot=s), non_blocking=True)
+            return ring[:len(slots)]
         graph, ring = self._g_local[(slots, "many")]
         graph.replay()
-        self._last_alt = self.fuse_next_forward and len(slots) % 2 == 0 and (not self.dp.collectives or self.factor_exchange)
+        self._last_alt = self._ends_on_alt(slots)
         self.steps_done += len(slots)
         return ring[:len(slots)]
 
