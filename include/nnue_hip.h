@@ -678,6 +678,48 @@ int nnue_engine_stream_step_stacks(const nnue_engine_model* m, const nnue_engine
                                    int64_t state_bytes, float* logits, float* density, int32_t* changed, int32_t* stack_out,
                                    void* scratch, int64_t scratch_bytes, nnue_stream_t stream);
 
+/* ---- the engine's integer inference as a matrix product (int8 matrix unit) --------------------------------------
+ *
+ * The accumulate step of the calls above, acc[b] = bias + sum of the table rows of b's active features taken mod 2^16
+ * (FeatureTransformer, engine/src/nnue_engine.cpp:236-283 of the header, :726-729), is the product of the 0/1 feature map
+ * [B][F] with the int16 table [F][L1].  Integer addition mod 2^16 depends neither on the order of the terms nor on the width of
+ * the accumulator, so int32 sums truncated to int16 are the engine's wrapped sums bit for bit, and the table splits exactly into
+ * int8 planes: lo = (int8)(w & 0xff), hi = (int8)((w - lo) >> 8), sum(lo) + 256 * sum(hi) == sum(w) (mod 2^16).  A table the
+ * serialiser wrote is clamped to +-127 (serialize.py:218-222) and needs the lo plane only.
+ * nnue_engine_matrix_supported: 1 where nnue_engine_evaluate_logits_matrix can run (planes 1 or 2, num_features < 2^24 so that
+ * no int32 sum of int8 products can overflow, layer sizes inside a workgroup's LDS), else 0; never launches.
+ * nnue_engine_table_planes_bytes: size of the packed planes (num_features and L1 padded to the product's tiles).
+ * nnue_engine_matrix_scratch: >= nnue_engine_scratch(m, B): the conv bytes and the int32 sums [B][L1]. */
+int nnue_engine_matrix_supported(const nnue_engine_model* m, int B, int planes);
+int64_t nnue_engine_table_planes_bytes(const nnue_engine_model* m, int planes);
+int64_t nnue_engine_matrix_scratch(const nnue_engine_model* m, int B, int planes);
+
+/* Packs m->ft_w (int16 [F][L1], the file's table: serialize.py:103-136; the engine reads it as
+ * engine/src/nnue_engine.cpp:236-283 adds its rows) into `planes` int8 planes in the layout the product reads, lo then hi,
+ * zero-padded, in one streaming launch: no host copy, no synchronisation.  table_planes: device, 16-byte aligned,
+ * bytes >= nnue_engine_table_planes_bytes(m, planes).  planes == 1: an element outside [-128, 127] is packed as its low byte and
+ * ADDED to misfit[0] (device int32; the caller zeroes it), one atomic per wave that saw any; planes == 2 leaves misfit alone.
+ * NNUE_E_ARG: null or misaligned pointer; NNUE_E_SHAPE: planes outside {1, 2}, L1 outside 2..2048, num_features >= 2^24;
+ * NNUE_E_SCRATCH: bytes too small. */
+int nnue_engine_pack_table(const nnue_engine_model* m, int planes, void* table_planes, int64_t bytes, int32_t* misfit,
+                           nnue_stream_t stream);
+
+/* NNUEEvaluator::evaluate_logits (engine/src/nnue_engine.cpp:704-734) for B images at once -- the logits
+ * evaluate_compiled_model's per-image engine call obtains (evaluate.py:143-176) -- with the accumulate step on the int8 matrix
+ * unit; bit-identical to nnue_engine_evaluate_logits / nnue_engine_evaluate_logits_stacks.  st == NULL: m's own stack; else the
+ * stack of every image is chosen as nnue_engine_evaluate_logits_stacks chooses it (stack_in, stack_out as there; stack_out is
+ * required iff st).  table_planes, planes: what nnue_engine_pack_table wrote for m->ft_w as it is now.
+ * Exactly one input, as nnue_engine_stream_step: images (B flat buffers of 3*H*W floats; a feature is on under the gather
+ * call's rule, conv byte > threshold and channel < 64) or active (uint8 [B][num_features], non-zero = on, every id counts; H, W
+ * and the conv part of the scratch are unused).  density[b] = the image's active count / num_features, counted once per image.
+ * scratch: 4-byte aligned, >= nnue_engine_matrix_scratch(m, B, planes) bytes.  Where the (B, L1) tile grid leaves CUs idle the
+ * features are split over workgroups and the int32 partial sums meet by integer atomics in sums zeroed on `stream`: the same
+ * bits for any split.  Codes as the gather calls; NNUE_E_SHAPE also where nnue_engine_matrix_supported is 0. */
+int nnue_engine_evaluate_logits_matrix(const nnue_engine_model* m, const nnue_engine_stacks* st, const void* table_planes,
+                                       int planes, const float* images, const uint8_t* active, int B, int H, int W,
+                                       const int32_t* stack_in, float* logits, float* density, int32_t* stack_out,
+                                       void* scratch, int64_t scratch_bytes, nnue_stream_t stream);
+
 /* ---- the engine's tensors from a live model ------------------------------------------------------------------------
  *
  * What serialize_model followed by a load of the file leaves in device memory, formed from the model's float32 parameters in

@@ -4,6 +4,8 @@
 // All arithmetic is the engine's integer arithmetic, so results are bit-identical to it; three of its behaviours are
 // reproduced on purpose (see oracle/nnue_engine_oracle.py): the image buffer is indexed HWC, the conv weight bytes
 // are read as [oc][kh][kw][ic], and the conv's dense [out_h][out_w][oc] output is read back flat with row length g.
+#include <cstdlib>
+
 #include "common.h"
 
 namespace {
@@ -347,6 +349,239 @@ __global__ __launch_bounds__(256) void engine_stream_kernel(const int8_t* __rest
               logits + (size_t)b * C);
 }
 
+// ---- whole batches on the int8 matrix unit --------------------------------------------------------------------------
+// The accumulate step of engine_stack_kernel as a matrix product: sums [B][L1] int32 = A [B][F] . table, with A the 0/1 byte map
+// of the active features and the int16 table as one int8 plane (every value fits a byte) or two (lo, hi: w == lo + 256 * hi
+// mod 2^16, hi may wrap).  Addition mod 2^16 does not depend on the order or on the accumulator's width, so the int32 sums,
+// truncated to int16 by the tail, are the engine's wrapped int16 sums bit for bit.  F < 2^24 keeps every int32 partial sum of
+// int8 products inside int32 (F * 128 < 2^31).
+// Plane layout (engine_pack_table_kernel writes it, the product's B-operand loads read it): [Kpad / 16][Npad][16] bytes, the 16
+// bytes being 16 consecutive features of one column -- one 16-byte load is one lane's B fragment of v_mfma_i32_32x32x32_i8
+// (lane l: column l & 31, features 16 * (l >> 5) .. + 15 of the 32).  Kpad, Npad: F, L1 rounded up to the K and N tile, zero-filled.
+constexpr int kMxBM = 128, kMxBN = 128, kMxBK = 64;
+constexpr int kMxAPitch = kMxBK + 16;  // LDS row pitch of the A tile in bytes (16-byte aligned rows, banks staggered)
+constexpr int kMxMaxFeatures = 1 << 24;
+constexpr int kMxMinTilesPerSlab = 4;
+
+typedef int mx_i32x4 __attribute__((ext_vector_type(4)));
+typedef int mx_i32x16 __attribute__((ext_vector_type(16)));
+
+union MxChunk {
+  uint4 v;
+  mx_i32x4 i;
+  uint8_t b[16];
+};
+
+struct MatrixLayout {
+  int64_t kpad, npad, plane_bytes, sums, total;  // sums: byte offset of the int32 [B][L1] sums in the scratch
+};
+
+__host__ __device__ inline MatrixLayout matrix_layout(int64_t B, int64_t F, int64_t L1) {
+  MatrixLayout l;
+  l.kpad = (F + kMxBK - 1) / kMxBK * kMxBK;
+  l.npad = (L1 + kMxBN - 1) / kMxBN * kMxBN;
+  l.plane_bytes = l.kpad * l.npad;
+  l.sums = (B * F + 255) / 256 * 256;
+  l.total = l.sums + B * L1 * 4;
+  return l;
+}
+
+// One thread = the 16 bytes of (16 features, one column) of every plane.  kPlanes == 1: an element outside [-128, 127] is packed
+// as its low byte and counted into misfit[0], one atomic per wave that saw any.
+template <int kPlanes>
+__global__ __launch_bounds__(256) void engine_pack_table_kernel(const int16_t* __restrict__ ft_w, int F, int L1, int npad,
+                                                                int64_t chunks, int64_t plane_bytes, int8_t* __restrict__ planes,
+                                                                int32_t* __restrict__ misfit) {
+  const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  int bad = 0;
+  if (c < chunks) {
+    const int64_t kb = c / npad;
+    const int n = (int)(c - kb * npad);
+    MxChunk lo, hi;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      const int64_t k = kb * 16 + j;
+      const int32_t w = (k < F && n < L1) ? (int32_t)ft_w[k * L1 + n] : 0;
+      const int8_t l = (int8_t)(w & 0xff);
+      lo.b[j] = (uint8_t)l;
+      hi.b[j] = (uint8_t)((w - (int32_t)l) >> 8);  // may wrap as int8: 256 * 256 == 0 (mod 2^16)
+      if (kPlanes == 1 && w != (int32_t)l) ++bad;
+    }
+    *reinterpret_cast<uint4*>(planes + c * 16) = lo.v;
+    if (kPlanes == 2) *reinterpret_cast<uint4*>(planes + plane_bytes + c * 16) = hi.v;
+  }
+  if (kPlanes == 1) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) bad += __shfl_xor(bad, o);
+    if ((threadIdx.x & 63) == 0 && bad) atomicAdd(misfit, bad);
+  }
+}
+
+// The 0/1 bytes of features f0 .. f0 + 15 of image b (zeros beyond B or F).  kFeatures: src is the caller's map, non-zero = on,
+// every id counts; otherwise the conv bytes under engine_stack_kernel's predicate.
+template <bool kFeatures>
+__device__ __forceinline__ uint4 matrix_a_chunk(const uint8_t* __restrict__ src, int b, int f0, int B, int F, float threshold, int oc,
+                                                bool aligned) {
+  MxChunk raw, out;
+  raw.v = make_uint4(0, 0, 0, 0);
+  out.v = make_uint4(0, 0, 0, 0);
+  if (b >= B || f0 >= F) return out.v;
+  const uint8_t* __restrict__ p = src + (size_t)b * F + f0;
+  const int n = F - f0 < 16 ? F - f0 : 16;
+  if (aligned) {  // F is a multiple of 16 here, so the chunk lies inside the row
+    raw.v = *reinterpret_cast<const uint4*>(p);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 16; ++j)
+      if (j < n) raw.b[j] = p[j];
+  }
+  int ch = kFeatures ? 0 : f0 % oc;
+#pragma unroll
+  for (int j = 0; j < 16; ++j) {
+    bool on;
+    if constexpr (kFeatures) {
+      on = raw.b[j] != 0;
+    } else {
+      on = (float)(int8_t)raw.b[j] > threshold && ch < 64;  // 64 channels per cell are bit-packed
+      if (++ch == oc) ch = 0;
+    }
+    out.b[j] = (j < n && on) ? 1 : 0;
+  }
+  return out.v;
+}
+
+// grid (Npad / 128, ceil(B / 128), slabs), 256 threads = 2 x 2 waves of 64 x 64 results (2 x 2 MFMA tiles of 32 x 32 per plane).
+// A K tile of 64 features: the A bytes are formed from src while staging (matrix_a_chunk) into LDS rows, the plane bytes are
+// copied as they lie; both products of a two-plane table share the A fragments and combine as lo + (hi << 8) before the wrap.
+// A slab covers tiles_per_slab K tiles; with more than one slab the partial sums meet by integer atomics in the zeroed sums
+// (bit-exact for any slab count: integer addition is associative).
+template <int kPlanes, bool kFeatures>
+__global__ __launch_bounds__(256) void engine_matrix_product_kernel(const uint8_t* __restrict__ src, float threshold, int oc, int B,
+                                                                    int F, int L1, int npad, int64_t plane_bytes,
+                                                                    const int8_t* __restrict__ planes, int ktiles, int tiles_per_slab,
+                                                                    int aligned, int atomic, int32_t* __restrict__ sums) {
+  __shared__ __attribute__((aligned(16))) uint8_t a_s[kMxBM * kMxAPitch];
+  __shared__ __attribute__((aligned(16))) uint8_t b_s[kPlanes][(kMxBK / 16) * kMxBN * 16];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int r = lane & 31, h = lane >> 5, wm = wave >> 1, wn = wave & 1;
+  const int n0 = blockIdx.x * kMxBN, m0 = blockIdx.y * kMxBM;
+  const int kt0 = blockIdx.z * tiles_per_slab;
+  const int kt1 = kt0 + tiles_per_slab < ktiles ? kt0 + tiles_per_slab : ktiles;
+
+  mx_i32x16 acc[kPlanes][2][2];
+#pragma unroll
+  for (int p = 0; p < kPlanes; ++p)
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[p][i][j][e] = 0;
+
+  uint4 a_reg[2], b_reg[kPlanes][2];
+  auto load = [&](int kt) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int c = tid + 256 * i;  // A: 128 rows x 4 chunks; planes: 4 feature blocks x 128 columns
+      a_reg[i] = matrix_a_chunk<kFeatures>(src, m0 + (c >> 2), kt * kMxBK + 16 * (c & 3), B, F, threshold, oc, aligned != 0);
+      const int64_t chunk = ((int64_t)kt * (kMxBK / 16) + (c >> 7)) * npad + n0 + (c & 127);
+#pragma unroll
+      for (int p = 0; p < kPlanes; ++p) b_reg[p][i] = *reinterpret_cast<const uint4*>(planes + p * plane_bytes + chunk * 16);
+    }
+  };
+  if (kt0 < kt1) load(kt0);
+  for (int kt = kt0; kt < kt1; ++kt) {
+    __syncthreads();  // the previous tile's fragment reads are done
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int c = tid + 256 * i;
+      *reinterpret_cast<uint4*>(a_s + (c >> 2) * kMxAPitch + 16 * (c & 3)) = a_reg[i];
+#pragma unroll
+      for (int p = 0; p < kPlanes; ++p) *reinterpret_cast<uint4*>(b_s[p] + c * 16) = b_reg[p][i];
+    }
+    __syncthreads();
+    if (kt + 1 < kt1) load(kt + 1);  // in flight under the products
+#pragma unroll
+    for (int ks = 0; ks < kMxBK / 32; ++ks) {
+      mx_i32x4 af[2];
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+        af[i] = *reinterpret_cast<const mx_i32x4*>(a_s + (wm * 64 + i * 32 + r) * kMxAPitch + ks * 32 + 16 * h);
+#pragma unroll
+      for (int p = 0; p < kPlanes; ++p)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          const mx_i32x4 bf = *reinterpret_cast<const mx_i32x4*>(b_s[p] + ((ks * 2 + h) * kMxBN + wn * 64 + j * 32 + r) * 16);
+#pragma unroll
+          for (int i = 0; i < 2; ++i) acc[p][i][j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(af[i], bf, acc[p][i][j], 0, 0, 0);
+        }
+    }
+  }
+
+  // C/D map of the 32 x 32 MFMA: column = lane & 31, row = (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5)
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int col = n0 + wn * 64 + j * 32 + r;
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int row = m0 + wm * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+        uint32_t v = (uint32_t)acc[0][i][j][e];
+        if (kPlanes == 2) v += (uint32_t)acc[kPlanes - 1][i][j][e] << 8;
+        if (row < B && col < L1) {
+          int32_t* dst = sums + (size_t)row * L1 + col;
+          if (atomic) atomicAdd(dst, (int32_t)v);
+          else *dst = (int32_t)v;
+        }
+      }
+    }
+}
+
+// One workgroup per image, as engine_stack_kernel after its gather: the image's active count under the product's predicate
+// (once per image, for density and the stack selector), the wrapped int16 accumulator from the int32 sums, clipped ReLU, tail.
+// dynamic LDS: ft [L1] i32 | pair [L1] i32 | h1 [L2] i32 | h2 [L3] i32 | counts [4] i32
+template <bool kFeatures, class Sel>
+__global__ __launch_bounds__(256) void engine_matrix_tail_kernel(const uint8_t* __restrict__ src, float threshold, int F, int oc,
+                                                                 const int32_t* __restrict__ sums, const int32_t* __restrict__ ft_b,
+                                                                 int quantized_one, const int8_t* __restrict__ l1_w,
+                                                                 const int32_t* __restrict__ l1_b, float l1_scale,
+                                                                 const int8_t* __restrict__ l2_w, const int32_t* __restrict__ l2_b,
+                                                                 int l2_scale, const int8_t* __restrict__ out_w,
+                                                                 const int32_t* __restrict__ out_b, float out_scale, int L1, int L2,
+                                                                 int L3, int C, float* __restrict__ logits, float* __restrict__ density,
+                                                                 Sel sel) {
+  extern __shared__ int32_t lds[];
+  int32_t* ft = lds;
+  int32_t* pair = ft + L1;
+  int32_t* h1 = pair + L1;
+  int32_t* h2 = h1 + L2;
+  int32_t* counts = h2 + L3;
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const uint8_t* __restrict__ row = src + (size_t)b * F;
+  int count = 0;
+  for (int f0 = wave * 64; f0 < F; f0 += 256) {
+    const int f = f0 + lane;
+    bool on;
+    if constexpr (kFeatures) on = f < F && row[f] != 0;
+    else on = f < F && (float)(int8_t)row[f] > threshold && (f % oc) < 64;  // 64 channels per cell are bit-packed
+    count += __popcll(__ballot(on));
+  }
+  if (lane == 0) counts[wave] = count;
+  for (int col = tid; col < L1; col += 256) {
+    const int16_t v = (int16_t)(uint16_t)((uint32_t)ft_b[col] + (uint32_t)sums[(size_t)b * L1 + col]);  // int16 accumulator wraps
+    ft[col] = clamp_i((int32_t)v, 0, quantized_one);
+  }
+  __syncthreads();
+  count = counts[0] + counts[1] + counts[2] + counts[3];
+  if (tid == 0) density[b] = (float)count / (float)F;
+
+  if constexpr (Sel::kSelect)
+    engine_select_stack(sel, b, count, F, L1, L2, L3, C, l1_w, l1_b, l1_scale, l2_w, l2_b, l2_scale, out_w, out_b, out_scale);
+  engine_tail(ft, pair, h1, h2, l1_w, l1_b, l1_scale, l2_w, l2_b, l2_scale, out_w, out_b, out_scale, L1, L2, L3, C,
+              logits + (size_t)b * C);
+}
+
 }  // namespace
 
 extern "C" int64_t nnue_engine_scratch(const nnue_engine_model* m, int B) {
@@ -557,4 +792,141 @@ extern "C" int nnue_engine_stream_step_stacks(const nnue_engine_model* m, const 
                                               int32_t* stack_out, void* scratch, int64_t scratch_bytes, nnue_stream_t stream) {
   return engine_stream_step("nnue_engine_stream_step_stacks", m, true, st, images, active, S, H, W, stack_in, state, state_bytes, logits,
                             density, changed, stack_out, scratch, scratch_bytes, stream);
+}
+
+// ---- the matrix form's entry points ---------------------------------------------------------------------------------
+static size_t engine_tail_lds(const nnue_engine_model* m) { return (size_t)(2 * m->l1 + m->l2 + m->l3 + 4) * sizeof(int32_t); }
+
+// What the matrix form itself can run: the plane count, the tail's LDS, and F small enough that no int32 sum can overflow.
+static bool engine_matrix_shape_ok(const nnue_engine_model* m, int planes) {
+  if (planes != 1 && planes != 2) return false;
+  if (m->num_features <= 0 || m->num_features >= kMxMaxFeatures) return false;
+  if (m->l1 < 2 || m->l1 > 256 * kMaxColsPerThread || m->l2 < 1 || m->l3 < 1) return false;
+  return engine_tail_lds(m) <= 64 * 1024;
+}
+
+extern "C" int nnue_engine_matrix_supported(const nnue_engine_model* m, int B, int planes) {
+  if (!m || B <= 0) return 0;
+  return engine_matrix_shape_ok(m, planes) ? 1 : 0;
+}
+
+extern "C" int64_t nnue_engine_table_planes_bytes(const nnue_engine_model* m, int planes) {
+  if (!m || (planes != 1 && planes != 2) || m->num_features <= 0 || m->l1 <= 0) return 0;
+  return planes * matrix_layout(1, m->num_features, m->l1).plane_bytes;
+}
+
+extern "C" int64_t nnue_engine_matrix_scratch(const nnue_engine_model* m, int B, int planes) {
+  if (!m || B <= 0 || (planes != 1 && planes != 2) || m->num_features <= 0 || m->l1 <= 0) return 0;
+  return matrix_layout(B, m->num_features, m->l1).total;
+}
+
+extern "C" int nnue_engine_pack_table(const nnue_engine_model* m, int planes, void* table_planes, int64_t bytes, int32_t* misfit,
+                                      nnue_stream_t stream) {
+  const char* fn = "nnue_engine_pack_table";
+  NNUE_REQUIRE(m && table_planes && misfit, NNUE_E_ARG, "%s: null pointer", fn);
+  NNUE_REQUIRE(m->ft_w, NNUE_E_ARG, "%s: model tensor missing", fn);
+  NNUE_REQUIRE(nnue_aligned16(table_planes) && (reinterpret_cast<uintptr_t>(misfit) & 3u) == 0, NNUE_E_ARG,
+               "%s: table_planes must be 16-byte aligned, misfit 4-byte aligned", fn);
+  NNUE_REQUIRE(m->num_features > 0 && m->l1 >= 2 && m->l1 <= 256 * kMaxColsPerThread, NNUE_E_SHAPE, "%s: F=%d L1=%d (2..%d)", fn,
+               m->num_features, m->l1, 256 * kMaxColsPerThread);
+  NNUE_REQUIRE(planes == 1 || planes == 2, NNUE_E_SHAPE, "%s: planes=%d (1 or 2)", fn, planes);
+  NNUE_REQUIRE(m->num_features < kMxMaxFeatures, NNUE_E_SHAPE, "%s: num_features %d >= 2^24", fn, m->num_features);
+  const MatrixLayout lay = matrix_layout(1, m->num_features, m->l1);
+  NNUE_REQUIRE(bytes >= planes * lay.plane_bytes, NNUE_E_SCRATCH, "%s: table_planes %lld < %lld bytes", fn, (long long)bytes,
+               (long long)(planes * lay.plane_bytes));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int64_t chunks = lay.plane_bytes / 16;
+  const dim3 grid((unsigned)((chunks + 255) / 256));
+  int8_t* dst = static_cast<int8_t*>(table_planes);
+  if (planes == 1)
+    hipLaunchKernelGGL((engine_pack_table_kernel<1>), grid, dim3(256), 0, s, m->ft_w, m->num_features, m->l1, (int)lay.npad, chunks,
+                       lay.plane_bytes, dst, misfit);
+  else
+    hipLaunchKernelGGL((engine_pack_table_kernel<2>), grid, dim3(256), 0, s, m->ft_w, m->num_features, m->l1, (int)lay.npad, chunks,
+                       lay.plane_bytes, dst, misfit);
+  return nnue_launch_status(fn);
+}
+
+// Slabs along K: enough workgroups for two per CU where the (B, L1) tile grid alone leaves CUs idle, every slab at least
+// kMxMinTilesPerSlab K tiles deep.  NNUE_ENGINE_MATRIX_KSPLIT (developer knob, read per call; 0 = this policy) forces the count.
+static int engine_matrix_slabs(int tiles, int ktiles) {
+  const char* e = std::getenv("NNUE_ENGINE_MATRIX_KSPLIT");
+  int slabs = e && *e ? std::atoi(e) : 0;
+  if (slabs <= 0) {
+    slabs = tiles >= 256 ? 1 : (512 + tiles - 1) / tiles;
+    const int deep = ktiles / kMxMinTilesPerSlab;
+    if (slabs > deep) slabs = deep;
+  }
+  if (slabs > ktiles) slabs = ktiles;
+  return slabs < 1 ? 1 : slabs;
+}
+
+template <int kPlanes, bool kFeatures>
+static void engine_launch_product(const nnue_engine_model* m, const uint8_t* src, int B, const MatrixLayout& lay, const int8_t* planes,
+                                  int32_t* sums, hipStream_t s) {
+  const int F = m->num_features, L1 = m->l1;
+  const int tiles_n = (int)(lay.npad / kMxBN), tiles_m = (B + kMxBM - 1) / kMxBM, ktiles = (int)(lay.kpad / kMxBK);
+  const int want = engine_matrix_slabs(tiles_n * tiles_m, ktiles);
+  const int per = (ktiles + want - 1) / want, slabs = (ktiles + per - 1) / per;
+  if (slabs > 1) nnue_zero_floats(reinterpret_cast<float*>(sums), (size_t)B * L1, s);  // zero bits either way
+  const int aligned = F % 16 == 0 && nnue_aligned16(src);
+  hipLaunchKernelGGL((engine_matrix_product_kernel<kPlanes, kFeatures>), dim3(tiles_n, tiles_m, slabs), dim3(256), 0, s, src,
+                     m->threshold, m->oc, B, F, L1, (int)lay.npad, lay.plane_bytes, planes, ktiles, per, aligned, slabs > 1 ? 1 : 0,
+                     sums);
+}
+
+template <bool kFeatures, class Sel>
+static void engine_launch_matrix_tail(const nnue_engine_model* m, const EngineTailArgs& t, const uint8_t* src, const int32_t* sums, int B,
+                                      float* logits, float* density, Sel sel, hipStream_t s) {
+  hipLaunchKernelGGL((engine_matrix_tail_kernel<kFeatures, Sel>), dim3(B), dim3(256), engine_tail_lds(m), s, src, m->threshold,
+                     m->num_features, m->oc, sums, m->ft_b, (int)(int16_t)m->quantized_one, t.l1_w, t.l1_b, t.l1_scale, t.l2_w, t.l2_b,
+                     t.l2_scale, t.out_w, t.out_b, t.out_scale, m->l1, m->l2, m->l3, m->classes, logits, density, sel);
+}
+
+extern "C" int nnue_engine_evaluate_logits_matrix(const nnue_engine_model* m, const nnue_engine_stacks* st, const void* table_planes,
+                                                  int planes, const float* images, const uint8_t* active, int B, int H, int W,
+                                                  const int32_t* stack_in, float* logits, float* density, int32_t* stack_out,
+                                                  void* scratch, int64_t scratch_bytes, nnue_stream_t stream) {
+  const char* fn = "nnue_engine_evaluate_logits_matrix";
+  NNUE_REQUIRE(m && table_planes && logits && density && scratch, NNUE_E_ARG, "%s: null pointer", fn);
+  if (st)
+    if (int rc = engine_check_stacks(st, stack_out, fn)) return rc;
+  NNUE_REQUIRE((images != nullptr) != (active != nullptr), NNUE_E_ARG, "%s: pass exactly one of images and active", fn);
+  NNUE_REQUIRE(nnue_aligned16(table_planes), NNUE_E_ARG, "%s: table_planes must be 16-byte aligned", fn);
+  NNUE_REQUIRE(engine_has_tensors(m, st), NNUE_E_ARG, "%s: model tensor missing", fn);
+  NNUE_REQUIRE(B > 0, NNUE_E_ARG, "%s: B=%d must be positive", fn, B);
+  if (int rc = engine_check_model(m, st, fn)) return rc;
+  const int oc = m->oc, F = m->num_features, L1 = m->l1;
+  NNUE_REQUIRE(planes == 1 || planes == 2, NNUE_E_SHAPE, "%s: planes=%d (1 or 2)", fn, planes);
+  NNUE_REQUIRE(F < kMxMaxFeatures, NNUE_E_SHAPE, "%s: num_features %d >= 2^24 (an int32 sum could overflow)", fn, F);
+  NNUE_REQUIRE(engine_tail_lds(m) <= 64 * 1024, NNUE_E_SHAPE, "%s: layer sizes need %zu bytes of LDS", fn, engine_tail_lds(m));
+  int stride = 1, OH = 0, OW = 0;
+  if (images) {
+    NNUE_REQUIRE(H > 0 && W > 0, NNUE_E_ARG, "%s: H=%d W=%d must be positive", fn, H, W);
+    if (int rc = engine_conv_geometry(m, H, W, fn, &stride, &OH, &OW)) return rc;
+    NNUE_REQUIRE((long long)B * H * W * 3 < (1ll << 40), NNUE_E_SHAPE, "%s: batch too large", fn);
+  }
+  const MatrixLayout lay = matrix_layout(B, F, L1);
+  NNUE_REQUIRE(scratch_bytes >= lay.total, NNUE_E_SCRATCH, "%s: scratch %lld < %lld bytes", fn, (long long)scratch_bytes,
+               (long long)lay.total);
+  NNUE_REQUIRE((reinterpret_cast<uintptr_t>(scratch) & 3u) == 0, NNUE_E_ARG, "%s: scratch must be 4-byte aligned", fn);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  uint8_t* conv = static_cast<uint8_t*>(scratch);
+  int32_t* sums = reinterpret_cast<int32_t*>(conv + lay.sums);
+  const int8_t* tp = static_cast<const int8_t*>(table_planes);
+  const EngineTailArgs t = engine_tail_args(m, st);
+  if (images) {
+    hipLaunchKernelGGL(engine_conv_kernel, dim3((F + 255) / 256, B), dim3(256), 0, s, images, m->conv_w, m->conv_b, m->conv_scale, H, W,
+                       stride, OH, OW, oc, F, reinterpret_cast<int8_t*>(conv));
+    if (planes == 1) engine_launch_product<1, false>(m, conv, B, lay, tp, sums, s);
+    else engine_launch_product<2, false>(m, conv, B, lay, tp, sums, s);
+    if (st) engine_launch_matrix_tail<false>(m, t, conv, sums, B, logits, density, engine_stack_sel(st, stack_in, stack_out), s);
+    else engine_launch_matrix_tail<false>(m, t, conv, sums, B, logits, density, NoStackSel{}, s);
+  } else {
+    if (planes == 1) engine_launch_product<1, true>(m, active, B, lay, tp, sums, s);
+    else engine_launch_product<2, true>(m, active, B, lay, tp, sums, s);
+    if (st) engine_launch_matrix_tail<true>(m, t, active, sums, B, logits, density, engine_stack_sel(st, stack_in, stack_out), s);
+    else engine_launch_matrix_tail<true>(m, t, active, sums, B, logits, density, NoStackSel{}, s);
+  }
+  return nnue_launch_status(fn);
 }

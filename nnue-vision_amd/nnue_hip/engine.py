@@ -12,10 +12,14 @@ caller -- the engine's ``layer_stack_index`` (nnue_engine.cpp:704-707), bit-iden
 ``EngineModel.from_model(model)`` builds the same tensors from a live ``nnue.NNUE`` on the device, without the file and without
 touching the model (one launch, include/nnue_hip.h: nnue_engine_quantize_model); ``requantize(model)`` repeats that launch into
 the tensors the engine already holds -- what a training loop does after every epoch.
+``evaluate_logits(..., path="matrix")`` and ``evaluate_features(active)`` run the accumulate step as one product on the int8
+matrix unit (include/nnue_hip.h: nnue_engine_evaluate_logits_matrix) over int8 planes of the table packed once
+(``prepare_matrix``): the same bits, since addition mod 2^16 depends on neither order nor accumulator width.
 """
 from __future__ import annotations
 
 import ctypes
+import os
 import struct
 from pathlib import Path
 from typing import Iterable, Optional, Tuple, Union
@@ -27,6 +31,15 @@ from . import lib
 
 
 _STACK_TENSORS = ("l1_w", "l1_b", "l2_w", "l2_b", "out_w", "out_b")
+
+_PATHS = ("gather", "matrix", "auto")
+# path="auto" takes the matrix form from this many map bytes (B * num_features) upwards.  The sweep of tools/bench_engine.py
+# --shape {c2,224} (profiles/engine_matrix.json; gather / matrix ms, matrix p90 below gather p10 at every point):
+#   CIFAR shape (F = 800, L1 = 1024)     B = 16: 0.261 / 0.052   128: 0.265 / 0.058   512: 0.270 / 0.065   4096: 0.624 / 0.226
+#   224x224 shape (F = 65536, L1 = 512)  B = 2: 26.7 / 0.114     64: 27.4 / 0.183     128: 27.4 / 0.258    1024: 37.2 / 1.24
+# The matrix form won at every measured point, so the constant is the smallest of them (CIFAR, B = 16); below it auto stays on
+# the gather form, which nothing measured there contradicts.
+_MATRIX_MIN_MAP_BYTES = 12800
 
 
 class _CModel(ctypes.Structure):  # include/nnue_hip.h: nnue_engine_model
@@ -76,9 +89,19 @@ class EngineModel:
     """Quantised tensors of one `.nnue` file on the device + the scalars of its header.  ``stack_scales`` (loaded with
     bucket="auto"): the six stack tensors hold all K stacks, stack-major, and every call selects a stack per image."""
 
-    def __init__(self, header: dict, tensors: dict, device, stack_scales: Optional[np.ndarray] = None):
+    def __init__(self, header: dict, tensors: dict, device, stack_scales: Optional[np.ndarray] = None,
+                 table_planes: Optional[int] = None):
         self.header = header
         self.device = torch.device(device)
+        # int8 planes of ft_w for the matrix form, outside self.tensors: 1 when every table value fits a byte, else 2 (lo, hi);
+        # None = not known on the host, prepare_matrix finds out from the one-plane pack's misfit count
+        ft_w = tensors.get("ft_w")
+        if table_planes is None and isinstance(ft_w, np.ndarray) and ft_w.size:
+            table_planes = 2 if int(ft_w.min()) < -128 or int(ft_w.max()) > 127 else 1
+        self.table_planes: Optional[int] = table_planes
+        self._planes: Optional[torch.Tensor] = None
+        self._misfit: Optional[torch.Tensor] = None
+        self._matrix_scratch: Optional[torch.Tensor] = None
         self.tensors = {k: (v if torch.is_tensor(v) else torch.from_numpy(v)).to(self.device) for k, v in tensors.items()}
         c = _CModel()
         for k in ("num_features", "l1", "l2", "l3", "classes", "grid", "oc"):
@@ -242,6 +265,8 @@ class EngineModel:
         lib._call("nnue_engine_quantize_model", *[t.data_ptr() for t in src], h["oc"], h["num_features"], h["l1"], h["l2"], h["l3"],
                   h["classes"], h["buckets"], self._stack_index, ctypes.addressof(self._c),
                   None if self._stacks is None else ctypes.addressof(self._stacks), self._bad.data_ptr(), lib._stream(src[1]))
+        if self._planes is not None:  # the matrix form's planes follow the table: same stream, same memory, nothing allocated
+            self._pack_planes(lib._stream(src[1]))
         if check:
             bad = int(self._bad.item())  # one scalar, once per call
             if bad:
@@ -283,7 +308,7 @@ class EngineModel:
                   "out_w": (lead + (c * l3,), torch.int8), "out_b": (lead + (c,), torch.int32)}
         tensors = {name: torch.zeros(shape, dtype=dtype, device=device) for name, (shape, dtype) in shapes.items()}
         scales = np.full((k, 3), h["conv_scale"], dtype=np.float32) if auto else None
-        engine = cls(h, tensors, device, scales)
+        engine = cls(h, tensors, device, scales, table_planes=1)  # the quantiser clamps the table to +-127
         engine._stack_index = 0 if auto or bucket is None or bucket >= k else int(bucket)  # nnue_engine.cpp:705-707
         engine._bad = torch.zeros((1,), dtype=torch.int32, device=device)
         engine._bad_known_zero = True
@@ -292,7 +317,8 @@ class EngineModel:
 
     def requantize(self, model, check: bool = True) -> None:
         """``from_model`` again, into the tensors this engine already holds: no allocation, every ``data_ptr()`` unchanged (a
-        captured graph over ``evaluate_logits`` stays valid), the by-value scalars refreshed.  Streams of this model refresh
+        captured graph over ``evaluate_logits`` stays valid; the matrix form's planes, once prepared, are re-packed in place
+        right after the quantise launch), the by-value scalars refreshed.  Streams of this model refresh
         their accumulators on their next step.  A model of another architecture or stack count is refused."""
         if self._bad is None:
             raise ValueError("requantize: this engine was loaded from a file; build it with EngineModel.from_model")
@@ -322,6 +348,113 @@ class EngineModel:
             raise ValueError("images: expected [B,3,H,W], or [B,3*H*W] with height and width")
         return b, h, w
 
+    # ---- the matrix form -------------------------------------------------------------------------
+    def _pack_planes(self, stream: int) -> None:
+        lib._call("nnue_engine_pack_table", ctypes.addressof(self._c), self.table_planes, self._planes.data_ptr(),
+                  self._planes.numel(), self._misfit.data_ptr(), stream)
+
+    def matrix_supported(self, batch: int = 1) -> bool:
+        """Whether the matrix form can run this model (include/nnue_hip.h: nnue_engine_matrix_supported)."""
+        return bool(lib.load().nnue_engine_matrix_supported(ctypes.byref(self._c), int(batch), self.table_planes or 1))
+
+    def prepare_matrix(self) -> None:
+        """Packs the int8 planes of the table for the matrix form (done by the first matrix call otherwise).  One launch; a
+        table whose range the host does not know is packed as one plane first and its misfit count read back, here only."""
+        if self._planes is not None:
+            return
+        if not self.matrix_supported():
+            raise lib.NnueHipError("prepare_matrix: the matrix form does not support this model "
+                                   f"(num_features={self.header['num_features']}, L1={self.header['l1']})")
+        if torch.cuda.is_current_stream_capturing():
+            raise lib.NnueHipError("prepare_matrix: call it before the capture (it allocates and may read a counter back)")
+        L = lib.load()
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            self._misfit = torch.zeros((1,), dtype=torch.int32, device=self.device)
+            probe = self.table_planes is None
+            if probe:
+                self.table_planes = 1
+            try:
+                nbytes = int(L.nnue_engine_table_planes_bytes(ctypes.byref(self._c), self.table_planes))
+                self._planes = torch.empty((nbytes,), dtype=torch.uint8, device=self.device)
+                self._pack_planes(stream)
+                if probe and int(self._misfit.item()):
+                    self.table_planes = 2
+                    nbytes = int(L.nnue_engine_table_planes_bytes(ctypes.byref(self._c), 2))
+                    self._planes = torch.empty((nbytes,), dtype=torch.uint8, device=self.device)
+                    self._pack_planes(stream)
+            except Exception:
+                self._planes = None
+                if probe:
+                    self.table_planes = None
+                raise
+
+    def _path(self, path: Optional[str], b: int, what: str) -> str:
+        """"gather" or "matrix" for a call on images (None = NNUE_ENGINE_PATH, default auto)."""
+        if path is None:
+            path = os.environ.get("NNUE_ENGINE_PATH", "auto")
+        if path not in _PATHS:
+            raise ValueError(f"{what}: path must be one of {_PATHS}, got {path!r}")
+        if path == "auto":
+            ready = self._planes is not None or not torch.cuda.is_current_stream_capturing()
+            big = b * int(self.header["num_features"]) >= _MATRIX_MIN_MAP_BYTES
+            return "matrix" if big and ready and self.matrix_supported(b) else "gather"
+        if path == "matrix" and not self.matrix_supported(b):
+            raise lib.NnueHipError(f"{what}: path=\"matrix\" does not support this model "
+                                   f"(num_features={self.header['num_features']}, L1={self.header['l1']})")
+        return path
+
+    def _evaluate_matrix(self, images: Optional[torch.Tensor], active: Optional[torch.Tensor], b: int, h: int, w: int,
+                         stacks: Optional[torch.Tensor], return_stacks: bool):
+        self.prepare_matrix()
+        scratch = self._matrix_scratch_for(b)
+        logits = torch.empty((b, self.num_classes), dtype=torch.float32, device=self.device)
+        density = torch.empty((b,), dtype=torch.float32, device=self.device)
+        src = images if images is not None else active
+        if self._stacks is None:
+            used = torch.zeros((b,), dtype=torch.int32, device=self.device) if return_stacks else None
+            st, used_ptr = None, 0
+        else:
+            used = torch.empty((b,), dtype=torch.int32, device=self.device)
+            st, used_ptr = ctypes.addressof(self._stacks), used.data_ptr()
+        lib._call("nnue_engine_evaluate_logits_matrix", ctypes.addressof(self._c), st, self._planes.data_ptr(), self.table_planes,
+                  lib._ptr(images), lib._ptr(active), b, h, w, lib._ptr(stacks), logits.data_ptr(), density.data_ptr(), used_ptr,
+                  scratch.data_ptr(), scratch.numel(), lib._stream(src))
+        return (logits, density, used) if return_stacks else (logits, density)
+
+    def evaluate_features(self, active: torch.Tensor, stacks: Optional[torch.Tensor] = None, return_stacks: bool = False,
+                          path: Optional[str] = None):
+        """``evaluate_logits`` from active-feature maps: bool or uint8 [B, num_features] on the device, non-zero = on, every id
+        counts (the rule of ``EngineStream.step_features``; no per-cell channel mask).  Always the matrix form -- the gather
+        kernels take no feature map -- so path="gather" raises ValueError and an unsupported model NnueHipError."""
+        if path is None:
+            path = os.environ.get("NNUE_ENGINE_PATH", "auto")
+            path = "matrix" if path == "gather" else path  # the variable chooses among forms that exist for the call
+        if path not in _PATHS:
+            raise ValueError(f"evaluate_features: path must be one of {_PATHS}, got {path!r}")
+        if path == "gather":
+            raise ValueError("evaluate_features: the gather kernels have no feature-map input; use path=\"matrix\"")
+        if not isinstance(active, torch.Tensor):
+            raise TypeError(f"active: expected a tensor, got {type(active).__name__}")
+        if active.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f"active: expected dtype torch.bool or torch.uint8, got {active.dtype}")
+        if not active.is_cuda or (self.device.index is not None and active.device.index != self.device.index):
+            raise ValueError(f"active: tensor is on {active.device}, the model on {self.device} (no CPU fallback in this build)")
+        f = int(self.header["num_features"])
+        if active.dim() != 2 or active.shape[0] < 1 or active.shape[1] != f:
+            raise ValueError(f"active: expected shape (B, {f}), got {tuple(active.shape)}")
+        b = int(active.shape[0])
+        self._path("matrix", b, "evaluate_features")
+        stacks = self._stack_arg(stacks, b, "evaluate_features")
+        return self._evaluate_matrix(None, active.contiguous(), b, 0, 0, stacks, return_stacks)
+
+    def _matrix_scratch_for(self, b: int) -> torch.Tensor:
+        """The matrix form's own buffer: growing it never moves the scratch a captured gather call points at."""
+        need = int(lib.load().nnue_engine_matrix_scratch(ctypes.byref(self._c), b, self.table_planes))
+        if self._matrix_scratch is None or self._matrix_scratch.numel() < need:
+            self._matrix_scratch = torch.empty((max(16, need),), dtype=torch.uint8, device=self.device)
+        return self._matrix_scratch
+
     def _scratch_for(self, b: int) -> torch.Tensor:
         need = int(lib.load().nnue_engine_scratch(ctypes.byref(self._c), b))
         if self._scratch is None or self._scratch.numel() < need:
@@ -329,16 +462,21 @@ class EngineModel:
         return self._scratch
 
     def evaluate_logits(self, images: torch.Tensor, height: Optional[int] = None, width: Optional[int] = None,
-                        stacks: Optional[torch.Tensor] = None, return_stacks: bool = False):
+                        stacks: Optional[torch.Tensor] = None, return_stacks: bool = False, path: Optional[str] = None):
         """(logits [B, C] float32, density [B] float32).  ``images`` is what the reference hands the engine: per sample
         a flat buffer of 3*H*W floats which the engine indexes as HWC -- for a [B,3,H,W] tensor that is its memory as
         it stands (evaluate.py:150-161 passes shape[1], shape[2] as H, W), which is reproduced, not corrected.
         A model loaded with bucket="auto" puts every image through the stack ``stack_of`` gives for its active-feature
         count, or through ``stacks`` (device int32/int64 [B]; outside [0, K) = stack 0).  return_stacks: also return the
-        stack every image used, int32 [B] (zeros for a single-stack model)."""
+        stack every image used, int32 [B] (zeros for a single-stack model).
+        path: "gather" (one workgroup per image adds its active table rows), "matrix" (one product on the int8 matrix
+        unit), or "auto" (matrix from the measured crossover upwards where the model allows it; inside a stream capture only
+        with the planes already prepared); None reads NNUE_ENGINE_PATH, default auto.  The bits are the same either way."""
         images = lib._need(images, torch.float32, "images")
         b, h, w = self._frames(images, height, width)
         stacks = self._stack_arg(stacks, b, "evaluate_logits")
+        if self._path(path, b, "evaluate_logits") == "matrix":
+            return self._evaluate_matrix(images, None, b, h, w, stacks, return_stacks)
         self._scratch_for(b)
         logits = torch.empty((b, self.num_classes), dtype=torch.float32, device=self.device)
         density = torch.empty((b,), dtype=torch.float32, device=self.device)

@@ -29,13 +29,13 @@ STACK_SHAPES = [
 ]
 
 
-def _median_ms(pairs):
-    torch.cuda.synchronize()
-    return statistics.median(a.elapsed_time(b) for a, b in pairs)
-
-
 def _alternate(calls, warmup, repeats):
     """Runs the calls in turn, warmup + repeats rounds; median event time of each over the timed rounds."""
+    return [st["median"] for st in _alternate_spread(calls, warmup, repeats)]
+
+
+def _alternate_spread(calls, warmup, repeats):
+    """_alternate with the spread: {"median", "p10", "p90"} in ms for each call."""
     times = [[] for _ in calls]
     for t in range(warmup + repeats):
         for i, fn in enumerate(calls):
@@ -45,7 +45,116 @@ def _alternate(calls, warmup, repeats):
             t1.record()
             if t >= warmup:
                 times[i].append((t0, t1))
-    return [_median_ms(ts) for ts in times]
+    torch.cuda.synchronize()
+    out = []
+    for ts in times:
+        ms = sorted(a.elapsed_time(b) for a, b in ts)
+        out.append({"median": statistics.median(ms), "p10": ms[len(ms) // 10], "p90": ms[(len(ms) * 9) // 10]})
+    return out
+
+
+def _stack_case(shape, K):
+    """The model file, engines and images of one --stacks row: (plain, auto, x)."""
+    torch.manual_seed(0)
+    size, B = shape["size"], shape["batch"]
+    model = nnue.NNUE(nnue.GridFeatureSet(shape["g"], shape["fps"]), shape["l1"], shape["l2"], shape["l3"],
+                      num_classes=shape["classes"], input_size=size, num_ls_buckets=K)
+    with torch.no_grad():
+        model.conv.weight.abs_()
+    with tempfile.TemporaryDirectory() as tmp:
+        path = Path(tmp) / "m.nnue"
+        with contextlib.redirect_stdout(sys.stderr):  # keep stdout to the one JSON object
+            serialize.serialize_model(model, path)
+        plain, auto = EngineModel.load(path), EngineModel.load(path, bucket="auto")
+    n = 3 * size * size
+    x = torch.randn(B, n, device="cuda") * 0.3 - 1.5
+    bright = torch.arange(n, device="cuda")[None, :] < (torch.arange(B, device="cuda") * n // (B - 1))[:, None]
+    x = (x + 3.0 * bright).view(B, 3, size, size).contiguous()
+    return model, plain, auto, x
+
+
+PATH_BATCHES = {"c2": (512, 4096, 16, 64, 128, 256, 1024, 2048), "224": (128, 1024, 1, 2, 4, 8, 16, 32, 64, 256, 512)}
+
+
+def bench_paths(shape_key, only, batches, warmup, repeats, extras):
+    """--shape {c2,224}: the gather form of evaluate_logits against the matrix form (path="gather" / "matrix"), in this process,
+    alternating inside one loop, on the model, file and images of the --stacks rows (single-stack load, so `gather` is that row's
+    plain_ms at its batch).  Per batch: median, 10th and 90th percentile of device-event-timed calls after warm-up; the first
+    two batches are the headline ones, the rest the crossover sweep behind engine._MATRIX_MIN_MAP_BYTES.  --path P times that
+    form alone (what a rocprofv3 --kernel-trace run of this tool wants).  With --extras: the pack launch, requantize with and
+    without planes, and evaluate_engine over resident images on either form.
+        python tools/bench_engine.py --shape 224 --extras > engine_matrix_224.json"""
+    import evaluate
+    shape = dict(STACK_SHAPES[0 if shape_key == "c2" else 1])
+    batches = tuple(batches) if batches else PATH_BATCHES[shape_key]
+    shape["batch"] = max(max(batches), 2)
+    model, engine, _, x_all = _stack_case(shape, 8)
+    F, L1 = int(engine.header["num_features"]), shape["l1"]
+    res = {"device": torch.cuda.get_device_name(0), "shape": shape["name"], "F": F, "L1": L1, "planes": None, "warmup": warmup,
+           "repeats": repeats, "timing": "median (p10, p90) of device-event-timed calls, gather and matrix alternating in one loop",
+           "cases": []}
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0.record()
+    engine.prepare_matrix()
+    t1.record()
+    torch.cuda.synchronize()
+    res["planes"], res["prepare_matrix_first_ms"] = engine.table_planes, t0.elapsed_time(t1)
+    for B in batches:
+        x = x_all[torch.linspace(0, x_all.shape[0] - 1, B).long().cuda()].contiguous()  # the whole dark-to-bright range at any B
+        g, m = engine.evaluate_logits(x, path="gather"), engine.evaluate_logits(x, path="matrix")
+        assert torch.equal(g[0], m[0]) and torch.equal(g[1], m[1])
+        row = {"batch": B, "map_bytes": B * F, "mean_density": float(g[1].double().mean())}
+        names = [only] if only else ["gather", "matrix"]
+        stats = _alternate_spread([lambda t, p=p: engine.evaluate_logits(x, path=p) for p in names], warmup, repeats)
+        for p, st in zip(names, stats):
+            row[p + "_ms"], row[p + "_p10_ms"], row[p + "_p90_ms"] = st["median"], st["p10"], st["p90"]
+        if not only:
+            row["gather_over_matrix"] = row["gather_ms"] / row["matrix_ms"]
+            row["matrix_wins_beyond_spread"] = row["matrix_p90_ms"] < row["gather_p10_ms"]
+            row["int8_macs_per_s"] = engine.table_planes * B * F * L1 / (row["matrix_ms"] * 1e-3)  # the whole call's time
+        print(json.dumps(row), file=sys.stderr)
+        res["cases"].append(row)
+    if extras and not only:
+        stream = torch.cuda.current_stream().cuda_stream
+        st = _alternate_spread([lambda t: engine._pack_planes(stream)], warmup, repeats)[0]
+        res["pack_launch_ms"] = st
+        res["pack_gbs"] = (2 * F * L1 + engine._planes.numel()) / (st["median"] * 1e-3) / 1e9
+        single = nnue.NNUE(nnue.GridFeatureSet(shape["g"], shape["fps"]), shape["l1"], shape["l2"], shape["l3"],
+                           num_classes=shape["classes"], input_size=shape["size"]).cuda()
+        live = EngineModel.from_model(single)
+
+        def requantize_ms():
+            ts = []
+            for _ in range(warmup + repeats):
+                torch.cuda.synchronize()
+                a = time.perf_counter()
+                live.requantize(single)
+                torch.cuda.synchronize()
+                ts.append((time.perf_counter() - a) * 1e3)
+            return statistics.median(ts[warmup:])
+
+        res["requantize_call_ms"] = requantize_ms()
+        live.prepare_matrix()
+        res["requantize_call_with_planes_ms"] = requantize_ms()
+        # evaluate_engine over resident images, gather form against auto
+        per, nb = (1000, 10) if shape_key == "224" else (500, 20)
+        loader = [(x_all[:per].roll(i, 0).contiguous(), torch.randint(0, shape["classes"], (per,), device="cuda")) for i in range(nb)]
+        out = {}
+        for name in ("gather", "auto"):
+            os.environ["NNUE_ENGINE_PATH"] = name
+            ts = []
+            for _ in range(3):
+                torch.cuda.synchronize()
+                a = time.perf_counter()
+                metrics = evaluate.evaluate_engine(engine, loader)
+                torch.cuda.synchronize()
+                ts.append((time.perf_counter() - a) * 1e3)
+            out[name] = {"wall_ms": statistics.median(ts), "ms_per_sample": metrics["ms_per_sample"], "acc": metrics["acc"],
+                         "latent_density": metrics["latent_density"]}
+        os.environ.pop("NNUE_ENGINE_PATH", None)
+        assert out["gather"]["acc"] == out["auto"]["acc"] and out["gather"]["latent_density"] == out["auto"]["latent_density"]
+        res["evaluate_engine"] = dict(out, images=per * nb, batch=per)
+    print(json.dumps(res))
 
 
 def bench_stacks(K, warmup, repeats):
@@ -59,22 +168,8 @@ def bench_stacks(K, warmup, repeats):
     res = {"device": torch.cuda.get_device_name(0), "stacks": K, "warmup": warmup, "repeats": repeats,
            "timing": "median of device-event-timed calls, plain and selected alternating in one loop", "cases": []}
     for shape in STACK_SHAPES:
-        torch.manual_seed(0)
-        size, B = shape["size"], shape["batch"]
-        model = nnue.NNUE(nnue.GridFeatureSet(shape["g"], shape["fps"]), shape["l1"], shape["l2"], shape["l3"],
-                          num_classes=shape["classes"], input_size=size, num_ls_buckets=K)
-        with torch.no_grad():
-            model.conv.weight.abs_()
-        with tempfile.TemporaryDirectory() as tmp:
-            path = Path(tmp) / "m.nnue"
-            with contextlib.redirect_stdout(sys.stderr):  # keep stdout to the one JSON object
-                serialize.serialize_model(model, path)
-            plain, auto = EngineModel.load(path), EngineModel.load(path, bucket="auto")
-        n = 3 * size * size
-        x = torch.randn(B, n, device="cuda") * 0.3 - 1.5
-        bright = torch.arange(n, device="cuda")[None, :] < (torch.arange(B, device="cuda") * n // (B - 1))[:, None]
-        x = (x + 3.0 * bright).view(B, 3, size, size).contiguous()
-        del bright
+        B = shape["batch"]
+        _, plain, auto, x = _stack_case(shape, K)
         frames = (x, x.roll(1, 0).contiguous())
         logits, density, stack = auto.evaluate_logits(x, return_stacks=True)
         same = stack == 0  # rows of stack 0 must be the plain call's, bit for bit
@@ -98,6 +193,10 @@ def bench_stacks(K, warmup, repeats):
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--stacks", type=int, default=0, help="K: time per-image stack selection against the plain call instead")
+    ap.add_argument("--shape", choices=("c2", "224"), help="time the gather form against the matrix form at this shape instead")
+    ap.add_argument("--path", choices=("gather", "matrix"), help="with --shape: time this form alone")
+    ap.add_argument("--batches", type=int, nargs="*", help="with --shape: the batch sizes (default: headline pair + sweep)")
+    ap.add_argument("--extras", action="store_true", help="with --shape: also pack, requantize and evaluate_engine")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--repeats", type=int, default=50)
     args = ap.parse_args()
@@ -105,6 +204,10 @@ def main():
         if not torch.cuda.is_available():
             raise SystemExit("bench_engine: needs a GPU")
         return bench_stacks(args.stacks, args.warmup, args.repeats)
+    if args.shape:
+        if not torch.cuda.is_available():
+            raise SystemExit("bench_engine: needs a GPU")
+        return bench_paths(args.shape, args.path, args.batches, args.warmup, args.repeats, args.extras)
     torch.manual_seed(0)
     model = nnue.NNUE(nnue.GridFeatureSet(10, 8), 1024, 128, 32, num_classes=10)
     res = {"model": "C2 architecture (800 -> 1024/128/32 -> 10), 32x32 images"}
