@@ -271,7 +271,9 @@ int nnue_ftm_conv_binarize_planes(const float* images, const float* weight, cons
 
 /* nnue_ftm_forward_l1 (nnue.py:686-710 + :660-666, :728-730) reading the planes nnue_ftm_conv_binarize_planes wrote from the
  * same `weight`; weight itself is read for the clamp-sink row F-1 only.  out and part are bitwise what nnue_ftm_forward_l1
- * gives with its 32-row bf16 tiles (NNUE_FTM_BF_BM=32). */
+ * gives with its 32-row bf16 tiles (NNUE_FTM_BF_BM=32).  Up to 7 K tiles of 128 (min(F - 1, P) <= 896) each wave loads its
+ * fragments of the planes straight into the MFMA's operands; deeper shapes, and NNUE_FTM_FWD_STREAM=0 (read per call), stage
+ * the planes through LDS -- the same bits. */
 int nnue_ftm_forward_l1_planes(const uint8_t* bits, const float* sink, const void* planes, int64_t planes_bytes,
                                const float* weight, const float* bias, const float* w1, int B, int F, int P, int L1,
                                int L2, float* out, float* part, nnue_stream_t stream);

@@ -423,25 +423,28 @@ constexpr int kL1Ld = 68;
 // latencies is left at the end of the tile: sink / bias / last table row, and the w1 fragments of this wave's first
 // two 16-unit column tiles.
 constexpr int kL1PreTiles = 2;
-template <int BM>
+// W14: the waves of the tile are 1 x 4 instead of 2 x 2 (the streamed forward below: a wave owns all BM rows x 16 columns, so
+// BM / 16 row fragments x 1 column fragment instead of BM / 32 x 2); only the placement of the accumulators follows it
+template <int BM, bool W14 = false>
 struct FusedL1Pre {
-  float sk[BM / 32][4];
-  float bv[2], wl[2];
+  static constexpr int kTM = W14 ? BM / 16 : BM / 32, kTN = W14 ? 1 : 2;
+  float sk[kTM][4];
+  float bv[kTN], wl[kTN];
   float4 bq[kL1PreTiles][4];
 };
 
-template <int BM>
-__device__ __forceinline__ void fused_l1_prefetch(const FwdL1Epi& e, FusedL1Pre<BM>& p, int m_base, int tile_n, int m0, int n0, int r,
+template <int BM, bool W14 = false>
+__device__ __forceinline__ void fused_l1_prefetch(const FwdL1Epi& e, FusedL1Pre<BM, W14>& p, int m_base, int tile_n, int m0, int n0, int r,
                                                   int q, int wave) {
 #pragma unroll
-  for (int i = 0; i < BM / 32; ++i)
+  for (int i = 0; i < FusedL1Pre<BM, W14>::kTM; ++i)
 #pragma unroll
     for (int ee = 0; ee < 4; ++ee) {
       const int m = m_base + m0 + 16 * i + 4 * q + ee;
       p.sk[i][ee] = m < e.B ? e.sink[m] : 0.0f;
     }
 #pragma unroll
-  for (int t = 0; t < 2; ++t) {
+  for (int t = 0; t < FusedL1Pre<BM, W14>::kTN; ++t) {
     const int colg = e.col(tile_n * 64 + n0 + 16 * t + r);
     p.bv[t] = e.bias[colg];
     p.wl[t] = e.w_last[colg];
@@ -460,15 +463,15 @@ __device__ __forceinline__ void fused_l1_prefetch(const FwdL1Epi& e, FusedL1Pre<
   }
 }
 
-template <int BM>
-__device__ __forceinline__ void fused_l1_epilogue(const FwdL1Epi& e, const FusedL1Pre<BM>& p, float* __restrict__ smem,
-                                                  const f32x4 (&acc)[BM / 32][2], int m_base, int tile_n, int m0, int n0, int r, int q,
-                                                  int wave, int tid) {
+template <int BM, bool W14 = false>
+__device__ __forceinline__ void fused_l1_epilogue(const FwdL1Epi& e, const FusedL1Pre<BM, W14>& p, float* __restrict__ smem,
+                                                  const f32x4 (&acc)[FusedL1Pre<BM, W14>::kTM][FusedL1Pre<BM, W14>::kTN], int m_base,
+                                                  int tile_n, int m0, int n0, int r, int q, int wave, int tid) {
   float* __restrict__ T = smem;
   float* __restrict__ L0 = smem + BM * kL1Ld;
-  constexpr int TM = BM / 32;
+  constexpr int TM = FusedL1Pre<BM, W14>::kTM;
 #pragma unroll
-  for (int t = 0; t < 2; ++t) {
+  for (int t = 0; t < FusedL1Pre<BM, W14>::kTN; ++t) {
     const int n_loc = n0 + 16 * t + r;
     const int colg = e.col(tile_n * 64 + n_loc);
     const float bv = p.bv[t], wl = p.wl[t];
@@ -1479,6 +1482,92 @@ __global__ __launch_bounds__(256) void ftm_forward_l1_planes_kernel(Mat ma, Mat 
   gemm_tile_bf<32, 64, true, FwdL1Epi, true>(smem, ma, mp, epi, M, N, 0, K, tiles_n, blockIdx.x, 0);
 }
 
+// The planes-fed forward with the table operand streamed from the plane buffer straight into the MFMA's operand registers.
+// The plane buffer already is the fragment image: block + plane * 16384 + bf_img(n, 4 kb + q) holds the 8 bf16 lane (r, q) feeds
+// one MFMA of 32-k block kb.  With the waves 1 x 4 (wave w: all 32 rows x columns 16 w .. 16 w + 15) no B fragment is shared
+// between waves, so B needs no LDS, no ds_write / ds_read and no barrier in the K loop; only the map -- shared by all four waves,
+// 8 KB of bf16 image per K tile -- is staged, all K tiles up front behind one barrier (hence at most kStreamKTiles K tiles).
+// One wave per SIMD has the whole register file: kStreamDepth K tiles of plane loads (12 x 16 bytes per lane and tile) are
+// requested ahead, a tile's registers refilled as soon as it is contracted.  Every load is unconditional and in-window (a K tile
+// past the last is the last one again, never contracted), so that the waits in front of the MFMAs count down.  Depth 3 was
+// measured against 4 and against every tile up front (7): forward 11.65 / 11.92 / 12.45 us at the CIFAR batch-512 shape -- a wave
+// has at most 64 loads outstanding, so a deeper request only delays the map's staging and the first MFMA behind its own issue.
+// Per output element the sum is gemm_tile_bf's in its order (K tiles, then kb ascending, planes 2, 1, 0; the same lane -> k
+// assignment), so `out` and the slabs keep their bits.
+constexpr int kStreamKTiles = 7, kStreamDepth = 3;
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void ftm_forward_l1_stream_kernel(Mat ma, Mat mp, FwdL1Epi epi,
+                                                                                                            int K, int tiles_n) {
+  constexpr int D = kStreamDepth;
+  static_assert(D >= 1 && D <= kStreamKTiles, "K tiles of plane loads requested ahead");
+  constexpr int kA = 32 * kBfK * 2, kEpi = 2 * 32 * kL1Ld * 4;  // one A image; the epilogue's two tiles alias the images
+  static_assert(kStreamKTiles * kA >= kEpi, "the epilogue's LDS aliases the A images");
+  __shared__ __attribute__((aligned(16))) unsigned char smem[kStreamKTiles * kA];
+  const __amdgpu_buffer_rsrc_t rsa = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(ma.p), 0, ma.bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsb = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(mp.p), 0, mp.bytes, 0x00020000);
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int r = lane & 15, q = lane >> 4;
+  const int tile = blockIdx.x, tile_n = tile % tiles_n, tile_m = tile / tiles_n;
+  const int m_base = tile_m * 32, n0 = 16 * wave;
+  const int ktiles = (K + kBfK - 1) / kBfK;  // 1 .. kStreamKTiles
+  // A: one 16-byte load per thread and K tile (gemm_tile_bf's akc_row / akc_grp), all tiles requested first.  The loads of the
+  // K tiles past the last one (kt >= ktiles) are issued too, so that the load count is the same for every shape: they read the
+  // next map row's bytes or, past the window of the buffer resource, zeros; their images are staged into LDS that the K loop
+  // never reads (the contraction of those tiles is skipped).
+  const int a_row = ((tid >> 4) << 1) | (tid & 1), a_grp = (tid >> 1) & 7;
+  u32x4 ra[kStreamKTiles];
+#pragma unroll
+  for (int kt = 0; kt < kStreamKTiles; ++kt)
+    ra[kt] = __builtin_amdgcn_raw_buffer_load_b128(rsa, (m_base + a_row) * ma.ld + kt * kBfK + a_grp * 16, 0, 0);
+  // then what the epilogue reads (queued behind plane loads it costs 0.9 us: loads return in order)
+  FusedL1Pre<32, true> l1pre;
+  fused_l1_prefetch<32, true>(epi, l1pre, m_base, tile_n, 0, n0, r, q, wave);
+  __builtin_amdgcn_sched_barrier(0);
+  // B: this lane's fragment of (K tile, kb, plane) -- the lane offset depends on kb only, block and plane are scalar
+  int b_off[kBfK / 32];
+#pragma unroll
+  for (int kb = 0; kb < kBfK / 32; ++kb) b_off[kb] = bf_img(n0 + r, 4 * kb + q);
+  u32x4 rb[D][kBfK / 32][3];
+  auto fetch = [&](int kt, u32x4 (&R)[kBfK / 32][3]) {
+    const int blk = (tile_n * ktiles + (kt < ktiles ? kt : ktiles - 1)) * kFwdPlaneBlock;
+#pragma unroll
+    for (int kb = 0; kb < kBfK / 32; ++kb)
+#pragma unroll
+      for (int pnum = 2; pnum >= 0; --pnum) R[kb][pnum] = __builtin_amdgcn_raw_buffer_load_b128(rsb, b_off[kb], blk + pnum * (64 * kBfK * 2), 0);
+  };
+#pragma unroll
+  for (int kt = 0; kt < D; ++kt) fetch(kt, rb[kt]);
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int kt = 0; kt < kStreamKTiles; ++kt) stage_map_k(smem + kt * kA, BfImg<kBfK>{}, a_row, a_grp * 2, ra[kt]);
+  __syncthreads();
+  f32x4 acc[2][1];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) acc[i][0] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int kt = 0; kt < kStreamKTiles; ++kt) {
+    u32x4 (&R)[kBfK / 32][3] = rb[kt % D];
+    if (kt < ktiles) {
+      const unsigned char* __restrict__ As = smem + kt * kA;
+#pragma unroll
+      for (int kb = 0; kb < kBfK / 32; ++kb) {
+        const int c = kb * 4 + q;
+        bf16x8 a[2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) a[i] = *reinterpret_cast<const bf16x8*>(As + bf_img(16 * i + r, c));
+#pragma unroll
+        for (int pnum = 2; pnum >= 0; --pnum)
+#pragma unroll
+          for (int i = 0; i < 2; ++i)
+            acc[i][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i], __builtin_bit_cast(bf16x8, R[kb][pnum]), acc[i][0], 0, 0, 0);
+      }
+    }
+    if (kt + D < kStreamKTiles) fetch(kt + D, R);  // (compile-time condition: the fetch itself is unconditional)
+  }
+  __syncthreads();  // the epilogue's tiles alias the A images
+  fused_l1_epilogue<32, true>(epi, l1pre, reinterpret_cast<float*>(smem), acc, m_base, tile_n, 0, n0, r, q, wave, tid);
+}
+
 // ga.n != NULL: the launch has one workgroup more than tiles (grid.x - 1 tiles); it groups the batch by layer-stack bucket
 // (bucket_group.h) -- work that only needs the binarise kernel's counts, like this product, and would otherwise be a launch
 // of its own between them.
@@ -2483,7 +2572,12 @@ extern "C" int nnue_ftm_forward_l1_planes(const uint8_t* bits, const float* sink
   const int direct = (F - 1 < P) ? F - 1 : P, tiles_n = L1 / 64;
   const Mat ma{bits, (unsigned)((size_t)B * P), P, kIntMax, kIntMax}, mp{planes, (unsigned)need, L1, kIntMax, kIntMax};
   const FwdL1Epi epi{bias, weight + (size_t)(F - 1) * L1, sink, out, w1, part, B, L1, L2, L1 / 2};
-  hipLaunchKernelGGL(ftm_forward_l1_planes_kernel, dim3((unsigned)(((B + 31) / 32) * tiles_n)), dim3(256), 0, st, ma, mp, epi, B, L1, direct, tiles_n);
+  const dim3 grid((unsigned)(((B + 31) / 32) * tiles_n));
+  // up to kStreamKTiles K tiles the table operand is streamed into the MFMA's registers (NNUE_FTM_FWD_STREAM=0, read per call:
+  // the LDS-staged kernel, which deeper shapes keep)
+  const int streamed = env_int("NNUE_FTM_FWD_STREAM", 1) != 0 && direct <= kStreamKTiles * kBfK;
+  if (streamed) hipLaunchKernelGGL(ftm_forward_l1_stream_kernel, grid, dim3(256), 0, st, ma, mp, epi, direct, tiles_n);
+  else hipLaunchKernelGGL(ftm_forward_l1_planes_kernel, grid, dim3(256), 0, st, ma, mp, epi, B, L1, direct, tiles_n);
   return nnue_launch_status("nnue_ftm_forward_l1_planes");
 }
 
