@@ -816,6 +816,54 @@ int nnue_load_batch(const uint8_t* images_u8, const int64_t* labels_all, const i
                     int B, int H, int W, int64_t N, int augment, uint64_t seed, uint64_t step,
                     float* out, int64_t* labels_out, nnue_stream_t stream);
 
+/* nnue_load_batch with a policy and a resize: the reference's augmentation_strength (data/datasets.py:173-195 "light",
+ * :301-350 "medium", the default) and the A.Resize(target_size) that closes every transform list (data/datasets.py:357-361),
+ * then Normalize + ToTensorV2 (:364-371).  out is [B,3,Ho,Wo]; one launch, no scratch.  policy: 0 = none (resize only),
+ * 1 = light, 2 = medium; anything else is NNUE_E_ARG.  H*W and Ho*Wo below 2^24, at most 65535 tiles of 16 x 16 output
+ * pixels (NNUE_E_SHAPE).  nnue_load_batch_params_count() = P, the floats per image of params_out.
+ *
+ * Draws: base = mix64(seed ^ mix64(index*C + step)), draw k = u01(mix64(base + k)) as nnue_load_batch.  Policy 1 uses draws
+ * 1..7 exactly as nnue_load_batch does (sizes taken from Ho x Wo) and its arithmetic (floor to uint8 levels included): at
+ * Ho == H, Wo == W it equals nnue_load_batch(augment = 1) bit for bit, and policy 0 equals augment = 0.  Policy 2 uses draws
+ * 16..43; per-pixel noise hashes mix64(base + 2^32 + (oy*Wo + ox)*3 + c).
+ *
+ * Geometry: the fired geometric stages and the resize compose into ONE map from output pixel (ox, oy) to source pixel
+ *   sx = m0*ox + m1*oy + m2 ; sy = m3*ox + m4*oy + m5
+ * and the source is sampled once, bilinearly.  From the output side: Affine^-1, Rotate^-1, Rot90^-1, Flip^-1, then the
+ * resize map s = (o + 0.5)*(src/dst) - 0.5.  With c = ((Wo-1)/2, (Ho-1)/2) and R(t) = [[cos t, -sin t], [sin t, cos t]]:
+ *   Affine^-1: p -> c + R(-angle)(p - c - (tx, ty)) / scale      Rotate^-1: p -> c + R(angle)(p - c)
+ *   Rot90^-1 (k quarter turns, on the Ho x Wo rectangle through u = (x+0.5)/Wo, v = (y+0.5)/Ho):
+ *     k = 1: (u, v) -> (1 - v, u) ; k = 2: (1 - u, 1 - v) ; k = 3: (v, 1 - u)            Flip^-1: x -> Wo - 1 - x
+ * If Rotate or Affine fired, a tap outside the source reads 0 (albumentations' constant fill); otherwise the sample
+ * coordinate is clamped into the image (cv2.resize).  albumentations resamples once per stage and rounds to uint8 between
+ * stages; this samples once and keeps float levels in [0, 255] throughout -- stated differences.
+ *
+ * Policy 2, in this order (probabilities and ranges of data/datasets.py:303-339):
+ *   1 HorizontalFlip p=.5   2 RandomRotate90 p=.5, k uniform in 0..3   3 Rotate p=.3, +-15 deg
+ *   4 Affine p=.3: translate +-10 % of each output side, isotropic scale .9..1.1, rotate +-15 deg
+ *   5 RandomBrightnessContrast p=.3: clamp(v*alpha + beta*255), alpha-1 and beta in +-.2
+ *   6 HueSaturationValue p=.3 in float HSV (H degrees, S and V in [0,1], H = 0 where max == min): H + 2*shift (+-10, wraps),
+ *     S + shift/255 (+-15, clamped), V + shift/255 (+-10, clamped)
+ *   7 OneOf blur p=.2, kind uniform: 0 box 3x3, 1 Gaussian 3x3 with sigma in [.5, 3] (weights exp(-d^2/(2 sigma^2)),
+ *     normalised, separable), 2 motion: the 3-tap line through the centre in direction 0 '-', 1 '|', 2 '\', 3 '/'; the
+ *     neighbours are stage 1-6 values, reflect-101 at the OUTPUT image's borders
+ *   8 GaussNoise p=.2: sigma in [.01, .05]*255, Box-Muller z = sqrt(-2 ln u1) cos(2 pi u2) per pixel and channel, clamped
+ *   9 CoarseDropout p=.3: one hole, each side uniform in [.05, .15] of the output side (>= 1 pixel), uniform position, fill 0
+ * Omitted from the medium list (each p <= .2): RandomShadow, RandomFog, GridDistortion, ElasticTransform, CLAHE, ColorJitter,
+ * Posterize, Equalize.  "heavy" (medium plus a second pass of stronger stages) is not built.
+ *
+ * params_out (may be NULL) receives per image what was drawn, P = 32 floats (values are recorded whether or not their stage
+ * fired; policy 0/1 leave the unused ones at their neutral value):
+ *   [0] stage flags: 1 flip, 2 rot90, 4 rotate, 8 affine, 16 brightness/contrast, 32 HSV, 64 blur, 128 noise, 256 dropout
+ *   [1] k   [2] Rotate angle (deg)   [3] Affine angle (deg)   [4] Affine scale   [5] tx   [6] ty (output pixels)
+ *   [7..12] m0..m5, the composed map as the kernel used it   [13] alpha   [14] beta
+ *   [15] hue shift   [16] saturation shift   [17] value shift   [18] blur kind   [19] Gaussian sigma   [20] motion direction
+ *   [21] noise sigma (levels)   [22] hole y0   [23] hole x0   [24] hole height   [25] hole width   [26..31] 0 */
+int nnue_load_batch_policy(const uint8_t* images_u8, const int64_t* labels_all, const int64_t* indices,
+                           int B, int H, int W, int64_t N, int Ho, int Wo, int policy, uint64_t seed, uint64_t step,
+                           float* out, int64_t* labels_out, float* params_out, nnue_stream_t stream);
+int nnue_load_batch_params_count(void);
+
 /* clip_grad_norm_ + torch.optim.Adam(lr, weight_decay) on flat buffers -- the optimizer create_optimizer picks
  * when optimizer_type != "sgd" (train.py:363-366, :465-470; torch defaults betas (0.9, 0.999), eps 1e-8, L2
  * weight decay added to the gradient, no amsgrad):

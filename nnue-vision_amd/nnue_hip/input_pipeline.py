@@ -4,13 +4,23 @@ The reference feeds training through torchvision + albumentations + DataLoader w
 (data/datasets.py:173-372, data/loaders.py:95-120): per image, on the CPU.  At the step rates this build
 reaches (a CIFAR-10 epoch is ~17 ms of GPU time) that path cannot keep up by orders of magnitude, so the
 dataset (50 000 x 32 x 32 x 3 uint8 = 154 MB for CIFAR) lives in HBM and one kernel per batch gathers,
-augments ("light" policy), normalises and transposes it straight into the trainer's input slot.
+augments, resizes, normalises and transposes it straight into the trainer's input slot.
+
+``augment`` selects the reference's ``augmentation_strength`` (data/datasets.py:173-195 "light", :301-350 "medium"):
+``False``, ``True`` / ``"light"`` or ``"medium"``; ``out_hw`` is the ``A.Resize(target_size)`` that closes every reference
+transform list (data/datasets.py:357-361).  The medium policy is HorizontalFlip, RandomRotate90, Rotate, Affine,
+RandomBrightnessContrast, HueSaturationValue, OneOf(Blur, GaussianBlur, MotionBlur), GaussNoise and CoarseDropout with
+the reference's probabilities and ranges; the geometric stages and the resize are one bilinear sample per image and
+values stay float between stages (include/nnue_hip.h defines every stage).  Omitted from the medium list (each
+p <= .2): RandomShadow, RandomFog, GridDistortion, ElasticTransform, CLAHE, ColorJitter, Posterize, Equalize.
+``"heavy"`` (medium plus a second pass of stronger stages) is not built and raises ``ValueError``.
 
 Datasets themselves (download / decode) are out of scope: construct ``GpuImageDataset`` from any uint8
 ``[N,H,W,3]`` array and integer labels.
 """
 from __future__ import annotations
 
+import numbers
 from typing import Iterator, Optional, Tuple
 
 import torch
@@ -18,9 +28,36 @@ import torch
 from . import lib
 
 
+def resolve_augment(augment) -> int:
+    """``augment=`` of GpuImageDataset -> the policy number of nnue_load_batch_policy (0 none, 1 light, 2 medium)."""
+    if augment is None or augment is False:
+        return 0
+    if augment is True:
+        return 1
+    if isinstance(augment, str):
+        if augment in ("light", "medium"):
+            return lib.LOAD_POLICIES[augment]
+        if augment == "heavy":
+            raise ValueError('augment="heavy" (medium plus a second pass of stronger stages, data/datasets.py:218-300) is not '
+                             'built: use "medium"')
+    raise ValueError(f'augment: expected False, True, "light" or "medium", got {augment!r}')
+
+
+def resolve_out_hw(out_hw) -> Optional[Tuple[int, int]]:
+    """``out_hw=`` of GpuImageDataset: None (the stored size), one side (square) or (height, width)."""
+    if out_hw is None:
+        return None
+    hw = (out_hw, out_hw) if isinstance(out_hw, numbers.Real) else tuple(out_hw)
+    if len(hw) != 2 or any(int(v) != v or int(v) <= 0 for v in hw):
+        raise ValueError(f"out_hw: expected a positive (height, width), got {out_hw!r}")
+    return int(hw[0]), int(hw[1])
+
+
 class GpuImageDataset:
-    def __init__(self, images_u8, labels, device=None, augment: bool = False, seed: int = 0,
-                 num_classes: Optional[int] = None):
+    def __init__(self, images_u8, labels, device=None, augment=False, seed: int = 0,
+                 num_classes: Optional[int] = None, out_hw=None):
+        resolve_augment(augment)  # refuse "heavy" and unknown strings here, not at the first batch
+        self.out_hw = resolve_out_hw(out_hw)
         device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         images_u8 = torch.as_tensor(images_u8)
         if images_u8.dtype != torch.uint8 or images_u8.dim() != 4 or images_u8.shape[3] != 3:
@@ -46,11 +83,22 @@ class GpuImageDataset:
     def image_hw(self) -> Tuple[int, int]:
         return int(self.images.shape[1]), int(self.images.shape[2])
 
-    def batch(self, indices: torch.Tensor, out: Optional[torch.Tensor] = None, labels_out: Optional[torch.Tensor] = None):
-        """One normalised (and, if enabled, augmented) batch for the given dataset indices (device int64)."""
+    @property
+    def output_hw(self) -> Tuple[int, int]:
+        """The size of the batches (the trainer's ``hw``): ``out_hw`` if given, else the stored size."""
+        return self.image_hw if self.out_hw is None else self.out_hw
+
+    def batch(self, indices: torch.Tensor, out: Optional[torch.Tensor] = None, labels_out: Optional[torch.Tensor] = None,
+              params_out: Optional[torch.Tensor] = None):
+        """One normalised (and, if enabled, augmented and resized) batch for the given dataset indices (device int64).
+        ``params_out`` (float32 [b, lib.load_batch_params_count()]) receives what was drawn for each image."""
         self.step += 1
-        return lib.load_batch(self.images, self.labels, indices.to(self.images.device), self.augment, self.seed, self.step,
-                              out=out, labels_out=labels_out)
+        policy = resolve_augment(self.augment)
+        if policy <= 1 and self.output_hw == self.image_hw and params_out is None:
+            return lib.load_batch(self.images, self.labels, indices.to(self.images.device), bool(policy), self.seed, self.step,
+                                  out=out, labels_out=labels_out)
+        return lib.load_batch_policy(self.images, self.labels, indices.to(self.images.device), policy, self.seed, self.step,
+                                     out_hw=self.output_hw, out=out, labels_out=labels_out, params_out=params_out)
 
     def loader(self, batch_size: int, shuffle: bool = False, drop_last: bool = False,
                generator: Optional[torch.Generator] = None) -> "GpuLoader":
@@ -123,3 +171,24 @@ def train_epoch(trainer, loader: GpuLoader):
             total += trainer.step(images, labels, slot=s, global_count=count)
         i += 1
     return total, n
+
+
+def augment_from_config(config, train: bool):
+    """(augment, out_hw) as train.py:278-287 passes them to create_data_loaders: ``use_augmentation``,
+    ``augmentation_strength`` (default "medium", data/loaders.py:23) and the model's ``input_size``; validation and test
+    loaders get no augmentation (data/loaders.py:95-120)."""
+    augment = False
+    if train and bool(getattr(config, "use_augmentation", True)):
+        augment = getattr(config, "augmentation_strength", "medium")
+    size = getattr(config, "input_size", None)
+    if isinstance(size, (tuple, list)):
+        size = tuple(size[-2:])  # datasets.py keeps the last two entries of a (C, H, W) target
+    return augment, resolve_out_hw(size)
+
+
+def dataset_from_config(config, images_u8, labels, train: bool, device=None, seed: int = 0) -> GpuImageDataset:
+    """A GpuImageDataset set up from a training config the way train.py:278-287 sets up the reference's loaders."""
+    augment, out_hw = augment_from_config(config, train)
+    num_classes = getattr(config, "num_classes", None)
+    return GpuImageDataset(images_u8, labels, device=device, augment=augment, seed=seed,
+                           num_classes=int(num_classes) if num_classes is not None else None, out_hw=out_hw)

@@ -134,6 +134,9 @@ SIGNATURES = {
     "nnue_confusion_accumulate": (_c_int, [_c_p, _c_p, _c_int, _c_int, _c_p, _c_p]),
     "nnue_load_batch": (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_i64, _c_int, ctypes.c_uint64, ctypes.c_uint64,
                                  _c_p, _c_p, _c_p]),
+    "nnue_load_batch_policy": (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_i64, _c_int, _c_int, _c_int, ctypes.c_uint64,
+                                        ctypes.c_uint64, _c_p, _c_p, _c_p, _c_p]),
+    "nnue_load_batch_params_count": (_c_int, []),
     "nnue_engine_scratch": (_c_i64, [_c_p, _c_int]),
     "nnue_engine_evaluate_logits": (_c_int, [_c_p, _c_p, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p, _c_i64, _c_p]),
     "nnue_engine_stream_state_bytes": (_c_i64, [_c_p, _c_int]),
@@ -1406,3 +1409,39 @@ def load_batch(images_u8: torch.Tensor, labels_all: torch.Tensor, indices: torch
     _call("nnue_load_batch", images_u8.data_ptr(), labels_all.data_ptr(), indices.data_ptr(), b, h, w, n, int(bool(augment)),
           int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1), out.data_ptr(), labels_out.data_ptr(), _stream(images_u8))
     return out, labels_out
+
+
+LOAD_POLICIES = {"none": 0, "light": 1, "medium": 2}  # nnue_load_batch_policy's policy argument
+
+
+def load_batch_policy(images_u8: torch.Tensor, labels_all: torch.Tensor, indices: torch.Tensor, policy: int, seed: int, step: int,
+                      out_hw: Optional[Tuple[int, int]] = None, out: Optional[torch.Tensor] = None,
+                      labels_out: Optional[torch.Tensor] = None, params_out: Optional[torch.Tensor] = None):
+    """uint8 [N,H,W,3] dataset + indices [B] -> augmented (policy 0 none / 1 light / 2 medium), resized to out_hw and normalised
+    float32 [B,3,Ho,Wo] and labels [B]; params_out (float32 [B, load_batch_params_count()]) receives what was drawn."""
+    images_u8 = _need(images_u8, torch.uint8, "dataset images")
+    if images_u8.dim() != 4 or images_u8.shape[3] != 3:
+        raise ValueError(f"dataset images: expected uint8 [N,H,W,3], got {tuple(images_u8.shape)}")
+    n, h, w, _ = images_u8.shape
+    ho, wo = (h, w) if out_hw is None else (int(out_hw[0]), int(out_hw[1]))
+    labels_all = _need(labels_all, torch.int64, "dataset labels", (n,))
+    indices = _need(indices, torch.int64, "indices")
+    b = indices.numel()
+    if out is None:
+        out = torch.empty((b, 3, max(ho, 0), max(wo, 0)), dtype=torch.float32, device=images_u8.device)
+    elif tuple(out.shape) != (b, 3, ho, wo) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("load_batch_policy: out must be a contiguous float32 [B,3,Ho,Wo] tensor")
+    if labels_out is None:
+        labels_out = torch.empty((b,), dtype=torch.int64, device=images_u8.device)
+    if params_out is not None:
+        params_out = _need(params_out, torch.float32, "params_out", (b, load_batch_params_count()))
+        if not params_out.is_contiguous():
+            raise ValueError("load_batch_policy: params_out must be contiguous (it is written in place)")
+    _call("nnue_load_batch_policy", images_u8.data_ptr(), labels_all.data_ptr(), indices.data_ptr(), b, h, w, n, ho, wo, int(policy),
+          int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1), out.data_ptr(), labels_out.data_ptr(), _ptr(params_out),
+          _stream(images_u8))
+    return out, labels_out
+
+
+def load_batch_params_count() -> int:
+    return int(load().nnue_load_batch_params_count())

@@ -93,7 +93,7 @@ def run_training(config, train_loader: Iterable, val_loader: Iterable, test_load
     model = build_model(config, device) if model is None else model.to(device)
     in_place = isinstance(train_loader, GpuLoader)  # GPU-resident dataset: batches are written straight into the input slots
     if in_place:
-        hw = train_loader.dataset.image_hw
+        hw = train_loader.dataset.output_hw  # the stored size unless the dataset resizes
     else:
         first_images, _ = next(iter(train_loader))
         hw = tuple(first_images.shape[2:])
