@@ -680,6 +680,37 @@ int nnue_engine_stream_step_stacks(const nnue_engine_model* m, const nnue_engine
                                    int64_t state_bytes, float* logits, float* density, int32_t* changed, int32_t* stack_out,
                                    void* scratch, int64_t scratch_bytes, nnue_stream_t stream);
 
+/* NNUEEvaluator::update_features(added, removed) (engine/src/nnue_engine.cpp:818-821, which runs
+ * FeatureTransformer::update_accumulator, :257-267) for S streams at once on the state of nnue_engine_stream_step, followed by
+ * the rest of evaluate_incremental (:739-786): the caller names the features that turned on and off instead of handing over the
+ * whole new set, so a step costs O(changes), and gets the logits its consumer reads (evaluate.py:143-176).
+ * Lists: CSR in device memory, int32 -- stream b adds added[added_off[b] .. added_off[b+1]) and removes
+ * removed[removed_off[b] .. removed_off[b+1]); n_added, n_removed are the lengths of the id buffers.  Every range is clipped to
+ * [0, n] and a reversed range is empty, so no offset can make the kernel read outside an id buffer.  A list with n == 0 may pass
+ * NULL for both of its pointers.
+ * Set semantics -- the stored set stays the true set and the accumulator bias + sum of rows(set) mod 2^16:
+ *     new = (old \ removed) + added;
+ * an id outside [0, num_features) is ignored (add_feature / remove_feature, :233-234), a removed id that is off and an added id
+ * that is on are ignored, a duplicate within a list counts once, an id in both lists ends up on (it is removed first and added
+ * again, which on a feature that was on nets to nothing mod 2^16).  On well-formed input -- added disjoint from the old set,
+ * removed a subset of it, no duplicates -- this is update_accumulator bit for bit.  A stream that is not valid (fresh, or its
+ * flag cleared) starts from the empty set and the bias and ignores `removed`: refresh_accumulator(added) (:806-816); the step
+ * sets its flag.  rebuild != 0, for all streams: after the delta went into the bits, every accumulator is re-formed from the
+ * bias and the rows of its new set and the stored sums are ignored -- for a table that changed under sets that are still right.
+ * save_accumulator / restore_accumulator (:792-804) need no call: a copy of `state` is the whole stream.
+ * st == NULL: m's own stack; else the stack of every stream is chosen as nnue_engine_stream_step_stacks chooses it, from the
+ * new set's size (stack_in, stack_out as there; stack_out is required iff st).  Outputs as nnue_engine_stream_step: logits
+ * [S][classes], density [S] = |new| / num_features, changed [S] = |new xor old| (|new| for a stream that was not valid).
+ * The state keeps its layout; this call, nnue_engine_stream_step and nnue_engine_stream_step_stacks may follow one another in
+ * any order on one buffer.  Checks and codes as those two; NNUE_E_ARG also for a negative n and for n > 0 with a NULL id or
+ * offset pointer.  Every refusal comes before anything is launched. */
+int nnue_engine_stream_update(const nnue_engine_model* m, const nnue_engine_stacks* st /* NULL: m's own stack */,
+                              const int32_t* added, const int32_t* added_off, int64_t n_added,
+                              const int32_t* removed, const int32_t* removed_off, int64_t n_removed,
+                              int S, int rebuild, const int32_t* stack_in, void* state, int64_t state_bytes,
+                              float* logits, float* density, int32_t* changed, int32_t* stack_out,
+                              nnue_stream_t stream);
+
 /* ---- the engine's integer inference as a matrix product (int8 matrix unit) --------------------------------------
  *
  * The accumulate step of the calls above, acc[b] = bias + sum of the table rows of b's active features taken mod 2^16

@@ -349,6 +349,187 @@ __global__ __launch_bounds__(256) void engine_stream_kernel(const int8_t* __rest
               logits + (size_t)b * C);
 }
 
+// Ids of one phase that the row walk of engine_stream_update_kernel takes per round (LDS work list, int32 each).
+constexpr int kUpdateChunk = 1024;
+
+// Stream b's range of a CSR list, clipped to the id buffer: [off[b], off[b + 1]) cut to [0, n], a reversed range = empty.  A
+// list with n == 0 is never dereferenced (its pointers may be null).
+__device__ __forceinline__ void update_range(const int32_t* __restrict__ off, int n, int b, int& lo, int& hi) {
+  lo = hi = 0;
+  if (n <= 0) return;
+  lo = off[b];
+  hi = off[b + 1];
+  lo = lo < 0 ? 0 : (lo > n ? n : lo);
+  hi = hi < 0 ? 0 : (hi > n ? n : hi);
+  if (hi < lo) hi = lo;
+}
+
+// One phase of the update: ids[lo, hi) are cleared from (kAdd == false) or set in (kAdd == true) the stream's bit words in LDS.
+// A 64-bit LDS atomic returns the word as it was, so of all threads that name one id -- duplicates included -- exactly the one
+// that flipped its bit appends the id to the work list; ids outside [0, F) and ids whose bit already has the wanted value flip
+// nothing.  After a barrier all 256 threads walk the list and subtract or add those table rows in their own columns (walk ==
+// false: the bits only, the caller re-forms the sums afterwards).  Four rows per trip, padded with row 0 times 0, so that the
+// loads of a trip do not wait for one another.  The list's counter only grows: `done` is its value before this round, known to
+// every thread, so a round needs no reset and two barriers -- appends | walk | next round's appends.
+template <bool kAdd>
+__device__ __forceinline__ void update_phase(const int32_t* __restrict__ ids, int lo, int hi, int F, int L1, bool walk,
+                                             const int16_t* __restrict__ ft_w, unsigned long long* cur, int32_t* work,
+                                             unsigned* work_n, unsigned& done, int32_t (&acc)[kMaxColsPerThread]) {
+  const int tid = threadIdx.x;
+  for (int base = lo, len; base < hi; base += len) {  // lo, hi are uniform over the workgroup; no sum here can pass hi <= 2^31 - 1
+    len = hi - base < kUpdateChunk ? hi - base : kUpdateChunk;
+    for (int i = tid; i < len; i += 256) {
+      const int id = ids[(size_t)base + i];
+      if ((unsigned)id >= (unsigned)F) continue;
+      const unsigned long long bit = 1ull << (id & 63);
+      const unsigned long long was = kAdd ? atomicOr(&cur[id >> 6], bit) : atomicAnd(&cur[id >> 6], ~bit);
+      if (((was & bit) != 0) != kAdd) work[atomicAdd(work_n, 1u) - done] = id;  // at most len <= kUpdateChunk appends
+    }
+    __syncthreads();
+    const int n = (int)(*work_n - done);  // unsigned: the counter may wrap, the difference does not
+    done += (unsigned)n;
+    if (walk) {
+      for (int i = 0; i < n; i += 4) {
+        const int16_t* __restrict__ wr[4];
+        int32_t mul[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const bool in = i + u < n;
+          wr[u] = ft_w + (size_t)(in ? work[i + u] : 0) * L1;
+          mul[u] = in ? (kAdd ? 1 : -1) : 0;
+        }
+#pragma unroll
+        for (int j = 0; j < kMaxColsPerThread; ++j) {
+          const int col = tid + 256 * j;
+          if (col < L1) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) acc[j] += mul[u] * (int32_t)wr[u][col];
+          }
+        }
+      }
+    }
+    __syncthreads();  // the walk has read the list and its counter before the next round appends
+  }
+}
+
+// FeatureTransformer::update_accumulator (nnue_engine.cpp:257-267; NNUEEvaluator::update_features, :818-821) for S independent
+// streams from two CSR id lists, one workgroup per stream, on the state of engine_stream_kernel -- with set semantics: the stored
+// set stays the true set, new = (old \ removed) + added, and the accumulator stays bias + sum of rows(set) mod 2^16.  Ids outside
+// [0, F) are ignored (add_feature / remove_feature, :233-234), a removed id that is off and an added id that is on are ignored,
+// a duplicate counts once; an id in both lists ends up on (removed first, then added: on a feature that was on the two rows
+// cancel mod 2^16).  On lists without such entries this is update_accumulator bit for bit.  A stream that is not valid starts from
+// the empty set and the bias and ignores `removed`: refresh_accumulator(added) (:806-816).  rebuild != 0 (all streams): the
+// delta goes into the bits only and every accumulator is re-formed from the bias and the rows of its new set, the stored sums
+// being ignored (they belong to another table).  Then the clipped ReLU and engine_tail, as engine_stream_kernel.
+// Read/write hazard on the bit words: the stream's CURRENT slot is updated in place and the parity stays.  A workgroup touches
+// only its own stream's words, and within it word c belongs to thread c % 256 alone: that thread copies it to LDS at the start,
+// and at the end reads it again (the old set, for `changed`) and only then stores the new word over it, in program order.  All
+// other traffic on the words is LDS atomics between barriers.  No thread reads a global word another thread writes.
+// dynamic LDS: ft [L1] i32 | pair [L1] i32 | h1 [L2] i32 | h2 [L3] i32 | counts [8] i32 | work_n [2] i32 | work [kUpdateChunk]
+// i32 | (8-byte aligned) cur [W64] u64
+template <class Sel>
+__global__ __launch_bounds__(256) void engine_stream_update_kernel(
+    const int32_t* __restrict__ added, const int32_t* __restrict__ added_off, int n_added, const int32_t* __restrict__ removed,
+    const int32_t* __restrict__ removed_off, int n_removed, int rebuild, int F, int S, const int16_t* __restrict__ ft_w,
+    const int32_t* __restrict__ ft_b, int quantized_one, const int8_t* __restrict__ l1_w, const int32_t* __restrict__ l1_b,
+    float l1_scale, const int8_t* __restrict__ l2_w, const int32_t* __restrict__ l2_b, int l2_scale, const int8_t* __restrict__ out_w,
+    const int32_t* __restrict__ out_b, float out_scale, int L1, int L2, int L3, int C, uint8_t* __restrict__ state,
+    float* __restrict__ logits, float* __restrict__ density, int32_t* __restrict__ changed, Sel sel) {
+  extern __shared__ int32_t lds[];
+  int32_t* ft = lds;
+  int32_t* pair = ft + L1;
+  int32_t* h1 = pair + L1;
+  int32_t* h2 = h1 + L2;
+  int32_t* counts = h2 + L3;  // [wave] new, [4 + wave] difference
+  unsigned* work_n = reinterpret_cast<unsigned*>(counts + 8);
+  int32_t* work = counts + 10;
+  const int W64 = (F + 63) / 64;
+  unsigned long long* cur = reinterpret_cast<unsigned long long*>(lds + ((2 * L1 + L2 + L3 + 10 + kUpdateChunk + 1) & ~1));
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+
+  const StreamLayout lay = stream_layout(S, F, L1);
+  int32_t* __restrict__ valid = reinterpret_cast<int32_t*>(state);
+  const int32_t* __restrict__ parity = reinterpret_cast<const int32_t*>(state + lay.parity);
+  int16_t* __restrict__ accs = reinterpret_cast<int16_t*>(state + lay.acc) + (size_t)b * L1;
+  const bool was_valid = valid[b] != 0;
+  unsigned long long* words = reinterpret_cast<unsigned long long*>(state + lay.bits) + ((size_t)(parity[b] & 1) * S + b) * W64;
+
+  for (int c = tid; c < W64; c += 256) cur[c] = was_valid ? words[c] : 0ull;
+  if (tid == 0) *work_n = 0;
+  const bool walk = rebuild == 0;
+  int32_t acc[kMaxColsPerThread];
+#pragma unroll
+  for (int j = 0; j < kMaxColsPerThread; ++j) {
+    const int col = tid + 256 * j;
+    acc[j] = col < L1 ? (was_valid && walk ? (int32_t)accs[col] : (int32_t)(int16_t)ft_b[col]) : 0;
+  }
+  __syncthreads();
+
+  // removed before added, with the phases' barriers between them: an id in both lists ends up on
+  int lo, hi;
+  unsigned done = 0;
+  if (was_valid) {
+    update_range(removed_off, n_removed, b, lo, hi);
+    update_phase<false>(removed, lo, hi, F, L1, walk, ft_w, cur, work, work_n, done, acc);
+  }
+  update_range(added_off, n_added, b, lo, hi);
+  update_phase<true>(added, lo, hi, F, L1, walk, ft_w, cur, work, work_n, done, acc);
+
+  if (!walk) {  // every wave walks the same words of the new set, as pass 2 of engine_stream_kernel on a refresh
+    for (int c = 0; c < W64; ++c) {
+      unsigned long long m = cur[c];
+      while (m) {
+        const int16_t* __restrict__ wr = ft_w + (size_t)(c * 64 + __builtin_ctzll(m)) * L1;
+        m &= m - 1;
+#pragma unroll
+        for (int j = 0; j < kMaxColsPerThread; ++j) {
+          const int col = tid + 256 * j;
+          if (col < L1) acc[j] += (int32_t)wr[col];
+        }
+      }
+    }
+  }
+
+  int n_new = 0, n_diff = 0;
+  for (int c = tid; c < W64; c += 256) {
+    const unsigned long long m = cur[c], o = was_valid ? words[c] : 0ull;
+    n_new += __popcll(m);
+    n_diff += __popcll(m ^ o);
+    if (!was_valid || m != o) words[c] = m;
+  }
+#pragma unroll
+  for (int sh = 32; sh >= 1; sh >>= 1) {
+    n_new += __shfl_xor(n_new, sh);
+    n_diff += __shfl_xor(n_diff, sh);
+  }
+  if (lane == 0) {
+    counts[wave] = n_new;
+    counts[4 + wave] = n_diff;
+  }
+#pragma unroll
+  for (int j = 0; j < kMaxColsPerThread; ++j) {
+    const int col = tid + 256 * j;
+    if (col < L1) {
+      const int16_t v = (int16_t)acc[j];  // int16 accumulator wraps
+      accs[col] = v;
+      ft[col] = clamp_i((int32_t)v, 0, quantized_one);
+    }
+  }
+  __syncthreads();
+  n_new = counts[0] + counts[1] + counts[2] + counts[3];
+  n_diff = counts[4] + counts[5] + counts[6] + counts[7];
+  if (tid == 0) {
+    density[b] = (float)n_new / (float)F;
+    changed[b] = was_valid ? n_diff : n_new;
+    valid[b] = 1;
+  }
+
+  if constexpr (Sel::kSelect)
+    engine_select_stack(sel, b, n_new, F, L1, L2, L3, C, l1_w, l1_b, l1_scale, l2_w, l2_b, l2_scale, out_w, out_b, out_scale);
+  engine_tail(ft, pair, h1, h2, l1_w, l1_b, l1_scale, l2_w, l2_b, l2_scale, out_w, out_b, out_scale, L1, L2, L3, C,
+              logits + (size_t)b * C);
+}
+
 // ---- whole batches on the int8 matrix unit --------------------------------------------------------------------------
 // The accumulate step of engine_stack_kernel as a matrix product: sums [B][L1] int32 = A [B][F] . table, with A the 0/1 byte map
 // of the active features and the int16 table as one int8 plane (every value fits a byte) or two (lo, hi: w == lo + 256 * hi
@@ -792,6 +973,53 @@ extern "C" int nnue_engine_stream_step_stacks(const nnue_engine_model* m, const 
                                               int32_t* stack_out, void* scratch, int64_t scratch_bytes, nnue_stream_t stream) {
   return engine_stream_step("nnue_engine_stream_step_stacks", m, true, st, images, active, S, H, W, stack_in, state, state_bytes, logits,
                             density, changed, stack_out, scratch, scratch_bytes, stream);
+}
+
+template <class Sel>
+static void engine_launch_stream_update(const nnue_engine_model* m, const EngineTailArgs& t, const int32_t* added,
+                                        const int32_t* added_off, int n_added, const int32_t* removed, const int32_t* removed_off,
+                                        int n_removed, int S, int rebuild, size_t lds, uint8_t* state, float* logits, float* density,
+                                        int32_t* changed, Sel sel, hipStream_t s) {
+  hipLaunchKernelGGL((engine_stream_update_kernel<Sel>), dim3(S), dim3(256), lds, s, added, added_off, n_added, removed, removed_off,
+                     n_removed, rebuild, m->num_features, S, m->ft_w, m->ft_b, (int)(int16_t)m->quantized_one, t.l1_w, t.l1_b,
+                     t.l1_scale, t.l2_w, t.l2_b, t.l2_scale, t.out_w, t.out_b, t.out_scale, m->l1, m->l2, m->l3, m->classes, state,
+                     logits, density, changed, sel);
+}
+
+extern "C" int nnue_engine_stream_update(const nnue_engine_model* m, const nnue_engine_stacks* st, const int32_t* added,
+                                         const int32_t* added_off, int64_t n_added, const int32_t* removed,
+                                         const int32_t* removed_off, int64_t n_removed, int S, int rebuild, const int32_t* stack_in,
+                                         void* state, int64_t state_bytes, float* logits, float* density, int32_t* changed,
+                                         int32_t* stack_out, nnue_stream_t stream) {
+  const char* fn = "nnue_engine_stream_update";
+  NNUE_REQUIRE(m && state && logits && density && changed, NNUE_E_ARG, "%s: null pointer", fn);
+  if (st)
+    if (int rc = engine_check_stacks(st, stack_out, fn)) return rc;
+  NNUE_REQUIRE(n_added >= 0 && n_removed >= 0, NNUE_E_ARG, "%s: n_added=%lld n_removed=%lld must not be negative", fn,
+               (long long)n_added, (long long)n_removed);
+  NNUE_REQUIRE((n_added == 0 || (added && added_off)) && (n_removed == 0 || (removed && removed_off)), NNUE_E_ARG,
+               "%s: a list with ids needs its id and offset pointers", fn);
+  NNUE_REQUIRE(nnue_aligned16(state), NNUE_E_ARG, "%s: state must be 16-byte aligned", fn);
+  NNUE_REQUIRE(engine_has_tensors(m, st), NNUE_E_ARG, "%s: model tensor missing", fn);
+  NNUE_REQUIRE(S > 0, NNUE_E_ARG, "%s: S=%d must be positive", fn, S);
+  if (int rc = engine_check_model(m, st, fn)) return rc;
+  const int F = m->num_features, L1 = m->l1, W64 = (F + 63) / 64;
+  const int64_t need = nnue_engine_stream_state_bytes(m, S);
+  NNUE_REQUIRE(state_bytes >= need, NNUE_E_SCRATCH, "%s: state %lld < %lld bytes", fn, (long long)state_bytes, (long long)need);
+  const size_t lds = (size_t)((2 * L1 + m->l2 + m->l3 + 10 + kUpdateChunk + 1) & ~1) * sizeof(int32_t) + (size_t)W64 * sizeof(uint64_t);
+  NNUE_REQUIRE(lds <= 64 * 1024, NNUE_E_SHAPE, "%s: layer and feature sizes need %zu bytes of LDS", fn, lds);
+  // the offsets are int32, so ids beyond 2^31 - 1 of a buffer are out of every range's reach
+  const int na = (int)(n_added > INT32_MAX ? INT32_MAX : n_added), nr = (int)(n_removed > INT32_MAX ? INT32_MAX : n_removed);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  uint8_t* sp = static_cast<uint8_t*>(state);
+  const EngineTailArgs t = engine_tail_args(m, st);
+  if (st)
+    engine_launch_stream_update(m, t, added, added_off, na, removed, removed_off, nr, S, rebuild != 0, lds, sp, logits, density, changed,
+                                engine_stack_sel(st, stack_in, stack_out), s);
+  else
+    engine_launch_stream_update(m, t, added, added_off, na, removed, removed_off, nr, S, rebuild != 0, lds, sp, logits, density, changed,
+                                NoStackSel{}, s);
+  return nnue_launch_status(fn);
 }
 
 // ---- the matrix form's entry points ---------------------------------------------------------------------------------

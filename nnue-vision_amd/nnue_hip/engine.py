@@ -5,7 +5,8 @@
 ``evaluate_logits(images)`` is ``NNUEEvaluator::evaluate_logits`` (nnue_engine.cpp:704-734) for a whole batch --
 bit-identical to the C++ engine (tests/golden/engine_cases.npz holds outputs of the real engine).
 ``stream(S)`` is ``NNUEEvaluator::evaluate_incremental`` (nnue_engine.cpp:739-786) for S independent frame sequences: each
-step updates a stored int16 accumulator by the features that changed, with the same bits as ``evaluate_logits``.
+step updates a stored int16 accumulator by the features that changed, with the same bits as ``evaluate_logits``; its
+``update(added, removed)`` takes just those features as two id lists (``NNUEEvaluator::update_features``, :818-821).
 ``EngineModel.load(path, bucket="auto")`` keeps all K layer stacks of the file; both calls then choose the stack of every image
 from its own active-feature count (``stack_of``, the rule a ``num_ls_buckets=K`` model is trained with) or take it from the
 caller -- the engine's ``layer_stack_index`` (nnue_engine.cpp:704-707), bit-identical to the engine stack by stack.
@@ -492,6 +493,56 @@ class EngineModel:
         return (logits, density, used) if return_stacks else (logits, density)
 
 
+_INT32_MIN, _INT32_MAX = -2 ** 31, 2 ** 31 - 1
+
+
+def pack_feature_lists(lists, num_streams: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``num_streams`` per-stream id lists (Python sequences, numpy arrays or tensors of integers, any mix, any of them empty) as
+    the CSR pair ``EngineStream.update`` takes: (ids int32 [total], offsets int32 [num_streams + 1]) on the CPU; stream b's ids
+    are ids[offsets[b]:offsets[b + 1]].  Pure host work, no device is touched.  An id outside int32 becomes -1 (ignored by the
+    kernel, never wrapped into the range).  ValueError for another number of lists, for ids that are not integers and for more
+    ids than int32 offsets can address."""
+    s = int(num_streams)
+    if isinstance(lists, (torch.Tensor, np.ndarray, str, bytes)) or not hasattr(lists, "__len__"):
+        raise ValueError(f"pack_feature_lists: expected a sequence of {s} id lists, got {type(lists).__name__}")
+    if len(lists) != s:
+        raise ValueError(f"pack_feature_lists: expected {s} id lists (one per stream), got {len(lists)}")
+    parts = []
+    for b, ids in enumerate(lists):
+        if isinstance(ids, torch.Tensor):
+            if ids.dtype not in (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64):
+                raise ValueError(f"pack_feature_lists: list {b} holds {ids.dtype}, expected integer ids")
+            a = ids.detach().cpu().numpy()
+        else:
+            a = np.asarray(ids)
+            if a.size == 0:
+                a = a.astype(np.int64)
+            elif a.dtype.kind not in "iu":
+                raise ValueError(f"pack_feature_lists: list {b} holds {a.dtype} values, expected integer ids")
+        if a.ndim != 1:
+            raise ValueError(f"pack_feature_lists: list {b} has shape {a.shape}, expected one dimension")
+        if a.dtype == np.uint64:
+            a = np.where(a > _INT32_MAX, np.uint64(_INT32_MAX + 1), a)
+        a = a.astype(np.int64)
+        parts.append(np.where((a < _INT32_MIN) | (a > _INT32_MAX), -1, a).astype(np.int32))
+    offsets = np.zeros(s + 1, dtype=np.int64)
+    np.cumsum([p.size for p in parts], out=offsets[1:])
+    if offsets[-1] > _INT32_MAX:
+        raise ValueError(f"pack_feature_lists: {int(offsets[-1])} ids are more than int32 offsets can address")
+    if np.any(np.diff(offsets) < 0):
+        raise ValueError("pack_feature_lists: offsets are not monotone")
+    ids = np.concatenate(parts) if parts else np.zeros(0, dtype=np.int32)
+    return torch.from_numpy(ids.astype(np.int32, copy=False)), torch.from_numpy(offsets.astype(np.int32))
+
+
+class EngineStreamSnapshot:
+    """What ``EngineStream.snapshot`` returns: a device copy of the stream state (sets, accumulators, flags), the stacks of the
+    last step, and the model generation the accumulators belong to."""
+
+    def __init__(self, model: "EngineModel", num_streams: int, state: torch.Tensor, stacks: torch.Tensor, generation: int):
+        self.model, self.num_streams, self.state, self.stacks, self.generation = model, num_streams, state, stacks, generation
+
+
 class EngineStream:
     """S independent frame sequences (for example one per camera) evaluated incrementally on the device: every stream keeps
     the engine's wrapped int16 accumulator and its last active-feature set, and a step applies only the features that
@@ -499,6 +550,10 @@ class EngineStream:
     are bit-identical to ``EngineModel.evaluate_logits`` on the same frames, whatever came before: int16 addition wraps,
     so the order and history of the terms do not matter.  A new stream, one passed to ``reset``, and every stream after the
     model's ``requantize``, is refreshed from the bias on its next step.  ``step`` (images) and ``step_features`` (feature maps) may be mixed on one stream.
+    ``update(added, removed)`` takes the two short id lists of the features that turned on and off instead of the whole new state
+    (NNUEEvaluator::update_features, nnue_engine.cpp:818-821), so a step costs O(changes); it mixes with the other two, keeps the
+    stored sets across a ``requantize`` (it rebuilds the sums once instead of forgetting the sets), and ``refresh`` /
+    ``snapshot`` / ``restore`` are the reference's refresh_accumulator and save / restore_accumulator (:792-816).
     On a model loaded with bucket="auto" every step chooses each stream's layer stack from the step's own feature count
     (or takes ``stacks=``, as ``evaluate_logits``); ``stacks`` holds the stacks of the last step, int32 [S]."""
 
@@ -580,3 +635,86 @@ class EngineStream:
         if tuple(active.shape) != (self.num_streams, self.num_features):
             raise ValueError(f"active: expected shape {(self.num_streams, self.num_features)}, got {tuple(active.shape)}")
         return self._run(None, active.contiguous(), 0, 0, stacks)
+
+    # ---- sparse add / remove lists ------------------------------------------------------------
+    def _csr(self, lists, what: str) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+        """One list argument of ``update`` as (ids int32 [n], offsets int32 [S + 1]) on the device, or (None, None)."""
+        if lists is None:
+            return None, None
+        dev, s = self.model.device, self.num_streams
+        if isinstance(lists, tuple) and len(lists) == 2 and all(isinstance(t, torch.Tensor) for t in lists):
+            ids, offsets = lists  # device CSR: no host work, no synchronisation
+            for t, name in ((ids, "ids"), (offsets, "offsets")):
+                if t.dtype not in (torch.int32, torch.int64):
+                    raise ValueError(f"{what}: {name} must be int32 or int64, got {t.dtype}")
+                if not t.is_cuda or (dev.index is not None and t.device.index != dev.index):
+                    raise ValueError(f"{what}: {name} is on {t.device}, the stream's state on {dev} (no CPU fallback in this build)")
+            if ids.dim() != 1 or ids.numel() > _INT32_MAX:
+                raise ValueError(f"{what}: ids must have one dimension and fewer than 2^31 elements, got shape {tuple(ids.shape)}")
+            if tuple(offsets.shape) != (s + 1,):
+                raise ValueError(f"{what}: offsets must have shape ({s + 1},), got {tuple(offsets.shape)}")
+            if ids.dtype == torch.int64:  # an id beyond int32 must not wrap into the range
+                ids = torch.where((ids >= _INT32_MIN) & (ids <= _INT32_MAX), ids, torch.full_like(ids, -1)).to(torch.int32)
+            if offsets.dtype == torch.int64:  # the kernel clips to [0, n] with n < 2^31: saturating keeps every clip where it was
+                offsets = offsets.clamp(_INT32_MIN, _INT32_MAX).to(torch.int32)
+            return ids.contiguous(), offsets.contiguous()
+        ids, offsets = pack_feature_lists(lists, s)
+        packed = torch.cat((offsets, ids)).to(dev)  # one copy
+        return packed[s + 1:], packed[:s + 1]
+
+    def _update(self, added, removed, stacks: Optional[torch.Tensor], fresh: bool
+                ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        m, s = self.model, self.num_streams
+        a_ids, a_off = self._csr(added, "added")
+        r_ids, r_off = self._csr(removed, "removed")
+        stacks = m._stack_arg(stacks, s, "EngineStream")
+        logits = torch.empty((s, m.num_classes), dtype=torch.float32, device=m.device)
+        density = torch.empty((s,), dtype=torch.float32, device=m.device)
+        changed = torch.empty((s,), dtype=torch.int32, device=m.device)
+        used = None if m._stacks is None else torch.empty((s,), dtype=torch.int32, device=m.device)
+        if fresh:
+            self._valid.fill_(0)
+        # after a requantize the stored sets are still right and only the sums are stale: one rebuild instead of a reset
+        rebuild = int(self._generation != m.generation)
+        lib._call("nnue_engine_stream_update", ctypes.addressof(m._c), None if used is None else ctypes.addressof(m._stacks),
+                  lib._ptr(a_ids), lib._ptr(a_off), 0 if a_ids is None else a_ids.numel(), lib._ptr(r_ids), lib._ptr(r_off),
+                  0 if r_ids is None else r_ids.numel(), s, rebuild, lib._ptr(stacks), self.state.data_ptr(), self.state.numel(),
+                  logits.data_ptr(), density.data_ptr(), changed.data_ptr(), lib._ptr(used), lib._stream(self.state))
+        self._generation = m.generation
+        if used is not None:
+            self.stacks = used
+        return logits, density, changed
+
+    def update(self, added, removed=None, stacks: Optional[torch.Tensor] = None
+               ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """One step from the features that turned on (``added``) and off (``removed``) per stream -- O(changes), where ``step``
+        and ``step_features`` read the whole new state.  Each list is a tuple ``(ids, offsets)`` of device tensors -- ids int32 or
+        int64 [n], offsets int32 or int64 [S + 1], stream b's ids being ids[offsets[b]:offsets[b + 1]]; no host work, no
+        synchronisation, fit for a stream capture -- or a sequence of S per-stream id sequences or tensors, packed on the host
+        (``pack_feature_lists``) and copied once; None = empty.  A tuple of two tensors is always read as (ids, offsets): hand
+        per-stream tensors over in a list.  Set semantics: new = (old - removed) | added; ids outside [0, num_features), removed ids
+        that are off, added ids that are on and duplicates are ignored, an id in both lists ends up on; offsets are clipped to the
+        id buffer.  A stream that is not valid takes ``added`` as its whole set.  Returns what ``step`` returns, bit-identical to
+        ``evaluate_features`` on the resulting sets; ``stacks`` as in ``step``."""
+        return self._update(added, removed, stacks, False)
+
+    def refresh(self, features, stacks: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """``reset()`` followed by ``update(features)``: every stream's set becomes its list
+        (NNUEEvaluator::refresh_accumulator, nnue_engine.cpp:806-816).  A refused call resets nothing."""
+        return self._update(features, None, stacks, True)
+
+    def snapshot(self) -> EngineStreamSnapshot:
+        """A point to come back to (save_accumulator, nnue_engine.cpp:792-797, for the whole stream state: sets included)."""
+        return EngineStreamSnapshot(self.model, self.num_streams, self.state.clone(), self.stacks.clone(), self._generation)
+
+    def restore(self, snap: EngineStreamSnapshot) -> None:
+        """Takes every stream back to ``snap`` (restore_accumulator, nnue_engine.cpp:799-804) with one device copy and no
+        synchronisation.  If the model was requantised since the snapshot, the next ``update`` rebuilds the sums and the next
+        ``step`` / ``step_features`` refreshes.  ValueError for a snapshot of another model or stream count."""
+        if not isinstance(snap, EngineStreamSnapshot):
+            raise TypeError(f"restore: expected an EngineStreamSnapshot, got {type(snap).__name__}")
+        if snap.model is not self.model or snap.num_streams != self.num_streams or snap.state.numel() != self.state.numel():
+            raise ValueError("restore: the snapshot belongs to another model or stream count")
+        self.state.copy_(snap.state)
+        self.stacks = snap.stacks.clone()
+        self._generation = snap.generation

@@ -145,6 +145,8 @@ SIGNATURES = {
                                                     _c_p]),
     "nnue_engine_stream_step_stacks": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_p,
                                                 _c_p, _c_p, _c_i64, _c_p]),
+    "nnue_engine_stream_update": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_i64, _c_int, _c_int, _c_p, _c_p, _c_i64, _c_p,
+                                           _c_p, _c_p, _c_p, _c_p]),
     "nnue_engine_matrix_supported": (_c_int, [_c_p, _c_int, _c_int]),
     "nnue_engine_table_planes_bytes": (_c_i64, [_c_p, _c_int]),
     "nnue_engine_matrix_scratch": (_c_i64, [_c_p, _c_int, _c_int]),
