@@ -44,14 +44,63 @@ __global__ __launch_bounds__(256) void engine_conv_kernel(const float* __restric
 
 __device__ __forceinline__ int32_t clamp_i(int32_t v, int32_t lo, int32_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
-// LayerStack::forward_multiclass (nnue_engine.cpp:480-539) of one image, from the clipped accumulator ft [L1] (LDS) to its
-// logits row; shared by the batched and the per-stream kernels.  The caller synchronises after writing ft.
-__device__ __forceinline__ void engine_tail(const int32_t* ft, int32_t* pair, int32_t* h1, int32_t* h2,
-                                            const int8_t* __restrict__ l1_w, const int32_t* __restrict__ l1_b, float l1_scale,
-                                            const int8_t* __restrict__ l2_w, const int32_t* __restrict__ l2_b, int l2_scale,
-                                            const int8_t* __restrict__ out_w, const int32_t* __restrict__ out_b, float out_scale,
-                                            int L1, int L2, int L3, int C, float* __restrict__ logits_row) {
+// What a per-image kernel reads of the network, by value in its arguments: the table, one layer stack -- the model's own, or
+// stack 0 of K packed stack-major, which engine_select_stack moves to the image's stack -- and the sizes.  engine_net builds it.
+struct EngineNet {
+  const int16_t* __restrict__ ft_w;
+  const int32_t* __restrict__ ft_b;
+  const int8_t* __restrict__ l1_w;
+  const int32_t* __restrict__ l1_b;
+  const int8_t* __restrict__ l2_w;
+  const int32_t* __restrict__ l2_b;
+  const int8_t* __restrict__ out_w;
+  const int32_t* __restrict__ out_b;
+  float l1_scale;
+  int l2_scale;
+  float out_scale, threshold;
+  int quantized_one, F, oc, L1, L2, L3, C;
+};
+
+// Dynamic LDS of the per-image kernels, offsets in int32 words from its start:
+//   ft [L1] | pair [L1] | h1 [L2] | h2 [L3] | counts [n_counts] | work_n [2] work [n_work] (only with n_work > 0) |
+//   (8-byte aligned) n_word_arrays x [W64] u64, W64 = ceil(F / 64)
+// The kernels take their pointers from it and the entry points the byte count they launch with and check against 64 KB.
+struct EngineLds {
+  int pair, h1, h2, counts, work_n, work, words;
+  size_t bytes;
+};
+
+__host__ __device__ inline EngineLds engine_lds(const EngineNet& net, int n_counts, int n_work, int n_word_arrays) {
+  EngineLds l;
+  l.pair = net.L1;
+  l.h1 = l.pair + net.L1;
+  l.h2 = l.h1 + net.L2;
+  l.counts = l.h2 + net.L3;
+  l.work_n = l.counts + n_counts;
+  l.work = l.work_n + (n_work ? 2 : 0);
+  const int end = l.work + n_work;
+  l.words = (end + 1) & ~1;
+  l.bytes = (size_t)(n_word_arrays ? l.words : end) * sizeof(int32_t) + (size_t)n_word_arrays * ((net.F + 63) / 64) * sizeof(uint64_t);
+  return l;
+}
+
+// Ids of one phase that the row walk of engine_stream_update_kernel takes per round (LDS work list, int32 each).
+constexpr int kUpdateChunk = 1024;
+
+// The three uses.  Batched kernels (gather and matrix tail): counts = one active count per wave (the gather form has its count
+// in registers and leaves the four words unused).  Stream step: counts = [wave] new, [4 + wave] difference; words = new | old.
+// Stream update: the same counts, the work list, words = the current set.
+__host__ __device__ inline EngineLds batch_lds(const EngineNet& net) { return engine_lds(net, 4, 0, 0); }
+__host__ __device__ inline EngineLds stream_lds(const EngineNet& net) { return engine_lds(net, 8, 0, 2); }
+__host__ __device__ inline EngineLds update_lds(const EngineNet& net) { return engine_lds(net, 8, kUpdateChunk, 1); }
+
+// LayerStack::forward_multiclass (nnue_engine.cpp:480-539) of one image, from the clipped accumulator ft [L1] at the start of
+// the LDS to its logits row; shared by all per-image kernels.  The caller synchronises after writing ft.
+__device__ __forceinline__ void engine_tail(const EngineNet& net, int32_t* lds, const EngineLds& lay, float* __restrict__ logits_row) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int L1 = net.L1, L2 = net.L2, L3 = net.L3;
+  const int32_t* ft = lds;
+  int32_t *pair = lds + lay.pair, *h1 = lds + lay.h1, *h2 = lds + lay.h2;
   // pairwise: (a * b) / 128 clamped to [0, 127] | a clamped to [0, 127]
   const int half = L1 / 2;
   for (int i = tid; i < L1; i += 256) {
@@ -64,13 +113,13 @@ __device__ __forceinline__ void engine_tail(const int32_t* ft, int32_t* pair, in
 
   // layer 1 (dense_forward_scalar: float division, truncation, clamp to [0, 127]); one wave per output
   for (int o = wave; o < L2; o += 4) {
-    const int8_t* __restrict__ wr = l1_w + (size_t)o * L1;
+    const int8_t* __restrict__ wr = net.l1_w + (size_t)o * L1;
     int32_t s = 0;
     for (int k = lane; k < L1; k += 64) s += pair[k] * (int32_t)wr[k];
 #pragma unroll
     for (int sh = 32; sh >= 1; sh >>= 1) s += __shfl_xor(s, sh);
     if (lane == 0) {
-      const float r = (float)(s + l1_b[o]) / l1_scale;
+      const float r = (float)(s + net.l1_b[o]) / net.l1_scale;
       h1[o] = clamp_i((int32_t)r, 0, 127);
     }
   }
@@ -78,19 +127,19 @@ __device__ __forceinline__ void engine_tail(const int32_t* ft, int32_t* pair, in
 
   // layer 2: integer division, clamp to [-127, 127], ReLU; weights are [L3][2 * L2], first L2 columns used
   for (int o = tid; o < L3; o += 256) {
-    const int8_t* __restrict__ wr = l2_w + (size_t)o * 2 * L2;
-    int32_t s = l2_b[o];
+    const int8_t* __restrict__ wr = net.l2_w + (size_t)o * 2 * L2;
+    int32_t s = net.l2_b[o];
     for (int k = 0; k < L2; ++k) s += h1[k] * (int32_t)wr[k];
-    int32_t r = clamp_i(s / l2_scale, -127, 127);
+    int32_t r = clamp_i(s / net.l2_scale, -127, 127);
     h2[o] = r > 0 ? r : 0;
   }
   __syncthreads();
 
-  for (int c = tid; c < C; c += 256) {
-    const int8_t* __restrict__ wr = out_w + (size_t)c * L3;
-    int32_t s = out_b[c];
+  for (int c = tid; c < net.C; c += 256) {
+    const int8_t* __restrict__ wr = net.out_w + (size_t)c * L3;
+    int32_t s = net.out_b[c];
     for (int j = 0; j < L3; ++j) s += h2[j] * (int32_t)wr[j];
-    logits_row[c] = (float)s / out_scale;
+    logits_row[c] = (float)s / net.out_scale;
   }
 }
 
@@ -116,92 +165,115 @@ struct StackSel {
 
 // Resolves the stack of image b from its active-feature count n (uniform over the workgroup), records it, and moves the tail's
 // weights, biases and scales to that stack.
-__device__ __forceinline__ void engine_select_stack(const StackSel& sel, int b, int n, int F, int L1, int L2, int L3, int C,
-                                                    const int8_t* __restrict__& l1_w, const int32_t* __restrict__& l1_b,
-                                                    float& l1_scale, const int8_t* __restrict__& l2_w,
-                                                    const int32_t* __restrict__& l2_b, int& l2_scale,
-                                                    const int8_t* __restrict__& out_w, const int32_t* __restrict__& out_b,
-                                                    float& out_scale) {
+__device__ __forceinline__ void engine_select_stack(const StackSel& sel, int b, int n, EngineNet& net) {
   int k;
   if (sel.stack_in) {
     k = sel.stack_in[b];
     if (k < 0 || k >= sel.K) k = 0;
   } else {
-    k = (int)((unsigned)(n * sel.K) / (unsigned)(F + 1));  // n <= F and F * K < 2^31 (checked on the host)
+    k = (int)((unsigned)(n * sel.K) / (unsigned)(net.F + 1));  // n <= F and F * K < 2^31 (checked on the host)
     if (k > sel.K - 1) k = sel.K - 1;
   }
   k = __builtin_amdgcn_readfirstlane(k);
   if (threadIdx.x == 0) sel.stack_out[b] = k;
-  l1_w += (size_t)k * (L2 + 1) * L1;
-  l1_b += (size_t)k * (L2 + 1);
-  l2_w += (size_t)k * L3 * 2 * L2;
-  l2_b += (size_t)k * L3;
-  out_w += (size_t)k * C * L3;
-  out_b += (size_t)k * C;
-  l1_scale = sel.l1_scale[k];
-  l2_scale = sel.l2_scale[k];
-  out_scale = sel.out_scale[k];
+  net.l1_w += (size_t)k * (net.L2 + 1) * net.L1;
+  net.l1_b += (size_t)k * (net.L2 + 1);
+  net.l2_w += (size_t)k * net.L3 * 2 * net.L2;
+  net.l2_b += (size_t)k * net.L3;
+  net.out_w += (size_t)k * net.C * net.L3;
+  net.out_b += (size_t)k * net.C;
+  net.l1_scale = sel.l1_scale[k];
+  net.l2_scale = sel.l2_scale[k];
+  net.out_scale = sel.out_scale[k];
+}
+
+// The epilogue of every per-image kernel, after a barrier behind the stores to ft: the stack of image b, chosen from its active
+// count n where the call selects, and the tail into the image's logits row.
+template <class Sel>
+__device__ __forceinline__ void engine_epilogue(EngineNet net, const Sel& sel, int b, int n, int32_t* lds, const EngineLds& lay,
+                                                float* __restrict__ logits) {
+  if constexpr (Sel::kSelect) engine_select_stack(sel, b, n, net);
+  engine_tail(net, lds, lay, logits + (size_t)b * net.C);
+}
+
+// Whether feature f of a row of F map bytes is on, as one lane of a ballot.  kFeatures: the row is a caller's map, non-zero = on,
+// every id counts (the reference's entry that takes feature indices applies no per-cell channel mask); otherwise conv bytes,
+// and the division by oc is reached only where the byte passes the threshold.  matrix_a_chunk states the same rule on the
+// bytes of a chunk with a running channel (through a shared helper the product kernels compile to 40 more instructions).
+template <bool kFeatures>
+__device__ __forceinline__ bool feature_on(const uint8_t* __restrict__ row, int f, const EngineNet& net) {
+  if (f >= net.F) return false;
+  if constexpr (kFeatures) return row[f] != 0;
+  else return (float)(int8_t)row[f] > net.threshold && (f % net.oc) < 64;  // 64 channels per cell are bit-packed
+}
+
+// A thread's columns of the accumulator, tid + 256 j (those below L1), in int32 registers; the int16 accumulator they stand for
+// wraps, and addition mod 2^16 does not depend on the width it is carried in.  acc_seed: from stored sums, or from the bias
+// (accs == nullptr).  row_add: plus or minus one table row.  acc_finish: the bias where the sums do not hold it yet (kBias),
+// wrap to int16, store the sums where the kernel keeps them (kStore), clipped ReLU into ft.
+__device__ __forceinline__ void acc_seed(const EngineNet& net, const int16_t* __restrict__ accs, int32_t (&acc)[kMaxColsPerThread]) {
+#pragma unroll
+  for (int j = 0; j < kMaxColsPerThread; ++j) {
+    const int col = threadIdx.x + 256 * j;
+    acc[j] = col < net.L1 ? (accs ? (int32_t)accs[col] : (int32_t)(int16_t)net.ft_b[col]) : 0;
+  }
+}
+
+template <bool kAdd>
+__device__ __forceinline__ void row_add(const EngineNet& net, int row, int32_t (&acc)[kMaxColsPerThread]) {
+  const int tid = threadIdx.x;
+  const int16_t* __restrict__ wr = net.ft_w + (size_t)row * net.L1;
+#pragma unroll
+  for (int j = 0; j < kMaxColsPerThread; ++j) {
+    const int col = tid + 256 * j;
+    if (col < net.L1) acc[j] += kAdd ? (int32_t)wr[col] : -(int32_t)wr[col];
+  }
+}
+
+__device__ __forceinline__ int32_t wrap_clip(int32_t sum, int quantized_one) {
+  return clamp_i((int32_t)(int16_t)sum, 0, quantized_one);  // int16 accumulator wraps
+}
+
+template <bool kBias, bool kStore>
+__device__ __forceinline__ void acc_finish(const EngineNet& net, const int32_t (&acc)[kMaxColsPerThread], int16_t* __restrict__ accs,
+                                           int32_t* ft) {
+#pragma unroll
+  for (int j = 0; j < kMaxColsPerThread; ++j) {
+    const int col = threadIdx.x + 256 * j;
+    if (col < net.L1) {
+      const int32_t sum = kBias ? (int32_t)(int16_t)net.ft_b[col] + acc[j] : acc[j];
+      if (kStore) accs[col] = (int16_t)sum;
+      ft[col] = wrap_clip(sum, net.quantized_one);
+    }
+  }
 }
 
 // One workgroup per image: feature grid + FeatureTransformer (int16 wrap-around) + clipped ReLU + forward_multiclass
-// (nnue_engine.h:236-283, simd_scalar.cpp:78-96, nnue_engine.cpp:726-729, :480-539).
-// dynamic LDS: ft [L1] i32 | pair [L1] i32 | h1 [L2] i32 | h2 [L3] i32 | counts [4] i32
+// (nnue_engine.h:236-283, simd_scalar.cpp:78-96, nnue_engine.cpp:726-729, :480-539).  dynamic LDS: batch_lds.
 // Sel = StackSel: the image's stack is resolved from `count` before the tail (see engine_select_stack).
 template <class Sel>
-__global__ __launch_bounds__(256) void engine_stack_kernel(const int8_t* __restrict__ conv, float threshold, int F, int oc,
-                                                           const int16_t* __restrict__ ft_w, const int32_t* __restrict__ ft_b,
-                                                           int quantized_one, const int8_t* __restrict__ l1_w,
-                                                           const int32_t* __restrict__ l1_b, float l1_scale,
-                                                           const int8_t* __restrict__ l2_w, const int32_t* __restrict__ l2_b,
-                                                           int l2_scale, const int8_t* __restrict__ out_w,
-                                                           const int32_t* __restrict__ out_b, float out_scale, int L1, int L2,
-                                                           int L3, int C, float* __restrict__ logits, float* __restrict__ density, Sel sel) {
+__global__ __launch_bounds__(256) void engine_stack_kernel(EngineNet net, const uint8_t* __restrict__ conv, float* __restrict__ logits,
+                                                           float* __restrict__ density, Sel sel) {
   extern __shared__ int32_t lds[];
-  int32_t* ft = lds;
-  int32_t* pair = ft + L1;
-  int32_t* h1 = pair + L1;
-  int32_t* h2 = h1 + L2;
-  int32_t* counts = h2 + L3;
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
-  const int8_t* __restrict__ cv = conv + (size_t)b * F;
+  const int b = blockIdx.x, lane = threadIdx.x & 63, F = net.F;
+  const uint8_t* __restrict__ cv = conv + (size_t)b * F;
 
   // active features, ascending: every wave forms the same ballots and adds the rows to its own columns
-  int32_t acc[kMaxColsPerThread];
-#pragma unroll
-  for (int j = 0; j < kMaxColsPerThread; ++j) acc[j] = 0;
+  int32_t acc[kMaxColsPerThread] = {};  // the bias joins at the finish: its loads up front would delay the first rows
   int count = 0;
   for (int f0 = 0; f0 < F; f0 += 64) {
-    const int f = f0 + lane;
-    const bool on = f < F && (float)cv[f] > threshold && (f % oc) < 64;  // 64 channels per cell are bit-packed
-    unsigned long long mask = __ballot(on);
+    unsigned long long mask = __ballot(feature_on<false>(cv, f0 + lane, net));
     count += __popcll(mask);
     while (mask) {
       const int row = f0 + __builtin_ctzll(mask);
       mask &= mask - 1;
-      const int16_t* __restrict__ wr = ft_w + (size_t)row * L1;
-#pragma unroll
-      for (int j = 0; j < kMaxColsPerThread; ++j) {
-        const int col = tid + 256 * j;
-        if (col < L1) acc[j] += (int32_t)wr[col];
-      }
+      row_add<true>(net, row, acc);
     }
   }
-#pragma unroll
-  for (int j = 0; j < kMaxColsPerThread; ++j) {
-    const int col = tid + 256 * j;
-    if (col < L1) {
-      const int16_t v = (int16_t)((int32_t)(int16_t)ft_b[col] + acc[j]);  // int16 accumulator wraps
-      ft[col] = clamp_i((int32_t)v, 0, quantized_one);
-    }
-  }
-  if (tid == 0) density[b] = (float)count / (float)F;
+  acc_finish<true, false>(net, acc, nullptr, lds);
+  if (threadIdx.x == 0) density[b] = (float)count / (float)F;
   __syncthreads();
-
-  if constexpr (Sel::kSelect)
-    engine_select_stack(sel, b, count, F, L1, L2, L3, C, l1_w, l1_b, l1_scale, l2_w, l2_b, l2_scale, out_w, out_b, out_scale);
-  engine_tail(ft, pair, h1, h2, l1_w, l1_b, l1_scale, l2_w, l2_b, l2_scale, out_w, out_b, out_scale, L1, L2, L3, C,
-              logits + (size_t)b * C);
-  (void)counts;
+  engine_epilogue(net, sel, b, count, lds, batch_lds(net), logits);
 }
 
 
@@ -224,61 +296,62 @@ __host__ __device__ inline StreamLayout stream_layout(int64_t S, int64_t F, int6
   return l;
 }
 
+// Stream b's part of the state: its valid flag, its parity, its accumulator, and the bit words of either slot.
+struct StreamView {
+  int32_t* __restrict__ valid;
+  int32_t* __restrict__ parity;
+  int16_t* __restrict__ accs;
+  unsigned long long* bits;  // slot 0 of the stream
+  size_t slot_stride;        // in words
+  __device__ __forceinline__ unsigned long long* words(int slot) const { return bits + slot * slot_stride; }
+};
+
+__device__ __forceinline__ StreamView stream_view(uint8_t* state, int S, int F, int L1, int b) {
+  const StreamLayout lay = stream_layout(S, F, L1);
+  const size_t W64 = (F + 63) / 64;
+  StreamView v;
+  v.valid = reinterpret_cast<int32_t*>(state) + b;
+  v.parity = reinterpret_cast<int32_t*>(state + lay.parity) + b;
+  v.accs = reinterpret_cast<int16_t*>(state + lay.acc) + (size_t)b * L1;
+  v.bits = reinterpret_cast<unsigned long long*>(state + lay.bits) + b * W64;
+  v.slot_stride = S * W64;
+  return v;
+}
+
 // NNUEEvaluator::evaluate_incremental (nnue_engine.cpp:739-786) for S independent streams, one workgroup per stream: the new
 // feature set, the difference to the stream's previous one, and FeatureTransformer::update_accumulator (:257-267) on the
 // stored int16 accumulator -- or refresh_accumulator (:806-816) from the bias when the stream is not valid, or when the
 // difference holds more features than the new set (then a refresh reads fewer table rows).  Both give the same bits: the
 // accumulator is int16 and wraps, and addition mod 2^16 does not depend on the order or the history of the terms.
 // Then the clipped ReLU and engine_tail, as engine_stack_kernel.
-// kFeatures: the set is given as a uint8 map active [S][F] (non-zero = on, every id counts: the reference's entry that takes
-// feature indices applies no per-cell channel mask); otherwise it is formed from the conv bytes with engine_stack_kernel's
-// predicate.
+// kFeatures: src is a uint8 map active [S][F], otherwise the conv bytes (see feature_on).
 // Read/write hazard on the bit words: they ping-pong between two slots ([2][S][W64] + a per-stream parity that flips at the
 // end of the step).  Every wave may read the old words at any time during the step while the new ones are stored into the
 // other slot, so no barrier has to order those reads before the stores, and a launch never reads a word it writes.
-// dynamic LDS: ft [L1] i32 | pair [L1] i32 | h1 [L2] i32 | h2 [L3] i32 | counts [8] i32 | (8-byte aligned) new [W64] u64 |
-// old [W64] u64
+// dynamic LDS: stream_lds.
 // Sel = StackSel: the stream's stack is resolved from `n_new` before the tail (see engine_select_stack); the state is the same.
 template <bool kFeatures, class Sel>
-__global__ __launch_bounds__(256) void engine_stream_kernel(const int8_t* __restrict__ conv, const uint8_t* __restrict__ active,
-                                                            float threshold, int F, int oc, int S, const int16_t* __restrict__ ft_w,
-                                                            const int32_t* __restrict__ ft_b, int quantized_one,
-                                                            const int8_t* __restrict__ l1_w, const int32_t* __restrict__ l1_b,
-                                                            float l1_scale, const int8_t* __restrict__ l2_w,
-                                                            const int32_t* __restrict__ l2_b, int l2_scale,
-                                                            const int8_t* __restrict__ out_w, const int32_t* __restrict__ out_b,
-                                                            float out_scale, int L1, int L2, int L3, int C, uint8_t* __restrict__ state,
-                                                            float* __restrict__ logits, float* __restrict__ density,
-                                                            int32_t* __restrict__ changed, Sel sel) {
+__global__ __launch_bounds__(256) void engine_stream_kernel(EngineNet net, const uint8_t* __restrict__ src, int S,
+                                                            uint8_t* __restrict__ state, float* __restrict__ logits,
+                                                            float* __restrict__ density, int32_t* __restrict__ changed, Sel sel) {
   extern __shared__ int32_t lds[];
-  int32_t* ft = lds;
-  int32_t* pair = ft + L1;
-  int32_t* h1 = pair + L1;
-  int32_t* h2 = h1 + L2;
-  int32_t* counts = h2 + L3;  // [wave] new, [4 + wave] difference
-  const int W64 = (F + 63) / 64;
-  unsigned long long* new_s = reinterpret_cast<unsigned long long*>(lds + ((2 * L1 + L2 + L3 + 8 + 1) & ~1));
+  const EngineLds lay = stream_lds(net);
+  const int F = net.F, W64 = (F + 63) / 64;
+  int32_t* counts = lds + lay.counts;  // [wave] new, [4 + wave] difference
+  unsigned long long* new_s = reinterpret_cast<unsigned long long*>(lds + lay.words);
   unsigned long long* old_s = new_s + W64;
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 
-  const StreamLayout lay = stream_layout(S, F, L1);
-  int32_t* __restrict__ valid = reinterpret_cast<int32_t*>(state);
-  int32_t* __restrict__ parity = reinterpret_cast<int32_t*>(state + lay.parity);
-  unsigned long long* __restrict__ bits = reinterpret_cast<unsigned long long*>(state + lay.bits);
-  int16_t* __restrict__ accs = reinterpret_cast<int16_t*>(state + lay.acc) + (size_t)b * L1;
-  const bool was_valid = valid[b] != 0;
-  const int par = parity[b] & 1;
-  const unsigned long long* __restrict__ old_w = bits + ((size_t)par * S + b) * W64;
-  unsigned long long* __restrict__ new_w = bits + ((size_t)(par ^ 1) * S + b) * W64;
+  const StreamView sv = stream_view(state, S, F, net.L1, b);
+  const bool was_valid = *sv.valid != 0;
+  const int par = *sv.parity & 1;
+  const unsigned long long* __restrict__ old_w = sv.words(par);
+  unsigned long long* __restrict__ new_w = sv.words(par ^ 1);
 
   // pass 1: wave w forms the ballots of chunks w, w + 4, ...: new set -> its slot and LDS, old set -> LDS, both popcounts
   int n_new = 0, n_diff = 0;
   for (int c = wave; c < W64; c += 4) {
-    const int f = c * 64 + lane;
-    bool on;
-    if constexpr (kFeatures) on = f < F && active[(size_t)b * F + f] != 0;
-    else on = f < F && (float)conv[(size_t)b * F + f] > threshold && (f % oc) < 64;  // 64 channels per cell are bit-packed
-    const unsigned long long m = __ballot(on);
+    const unsigned long long m = __ballot(feature_on<kFeatures>(src + (size_t)b * F, c * 64 + lane, net));
     const unsigned long long o = was_valid ? old_w[c] : 0ull;
     n_new += __popcll(m);
     n_diff += __popcll(m ^ o);
@@ -299,58 +372,23 @@ __global__ __launch_bounds__(256) void engine_stream_kernel(const int8_t* __rest
 
   // pass 2: every wave walks the same words and updates its own columns in int32 registers seeded from the state or the bias
   int32_t acc[kMaxColsPerThread];
-#pragma unroll
-  for (int j = 0; j < kMaxColsPerThread; ++j) {
-    const int col = tid + 256 * j;
-    acc[j] = col < L1 ? (refresh ? (int32_t)(int16_t)ft_b[col] : (int32_t)accs[col]) : 0;
-  }
+  acc_seed(net, refresh ? nullptr : sv.accs, acc);
   for (int c = 0; c < W64; ++c) {
     const unsigned long long m = new_s[c], o = refresh ? 0ull : old_s[c];
     unsigned long long add = m & ~o, sub = o & ~m;
-    while (add) {
-      const int16_t* __restrict__ wr = ft_w + (size_t)(c * 64 + __builtin_ctzll(add)) * L1;
-      add &= add - 1;
-#pragma unroll
-      for (int j = 0; j < kMaxColsPerThread; ++j) {
-        const int col = tid + 256 * j;
-        if (col < L1) acc[j] += (int32_t)wr[col];
-      }
-    }
-    while (sub) {
-      const int16_t* __restrict__ wr = ft_w + (size_t)(c * 64 + __builtin_ctzll(sub)) * L1;
-      sub &= sub - 1;
-#pragma unroll
-      for (int j = 0; j < kMaxColsPerThread; ++j) {
-        const int col = tid + 256 * j;
-        if (col < L1) acc[j] -= (int32_t)wr[col];
-      }
-    }
+    for (; add; add &= add - 1) row_add<true>(net, c * 64 + __builtin_ctzll(add), acc);
+    for (; sub; sub &= sub - 1) row_add<false>(net, c * 64 + __builtin_ctzll(sub), acc);
   }
-#pragma unroll
-  for (int j = 0; j < kMaxColsPerThread; ++j) {
-    const int col = tid + 256 * j;
-    if (col < L1) {
-      const int16_t v = (int16_t)acc[j];  // int16 accumulator wraps
-      accs[col] = v;
-      ft[col] = clamp_i((int32_t)v, 0, quantized_one);
-    }
-  }
+  acc_finish<false, true>(net, acc, sv.accs, lds);
   if (tid == 0) {
     density[b] = (float)n_new / (float)F;
     changed[b] = was_valid ? n_diff : n_new;
-    valid[b] = 1;
-    parity[b] = par ^ 1;
+    *sv.valid = 1;
+    *sv.parity = par ^ 1;
   }
   __syncthreads();
-
-  if constexpr (Sel::kSelect)
-    engine_select_stack(sel, b, n_new, F, L1, L2, L3, C, l1_w, l1_b, l1_scale, l2_w, l2_b, l2_scale, out_w, out_b, out_scale);
-  engine_tail(ft, pair, h1, h2, l1_w, l1_b, l1_scale, l2_w, l2_b, l2_scale, out_w, out_b, out_scale, L1, L2, L3, C,
-              logits + (size_t)b * C);
+  engine_epilogue(net, sel, b, n_new, lds, lay, logits);
 }
-
-// Ids of one phase that the row walk of engine_stream_update_kernel takes per round (LDS work list, int32 each).
-constexpr int kUpdateChunk = 1024;
 
 // Stream b's range of a CSR list, clipped to the id buffer: [off[b], off[b + 1]) cut to [0, n], a reversed range = empty.  A
 // list with n == 0 is never dereferenced (its pointers may be null).
@@ -425,44 +463,30 @@ __device__ __forceinline__ void update_phase(const int32_t* __restrict__ ids, in
 // only its own stream's words, and within it word c belongs to thread c % 256 alone: that thread copies it to LDS at the start,
 // and at the end reads it again (the old set, for `changed`) and only then stores the new word over it, in program order.  All
 // other traffic on the words is LDS atomics between barriers.  No thread reads a global word another thread writes.
-// dynamic LDS: ft [L1] i32 | pair [L1] i32 | h1 [L2] i32 | h2 [L3] i32 | counts [8] i32 | work_n [2] i32 | work [kUpdateChunk]
-// i32 | (8-byte aligned) cur [W64] u64
+// dynamic LDS: update_lds.
 template <class Sel>
 __global__ __launch_bounds__(256) void engine_stream_update_kernel(
-    const int32_t* __restrict__ added, const int32_t* __restrict__ added_off, int n_added, const int32_t* __restrict__ removed,
-    const int32_t* __restrict__ removed_off, int n_removed, int rebuild, int F, int S, const int16_t* __restrict__ ft_w,
-    const int32_t* __restrict__ ft_b, int quantized_one, const int8_t* __restrict__ l1_w, const int32_t* __restrict__ l1_b,
-    float l1_scale, const int8_t* __restrict__ l2_w, const int32_t* __restrict__ l2_b, int l2_scale, const int8_t* __restrict__ out_w,
-    const int32_t* __restrict__ out_b, float out_scale, int L1, int L2, int L3, int C, uint8_t* __restrict__ state,
-    float* __restrict__ logits, float* __restrict__ density, int32_t* __restrict__ changed, Sel sel) {
+    EngineNet net, const int32_t* __restrict__ added, const int32_t* __restrict__ added_off, int n_added,
+    const int32_t* __restrict__ removed, const int32_t* __restrict__ removed_off, int n_removed, int rebuild, int S,
+    uint8_t* __restrict__ state, float* __restrict__ logits, float* __restrict__ density, int32_t* __restrict__ changed, Sel sel) {
   extern __shared__ int32_t lds[];
-  int32_t* ft = lds;
-  int32_t* pair = ft + L1;
-  int32_t* h1 = pair + L1;
-  int32_t* h2 = h1 + L2;
-  int32_t* counts = h2 + L3;  // [wave] new, [4 + wave] difference
-  unsigned* work_n = reinterpret_cast<unsigned*>(counts + 8);
-  int32_t* work = counts + 10;
-  const int W64 = (F + 63) / 64;
-  unsigned long long* cur = reinterpret_cast<unsigned long long*>(lds + ((2 * L1 + L2 + L3 + 10 + kUpdateChunk + 1) & ~1));
+  const EngineLds lay = update_lds(net);
+  const int F = net.F, W64 = (F + 63) / 64;
+  int32_t* counts = lds + lay.counts;  // [wave] new, [4 + wave] difference
+  unsigned* work_n = reinterpret_cast<unsigned*>(lds + lay.work_n);
+  int32_t* work = lds + lay.work;
+  unsigned long long* cur = reinterpret_cast<unsigned long long*>(lds + lay.words);
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 
-  const StreamLayout lay = stream_layout(S, F, L1);
-  int32_t* __restrict__ valid = reinterpret_cast<int32_t*>(state);
-  const int32_t* __restrict__ parity = reinterpret_cast<const int32_t*>(state + lay.parity);
-  int16_t* __restrict__ accs = reinterpret_cast<int16_t*>(state + lay.acc) + (size_t)b * L1;
-  const bool was_valid = valid[b] != 0;
-  unsigned long long* words = reinterpret_cast<unsigned long long*>(state + lay.bits) + ((size_t)(parity[b] & 1) * S + b) * W64;
+  const StreamView sv = stream_view(state, S, F, net.L1, b);
+  const bool was_valid = *sv.valid != 0;
+  unsigned long long* words = sv.words(*sv.parity & 1);
 
   for (int c = tid; c < W64; c += 256) cur[c] = was_valid ? words[c] : 0ull;
   if (tid == 0) *work_n = 0;
   const bool walk = rebuild == 0;
   int32_t acc[kMaxColsPerThread];
-#pragma unroll
-  for (int j = 0; j < kMaxColsPerThread; ++j) {
-    const int col = tid + 256 * j;
-    acc[j] = col < L1 ? (was_valid && walk ? (int32_t)accs[col] : (int32_t)(int16_t)ft_b[col]) : 0;
-  }
+  acc_seed(net, was_valid && walk ? sv.accs : nullptr, acc);
   __syncthreads();
 
   // removed before added, with the phases' barriers between them: an id in both lists ends up on
@@ -470,24 +494,14 @@ __global__ __launch_bounds__(256) void engine_stream_update_kernel(
   unsigned done = 0;
   if (was_valid) {
     update_range(removed_off, n_removed, b, lo, hi);
-    update_phase<false>(removed, lo, hi, F, L1, walk, ft_w, cur, work, work_n, done, acc);
+    update_phase<false>(removed, lo, hi, F, net.L1, walk, net.ft_w, cur, work, work_n, done, acc);
   }
   update_range(added_off, n_added, b, lo, hi);
-  update_phase<true>(added, lo, hi, F, L1, walk, ft_w, cur, work, work_n, done, acc);
+  update_phase<true>(added, lo, hi, F, net.L1, walk, net.ft_w, cur, work, work_n, done, acc);
 
   if (!walk) {  // every wave walks the same words of the new set, as pass 2 of engine_stream_kernel on a refresh
-    for (int c = 0; c < W64; ++c) {
-      unsigned long long m = cur[c];
-      while (m) {
-        const int16_t* __restrict__ wr = ft_w + (size_t)(c * 64 + __builtin_ctzll(m)) * L1;
-        m &= m - 1;
-#pragma unroll
-        for (int j = 0; j < kMaxColsPerThread; ++j) {
-          const int col = tid + 256 * j;
-          if (col < L1) acc[j] += (int32_t)wr[col];
-        }
-      }
-    }
+    for (int c = 0; c < W64; ++c)
+      for (unsigned long long m = cur[c]; m; m &= m - 1) row_add<true>(net, c * 64 + __builtin_ctzll(m), acc);
   }
 
   int n_new = 0, n_diff = 0;
@@ -506,28 +520,16 @@ __global__ __launch_bounds__(256) void engine_stream_update_kernel(
     counts[wave] = n_new;
     counts[4 + wave] = n_diff;
   }
-#pragma unroll
-  for (int j = 0; j < kMaxColsPerThread; ++j) {
-    const int col = tid + 256 * j;
-    if (col < L1) {
-      const int16_t v = (int16_t)acc[j];  // int16 accumulator wraps
-      accs[col] = v;
-      ft[col] = clamp_i((int32_t)v, 0, quantized_one);
-    }
-  }
+  acc_finish<false, true>(net, acc, sv.accs, lds);
   __syncthreads();
   n_new = counts[0] + counts[1] + counts[2] + counts[3];
   n_diff = counts[4] + counts[5] + counts[6] + counts[7];
   if (tid == 0) {
     density[b] = (float)n_new / (float)F;
     changed[b] = was_valid ? n_diff : n_new;
-    valid[b] = 1;
+    *sv.valid = 1;
   }
-
-  if constexpr (Sel::kSelect)
-    engine_select_stack(sel, b, n_new, F, L1, L2, L3, C, l1_w, l1_b, l1_scale, l2_w, l2_b, l2_scale, out_w, out_b, out_scale);
-  engine_tail(ft, pair, h1, h2, l1_w, l1_b, l1_scale, l2_w, l2_b, l2_scale, out_w, out_b, out_scale, L1, L2, L3, C,
-              logits + (size_t)b * C);
+  engine_epilogue(net, sel, b, n_new, lds, lay, logits);
 }
 
 // ---- whole batches on the int8 matrix unit --------------------------------------------------------------------------
@@ -599,7 +601,7 @@ __global__ __launch_bounds__(256) void engine_pack_table_kernel(const int16_t* _
 }
 
 // The 0/1 bytes of features f0 .. f0 + 15 of image b (zeros beyond B or F).  kFeatures: src is the caller's map, non-zero = on,
-// every id counts; otherwise the conv bytes under engine_stack_kernel's predicate.
+// every id counts; otherwise the conv bytes under feature_on's rule.
 template <bool kFeatures>
 __device__ __forceinline__ uint4 matrix_a_chunk(const uint8_t* __restrict__ src, int b, int f0, int B, int F, float threshold, int oc,
                                                 bool aligned) {
@@ -619,7 +621,7 @@ __device__ __forceinline__ uint4 matrix_a_chunk(const uint8_t* __restrict__ src,
   int ch = kFeatures ? 0 : f0 % oc;
 #pragma unroll
   for (int j = 0; j < 16; ++j) {
-    bool on;
+    bool on;  // feature_on's rule, stated a second time on purpose (see there)
     if constexpr (kFeatures) {
       on = raw.b[j] != 0;
     } else {
@@ -721,46 +723,25 @@ __global__ __launch_bounds__(256) void engine_matrix_product_kernel(const uint8_
 
 // One workgroup per image, as engine_stack_kernel after its gather: the image's active count under the product's predicate
 // (once per image, for density and the stack selector), the wrapped int16 accumulator from the int32 sums, clipped ReLU, tail.
-// dynamic LDS: ft [L1] i32 | pair [L1] i32 | h1 [L2] i32 | h2 [L3] i32 | counts [4] i32
+// dynamic LDS: batch_lds.
 template <bool kFeatures, class Sel>
-__global__ __launch_bounds__(256) void engine_matrix_tail_kernel(const uint8_t* __restrict__ src, float threshold, int F, int oc,
-                                                                 const int32_t* __restrict__ sums, const int32_t* __restrict__ ft_b,
-                                                                 int quantized_one, const int8_t* __restrict__ l1_w,
-                                                                 const int32_t* __restrict__ l1_b, float l1_scale,
-                                                                 const int8_t* __restrict__ l2_w, const int32_t* __restrict__ l2_b,
-                                                                 int l2_scale, const int8_t* __restrict__ out_w,
-                                                                 const int32_t* __restrict__ out_b, float out_scale, int L1, int L2,
-                                                                 int L3, int C, float* __restrict__ logits, float* __restrict__ density,
-                                                                 Sel sel) {
+__global__ __launch_bounds__(256) void engine_matrix_tail_kernel(EngineNet net, const uint8_t* __restrict__ src,
+                                                                 const int32_t* __restrict__ sums, float* __restrict__ logits,
+                                                                 float* __restrict__ density, Sel sel) {
   extern __shared__ int32_t lds[];
-  int32_t* ft = lds;
-  int32_t* pair = ft + L1;
-  int32_t* h1 = pair + L1;
-  int32_t* h2 = h1 + L2;
-  int32_t* counts = h2 + L3;
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const EngineLds lay = batch_lds(net);
+  int32_t* counts = lds + lay.counts;
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, F = net.F;
   const uint8_t* __restrict__ row = src + (size_t)b * F;
   int count = 0;
-  for (int f0 = wave * 64; f0 < F; f0 += 256) {
-    const int f = f0 + lane;
-    bool on;
-    if constexpr (kFeatures) on = f < F && row[f] != 0;
-    else on = f < F && (float)(int8_t)row[f] > threshold && (f % oc) < 64;  // 64 channels per cell are bit-packed
-    count += __popcll(__ballot(on));
-  }
+  for (int f0 = wave * 64; f0 < F; f0 += 256) count += __popcll(__ballot(feature_on<kFeatures>(row, f0 + lane, net)));
   if (lane == 0) counts[wave] = count;
-  for (int col = tid; col < L1; col += 256) {
-    const int16_t v = (int16_t)(uint16_t)((uint32_t)ft_b[col] + (uint32_t)sums[(size_t)b * L1 + col]);  // int16 accumulator wraps
-    ft[col] = clamp_i((int32_t)v, 0, quantized_one);
-  }
+  for (int col = tid; col < net.L1; col += 256)
+    lds[col] = wrap_clip((int32_t)((uint32_t)net.ft_b[col] + (uint32_t)sums[(size_t)b * net.L1 + col]), net.quantized_one);
   __syncthreads();
   count = counts[0] + counts[1] + counts[2] + counts[3];
   if (tid == 0) density[b] = (float)count / (float)F;
-
-  if constexpr (Sel::kSelect)
-    engine_select_stack(sel, b, count, F, L1, L2, L3, C, l1_w, l1_b, l1_scale, l2_w, l2_b, l2_scale, out_w, out_b, out_scale);
-  engine_tail(ft, pair, h1, h2, l1_w, l1_b, l1_scale, l2_w, l2_b, l2_scale, out_w, out_b, out_scale, L1, L2, L3, C,
-              logits + (size_t)b * C);
+  engine_epilogue(net, sel, b, count, lds, lay, logits);
 }
 
 }  // namespace
@@ -805,41 +786,53 @@ static int engine_check_model(const nnue_engine_model* m, const nnue_engine_stac
   return NNUE_OK;
 }
 
+struct ConvGeometry {
+  int H, W, stride, OH, OW;
+};
+
 // The engine's own stride rule, ceil((H-1)/(g-1)) (nnue_engine.cpp:710-718) -- not the training stride -- and the
 // rejection of an image whose conv map would overrun the engine's grid buffer.
-static int engine_conv_geometry(const nnue_engine_model* m, int H, int W, const char* fn, int* stride_out, int* oh_out, int* ow_out) {
+static int engine_conv_geometry(const nnue_engine_model* m, int H, int W, const char* fn, ConvGeometry* out) {
+  NNUE_REQUIRE(H > 0 && W > 0, NNUE_E_ARG, "%s: H=%d W=%d must be positive", fn, H, W);
   const int g = m->grid, oc = m->oc, F = m->num_features;
   int stride = g > 1 ? (H - 1 + g - 2) / (g - 1) : (H > 1 ? H : 1);
   if (stride < 1) stride = 1;
   const int OH = (H + 2 - 3) / stride + 1, OW = (W + 2 - 3) / stride + 1;
   NNUE_REQUIRE(OH > 0 && OW > 0 && (long long)OH * OW * oc <= F, NNUE_E_SHAPE,
                "%s: a %dx%d image gives a %dx%d map that overruns the engine's %dx%d grid buffer", fn, H, W, OH, OW, g, g);
-  *stride_out = stride;
-  *oh_out = OH;
-  *ow_out = OW;
+  *out = {H, W, stride, OH, OW};
   return NNUE_OK;
 }
 
-// The tail's tensors as the kernels take them: the model's stack, or the base of the packed stacks (their scales travel in
-// the StackSel instead).
-struct EngineTailArgs {
-  const int8_t* l1_w;
-  const int32_t* l1_b;
-  float l1_scale;
-  const int8_t* l2_w;
-  const int32_t* l2_b;
-  int l2_scale;
-  const int8_t* out_w;
-  const int32_t* out_b;
-  float out_scale;
-};
-
-static EngineTailArgs engine_tail_args(const nnue_engine_model* m, const nnue_engine_stacks* st) {
-  if (st) return {st->l1_w, st->l1_b, 0.0f, st->l2_w, st->l2_b, 1, st->out_w, st->out_b, 0.0f};
-  return {m->l1_w, m->l1_b, m->l1_scale, m->l2_w, m->l2_b, (int)m->l2_scale, m->out_w, m->out_b, m->out_scale};
+static void engine_launch_conv(const nnue_engine_model* m, const float* images, int n, const ConvGeometry& g, void* conv, hipStream_t s) {
+  const int F = m->num_features;
+  hipLaunchKernelGGL(engine_conv_kernel, dim3((F + 255) / 256, n), dim3(256), 0, s, images, m->conv_w, m->conv_b, m->conv_scale, g.H,
+                     g.W, g.stride, g.OH, g.OW, m->oc, F, static_cast<int8_t*>(conv));
 }
 
-static StackSel engine_stack_sel(const nnue_engine_stacks* st, const int32_t* stack_in, int32_t* stack_out) {
+// What every launching entry point checks first: the call's pointers (`pointers`: all of them given), then the stacks argument
+// of a selecting call.  Its own argument checks, the model's tensors, a positive count and engine_check_model follow in the
+// entry point, in the order the ABI tests pin.
+static int engine_check_call(const char* fn, bool pointers, bool select, const nnue_engine_stacks* st, const void* stack_out) {
+  NNUE_REQUIRE(pointers, NNUE_E_ARG, "%s: null pointer", fn);
+  return select ? engine_check_stacks(st, stack_out, fn) : NNUE_OK;
+}
+
+// The kernels' argument block of a checked call: the model's own stack, or the base of the packed stacks (their scales travel
+// in the StackSel instead).
+static EngineNet engine_net(const nnue_engine_model* m, const nnue_engine_stacks* st) {
+  const float threshold = m->threshold;
+  const int q1 = (int)(int16_t)m->quantized_one, F = m->num_features, oc = m->oc, L1 = m->l1, L2 = m->l2, L3 = m->l3, C = m->classes;
+  if (st)
+    return {m->ft_w, m->ft_b, st->l1_w, st->l1_b, st->l2_w, st->l2_b, st->out_w, st->out_b, 0.0f, 1, 0.0f, threshold, q1, F, oc, L1, L2, L3, C};
+  return {m->ft_w, m->ft_b, m->l1_w, m->l1_b, m->l2_w, m->l2_b, m->out_w, m->out_b, m->l1_scale, (int)m->l2_scale, m->out_scale,
+          threshold, q1, F, oc, L1, L2, L3, C};
+}
+
+// Calls fn with the selector of the call: the StackSel of st, or NoStackSel without stacks.
+template <class Fn>
+static void engine_with_sel(const nnue_engine_stacks* st, const int32_t* stack_in, int32_t* stack_out, Fn fn) {
+  if (!st) return fn(NoStackSel{});
   StackSel sel{};
   sel.K = st->count;
   sel.stack_in = stack_in;
@@ -849,42 +842,31 @@ static StackSel engine_stack_sel(const nnue_engine_stacks* st, const int32_t* st
     sel.l2_scale[k] = (int)st->scales[3 * k + 1];
     sel.out_scale[k] = st->scales[3 * k + 2];
   }
-  return sel;
-}
-
-template <class Sel>
-static void engine_launch_stack(const nnue_engine_model* m, const EngineTailArgs& t, const int8_t* conv, int B, size_t lds,
-                                float* logits, float* density, Sel sel, hipStream_t s) {
-  hipLaunchKernelGGL((engine_stack_kernel<Sel>), dim3(B), dim3(256), lds, s, conv, m->threshold, m->num_features, m->oc, m->ft_w,
-                     m->ft_b, (int)(int16_t)m->quantized_one, t.l1_w, t.l1_b, t.l1_scale, t.l2_w, t.l2_b, t.l2_scale, t.out_w,
-                     t.out_b, t.out_scale, m->l1, m->l2, m->l3, m->classes, logits, density, sel);
+  fn(sel);
 }
 
 // nnue_engine_evaluate_logits (select == false; st, stack_in and stack_out unused) and nnue_engine_evaluate_logits_stacks.
 static int engine_evaluate(const char* fn, const nnue_engine_model* m, bool select, const nnue_engine_stacks* st,
                            const float* images, int B, int H, int W, const int32_t* stack_in, float* logits, float* density,
                            int32_t* stack_out, void* scratch, int64_t scratch_bytes, nnue_stream_t stream) {
-  NNUE_REQUIRE(m && images && logits && density && scratch, NNUE_E_ARG, "%s: null pointer", fn);
-  if (select)
-    if (int rc = engine_check_stacks(st, stack_out, fn)) return rc;
+  if (int rc = engine_check_call(fn, m && images && logits && density && scratch, select, st, stack_out)) return rc;
   NNUE_REQUIRE(engine_has_tensors(m, st), NNUE_E_ARG, "%s: model tensor missing", fn);
   NNUE_REQUIRE(B > 0 && H > 0 && W > 0, NNUE_E_ARG, "%s: B=%d H=%d W=%d must be positive", fn, B, H, W);
   if (int rc = engine_check_model(m, st, fn)) return rc;
-  const int oc = m->oc, F = m->num_features;
-  int stride, OH, OW;
-  if (int rc = engine_conv_geometry(m, H, W, fn, &stride, &OH, &OW)) return rc;
-  NNUE_REQUIRE(scratch_bytes >= (int64_t)B * F, NNUE_E_SCRATCH, "%s: scratch %lld < %lld bytes", fn, (long long)scratch_bytes,
-               (long long)B * F);
+  const EngineNet net = engine_net(m, st);
+  ConvGeometry geo{};
+  if (int rc = engine_conv_geometry(m, H, W, fn, &geo)) return rc;
+  NNUE_REQUIRE(scratch_bytes >= (int64_t)B * net.F, NNUE_E_SCRATCH, "%s: scratch %lld < %lld bytes", fn, (long long)scratch_bytes,
+               (long long)B * net.F);
   NNUE_REQUIRE((long long)B * H * W * 3 < (1ll << 40), NNUE_E_SHAPE, "%s: batch too large", fn);
-  const size_t lds = (size_t)(2 * m->l1 + m->l2 + m->l3 + 4) * sizeof(int32_t);
+  const size_t lds = batch_lds(net).bytes;
   NNUE_REQUIRE(lds <= 64 * 1024, NNUE_E_SHAPE, "%s: layer sizes need %zu bytes of LDS", fn, lds);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  int8_t* conv = static_cast<int8_t*>(scratch);
-  hipLaunchKernelGGL(engine_conv_kernel, dim3((F + 255) / 256, B), dim3(256), 0, s, images, m->conv_w, m->conv_b, m->conv_scale, H, W,
-                     stride, OH, OW, oc, F, conv);
-  const EngineTailArgs t = engine_tail_args(m, st);
-  if (select) engine_launch_stack(m, t, conv, B, lds, logits, density, engine_stack_sel(st, stack_in, stack_out), s);
-  else engine_launch_stack(m, t, conv, B, lds, logits, density, NoStackSel{}, s);
+  const uint8_t* conv = static_cast<const uint8_t*>(scratch);
+  engine_launch_conv(m, images, B, geo, scratch, s);
+  engine_with_sel(st, stack_in, stack_out, [&](auto sel) {
+    hipLaunchKernelGGL((engine_stack_kernel<decltype(sel)>), dim3(B), dim3(256), lds, s, net, conv, logits, density, sel);
+  });
   return nnue_launch_status(fn);
 }
 
@@ -906,13 +888,12 @@ extern "C" int64_t nnue_engine_stream_state_bytes(const nnue_engine_model* m, in
   return stream_layout(S, m->num_features, m->l1).total;
 }
 
-template <bool kFeatures, class Sel>
-static void engine_launch_stream(const nnue_engine_model* m, const EngineTailArgs& t, const int8_t* conv, const uint8_t* active,
-                                 int S, size_t lds, uint8_t* state, float* logits, float* density, int32_t* changed, Sel sel,
-                                 hipStream_t s) {
-  hipLaunchKernelGGL((engine_stream_kernel<kFeatures, Sel>), dim3(S), dim3(256), lds, s, conv, active, m->threshold, m->num_features,
-                     m->oc, S, m->ft_w, m->ft_b, (int)(int16_t)m->quantized_one, t.l1_w, t.l1_b, t.l1_scale, t.l2_w, t.l2_b,
-                     t.l2_scale, t.out_w, t.out_b, t.out_scale, m->l1, m->l2, m->l3, m->classes, state, logits, density, changed, sel);
+// The state checks of the stream entry points, after the prologue: the buffer's size and the kernel's LDS.
+static int engine_check_state(const char* fn, const nnue_engine_model* m, int S, int64_t state_bytes, size_t lds) {
+  const int64_t need = nnue_engine_stream_state_bytes(m, S);
+  NNUE_REQUIRE(state_bytes >= need, NNUE_E_SCRATCH, "%s: state %lld < %lld bytes", fn, (long long)state_bytes, (long long)need);
+  NNUE_REQUIRE(lds <= 64 * 1024, NNUE_E_SHAPE, "%s: layer and feature sizes need %zu bytes of LDS", fn, lds);
+  return NNUE_OK;
 }
 
 // nnue_engine_stream_step (select == false; st, stack_in and stack_out unused) and nnue_engine_stream_step_stacks.
@@ -920,43 +901,34 @@ static int engine_stream_step(const char* fn, const nnue_engine_model* m, bool s
                               const float* images, const uint8_t* active, int S, int H, int W, const int32_t* stack_in, void* state,
                               int64_t state_bytes, float* logits, float* density, int32_t* changed, int32_t* stack_out,
                               void* scratch, int64_t scratch_bytes, nnue_stream_t stream) {
-  NNUE_REQUIRE(m && state && logits && density && changed, NNUE_E_ARG, "%s: null pointer", fn);
-  if (select)
-    if (int rc = engine_check_stacks(st, stack_out, fn)) return rc;
+  if (int rc = engine_check_call(fn, m && state && logits && density && changed, select, st, stack_out)) return rc;
   NNUE_REQUIRE((images != nullptr) != (active != nullptr), NNUE_E_ARG, "%s: pass exactly one of images and active", fn);
   NNUE_REQUIRE(nnue_aligned16(state), NNUE_E_ARG, "%s: state must be 16-byte aligned", fn);
   NNUE_REQUIRE(engine_has_tensors(m, st), NNUE_E_ARG, "%s: model tensor missing", fn);
   NNUE_REQUIRE(S > 0, NNUE_E_ARG, "%s: S=%d must be positive", fn, S);
   if (int rc = engine_check_model(m, st, fn)) return rc;
-  const int oc = m->oc, F = m->num_features, L1 = m->l1, W64 = (F + 63) / 64;
-  const int64_t need = nnue_engine_stream_state_bytes(m, S);
-  NNUE_REQUIRE(state_bytes >= need, NNUE_E_SCRATCH, "%s: state %lld < %lld bytes", fn, (long long)state_bytes, (long long)need);
-  const size_t lds = (size_t)((2 * L1 + m->l2 + m->l3 + 8 + 1) & ~1) * sizeof(int32_t) + (size_t)2 * W64 * sizeof(uint64_t);
-  NNUE_REQUIRE(lds <= 64 * 1024, NNUE_E_SHAPE, "%s: layer and feature sizes need %zu bytes of LDS", fn, lds);
-  int stride = 1, OH = 0, OW = 0;
+  const EngineNet net = engine_net(m, st);
+  const size_t lds = stream_lds(net).bytes;
+  if (int rc = engine_check_state(fn, m, S, state_bytes, lds)) return rc;
+  ConvGeometry geo{};
   if (images) {
-    NNUE_REQUIRE(H > 0 && W > 0, NNUE_E_ARG, "%s: H=%d W=%d must be positive", fn, H, W);
-    if (int rc = engine_conv_geometry(m, H, W, fn, &stride, &OH, &OW)) return rc;
+    if (int rc = engine_conv_geometry(m, H, W, fn, &geo)) return rc;
     NNUE_REQUIRE(scratch, NNUE_E_ARG, "%s: images need scratch", fn);
-    NNUE_REQUIRE(scratch_bytes >= (int64_t)S * F, NNUE_E_SCRATCH, "%s: scratch %lld < %lld bytes", fn, (long long)scratch_bytes,
-                 (long long)S * F);
+    NNUE_REQUIRE(scratch_bytes >= (int64_t)S * net.F, NNUE_E_SCRATCH, "%s: scratch %lld < %lld bytes", fn, (long long)scratch_bytes,
+                 (long long)S * net.F);
     NNUE_REQUIRE((long long)S * H * W * 3 < (1ll << 40), NNUE_E_SHAPE, "%s: batch too large", fn);
   }
   hipStream_t s = static_cast<hipStream_t>(stream);
   uint8_t* sp = static_cast<uint8_t*>(state);
-  const EngineTailArgs t = engine_tail_args(m, st);
-  if (images) {
-    int8_t* conv = static_cast<int8_t*>(scratch);
-    hipLaunchKernelGGL(engine_conv_kernel, dim3((F + 255) / 256, S), dim3(256), 0, s, images, m->conv_w, m->conv_b, m->conv_scale, H,
-                       W, stride, OH, OW, oc, F, conv);
-    if (select)
-      engine_launch_stream<false>(m, t, conv, nullptr, S, lds, sp, logits, density, changed, engine_stack_sel(st, stack_in, stack_out), s);
-    else engine_launch_stream<false>(m, t, conv, nullptr, S, lds, sp, logits, density, changed, NoStackSel{}, s);
-  } else {
-    if (select)
-      engine_launch_stream<true>(m, t, nullptr, active, S, lds, sp, logits, density, changed, engine_stack_sel(st, stack_in, stack_out), s);
-    else engine_launch_stream<true>(m, t, nullptr, active, S, lds, sp, logits, density, changed, NoStackSel{}, s);
-  }
+  if (images) engine_launch_conv(m, images, S, geo, scratch, s);
+  engine_with_sel(st, stack_in, stack_out, [&](auto sel) {
+    if (images)
+      hipLaunchKernelGGL((engine_stream_kernel<false, decltype(sel)>), dim3(S), dim3(256), lds, s, net,
+                         static_cast<const uint8_t*>(scratch), S, sp, logits, density, changed, sel);
+    else
+      hipLaunchKernelGGL((engine_stream_kernel<true, decltype(sel)>), dim3(S), dim3(256), lds, s, net, active, S, sp, logits, density,
+                         changed, sel);
+  });
   return nnue_launch_status(fn);
 }
 
@@ -975,26 +947,13 @@ extern "C" int nnue_engine_stream_step_stacks(const nnue_engine_model* m, const 
                             density, changed, stack_out, scratch, scratch_bytes, stream);
 }
 
-template <class Sel>
-static void engine_launch_stream_update(const nnue_engine_model* m, const EngineTailArgs& t, const int32_t* added,
-                                        const int32_t* added_off, int n_added, const int32_t* removed, const int32_t* removed_off,
-                                        int n_removed, int S, int rebuild, size_t lds, uint8_t* state, float* logits, float* density,
-                                        int32_t* changed, Sel sel, hipStream_t s) {
-  hipLaunchKernelGGL((engine_stream_update_kernel<Sel>), dim3(S), dim3(256), lds, s, added, added_off, n_added, removed, removed_off,
-                     n_removed, rebuild, m->num_features, S, m->ft_w, m->ft_b, (int)(int16_t)m->quantized_one, t.l1_w, t.l1_b,
-                     t.l1_scale, t.l2_w, t.l2_b, t.l2_scale, t.out_w, t.out_b, t.out_scale, m->l1, m->l2, m->l3, m->classes, state,
-                     logits, density, changed, sel);
-}
-
 extern "C" int nnue_engine_stream_update(const nnue_engine_model* m, const nnue_engine_stacks* st, const int32_t* added,
                                          const int32_t* added_off, int64_t n_added, const int32_t* removed,
                                          const int32_t* removed_off, int64_t n_removed, int S, int rebuild, const int32_t* stack_in,
                                          void* state, int64_t state_bytes, float* logits, float* density, int32_t* changed,
                                          int32_t* stack_out, nnue_stream_t stream) {
   const char* fn = "nnue_engine_stream_update";
-  NNUE_REQUIRE(m && state && logits && density && changed, NNUE_E_ARG, "%s: null pointer", fn);
-  if (st)
-    if (int rc = engine_check_stacks(st, stack_out, fn)) return rc;
+  if (int rc = engine_check_call(fn, m && state && logits && density && changed, st != nullptr, st, stack_out)) return rc;
   NNUE_REQUIRE(n_added >= 0 && n_removed >= 0, NNUE_E_ARG, "%s: n_added=%lld n_removed=%lld must not be negative", fn,
                (long long)n_added, (long long)n_removed);
   NNUE_REQUIRE((n_added == 0 || (added && added_off)) && (n_removed == 0 || (removed && removed_off)), NNUE_E_ARG,
@@ -1003,34 +962,26 @@ extern "C" int nnue_engine_stream_update(const nnue_engine_model* m, const nnue_
   NNUE_REQUIRE(engine_has_tensors(m, st), NNUE_E_ARG, "%s: model tensor missing", fn);
   NNUE_REQUIRE(S > 0, NNUE_E_ARG, "%s: S=%d must be positive", fn, S);
   if (int rc = engine_check_model(m, st, fn)) return rc;
-  const int F = m->num_features, L1 = m->l1, W64 = (F + 63) / 64;
-  const int64_t need = nnue_engine_stream_state_bytes(m, S);
-  NNUE_REQUIRE(state_bytes >= need, NNUE_E_SCRATCH, "%s: state %lld < %lld bytes", fn, (long long)state_bytes, (long long)need);
-  const size_t lds = (size_t)((2 * L1 + m->l2 + m->l3 + 10 + kUpdateChunk + 1) & ~1) * sizeof(int32_t) + (size_t)W64 * sizeof(uint64_t);
-  NNUE_REQUIRE(lds <= 64 * 1024, NNUE_E_SHAPE, "%s: layer and feature sizes need %zu bytes of LDS", fn, lds);
+  const EngineNet net = engine_net(m, st);
+  const size_t lds = update_lds(net).bytes;
+  if (int rc = engine_check_state(fn, m, S, state_bytes, lds)) return rc;
   // the offsets are int32, so ids beyond 2^31 - 1 of a buffer are out of every range's reach
   const int na = (int)(n_added > INT32_MAX ? INT32_MAX : n_added), nr = (int)(n_removed > INT32_MAX ? INT32_MAX : n_removed);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  uint8_t* sp = static_cast<uint8_t*>(state);
-  const EngineTailArgs t = engine_tail_args(m, st);
-  if (st)
-    engine_launch_stream_update(m, t, added, added_off, na, removed, removed_off, nr, S, rebuild != 0, lds, sp, logits, density, changed,
-                                engine_stack_sel(st, stack_in, stack_out), s);
-  else
-    engine_launch_stream_update(m, t, added, added_off, na, removed, removed_off, nr, S, rebuild != 0, lds, sp, logits, density, changed,
-                                NoStackSel{}, s);
+  engine_with_sel(st, stack_in, stack_out, [&](auto sel) {
+    hipLaunchKernelGGL((engine_stream_update_kernel<decltype(sel)>), dim3(S), dim3(256), lds, s, net, added, added_off, na, removed,
+                       removed_off, nr, (int)(rebuild != 0), S, static_cast<uint8_t*>(state), logits, density, changed, sel);
+  });
   return nnue_launch_status(fn);
 }
 
 // ---- the matrix form's entry points ---------------------------------------------------------------------------------
-static size_t engine_tail_lds(const nnue_engine_model* m) { return (size_t)(2 * m->l1 + m->l2 + m->l3 + 4) * sizeof(int32_t); }
-
 // What the matrix form itself can run: the plane count, the tail's LDS, and F small enough that no int32 sum can overflow.
 static bool engine_matrix_shape_ok(const nnue_engine_model* m, int planes) {
   if (planes != 1 && planes != 2) return false;
   if (m->num_features <= 0 || m->num_features >= kMxMaxFeatures) return false;
   if (m->l1 < 2 || m->l1 > 256 * kMaxColsPerThread || m->l2 < 1 || m->l3 < 1) return false;
-  return engine_tail_lds(m) <= 64 * 1024;
+  return batch_lds(engine_net(m, nullptr)).bytes <= 64 * 1024;
 }
 
 extern "C" int nnue_engine_matrix_supported(const nnue_engine_model* m, int B, int planes) {
@@ -1103,12 +1054,15 @@ static void engine_launch_product(const nnue_engine_model* m, const uint8_t* src
                      sums);
 }
 
+// The product and the tail over one source of bytes: the conv map (kFeatures == false) or the caller's feature map.
 template <bool kFeatures, class Sel>
-static void engine_launch_matrix_tail(const nnue_engine_model* m, const EngineTailArgs& t, const uint8_t* src, const int32_t* sums, int B,
-                                      float* logits, float* density, Sel sel, hipStream_t s) {
-  hipLaunchKernelGGL((engine_matrix_tail_kernel<kFeatures, Sel>), dim3(B), dim3(256), engine_tail_lds(m), s, src, m->threshold,
-                     m->num_features, m->oc, sums, m->ft_b, (int)(int16_t)m->quantized_one, t.l1_w, t.l1_b, t.l1_scale, t.l2_w, t.l2_b,
-                     t.l2_scale, t.out_w, t.out_b, t.out_scale, m->l1, m->l2, m->l3, m->classes, logits, density, sel);
+static void engine_launch_matrix(const nnue_engine_model* m, const EngineNet& net, int planes, const uint8_t* src, int B,
+                                 const MatrixLayout& lay, const int8_t* tp, int32_t* sums, float* logits, float* density, Sel sel,
+                                 hipStream_t s) {
+  if (planes == 1) engine_launch_product<1, kFeatures>(m, src, B, lay, tp, sums, s);
+  else engine_launch_product<2, kFeatures>(m, src, B, lay, tp, sums, s);
+  hipLaunchKernelGGL((engine_matrix_tail_kernel<kFeatures, Sel>), dim3(B), dim3(256), batch_lds(net).bytes, s, net, src, sums, logits,
+                     density, sel);
 }
 
 extern "C" int nnue_engine_evaluate_logits_matrix(const nnue_engine_model* m, const nnue_engine_stacks* st, const void* table_planes,
@@ -1116,25 +1070,22 @@ extern "C" int nnue_engine_evaluate_logits_matrix(const nnue_engine_model* m, co
                                                   const int32_t* stack_in, float* logits, float* density, int32_t* stack_out,
                                                   void* scratch, int64_t scratch_bytes, nnue_stream_t stream) {
   const char* fn = "nnue_engine_evaluate_logits_matrix";
-  NNUE_REQUIRE(m && table_planes && logits && density && scratch, NNUE_E_ARG, "%s: null pointer", fn);
-  if (st)
-    if (int rc = engine_check_stacks(st, stack_out, fn)) return rc;
+  if (int rc = engine_check_call(fn, m && table_planes && logits && density && scratch, st != nullptr, st, stack_out)) return rc;
   NNUE_REQUIRE((images != nullptr) != (active != nullptr), NNUE_E_ARG, "%s: pass exactly one of images and active", fn);
   NNUE_REQUIRE(nnue_aligned16(table_planes), NNUE_E_ARG, "%s: table_planes must be 16-byte aligned", fn);
   NNUE_REQUIRE(engine_has_tensors(m, st), NNUE_E_ARG, "%s: model tensor missing", fn);
   NNUE_REQUIRE(B > 0, NNUE_E_ARG, "%s: B=%d must be positive", fn, B);
   if (int rc = engine_check_model(m, st, fn)) return rc;
-  const int oc = m->oc, F = m->num_features, L1 = m->l1;
+  const EngineNet net = engine_net(m, st);
   NNUE_REQUIRE(planes == 1 || planes == 2, NNUE_E_SHAPE, "%s: planes=%d (1 or 2)", fn, planes);
-  NNUE_REQUIRE(F < kMxMaxFeatures, NNUE_E_SHAPE, "%s: num_features %d >= 2^24 (an int32 sum could overflow)", fn, F);
-  NNUE_REQUIRE(engine_tail_lds(m) <= 64 * 1024, NNUE_E_SHAPE, "%s: layer sizes need %zu bytes of LDS", fn, engine_tail_lds(m));
-  int stride = 1, OH = 0, OW = 0;
+  NNUE_REQUIRE(net.F < kMxMaxFeatures, NNUE_E_SHAPE, "%s: num_features %d >= 2^24 (an int32 sum could overflow)", fn, net.F);
+  NNUE_REQUIRE(batch_lds(net).bytes <= 64 * 1024, NNUE_E_SHAPE, "%s: layer sizes need %zu bytes of LDS", fn, batch_lds(net).bytes);
+  ConvGeometry geo{};
   if (images) {
-    NNUE_REQUIRE(H > 0 && W > 0, NNUE_E_ARG, "%s: H=%d W=%d must be positive", fn, H, W);
-    if (int rc = engine_conv_geometry(m, H, W, fn, &stride, &OH, &OW)) return rc;
+    if (int rc = engine_conv_geometry(m, H, W, fn, &geo)) return rc;
     NNUE_REQUIRE((long long)B * H * W * 3 < (1ll << 40), NNUE_E_SHAPE, "%s: batch too large", fn);
   }
-  const MatrixLayout lay = matrix_layout(B, F, L1);
+  const MatrixLayout lay = matrix_layout(B, net.F, net.L1);
   NNUE_REQUIRE(scratch_bytes >= lay.total, NNUE_E_SCRATCH, "%s: scratch %lld < %lld bytes", fn, (long long)scratch_bytes,
                (long long)lay.total);
   NNUE_REQUIRE((reinterpret_cast<uintptr_t>(scratch) & 3u) == 0, NNUE_E_ARG, "%s: scratch must be 4-byte aligned", fn);
@@ -1142,19 +1093,10 @@ extern "C" int nnue_engine_evaluate_logits_matrix(const nnue_engine_model* m, co
   uint8_t* conv = static_cast<uint8_t*>(scratch);
   int32_t* sums = reinterpret_cast<int32_t*>(conv + lay.sums);
   const int8_t* tp = static_cast<const int8_t*>(table_planes);
-  const EngineTailArgs t = engine_tail_args(m, st);
-  if (images) {
-    hipLaunchKernelGGL(engine_conv_kernel, dim3((F + 255) / 256, B), dim3(256), 0, s, images, m->conv_w, m->conv_b, m->conv_scale, H, W,
-                       stride, OH, OW, oc, F, reinterpret_cast<int8_t*>(conv));
-    if (planes == 1) engine_launch_product<1, false>(m, conv, B, lay, tp, sums, s);
-    else engine_launch_product<2, false>(m, conv, B, lay, tp, sums, s);
-    if (st) engine_launch_matrix_tail<false>(m, t, conv, sums, B, logits, density, engine_stack_sel(st, stack_in, stack_out), s);
-    else engine_launch_matrix_tail<false>(m, t, conv, sums, B, logits, density, NoStackSel{}, s);
-  } else {
-    if (planes == 1) engine_launch_product<1, true>(m, active, B, lay, tp, sums, s);
-    else engine_launch_product<2, true>(m, active, B, lay, tp, sums, s);
-    if (st) engine_launch_matrix_tail<true>(m, t, active, sums, B, logits, density, engine_stack_sel(st, stack_in, stack_out), s);
-    else engine_launch_matrix_tail<true>(m, t, active, sums, B, logits, density, NoStackSel{}, s);
-  }
+  if (images) engine_launch_conv(m, images, B, geo, conv, s);
+  engine_with_sel(st, stack_in, stack_out, [&](auto sel) {
+    if (images) engine_launch_matrix<false>(m, net, planes, conv, B, lay, tp, sums, logits, density, sel, s);
+    else engine_launch_matrix<true>(m, net, planes, active, B, lay, tp, sums, logits, density, sel, s);
+  });
   return nnue_launch_status(fn);
 }

@@ -136,6 +136,23 @@ class EngineModel:
         """Layer stacks the model selects among: K after load(bucket="auto"), else 1."""
         return 1 if self._stacks is None else int(self._stacks.count)
 
+    def _on_device(self, t: torch.Tensor) -> bool:
+        """Whether ``t`` is a device tensor on the model's device."""
+        return t.is_cuda and (self.device.index is None or t.device.index == self.device.index)
+
+    def _outputs(self, n: int, changed: bool = False, zero_stacks: bool = False):
+        """What a call on n images or streams writes: (logits [n, C] float32, density [n] float32, changed [n] int32 or None,
+        used [n] int32).  ``used`` takes the stacks of a stack-selecting model; a single-stack model has None there, or zeros
+        where the caller returns them (zero_stacks)."""
+        logits = torch.empty((n, self.num_classes), dtype=torch.float32, device=self.device)
+        density = torch.empty((n,), dtype=torch.float32, device=self.device)
+        delta = torch.empty((n,), dtype=torch.int32, device=self.device) if changed else None
+        if self._stacks is not None:
+            used = torch.empty((n,), dtype=torch.int32, device=self.device)
+        else:
+            used = torch.zeros((n,), dtype=torch.int32, device=self.device) if zero_stacks else None
+        return logits, density, delta, used
+
     def _stack_arg(self, stacks: Optional[torch.Tensor], n: int, what: str) -> Optional[torch.Tensor]:
         """The caller's stack indices as the int32 [n] device tensor the C call takes (outside [0, K) = stack 0)."""
         if stacks is None:
@@ -409,15 +426,9 @@ class EngineModel:
                          stacks: Optional[torch.Tensor], return_stacks: bool):
         self.prepare_matrix()
         scratch = self._matrix_scratch_for(b)
-        logits = torch.empty((b, self.num_classes), dtype=torch.float32, device=self.device)
-        density = torch.empty((b,), dtype=torch.float32, device=self.device)
+        logits, density, _, used = self._outputs(b, zero_stacks=return_stacks)
         src = images if images is not None else active
-        if self._stacks is None:
-            used = torch.zeros((b,), dtype=torch.int32, device=self.device) if return_stacks else None
-            st, used_ptr = None, 0
-        else:
-            used = torch.empty((b,), dtype=torch.int32, device=self.device)
-            st, used_ptr = ctypes.addressof(self._stacks), used.data_ptr()
+        st, used_ptr = (None, 0) if self._stacks is None else (ctypes.addressof(self._stacks), used.data_ptr())
         lib._call("nnue_engine_evaluate_logits_matrix", ctypes.addressof(self._c), st, self._planes.data_ptr(), self.table_planes,
                   lib._ptr(images), lib._ptr(active), b, h, w, lib._ptr(stacks), logits.data_ptr(), density.data_ptr(), used_ptr,
                   scratch.data_ptr(), scratch.numel(), lib._stream(src))
@@ -439,7 +450,7 @@ class EngineModel:
             raise TypeError(f"active: expected a tensor, got {type(active).__name__}")
         if active.dtype not in (torch.bool, torch.uint8):
             raise ValueError(f"active: expected dtype torch.bool or torch.uint8, got {active.dtype}")
-        if not active.is_cuda or (self.device.index is not None and active.device.index != self.device.index):
+        if not self._on_device(active):
             raise ValueError(f"active: tensor is on {active.device}, the model on {self.device} (no CPU fallback in this build)")
         f = int(self.header["num_features"])
         if active.dim() != 2 or active.shape[0] < 1 or active.shape[1] != f:
@@ -479,14 +490,11 @@ class EngineModel:
         if self._path(path, b, "evaluate_logits") == "matrix":
             return self._evaluate_matrix(images, None, b, h, w, stacks, return_stacks)
         self._scratch_for(b)
-        logits = torch.empty((b, self.num_classes), dtype=torch.float32, device=self.device)
-        density = torch.empty((b,), dtype=torch.float32, device=self.device)
+        logits, density, _, used = self._outputs(b, zero_stacks=return_stacks)
         if self._stacks is None:
             lib._call("nnue_engine_evaluate_logits", ctypes.addressof(self._c), images.data_ptr(), b, h, w, logits.data_ptr(),
                       density.data_ptr(), self._scratch.data_ptr(), self._scratch.numel(), lib._stream(images))
-            used = torch.zeros((b,), dtype=torch.int32, device=self.device) if return_stacks else None
         else:
-            used = torch.empty((b,), dtype=torch.int32, device=self.device)
             lib._call("nnue_engine_evaluate_logits_stacks", ctypes.addressof(self._c), ctypes.addressof(self._stacks),
                       images.data_ptr(), b, h, w, lib._ptr(stacks), logits.data_ptr(), density.data_ptr(), used.data_ptr(),
                       self._scratch.data_ptr(), self._scratch.numel(), lib._stream(images))
@@ -586,8 +594,7 @@ class EngineStream:
             raise TypeError(f"{what}: expected a tensor, got {type(t).__name__}")
         if t.dtype not in dtypes:
             raise ValueError(f"{what}: expected dtype {' or '.join(str(d) for d in dtypes)}, got {t.dtype}")
-        dev = self.model.device
-        if not t.is_cuda or (dev.index is not None and t.device.index != dev.index):
+        if not self.model._on_device(t):
             raise ValueError(f"{what}: tensor is on {t.device}, the stream's state on {self.model.device} "
                              "(no CPU fallback in this build)")
         if t.dim() < 1 or t.shape[0] != self.num_streams:
@@ -600,9 +607,7 @@ class EngineStream:
             self._valid.fill_(0)
             self._generation = m.generation
         stacks = m._stack_arg(stacks, s, "EngineStream")
-        logits = torch.empty((s, m.num_classes), dtype=torch.float32, device=m.device)
-        density = torch.empty((s,), dtype=torch.float32, device=m.device)
-        changed = torch.empty((s,), dtype=torch.int32, device=m.device)
+        logits, density, changed, used = m._outputs(s, changed=True)
         scratch = m._scratch_for(s) if images is not None else None
         src = images if images is not None else active
         if m._stacks is None:
@@ -610,7 +615,6 @@ class EngineStream:
                       self.state.data_ptr(), self.state.numel(), logits.data_ptr(), density.data_ptr(), changed.data_ptr(),
                       lib._ptr(scratch), 0 if scratch is None else scratch.numel(), lib._stream(src))
         else:
-            used = torch.empty((s,), dtype=torch.int32, device=m.device)
             lib._call("nnue_engine_stream_step_stacks", ctypes.addressof(m._c), ctypes.addressof(m._stacks), lib._ptr(images),
                       lib._ptr(active), s, h, w, lib._ptr(stacks), self.state.data_ptr(), self.state.numel(), logits.data_ptr(),
                       density.data_ptr(), changed.data_ptr(), used.data_ptr(), lib._ptr(scratch),
@@ -647,7 +651,7 @@ class EngineStream:
             for t, name in ((ids, "ids"), (offsets, "offsets")):
                 if t.dtype not in (torch.int32, torch.int64):
                     raise ValueError(f"{what}: {name} must be int32 or int64, got {t.dtype}")
-                if not t.is_cuda or (dev.index is not None and t.device.index != dev.index):
+                if not self.model._on_device(t):
                     raise ValueError(f"{what}: {name} is on {t.device}, the stream's state on {dev} (no CPU fallback in this build)")
             if ids.dim() != 1 or ids.numel() > _INT32_MAX:
                 raise ValueError(f"{what}: ids must have one dimension and fewer than 2^31 elements, got shape {tuple(ids.shape)}")
@@ -668,10 +672,7 @@ class EngineStream:
         a_ids, a_off = self._csr(added, "added")
         r_ids, r_off = self._csr(removed, "removed")
         stacks = m._stack_arg(stacks, s, "EngineStream")
-        logits = torch.empty((s, m.num_classes), dtype=torch.float32, device=m.device)
-        density = torch.empty((s,), dtype=torch.float32, device=m.device)
-        changed = torch.empty((s,), dtype=torch.int32, device=m.device)
-        used = None if m._stacks is None else torch.empty((s,), dtype=torch.int32, device=m.device)
+        logits, density, changed, used = m._outputs(s, changed=True)
         if fresh:
             self._valid.fill_(0)
         # after a requantize the stored sets are still right and only the sums are stale: one rebuild instead of a reset

@@ -403,3 +403,51 @@ def test_evaluate_compiled_model_selects_stacks(tmp_path, cases):
     want = evaluate.compute_metrics(logits, y.cuda())
     assert all(metrics[k] == want[k] for k in want)
     assert metrics["latent_density"] == float(density.double().mean().item())
+
+
+@pytest.mark.parametrize("K", [1, 2])
+def test_every_entry_agrees_past_the_first_column_slot(tmp_path, K):
+    """L1 = 320: a thread owns columns tid and tid + 256, and the second one exists only for tid < 64, so the row walk's
+    ``col < L1`` guard decides in slot 1.  F = 5*5*6 = 150 is three 64-bit words with a ragged last one.  Every way into the
+    engine -- gather, matrix, feature maps, stream steps, refresh + a sparse update -- must give the same bits, the oracle's.
+    K = 1 is the plain single-stack load, K = 2 selects per image."""
+    c = Case(tmp_path, (5, 6, 320, 8, 8, 3, 17), K, 5)  # 17x17: stride 4, a 5x5 map, so all 150 ids can turn on
+    assert c.F == 150 and c.ref["l1"] == 320
+    engine = EngineModel.load(c.path, bucket="auto") if K > 1 else EngineModel.load(c.path)
+    assert engine.num_stacks == K
+    x = c.images.cuda()
+    maps = torch.from_numpy(np.stack([_ids(c, c.images[i]) for i in range(c.B)]))
+    assert [int(n) for n in maps.sum(1)] == c.counts and min(c.counts) == 0 and max(c.counts) == c.F
+
+    want = engine.evaluate_logits(x, path="gather", return_stacks=True)
+    got = {"matrix": engine.evaluate_logits(x, path="matrix", return_stacks=True),
+           "features": engine.evaluate_features(maps.cuda(), return_stacks=True)}
+    stream = engine.stream(c.B)
+    got["step"] = stream.step(x)[:2] + (stream.stacks,)
+    stream = engine.stream(c.B)
+    got["step_features"] = stream.step_features(maps.cuda())[:2] + (stream.stacks,)
+    # refresh to a set three ids short and three ids over, then one update back: with a duplicate and an id outside [0, F)
+    start, added, removed = maps.clone(), [], []
+    for s in range(c.B):
+        on, off = np.nonzero(maps[s].numpy())[0], np.nonzero(~maps[s].numpy())[0]
+        add, rem = [int(i) for i in on[1::max(1, on.size // 3)][:3]], [int(i) for i in off[::max(1, off.size // 3)][:3]]
+        start[s, torch.tensor(add, dtype=torch.long)] = False
+        start[s, torch.tensor(rem, dtype=torch.long)] = True
+        added.append(add + add[:1] + [c.F + 5])
+        removed.append(rem + rem[:1] + [-1])
+    assert any(len(a) == 5 and len(r) == 5 for a, r in zip(added, removed))
+    stream = engine.stream(c.B)
+    stream.refresh([np.nonzero(start[s].numpy())[0] for s in range(c.B)])
+    logits, density, changed = stream.update(added, removed)
+    assert [int(v) for v in changed] == [len(set(a)) + len(set(r)) - 2 for a, r in zip(added, removed)]
+    got["update"] = (logits, density, stream.stacks)
+
+    for name, (logits, density, stack) in got.items():
+        assert torch.equal(logits, want[0]), name
+        assert torch.equal(density, want[1]), name
+        assert torch.equal(stack, want[2]), name
+    assert [int(k) for k in want[2]] == c.stacks and set(c.stacks) == set(range(K))
+    for i in range(c.B):
+        want_logits, want_density = c.oracle(i, c.stacks[i])
+        assert np.array_equal(want[0][i].cpu().numpy(), want_logits), i
+        assert float(want[1][i]) == float(want_density), i
