@@ -3,7 +3,7 @@
 ``EngineModel.load(path)`` parses a ``.nnue`` file the way ``NNUEEvaluator::load_model`` does
 (engine/src/nnue_engine.cpp:544-657; same rejections) and keeps its quantised tensors in device memory;
 ``evaluate_logits(images)`` is ``NNUEEvaluator::evaluate_logits`` (nnue_engine.cpp:704-734) for a whole batch --
-bit-identical to the C++ engine (tests/golden/engine_cases.npz holds outputs of the real engine).
+bit-identical to the C++ engine (tests/golden/engine_cases.npz and engine_shapes.npz hold outputs of the real engine).
 ``stream(S)`` is ``NNUEEvaluator::evaluate_incremental`` (nnue_engine.cpp:739-786) for S independent frame sequences: each
 step updates a stored int16 accumulator by the features that changed, with the same bits as ``evaluate_logits``; its
 ``update(added, removed)`` takes just those features as two id lists (``NNUEEvaluator::update_features``, :818-821).

@@ -3,7 +3,9 @@
 
 Pinned against outputs of the real engine: `oracle/_ref/nnue_inference` (the reference's own sources compiled by
 oracle/Makefile) was run on the committed `.nnue` fixtures; tests/golden/make_golden_engine.py holds the recipe and
-tests/golden/engine_cases.npz the inputs and printed outputs.  Only tests/, __graft_entry__.smoke() and bench.py's
+tests/golden/engine_cases.npz the inputs and printed outputs; tests/golden/engine_shapes.npz (oracle/engine_driver.cpp,
+tests/golden/make_golden_engine_shapes.py) holds the same for frames with W != H, more than 64 channels per cell and
+`bucket` 0..K, with the engine's active feature ids.  Only tests/, __graft_entry__.smoke() and bench.py's
 cpu_baseline leg may import this module.
 
 The engine has three behaviours that are easy to miss and are kept here exactly as they are:

@@ -1,6 +1,9 @@
 """Per-image layer-stack selection in the engine's integer inference (EngineModel.load(bucket="auto"),
 nnue_engine_evaluate_logits_stacks, nnue_engine_stream_step_stacks): bit-identical to the engine oracle with the stack the
 rule -- or the caller -- picks, for whole batches and for the incremental per-stream form.  ``-m gpu``.
+The oracle's own `bucket` argument is held to the real C++ engine at indices 0..4 of a K = 4 file by
+tests/golden/engine_shapes.npz (tests/test_engine_oracle.py), and test_gpu_engine_recorded_shapes.py holds the same entry points
+to that record directly; what rests on the oracle alone here are the other stack counts (K = 2, 3, 8, 64) and shapes.
 
 Models are built as test_gpu_engine.test_fresh_models_against_the_oracle builds them (table x3 so the int16 sums wrap, uniform
 bias) with K layer stacks and a non-negative conv, so that a bright region turns every channel on and a dark one every channel

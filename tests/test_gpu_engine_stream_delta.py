@@ -1,6 +1,8 @@
 """Sparse add / remove lists on the engine's streams (EngineStream.update / refresh / snapshot / restore,
 nnue_engine_stream_update): set semantics on dirty lists, bit-identical to the oracle's ft_forward + forward_multiclass on the
-resulting sets -- hence to ``evaluate_features`` and the real C++ engine -- whatever the history.  ``-m gpu``."""
+resulting sets -- hence to ``evaluate_features`` and the real C++ engine -- whatever the history.  ``-m gpu``.
+"The real C++ engine" is reached through the oracle here; refresh / update between id sets RECORDED from that engine, with its
+recorded logits as the answer, is test_gpu_engine_recorded_shapes.py (tests/golden/engine_shapes.npz)."""
 import numpy as np
 import pytest
 import torch
