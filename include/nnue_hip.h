@@ -753,6 +753,66 @@ int nnue_engine_evaluate_logits_matrix(const nnue_engine_model* m, const nnue_en
                                        const int32_t* stack_in, float* logits, float* density, int32_t* stack_out,
                                        void* scratch, int64_t scratch_bytes, nnue_stream_t stream);
 
+/* ---- the engine's integer inference from uint8 frames -------------------------------------------------------------
+ *
+ * Every source of images is uint8 -- the dataset store of nnue_load_batch ([N][H][W][3]), a camera's frames -- and the engine's
+ * first act on a float is q = (int32)(x * conv_scale) (ConvLayer::forward, engine/src/nnue_engine.cpp:48-158).  The calls below
+ * take the bytes themselves: a frame is 3*H*W uint8 u[0 .. 3HW), HWC, and stands for the flat float buffer x[0 .. 3HW) the
+ * engine indexes HWC,
+ *     layout 0 (chw)  x[i] = norm(u[(i mod HW)*3 + i div HW], i div HW) -- the memory nnue_load_batch(augment = 0) writes for the
+ *                     image, a CHW tensor, handed to the engine flat as the reference hands it (evaluate.py:150-161): the
+ *                     reference's compiled metric, quirk included;
+ *     layout 1 (hwc)  x[i] = norm(u[i], i mod 3) -- the frame is what the engine's indexing means;
+ *     norm(v, c) = ((float)v - mean255[c]) * inv_std255[c] in float32, in this order (A.Normalize, data/datasets.py:366-369),
+ *     mean255[c] = mean[c] * 255.0f and inv_std255[c] = 1.0f / (std[c] * 255.0f) formed by the caller in float32; with the
+ *     ImageNet constants they are nnue_load_batch's own, bit for bit.
+ * From x on everything is the float call: with layout 0 and those constants a u8 call is bit-identical to its float twin on
+ * nnue_load_batch(augment = 0) of the same indices -- logits, density, changed and the stacks used.  The float batch is never
+ * written: the front forms the 768 possible q once per workgroup by the expression above and the conv is integer arithmetic.
+ * The struct is read on the host; data and indices are device memory.  indices[b] is clamped to [0, count) as nnue_load_batch
+ * clamps it; without indices frame b is data + b*3*H*W.  No load touches a byte outside [data, data + count*3*H*W). */
+typedef struct nnue_engine_u8_frames {
+  const uint8_t* data;    /* device: count frames of 3*H*W bytes, HWC; any byte alignment */
+  const int64_t* indices; /* device [B] into data, or NULL: frame b is data + b*3*H*W (then count >= B) */
+  int64_t count;          /* frames in data, >= 1 */
+  int32_t layout;         /* 0 chw (the memory nnue_load_batch writes), 1 hwc */
+  float mean255[3], inv_std255[3];
+} nnue_engine_u8_frames;
+
+/* NNUEEvaluator::evaluate_logits (engine/src/nnue_engine.cpp:704-734) for B uint8 frames -- the logits
+ * evaluate_compiled_model's per-image engine call obtains (evaluate.py:150-161) on Normalize's output (data/datasets.py:366-369)
+ * -- with the conv (nnue_engine.cpp:48-158) read from the bytes as defined above.  st == NULL: m's own stack, as
+ * nnue_engine_evaluate_logits; else per-image selection as nnue_engine_evaluate_logits_stacks (stack_in, stack_out as there;
+ * stack_out required iff st).  scratch >= nnue_engine_scratch(m, B).  Checks and codes as those two calls; NNUE_E_ARG also for a
+ * null src or src->data, a layout outside {0, 1}, count < 1, count < B without indices, a constant that is not finite,
+ * inv_std255 <= 0, and constants under which a byte times m->conv_scale leaves int32; NNUE_E_SHAPE also where the source rows
+ * of one output row exceed a workgroup's LDS (frames wider than about 1700 pixels) or a frame holds 2^31 bytes.  No call copies
+ * between host and device, allocates or synchronises; fit for stream capture. */
+int nnue_engine_evaluate_logits_u8(const nnue_engine_model* m, const nnue_engine_stacks* st /* NULL: m's own stack */,
+                                   const nnue_engine_u8_frames* src, int B, int H, int W, const int32_t* stack_in,
+                                   float* logits, float* density, int32_t* stack_out, void* scratch, int64_t scratch_bytes,
+                                   nnue_stream_t stream);
+
+/* nnue_engine_evaluate_logits_matrix (NNUEEvaluator::evaluate_logits, engine/src/nnue_engine.cpp:704-734; evaluate.py:150-161)
+ * with the conv bytes formed from uint8 frames (nnue_engine.cpp:48-158 on Normalize's output, data/datasets.py:366-369) as
+ * nnue_engine_evaluate_logits_u8 forms them; the product and the tail are the float twin's launches.  table_planes, planes,
+ * scratch (>= nnue_engine_matrix_scratch(m, B, planes), 4-byte aligned) and codes as the float twin, src and its refusals as
+ * nnue_engine_evaluate_logits_u8. */
+int nnue_engine_evaluate_logits_matrix_u8(const nnue_engine_model* m, const nnue_engine_stacks* st, const void* table_planes,
+                                          int planes, const nnue_engine_u8_frames* src, int B, int H, int W,
+                                          const int32_t* stack_in, float* logits, float* density, int32_t* stack_out,
+                                          void* scratch, int64_t scratch_bytes, nnue_stream_t stream);
+
+/* NNUEEvaluator::evaluate_incremental (engine/src/nnue_engine.cpp:739-786) for S streams whose frames arrive as uint8: the
+ * step of nnue_engine_stream_step / nnue_engine_stream_step_stacks (st == NULL / given) on the conv bytes formed from src
+ * (nnue_engine.cpp:48-158 on Normalize's output, data/datasets.py:366-369; the logits its consumer reads, evaluate.py:150-161).
+ * Same state, same outputs; this call and every other stream call may follow one another on one state buffer.  scratch >=
+ * nnue_engine_scratch(m, S).  Codes as the float twin, src and its refusals as nnue_engine_evaluate_logits_u8. */
+int nnue_engine_stream_step_u8(const nnue_engine_model* m, const nnue_engine_stacks* st, const nnue_engine_u8_frames* src,
+                               int S, int H, int W, const int32_t* stack_in, void* state, int64_t state_bytes,
+                               float* logits, float* density, int32_t* changed, int32_t* stack_out, void* scratch,
+                               int64_t scratch_bytes, nnue_stream_t stream);
+
 /* ---- the engine's tensors from a live model ------------------------------------------------------------------------
  *
  * What serialize_model followed by a load of the file leaves in device memory, formed from the model's float32 parameters in

@@ -7,6 +7,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "engine_u8.h"
 
 namespace {
 
@@ -810,6 +811,29 @@ static void engine_launch_conv(const nnue_engine_model* m, const float* images, 
                      g.W, g.stride, g.OH, g.OW, m->oc, F, static_cast<int8_t*>(conv));
 }
 
+// Where a call's conv bytes come from: float images through engine_conv_kernel, or uint8 frames through the front of
+// engine_u8_kernels.hip (u8 == true; the descriptor may still be null, which the entry point refuses).  Either way the bytes
+// land in the same scratch and every consumer behind them is the same launch.
+struct EngineFrames {
+  const float* images;
+  const nnue_engine_u8_frames* src;
+  bool u8;
+  bool given() const { return u8 ? (src && src->data) : images != nullptr; }
+};
+
+// The checks of a u8 call that follow the model's and the geometry's (none for float images).
+static int engine_check_frames(const char* fn, const nnue_engine_model* m, const EngineFrames& in, int n, const ConvGeometry& g,
+                               EngineU8Plan* plan) {
+  if (!in.u8) return NNUE_OK;
+  return nnue_engine_u8_plan(fn, m, n, g.H, g.W, g.stride, g.OH, g.OW, plan);
+}
+
+static void engine_launch_front(const nnue_engine_model* m, const EngineFrames& in, int n, const ConvGeometry& g,
+                                const EngineU8Plan& plan, void* conv, hipStream_t s) {
+  if (in.u8) nnue_engine_u8_launch(m, in.src, n, g.H, g.W, g.stride, g.OH, g.OW, plan, conv, s);
+  else engine_launch_conv(m, in.images, n, g, conv, s);
+}
+
 // What every launching entry point checks first: the call's pointers (`pointers`: all of them given), then the stacks argument
 // of a selecting call.  Its own argument checks, the model's tensors, a positive count and engine_check_model follow in the
 // entry point, in the order the ABI tests pin.
@@ -847,12 +871,14 @@ static void engine_with_sel(const nnue_engine_stacks* st, const int32_t* stack_i
 
 // nnue_engine_evaluate_logits (select == false; st, stack_in and stack_out unused) and nnue_engine_evaluate_logits_stacks.
 static int engine_evaluate(const char* fn, const nnue_engine_model* m, bool select, const nnue_engine_stacks* st,
-                           const float* images, int B, int H, int W, const int32_t* stack_in, float* logits, float* density,
+                           const EngineFrames& in, int B, int H, int W, const int32_t* stack_in, float* logits, float* density,
                            int32_t* stack_out, void* scratch, int64_t scratch_bytes, nnue_stream_t stream) {
-  if (int rc = engine_check_call(fn, m && images && logits && density && scratch, select, st, stack_out)) return rc;
+  if (int rc = engine_check_call(fn, m && in.given() && logits && density && scratch, select, st, stack_out)) return rc;
   NNUE_REQUIRE(engine_has_tensors(m, st), NNUE_E_ARG, "%s: model tensor missing", fn);
   NNUE_REQUIRE(B > 0 && H > 0 && W > 0, NNUE_E_ARG, "%s: B=%d H=%d W=%d must be positive", fn, B, H, W);
   if (int rc = engine_check_model(m, st, fn)) return rc;
+  if (in.u8)
+    if (int rc = nnue_engine_u8_check(fn, m, in.src, B)) return rc;
   const EngineNet net = engine_net(m, st);
   ConvGeometry geo{};
   if (int rc = engine_conv_geometry(m, H, W, fn, &geo)) return rc;
@@ -861,9 +887,11 @@ static int engine_evaluate(const char* fn, const nnue_engine_model* m, bool sele
   NNUE_REQUIRE((long long)B * H * W * 3 < (1ll << 40), NNUE_E_SHAPE, "%s: batch too large", fn);
   const size_t lds = batch_lds(net).bytes;
   NNUE_REQUIRE(lds <= 64 * 1024, NNUE_E_SHAPE, "%s: layer sizes need %zu bytes of LDS", fn, lds);
+  EngineU8Plan plan{};
+  if (int rc = engine_check_frames(fn, m, in, B, geo, &plan)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const uint8_t* conv = static_cast<const uint8_t*>(scratch);
-  engine_launch_conv(m, images, B, geo, scratch, s);
+  engine_launch_front(m, in, B, geo, plan, scratch, s);
   engine_with_sel(st, stack_in, stack_out, [&](auto sel) {
     hipLaunchKernelGGL((engine_stack_kernel<decltype(sel)>), dim3(B), dim3(256), lds, s, net, conv, logits, density, sel);
   });
@@ -872,15 +900,23 @@ static int engine_evaluate(const char* fn, const nnue_engine_model* m, bool sele
 
 extern "C" int nnue_engine_evaluate_logits(const nnue_engine_model* m, const float* images, int B, int H, int W, float* logits,
                                            float* density, void* scratch, int64_t scratch_bytes, nnue_stream_t stream) {
-  return engine_evaluate("nnue_engine_evaluate_logits", m, false, nullptr, images, B, H, W, nullptr, logits, density, nullptr, scratch,
-                         scratch_bytes, stream);
+  return engine_evaluate("nnue_engine_evaluate_logits", m, false, nullptr, {images, nullptr, false}, B, H, W, nullptr, logits, density,
+                         nullptr, scratch, scratch_bytes, stream);
 }
 
 extern "C" int nnue_engine_evaluate_logits_stacks(const nnue_engine_model* m, const nnue_engine_stacks* st, const float* images,
                                                   int B, int H, int W, const int32_t* stack_in, float* logits, float* density,
                                                   int32_t* stack_out, void* scratch, int64_t scratch_bytes, nnue_stream_t stream) {
-  return engine_evaluate("nnue_engine_evaluate_logits_stacks", m, true, st, images, B, H, W, stack_in, logits, density, stack_out,
-                         scratch, scratch_bytes, stream);
+  return engine_evaluate("nnue_engine_evaluate_logits_stacks", m, true, st, {images, nullptr, false}, B, H, W, stack_in, logits,
+                         density, stack_out, scratch, scratch_bytes, stream);
+}
+
+extern "C" int nnue_engine_evaluate_logits_u8(const nnue_engine_model* m, const nnue_engine_stacks* st,
+                                              const nnue_engine_u8_frames* src, int B, int H, int W, const int32_t* stack_in,
+                                              float* logits, float* density, int32_t* stack_out, void* scratch,
+                                              int64_t scratch_bytes, nnue_stream_t stream) {
+  return engine_evaluate("nnue_engine_evaluate_logits_u8", m, st != nullptr, st, {nullptr, src, true}, B, H, W, stack_in, logits,
+                         density, stack_out, scratch, scratch_bytes, stream);
 }
 
 extern "C" int64_t nnue_engine_stream_state_bytes(const nnue_engine_model* m, int S) {
@@ -898,29 +934,35 @@ static int engine_check_state(const char* fn, const nnue_engine_model* m, int S,
 
 // nnue_engine_stream_step (select == false; st, stack_in and stack_out unused) and nnue_engine_stream_step_stacks.
 static int engine_stream_step(const char* fn, const nnue_engine_model* m, bool select, const nnue_engine_stacks* st,
-                              const float* images, const uint8_t* active, int S, int H, int W, const int32_t* stack_in, void* state,
-                              int64_t state_bytes, float* logits, float* density, int32_t* changed, int32_t* stack_out,
-                              void* scratch, int64_t scratch_bytes, nnue_stream_t stream) {
+                              const EngineFrames& in, const uint8_t* active, int S, int H, int W, const int32_t* stack_in,
+                              void* state, int64_t state_bytes, float* logits, float* density, int32_t* changed,
+                              int32_t* stack_out, void* scratch, int64_t scratch_bytes, nnue_stream_t stream) {
   if (int rc = engine_check_call(fn, m && state && logits && density && changed, select, st, stack_out)) return rc;
-  NNUE_REQUIRE((images != nullptr) != (active != nullptr), NNUE_E_ARG, "%s: pass exactly one of images and active", fn);
+  const bool images = in.given();
+  if (in.u8) NNUE_REQUIRE(images, NNUE_E_ARG, "%s: null pointer", fn);
+  NNUE_REQUIRE(images != (active != nullptr), NNUE_E_ARG, "%s: pass exactly one of images and active", fn);
   NNUE_REQUIRE(nnue_aligned16(state), NNUE_E_ARG, "%s: state must be 16-byte aligned", fn);
   NNUE_REQUIRE(engine_has_tensors(m, st), NNUE_E_ARG, "%s: model tensor missing", fn);
   NNUE_REQUIRE(S > 0, NNUE_E_ARG, "%s: S=%d must be positive", fn, S);
   if (int rc = engine_check_model(m, st, fn)) return rc;
+  if (in.u8)
+    if (int rc = nnue_engine_u8_check(fn, m, in.src, S)) return rc;
   const EngineNet net = engine_net(m, st);
   const size_t lds = stream_lds(net).bytes;
   if (int rc = engine_check_state(fn, m, S, state_bytes, lds)) return rc;
   ConvGeometry geo{};
+  EngineU8Plan plan{};
   if (images) {
     if (int rc = engine_conv_geometry(m, H, W, fn, &geo)) return rc;
     NNUE_REQUIRE(scratch, NNUE_E_ARG, "%s: images need scratch", fn);
     NNUE_REQUIRE(scratch_bytes >= (int64_t)S * net.F, NNUE_E_SCRATCH, "%s: scratch %lld < %lld bytes", fn, (long long)scratch_bytes,
                  (long long)S * net.F);
     NNUE_REQUIRE((long long)S * H * W * 3 < (1ll << 40), NNUE_E_SHAPE, "%s: batch too large", fn);
+    if (int rc = engine_check_frames(fn, m, in, S, geo, &plan)) return rc;
   }
   hipStream_t s = static_cast<hipStream_t>(stream);
   uint8_t* sp = static_cast<uint8_t*>(state);
-  if (images) engine_launch_conv(m, images, S, geo, scratch, s);
+  if (images) engine_launch_front(m, in, S, geo, plan, scratch, s);
   engine_with_sel(st, stack_in, stack_out, [&](auto sel) {
     if (images)
       hipLaunchKernelGGL((engine_stream_kernel<false, decltype(sel)>), dim3(S), dim3(256), lds, s, net,
@@ -935,16 +977,24 @@ static int engine_stream_step(const char* fn, const nnue_engine_model* m, bool s
 extern "C" int nnue_engine_stream_step(const nnue_engine_model* m, const float* images, const uint8_t* active, int S, int H, int W,
                                        void* state, int64_t state_bytes, float* logits, float* density, int32_t* changed,
                                        void* scratch, int64_t scratch_bytes, nnue_stream_t stream) {
-  return engine_stream_step("nnue_engine_stream_step", m, false, nullptr, images, active, S, H, W, nullptr, state, state_bytes, logits,
-                            density, changed, nullptr, scratch, scratch_bytes, stream);
+  return engine_stream_step("nnue_engine_stream_step", m, false, nullptr, {images, nullptr, false}, active, S, H, W, nullptr, state,
+                            state_bytes, logits, density, changed, nullptr, scratch, scratch_bytes, stream);
 }
 
 extern "C" int nnue_engine_stream_step_stacks(const nnue_engine_model* m, const nnue_engine_stacks* st, const float* images,
                                               const uint8_t* active, int S, int H, int W, const int32_t* stack_in, void* state,
                                               int64_t state_bytes, float* logits, float* density, int32_t* changed,
                                               int32_t* stack_out, void* scratch, int64_t scratch_bytes, nnue_stream_t stream) {
-  return engine_stream_step("nnue_engine_stream_step_stacks", m, true, st, images, active, S, H, W, stack_in, state, state_bytes, logits,
-                            density, changed, stack_out, scratch, scratch_bytes, stream);
+  return engine_stream_step("nnue_engine_stream_step_stacks", m, true, st, {images, nullptr, false}, active, S, H, W, stack_in, state,
+                            state_bytes, logits, density, changed, stack_out, scratch, scratch_bytes, stream);
+}
+
+extern "C" int nnue_engine_stream_step_u8(const nnue_engine_model* m, const nnue_engine_stacks* st, const nnue_engine_u8_frames* src,
+                                          int S, int H, int W, const int32_t* stack_in, void* state, int64_t state_bytes,
+                                          float* logits, float* density, int32_t* changed, int32_t* stack_out, void* scratch,
+                                          int64_t scratch_bytes, nnue_stream_t stream) {
+  return engine_stream_step("nnue_engine_stream_step_u8", m, st != nullptr, st, {nullptr, src, true}, nullptr, S, H, W, stack_in,
+                            state, state_bytes, logits, density, changed, stack_out, scratch, scratch_bytes, stream);
 }
 
 extern "C" int nnue_engine_stream_update(const nnue_engine_model* m, const nnue_engine_stacks* st, const int32_t* added,
@@ -1065,17 +1115,21 @@ static void engine_launch_matrix(const nnue_engine_model* m, const EngineNet& ne
                      density, sel);
 }
 
-extern "C" int nnue_engine_evaluate_logits_matrix(const nnue_engine_model* m, const nnue_engine_stacks* st, const void* table_planes,
-                                                  int planes, const float* images, const uint8_t* active, int B, int H, int W,
-                                                  const int32_t* stack_in, float* logits, float* density, int32_t* stack_out,
-                                                  void* scratch, int64_t scratch_bytes, nnue_stream_t stream) {
-  const char* fn = "nnue_engine_evaluate_logits_matrix";
+// nnue_engine_evaluate_logits_matrix and its u8 twin.
+static int engine_evaluate_matrix(const char* fn, const nnue_engine_model* m, const nnue_engine_stacks* st, const void* table_planes,
+                                  int planes, const EngineFrames& in, const uint8_t* active, int B, int H, int W,
+                                  const int32_t* stack_in, float* logits, float* density, int32_t* stack_out, void* scratch,
+                                  int64_t scratch_bytes, nnue_stream_t stream) {
+  const bool images = in.given();
   if (int rc = engine_check_call(fn, m && table_planes && logits && density && scratch, st != nullptr, st, stack_out)) return rc;
-  NNUE_REQUIRE((images != nullptr) != (active != nullptr), NNUE_E_ARG, "%s: pass exactly one of images and active", fn);
+  if (in.u8) NNUE_REQUIRE(images, NNUE_E_ARG, "%s: null pointer", fn);
+  NNUE_REQUIRE(images != (active != nullptr), NNUE_E_ARG, "%s: pass exactly one of images and active", fn);
   NNUE_REQUIRE(nnue_aligned16(table_planes), NNUE_E_ARG, "%s: table_planes must be 16-byte aligned", fn);
   NNUE_REQUIRE(engine_has_tensors(m, st), NNUE_E_ARG, "%s: model tensor missing", fn);
   NNUE_REQUIRE(B > 0, NNUE_E_ARG, "%s: B=%d must be positive", fn, B);
   if (int rc = engine_check_model(m, st, fn)) return rc;
+  if (in.u8)
+    if (int rc = nnue_engine_u8_check(fn, m, in.src, B)) return rc;
   const EngineNet net = engine_net(m, st);
   NNUE_REQUIRE(planes == 1 || planes == 2, NNUE_E_SHAPE, "%s: planes=%d (1 or 2)", fn, planes);
   NNUE_REQUIRE(net.F < kMxMaxFeatures, NNUE_E_SHAPE, "%s: num_features %d >= 2^24 (an int32 sum could overflow)", fn, net.F);
@@ -1089,14 +1143,33 @@ extern "C" int nnue_engine_evaluate_logits_matrix(const nnue_engine_model* m, co
   NNUE_REQUIRE(scratch_bytes >= lay.total, NNUE_E_SCRATCH, "%s: scratch %lld < %lld bytes", fn, (long long)scratch_bytes,
                (long long)lay.total);
   NNUE_REQUIRE((reinterpret_cast<uintptr_t>(scratch) & 3u) == 0, NNUE_E_ARG, "%s: scratch must be 4-byte aligned", fn);
+  EngineU8Plan plan{};
+  if (images)
+    if (int rc = engine_check_frames(fn, m, in, B, geo, &plan)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   uint8_t* conv = static_cast<uint8_t*>(scratch);
   int32_t* sums = reinterpret_cast<int32_t*>(conv + lay.sums);
   const int8_t* tp = static_cast<const int8_t*>(table_planes);
-  if (images) engine_launch_conv(m, images, B, geo, conv, s);
+  if (images) engine_launch_front(m, in, B, geo, plan, conv, s);
   engine_with_sel(st, stack_in, stack_out, [&](auto sel) {
     if (images) engine_launch_matrix<false>(m, net, planes, conv, B, lay, tp, sums, logits, density, sel, s);
     else engine_launch_matrix<true>(m, net, planes, active, B, lay, tp, sums, logits, density, sel, s);
   });
   return nnue_launch_status(fn);
+}
+
+extern "C" int nnue_engine_evaluate_logits_matrix(const nnue_engine_model* m, const nnue_engine_stacks* st, const void* table_planes,
+                                                  int planes, const float* images, const uint8_t* active, int B, int H, int W,
+                                                  const int32_t* stack_in, float* logits, float* density, int32_t* stack_out,
+                                                  void* scratch, int64_t scratch_bytes, nnue_stream_t stream) {
+  return engine_evaluate_matrix("nnue_engine_evaluate_logits_matrix", m, st, table_planes, planes, {images, nullptr, false}, active,
+                                B, H, W, stack_in, logits, density, stack_out, scratch, scratch_bytes, stream);
+}
+
+extern "C" int nnue_engine_evaluate_logits_matrix_u8(const nnue_engine_model* m, const nnue_engine_stacks* st, const void* table_planes,
+                                                     int planes, const nnue_engine_u8_frames* src, int B, int H, int W,
+                                                     const int32_t* stack_in, float* logits, float* density, int32_t* stack_out,
+                                                     void* scratch, int64_t scratch_bytes, nnue_stream_t stream) {
+  return engine_evaluate_matrix("nnue_engine_evaluate_logits_matrix_u8", m, st, table_planes, planes, {nullptr, src, true}, nullptr,
+                                B, H, W, stack_in, logits, density, stack_out, scratch, scratch_bytes, stream);
 }

@@ -182,23 +182,47 @@ def evaluate_compiled_model(model: torch.nn.Module, loader, model_type: str) -> 
     return metrics
 
 
-def evaluate_engine(engine, loader) -> Dict[str, float]:
+def _engine_batches(engine, loader, source: str):
+    """What evaluate_engine walks: per batch (the engine call, labels, sample count).  source="float": the loader's batches.
+    source="u8": the index batches of a GpuLoader over an un-augmented, un-resized dataset, evaluated straight from its uint8
+    store -- the same images, labels and order, without the float batches."""
+    if source == "float":
+        for images, labels in loader:
+            images = images.to(engine.device, non_blocking=True).float().contiguous()
+            yield (lambda x=images: engine.evaluate_logits(x)), labels, int(images.shape[0])
+        return
+    from nnue_hip.input_pipeline import GpuLoader, resolve_augment
+    if not isinstance(loader, GpuLoader):
+        raise ValueError(f"evaluate_engine: source=\"u8\" needs a GpuLoader (a resident uint8 dataset), got {type(loader).__name__}")
+    ds = loader.dataset
+    if resolve_augment(ds.augment) != 0 or ds.output_hw != ds.image_hw:
+        raise ValueError("evaluate_engine: source=\"u8\" reads the stored bytes: the dataset must have no augmentation and no resize "
+                         f"(augment={ds.augment!r}, out_hw={ds.out_hw})")
+    for idx in loader.index_batches():
+        yield (lambda i=idx: engine.evaluate_logits_u8(ds.images, indices=i)), ds.labels[idx], int(idx.numel())
+
+
+def evaluate_engine(engine, loader, source: str = "float") -> Dict[str, float]:
     """``evaluate_compiled_model``'s metrics (evaluate.py:88-385; same keys) for an ``EngineModel`` that is already on the
     device, with ``evaluate_model``'s label handling.  Every batch's logits go straight into the confusion kernel and the
     densities into a float64 device sum; an event pair brackets each engine call, and the only synchronisation is the one
-    read-back at the end, where the event times are summed into ``ms_per_sample`` (GPU time of the engine call per sample)."""
+    read-back at the end, where the event times are summed into ``ms_per_sample`` (GPU time of the engine call per sample).
+    source="u8": ``loader`` is a ``GpuLoader`` whose dataset has no augmentation and no resize (ValueError otherwise), and every
+    batch is ``engine.evaluate_logits_u8(dataset.images, indices)`` on the loader's index batches: the same metrics, bit for
+    bit, without writing the normalised float batches."""
+    if source not in ("float", "u8"):
+        raise ValueError(f"evaluate_engine: source must be \"float\" or \"u8\", got {source!r}")
     device = engine.device
     confusion, density_sum = None, torch.zeros((1,), dtype=torch.float64, device=device)
     events, samples = [], 0
-    for images, labels in loader:
-        images = images.to(device, non_blocking=True).float().contiguous()
+    for call, labels, count in _engine_batches(engine, loader, source):
         labels = labels.to(device, non_blocking=True).long().reshape(-1)
         t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         t0.record()
-        logits, density = engine.evaluate_logits(images)
+        logits, density = call()
         t1.record()
         events.append((t0, t1))
-        samples += int(images.shape[0])
+        samples += count
         if logits.shape[1] == 1:
             labels = (labels > 0).long()
         confusion = _lib.confusion_accumulate(logits, labels, confusion)

@@ -16,6 +16,10 @@ the tensors the engine already holds -- what a training loop does after every ep
 ``evaluate_logits(..., path="matrix")`` and ``evaluate_features(active)`` run the accumulate step as one product on the int8
 matrix unit (include/nnue_hip.h: nnue_engine_evaluate_logits_matrix) over int8 planes of the table packed once
 (``prepare_matrix``): the same bits, since addition mod 2^16 depends on neither order nor accumulator width.
+``evaluate_logits_u8(store, indices)`` and ``EngineStream.step_u8`` take uint8 ``[N,H,W,3]`` frames -- the dataset store of
+``GpuImageDataset``, a camera's frames -- and form the conv bytes straight from them (include/nnue_hip.h:
+nnue_engine_evaluate_logits_u8): with the defaults, the bits of the float call on ``lib.load_batch`` of the same indices,
+without the float batch.
 """
 from __future__ import annotations
 
@@ -52,6 +56,35 @@ class _CModel(ctypes.Structure):  # include/nnue_hip.h: nnue_engine_model
 class _CStacks(ctypes.Structure):  # include/nnue_hip.h: nnue_engine_stacks
     _fields_ = ([("count", ctypes.c_int32), ("scales", ctypes.POINTER(ctypes.c_float))]
                 + [(n, ctypes.c_void_p) for n in _STACK_TENSORS])
+
+
+class _CU8Frames(ctypes.Structure):  # include/nnue_hip.h: nnue_engine_u8_frames
+    _fields_ = [("data", ctypes.c_void_p), ("indices", ctypes.c_void_p), ("count", ctypes.c_int64), ("layout", ctypes.c_int32),
+                ("mean255", ctypes.c_float * 3), ("inv_std255", ctypes.c_float * 3)]
+
+
+U8_LAYOUTS = {"chw": 0, "hwc": 1}
+# A.Normalize's defaults in the reference's transform lists (data/datasets.py:366-369)
+IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+
+
+def u8_constants(mean=None, std=None) -> Tuple[np.ndarray, np.ndarray]:
+    """(mean255, inv_std255) float32 [3] as the u8 calls take them: mean * 255 and 1 / (std * 255), every operation in float32
+    (with the defaults: the constants of ``lib.load_batch``, bit for bit).  ValueError for anything but three finite numbers,
+    or a std that is not positive."""
+    out = []
+    for name, given, default in (("mean", mean, IMAGENET_MEAN), ("std", std, IMAGENET_STD)):
+        try:
+            a = np.asarray(default if given is None else given, dtype=np.float32).reshape(-1)
+        except (TypeError, ValueError):
+            raise ValueError(f"{name}: expected three numbers, got {given!r}") from None
+        if a.shape != (3,) or not np.all(np.isfinite(a)):
+            raise ValueError(f"{name}: expected three finite numbers, got {given!r}")
+        out.append(a)
+    mean32, std32 = out
+    if np.any(std32 <= 0):
+        raise ValueError(f"std: every channel must be positive, got {std!r}")
+    return mean32 * np.float32(255.0), np.float32(1.0) / (std32 * np.float32(255.0))
 
 
 class EngineFormatError(ValueError):
@@ -355,6 +388,71 @@ class EngineModel:
         """Incremental evaluation of ``num_streams`` frame sequences (see EngineStream)."""
         return EngineStream(self, num_streams)
 
+    def _u8_frames(self, images_u8, indices, layout, mean, std, what: str, count: Optional[int] = None):
+        """The host descriptor of a u8 call: (struct, the tensors it points at, B, H, W).  ``count``: the number of frames the
+        call needs (a stream's S), None = whatever the arguments name."""
+        if not isinstance(images_u8, torch.Tensor):
+            raise TypeError(f"{what}: expected a tensor, got {type(images_u8).__name__}")
+        if images_u8.dtype != torch.uint8:
+            raise TypeError(f"{what}: expected torch.uint8, got {images_u8.dtype}")
+        if not self._on_device(images_u8):
+            raise ValueError(f"{what}: tensor is on {images_u8.device}, the model on {self.device} (no CPU fallback in this build)")
+        if images_u8.dim() != 4 or images_u8.shape[3] != 3 or min(images_u8.shape) < 1:
+            raise ValueError(f"{what}: expected uint8 [N,H,W,3], got {tuple(images_u8.shape)}")
+        if not images_u8.is_contiguous():
+            raise ValueError(f"{what}: the frames must be contiguous (a view with a storage offset is fine)")
+        if layout not in U8_LAYOUTS:
+            raise ValueError(f"{what}: layout must be one of {tuple(U8_LAYOUTS)}, got {layout!r}")
+        mean255, inv_std255 = u8_constants(mean, std)
+        n, h, w = (int(v) for v in images_u8.shape[:3])
+        if indices is None:
+            b = n
+        else:
+            if not isinstance(indices, torch.Tensor) or indices.dtype != torch.int64:
+                raise TypeError(f"{what}: indices must be an int64 tensor")
+            if not self._on_device(indices) or indices.dim() != 1 or indices.numel() < 1:
+                raise ValueError(f"{what}: indices must be a device tensor of shape (B,), got {tuple(indices.shape)} on {indices.device}")
+            indices = indices.contiguous()
+            b = int(indices.numel())
+        if count is not None and b != count:
+            raise ValueError(f"{what}: expected {count} frames, got {b}")
+        c = _CU8Frames()
+        c.data, c.indices, c.count, c.layout = images_u8.data_ptr(), lib._ptr(indices) or None, n, U8_LAYOUTS[layout]
+        c.mean255[:], c.inv_std255[:] = mean255.tolist(), inv_std255.tolist()
+        return c, (images_u8, indices), b, h, w
+
+    def evaluate_logits_u8(self, images_u8: torch.Tensor, indices: Optional[torch.Tensor] = None, layout: str = "chw",
+                           mean=None, std=None, stacks: Optional[torch.Tensor] = None, return_stacks: bool = False,
+                           path: Optional[str] = None):
+        """``evaluate_logits`` straight from uint8 frames: ``images_u8`` is a contiguous uint8 device tensor [N,H,W,3] (the store
+        of a ``GpuImageDataset``, or frames; a view with a storage offset is fine), ``indices`` a device int64 [B] into it
+        (clamped to [0, N) as ``lib.load_batch`` clamps them) or None for all N in order.
+        layout="chw" (default): the float buffer of every image is the memory ``lib.load_batch(augment=False)`` writes for it,
+        a CHW tensor handed to the engine flat as the reference does (evaluate.py:150-161) -- with the default ``mean`` /
+        ``std`` (the ImageNet constants, data/datasets.py:366-369) the results are bit-identical to
+        ``evaluate_logits(lib.load_batch(images_u8, labels, indices, False, 0, 0)[0])``.  layout="hwc": the frame's bytes are
+        what the engine's HWC indexing means, x[i] = norm(u[i], i % 3).  norm(v, c) = (v - 255 mean[c]) / (255 std[c]) in
+        float32 (include/nnue_hip.h has the exact expression).  ``stacks``, ``return_stacks`` and ``path`` as ``evaluate_logits``.
+        TypeError for a tensor that is not uint8 / indices that are not int64, ValueError for shape, device, contiguity, layout
+        and constants."""
+        src, keep, b, h, w = self._u8_frames(images_u8, indices, layout, mean, std, "images_u8")
+        stacks = self._stack_arg(stacks, b, "evaluate_logits_u8")
+        logits, density, _, used = self._outputs(b, zero_stacks=return_stacks)
+        st, used_ptr = (None, None) if self._stacks is None else (ctypes.addressof(self._stacks), used.data_ptr())
+        if self._path(path, b, "evaluate_logits_u8") == "matrix":
+            self.prepare_matrix()
+            scratch = self._matrix_scratch_for(b)
+            lib._call("nnue_engine_evaluate_logits_matrix_u8", ctypes.addressof(self._c), st, self._planes.data_ptr(),
+                      self.table_planes, ctypes.addressof(src), b, h, w, lib._ptr(stacks) or None, logits.data_ptr(),
+                      density.data_ptr(), used_ptr, scratch.data_ptr(), scratch.numel(), lib._stream(images_u8))
+        else:
+            scratch = self._scratch_for(b)
+            lib._call("nnue_engine_evaluate_logits_u8", ctypes.addressof(self._c), st, ctypes.addressof(src), b, h, w,
+                      lib._ptr(stacks) or None, logits.data_ptr(), density.data_ptr(), used_ptr, scratch.data_ptr(), scratch.numel(),
+                      lib._stream(images_u8))
+        del keep
+        return (logits, density, used) if return_stacks else (logits, density)
+
     def _frames(self, images: torch.Tensor, height: Optional[int], width: Optional[int]) -> Tuple[int, int, int]:
         if images.dim() == 4:
             b, h, w = images.shape[0], images.shape[2], images.shape[3]
@@ -601,7 +699,7 @@ class EngineStream:
             raise ValueError(f"{what}: expected {self.num_streams} streams in dim 0, got shape {tuple(t.shape)}")
 
     def _run(self, images: Optional[torch.Tensor], active: Optional[torch.Tensor], h: int, w: int,
-             stacks: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+             stacks: Optional[torch.Tensor] = None, u8=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         m, s = self.model, self.num_streams
         if self._generation != m.generation:  # the model was requantised: the accumulators are sums over the old table
             self._valid.fill_(0)
@@ -610,7 +708,14 @@ class EngineStream:
         logits, density, changed, used = m._outputs(s, changed=True)
         scratch = m._scratch_for(s) if images is not None else None
         src = images if images is not None else active
-        if m._stacks is None:
+        if u8 is not None:  # (descriptor, the uint8 frames): `images` is those frames, the state and the outputs are the same
+            st, used_ptr = (None, None) if m._stacks is None else (ctypes.addressof(m._stacks), used.data_ptr())
+            lib._call("nnue_engine_stream_step_u8", ctypes.addressof(m._c), st, ctypes.addressof(u8), s, h, w, lib._ptr(stacks) or None,
+                      self.state.data_ptr(), self.state.numel(), logits.data_ptr(), density.data_ptr(), changed.data_ptr(), used_ptr,
+                      scratch.data_ptr(), scratch.numel(), lib._stream(src))
+            if m._stacks is not None:
+                self.stacks = used
+        elif m._stacks is None:
             lib._call("nnue_engine_stream_step", ctypes.addressof(m._c), lib._ptr(images), lib._ptr(active), s, h, w,
                       self.state.data_ptr(), self.state.numel(), logits.data_ptr(), density.data_ptr(), changed.data_ptr(),
                       lib._ptr(scratch), 0 if scratch is None else scratch.numel(), lib._stream(src))
@@ -630,6 +735,15 @@ class EngineStream:
         self._check(frames, "frames", (torch.float32,))
         _, h, w = self.model._frames(frames, height, width)
         return self._run(frames.contiguous(), None, h, w, stacks)
+
+    def step_u8(self, frames_u8: torch.Tensor, indices: Optional[torch.Tensor] = None, layout: str = "chw", mean=None, std=None,
+                stacks: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """``step`` from uint8 frames, in the forms ``EngineModel.evaluate_logits_u8`` takes: ``frames_u8`` uint8 [N,H,W,3] on
+        the device and ``indices`` int64 [S] into it, or None with N == S (stream s takes frame s).  Returns what ``step``
+        returns, on the same state -- bit-identical to ``evaluate_logits_u8`` on the same frames -- and mixes freely with
+        ``step``, ``step_features`` and ``update``."""
+        src, keep, _, h, w = self.model._u8_frames(frames_u8, indices, layout, mean, std, "frames_u8", count=self.num_streams)
+        return self._run(keep[0], None, h, w, stacks, u8=src)
 
     def step_features(self, active: torch.Tensor, stacks: Optional[torch.Tensor] = None
                       ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:

@@ -153,6 +153,11 @@ SIGNATURES = {
     "nnue_engine_pack_table": (_c_int, [_c_p, _c_int, _c_p, _c_i64, _c_p, _c_p]),
     "nnue_engine_evaluate_logits_matrix": (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_p, _c_p, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p,
                                                     _c_p, _c_p, _c_i64, _c_p]),
+    "nnue_engine_evaluate_logits_u8": (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p]),
+    "nnue_engine_evaluate_logits_matrix_u8": (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_p, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p, _c_p,
+                                                       _c_p, _c_i64, _c_p]),
+    "nnue_engine_stream_step_u8": (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p,
+                                            _c_i64, _c_p]),
     "nnue_engine_quantize_model": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int,
                                             _c_int, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p, _c_p]),
     "nnue_sgd_scratch": (_c_i64, [_c_i64]),

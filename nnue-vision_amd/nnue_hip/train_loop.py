@@ -16,7 +16,8 @@ NNUE model, minus the parts that are out of scope here (W&B, RunPod, dataset dow
   (``EngineModel.requantize``) and run over the validation loader (``evaluate.evaluate_engine``); the row gains
   ``compiled/f1``, ``compiled/accuracy``, ``compiled/ms_per_sample`` and ``compiled/latent_density``.  Unlike the reference,
   whose call clamps the live weights through ``serialize_model``, this leaves the parameters alone: a run with the metrics on
-  is bitwise the run with them off.
+  is bitwise the run with them off.  The optional config attribute ``compiled_eval_source`` (default ``"float"``) is
+  ``evaluate_engine``'s ``source``: ``"u8"`` evaluates straight from the uint8 store of a ``GpuLoader``'s dataset.
 
 Loaders are any iterables of ``(images float32 [b,3,H,W], labels int [b])`` batches; the data pipeline itself
 (torchvision / albumentations) is out of scope.
@@ -87,6 +88,7 @@ def run_training(config, train_loader: Iterable, val_loader: Iterable, test_load
     import evaluate
     if compiled_eval is None:
         compiled_eval = bool(getattr(config, "compiled_eval", False))
+    compiled_eval_source = str(getattr(config, "compiled_eval_source", "float"))
     if not torch.cuda.is_available():
         raise lib.NnueHipError("training runs on the GPU only (no CPU fallback in this build)")
     device = torch.device("cuda", torch.cuda.current_device())
@@ -132,7 +134,7 @@ def run_training(config, train_loader: Iterable, val_loader: Iterable, test_load
                 f"Val Acc: {val_metrics['acc']:.4f}")
         if engine is not None:  # train.py:389-427
             engine.requantize(model)
-            compiled = evaluate.evaluate_engine(engine, val_loader)
+            compiled = evaluate.evaluate_engine(engine, val_loader, source=compiled_eval_source)
             row.update({"compiled/f1": compiled["f1"], "compiled/accuracy": compiled["acc"],
                         "compiled/ms_per_sample": compiled["ms_per_sample"], "compiled/latent_density": compiled["latent_density"]})
             line += (f" | Compiled F1: {compiled['f1']:.4f}, Compiled Acc: {compiled['acc']:.4f}, "

@@ -157,6 +157,74 @@ def bench_paths(shape_key, only, batches, warmup, repeats, extras):
     print(json.dumps(res))
 
 
+U8_BATCHES = {"224": (128, 1024), "c2": (512, 4096)}
+U8_STREAMS = 1024
+
+
+def bench_u8(shape_keys, only, batches, warmup, repeats):
+    """--u8: the uint8 input form against the parent's way of evaluating a resident uint8 dataset, in this process, on one
+    GpuImageDataset per shape.  (a) `float`: dataset.batch(idx) then evaluate_logits -- both launches inside the timed window;
+    (b) `u8`: evaluate_logits_u8(dataset.images, idx).  The two alternate inside one loop, for path="matrix" and "gather", at
+    --shape 224 (batch 128 and 1024) and c2 (512 and 4096); then stream(1024).step_u8 against batch + step on frames that
+    alternate between two index sets.  Per row: median, 10th and 90th percentile of device-event-timed calls after warm-up;
+    the two forms' logits and densities are asserted bitwise equal on the timed inputs first.  --path P times that path
+    alone (what a rocprofv3 --kernel-trace run wants: engine_conv_kernel and engine_conv_u8_kernel are both in it).
+        python tools/bench_engine.py --u8 > profiles/engine_u8.json"""
+    from nnue_hip.input_pipeline import GpuImageDataset
+    res = {"device": torch.cuda.get_device_name(0), "warmup": warmup, "repeats": repeats,
+           "timing": "median (p10, p90) of device-event-timed calls; float = dataset.batch(idx) + evaluate_logits, u8 = "
+                     "evaluate_logits_u8(dataset.images, idx), alternating in one loop on one resident uint8 dataset",
+           "shapes": []}
+    for key in shape_keys:
+        shape = dict(STACK_SHAPES[0 if key == "c2" else 1])
+        sizes = tuple(batches) if batches else U8_BATCHES[key]
+        shape["batch"] = 2
+        _, engine, _, _ = _stack_case(shape, 1)
+        size, n = shape["size"], max(max(sizes), U8_STREAMS)
+        gen = torch.Generator(device="cuda").manual_seed(7)
+        images = torch.randint(0, 256, (n, size, size, 3), dtype=torch.uint8, device="cuda", generator=gen)
+        ds = GpuImageDataset(images, torch.zeros(n, dtype=torch.int64))
+        engine.prepare_matrix()
+        F = int(engine.header["num_features"])
+        out = {"shape": shape["name"], "F": F, "L1": shape["l1"], "frame_bytes": 3 * size * size, "cases": []}
+        for B in sizes:
+            idx = torch.randperm(n, device="cuda", generator=gen)[:B]
+            for path in ([only] if only else ["matrix", "gather"]):
+                a = engine.evaluate_logits(ds.batch(idx)[0], path=path)
+                b = engine.evaluate_logits_u8(ds.images, idx, path=path)
+                assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
+                row = {"batch": B, "path": path, "mean_density": float(a[1].double().mean()),
+                       "u8_bytes_read": B * 3 * size * size, "float_bytes_written_and_read": 2 * 4 * B * 3 * size * size}
+                stats = _alternate_spread([lambda t: engine.evaluate_logits(ds.batch(idx)[0], path=path),
+                                           lambda t: engine.evaluate_logits_u8(ds.images, idx, path=path)], warmup, repeats)
+                for name, st in zip(("float", "u8"), stats):
+                    row[name + "_ms"], row[name + "_p10_ms"], row[name + "_p90_ms"] = st["median"], st["p10"], st["p90"]
+                row["float_over_u8"] = row["float_ms"] / row["u8_ms"]
+                row["u8_wins_beyond_spread"] = row["u8_p90_ms"] < row["float_p10_ms"]
+                row["u8_loses_beyond_spread"] = row["u8_p10_ms"] > row["float_p90_ms"]
+                print(json.dumps(row), file=sys.stderr)
+                out["cases"].append(row)
+        if not only:
+            S = U8_STREAMS
+            sets = [torch.randperm(n, device="cuda", generator=gen)[:S] for _ in range(2)]
+            sf, su = engine.stream(S), engine.stream(S)
+            for t in range(2):
+                a, b = sf.step(ds.batch(sets[t])[0]), su.step_u8(ds.images, sets[t])
+                assert all(torch.equal(p, q) for p, q in zip(a, b))
+            stats = _alternate_spread([lambda t: sf.step(ds.batch(sets[t & 1])[0]), lambda t: su.step_u8(ds.images, sets[t & 1])],
+                                      warmup, repeats)
+            row = {"streams": S}
+            for name, st in zip(("float", "u8"), stats):
+                row[name + "_ms"], row[name + "_p10_ms"], row[name + "_p90_ms"] = st["median"], st["p10"], st["p90"]
+            row["float_over_u8"] = row["float_ms"] / row["u8_ms"]
+            row["u8_wins_beyond_spread"] = row["u8_p90_ms"] < row["float_p10_ms"]
+            print(json.dumps(row), file=sys.stderr)
+            out["stream"] = row
+        res["shapes"].append(out)
+        del ds, images, engine
+    print(json.dumps(res))
+
+
 def bench_stacks(K, warmup, repeats):
     """--stacks K: per-image layer-stack selection (EngineModel.load(bucket="auto")) against the plain single-stack call, in
     this process, on the same K-stack file and the same images, at the CIFAR shape (10x10x8, 1024/128/32, batch 4096) and the
@@ -197,9 +265,14 @@ def main():
     ap.add_argument("--path", choices=("gather", "matrix"), help="with --shape: time this form alone")
     ap.add_argument("--batches", type=int, nargs="*", help="with --shape: the batch sizes (default: headline pair + sweep)")
     ap.add_argument("--extras", action="store_true", help="with --shape: also pack, requantize and evaluate_engine")
+    ap.add_argument("--u8", action="store_true", help="time the uint8 input form against batch + evaluate_logits (--shape: one shape)")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--repeats", type=int, default=50)
     args = ap.parse_args()
+    if args.u8:
+        if not torch.cuda.is_available():
+            raise SystemExit("bench_engine: needs a GPU")
+        return bench_u8([args.shape] if args.shape else ["224", "c2"], args.path, args.batches, args.warmup, args.repeats)
     if args.stacks:
         if not torch.cuda.is_available():
             raise SystemExit("bench_engine: needs a GPU")
