@@ -329,6 +329,41 @@ int nnue_ftm_backward(const uint8_t* bits, const float* sink, const float* d_out
                       const float* ste_thr, int H, int W, int stride, float* ste_partial, int64_t ste_partial_bytes,
                       nnue_stream_t stream);
 
+/* The table rows the value gradient d_val = (d_out W^T) . A of the STE ride reads, as pre-split bf16 planes written once per step
+ * by rider workgroups of the conv launch.  The contraction runs along L1, so a 16-byte chunk is 8 consecutive j (L1 index) of one
+ * table row; the writer applies the value tiles' column order (tile t, column n: channel n / 8, grid position min(8 t + n % 8,
+ * G - 1), G = P / 8) and the row clamp p >= F-1 -> F-1 (nnue.py:701).  One 48 KB block per (column tile t, 128-deep K tile kt),
+ * block t * ktiles + kt (ktiles = ceil(L1 / 128)); inside a block plane p (0 hi, 1 mid, 2 lo: weight = hi + mid + lo exactly) of
+ * column n = 16 w + r, j = 128 kt + 32 kb + 8 q .. + 7 sits at byte p * 16384 + ((4 w + kb) * 64 + 16 q + r) * 16 (the MFMA's
+ * fragment order); j >= L1 are zeros.
+ * _supported: shapes whose merged backward takes the STE ride on 32-row value tiles (nnue_ftm_backward_ste_chunks > 0 with
+ * ceil(B / 32) row tiles), L1 % 8 == 0, at least 256 value tiles (NNUE_FTM_VAL_PLANES_MIN_TILES, read per call, lowers the floor
+ * for tests), NNUE_FTM_VAL_PLANES != 0 (read per call).  _bytes: the size of the plane buffer (0 where none exists). */
+int nnue_ftm_value_planes_supported(int B, int F, int P, int L1, int H, int W, int stride);
+int64_t nnue_ftm_value_planes_bytes(int B, int F, int P, int L1);
+
+/* nnue_ftm_conv_binarize_planes (self.conv + StraightThroughBinary.forward, nnue.py:640, :646-647, :19-25) whose launch also
+ * writes the value planes of `table` into `val_planes`: more rider workgroups behind the forward's.  conv_out, bits, n, sink and
+ * `planes` are bitwise nnue_ftm_conv_binarize_planes'.  Shapes: both _supported queries; planes == NULL: the value planes alone
+ * (nnue_ftm_value_planes_supported shapes), no forward riders. */
+int nnue_ftm_conv_binarize_value_planes(const float* images, const float* weight, const float* thr, int B, int H, int W,
+                                        int fps, int stride, int F, const float* table, int L1, int L2, void* planes,
+                                        int64_t planes_bytes, void* val_planes, int64_t val_planes_bytes, float* conv_out,
+                                        uint8_t* bits, int32_t* n, float* sink, nnue_stream_t stream);
+
+/* nnue_ftm_backward (autograd of nnue.py:702-708 and :628-633) whose 32-row value tiles read the table from `val_planes` (written
+ * this step by nnue_ftm_conv_binarize_value_planes from the same `weight`) as six bf16 plane products instead of the f32 MFMA.
+ * Taken where nnue_ftm_value_planes_supported says yes and ste_partial != NULL; every other call launches what nnue_ftm_backward
+ * launches (val_planes must still be a valid pointer).  d_weight, d_bias, d_w1, sq_partial and the small gradients are bitwise
+ * nnue_ftm_backward's; d_conv_out and the STE partials differ by the summation order and the dropped mid.lo + lo.mid + lo.lo
+ * terms (below 2^-23 of a product). */
+int nnue_ftm_backward_planes(const uint8_t* bits, const float* sink, const float* d_out, const float* weight,
+                             int B, int F, int P, int L1, float* d_weight, float* d_bias, float* d_conv_out,
+                             const float* ft, const float* d_z1, int L2, float* d_w1, float* sq_partial,
+                             const nnue_cls_rider* small, const float* ste_images, const float* ste_patches, const float* ste_conv_out,
+                             const float* ste_thr, int H, int W, int stride, float* ste_partial, int64_t ste_partial_bytes,
+                             const void* val_planes, int64_t val_planes_bytes, nnue_stream_t stream);
+
 /* ---- pairwise product + SimpleClassifier -------------------------------------- */
 
 /* Forward of  l0 = cat(x[:, :L1/2] * x[:, L1/2:], x[:, :L1/2])  (nnue.py:660-666, when

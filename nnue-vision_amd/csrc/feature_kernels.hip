@@ -98,6 +98,31 @@ __global__ __launch_bounds__(256) void conv_binarize_planes_kernel(const float* 
   conv_binarize_body<kFullUnroll, false>(img, prm, out, bits, n, sink, H, W, fps, stride, Gh, Gw, F, slices, id % B, id / B, w_lds, [] {});
 }
 
+// The planes launch with a second set of riders behind the first: the table rows the merged backward's value tiles read, as the
+// bf16 planes of value_planes.h (nnue_ftm_conv_binarize_value_planes).  A kernel of its own again, so that
+// conv_binarize_planes_kernel keeps its arguments and instruction stream; the order is conv workgroups, forward riders (the
+// forward is the next launch), value riders (read three launches later).
+#include "value_planes.h"
+
+template <bool kFullUnroll>
+__global__ __launch_bounds__(256) void conv_binarize_planes2_kernel(const float* __restrict__ img, const float* __restrict__ w,
+                                                                    const float* __restrict__ thr, float* __restrict__ out,
+                                                                    uint8_t* __restrict__ bits, int* __restrict__ n,
+                                                                    float* __restrict__ sink, int B, int H, int W, int fps, int stride,
+                                                                    int Gh, int Gw, int F, int slices, FwdPlaneArgs pa, int fwd_riders,
+                                                                    ValPlaneArgs va) {
+  extern __shared__ __attribute__((aligned(16))) float w_lds[];
+  const int id = (int)blockIdx.x;
+  if (id >= B * slices) {
+    const int rider = id - B * slices;
+    if (rider < fwd_riders) forward_planes_write(pa, rider);
+    else value_planes_write(va, rider - fwd_riders);
+    return;
+  }
+  ConvParamsPlain prm{w, thr};
+  conv_binarize_body<kFullUnroll, false>(img, prm, out, bits, n, sink, H, W, fps, stride, Gh, Gw, F, slices, id % B, id / B, w_lds, [] {});
+}
+
 // ------------------------------------------------------------------ binarise + compact
 // One workgroup per sample walks the flat ids p = c*G + hw in ascending order, 256 at a time:
 // bit = conv_out > thr[c]; wave ballots + a 4-entry LDS scan give each active id its slot, so the
@@ -518,6 +543,9 @@ struct PlaneRide {  // nnue_ftm_conv_binarize_planes: the table and its plane bu
   int L1, L2;
   void* planes;
   int64_t planes_bytes;
+  void* val_planes = nullptr;  // nnue_ftm_conv_binarize_value_planes: the value planes as well (want_val)
+  int64_t val_planes_bytes = 0;
+  bool want_val = false;
 };
 
 int conv_binarize_impl(const char* who, const float* images, const float* weight, const float* thr, int B, int H, int W, int fps, int stride, int F,
@@ -532,14 +560,29 @@ int conv_binarize_impl(const char* who, const float* images, const float* weight
   NNUE_REQUIRE(G * fps < (1ll << 30) && (long long)B * G * fps < (1ll << 40), NNUE_E_SHAPE, "%s: map too large", who);
   NNUE_REQUIRE(!patches || 27ll * B * G * 4 < (1ll << 31), NNUE_E_SHAPE, "%s: the im2col buffer must stay below 2 GiB", who);
   const int P = (int)(G * fps);
+  const bool fwd_ride = ride.table && (ride.planes || !ride.want_val);  // (the value planes can be written alone: planes == NULL)
   if (ride.table) {  // every check before the first launch (the counters' zero fill below)
-    NNUE_REQUIRE(ride.planes, NNUE_E_ARG, "%s: null pointer", who);
-    NNUE_REQUIRE(nnue_ftm_forward_l1_planes_supported(B, F, P, ride.L1, ride.L2), NNUE_E_SHAPE,
-                 "%s: B=%d F=%d P=%d L1=%d L2=%d is not a planes-fed forward shape (nnue_ftm_forward_l1_planes_supported)", who, B, F, P, ride.L1,
-                 ride.L2);
-    NNUE_REQUIRE(nnue_aligned16(ride.table) && nnue_aligned16(ride.planes), NNUE_E_ARG, "%s: pointers must be 16-byte aligned", who);
-    NNUE_REQUIRE(ride.planes_bytes >= nnue_ftm_forward_planes_bytes(B, F, P, ride.L1), NNUE_E_SCRATCH, "%s: plane buffer of %lld bytes, needs %lld", who,
-                 (long long)ride.planes_bytes, (long long)nnue_ftm_forward_planes_bytes(B, F, P, ride.L1));
+    NNUE_REQUIRE(nnue_aligned16(ride.table), NNUE_E_ARG, "%s: pointers must be 16-byte aligned", who);
+    if (fwd_ride) {
+      NNUE_REQUIRE(ride.planes, NNUE_E_ARG, "%s: null pointer", who);
+      NNUE_REQUIRE(nnue_ftm_forward_l1_planes_supported(B, F, P, ride.L1, ride.L2), NNUE_E_SHAPE,
+                   "%s: B=%d F=%d P=%d L1=%d L2=%d is not a planes-fed forward shape (nnue_ftm_forward_l1_planes_supported)", who, B, F, P,
+                   ride.L1, ride.L2);
+      NNUE_REQUIRE(nnue_aligned16(ride.planes), NNUE_E_ARG, "%s: pointers must be 16-byte aligned", who);
+      NNUE_REQUIRE(ride.planes_bytes >= nnue_ftm_forward_planes_bytes(B, F, P, ride.L1), NNUE_E_SCRATCH,
+                   "%s: plane buffer of %lld bytes, needs %lld", who, (long long)ride.planes_bytes,
+                   (long long)nnue_ftm_forward_planes_bytes(B, F, P, ride.L1));
+    }
+    if (ride.want_val) {
+      NNUE_REQUIRE(ride.val_planes, NNUE_E_ARG, "%s: null pointer", who);
+      NNUE_REQUIRE(fps == 8 && nnue_ftm_value_planes_supported(B, F, P, ride.L1, H, W, stride), NNUE_E_SHAPE,
+                   "%s: B=%d F=%d P=%d L1=%d H=%d W=%d stride=%d is not a value-planes shape (nnue_ftm_value_planes_supported)", who, B, F, P,
+                   ride.L1, H, W, stride);
+      NNUE_REQUIRE(nnue_aligned16(ride.val_planes), NNUE_E_ARG, "%s: pointers must be 16-byte aligned", who);
+      NNUE_REQUIRE(ride.val_planes_bytes >= nnue_ftm_value_planes_bytes(B, F, P, ride.L1), NNUE_E_SCRATCH,
+                   "%s: value-plane buffer of %lld bytes, needs %lld", who, (long long)ride.val_planes_bytes,
+                   (long long)nnue_ftm_value_planes_bytes(B, F, P, ride.L1));
+    }
   }
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int threads = G <= 64 ? 64 : (G <= 128 ? 128 : 256);
@@ -553,7 +596,15 @@ int conv_binarize_impl(const char* who, const float* images, const float* weight
   if (ride.table) {
     const int direct = (F - 1 < P) ? F - 1 : P, ktiles = (direct + kBfK - 1) / kBfK, parts = 256 / threads;
     const FwdPlaneArgs pa{ride.table, static_cast<unsigned char*>(ride.planes), (unsigned)((size_t)direct * ride.L1 * 4), ride.L1, ktiles, parts};
-    const int riders = (ride.L1 / 64) * ktiles * parts;
+    const int riders = fwd_ride ? (ride.L1 / 64) * ktiles * parts : 0;
+    if (ride.want_val) {
+      const int vk = (ride.L1 + kBfK - 1) / kBfK, v_riders = (int)((G + 7) / 8) * vk * parts;
+      const ValPlaneArgs va{ride.table, static_cast<unsigned char*>(ride.val_planes), (unsigned)((size_t)F * ride.L1 * 4), ride.L1, F, (int)G, vk, parts};
+      const dim3 grid2((unsigned)(B * slices + riders + v_riders));
+      hipLaunchKernelGGL((conv_binarize_planes2_kernel<true>), grid2, dim3(threads), lds, s, images, weight, thr, conv_out, bits, n, sink, B, H, W,
+                         fps, stride, Gh, Gw, F, slices, pa, riders, va);
+      return nnue_launch_status(who);
+    }
     const dim3 grid((unsigned)(B * slices + riders));
     if (fps <= 16)
       hipLaunchKernelGGL((conv_binarize_planes_kernel<true>), grid, dim3(threads), lds, s, images, weight, thr, conv_out, bits, n, sink, B, H, W, fps,
@@ -597,6 +648,15 @@ extern "C" int nnue_ftm_conv_binarize_planes(const float* images, const float* w
   NNUE_REQUIRE(table && planes, NNUE_E_ARG, "nnue_ftm_conv_binarize_planes: null pointer");
   return conv_binarize_impl("nnue_ftm_conv_binarize_planes", images, weight, thr, B, H, W, fps, stride, F, conv_out, nullptr, bits, n, sink, stream,
                             PlaneRide{table, L1, L2, planes, planes_bytes});
+}
+
+extern "C" int nnue_ftm_conv_binarize_value_planes(const float* images, const float* weight, const float* thr, int B, int H, int W, int fps,
+                                                   int stride, int F, const float* table, int L1, int L2, void* planes, int64_t planes_bytes,
+                                                   void* val_planes, int64_t val_planes_bytes, float* conv_out, uint8_t* bits, int32_t* n,
+                                                   float* sink, nnue_stream_t stream) {
+  NNUE_REQUIRE(table && val_planes, NNUE_E_ARG, "nnue_ftm_conv_binarize_value_planes: null pointer");
+  return conv_binarize_impl("nnue_ftm_conv_binarize_value_planes", images, weight, thr, B, H, W, fps, stride, F, conv_out, nullptr, bits, n, sink,
+                            stream, PlaneRide{table, L1, L2, planes, planes_bytes, val_planes, val_planes_bytes, true});
 }
 
 extern "C" int nnue_binarize_features(const float* conv_out, const float* thr, int B, int fps, int Gh, int Gw, int F,

@@ -47,6 +47,7 @@ struct Mat {
 };
 using u32x4 = __attribute__((__vector_size__(4 * sizeof(unsigned)))) unsigned;
 #include "forward_planes.h"  // kBfK, bf_img, bf16_split.h (split3 / split_block / split8, stage_map_k / stage_map_m), the plane buffer
+#include "value_planes.h"    // the value gradient's table rows as planes in fragment order (gemm_tile_val_planes)
 
 // The raw 16 bytes (float operand) or 4 bytes (byte operand, in .x) of (outer, inner .. inner+3).  Nothing is done to
 // the value here: widening / splitting happens when the registers are stored to LDS, one K tile later, so the load
@@ -207,6 +208,12 @@ struct ValSteEpi {
     return (j >> 3) * G + (hw < G ? hw : G - 1);
   }
 };
+// ValSteEpi whose tile reads the table from the value planes the conv launch wrote this step (gemm_tile_val_planes)
+struct ValStePlanesEpi : ValSteEpi {
+  const unsigned char* __restrict__ planes;  // value_planes.h
+  unsigned planes_bytes;
+  int ktiles;  // K tiles of 128 along L1
+};
 constexpr float kFtmSteSharpness = 10.0f;  // k, nnue.py:41 (the STE kernel's constant)
 
 template <class Epi, class = void>
@@ -273,20 +280,23 @@ __device__ __forceinline__ void ste_pixels_select(SteFrag<BM>& f, int r) {
 // What the epilogue of a ValSteEpi tile reads from memory: the map bytes and conv outputs under the lane's accumulator
 // registers and its columns' thresholds, as loaded (unconditionally, rows and positions clamped into range; ste_tile applies
 // the guards).  Requested in the last K tile, where the staging registers are free and the MFMAs of that tile hide the trip.
-template <int BM>
+// W14: the waves of the tile are 1 x 4 instead of 2 x 2 (gemm_tile_val_planes: a wave owns all BM rows x 16 columns); only the
+// placement of the accumulators follows it, as for FusedL1Pre
+template <int BM, bool W14 = false>
 struct StePre {
-  uint8_t bit[BM / 32][2][4];
-  float cv[BM / 32][2][4], th[2];
+  static constexpr int kTM = W14 ? BM / 16 : BM / 32, kTN = W14 ? 1 : 2;
+  uint8_t bit[kTM][kTN][4];
+  float cv[kTM][kTN][4], th[kTN];
 };
-template <int BM>
-__device__ __forceinline__ void ste_prefetch(const ValSteEpi& e, StePre<BM>& p, int M, int m_base, int tile_n, int m0, int n0, int r, int q) {
+template <int BM, bool W14 = false>
+__device__ __forceinline__ void ste_prefetch(const ValSteEpi& e, StePre<BM, W14>& p, int M, int m_base, int tile_n, int m0, int n0, int r, int q) {
 #pragma unroll
-  for (int t = 0; t < 2; ++t) {
+  for (int t = 0; t < StePre<BM, W14>::kTN; ++t) {
     const int j = n0 + 16 * t + r, c = j >> 3, hw = tile_n * 8 + (j & 7);
     const int pp = c * e.G + (hw < e.G ? hw : 0);
     p.th[t] = e.thr[c];
 #pragma unroll
-    for (int i = 0; i < BM / 32; ++i)
+    for (int i = 0; i < StePre<BM, W14>::kTM; ++i)
 #pragma unroll
       for (int ee = 0; ee < 4; ++ee) {
         const int m = min(m_base + m0 + 16 * i + 4 * q + ee, M - 1);
@@ -296,15 +306,16 @@ __device__ __forceinline__ void ste_prefetch(const ValSteEpi& e, StePre<BM>& p, 
   }
 }
 
-// Epilogue of a ValSteEpi tile (BN = 64, waves 2 x 2, accumulator register e of lane 16 q + r = C[row 4 q + e][col r]):
+// Epilogue of a ValSteEpi tile (BN = 64, waves 2 x 2 or -- W14 -- 1 x 4, accumulator register e of lane 16 q + r = C[row 4 q + e][col r]):
 // the masked d tile and its threshold terms d k s (1 - s) go to LDS as the rows 0..7 / 8..15 of a [16][8 BM] operand, the
 // pixel fragments are the other one, and one 16 x 32 MFMA tile per wave contracts its quarter of the pairs; the four waves'
 // tiles are summed in wave order.  `smem` is free (the K loop ended with a barrier) and holds >= 16 (8 BM + 4) + 2048 floats.
-template <int BM, int BN>
-__device__ __forceinline__ void ste_tile(float* __restrict__ smem, const ValSteEpi& e, const f32x4 (&acc)[BM / 32][BN / 32], const SteFrag<BM>& f,
-                                         const StePre<BM>& pre, int M, int m_base, int tile_n, int m0, int n0, int tile) {
+template <int BM, int BN, bool W14 = false>
+__device__ __forceinline__ void ste_tile(float* __restrict__ smem, const ValSteEpi& e,
+                                         const f32x4 (&acc)[StePre<BM, W14>::kTM][StePre<BM, W14>::kTN], const SteFrag<BM>& f,
+                                         const StePre<BM, W14>& pre, int M, int m_base, int tile_n, int m0, int n0, int tile) {
   static_assert(BN == 64, "a tile holds the 8 channels of 8 positions");
-  constexpr int TM = BM / 32, TN = BN / 32, LDA = 8 * BM + 4;
+  constexpr int TM = StePre<BM, W14>::kTM, TN = StePre<BM, W14>::kTN, LDA = 8 * BM + 4;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = lane & 15, q = lane >> 4;
@@ -1450,6 +1461,110 @@ __global__ __launch_bounds__(256) void ftm_gemm_bf6_kernel(Mat ma, Mat mb, Epi e
   gemm_tile_bf6<BM, BN, Epi, KT, ABL>(smem, ma, mb, epi, M, N, 0, K, tiles_n, blockIdx.x, 0);
 }
 
+// ---- the 32 x 64 value tile of the STE ride fed the table's value planes (value_planes.h) --------------------------------
+// gemm_tile_bf6's six plane products in its term order (per 32-k block: lo hi, hi lo, mid mid, mid hi, hi mid, hi hi; K tiles
+// and blocks ascending) with the waves 1 x 4: wave w owns all 32 rows x columns 16 w .. 16 w + 15, so no B fragment is shared
+// between waves and B needs no LDS, no split and no barrier -- one 16-byte load per (32-k block, plane) and lane, straight from
+// the plane buffer into the MFMA's operand.  The loads of a block are requested in consumption order (planes 0, 2, 1) one K
+// tile (four blocks, 48 registers) ahead: block kb of tile t + 1 is requested as soon as block kb of tile t is contracted, and
+// every request is unconditional and in-window, so the waits in front of the MFMAs count down (12 loads of B and the 4 of A in
+// flight at a tile's start).  The depth is bounded by the launch's 168 registers (three workgroups per CU), not by the latency.
+// A (d_out, shared by the four waves) is fetched, split with split8 and staged per K tile of 128 into three bf16 images as
+// gemm_tile_bf6 stages its A; two sets of images alternate, so a K tile costs one barrier.  The last K tile is written out
+// behind the loop: its staging and refill registers are dead, and it requests what the epilogue reads (ste_pixels,
+// ste_prefetch) under its MFMAs.
+constexpr int kValPlanesLds = 2 * 3 * 32 * kBfK * 2;  // 48 KB
+template <class Epi>
+__device__ __forceinline__ void gemm_tile_val_planes(unsigned char* __restrict__ smem, const Mat& ma, const Epi& epi, int M, int tiles_n, int tile) {
+  constexpr int BM = 32, KB = kBfK / 32, PA = BM * kBfK * 2, kSet = 3 * PA;
+  const __amdgpu_buffer_rsrc_t rsa = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(ma.p), 0, ma.bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsb = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(epi.planes), 0, epi.planes_bytes, 0x00020000);
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int r = lane & 15, q = lane >> 4;
+  const int tile_n = tile % tiles_n, tile_m = tile / tiles_n;
+  const int m_base = tile_m * BM, n0 = 16 * wave;
+  const int ktiles = epi.ktiles;  // >= 1
+  // A: two 8-k runs per thread and K tile (row g / 16, run g % 16 of g = tid, tid + 256): consecutive lanes walk a row
+  u32x4 ra[2][2];
+  auto fetch_a = [&](int k0) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int g = tid + 256 * i, row = g >> 4, k = k0 + (g & 15) * 8;
+      ra[i][0] = mat_load<false>(rsa, ma, m_base + row, k);
+      ra[i][1] = mat_load<false>(rsa, ma, m_base + row, k + 4);
+    }
+  };
+  auto stage = [&](unsigned char* __restrict__ As) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int g = tid + 256 * i, row = g >> 4, c = g & 15;
+      u32x4 hi, mid, lo;
+      split8(ra[i][0], ra[i][1], hi, mid, lo);
+      *reinterpret_cast<u32x4*>(As + bf_img(row, c)) = hi;
+      *reinterpret_cast<u32x4*>(As + PA + bf_img(row, c)) = mid;
+      *reinterpret_cast<u32x4*>(As + 2 * PA + bf_img(row, c)) = lo;
+    }
+  };
+  // B: the lane's 16 bytes of fragment (wave, kb) of plane p of block (tile_n, kt); everything but lane * 16 is scalar
+  u32x4 rb[KB][3];
+  auto fetch_b = [&](int kt, int kb) {
+    const int at = (tile_n * ktiles + kt) * kValPlaneBlock + val_plane_frag(wave, kb);
+    rb[kb][0] = __builtin_amdgcn_raw_buffer_load_b128(rsb, lane * 16, at, 0);
+    rb[kb][2] = __builtin_amdgcn_raw_buffer_load_b128(rsb, lane * 16, at + 2 * kValPlaneBytes, 0);
+    rb[kb][1] = __builtin_amdgcn_raw_buffer_load_b128(rsb, lane * 16, at + kValPlaneBytes, 0);
+  };
+  f32x4 acc[2][1];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) acc[i][0] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  auto contract_block = [&](const unsigned char* __restrict__ As, int kb) {
+    const int c = kb * 4 + q;  // this lane's 8 k of the 32-k block
+    bf16x8 a[3][2];
+#pragma unroll
+    for (int pl = 0; pl < 3; ++pl)
+#pragma unroll
+      for (int i = 0; i < 2; ++i) a[pl][i] = *reinterpret_cast<const bf16x8*>(As + pl * PA + bf_img(16 * i + r, c));
+    constexpr int pa[6] = {2, 0, 1, 1, 0, 0}, pb[6] = {0, 2, 1, 0, 1, 0};  // smallest terms first (gemm_tile_bf6)
+#pragma unroll
+    for (int s6 = 0; s6 < 6; ++s6)
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+        acc[i][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[pa[s6]][i], __builtin_bit_cast(bf16x8, rb[kb][pb[s6]]), acc[i][0], 0, 0, 0);
+  };
+  fetch_a(0);
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int kb = 0; kb < KB; ++kb) fetch_b(0, kb);
+  __builtin_amdgcn_sched_barrier(0);
+  int kt = 0;
+  for (; kt + 1 < ktiles; ++kt) {
+    unsigned char* __restrict__ As = smem + (kt & 1) * kSet;
+    stage(As);
+    __syncthreads();
+    fetch_a((kt + 1) * kBfK);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int kb = 0; kb < KB; ++kb) {
+      contract_block(As, kb);
+      fetch_b(kt + 1, kb);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+  unsigned char* __restrict__ As = smem + (kt & 1) * kSet;
+  stage(As);
+  __syncthreads();
+  SteFrag<BM> stef;
+  StePre<BM, true> stepre;
+  ste_pixels<BM>(epi, stef, M, m_base, tile_n, wave, r, q);
+  ste_prefetch<BM, true>(epi, stepre, M, m_base, tile_n, 0, n0, r, q);
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int kb = 0; kb < KB; ++kb) contract_block(As, kb);
+  ste_pixels_select<BM>(stef, r);
+  __syncthreads();  // the epilogue's LDS aliases the A images
+  ste_tile<BM, 64, true>(reinterpret_cast<float*>(smem), epi, acc, stef, stepre, M, m_base, tile_n, 0, n0, tile);
+}
+
 template <int BM, int BN, bool AKC, class Epi>
 __global__ __launch_bounds__(256) void ftm_gemm_bf_kernel(Mat ma, Mat mb, Epi epi, int M, int N, int K, int klen, int tiles_n, GroupArgs ga) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[gemm_bf_lds_bytes<BM, BN, kBfK>()];
@@ -1737,12 +1852,16 @@ __global__ __launch_bounds__(256) void ftm_backward_kernel(Mat wa, Mat wb, BwwEp
 }
 
 // The same launch with the weight-gradient tiles on the bf16 matrix unit (gemm_tile_bf, WM x 64 x 128); value-gradient
-// tiles (both operands f32) and the rider keep the f32 MFMA.  VE = ValSteEpi: the value tiles also leave the STE partials.
+// tiles (both operands f32) and the rider keep the f32 MFMA.  VE = ValSteEpi: the value tiles also leave the STE partials;
+// VE = ValStePlanesEpi: and read the table from the value planes, as six bf16 plane products (gemm_tile_val_planes).
 template <int WM, int VM, int VN, int VK, bool V6 = false, bool W64 = false, class VE = ValEpi>
 __global__ __launch_bounds__(256) void ftm_backward_bf_kernel(Mat wa, Mat wb, BwwEpi we, int wM, int wN, int wK, int w_tiles_n, int n_w,
                                                               Mat va, Mat vb, VE ve, int vM, int vN, int vK, int v_tiles_n, int n_v,
                                                               CwArgs c, TailRows t, SmallWgrad sw) {
-  constexpr int kW = gemm_bf_lds_bytes<WM, 64, W64 ? kBf64K : kBfK>(), kV = V6 ? gemm_bf6_lds_bytes<VM, VN>() : gemm_lds_floats<VM, VN, VK, true, true>() * 4;
+  constexpr bool VP = std::is_same<VE, ValStePlanesEpi>::value;  // the value tiles read the table's value planes (gemm_tile_val_planes)
+  static_assert(!VP || (VM == 32 && VN == 64 && VK == kBfK && !V6), "the planes-fed value tile is 32 x 64 x 128");
+  constexpr int kW = gemm_bf_lds_bytes<WM, 64, W64 ? kBf64K : kBfK>(),
+                kV = VP ? kValPlanesLds : V6 ? gemm_bf6_lds_bytes<VM, VN>() : gemm_lds_floats<VM, VN, VK, true, true>() * 4;
   constexpr int kC = gemm_lds_floats<32, 64, 128, false, false>() * 4;
   constexpr int kWV = kW > kV ? kW : kV;
   constexpr int kLds = kWV > kC ? kWV : kC;
@@ -1751,7 +1870,8 @@ __global__ __launch_bounds__(256) void ftm_backward_bf_kernel(Mat wa, Mat wb, Bw
   float* smem = reinterpret_cast<float*>(smem_b);
   const int blk = blockIdx.x;
   if (blk < n_v) {
-    if constexpr (V6) gemm_tile_bf6<VM, VN, VE>(smem_b, va, vb, ve, vM, vN, 0, vK, v_tiles_n, blk, 0);
+    if constexpr (VP) gemm_tile_val_planes<VE>(smem_b, va, ve, vM, v_tiles_n, blk);  // (K = L1 as ve.ktiles tiles of 128)
+    else if constexpr (V6) gemm_tile_bf6<VM, VN, VE>(smem_b, va, vb, ve, vM, vN, 0, vK, v_tiles_n, blk, 0);
     else gemm_tile<VM, VN, VK, true, true, VE>(smem, va, vb, ve, vM, vN, 0, vK, v_tiles_n, blk, 0);
   } else if (blk < n_v + n_w) {
     if constexpr (W64) gemm_tile_bf64<WM, false, BwwEpi>(smem_b, wa, wb, we, wM, wN, 0, wK, w_tiles_n, blk - n_v, 0);
@@ -2287,6 +2407,7 @@ bool merged_backward_shape(int B, int F, int P, int L1, bool* big) {
 }
 // value tiles of the merged launch as six bf16 plane products: for the 64 x 64 tiles (C3 shapes: 43.5 vs 46.0 us for the
 // launch); the 32 x 64 tiles of the batch-512 shape are latency-bound per K tile and lose with the 64-deep bf16 tiles (27.2 vs 26.3 us)
+// -- they take the six plane products only with the table split once per step and streamed from the value planes (val_planes_tiles)
 // weight tiles with K tiles of 64 (gemm_tile_bf64) in the merged launch
 bool merged_w64() {
   static const int w64 = env_int("NNUE_FTM_BWD_W64", 1);  // developer knob
@@ -2311,6 +2432,10 @@ struct SteArgs {  // the STE stage 1 riding in the value tiles (nnue_ftm_backwar
   float* partial;
   int64_t partial_bytes;
 };
+struct ValPlanes {  // nnue_ftm_backward_planes: the plane buffer nnue_ftm_conv_binarize_value_planes wrote this step
+  const void* p;
+  int64_t bytes;
+};
 
 // Value tiles of the merged launch when they carry the STE partials (= the partials' run length), 0 where the shape is not taken:
 // 8 channels (fps * G == P with G the grid of an H x W image at `stride`), the merged launch with its default bf16 weight tiles
@@ -2329,6 +2454,35 @@ int64_t ste_ride_tiles(int B, int F, int P, int L1, int H, int W, int stride) {
   return (int64_t)((B + vm - 1) / vm) * ((Gh * Gw + 7) / 8);
 }
 }  // namespace
+
+namespace {
+// Value tiles of the merged launch that read the table's value planes (value_planes.h; gemm_tile_val_planes), 0 where the shape
+// is not taken: the STE ride's shape on 32-row value tiles (ste_ride_tiles' conditions, restated on P alone for
+// nnue_ftm_uses_bf16, which knows no image size), L1 a multiple of the planes' 8-j chunk, and at least one value tile per CU --
+// the shape the planes were measured at; below it the tiles of a launch do not queue behind each other's matrix time and keep
+// the f32 tiles.  NNUE_FTM_VAL_PLANES=0 (today's f32 tiles) and NNUE_FTM_VAL_PLANES_MIN_TILES (the floor; tests reach the
+// kernel at small shapes with 1) are developer knobs read per call.
+int64_t val_planes_tiles(int B, int F, int P, int L1) {
+  if (env_int("NNUE_FTM_VAL_PLANES", 1) == 0) return 0;
+  if (!nnue_ftm_supported(F, P, L1) || !shape_ok(B, F, P, L1) || P % 8 != 0 || L1 % 8 != 0) return 0;
+  bool big = false;
+  if (!merged_backward_shape(B, F, P, L1, &big) || merged_bf_wm() != 64 || !merged_w64()) return 0;
+  if (big || plan(B, P, L1, true, false).cfg != 0) return 0;  // 64-row value tiles
+  const int64_t tiles = (int64_t)((B + 31) / 32) * ((P / 8 + 7) / 8);
+  if (tiles < env_int("NNUE_FTM_VAL_PLANES_MIN_TILES", 256)) return 0;
+  return (int64_t)((P / 8 + 7) / 8) * ((L1 + kBfK - 1) / kBfK) * kValPlaneBlock < (1ll << 31) ? tiles : 0;
+}
+}  // namespace
+
+extern "C" int nnue_ftm_value_planes_supported(int B, int F, int P, int L1, int H, int W, int stride) {
+  const int64_t tiles = val_planes_tiles(B, F, P, L1);
+  return tiles > 0 && ste_ride_tiles(B, F, P, L1, H, W, stride) == tiles;
+}
+
+extern "C" int64_t nnue_ftm_value_planes_bytes(int B, int F, int P, int L1) {
+  if (B <= 0 || F <= 1 || P <= 0 || L1 <= 0 || P % 8 != 0 || L1 % 8 != 0) return 0;
+  return (int64_t)((P / 8 + 7) / 8) * ((L1 + kBfK - 1) / kBfK) * kValPlaneBlock;
+}
 
 extern "C" int64_t nnue_ftm_backward_ste_chunks(int B, int F, int P, int L1, int H, int W, int stride) {
   return ste_ride_tiles(B, F, P, L1, H, W, stride);
@@ -2364,7 +2518,7 @@ namespace {
 int ftm_backward_impl(const uint8_t* bits, const float* sink, const float* d_out, const float* weight, int B, int F, int P, int L1,
                       float* d_weight, float* d_bias, float* d_conv_out, const float* ft, const float* d_z1, int L2, float* d_w1,
                       float* sq_partial, int K, const int32_t* seg, int grouped_rows, const nnue_cls_rider* small, const SteArgs* ste,
-                      nnue_stream_t stream);
+                      nnue_stream_t stream, const ValPlanes* vp = nullptr);
 }
 extern "C" int nnue_ftm_backward(const uint8_t* bits, const float* sink, const float* d_out, const float* weight, int B, int F, int P,
                                  int L1, float* d_weight, float* d_bias, float* d_conv_out, const float* ft, const float* d_z1, int L2,
@@ -2373,6 +2527,17 @@ extern "C" int nnue_ftm_backward(const uint8_t* bits, const float* sink, const f
   const SteArgs sa{ste_images, ste_patches, ste_conv_out, ste_thr, H, W, stride, ste_partial, ste_partial_bytes};
   return ftm_backward_impl(bits, sink, d_out, weight, B, F, P, L1, d_weight, d_bias, d_conv_out, ft, d_z1, L2, d_w1, sq_partial, 1, nullptr, 0,
                            small, ste_partial ? &sa : nullptr, stream);
+}
+extern "C" int nnue_ftm_backward_planes(const uint8_t* bits, const float* sink, const float* d_out, const float* weight, int B, int F, int P,
+                                        int L1, float* d_weight, float* d_bias, float* d_conv_out, const float* ft, const float* d_z1, int L2,
+                                        float* d_w1, float* sq_partial, const nnue_cls_rider* small, const float* ste_images,
+                                        const float* ste_patches, const float* ste_conv_out, const float* ste_thr, int H, int W, int stride,
+                                        float* ste_partial, int64_t ste_partial_bytes, const void* val_planes, int64_t val_planes_bytes,
+                                        nnue_stream_t stream) {
+  const SteArgs sa{ste_images, ste_patches, ste_conv_out, ste_thr, H, W, stride, ste_partial, ste_partial_bytes};
+  const ValPlanes vp{val_planes, val_planes_bytes};
+  return ftm_backward_impl(bits, sink, d_out, weight, B, F, P, L1, d_weight, d_bias, d_conv_out, ft, d_z1, L2, d_w1, sq_partial, 1, nullptr, 0,
+                           small, ste_partial ? &sa : nullptr, stream, &vp);
 }
 extern "C" int nnue_ftm_backward_bucketed(const uint8_t* bits, const float* sink, const float* d_out, const float* weight, int B, int F,
                                           int P, int L1, float* d_weight, float* d_bias, float* d_conv_out, const float* ft_grouped,
@@ -2391,7 +2556,7 @@ namespace {
 int ftm_backward_impl(const uint8_t* bits, const float* sink, const float* d_out, const float* weight, int B, int F, int P, int L1,
                       float* d_weight, float* d_bias, float* d_conv_out, const float* ft, const float* d_z1, int L2, float* d_w1,
                       float* sq_partial, int K, const int32_t* seg, int grouped_rows, const nnue_cls_rider* small, const SteArgs* ste,
-                      nnue_stream_t stream) {
+                      nnue_stream_t stream, const ValPlanes* vp) {
   NNUE_REQUIRE(bits && sink && d_out && weight && d_weight && d_bias && (d_conv_out || ste), NNUE_E_ARG, "nnue_ftm_backward: null pointer");
   const int64_t ste_tiles = ste ? ste_ride_tiles(B, F, P, L1, ste->H, ste->W, ste->stride) : 0;
   NNUE_REQUIRE(!ste || ((ste->img || ste->patches) && ste->conv_out && ste->thr && ste->partial), NNUE_E_ARG,
@@ -2407,6 +2572,15 @@ int ftm_backward_impl(const uint8_t* bits, const float* sink, const float* d_out
   NNUE_REQUIRE(nnue_ftm_supported(F, P, L1), NNUE_E_SHAPE, "nnue_ftm_backward: P=%d and L1=%d must be multiples of 4", P, L1);
   NNUE_REQUIRE(nnue_aligned16(bits) && nnue_aligned16(d_out) && nnue_aligned16(weight), NNUE_E_ARG,
                "nnue_ftm_backward: pointers must be 16-byte aligned");
+  // the value planes are read where the shape takes them and the STE rides (else: the launch of nnue_ftm_backward)
+  const bool planes_fed = vp && ste && nnue_ftm_value_planes_supported(B, F, P, L1, ste->H, ste->W, ste->stride);
+  if (vp) {
+    NNUE_REQUIRE(vp->p, NNUE_E_ARG, "nnue_ftm_backward_planes: null pointer");
+    NNUE_REQUIRE(nnue_aligned16(vp->p), NNUE_E_ARG, "nnue_ftm_backward_planes: pointers must be 16-byte aligned");
+    NNUE_REQUIRE(!planes_fed || vp->bytes >= nnue_ftm_value_planes_bytes(B, F, P, L1), NNUE_E_SCRATCH,
+                 "nnue_ftm_backward_planes: value-plane buffer of %lld bytes, needs %lld", (long long)vp->bytes,
+                 (long long)nnue_ftm_value_planes_bytes(B, F, P, L1));
+  }
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int direct = (F - 1 < P) ? F - 1 : P;
   const Shape sw = plan(direct > 0 ? direct : 1, L1, B, false, false), sv = plan(B, P, L1, true, false);
@@ -2483,7 +2657,16 @@ int ftm_backward_impl(const uint8_t* bits, const float* sink, const float* d_out
   // workgroups per CU instead of two (the 168 registers allow exactly that): 43.5 -> 37.7 us at the C3 shapes, 26.2 -> 25.1 us at C2
   const bool w64 = merged_w64();
   if (ste) {  // the value tiles leave the STE partials (ValSteEpi; nnue_ftm_backward_ste_chunks said the shape is taken)
-    if (v_small)
+    if (planes_fed) {  // (v_small by nnue_ftm_value_planes_supported)
+      const int ktiles = (L1 + kBfK - 1) / kBfK;
+      ValStePlanesEpi vps{};
+      static_cast<ValSteEpi&>(vps) = vs;
+      vps.planes = static_cast<const unsigned char*>(vp->p);
+      vps.planes_bytes = (unsigned)nnue_ftm_value_planes_bytes(B, F, P, L1);
+      vps.ktiles = ktiles;
+      hipLaunchKernelGGL((ftm_backward_bf_kernel<64, 32, 64, 128, false, true, ValStePlanesEpi>), grid, dim3(256), 0, st, wa, wb, we, direct, L1, B,
+                         swr.tiles_n, n_w, va, vb, vps, B, P, L1, v_tiles_n, n_v, cw, t, sgw);
+    } else if (v_small)
       hipLaunchKernelGGL((ftm_backward_bf_kernel<64, 32, 64, 128, false, true, ValSteEpi>), grid, dim3(256), 0, st, wa, wb, we, direct, L1, B,
                          swr.tiles_n, n_w, va, vb, vs, B, P, L1, v_tiles_n, n_v, cw, t, sgw);
     else if (v6)
@@ -2887,6 +3070,8 @@ extern "C" int nnue_ftm_uses_bf16(int which, int B, int F, int P, int L1) {
   if (which == 1) return plan(direct, L1, B, false, false, true).cfg >= 6;
   if (which == 2) { bool big = false; return merged_backward_shape(B, F, P, L1, &big) ? merged_bf_wm() != 0 : plan(direct, L1, B, false, false, true).cfg >= 6; }
   if (which == 4) return values_bf6(B, P, L1);            // stand-alone value gradient: six bf16 plane products
-  if (which == 5) return merged_values_bf6(B, F, P, L1);  // value tiles of the merged launch
+  // value tiles of the merged launch: six plane products on 64-row tiles, or on the 32-row tiles fed the value planes (a caller
+  // with the STE ride passes them where nnue_ftm_value_planes_supported says yes: NnueTrainer)
+  if (which == 5) return merged_values_bf6(B, F, P, L1) || val_planes_tiles(B, F, P, L1) > 0;
   return 1;
 }

@@ -95,6 +95,13 @@ SIGNATURES = {
     "nnue_ftm_backward": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p,
                                    _c_p, _c_p, _c_int, _c_p, _c_p, _c_rider, _c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_int,
                                    _c_p, _c_i64, _c_p]),
+    "nnue_ftm_value_planes_supported": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int]),
+    "nnue_ftm_value_planes_bytes": (_c_i64, [_c_int, _c_int, _c_int, _c_int]),
+    "nnue_ftm_conv_binarize_value_planes": (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_p, _c_int, _c_int, _c_p,
+                                                     _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p]),
+    "nnue_ftm_backward_planes": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p,
+                                          _c_p, _c_p, _c_int, _c_p, _c_p, _c_rider, _c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_int,
+                                          _c_p, _c_i64, _c_p, _c_i64, _c_p]),
     "nnue_ftm_backward_bucketed": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p,
                                             _c_p, _c_p, _c_int, _c_p, _c_p, _c_int, _c_p, _c_int, _c_rider, _c_p, _c_p, _c_p,
                                             _c_p, _c_int, _c_int, _c_int, _c_p, _c_i64, _c_p]),
@@ -263,7 +270,8 @@ class time_calls:
 
 
 # entry points timed under the name of the call they replace (a caller's timer keys name the plain forms)
-_TIMED_AS = {"nnue_ftm_conv_binarize_planes": "nnue_ftm_conv_binarize", "nnue_ftm_forward_l1_planes": "nnue_ftm_forward_l1"}
+_TIMED_AS = {"nnue_ftm_conv_binarize_planes": "nnue_ftm_conv_binarize", "nnue_ftm_forward_l1_planes": "nnue_ftm_forward_l1",
+             "nnue_ftm_conv_binarize_value_planes": "nnue_ftm_conv_binarize", "nnue_ftm_backward_planes": "nnue_ftm_backward"}
 
 
 def _call(name: str, *args) -> None:
@@ -816,9 +824,12 @@ def ftm_forward_planes_bytes(batch: int, num_rows: int, positions: int, l1: int)
 
 
 def ftm_conv_binarize_planes(images: torch.Tensor, weight: torch.Tensor, thr: torch.Tensor, stride: int, table: torch.Tensor, l2: int,
-                             planes: torch.Tensor, conv_out: Optional[torch.Tensor] = None, fm: Optional[FeatureMatrix] = None):
+                             planes: torch.Tensor, conv_out: Optional[torch.Tensor] = None, fm: Optional[FeatureMatrix] = None,
+                             val_planes: Optional[torch.Tensor] = None):
     """ftm_conv_binarize whose launch also leaves `table` (input.weight) as the bf16 planes ftm_forward_l1_planes reads
-    (`planes`: a uint8 buffer of ftm_forward_planes_bytes); returns (conv_out, fm), bitwise ftm_conv_binarize's."""
+    (`planes`: a uint8 buffer of ftm_forward_planes_bytes); returns (conv_out, fm), bitwise ftm_conv_binarize's.
+    val_planes (a uint8 buffer of ftm_value_planes_bytes; shapes: ftm_value_planes_supported): the launch also leaves the planes
+    ftm_backward(val_planes=...) reads."""
     images = _need(images, torch.float32, "images")
     if images.dim() != 4 or images.shape[1] != 3:
         raise ValueError(f"images: expected [B,3,H,W], got {tuple(images.shape)}")
@@ -830,7 +841,8 @@ def ftm_conv_binarize_planes(images: torch.Tensor, weight: torch.Tensor, thr: to
     thr = _need(thr.reshape(-1), torch.float32, "threshold", (fps,))
     table = _need(table, torch.float32, "input.weight")
     f, l1 = table.shape
-    planes = _need(planes, torch.uint8, "planes")
+    if planes is not None or val_planes is None:  # (planes=None with val_planes: the value planes alone)
+        planes = _need(planes, torch.uint8, "planes")
     gh, gw = conv_out_hw(h, w, stride)
     if conv_out is None:
         conv_out = torch.empty((b, fps, gh, gw), dtype=torch.float32, device=images.device)
@@ -840,6 +852,12 @@ def ftm_conv_binarize_planes(images: torch.Tensor, weight: torch.Tensor, thr: to
         fm = FeatureMatrix.empty(b, fps * gh * gw, f, l1, images.device)
     elif fm.batch != b or fm.positions != fps * gh * gw or fm.num_rows != f:
         raise ValueError("ftm_conv_binarize_planes: buffers do not match the map")
+    if val_planes is not None:
+        val_planes = _need(val_planes, torch.uint8, "val_planes")
+        _call("nnue_ftm_conv_binarize_value_planes", images.data_ptr(), weight.data_ptr(), thr.data_ptr(), b, h, w, fps, int(stride), f,
+              table.data_ptr(), l1, int(l2), _ptr(planes), planes.numel() if planes is not None else 0, val_planes.data_ptr(), val_planes.numel(),
+              conv_out.data_ptr(), fm.bits.data_ptr(), fm.n.data_ptr(), fm.sink.data_ptr(), _stream(images))
+        return conv_out, fm
     _call("nnue_ftm_conv_binarize_planes", images.data_ptr(), weight.data_ptr(), thr.data_ptr(), b, h, w, fps, int(stride), f,
           table.data_ptr(), l1, int(l2), planes.data_ptr(), planes.numel(), conv_out.data_ptr(), fm.bits.data_ptr(), fm.n.data_ptr(),
           fm.sink.data_ptr(), _stream(images))
@@ -908,6 +926,15 @@ def ftm_backward_cw_supported(b: int, f: int, p: int, l1: int, l2: int) -> bool:
     return bool(load().nnue_ftm_backward_cw_supported(b, f, p, l1, l2))
 
 
+def ftm_value_planes_supported(b: int, f: int, p: int, l1: int, h: int, w: int, stride: int) -> bool:
+    """Shapes whose merged backward reads the table's value planes (ftm_backward(val_planes=...)); NNUE_FTM_VAL_PLANES=0: none."""
+    return bool(load().nnue_ftm_value_planes_supported(int(b), int(f), int(p), int(l1), int(h), int(w), int(stride)))
+
+
+def ftm_value_planes_bytes(b: int, f: int, p: int, l1: int) -> int:
+    return int(load().nnue_ftm_value_planes_bytes(int(b), int(f), int(p), int(l1)))
+
+
 def ftm_backward_ste_chunks(b: int, f: int, p: int, l1: int, h: int, w: int, stride: int) -> int:
     """Runs of STE partials the merged backward's value tiles leave for this shape (ftm_backward(ste=...)); 0: not taken."""
     return int(load().nnue_ftm_backward_ste_chunks(b, f, p, l1, h, w, stride))
@@ -916,7 +943,8 @@ def ftm_backward_ste_chunks(b: int, f: int, p: int, l1: int, h: int, w: int, str
 def ftm_backward(d_out: torch.Tensor, weight: torch.Tensor, fm: FeatureMatrix, d_weight: Optional[torch.Tensor] = None,
                  d_bias: Optional[torch.Tensor] = None, dst: Optional[torch.Tensor] = None, ft: Optional[torch.Tensor] = None,
                  d_z1: Optional[torch.Tensor] = None, d_w1: Optional[torch.Tensor] = None,
-                 sq_partial: Optional[torch.Tensor] = None, buckets=None, small: Optional["NnueClsRider"] = None, ste=None):
+                 sq_partial: Optional[torch.Tensor] = None, buckets=None, small: Optional["NnueClsRider"] = None, ste=None,
+                 val_planes: Optional[torch.Tensor] = None):
     """(d_weight, d_bias, d_conv_out) in one launch; bitwise the results of ftm_backward_weight + ftm_backward_values.
     ste = (images [B, 3, H, W], conv_out, thr, stride, partial[, patches]): the value tiles also leave stage 1 of ste_conv_backward
     as [fps * 28][ftm_backward_ste_chunks(...)] floats in `partial` (its second stage: sgd_step(ste=...)); with the im2col
@@ -925,7 +953,9 @@ def ftm_backward(d_out: torch.Tensor, weight: torch.Tensor, fm: FeatureMatrix, d
     small (classifier_train_rider(...)): the classifier's small gradients + mean loss run as one more tile family of the launch.
     With ft [B, L1], d_z1 [B, L2] and d_w1 [L2, L1] the launch also writes d_w1 = d_z1^T l0 (the pairwise block of ft).
     buckets (a BucketPlan): d_w1 [K, L2, L1]; ft / d_z1 are then the GROUPED-row copies [tiles*16, .] the bucketed
-    classifier step left in its scratch."""
+    classifier step left in its scratch.
+    val_planes (with ste, no buckets): the planes ftm_conv_binarize_planes(val_planes=...) wrote from `weight` this step; where
+    ftm_value_planes_supported says yes the value tiles read them (six bf16 plane products) instead of the table."""
     d_out = _need(d_out, torch.float32, "d_out")
     weight = _need(weight, torch.float32, "input.weight")
     b, l1 = d_out.shape
@@ -967,7 +997,12 @@ def ftm_backward(d_out: torch.Tensor, weight: torch.Tensor, fm: FeatureMatrix, d
             fm.positions, l1, d_weight.data_ptr(), d_bias.data_ptr(), _ptr(dst),
             _ptr(ft if d_w1 is not None else None), _ptr(d_z1 if d_w1 is not None else None), l2, _ptr(d_w1), _ptr(sq_partial))
     rider = ctypes.pointer(small) if small is not None else None
-    if buckets is None:
+    if val_planes is not None:
+        if buckets is not None:
+            raise ValueError("ftm_backward: the value planes have no bucketed form")
+        val_planes = _need(val_planes, torch.uint8, "val_planes")
+        _call("nnue_ftm_backward_planes", *args, rider, *ste_args, val_planes.data_ptr(), val_planes.numel(), _stream(d_out))
+    elif buckets is None:
         _call("nnue_ftm_backward", *args, rider, *ste_args, _stream(d_out))
     else:
         _call("nnue_ftm_backward_bucketed", *args, buckets.K, buckets.seg.data_ptr(), rows, rider, *ste_args, _stream(d_out))

@@ -349,6 +349,15 @@ class NnueTrainer:
             need = self.fps * 28 * ste_chunks * 4
             if self.ste_scratch.numel() < need:
                 self.ste_scratch = torch.empty((need,), **u8)
+        # Where the ride runs 32-row value tiles on a chip-filling launch (the CIFAR batch-512 shape, where the forward takes its
+        # planes too), the conv launch's riders also leave the table rows the value gradient reads as bf16 planes, and the merged
+        # backward's value tiles read those on the bf16 matrix unit (nnue_ftm_conv_binarize_value_planes ->
+        # nnue_ftm_backward_planes).  Written by a step's conv launch and read by that step's backward only: the table is updated
+        # after it.  NNUE_FTM_VAL_PLANES=0 keeps the f32 tiles.
+        self.val_planes = None
+        if (self.ride_ste and not self.use_patches and self.bucket_plan is None
+                and lib.ftm_value_planes_supported(B, self.F, self.P, self.L1, self.H, self.W, self.stride)):
+            self.val_planes = torch.empty((lib.ftm_value_planes_bytes(B, self.F, self.P, self.L1),), **u8)
         # Inside a step group (step_many) the table's update of step t and the FeatureTransformer forward of step t+1 are ONE
         # pass over the table (nnue_ftm_backward_weight_update_forward: the next batch is resident, its map only needs the conv
         # weights the small tensors' update has just written, and the update leaves every new table tile in registers) -- the
@@ -449,9 +458,9 @@ class NnueTrainer:
     def _segment(self, name: str) -> None:
         p, g = self.p, self.g
         if name == "front":
-            if self.fwd_planes:  # conv + {0,1} map + counts, and the table's bf16 planes from the same launch's riders
+            if self.fwd_planes or self.val_planes is not None:  # conv + {0,1} map + counts, and the table's bf16 planes from the same launch's riders
                 lib.ftm_conv_binarize_planes(self.images, p["conv.weight"], p["visual_threshold"], self.stride, p["input.weight"], self.L2,
-                                             self.planes, conv_out=self.conv_out, fm=self.fm)
+                                             self.planes, conv_out=self.conv_out, fm=self.fm, val_planes=self.val_planes)
                 return
             if self.use_mfma:  # conv + {0,1} map + counts in one launch
                 lib.ftm_conv_binarize(self.images, p["conv.weight"], p["visual_threshold"], self.stride, self.F, self.L1,
@@ -505,7 +514,7 @@ class NnueTrainer:
                                  d_w1=g["classifier.classifier.0.weight"] if self.ride_dw1 else None, sq_partial=self.sq_partial,
                                  buckets=self.bucket_plan, small=self._rider(self.loss) if self.ride_small else None,
                                  ste=((self.images, self.conv_out, p["visual_threshold"], self.stride, self.ste_scratch, self.patches)
-                                      if self.ride_ste else None))
+                                      if self.ride_ste else None), val_planes=self.val_planes)
             elif self.use_mfma:
                 lib.ftm_backward_weight(self.d_ft, self.fm, d_weight=g["input.weight"], d_bias=g["input.bias"])
             elif self.use_bits:
