@@ -231,8 +231,12 @@ __device__ __forceinline__ void row_add(const EngineNet& net, int row, int32_t (
   }
 }
 
+// max(0, min(v, q1)) in the engine's order (nnue_engine.cpp:726-729): with a negative quantized_one the result is 0 everywhere,
+// where a clamp that tests the lower bound first would give quantized_one for every v >= 0.
 __device__ __forceinline__ int32_t wrap_clip(int32_t sum, int quantized_one) {
-  return clamp_i((int32_t)(int16_t)sum, 0, quantized_one);  // int16 accumulator wraps
+  const int32_t v = (int32_t)(int16_t)sum;  // int16 accumulator wraps
+  const int32_t m = v < quantized_one ? v : quantized_one;
+  return m > 0 ? m : 0;
 }
 
 template <bool kBias, bool kStore>

@@ -4,7 +4,7 @@
 // points (nnue_engine.h is found on the include path oracle/Makefile sets; the engine's sources are compiled where they
 // lie) with a layer stack index of the caller's choice, for several images and indices per process:
 //
-//   engine_driver <model.nnue> <images.bin> <H> <W> <count> <k> [<k> ...]
+//   engine_driver [--bits] <model.nnue> <images.bin> <H> <W> <count> <k> [<k> ...]
 //
 // images.bin holds `count` buffers of 3*H*W float32 each, handed to the engine as they stand.  One line per (image, k):
 //
@@ -12,16 +12,36 @@
 //
 // logits and density with ten fixed decimals (the tool's format; density = float(active ids) / float(total features), its
 // expression), the ids as the engine returns them after that very call.  A call that returns no logits ends the run with
-// status 2.
+// status 2.  Ten decimals are exact for multiples of 1/64 but not for a quotient by 3.0 or 0.1: with the leading flag --bits
+// every logit and the density are printed as the eight hex digits of their float32 bit pattern instead (the rest of the line,
+// and the output without the flag, are unchanged).
 #include <nnue_engine.h>
 
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
+static void print_float(float v, bool bits) {
+    if (!bits) {
+        std::printf("%.10f", static_cast<double>(v));
+        return;
+    }
+    std::uint32_t u;
+    std::memcpy(&u, &v, sizeof u);
+    std::printf("%08x", static_cast<unsigned>(u));
+}
+
 int main(int argc, char** argv) {
+    const char* program = argv[0];
+    const bool bits = argc > 1 && std::strcmp(argv[1], "--bits") == 0;
+    if (bits) {
+        ++argv;
+        --argc;
+    }
     if (argc < 7) {
-        std::fprintf(stderr, "usage: %s <model.nnue> <images.bin> <H> <W> <count> <k> [<k> ...]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s [--bits] <model.nnue> <images.bin> <H> <W> <count> <k> [<k> ...]\n", program);
         return 1;
     }
     const int h = std::atoi(argv[3]), w = std::atoi(argv[4]), count = std::atoi(argv[5]);
@@ -57,8 +77,13 @@ int main(int argc, char** argv) {
             engine.get_active_features(ids);
             const float density = total > 0 ? static_cast<float>(ids.size()) / total : 0.0f;
             std::printf("%d %d |", i, k);
-            for (size_t c = 0; c < logits.size(); ++c) std::printf("%s%.10f", c ? "," : " ", static_cast<double>(logits[c]));
-            std::printf(" | %.10f |", static_cast<double>(density));
+            for (size_t c = 0; c < logits.size(); ++c) {
+                std::printf("%s", c ? "," : " ");
+                print_float(logits[c], bits);
+            }
+            std::printf(" | ");
+            print_float(density, bits);
+            std::printf(" |");
             for (int id : ids) std::printf(" %d", id);
             std::printf("\n");
         }

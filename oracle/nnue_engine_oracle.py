@@ -5,8 +5,9 @@ Pinned against outputs of the real engine: `oracle/_ref/nnue_inference` (the ref
 oracle/Makefile) was run on the committed `.nnue` fixtures; tests/golden/make_golden_engine.py holds the recipe and
 tests/golden/engine_cases.npz the inputs and printed outputs; tests/golden/engine_shapes.npz (oracle/engine_driver.cpp,
 tests/golden/make_golden_engine_shapes.py) holds the same for frames with W != H, more than 64 channels per cell and
-`bucket` 0..K, with the engine's active feature ids.  Only tests/, __graft_entry__.smoke() and bench.py's
-cpu_baseline leg may import this module.
+`bucket` 0..K, with the engine's active feature ids; tests/golden/engine_edges.npz (make_golden_engine_edges.py) the float32
+bit patterns for models whose scales, quantized_one, thresholds, table and biases leave what serialize.py writes.
+Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this module.
 
 The engine has three behaviours that are easy to miss and are kept here exactly as they are:
   * the image buffer is indexed as HWC (`input[(h*W + w)*3 + c]`, nnue_engine.cpp:66) although the Python side
@@ -118,8 +119,8 @@ def _trunc_div(a: np.ndarray, d: int) -> np.ndarray:
     return np.sign(a) * (np.abs(a) // d)
 
 
-def conv_forward(m, image_flat: np.ndarray, h: int, w: int) -> Tuple[np.ndarray, int]:
-    """ConvLayer::forward (nnue_engine.cpp:48-158): int8 [out_h][out_w][oc], and the stride used."""
+def conv_accumulate(m, image_flat: np.ndarray, h: int, w: int) -> Tuple[np.ndarray, int]:
+    """The int32 sums of ConvLayer::forward before its division (int64 [out_h][out_w][oc]), and the stride used."""
     oc, scale = m["oc"], np.float32(m["conv_scale"])
     s = conv_stride(h, m["grid"])
     oh, ow = (h + 2 - 3) // s + 1, (w + 2 - 3) // s + 1
@@ -132,7 +133,13 @@ def conv_forward(m, image_flat: np.ndarray, h: int, w: int) -> Tuple[np.ndarray,
         for kw in range(3):
             patch = xp[kh:kh + (oh - 1) * s + 1:s, kw:kw + (ow - 1) * s + 1:s]  # [oh][ow][ic]
             acc += np.einsum("hwi,oi->hwo", patch, wq[:, kh, kw, :])
-    out = np.clip(_trunc_div(acc, int(scale)), -127, 127).astype(np.int8)
+    return acc, s
+
+
+def conv_forward(m, image_flat: np.ndarray, h: int, w: int) -> Tuple[np.ndarray, int]:
+    """ConvLayer::forward (nnue_engine.cpp:48-158): int8 [out_h][out_w][oc], and the stride used."""
+    acc, s = conv_accumulate(m, image_flat, h, w)
+    out = np.clip(_trunc_div(acc, int(np.float32(m["conv_scale"]))), -127, 127).astype(np.int8)
     return out, s
 
 
@@ -150,28 +157,48 @@ def active_features(m, conv_out: np.ndarray) -> np.ndarray:
     return np.nonzero(on)[0].astype(np.int64)
 
 
+def ft_accumulate(m, ids: np.ndarray) -> np.ndarray:
+    """The accumulator sums of FeatureTransformer::forward as integers, before the int16 arithmetic wraps them."""
+    return m["ft_b"].astype(np.int64) + m["ft_w"][ids].astype(np.int64).sum(axis=0)
+
+
 def ft_forward(m, ids: np.ndarray) -> np.ndarray:
     """FeatureTransformer::forward with int16 wrap-around (simd_scalar.cpp:78-96), then the clipped ReLU of
-    nnue_engine.cpp:726-729."""
-    acc = m["ft_b"].astype(np.int64) + m["ft_w"][ids].astype(np.int64).sum(axis=0)
-    acc = ((acc + 32768) % 65536 - 32768).astype(np.int64)  # int16 arithmetic wraps
-    return np.clip(acc, 0, int(np.int16(m["quantized_one"])))
+    nnue_engine.cpp:726-729: max(0, min(v, (int16)quantized_one)), in that order -- with a negative quantized_one the
+    result is 0 everywhere (np.clip would give quantized_one)."""
+    acc = ((ft_accumulate(m, ids) + 32768) % 65536 - 32768).astype(np.int64)  # int16 arithmetic wraps
+    return np.maximum(0, np.minimum(acc, int(np.int16(m["quantized_one"]))))
+
+
+def stack_trace(s, ft: np.ndarray, l1: int, l2: int, l3: int, quot1=None) -> Dict[str, np.ndarray]:
+    """LayerStack::forward_multiclass (nnue_engine.cpp:480-539) with every intermediate: a, b (the two halves of ft), prod
+    = a*b/128 and pair (after the clamps), acc1 / quot1 / h1, acc2 / quot2 / h2 (the sums, the quotients before their clamps,
+    the layer outputs), acc3 and the float32 logits.  quot1: a function of the trace so far that gives the layer-1 quotient
+    in place of the engine's (tests ask what another rounding of it would do to the logits)."""
+    half = l1 // 2
+    t: Dict[str, np.ndarray] = {"a": ft[:half].astype(np.int64), "b": ft[half:2 * half].astype(np.int64)}
+    t["prod"] = _trunc_div(t["a"] * t["b"], 128)
+    pair = np.zeros(l1, dtype=np.int64)
+    pair[:half] = np.clip(t["prod"], 0, 127)
+    pair[half:2 * half] = np.clip(t["a"], 0, 127)
+    t["pair"] = pair
+    t["acc1"] = s["l1_b"][:l2].astype(np.int64) + s["l1_w"][:l2].astype(np.int64) @ pair
+    # dense_forward_scalar: float division, truncation, clamp to [0, 127] (simd_scalar.cpp:117-136)
+    t["quot1"] = np.trunc(t["acc1"].astype(np.float32) / np.float32(s["l1_scale"])).astype(np.int64)
+    if quot1 is not None:
+        t["quot1"] = np.asarray(quot1(t), dtype=np.int64)
+    t["h1"] = np.clip(t["quot1"], 0, 127)
+    t["acc2"] = s["l2_b"].astype(np.int64) + s["l2_w"][:, :l2].astype(np.int64) @ t["h1"]
+    t["quot2"] = _trunc_div(t["acc2"], int(np.float32(s["l2_scale"])))
+    t["h2"] = np.maximum(np.clip(t["quot2"], -127, 127), 0)
+    t["acc3"] = s["out_b"].astype(np.int64) + s["out_w"].astype(np.int64) @ t["h2"]
+    t["logits"] = (t["acc3"].astype(np.float32) / np.float32(s["out_scale"])).astype(np.float32)
+    return t
 
 
 def forward_multiclass(s, ft: np.ndarray, l1: int, l2: int, l3: int) -> np.ndarray:
     """LayerStack::forward_multiclass (nnue_engine.cpp:480-539)."""
-    half = l1 // 2
-    a, b = ft[:half], ft[half:2 * half]
-    pair = np.zeros(l1, dtype=np.int64)
-    pair[:half] = np.clip(_trunc_div(a * b, 128), 0, 127)
-    pair[half:2 * half] = np.clip(a, 0, 127)
-    acc1 = s["l1_b"][:l2].astype(np.int64) + s["l1_w"][:l2].astype(np.int64) @ pair
-    # dense_forward_scalar: float division, truncation, clamp to [0, 127] (simd_scalar.cpp:117-136)
-    h1 = np.clip(np.trunc(acc1.astype(np.float32) / np.float32(s["l1_scale"])).astype(np.int64), 0, 127)
-    acc2 = s["l2_b"].astype(np.int64) + s["l2_w"][:, :l2].astype(np.int64) @ h1
-    h2 = np.maximum(np.clip(_trunc_div(acc2, int(np.float32(s["l2_scale"]))), -127, 127), 0)
-    acc3 = s["out_b"].astype(np.int64) + s["out_w"].astype(np.int64) @ h2
-    return (acc3.astype(np.float32) / np.float32(s["out_scale"])).astype(np.float32)
+    return stack_trace(s, ft, l1, l2, l3)["logits"]
 
 
 def evaluate_logits(m, image_flat: np.ndarray, h: int, w: int, bucket: int = 0) -> Tuple[np.ndarray, np.float32]:
