@@ -848,6 +848,40 @@ int nnue_engine_stream_step_u8(const nnue_engine_model* m, const nnue_engine_sta
                                float* logits, float* density, int32_t* changed, int32_t* stack_out, void* scratch,
                                int64_t scratch_bytes, nnue_stream_t stream);
 
+/* nnue_engine_stream_step_u8 from the dirty rectangles of the frames: NNUEEvaluator::evaluate_incremental /
+ * update_features (engine/src/nnue_engine.cpp:739-786, :818-821) with the added and removed feature lists derived on the device
+ * from the pixels -- the conv (nnue_engine.cpp:48-158 on Normalize's output, data/datasets.py:366-369; the logits its consumer
+ * reads, evaluate.py:150-161) is re-run only on the grid cells a rectangle touches, and only the table rows that flipped are
+ * walked.  A step costs O(touched cells + flips) per stream and needs no scratch.
+ * Rectangles: CSR in device memory, int32 -- stream s owns rects[rect_off[s] .. rect_off[s+1]), each y0, x0, y1, x1, half-open,
+ * in frame pixels; n_rects is the number of rectangles in the buffer.  Every range is clipped to [0, n_rects] and a reversed
+ * range is empty, as the ranges of nnue_engine_stream_update; with n_rects == 0 both pointers may be NULL.
+ * Definition, as set arithmetic.  Geometry is the engine's: stride = ceil((H-1)/(grid-1)), OH = (H-1)/stride + 1, OW =
+ * (W-1)/stride + 1; cell (oh, ow) reads frame rows oh*stride-1 .. oh*stride+1 and columns ow*stride-1 .. ow*stride+1, zero
+ * padding outside the frame.  For stream s let cells(s) be the cells whose window meets any of its rectangles, each rectangle
+ * first clipped to [0,H) x [0,W).  For every such cell and every channel c < oc, feature (oh*OW + ow)*oc + c takes the value
+ * nnue_engine_stream_step_u8 would give it on this frame (the same 768-entry table, taps, truncating division, clamp, and
+ * (float)(int8)q > threshold && c < 64); every other bit of the stream's stored set keeps its value.  The accumulator, logits,
+ * density = |new| / num_features, changed = |new xor old| and the stack choice follow as in the other stream calls.
+ * Hence: if the frame differs from the one behind the stored set only inside the rectangles -- same H x W, layout, constants and
+ * model tensors -- every output is bit-identical to nnue_engine_stream_step_u8 on the whole frame.  That condition is the
+ * caller's promise; breaking it is not undefined behaviour, the result is the set arithmetic above.
+ * Overlapping and repeated rectangles are harmless; an empty or inverted rectangle, and one wholly outside the frame, select
+ * nothing; a stream without rectangles returns its unchanged logits with changed == 0.  A stream that is not valid ignores its
+ * rectangles: it is evaluated over the whole frame from the empty set and the bias, as the whole-frame step evaluates it, and
+ * becomes valid.  Only src->layout == 1 (hwc) is accepted: under chw a pixel rectangle does not map to neighbouring taps
+ * (NNUE_E_ARG).  The state keeps its layout; this call and every other stream call may follow one another on one buffer.
+ * No scratch, no allocation, no host-device copy, no synchronisation: fit for stream capture.  Checks and codes as
+ * nnue_engine_stream_step_u8 and nnue_engine_stream_update (stack_out required iff st); NNUE_E_ARG also for n_rects < 0 and for
+ * n_rects > 0 with a NULL rects or rect_off; NNUE_E_SHAPE where the kernel's LDS (that of nnue_engine_stream_update plus the
+ * table) exceeds 64 KB or a frame holds 2^31 bytes.  Every refusal comes before anything is launched. */
+int nnue_engine_stream_step_u8_regions(const nnue_engine_model* m, const nnue_engine_stacks* st /* NULL: m's own stack */,
+                                       const nnue_engine_u8_frames* src, int S, int H, int W,
+                                       const int32_t* rects /* device [n_rects][4]: y0, x0, y1, x1, half-open, frame pixels */,
+                                       const int32_t* rect_off /* device [S + 1], CSR over rects */, int64_t n_rects,
+                                       const int32_t* stack_in, void* state, int64_t state_bytes,
+                                       float* logits, float* density, int32_t* changed, int32_t* stack_out, nnue_stream_t stream);
+
 /* ---- the engine's tensors from a live model ------------------------------------------------------------------------
  *
  * What serialize_model followed by a load of the file leaves in device memory, formed from the model's float32 parameters in

@@ -537,6 +537,218 @@ __global__ __launch_bounds__(256) void engine_stream_update_kernel(
   engine_epilogue(net, sel, b, n_new, lds, lay, logits);
 }
 
+// What the region step reads besides the network: the uint8 frames (the fields of nnue_engine_u8_frames, layout hwc), the conv's
+// bytes, the engine's geometry of an H x W frame, and the CSR list of dirty rectangles [n_rects][4] = y0, x0, y1, x1.
+struct RegionFront {
+  const uint8_t* __restrict__ data;
+  const int64_t* __restrict__ indices;
+  int64_t count;
+  const int8_t* __restrict__ w;
+  const int32_t* __restrict__ bias;
+  const int32_t* __restrict__ rects;
+  const int32_t* __restrict__ rect_off;
+  int n_rects;
+  float mean0, mean1, mean2, inv0, inv1, inv2, scale;
+  int H, W, stride, OH, OW;
+};
+
+// LDS of the region step: update_lds, then the 768-word quantisation table (update_lds ends on an 8-byte boundary).
+__host__ __device__ inline size_t regions_lds_bytes(const EngineNet& net) { return update_lds(net).bytes + kU8Table * sizeof(int32_t); }
+
+// The conv byte of cell (oh, ow), channel c, from the frame's bytes: engine_conv_u8_kernel's arithmetic under layout hwc -- the
+// table's q, the taps in [oc][kh][kw][ic] order, zero padding outside the frame, truncating division, clamp.  No byte outside
+// the frame's 3 * H * W is read.
+__device__ __forceinline__ int32_t region_conv_byte(const RegionFront& a, const uint8_t* __restrict__ img, const int32_t* tab, int oh,
+                                                    int ow, int c) {
+  const int8_t* __restrict__ wr = a.w + c * 27;
+  int32_t acc = a.bias[c];
+#pragma unroll
+  for (int kh = 0; kh < 3; ++kh) {
+    const int ih = oh * a.stride + kh - 1;
+    if (ih < 0 || ih >= a.H) continue;
+#pragma unroll
+    for (int kw = 0; kw < 3; ++kw) {
+      const int iw = ow * a.stride + kw - 1;
+      if (iw < 0 || iw >= a.W) continue;
+      const uint8_t* __restrict__ px = img + (ih * a.W + iw) * 3;  // 3 * H * W < 2^31 (checked on the host)
+#pragma unroll
+      for (int ic = 0; ic < 3; ++ic) acc += tab[ic * 256 + px[ic]] * (int32_t)wr[(kh * 3 + kw) * 3 + ic];
+    }
+  }
+  const int32_t q = acc / (int32_t)a.scale;  // truncating division, as the engine
+  return q < -127 ? -127 : (q > 127 ? 127 : q);
+}
+
+// Cells of one axis whose three taps, at cell * stride - 1 .. + 1, meet the pixels [p0, p1) (already clipped to the frame, p0 <
+// p1): cell * stride + 1 >= p0 and cell * stride - 1 <= p1 - 1, cut to [0, n).  Exact; lo > hi = no cell (at stride >= 3 the
+// pixels between two cells' windows belong to none).
+__device__ __forceinline__ void region_cells(int p0, int p1, int stride, int n, int& lo, int& hi) {
+  lo = p0 <= 1 ? 0 : (p0 - 1 + stride - 1) / stride;
+  hi = p1 / stride;
+  if (hi > n - 1) hi = n - 1;
+}
+
+// One block of candidates of the region step, a candidate being one (cell, channel) pair, in rounds of at most kUpdateChunk.
+// full == false: the n candidates are the cells [oh_lo, ..) x [ow_lo, ow_lo + nw) times the oc channels.  full == true: they are
+// the ids [0, F) themselves, the ids behind the conv map standing for the zero bytes of the engine's zero-filled buffer.  A
+// thread forms its candidate's byte, hence the wanted bit (feature_on's rule), and where the stream's LDS word disagrees sets or
+// clears the bit with a 64-bit LDS atomic; the atomic returns the word as it was, so of all threads that name one feature the one
+// that flipped it appends the id -- ~id for a feature that went off -- to the work list.  Then all 256 threads walk the list over
+// their own columns, four rows per trip, as update_phase (counter, `done` and barriers as there).
+__device__ __forceinline__ void regions_phase(const EngineNet& net, const RegionFront& a, const uint8_t* __restrict__ img,
+                                              const int32_t* tab, bool full, int n, int oh_lo, int ow_lo, int nw,
+                                              unsigned long long* cur, int32_t* work, unsigned* work_n, unsigned& done,
+                                              int32_t (&acc)[kMaxColsPerThread]) {
+  const int tid = threadIdx.x, oc = net.oc, L1 = net.L1;
+  const int map = a.OH * a.OW * oc;  // <= F (checked on the host)
+  for (int base = 0, len; base < n; base += len) {  // n <= F, uniform over the workgroup
+    len = n - base < kUpdateChunk ? n - base : kUpdateChunk;
+    for (int i = tid; i < len; i += 256) {
+      const int idx = base + i;
+      int id, c;
+      int32_t q = 0;
+      if (full) {
+        id = idx;
+        const int pos = id / oc;
+        c = id - pos * oc;
+        if (id < map) {
+          const int oh = pos / a.OW;
+          q = region_conv_byte(a, img, tab, oh, pos - oh * a.OW, c);
+        }
+      } else {
+        const int cell = idx / oc, r = cell / nw;
+        c = idx - cell * oc;
+        const int oh = oh_lo + r, ow = ow_lo + cell - r * nw;
+        id = (oh * a.OW + ow) * oc + c;
+        q = region_conv_byte(a, img, tab, oh, ow, c);
+      }
+      const bool want = (float)(int8_t)q > net.threshold && c < 64;  // 64 channels per cell are bit-packed
+      const unsigned long long bit = 1ull << (id & 63);
+      if (((cur[id >> 6] & bit) != 0) == want) continue;
+      const unsigned long long was = want ? atomicOr(&cur[id >> 6], bit) : atomicAnd(&cur[id >> 6], ~bit);
+      if (((was & bit) != 0) != want) work[atomicAdd(work_n, 1u) - done] = want ? id : ~id;  // at most len <= kUpdateChunk appends
+    }
+    __syncthreads();
+    const int m = (int)(*work_n - done);  // unsigned: the counter may wrap, the difference does not
+    done += (unsigned)m;
+    for (int i = 0; i < m; i += 4) {
+      const int16_t* __restrict__ wr[4];
+      int32_t mul[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const bool in = i + u < m;
+        const int32_t e = in ? work[i + u] : 0;
+        wr[u] = net.ft_w + (size_t)(e < 0 ? ~e : e) * L1;
+        mul[u] = in ? (e < 0 ? -1 : 1) : 0;
+      }
+#pragma unroll
+      for (int j = 0; j < kMaxColsPerThread; ++j) {
+        const int col = tid + 256 * j;
+        if (col < L1) {
+#pragma unroll
+          for (int u = 0; u < 4; ++u) acc[j] += mul[u] * (int32_t)wr[u][col];
+        }
+      }
+    }
+    __syncthreads();  // the walk has read the list and its counter before the next round appends
+  }
+}
+
+// evaluate_incremental / update_features (nnue_engine.cpp:739-786, :818-821) for S streams whose feature lists are derived on
+// the device from the dirty rectangles of uint8 frames, one workgroup per stream, on the state of engine_stream_kernel.  Set
+// arithmetic: every feature of a cell whose 3 x 3 window meets one of the stream's rectangles (each clipped to the frame) takes
+// the value the whole-frame u8 step would give it on this frame (ConvLayer::forward, :48-158, on the bytes; feature_on's rule);
+// every other bit of the stored set keeps its value; the accumulator stays bias + sum of rows(set) mod 2^16.  Overlapping and
+// repeated rectangles recompute a cell to the same bit and flip nothing; an empty, inverted or outside rectangle selects no
+// cell.  A stream that is not valid ignores its rectangles: every id of [0, F) is a candidate, from the empty set and the bias.
+// Then the popcounts, the clipped ReLU and engine_tail, as engine_stream_update_kernel.
+// Read/write hazard on the bit words: as engine_stream_update_kernel -- the current slot is updated in place, word c belongs to
+// thread c % 256 alone at both ends, all other traffic on the words is LDS atomics and reads of bits no other thread of the
+// round names, between barriers.
+// dynamic LDS: regions_lds_bytes.
+template <class Sel>
+__global__ __launch_bounds__(256) void engine_stream_regions_kernel(EngineNet net, RegionFront a, int S, uint8_t* __restrict__ state,
+                                                                    float* __restrict__ logits, float* __restrict__ density,
+                                                                    int32_t* __restrict__ changed, Sel sel) {
+  extern __shared__ int32_t lds[];
+  const EngineLds lay = update_lds(net);
+  const int F = net.F, W64 = (F + 63) / 64;
+  int32_t* counts = lds + lay.counts;  // [wave] new, [4 + wave] difference
+  unsigned* work_n = reinterpret_cast<unsigned*>(lds + lay.work_n);
+  int32_t* work = lds + lay.work;
+  unsigned long long* cur = reinterpret_cast<unsigned long long*>(lds + lay.words);
+  int32_t* tab = reinterpret_cast<int32_t*>(cur + W64);
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+
+  const StreamView sv = stream_view(state, S, F, net.L1, b);
+  const bool was_valid = *sv.valid != 0;
+  unsigned long long* words = sv.words(*sv.parity & 1);
+
+  for (int c = tid; c < W64; c += 256) cur[c] = was_valid ? words[c] : 0ull;
+  tab[tid] = u8_quantise(tid, a.mean0, a.inv0, a.scale);
+  tab[256 + tid] = u8_quantise(tid, a.mean1, a.inv1, a.scale);
+  tab[512 + tid] = u8_quantise(tid, a.mean2, a.inv2, a.scale);
+  if (tid == 0) *work_n = 0;
+  int32_t acc[kMaxColsPerThread];
+  acc_seed(net, was_valid ? sv.accs : nullptr, acc);
+
+  int64_t idx = b;  // without indices: frame b, and count >= S (checked on the host)
+  if (a.indices) {
+    idx = a.indices[b];
+    idx = idx < 0 ? 0 : (idx >= a.count ? a.count - 1 : idx);  // as load_batch_kernel
+  }
+  const uint8_t* __restrict__ img = a.data + (size_t)idx * 3 * a.H * a.W;
+  __syncthreads();
+
+  unsigned done = 0;
+  if (!was_valid) {
+    regions_phase(net, a, img, tab, true, F, 0, 0, 1, cur, work, work_n, done, acc);
+  } else {
+    int lo, hi;
+    update_range(a.rect_off, a.n_rects, b, lo, hi);
+    for (int r = lo; r < hi; ++r) {  // uniform over the workgroup: every thread reads the same four words
+      const int32_t* __restrict__ rc = a.rects + (size_t)r * 4;
+      int y0 = rc[0], x0 = rc[1], y1 = rc[2], x1 = rc[3];
+      y0 = y0 < 0 ? 0 : y0, x0 = x0 < 0 ? 0 : x0;
+      y1 = y1 > a.H ? a.H : y1, x1 = x1 > a.W ? a.W : x1;
+      if (y0 >= y1 || x0 >= x1) continue;
+      int oh_lo, oh_hi, ow_lo, ow_hi;
+      region_cells(y0, y1, a.stride, a.OH, oh_lo, oh_hi);
+      region_cells(x0, x1, a.stride, a.OW, ow_lo, ow_hi);
+      if (oh_lo > oh_hi || ow_lo > ow_hi) continue;
+      const int nw = ow_hi - ow_lo + 1;
+      regions_phase(net, a, img, tab, false, (oh_hi - oh_lo + 1) * nw * net.oc, oh_lo, ow_lo, nw, cur, work, work_n, done, acc);
+    }
+  }
+
+  int n_new = 0, n_diff = 0;
+  for (int c = tid; c < W64; c += 256) {
+    const unsigned long long m = cur[c], o = was_valid ? words[c] : 0ull;
+    n_new += __popcll(m);
+    n_diff += __popcll(m ^ o);
+    if (!was_valid || m != o) words[c] = m;
+  }
+#pragma unroll
+  for (int sh = 32; sh >= 1; sh >>= 1) {
+    n_new += __shfl_xor(n_new, sh);
+    n_diff += __shfl_xor(n_diff, sh);
+  }
+  if (lane == 0) {
+    counts[wave] = n_new;
+    counts[4 + wave] = n_diff;
+  }
+  acc_finish<false, true>(net, acc, sv.accs, lds);
+  __syncthreads();
+  n_new = counts[0] + counts[1] + counts[2] + counts[3];
+  n_diff = counts[4] + counts[5] + counts[6] + counts[7];
+  if (tid == 0) {
+    density[b] = (float)n_new / (float)F;
+    changed[b] = was_valid ? n_diff : n_new;
+    *sv.valid = 1;
+  }
+  engine_epilogue(net, sel, b, n_new, lds, lay, logits);
+}
+
 // ---- whole batches on the int8 matrix unit --------------------------------------------------------------------------
 // The accumulate step of engine_stack_kernel as a matrix product: sums [B][L1] int32 = A [B][F] . table, with A the 0/1 byte map
 // of the active features and the int16 table as one int8 plane (every value fits a byte) or two (lo, hi: w == lo + 256 * hi
@@ -1025,6 +1237,52 @@ extern "C" int nnue_engine_stream_update(const nnue_engine_model* m, const nnue_
   engine_with_sel(st, stack_in, stack_out, [&](auto sel) {
     hipLaunchKernelGGL((engine_stream_update_kernel<decltype(sel)>), dim3(S), dim3(256), lds, s, net, added, added_off, na, removed,
                        removed_off, nr, (int)(rebuild != 0), S, static_cast<uint8_t*>(state), logits, density, changed, sel);
+  });
+  return nnue_launch_status(fn);
+}
+
+extern "C" int nnue_engine_stream_step_u8_regions(const nnue_engine_model* m, const nnue_engine_stacks* st,
+                                                  const nnue_engine_u8_frames* src, int S, int H, int W, const int32_t* rects,
+                                                  const int32_t* rect_off, int64_t n_rects, const int32_t* stack_in, void* state,
+                                                  int64_t state_bytes, float* logits, float* density, int32_t* changed,
+                                                  int32_t* stack_out, nnue_stream_t stream) {
+  const char* fn = "nnue_engine_stream_step_u8_regions";
+  if (int rc = engine_check_call(fn, m && state && logits && density && changed, st != nullptr, st, stack_out)) return rc;
+  NNUE_REQUIRE(src && src->data, NNUE_E_ARG, "%s: null pointer", fn);
+  NNUE_REQUIRE(n_rects >= 0, NNUE_E_ARG, "%s: n_rects=%lld must not be negative", fn, (long long)n_rects);
+  NNUE_REQUIRE(n_rects == 0 || (rects && rect_off), NNUE_E_ARG, "%s: a list with rectangles needs its rectangle and offset pointers", fn);
+  NNUE_REQUIRE(nnue_aligned16(state), NNUE_E_ARG, "%s: state must be 16-byte aligned", fn);
+  NNUE_REQUIRE(engine_has_tensors(m, st), NNUE_E_ARG, "%s: model tensor missing", fn);
+  NNUE_REQUIRE(S > 0, NNUE_E_ARG, "%s: S=%d must be positive", fn, S);
+  if (int rc = engine_check_model(m, st, fn)) return rc;
+  if (int rc = nnue_engine_u8_check(fn, m, src, S)) return rc;
+  NNUE_REQUIRE(src->layout == 1, NNUE_E_ARG,
+               "%s: layout %d: only hwc (1) is accepted, under chw a pixel rectangle does not map to neighbouring taps", fn, src->layout);
+  const EngineNet net = engine_net(m, st);
+  const size_t lds = regions_lds_bytes(net);
+  if (int rc = engine_check_state(fn, m, S, state_bytes, lds)) return rc;
+  ConvGeometry geo{};
+  if (int rc = engine_conv_geometry(m, H, W, fn, &geo)) return rc;
+  NNUE_REQUIRE(3ll * H * W < (1ll << 31), NNUE_E_SHAPE, "%s: a %dx%d frame holds 2^31 bytes or more", fn, H, W);
+  NNUE_REQUIRE((long long)S * H * W * 3 < (1ll << 40), NNUE_E_SHAPE, "%s: batch too large", fn);
+  RegionFront a{};
+  a.data = src->data;
+  a.indices = src->indices;
+  a.count = src->count;
+  a.w = m->conv_w;
+  a.bias = m->conv_b;
+  a.rects = rects;
+  a.rect_off = rect_off;
+  // the offsets are int32, so rectangles beyond 2^31 - 1 of a buffer are out of every range's reach
+  a.n_rects = (int)(n_rects > INT32_MAX ? INT32_MAX : n_rects);
+  a.mean0 = src->mean255[0], a.mean1 = src->mean255[1], a.mean2 = src->mean255[2];
+  a.inv0 = src->inv_std255[0], a.inv1 = src->inv_std255[1], a.inv2 = src->inv_std255[2];
+  a.scale = m->conv_scale;
+  a.H = H, a.W = W, a.stride = geo.stride, a.OH = geo.OH, a.OW = geo.OW;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  engine_with_sel(st, stack_in, stack_out, [&](auto sel) {
+    hipLaunchKernelGGL((engine_stream_regions_kernel<decltype(sel)>), dim3(S), dim3(256), lds, s, net, a, S,
+                       static_cast<uint8_t*>(state), logits, density, changed, sel);
   });
   return nnue_launch_status(fn);
 }

@@ -5,6 +5,15 @@
 #pragma once
 #include "common.h"
 
+// The 768 possible q = (int32)(x * conv_scale) of a byte in a channel, one table per workgroup: [channel][byte], int32 entries.
+// Shared by the whole-frame front and the region step of engine_kernels.hip, so that both form every entry by one expression.
+constexpr int kU8Table = 3 * 256;
+
+__device__ __forceinline__ int32_t u8_quantise(int v, float mean255, float inv_std255, float scale) {
+  const float x = ((float)v - mean255) * inv_std255;  // the float load_batch_kernel stores
+  return (int32_t)(x * scale);                        // what engine_conv_kernel makes of it
+}
+
 // How one launch splits the work: a workgroup = (image, band of `rows` output rows).
 struct EngineU8Plan {
   int rows, bands, slots, row_len, oc_log2;

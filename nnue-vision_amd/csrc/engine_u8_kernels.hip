@@ -20,7 +20,6 @@
 
 namespace {
 
-constexpr int kU8Table = 3 * 256;           // int32 entries
 constexpr int kU8LdsBudget = 24 * 1024;     // the plan's target per workgroup: six or more workgroups share a CU's 160 KB
 constexpr int kU8LdsMax = 64 * 1024;
 constexpr int kU8MinWorkgroups = 1024;      // bands are halved while a launch would have fewer (256 CUs)
@@ -36,11 +35,6 @@ struct U8Front {
   int layout, H, W, stride, OH, OW, oc, F;
   int rows, bands, row_len, oc_log2, rows_words;  // rows_words: int32 words of the staged rows, a multiple of 4
 };
-
-__device__ __forceinline__ int32_t u8_quantise(int v, float mean255, float inv_std255, float scale) {
-  const float x = ((float)v - mean255) * inv_std255;  // the float load_batch_kernel stores
-  return (int32_t)(x * scale);                        // what engine_conv_kernel makes of it
-}
 
 // Bytes [0, n) behind the global address `first`, from src (LDS, laid out so that src[first & 15] is the first byte) or zeros
 // (src == nullptr): chunks [j0, j1) of the 16-byte grid over [first - (first & 15), ...), whole chunks as one store, the

@@ -19,7 +19,9 @@ matrix unit (include/nnue_hip.h: nnue_engine_evaluate_logits_matrix) over int8 p
 ``evaluate_logits_u8(store, indices)`` and ``EngineStream.step_u8`` take uint8 ``[N,H,W,3]`` frames -- the dataset store of
 ``GpuImageDataset``, a camera's frames -- and form the conv bytes straight from them (include/nnue_hip.h:
 nnue_engine_evaluate_logits_u8): with the defaults, the bits of the float call on ``lib.load_batch`` of the same indices,
-without the float batch.
+without the float batch.  ``EngineStream.step_u8_regions(frames, rects)`` is that step from the frames' dirty rectangles: the conv re-run
+only on the grid cells a rectangle touches, the flipped table rows walked, no conv scratch (include/nnue_hip.h:
+nnue_engine_stream_step_u8_regions).
 """
 from __future__ import annotations
 
@@ -641,12 +643,44 @@ def pack_feature_lists(lists, num_streams: int) -> Tuple[torch.Tensor, torch.Ten
     return torch.from_numpy(ids.astype(np.int32, copy=False)), torch.from_numpy(offsets.astype(np.int32))
 
 
+def pack_rect_lists(lists, num_streams: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``num_streams`` per-stream lists of rectangles (each a sequence of 4 integers y0, x0, y1, x1, half-open, in frame pixels;
+    any list may be empty) as the CSR pair ``EngineStream.step_u8_regions`` takes: (rects int32 [total, 4], offsets int32
+    [num_streams + 1]) on the CPU.  Pure host work.  A coordinate outside int32 is saturated, which leaves the rectangle's
+    intersection with any frame where it was.  ValueError for another number of lists and for entries that are not 4 integers."""
+    s = int(num_streams)
+    if isinstance(lists, (torch.Tensor, np.ndarray, str, bytes)) or not hasattr(lists, "__len__"):
+        raise ValueError(f"pack_rect_lists: expected a sequence of {s} rectangle lists, got {type(lists).__name__}")
+    if len(lists) != s:
+        raise ValueError(f"pack_rect_lists: expected {s} rectangle lists (one per stream), got {len(lists)}")
+    parts = []
+    for b, rects in enumerate(lists):
+        a = rects.detach().cpu().numpy() if isinstance(rects, torch.Tensor) else np.asarray(rects)
+        if a.size == 0:
+            a = np.zeros((0, 4), dtype=np.int64)
+        elif a.dtype.kind not in "iu":
+            raise ValueError(f"pack_rect_lists: list {b} holds {a.dtype} values, expected integer coordinates")
+        if a.ndim != 2 or a.shape[1] != 4:
+            raise ValueError(f"pack_rect_lists: list {b} has shape {a.shape}, expected (n, 4): y0, x0, y1, x1 per rectangle")
+        if a.dtype == np.uint64:
+            a = np.minimum(a, np.uint64(_INT32_MAX))
+        parts.append(np.clip(a.astype(np.int64), _INT32_MIN, _INT32_MAX).astype(np.int32))
+    offsets = np.zeros(s + 1, dtype=np.int64)
+    np.cumsum([p.shape[0] for p in parts], out=offsets[1:])
+    if offsets[-1] > _INT32_MAX:
+        raise ValueError(f"pack_rect_lists: {int(offsets[-1])} rectangles are more than int32 offsets can address")
+    rects = np.concatenate(parts) if parts else np.zeros((0, 4), dtype=np.int32)
+    return torch.from_numpy(rects.astype(np.int32, copy=False)), torch.from_numpy(offsets.astype(np.int32))
+
+
 class EngineStreamSnapshot:
     """What ``EngineStream.snapshot`` returns: a device copy of the stream state (sets, accumulators, flags), the stacks of the
     last step, and the model generation the accumulators belong to."""
 
-    def __init__(self, model: "EngineModel", num_streams: int, state: torch.Tensor, stacks: torch.Tensor, generation: int):
+    def __init__(self, model: "EngineModel", num_streams: int, state: torch.Tensor, stacks: torch.Tensor, generation: int,
+                 frame_hw: Optional[Tuple[int, int]] = None):
         self.model, self.num_streams, self.state, self.stacks, self.generation = model, num_streams, state, stacks, generation
+        self.frame_hw = frame_hw
 
 
 class EngineStream:
@@ -660,6 +694,7 @@ class EngineStream:
     (NNUEEvaluator::update_features, nnue_engine.cpp:818-821), so a step costs O(changes); it mixes with the other two, keeps the
     stored sets across a ``requantize`` (it rebuilds the sums once instead of forgetting the sets), and ``refresh`` /
     ``snapshot`` / ``restore`` are the reference's refresh_accumulator and save / restore_accumulator (:792-816).
+    ``step_u8_regions(frames_u8, rects)`` derives those lists on the device from the dirty rectangles of uint8 frames.
     On a model loaded with bucket="auto" every step chooses each stream's layer stack from the step's own feature count
     (or takes ``stacks=``, as ``evaluate_logits``); ``stacks`` holds the stacks of the last step, int32 [S]."""
 
@@ -675,11 +710,14 @@ class EngineStream:
         self._valid = self.state[:4 * s].view(torch.int32)
         self.stacks = torch.zeros((s,), dtype=torch.int32, device=model.device)
         self._generation = model.generation
+        self._frame_hw: Optional[Tuple[int, int]] = None  # H x W of the last step that took frames (step, step_u8, step_u8_regions)
+        self._unit_offsets: Optional[torch.Tensor] = None  # arange(S + 1) int32, for one rectangle per stream
 
     def reset(self, streams: Optional[Iterable[int]] = None) -> None:
         """Marks all streams, or the given indices, for a refresh from the bias on the next step."""
         if streams is None:
             self._valid.fill_(0)
+            self._frame_hw = None  # no stored set is left to belong to a frame size
             return
         idx = sorted({int(i) for i in streams})
         if idx and (idx[0] < 0 or idx[-1] >= self.num_streams):
@@ -708,6 +746,8 @@ class EngineStream:
         logits, density, changed, used = m._outputs(s, changed=True)
         scratch = m._scratch_for(s) if images is not None else None
         src = images if images is not None else active
+        if images is not None:
+            self._frame_hw = (h, w)
         if u8 is not None:  # (descriptor, the uint8 frames): `images` is those frames, the state and the outputs are the same
             st, used_ptr = (None, None) if m._stacks is None else (ctypes.addressof(m._stacks), used.data_ptr())
             lib._call("nnue_engine_stream_step_u8", ctypes.addressof(m._c), st, ctypes.addressof(u8), s, h, w, lib._ptr(stacks) or None,
@@ -818,9 +858,89 @@ class EngineStream:
         (NNUEEvaluator::refresh_accumulator, nnue_engine.cpp:806-816).  A refused call resets nothing."""
         return self._update(features, None, stacks, True)
 
+    # ---- dirty rectangles of uint8 frames -------------------------------------------------------
+    def _rect_csr(self, rects) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The ``rects`` argument of ``step_u8_regions`` as (rects int32 [R, 4], offsets int32 [S + 1]) on the device."""
+        dev, s = self.model.device, self.num_streams
+        what = "rects"
+        pair = isinstance(rects, tuple) and len(rects) == 2 and all(isinstance(t, torch.Tensor) for t in rects)
+        if isinstance(rects, torch.Tensor) or pair:  # device forms: no host work, no synchronisation
+            boxes, offsets = rects if pair else (rects, None)
+            if boxes.dtype != torch.int32:
+                raise ValueError(f"{what}: rectangles must be int32, got {boxes.dtype}")
+            if not self.model._on_device(boxes):
+                raise ValueError(f"{what}: tensor is on {boxes.device}, the stream's state on {dev} (no CPU fallback in this build)")
+            if boxes.dim() != 2 or boxes.shape[1] != 4 or boxes.shape[0] > _INT32_MAX:
+                raise ValueError(f"{what}: expected shape (R, 4) -- y0, x0, y1, x1 per rectangle -- got {tuple(boxes.shape)}")
+            if offsets is None:
+                if boxes.shape[0] != s:
+                    raise ValueError(f"{what}: a single tensor holds one rectangle per stream, expected shape ({s}, 4), got "
+                                     f"{tuple(boxes.shape)}; pass (rects, offsets) for another count")
+                if self._unit_offsets is None:
+                    self._unit_offsets = torch.arange(s + 1, dtype=torch.int32, device=dev)
+                offsets = self._unit_offsets
+            else:
+                if offsets.dtype not in (torch.int32, torch.int64):
+                    raise ValueError(f"{what}: offsets must be int32 or int64, got {offsets.dtype}")
+                if not self.model._on_device(offsets):
+                    raise ValueError(f"{what}: offsets are on {offsets.device}, the stream's state on {dev}")
+                if tuple(offsets.shape) != (s + 1,):
+                    raise ValueError(f"{what}: offsets must have shape ({s + 1},), got {tuple(offsets.shape)}")
+                if offsets.dtype == torch.int64:  # saturating keeps every clip to [0, R] where it was
+                    offsets = offsets.clamp(_INT32_MIN, _INT32_MAX).to(torch.int32)
+            return boxes.contiguous(), offsets.contiguous()
+        boxes, offsets = pack_rect_lists(rects, s)
+        packed = torch.cat((offsets, boxes.reshape(-1))).to(dev)  # one copy
+        return packed[s + 1:].view(-1, 4), packed[:s + 1]
+
+    def step_u8_regions(self, frames_u8: torch.Tensor, rects, indices: Optional[torch.Tensor] = None, mean=None, std=None,
+                        stacks: Optional[torch.Tensor] = None, layout: str = "hwc"
+                        ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """``step_u8(layout="hwc")`` from the dirty rectangles of the frames: the conv is re-run only on the grid cells whose
+        3 x 3 window touches a rectangle and only the table rows that flipped are walked -- O(touched cells + flips) per stream,
+        no conv scratch (include/nnue_hip.h: nnue_engine_stream_step_u8_regions has the definition as set arithmetic).
+        ``frames_u8`` and ``indices`` as ``step_u8``.  ``rects``: rectangles y0, x0, y1, x1, half-open, in frame pixels, as an
+        int32 device tensor [S, 4] (one per stream), a tuple ``(rects int32 [R, 4], offsets int32 or int64 [S + 1])`` of device
+        tensors (stream s owns rects[offsets[s]:offsets[s + 1]]) -- both without host work, fit for a stream capture -- or a
+        sequence of S per-stream sequences of 4-tuples, packed on the host (``pack_rect_lists``) and copied once.
+        If the frames differ from those behind the stored sets only inside the rectangles, the result is bit-identical to
+        ``step_u8(frames_u8, indices, layout="hwc")``; otherwise only the touched cells' features are replaced.  Overlapping,
+        repeated, empty, inverted and outside rectangles are harmless; a stream without rectangles returns its previous logits
+        and changed == 0; a stream that is not valid (new, ``reset``, or after ``requantize``) is evaluated over its whole frame.
+        Only layout="hwc" exists: under "chw" a pixel rectangle does not map to neighbouring taps.  ValueError for that, for a
+        wrong dtype or shape of ``rects``, and for an H x W other than that of the stream's last step that took frames
+        (``reset()`` of all streams, or a whole-frame step, changes the size)."""
+        if layout != "hwc":
+            raise ValueError(f"step_u8_regions: layout must be \"hwc\", got {layout!r} (under \"chw\" a pixel rectangle does not "
+                             "map to neighbouring taps)")
+        m, s = self.model, self.num_streams
+        src, keep, _, h, w = m._u8_frames(frames_u8, indices, layout, mean, std, "frames_u8", count=s)
+        boxes, offsets = self._rect_csr(rects)
+        stale = self._generation != m.generation  # the model was requantised: sets and sums belong to the old tensors
+        if not stale and self._frame_hw is not None and self._frame_hw != (h, w):
+            raise ValueError(f"step_u8_regions: frames are {h}x{w}, the stream's last frame step was {self._frame_hw[0]}x"
+                             f"{self._frame_hw[1]}: the stored sets belong to another grid (reset() all streams, or take a "
+                             "whole-frame step)")
+        if stale:
+            self._valid.fill_(0)
+            self._generation = m.generation
+        stacks = m._stack_arg(stacks, s, "EngineStream")
+        logits, density, changed, used = m._outputs(s, changed=True)
+        st, used_ptr = (None, None) if m._stacks is None else (ctypes.addressof(m._stacks), used.data_ptr())
+        lib._call("nnue_engine_stream_step_u8_regions", ctypes.addressof(m._c), st, ctypes.addressof(src), s, h, w,
+                  lib._ptr(boxes) or None, lib._ptr(offsets) or None, int(boxes.shape[0]), lib._ptr(stacks) or None,
+                  self.state.data_ptr(), self.state.numel(), logits.data_ptr(), density.data_ptr(), changed.data_ptr(), used_ptr,
+                  lib._stream(keep[0]))
+        del keep
+        self._frame_hw = (h, w)
+        if m._stacks is not None:
+            self.stacks = used
+        return logits, density, changed
+
     def snapshot(self) -> EngineStreamSnapshot:
         """A point to come back to (save_accumulator, nnue_engine.cpp:792-797, for the whole stream state: sets included)."""
-        return EngineStreamSnapshot(self.model, self.num_streams, self.state.clone(), self.stacks.clone(), self._generation)
+        return EngineStreamSnapshot(self.model, self.num_streams, self.state.clone(), self.stacks.clone(), self._generation,
+                                    self._frame_hw)
 
     def restore(self, snap: EngineStreamSnapshot) -> None:
         """Takes every stream back to ``snap`` (restore_accumulator, nnue_engine.cpp:799-804) with one device copy and no
@@ -833,3 +953,4 @@ class EngineStream:
         self.state.copy_(snap.state)
         self.stacks = snap.stacks.clone()
         self._generation = snap.generation
+        self._frame_hw = snap.frame_hw

@@ -165,6 +165,8 @@ SIGNATURES = {
                                                        _c_p, _c_i64, _c_p]),
     "nnue_engine_stream_step_u8": (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p,
                                             _c_i64, _c_p]),
+    "nnue_engine_stream_step_u8_regions": (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_i64,
+                                                    _c_p, _c_p, _c_p, _c_p, _c_p]),
     "nnue_engine_quantize_model": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_int,
                                             _c_int, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p, _c_p]),
     "nnue_sgd_scratch": (_c_i64, [_c_i64]),
