@@ -116,13 +116,12 @@ struct BwwEpi {  // d_weight rows with a position of their own
 // The weight gradient consumed where it is produced: clip_grad_norm_ + SGD(momentum, weight decay) (train.py:363-366,
 // :457-464) applied to the table rows in place, element by element exactly as sgd_apply_kernel does -- d_weight is never
 // written (268 MB written and read back per step at the 224x224 configuration).  The clip coefficient comes from the
-// device scalar the optimizer's norm pass left (its table part formed without the gradient: nnue_ftm_gram_sqnorm).
+// device scalar the optimizer's norm pass left (its table part formed without the gradient: nnue_ftm_gram_sqnorm).  Only the
+// bf16-split tiles take it (rmw_tile).
 struct BwwSgdEpi {
   static constexpr bool kAU8 = true;
   static constexpr bool kFusedL1 = false;
-  static constexpr bool kBPair = false;
-  static constexpr bool kSq = false;
-  static constexpr bool kRmw = true;  // read-modify-write epilogue: goes through LDS so that rows are touched as whole 16-byte runs
+  static constexpr bool kRmw = true;  // read-modify-write epilogue: goes through LDS so that rows are touched as whole 16-byte runs (rmw_tile)
   float* __restrict__ weight;    // table rows [0, direct), updated in place
   float* __restrict__ momentum;  // matching momentum rows or NULL
   const float* __restrict__ coef;  // clip coefficient (device scalar)
@@ -131,17 +130,6 @@ struct BwwSgdEpi {
   int first_step;
   int xcd_remap;  // 1: workgroups that share an XCD (equal blockIdx % 8) take consecutive tiles
   const float* __restrict__ lr_dev;  // when non-NULL the learning rate is read from this device float (a scheduler's hook: no re-capture)
-  __device__ __forceinline__ float2 col(int) const { return make_float2(coef[0] * scale, 0.f); }
-  __device__ __forceinline__ float pre(int m, int n) const { return weight[(size_t)m * L1 + n]; }
-  __device__ __forceinline__ void store(int m, int n, float v, float2 c, float w, int) const {
-    const size_t i = (size_t)m * L1 + n;
-    float gi = fmaf(wd, w, v * c.x);
-    if (momentum) {
-      gi = first_step ? gi : fmaf(mom, momentum[i], gi);
-      momentum[i] = gi;
-    }
-    weight[i] = w - (lr_dev ? lr_dev[0] : lr) * gi;
-  }
 };
 
 // The same for the reference's other optimizer: clip_grad_norm_ + torch.optim.Adam (train.py:363-366, :465-470) applied to
@@ -2113,56 +2101,82 @@ int env_int(const char* name, int fallback) {
   return v && *v ? std::atoi(v) : fallback;
 }
 
+// Every environment variable this file reads (developer knobs; DESIGN.md §8 lists the same names).
+namespace knob {
+// read per call: tests switch these inside one process
+bool bf16() { return env_int("NNUE_FTM_BF16", 1) != 0; }  // 0: every product on the f32 MFMA
+int bf_bm() { return env_int("NNUE_FTM_BF_BM", 0); }      // 32 / 64 / 128 forces the bf16 tile height of plan()
+int bf_wm() { return env_int("NNUE_FTM_BF_WM", 64); }     // 32: 32-row bf16 weight tiles in the merged backward
+bool val_planes() { return env_int("NNUE_FTM_VAL_PLANES", 1) != 0; }  // 0: the merged backward's value tiles never read planes
+int val_planes_min_tiles() { return env_int("NNUE_FTM_VAL_PLANES_MIN_TILES", 256); }  // (tests reach the kernel at small shapes with 1)
+int fwd_planes_min_wg() { return env_int("NNUE_FTM_FWD_PLANES_MIN_WG", 256); }        // (likewise, the planes-fed forward)
+bool fwd_stream() { return env_int("NNUE_FTM_FWD_STREAM", 1) != 0; }  // 0: the LDS-staged planes-fed forward
+int uf_abl() { return env_int("NNUE_FTM_UF_ABL", 0); }                // timing-only ablation of the fused update + forward
+// read once per process
+bool split_backward() { static const int v = env_int("NNUE_FTM_SPLIT_BACKWARD", 0); return v != 0; }  // never the merged backward
+bool ride_ste_v64() { static const int v = env_int("NNUE_FTM_RIDE_STE_V64", 0); return v != 0; }  // the STE also rides in 64 x 64 value tiles
+#ifdef NNUE_ABLATIONS  // timing-only ablations (WRONG results), tools/debug: compiled only with NNUE_BUILD_ABLATIONS=1 (csrc/build.py)
+int bf6_abl() { static const int v = env_int("NNUE_FTM_BF6_ABL", 0); return v; }
+#endif
+}  // namespace knob
+
 // Tile shapes (BM, BN, BK).  BK grows as the tile shrinks so that a K tile always carries >= 2048 MFMA cycles/wave.
+enum Tile { kF32Flat, kF32Square, kF32Tall, kF32Wide, kBf32, kBf64, kBf128, kTileCount };
+constexpr int kTileDims[kTileCount][3] = {{32, 64, 128}, {64, 64, 64}, {128, 64, 32}, {64, 128, 32},  // f32 MFMA
+                                          {32, 64, 128}, {64, 64, 128}, {128, 64, 128}};              // bf16-split tiles (gemm_tile_bf)
 struct Shape {
-  int cfg;  // row of kCfg: 0-5 the f32 tiles, 6-8 the bf16-split tiles of 32 / 64 / 128 rows
+  Tile tile;
+  bool bf;  // a bf16-split tile
   int bm, bn, bk, tiles_m, tiles_n, ksplit, klen;
 };
-constexpr int kCfg[9][3] = {{32, 64, 128}, {64, 64, 64}, {128, 64, 32}, {64, 128, 32}, {128, 64, 64}, {64, 128, 64},
-                            {32, 64, 128}, {64, 64, 128}, {128, 64, 128}};  // 6..8: bf16-split tiles (gemm_tile_bf)
+// `tile` over an M x N x K product in one K slab
+Shape shape_of(Tile tile, int M, int N, int K) {
+  Shape s;
+  s.tile = tile;
+  s.bf = tile >= kBf32;
+  s.bm = kTileDims[tile][0]; s.bn = kTileDims[tile][1]; s.bk = kTileDims[tile][2];
+  s.tiles_m = (M + s.bm - 1) / s.bm;
+  s.tiles_n = (N + s.bn - 1) / s.bn;
+  s.ksplit = 1;
+  s.klen = (K + s.bk - 1) / s.bk * s.bk;
+  return s;
+}
 
 // The two products over the binary map run on the bf16 matrix unit (exact three-way split of the f32 operand) unless
-// NNUE_FTM_BF16=0; NNUE_FTM_BF_BM forces the bf16 tile height (developer knob).
-bool use_bf16() { return env_int("NNUE_FTM_BF16", 1) != 0; }  // read per call: tests switch it inside one process
-
+// NNUE_FTM_BF16=0; NNUE_FTM_BF_BM forces the bf16 tile height.
+//
 // prefer_m: the operand re-read per M tile is the big one (the table, in forward and value gradient), so take tall
 // tiles; otherwise (weight gradient: the map is re-read per N tile) take wide ones.  The largest preferred shape
 // that still gives every CU a workgroup wins; the forward of a small batch (M <= 128: one tall tile covers it, the
 // table is then read exactly once) splits K until there are about two workgroups per CU.
 Shape plan(int M, int N, int K, bool prefer_m, bool allow_split, bool bf_ok = false) {
-  static const int force_cfg = env_int("NNUE_FTM_CFG", -1), force_split = env_int("NNUE_FTM_KSPLIT", 0);
-  const int force_bf_bm = env_int("NNUE_FTM_BF_BM", 0);
-  const int order_m[3] = {2, 1, 0}, order_n[3] = {3, 1, 0};
-  const int* order = prefer_m ? order_m : order_n;
-  auto tiles = [&](int c) { return (long long)((M + kCfg[c][0] - 1) / kCfg[c][0]) * ((N + kCfg[c][1] - 1) / kCfg[c][1]); };
-  int cfg = order[2];
+  const Tile order_m[3] = {kF32Tall, kF32Square, kF32Flat}, order_n[3] = {kF32Wide, kF32Square, kF32Flat};
+  const Tile* order = prefer_m ? order_m : order_n;
+  auto tiles = [&](Tile c) { return (long long)((M + kTileDims[c][0] - 1) / kTileDims[c][0]) * ((N + kTileDims[c][1] - 1) / kTileDims[c][1]); };
+  Tile tile = order[2];
   for (int i = 0; i < 3; ++i)
-    if (tiles(order[i]) >= 256) { cfg = order[i]; break; }
+    if (tiles(order[i]) >= 256) { tile = order[i]; break; }
   const bool small_m = allow_split && M <= 128;
-  if (small_m) cfg = 2;
-  if (force_cfg >= 0 && force_cfg < 6) cfg = force_cfg;
-  if (bf_ok && use_bf16()) {
+  if (small_m) tile = kF32Tall;
+  if (bf_ok && knob::bf16()) {
     // The split of the f32 operand (5.5 VALU per value) is amortised over the tile's rows, so only tall tiles pay:
     // 128 or 64 rows where they still fill the chip, the split-K forward of a small batch (128 rows).  Launch-sized
     // products that would need 32-row tiles stay on the f32 MFMA (measured at the CIFAR batch-512 shape: forward 21.8 us
     // with 32-row bf16 tiles, 25.7 with 64-row ones that leave half the CUs idle, 20.3 with the f32 kernel).
-    for (int c = 8; c >= 7; --c)
-      if (tiles(c) >= 256) { cfg = c; break; }
+    for (Tile c : {kBf128, kBf64})
+      if (tiles(c) >= 256) { tile = c; break; }
     // split-K forward of a small batch: only where K still gives the 128-deep bf16 tiles many slabs (the 65 536-row table);
     // at K = 799 the f32 tiles (K tile 32: six slabs) fill more of the chip than one workgroup walking seven bf16 K tiles
-    if (small_m) cfg = (K >= 4096) ? 8 : 2;
-    if (force_bf_bm == 32 || force_bf_bm == 64 || force_bf_bm == 128) cfg = force_bf_bm == 32 ? 6 : force_bf_bm == 64 ? 7 : 8;
+    if (small_m) tile = (K >= 4096) ? kBf128 : kF32Tall;
+    const int force_bm = knob::bf_bm();
+    if (force_bm == 32 || force_bm == 64 || force_bm == 128) tile = force_bm == 32 ? kBf32 : force_bm == 64 ? kBf64 : kBf128;
   }
-  Shape s;
-  s.cfg = cfg;
-  s.bm = kCfg[cfg][0]; s.bn = kCfg[cfg][1]; s.bk = kCfg[cfg][2];
-  s.tiles_m = (M + s.bm - 1) / s.bm;
-  s.tiles_n = (N + s.bn - 1) / s.bn;
+  Shape s = shape_of(tile, M, N, K);
   const long long blocks = (long long)s.tiles_m * s.tiles_n;
   const int ktiles = (K + s.bk - 1) / s.bk;
   int split = 1;
-  if (allow_split && (small_m || force_split)) {
-    split = force_split ? force_split : (int)((512 + blocks - 1) / blocks);
+  if (small_m) {
+    split = (int)((512 + blocks - 1) / blocks);
     if (split > ktiles / 4) split = ktiles / 4;  // at least four K tiles per slab
     if (split > 64) split = 64;
     if (split < 1) split = 1;
@@ -2173,39 +2187,44 @@ Shape plan(int M, int N, int K, bool prefer_m, bool allow_split, bool bf_ok = fa
   return s;
 }
 
+// One product by the kernel of its Shape.  Only what an epilogue's callers can plan is instantiated: the in-place update
+// epilogues (update_product_shape) never see an f32 tile, and their 128-row tiles are always the 64-deep ones.
 template <bool AKC, bool BKC, class Epi>
 void launch(hipStream_t st, const Shape& s, Mat ma, Mat mb, Epi epi, int M, int N, int K, GroupArgs ga = GroupArgs{}) {
   const dim3 grid((unsigned)(s.tiles_m * s.tiles_n) + (ga.n ? 1u : 0u), (unsigned)s.ksplit);
-  if (s.cfg < 6) {
-    if constexpr (!is_adam<Epi>::value) {  // (the f32 tiles have no Adam epilogue: rmw_tile_adam is the bf16-split tiles')
 #define NNUE_FTM_LAUNCH(BM, BN, BK) \
   hipLaunchKernelGGL((ftm_gemm_kernel<BM, BN, BK, AKC, BKC, Epi>), grid, dim3(256), 0, st, ma, mb, epi, M, N, K, s.klen, s.tiles_n, ga)
-      switch (s.cfg) {
-        case 0: NNUE_FTM_LAUNCH(32, 64, 128); break;
-        case 1: NNUE_FTM_LAUNCH(64, 64, 64); break;
-        case 2: NNUE_FTM_LAUNCH(128, 64, 32); break;
-        case 3: NNUE_FTM_LAUNCH(64, 128, 32); break;
-        case 4: NNUE_FTM_LAUNCH(128, 64, 64); break;
-        default: NNUE_FTM_LAUNCH(64, 128, 64); break;
-      }
-#undef NNUE_FTM_LAUNCH
-    }
-    return;
-  }
-  if constexpr (!BKC && Epi::kAU8) {  // bf16-split tiles: the map times an f32 operand that is contiguous along its rows
 #define NNUE_FTM_LAUNCH_BF(BM) \
   hipLaunchKernelGGL((ftm_gemm_bf_kernel<BM, 64, AKC, Epi>), grid, dim3(256), 0, st, ma, mb, epi, M, N, K, s.klen, s.tiles_n, ga)
-    // 128-row tiles of the big-table kernels (split-K forward, update in the epilogue) with K tiles of 64: 40 KB and
-    // 124 / 152 registers instead of 80 KB and ~190 / 200 -- four / three workgroups per CU instead of two: forward 67.5 -> 64 us,
-    // update 192.5 -> 184 us at the 224x224 shape (A/B in one run)
-    static const int kt64 = env_int("NNUE_FTM_BF_KT64", 1);  // developer knob
-    if (s.cfg == 6) NNUE_FTM_LAUNCH_BF(32);
-    else if (s.cfg == 7) NNUE_FTM_LAUNCH_BF(64);
-    else if (kt64 && !ga.n && (std::is_same<Epi, FwdEpi>::value || is_rmw<Epi>::value))
-      hipLaunchKernelGGL((ftm_gemm_bf64_kernel<AKC, Epi>), grid, dim3(256), 0, st, ma, mb, epi, M, N, K, s.klen, s.tiles_n);
-    else NNUE_FTM_LAUNCH_BF(128);
-#undef NNUE_FTM_LAUNCH_BF
+  // 128-row tiles of the big-table kernels (split-K forward, update in the epilogue) with K tiles of 64: 40 KB and
+  // 124 / 152 registers instead of 80 KB and ~190 / 200 -- four / three workgroups per CU instead of two: forward 67.5 -> 64 us,
+  // update 192.5 -> 184 us at the 224x224 shape (A/B in one run)
+#define NNUE_FTM_LAUNCH_BF64() \
+  hipLaunchKernelGGL((ftm_gemm_bf64_kernel<AKC, Epi>), grid, dim3(256), 0, st, ma, mb, epi, M, N, K, s.klen, s.tiles_n)
+  if constexpr (!is_rmw<Epi>::value) {
+    switch (s.tile) {
+      case kF32Flat: NNUE_FTM_LAUNCH(32, 64, 128); return;
+      case kF32Square: NNUE_FTM_LAUNCH(64, 64, 64); return;
+      case kF32Tall: NNUE_FTM_LAUNCH(128, 64, 32); return;
+      case kF32Wide: NNUE_FTM_LAUNCH(64, 128, 32); return;
+      default: break;
+    }
   }
+  if constexpr (!BKC && Epi::kAU8) {  // bf16-split tiles: the map times an f32 operand that is contiguous along its rows
+    switch (s.tile) {
+      case kBf32: NNUE_FTM_LAUNCH_BF(32); return;
+      case kBf64: NNUE_FTM_LAUNCH_BF(64); return;
+      case kBf128:
+        if constexpr (is_rmw<Epi>::value) NNUE_FTM_LAUNCH_BF64();  // (no grouping rider beside an update)
+        else if constexpr (std::is_same<Epi, FwdEpi>::value) { if (ga.n) NNUE_FTM_LAUNCH_BF(128); else NNUE_FTM_LAUNCH_BF64(); }
+        else NNUE_FTM_LAUNCH_BF(128);
+        return;
+      default: break;
+    }
+  }
+#undef NNUE_FTM_LAUNCH_BF64
+#undef NNUE_FTM_LAUNCH_BF
+#undef NNUE_FTM_LAUNCH
 }
 
 // every operand is addressed with 32-bit byte offsets (tile overhang included)
@@ -2334,9 +2353,7 @@ int backward_weight_impl(const uint8_t* bits, const float* sink, const float* d_
 namespace {
 // the stand-alone value gradient as six bf16 plane products (gemm_tile_bf6): the big-map shape's 128 x 64 tiles
 bool values_bf6(int B, int P, int L1) {
-  static const int bf6 = env_int("NNUE_FTM_VAL_BF6", 1);  // developer knob
-  const Shape s = plan(B, P, L1, true, false);
-  return bf6 && use_bf16() && s.cfg == 2 && s.ksplit == 1 && L1 % 8 == 0;
+  return knob::bf16() && plan(B, P, L1, true, false).tile == kF32Tall && L1 % 8 == 0;
 }
 }  // namespace
 
@@ -2362,8 +2379,8 @@ extern "C" int nnue_ftm_backward_values(const uint8_t* bits, const float* d_out,
     // K tiles of 32: six images of a 128 x 64 tile are 36 KB and 120 registers -- four workgroups per CU -- 100 us against
     // 115 us with K tiles of 64 (72 KB, two per CU) and 147 us on the f32 MFMA at the 224x224 shape
     const dim3 grid((unsigned)(s.tiles_m * s.tiles_n));
-#ifdef NNUE_ABLATIONS  // timing-only ablations (WRONG results), tools/debug: compiled only with NNUE_BUILD_ABLATIONS=1 (csrc/build.py)
-    static const int abl = env_int("NNUE_FTM_BF6_ABL", 0);
+#ifdef NNUE_ABLATIONS
+    const int abl = knob::bf6_abl();
 #define NNUE_ABL(N) if (abl == N) { hipLaunchKernelGGL((ftm_gemm_bf6_kernel<128, 64, ValEpi, 32, N>), grid, dim3(256), 0, st, ma, mb, epi, B, P, L1, s.tiles_n); return nnue_launch_status("nnue_ftm_backward_values"); }
     NNUE_ABL(1) NNUE_ABL(2) NNUE_ABL(3) NNUE_ABL(4) NNUE_ABL(5)
 #undef NNUE_ABL
@@ -2387,42 +2404,6 @@ extern "C" int nnue_ftm_backward_values_ws(const uint8_t* bits, const float* d_o
 // Both gradients of the binary-map FeatureTransformer in one launch (see ftm_backward_kernel); falls back to the two
 // separate launches for tile-shape pairs that are not instantiated.
 namespace {
-// the shape pair the merged launch is used for (also the condition for the d_w1 tile family to ride along)
-// weight-gradient tile height of the merged launch when it runs on the bf16 matrix unit (0: f32 tiles)
-int merged_bf_wm() {
-  const int wm = env_int("NNUE_FTM_BF_WM", 64);
-  return use_bf16() ? (wm == 32 ? 32 : 64) : 0;
-}
-
-bool merged_backward_shape(int B, int F, int P, int L1, bool* big) {
-  const int direct = (F - 1 < P) ? F - 1 : P;
-  if (direct <= 0) return false;
-  static const int split_launch = env_int("NNUE_FTM_SPLIT_BACKWARD", 0);
-  static const int force_pair = env_int("NNUE_FTM_BWD_PAIR", 0);  // developer knob: 11 forces 64x64x64, 1 forbids it
-  const Shape sw = plan(direct, L1, B, false, false), sv = plan(B, P, L1, true, false);
-  const long long tiles64 = (long long)((direct + 63) / 64) * ((L1 + 63) / 64) + (long long)((B + 63) / 64) * ((P + 63) / 64);
-  const bool small_pair = sw.cfg == 0 && (sv.cfg == 0 || sv.cfg == 1);
-  *big = force_pair == 11 || (force_pair != 1 && small_pair && tiles64 >= 448);
-  return !split_launch && (small_pair || *big);
-}
-// value tiles of the merged launch as six bf16 plane products: for the 64 x 64 tiles (C3 shapes: 43.5 vs 46.0 us for the
-// launch); the 32 x 64 tiles of the batch-512 shape are latency-bound per K tile and lose with the 64-deep bf16 tiles (27.2 vs 26.3 us)
-// -- they take the six plane products only with the table split once per step and streamed from the value planes (val_planes_tiles)
-// weight tiles with K tiles of 64 (gemm_tile_bf64) in the merged launch
-bool merged_w64() {
-  static const int w64 = env_int("NNUE_FTM_BWD_W64", 1);  // developer knob
-  return w64 != 0;
-}
-bool merged_values_bf6(int B, int F, int P, int L1) {
-  static const int bf6 = env_int("NNUE_FTM_BWD_BF6", 1);  // developer knob
-  bool big = false;
-  if (!merged_backward_shape(B, F, P, L1, &big) || !merged_bf_wm()) return false;
-  const bool v_small = !big && plan(B, P, L1, true, false).cfg == 0;
-  return bf6 && !v_small && L1 % 8 == 0;
-}
-}  // namespace
-
-namespace {
 struct SteArgs {  // the STE stage 1 riding in the value tiles (nnue_ftm_backward's ste_* arguments)
   const float* img;
   const float* patches;
@@ -2437,46 +2418,115 @@ struct ValPlanes {  // nnue_ftm_backward_planes: the plane buffer nnue_ftm_conv_
   int64_t bytes;
 };
 
-// Value tiles of the merged launch when they carry the STE partials (= the partials' run length), 0 where the shape is not taken:
-// 8 channels (fps * G == P with G the grid of an H x W image at `stride`), the merged launch with its default bf16 weight tiles
-// and 32 x 64 value tiles (the batch-512 CIFAR shape: 0.0830 -> 0.0801 ms per step).  The 64 x 64 bf16-plane value tiles of the
-// batch-1024 shapes also take the epilogue (ftm_backward_bf_kernel<.., ValSteEpi>) but lose there -- C3 0.1266 -> 0.1312 ms:
-// their 64 pixel registers are requested after the K loop -- so they keep the STE launch.
-int64_t ste_ride_tiles(int B, int F, int P, int L1, int H, int W, int stride) {
-  if (!nnue_ftm_supported(F, P, L1) || !shape_ok(B, F, P, L1) || H <= 0 || W <= 0 || stride <= 0) return 0;
-  const long long Gh = (H - 1) / stride + 1, Gw = (W - 1) / stride + 1;
-  if (8 * Gh * Gw != P || (long long)B * 3 * H * W >= (1ll << 40)) return 0;
-  bool big = false;
-  if (!merged_backward_shape(B, F, P, L1, &big) || merged_bf_wm() != 64 || !merged_w64()) return 0;
-  static const int wide = env_int("NNUE_FTM_RIDE_STE_V64", 0);  // developer knob: 1 also rides in the 64 x 64 value tiles
-  const int vm = (!big && plan(B, P, L1, true, false).cfg == 0) ? 32 : 64;
-  if (vm != 32 && !wide) return 0;
-  return (int64_t)((B + vm - 1) / vm) * ((Gh * Gw + 7) / 8);
-}
-}  // namespace
+// The kernels of the merged launch, named <weight tile>_<value tile>: F32 a x b are ftm_backward_kernel's f32 tiles of a / b
+// rows; Bf32 / Bf64 are ftm_backward_bf_kernel's bf16 weight tiles of 32 rows (K tiles of 128) / 64 rows (K tiles of 64) beside
+// value tiles V32 (32 x 64 x 128, f32), V64 (64 x 64 x 64, f32) or V64x6 (64 x 64 x 64, six bf16 plane products); ...Ste: the value
+// tiles leave the STE partials (ValSteEpi), ...StePlanes: and read the table's value planes (ValStePlanesEpi).
+enum class BwdKernel {
+  kNone,  // the two stand-alone launches
+  kF32_32x32, kF32_32x64, kF32_64x64,
+  kBf32_V32, kBf32_V64, kBf32_V64x6,
+  kBf64_V32, kBf64_V64, kBf64_V64x6,
+  kBf64_V32Ste, kBf64_V32StePlanes, kBf64_V64Ste, kBf64_V64x6Ste,
+};
 
-namespace {
-// Value tiles of the merged launch that read the table's value planes (value_planes.h; gemm_tile_val_planes), 0 where the shape
-// is not taken: the STE ride's shape on 32-row value tiles (ste_ride_tiles' conditions, restated on P alone for
-// nnue_ftm_uses_bf16, which knows no image size), L1 a multiple of the planes' 8-j chunk, and at least one value tile per CU --
-// the shape the planes were measured at; below it the tiles of a launch do not queue behind each other's matrix time and keep
-// the f32 tiles.  NNUE_FTM_VAL_PLANES=0 (today's f32 tiles) and NNUE_FTM_VAL_PLANES_MIN_TILES (the floor; tests reach the
-// kernel at small shapes with 1) are developer knobs read per call.
-int64_t val_planes_tiles(int B, int F, int P, int L1) {
-  if (env_int("NNUE_FTM_VAL_PLANES", 1) == 0) return 0;
-  if (!nnue_ftm_supported(F, P, L1) || !shape_ok(B, F, P, L1) || P % 8 != 0 || L1 % 8 != 0) return 0;
-  bool big = false;
-  if (!merged_backward_shape(B, F, P, L1, &big) || merged_bf_wm() != 64 || !merged_w64()) return 0;
-  if (big || plan(B, P, L1, true, false).cfg != 0) return 0;  // 64-row value tiles
-  const int64_t tiles = (int64_t)((B + 31) / 32) * ((P / 8 + 7) / 8);
-  if (tiles < env_int("NNUE_FTM_VAL_PLANES_MIN_TILES", 256)) return 0;
-  return (int64_t)((P / 8 + 7) / 8) * ((L1 + kBfK - 1) / kBfK) * kValPlaneBlock < (1ll << 31) ? tiles : 0;
+// Everything the shape and the knobs decide about nnue_ftm_backward: the host queries and the dispatch only read it.
+struct MergedBackward {
+  bool taken;  // one merged launch (also the condition for the d_w1 tile family to ride along); else all below but sq_count is 0
+  bool big;    // 64 x 64 x 64 tiles for both products
+  // weight-gradient tiles, w_bm x 64: bf16-split of height w_bf (K tiles of w_bk) or, w_bf == 0, the f32 tile w_bm x 64 x w_bk
+  int w_bf, w_bm, w_bk, w_tiles_n, n_w;
+  // value-gradient tiles, v_bm x 64 (32 x 64 x 128 or 64 x 64 x 64); v6: as six bf16 plane products
+  int v_bm, v_tiles_n, n_v;
+  bool v6;
+  // Value tiles when they carry the STE partials (= the partials' run length; they replace n_v), 0 where the image's grid is not
+  // the map's or the variant has no STE form
+  int64_t ste_tiles;
+  // Value tiles that read the table's value planes (value_planes.h; gemm_tile_val_planes) on P alone, for nnue_ftm_uses_bf16,
+  // which knows no image size; the planes are fed where the STE rides on as many tiles (val_planes)
+  int64_t val_planes_tiles;
+  bool val_planes;
+  // Squared-norm partials the launch leaves (one per weight-gradient tile); not taken: the stand-alone weight gradient's, 0 when
+  // that product is split along K (never for this operand order today)
+  int64_t sq_count;
+  BwdKernel kernel, ste_kernel;  // without / with the STE partials (kNone where ste_tiles == 0)
+};
+
+MergedBackward merged_backward_plan(int B, int F, int P, int L1, int H = 0, int W = 0, int stride = 0) {
+  MergedBackward m{};
+  if (!nnue_ftm_supported(F, P, L1) || !shape_ok(B, F, P, L1)) return m;
+  const int direct = (F - 1 < P) ? F - 1 : P;
+  if (direct <= 0) return m;
+  // measured: one launch wins where the products are launch-sized (C2 -10 %, C3 -8 % of the two launches) and loses
+  // 7 % at the 224x224 shapes, where each product fills the chip by itself and the two tile shapes fight over L2.
+  const Shape sw = plan(direct, L1, B, false, false), sv = plan(B, P, L1, true, false);
+  m.taken = !knob::split_backward() && sw.tile == kF32Flat && (sv.tile == kF32Flat || sv.tile == kF32Square);
+  if (!m.taken) {
+    const Shape s = plan(direct, L1, B, false, false, true);
+    m.sq_count = s.ksplit == 1 ? (int64_t)s.tiles_m * s.tiles_n : 0;
+    return m;
+  }
+  // Tile shapes for the shared launch: the products sit near the L2 -> LDS fill rate at these sizes (32x64 tiles: 10.7
+  // flop per staged byte), so 64x64x64 tiles (16 flop/B) are taken for both as soon as the two products together still
+  // give ~1.75 workgroups per CU (C3: 45.5 vs 49.3 us); below that the small tiles win (C2: 28 vs 37 us).
+  const long long tiles64 = (long long)((direct + 63) / 64) * ((L1 + 63) / 64) + (long long)((B + 63) / 64) * ((P + 63) / 64);
+  m.big = tiles64 >= 448;
+
+  // Weight tiles on the bf16 matrix unit unless NNUE_FTM_BF16=0: 64 rows, or 32 with NNUE_FTM_BF_WM=32.  The 64-row ones with K
+  // tiles of 64 (gemm_tile_bf64): the launch's LDS drops from 64 KB to the rider's 52 KB -- three workgroups per CU instead of
+  // two (the 168 registers allow exactly that): 43.5 -> 37.7 us at the C3 shapes, 26.2 -> 25.1 us at C2
+  m.w_bf = !knob::bf16() ? 0 : knob::bf_wm() == 32 ? 32 : 64;
+  const Shape wf = m.big ? shape_of(kF32Square, direct, L1, B) : sw;
+  m.w_bm = m.w_bf ? m.w_bf : wf.bm;
+  m.w_bk = m.w_bf == 64 ? 64 : m.w_bf == 32 ? 128 : wf.bk;
+  m.w_tiles_n = (L1 + 63) / 64;
+  m.n_w = ((direct + m.w_bm - 1) / m.w_bm) * m.w_tiles_n;
+  m.sq_count = m.n_w;
+
+  // (value-gradient tiles of 32 x 32 x 128 -- twice the workgroups, two resident per CU -- were measured at the CIFAR
+  // batch-512 shape and lose: 30.5 vs 28.9 us for the launch)
+  const bool v_small = !m.big && sv.tile == kF32Flat;
+  m.v_bm = v_small ? 32 : 64;
+  m.v_tiles_n = (P + 63) / 64;
+  m.n_v = ((B + m.v_bm - 1) / m.v_bm) * m.v_tiles_n;
+  // value tiles as six bf16 plane products: for the 64 x 64 tiles (C3 shapes: 43.5 vs 46.0 us for the launch); the 32 x 64 tiles
+  // of the batch-512 shape are latency-bound per K tile and lose with the 64-deep bf16 tiles (27.2 vs 26.3 us) -- they take the
+  // six plane products only with the table split once per step and streamed from the value planes (val_planes_tiles)
+  m.v6 = m.w_bf && !v_small && L1 % 8 == 0;
+
+  m.kernel = m.w_bf == 64   ? (v_small ? BwdKernel::kBf64_V32 : m.v6 ? BwdKernel::kBf64_V64x6 : BwdKernel::kBf64_V64)
+             : m.w_bf == 32 ? (v_small ? BwdKernel::kBf32_V32 : m.v6 ? BwdKernel::kBf32_V64x6 : BwdKernel::kBf32_V64)
+             : m.big        ? BwdKernel::kF32_64x64
+             : v_small      ? BwdKernel::kF32_32x32
+                            : BwdKernel::kF32_32x64;
+
+  // The STE ride: 8 channels (fps * G == P with G the grid of an H x W image at `stride`), the merged launch with its default
+  // bf16 weight tiles and 32 x 64 value tiles (the batch-512 CIFAR shape: 0.0830 -> 0.0801 ms per step).  The 64 x 64 bf16-plane
+  // value tiles of the batch-1024 shapes also take the epilogue (ftm_backward_bf_kernel<.., ValSteEpi>) but lose there -- C3
+  // 0.1266 -> 0.1312 ms: their 64 pixel registers are requested after the K loop -- so they keep the STE launch
+  // (NNUE_FTM_RIDE_STE_V64=1 rides there all the same).
+  if (m.w_bf == 64 && (v_small || knob::ride_ste_v64()) && H > 0 && W > 0 && stride > 0) {
+    const long long Gh = (H - 1) / stride + 1, Gw = (W - 1) / stride + 1;
+    if (8 * Gh * Gw == P && (long long)B * 3 * H * W < (1ll << 40)) {
+      m.ste_tiles = (int64_t)((B + m.v_bm - 1) / m.v_bm) * ((Gh * Gw + 7) / 8);
+      m.ste_kernel = v_small ? BwdKernel::kBf64_V32Ste : m.v6 ? BwdKernel::kBf64_V64x6Ste : BwdKernel::kBf64_V64Ste;
+    }
+  }
+  // The value planes: the STE ride's shape on 32-row value tiles, L1 a multiple of the planes' 8-j chunk, and at least one value
+  // tile per CU -- the shape the planes were measured at; below it the tiles of a launch do not queue behind each other's matrix
+  // time and keep the f32 tiles.  NNUE_FTM_VAL_PLANES=0 keeps the f32 tiles everywhere; NNUE_FTM_VAL_PLANES_MIN_TILES is the floor.
+  if (knob::val_planes() && m.w_bf == 64 && v_small && P % 8 == 0 && L1 % 8 == 0) {
+    const int64_t tiles = (int64_t)((B + 31) / 32) * ((P / 8 + 7) / 8);
+    const bool addressable = (int64_t)((P / 8 + 7) / 8) * ((L1 + kBfK - 1) / kBfK) * kValPlaneBlock < (1ll << 31);
+    if (tiles >= knob::val_planes_min_tiles() && addressable) m.val_planes_tiles = tiles;
+  }
+  m.val_planes = m.val_planes_tiles > 0 && m.ste_tiles == m.val_planes_tiles;
+  return m;
 }
 }  // namespace
 
 extern "C" int nnue_ftm_value_planes_supported(int B, int F, int P, int L1, int H, int W, int stride) {
-  const int64_t tiles = val_planes_tiles(B, F, P, L1);
-  return tiles > 0 && ste_ride_tiles(B, F, P, L1, H, W, stride) == tiles;
+  return merged_backward_plan(B, F, P, L1, H, W, stride).val_planes;
 }
 
 extern "C" int64_t nnue_ftm_value_planes_bytes(int B, int F, int P, int L1) {
@@ -2485,33 +2535,18 @@ extern "C" int64_t nnue_ftm_value_planes_bytes(int B, int F, int P, int L1) {
 }
 
 extern "C" int64_t nnue_ftm_backward_ste_chunks(int B, int F, int P, int L1, int H, int W, int stride) {
-  return ste_ride_tiles(B, F, P, L1, H, W, stride);
+  return merged_backward_plan(B, F, P, L1, H, W, stride).ste_tiles;
 }
 extern "C" int nnue_ftm_backward_ste_supported(int B, int F, int P, int L1, int H, int W, int stride) {
-  return ste_ride_tiles(B, F, P, L1, H, W, stride) > 0;
+  return merged_backward_plan(B, F, P, L1, H, W, stride).ste_tiles > 0;
 }
 
 // Number of squared-norm partials nnue_ftm_backward leaves (one per weight-gradient tile), 0 when the product is split
 // along K (never for this operand order today) or the shape is not taken.
-extern "C" int64_t nnue_ftm_backward_sq_count(int B, int F, int P, int L1) {
-  if (!nnue_ftm_supported(F, P, L1) || !shape_ok(B, F, P, L1)) return 0;
-  const int direct = (F - 1 < P) ? F - 1 : P;
-  if (direct <= 0) return 0;
-  bool big = false;
-  if (merged_backward_shape(B, F, P, L1, &big)) {
-    if (const int wm = merged_bf_wm()) return (int64_t)((direct + wm - 1) / wm) * ((L1 + 63) / 64);
-    if (big) return (int64_t)((direct + 63) / 64) * ((L1 + 63) / 64);
-    const Shape s = plan(direct, L1, B, false, false);
-    return (int64_t)s.tiles_m * s.tiles_n;
-  }
-  const Shape s = plan(direct, L1, B, false, false, true);
-  return s.ksplit == 1 ? (int64_t)s.tiles_m * s.tiles_n : 0;
-}
+extern "C" int64_t nnue_ftm_backward_sq_count(int B, int F, int P, int L1) { return merged_backward_plan(B, F, P, L1).sq_count; }
 
 extern "C" int nnue_ftm_backward_cw_supported(int B, int F, int P, int L1, int L2) {
-  bool big = false;
-  return nnue_ftm_supported(F, P, L1) && shape_ok(B, F, P, L1) && merged_backward_shape(B, F, P, L1, &big) && L1 % 128 == 0 && L2 > 0 &&
-         L2 % 4 == 0 && ((long long)B + 256) * L2 * 4 < (1ll << 31);
+  return merged_backward_plan(B, F, P, L1).taken && L1 % 128 == 0 && L2 > 0 && L2 % 4 == 0 && ((long long)B + 256) * L2 * 4 < (1ll << 31);
 }
 
 namespace {
@@ -2558,7 +2593,8 @@ int ftm_backward_impl(const uint8_t* bits, const float* sink, const float* d_out
                       float* sq_partial, int K, const int32_t* seg, int grouped_rows, const nnue_cls_rider* small, const SteArgs* ste,
                       nnue_stream_t stream, const ValPlanes* vp) {
   NNUE_REQUIRE(bits && sink && d_out && weight && d_weight && d_bias && (d_conv_out || ste), NNUE_E_ARG, "nnue_ftm_backward: null pointer");
-  const int64_t ste_tiles = ste ? ste_ride_tiles(B, F, P, L1, ste->H, ste->W, ste->stride) : 0;
+  const MergedBackward mb = ste ? merged_backward_plan(B, F, P, L1, ste->H, ste->W, ste->stride) : merged_backward_plan(B, F, P, L1);
+  const int64_t ste_tiles = mb.ste_tiles;
   NNUE_REQUIRE(!ste || ((ste->img || ste->patches) && ste->conv_out && ste->thr && ste->partial), NNUE_E_ARG,
                "nnue_ftm_backward: null STE pointer");
   NNUE_REQUIRE(!ste || ste_tiles > 0, NNUE_E_SHAPE, "nnue_ftm_backward: STE partials requested for a shape the merged launch does not take "
@@ -2573,7 +2609,7 @@ int ftm_backward_impl(const uint8_t* bits, const float* sink, const float* d_out
   NNUE_REQUIRE(nnue_aligned16(bits) && nnue_aligned16(d_out) && nnue_aligned16(weight), NNUE_E_ARG,
                "nnue_ftm_backward: pointers must be 16-byte aligned");
   // the value planes are read where the shape takes them and the STE rides (else: the launch of nnue_ftm_backward)
-  const bool planes_fed = vp && ste && nnue_ftm_value_planes_supported(B, F, P, L1, ste->H, ste->W, ste->stride);
+  const bool planes_fed = vp && ste && mb.val_planes;
   if (vp) {
     NNUE_REQUIRE(vp->p, NNUE_E_ARG, "nnue_ftm_backward_planes: null pointer");
     NNUE_REQUIRE(nnue_aligned16(vp->p), NNUE_E_ARG, "nnue_ftm_backward_planes: pointers must be 16-byte aligned");
@@ -2583,19 +2619,8 @@ int ftm_backward_impl(const uint8_t* bits, const float* sink, const float* d_out
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int direct = (F - 1 < P) ? F - 1 : P;
-  const Shape sw = plan(direct > 0 ? direct : 1, L1, B, false, false), sv = plan(B, P, L1, true, false);
-  // measured: one launch wins where the products are launch-sized (C2 -10 %, C3 -8 % of the two launches) and loses
-  // 7 % at the 224x224 shapes, where each product fills the chip by itself and the two tile shapes fight over L2.
-  // Tile shapes for the shared launch: the products sit near the L2 -> LDS fill rate at these sizes (32x64 tiles: 10.7
-  // flop per staged byte), so 64x64x64 tiles (16 flop/B) are taken for both as soon as the two products together still
-  // give ~1.75 workgroups per CU (C3: 45.5 vs 49.3 us); below that the small tiles win (C2: 28 vs 37 us).
-  bool big_pair = false;
-  const bool pair_ok = merged_backward_shape(B, F, P, L1, &big_pair);
-  Shape sw2 = sw, sv2 = sv;
-  for (Shape* q : {&sw2, &sv2}) { q->cfg = 1; q->bm = 64; q->bn = 64; q->bk = 64; }
-  sw2.tiles_m = (direct + 63) / 64; sw2.tiles_n = (L1 + 63) / 64; sv2.tiles_m = (B + 63) / 64; sv2.tiles_n = (P + 63) / 64;
-  NNUE_REQUIRE(!small || pair_ok, NNUE_E_SHAPE, "nnue_ftm_backward: the classifier's small gradients can ride only in the merged launch");
-  if (!pair_ok) {
+  NNUE_REQUIRE(!small || mb.taken, NNUE_E_SHAPE, "nnue_ftm_backward: the classifier's small gradients can ride only in the merged launch");
+  if (!mb.taken) {
     const int rc = backward_weight_impl(bits, sink, d_out, B, F, P, L1, d_weight, d_bias, sq_partial, stream);
     return rc != NNUE_OK ? rc : nnue_ftm_backward_values(bits, d_out, weight, B, F, P, L1, d_conv_out, stream);
   }
@@ -2604,20 +2629,20 @@ int ftm_backward_impl(const uint8_t* bits, const float* sink, const float* d_out
   const BwwEpi we{d_weight, L1, sq_partial};
   const ValEpi ve{bits, d_conv_out, P};
   const TailRows t = tail_rows(d_out, sink, B, L1, direct, F, d_weight, d_bias);
-  const int bf_wm = merged_bf_wm();
-  Shape sw3 = sw;  // bf16 weight-gradient tiles: bf_wm x 64 x 128
-  if (bf_wm) { sw3.bm = bf_wm; sw3.bn = 64; sw3.bk = 128; sw3.tiles_m = (direct + bf_wm - 1) / bf_wm; sw3.tiles_n = (L1 + 63) / 64; }
-  const Shape& swr = bf_wm ? sw3 : big_pair ? sw2 : sw;
-  // (value-gradient tiles of 32 x 32 x 128 -- twice the workgroups, two resident per CU -- were measured at the CIFAR
-  // batch-512 shape and lose: 30.5 vs 28.9 us for the launch)
-  const Shape& svr = big_pair ? sv2 : sv;
   // STE ride: the value tiles' columns are the 8 channels of 8 grid positions (ValSteEpi), ceil(G / 8) tiles along N
-  const int G = P / 8, v_tiles_n = ste ? (G + 7) / 8 : svr.tiles_n;
-  const int n_w = swr.tiles_m * swr.tiles_n, n_v = svr.tiles_m * v_tiles_n, n_t = t.col_blocks * (1 + t.zero_slices);
+  const int G = P / 8, v_tiles_n = ste ? (G + 7) / 8 : mb.v_tiles_n;
+  const int n_w = mb.n_w, n_v = ste ? (int)mb.ste_tiles : mb.n_v, n_t = t.col_blocks * (1 + t.zero_slices);
   ValSteEpi vs{};
   if (ste) {
     const int Gw = (ste->W - 1) / ste->stride + 1;
     vs = ValSteEpi{bits, d_conv_out, P, ste->img, ste->patches, ste->conv_out, ste->thr, ste->H, ste->W, ste->stride, Gw, G, ste->partial, n_v};
+  }
+  ValStePlanesEpi vps{};
+  if (planes_fed) {
+    static_cast<ValSteEpi&>(vps) = vs;
+    vps.planes = static_cast<const unsigned char*>(vp->p);
+    vps.planes_bytes = (unsigned)nnue_ftm_value_planes_bytes(B, F, P, L1);
+    vps.ktiles = (L1 + kBfK - 1) / kBfK;
   }
   CwArgs cw{};
   if (want_cw) {  // d_w1 [L2][L1] = d_z1^T [L2 x B] l0 [B x L1]   (per bucket over its own grouped rows when seg != NULL)
@@ -2626,7 +2651,7 @@ int ftm_backward_impl(const uint8_t* bits, const float* sink, const float* d_out
     cw.b = Mat{ft, (unsigned)((size_t)rows * L1 * 4), L1, kIntMax, kIntMax};
     cw.e = CwEpi{d_w1, L1, L1 / 2};
     cw.M = L2; cw.N = L1; cw.K = B; cw.tiles_n = (L1 + 63) / 64;
-    const int cw_bm = bf_wm ? 32 : swr.bm;  // the rider keeps f32 tiles: the weight-gradient shape, or 32 x 64 x 128 beside bf16 tiles
+    const int cw_bm = mb.w_bf ? 32 : mb.w_bm;  // the rider keeps f32 tiles: the weight-gradient shape, or 32 x 64 x 128 beside bf16 tiles
     cw.per_bucket = ((L2 + cw_bm - 1) / cw_bm) * cw.tiles_n;
     cw.seg = seg;
     cw.n_c = cw.per_bucket * (seg ? K : 1);
@@ -2637,52 +2662,26 @@ int ftm_backward_impl(const uint8_t* bits, const float* sink, const float* d_out
   if (small) memcpy(&sgw, small, sizeof(SmallWgrad));
   const int n_s = small ? sgw.wgrad_blocks : 0;
   const dim3 grid((unsigned)(n_w + n_v + cw.n_c + n_t + n_s));
-#define NNUE_FTM_BWD(WM, WN, WK, VM, VN, VK)                                                                                          \
-  hipLaunchKernelGGL((ftm_backward_kernel<WM, WN, WK, VM, VN, VK>), grid, dim3(256), 0, st, wa, wb, we, direct, L1, B, swr.tiles_n, n_w, va, \
-                     vb, ve, B, P, L1, svr.tiles_n, n_v, cw, t, sgw)
-#define NNUE_FTM_BWD_BF(WM, VM, VN, VK)                                                                                                  \
-  do {                                                                                                                                   \
-    if (w64 && WM == 64 && !v6) hipLaunchKernelGGL((ftm_backward_bf_kernel<64, VM, VN, VK, false, true>), grid, dim3(256), 0, st, wa, wb, we, direct, L1, B, \
-                               swr.tiles_n, n_w, va, vb, ve, B, P, L1, svr.tiles_n, n_v, cw, t, sgw);                                    \
-    else if (w64 && WM == 64) hipLaunchKernelGGL((ftm_backward_bf_kernel<64, VM, VN, VK, true, true>), grid, dim3(256), 0, st, wa, wb, we, direct, L1, B, \
-                               swr.tiles_n, n_w, va, vb, ve, B, P, L1, svr.tiles_n, n_v, cw, t, sgw);                                    \
-    else if (v6) hipLaunchKernelGGL((ftm_backward_bf_kernel<WM, VM, VN, VK, true>), grid, dim3(256), 0, st, wa, wb, we, direct, L1, B, swr.tiles_n, n_w, va, \
-                               vb, ve, B, P, L1, svr.tiles_n, n_v, cw, t, sgw);                                                           \
-    else hipLaunchKernelGGL((ftm_backward_bf_kernel<WM, VM, VN, VK>), grid, dim3(256), 0, st, wa, wb, we, direct, L1, B, swr.tiles_n, n_w, va, vb, \
-                            ve, B, P, L1, svr.tiles_n, n_v, cw, t, sgw);                                                                  \
-  } while (0)
-  const bool v_small = !big_pair && sv.cfg == 0;
-  const bool v6 = merged_values_bf6(B, F, P, L1);
-  // weight tiles with K tiles of 64 (gemm_tile_bf64): the launch's LDS drops from 64 KB to the rider's 52 KB -- three
-  // workgroups per CU instead of two (the 168 registers allow exactly that): 43.5 -> 37.7 us at the C3 shapes, 26.2 -> 25.1 us at C2
-  const bool w64 = merged_w64();
-  if (ste) {  // the value tiles leave the STE partials (ValSteEpi; nnue_ftm_backward_ste_chunks said the shape is taken)
-    if (planes_fed) {  // (v_small by nnue_ftm_value_planes_supported)
-      const int ktiles = (L1 + kBfK - 1) / kBfK;
-      ValStePlanesEpi vps{};
-      static_cast<ValSteEpi&>(vps) = vs;
-      vps.planes = static_cast<const unsigned char*>(vp->p);
-      vps.planes_bytes = (unsigned)nnue_ftm_value_planes_bytes(B, F, P, L1);
-      vps.ktiles = ktiles;
-      hipLaunchKernelGGL((ftm_backward_bf_kernel<64, 32, 64, 128, false, true, ValStePlanesEpi>), grid, dim3(256), 0, st, wa, wb, we, direct, L1, B,
-                         swr.tiles_n, n_w, va, vb, vps, B, P, L1, v_tiles_n, n_v, cw, t, sgw);
-    } else if (v_small)
-      hipLaunchKernelGGL((ftm_backward_bf_kernel<64, 32, 64, 128, false, true, ValSteEpi>), grid, dim3(256), 0, st, wa, wb, we, direct, L1, B,
-                         swr.tiles_n, n_w, va, vb, vs, B, P, L1, v_tiles_n, n_v, cw, t, sgw);
-    else if (v6)
-      hipLaunchKernelGGL((ftm_backward_bf_kernel<64, 64, 64, 64, true, true, ValSteEpi>), grid, dim3(256), 0, st, wa, wb, we, direct, L1, B,
-                         swr.tiles_n, n_w, va, vb, vs, B, P, L1, v_tiles_n, n_v, cw, t, sgw);
-    else
-      hipLaunchKernelGGL((ftm_backward_bf_kernel<64, 64, 64, 64, false, true, ValSteEpi>), grid, dim3(256), 0, st, wa, wb, we, direct, L1, B,
-                         swr.tiles_n, n_w, va, vb, vs, B, P, L1, v_tiles_n, n_v, cw, t, sgw);
-    return nnue_launch_status("nnue_ftm_backward");
+#define NNUE_FTM_BWD(KERNEL, VEPI)                                                                                                          \
+  hipLaunchKernelGGL(KERNEL, grid, dim3(256), 0, st, wa, wb, we, direct, L1, B, mb.w_tiles_n, n_w, va, vb, VEPI, B, P, L1, v_tiles_n, n_v, cw, \
+                     t, sgw)
+  // (the STE forms: nnue_ftm_backward_ste_chunks said the shape is taken)
+  switch (planes_fed ? BwdKernel::kBf64_V32StePlanes : ste ? mb.ste_kernel : mb.kernel) {
+    case BwdKernel::kF32_32x32: NNUE_FTM_BWD((ftm_backward_kernel<32, 64, 128, 32, 64, 128>), ve); break;
+    case BwdKernel::kF32_32x64: NNUE_FTM_BWD((ftm_backward_kernel<32, 64, 128, 64, 64, 64>), ve); break;
+    case BwdKernel::kF32_64x64: NNUE_FTM_BWD((ftm_backward_kernel<64, 64, 64, 64, 64, 64>), ve); break;
+    case BwdKernel::kBf32_V32: NNUE_FTM_BWD((ftm_backward_bf_kernel<32, 32, 64, 128>), ve); break;
+    case BwdKernel::kBf32_V64: NNUE_FTM_BWD((ftm_backward_bf_kernel<32, 64, 64, 64>), ve); break;
+    case BwdKernel::kBf32_V64x6: NNUE_FTM_BWD((ftm_backward_bf_kernel<32, 64, 64, 64, true>), ve); break;
+    case BwdKernel::kBf64_V32: NNUE_FTM_BWD((ftm_backward_bf_kernel<64, 32, 64, 128, false, true>), ve); break;
+    case BwdKernel::kBf64_V64: NNUE_FTM_BWD((ftm_backward_bf_kernel<64, 64, 64, 64, false, true>), ve); break;
+    case BwdKernel::kBf64_V64x6: NNUE_FTM_BWD((ftm_backward_bf_kernel<64, 64, 64, 64, true, true>), ve); break;
+    case BwdKernel::kBf64_V32Ste: NNUE_FTM_BWD((ftm_backward_bf_kernel<64, 32, 64, 128, false, true, ValSteEpi>), vs); break;
+    case BwdKernel::kBf64_V32StePlanes: NNUE_FTM_BWD((ftm_backward_bf_kernel<64, 32, 64, 128, false, true, ValStePlanesEpi>), vps); break;
+    case BwdKernel::kBf64_V64Ste: NNUE_FTM_BWD((ftm_backward_bf_kernel<64, 64, 64, 64, false, true, ValSteEpi>), vs); break;
+    case BwdKernel::kBf64_V64x6Ste: NNUE_FTM_BWD((ftm_backward_bf_kernel<64, 64, 64, 64, true, true, ValSteEpi>), vs); break;
+    case BwdKernel::kNone: break;  // (not taken: returned above)
   }
-  if (bf_wm == 64) { if (v_small) NNUE_FTM_BWD_BF(64, 32, 64, 128); else NNUE_FTM_BWD_BF(64, 64, 64, 64); }
-  else if (bf_wm == 32) { if (v_small) NNUE_FTM_BWD_BF(32, 32, 64, 128); else NNUE_FTM_BWD_BF(32, 64, 64, 64); }
-  else if (big_pair) NNUE_FTM_BWD(64, 64, 64, 64, 64, 64);
-  else if (sv.cfg == 0) NNUE_FTM_BWD(32, 64, 128, 32, 64, 128);
-  else NNUE_FTM_BWD(32, 64, 128, 64, 64, 64);
-#undef NNUE_FTM_BWD_BF
 #undef NNUE_FTM_BWD
   return nnue_launch_status("nnue_ftm_backward");
 }
@@ -2696,7 +2695,7 @@ extern "C" int nnue_ftm_forward_l1_supported(int B, int F, int P, int L1, int L2
   const int direct = (F - 1 < P) ? F - 1 : P;
   if (direct <= 0) return 0;
   const Shape s = plan(B, L1, direct, true, true, true);
-  return (s.cfg == 0 || s.cfg == 1 || s.cfg == 6 || s.cfg == 7) && s.ksplit == 1;
+  return (s.tile == kF32Flat || s.tile == kF32Square || s.tile == kBf32 || s.tile == kBf64) && s.ksplit == 1;
 }
 
 extern "C" int nnue_ftm_forward_l1(const uint8_t* bits, const float* sink, const float* weight, const float* bias, const float* w1, int B,
@@ -2712,9 +2711,9 @@ extern "C" int nnue_ftm_forward_l1(const uint8_t* bits, const float* sink, const
   const Mat ma{bits, (unsigned)((size_t)B * P), P, kIntMax, kIntMax}, mb{weight, (unsigned)((size_t)direct * L1 * 4), L1, kIntMax, kIntMax};
   const FwdL1Epi epi{bias, weight + (size_t)(F - 1) * L1, sink, out, w1, part, B, L1, L2, L1 / 2};
   const dim3 grid((unsigned)(s.tiles_m * s.tiles_n));
-  if (s.cfg == 0) hipLaunchKernelGGL((ftm_forward_l1_kernel<32, 128>), grid, dim3(256), 0, st, ma, mb, epi, B, L1, direct, s.tiles_n);
-  else if (s.cfg == 1) hipLaunchKernelGGL((ftm_forward_l1_kernel<64, 64>), grid, dim3(256), 0, st, ma, mb, epi, B, L1, direct, s.tiles_n);
-  else if (s.cfg == 6) hipLaunchKernelGGL((ftm_forward_l1_bf_kernel<32>), grid, dim3(256), 0, st, ma, mb, epi, B, L1, direct, s.tiles_n);
+  if (s.tile == kF32Flat) hipLaunchKernelGGL((ftm_forward_l1_kernel<32, 128>), grid, dim3(256), 0, st, ma, mb, epi, B, L1, direct, s.tiles_n);
+  else if (s.tile == kF32Square) hipLaunchKernelGGL((ftm_forward_l1_kernel<64, 64>), grid, dim3(256), 0, st, ma, mb, epi, B, L1, direct, s.tiles_n);
+  else if (s.tile == kBf32) hipLaunchKernelGGL((ftm_forward_l1_bf_kernel<32>), grid, dim3(256), 0, st, ma, mb, epi, B, L1, direct, s.tiles_n);
   else hipLaunchKernelGGL((ftm_forward_l1_bf_kernel<64>), grid, dim3(256), 0, st, ma, mb, epi, B, L1, direct, s.tiles_n);
   return nnue_launch_status("nnue_ftm_forward_l1");
 }
@@ -2729,7 +2728,7 @@ extern "C" int nnue_ftm_forward_l1_planes_supported(int B, int F, int P, int L1,
   const int direct = (F - 1 < P) ? F - 1 : P;
   if ((long long)direct * L1 * 4 > (long long)kStreamTableBytes) return 0;  // a streamed table
   const long long t32 = (long long)((B + 31) / 32) * (L1 / 64), t64 = (long long)((B + 63) / 64) * (L1 / 64);
-  return t32 >= env_int("NNUE_FTM_FWD_PLANES_MIN_WG", 256) && t64 < 256;
+  return t32 >= knob::fwd_planes_min_wg() && t64 < 256;
 }
 
 extern "C" int64_t nnue_ftm_forward_planes_bytes(int B, int F, int P, int L1) {
@@ -2758,7 +2757,7 @@ extern "C" int nnue_ftm_forward_l1_planes(const uint8_t* bits, const float* sink
   const dim3 grid((unsigned)(((B + 31) / 32) * tiles_n));
   // up to kStreamKTiles K tiles the table operand is streamed into the MFMA's registers (NNUE_FTM_FWD_STREAM=0, read per call:
   // the LDS-staged kernel, which deeper shapes keep)
-  const int streamed = env_int("NNUE_FTM_FWD_STREAM", 1) != 0 && direct <= kStreamKTiles * kBfK;
+  const bool streamed = knob::fwd_stream() && direct <= kStreamKTiles * kBfK;
   if (streamed) hipLaunchKernelGGL(ftm_forward_l1_stream_kernel, grid, dim3(256), 0, st, ma, mp, epi, direct, tiles_n);
   else hipLaunchKernelGGL(ftm_forward_l1_planes_kernel, grid, dim3(256), 0, st, ma, mp, epi, B, L1, direct, tiles_n);
   return nnue_launch_status("nnue_ftm_forward_l1_planes");
@@ -2775,8 +2774,7 @@ struct GramPlan { int pairs, slices, wave_steps; };
 GramPlan gram_plan(int B, int direct) {
   const int tiles_b = (B + 31) / 32, pairs = tiles_b * (tiles_b + 1) / 2;
   const int steps = direct > 0 ? (direct + 63) / 64 : 1;
-  static const int want_wgs = env_int("NNUE_FTM_GRAM_WGS", 512);  // developer knob
-  int want = want_wgs / pairs;
+  int want = 512 / pairs;
   want = want < 1 ? 1 : want;
   int per = (steps + want * 4 - 1) / (want * 4);
   per = ((per + 3) / 4) * 4;
@@ -2874,10 +2872,7 @@ int update_ptrs_aligned(const char* who, const void* bits, const void* d_out, co
 // the in-place epilogues live there -- and never split along K
 int update_product_shape(const char* who, int direct, int L1, int B, Shape* out) {
   Shape s = plan(direct, L1, B, false, false, true);
-  if (s.cfg < 6) {  // launch-sized product: a 64-row bf16 tile
-    s.cfg = 7; s.bm = 64; s.bn = 64; s.bk = kBfK;
-    s.tiles_m = (direct + 63) / 64; s.tiles_n = (L1 + 63) / 64; s.ksplit = 1; s.klen = (B + kBfK - 1) / kBfK * kBfK;
-  }
+  if (!s.bf) s = shape_of(kBf64, direct, L1, B);  // launch-sized product: a 64-row bf16 tile
   NNUE_REQUIRE(s.ksplit == 1, NNUE_E_SHAPE, "%s: the product must not be split along K", who);
   *out = s;
   return NNUE_OK;
@@ -2926,12 +2921,11 @@ int update_forward_launch(const char* who, std::conditional_t<kAdam, UpdFwdAdam,
   const int64_t need = (int64_t)s.ksplit * a.Bn * a.L1 * (int64_t)sizeof(float);
   NNUE_REQUIRE(nx.scratch_bytes >= need, NNUE_E_SCRATCH, "%s: scratch %lld < %lld bytes", who, (long long)nx.scratch_bytes, (long long)need);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  static const int xcd = env_int("NNUE_FTM_XCD_REMAP", 1);  // developer knob
   a.slabs = static_cast<float*>(nx.scratch);
   a.klen = s.klen;
   a.tiles_n = s.tiles_n;
-  a.xcd_remap = (xcd && s.ksplit % 8 == 0) ? 1 : 0;
-  a.abl = env_int("NNUE_FTM_UF_ABL", 0);
+  a.xcd_remap = s.ksplit % 8 == 0 ? 1 : 0;
+  a.abl = knob::uf_abl();
   const dim3 grid((unsigned)(s.tiles_n * s.ksplit));
   const bool mom = a.momentum != nullptr;
   auto go = [&](auto nk) {
@@ -2966,9 +2960,8 @@ extern "C" int nnue_ftm_backward_weight_update(const uint8_t* bits, const float*
   if (const int rc = update_ptrs_aligned(who, bits, d_out, weight, nullptr, nullptr)) return rc;
   const int direct = (F - 1 < P) ? F - 1 : P;
   if (direct <= 0) return NNUE_OK;
-  static const int xcd = env_int("NNUE_FTM_XCD_REMAP", 1);  // developer knob
   return update_launch(who, bits, d_out, B, P, L1, direct,
-                       BwwSgdEpi{weight, momentum == 0.0f ? nullptr : momentum_rows, coef, L1, lr, momentum, weight_decay, grad_scale, first_step, xcd, lr_dev},
+                       BwwSgdEpi{weight, momentum == 0.0f ? nullptr : momentum_rows, coef, L1, lr, momentum, weight_decay, grad_scale, first_step, /*xcd_remap=*/1, lr_dev},
                        stream);
 }
 
@@ -2979,11 +2972,10 @@ extern "C" int nnue_ftm_update_forward_supported(int B, int B_next, int F, int P
   const int nk = (B + 63) / 64;  // K tiles of the weight-gradient product: 1, 2, 4, 8 or 16
   if (nk > 16 || (nk & (nk - 1)) != 0) return 0;
   const int direct = (F - 1 < P) ? F - 1 : P;
-  if (direct <= 0 || !use_bf16()) return 0;
+  if (direct <= 0 || !knob::bf16()) return 0;
   // the forward must be the split-K product of 128 x 64 bf16-split tiles with 64-deep K tiles, whole 128-row table tiles per slab
   const Shape s = plan(B_next, L1, direct, true, true, true);
-  static const int kt64 = env_int("NNUE_FTM_BF_KT64", 1);
-  return s.cfg == 8 && kt64 && s.ksplit > 1 && s.klen % 128 == 0 && plan(direct, L1, B, false, false, true).cfg == 8;
+  return s.tile == kBf128 && s.ksplit > 1 && s.klen % 128 == 0 && plan(direct, L1, B, false, false, true).tile == kBf128;
 }
 
 extern "C" int nnue_ftm_backward_weight_update_forward(const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight,
@@ -3029,9 +3021,8 @@ extern "C" int nnue_ftm_backward_weight_update_adam(const uint8_t* bits, const f
   if (const int rc = update_ptrs_aligned(who, bits, d_out, weight, nullptr, nullptr)) return rc;
   const int direct = (F - 1 < P) ? F - 1 : P;
   if (direct <= 0) return NNUE_OK;
-  static const int xcd = env_int("NNUE_FTM_XCD_REMAP", 1);  // developer knob
   return update_launch(who, bits, d_out, B, P, L1, direct,
-                       BwwAdamEpi{weight, exp_avg_rows, exp_avg_sq_rows, coef, step_counter, L1, lr, beta1, beta2, eps, weight_decay, grad_scale, xcd, lr_dev},
+                       BwwAdamEpi{weight, exp_avg_rows, exp_avg_sq_rows, coef, step_counter, L1, lr, beta1, beta2, eps, weight_decay, grad_scale, /*xcd_remap=*/1, lr_dev},
                        stream);
 }
 
@@ -3066,12 +3057,13 @@ extern "C" int nnue_ftm_uses_bf16(int which, int B, int F, int P, int L1) {
   if (!nnue_ftm_supported(F, P, L1) || !shape_ok(B, F, P, L1)) return 0;
   const int direct = (F - 1 < P) ? F - 1 : P;
   if (direct <= 0) return 0;
-  if (which == 0) return plan(B, L1, direct, true, true, true).cfg >= 6;
-  if (which == 1) return plan(direct, L1, B, false, false, true).cfg >= 6;
-  if (which == 2) { bool big = false; return merged_backward_shape(B, F, P, L1, &big) ? merged_bf_wm() != 0 : plan(direct, L1, B, false, false, true).cfg >= 6; }
+  if (which == 0) return plan(B, L1, direct, true, true, true).bf;
+  if (which == 1) return plan(direct, L1, B, false, false, true).bf;
+  const MergedBackward mb = merged_backward_plan(B, F, P, L1);
+  if (which == 2) return mb.taken ? mb.w_bf != 0 : plan(direct, L1, B, false, false, true).bf;
   if (which == 4) return values_bf6(B, P, L1);            // stand-alone value gradient: six bf16 plane products
   // value tiles of the merged launch: six plane products on 64-row tiles, or on the 32-row tiles fed the value planes (a caller
   // with the STE ride passes them where nnue_ftm_value_planes_supported says yes: NnueTrainer)
-  if (which == 5) return merged_values_bf6(B, F, P, L1) || val_planes_tiles(B, F, P, L1) > 0;
+  if (which == 5) return mb.v6 || mb.val_planes_tiles > 0;
   return 1;
 }

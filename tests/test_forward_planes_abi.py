@@ -33,7 +33,6 @@ def test_size_query_at_the_flagship_shape_and_at_sizes_without_a_buffer():
 def test_shape_policy(monkeypatch):
     monkeypatch.delenv("NNUE_FTM_FWD_PLANES_MIN_WG", raising=False)
     monkeypatch.delenv("NNUE_FTM_BF_BM", raising=False)
-    monkeypatch.delenv("NNUE_FTM_CFG", raising=False)
     ok = lib.ftm_forward_l1_planes_supported
     assert ok(512, 800, 968, 1024, 128)            # c2: 16 x 16 tiles of 32 rows, today's f32 32-row forward
     assert not ok(32, 800, 968, 64, 32)            # c1: one row tile (a split-K forward, not a fused-forward shape at all)

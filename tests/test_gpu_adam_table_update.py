@@ -219,7 +219,7 @@ def _bigtable_pair(monkeypatch, **opt):
     twin = nnue.NNUE(grid, l1, 32, 16, num_classes=10, input_size=64).to(DEV)
     twin.load_state_dict(model.state_dict())
     tr = NnueTrainer(model, 64, (hw, hw), **opt)
-    if not tr.fuse_next_forward and (os.environ.get("NNUE_FTM_BF16") == "0" or os.environ.get("NNUE_FTM_BF_KT64") == "0"):
+    if not tr.fuse_next_forward and os.environ.get("NNUE_FTM_BF16") == "0":
         pytest.skip("a developer knob took the forward off the bf16-split 64-deep tiles the fused pass is built on")
     assert tr.fuse_table_update and tr.fuse_next_forward and not tr.grads_materialised
     monkeypatch.setenv("NNUE_FUSE_NEXT_FORWARD", "0")
@@ -291,8 +291,8 @@ def test_a_step_group_at_the_224_shape_follows_the_oracle_with_adam():
     tr = NnueTrainer(model.to(DEV), cfg["batch"], (cfg["image"], cfg["image"]), use_graph=True, input_slots=3, optimizer="adam", **opt)
     if not tr.fuse_next_forward:
         assert os.environ.get("NNUE_FUSE_NEXT_FORWARD") == "0" or os.environ.get("NNUE_FUSE_TABLE_UPDATE") == "0" \
-            or os.environ.get("NNUE_FT_PATH", "auto") not in ("auto", "mfma") or os.environ.get("NNUE_FTM_BF16") == "0" \
-            or os.environ.get("NNUE_FTM_BF_KT64") == "0", "the 224x224 shape must take the fused pass by default"
+            or os.environ.get("NNUE_FT_PATH", "auto") not in ("auto", "mfma") or os.environ.get("NNUE_FTM_BF16") == "0", \
+            "the 224x224 shape must take the fused pass by default"
         pytest.skip("a knob switched the fused update + next forward off")
     assert tr.fuse_table_update and not tr.grads_materialised
     gen = torch.Generator().manual_seed(79)

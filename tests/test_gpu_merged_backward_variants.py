@@ -2,7 +2,7 @@
 ftm_backward_kernel and ftm_backward_bf_kernel) that the shape policy can launch with per-call knobs, at ragged shapes, against
 float64.  GPU tests are marked ``gpu``; the policy test at the top runs without one.
 
-The policy (merged_backward_shape, merged_values_bf6, merged_bf_wm in csrc/ftm_kernels.hip) picks the kernel from the shape alone:
+The policy (merged_backward_plan in csrc/ftm_kernels.hip) picks the kernel from the shape alone:
   big    the two products give >= 448 tiles of 64 x 64: 64 x 64 x 64 tiles for both
   mid    fewer tiles, but the value product alone takes 64-row tiles: 64 x 64 x 64 value tiles, 32-row f32 weight tiles
   small  32 x 64 x 128 value tiles (the batch-512 CIFAR launch; every other test of the merged launch at a ragged shape lands here)
@@ -11,9 +11,7 @@ per call) swap the weight tiles.  ROWS below are the smallest shapes of each cla
 tails on every axis; each names the kernel it must reach under the three knob settings, and test_which_kernel_serves_the_call
 reads that name off the profiler, so a policy change that moves a shape elsewhere fails instead of hollowing the file.
 
-Nine instantiations are reachable this way and all are named in ROWS.  The dispatcher's macro also instantiates
-ftm_backward_bf_kernel<64, 32, 64, 128, true, true> and <32, 32, 64, 128, true>: six-plane values on 32-row value tiles, which
-merged_values_bf6 never asks for (it excludes exactly the shapes that take 32-row value tiles), so no call can launch them.
+Nine instantiations are reachable this way and all are named in ROWS.
 
 Two value regimes per (shape, knob):
   grid    weight and d_out are multiples of 2^-6 in [-1, 1], the map has density 0.3 below the clamp sink and at most 16 active
@@ -66,7 +64,7 @@ ROWS = (
 KNOBS = ("default", "wm32", "f32")
 RIDER_ROWS = (ROWS[3], ROWS[7])
 ROW_ID = lambda row: "x".join(map(str, row[0]))  # noqa: E731
-STATIC_KNOBS = ("NNUE_FTM_SPLIT_BACKWARD", "NNUE_FTM_BWD_PAIR", "NNUE_FTM_BWD_W64", "NNUE_FTM_BWD_BF6", "NNUE_FTM_CFG", "NNUE_FTM_VAL_BF6")
+STATIC_KNOBS = ("NNUE_FTM_SPLIT_BACKWARD",)
 _CASES = {}
 
 

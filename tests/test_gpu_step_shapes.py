@@ -182,8 +182,8 @@ def test_a_step_group_at_the_224_shape_follows_the_oracle(expect_factor_exchange
     assert tr.factor_exchange == expect_factor_exchange and (not expect_factor_exchange or tr.capture_collectives)
     if not tr.fuse_next_forward:
         assert os.environ.get("NNUE_FUSE_NEXT_FORWARD") == "0" or os.environ.get("NNUE_FUSE_TABLE_UPDATE") == "0" \
-            or os.environ.get("NNUE_FT_PATH", "auto") not in ("auto", "mfma") or os.environ.get("NNUE_FTM_BF16") == "0" \
-            or os.environ.get("NNUE_FTM_BF_KT64") == "0", "the 224x224 shape must take the fused pass by default"
+            or os.environ.get("NNUE_FT_PATH", "auto") not in ("auto", "mfma") or os.environ.get("NNUE_FTM_BF16") == "0", \
+            "the 224x224 shape must take the fused pass by default"
         pytest.skip("a knob switched the fused update + next forward off")
     gen = torch.Generator().manual_seed(78)
     bufs, ref_losses = {}, []

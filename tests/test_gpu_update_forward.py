@@ -102,7 +102,7 @@ def test_argument_errors():
     from nnue_hip import lib
     L = lib.load()
     import os
-    if os.environ.get("NNUE_FTM_BF16") == "0" or os.environ.get("NNUE_FTM_BF_KT64") == "0":
+    if os.environ.get("NNUE_FTM_BF16") == "0":
         pytest.skip("a developer knob took the forward off the tiles the fused pass is built on")
     assert L.nnue_ftm_update_forward_supported(128, 128, 65536, 65536, 1024) == 1
     assert L.nnue_ftm_update_forward_supported(1024, 128, 65536, 65536, 1024) == 1  # eight ranks' factors

@@ -60,7 +60,7 @@ def _trainer(monkeypatch, fuse_next, **opt):
     torch.manual_seed(0)
     model = nnue.NNUE(nnue.GridFeatureSet(16, 32), 256, 32, 16, num_classes=10, input_size=64).to(DEV)
     tr = NnueTrainer(model, 64, (64, 64), lr=1e-3, weight_decay=1e-4, max_grad_norm=1.0, input_slots=3, use_graph=True, **opt)
-    if fuse_next == "1" and not tr.fuse_next_forward and (os.environ.get("NNUE_FTM_BF16") == "0" or os.environ.get("NNUE_FTM_BF_KT64") == "0"):
+    if fuse_next == "1" and not tr.fuse_next_forward and os.environ.get("NNUE_FTM_BF16") == "0":
         pytest.skip("a developer knob took the forward off the bf16-split 64-deep tiles the fused pass is built on")
     assert tr.fuse_next_forward == (fuse_next == "1") and not tr.grads_materialised
     gen = torch.Generator().manual_seed(5)

@@ -13,7 +13,7 @@ C2 = (512, 800, 968, 1024, 32, 32, 3)  # B, F, P, L1, H, W, stride
 
 @pytest.fixture(autouse=True)
 def knobs_unset(monkeypatch):
-    for knob in ("NNUE_FTM_VAL_PLANES", "NNUE_FTM_VAL_PLANES_MIN_TILES", "NNUE_FTM_BF16", "NNUE_FTM_BF_WM", "NNUE_FTM_BWD_W64", "NNUE_FTM_CFG"):
+    for knob in ("NNUE_FTM_VAL_PLANES", "NNUE_FTM_VAL_PLANES_MIN_TILES", "NNUE_FTM_BF16", "NNUE_FTM_BF_WM"):
         monkeypatch.delenv(knob, raising=False)
 
 
