@@ -33,7 +33,7 @@ import nnue_oracle as orc
 from conftest import assert_close_grad
 from test_gpu_optim import K, NORM_RTOL, U, assert_within, f32
 from test_gpu_step_shapes import SHAPES as STEP_SHAPES, clean_batch
-from test_gpu_update_forward import SHAPES, _map
+from test_gpu_update_forward import SHAPES, _map, require_fused_pass
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -85,8 +85,7 @@ def test_fused_pass_is_bitwise_its_two_halves(shape, later, wd):
     lib.load()
     b, f, p, l1 = shape[:4]
     bn = shape[4] if len(shape) > 4 else b
-    if not lib.ftm_update_forward_supported(b, f, p, l1, bn):
-        pytest.skip("shape is not a split-K forward over a big table")
+    require_fused_pass(lib, b, f, p, l1, bn)
     gen = torch.Generator().manual_seed(b * 7 + f)
     fm, fm_next = _map(lib, gen, b, p, f, l1), _map(lib, gen, bn, p, f, l1, density=0.3)
     d_out = (torch.randn(b, l1, generator=gen) * 0.05).to(DEV)

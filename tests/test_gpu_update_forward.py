@@ -22,10 +22,22 @@ def _map(lib, gen, b, p, f, l1, density=0.42):
 
 
 # (B, F, P, L1[, B_next]): split-K forward over >= 4096 table rows; ragged batch, table rows that are no multiple of a tile, a
-# clamp sink (P > F - 1), the 224x224 shape itself, and the factor exchange's shapes (B = the all-gathered global batch of 2, 4
-# and 8 ranks: 4, 8, 16 K tiles in the weight-gradient product; B_next = this rank's next batch)
-SHAPES = [(128, 8192, 8192, 256), (100, 9001, 9000, 256), (128, 5000, 8192, 128), (64, 16400, 16400, 192), (128, 65536, 65536, 1024),
-          (256, 8192, 8192, 256, 128), (500, 8192, 8192, 256, 125), (1024, 8192, 8192, 256, 128)]
+# clamp sink (P > F - 1: 7385 positions share table row F - 1), the 224x224 shape itself, the factor exchange's shapes (B = the
+# all-gathered global batch of 2, 4 and 8 ranks: 4, 8, 16 K tiles in the weight-gradient product; B_next = this rank's next
+# batch), and a ragged batch beside the sink
+SHAPES = [(128, 8192, 8192, 256), (100, 9001, 9000, 256), (128, 9000, 16384, 256), (64, 16400, 16400, 192), (128, 65536, 65536, 1024),
+          (256, 8192, 8192, 256, 128), (500, 8192, 8192, 256, 125), (1024, 8192, 8192, 256, 128), (100, 9000, 16384, 256)]
+
+
+def require_fused_pass(lib, b, f, p, l1, bn=None):
+    """Every shape of this file is one the fused pass takes; only a developer knob that moves the products off the bf16-split
+    128-row tiles it is built on (NNUE_FTM_BF16=0, a forced tile height) may say otherwise, and then the test has no subject."""
+    import os
+    if lib.ftm_update_forward_supported(b, f, p, l1, bn):
+        return
+    knob = os.environ.get("NNUE_FTM_BF16") == "0" or os.environ.get("NNUE_FTM_BF_BM") not in (None, "", "0", "128")
+    assert knob, f"nnue_ftm_update_forward_supported says no at {(b, f, p, l1, bn)}: the shape does not reach the fused pass"
+    pytest.skip("a developer knob took the forward off the tiles the fused pass is built on")
 
 
 @pytest.mark.parametrize("shape", SHAPES)
@@ -35,8 +47,7 @@ def test_bitwise_the_two_separate_calls(shape, first, mom):
     lib.load()
     b, f, p, l1 = shape[:4]
     bn = shape[4] if len(shape) > 4 else b
-    if not lib.ftm_update_forward_supported(b, f, p, l1, bn):
-        pytest.skip("shape is not a split-K forward over a big table")
+    require_fused_pass(lib, b, f, p, l1, bn)
     gen = torch.Generator().manual_seed(b * 7 + f)
     fm, fm_next = _map(lib, gen, b, p, f, l1), _map(lib, gen, bn, p, f, l1, density=0.3)
     d_out = (torch.randn(b, l1, generator=gen) * 0.05).to(DEV)
@@ -69,12 +80,21 @@ def test_bitwise_the_two_separate_calls(shape, first, mom):
 
 def test_against_float64():
     """The fused pass against plain float64 arithmetic (not only against its two halves)."""
+    _against_float64(128, 8192, 8192, 256)
+
+
+def test_against_float64_at_a_clamp_sink():
+    """P > F: 7385 positions of the next map share table row F - 1 (nnue.py:701), so the forward's finish adds
+    sink_next * w[F-1] with counts in the thousands; a ragged batch beside it."""
+    _against_float64(128, 9000, 16384, 256)
+    _against_float64(100, 9000, 16384, 256)
+
+
+def _against_float64(b, f, p, l1):
     from conftest import assert_close_grad, assert_close_logits
     from nnue_hip import lib
     lib.load()
-    b, f, p, l1 = 128, 8192, 8192, 256
-    if not lib.ftm_update_forward_supported(b, f, p, l1):
-        pytest.skip("a developer knob took the forward off the tiles the fused pass is built on")
+    require_fused_pass(lib, b, f, p, l1)
     gen = torch.Generator().manual_seed(5)
     fm, fm_next = _map(lib, gen, b, p, f, l1), _map(lib, gen, b, p, f, l1)
     d_out = (torch.randn(b, l1, generator=gen) * 0.05).to(DEV)
@@ -82,7 +102,8 @@ def test_against_float64():
     momentum = (torch.randn(f, l1, generator=gen) * 0.01).to(DEV)
     bias = torch.randn(l1, generator=gen).to(DEV)
     coef, lr, mom, wd, scale = 0.8, 0.05, 0.9, 2e-4, 1.0 / b
-    direct = f - 1
+    direct = min(f - 1, p)
+    assert p == f or int(fm_next.sink.max()) > 1000  # (the sink counts of a clamp-sink map)
     A, An = fm.bits.double(), fm_next.bits.double()
     g = coef * scale * (A[:, :direct].T @ d_out.double()) + wd * weight[:direct].double()
     m64 = mom * momentum[:direct].double() + g
