@@ -86,7 +86,7 @@ int nnue_sparse_values_backward(const float* d_val, const int64_t* idx, int B, i
  * (rows = min(p, F-1), pos = p, coef = 1) and as coefT [F, ldb] (rows < F-1: the bit;
  * row F-1: the number of active ids >= F-1 -- the clamp of nnue.py:701).  Ids are bit-exact
  * given conv_out.  Every element of rows/pos/coef beyond n[b] is left untouched;
- * coefT is fully overwritten for b < B. */
+ * coefT is fully overwritten: its pad columns B <= b < ldb are zero in every row. */
 int nnue_binarize_features(const float* conv_out, const float* thr,
                            int B, int fps, int Gh, int Gw, int F,
                            int32_t* rows, int32_t* pos, float* coef, int32_t* n,

@@ -171,6 +171,9 @@ __global__ __launch_bounds__(256) void binarize_compact_kernel(const float* __re
     n[b] = written;
     coefT[(size_t)(F - 1) * ldb + b] = (float)sink;
   }
+  // the pad columns [B, ldb) of the sink row are zero like those of every other row (the last sample's workgroup writes them)
+  if (b == (int)gridDim.x - 1)
+    for (int j = b + 1 + tid; j < ldb; j += 256) coefT[(size_t)(F - 1) * ldb + j] = 0.0f;
 }
 
 // coefT rows 0..F-2 as a 64x64 LDS-tiled transpose of the bit map: reads are coalesced along the
