@@ -1160,6 +1160,16 @@ def classifier_train_grouped_offsets(b: int, l1: int, l2: int, l3: int, c: int, 
             int(lib.nnue_classifier_train_x_grouped_offset(b, l1, l2, l3, c, buckets)))
 
 
+# the bits of classifier_train_step's ``phases`` (include/nnue_hip.h, nnue_classifier_train_step)
+CLS_PHASE_DX = 1         # activations, per-sample losses and d_x
+CLS_PHASE_SMALL = 2      # the mean loss and the six weight/bias gradients (needs CLS_PHASE_DX on the same scratch)
+CLS_DW1_BESIDE_DX = 4    # the first-layer weight product shares the d_x launch; the CLS_PHASE_SMALL call only sums its slabs
+CLS_L1_SLABS_GIVEN = 8   # the layer-1 slabs are at the start of scratch already (ftm_forward_l1's epilogue)
+CLS_DW1_RIDES = 16       # d_w1 is left to ftm_backward's rider (not with CLS_DW1_BESIDE_DX)
+CLS_SMALL_RIDE = 32      # ... and so are the small gradients and the mean loss (ftm_backward's `small`)
+CLS_TAIL_IN_DX = 64      # the per-sample tail runs inside the d_x launch (only on top of all of 1 | 2 | 8 | 16 | 32)
+
+
 def classifier_train_step(x, pairwise: bool, w1, b1, w2, b2, w3, b3, labels, grad_scale: float = 1.0, clip: float = 0.0,
                           want_dx: bool = True, scratch: Optional[torch.Tensor] = None, out=None, loss_out=None,
                           grads=None, d_x=None, phases: int = 3, buckets: Optional[BucketPlan] = None):

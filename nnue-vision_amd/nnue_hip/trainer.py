@@ -36,7 +36,7 @@ import os
 import torch
 import torch.distributed as dist
 
-from . import lib
+from . import lib, step_mode
 
 SKIP = ("nnue2score",)  # no gradient ever reaches it (reference tests/test_model.py:179-182)
 
@@ -204,45 +204,31 @@ class NnueTrainer:
                 prm.data = self.p[k]
                 prm.grad = self.g[k]
 
-        # ---- static activations and scratch
+        # ---- the step mode: every launch decision, resolved once from shape, optimizer, ranks and knobs (step_mode.py)
         B = self.B
+        # the table rows the product d_W = A^T d_out covers, as a range of the flat buffers
+        tbl_lo = self.layout.offsets[self.layout.names.index("input.weight")]
+        tbl_hi = tbl_lo + min(self.F - 1, self.P) * self.L1
+        m = self.mode = step_mode.resolve(
+            B=B, H=self.H, W=self.W, stride=self.stride, fps=self.fps, F=self.F, L1=self.L1, L2=self.L2, L3=self.L3, C=self.C,
+            K=self.K, optimizer=optimizer, dp=step_mode.DpFacts(self.dp.collectives, self.dp.world, self.dp.buckets, self.dp.backend),
+            use_graph=use_graph, lead_names=self.layout.names[:3], tbl_lo=tbl_lo, tbl_hi=tbl_hi, count=self.layout.count)
+        self.ft_path, self.use_mfma, self.use_bits = m.ft_path, m.ft_path == "mfma", m.ft_path == "bits"
+        self.use_patches, self.fuse_l1, self.fwd_planes = m.use_patches, m.fuse_l1, m.fwd_planes
+        self.merge_backward, self.ride_dw1, self.ride_small, self.fuse_tail_dx = m.merge_backward, m.ride_dw1, m.ride_small, m.fuse_tail_dx
+        self.defer_ste, self.ride_ste, self.ste_chunks = m.defer_ste, m.ride_ste, m.ste_chunks
+        self.fuse_table_update, self.fuse_next_forward, self.grads_materialised = m.fuse_table_update, m.fuse_next_forward, m.grads_materialised
+        self.factor_exchange, self.sharded_update, self.sq_range = m.factor_exchange, m.sharded_update, m.sq_range
+        self.capture_collectives = m.capture_collectives  # (cleared when a capture fails)
+
+        # ---- static activations and scratch, allocated from the mode
         # input ring: a loader fills slot k while slot k-1 trains; kernels read the slots in place
         self.inputs = [(torch.empty((B, 3, self.H, self.W), **f32), torch.empty((B,), dtype=torch.int64, device=self.dev))
                        for _ in range(max(1, input_slots))]
         self.images, self.labels = self.inputs[0]
         self.conv_out = torch.empty((B, self.fps, self.gh, self.gw), **f32)
-        self.patches = None  # (set below for the product form at large strides)
-        # binary features: float {0,1} map + dense MFMA products when the shape allows, else bit masks + LDS-staged
-        # gather kernels, else id lists
-        self.ft_path = lib.ft_path(self.F, self.P, self.L1, B)
-        self.use_mfma, self.use_bits = self.ft_path == "mfma", self.ft_path == "bits"
         self.fm = lib.FeatureMatrix.empty(B, self.P, self.F, self.L1, self.dev) if self.use_mfma else None
-        # Large strides (the taps of neighbouring positions do not overlap: 224x224 at stride 7 reads 3 of every 7 rows and the
-        # backward would gather them again): the conv launch also leaves the im2col form of the images -- 27 floats per position,
-        # 0.18 of the image bytes -- and the STE backward reads the patches instead of the images (bitwise).
-        # NNUE_CONV_PATCHES=0|1|auto (auto: images more than twice their patches).
-        pm = os.environ.get("NNUE_CONV_PATCHES", "auto")
-        self.use_patches = (self.use_mfma and self.fps <= 64 and pm != "0"
-                            and (pm == "1" or 3 * self.H * self.W > 2 * 27 * self.gh * self.gw))
-        if self.use_patches:
-            self.patches = torch.empty((27, B * self.gh * self.gw), **f32)
-        # Data parallel with a bandwidth-sized table: the ranks all-gather the FACTORS of the table's gradient (the map as
-        # bits + d_ft, ~1.5 MB per rank at the 224x224 shape) instead of reducing the 269 MB product, and every rank runs the
-        # fused single-rank path (Gram norm, update in the product's epilogue) on the global factors: no big collective, no
-        # materialised d_W, bitwise identical replicas.  The other gradients travel in the same all-gather and are summed in
-        # rank order (lib.FactorExchange).  NNUE_DP_FACTOR_EXCHANGE=auto|1|0; auto = tables of 32 MB or more.
-        fx_mode = os.environ.get("NNUE_DP_FACTOR_EXCHANGE", "auto")
-        # the table rows the product d_W = A^T d_out covers, as a range of the flat buffers; every form that leaves those rows to
-        # the product's launch (their sums of squares, their update) needs the range non-empty and float4-aligned
-        tbl_lo = self.layout.offsets[self.layout.names.index("input.weight")]
-        tbl_hi = tbl_lo + min(self.F - 1, self.P) * self.L1
-        tbl_ok = tbl_hi > tbl_lo and tbl_lo % 4 == 0 and tbl_hi % 4 == 0
-        big_table = self.F * self.L1 * 4 >= (32 << 20)
-        gb = B * self.dp.world
-        self.factor_exchange = (self.dp.collectives and self.use_mfma and optimizer == "sgd" and self.dp.buckets == 1 and tbl_ok
-                                and self.layout.names[:3] == ["visual_threshold", "conv.weight", "input.weight"]
-                                and gb * self.L1 <= (1 << 24) and ((gb + 15) // 16) * ((self.L1 + 15) // 16) <= 65536
-                                and fx_mode != "0" and (fx_mode == "1" or big_table))
+        self.patches = torch.empty((27, B * self.gh * self.gw), **f32) if self.use_patches else None  # the images' im2col form
         self.fx = None
         if self.factor_exchange:
             self.fx = lib.FactorExchange(self.dp.world, self.dp.rank, B, self.P, self.F, self.L1, head=tbl_lo, tail_lo=tbl_hi,
@@ -265,38 +251,17 @@ class NnueTrainer:
         self.cls_scratch = torch.empty((max(lib.classifier_scratch_bytes(B, self.L1, self.L2, self.L3, self.K),
                                             lib.classifier_train_scratch_bytes(B, self.L1, self.L2, self.L3, self.C, self.K)),), **u8)
         self.bucket_plan = lib.BucketPlan(B, self.K, self.dev) if self.K > 1 else None
-        self.ste_scratch = torch.empty((max(16, lib.load().nnue_ste_conv_backward_scratch(B, self.fps, self.gh, self.gw)),), **u8)
+        # the STE launch's own scratch, or the partials the merged backward's ride leaves (fps * 28 outputs, float)
+        self.ste_scratch = torch.empty((max(16, lib.load().nnue_ste_conv_backward_scratch(B, self.fps, self.gh, self.gw),
+                                            self.fps * 28 * self.ste_chunks * 4 if self.ride_ste else 0),), **u8)
         self.sgd_scratch = torch.empty((lib.sgd_scratch_bytes(self.layout.count),), **u8)
-        # single rank + SGD: the second stage of the STE / conv-weight gradient sum rides in the optimizer's norm launch
-        # (with collectives the gradients must be complete before the all-reduce)
-        self.defer_ste = (not self.dp.collectives and optimizer == "sgd" and os.environ.get("NNUE_DEFER_STE", "1") != "0"
-                          and self.fps * 28 <= 4096 and self.layout.names[:2] == ["visual_threshold", "conv.weight"])
-        self.ste_chunks = lib.ste_conv_backward_chunks(B, self.fps, self.gh, self.gw)
-        # K > 1: the first layer's weights differ per sample, so its product is the classifier's own grouped launch
-        # (bucket-homogeneous MFMA tiles) instead of the FeatureTransformer forward's epilogue / backward rider
-        self.fuse_l1 = (self.K == 1 and self.use_mfma and os.environ.get("NNUE_FUSE_L1", "1") != "0"
-                        and lib.ftm_forward_l1_supported(B, self.F, self.P, self.L1, self.L2))
-        # Where that forward runs 32-row tiles (the CIFAR batch-512 shape), the conv launch's rider workgroups leave the table as
-        # pre-split bf16 planes once per step and the forward reads those on the bf16 matrix unit (nnue_ftm_conv_binarize_planes
-        # -> nnue_ftm_forward_l1_planes) instead of the table on the f32 one.  NNUE_FTM_FWD_PLANES=0 keeps the two plain calls.
-        self.fwd_planes = (self.fuse_l1 and not self.use_patches and os.environ.get("NNUE_FTM_FWD_PLANES", "1") != "0"
-                           and lib.ftm_forward_l1_planes_supported(B, self.F, self.P, self.L1, self.L2))
         self.planes = (torch.empty((lib.ftm_forward_planes_bytes(B, self.F, self.P, self.L1),), **u8) if self.fwd_planes else None)
-        # Sharded update for bandwidth-sized flat buffers under collectives (SGD): reduce-scatter, per-shard clip + SGD with
-        # the norm assembled from all-gathered block partials, all-gather of the parameters.  NNUE_DP_SHARDED_UPDATE=0|1|auto
-        mode = os.environ.get("NNUE_DP_SHARDED_UPDATE", "auto")
-        self.sharded_update = (self.dp.collectives and optimizer == "sgd" and self.dp.buckets == 1 and mode != "0"
-                               and not self.factor_exchange and (mode == "1" or self.layout.count * 4 >= (64 << 20)))
         if self.sharded_update:
             per = self.layout.count // self.dp.world
             self.grad_shard = torch.empty((per,), **f32)
             self.norm_parts = 256
             self.local_partials = torch.empty((self.norm_parts,), **f32)
             self.all_partials = torch.empty((self.norm_parts * self.dp.world,), **f32)
-        # the collective(s) captured into the step graph (torch's NCCL path is capturable): one replay per step, no host
-        # round trip between the local kernels, the exchange and the update.  NNUE_DP_CAPTURE=0 keeps the eager collective.
-        self.capture_collectives = (self.dp.collectives and use_graph and self.dp.backend == "nccl" and self.dp.buckets == 1
-                                    and os.environ.get("NNUE_DP_CAPTURE", "1") != "0")
         # the learning rate lives in a device scalar the optimizer kernels read: ``trainer.lr = x`` (a scheduler's hook) is one
         # tiny fill, the recorded plans and captured graphs stay valid (the other hyper-parameters are constants of the plans)
         self.lr_dev = torch.full((1,), float(lr), **f32)
@@ -306,72 +271,19 @@ class NnueTrainer:
         self._plan_local = self._plan_seg = self._plan_update_first = self._plan_update = None
         self._plan_slot = 0
         self._side = torch.cuda.Stream(device=self.dev) if use_graph else None
-        self.merge_backward = os.environ.get("NNUE_FTM_SPLIT_BACKWARD", "0") != "1"
-        # the classifier's first-layer weight gradient rides in the merged FeatureTransformer backward launch (a third
-        # tile family reading d_z1 out of the classifier's scratch) where that launch is used
-        self.ride_dw1 = (self.use_mfma and self.merge_backward and os.environ.get("NNUE_FTM_RIDE_DW1", "1") != "0"
-                         and lib.ftm_backward_cw_supported(B, self.F, self.P, self.L1, self.L2))
-        # Big tables on a single rank (SGD or Adam): the FeatureTransformer weight gradient is never materialised.  Its squared
-        # norm comes from two B x B Gram matrices (nnue_ftm_gram_sqnorm), the optimizer's norm/apply pass skips those rows
-        # and leaves the clip coefficient in a device scalar, and the product d_W = A^T d_out runs LAST, applying the update
-        # to the table (Adam: and to its two moments) in its epilogue (nnue_ftm_backward_weight_update[_adam]): no 268 MB write
-        # + read at the 224x224 shape.
-        want = os.environ.get("NNUE_FUSE_TABLE_UPDATE", "auto")
-        self.fuse_table_update = (self.use_mfma and not self.dp.collectives and tbl_ok and B * self.L1 <= (1 << 24) and want != "0"
-                                  and (big_table or want == "1"))
-        # With the fused table update ``model.input.weight.grad`` (a view of flat_grads) is never written: rows the product
-        # covers stay at the zeros they were allocated with.  ``grads_materialised`` says so; callers that want the table's
-        # gradient for logging or custom clipping set NNUE_FUSE_TABLE_UPDATE=0.
-        self.grads_materialised = not (self.fuse_table_update or self.factor_exchange)
-        # sq_partial: the sums of squares of the table's share (flat_grads[sq_range]) of the clip norm, left by its producer
-        self.sq_partial = self.sq_range = self.gram = self.clip_coef = None
-        n_sq = lib.ftm_backward_sq_count(B, self.F, self.P, self.L1) if (self.use_mfma and self.merge_backward) else 0
-        if not self.grads_materialised:  # the Gram form; under the factor exchange on the global factors (B * world rows)
-            self.ride_dw1 = False  # the rider lives in the merged launch, which this path does not use
-            self.sq_partial = torch.empty((int(lib.load().nnue_ftm_gram_sq_count(gb, self.L1)),), **f32)
-            self.sq_range = (tbl_lo, tbl_hi)
+        # sq_partial: the sums of squares of the table's share (flat_grads[sq_range]) of the clip norm, left by its producer;
+        # the Gram form (m.sq == "gram") also takes its scratch and leaves the clip coefficient for the table's update
+        self.sq_partial = torch.empty((m.sq_count,), **f32) if m.sq != "none" else None
+        self.gram = self.clip_coef = None
+        if m.sq == "gram":
             self.gram = torch.zeros((lib.ftm_gram_scratch(self.fx.g_fm if self.factor_exchange else self.fm),), **f32)
             self.clip_coef = torch.ones((), **f32)
-        elif n_sq > 0 and not self.dp.collectives and optimizer == "sgd" and tbl_ok and os.environ.get("NNUE_NORM_PARTIALS", "1") != "0":
-            # single rank + SGD: the FT weight-gradient tiles leave their sums of squares, so the clip norm does not read
-            # those rows of the flat gradient buffer again (268 MB at the 224x224 configuration)
-            self.sq_partial = torch.empty((n_sq,), **f32)
-            self.sq_range = (tbl_lo, tbl_hi)
-        # Single rank + SGD with the merged FeatureTransformer backward: its value-gradient tiles also reduce d_conv_out into the
-        # STE partials (stage 1 of ste_conv_backward) in their epilogue, so the STE launch disappears and d_conv_out is not
-        # stored; the second stage stays in the norm launch.  With the im2col patches the epilogue reads them instead of the images
-        # (the same bits, as the STE kernel's two forms).  NNUE_FTM_RIDE_STE=0 keeps the STE launch.
-        ste_chunks = lib.ftm_backward_ste_chunks(B, self.F, self.P, self.L1, self.H, self.W, self.stride) if self.use_mfma else 0
-        self.ride_ste = (self.defer_ste and self.merge_backward and not self.fuse_table_update
-                         and not self.factor_exchange and ste_chunks > 0 and os.environ.get("NNUE_FTM_RIDE_STE", "1") != "0")
-        if self.ride_ste:
-            self.ste_chunks = ste_chunks
-            need = self.fps * 28 * ste_chunks * 4
-            if self.ste_scratch.numel() < need:
-                self.ste_scratch = torch.empty((need,), **u8)
-        # Where the ride runs 32-row value tiles on a chip-filling launch (the CIFAR batch-512 shape, where the forward takes its
-        # planes too), the conv launch's riders also leave the table rows the value gradient reads as bf16 planes, and the merged
-        # backward's value tiles read those on the bf16 matrix unit (nnue_ftm_conv_binarize_value_planes ->
-        # nnue_ftm_backward_planes).  Written by a step's conv launch and read by that step's backward only: the table is updated
-        # after it.  NNUE_FTM_VAL_PLANES=0 keeps the f32 tiles.
-        self.val_planes = None
-        if (self.ride_ste and not self.use_patches and self.bucket_plan is None
-                and lib.ftm_value_planes_supported(B, self.F, self.P, self.L1, self.H, self.W, self.stride)):
-            self.val_planes = torch.empty((lib.ftm_value_planes_bytes(B, self.F, self.P, self.L1),), **u8)
-        # Inside a step group (step_many) the table's update of step t and the FeatureTransformer forward of step t+1 are ONE
-        # pass over the table (nnue_ftm_backward_weight_update_forward: the next batch is resident, its map only needs the conv
-        # weights the small tensors' update has just written, and the update leaves every new table tile in registers) -- the
-        # forward's own 268 MB read of the table disappears.  Two maps alternate (the update still reads step t's while step
-        # t+1's is being written).  Bitwise the separate kernels.  NNUE_FUSE_NEXT_FORWARD=0 keeps them separate.
-        # (Under the factor exchange the update contracts the all-gathered GLOBAL batch, the next forward this rank's own next map.)
-        self.fuse_next_forward = ((self.fuse_table_update or self.factor_exchange) and not self.fuse_l1 and self.K == 1
-                                  and os.environ.get("NNUE_FUSE_NEXT_FORWARD", "1") != "0"
-                                  and lib.ftm_update_forward_supported(gb if self.factor_exchange else B, self.F, self.P, self.L1, B))
+        self.val_planes = torch.empty((lib.ftm_value_planes_bytes(B, self.F, self.P, self.L1),), **u8) if m.val_planes else None
         self.fm_alt = lib.FeatureMatrix.empty(B, self.P, self.F, self.L1, self.dev) if self.fuse_next_forward else None
         if self.fm_alt is not None and self.fx is not None:
             self.fm_alt.sink = self.fx.sink  # (both local maps' sink counts live in this rank's chunk: only one of them is live at a time)
         self._last_alt = False  # the last step's map is the second one (an even-length step group)
-        self.d_z1 = self.ft_rider = None
+        self.d_z1 = self.ft_rider = None  # the operands of the merged backward's d_w1 rider, out of the classifier's scratch
         if self.ride_dw1 and self.K == 1:
             off = lib.classifier_train_dz1_offset(B, self.L1, self.L2, self.L3, self.C, True)
             self.d_z1 = self.cls_scratch[off:off + B * self.L2 * 4].view(torch.float32).view(B, self.L2)
@@ -383,13 +295,6 @@ class NnueTrainer:
             o_dz, o_x = lib.classifier_train_grouped_offsets(B, self.L1, self.L2, self.L3, self.C, self.K)
             self.d_z1 = self.cls_scratch[o_dz:o_dz + rows * self.L2 * 4].view(torch.float32).view(rows, self.L2)
             self.ft_rider = self.cls_scratch[o_x:o_x + rows * self.L1 * 4].view(torch.float32).view(rows, self.L1)
-        # ... and so do the classifier's small gradients + mean loss (one more tile family of that launch; the classifier's d_x
-        # launch then holds only d_x tiles).  NNUE_CLS_RIDE_SMALL=0 keeps them beside d_x.
-        self.ride_small = self.ride_dw1 and os.environ.get("NNUE_CLS_RIDE_SMALL", "1") != "0"
-        # ... and then the classifier's per-sample tail runs inside its d_x launch (phases 123: each d_x row tile recomputes the
-        # tail of its own 16 rows; bitwise the two launches).  NNUE_CLS_FUSE_TAIL_DX=0 keeps the two launches.
-        self.fuse_tail_dx = (self.fuse_l1 and self.ride_small and os.environ.get("NNUE_CLS_FUSE_TAIL_DX", "1") != "0"
-                             and lib.classifier_train_fused_tail_supported(B, self.L1, self.L2, self.L3, self.C, self.K))
         self._riders = {}  # mean-loss destination -> host struct (kept alive: recorded plans hold pointers to them)
 
     # ------------------------------------------------------------------ hyper-parameters
@@ -458,7 +363,7 @@ class NnueTrainer:
     def _segment(self, name: str) -> None:
         p, g = self.p, self.g
         if name == "front":
-            if self.fwd_planes or self.val_planes is not None:  # conv + {0,1} map + counts, and the table's bf16 planes from the same launch's riders
+            if self.mode.conv_planes:  # conv + {0,1} map + counts, and the table's bf16 planes from the same launch's riders
                 lib.ftm_conv_binarize_planes(self.images, p["conv.weight"], p["visual_threshold"], self.stride, p["input.weight"], self.L2,
                                              self.planes, conv_out=self.conv_out, fm=self.fm, val_planes=self.val_planes)
                 return
@@ -479,7 +384,7 @@ class NnueTrainer:
                 feats = self.bits if self.use_bits else self.act
                 lib.bucket_group(feats.n, self.P, self.K, plan=self.bucket_plan)
             # (product form: the grouping rides in the FeatureTransformer forward launch as one extra workgroup)
-            if self.use_mfma and self.fuse_l1:
+            if self.fuse_l1:
                 # the forward's epilogue also forms the classifier's layer-1 slabs (start of its scratch)
                 if self.fwd_planes:
                     lib.ftm_forward_l1_planes(p["input.weight"], p["input.bias"], self.fm, self.planes, p["classifier.classifier.0.weight"],
@@ -487,8 +392,7 @@ class NnueTrainer:
                 else:
                     lib.ftm_forward_l1(p["input.weight"], p["input.bias"], self.fm, p["classifier.classifier.0.weight"], self.cls_scratch,
                                        out=self.ft)
-                # 27: both phases, d_w1 left to the merged backward; + 32: the small gradients too; + 64: the tail in the d_x launch
-                self._cls_step((123 if self.fuse_tail_dx else 59 if self.ride_small else 27) if self.ride_dw1 else 13)
+                self._cls_step(self.mode.phases)
                 return
             if self.use_mfma:
                 lib.ftm_forward(p["input.weight"], p["input.bias"], self.fm, out=self.ft, group=self.bucket_plan)
@@ -496,7 +400,7 @@ class NnueTrainer:
                 lib.ftb_forward(p["input.weight"], p["input.bias"], self.bits, out=self.ft)
             else:
                 lib.ft_forward(p["input.weight"], p["input.bias"], self.act, out=self.ft)
-            self._cls_step((51 if self.ride_small else 19) if self.ride_dw1 else 5)  # 5: + the first-layer weight product beside d_x
+            self._cls_step(self.mode.phases)
         elif name == "ft_wgrad":
             if self.factor_exchange:
                 # this rank's share of the rows the product does not cover; they travel with the small gradients, the
@@ -507,7 +411,7 @@ class NnueTrainer:
                 # the product itself is part of the update (_update)
                 # (the tail rows' workgroups ride in the Gram product's launch)
                 lib.ftm_gram_sqnorm(self.fm, self.d_ft, self.gram, self.sq_partial, tail=(g["input.weight"], g["input.bias"]))
-            elif self.use_mfma and self.merge_backward:
+            elif self.mode.merged_backward_launch:
                 # weight gradient, value gradient and tail rows share one launch (independent work, all read d_ft)
                 lib.ftm_backward(self.d_ft, p["input.weight"], self.fm, d_weight=g["input.weight"], d_bias=g["input.bias"],
                                  dst=None if self.ride_ste else self.d_conv_out, ft=self.ft_rider, d_z1=self.d_z1,
@@ -523,9 +427,9 @@ class NnueTrainer:
                 lib.ft_backward_weight(self.d_ft, self.act, self.F, d_weight=g["input.weight"], d_bias=g["input.bias"])
         elif name == "cls_wgrad":
             if not self.ride_dw1:  # else the small gradients already rode in the d_x launch of "forward"
-                self._cls_step(6)
+                self._cls_step(lib.CLS_PHASE_SMALL | lib.CLS_DW1_BESIDE_DX)
         elif name == "tail":
-            if self.use_mfma and self.merge_backward and not self.fuse_table_update and not self.factor_exchange:
+            if self.mode.merged_backward_launch:
                 pass  # d_conv_out came out of the merged launch in "ft_wgrad"
             elif self.use_mfma:
                 lib.ftm_backward_values(self.d_ft, p["input.weight"], self.fm, dst=self.d_conv_out)
@@ -538,11 +442,11 @@ class NnueTrainer:
             if self.use_patches:
                 lib.ste_conv_backward_patches(self.patches, self.conv_out, p["visual_threshold"], self.d_conv_out, self.gh, self.gw,
                                               d_thr=g["visual_threshold"], d_weight=g["conv.weight"], scratch=self.ste_scratch,
-                                              stages=1 if self.defer_ste else 3)
+                                              stages=self.mode.ste_stages)
             else:
                 lib.ste_conv_backward(self.images, self.conv_out, p["visual_threshold"], self.d_conv_out, self.stride,
                                       d_thr=g["visual_threshold"], d_weight=g["conv.weight"], scratch=self.ste_scratch,
-                                      stages=1 if self.defer_ste else 3)
+                                      stages=self.mode.ste_stages)
         else:
             raise KeyError(name)
 
@@ -559,8 +463,8 @@ class NnueTrainer:
         """The optimizer's launch on the flat buffers: clip norm + update of every tensor.  Where the table's gradient is never
         materialised (fuse_table_update, factor_exchange) it takes the table's share of the norm from the Gram partials, leaves
         the table's rows alone and the clip coefficient in ``clip_coef`` for _table_update."""
-        ext = (self.sq_partial, *self.sq_range) if self.sq_partial is not None else None
-        elsewhere = not self.grads_materialised
+        ext = (self.sq_partial, *self.sq_range) if self.mode.sq != "none" else None
+        elsewhere = self.mode.sq == "gram"
         if self.optimizer == "adam":
             lib.adam_step(self.flat_params, self.flat_grads, self.flat_exp_avg, self.flat_exp_avg_sq, self.adam_step_count,
                           self.lr, self.betas, self.eps, self.weight_decay, self.max_grad_norm, scale, self.grad_norm,
@@ -893,7 +797,7 @@ class NnueTrainer:
 
     def _group_fuses(self, slots) -> bool:
         """In a group on `slots` the table update of every step but the last also forms the next step's forward."""
-        return self.fuse_next_forward and len(slots) > 1 and (not self.dp.collectives or self.factor_exchange)
+        return self.fuse_next_forward and len(slots) > 1  # (the mode has it only on a single rank or under the factor exchange)
 
     def _ends_on_alt(self, slots) -> bool:
         """The last step of a group on `slots` leaves its map in the second one (the maps alternate within a fused group)."""

@@ -1,12 +1,14 @@
-"""The mode table of tests/trainer_modes.py, settled without a GPU: the library's launch-free queries (lib.ft_path,
-nnue_ftm_forward_l1_supported, ..._l1_planes_supported, ..._backward_cw_supported, ..._backward_ste_chunks,
-..._value_planes_supported, ..._update_forward_supported, nnue_classifier_train_fused_tail_supported,
-nnue_ftm_backward_sq_count) answer for every row as the table says, and the table as a whole covers every flag in both
-values, every phase mask and every combination it was written for.  tests/test_gpu_trainer_modes.py then holds the live
-trainer to the same table and each row's step to the oracle."""
+"""The mode table of tests/trainer_modes.py, settled without a GPU: the trainer's own resolver (nnue_hip.step_mode.resolve,
+over the library's launch-free queries) answers for every row as the table says, and the table as a whole covers every flag in
+both values, every phase mask and every combination it was written for.  The data-parallel decisions, which the table's
+single-rank rows do not reach, have their own table here.  tests/test_gpu_trainer_modes.py then holds the live trainer to the
+same table and each row's step to the oracle."""
 import pytest
 
-from trainer_modes import A_MODES, FLAGS, PHASES, ROWS, ROW_NAMES, BY_NAME, differences, geometry, launches_of, resolve, set_knobs
+from nnue_hip import lib
+from nnue_hip.step_mode import DpFacts
+from trainer_modes import A, A_MODES, FLAGS, PHASES, ROWS, ROW_NAMES, BY_NAME, Row, build_model, differences, geometry, launches_of, \
+    resolve, set_knobs, step_mode_of, LEAD
 
 
 @pytest.mark.parametrize("name", ROW_NAMES)
@@ -23,7 +25,6 @@ def test_the_bf16_products_are_on_by_default(monkeypatch):
     """What the big-table rows were chosen for rests on the bf16-split tiles (nnue_ftm_uses_bf16; NNUE_FTM_BF16 is read per
     call): the split-K forward and the update in the weight gradient's epilogue at the 8192-row table, the six-plane
     stand-alone value gradient at the 16384-row one."""
-    from nnue_hip import lib
     uses = lib.load().nnue_ftm_uses_bf16
     set_knobs(monkeypatch, BY_NAME["t8192_ftu"])
     small, big = BY_NAME["t8192_ftu"].config, BY_NAME["t16384_b160"].config
@@ -125,3 +126,86 @@ def test_the_launch_list_follows_the_mode():
         "nnue_ftm_conv_binarize", "nnue_ftm_forward", "nnue_classifier_train_step", "nnue_ftm_gram_sqnorm_tail",
         "nnue_classifier_train_step", "nnue_ftm_backward_values_ws", "nnue_ste_conv_backward", "nnue_adam_step_ext",
         "nnue_ftm_backward_weight_update_adam"]
+
+
+def test_geometry_is_the_flat_layouts():
+    """geometry's restatement of the table's range of the flat buffers against FlatLayout.of on each row's model (CPU)."""
+    from nnue_hip.trainer import FlatLayout
+    for cfg in {tuple(sorted((k, row.config[k]) for k in ("grid", "fps", "image", "l1", "l2", "l3", "classes", "K"))) for row in ROWS}:
+        cfg = {**A, **dict(cfg)}
+        g, layout = geometry(cfg), FlatLayout.of(build_model(cfg))
+        assert layout.names[:3] == LEAD
+        lo = layout.offsets[2]
+        assert (g["tbl_lo"], g["tbl_hi"]) == (lo, lo + min(g["F"] - 1, g["P"]) * cfg["l1"]), cfg
+        assert layout.shapes[2] == (g["F"], cfg["l1"]) and layout.count >= g["tbl_hi"]
+
+
+def test_the_phase_bits_compose_the_masks_the_library_takes():
+    dx, small, beside, slabs = lib.CLS_PHASE_DX, lib.CLS_PHASE_SMALL, lib.CLS_DW1_BESIDE_DX, lib.CLS_L1_SLABS_GIVEN
+    rides, small_ride, tail = lib.CLS_DW1_RIDES, lib.CLS_SMALL_RIDE, lib.CLS_TAIL_IN_DX
+    assert (dx, small, beside, slabs, rides, small_ride, tail) == (1, 2, 4, 8, 16, 32, 64)
+    assert dx | beside == 5 and small | beside == 6 and dx | beside | slabs == 13
+    assert dx | small | rides == 19 and dx | small | rides | slabs == 27
+    assert dx | small | rides | small_ride == 51 and dx | small | rides | small_ride | slabs == 59
+    assert dx | small | rides | small_ride | slabs | tail == 123
+
+
+# ---- data parallel: what NnueTrainer decides from DataParallel's facts (collectives, world, buckets, backend), as rows of
+# (name, configuration over A, knobs, arguments of step_mode_of, what the StepMode must say)
+BIG = dict(grid=32, fps=32, image=96, batch=64)  # a 32768 x 256 table: 32 MB, where the factor exchange turns itself on
+NO_FX = {"NNUE_DP_FACTOR_EXCHANGE": "0"}
+ALL_REDUCE = dict(factor_exchange=False, sharded_update=False, grads_materialised=True, sq="none", sq_range=None, sq_count=0)
+
+
+def ranks(world=2, buckets=1, backend="nccl"):
+    return DpFacts(True, world, buckets, backend)
+
+
+DP_ROWS = (
+    ("A: one all-reduce, complete gradients before it", {}, {}, dict(dp=ranks()),
+     dict(ALL_REDUCE, defer_ste=False, ride_ste=False, fuse_table_update=False, ste_stages=3, capture_collectives=True,
+          ride_dw1=True, ride_small=True, fuse_l1=True, phases=59, merged_backward_launch=True)),
+    ("A on one rank with the collectives forced", {}, {}, dict(dp=ranks(world=1)),
+     dict(ALL_REDUCE, defer_ste=False, ride_ste=False, fuse_table_update=False, ste_stages=3, capture_collectives=True)),
+    ("big table: the factor exchange", BIG, {}, dict(dp=ranks()),
+     dict(factor_exchange=True, sharded_update=False, grads_materialised=False, sq="gram", ride_dw1=False, ride_small=False,
+          fuse_table_update=False, merged_backward_launch=False, defer_ste=False, ride_ste=False, ste_stages=3,
+          capture_collectives=True)),
+    ("big table, the exchange forced at a small one", {}, {"NNUE_DP_FACTOR_EXCHANGE": "1"}, dict(dp=ranks()),
+     dict(factor_exchange=True, grads_materialised=False, sq="gram", ride_dw1=False, phases=13)),
+    ("big table without the exchange, flat buffers of 64 MB: the sharded update", BIG, NO_FX, dict(dp=ranks(), count=16 << 20),
+     dict(ALL_REDUCE, sharded_update=True)),
+    ("big table without the exchange, flat buffers below 64 MB", BIG, NO_FX, dict(dp=ranks(), count=(16 << 20) - 4), ALL_REDUCE),
+    ("small buffers, the sharded update forced", {}, {"NNUE_DP_SHARDED_UPDATE": "1"}, dict(dp=ranks()), dict(ALL_REDUCE, sharded_update=True)),
+    ("big table and buffers, the sharded update refused", BIG, {**NO_FX, "NNUE_DP_SHARDED_UPDATE": "0"}, dict(dp=ranks(), count=16 << 20),
+     ALL_REDUCE),
+    ("two buckets: neither exchange nor shards nor capture", BIG, {}, dict(dp=ranks(buckets=2), count=16 << 20),
+     dict(ALL_REDUCE, capture_collectives=False)),
+    ("gloo: the collective stays eager", {}, {}, dict(dp=ranks(backend="gloo")), dict(ALL_REDUCE, capture_collectives=False)),
+    ("no graphs: the collective stays eager", {}, {}, dict(dp=ranks(), use_graph=False), dict(ALL_REDUCE, capture_collectives=False)),
+    ("NNUE_DP_CAPTURE=0", {}, {"NNUE_DP_CAPTURE": "0"}, dict(dp=ranks()), dict(ALL_REDUCE, capture_collectives=False)),
+    ("Adam at the big table: no exchange, no shards", dict(BIG, optimizer="adam"), {}, dict(dp=ranks(), count=16 << 20), ALL_REDUCE),
+)
+
+
+@pytest.mark.parametrize("what,cfg,env,args,expect", DP_ROWS, ids=[r[0] for r in DP_ROWS])
+def test_the_data_parallel_decisions(what, cfg, env, args, expect, monkeypatch):
+    cfg = {**A, **cfg}
+    set_knobs(monkeypatch, Row(what, env=env))
+    sm = step_mode_of(cfg, **args)
+    assert sm.ft_path == "mfma"
+    wrong = differences({k: getattr(sm, k) for k in expect}, expect)
+    assert not wrong, f"{what}: " + "; ".join(wrong) + f" ({sm.describe()})"
+    if sm.sq == "gram":  # the norm's Gram product contracts the GLOBAL batch
+        g = geometry(cfg)
+        assert sm.sq_range == (g["tbl_lo"], g["tbl_hi"])
+        assert sm.sq_count == int(lib.load().nnue_ftm_gram_sq_count(cfg["batch"] * args["dp"].world, cfg["l1"]))
+    assert sm.phases in PHASES
+
+
+def test_describe_is_the_row_of_the_record(monkeypatch):
+    set_knobs(monkeypatch, BY_NAME["A"])
+    assert step_mode_of(BY_NAME["A"].config).describe() == \
+        "mfma | defer_ste, fuse_l1, ride_dw1, ride_ste, ride_small | sq tiles | phases 59 | STE ride, 112 chunks"
+    set_knobs(monkeypatch, BY_NAME["g5_bits"])
+    assert step_mode_of(BY_NAME["g5_bits"].config).describe() == "bits | defer_ste | sq none | phases 5 | STE stages=1"

@@ -1,7 +1,7 @@
-"""The step modes NnueTrainer resolves to (nnue_hip/trainer.py: __init__, _segment, _small_update, _table_update), as a table of
+"""The step modes NnueTrainer resolves to (nnue_hip/step_mode.py::resolve, consumed by nnue_hip/trainer.py), as a table of
 named configurations with the mode each one must take, and the driver that holds a whole optimizer step in that mode to the
 float64 oracle (oracle.loss_and_grads_explicit + oracle.sgd_step / oracle.adam_step).  A helper, not a test module:
-tests/test_trainer_modes_policy.py settles the table from the launch-free queries on any machine,
+tests/test_trainer_modes_policy.py holds the trainer's own resolver to the table on any machine (it is launch-free),
 tests/test_gpu_trainer_modes.py runs every row on the GPU.
 
 A mode is the dict ``A_MODES`` shows: the trainer's flags, where the table's share of the clip norm comes from (``sq``: the
@@ -13,7 +13,6 @@ NNUE_FTM_SPLIT_BACKWARD and NNUE_FTM_RIDE_STE_V64 are read once per process by t
 test process: ``merge_backward`` is part of the mode but takes one value only.
 """
 import contextlib
-import os
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Tuple
 
@@ -144,7 +143,7 @@ def set_knobs(monkeypatch, row: Row) -> None:
         monkeypatch.setenv(k, v)
 
 
-# ------------------------------------------------------------------------------------------------ the resolution, restated
+# ------------------------------------------------------------------------------------------------ the resolution
 def geometry(cfg: Dict) -> Dict:
     """Shapes as nnue.NNUE and the trainer derive them: stride, map side, positions P, table rows F, table range of the flat
     buffers (FlatLayout.of: visual_threshold, conv.weight, input.weight, ... each padded to four floats)."""
@@ -156,51 +155,27 @@ def geometry(cfg: Dict) -> Dict:
     return dict(stride=stride, side=side, P=p, F=f, tbl_lo=lo, tbl_hi=hi)
 
 
-def resolve(cfg: Dict) -> Dict:
-    """The mode a single-rank trainer of this configuration takes under the current environment, from the launch-free
-    queries alone (no GPU): NnueTrainer.__init__ and the phase / stage choices of _segment, restated."""
-    from nnue_hip import lib
-    env = os.environ.get
-    on = lambda k: env(k, "1") != "0"  # noqa: E731
+LEAD = ["visual_threshold", "conv.weight", "input.weight"]  # FlatLayout.of's first names (test_geometry_is_the_flat_layouts)
+
+
+def step_mode_of(cfg: Dict, dp=None, use_graph: bool = True, count: Optional[int] = None):
+    """nnue_hip.step_mode.resolve -- the policy the trainer itself uses -- at this configuration under the current
+    environment, from the launch-free queries alone (no GPU).  dp: step_mode.DpFacts (default: one rank); count: the flat
+    buffers' length (default: up to the table's end -- only the sharded update's threshold reads it)."""
+    from nnue_hip import step_mode
     g = geometry(cfg)
-    B, F, P, H, stride, side = cfg["batch"], g["F"], g["P"], cfg["image"], g["stride"], g["side"]
-    L1, L2, L3, C, K, fps = cfg["l1"], cfg["l2"], cfg["l3"], cfg["classes"], cfg["K"], cfg["fps"]
-    sgd = cfg["optimizer"] == "sgd"
-    m = dict(optimizer=cfg["optimizer"], grouped=K > 1)
-    m["ft_path"] = lib.ft_path(F, P, L1, B)
-    mfma = m["ft_path"] == "mfma"
-    pm = env("NNUE_CONV_PATCHES", "auto")
-    m["use_patches"] = bool(mfma and fps <= 64 and pm != "0" and (pm == "1" or 3 * H * H > 2 * 27 * side * side))
-    tbl_ok = g["tbl_hi"] > g["tbl_lo"] and g["tbl_lo"] % 4 == 0 and g["tbl_hi"] % 4 == 0
-    m["defer_ste"] = sgd and on("NNUE_DEFER_STE") and fps * 28 <= 4096
-    m["fuse_l1"] = K == 1 and mfma and on("NNUE_FUSE_L1") and lib.ftm_forward_l1_supported(B, F, P, L1, L2)
-    m["fwd_planes"] = (m["fuse_l1"] and not m["use_patches"] and on("NNUE_FTM_FWD_PLANES")
-                       and lib.ftm_forward_l1_planes_supported(B, F, P, L1, L2))
-    m["merge_backward"] = env("NNUE_FTM_SPLIT_BACKWARD", "0") != "1"
-    m["ride_dw1"] = mfma and m["merge_backward"] and on("NNUE_FTM_RIDE_DW1") and lib.ftm_backward_cw_supported(B, F, P, L1, L2)
-    want = env("NNUE_FUSE_TABLE_UPDATE", "auto")
-    m["fuse_table_update"] = (mfma and tbl_ok and B * L1 <= (1 << 24) and want != "0"
-                              and (F * L1 * 4 >= (32 << 20) or want == "1"))
-    n_sq = lib.ftm_backward_sq_count(B, F, P, L1) if (mfma and m["merge_backward"]) else 0
-    if m["fuse_table_update"]:
-        m["ride_dw1"], m["sq"] = False, "gram"
-    else:
-        m["sq"] = "tiles" if (n_sq > 0 and sgd and tbl_ok and on("NNUE_NORM_PARTIALS")) else "none"
-    chunks = lib.ftm_backward_ste_chunks(B, F, P, L1, H, H, stride) if mfma else 0
-    m["ride_ste"] = (m["defer_ste"] and m["merge_backward"] and not m["fuse_table_update"] and chunks > 0 and on("NNUE_FTM_RIDE_STE"))
-    m["ste_chunks"] = chunks if m["ride_ste"] else 0
-    m["val_planes"] = (m["ride_ste"] and not m["use_patches"] and K == 1 and lib.ftm_value_planes_supported(B, F, P, L1, H, H, stride))
-    m["fuse_next_forward"] = (m["fuse_table_update"] and not m["fuse_l1"] and K == 1 and on("NNUE_FUSE_NEXT_FORWARD")
-                              and lib.ftm_update_forward_supported(B, F, P, L1, B))
-    m["ride_small"] = m["ride_dw1"] and on("NNUE_CLS_RIDE_SMALL")
-    m["fuse_tail_dx"] = (m["fuse_l1"] and m["ride_small"] and on("NNUE_CLS_FUSE_TAIL_DX")
-                         and lib.classifier_train_fused_tail_supported(B, L1, L2, L3, C, K))
-    if m["fuse_l1"]:
-        m["phases"] = (123 if m["fuse_tail_dx"] else 59 if m["ride_small"] else 27) if m["ride_dw1"] else 13
-    else:
-        m["phases"] = (51 if m["ride_small"] else 19) if m["ride_dw1"] else 5
-    m["ste_launch"] = None if m["ride_ste"] else (1 if m["defer_ste"] else 3)
-    return {k: (bool(v) if k in FLAGS or k == "merge_backward" else v) for k, v in m.items()}
+    return step_mode.resolve(B=cfg["batch"], H=cfg["image"], W=cfg["image"], stride=g["stride"], fps=cfg["fps"], F=g["F"],
+                             L1=cfg["l1"], L2=cfg["l2"], L3=cfg["l3"], C=cfg["classes"], K=cfg["K"], optimizer=cfg["optimizer"],
+                             dp=dp or step_mode.DpFacts(), use_graph=use_graph, lead_names=LEAD, tbl_lo=g["tbl_lo"],
+                             tbl_hi=g["tbl_hi"], count=g["tbl_hi"] if count is None else count)
+
+
+def resolve(cfg: Dict) -> Dict:
+    """The mode a single-rank trainer of this configuration takes, as the dict the table uses."""
+    sm = step_mode_of(cfg)
+    m = {k: getattr(sm, k) for k in A_MODES if k not in ("grouped", "optimizer", "ste_chunks", "ste_launch")}
+    m.update(grouped=cfg["K"] > 1, optimizer=cfg["optimizer"], ste_chunks=sm.ste_chunks if sm.ride_ste else 0, ste_launch=sm.ste_stages)
+    return m
 
 
 def launches_of(m: Dict) -> List[str]:
