@@ -307,7 +307,10 @@ int nnue_ftm_backward_ste_supported(int B, int F, int P, int L1, int H, int W, i
  * Optional rider (d_w1 != NULL, shapes: nnue_ftm_backward_cw_supported, declared above): the weight gradient of the
  * classifier's first Linear, d_w1[L2][L1] = d_z1^T l0 (autograd of nnue.py:728-730 through the pairwise block
  * nnue.py:660-666), from ft[B][L1] (the FeatureTransformer output) and d_z1[B][L2] (left in the classifier's scratch
- * by nnue_classifier_train_step, at nnue_classifier_train_dz1_offset); pair with phases bit 16 there.
+ * by nnue_classifier_train_step, at nnue_classifier_train_dz1_offset); pair with phases bit 16 there.  Beside bf16
+ * weight tiles (nnue_ftm_uses_bf16(2, ...)) the rider runs as six bf16 plane products, the value gradient's
+ * arithmetic: terms below an f32 rounding of a product are dropped and an Inf operand gives NaN; with NNUE_FTM_BF16=0
+ * it runs on the f32 MFMA.
  * sq_partial (may be NULL): nnue_ftm_backward_sq_count(B, F, P, L1) floats (declared above) that receive, per
  * weight-gradient tile, the sum of the squares of the elements it wrote -- together the squared norm of
  * d_weight[0 .. min(F-1, P)) -- so that nnue_sgd_step (ext_partial) need not read those rows again for

@@ -1449,6 +1449,122 @@ __global__ __launch_bounds__(256) void ftm_gemm_bf6_kernel(Mat ma, Mat mb, Epi e
   gemm_tile_bf6<BM, BN, Epi, KT, ABL>(smem, ma, mb, epi, M, N, 0, K, tiles_n, blockIdx.x, 0);
 }
 
+// ---- gemm_tile_bf6's six plane products for operands that are both contiguous ACROSS k (the d_w1 rider) -------------------
+// A[m][k] = ma(k, m) and B[k][n] = mb(k, n) lie along m / n in memory -- the operand order of the bf16 weight tiles -- so both
+// are staged the gemm_tile_bf64 way: a thread owns a 4 k x 4 row block (four 16-byte loads), splits it exactly into the three
+// planes (split_block) and writes, per row and plane, one 8-byte half chunk of a bf64_img image.  Tile 32 x 64 x 64, waves
+// 2 x 2 (one row fragment x two column fragments per wave), LDS 3 (32 + 64) 64 2 = 36 864 B.  B's 64 x 64 block takes all 256
+// threads, A's 64 x 32 block the first two waves (the others request outside the window, like gemm_tile_bf64's A).  The
+// contraction is gemm_tile_bf6's: per 32-k block lo hi, hi lo, mid mid, mid hi, hi mid, hi hi, consecutive MFMAs on different
+// accumulators; mid lo + lo mid + lo lo are left out (below an f32 rounding of a product).  CwEpi::kBPair: in the product half
+// l0 = ft[:, c] ft[:, c + L1/2] is formed in f32 from two loads before the split (a uniform branch: a 64-column tile lies in
+// one half).  k_lo need not be a multiple of anything (a bucket's first grouped row); rows from k_hi on are outside both
+// windows and read as zero, k_lo == k_hi stores zeros.  Every load is unconditional.  As in every split tile an Inf operand
+// leaves NaN in its products (split3 forms Inf - Inf).
+constexpr int kBf6tLds = 3 * (32 + 64) * kBf64K * 2;
+template <class Epi>
+__device__ __forceinline__ void gemm_tile_bf6t(unsigned char* __restrict__ smem, const Mat& ma, const Mat& mb, const Epi& epi, int M, int N,
+                                               int k_lo, int k_hi, int tiles_n, int tile) {
+  constexpr int BM = 32, BN = 64, KT = kBf64K, TN = BN / 32;
+  constexpr int PA = BM * KT * 2, PB = BN * KT * 2;  // bytes per plane
+  unsigned char* __restrict__ As = smem;
+  unsigned char* __restrict__ Bs = smem + 3 * PA;
+  const __amdgpu_buffer_rsrc_t rsa = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(ma.p), 0, ma.bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsb = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(mb.p), 0, mb.bytes, 0x00020000);
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int r = lane & 15, q = lane >> 4;
+  const int tile_n = tile % tiles_n, tile_m = tile / tiles_n;
+  const int m_base = tile_m * BM, n_base = tile_n * BN;
+  const int m0 = (wave >> 1) * (BM / 2), n0 = (wave & 1) * (BN / 2);
+  // B: thread = (k block of 4: 16 of them, n block of 4: 16 of them), gemm_tile_bf64's assignment
+  const int bn4 = (((lane & 3) | ((lane >> 4) << 2))) * 4, bk4 = (((lane >> 2) & 3) | (wave << 2)) * 4;
+  // A: waves 0 and 1 = (k block of 4: 16 of them, m block of 4: 8 of them)
+  const int am4 = ((lane & 3) | (((lane >> 4) & 1) << 2)) * 4, ak4 = (((lane >> 2) & 3) | ((lane >> 5) << 2) | ((wave & 1) << 3)) * 4;
+  const bool a_on = wave < 2;  // uniform
+  const int a_off = (m_base + am4) * 4;
+  bool b_prod = false;
+  int b_off = (n_base + bn4) * 4;
+  if constexpr (Epi::kBPair) {
+    b_prod = n_base < epi.half;
+    if (!b_prod) b_off -= epi.half * 4;
+  }
+  u32x4 ra[4], rb[4], rb2[Epi::kBPair ? 4 : 1];
+  auto fetch = [&](int k0) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      ra[j] = __builtin_amdgcn_raw_buffer_load_b128(rsa, a_on ? (k0 + ak4 + j) * ma.ld * 4 + a_off : 0x7ffffff0, 0, 0);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) rb[j] = __builtin_amdgcn_raw_buffer_load_b128(rsb, (k0 + bk4 + j) * mb.ld * 4 + b_off, 0, 0);
+    if constexpr (Epi::kBPair) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        rb2[j] = __builtin_amdgcn_raw_buffer_load_b128(rsb, b_prod ? (k0 + bk4 + j) * mb.ld * 4 + b_off + epi.half * 4 : 0x7ffffff0, 0, 0);
+    }
+  };
+  auto stage = [&]() {
+    u32x2 pl[3][4];
+    if (a_on) {
+      split_block<2>(ra, pl);
+      const int half = (ak4 & 4) ? 8 : 0;
+#pragma unroll
+      for (int pnum = 0; pnum < 3; ++pnum)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) *reinterpret_cast<u32x2*>(As + pnum * PA + bf64_img(am4 + e, ak4 >> 3) + half) = pl[pnum][e];
+    }
+    if constexpr (Epi::kBPair) {
+      if (b_prod) {
+        float4 v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const float4 x = widen<false>(rb[j]), w = widen<false>(rb2[j]);
+          v[j] = make_float4(x.x * w.x, x.y * w.y, x.z * w.z, x.w * w.w);
+        }
+        split_block<2>(v, pl);
+      } else {
+        split_block<2>(rb, pl);
+      }
+    } else {
+      split_block<2>(rb, pl);
+    }
+    const int half = (bk4 & 4) ? 8 : 0;
+#pragma unroll
+    for (int pnum = 0; pnum < 3; ++pnum)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) *reinterpret_cast<u32x2*>(Bs + pnum * PB + bf64_img(bn4 + e, bk4 >> 3) + half) = pl[pnum][e];
+  };
+  f32x4 acc[1][TN];
+#pragma unroll
+  for (int t = 0; t < TN; ++t) acc[0][t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  auto contract = [&]() {
+#pragma unroll
+    for (int kb = 0; kb < KT / 32; ++kb) {
+      const int c = kb * 4 + q;  // this lane's 8 k of the 32-k block
+      bf16x8 a[3], b[3][TN];
+#pragma unroll
+      for (int pnum = 0; pnum < 3; ++pnum) {
+        a[pnum] = *reinterpret_cast<const bf16x8*>(As + pnum * PA + bf64_img(m0 + r, c));
+#pragma unroll
+        for (int t = 0; t < TN; ++t) b[pnum][t] = *reinterpret_cast<const bf16x8*>(Bs + pnum * PB + bf64_img(n0 + 16 * t + r, c));
+      }
+      constexpr int pa[6] = {2, 0, 1, 1, 0, 0}, pb[6] = {0, 2, 1, 0, 1, 0};  // smallest terms first (gemm_tile_bf6)
+#pragma unroll
+      for (int s6 = 0; s6 < 6; ++s6)
+#pragma unroll
+        for (int t = 0; t < TN; ++t) acc[0][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[pa[s6]], b[pb[s6]][t], acc[0][t], 0, 0, 0);
+    }
+  };
+  fetch(k_lo);
+  for (int k0 = k_lo; k0 < k_hi; k0 += KT) {
+    stage();
+    __syncthreads();
+    if (k0 + KT < k_hi) fetch(k0 + KT);
+    contract();
+    __syncthreads();
+  }
+  store_tile<BM, BN, Epi>(reinterpret_cast<float*>(smem), epi, acc, M, N, m_base, n_base, m0, n0, tile, 0);
+}
+
 // ---- the 32 x 64 value tile of the STE ride fed the table's value planes (value_planes.h) --------------------------------
 // gemm_tile_bf6's six plane products in its term order (per 32-k block: lo hi, hi lo, mid mid, mid hi, hi mid, hi hi; K tiles
 // and blocks ascending) with the waves 1 x 4: wave w owns all 32 rows x columns 16 w .. 16 w + 15, so no B fragment is shared
@@ -1839,9 +1955,10 @@ __global__ __launch_bounds__(256) void ftm_backward_kernel(Mat wa, Mat wb, BwwEp
   }
 }
 
-// The same launch with the weight-gradient tiles on the bf16 matrix unit (gemm_tile_bf, WM x 64 x 128); value-gradient
-// tiles (both operands f32) and the rider keep the f32 MFMA.  VE = ValSteEpi: the value tiles also leave the STE partials;
-// VE = ValStePlanesEpi: and read the table from the value planes, as six bf16 plane products (gemm_tile_val_planes).
+// The same launch with the weight-gradient tiles on the bf16 matrix unit (gemm_tile_bf, WM x 64 x 128) and the rider as six bf16
+// plane products (gemm_tile_bf6t, 32 x 64 x 64); value-gradient tiles (both operands f32) keep the f32 MFMA unless V6 (six plane
+// products, gemm_tile_bf6).  VE = ValSteEpi: the value tiles also leave the STE partials; VE = ValStePlanesEpi: and read the
+// table from the value planes, as six bf16 plane products (gemm_tile_val_planes).
 template <int WM, int VM, int VN, int VK, bool V6 = false, bool W64 = false, class VE = ValEpi>
 __global__ __launch_bounds__(256) void ftm_backward_bf_kernel(Mat wa, Mat wb, BwwEpi we, int wM, int wN, int wK, int w_tiles_n, int n_w,
                                                               Mat va, Mat vb, VE ve, int vM, int vN, int vK, int v_tiles_n, int n_v,
@@ -1850,10 +1967,14 @@ __global__ __launch_bounds__(256) void ftm_backward_bf_kernel(Mat wa, Mat wb, Bw
   static_assert(!VP || (VM == 32 && VN == 64 && VK == kBfK && !V6), "the planes-fed value tile is 32 x 64 x 128");
   constexpr int kW = gemm_bf_lds_bytes<WM, 64, W64 ? kBf64K : kBfK>(),
                 kV = VP ? kValPlanesLds : V6 ? gemm_bf6_lds_bytes<VM, VN>() : gemm_lds_floats<VM, VN, VK, true, true>() * 4;
-  constexpr int kC = gemm_lds_floats<32, 64, 128, false, false>() * 4;
+  constexpr int kC = kBf6tLds;
   constexpr int kWV = kW > kV ? kW : kV;
-  constexpr int kLds = kWV > kC ? kWV : kC;
+  // (the f32 rider's 52 KB used to cover the STE epilogue of the 64-row f32 value tiles, whose own images are 32 KB)
+  constexpr int kSte = is_ste<VE>::value ? (16 * (8 * VM + 4) + 2048) * 4 : 0;
+  constexpr int kTiles = kWV > kC ? kWV : kC;
+  constexpr int kLds = kTiles > kSte ? kTiles : kSte;
   static_assert(!is_ste<VE>::value || (16 * (8 * VM + 4) + 2048) * 4 <= kLds, "the STE epilogue borrows the tile's LDS");
+  static_assert(1024 * 4 <= kLds, "the tail-row (512 floats) and small-gradient (1024 floats) blocks borrow the tile's LDS");
   __shared__ __attribute__((aligned(16))) unsigned char smem_b[kLds];
   float* smem = reinterpret_cast<float*>(smem_b);
   const int blk = blockIdx.x;
@@ -1874,9 +1995,9 @@ __global__ __launch_bounds__(256) void ftm_backward_bf_kernel(Mat wa, Mat wb, Bw
       b.bytes = (unsigned)k_hi * (unsigned)b.ld * 4u;
       CwEpi e = c.e;
       e.d_w1 += (size_t)kb * c.M * c.N;
-      gemm_tile<32, 64, 128, false, false, CwEpi>(smem, a, b, e, c.M, c.N, k_lo, k_hi, c.tiles_n, t2 - kb * c.per_bucket, 0);
+      gemm_tile_bf6t<CwEpi>(smem_b, a, b, e, c.M, c.N, k_lo, k_hi, c.tiles_n, t2 - kb * c.per_bucket);
     } else {
-      gemm_tile<32, 64, 128, false, false, CwEpi>(smem, c.a, c.b, c.e, c.M, c.N, 0, c.K, c.tiles_n, t2, 0);
+      gemm_tile_bf6t<CwEpi>(smem_b, c.a, c.b, c.e, c.M, c.N, 0, c.K, c.tiles_n, t2);
     }
   } else {
     const int i = blk - n_w - n_v - c.n_c, n_t = t.col_blocks * (1 + t.zero_slices);
@@ -2474,7 +2595,8 @@ MergedBackward merged_backward_plan(int B, int F, int P, int L1, int H = 0, int 
 
   // Weight tiles on the bf16 matrix unit unless NNUE_FTM_BF16=0: 64 rows, or 32 with NNUE_FTM_BF_WM=32.  The 64-row ones with K
   // tiles of 64 (gemm_tile_bf64): the launch's LDS drops from 64 KB to the rider's 52 KB -- three workgroups per CU instead of
-  // two (the 168 registers allow exactly that): 43.5 -> 37.7 us at the C3 shapes, 26.2 -> 25.1 us at C2
+  // two (the 168 registers allow exactly that): 43.5 -> 37.7 us at the C3 shapes, 26.2 -> 25.1 us at C2.  (The rider's
+  // six-plane tile, gemm_tile_bf6t, needs 36 KB: the launch's LDS is now the value tiles' 36-48 KB, still three per CU.)
   m.w_bf = !knob::bf16() ? 0 : knob::bf_wm() == 32 ? 32 : 64;
   const Shape wf = m.big ? shape_of(kF32Square, direct, L1, B) : sw;
   m.w_bm = m.w_bf ? m.w_bf : wf.bm;
@@ -2651,7 +2773,7 @@ int ftm_backward_impl(const uint8_t* bits, const float* sink, const float* d_out
     cw.b = Mat{ft, (unsigned)((size_t)rows * L1 * 4), L1, kIntMax, kIntMax};
     cw.e = CwEpi{d_w1, L1, L1 / 2};
     cw.M = L2; cw.N = L1; cw.K = B; cw.tiles_n = (L1 + 63) / 64;
-    const int cw_bm = mb.w_bf ? 32 : mb.w_bm;  // the rider keeps f32 tiles: the weight-gradient shape, or 32 x 64 x 128 beside bf16 tiles
+    const int cw_bm = mb.w_bf ? 32 : mb.w_bm;  // the rider's tiles: the f32 weight-gradient shape, or 32 x 64 (six bf16 plane products, gemm_tile_bf6t) beside bf16 tiles
     cw.per_bucket = ((L2 + cw_bm - 1) / cw_bm) * cw.tiles_n;
     cw.seg = seg;
     cw.n_c = cw.per_bucket * (seg ? K : 1);
