@@ -2,7 +2,8 @@
 named configurations with the mode each one must take, and the driver that holds a whole optimizer step in that mode to the
 float64 oracle (oracle.loss_and_grads_explicit + oracle.sgd_step / oracle.adam_step).  A helper, not a test module:
 tests/test_trainer_modes_policy.py holds the trainer's own resolver to the table on any machine (it is launch-free),
-tests/test_gpu_trainer_modes.py runs every row on the GPU.
+tests/test_gpu_trainer_modes.py runs every row on the GPU.  The bars are written once, in ``compare_held``, over plain tensors:
+``check_step`` applies them to a single-rank trainer, tests/dp_modes.py to each rank of a process group.
 
 A mode is the dict ``A_MODES`` shows: the trainer's flags, where the table's share of the clip norm comes from (``sq``: the
 weight-gradient tiles, the Gram product, or nowhere: the optimizer reads the rows), the classifier's phase mask of the forward
@@ -355,13 +356,19 @@ def _ratio_logits(got, ref, rtol=1e-4) -> float:
     return float(((got - ref).abs() / (rtol * torch.clamp(ref.abs(), min=1.0))).max())
 
 
-def check_step(tr, ref: Dict, was: Dict[str, torch.Tensor], loss: torch.Tensor, what: str, ratios: Dict[str, float]) -> None:
-    """One trainer step against one oracle step at the project's bars (tests/test_gpu_step_shapes.py; Adam:
-    test_a_step_group_at_the_224_shape_follows_the_oracle_with_adam).  `was`: the trainer's parameters before the step.
-    ratios: the worst error over its bar per kind of check, kept for the record before anything is asserted."""
+def compare_held(held: Dict, ref: Dict, B: int, n: int, scale: Optional[float], what: str, ratios: Dict[str, float]) -> List[str]:
+    """What a trainer holds after one step, as plain tensors, against one oracle step at the project's bars
+    (tests/test_gpu_step_shapes.py; Adam: test_a_step_group_at_the_224_shape_follows_the_oracle_with_adam): the one place the
+    bars are written.  Returns the failures; ``ratios`` keeps the worst error over its bar per kind of check.
+
+    held (every key optional but ``optimizer``; a missing one is not compared): ``logits`` [>= n, C], ``loss``, ``norm``,
+    ``grads`` {name: tensor, as the kernels leave them: sums over the rows divided by B}, ``params`` and ``was`` {name:
+    parameters after / before the step}, ``momentum`` | ``exp_avg`` + ``exp_avg_sq`` {name: tensor}, ``optimizer``, and
+    ``sink``: the table row F - 1 of a clamp-sink map (P > F), else None.  A name is looked up in ``ref`` as it stands, so a
+    caller that holds only a piece of a tensor passes the same piece of the oracle's under the same name.  scale: what
+    restores the oracle's mean over the real samples from the held gradients (None: B / n, the single-rank short batch)."""
     import nnue_oracle as orc
-    from conftest import assert_close_grad, assert_close_logits
-    n, B = ref["images"].shape[0], tr.B
+    scale = B / n if scale is None else scale
     fails: List[str] = []
 
     def note(kind: str, ratio: float, detail: str = "") -> None:
@@ -374,37 +381,60 @@ def check_step(tr, ref: Dict, was: Dict[str, torch.Tensor], loss: torch.Tensor, 
         sums the gradient of every position past it, two orders above the other rows, and a per-tensor bar scaled by it
         would let an error confined to the product's rows (1e-3 of them, in _table_update's scale) pass."""
         yield "", slice(None)
-        if k == "input.weight" and tr.P > tr.F:
-            yield " (rows below the sink)", slice(0, tr.F - 1)
+        if k == "input.weight" and held.get("sink") is not None:
+            yield " (rows below the sink)", slice(0, held["sink"])
 
+    if "logits" in held and n > 0:
+        note("logits", _ratio_logits(held["logits"][:n], ref["logits"]))
+    if "loss" in held:
+        note("loss", abs(float(held["loss"]) - ref["loss"]) / (1e-4 * max(1.0, abs(ref["loss"]))))
+    if "norm" in held:
+        note("norm", abs(float(held["norm"]) - ref["norm"]) / (1e-4 * ref["norm"]))
+    for k, got in held.get("grads", {}).items():  # (a short batch: the kernels divide by B, the update's scale restores the mean over n)
+        for label, rows in parts(k):
+            note("grad", _ratio_grad(got[rows] * scale, ref["grads"][k][rows]), k + label)
+    adam = held["optimizer"] == "adam"
+    for k in (orc.TRAINABLE_KEYS if "params" in held else ()):
+        for label, rows in parts(k):
+            p_ref, p_got = ref["after"][k][rows], held["params"][k][rows]
+            if adam:
+                # Adam divides by sqrt(v): an element whose gradient is ~0 amplifies rounding, so compare on the update scale
+                note("adam parameters", float((p_got.cpu().double() - p_ref).abs().max()) / (2e-5 + 1e-4 * float(p_ref.abs().max())), k + label)
+                continue
+            note("parameters", _ratio_grad(p_got, p_ref, rtol=1e-5), k + label)
+            got_d, ref_d = (p_got - held["was"][k][rows]).cpu().double(), p_ref - ref["before"][k][rows]
+            floor = 2 * 2.0 ** -23 * float(p_ref.abs().max())  # a float32 parameter cannot move by less than its own rounding
+            note("update", float((got_d - ref_d).abs().max()) / (2e-4 * float(ref_d.abs().max()) + floor), k + label)
+    for kind, of in (("exp_avg", lambda st: st["m"]), ("exp_avg_sq", lambda st: st["v"]), ("momentum", lambda st: st)):
+        for k, got in held.get(kind, {}).items():
+            for label, rows in parts(k):
+                note(kind, _ratio_grad(got[rows], of(ref["state"][k])[rows]), k + label)
+    return fails
+
+
+def held_by(tr, was: Optional[Dict[str, torch.Tensor]] = None) -> Dict:
+    """compare_held's ``held`` of a trainer whose flat buffers are whole (a single rank, or a replica after an all-reduce),
+    without logits, loss and norm."""
+    held = dict(optimizer=tr.optimizer, sink=tr.F - 1 if tr.P > tr.F else None, params=tr.p, was=was)
+    if tr.grads_materialised:
+        held["grads"] = tr.layout.views(tr.flat_grads)
+    if tr.optimizer == "adam":
+        held.update(exp_avg=tr.layout.views(tr.flat_exp_avg), exp_avg_sq=tr.layout.views(tr.flat_exp_avg_sq))
+    elif tr.flat_momentum is not None:
+        held["momentum"] = tr.layout.views(tr.flat_momentum)
+    return held
+
+
+def check_step(tr, ref: Dict, was: Dict[str, torch.Tensor], loss: torch.Tensor, what: str, ratios: Dict[str, float]) -> None:
+    """One trainer step against one oracle step at compare_held's bars.  `was`: the trainer's parameters before the step.
+    ratios: the worst error over its bar per kind of check, kept for the record before anything is asserted."""
+    from conftest import assert_close_grad, assert_close_logits
+    n, B = ref["images"].shape[0], tr.B
     torch.cuda.synchronize()
     if n == B:
         n_mean, n_max = tr.active_stats()
         assert n_max == int(ref["n"].max()) and abs(n_mean - float(ref["n"].float().mean())) < 1e-2, f"{what}: feature counts differ"
-    note("logits", _ratio_logits(tr.logits[:n], ref["logits"]))
-    note("loss", abs(float(loss) - ref["loss"]) / (1e-4 * max(1.0, abs(ref["loss"]))))
-    note("norm", abs(float(tr.grad_norm) - ref["norm"]) / (1e-4 * ref["norm"]))
-    if tr.grads_materialised:
-        got = tr.layout.views(tr.flat_grads)
-        for k, g in ref["grads"].items():  # (a short batch: the kernels divide by B, the update's scale restores the mean over n)
-            for label, rows in parts(k):
-                note("grad", _ratio_grad(got[k][rows] * (B / n), g[rows]), k + label)
-    adam = tr.optimizer == "adam"
-    for k in orc.TRAINABLE_KEYS:
-        for label, rows in parts(k):
-            p_ref, p_got = ref["after"][k][rows], tr.p[k][rows]
-            if adam:
-                # Adam divides by sqrt(v): an element whose gradient is ~0 amplifies rounding, so compare on the update scale
-                note("adam parameters", float((p_got.cpu().double() - p_ref).abs().max()) / (2e-5 + 1e-4 * float(p_ref.abs().max())), k + label)
-                note("exp_avg", _ratio_grad(tr.layout.views(tr.flat_exp_avg)[k][rows], ref["state"][k]["m"][rows]), k + label)
-                note("exp_avg_sq", _ratio_grad(tr.layout.views(tr.flat_exp_avg_sq)[k][rows], ref["state"][k]["v"][rows]), k + label)
-                continue
-            note("parameters", _ratio_grad(p_got, p_ref, rtol=1e-5), k + label)
-            got_d, ref_d = (p_got - was[k][rows]).cpu().double(), p_ref - ref["before"][k][rows]
-            floor = 2 * 2.0 ** -23 * float(p_ref.abs().max())  # a float32 parameter cannot move by less than its own rounding
-            note("update", float((got_d - ref_d).abs().max()) / (2e-4 * float(ref_d.abs().max()) + floor), k + label)
-            if tr.flat_momentum is not None:
-                note("momentum", _ratio_grad(tr.layout.views(tr.flat_momentum)[k][rows], ref["state"][k][rows]), k + label)
+    fails = compare_held(dict(held_by(tr, was), logits=tr.logits, loss=loss, norm=tr.grad_norm), ref, B, n, None, what, ratios)
     assert not fails, "; ".join(fails)
     # the same bars through the project's own assertions
     assert_close_logits(tr.logits[:n], ref["logits"], f"{what} logits")
