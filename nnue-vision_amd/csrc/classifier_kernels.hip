@@ -864,67 +864,103 @@ __global__ __launch_bounds__(NT) void tail_train_kernel(const float* __restrict_
 // the same tail; the one of column group 0 writes its outputs (h1, h2, logits, sample_loss, d_logits, d_z2, d_z1 --
 // what the merged FeatureTransformer backward's riders read), the others keep d_z1 in LDS only.
 //
-// Each output is formed by the expressions tail_train_kernel<128, true> uses, in its order: slab sum in slab order,
-// four tail_dot4 chains combined by xor 1 then xor 2, the 64-lane softmax butterflies, dz2_slice<4> + slice_tree<4>,
-// d_z1 serially in row order -- and d_x by the l1_backward_x_body pieces: bitwise the two launches.
+// The slab sum (slab order, skip-not-add), act_fn / gate_fn, the 64-lane softmax butterflies and the loss are those of
+// tail_train_kernel; the four small products run on the f32 MFMA (below), and d_x is formed by the l1_backward_x_body
+// pieces.  At the shapes this kernel takes every phase combination runs it (DX = false: the tail alone), so the launch
+// forms agree bitwise; tail_train_kernel serves every other shape.
 //
-// Loads: the W1 column slice, the x values of the pairwise epilogue, the small weights, biases, labels and the tile's
-// first 16 slabs are all requested at entry (one dependent load level).  Placement: blocks are numbered so that all
+// Loads: the W1 column slice, the x values of the pairwise epilogue, the small products' B fragments, biases, labels and
+// the tile's first 16 slabs are all requested at entry (one dependent load level).  Placement: blocks are numbered so that all
 // column groups of a row tile share blockIdx % 8 (round-robin dispatch puts them on one XCD, whose L2 then serves the 7
 // repeated reads of the tile's 128 KB of slabs); results do not depend on it.
 constexpr int kTdxRows = 16, kTdxThreads = 512, kTdxMaxC = 64;
 
-// dz2_slice<S> for C <= kTdxMaxC with its tail loop unrolled and predicated (same fmas in the same order): the
-// per-lane trip counts of the loop form made every thread wait out one LDS round trip per class
-template <int S>
-__device__ __forceinline__ float dz2_slice_small(const float* dl, const float* w3j, int cp, int C, int L3) {
-  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-  int c = cp;
-  for (int m = 0, mu = C > 3 * S ? (C - 3 * S + 4 * S - 1) / (4 * S) : 0; m < mu; ++m) {  // uniform bound (cp = 0)
-    const bool act = c + 3 * S < C;
-    const int cc = act ? c : 0;
-    const float f0 = fmaf(dl[cc], w3j[(size_t)cc * L3], s0), f1 = fmaf(dl[cc + S], w3j[(size_t)(cc + S) * L3], s1);
-    const float f2 = fmaf(dl[cc + 2 * S], w3j[(size_t)(cc + 2 * S) * L3], s2), f3 = fmaf(dl[cc + 3 * S], w3j[(size_t)(cc + 3 * S) * L3], s3);
-    s0 = act ? f0 : s0; s1 = act ? f1 : s1; s2 = act ? f2 : s2; s3 = act ? f3 : s3;
-    c = act ? c + 4 * S : c;
-  }
-#pragma unroll
-  for (int t = 0; t < 3; ++t) {  // c + 3S >= C here: at most three classes are left
-    const bool act = c + S * t < C;
-    const int cc = act ? c + S * t : 0;
-    const float f = fmaf(dl[cc], w3j[(size_t)cc * L3], s0);
-    s0 = act ? f : s0;
-  }
-  return (s0 + s1) + (s2 + s3);
-}
+// Timing-only hooks (NNUE_ABLATIONS builds, tools/debug/tail_abl.sh).  SKIP (a template parameter, so that the kernel
+// with the knob off is the shipped code; NNUE_CLS_ABL_SKIP_TAIL_PRODUCTS=1 launches it): the four small products are
+// not formed -- WRONG results, their outputs are stored as zeros.  clocks (NNUE_CLS_ABL_TAIL_CLOCKS=1) =
+// [workgroup][kTdxClocks] shader-clock readings, one per phase boundary, taken by thread 0 and written with ordinary
+// stores.  A default build compiles neither.
+#ifdef NNUE_ABLATIONS
+constexpr int kTdxClocks = 10;
+struct TdxAbl { long long* clocks; };
+#define NNUE_TDX_ABL_PARAM , TdxAbl abl
+#define NNUE_TDX_CLOCK(i) do { if (abl.clocks && threadIdx.x == 0) abl.clocks[(size_t)blockIdx.x * kTdxClocks + (i)] = clock64(); } while (0)
+#else
+#define NNUE_TDX_ABL_PARAM
+#define NNUE_TDX_CLOCK(i) do { } while (0)
+#endif
+
+// ---- the tile tail's four small products on the f32 MFMA (v_mfma_f32_16x16x4_f32: exact fp32 products, fp32 sums)
+// The tile has 16 rows = the M of one MFMA, so every product of the tail is a few 16 x 16 output tiles; lane (r, q) =
+// (lane & 15, lane >> 4) gives A[row r][k = q] and B[k = q][column r] and receives D[row 4 q + e][column r], e = 0..3.
+// The k walk of every product is the same: groups g of 16, step e of a group takes k = 16 g + 4 q + e from lane q (one
+// float4 of the A row per group), so a row's sums depend on that row's inputs only and have one fixed order.
+//   h2     16 x 32, K = 128: wave = 2 kq + t forms K quarter kq of column tile t; the four partials are summed from
+//          LDS in the order 0..3, then + b2 and act_fn (a 32-MFMA chain in two waves cost 4x the 8 of a quarter)
+//   logits 16 x C,  K = 32:  wave w < ceil(C / 16) forms classes 16 w .. 16 w + 15, then + b3
+//   d_z2   16 x 32, K = C:   wave 4 + 2 kh + t forms class half kh (32 classes) of column tile t, groups of 16 classes
+//          wholly past C left out; the two partials are summed in the order 0, 1, then gate_fn
+//   d_z1   16 x 128, K = 32: wave w forms columns 16 w .. 16 w + 15, gate_fn on the accumulator
+// The B fragments come straight from global memory at kernel entry (24 floats per lane, beside the other entry loads);
+// classes >= C are read from a clamped address and replaced by exact zeros on both operands where they are used.
+struct TailFrags {
+  float w2f[8];  // h2:   w2[16 t + r][32 kq + 16 g + 4 q + e]
+  float w2b[8];  // d_z1: w2[16 g + 4 q + e][16 wave + r]
+  float w3f[8];  // waves 0..3 (logits): w3[16 wave + r][16 g + 4 q + e]; waves 4..7 (d_z2): w3[32 kh + 16 g + 4 q + e][16 t + r]
+  float b3v;     // b3[16 (wave & 3) + r]
+};
 
 template <int L2, int L3>
+__device__ __forceinline__ void tail_load_frags(TailFrags& f, const float* __restrict__ w2, const float* __restrict__ w3,
+                                                const float* __restrict__ b3, int C, int wave, int r, int q) {
+  static_assert(L2 == 128 && L3 == 32, "tail_load_frags: the wave roles are laid out for 128 / 32");
+  const int t = wave & 1, kq = wave >> 1, kh = (wave >> 1) & 1;
+  const bool lg = wave < 4;  // wave-uniform
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const int k = 16 * (i >> 2) + 4 * q + (i & 3);
+    f.w2f[i] = w2[(16 * t + r) * L2 + 32 * kq + k];
+    f.w2b[i] = w2[k * L2 + 16 * wave + r];
+    const int cls = lg ? 16 * wave + r : 32 * kh + k, unit = lg ? k : 16 * t + r;
+    f.w3f[i] = w3[min(cls, C - 1) * L3 + unit];
+  }
+  f.b3v = b3[min(16 * (wave & 3) + r, C - 1)];
+}
+
+// acc += A B over one group of 16 k: a = the lane's float4 of its A row, b = its four B values
+__device__ __forceinline__ f32x4 tail_mma4(const float4& a, float b0, float b1, float b2, float b3, f32x4 acc) {
+  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b0, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b1, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b2, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b3, acc, 0, 0, 0);
+  return acc;
+}
+
+// DX: the d_x tiles follow the tail (phases 123).  !DX: the tail alone, one workgroup per row tile (n_cg = 1; x, w1 and
+// d_x are not read) -- what every other phase combination runs at these shapes, so that all of them form the tail's
+// values with the same arithmetic.
+template <int L2, int L3, bool DX, bool SKIP = false>
 __global__ __launch_bounds__(kTdxThreads) void tail_dx_train_kernel(
     const float* __restrict__ part, int ksplit, const float* __restrict__ b1, const float* __restrict__ w2,
     const float* __restrict__ b2, const float* __restrict__ w3, const float* __restrict__ b3, float clip,
     const int64_t* __restrict__ labels, float scale_over_b, int B, int C, float* __restrict__ h1, float* __restrict__ h2,
     float* __restrict__ logits, float* __restrict__ sample_loss, float* __restrict__ d_logits, float* __restrict__ d_z1,
     float* __restrict__ d_z2, const float* __restrict__ x, const float* __restrict__ w1, int L1, float* __restrict__ d_x,
-    int m_tiles, int n_cg) {
+    int m_tiles, int n_cg NNUE_TDX_ABL_PARAM) {
   constexpr int T = kTdxRows, NT = kTdxThreads, NWAVE = NT / 64;
   constexpr int NI = T * L2 / 4 / NT;       // float4 slots of the tile's slab rows per thread
   constexpr int NCH = L2 / (16 * kBwxKC);   // K chunks of the d_x product
-  constexpr int RP = NT / 4 / L3;           // rows per pass of the four-thread dot products
-  static_assert(NI >= 1 && NI * NT * 4 == T * L2 && NT % L2 == 0 && L3 % 16 == 0 && (NT / 4) % L3 == 0 && T % RP == 0,
+  static_assert(NI >= 1 && NI * NT * 4 == T * L2 && T * L3 == NT && NWAVE == 8 && T == 16,
                 "tail_dx_train_kernel: unsupported layer widths");
-  __shared__ float4 w2s4[L3 * L2 / 4];  // w2 [L3][L2]
-  __shared__ float4 w3s4[kTdxMaxC * L3 / 4];  // w3 [C][L3]
-  __shared__ __attribute__((aligned(16))) float h1s[T][L2];
-  __shared__ __attribute__((aligned(16))) float dz1s[T][L2];
-  __shared__ __attribute__((aligned(16))) float h2s[T][L3];
-  __shared__ float dz2s[T][L3];
-  __shared__ float ps[T][4][L3];
-  __shared__ float lgs[T][kTdxMaxC];  // logits, then d_logits
-  __shared__ float b2s[L3], b3s[kTdxMaxC];
+  // rows are padded by 4 floats: the 16 rows' float4 A reads of one k group then fall in 16 different bank groups
+  __shared__ __attribute__((aligned(16))) float h1s[T][L2 + 4];
+  __shared__ __attribute__((aligned(16))) float dz1s[T][L2 + 4];
+  __shared__ __attribute__((aligned(16))) float h2s[T][L3 + 4];
+  __shared__ __attribute__((aligned(16))) float dz2s[T][L3 + 4];
+  __shared__ float ps[T][4][L3];  // partial h2 sums [row][K quarter][unit], then partial d_z2 sums [row][class half][unit]
+  __shared__ __attribute__((aligned(16))) float lgs[T][kTdxMaxC + 4];  // logits, then d_logits
   __shared__ int64_t ys[T];
-  __shared__ f32x4 xch[NWAVE][64];  // d_x accumulators swapped between the two waves of a pair
-  const float* w2s = reinterpret_cast<const float*>(w2s4);
-  const float* w3s = reinterpret_cast<const float*>(w3s4);
+  __shared__ f32x4 xch[DX ? NWAVE : 1][64];  // d_x accumulators swapped between the two waves of a pair
 
   const int blk = blockIdx.x, slot = blk >> 3;
   const int mt = (slot / n_cg) * 8 + (blk & 7), cg = slot % n_cg;
@@ -932,6 +968,8 @@ __global__ __launch_bounds__(kTdxThreads) void tail_dx_train_kernel(
   const bool writer = cg == 0;
   const int row0 = mt * T;
   const int tid = threadIdx.x;
+  constexpr bool skip = SKIP;
+  NNUE_TDX_CLOCK(0);
 
   // ---- the d_x operands: a pair of 16-column tiles (c0, c0 + L1/2) per two waves, one tile per wave; this wave's W1
   // column slice and the x values of its epilogue are requested first and used after the tail
@@ -945,25 +983,19 @@ __global__ __launch_bounds__(kTdxThreads) void tail_dx_train_kernel(
 #pragma unroll
   for (int e = 0; e < 4; ++e) orows[e] = row0 + 4 * q + e;
   float bw[NCH][kBwxKC][4];
-#pragma unroll
-  for (int n = 0; n < NCH; ++n) bwx_load_b_tile(bw[n], w1, n * 16 * kBwxKC, L1, L2, cm, r, q);
   float xv[4];  // the c1 tile's wave multiplies by x[c0], the c0 tile's by x[c1]
+  if constexpr (DX) {
 #pragma unroll
-  for (int e = 0; e < 4; ++e) xv[e] = x[(size_t)min(orows[e], B - 1) * L1 + (hi ? c0 : c1) + r];  // a padding row stores nothing
+    for (int n = 0; n < NCH; ++n) bwx_load_b_tile(bw[n], w1, n * 16 * kBwxKC, L1, L2, cm, r, q);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) xv[e] = x[(size_t)min(orows[e], B - 1) * L1 + (hi ? c0 : c1) + r];  // a padding row stores nothing
+  }
 
-  // ---- then the small weights, biases, labels and the slabs.  Every load is unconditional from an in-bounds
-  // address and masked afterwards: a guarded load becomes a branch with a wait of its own.
-  constexpr int NW2 = L3 * L2 / 4 / NT;  // float4 of w2 per thread
-  constexpr int NW3 = kTdxMaxC * L3 / 4 / NT;
-  static_assert(NW2 >= 1 && NW2 * NT * 4 == L3 * L2 && NW3 >= 1 && NW3 * NT * 4 == kTdxMaxC * L3, "tail_dx_train_kernel: staging shape");
-  float4 w2v[NW2], w3v[NW3];
-#pragma unroll
-  for (int i = 0; i < NW2; ++i) w2v[i] = reinterpret_cast<const float4*>(w2)[tid + NT * i];
-  const int n_w3 = C * L3 / 4;
-#pragma unroll
-  for (int i = 0; i < NW3; ++i) w3v[i] = reinterpret_cast<const float4*>(w3)[min(tid + NT * i, n_w3 - 1)];
+  // ---- then the small products' B fragments, biases, labels and the slabs.  Every load is unconditional from an
+  // in-bounds address and masked afterwards: a guarded load becomes a branch with a wait of its own.
+  TailFrags fr;
+  tail_load_frags<L2, L3>(fr, w2, w3, b3, C, wave, r, q);
   const float b2v = b2[tid % L3];
-  const float b3v = b3[min(tid, C - 1)];
   const int64_t yv = labels[min(row0 + (tid % T), B - 1)];
   int srow[NI], scol[NI];
   float4 z4[NI];
@@ -1000,14 +1032,6 @@ __global__ __launch_bounds__(kTdxThreads) void tail_dx_train_kernel(
   {
     float4 v[NI][16];
     load_batch(0, v);
-    // the staged weights go to LDS while the first batch is in flight (their loads were issued before it)
-#pragma unroll
-    for (int i = 0; i < NW2; ++i) w2s4[tid + NT * i] = w2v[i];
-#pragma unroll
-    for (int i = 0; i < NW3; ++i)
-      if (tid + NT * i < n_w3) w3s4[tid + NT * i] = w3v[i];
-    if (tid < L3) b2s[tid] = b2v;
-    if (tid < C) b3s[tid] = b3v;
     if (tid < T) ys[tid] = row0 + tid < B ? yv : -1;
     sum_batch(0, v);
   }
@@ -1026,50 +1050,62 @@ __global__ __launch_bounds__(kTdxThreads) void tail_dx_train_kernel(
     if (writer && row0 + srow[i] < B) *reinterpret_cast<float4*>(h1 + (size_t)(row0 + srow[i]) * L2 + scol[i]) = h;
   }
   __syncthreads();
+  NNUE_TDX_CLOCK(1);
 
-  const int part4 = tid & 3, og = tid >> 2;  // four threads per dot product
-  // ---- h2 = act(w2 h1 + b2): unit j = og % L3 (its w2 row held in registers), RP rows per pass
+  const f32x4 zero4 = (f32x4){0.f, 0.f, 0.f, 0.f};
+  const int orow_t = tid / L3, ounit = tid % L3;  // the (row, unit) of T x L3 values this thread finishes
+  // ---- h2 = act(w2 h1 + b2): K quarter kq of column tile t per wave, then the quarters in order
   {
-    const int j = og % L3;
-    float4 wf[L2 / 16];
+    const int t = wave & 1, kq = wave >> 1;
+    f32x4 acc = zero4;
+    if constexpr (!skip) {
 #pragma unroll
-    for (int m = 0; m < L2 / 16; ++m) wf[m] = w2s4[(j * L2 + 4 * part4 + 16 * m) / 4];
-    const float bj = b2s[j];
+      for (int g = 0; g < 2; ++g) {
+        const float4 a = *reinterpret_cast<const float4*>(&h1s[r][32 * kq + 16 * g + 4 * q]);
+        acc = tail_mma4(a, fr.w2f[4 * g], fr.w2f[4 * g + 1], fr.w2f[4 * g + 2], fr.w2f[4 * g + 3], acc);
+      }
+    }
 #pragma unroll
-    for (int it = 0; it < T / RP; ++it) {  // compile-time trip count: the rows' chains interleave
-      const int rr = og / L3 + RP * it;
-      float z = 0.f;
+    for (int e = 0; e < 4; ++e) ps[4 * q + e][kq][16 * t + r] = acc[e];
+  }
+  __syncthreads();
+  NNUE_TDX_CLOCK(2);
+  {
+    float z = ps[orow_t][0][ounit];
+    z += ps[orow_t][1][ounit];
+    z += ps[orow_t][2][ounit];
+    z += ps[orow_t][3][ounit];
+    const float h = act_fn(z + b2v, clip);
+    h2s[orow_t][ounit] = h;
+    if (writer && row0 + orow_t < B) h2[(size_t)(row0 + orow_t) * L3 + ounit] = h;
+  }
+  __syncthreads();
+  NNUE_TDX_CLOCK(3);
+  // ---- logits = w3 h2 + b3: classes 16 wave .. 16 wave + 15 in wave < ceil(C / 16); the others go on to the barrier
+  if (16 * wave < C) {  // wave-uniform; C <= kTdxMaxC = 64: waves 0..3, the ones that hold the logits fragments
+    const int n = 16 * wave + r;
+    const bool n_in = n < C;
+    f32x4 acc = zero4;
+    if constexpr (!skip) {
 #pragma unroll
-      for (int m = 0; m < L2 / 16; ++m) z = tail_dot4(wf[m], *reinterpret_cast<const float4*>(&h1s[rr][4 * part4 + 16 * m]), z);
-      z += lane_xor<1>(z);
-      z += lane_xor<2>(z);
-      if (part4 == 0) {
-        const float h = act_fn(z + bj, clip);
-        h2s[rr][j] = h;
-        if (writer && row0 + rr < B) h2[(size_t)(row0 + rr) * L3 + j] = h;
+      for (int g = 0; g < 2; ++g) {
+        const float4 a = *reinterpret_cast<const float4*>(&h2s[r][16 * g + 4 * q]);
+        acc = tail_mma4(a, n_in ? fr.w3f[4 * g] : 0.f, n_in ? fr.w3f[4 * g + 1] : 0.f, n_in ? fr.w3f[4 * g + 2] : 0.f,
+                        n_in ? fr.w3f[4 * g + 3] : 0.f, acc);
+      }
+    }
+    if (n_in) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int rr = 4 * q + e;
+        const float z = acc[e] + fr.b3v;
+        lgs[rr][n] = z;
+        if (writer && row0 + rr < B) logits[(size_t)(row0 + rr) * C + n] = z;
       }
     }
   }
   __syncthreads();
-  // ---- logits = w3 h2 + b3
-  for (int o0 = 0; o0 < T * C; o0 += NT / 4) {  // uniform trip count: the shuffles need every lane
-    const int o = o0 + og;
-    const bool v = o < T * C;
-    const int rr = v ? o / C : 0, c = v ? o - rr * C : 0;
-    float z = 0.f;
-#pragma unroll
-    for (int k = 4 * part4; k < L3; k += 16)
-      z = tail_dot4(*reinterpret_cast<const float4*>(w3s + c * L3 + k), *reinterpret_cast<const float4*>(&h2s[rr][k]), z);
-    z = v ? z : 0.f;
-    z += lane_xor<1>(z);
-    z += lane_xor<2>(z);
-    if (v && part4 == 0) {
-      z += b3s[c];
-      lgs[rr][c] = z;
-      if (writer && row0 + rr < B) logits[(size_t)(row0 + rr) * C + c] = z;
-    }
-  }
-  __syncthreads();
+  NNUE_TDX_CLOCK(4);
   // ---- softmax cross-entropy and d_logits: rows wave, wave + NWAVE, ... of the tile (interleaved), lane = class
   {
     constexpr int RW = T / NWAVE;
@@ -1094,46 +1130,61 @@ __global__ __launch_bounds__(kTdxThreads) void tail_dx_train_kernel(
     }
   }
   __syncthreads();
-  // ---- d_z2 = gate(w3^T d_logits): four class slices per value, then the fixed tree
+  NNUE_TDX_CLOCK(5);
+  // ---- d_z2 = gate(w3^T d_logits): class half kh of column tile t in wave 4 + 2 kh + t, then the halves in order
+  if (wave >= 4) {
+    const int t = wave & 1, kh = (wave >> 1) & 1;
+    f32x4 acc = zero4;
+    if constexpr (!skip) {
 #pragma unroll
-  for (int it = 0; it < T * 4 * L3 / NT; ++it) {
-    const int i = tid + NT * it;
-    const int j = i % L3, cp = (i / L3) & 3, rr = i / (4 * L3);
-    ps[rr][cp][j] = dz2_slice_small<4>(lgs[rr], w3s + j, cp, C, L3);
-  }
-  __syncthreads();
-#pragma unroll
-  for (int it = 0; it < (T * L3 + NT - 1) / NT; ++it) {
-    const int i = tid + NT * it, rr = i / L3, j = i % L3;
-    if (i < T * L3) {
-      float qv[4] = {ps[rr][0][j], ps[rr][1][j], ps[rr][2][j], ps[rr][3][j]};
-      const float v = gate_fn(slice_tree<4>(qv), h2s[rr][j], clip);
-      dz2s[rr][j] = v;
-      if (writer && row0 + rr < B) d_z2[(size_t)(row0 + rr) * L3 + j] = v;
+      for (int g = 0; g < 2; ++g) {
+        const int cb = 32 * kh + 16 * g;
+        if (cb < C) {  // uniform: a group of 16 classes wholly past C adds nothing
+          const int c = cb + 4 * q;
+          float4 a = *reinterpret_cast<const float4*>(&lgs[r][c]);  // LDS past class C was never written: select, not multiply
+          a.x = c < C ? a.x : 0.f; a.y = c + 1 < C ? a.y : 0.f; a.z = c + 2 < C ? a.z : 0.f; a.w = c + 3 < C ? a.w : 0.f;
+          acc = tail_mma4(a, c < C ? fr.w3f[4 * g] : 0.f, c + 1 < C ? fr.w3f[4 * g + 1] : 0.f, c + 2 < C ? fr.w3f[4 * g + 2] : 0.f,
+                          c + 3 < C ? fr.w3f[4 * g + 3] : 0.f, acc);
+        }
+      }
     }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) ps[4 * q + e][kh][16 * t + r] = acc[e];
   }
   __syncthreads();
-  // ---- d_z1 = gate(w2^T d_z2): unit k = tid % L2 (its w2 column in registers), serial in row order
+  NNUE_TDX_CLOCK(6);
   {
-    const int k = tid % L2;
-    float wc[L3];
+    const float s = ps[orow_t][0][ounit] + ps[orow_t][1][ounit];
+    const float v = gate_fn(s, h2s[orow_t][ounit], clip);
+    dz2s[orow_t][ounit] = v;
+    if (writer && row0 + orow_t < B) d_z2[(size_t)(row0 + orow_t) * L3 + ounit] = v;
+  }
+  __syncthreads();
+  NNUE_TDX_CLOCK(7);
+  // ---- d_z1 = gate(w2^T d_z2): columns 16 wave .. 16 wave + 15 per wave
+  {
+    f32x4 acc = zero4;
+    if constexpr (!skip) {
 #pragma unroll
-    for (int j = 0; j < L3; ++j) wc[j] = w2s[j * L2 + k];
+      for (int g = 0; g < 2; ++g) {
+        const float4 a = *reinterpret_cast<const float4*>(&dz2s[r][16 * g + 4 * q]);
+        acc = tail_mma4(a, fr.w2b[4 * g], fr.w2b[4 * g + 1], fr.w2b[4 * g + 2], fr.w2b[4 * g + 3], acc);
+      }
+    }
+    const int k = 16 * wave + r;
 #pragma unroll
-    for (int it = 0; it < T * L2 / NT; ++it) {
-      const int rr = tid / L2 + (NT / L2) * it;
-      float s = 0.f;
-#pragma unroll
-      for (int j = 0; j < L3; ++j) s = fmaf(dz2s[rr][j], wc[j], s);
-      const float v = gate_fn(s, h1s[rr][k], clip);
+    for (int e = 0; e < 4; ++e) {
+      const int rr = 4 * q + e;
+      const float v = gate_fn(acc[e], h1s[rr][k], clip);
       dz1s[rr][k] = v;
       if (writer && row0 + rr < B) d_z1[(size_t)(row0 + rr) * L2 + k] = v;
     }
   }
   __syncthreads();
+  NNUE_TDX_CLOCK(8);
   // ---- d_x: this wave's tile with l1_backward_x_body's operands and MFMA order, then the pairwise epilogue with the
   // partner wave's accumulator
-  {
+  if constexpr (DX) {
     const bool row_ok = row0 + r < B;
     f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -1154,6 +1205,7 @@ __global__ __launch_bounds__(kTdxThreads) void tail_dx_train_kernel(
       else o[c0 + r] = fmaf(acc[e], xv[e], other[e]);  // fma(acc0, x[c1], acc1)
     }
   }
+  NNUE_TDX_CLOCK(9);
 }
 
 // ------------------------------------------------------------------ shape policy (shared by scratch + launch)
@@ -1428,6 +1480,11 @@ TrainLayout train_layout(const ClsPlan& p, int B, int L1, int L2, int L3, int C,
   return t;
 }
 
+#ifdef NNUE_ABLATIONS
+long long* g_tdx_clocks = nullptr;  // the last tail_dx_train_kernel launch's phase clocks (NNUE_CLS_ABL_TAIL_CLOCKS=1)
+int g_tdx_clock_blocks = 0;
+#endif
+
 int train_step_impl(const float* x, int pairwise, const float* w1, const float* b1, const float* w2, const float* b2, const float* w3,
                     const float* b3, float clip, const int64_t* labels, float grad_scale, int B, int L1, int L2, int L3, int C, float* h1,
                     float* h2, float* logits, float* sample_loss, float* loss, float* d_x, float* d_w1, float* d_b1, float* d_w2,
@@ -1495,11 +1552,43 @@ int train_step_impl(const float* x, int pairwise, const float* w1, const float* 
                "(B=%d L1=%d L2=%d L3=%d C=%d K=%d pairwise=%d)", B, L1, L2, L3, C, K, pairwise);
   NNUE_REQUIRE(!fuse_tail || (nnue_aligned16(w2) && nnue_aligned16(w3)), NNUE_E_ARG,
                "nnue_classifier_train_step: phases 123 needs 16-byte aligned w2 and w3");
+  // The tile tail (tail_dx_train_kernel): at every shape the fused predicate takes, EVERY phase combination forms the
+  // per-sample tail with it -- followed by the d_x tiles in the same launch (phases 123) or alone, one workgroup per row
+  // tile -- so that the launch forms agree bitwise.  Every other shape keeps tail_train_kernel.
+  const bool tile_tail = tail_dx_supported(B, L1, L2, L3, C, K, pairwise);
+  auto launch_tile_tail = [&](bool dx, int slabs_in) {
+    const int n_cg = dx ? L1 / 32 / (kTdxThreads / 128) : 1;  // pairs of 16-column tiles / pairs per workgroup
+    const int tdx_grid = (m_tiles + 7) / 8 * 8 * n_cg;
+#ifdef NNUE_ABLATIONS  // timing-only hooks of tail_dx_train_kernel (tools/debug/tail_abl.sh)
+    static const int abl_skip = [] { const char* e = getenv("NNUE_CLS_ABL_SKIP_TAIL_PRODUCTS"); return e ? atoi(e) : 0; }();
+    static const int abl_clocks = [] { const char* e = getenv("NNUE_CLS_ABL_TAIL_CLOCKS"); return e ? atoi(e) : 0; }();
+    if (abl_clocks && tdx_grid > g_tdx_clock_blocks) {  // eager launches only: this allocates
+      if (g_tdx_clocks) (void)hipFree(g_tdx_clocks);
+      g_tdx_clocks = nullptr;
+      g_tdx_clock_blocks = hipMalloc(&g_tdx_clocks, (size_t)tdx_grid * kTdxClocks * sizeof(long long)) == hipSuccess ? tdx_grid : 0;
+    }
+    if (abl_clocks && g_tdx_clocks) (void)hipMemsetAsync(g_tdx_clocks, 0, (size_t)g_tdx_clock_blocks * kTdxClocks * sizeof(long long), s);
+    const TdxAbl abl{abl_clocks ? g_tdx_clocks : nullptr};
+#define NNUE_TDX_ABL_ARG , abl
+#else
+    constexpr int abl_skip = 0;
+#define NNUE_TDX_ABL_ARG
+#endif
+#define NNUE_TDX(DX, SKIP)                                                                                                                \
+  hipLaunchKernelGGL((tail_dx_train_kernel<128, 32, DX, SKIP>), dim3(tdx_grid), dim3(kTdxThreads), 0, s, part, slabs_in, b1, w2, b2, w3, b3, \
+                     clip, labels, grad_scale / (float)B, B, C, h1, h2, logits, sample_loss, d_logits, d_z1, d_z2, x, w1, L1, d_x, m_tiles, \
+                     n_cg NNUE_TDX_ABL_ARG)
+    if (abl_skip) {
+#ifdef NNUE_ABLATIONS
+      if (dx) NNUE_TDX(true, true); else NNUE_TDX(false, true);
+#endif
+    } else if (dx) NNUE_TDX(true, false);
+    else NNUE_TDX(false, false);
+#undef NNUE_TDX
+#undef NNUE_TDX_ABL_ARG
+  };
   if (fuse_tail) {  // phases 123: the slabs are in scratch, d_w1 and the small gradients ride in nnue_ftm_backward's launch
-    const int n_cg = L1 / 32 / (kTdxThreads / 128);  // pairs of 16-column tiles / pairs per workgroup
-    hipLaunchKernelGGL((tail_dx_train_kernel<128, 32>), dim3((m_tiles + 7) / 8 * 8 * n_cg), dim3(kTdxThreads), 0, s, part, L1 / 64, b1, w2, b2,
-                       w3, b3, clip, labels, grad_scale / (float)B, B, C, h1, h2, logits, sample_loss, d_logits, d_z1, d_z2, x, w1, L1, d_x,
-                       m_tiles, n_cg);
+    launch_tile_tail(true, L1 / 64);
     return nnue_launch_status("nnue_classifier_train_step");
   }
   if (phases & 1) {
@@ -1516,7 +1605,8 @@ int train_step_impl(const float* x, int pairwise, const float* w1, const float* 
 #define NNUE_TAIL(NT, V)                                                                                                                  \
   hipLaunchKernelGGL((tail_train_kernel<NT, V>), dim3(tail_grid), dim3(NT), (size_t)tail_lds, s, part, tail_slabs, b1, w2, b2, w3, b3, clip, \
                      labels, grad_scale / (float)B, B, L2, L3, C, h1, h2, logits, sample_loss, d_logits, d_z1, d_z2, bk, x, L1, x_g, d_z1_g)
-    if (C > 256) { if (vec) NNUE_TAIL(512, true); else NNUE_TAIL(512, false); }
+    if (tile_tail) launch_tile_tail(false, tail_slabs);
+    else if (C > 256) { if (vec) NNUE_TAIL(512, true); else NNUE_TAIL(512, false); }
     else { if (vec) NNUE_TAIL(128, true); else NNUE_TAIL(128, false); }
 #undef NNUE_TAIL
     if (d_x) {
@@ -1562,6 +1652,17 @@ int train_step_impl(const float* x, int pairwise, const float* w1, const float* 
   return nnue_launch_status("nnue_classifier_train_step");
 }
 }  // namespace
+
+#ifdef NNUE_ABLATIONS
+// the phase clocks of the last tail_dx_train_kernel launch: out[workgroup][kTdxClocks]; returns the workgroup count (or -1)
+extern "C" int nnue_cls_abl_tail_clocks(long long* out, int max_blocks) {
+  if (!g_tdx_clocks || !out) return -1;
+  const int n = g_tdx_clock_blocks < max_blocks ? g_tdx_clock_blocks : max_blocks;
+  if (hipDeviceSynchronize() != hipSuccess) return -1;
+  if (hipMemcpy(out, g_tdx_clocks, (size_t)n * kTdxClocks * sizeof(long long), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  return n;
+}
+#endif
 
 extern "C" int64_t nnue_classifier_train_scratch(int B, int L1, int L2, int L3, int C) {
   return nnue_classifier_train_scratch_bucketed(B, L1, L2, L3, C, 1);
