@@ -51,13 +51,7 @@ class EvalPlan:
         self.confusion = torch.zeros((k, k), dtype=torch.int64, device=self.dev)
         self.loss_sum = torch.zeros((), dtype=torch.float64, device=self.dev)
         self.metric_labels = torch.empty((batch,), dtype=torch.int64, device=self.dev) if c == 1 else self.labels
-        if self.path == "mfma":
-            self.feats = lib.FeatureMatrix.empty(batch, fps * gh * gw, f, l1, self.dev)
-        elif self.path == "bits":
-            self.feats = lib.FeatureBits.empty(batch, fps * gh * gw, f, l1, self.dev)
-        else:
-            self.feats = lib.ActList.empty(batch, fps * gh * gw, f, self.dev)
-        self.num_rows, self.l1 = f, l1
+        self.feats = lib.FT_FAMILIES[self.path].empty(batch, self.positions, f, l1, self.dev)
         self.graph = None
 
     def stale(self, model) -> bool:
@@ -68,17 +62,8 @@ class EvalPlan:
 
     def _body(self) -> None:
         thr, conv_w, ft_w, ft_b, w1, b1, w2, b2, w3, b3 = self.params
-        if self.path == "mfma":
-            lib.ftm_conv_binarize(self.images, conv_w, thr, self.stride, self.num_rows, self.l1, conv_out=self.conv_out, fm=self.feats)
-            lib.ftm_forward(ft_w, ft_b, self.feats, out=self.ft)
-        elif self.path == "bits":
-            lib.conv3x3_forward(self.images, conv_w, self.stride, out=self.conv_out)
-            lib.binarize_bits(self.conv_out, thr, self.num_rows, self.l1, bits=self.feats, stages=1)
-            lib.ftb_forward(ft_w, ft_b, self.feats, out=self.ft)
-        else:
-            lib.conv3x3_forward(self.images, conv_w, self.stride, out=self.conv_out)
-            lib.binarize_features(self.conv_out, thr, self.num_rows, act=self.feats)
-            lib.ft_forward(ft_w, ft_b, self.feats, out=self.ft)
+        self.feats.front(self.images, conv_w, thr, self.stride, self.conv_out)
+        self.feats.forward(ft_w, ft_b, out=self.ft)
         if self.bucket_plan is not None:
             lib.bucket_group(self.feats.n, self.positions, self.K, plan=self.bucket_plan)
         lib.classifier_forward(self.ft, True, w1, b1, w2, b2, w3, b3, self.clip, scratch=self.cls_scratch, out=self.acts,

@@ -336,6 +336,22 @@ def round_up(v: int, m: int) -> int:
     return (v + m - 1) // m * m
 
 
+# ---------------------------------------------------------------------------- the FeatureTransformer kernel families
+# Three kernel families run the FeatureTransformer on the binary map.  Each keeps one batch's active features in its own class
+# (FT_FAMILIES: "mfma" FeatureMatrix, "bits" FeatureBits, "list" ActList) and the three classes have the same members, thin
+# calls of the module-level ftm_* / ftb_* / ft_* functions, so a consumer picks the class once (ft_path) and never asks again:
+#   family, n (int32 [B]: active positions per sample), empty(batch, positions, num_rows, l1, device)
+#   binarize(conv_out, thr, stages=3)   stage 1: what the forward and the value gradient read; stage 2: what only the weight
+#       gradient reads, the bit family's transposed masks (the other two leave everything in stage 1: stages=2 launches nothing)
+#   front(images, conv_w, thr, stride, conv_out, patches=None)   images -> conv_out and stage 1, in the family's own launches
+#   forward(weight, bias, out=None, group=None)   group (a BucketPlan): the launch(es) also form the bucket grouping from n
+#   backward_weight(d_out, d_weight=None, d_bias=None, want_weight=True, want_bias=True), backward_values(d_out, weight, dst=None)
+def _gather_front(self, images, conv_w, thr, stride: int, conv_out, patches=None):
+    """front() of the two gather families: the conv launch, then the first stage of their own binarise launch."""
+    conv3x3_forward(images, conv_w, stride, out=conv_out)
+    self.binarize(conv_out, thr, stages=1)
+
+
 @dataclass
 class ActList:
     """Active-feature list + transposed coefficients (layout: include/nnue_hip.h)."""
@@ -346,19 +362,36 @@ class ActList:
     coefT: torch.Tensor  # float32 [F, ldb]
     cap: int
     ldb: int
+    family = "list"
 
-    @property
-    def batch(self) -> int:
-        return self.n.shape[0]
+    batch = property(lambda self: self.n.shape[0])
+    num_rows = property(lambda self: self.coefT.shape[0])
 
     @staticmethod
-    def empty(batch: int, cap: int, num_rows: int, device) -> "ActList":
-        ldb = round_up(batch, 64)
+    def empty(batch: int, positions: int, num_rows: int, l1, device=None) -> "ActList":
+        # l1 is not used (the lists do not depend on the table's width); the form without it, empty(batch, cap, num_rows, device), works too
+        cap, ldb, device = positions, round_up(batch, 64), l1 if device is None else device
         i32 = dict(dtype=torch.int32, device=device)
         return ActList(torch.empty((batch, cap), **i32), torch.empty((batch, cap), **i32),
                        torch.empty((batch, cap), dtype=torch.float32, device=device),
                        torch.empty((batch,), **i32),
                        torch.empty((num_rows, ldb), dtype=torch.float32, device=device), cap, ldb)
+
+    def binarize(self, conv_out, thr, stages: int = 3) -> "ActList":
+        return binarize_features(conv_out, thr, self.num_rows, act=self) if stages & 1 else self
+
+    def forward(self, weight, bias, out=None, group=None):
+        if group is not None:  # (the gather kernels have no workgroup to spare for it: a launch ahead of theirs)
+            bucket_group(self.n, self.cap, group.K, plan=group)
+        return ft_forward(weight, bias, self, out=out)
+
+    def backward_weight(self, d_out, d_weight=None, d_bias=None, want_weight: bool = True, want_bias: bool = True):
+        return ft_backward_weight(d_out, self, self.num_rows, d_weight, d_bias, want_weight, want_bias)
+
+    def backward_values(self, d_out, weight, dst=None):
+        return ft_backward_values(d_out, weight, self, self.cap, dst=dst)
+
+    front = _gather_front
 
 
 # ---------------------------------------------------------------------------- front end
@@ -425,7 +458,7 @@ def binarize_features(conv_out: torch.Tensor, thr: torch.Tensor, num_rows: int,
     thr = _need(thr.reshape(-1), torch.float32, "threshold", (fps,))
     cap = fps * gh * gw
     if act is None:
-        act = ActList.empty(b, cap, num_rows, conv_out.device)
+        act = ActList.empty(b, cap, num_rows, 0, conv_out.device)
     elif act.cap != cap or act.batch != b or act.coefT.shape != (num_rows, act.ldb):
         raise ValueError("binarize_features: act list does not match the map")
     _call("nnue_binarize_features", conv_out.data_ptr(), thr.data_ptr(), b, fps, gh, gw, num_rows,
@@ -443,6 +476,17 @@ def act_to_padded(act: ActList, width: int) -> Tuple[torch.Tensor, torch.Tensor]
     return idx, val
 
 
+def _ste_outputs(b: int, fps: int, gh: int, gw: int, dev, d_thr, d_weight, scratch):
+    """The two results and the scratch of the STE backward's two forms, allocated where the caller gave none."""
+    if d_thr is None:
+        d_thr = torch.empty((fps,), dtype=torch.float32, device=dev)
+    if d_weight is None:
+        d_weight = torch.empty((fps, 3, 3, 3), dtype=torch.float32, device=dev)
+    if scratch is None:
+        scratch = torch.empty((load().nnue_ste_conv_backward_scratch(b, fps, gh, gw),), dtype=torch.uint8, device=dev)
+    return d_thr, d_weight, scratch
+
+
 def ste_conv_backward(images, conv_out, thr, d_conv_out, stride: int,
                       d_thr: Optional[torch.Tensor] = None, d_weight: Optional[torch.Tensor] = None,
                       scratch: Optional[torch.Tensor] = None, stages: int = 3):
@@ -455,14 +499,7 @@ def ste_conv_backward(images, conv_out, thr, d_conv_out, stride: int,
     conv_out = _need(conv_out, torch.float32, "conv_out", (b, fps, gh, gw))
     d_conv_out = _need(d_conv_out, torch.float32, "d_conv_out").view(b, fps, gh, gw)
     thr = _need(thr.reshape(-1), torch.float32, "threshold", (fps,))
-    dev = images.device
-    if d_thr is None:
-        d_thr = torch.empty((fps,), dtype=torch.float32, device=dev)
-    if d_weight is None:
-        d_weight = torch.empty((fps, 3, 3, 3), dtype=torch.float32, device=dev)
-    need = load().nnue_ste_conv_backward_scratch(b, fps, gh, gw)
-    if scratch is None:
-        scratch = torch.empty((need,), dtype=torch.uint8, device=dev)
+    d_thr, d_weight, scratch = _ste_outputs(b, fps, gh, gw, images.device, d_thr, d_weight, scratch)
     _call("nnue_ste_conv_backward", images.data_ptr(), conv_out.data_ptr(), thr.data_ptr(), d_conv_out.data_ptr(),
           b, h, w, fps, stride, d_thr.data_ptr(), d_weight.data_ptr(), scratch.data_ptr(), scratch.numel(), int(stages),
           _stream(images))
@@ -479,14 +516,7 @@ def ste_conv_backward_patches(patches, conv_out, thr, d_conv_out, gh: int, gw: i
     patches = _need(patches, torch.float32, "patches", (27, b * gh * gw))
     d_conv_out = _need(d_conv_out, torch.float32, "d_conv_out").view(b, fps, gh, gw)
     thr = _need(thr.reshape(-1), torch.float32, "threshold", (fps,))
-    dev = patches.device
-    if d_thr is None:
-        d_thr = torch.empty((fps,), dtype=torch.float32, device=dev)
-    if d_weight is None:
-        d_weight = torch.empty((fps, 3, 3, 3), dtype=torch.float32, device=dev)
-    need = load().nnue_ste_conv_backward_scratch(b, fps, gh, gw)
-    if scratch is None:
-        scratch = torch.empty((need,), dtype=torch.uint8, device=dev)
+    d_thr, d_weight, scratch = _ste_outputs(b, fps, gh, gw, patches.device, d_thr, d_weight, scratch)
     _call("nnue_ste_conv_backward_patches", patches.data_ptr(), conv_out.data_ptr(), thr.data_ptr(), d_conv_out.data_ptr(), b, fps, gh, gw,
           d_thr.data_ptr(), d_weight.data_ptr(), scratch.data_ptr(), scratch.numel(), int(stages), _stream(patches))
     return d_thr, d_weight
@@ -505,7 +535,7 @@ def ft_prepare(idx: torch.Tensor, val: torch.Tensor, num_rows: int) -> ActList:
     idx = _need(idx, torch.int64, "feature_indices")
     val = _need(val, torch.float32, "feature_values")
     b, m = idx.shape
-    act = ActList.empty(b, m, num_rows, idx.device)
+    act = ActList.empty(b, m, num_rows, 0, idx.device)
     _call("nnue_ft_prepare", idx.data_ptr(), val.data_ptr(), b, m, num_rows, act.rows.data_ptr(), act.pos.data_ptr(),
           act.coef.data_ptr(), act.n.data_ptr(), act.coefT.data_ptr(), act.ldb, _stream(idx))
     return act
@@ -573,10 +603,27 @@ class FeatureBits:
     scratch: torch.Tensor  # uint8, split-slab workspace of the gather kernels
     positions: int       # P = fps*Gh*Gw
     num_rows: int        # F
+    family = "bits"
 
     @property
     def batch(self) -> int:
         return self.n.shape[0]
+
+    def binarize(self, conv_out, thr, stages: int = 3) -> "FeatureBits":
+        return binarize_bits(conv_out, thr, self.num_rows, 0, bits=self, stages=stages)  # (l1 only sizes a new object's scratch)
+
+    def forward(self, weight, bias, out=None, group=None):
+        if group is not None:  # (as ActList.forward)
+            bucket_group(self.n, self.positions, group.K, plan=group)
+        return ftb_forward(weight, bias, self, out=out)
+
+    def backward_weight(self, d_out, d_weight=None, d_bias=None, want_weight: bool = True, want_bias: bool = True):
+        return ftb_backward_weight(d_out, self, d_weight, d_bias, want_weight, want_bias)
+
+    def backward_values(self, d_out, weight, dst=None):
+        return ftb_backward_values(d_out, weight, self, dst=dst)
+
+    front = _gather_front
 
     @staticmethod
     def empty(batch: int, positions: int, num_rows: int, l1: int, device) -> "FeatureBits":
@@ -599,14 +646,15 @@ def ftb_supported(l1: int) -> bool:
     return bool(load().nnue_ftb_supported(int(l1)))
 
 
-def ft_path(num_rows: int, positions: int, l1: int, batch: int = 1) -> str:
-    """Which FeatureTransformer kernels the fused path uses for the binary map: "mfma" | "bits" | "list".
+def ft_path(num_rows: int, positions: int, l1: int, batch: int = 1, mode: Optional[str] = None) -> str:
+    """Which FeatureTransformer kernels the fused path uses for the binary map: "mfma" | "bits" | "list" (a key of FT_FAMILIES).
 
     "mfma" = dense f32-MFMA products over the float {0,1} map (fastest at the reference's ~43 % density and still
     ahead at 1 %); "bits" = tile-list kernels that stage table tiles in LDS once per sample tile; "list" = id-list
-    gather kernels (any shape).  NNUE_FT_PATH=mfma|bits|list forces one where the shape allows it; the default
-    takes the first of mfma, bits, list that supports the shape."""
-    mode = os.environ.get("NNUE_FT_PATH", "auto")
+    gather kernels (any shape).  mode = "mfma" | "bits" | "list" forces one where the shape allows it; "auto" takes the first of
+    mfma, bits, list that supports the shape.  mode=None reads NNUE_FT_PATH (default "auto"): a given mode wins over it."""
+    if mode is None:
+        mode = os.environ.get("NNUE_FT_PATH", "auto")
     # the product kernels address every operand with 32-bit byte offsets (batch-sized ones included)
     fits = (batch + 256) * positions * 4 < 2 ** 31 and (batch + 256) * l1 * 4 < 2 ** 31
     can_mfma, can_bits = fits and ftm_supported(num_rows, positions, l1), ftb_supported(l1)
@@ -617,11 +665,6 @@ def ft_path(num_rows: int, positions: int, l1: int, batch: int = 1) -> str:
     if can_mfma:
         return "mfma"
     return "bits" if can_bits else "list"
-
-
-def use_bit_path(num_rows: int, l1: int) -> bool:
-    """True when the LDS-staged tile-list kernels are allowed for this width (see ft_path)."""
-    return os.environ.get("NNUE_FT_PATH", "auto") != "list" and ftb_supported(l1)
 
 
 def binarize_bits(conv_out: torch.Tensor, thr: torch.Tensor, num_rows: int, l1: int,
@@ -704,6 +747,7 @@ class FeatureMatrix:
     scratch: torch.Tensor  # uint8, split-K slabs of the forward
     positions: int
     num_rows: int
+    family = "mfma"
 
     def __init__(self, bits, n, sink, scratch, positions, num_rows):
         self.bits, self.n, self.sink, self.scratch, self.positions, self.num_rows = bits, n, sink, scratch, positions, num_rows
@@ -719,6 +763,25 @@ class FeatureMatrix:
                              torch.empty((batch,), dtype=torch.float32, device=device),
                              torch.empty((max(16, ftm_scratch_bytes(batch, num_rows, positions, l1)),), dtype=torch.uint8, device=device),
                              positions, num_rows)
+
+    def binarize(self, conv_out, thr, stages: int = 3) -> "FeatureMatrix":  # (l1 = 0 here and in front: it only sizes a new object's scratch)
+        return ftm_binarize(conv_out, thr, self.num_rows, 0, fm=self) if stages & 1 else self
+
+    def front(self, images, conv_w, thr, stride: int, conv_out, patches=None):
+        """conv + map + counts in ONE launch; patches: it also leaves the images' im2col form."""
+        ftm_conv_binarize(images, conv_w, thr, stride, self.num_rows, 0, conv_out=conv_out, fm=self, patches=patches)
+
+    def forward(self, weight, bias, out=None, group=None):
+        return ftm_forward(weight, bias, self, out=out, group=group)  # (the grouping rides in the launch)
+
+    def backward_weight(self, d_out, d_weight=None, d_bias=None, want_weight: bool = True, want_bias: bool = True):
+        return ftm_backward_weight(d_out, self, d_weight, d_bias, want_weight, want_bias)
+
+    def backward_values(self, d_out, weight, dst=None):
+        return ftm_backward_values(d_out, weight, self, dst=dst)
+
+
+FT_FAMILIES = {"mfma": FeatureMatrix, "bits": FeatureBits, "list": ActList}  # ft_path's answer -> the family's class
 
 
 def ftm_binarize(conv_out: torch.Tensor, thr: torch.Tensor, num_rows: int, l1: int,
@@ -737,12 +800,9 @@ def ftm_binarize(conv_out: torch.Tensor, thr: torch.Tensor, num_rows: int, l1: i
     return fm
 
 
-def ftm_conv_binarize(images: torch.Tensor, weight: torch.Tensor, thr: torch.Tensor, stride: int, num_rows: int, l1: int,
-                      conv_out: Optional[torch.Tensor] = None, fm: Optional[FeatureMatrix] = None,
-                      patches: Optional[torch.Tensor] = None):
-    """conv3x3_forward + ftm_binarize in one launch; returns (conv_out, fm), bitwise the two separate calls.
-    patches (float32 [27, B*Gh*Gw]): the launch also leaves the im2col form of the images (ste_conv_backward_patches reads
-    it)."""
+def _conv_front(who: str, images, weight, thr, stride: int, num_rows: int, l1: int, conv_out, fm):
+    """What the one-launch conv + map forms share: images, conv weight and thresholds checked, conv_out and the map checked or
+    allocated.  Returns (images, weight, thr, (b, h, w, fps, gh, gw), conv_out, fm)."""
     images = _need(images, torch.float32, "images")
     if images.dim() != 4 or images.shape[1] != 3:
         raise ValueError(f"images: expected [B,3,H,W], got {tuple(images.shape)}")
@@ -756,11 +816,22 @@ def ftm_conv_binarize(images: torch.Tensor, weight: torch.Tensor, thr: torch.Ten
     if conv_out is None:
         conv_out = torch.empty((b, fps, gh, gw), dtype=torch.float32, device=images.device)
     elif tuple(conv_out.shape) != (b, fps, gh, gw):
-        raise ValueError("ftm_conv_binarize: conv_out has the wrong shape")
+        raise ValueError(f"{who}: conv_out has the wrong shape")
     if fm is None:
         fm = FeatureMatrix.empty(b, fps * gh * gw, num_rows, l1, images.device)
     elif fm.batch != b or fm.positions != fps * gh * gw or fm.num_rows != num_rows:
-        raise ValueError("ftm_conv_binarize: buffers do not match the map")
+        raise ValueError(f"{who}: buffers do not match the map")
+    return images, weight, thr, (b, h, w, fps, gh, gw), conv_out, fm
+
+
+def ftm_conv_binarize(images: torch.Tensor, weight: torch.Tensor, thr: torch.Tensor, stride: int, num_rows: int, l1: int,
+                      conv_out: Optional[torch.Tensor] = None, fm: Optional[FeatureMatrix] = None,
+                      patches: Optional[torch.Tensor] = None):
+    """conv3x3_forward + ftm_binarize in one launch; returns (conv_out, fm), bitwise the two separate calls.
+    patches (float32 [27, B*Gh*Gw]): the launch also leaves the im2col form of the images (ste_conv_backward_patches reads
+    it)."""
+    images, weight, thr, (b, h, w, fps, gh, gw), conv_out, fm = _conv_front("ftm_conv_binarize", images, weight, thr, stride, num_rows, l1,
+                                                                            conv_out, fm)
     if patches is not None:
         patches = _need(patches, torch.float32, "patches", (27, b * gh * gw))
         _call("nnue_ftm_conv_binarize_patches", images.data_ptr(), weight.data_ptr(), thr.data_ptr(), b, h, w, fps, int(stride), int(num_rows),
@@ -797,21 +868,28 @@ def ftm_forward_l1_supported(batch: int, num_rows: int, positions: int, l1: int,
     return bool(load().nnue_ftm_forward_l1_supported(int(batch), int(num_rows), int(positions), int(l1), int(l2)))
 
 
-def ftm_forward_l1(weight: torch.Tensor, bias: torch.Tensor, fm: FeatureMatrix, w1: torch.Tensor, part: torch.Tensor,
-                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """ftm_forward + the classifier's layer-1 slabs part[L1/64][B][L2] (written at the start of `part`, the
-    classifier's scratch buffer; consumed by classifier_train_step(phases | 8))."""
+def _forward_l1_operands(who: str, weight, bias, fm: FeatureMatrix, w1, part, out):
+    """What the two fused-forward forms share: table, bias, w1 and the slab buffer checked, the output allocated where none is
+    given.  Returns (weight, bias, w1, (f, l1, l2), out)."""
     weight = _need(weight, torch.float32, "input.weight")
     f, l1 = weight.shape
     bias = _need(bias, torch.float32, "input.bias", (l1,))
     l2 = w1.shape[0]
     w1 = _need(w1, torch.float32, "classifier.0.weight", (l2, l1))
     if f != fm.num_rows:
-        raise ValueError("ftm_forward_l1: the map was built for a different table")
+        raise ValueError(f"{who}: the map was built for a different table")
     if not part.is_cuda or part.numel() * part.element_size() < (l1 // 64) * fm.batch * l2 * 4:
-        raise ValueError("ftm_forward_l1: part buffer too small for [L1/64][B][L2] floats")
+        raise ValueError(f"{who}: part buffer too small for [L1/64][B][L2] floats")
     if out is None:
         out = torch.empty((fm.batch, l1), dtype=torch.float32, device=weight.device)
+    return weight, bias, w1, (f, l1, l2), out
+
+
+def ftm_forward_l1(weight: torch.Tensor, bias: torch.Tensor, fm: FeatureMatrix, w1: torch.Tensor, part: torch.Tensor,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ftm_forward + the classifier's layer-1 slabs part[L1/64][B][L2] (written at the start of `part`, the
+    classifier's scratch buffer; consumed by classifier_train_step(phases | 8))."""
+    weight, bias, w1, (f, l1, l2), out = _forward_l1_operands("ftm_forward_l1", weight, bias, fm, w1, part, out)
     _call("nnue_ftm_forward_l1", fm.bits.data_ptr(), fm.sink.data_ptr(), weight.data_ptr(), bias.data_ptr(), w1.data_ptr(),
           fm.batch, f, fm.positions, l1, l2, out.data_ptr(), part.data_ptr(), _stream(weight))
     return out
@@ -832,28 +910,12 @@ def ftm_conv_binarize_planes(images: torch.Tensor, weight: torch.Tensor, thr: to
     (`planes`: a uint8 buffer of ftm_forward_planes_bytes); returns (conv_out, fm), bitwise ftm_conv_binarize's.
     val_planes (a uint8 buffer of ftm_value_planes_bytes; shapes: ftm_value_planes_supported): the launch also leaves the planes
     ftm_backward(val_planes=...) reads."""
-    images = _need(images, torch.float32, "images")
-    if images.dim() != 4 or images.shape[1] != 3:
-        raise ValueError(f"images: expected [B,3,H,W], got {tuple(images.shape)}")
-    b, _, h, w = images.shape
-    weight = _need(weight, torch.float32, "conv.weight")
-    fps = weight.shape[0]
-    if tuple(weight.shape) != (fps, 3, 3, 3):
-        raise ValueError("conv.weight: expected [fps,3,3,3]")
-    thr = _need(thr.reshape(-1), torch.float32, "threshold", (fps,))
     table = _need(table, torch.float32, "input.weight")
     f, l1 = table.shape
     if planes is not None or val_planes is None:  # (planes=None with val_planes: the value planes alone)
         planes = _need(planes, torch.uint8, "planes")
-    gh, gw = conv_out_hw(h, w, stride)
-    if conv_out is None:
-        conv_out = torch.empty((b, fps, gh, gw), dtype=torch.float32, device=images.device)
-    elif tuple(conv_out.shape) != (b, fps, gh, gw):
-        raise ValueError("ftm_conv_binarize_planes: conv_out has the wrong shape")
-    if fm is None:
-        fm = FeatureMatrix.empty(b, fps * gh * gw, f, l1, images.device)
-    elif fm.batch != b or fm.positions != fps * gh * gw or fm.num_rows != f:
-        raise ValueError("ftm_conv_binarize_planes: buffers do not match the map")
+    images, weight, thr, (b, h, w, fps, gh, gw), conv_out, fm = _conv_front("ftm_conv_binarize_planes", images, weight, thr, stride, f, l1,
+                                                                            conv_out, fm)
     if val_planes is not None:
         val_planes = _need(val_planes, torch.uint8, "val_planes")
         _call("nnue_ftm_conv_binarize_value_planes", images.data_ptr(), weight.data_ptr(), thr.data_ptr(), b, h, w, fps, int(stride), f,
@@ -869,18 +931,8 @@ def ftm_conv_binarize_planes(images: torch.Tensor, weight: torch.Tensor, thr: to
 def ftm_forward_l1_planes(weight: torch.Tensor, bias: torch.Tensor, fm: FeatureMatrix, planes: torch.Tensor, w1: torch.Tensor,
                           part: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """ftm_forward_l1 reading the planes ftm_conv_binarize_planes wrote from `weight` (bitwise its 32-row bf16 form)."""
-    weight = _need(weight, torch.float32, "input.weight")
-    f, l1 = weight.shape
-    bias = _need(bias, torch.float32, "input.bias", (l1,))
-    l2 = w1.shape[0]
-    w1 = _need(w1, torch.float32, "classifier.0.weight", (l2, l1))
     planes = _need(planes, torch.uint8, "planes")
-    if f != fm.num_rows:
-        raise ValueError("ftm_forward_l1_planes: the map was built for a different table")
-    if not part.is_cuda or part.numel() * part.element_size() < (l1 // 64) * fm.batch * l2 * 4:
-        raise ValueError("ftm_forward_l1_planes: part buffer too small for [L1/64][B][L2] floats")
-    if out is None:
-        out = torch.empty((fm.batch, l1), dtype=torch.float32, device=weight.device)
+    weight, bias, w1, (f, l1, l2), out = _forward_l1_operands("ftm_forward_l1_planes", weight, bias, fm, w1, part, out)
     _call("nnue_ftm_forward_l1_planes", fm.bits.data_ptr(), fm.sink.data_ptr(), planes.data_ptr(), planes.numel(), weight.data_ptr(),
           bias.data_ptr(), w1.data_ptr(), fm.batch, f, fm.positions, l1, l2, out.data_ptr(), part.data_ptr(), _stream(weight))
     return out

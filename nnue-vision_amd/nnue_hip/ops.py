@@ -87,16 +87,11 @@ class NnueFn(torch.autograd.Function):
         images = images.contiguous()
         conv_out = lib.conv3x3_forward(images, conv_w, stride)
         # binary features: dense MFMA products over the float map, else bit masks + LDS-staged tiles, else id lists
-        ctx.path = lib.ft_path(ft_w.shape[0], conv_out[0].numel(), ft_w.shape[1], conv_out.shape[0])
-        if ctx.path == "mfma":
-            feats = lib.ftm_binarize(conv_out, thr, ft_w.shape[0], ft_w.shape[1])
-            ft = lib.ftm_forward(ft_w, ft_b, feats)
-        elif ctx.path == "bits":
-            feats = lib.binarize_bits(conv_out, thr, ft_w.shape[0], ft_w.shape[1])
-            ft = lib.ftb_forward(ft_w, ft_b, feats)
-        else:
-            feats = lib.binarize_features(conv_out, thr, ft_w.shape[0])
-            ft = lib.ft_forward(ft_w, ft_b, feats)
+        f, l1 = ft_w.shape
+        ctx.path = lib.ft_path(f, conv_out[0].numel(), l1, conv_out.shape[0])
+        feats = lib.FT_FAMILIES[ctx.path].empty(conv_out.shape[0], conv_out[0].numel(), f, l1, conv_out.device)
+        feats.binarize(conv_out, thr, stages=3)
+        ft = feats.forward(ft_w, ft_b)
         # bucketed layer stacks: each sample's stack follows from its active-feature count, grouped on the device
         plan = lib.bucket_group(feats.n, conv_out[0].numel(), w1.shape[0]) if w1.dim() == 3 else None
         h1, h2, logits = lib.classifier_forward(ft, True, w1, b1, w2, b2, w3, b3, clip, buckets=plan)
@@ -112,20 +107,10 @@ class NnueFn(torch.autograd.Function):
         d_ft, g_cls = lib.classifier_backward(ft, True, w1, w2, w3, h1, h2, d_logits.contiguous(), ctx.clip, buckets=ctx.plan)
         d_ftw = d_ftb = d_thr = d_conv_w = d_images = None
         if need[3] or need[4]:
-            if ctx.path == "mfma":
-                d_ftw, d_ftb = lib.ftm_backward_weight(d_ft, feats, want_weight=need[3], want_bias=need[4])
-            elif ctx.path == "bits":
-                d_ftw, d_ftb = lib.ftb_backward_weight(d_ft, feats, want_weight=need[3], want_bias=need[4])
-            else:
-                d_ftw, d_ftb = lib.ft_backward_weight(d_ft, feats, ft_w.shape[0], want_weight=need[3], want_bias=need[4])
+            d_ftw, d_ftb = feats.backward_weight(d_ft, want_weight=need[3], want_bias=need[4])
         if need[0] or need[1] or need[2]:
             # value gradient of the binary features == d(conv_out) (identity STE, nnue.py:33)
-            if ctx.path == "mfma":
-                d_conv_out = lib.ftm_backward_values(d_ft, ft_w, feats).view_as(conv_out)
-            elif ctx.path == "bits":
-                d_conv_out = lib.ftb_backward_values(d_ft, ft_w, feats).view_as(conv_out)
-            else:
-                d_conv_out = lib.ft_backward_values(d_ft, ft_w, feats, feats.cap).view_as(conv_out)
+            d_conv_out = feats.backward_values(d_ft, ft_w).view_as(conv_out)
             if need[1] or need[2]:
                 d_thr, d_conv_w = lib.ste_conv_backward(images, conv_out, thr, d_conv_out, ctx.stride)
                 d_thr = d_thr.view_as(thr)

@@ -46,6 +46,8 @@ class StepMode:
     merged_backward_launch: bool  # one launch produces weight gradient, value gradient (d_conv_out) and tail rows
 
     conv_planes = property(lambda self: self.fwd_planes or self.val_planes)  # the conv launch's riders leave planes of the table
+    use_mfma = property(lambda self: self.ft_path == "mfma")
+    use_bits = property(lambda self: self.ft_path == "bits")
 
     def describe(self) -> str:
         """One line, as a row of profiles/trainer_modes.md: path | flags on | sq | phases | STE."""
@@ -61,15 +63,15 @@ def _on(knob: str) -> bool:
 
 def resolve(*, B: int, H: int, W: int, stride: int, fps: int, F: int, L1: int, L2: int, L3: int, C: int, K: int, optimizer: str,
             dp: DpFacts = DpFacts(), use_graph: bool = True, lead_names: Sequence[str], tbl_lo: int, tbl_hi: int,
-            count: int) -> StepMode:
+            count: int, ft_path: Optional[str] = None) -> StepMode:
     """lead_names: the first parameters of the flat layout; tbl_lo/tbl_hi: the table rows the product d_W = A^T d_out covers, as
-    a range of the flat buffers; count: their length (FlatLayout)."""
+    a range of the flat buffers; count: their length (FlatLayout); ft_path: lib.ft_path's ``mode`` (None: NNUE_FT_PATH)."""
     gh, gw = lib.conv_out_hw(H, W, stride)
     P = fps * gh * gw
     sgd, lead = optimizer == "sgd", list(lead_names)
     # binary features: float {0,1} map + dense MFMA products when the shape allows, else bit masks + LDS-staged
     # gather kernels, else id lists
-    ft_path = lib.ft_path(F, P, L1, B)
+    ft_path = lib.ft_path(F, P, L1, B, mode=ft_path)
     mfma = ft_path == "mfma"
     # Large strides (the taps of neighbouring positions do not overlap: 224x224 at stride 7 reads 3 of every 7 rows and the
     # backward would gather them again): the conv launch also leaves the im2col form of the images -- 27 floats per position,

@@ -159,7 +159,9 @@ class NnueTrainer:
 
     def __init__(self, model, batch_size: int, image_hw: Tuple[int, int], lr: float, momentum: float = 0.0,
                  weight_decay: float = 0.0, max_grad_norm: float = 0.0, group=None, use_graph: bool = True,
-                 input_slots: int = 1, optimizer: str = "sgd", betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8):
+                 input_slots: int = 1, optimizer: str = "sgd", betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
+                 ft_path: Optional[str] = None):
+        """ft_path: the FeatureTransformer kernel family, as lib.ft_path's ``mode`` (None: NNUE_FT_PATH decides)."""
         lib.load()
         p0 = next(model.parameters())
         if not p0.is_cuda:
@@ -209,17 +211,14 @@ class NnueTrainer:
         # the table rows the product d_W = A^T d_out covers, as a range of the flat buffers
         tbl_lo = self.layout.offsets[self.layout.names.index("input.weight")]
         tbl_hi = tbl_lo + min(self.F - 1, self.P) * self.L1
-        m = self.mode = step_mode.resolve(
+        # ``self.mode`` is the one store: MODE_NAMES (below the class) makes its flags readable on the trainer, read-only
+        self.mode = step_mode.resolve(
             B=B, H=self.H, W=self.W, stride=self.stride, fps=self.fps, F=self.F, L1=self.L1, L2=self.L2, L3=self.L3, C=self.C,
             K=self.K, optimizer=optimizer, dp=step_mode.DpFacts(self.dp.collectives, self.dp.world, self.dp.buckets, self.dp.backend),
-            use_graph=use_graph, lead_names=self.layout.names[:3], tbl_lo=tbl_lo, tbl_hi=tbl_hi, count=self.layout.count)
-        self.ft_path, self.use_mfma, self.use_bits = m.ft_path, m.ft_path == "mfma", m.ft_path == "bits"
-        self.use_patches, self.fuse_l1, self.fwd_planes = m.use_patches, m.fuse_l1, m.fwd_planes
-        self.merge_backward, self.ride_dw1, self.ride_small, self.fuse_tail_dx = m.merge_backward, m.ride_dw1, m.ride_small, m.fuse_tail_dx
-        self.defer_ste, self.ride_ste, self.ste_chunks = m.defer_ste, m.ride_ste, m.ste_chunks
-        self.fuse_table_update, self.fuse_next_forward, self.grads_materialised = m.fuse_table_update, m.fuse_next_forward, m.grads_materialised
-        self.factor_exchange, self.sharded_update, self.sq_range = m.factor_exchange, m.sharded_update, m.sq_range
-        self.capture_collectives = m.capture_collectives  # (cleared when a capture fails)
+            use_graph=use_graph, lead_names=self.layout.names[:3], tbl_lo=tbl_lo, tbl_hi=tbl_hi, count=self.layout.count, ft_path=ft_path)
+        # the two names that are not the mode's: capture_collectives is run-time state (a failed capture clears it, the mode gives
+        # its start), and ``val_planes`` further down is the plane BUFFER (the flag is ``self.mode.val_planes``)
+        self.capture_collectives = self.mode.capture_collectives
 
         # ---- static activations and scratch, allocated from the mode
         # input ring: a loader fills slot k while slot k-1 trains; kernels read the slots in place
@@ -227,15 +226,14 @@ class NnueTrainer:
                        for _ in range(max(1, input_slots))]
         self.images, self.labels = self.inputs[0]
         self.conv_out = torch.empty((B, self.fps, self.gh, self.gw), **f32)
-        self.fm = lib.FeatureMatrix.empty(B, self.P, self.F, self.L1, self.dev) if self.use_mfma else None
-        self.patches = torch.empty((27, B * self.gh * self.gw), **f32) if self.use_patches else None  # the images' im2col form
+        # the live map of the step, in the mode's kernel family (``fm`` / ``bits`` / ``act`` name it by family)
+        self.feats = lib.FT_FAMILIES[self.mode.ft_path].empty(B, self.P, self.F, self.L1, self.dev)
+        self.patches = torch.empty((27, B * self.gh * self.gw), **f32) if self.mode.use_patches else None  # the images' im2col form
         self.fx = None
-        if self.factor_exchange:
+        if self.mode.factor_exchange:
             self.fx = lib.FactorExchange(self.dp.world, self.dp.rank, B, self.P, self.F, self.L1, head=tbl_lo, tail_lo=tbl_hi,
                                          tail=self.layout.count - tbl_hi, device=self.dev)
-            self.fm.sink = self.fx.sink  # written by the binarise kernel straight into this rank's chunk
-        self.bits = lib.FeatureBits.empty(B, self.P, self.F, self.L1, self.dev) if self.use_bits else None
-        self.act = lib.ActList.empty(B, self.P, self.F, self.dev) if self.ft_path == "list" else None
+            self.feats.sink = self.fx.sink  # written by the binarise kernel straight into this rank's chunk
         self.ft = torch.empty((B, self.L1), **f32)
         self.h1 = torch.empty((B, self.L2), **f32)
         self.h2 = torch.empty((B, self.L3), **f32)
@@ -253,10 +251,10 @@ class NnueTrainer:
         self.bucket_plan = lib.BucketPlan(B, self.K, self.dev) if self.K > 1 else None
         # the STE launch's own scratch, or the partials the merged backward's ride leaves (fps * 28 outputs, float)
         self.ste_scratch = torch.empty((max(16, lib.load().nnue_ste_conv_backward_scratch(B, self.fps, self.gh, self.gw),
-                                            self.fps * 28 * self.ste_chunks * 4 if self.ride_ste else 0),), **u8)
+                                            self.fps * 28 * self.mode.ste_chunks * 4 if self.mode.ride_ste else 0),), **u8)
         self.sgd_scratch = torch.empty((lib.sgd_scratch_bytes(self.layout.count),), **u8)
-        self.planes = (torch.empty((lib.ftm_forward_planes_bytes(B, self.F, self.P, self.L1),), **u8) if self.fwd_planes else None)
-        if self.sharded_update:
+        self.planes = (torch.empty((lib.ftm_forward_planes_bytes(B, self.F, self.P, self.L1),), **u8) if self.mode.fwd_planes else None)
+        if self.mode.sharded_update:
             per = self.layout.count // self.dp.world
             self.grad_shard = torch.empty((per,), **f32)
             self.norm_parts = 256
@@ -273,22 +271,22 @@ class NnueTrainer:
         self._side = torch.cuda.Stream(device=self.dev) if use_graph else None
         # sq_partial: the sums of squares of the table's share (flat_grads[sq_range]) of the clip norm, left by its producer;
         # the Gram form (m.sq == "gram") also takes its scratch and leaves the clip coefficient for the table's update
-        self.sq_partial = torch.empty((m.sq_count,), **f32) if m.sq != "none" else None
+        self.sq_partial = torch.empty((self.mode.sq_count,), **f32) if self.mode.sq != "none" else None
         self.gram = self.clip_coef = None
-        if m.sq == "gram":
-            self.gram = torch.zeros((lib.ftm_gram_scratch(self.fx.g_fm if self.factor_exchange else self.fm),), **f32)
+        if self.mode.sq == "gram":
+            self.gram = torch.zeros((lib.ftm_gram_scratch(self.fx.g_fm if self.mode.factor_exchange else self.feats),), **f32)
             self.clip_coef = torch.ones((), **f32)
-        self.val_planes = torch.empty((lib.ftm_value_planes_bytes(B, self.F, self.P, self.L1),), **u8) if m.val_planes else None
-        self.fm_alt = lib.FeatureMatrix.empty(B, self.P, self.F, self.L1, self.dev) if self.fuse_next_forward else None
+        self.val_planes = torch.empty((lib.ftm_value_planes_bytes(B, self.F, self.P, self.L1),), **u8) if self.mode.val_planes else None
+        self.fm_alt = lib.FeatureMatrix.empty(B, self.P, self.F, self.L1, self.dev) if self.mode.fuse_next_forward else None
         if self.fm_alt is not None and self.fx is not None:
             self.fm_alt.sink = self.fx.sink  # (both local maps' sink counts live in this rank's chunk: only one of them is live at a time)
         self._last_alt = False  # the last step's map is the second one (an even-length step group)
         self.d_z1 = self.ft_rider = None  # the operands of the merged backward's d_w1 rider, out of the classifier's scratch
-        if self.ride_dw1 and self.K == 1:
+        if self.mode.ride_dw1 and self.K == 1:
             off = lib.classifier_train_dz1_offset(B, self.L1, self.L2, self.L3, self.C, True)
             self.d_z1 = self.cls_scratch[off:off + B * self.L2 * 4].view(torch.float32).view(B, self.L2)
             self.ft_rider = self.ft
-        elif self.ride_dw1:
+        elif self.mode.ride_dw1:
             # bucketed stacks: the rider contracts each bucket's own rows, so its operands are the grouped-row copies
             # the classifier's per-sample kernel leaves in the scratch
             rows = self.bucket_plan.tiles * 16
@@ -361,85 +359,61 @@ class NnueTrainer:
         return self._riders[key]
 
     def _segment(self, name: str) -> None:
-        p, g = self.p, self.g
+        """The branches here are the launches only the product family has (plane riders, fused layer 1, merged backward, Gram
+        norm / table update, factor exchange: the mode has them on that family alone); everything else is the live map's own
+        member, whatever its family."""
+        p, g, feats = self.p, self.g, self.feats
         if name == "front":
             if self.mode.conv_planes:  # conv + {0,1} map + counts, and the table's bf16 planes from the same launch's riders
                 lib.ftm_conv_binarize_planes(self.images, p["conv.weight"], p["visual_threshold"], self.stride, p["input.weight"], self.L2,
-                                             self.planes, conv_out=self.conv_out, fm=self.fm, val_planes=self.val_planes)
-                return
-            if self.use_mfma:  # conv + {0,1} map + counts in one launch
-                lib.ftm_conv_binarize(self.images, p["conv.weight"], p["visual_threshold"], self.stride, self.F, self.L1,
-                                      conv_out=self.conv_out, fm=self.fm, patches=self.patches)
-                return
-            lib.conv3x3_forward(self.images, p["conv.weight"], self.stride, out=self.conv_out)
-            if self.use_bits:
-                lib.binarize_bits(self.conv_out, p["visual_threshold"], self.F, self.L1, bits=self.bits, stages=1)
-            else:
-                lib.binarize_features(self.conv_out, p["visual_threshold"], self.F, act=self.act)
-        elif name == "transpose":
-            if self.use_bits:
-                lib.binarize_bits(self.conv_out, p["visual_threshold"], self.F, self.L1, bits=self.bits, stages=2)
+                                             self.planes, conv_out=self.conv_out, fm=feats, val_planes=self.val_planes)
+            else:  # the product family: one launch; the gather families: conv, then the per-sample half of their binarise
+                feats.front(self.images, p["conv.weight"], p["visual_threshold"], self.stride, self.conv_out, patches=self.patches)
+        elif name == "transpose":  # (the bit family's transposed masks; nothing in the other two)
+            feats.binarize(self.conv_out, p["visual_threshold"], stages=2)
         elif name == "forward":
-            if self.bucket_plan is not None and not self.use_mfma:  # stack of each sample from the counts the binarise kernel just wrote
-                feats = self.bits if self.use_bits else self.act
-                lib.bucket_group(feats.n, self.P, self.K, plan=self.bucket_plan)
-            # (product form: the grouping rides in the FeatureTransformer forward launch as one extra workgroup)
-            if self.fuse_l1:
+            if self.mode.fuse_l1:
                 # the forward's epilogue also forms the classifier's layer-1 slabs (start of its scratch)
-                if self.fwd_planes:
-                    lib.ftm_forward_l1_planes(p["input.weight"], p["input.bias"], self.fm, self.planes, p["classifier.classifier.0.weight"],
+                if self.mode.fwd_planes:
+                    lib.ftm_forward_l1_planes(p["input.weight"], p["input.bias"], feats, self.planes, p["classifier.classifier.0.weight"],
                                               self.cls_scratch, out=self.ft)
                 else:
-                    lib.ftm_forward_l1(p["input.weight"], p["input.bias"], self.fm, p["classifier.classifier.0.weight"], self.cls_scratch,
+                    lib.ftm_forward_l1(p["input.weight"], p["input.bias"], feats, p["classifier.classifier.0.weight"], self.cls_scratch,
                                        out=self.ft)
-                self._cls_step(self.mode.phases)
-                return
-            if self.use_mfma:
-                lib.ftm_forward(p["input.weight"], p["input.bias"], self.fm, out=self.ft, group=self.bucket_plan)
-            elif self.use_bits:
-                lib.ftb_forward(p["input.weight"], p["input.bias"], self.bits, out=self.ft)
             else:
-                lib.ft_forward(p["input.weight"], p["input.bias"], self.act, out=self.ft)
+                # several stacks: the stack of each sample from the counts the binarise kernel just wrote (product family: one
+                # extra workgroup of the forward launch; gather families: a launch ahead of it)
+                feats.forward(p["input.weight"], p["input.bias"], out=self.ft, group=self.bucket_plan)
             self._cls_step(self.mode.phases)
         elif name == "ft_wgrad":
-            if self.factor_exchange:
+            if self.mode.factor_exchange:
                 # this rank's share of the rows the product does not cover; they travel with the small gradients, the
                 # norm and the product wait for the global factors (_exchange_and_update)
-                lib.ftm_backward_tail_rows(self.d_ft, self.fm, g["input.weight"], g["input.bias"])
-            elif self.fuse_table_update:
+                lib.ftm_backward_tail_rows(self.d_ft, feats, g["input.weight"], g["input.bias"])
+            elif self.mode.fuse_table_update:
                 # rows the product does not cover (bias, clamp-sink row, unreachable rows) + the Gram form of the norm;
                 # the product itself is part of the update (_update)
                 # (the tail rows' workgroups ride in the Gram product's launch)
-                lib.ftm_gram_sqnorm(self.fm, self.d_ft, self.gram, self.sq_partial, tail=(g["input.weight"], g["input.bias"]))
+                lib.ftm_gram_sqnorm(feats, self.d_ft, self.gram, self.sq_partial, tail=(g["input.weight"], g["input.bias"]))
             elif self.mode.merged_backward_launch:
                 # weight gradient, value gradient and tail rows share one launch (independent work, all read d_ft)
-                lib.ftm_backward(self.d_ft, p["input.weight"], self.fm, d_weight=g["input.weight"], d_bias=g["input.bias"],
-                                 dst=None if self.ride_ste else self.d_conv_out, ft=self.ft_rider, d_z1=self.d_z1,
-                                 d_w1=g["classifier.classifier.0.weight"] if self.ride_dw1 else None, sq_partial=self.sq_partial,
-                                 buckets=self.bucket_plan, small=self._rider(self.loss) if self.ride_small else None,
+                lib.ftm_backward(self.d_ft, p["input.weight"], feats, d_weight=g["input.weight"], d_bias=g["input.bias"],
+                                 dst=None if self.mode.ride_ste else self.d_conv_out, ft=self.ft_rider, d_z1=self.d_z1,
+                                 d_w1=g["classifier.classifier.0.weight"] if self.mode.ride_dw1 else None, sq_partial=self.sq_partial,
+                                 buckets=self.bucket_plan, small=self._rider(self.loss) if self.mode.ride_small else None,
                                  ste=((self.images, self.conv_out, p["visual_threshold"], self.stride, self.ste_scratch, self.patches)
-                                      if self.ride_ste else None), val_planes=self.val_planes)
-            elif self.use_mfma:
-                lib.ftm_backward_weight(self.d_ft, self.fm, d_weight=g["input.weight"], d_bias=g["input.bias"])
-            elif self.use_bits:
-                lib.ftb_backward_weight(self.d_ft, self.bits, d_weight=g["input.weight"], d_bias=g["input.bias"])
+                                      if self.mode.ride_ste else None), val_planes=self.val_planes)
             else:
-                lib.ft_backward_weight(self.d_ft, self.act, self.F, d_weight=g["input.weight"], d_bias=g["input.bias"])
+                feats.backward_weight(self.d_ft, d_weight=g["input.weight"], d_bias=g["input.bias"])
         elif name == "cls_wgrad":
-            if not self.ride_dw1:  # else the small gradients already rode in the d_x launch of "forward"
+            if not self.mode.ride_dw1:  # else the small gradients already rode in the d_x launch of "forward"
                 self._cls_step(lib.CLS_PHASE_SMALL | lib.CLS_DW1_BESIDE_DX)
         elif name == "tail":
-            if self.mode.merged_backward_launch:
-                pass  # d_conv_out came out of the merged launch in "ft_wgrad"
-            elif self.use_mfma:
-                lib.ftm_backward_values(self.d_ft, p["input.weight"], self.fm, dst=self.d_conv_out)
-            elif self.use_bits:
-                lib.ftb_backward_values(self.d_ft, p["input.weight"], self.bits, dst=self.d_conv_out)
-            else:
-                lib.ft_backward_values(self.d_ft, p["input.weight"], self.act, self.P, dst=self.d_conv_out)
-            if self.ride_ste:
+            if not self.mode.merged_backward_launch:  # (else d_conv_out came out of the merged launch in "ft_wgrad")
+                feats.backward_values(self.d_ft, p["input.weight"], dst=self.d_conv_out)
+            if self.mode.ride_ste:
                 return  # stage 1 rode in the merged launch ("ft_wgrad"), stage 2 rides in the norm launch
-            if self.use_patches:
+            if self.mode.use_patches:
                 lib.ste_conv_backward_patches(self.patches, self.conv_out, p["visual_threshold"], self.d_conv_out, self.gh, self.gw,
                                               d_thr=g["visual_threshold"], d_weight=g["conv.weight"], scratch=self.ste_scratch,
                                               stages=self.mode.ste_stages)
@@ -463,15 +437,15 @@ class NnueTrainer:
         """The optimizer's launch on the flat buffers: clip norm + update of every tensor.  Where the table's gradient is never
         materialised (fuse_table_update, factor_exchange) it takes the table's share of the norm from the Gram partials, leaves
         the table's rows alone and the clip coefficient in ``clip_coef`` for _table_update."""
-        ext = (self.sq_partial, *self.sq_range) if self.mode.sq != "none" else None
+        ext = (self.sq_partial, *self.mode.sq_range) if self.mode.sq != "none" else None
         elsewhere = self.mode.sq == "gram"
         if self.optimizer == "adam":
             lib.adam_step(self.flat_params, self.flat_grads, self.flat_exp_avg, self.flat_exp_avg_sq, self.adam_step_count,
                           self.lr, self.betas, self.eps, self.weight_decay, self.max_grad_norm, scale, self.grad_norm,
                           self.sgd_scratch, lr_dev=self.lr_dev, ext=ext, coef_out=self.clip_coef, ext_applied_elsewhere=elsewhere)
             return
-        ste = ((self.ste_scratch, self.ste_chunks, self.fps, self.g["visual_threshold"], self.g["conv.weight"])
-               if self.defer_ste else None)
+        ste = ((self.ste_scratch, self.mode.ste_chunks, self.fps, self.g["visual_threshold"], self.g["conv.weight"])
+               if self.mode.defer_ste else None)
         lib.sgd_step(self.flat_params, self.flat_grads, self.flat_momentum, self.lr, self.momentum, self.weight_decay,
                      self.max_grad_norm, scale, first, self.grad_norm, self.sgd_scratch, ste=ste, ext=ext,
                      coef_out=self.clip_coef, ext_applied_elsewhere=elsewhere, lr_dev=self.lr_dev)
@@ -480,7 +454,7 @@ class NnueTrainer:
         """The product d_W = A^T d_ft (A: map `fm`) with the table's update in its epilogue, after _small_update: SGD on the
         momentum's rows or Adam on the two moments' rows.  nxt: the same pass over the table also forms the FeatureTransformer
         forward of map `nxt` into ``self.ft`` (_next_map has written it; the small update the bias and table row F-1)."""
-        lo, hi = self.sq_range
+        lo, hi = self.mode.sq_range
         forward = () if nxt is None else (nxt, self.p["input.bias"], self.ft)
         if self.optimizer == "adam":
             fn = lib.ftm_backward_weight_update_adam if nxt is None else lib.ftm_backward_weight_update_forward_adam
@@ -495,33 +469,32 @@ class NnueTrainer:
     def _next_map(self, slot: int, nxt) -> None:
         """conv + {0,1} map of input slot `slot` into map `nxt`, between the two halves of an update that forms the next step's
         forward: it needs the conv weights and thresholds the small update has just written."""
-        lib.ftm_conv_binarize(self.inputs[slot][0], self.p["conv.weight"], self.p["visual_threshold"], self.stride, self.F, self.L1,
-                              conv_out=self.conv_out, fm=nxt, patches=self.patches)
+        nxt.front(self.inputs[slot][0], self.p["conv.weight"], self.p["visual_threshold"], self.stride, self.conv_out, patches=self.patches)
 
     def _update(self, first: bool, grad_scale: Optional[float] = None) -> None:
         scale = self.dp.grad_scale if grad_scale is None else grad_scale
         self._small_update(first, scale)
-        if self.fuse_table_update:  # the product runs LAST and applies the table's share
-            self._table_update(first, scale, self.d_ft, self.fm)
+        if self.mode.fuse_table_update:  # the product runs LAST and applies the table's share
+            self._table_update(first, scale, self.d_ft, self.feats)
 
     def _exchange_and_update(self, first: bool, grad_scale: Optional[float] = None, alt: bool = False,
                              next_slot: Optional[int] = None) -> None:
         """Everything after the local kernels of a data-parallel step, as launches on the current stream: the gradient
         exchange and the optimizer.  Capturable (no host synchronisation).  alt: this step's local map is the second one;
         next_slot (step groups under the factor exchange): the table update also forms the forward of the step on that slot."""
-        if self.factor_exchange:
+        if self.mode.factor_exchange:
             fx, scale = self.fx, (self.dp.grad_scale if grad_scale is None else grad_scale)
-            fx.pack(self.fm_alt if alt else self.fm, self.flat_grads)
+            fx.pack(self.fm_alt if alt else self.feats, self.flat_grads)
             self.dp.all_gather_chunks(fx.chunks)  # the step's one collective
             fx.unpack(self.flat_grads)
             lib.ftm_gram_sqnorm(fx.g_fm, fx.g_dft, self.gram, self.sq_partial)
             self._small_update(first, scale)
-            nxt = None if next_slot is None else (self.fm if alt else self.fm_alt)
+            nxt = None if next_slot is None else (self.feats if alt else self.fm_alt)
             if nxt is not None:
                 self._next_map(next_slot, nxt)
             self._table_update(first, scale, fx.g_dft, fx.g_fm, nxt)
             return
-        if not self.sharded_update:
+        if not self.mode.sharded_update:
             self.dp.allreduce_sum(self.flat_grads, async_op=False)
             self._update(first, grad_scale)
             return
@@ -594,7 +567,7 @@ class NnueTrainer:
                     self._segment(name)
                 self._plan_seg[name] = list(calls)
             self._plan_local = [c for name in self.SEGMENTS for c in self._plan_seg[name]]
-        if self._plan_update is None and (self.sharded_update or self.factor_exchange):
+        if self._plan_update is None and (self.mode.sharded_update or self.mode.factor_exchange):
             self._plan_update_first = self._plan_update = []  # these modes issue exchange + update themselves (_exchange_and_update)
         if self._plan_update is None:
             live = [self.flat_params, self.flat_grads, self.grad_norm] + self._optimizer_buffers()
@@ -611,7 +584,7 @@ class NnueTrainer:
 
     def _alt_swap(self) -> dict:
         """Pointer substitutions that make a recorded call use the second map (fuse_next_forward)."""
-        a, b = self.fm, self.fm_alt
+        a, b = self.feats, self.fm_alt
         return {a.bits.data_ptr(): b.bits.data_ptr(), a.n.data_ptr(): b.n.data_ptr(), a.sink.data_ptr(): b.sink.data_ptr(),
                 a.scratch.data_ptr(): b.scratch.data_ptr()}
 
@@ -629,7 +602,7 @@ class NnueTrainer:
         rider_swap = None
         if loss is not None:
             swap[self.loss.data_ptr()] = loss.data_ptr()
-            if self.ride_small:  # the mean loss's destination sits inside the rider's host struct: use the struct made for `loss`
+            if self.mode.ride_small:  # the mean loss's destination sits inside the rider's host struct: use the struct made for `loss`
                 rider_swap = (ctypes.addressof(self._rider(self.loss)), ctypes.pointer(self._rider(loss)))
 
         def sub(a):
@@ -733,7 +706,7 @@ class NnueTrainer:
             return self.loss
         if not self.dp.collectives:
             run("all")
-        elif self.sharded_update or self.factor_exchange:
+        elif self.mode.sharded_update or self.mode.factor_exchange:
             run("all")
             with lib.time_calls(timers):
                 self._exchange_and_update(first, grad_scale=self.dp.grad_scale * ragged if ragged is not None else None)
@@ -783,7 +756,7 @@ class NnueTrainer:
             elif fuse and i + 1 < len(slots):
                 # small tensors (and the clip coefficient) first: the next map needs the updated conv weights and thresholds,
                 # the next forward's finish the updated bias and table row F-1
-                cur, nxt = (self.fm_alt, self.fm) if alt else (self.fm, self.fm_alt)
+                cur, nxt = (self.fm_alt, self.feats) if alt else (self.feats, self.fm_alt)
                 with lib.time_calls(timers):
                     self._small_update(False, self.dp.grad_scale)
                     self._next_map(slots[i + 1], nxt)
@@ -797,7 +770,7 @@ class NnueTrainer:
 
     def _group_fuses(self, slots) -> bool:
         """In a group on `slots` the table update of every step but the last also forms the next step's forward."""
-        return self.fuse_next_forward and len(slots) > 1  # (the mode has it only on a single rank or under the factor exchange)
+        return self.mode.fuse_next_forward and len(slots) > 1  # (the mode has it only on a single rank or under the factor exchange)
 
     def _ends_on_alt(self, slots) -> bool:
         """The last step of a group on `slots` leaves its map in the second one (the maps alternate within a fused group)."""
@@ -862,22 +835,14 @@ class NnueTrainer:
 
     def rebuilt(self, ft_path: str) -> "NnueTrainer":
         """A trainer for the same model, shapes, hyper-parameters and optimizer state that uses another FeatureTransformer
-        kernel family (``"mfma"`` | ``"bits"`` | ``"list"`` | ``"auto"``, as NNUE_FT_PATH) -- the train loop's density check
+        kernel family (``"mfma"`` | ``"bits"`` | ``"list"`` | ``"auto"``: the constructor's ``ft_path``) -- the train loop's density check
         calls this at an epoch boundary when the learnable thresholds have moved the active-feature density across the
         measured crossover of the dense-product and gather forms.  This trainer must not be used afterwards (the module's
         parameters become views of the new trainer's buffers)."""
         torch.cuda.synchronize(self.dev)
-        old = os.environ.get("NNUE_FT_PATH")
-        os.environ["NNUE_FT_PATH"] = ft_path
-        try:
-            new = NnueTrainer(self.model, self.B, (self.H, self.W), group=self.dp.group, use_graph=self.use_graph,
-                              input_slots=len(self.inputs), optimizer=self.optimizer, betas=self.betas, eps=self.eps, **self._hyper)
-        finally:
-            if old is None:
-                os.environ.pop("NNUE_FT_PATH", None)
-            else:
-                os.environ["NNUE_FT_PATH"] = old
-        if self.sharded_update and self.flat_momentum is not None and self.dp.world > 1 and self.steps_done > 0:
+        new = NnueTrainer(self.model, self.B, (self.H, self.W), group=self.dp.group, use_graph=self.use_graph, input_slots=len(self.inputs),
+                          optimizer=self.optimizer, betas=self.betas, eps=self.eps, ft_path=ft_path, **self._hyper)
+        if self.mode.sharded_update and self.flat_momentum is not None and self.dp.world > 1 and self.steps_done > 0:
             self.dp.all_gather(self.flat_momentum, self.dp.shard_of(self.flat_momentum))
         for src, dst in zip(self._optimizer_buffers(), new._optimizer_buffers()):
             dst.copy_(src)
@@ -892,7 +857,7 @@ class NnueTrainer:
         With the sharded update (more than one rank, bandwidth-sized buffers) every rank owns only its shard of the
         momentum, so this call first all-gathers the shards: it is then a COLLECTIVE and every rank must make it (the
         train loop does: all ranks reach the same best-F1 decision)."""
-        if self.sharded_update and self.flat_momentum is not None and self.dp.world > 1 and self.steps_done > 0:
+        if self.mode.sharded_update and self.flat_momentum is not None and self.dp.world > 1 and self.steps_done > 0:
             torch.cuda.current_stream(self.dev).synchronize()
             self.dp.all_gather(self.flat_momentum, self.dp.shard_of(self.flat_momentum))
         params = list(self.model.parameters())
@@ -922,6 +887,17 @@ class NnueTrainer:
 
     def active_stats(self) -> Tuple[float, int]:
         """(mean, max) active features per image of the last batch -- reads back; not for timed regions."""
-        fm = self.fm_alt if (self.use_mfma and self._last_alt) else self.fm
-        n = (fm if self.use_mfma else self.bits if self.use_bits else self.act).n.float()
+        n = (self.fm_alt if self._last_alt else self.feats).n.float()  # (_last_alt: only where the mode has the second map)
         return float(n.mean()), int(n.max())
+
+
+# The mode's flags as read-only attributes of the trainer (bench.py and the tests read them there): ``self.mode`` is the only
+# store, so an assignment to one of these names raises instead of leaving the two views apart.
+MODE_NAMES = ("ft_path", "use_mfma", "use_bits", "use_patches", "fuse_l1", "fwd_planes", "merge_backward", "ride_dw1", "ride_small",
+              "fuse_tail_dx", "defer_ste", "ride_ste", "ste_chunks", "fuse_table_update", "fuse_next_forward", "grads_materialised",
+              "factor_exchange", "sharded_update", "sq_range")
+for _name in MODE_NAMES:
+    setattr(NnueTrainer, _name, property(lambda self, _name=_name: getattr(self.mode, _name)))
+# the live map under its family's name (None for the other two families)
+for _name, _family in (("fm", "mfma"), ("bits", "bits"), ("act", "list")):
+    setattr(NnueTrainer, _name, property(lambda self, _family=_family: self.feats if self.feats.family == _family else None))

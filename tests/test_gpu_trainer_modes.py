@@ -1,15 +1,16 @@
 """Every step mode of tests/trainer_modes.py's table on the GPU: the live trainer takes the mode the table says (flags, phase
 mask, STE stages, launch list), three eager optimizer steps in that mode -- clip active, clip inactive, a short last batch --
 follow the float64 oracle at the project's bars, and the same steps as graph replays and as one step group are bitwise the
-eager ones.  One test per row; ``-m gpu``.  Each row prints one ``TRAINER_MODE {json}`` line (mode, launches, worst error over
+eager ones.  One test per row, and one of the kernel family handed to ``rebuilt`` as an argument; ``-m gpu``.  Each row prints one ``TRAINER_MODE {json}`` line (mode, launches, worst error over
 each bar): profiles/trainer_modes.md is that record."""
 import json
+import os
 
 import pytest
 import torch
 
-from trainer_modes import BY_NAME, ROW_NAMES, CallLog, check_step, differences, flags_of, launches_of, modes_of, oracle_steps, same, \
-    set_knobs, snapshot, trainer_for
+from trainer_modes import A, BY_NAME, ROW_NAMES, CallLog, build_model, check_step, differences, flags_of, hyper, launches_of, modes_of, \
+    oracle_steps, same, set_knobs, snapshot, trainer_for
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -80,3 +81,35 @@ def test_the_row_takes_its_mode_and_its_steps_follow_the_oracle(name, monkeypatc
                             assert_close_grad(a.float(), b.float(), f"{name}: state after the slots")
     finally:
         print("TRAINER_MODE " + json.dumps(record, sort_keys=True))
+
+
+def test_rebuilt_takes_the_family_as_an_argument_and_the_flags_live_in_the_mode_alone(monkeypatch):
+    """Configuration A at batch 40 (the smallest shape of the suite at which all three kernel families run): rebuilt(p) leaves
+    the process environment alone and gives the trainer a fresh one gives under NNUE_FT_PATH=p -- the same mode, and bitwise the
+    same first step; the mode's flags on the trainer are read-only views of ``trainer.mode``."""
+    from nnue_hip.trainer import NnueTrainer
+    cfg = dict(A, batch=40)
+    set_knobs(monkeypatch, BY_NAME["A"])
+    gen = torch.Generator().manual_seed(11)
+    images = torch.rand((40, 3, 32, 32), generator=gen).to(DEV)
+    labels = torch.randint(0, cfg["classes"], (40,), generator=gen).to(DEV)
+    with trainer_for(cfg) as (tr, _):
+        assert tr.ft_path == "mfma"
+        snap = dict(os.environ)
+        for path in ("bits", "list", "mfma"):
+            tr2 = tr.rebuilt(path)
+            assert dict(os.environ) == snap
+            assert tr2.ft_path == path and tr2.steps_done == 0
+            twin = build_model(cfg)
+            twin.load_state_dict({k: v.detach().clone() for k, v in tr2.model.state_dict().items()})
+            with monkeypatch.context() as forced:
+                forced.setenv("NNUE_FT_PATH", path)
+                fresh = NnueTrainer(twin.to(DEV), 40, (32, 32), max_grad_norm=1.0, **hyper(cfg))
+            assert tr2.mode == fresh.mode, f"{tr2.mode.describe()} != {fresh.mode.describe()}"
+            for t in (tr2, fresh):
+                t.step(images, labels)
+            torch.cuda.synchronize()
+            assert torch.equal(tr2.flat_params, fresh.flat_params) and torch.equal(tr2.grad_norm, fresh.grad_norm), path
+        with pytest.raises(AttributeError):
+            tr.fuse_l1 = False
+        assert tr.fuse_l1 is tr.mode.fuse_l1

@@ -3,6 +3,8 @@ over the library's launch-free queries) answers for every row as the table says,
 both values, every phase mask and every combination it was written for.  The data-parallel decisions, which the table's
 single-rank rows do not reach, have their own table here.  tests/test_gpu_trainer_modes.py then holds the live trainer to the
 same table and each row's step to the oracle."""
+import os
+
 import pytest
 
 from nnue_hip import lib
@@ -209,3 +211,32 @@ def test_describe_is_the_row_of_the_record(monkeypatch):
         "mfma | defer_ste, fuse_l1, ride_dw1, ride_ste, ride_small | sq tiles | phases 59 | STE ride, 112 chunks"
     set_knobs(monkeypatch, BY_NAME["g5_bits"])
     assert step_mode_of(BY_NAME["g5_bits"].config).describe() == "bits | defer_ste | sq none | phases 5 | STE stages=1"
+
+
+# ---- the kernel family as an argument (resolve(ft_path=...), what NnueTrainer(ft_path=...) and rebuilt() pass) against the same
+# family forced through the process environment
+@pytest.mark.parametrize("path", ("bits", "list", "mfma", "auto"))
+@pytest.mark.parametrize("name", ("A", "A_k4_clip", "g5_bits"))
+def test_the_family_as_an_argument_resolves_as_the_variable_does(name, path, monkeypatch):
+    row = BY_NAME[name]
+    set_knobs(monkeypatch, row)
+    monkeypatch.setenv("NNUE_FT_PATH", path)
+    by_variable = step_mode_of(row.config)
+    monkeypatch.delenv("NNUE_FT_PATH")
+    before = dict(os.environ)
+    by_argument = step_mode_of(row.config, ft_path=path)
+    assert dict(os.environ) == before
+    assert by_argument == by_variable, f"{by_argument.describe()} != {by_variable.describe()}"
+
+
+@pytest.mark.parametrize("name", ("A", "A_k4_clip", "g5_bits"))
+def test_the_family_argument_wins_over_the_variable(name, monkeypatch):
+    row = BY_NAME[name]
+    set_knobs(monkeypatch, row)
+    monkeypatch.setenv("NNUE_FT_PATH", "bits")
+    want = step_mode_of(row.config)
+    monkeypatch.setenv("NNUE_FT_PATH", "list")
+    before = dict(os.environ)
+    assert step_mode_of(row.config, ft_path="bits") == want
+    assert dict(os.environ) == before
+    assert step_mode_of(row.config).ft_path == "list"  # (and without the argument the variable still decides)

@@ -159,16 +159,17 @@ def geometry(cfg: Dict) -> Dict:
 LEAD = ["visual_threshold", "conv.weight", "input.weight"]  # FlatLayout.of's first names (test_geometry_is_the_flat_layouts)
 
 
-def step_mode_of(cfg: Dict, dp=None, use_graph: bool = True, count: Optional[int] = None):
+def step_mode_of(cfg: Dict, dp=None, use_graph: bool = True, count: Optional[int] = None, ft_path: Optional[str] = None):
     """nnue_hip.step_mode.resolve -- the policy the trainer itself uses -- at this configuration under the current
     environment, from the launch-free queries alone (no GPU).  dp: step_mode.DpFacts (default: one rank); count: the flat
-    buffers' length (default: up to the table's end -- only the sharded update's threshold reads it)."""
+    buffers' length (default: up to the table's end -- only the sharded update's threshold reads it); ft_path: the kernel
+    family as an argument (default: NNUE_FT_PATH decides)."""
     from nnue_hip import step_mode
     g = geometry(cfg)
     return step_mode.resolve(B=cfg["batch"], H=cfg["image"], W=cfg["image"], stride=g["stride"], fps=cfg["fps"], F=g["F"],
                              L1=cfg["l1"], L2=cfg["l2"], L3=cfg["l3"], C=cfg["classes"], K=cfg["K"], optimizer=cfg["optimizer"],
                              dp=dp or step_mode.DpFacts(), use_graph=use_graph, lead_names=LEAD, tbl_lo=g["tbl_lo"],
-                             tbl_hi=g["tbl_hi"], count=g["tbl_hi"] if count is None else count)
+                             tbl_hi=g["tbl_hi"], count=g["tbl_hi"] if count is None else count, ft_path=ft_path)
 
 
 def resolve(cfg: Dict) -> Dict:
