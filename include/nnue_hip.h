@@ -967,6 +967,16 @@ int nnue_sgd_step(float* params, float* grads, float* momentum_buf, int64_t coun
                   const float* ext_partial, int ext_count, int64_t ext_lo, int64_t ext_hi,
                   float* coef_out, int ext_applied_elsewhere, const float* lr_dev, nnue_stream_t stream);
 
+/* One step of a per-iteration learning-rate schedule, on the device, so that it can sit inside a captured step graph ahead of
+ * the optimizer launches that read lr_dev.  The reference fixes the rate when it builds its optimizers (train.py:457-471) and
+ * defines the per-iteration schedule its configs ask for in training_utils.py:283-336 (get_lr: warm-up, cosine decay, cyclical
+ * modulation); `table` holds that schedule -- or any other -- tabulated on the host, n float32 values, one per optimizer step.
+ *   i = clamp(position[0], 0, n-1) ; lr_out[0] = table[i] ; position[0] = min(position[0] + 1, INT32_MAX)
+ * (past the end of the table the last value holds; the counter saturates, it never wraps).  One launch of one wavefront;
+ * table, position and lr_out are device pointers.  NNUE_E_ARG: a null pointer, n <= 0 or n > INT32_MAX; nothing is launched
+ * then. */
+int nnue_lr_schedule_step(const float* table, int64_t n, int32_t* position, float* lr_out, nnue_stream_t stream);
+
 /* ---- input pipeline ------------------------------------------------------------------------------
  * One batch of GenericVisionDataset.__getitem__ + collate (data/datasets.py:173-195, :358-372) from a uint8
  * dataset resident in HBM: images_u8 [N,H,W,3], labels_all [N]; indices [B] select the samples.  Writes

@@ -945,3 +945,24 @@ extern "C" int nnue_multi_adam_step(float* const* params, float* const* grads, f
   return multi_step<true>("nnue_multi_adam_step", params, grads, exp_avgs, exp_avg_sqs, step_counters, counts, n, lr, beta1, beta2, eps,
                           weight_decay, nullptr, max_norm, norm_out, scratch, scratch_bytes, lr_dev, stream);
 }
+
+namespace {
+
+// One wavefront, lane 0 does the work: the step's rate out of a host-made table, the position one further (saturating).
+__global__ void __launch_bounds__(64) lr_schedule_step_kernel(const float* __restrict__ table, int n, int32_t* __restrict__ position,
+                                                              float* __restrict__ lr_out) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  const int32_t pos = position[0];
+  const int32_t i = pos < 0 ? 0 : (pos > n - 1 ? n - 1 : pos);
+  lr_out[0] = table[i];
+  position[0] = pos < INT32_MAX ? pos + 1 : INT32_MAX;
+}
+
+}  // namespace
+
+extern "C" int nnue_lr_schedule_step(const float* table, int64_t n, int32_t* position, float* lr_out, nnue_stream_t stream) {
+  NNUE_REQUIRE(table && position && lr_out, NNUE_E_ARG, "nnue_lr_schedule_step: null pointer");
+  NNUE_REQUIRE(n > 0 && n <= (int64_t)INT32_MAX, NNUE_E_ARG, "nnue_lr_schedule_step: n=%lld must be in 1..2^31-1", (long long)n);
+  hipLaunchKernelGGL(lr_schedule_step_kernel, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), table, (int)n, position, lr_out);
+  return nnue_launch_status("nnue_lr_schedule_step");
+}

@@ -178,6 +178,7 @@ SIGNATURES = {
                                 _c_p, _c_p, _c_i64, _c_p, _c_p]),
     "nnue_sgd_step": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_f, _c_f, _c_f, _c_f, _c_f, _c_int,
                                _c_p, _c_p, _c_i64, _c_p, _c_int, _c_int, _c_p, _c_p, _c_p, _c_int, _c_i64, _c_i64, _c_p, _c_int, _c_p, _c_p]),
+    "nnue_lr_schedule_step": (_c_int, [_c_p, _c_i64, _c_p, _c_p, _c_p]),
     "nnue_ftm_uses_bf16": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int]),
     "nnue_sqnorm_partials": (_c_int, [_c_p, _c_i64, _c_p, _c_int, _c_p]),
     "nnue_dp_factor_chunk_bytes": (_c_i64, [_c_int, _c_int, _c_int, _c_i64]),
@@ -1467,6 +1468,17 @@ def sgd_step(params: torch.Tensor, grads: torch.Tensor, momentum_buf: Optional[t
           float(momentum), float(weight_decay), float(max_norm), float(grad_scale), int(bool(first_step)),
           _ptr(norm_out), scratch.data_ptr(), scratch.numel(), *ste_args, *ext_args, _ptr(coef_out), int(bool(ext_applied_elsewhere)),
           _ptr(lr_dev), _stream(params))
+
+
+def lr_schedule_step(table: torch.Tensor, position: torch.Tensor, lr_out: torch.Tensor) -> None:
+    """lr_out[0] <- table[clamp(position[0], 0, n-1)], then position[0] += 1 (saturating): one optimizer step of a tabulated
+    learning-rate schedule, on the device -- recorded into plans and captured into graphs like every other call."""
+    table = _need(table, torch.float32, "schedule table")
+    if table.dim() != 1 or table.numel() < 1:
+        raise ValueError(f"schedule table: expected a 1-D tensor of at least one value, got shape {tuple(table.shape)}")
+    _need(position, torch.int32, "schedule position", (1,))
+    _need(lr_out, torch.float32, "learning rate", (1,))
+    _call("nnue_lr_schedule_step", table.data_ptr(), table.numel(), position.data_ptr(), lr_out.data_ptr(), _stream(table))
 
 
 def adam_step(params: torch.Tensor, grads: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor,

@@ -18,6 +18,16 @@ NNUE model, minus the parts that are out of scope here (W&B, RunPod, dataset dow
   whose call clamps the live weights through ``serialize_model``, this leaves the parameters alone: a run with the metrics on
   is bitwise the run with them off.  The optional config attribute ``compiled_eval_source`` (default ``"float"``) is
   ``evaluate_engine``'s ``source``: ``"u8"`` evaluates straight from the uint8 store of a ``GpuLoader``'s dataset.
+* ``lr_schedule`` (argument: an ``LrSchedule`` or a sequence of per-step rates; default ``LrSchedule.from_config``, which is
+  None unless the config sets the new attribute ``lr_schedule``) attaches a per-step schedule to the trainer
+  (training_utils.py:283-336, which the reference defines and never calls); each history row then gains ``train/lr``, the
+  rate of the epoch's last step.
+* ``save_last`` / ``resume_from`` (arguments, or the config attributes of those names; off by default): after each epoch's
+  evaluations ``last.ckpt`` is written beside ``best-model.ckpt`` -- the five reference keys plus ``"run_state"`` (the
+  trainer's state, the epoch and step counts, best-so-far values, the history, the GPU dataset's draw counter and the
+  shuffle generator's state) -- and ``resume_from`` continues such a run at the next epoch with the same bits an
+  uninterrupted run has.  Epoch boundaries only; validation and test loaders are expected to be deterministic, as
+  data/loaders.py:95-120 builds them; the exact continuation of the input pipeline holds for a ``GpuLoader``.
 
 Loaders are any iterables of ``(images float32 [b,3,H,W], labels int [b])`` batches; the data pipeline itself
 (torchvision / albumentations) is out of scope.
@@ -36,6 +46,7 @@ import torch
 
 from . import lib
 from .trainer import NnueTrainer
+from .lr_schedule import LrSchedule
 from .input_pipeline import GpuLoader, train_epoch
 
 
@@ -84,8 +95,15 @@ def build_model(config, device):
 
 def run_training(config, train_loader: Iterable, val_loader: Iterable, test_loader: Optional[Iterable] = None, model=None,
                  checkpoint_dir=None, log: Callable[[str], None] = print, use_graph: bool = True,
-                 compiled_eval: Optional[bool] = None) -> TrainResult:
+                 compiled_eval: Optional[bool] = None, save_last: Optional[bool] = None, resume_from=None,
+                 lr_schedule=None) -> TrainResult:
     import evaluate
+    if save_last is None:
+        save_last = bool(getattr(config, "save_last", False))
+    if resume_from is None:
+        resume_from = getattr(config, "resume_from", None)
+    optimizer_type = "sgd" if config.optimizer_type == "sgd" else "adam"
+    resumed = _read_resume_file(resume_from, config, optimizer_type) if resume_from else None
     if compiled_eval is None:
         compiled_eval = bool(getattr(config, "compiled_eval", False))
     compiled_eval_source = str(getattr(config, "compiled_eval_source", "float"))
@@ -93,6 +111,8 @@ def run_training(config, train_loader: Iterable, val_loader: Iterable, test_load
         raise lib.NnueHipError("training runs on the GPU only (no CPU fallback in this build)")
     device = torch.device("cuda", torch.cuda.current_device())
     model = build_model(config, device) if model is None else model.to(device)
+    if resumed is not None:
+        model.load_state_dict(resumed["model_state_dict"])
     in_place = isinstance(train_loader, GpuLoader)  # GPU-resident dataset: batches are written straight into the input slots
     if in_place:
         hw = train_loader.dataset.output_hw  # the stored size unless the dataset resizes
@@ -107,13 +127,33 @@ def run_training(config, train_loader: Iterable, val_loader: Iterable, test_load
         opt = dict(optimizer="adam")
     trainer = NnueTrainer(model, batch, hw, lr=float(config.learning_rate), weight_decay=float(config.weight_decay),
                           max_grad_norm=clip, use_graph=use_graph, input_slots=8 if in_place else 1, **opt)
+    if lr_schedule is None and getattr(config, "lr_schedule", False):
+        lr_schedule = LrSchedule.from_config(config, len(train_loader))
+    if isinstance(lr_schedule, LrSchedule):
+        # the run's steps, and the whole decay with the constant that follows it (a run resumed under a longer max_epochs then
+        # finds the same table)
+        lr_schedule = lr_schedule.values(max(1, int(config.max_epochs) * len(train_loader), lr_schedule.lr_decay_iters + 2))
+    if lr_schedule is not None:
+        trainer.set_lr_schedule(lr_schedule)
     result = TrainResult()
     ckpt_dir = Path(checkpoint_dir) if checkpoint_dir is not None else None
+    if save_last and ckpt_dir is None:
+        raise ValueError("save_last needs checkpoint_dir")
+    first_epoch = 0
+    if resumed is not None:
+        run = resumed["run_state"]
+        trainer.load_state_dict(dict(run["trainer"], optimizer=resumed["optimizer_state_dict"]))
+        _restore_loader_state(train_loader, run["loader"], device)
+        result.history, result.steps = [dict(r) for r in run["history"]], int(run["steps"])
+        result.best_val_f1, result.best_epoch = float(run["best_val_f1"]), int(run["best_epoch"])
+        if ckpt_dir is not None and result.best_epoch >= 0 and (ckpt_dir / "best-model.ckpt").exists():
+            result.checkpoint_path = ckpt_dir / "best-model.ckpt"
+        first_epoch = int(run["epochs_done"])
     engine = None
     if compiled_eval:
         from .engine import EngineModel
         engine = EngineModel.from_model(model)
-    for epoch in range(int(config.max_epochs)):
+    for epoch in range(first_epoch, int(config.max_epochs)):
         model.train()
         if in_place:
             result.steps += train_epoch(trainer, train_loader)[1]
@@ -129,6 +169,8 @@ def run_training(config, train_loader: Iterable, val_loader: Iterable, test_load
         row = {"epoch": epoch, "train/epoch_loss": train_loss, "train/epoch_f1": train_metrics["f1"],
                "train/epoch_accuracy": train_metrics["acc"], "val/loss": val_loss, "val/f1": val_metrics["f1"],
                "val/accuracy": val_metrics["acc"]}
+        if trainer.lr_table is not None:
+            row["train/lr"] = trainer.lr_last
         line = (f"Epoch {epoch + 1}/{config.max_epochs} - Train Loss: {train_loss:.4f}, Train F1: {train_metrics['f1']:.4f}, "
                 f"Train Acc: {train_metrics['acc']:.4f} | Val Loss: {val_loss:.4f}, Val F1: {val_metrics['f1']:.4f}, "
                 f"Val Acc: {val_metrics['acc']:.4f}")
@@ -141,16 +183,34 @@ def run_training(config, train_loader: Iterable, val_loader: Iterable, test_load
                      f"Speed: {compiled['ms_per_sample']:.2f}ms/sample, Density: {compiled['latent_density']:.4f}")
         result.history.append(row)
         log(line)
+        # with save_last EVERY rank takes the trainer's state once per epoch, whatever its own best-F1 decision (under the
+        # sharded update that call is a collective), and only rank 0 writes; without it everything is as it was
+        state = _to_cpu(trainer.state_dict()) if save_last else None
+        writes = ckpt_dir is not None and (not save_last or trainer.dp.rank == 0)
+
+        def five_keys():
+            return {"epoch": epoch,
+                    "model_state_dict": {k: v.detach().cpu().clone() for k, v in model.state_dict().items()},
+                    "optimizer_state_dict": state["optimizer"] if save_last else _to_cpu(trainer.optimizer_state_dict()),
+                    "metrics": {"val_f1": val_metrics["f1"], "val_loss": val_loss},
+                    "config_name": config.name}
         if val_metrics["f1"] > result.best_val_f1:
             result.best_val_f1, result.best_epoch = val_metrics["f1"], epoch
             if ckpt_dir is not None:
-                ckpt_dir.mkdir(parents=True, exist_ok=True)
                 result.checkpoint_path = ckpt_dir / "best-model.ckpt"
-                torch.save({"epoch": epoch,
-                            "model_state_dict": {k: v.detach().cpu().clone() for k, v in model.state_dict().items()},
-                            "optimizer_state_dict": _to_cpu(trainer.optimizer_state_dict()),
-                            "metrics": {"val_f1": val_metrics["f1"], "val_loss": val_loss},
-                            "config_name": config.name}, result.checkpoint_path)
+                if writes:
+                    ckpt_dir.mkdir(parents=True, exist_ok=True)
+                    torch.save(five_keys(), result.checkpoint_path)
+        if save_last and writes:
+            ckpt_dir.mkdir(parents=True, exist_ok=True)
+            last = five_keys()
+            last["run_state"] = {"trainer": {k: v for k, v in state.items() if k != "optimizer"},  # (the optimizer state is above)
+                                 "epochs_done": epoch + 1, "steps": result.steps, "best_val_f1": float(result.best_val_f1),
+                                 "best_epoch": result.best_epoch, "history": [_plain(r) for r in result.history],
+                                 "loader": _loader_state(train_loader, device)}
+            tmp = ckpt_dir / "last.ckpt.tmp"
+            torch.save(last, tmp)
+            os.replace(tmp, ckpt_dir / "last.ckpt")
     if test_loader is not None:
         model.eval()
         test_loss, test_metrics = evaluate.evaluate_model(model, test_loader, None, device)
@@ -193,6 +253,51 @@ def train_model(config, model_type: str = "nnue", train_loader=None, val_loader=
         raise ValueError("train_model needs train_loader and val_loader (the data pipeline is out of scope)")
     run_training(config, train_loader, val_loader, test_loader, **kwargs)
     return 0
+
+
+def _plain(row: dict) -> dict:
+    """A history row as plain Python numbers (what ``torch.load(..., weights_only=True)`` reads back)."""
+    return {k: (int(v) if isinstance(v, (bool, int)) else float(v)) for k, v in row.items()}
+
+
+def _loader_state(loader, device) -> Optional[dict]:
+    """What the train loader carries from epoch to epoch: the GPU dataset's draw counter and the state of the generator its
+    shuffle draws from -- its own, or the device's default one (``randperm(device=...)``) when it has none.  None for any
+    other iterable: its state is the caller's."""
+    if not isinstance(loader, GpuLoader):
+        return None
+    if loader.generator is not None:
+        return {"dataset_step": int(loader.dataset.step), "generator": loader.generator.get_state().clone(), "device_rng": None}
+    return {"dataset_step": int(loader.dataset.step), "generator": None, "device_rng": torch.cuda.get_rng_state(device).clone()}
+
+
+def _restore_loader_state(loader, state: Optional[dict], device) -> None:
+    if isinstance(loader, GpuLoader) != (state is not None):
+        raise ValueError("the run was saved with another kind of train loader (GpuLoader or not)")
+    if state is None:
+        return
+    if (loader.generator is not None) != (state["generator"] is not None):
+        raise ValueError("the run was saved with a train loader whose shuffle generator was " +
+                         ("its own" if state["generator"] is not None else "the device's default one"))
+    loader.dataset.step = int(state["dataset_step"])
+    if loader.generator is not None:
+        loader.generator.set_state(state["generator"].cpu())
+    else:
+        torch.cuda.set_rng_state(state["device_rng"].cpu(), device)
+
+
+def _read_resume_file(path, config, optimizer_type: str) -> dict:
+    """The contents of a ``last.ckpt`` after the checks a resume refuses on (ValueError): no run state, another config,
+    another optimizer type."""
+    ckpt = torch.load(path, map_location="cpu", weights_only=True)
+    if not isinstance(ckpt, dict) or "run_state" not in ckpt:
+        raise ValueError(f"{path} holds no run state (a best-model.ckpt cannot be resumed from: save with save_last)")
+    if ckpt.get("config_name") != config.name:
+        raise ValueError(f"{path} was written by a run of config {ckpt.get('config_name')!r}, not {config.name!r}")
+    saved = ckpt["run_state"]["trainer"].get("optimizer_type")
+    if saved != optimizer_type:
+        raise ValueError(f"{path} was written by a run with optimizer type {saved!r}, not {optimizer_type!r}")
+    return ckpt
 
 
 def _to_cpu(obj):

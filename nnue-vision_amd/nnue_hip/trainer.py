@@ -263,6 +263,10 @@ class NnueTrainer:
         # the learning rate lives in a device scalar the optimizer kernels read: ``trainer.lr = x`` (a scheduler's hook) is one
         # tiny fill, the recorded plans and captured graphs stay valid (the other hyper-parameters are constants of the plans)
         self.lr_dev = torch.full((1,), float(lr), **f32)
+        # a per-step schedule (set_lr_schedule): a device table the step's first optimizer-side launch indexes into lr_dev, its
+        # position on the device, and the host's mirrors of both (no read-back anywhere)
+        self.lr_table = self.lr_pos = self._lr_values = None
+        self.lr_position = 0
         self.steps_done = 0
         self.use_graph = use_graph
         self._g_local, self._g_update = {}, None
@@ -311,12 +315,29 @@ class NnueTrainer:
         if key == "momentum" and self.optimizer == "sgd" and bool(value) != (self.flat_momentum is not None):
             raise ValueError("momentum cannot be switched on or off after construction (the buffer layout is fixed)")
         self._hyper[key] = value
+        self._drop_update_plans()
+
+    def _drop_update_plans(self) -> None:
+        """The update plans are re-recorded at the next step and every graph that contains an update is dropped; the local
+        plan and the graphs of the local step alone stay."""
         self._plan_update_first = self._plan_update = None
         self._g_update = None
         for key_ in [k for k in self._g_local if k[1] in ("full", "full_dp", "many")]:  # every graph that contains an update
             del self._g_local[key_]
 
-    lr = property(lambda self: self._hyper["lr"], lambda self, v: self._set_hyper("lr", float(v)))
+    def _get_lr(self) -> float:
+        if self._lr_values is not None:  # the value the next step will use
+            return float(self._lr_values[min(self.lr_position, self._lr_values.numel() - 1)])
+        return self._hyper["lr"]
+
+    def _assign_lr(self, value: float) -> None:
+        if self._lr_values is not None:
+            raise ValueError("a learning-rate schedule is attached and would overwrite this value at the next step: "
+                             "clear the schedule first (clear_lr_schedule)")
+        self._set_hyper("lr", float(value))
+
+    lr = property(_get_lr, _assign_lr)
+    lr_last = property(lambda self: self._hyper["lr"], doc="the rate lr_dev holds: under a schedule, the last step's")
     momentum = property(lambda self: self._hyper["momentum"], lambda self, v: self._set_hyper("momentum", float(v)))
     weight_decay = property(lambda self: self._hyper["weight_decay"], lambda self, v: self._set_hyper("weight_decay", float(v)))
     max_grad_norm = property(lambda self: self._hyper["max_grad_norm"], lambda self, v: self._set_hyper("max_grad_norm", float(v)))
@@ -324,6 +345,50 @@ class NnueTrainer:
     def set_lr(self, lr: float) -> None:
         """Learning rate for the following steps (a scheduler's hook)."""
         self.lr = lr
+
+    # A per-step schedule (the reference's get_lr, training_utils.py:283-336, tabulated by lr_schedule.LrSchedule -- or any
+    # other table): one tiny launch at the head of every step's optimizer side copies the step's value into ``lr_dev`` and moves
+    # the position on.  The launch is part of the recorded plans, hence inside every captured graph: a step group replays
+    # with a different rate per step.  With ranks every rank attaches the same values; the counters advance alike without
+    # any communication.  Attaching, replacing or clearing re-records the update plans like a change of momentum.
+    def set_lr_schedule(self, values, position: int = 0) -> None:
+        """Optimizer step number t, counted from position 0, uses ``values[min(t, len - 1)]``; the next step is number
+        ``position``."""
+        values = torch.as_tensor(values).detach().to(device="cpu", dtype=torch.float32).contiguous()
+        if values.dim() != 1 or values.numel() < 1:
+            raise ValueError(f"a schedule is a 1-D sequence of at least one value, got shape {tuple(values.shape)}")
+        if values.numel() > 2**31 - 1:
+            raise ValueError("a schedule has at most 2^31 - 1 values")
+        position = int(position)
+        if not 0 <= position <= 2**31 - 1:
+            raise ValueError(f"schedule position {position} must lie in 0 .. 2^31 - 1")
+        self._lr_values = values.clone()
+        self.lr_table = values.to(self.dev)
+        self.lr_pos = torch.full((1,), position, dtype=torch.int32, device=self.dev)
+        self.lr_position = position
+        self._drop_update_plans()
+
+    def clear_lr_schedule(self) -> None:
+        """Detaches the schedule; the rate stays at the last value used (``trainer.lr`` reads and sets it again)."""
+        if self._lr_values is None:
+            return
+        self.lr_table = self.lr_pos = self._lr_values = None
+        self.lr_position = 0
+        self._drop_update_plans()
+
+    def _lr_tick(self) -> None:
+        """The schedule's launch of one optimizer step: called once per step, ahead of the first launch that reads lr_dev
+        (_small_update and the sharded update's own optimizer call are the two places a step's optimizer side begins)."""
+        if self.lr_table is not None:
+            lib.lr_schedule_step(self.lr_table, self.lr_pos, self.lr_dev)
+
+    def _advance(self, steps: int) -> None:
+        """The host's count of optimizer steps, and the schedule's mirrors with it (lr_position; _hyper['lr'] = what lr_dev
+        now holds)."""
+        self.steps_done += steps
+        if self._lr_values is not None:
+            self.lr_position = min(self.lr_position + steps, 2**31 - 1)
+            self._hyper["lr"] = float(self._lr_values[min(self.lr_position - 1, self._lr_values.numel() - 1)])
 
     # ------------------------------------------------------------------ kernel sequences
     def _cls_params(self):
@@ -436,7 +501,9 @@ class NnueTrainer:
     def _small_update(self, first: bool, scale: float) -> None:
         """The optimizer's launch on the flat buffers: clip norm + update of every tensor.  Where the table's gradient is never
         materialised (fuse_table_update, factor_exchange) it takes the table's share of the norm from the Gram partials, leaves
-        the table's rows alone and the clip coefficient in ``clip_coef`` for _table_update."""
+        the table's rows alone and the clip coefficient in ``clip_coef`` for _table_update.  It is the first launch of a step that
+        reads lr_dev, so the schedule's launch goes ahead of it."""
+        self._lr_tick()
         ext = (self.sq_partial, *self.mode.sq_range) if self.mode.sq != "none" else None
         elsewhere = self.mode.sq == "gram"
         if self.optimizer == "adam":
@@ -504,6 +571,7 @@ class NnueTrainer:
         lib.sqnorm_partials(self.grad_shard, self.local_partials)
         dp.all_gather(self.all_partials, self.local_partials)  # rank-major, fixed order: every rank forms the identical norm
         mom = dp.shard_of(self.flat_momentum) if self.flat_momentum is not None else None
+        self._lr_tick()
         lib.sgd_step(dp.shard_of(self.flat_params), self.grad_shard, mom, self.lr, self.momentum, self.weight_decay, self.max_grad_norm,
                      scale, first, self.grad_norm, self.sgd_scratch, ext=(self.all_partials, 0, self.grad_shard.numel()), lr_dev=self.lr_dev)
         dp.all_gather(self.flat_params, dp.shard_of(self.flat_params))
@@ -571,6 +639,8 @@ class NnueTrainer:
             self._plan_update_first = self._plan_update = []  # these modes issue exchange + update themselves (_exchange_and_update)
         if self._plan_update is None:
             live = [self.flat_params, self.flat_grads, self.grad_norm] + self._optimizer_buffers()
+            if self.lr_table is not None:  # (recording would otherwise move the schedule two steps)
+                live += [self.lr_pos, self.lr_dev]
             keep = [t.clone() for t in live]  # recording executes the updates: put everything back afterwards
             with lib.record_calls() as calls:
                 self._update(True)
@@ -692,7 +762,7 @@ class NnueTrainer:
                     self.capture_collectives = False
             if self.capture_collectives:
                 self._g_local[(slot, "full_dp")].replay()
-                self.steps_done += 1
+                self._advance(1)
                 return self.loss
         if graphs and not self.dp.collectives and not first and ragged is None:
             # single rank, steady state: local step + update are ONE graph (one replay per step)
@@ -702,7 +772,7 @@ class NnueTrainer:
                     lib.run_plan(upd, st.cuda_stream)
                 self._g_local[(slot, "full")] = self._capture(full)
             self._g_local[(slot, "full")].replay()
-            self.steps_done += 1
+            self._advance(1)
             return self.loss
         if not self.dp.collectives:
             run("all")
@@ -710,7 +780,7 @@ class NnueTrainer:
             run("all")
             with lib.time_calls(timers):
                 self._exchange_and_update(first, grad_scale=self.dp.grad_scale * ragged if ragged is not None else None)
-            self.steps_done += 1
+            self._advance(1)
             return self.loss * ragged if ragged is not None else self.loss
         elif not two_buckets:
             # one message: the whole flat gradient buffer, after the local graph; the wait is a stream dependency
@@ -732,7 +802,7 @@ class NnueTrainer:
             small.wait()
         if ragged is not None:
             self._update(first, grad_scale=self.dp.grad_scale * ragged)
-            self.steps_done += 1
+            self._advance(1)
             return self.loss * ragged
         if first:
             lib.run_plan(upd_first, stream, timers)
@@ -740,7 +810,7 @@ class NnueTrainer:
             self._g_update.replay()
         else:
             lib.run_plan(upd, stream, timers)
-        self.steps_done += 1
+        self._advance(1)
         return self.loss
 
     def _run_many(self, st: torch.cuda.Stream, slots, ring: torch.Tensor, upd, timers=None) -> None:
@@ -801,7 +871,7 @@ class NnueTrainer:
             ring = self._ring(len(slots))
             self._run_many(torch.cuda.current_stream(self.dev), slots, ring, upd, timers)
             self._last_alt = self._ends_on_alt(slots)
-            self.steps_done += len(slots)
+            self._advance(len(slots))
             return ring[:len(slots)]
         one_graph = (self.use_graph and self.steps_done > 0 and self._plan_local is not None
                      and (not self.dp.collectives or self.capture_collectives))
@@ -830,7 +900,7 @@ class NnueTrainer:
         graph, ring = self._g_local[(slots, "many")]
         graph.replay()
         self._last_alt = self._ends_on_alt(slots)
-        self.steps_done += len(slots)
+        self._advance(len(slots))
         return ring[:len(slots)]
 
     def rebuilt(self, ft_path: str) -> "NnueTrainer":
@@ -847,7 +917,113 @@ class NnueTrainer:
         for src, dst in zip(self._optimizer_buffers(), new._optimizer_buffers()):
             dst.copy_(src)
         new.steps_done = self.steps_done
+        if self._lr_values is not None:  # (lr_dev already holds the last value used: the constructor got _hyper's)
+            new.set_lr_schedule(self._lr_values, self.lr_position)
         return new
+
+    # ------------------------------------------------------------------ run state (checkpoint / resume)
+    def state_dict(self) -> dict:
+        """Everything the trainer carries from step to step, apart from the model's parameters (``model.state_dict()`` has
+        those): tensors, numbers, strings, dicts and lists only, so ``torch.load(..., weights_only=True)`` reads it back.  A
+        COLLECTIVE exactly where optimizer_state_dict() is one (sharded update with more than one rank)."""
+        schedule = None
+        if self._lr_values is not None:
+            schedule = {"values": self._lr_values.clone(), "position": int(self.lr_position)}
+        return {"version": 1, "optimizer_type": self.optimizer, "optimizer": self.optimizer_state_dict(),
+                "steps_done": int(self.steps_done), "lr": float(self._hyper["lr"]), "lr_schedule": schedule}
+
+    def _checked_optimizer_state(self, sd: dict, steps_done: int):
+        """The flat-buffer sources of a torch optimizer state dict, {buffer name: {parameter name: tensor}}, after checking
+        them against this trainer's optimizer, momentum and layout (ValueError otherwise; nothing is changed here)."""
+        if not isinstance(sd, dict) or "state" not in sd:
+            raise ValueError("not a torch optimizer state dict (no 'state')")
+        index = {k: i for i, (k, _) in enumerate(self.model.named_parameters())}
+        state = sd["state"]
+        keys = (("exp_avg", "exp_avg_sq") if self.optimizer == "adam" else
+                (("momentum_buffer",) if self.flat_momentum is not None else ()))
+        out = {key: {} for key in keys}
+        if steps_done == 0 and not state:
+            return out  # a trainer that has not stepped yet: nothing to restore
+        foreign = {"sgd": ("exp_avg", "exp_avg_sq"), "adam": ("momentum_buffer",)}[self.optimizer]
+        for k, shape in zip(self.layout.names, self.layout.shapes):
+            entry = state.get(index[k], state.get(str(index[k])))
+            if entry is None:
+                if keys:
+                    raise ValueError(f"optimizer state has no entry for parameter {k!r}")
+                continue
+            if any(f in entry for f in foreign):
+                raise ValueError(f"optimizer state of parameter {k!r} belongs to another optimizer type than {self.optimizer!r}")
+            if not keys and entry.get("momentum_buffer") is not None:
+                raise ValueError("the state has momentum buffers but this trainer was built without momentum")
+            for key in keys:
+                t = entry.get(key)
+                if not torch.is_tensor(t):
+                    raise ValueError(f"optimizer state of parameter {k!r} has no {key!r}"
+                                     + (" (momentum missing)" if key == "momentum_buffer" else ""))
+                if tuple(t.shape) != tuple(shape):
+                    raise ValueError(f"{key} of {k!r}: shape {tuple(t.shape)} does not match the layout's {tuple(shape)}")
+                out[key][k] = t
+        return out
+
+    def load_optimizer_state_dict(self, sd: dict, steps_done: int) -> None:
+        """Restores the optimizer state from a torch optimizer state dict (optimizer_state_dict()'s format: the
+        ``optimizer_state_dict`` of a ``best-model.ckpt``) IN PLACE, and the step count with it: no buffer is re-bound, so
+        recorded plans and captured graphs stay valid.  Validates first; on ValueError nothing has changed."""
+        steps_done = int(steps_done)
+        if steps_done < 0:
+            raise ValueError(f"steps_done = {steps_done} must not be negative")
+        self._apply_optimizer_state(self._checked_optimizer_state(sd, steps_done), steps_done)
+
+    def _apply_optimizer_state(self, sources: dict, steps_done: int) -> None:
+        flats = {"momentum_buffer": self.flat_momentum, "exp_avg": self.flat_exp_avg, "exp_avg_sq": self.flat_exp_avg_sq}
+        for key, tensors in sources.items():
+            if not tensors:  # (a state taken before the first step: the buffers' initial zeros)
+                flats[key].zero_()
+                continue
+            for k, v in self.layout.views(flats[key]).items():
+                v.copy_(tensors[k])
+        if self.adam_step_count is not None:
+            self.adam_step_count.fill_(steps_done)
+        # with steps_done > 0 the momentum-initialising first-step plan never runs again (step() reads steps_done)
+        self.steps_done = steps_done
+        self._last_alt = False
+
+    def load_state_dict(self, sd: dict) -> None:
+        """state_dict()'s counterpart, on a fresh trainer or on a used one between steps.  Validates first (optimizer type,
+        presence of momentum, every tensor's shape against the layout; ValueError, nothing changed), then copies in place: the
+        momentum or both moments into the flat buffers, Adam's step into adam_step_count, the rate into lr_dev, the schedule's
+        values and position into lr_table / lr_pos / lr_position, and steps_done.  No buffer is re-bound -- recorded plans and
+        captured graphs hold raw pointers and stay valid; only a schedule of another length than the attached one (or a
+        schedule where none is attached, or none where one is) goes through set_lr_schedule / clear_lr_schedule and their
+        rules.  The model's parameters are not in this dict: ``model.load_state_dict`` restores them, in place too."""
+        if not isinstance(sd, dict) or sd.get("version") != 1:
+            raise ValueError("not a trainer state dict of version 1")
+        if sd.get("optimizer_type") != self.optimizer:
+            raise ValueError(f"the state is of optimizer type {sd.get('optimizer_type')!r}, this trainer's is {self.optimizer!r}")
+        steps_done = int(sd["steps_done"])
+        if steps_done < 0:
+            raise ValueError(f"steps_done = {steps_done} must not be negative")
+        sources = self._checked_optimizer_state(sd["optimizer"], steps_done)
+        schedule = sd.get("lr_schedule")
+        if schedule is not None:
+            values = torch.as_tensor(schedule["values"]).detach().to(device="cpu", dtype=torch.float32)
+            position = int(schedule["position"])
+            if values.dim() != 1 or values.numel() < 1 or not 0 <= position <= 2**31 - 1:
+                raise ValueError("lr_schedule: expected 1-D values of at least one entry and a position in 0 .. 2^31 - 1")
+        lr = float(sd["lr"])
+        # ---- validated: from here on only in-place copies
+        self._apply_optimizer_state(sources, steps_done)
+        if schedule is None:
+            self.clear_lr_schedule()
+        elif self._lr_values is None or self._lr_values.numel() != values.numel():
+            self.set_lr_schedule(values, position)
+        else:
+            self._lr_values.copy_(values)
+            self.lr_table.copy_(values)
+            self.lr_pos.fill_(position)
+            self.lr_position = position
+        self._hyper["lr"] = lr
+        self.lr_dev.fill_(lr)
 
     def optimizer_state_dict(self) -> dict:
         """The optimizer state in torch.optim's own state_dict format (SGD momentum buffers, or Adam's step /
