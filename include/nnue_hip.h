@@ -392,27 +392,38 @@ int nnue_classifier_backward(const float* x, int pairwise,
                              float* d_w3, float* d_b3,
                              void* scratch, int64_t scratch_bytes, nnue_stream_t stream);
 
+/* The bits of nnue_classifier_train_step's `phases` (described there). */
+#define NNUE_CLS_PHASE_DX 1        /* activations, per-sample losses and d_x */
+#define NNUE_CLS_PHASE_SMALL 2     /* the mean loss and the six weight/bias gradients */
+#define NNUE_CLS_DW1_BESIDE_DX 4   /* the first-layer weight product shares the d_x launch */
+#define NNUE_CLS_L1_SLABS_GIVEN 8  /* the layer-1 slabs are at the start of scratch already */
+#define NNUE_CLS_DW1_RIDES 16      /* d_w1 is left to nnue_ftm_backward's rider */
+#define NNUE_CLS_SMALL_RIDE 32     /* ... and so are the small gradients and the mean loss */
+#define NNUE_CLS_TAIL_IN_DX 64     /* the per-sample tail runs inside the d_x launch (only as 123) */
+
 /* The three calls above as ONE training step of the pairwise/classifier block with mean cross-entropy
  * (nnue.py:660-669, :728-734 + compute_loss, train.py:250-254, and their autograd): same results as
  * nnue_classifier_forward -> nnue_cross_entropy(grad_scale) -> nnue_classifier_backward, but the narrow
  * layers, the loss and their backward run per sample in a single kernel.  d_x may be NULL.
- * phases: 1 = activations, per-sample losses and d_x (the critical path of a training step), 2 = the mean loss
- * and the six weight/bias gradients (needs phase 1 on the same scratch; nothing downstream waits for it, so a
- * caller may run it on a second stream), 3 = both.  Adding 4 (phases 5 then 6, or 7) moves the first-layer weight
- * product into phase 1's d_x launch -- both only need d_z1, so the two small products share the chip; the phase-2
- * call (same arguments) then only sums its slabs.  Results are identical either way.  Adding 8 says the layer-1
+ * phases is a sum of the NNUE_CLS_* bits below.  NNUE_CLS_PHASE_DX (1) = activations, per-sample losses and d_x (the
+ * critical path of a training step), NNUE_CLS_PHASE_SMALL (2) = the mean loss and the six weight/bias gradients (needs
+ * NNUE_CLS_PHASE_DX on the same scratch; nothing downstream waits for it, so a caller may run it on a second stream),
+ * 3 = both.  NNUE_CLS_DW1_BESIDE_DX (4; phases 5 then 6, or 7) moves the first-layer weight product into the d_x launch
+ * -- both only need d_z1, so the two small products share the chip; the NNUE_CLS_PHASE_SMALL call (same arguments)
+ * then only sums its slabs.  Results are identical either way.  NNUE_CLS_L1_SLABS_GIVEN (8) says the layer-1
  * pre-activation slabs part[L1/64][B][L2] are already at the START of scratch, written by nnue_ftm_forward_l1 (the
- * FeatureTransformer forward forms them in its epilogue); phase 1 then launches no layer-1 product of its own.
- * Adding 16 (not together with 4) says d_w1 is produced by nnue_ftm_backward's rider from the d_z1 this call leaves
- * in scratch at byte offset nnue_classifier_train_dz1_offset (-1 for non-positive sizes): no first-layer weight
- * product and no slab sum are launched here, d_w1 is not written; with both phases in the one call (19, 27) the
- * small weight/bias gradients and the mean loss share the d_x launch -- unless 32 is added as well (51, 59): then they
- * are left to nnue_ftm_backward's launch too (its `small` argument, filled by nnue_classifier_train_rider with the same
- * tensors and scratch), and the d_x launch holds only d_x tiles.  Adding 64 exists in that one combination only
- * (123 = 59 + 64; any other use of bit 64 is refused as a bad phases value): the per-sample tail runs inside the d_x
- * launch -- each d_x row tile recomputes the tail of its own 16 rows, so phase 1 is one launch -- with outputs bitwise
- * those of 59.  It needs nnue_classifier_train_fused_tail_supported(B, L1, L2, L3, C, 1, pairwise) (else NNUE_E_SHAPE)
- * and 16-byte aligned w2 and w3.
+ * FeatureTransformer forward forms them in its epilogue); NNUE_CLS_PHASE_DX then launches no layer-1 product of its
+ * own.  NNUE_CLS_DW1_RIDES (16, not together with NNUE_CLS_DW1_BESIDE_DX) says d_w1 is produced by nnue_ftm_backward's
+ * rider from the d_z1 this call leaves in scratch at byte offset nnue_classifier_train_dz1_offset (-1 for non-positive
+ * sizes): no first-layer weight product and no slab sum are launched here, d_w1 is not written; with both phases in the
+ * one call (19, 27) the small weight/bias gradients and the mean loss share the d_x launch -- unless
+ * NNUE_CLS_SMALL_RIDE (32) is added as well (51, 59): then they are left to nnue_ftm_backward's launch too (its `small`
+ * argument, filled by nnue_classifier_train_rider with the same tensors and scratch), and the d_x launch holds only d_x
+ * tiles.  NNUE_CLS_TAIL_IN_DX (64) exists in that one combination only (123 = 59 + 64; any other use of it is refused
+ * as a bad phases value): the per-sample tail runs inside the d_x launch -- each d_x row tile recomputes the tail of its
+ * own 16 rows, so NNUE_CLS_PHASE_DX is one launch -- with outputs bitwise those of 59.  It needs
+ * nnue_classifier_train_fused_tail_supported(B, L1, L2, L3, C, 1, pairwise) (else NNUE_E_SHAPE) and 16-byte aligned w2
+ * and w3.
  * scratch >= nnue_classifier_train_scratch(B, L1, L2, L3, C) bytes. */
 int64_t nnue_classifier_train_scratch(int B, int L1, int L2, int L3, int C);
 int64_t nnue_classifier_train_dz1_offset(int B, int L1, int L2, int L3, int C, int pairwise);

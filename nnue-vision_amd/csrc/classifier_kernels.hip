@@ -1208,6 +1208,79 @@ __global__ __launch_bounds__(kTdxThreads) void tail_dx_train_kernel(
   NNUE_TDX_CLOCK(9);
 }
 
+// ---- bucket selector + grouping (one workgroup; B a few thousand at most matters for speed, any B is correct) -----
+// bucket[b] = min(K-1, n[b] * K / (P + 1))  (P = flat ids of the map; P == 0: n[b] already IS the bucket, clamped)
+// then a stable counting sort of the samples into bucket-homogeneous 16-row tiles.
+#include "bucket_group.h"
+
+constexpr int kGroupThreads = 1024;  // one pass over a batch of 1024: every phase of the kernel is a latency, not work
+__global__ __launch_bounds__(kGroupThreads) void bucket_group_kernel(GroupArgs ga) {
+  __shared__ int lds[kGroupLdsInts];
+  bucket_group_body<kGroupThreads>(ga, lds);
+}
+
+}  // namespace
+
+// d_x and the small weight/bias gradients + mean loss in one launch: both only read what the per-sample tail kernel
+// left (d_z1 resp. d_logits, d_z2, h1, h2), so the two launch-sized jobs share the chip (x blocks first).
+__global__ __launch_bounds__(256) void l1_backward_x_small_wgrad(const float* __restrict__ x, int pairwise, const float* __restrict__ w1,
+                                                                 const float* __restrict__ d_z1, int B, int L1, int L2,
+                                                                 float* __restrict__ d_x, int x_blocks, SmallWgrad a) {
+  if ((int)blockIdx.x < x_blocks) l1_backward_x_body(x, pairwise, w1, d_z1, B, L1, L2, d_x, blockIdx.x, a.bk);
+  else {
+    __shared__ float red[1024];
+    small_wgrad_body(a, (int)blockIdx.x - x_blocks, red);
+  }
+}
+
+// =============================================================================== host half
+// What the shape decides (ClsPlan), where things lie in scratch (BackwardLayout, TrainLayout), what one training-step call
+// launches (TrainStepPlan), one launcher per product, and the C ABI.  Nothing below this line runs on the device.
+
+// ---- timing-only hooks (NNUE_BUILD_ABLATIONS=1 of csrc/build.py; tools/debug/tail_abl.sh, tools/debug/tail_clocks.py): WRONG
+// results by design.  The dispatch calls abl_skip_small() and launch_tail_dx_kernel() unconditionally; a default build has the
+// constant and the plain forms.
+#ifdef NNUE_ABLATIONS
+namespace {
+long long* g_tdx_clocks = nullptr;  // the last tail_dx_train_kernel launch's phase clocks (NNUE_CLS_ABL_TAIL_CLOCKS=1)
+int g_tdx_clock_blocks = 0;
+int abl_knob(const char* name) { const char* e = getenv(name); return e ? atoi(e) : 0; }
+// the d_x blocks alone -- what the launch would cost if the small gradients rode elsewhere
+bool abl_skip_small() { static const int v = abl_knob("NNUE_CLS_ABL_SKIP_SMALL"); return v != 0; }
+
+template <bool DX, typename... Args> void launch_tail_dx_kernel(int grid, hipStream_t s, Args... args) {
+  static const int skip = abl_knob("NNUE_CLS_ABL_SKIP_TAIL_PRODUCTS"), clocks = abl_knob("NNUE_CLS_ABL_TAIL_CLOCKS");
+  if (clocks && grid > g_tdx_clock_blocks) {  // eager launches only: this allocates
+    if (g_tdx_clocks) (void)hipFree(g_tdx_clocks);
+    g_tdx_clocks = nullptr;
+    g_tdx_clock_blocks = hipMalloc(&g_tdx_clocks, (size_t)grid * kTdxClocks * sizeof(long long)) == hipSuccess ? grid : 0;
+  }
+  if (clocks && g_tdx_clocks) (void)hipMemsetAsync(g_tdx_clocks, 0, (size_t)g_tdx_clock_blocks * kTdxClocks * sizeof(long long), s);
+  const TdxAbl abl{clocks ? g_tdx_clocks : nullptr};
+  if (skip) hipLaunchKernelGGL((tail_dx_train_kernel<128, 32, DX, true>), dim3(grid), dim3(kTdxThreads), 0, s, args..., abl);
+  else hipLaunchKernelGGL((tail_dx_train_kernel<128, 32, DX, false>), dim3(grid), dim3(kTdxThreads), 0, s, args..., abl);
+}
+}  // namespace
+
+// the phase clocks of the last tail_dx_train_kernel launch: out[workgroup][kTdxClocks]; returns the workgroup count (or -1)
+extern "C" int nnue_cls_abl_tail_clocks(long long* out, int max_blocks) {
+  if (!g_tdx_clocks || !out) return -1;
+  const int n = g_tdx_clock_blocks < max_blocks ? g_tdx_clock_blocks : max_blocks;
+  if (hipDeviceSynchronize() != hipSuccess) return -1;
+  if (hipMemcpy(out, g_tdx_clocks, (size_t)n * kTdxClocks * sizeof(long long), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  return n;
+}
+#else
+namespace {
+constexpr bool abl_skip_small() { return false; }
+template <bool DX, typename... Args> void launch_tail_dx_kernel(int grid, hipStream_t s, Args... args) {
+  hipLaunchKernelGGL((tail_dx_train_kernel<128, 32, DX, false>), dim3(grid), dim3(kTdxThreads), 0, s, args...);
+}
+}  // namespace
+#endif
+
+namespace {
+
 // ------------------------------------------------------------------ shape policy (shared by scratch + launch)
 struct ClsPlan {
   bool fwd_mfma, bww_mfma, bwx_mfma;
@@ -1216,6 +1289,8 @@ struct ClsPlan {
 };
 
 int bucket_tiles(int B, int K) { return (B + 15) / 16 + K; }  // sum_k ceil(c_k / 16) <= B / 16 + K
+// 16-row tiles of the first-layer products; a grouping (buckets_from) was made for bucket_tiles(B, K) of them
+int row_tiles(int B, int K) { return K > 1 ? bucket_tiles(B, K) : (B + 15) / 16; }
 
 // tail_dx_train_kernel's shapes: one layer stack, the pairwise block, whole 4-wave column groups, a wave per row of
 // logits, and the layer widths it is instantiated for (those of every shipped configuration)
@@ -1229,7 +1304,7 @@ ClsPlan make_plan(int B, int L1, int L2, int pairwise, int K = 1) {
   p.fwd_ksplit = 1;
   if (p.fwd_mfma) {
     // enough K slabs for >= ~1024 waves, each slab a multiple of 16 and (pairwise) inside one half
-    const int tiles = (K > 1 ? bucket_tiles(B, K) : (B + 15) / 16) * ((L2 + 63) / 64);
+    const int tiles = row_tiles(B, K) * ((L2 + 63) / 64);
     int ks = 1;
     while (tiles * ks < 1024 && L1 % (ks * 2 * 16) == 0 && L1 / (ks * 2) >= 64) ks *= 2;
     if (pairwise && ks == 1) ks = 2;
@@ -1240,47 +1315,214 @@ ClsPlan make_plan(int B, int L1, int L2, int pairwise, int K = 1) {
   p.bww_mfma = (L1 % 64 == 0) && (L2 % 32 == 0);
   p.bww_ksplit = 1;
   p.bww_klen = B;
-  if (p.bww_mfma && K > 1) {
-    // per bucket: slices of klen rows of its own segment; a bucket that holds every sample gets ks slices, one that
+  if (p.bww_mfma) {
+    // K > 1, per bucket: slices of klen rows of its own segment; a bucket that holds every sample gets ks slices, one that
     // holds B / K of them one -- the number of non-empty slices (= slabs written and summed) is <= ks + K
-    const int tiles = (L2 / 32) * (L1 / 64);
+    const int tiles = (L2 / 32) * (L1 / 64), want = K > 1 ? 512 : 1024, min_rows = K > 1 ? 64 : 32, unit = K > 1 ? 16 : 4;
     int ks = 1;
-    while (tiles * ks < 512 && B / (ks * 2) >= 64) ks *= 2;
+    while (tiles * ks < want && B / (ks * 2) >= min_rows) ks *= 2;
     p.bww_ksplit = ks;
-    p.bww_klen = (((B + ks - 1) / ks) + 15) / 16 * 16;
-  } else if (p.bww_mfma) {
-    const int tiles = (L2 / 32) * (L1 / 64);
-    int ks = 1;
-    while (tiles * ks < 1024 && B / (ks * 2) >= 32) ks *= 2;
-    p.bww_ksplit = ks;
-    p.bww_klen = ((B + ks - 1) / ks + 3) / 4 * 4;
+    p.bww_klen = ((B + ks - 1) / ks + unit - 1) / unit * unit;
   }
   p.bwx_mfma = (L1 % 32 == 0) && (L2 % 16 == 0);
   return p;
 }
 
-int64_t plan_scratch_floats(const ClsPlan& p, int B, int L1, int L2, int L3, int K = 1) {
+// d_w1 is formed as bww_ksplit batch slabs per stack that a second pass sums (MFMA form only: make_plan splits nothing else)
+bool slab_pass(const ClsPlan& p) { return p.bww_mfma && p.bww_ksplit > 1; }
+long long dw1_floats(int K, int L1, int L2) { return (long long)K * L2 * L1; }
+int64_t slab_floats(const ClsPlan& p, int L1, int L2, int K) { return p.bww_ksplit > 1 ? (int64_t)p.bww_ksplit * dw1_floats(K, L1, L2) : 0; }
+unsigned slab_sum_blocks(long long count) { return (unsigned)((count / 4 + 255) / 256); }  // a float4 per thread
+
+// ------------------------------------------------------------------ scratch layouts (float offsets): one author each
+// nnue_classifier_forward keeps its fwd_ksplit partial sums at the start of the buffer, nnue_classifier_backward d_z1, d_z2
+// and the d_w1 slabs; `total` covers whichever is more.
+struct BackwardLayout { int64_t part, d_z1, d_z2, slabs, total; };
+BackwardLayout backward_layout(const ClsPlan& p, int B, int L1, int L2, int L3, int K = 1) {
+  BackwardLayout t{};
+  t.part = t.d_z1 = 0;  // the two calls use the buffer one after the other
+  t.d_z2 = t.d_z1 + nnue_round_up((int64_t)B * L2, 4);
+  t.slabs = t.d_z2 + nnue_round_up((int64_t)B * L3, 4);
+  // The total is the one nnue_classifier_scratch has always answered: the UNROUNDED sizes + 64 floats.  The two round-ups
+  // above take at most 6 of the 64; the other 58 are slack.
   const int64_t fwd = (int64_t)p.fwd_ksplit * B * L2;
-  const int64_t bwd = (int64_t)B * L2 + (int64_t)B * L3 + (p.bww_ksplit > 1 ? (int64_t)p.bww_ksplit * K * L2 * L1 : 0);
-  return (fwd > bwd ? fwd : bwd) + 64;
+  const int64_t bwd = (int64_t)B * L2 + (int64_t)B * L3 + slab_floats(p, L1, L2, K);
+  t.total = (fwd > bwd ? fwd : bwd) + 64;
+  return t;
 }
 
-// ---- bucket selector + grouping (one workgroup; B a few thousand at most matters for speed, any B is correct) -----
-// bucket[b] = min(K-1, n[b] * K / (P + 1))  (P = flat ids of the map; P == 0: n[b] already IS the bucket, clamped)
-// then a stable counting sort of the samples into bucket-homogeneous 16-row tiles.
-#include "bucket_group.h"
-
-constexpr int kGroupThreads = 1024;  // one pass over a batch of 1024: every phase of the kernel is a latency, not work
-__global__ __launch_bounds__(kGroupThreads) void bucket_group_kernel(GroupArgs ga) {
-  __shared__ int lds[kGroupLdsInts];
-  bucket_group_body<kGroupThreads>(ga, lds);
+struct TrainLayout { int64_t part, d_z1, d_z2, d_logits, slabs, d_z1_g, x_g, total; };
+TrainLayout train_layout(const ClsPlan& p, int B, int L1, int L2, int L3, int C, int K = 1) {
+  TrainLayout t{};
+  int64_t off = 0;
+  auto take = [&](int64_t n) { const int64_t o = off; off += nnue_round_up(n, 4); return o; };
+  // the layer-1 slabs come from this module's own forward (fwd_ksplit of them) or from the fused FeatureTransformer
+  // forward (one per 64 columns of L1, NNUE_CLS_L1_SLABS_GIVEN): room for whichever is more
+  const int64_t ext = (L1 % 64 == 0) ? L1 / 64 : 0;
+  t.part = take((p.fwd_ksplit > ext ? (int64_t)p.fwd_ksplit : ext) * B * L2);
+  t.d_z1 = take((int64_t)B * L2);
+  t.d_z2 = take((int64_t)B * L3);
+  t.d_logits = take((int64_t)B * C);
+  t.slabs = take(slab_floats(p, L1, L2, K));
+  // bucketed stacks: grouped-row copies of d_z1 and of the block's input for the d_w1 product in nnue_ftm_backward_bucketed
+  const int64_t grows = K > 1 ? (int64_t)bucket_tiles(B, K) * 16 : 0;
+  t.d_z1_g = take(grows * L2);
+  t.x_g = take(grows * L1);
+  t.total = off + 4;
+  return t;
 }
 
-Buckets no_buckets() { return Buckets{1, nullptr, nullptr, nullptr, nullptr, 0}; }
+// ------------------------------------------------------------------ the plan of one nnue_classifier_train_step call
+constexpr int kClsBothPhases = NNUE_CLS_PHASE_DX | NNUE_CLS_PHASE_SMALL;
+constexpr int kClsPhaseBits = kClsBothPhases | NNUE_CLS_DW1_BESIDE_DX | NNUE_CLS_L1_SLABS_GIVEN | NNUE_CLS_DW1_RIDES | NNUE_CLS_SMALL_RIDE;
+// NNUE_CLS_TAIL_IN_DX exists in one combination only: on top of everything that leaves this call nothing but d_x
+constexpr int kClsFusedStep = (kClsPhaseBits & ~NNUE_CLS_DW1_BESIDE_DX) | NNUE_CLS_TAIL_IN_DX;
 
-// host-side check + conversion of the C struct; K == 1 -> the reference path whatever the pointers say
+bool phases_valid(int ph) {
+  constexpr int ride_needs = kClsBothPhases | NNUE_CLS_DW1_RIDES;
+  if (ph == kClsFusedStep) return true;
+  if ((ph & ~kClsPhaseBits) || !(ph & kClsBothPhases)) return false;  // a negative value has bits outside the mask
+  if ((ph & NNUE_CLS_DW1_BESIDE_DX) && (ph & NNUE_CLS_DW1_RIDES)) return false;
+  return !(ph & NNUE_CLS_SMALL_RIDE) || (ph & ride_needs) == ride_needs;
+}
+
+// The checks that need nothing but the plan's inputs: the first one the call fails, in the order the call has always made
+// them.  The entry point words them, with its pointer checks in between.
+enum class Refusal { none, bad_phases, slabs_many_stacks, dw1_rides_stack_shape, slabs_shape, sizes, odd_l1, tail_lds, small_ride_no_dx,
+                     fused_tail_shape };
+enum class TailLaunch { none, tile, sample128, sample512 };  // tail_dx_train_kernel without d_x tiles, or tail_train_kernel<NT, vec>
+// with_tail: tail_dx_train_kernel with its d_x tiles (kClsFusedStep), the whole call | with_dw1: l1_backward_xw_mfma, the d_w1
+// product beside d_x (NNUE_CLS_DW1_BESIDE_DX) | with_small: l1_backward_x_small_wgrad, where the small gradients and the mean
+// loss ride (dx_hosts_small) or could | alone: launch_l1_backward_x
+enum class DxLaunch { none, with_tail, with_dw1, with_small, alone };
+
+struct TrainStepPlan {
+  Refusal refusal;
+  ClsPlan p;
+  TrainLayout t;
+  bool l1_forward;                  // launch_l1_forward (false: NNUE_CLS_L1_SLABS_GIVEN, or no NNUE_CLS_PHASE_DX)
+  TailLaunch tail;
+  bool tail_vec;                    // tail_train_kernel's float4 form
+  int tail_grid, tail_slabs;        // tail_train_kernel: a workgroup per sample or per grouped row; layer-1 slabs either tail sums
+  int64_t tail_lds;                 // bytes
+  int tdx_cg, tdx_grid;             // tail_dx_train_kernel: column groups per row tile, workgroups
+  bool grouped;                     // K > 1 with d_w1 left to nnue_ftm_backward_bucketed: the tail also leaves that product's grouped operands
+  DxLaunch dx;
+  bool dx_hosts_small;              // with_small: false under NNUE_CLS_SMALL_RIDE (they ride in nnue_ftm_backward's launch instead)
+  bool dw1_product, small_wgrad;    // NNUE_CLS_PHASE_SMALL: launch_l1_backward_w; small_wgrad_kernel, with the piggy-backed d_w1 slab sum:
+  int sum_slabs, slab_blocks;       // slabs it sums (0: none) in that many workgroups more
+};
+
+TrainStepPlan train_step_plan(int pairwise, int B, int L1, int L2, int L3, int C, int K, int phases, bool want_dx, bool tail_vec_ok) {
+  // The entry point calls this before it has checked the sizes: nothing above Refusal::sizes reads more of them than L1 % n,
+  // and make_plan and the layouts are reached only with positive sizes.
+  TrainStepPlan sp{};
+  auto refuse = [&](Refusal r) { sp.refusal = r; return sp; };
+  if (!phases_valid(phases)) return refuse(Refusal::bad_phases);
+  const bool fused = phases == kClsFusedStep;
+  const bool slabs_given = phases & NNUE_CLS_L1_SLABS_GIVEN, dw1_rides = phases & NNUE_CLS_DW1_RIDES;
+  const bool small_ride = phases & NNUE_CLS_SMALL_RIDE, beside = phases & NNUE_CLS_DW1_BESIDE_DX;
+  if (K != 1 && slabs_given) return refuse(Refusal::slabs_many_stacks);
+  if (K != 1 && dw1_rides && !(pairwise && L1 % 4 == 0)) return refuse(Refusal::dw1_rides_stack_shape);
+  if (slabs_given && !(pairwise && L1 % 64 == 0)) return refuse(Refusal::slabs_shape);
+  if (!(B > 0 && L1 > 0 && L2 > 0 && L3 > 0 && C > 0)) return refuse(Refusal::sizes);
+  if (pairwise && L1 % 2 != 0) return refuse(Refusal::odd_l1);
+  sp.tail_lds = ((int64_t)L2 + 2 * L3 + C + 8) * 4;
+  if (sp.tail_lds > 64 * 1024) return refuse(Refusal::tail_lds);
+  const ClsPlan& p = sp.p = make_plan(B, L1, L2, pairwise, K);
+  sp.t = train_layout(p, B, L1, L2, L3, C, K);
+  sp.grouped = K > 1 && dw1_rides;
+  sp.tail_grid = sp.grouped ? bucket_tiles(B, K) * 16 : B;
+  sp.tail_slabs = slabs_given ? L1 / 64 : p.fwd_ksplit;
+  sp.sum_slabs = slab_pass(p) && !dw1_rides ? p.bww_ksplit : 0;
+  sp.slab_blocks = sp.sum_slabs ? (int)slab_sum_blocks(dw1_floats(K, L1, L2)) : 0;
+  // the d_w1 product runs in the d_x launch (both MFMA forms, d_x requested); a later NNUE_CLS_PHASE_SMALL call with the same
+  // bit then only sums its slabs
+  const bool early_bww = beside && p.bwx_mfma && p.bww_mfma && want_dx;
+  // both phases in one call with d_w1 left to nnue_ftm_backward: the small gradients ride in the d_x launch
+  const bool small_in_dx = (phases & kClsBothPhases) == kClsBothPhases && dw1_rides && p.bwx_mfma && want_dx;
+  if (small_ride && !small_in_dx) return refuse(Refusal::small_ride_no_dx);
+  // The tile tail (tail_dx_train_kernel): at every shape the fused predicate takes, EVERY phase combination forms the
+  // per-sample tail with it -- followed by the d_x tiles in the same launch (kClsFusedStep) or alone, one workgroup per row
+  // tile -- so that the launch forms agree bitwise.  Every other shape keeps tail_train_kernel.
+  const bool tile_tail = tail_dx_supported(B, L1, L2, L3, C, K, pairwise);
+  if (fused && !tile_tail) return refuse(Refusal::fused_tail_shape);
+  sp.tdx_cg = fused ? L1 / 32 / (kTdxThreads / 128) : 1;  // pairs of 16-column tiles / pairs per workgroup
+  sp.tdx_grid = (row_tiles(B, K) + 7) / 8 * 8 * sp.tdx_cg;
+  // fused: the slabs are in scratch, d_w1 and the small gradients ride in nnue_ftm_backward's launch (small_in_dx holds)
+  if (fused) sp.dx = DxLaunch::with_tail;
+  else if (phases & NNUE_CLS_PHASE_DX) {
+    sp.l1_forward = !slabs_given;  // else part[L1/64][B][L2] was written by nnue_ftm_forward_l1 (the FeatureTransformer forward's epilogue)
+    sp.tail = tile_tail ? TailLaunch::tile : C > 256 ? TailLaunch::sample512 : TailLaunch::sample128;
+    sp.tail_vec = L2 % 4 == 0 && L3 % 4 == 0 && tail_vec_ok;
+    if (want_dx) sp.dx = early_bww ? DxLaunch::with_dw1 : small_in_dx ? DxLaunch::with_small : DxLaunch::alone;
+    sp.dx_hosts_small = sp.dx == DxLaunch::with_small && !small_ride;
+  }
+  if ((phases & NNUE_CLS_PHASE_SMALL) && !small_in_dx) {  // needs NNUE_CLS_PHASE_DX's h1, h2, d_logits, d_z1, d_z2 (scratch)
+    sp.dw1_product = !early_bww && !dw1_rides;  // else it ran beside d_x, or rides in nnue_ftm_backward's launch
+    sp.small_wgrad = true;
+  }
+  return sp;
+}
+
+// ------------------------------------------------------------------ one launcher per product
+// what every first-layer product reads
+struct L1Call { const float* x; int pairwise, B, L1, L2; Buckets bk; hipStream_t s; };
+unsigned wave_blocks(long long waves) { return (unsigned)((waves + 3) / 4); }  // 256-thread workgroups of four waves
+// workgroups of the MFMA d_x product and of the MFMA d_w1 product
+int bwx_blocks(const L1Call& c) { return (int)wave_blocks((long long)row_tiles(c.B, c.bk.K) * (c.L1 / 32)); }
+int bww_blocks(const ClsPlan& p, const L1Call& c) { return (int)wave_blocks((long long)c.bk.K * (c.L2 / 32) * (c.L1 / 64) * p.bww_ksplit); }
+
+// part[fwd_ksplit][B][L2] = slabs of l0 W1^T
+void launch_l1_forward(const ClsPlan& p, const L1Call& c, const float* w1, float* part) {
+  if (p.fwd_mfma)
+    hipLaunchKernelGGL(l1_forward_mfma, dim3(wave_blocks((long long)row_tiles(c.B, c.bk.K) * ((c.L2 + 63) / 64) * p.fwd_ksplit)), dim3(256),
+                       0, c.s, c.x, c.pairwise, w1, c.B, c.L1, c.L2, p.fwd_ksplit, part, c.bk);
+  else
+    hipLaunchKernelGGL(l1_forward_simple, dim3(wave_blocks((long long)c.B * c.L2)), dim3(256), 0, c.s, c.x, c.pairwise, w1, c.B, c.L1, c.L2,
+                       part, c.bk);
+}
+
+// d_w1 = d_z1^T l0: into `slabs` where a slab pass follows (slab_pass(p)), else into d_w1
+void launch_l1_backward_w(const ClsPlan& p, const L1Call& c, const float* d_z1, float* slabs, float* d_w1) {
+  if (p.bww_mfma)
+    hipLaunchKernelGGL(l1_backward_w_mfma, dim3((unsigned)bww_blocks(p, c)), dim3(256), 0, c.s, c.x, c.pairwise, d_z1, c.B, c.L1, c.L2,
+                       p.bww_ksplit, p.bww_klen, slab_pass(p) ? slabs : d_w1, c.bk);
+  else
+    hipLaunchKernelGGL(l1_backward_w_simple, dim3(c.bk.K * c.L2, (c.L1 + 255) / 256), dim3(256), 0, c.s, c.x, c.pairwise, d_z1, c.B, c.L1,
+                       c.L2, d_w1, c.bk);
+}
+
+// d_x = (d_z1 W1) through the pairwise block
+void launch_l1_backward_x(const ClsPlan& p, const L1Call& c, const float* w1, const float* d_z1, float* d_x) {
+  if (p.bwx_mfma)
+    hipLaunchKernelGGL(l1_backward_x_mfma, dim3((unsigned)bwx_blocks(c)), dim3(256), 0, c.s, c.x, c.pairwise, w1, d_z1, c.B, c.L1, c.L2, d_x,
+                       c.bk);
+  else
+    hipLaunchKernelGGL(l1_backward_x_simple, dim3(c.B, ((c.pairwise ? c.L1 / 2 : c.L1) + 255) / 256), dim3(256), 0, c.s, c.x, c.pairwise, w1,
+                       d_z1, c.B, c.L1, c.L2, d_x, c.bk);
+}
+
+// The small-gradient family's arguments.  loss_out NULL: no mean-loss block (its workgroup is not counted).  The piggy-backed
+// d_w1 slab sum runs where n_slabs > 0; slab_count is what the callers have always passed (0 from nnue_classifier_backward).
+struct SlabSum { const float* slabs; int n_slabs; long long slab_count; float* d_w1; };
+SmallWgrad small_wgrad_args(const ClsPlan& p, int B, int L2, int L3, int C, const Buckets& bk, const float* d_logits, const float* d_z2,
+                            const float* d_z1, const float* h1, const float* h2, float* d_b1, float* d_w2, float* d_b2, float* d_w3,
+                            float* d_b3, const float* sample_loss, float* loss_out, const SlabSum& sum) {
+  SmallWgrad a{};
+  a.d_logits = d_logits, a.d_z2 = d_z2, a.d_z1 = d_z1, a.h1 = h1, a.h2 = h2;
+  a.B = B, a.L2 = L2, a.L3 = L3, a.C = C;
+  a.d_w3 = d_w3, a.d_b3 = d_b3, a.d_w2 = d_w2, a.d_b2 = d_b2, a.d_b1 = d_b1;
+  a.sample_loss = sample_loss, a.loss_out = loss_out;
+  a.wgrad_blocks = small_wgrad_tiles(L2, L3, C) * bk.K + (loss_out ? 1 : 0);
+  a.slabs = sum.slabs, a.n_slabs = sum.n_slabs, a.slab_count = sum.slab_count, a.d_w1 = sum.d_w1;
+  a.bk = bk, a.bww_klen = p.bww_klen;
+  return a;
+}
+
+// host-side check + conversion of the C struct; NULL or K == 1 -> the reference path whatever the pointers say
 int buckets_from(const nnue_buckets* c, int B, Buckets* out, const char* who) {
-  *out = no_buckets();
+  *out = Buckets{1, nullptr, nullptr, nullptr, nullptr, 0};
   if (!c || c->K <= 1) return NNUE_OK;
   NNUE_REQUIRE(c->K <= kMaxBuckets, NNUE_E_SHAPE, "%s: %d layer stacks (at most %d)", who, c->K, kMaxBuckets);
   NNUE_REQUIRE(c->bucket && c->rows && c->tile_bucket && c->seg, NNUE_E_ARG, "%s: null bucket pointer", who);
@@ -1293,103 +1535,14 @@ int buckets_from(const nnue_buckets* c, int B, Buckets* out, const char* who) {
 }  // namespace
 
 // =============================================================================== C ABI
-namespace {
-
-int forward_impl(const float* x, int pairwise, const float* w1, const float* b1, const float* w2, const float* b2, const float* w3,
-                 const float* b3, float clip, int B, int L1, int L2, int L3, int C, float* h1, float* h2, float* logits, void* scratch,
-                 int64_t scratch_bytes, const Buckets& bk, nnue_stream_t stream) {
-  NNUE_REQUIRE(x && w1 && b1 && w2 && b2 && w3 && b3 && h1 && h2 && logits && scratch, NNUE_E_ARG,
-               "nnue_classifier_forward: null pointer");
-  NNUE_REQUIRE(B > 0 && L1 > 0 && L2 > 0 && L3 > 0 && C > 0, NNUE_E_ARG,
-               "nnue_classifier_forward: B=%d L1=%d L2=%d L3=%d C=%d must be positive", B, L1, L2, L3, C);
-  NNUE_REQUIRE(!pairwise || L1 % 2 == 0, NNUE_E_SHAPE, "nnue_classifier_forward: pairwise needs an even L1 (got %d)", L1);
-  NNUE_REQUIRE((int64_t)(L2 + L3) * 4 <= 64 * 1024, NNUE_E_SHAPE, "nnue_classifier_forward: L2+L3 too large for the LDS tail");
-  const ClsPlan p = make_plan(B, L1, L2, pairwise, bk.K);
-  NNUE_REQUIRE(scratch_bytes >= plan_scratch_floats(p, B, L1, L2, L3, bk.K) * (int64_t)sizeof(float), NNUE_E_SCRATCH,
-               "nnue_classifier_forward: scratch %lld bytes too small", (long long)scratch_bytes);
-  NNUE_REQUIRE(nnue_aligned16(x) && nnue_aligned16(w1) && nnue_aligned16(scratch), NNUE_E_ARG,
-               "nnue_classifier_forward: pointers must be 16-byte aligned");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  float* part = static_cast<float*>(scratch);
-  const int m_tiles = bk.rows ? bk.tiles : (B + 15) / 16;
-  if (p.fwd_mfma) {
-    const long long waves = (long long)m_tiles * ((L2 + 63) / 64) * p.fwd_ksplit;
-    hipLaunchKernelGGL(l1_forward_mfma, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, x, pairwise, w1, B, L1, L2,
-                       p.fwd_ksplit, part, bk);
-  } else {
-    const long long waves = (long long)B * L2;
-    hipLaunchKernelGGL(l1_forward_simple, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, x, pairwise, w1, B, L1, L2, part, bk);
-  }
-  hipLaunchKernelGGL(tail_forward_kernel, dim3(B), dim3(128), (size_t)(L2 + L3) * sizeof(float), s, part, p.fwd_ksplit, b1,
-                     w2, b2, w3, b3, clip, B, L2, L3, C, h1, h2, logits, bk);
-  return nnue_launch_status("nnue_classifier_forward");
-}
-
-int backward_impl(const float* x, int pairwise, const float* w1, const float* w2, const float* w3, float clip, const float* h1,
-                  const float* h2, const float* d_logits, int B, int L1, int L2, int L3, int C, float* d_x, float* d_w1, float* d_b1,
-                  float* d_w2, float* d_b2, float* d_w3, float* d_b3, void* scratch, int64_t scratch_bytes, const Buckets& bk,
-                  nnue_stream_t stream) {
-  NNUE_REQUIRE(x && w1 && w2 && w3 && h1 && h2 && d_logits && scratch, NNUE_E_ARG, "nnue_classifier_backward: null input pointer");
-  NNUE_REQUIRE(d_w1 && d_b1 && d_w2 && d_b2 && d_w3 && d_b3, NNUE_E_ARG, "nnue_classifier_backward: null gradient pointer");
-  NNUE_REQUIRE(B > 0 && L1 > 0 && L2 > 0 && L3 > 0 && C > 0, NNUE_E_ARG,
-               "nnue_classifier_backward: B=%d L1=%d L2=%d L3=%d C=%d must be positive", B, L1, L2, L3, C);
-  NNUE_REQUIRE(!pairwise || L1 % 2 == 0, NNUE_E_SHAPE, "nnue_classifier_backward: pairwise needs an even L1 (got %d)", L1);
-  NNUE_REQUIRE((int64_t)(C + L3) * 4 <= 64 * 1024, NNUE_E_SHAPE, "nnue_classifier_backward: C+L3 too large for the LDS tail");
-  const ClsPlan p = make_plan(B, L1, L2, pairwise, bk.K);
-  NNUE_REQUIRE(scratch_bytes >= plan_scratch_floats(p, B, L1, L2, L3, bk.K) * (int64_t)sizeof(float), NNUE_E_SCRATCH,
-               "nnue_classifier_backward: scratch %lld bytes too small", (long long)scratch_bytes);
-  NNUE_REQUIRE(nnue_aligned16(x) && nnue_aligned16(w1) && nnue_aligned16(scratch) && nnue_aligned16(d_w1), NNUE_E_ARG,
-               "nnue_classifier_backward: pointers must be 16-byte aligned");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int K = bk.K;
-  const int m_tiles = bk.rows ? bk.tiles : (B + 15) / 16;
-  float* d_z1 = static_cast<float*>(scratch);
-  float* d_z2 = d_z1 + nnue_round_up((int64_t)B * L2, 4);
-  float* slabs = d_z2 + nnue_round_up((int64_t)B * L3, 4);
-  hipLaunchKernelGGL(tail_backward_kernel, dim3(B), dim3(128), (size_t)(C + L3) * sizeof(float), s, d_logits, h1, h2, w2, w3,
-                     clip, L2, L3, C, d_z1, d_z2, bk);
-  {
-    const int tiles = small_wgrad_tiles(L2, L3, C) * K;  // no mean loss here
-    const SmallWgrad a{d_logits, d_z2, d_z1, h1, h2, B, L2, L3, C, d_w3, d_b3, d_w2, d_b2, d_b1, nullptr, nullptr, tiles,
-                       nullptr, 0, 0ll, nullptr, bk, p.bww_klen};
-    hipLaunchKernelGGL(small_wgrad_kernel, dim3((unsigned)tiles), dim3(256), 0, s, a);
-  }
-  if (p.bww_mfma) {
-    const long long waves = (long long)K * (L2 / 32) * (L1 / 64) * p.bww_ksplit;
-    float* target = p.bww_ksplit > 1 ? slabs : d_w1;
-    hipLaunchKernelGGL(l1_backward_w_mfma, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, x, pairwise, d_z1, B, L1, L2,
-                       p.bww_ksplit, p.bww_klen, target, bk);
-    if (p.bww_ksplit > 1) {
-      const long long count = (long long)K * L2 * L1;
-      hipLaunchKernelGGL(slab_sum_kernel, dim3((unsigned)((count / 4 + 255) / 256)), dim3(256), 0, s, slabs, p.bww_ksplit,
-                         count, d_w1, bk, p.bww_klen);
-    }
-  } else {
-    hipLaunchKernelGGL(l1_backward_w_simple, dim3(K * L2, (L1 + 255) / 256), dim3(256), 0, s, x, pairwise, d_z1, B, L1, L2, d_w1, bk);
-  }
-  if (d_x) {
-    if (p.bwx_mfma) {
-      const long long waves = (long long)m_tiles * (L1 / 32);
-      hipLaunchKernelGGL(l1_backward_x_mfma, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, x, pairwise, w1, d_z1, B, L1,
-                         L2, d_x, bk);
-    } else {
-      const int cols = pairwise ? L1 / 2 : L1;
-      hipLaunchKernelGGL(l1_backward_x_simple, dim3(B, (cols + 255) / 256), dim3(256), 0, s, x, pairwise, w1, d_z1, B, L1, L2,
-                         d_x, bk);
-    }
-  }
-  return nnue_launch_status("nnue_classifier_backward");
-}
-
-}  // namespace
-
+// Every plain entry point is its *_bucketed form without a grouping (buckets_from(NULL): one layer stack).
 extern "C" int64_t nnue_classifier_scratch(int B, int L1, int L2, int L3) { return nnue_classifier_scratch_bucketed(B, L1, L2, L3, 1); }
 
 extern "C" int64_t nnue_classifier_scratch_bucketed(int B, int L1, int L2, int L3, int K) {
   if (B <= 0 || L1 <= 0 || L2 <= 0 || L3 <= 0 || K <= 0) return 0;
-  const ClsPlan a = make_plan(B, L1, L2, 0, K), b = make_plan(B, L1, L2, 1, K);
-  const int64_t fa = plan_scratch_floats(a, B, L1, L2, L3, K), fb = plan_scratch_floats(b, B, L1, L2, L3, K);
-  return (fa > fb ? fa : fb) * (int64_t)sizeof(float);
+  const int64_t a = backward_layout(make_plan(B, L1, L2, 0, K), B, L1, L2, L3, K).total;
+  const int64_t b = backward_layout(make_plan(B, L1, L2, 1, K), B, L1, L2, L3, K).total;
+  return (a > b ? a : b) * (int64_t)sizeof(float);
 }
 
 extern "C" int nnue_bucket_tile_count(int B, int K) { return (B > 0 && K > 0) ? bucket_tiles(B, K) : 0; }
@@ -1404,12 +1557,11 @@ extern "C" int nnue_bucket_group(const int32_t* n, int B, int P, int K, int32_t*
   return nnue_launch_status("nnue_bucket_group");
 }
 
-extern "C" int nnue_classifier_forward(const float* x, int pairwise, const float* w1, const float* b1, const float* w2,
-                                       const float* b2, const float* w3, const float* b3, float clip, int B, int L1,
-                                       int L2, int L3, int C, float* h1, float* h2, float* logits, void* scratch,
-                                       int64_t scratch_bytes, nnue_stream_t stream) {
-  return forward_impl(x, pairwise, w1, b1, w2, b2, w3, b3, clip, B, L1, L2, L3, C, h1, h2, logits, scratch, scratch_bytes, no_buckets(),
-                      stream);
+extern "C" int nnue_classifier_forward(const float* x, int pairwise, const float* w1, const float* b1, const float* w2, const float* b2,
+                                       const float* w3, const float* b3, float clip, int B, int L1, int L2, int L3, int C, float* h1,
+                                       float* h2, float* logits, void* scratch, int64_t scratch_bytes, nnue_stream_t stream) {
+  return nnue_classifier_forward_bucketed(x, pairwise, w1, b1, w2, b2, w3, b3, clip, B, L1, L2, L3, C, h1, h2, logits, scratch,
+                                          scratch_bytes, nullptr, stream);
 }
 
 extern "C" int nnue_classifier_forward_bucketed(const float* x, int pairwise, const float* w1, const float* b1, const float* w2,
@@ -1419,16 +1571,32 @@ extern "C" int nnue_classifier_forward_bucketed(const float* x, int pairwise, co
   Buckets bk;
   const int rc = buckets_from(buckets, B, &bk, "nnue_classifier_forward_bucketed");
   if (rc != NNUE_OK) return rc;
-  return forward_impl(x, pairwise, w1, b1, w2, b2, w3, b3, clip, B, L1, L2, L3, C, h1, h2, logits, scratch, scratch_bytes, bk, stream);
+  NNUE_REQUIRE(x && w1 && b1 && w2 && b2 && w3 && b3 && h1 && h2 && logits && scratch, NNUE_E_ARG,
+               "nnue_classifier_forward: null pointer");
+  NNUE_REQUIRE(B > 0 && L1 > 0 && L2 > 0 && L3 > 0 && C > 0, NNUE_E_ARG,
+               "nnue_classifier_forward: B=%d L1=%d L2=%d L3=%d C=%d must be positive", B, L1, L2, L3, C);
+  NNUE_REQUIRE(!pairwise || L1 % 2 == 0, NNUE_E_SHAPE, "nnue_classifier_forward: pairwise needs an even L1 (got %d)", L1);
+  NNUE_REQUIRE((int64_t)(L2 + L3) * 4 <= 64 * 1024, NNUE_E_SHAPE, "nnue_classifier_forward: L2+L3 too large for the LDS tail");
+  const ClsPlan p = make_plan(B, L1, L2, pairwise, bk.K);
+  const BackwardLayout t = backward_layout(p, B, L1, L2, L3, bk.K);
+  NNUE_REQUIRE(scratch_bytes >= t.total * (int64_t)sizeof(float), NNUE_E_SCRATCH,
+               "nnue_classifier_forward: scratch %lld bytes too small", (long long)scratch_bytes);
+  NNUE_REQUIRE(nnue_aligned16(x) && nnue_aligned16(w1) && nnue_aligned16(scratch), NNUE_E_ARG,
+               "nnue_classifier_forward: pointers must be 16-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  float* part = static_cast<float*>(scratch) + t.part;
+  launch_l1_forward(p, L1Call{x, pairwise, B, L1, L2, bk, s}, w1, part);
+  hipLaunchKernelGGL(tail_forward_kernel, dim3(B), dim3(128), (size_t)(L2 + L3) * sizeof(float), s, part, p.fwd_ksplit, b1,
+                     w2, b2, w3, b3, clip, B, L2, L3, C, h1, h2, logits, bk);
+  return nnue_launch_status("nnue_classifier_forward");
 }
 
-extern "C" int nnue_classifier_backward(const float* x, int pairwise, const float* w1, const float* w2, const float* w3,
-                                        float clip, const float* h1, const float* h2, const float* d_logits, int B, int L1,
-                                        int L2, int L3, int C, float* d_x, float* d_w1, float* d_b1, float* d_w2,
-                                        float* d_b2, float* d_w3, float* d_b3, void* scratch, int64_t scratch_bytes,
-                                        nnue_stream_t stream) {
-  return backward_impl(x, pairwise, w1, w2, w3, clip, h1, h2, d_logits, B, L1, L2, L3, C, d_x, d_w1, d_b1, d_w2, d_b2, d_w3, d_b3, scratch,
-                       scratch_bytes, no_buckets(), stream);
+extern "C" int nnue_classifier_backward(const float* x, int pairwise, const float* w1, const float* w2, const float* w3, float clip,
+                                        const float* h1, const float* h2, const float* d_logits, int B, int L1, int L2, int L3, int C,
+                                        float* d_x, float* d_w1, float* d_b1, float* d_w2, float* d_b2, float* d_w3, float* d_b3,
+                                        void* scratch, int64_t scratch_bytes, nnue_stream_t stream) {
+  return nnue_classifier_backward_bucketed(x, pairwise, w1, w2, w3, clip, h1, h2, d_logits, B, L1, L2, L3, C, d_x, d_w1, d_b1, d_w2, d_b2,
+                                           d_w3, d_b3, scratch, scratch_bytes, nullptr, stream);
 }
 
 extern "C" int nnue_classifier_backward_bucketed(const float* x, int pairwise, const float* w1, const float* w2, const float* w3,
@@ -1439,231 +1607,35 @@ extern "C" int nnue_classifier_backward_bucketed(const float* x, int pairwise, c
   Buckets bk;
   const int rc = buckets_from(buckets, B, &bk, "nnue_classifier_backward_bucketed");
   if (rc != NNUE_OK) return rc;
-  return backward_impl(x, pairwise, w1, w2, w3, clip, h1, h2, d_logits, B, L1, L2, L3, C, d_x, d_w1, d_b1, d_w2, d_b2, d_w3, d_b3, scratch,
-                       scratch_bytes, bk, stream);
-}
-
-// d_x and the small weight/bias gradients + mean loss in one launch: both only read what the per-sample tail kernel
-// left (d_z1 resp. d_logits, d_z2, h1, h2), so the two launch-sized jobs share the chip (x blocks first).
-__global__ __launch_bounds__(256) void l1_backward_x_small_wgrad(const float* __restrict__ x, int pairwise, const float* __restrict__ w1,
-                                                                 const float* __restrict__ d_z1, int B, int L1, int L2,
-                                                                 float* __restrict__ d_x, int x_blocks, SmallWgrad a) {
-  if ((int)blockIdx.x < x_blocks) l1_backward_x_body(x, pairwise, w1, d_z1, B, L1, L2, d_x, blockIdx.x, a.bk);
-  else {
-    __shared__ float red[1024];
-    small_wgrad_body(a, (int)blockIdx.x - x_blocks, red);
-  }
+  NNUE_REQUIRE(x && w1 && w2 && w3 && h1 && h2 && d_logits && scratch, NNUE_E_ARG, "nnue_classifier_backward: null input pointer");
+  NNUE_REQUIRE(d_w1 && d_b1 && d_w2 && d_b2 && d_w3 && d_b3, NNUE_E_ARG, "nnue_classifier_backward: null gradient pointer");
+  NNUE_REQUIRE(B > 0 && L1 > 0 && L2 > 0 && L3 > 0 && C > 0, NNUE_E_ARG,
+               "nnue_classifier_backward: B=%d L1=%d L2=%d L3=%d C=%d must be positive", B, L1, L2, L3, C);
+  NNUE_REQUIRE(!pairwise || L1 % 2 == 0, NNUE_E_SHAPE, "nnue_classifier_backward: pairwise needs an even L1 (got %d)", L1);
+  NNUE_REQUIRE((int64_t)(C + L3) * 4 <= 64 * 1024, NNUE_E_SHAPE, "nnue_classifier_backward: C+L3 too large for the LDS tail");
+  const ClsPlan p = make_plan(B, L1, L2, pairwise, bk.K);
+  const BackwardLayout t = backward_layout(p, B, L1, L2, L3, bk.K);
+  NNUE_REQUIRE(scratch_bytes >= t.total * (int64_t)sizeof(float), NNUE_E_SCRATCH,
+               "nnue_classifier_backward: scratch %lld bytes too small", (long long)scratch_bytes);
+  NNUE_REQUIRE(nnue_aligned16(x) && nnue_aligned16(w1) && nnue_aligned16(scratch) && nnue_aligned16(d_w1), NNUE_E_ARG,
+               "nnue_classifier_backward: pointers must be 16-byte aligned");
+  const L1Call l1{x, pairwise, B, L1, L2, bk, static_cast<hipStream_t>(stream)};
+  float* base = static_cast<float*>(scratch);
+  float *d_z1 = base + t.d_z1, *d_z2 = base + t.d_z2, *slabs = base + t.slabs;
+  hipLaunchKernelGGL(tail_backward_kernel, dim3(B), dim3(128), (size_t)(C + L3) * sizeof(float), l1.s, d_logits, h1, h2, w2, w3,
+                     clip, L2, L3, C, d_z1, d_z2, bk);
+  const SmallWgrad sw = small_wgrad_args(p, B, L2, L3, C, bk, d_logits, d_z2, d_z1, h1, h2, d_b1, d_w2, d_b2, d_w3, d_b3, nullptr, nullptr,
+                                         SlabSum{});  // no mean loss here, and the slab sum is a launch of its own
+  hipLaunchKernelGGL(small_wgrad_kernel, dim3((unsigned)sw.wgrad_blocks), dim3(256), 0, l1.s, sw);
+  launch_l1_backward_w(p, l1, d_z1, slabs, d_w1);
+  const long long count = dw1_floats(bk.K, L1, L2);
+  if (slab_pass(p))
+    hipLaunchKernelGGL(slab_sum_kernel, dim3(slab_sum_blocks(count)), dim3(256), 0, l1.s, slabs, p.bww_ksplit, count, d_w1, bk, p.bww_klen);
+  if (d_x) launch_l1_backward_x(p, l1, w1, d_z1, d_x);
+  return nnue_launch_status("nnue_classifier_backward");
 }
 
 // ---------------------------------------------------------------- fused training step of the classifier block
-namespace {
-struct TrainLayout {
-  int64_t part, d_z1, d_z2, d_logits, slabs, d_z1_g, x_g, total;  // float offsets
-};
-TrainLayout train_layout(const ClsPlan& p, int B, int L1, int L2, int L3, int C, int K = 1) {
-  TrainLayout t{};
-  int64_t off = 0;
-  auto take = [&](int64_t n) { const int64_t o = off; off += nnue_round_up(n, 4); return o; };
-  // the layer-1 slabs come from this module's own forward (fwd_ksplit of them) or from the fused FeatureTransformer
-  // forward (one per 64 columns of L1, phases bit 8): room for whichever is more
-  const int64_t ext = (L1 % 64 == 0) ? L1 / 64 : 0;
-  t.part = take((p.fwd_ksplit > ext ? (int64_t)p.fwd_ksplit : ext) * B * L2);
-  t.d_z1 = take((int64_t)B * L2);
-  t.d_z2 = take((int64_t)B * L3);
-  t.d_logits = take((int64_t)B * C);
-  t.slabs = take(p.bww_ksplit > 1 ? (int64_t)p.bww_ksplit * K * L2 * L1 : 0);
-  // bucketed stacks: grouped-row copies of d_z1 and of the block's input for the d_w1 product in nnue_ftm_backward_bucketed
-  const int64_t grows = K > 1 ? (int64_t)bucket_tiles(B, K) * 16 : 0;
-  t.d_z1_g = take(grows * L2);
-  t.x_g = take(grows * L1);
-  t.total = off + 4;
-  return t;
-}
-
-#ifdef NNUE_ABLATIONS
-long long* g_tdx_clocks = nullptr;  // the last tail_dx_train_kernel launch's phase clocks (NNUE_CLS_ABL_TAIL_CLOCKS=1)
-int g_tdx_clock_blocks = 0;
-#endif
-
-int train_step_impl(const float* x, int pairwise, const float* w1, const float* b1, const float* w2, const float* b2, const float* w3,
-                    const float* b3, float clip, const int64_t* labels, float grad_scale, int B, int L1, int L2, int L3, int C, float* h1,
-                    float* h2, float* logits, float* sample_loss, float* loss, float* d_x, float* d_w1, float* d_b1, float* d_w2,
-                    float* d_b2, float* d_w3, float* d_b3, void* scratch, int64_t scratch_bytes, int phases, const Buckets& bk,
-                    nnue_stream_t stream) {
-  NNUE_REQUIRE(x && w1 && b1 && w2 && b2 && w3 && b3 && labels && h1 && h2 && logits && sample_loss && loss && scratch,
-               NNUE_E_ARG, "nnue_classifier_train_step: null pointer");
-  // bit 64 exists in one combination only: 123 = 59 + the per-sample tail inside the d_x launch
-  const bool fuse_tail = phases == 123;
-  if (fuse_tail) phases = 59;
-  NNUE_REQUIRE(phases >= 1 && phases <= 63 && (phases & 3) && (phases & 20) != 20 && (!(phases & 32) || (phases & 19) == 19), NNUE_E_ARG,
-               "nnue_classifier_train_step: phases = 1 (activations + d_x) | 2 (weight gradients + loss) [| 4: first-layer weight product beside "
-               "d_x] [| 8: layer-1 slabs already at the start of scratch] [| 16 (not with 4): d_w1 comes from nnue_ftm_backward] [| 32 (with 1, 2 "
-               "and 16): the small gradients and the mean loss ride in nnue_ftm_backward's launch as well] [| 64 (only as 123 = 59 + 64): the "
-               "per-sample tail runs in the d_x launch]");
-  const bool ext_dw1 = (phases & 16) != 0;
-  const bool ext_small = (phases & 32) != 0;
-  const bool ext_slabs = (phases & 8) != 0;
-  const int K = bk.K;
-  NNUE_REQUIRE(K == 1 || !ext_slabs, NNUE_E_ARG,
-               "nnue_classifier_train_step: phases bit 8 (layer-1 slabs formed in the FeatureTransformer forward's epilogue) exists for one layer stack only");
-  NNUE_REQUIRE(K == 1 || !ext_dw1 || (pairwise && L1 % 4 == 0), NNUE_E_SHAPE,
-               "nnue_classifier_train_step: phases bit 16 with K > 1 needs the pairwise block and L1 %% 4 == 0");
-  NNUE_REQUIRE(!ext_slabs || (pairwise && L1 % 64 == 0), NNUE_E_SHAPE,
-               "nnue_classifier_train_step: phases bit 8 needs the pairwise block and L1 %% 64 == 0 (got L1=%d)", L1);
-  NNUE_REQUIRE(d_w1 && d_b1 && d_w2 && d_b2 && d_w3 && d_b3, NNUE_E_ARG, "nnue_classifier_train_step: null gradient pointer");
-  NNUE_REQUIRE(B > 0 && L1 > 0 && L2 > 0 && L3 > 0 && C > 0, NNUE_E_ARG,
-               "nnue_classifier_train_step: B=%d L1=%d L2=%d L3=%d C=%d must be positive", B, L1, L2, L3, C);
-  NNUE_REQUIRE(!pairwise || L1 % 2 == 0, NNUE_E_SHAPE, "nnue_classifier_train_step: pairwise needs an even L1 (got %d)", L1);
-  const int64_t tail_lds = ((int64_t)L2 + 2 * L3 + C + 8) * 4;
-  NNUE_REQUIRE(tail_lds <= 64 * 1024, NNUE_E_SHAPE, "nnue_classifier_train_step: L2+2*L3+C too large for the LDS tail");
-  const ClsPlan p = make_plan(B, L1, L2, pairwise, K);
-  const TrainLayout t = train_layout(p, B, L1, L2, L3, C, K);
-  NNUE_REQUIRE(scratch_bytes >= t.total * (int64_t)sizeof(float), NNUE_E_SCRATCH,
-               "nnue_classifier_train_step: scratch %lld < %lld bytes", (long long)scratch_bytes, (long long)(t.total * 4));
-  NNUE_REQUIRE(nnue_aligned16(x) && nnue_aligned16(w1) && nnue_aligned16(scratch) && nnue_aligned16(d_w1) && nnue_aligned16(h1) &&
-                   nnue_aligned16(h2),
-               NNUE_E_ARG, "nnue_classifier_train_step: pointers must be 16-byte aligned");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  float* base = static_cast<float*>(scratch);
-  float *part = base + t.part, *d_z1 = base + t.d_z1, *d_z2 = base + t.d_z2, *d_logits = base + t.d_logits, *slabs = base + t.slabs;
-  // K > 1 with d_w1 left to nnue_ftm_backward_bucketed: the tail kernel runs per grouped row and leaves that product's operands
-  const bool grouped = K > 1 && ext_dw1;
-  float* d_z1_g = grouped ? base + t.d_z1_g : nullptr;
-  float* x_g = grouped ? base + t.x_g : nullptr;
-  const int tail_grid = grouped ? bk.tiles * 16 : B;
-  const bool slab_pass = p.bww_mfma && p.bww_ksplit > 1;
-  const int m_tiles = bk.rows ? bk.tiles : (B + 15) / 16;
-  // bit 4: the d_w1 product runs in phase 1's d_x launch (both MFMA forms, d_x requested); a later phase-2 call with the
-  // same bit then only sums its slabs
-  const bool early_bww = (phases & 4) && p.bwx_mfma && p.bww_mfma && d_x != nullptr;
-  const int tail_slabs = ext_slabs ? L1 / 64 : p.fwd_ksplit;
-  // one launch: the small weight/bias gradients (per layer stack), the mean loss and (piggy-backed) the d_w1 slab sum
-  const int wgrad_blocks = small_wgrad_tiles(L2, L3, C) * K + 1;  // one workgroup per (tile, stack) + the mean loss
-  const long long count = (long long)K * L2 * L1;
-  const int slab_blocks = slab_pass && !ext_dw1 ? (int)((count / 4 + 255) / 256) : 0;
-  const SmallWgrad sw{d_logits, d_z2, d_z1, h1, h2, B, L2, L3, C, d_w3, d_b3, d_w2, d_b2, d_b1, sample_loss, loss, wgrad_blocks,
-                      slabs, slab_pass && !ext_dw1 ? p.bww_ksplit : 0, count, d_w1, bk, p.bww_klen};
-  // both phases in one call with d_w1 left to nnue_ftm_backward: the small gradients ride in the d_x launch
-  const bool wgrad_rides = (phases & 3) == 3 && ext_dw1 && p.bwx_mfma && d_x != nullptr;
-  NNUE_REQUIRE(!ext_small || wgrad_rides, NNUE_E_SHAPE,
-               "nnue_classifier_train_step: phases bit 32 needs the d_x launch the small gradients otherwise ride in (MFMA shapes, d_x requested)");
-  NNUE_REQUIRE(!fuse_tail || tail_dx_supported(B, L1, L2, L3, C, K, pairwise), NNUE_E_SHAPE,
-               "nnue_classifier_train_step: phases 123 (tail inside the d_x launch) needs nnue_classifier_train_fused_tail_supported "
-               "(B=%d L1=%d L2=%d L3=%d C=%d K=%d pairwise=%d)", B, L1, L2, L3, C, K, pairwise);
-  NNUE_REQUIRE(!fuse_tail || (nnue_aligned16(w2) && nnue_aligned16(w3)), NNUE_E_ARG,
-               "nnue_classifier_train_step: phases 123 needs 16-byte aligned w2 and w3");
-  // The tile tail (tail_dx_train_kernel): at every shape the fused predicate takes, EVERY phase combination forms the
-  // per-sample tail with it -- followed by the d_x tiles in the same launch (phases 123) or alone, one workgroup per row
-  // tile -- so that the launch forms agree bitwise.  Every other shape keeps tail_train_kernel.
-  const bool tile_tail = tail_dx_supported(B, L1, L2, L3, C, K, pairwise);
-  auto launch_tile_tail = [&](bool dx, int slabs_in) {
-    const int n_cg = dx ? L1 / 32 / (kTdxThreads / 128) : 1;  // pairs of 16-column tiles / pairs per workgroup
-    const int tdx_grid = (m_tiles + 7) / 8 * 8 * n_cg;
-#ifdef NNUE_ABLATIONS  // timing-only hooks of tail_dx_train_kernel (tools/debug/tail_abl.sh)
-    static const int abl_skip = [] { const char* e = getenv("NNUE_CLS_ABL_SKIP_TAIL_PRODUCTS"); return e ? atoi(e) : 0; }();
-    static const int abl_clocks = [] { const char* e = getenv("NNUE_CLS_ABL_TAIL_CLOCKS"); return e ? atoi(e) : 0; }();
-    if (abl_clocks && tdx_grid > g_tdx_clock_blocks) {  // eager launches only: this allocates
-      if (g_tdx_clocks) (void)hipFree(g_tdx_clocks);
-      g_tdx_clocks = nullptr;
-      g_tdx_clock_blocks = hipMalloc(&g_tdx_clocks, (size_t)tdx_grid * kTdxClocks * sizeof(long long)) == hipSuccess ? tdx_grid : 0;
-    }
-    if (abl_clocks && g_tdx_clocks) (void)hipMemsetAsync(g_tdx_clocks, 0, (size_t)g_tdx_clock_blocks * kTdxClocks * sizeof(long long), s);
-    const TdxAbl abl{abl_clocks ? g_tdx_clocks : nullptr};
-#define NNUE_TDX_ABL_ARG , abl
-#else
-    constexpr int abl_skip = 0;
-#define NNUE_TDX_ABL_ARG
-#endif
-#define NNUE_TDX(DX, SKIP)                                                                                                                \
-  hipLaunchKernelGGL((tail_dx_train_kernel<128, 32, DX, SKIP>), dim3(tdx_grid), dim3(kTdxThreads), 0, s, part, slabs_in, b1, w2, b2, w3, b3, \
-                     clip, labels, grad_scale / (float)B, B, C, h1, h2, logits, sample_loss, d_logits, d_z1, d_z2, x, w1, L1, d_x, m_tiles, \
-                     n_cg NNUE_TDX_ABL_ARG)
-    if (abl_skip) {
-#ifdef NNUE_ABLATIONS
-      if (dx) NNUE_TDX(true, true); else NNUE_TDX(false, true);
-#endif
-    } else if (dx) NNUE_TDX(true, false);
-    else NNUE_TDX(false, false);
-#undef NNUE_TDX
-#undef NNUE_TDX_ABL_ARG
-  };
-  if (fuse_tail) {  // phases 123: the slabs are in scratch, d_w1 and the small gradients ride in nnue_ftm_backward's launch
-    launch_tile_tail(true, L1 / 64);
-    return nnue_launch_status("nnue_classifier_train_step");
-  }
-  if (phases & 1) {
-    if (ext_slabs) {
-      // part[L1/64][B][L2] was written by nnue_ftm_forward_l1 (the FeatureTransformer forward's epilogue)
-    } else if (p.fwd_mfma) {
-      const long long waves = (long long)m_tiles * ((L2 + 63) / 64) * p.fwd_ksplit;
-      hipLaunchKernelGGL(l1_forward_mfma, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, x, pairwise, w1, B, L1, L2, p.fwd_ksplit, part, bk);
-    } else {
-      const long long waves = (long long)B * L2;
-      hipLaunchKernelGGL(l1_forward_simple, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, x, pairwise, w1, B, L1, L2, part, bk);
-    }
-    const bool vec = L2 % 4 == 0 && L3 % 4 == 0 && nnue_aligned16(w2) && nnue_aligned16(w3);
-#define NNUE_TAIL(NT, V)                                                                                                                  \
-  hipLaunchKernelGGL((tail_train_kernel<NT, V>), dim3(tail_grid), dim3(NT), (size_t)tail_lds, s, part, tail_slabs, b1, w2, b2, w3, b3, clip, \
-                     labels, grad_scale / (float)B, B, L2, L3, C, h1, h2, logits, sample_loss, d_logits, d_z1, d_z2, bk, x, L1, x_g, d_z1_g)
-    if (tile_tail) launch_tile_tail(false, tail_slabs);
-    else if (C > 256) { if (vec) NNUE_TAIL(512, true); else NNUE_TAIL(512, false); }
-    else { if (vec) NNUE_TAIL(128, true); else NNUE_TAIL(128, false); }
-#undef NNUE_TAIL
-    if (d_x) {
-      if (p.bwx_mfma && early_bww) {
-        const long long xw = (long long)m_tiles * (L1 / 32), ww = (long long)K * (L2 / 32) * (L1 / 64) * p.bww_ksplit;
-        const int w_blocks = (int)((ww + 3) / 4);
-        hipLaunchKernelGGL(l1_backward_xw_mfma, dim3((unsigned)(w_blocks + (xw + 3) / 4)), dim3(256), 0, s, x, pairwise, w1, d_z1, B, L1, L2,
-                           d_x, w_blocks, p.bww_ksplit, p.bww_klen, slab_pass ? slabs : d_w1, bk);
-      } else if (wgrad_rides) {
-        const long long waves = (long long)m_tiles * (L1 / 32);
-        const int x_blocks = (int)((waves + 3) / 4);
-        // timing-only ablation (tools/debug, WRONG small gradients): the d_x blocks alone -- what the launch would cost if the small
-        // gradients rode elsewhere
-#ifdef NNUE_ABLATIONS  // compiled only with NNUE_BUILD_ABLATIONS=1 (csrc/build.py)
-        static const int skip_small = [] { const char* e = getenv("NNUE_CLS_ABL_SKIP_SMALL"); return e ? atoi(e) : 0; }();
-#else
-        constexpr int skip_small = 0;
-#endif
-        hipLaunchKernelGGL(l1_backward_x_small_wgrad, dim3((unsigned)(x_blocks + ((skip_small || ext_small) ? 0 : wgrad_blocks))), dim3(256), 0, s, x, pairwise, w1,
-                           (const float*)d_z1, B, L1, L2, d_x, x_blocks, sw);
-      } else if (p.bwx_mfma) {
-        const long long waves = (long long)m_tiles * (L1 / 32);
-        hipLaunchKernelGGL(l1_backward_x_mfma, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, x, pairwise, w1, d_z1, B, L1, L2, d_x, bk);
-      } else {
-        const int cols = pairwise ? L1 / 2 : L1;
-        hipLaunchKernelGGL(l1_backward_x_simple, dim3(B, (cols + 255) / 256), dim3(256), 0, s, x, pairwise, w1, d_z1, B, L1, L2, d_x, bk);
-      }
-    }
-  }
-  if (wgrad_rides) return nnue_launch_status("nnue_classifier_train_step");
-  if (phases & 2) {  // needs phase 1's h1, h2, d_logits, d_z1, d_z2 (scratch) -- nothing downstream depends on it
-    if (early_bww || ext_dw1) {
-      // the first-layer product already ran beside d_x (phases bit 4), or rides in nnue_ftm_backward's launch (bit 16)
-    } else if (p.bww_mfma) {
-      const long long waves = (long long)K * (L2 / 32) * (L1 / 64) * p.bww_ksplit;
-      hipLaunchKernelGGL(l1_backward_w_mfma, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, x, pairwise, d_z1, B, L1, L2, p.bww_ksplit,
-                         p.bww_klen, slab_pass ? slabs : d_w1, bk);
-    } else {
-      hipLaunchKernelGGL(l1_backward_w_simple, dim3(K * L2, (L1 + 255) / 256), dim3(256), 0, s, x, pairwise, d_z1, B, L1, L2, d_w1, bk);
-    }
-    hipLaunchKernelGGL(small_wgrad_kernel, dim3(wgrad_blocks + slab_blocks), dim3(256), 0, s, sw);
-  }
-  return nnue_launch_status("nnue_classifier_train_step");
-}
-}  // namespace
-
-#ifdef NNUE_ABLATIONS
-// the phase clocks of the last tail_dx_train_kernel launch: out[workgroup][kTdxClocks]; returns the workgroup count (or -1)
-extern "C" int nnue_cls_abl_tail_clocks(long long* out, int max_blocks) {
-  if (!g_tdx_clocks || !out) return -1;
-  const int n = g_tdx_clock_blocks < max_blocks ? g_tdx_clock_blocks : max_blocks;
-  if (hipDeviceSynchronize() != hipSuccess) return -1;
-  if (hipMemcpy(out, g_tdx_clocks, (size_t)n * kTdxClocks * sizeof(long long), hipMemcpyDeviceToHost) != hipSuccess) return -1;
-  return n;
-}
-#endif
-
 extern "C" int64_t nnue_classifier_train_scratch(int B, int L1, int L2, int L3, int C) {
   return nnue_classifier_train_scratch_bucketed(B, L1, L2, L3, C, 1);
 }
@@ -1694,8 +1666,8 @@ extern "C" int64_t nnue_classifier_train_x_grouped_offset(int B, int L1, int L2,
   return train_layout(make_plan(B, L1, L2, 1, K), B, L1, L2, L3, C, K).x_g * (int64_t)sizeof(float);
 }
 
-// The arguments of the small-gradient tile family for a step run with phases bit 32 (host side only; what train_step_impl builds
-// for its own launch, with no slab pass: d_w1 belongs to nnue_ftm_backward's rider in this mode)
+// The arguments of the small-gradient tile family for a step run with NNUE_CLS_SMALL_RIDE (host side only): those of the
+// step's own launch (small_wgrad_args) with no slab sum -- d_w1 belongs to nnue_ftm_backward's rider in this mode
 extern "C" int nnue_classifier_train_rider(int pairwise, int B, int L1, int L2, int L3, int C, const float* h1, const float* h2,
                                            const float* sample_loss, float* loss, float* d_b1, float* d_w2, float* d_b2, float* d_w3,
                                            float* d_b3, void* scratch, int64_t scratch_bytes, const nnue_buckets* buckets,
@@ -1711,25 +1683,25 @@ extern "C" int nnue_classifier_train_rider(int pairwise, int B, int L1, int L2, 
   NNUE_REQUIRE(scratch_bytes >= t.total * (int64_t)sizeof(float), NNUE_E_SCRATCH, "nnue_classifier_train_rider: scratch %lld < %lld bytes",
                (long long)scratch_bytes, (long long)(t.total * 4));
   float* base = static_cast<float*>(scratch);
-  const int wgrad_blocks = small_wgrad_tiles(L2, L3, C) * bk.K + 1;
-  const SmallWgrad sw{base + t.d_logits, base + t.d_z2, base + t.d_z1, h1, h2, B, L2, L3, C, d_w3, d_b3, d_w2, d_b2, d_b1, sample_loss, loss,
-                      wgrad_blocks, nullptr, 0, (long long)bk.K * L2 * L1, nullptr, bk, p.bww_klen};
+  const SmallWgrad sw = small_wgrad_args(p, B, L2, L3, C, bk, base + t.d_logits, base + t.d_z2, base + t.d_z1, h1, h2, d_b1, d_w2, d_b2, d_w3,
+                                         d_b3, sample_loss, loss, SlabSum{nullptr, 0, dw1_floats(bk.K, L1, L2), nullptr});
   static_assert(sizeof(SmallWgrad) <= sizeof(nnue_cls_rider), "nnue_cls_rider is too small");
   memset(out, 0, sizeof(*out));
   memcpy(out, &sw, sizeof(sw));
   return NNUE_OK;
 }
 
-extern "C" int nnue_classifier_train_step(const float* x, int pairwise, const float* w1, const float* b1, const float* w2,
-                                          const float* b2, const float* w3, const float* b3, float clip,
-                                          const int64_t* labels, float grad_scale, int B, int L1, int L2, int L3, int C,
-                                          float* h1, float* h2, float* logits, float* sample_loss, float* loss, float* d_x,
-                                          float* d_w1, float* d_b1, float* d_w2, float* d_b2, float* d_w3, float* d_b3,
-                                          void* scratch, int64_t scratch_bytes, int phases, nnue_stream_t stream) {
-  return train_step_impl(x, pairwise, w1, b1, w2, b2, w3, b3, clip, labels, grad_scale, B, L1, L2, L3, C, h1, h2, logits, sample_loss, loss,
-                         d_x, d_w1, d_b1, d_w2, d_b2, d_w3, d_b3, scratch, scratch_bytes, phases, no_buckets(), stream);
+extern "C" int nnue_classifier_train_step(const float* x, int pairwise, const float* w1, const float* b1, const float* w2, const float* b2,
+                                          const float* w3, const float* b3, float clip, const int64_t* labels, float grad_scale, int B,
+                                          int L1, int L2, int L3, int C, float* h1, float* h2, float* logits, float* sample_loss,
+                                          float* loss, float* d_x, float* d_w1, float* d_b1, float* d_w2, float* d_b2, float* d_w3,
+                                          float* d_b3, void* scratch, int64_t scratch_bytes, int phases, nnue_stream_t stream) {
+  return nnue_classifier_train_step_bucketed(x, pairwise, w1, b1, w2, b2, w3, b3, clip, labels, grad_scale, B, L1, L2, L3, C, h1, h2, logits,
+                                             sample_loss, loss, d_x, d_w1, d_b1, d_w2, d_b2, d_w3, d_b3, scratch, scratch_bytes, phases,
+                                             nullptr, stream);
 }
 
+// Checks in the order they have always had, then one arm per field of the plan (train_step_plan)
 extern "C" int nnue_classifier_train_step_bucketed(const float* x, int pairwise, const float* w1, const float* b1, const float* w2,
                                                    const float* b2, const float* w3, const float* b3, float clip, const int64_t* labels,
                                                    float grad_scale, int B, int L1, int L2, int L3, int C, float* h1, float* h2,
@@ -1739,6 +1711,76 @@ extern "C" int nnue_classifier_train_step_bucketed(const float* x, int pairwise,
   Buckets bk;
   const int rc = buckets_from(buckets, B, &bk, "nnue_classifier_train_step_bucketed");
   if (rc != NNUE_OK) return rc;
-  return train_step_impl(x, pairwise, w1, b1, w2, b2, w3, b3, clip, labels, grad_scale, B, L1, L2, L3, C, h1, h2, logits, sample_loss, loss,
-                         d_x, d_w1, d_b1, d_w2, d_b2, d_w3, d_b3, scratch, scratch_bytes, phases, bk, stream);
+  NNUE_REQUIRE(x && w1 && b1 && w2 && b2 && w3 && b3 && labels && h1 && h2 && logits && sample_loss && loss && scratch,
+               NNUE_E_ARG, "nnue_classifier_train_step: null pointer");
+  const int K = bk.K;
+  const TrainStepPlan sp = train_step_plan(pairwise, B, L1, L2, L3, C, K, phases, d_x != nullptr, nnue_aligned16(w2) && nnue_aligned16(w3));
+  const ClsPlan& p = sp.p;
+  const TrainLayout& t = sp.t;
+  NNUE_REQUIRE(sp.refusal != Refusal::bad_phases, NNUE_E_ARG,
+               "nnue_classifier_train_step: phases = 1 (activations + d_x) | 2 (weight gradients + loss) [| 4: first-layer weight product beside "
+               "d_x] [| 8: layer-1 slabs already at the start of scratch] [| 16 (not with 4): d_w1 comes from nnue_ftm_backward] [| 32 (with 1, 2 "
+               "and 16): the small gradients and the mean loss ride in nnue_ftm_backward's launch as well] [| 64 (only as 123 = 59 + 64): the "
+               "per-sample tail runs in the d_x launch]");
+  NNUE_REQUIRE(sp.refusal != Refusal::slabs_many_stacks, NNUE_E_ARG,
+               "nnue_classifier_train_step: phases bit 8 (layer-1 slabs formed in the FeatureTransformer forward's epilogue) exists for one layer stack only");
+  NNUE_REQUIRE(sp.refusal != Refusal::dw1_rides_stack_shape, NNUE_E_SHAPE,
+               "nnue_classifier_train_step: phases bit 16 with K > 1 needs the pairwise block and L1 %% 4 == 0");
+  NNUE_REQUIRE(sp.refusal != Refusal::slabs_shape, NNUE_E_SHAPE,
+               "nnue_classifier_train_step: phases bit 8 needs the pairwise block and L1 %% 64 == 0 (got L1=%d)", L1);
+  NNUE_REQUIRE(d_w1 && d_b1 && d_w2 && d_b2 && d_w3 && d_b3, NNUE_E_ARG, "nnue_classifier_train_step: null gradient pointer");
+  NNUE_REQUIRE(sp.refusal != Refusal::sizes, NNUE_E_ARG, "nnue_classifier_train_step: B=%d L1=%d L2=%d L3=%d C=%d must be positive", B, L1, L2,
+               L3, C);
+  NNUE_REQUIRE(sp.refusal != Refusal::odd_l1, NNUE_E_SHAPE, "nnue_classifier_train_step: pairwise needs an even L1 (got %d)", L1);
+  NNUE_REQUIRE(sp.refusal != Refusal::tail_lds, NNUE_E_SHAPE, "nnue_classifier_train_step: L2+2*L3+C too large for the LDS tail");
+  NNUE_REQUIRE(scratch_bytes >= t.total * (int64_t)sizeof(float), NNUE_E_SCRATCH,
+               "nnue_classifier_train_step: scratch %lld < %lld bytes", (long long)scratch_bytes, (long long)(t.total * 4));
+  NNUE_REQUIRE(nnue_aligned16(x) && nnue_aligned16(w1) && nnue_aligned16(scratch) && nnue_aligned16(d_w1) && nnue_aligned16(h1) &&
+                   nnue_aligned16(h2),
+               NNUE_E_ARG, "nnue_classifier_train_step: pointers must be 16-byte aligned");
+  NNUE_REQUIRE(sp.refusal != Refusal::small_ride_no_dx, NNUE_E_SHAPE,
+               "nnue_classifier_train_step: phases bit 32 needs the d_x launch the small gradients otherwise ride in (MFMA shapes, d_x requested)");
+  NNUE_REQUIRE(sp.refusal != Refusal::fused_tail_shape, NNUE_E_SHAPE,
+               "nnue_classifier_train_step: phases 123 (tail inside the d_x launch) needs nnue_classifier_train_fused_tail_supported "
+               "(B=%d L1=%d L2=%d L3=%d C=%d K=%d pairwise=%d)", B, L1, L2, L3, C, K, pairwise);
+  NNUE_REQUIRE(sp.dx != DxLaunch::with_tail || (nnue_aligned16(w2) && nnue_aligned16(w3)), NNUE_E_ARG,
+               "nnue_classifier_train_step: phases 123 needs 16-byte aligned w2 and w3");
+
+  const L1Call l1{x, pairwise, B, L1, L2, bk, static_cast<hipStream_t>(stream)};
+  hipStream_t s = l1.s;
+  float* base = static_cast<float*>(scratch);
+  float *part = base + t.part, *d_z1 = base + t.d_z1, *d_z2 = base + t.d_z2, *d_logits = base + t.d_logits, *slabs = base + t.slabs;
+  float *d_z1_g = sp.grouped ? base + t.d_z1_g : nullptr, *x_g = sp.grouped ? base + t.x_g : nullptr;
+  // one launch: the small weight/bias gradients (per layer stack), the mean loss and (piggy-backed) the d_w1 slab sum
+  const SmallWgrad sw = small_wgrad_args(p, B, L2, L3, C, bk, d_logits, d_z2, d_z1, h1, h2, d_b1, d_w2, d_b2, d_w3, d_b3, sample_loss, loss,
+                                         SlabSum{slabs, sp.sum_slabs, dw1_floats(K, L1, L2), d_w1});
+  auto tile_tail = [&](auto with_dx) {
+    launch_tail_dx_kernel<decltype(with_dx)::value>(sp.tdx_grid, s, part, sp.tail_slabs, b1, w2, b2, w3, b3, clip, labels, grad_scale / (float)B,
+                                                    B, C, h1, h2, logits, sample_loss, d_logits, d_z1, d_z2, x, w1, L1, d_x,
+                                                    row_tiles(B, K), sp.tdx_cg);
+  };
+#define NNUE_TAIL(NT, V)                                                                                                                  \
+  hipLaunchKernelGGL((tail_train_kernel<NT, V>), dim3(sp.tail_grid), dim3(NT), (size_t)sp.tail_lds, s, part, sp.tail_slabs, b1, w2, b2, w3, b3, \
+                     clip, labels, grad_scale / (float)B, B, L2, L3, C, h1, h2, logits, sample_loss, d_logits, d_z1, d_z2, bk, x, L1, x_g, d_z1_g)
+
+  // A kernel template's instantiations stand in the code object in the order of their first use here: tail_dx_train_kernel
+  // with, then without d_x tiles, tail_train_kernel<512, .>, <128, .>.  A new arm goes behind them, so that no kernel moves.
+  if (sp.dx == DxLaunch::with_tail) tile_tail(std::true_type{});  // the whole call: nothing below is planned with it
+  if (sp.l1_forward) launch_l1_forward(p, l1, w1, part);
+  if (sp.tail == TailLaunch::tile) tile_tail(std::false_type{});
+  else if (sp.tail == TailLaunch::sample512) { if (sp.tail_vec) NNUE_TAIL(512, true); else NNUE_TAIL(512, false); }
+  else if (sp.tail == TailLaunch::sample128) { if (sp.tail_vec) NNUE_TAIL(128, true); else NNUE_TAIL(128, false); }
+#undef NNUE_TAIL
+  if (sp.dx == DxLaunch::with_dw1) {
+    const int w_blocks = bww_blocks(p, l1);
+    hipLaunchKernelGGL(l1_backward_xw_mfma, dim3((unsigned)(w_blocks + bwx_blocks(l1))), dim3(256), 0, s, x, pairwise, w1, d_z1, B, L1, L2, d_x,
+                       w_blocks, p.bww_ksplit, p.bww_klen, slab_pass(p) ? slabs : d_w1, bk);
+  } else if (sp.dx == DxLaunch::with_small) {
+    const int x_blocks = bwx_blocks(l1), small_blocks = sp.dx_hosts_small && !abl_skip_small() ? sw.wgrad_blocks : 0;
+    hipLaunchKernelGGL(l1_backward_x_small_wgrad, dim3((unsigned)(x_blocks + small_blocks)), dim3(256), 0, s, x, pairwise, w1,
+                       (const float*)d_z1, B, L1, L2, d_x, x_blocks, sw);
+  } else if (sp.dx == DxLaunch::alone) launch_l1_backward_x(p, l1, w1, d_z1, d_x);
+  if (sp.dw1_product) launch_l1_backward_w(p, l1, d_z1, slabs, d_w1);
+  if (sp.small_wgrad) hipLaunchKernelGGL(small_wgrad_kernel, dim3(sw.wgrad_blocks + sp.slab_blocks), dim3(256), 0, s, sw);
+  return nnue_launch_status("nnue_classifier_train_step");
 }
