@@ -526,6 +526,51 @@ int nnue_classifier_train_step_bucketed(const float* x, int pairwise,
                                         void* scratch, int64_t scratch_bytes, int phases,
                                         const nnue_buckets* buckets, nnue_stream_t stream);
 
+/* ---- soft targets (build extension: label smoothing, mixup, CutMix) -------------------------------------------------
+ *
+ * The reference's loop trains on one integer label per sample (compute_loss, train.py:250-254); label smoothing is one
+ * argument of its F.cross_entropy and mixup / CutMix two lines around the batch.  Here the loss sits inside the
+ * classifier's tail kernels, so the soft form is an arm of those kernels.  Per sample b: labels a = labels[b] and
+ * a2 = labels_b[b], a weight lam[b] in [0, 1], and one smoothing constant eps in [0, 1) per call; labels_b == NULL
+ * means a2 = a and lam = 1 (lam is then not read).  With mx = max_c z_c and se = sum_c exp(z_c - mx):
+ *     t_c       = (1-eps) (lam [c == a] + (1-lam) [c == a2]) + eps/C
+ *     loss_b    = log(se) + (1-eps) (lam (mx - z_a) + (1-lam) (mx - z_a2)) + (eps/C) sum_c (mx - z_c)
+ *     d_logit_c = (exp(z_c - mx)/se - t_c) grad_scale / B
+ * = lam CE(z, a) + (1-lam) CE(z, a2), each with label_smoothing = eps as F.cross_entropy defines it.  Every term of the
+ * loss is non-negative and each mx - z is formed before anything is summed (the form of the plain loss), so it stays
+ * accurate with logits near 1e4.  A sample counts iff a is in [0, C) and (lam == 1 or a2 is in [0, C)); otherwise its
+ * loss is 0 and its gradient row is 0 (the padding rule of the plain kernels; -1 pads a short batch).  The mean is over
+ * B, summed in sample order.  With eps = 0, lam = 1 the values are those of the plain entry points. */
+
+/* nnue_classifier_train_step / _bucketed (nnue.py:660-669, :728-734 + compute_loss, train.py:250-254, and their autograd)
+ * on the soft targets above: the same phases, plan, scratch layout, refusals and launches, with the SOFT arm of the
+ * per-sample tail (whichever kernel the plan picks) in place of the plain one; h1, h2 and logits do not depend on the
+ * loss and are bitwise the plain call's.  Two more refusals, both NNUE_E_ARG with nothing launched: eps outside [0, 1),
+ * and labels_b without lam. */
+int nnue_classifier_train_step_soft(const float* x, int pairwise,
+                                    const float* w1, const float* b1, const float* w2, const float* b2,
+                                    const float* w3, const float* b3, float clip,
+                                    const int64_t* labels, float grad_scale,
+                                    int B, int L1, int L2, int L3, int C,
+                                    float* h1, float* h2, float* logits, float* sample_loss, float* loss,
+                                    float* d_x, float* d_w1, float* d_b1, float* d_w2, float* d_b2,
+                                    float* d_w3, float* d_b3,
+                                    void* scratch, int64_t scratch_bytes, int phases,
+                                    const int64_t* labels_b, const float* lam, float eps, nnue_stream_t stream);
+/* the bucketed form of the call above (train.py:250-254, :360-361 on top of nnue.py:728-734 per stack); the grouped mode of
+ * phases bit 16 comes with it. */
+int nnue_classifier_train_step_soft_bucketed(const float* x, int pairwise,
+                                             const float* w1, const float* b1, const float* w2, const float* b2,
+                                             const float* w3, const float* b3, float clip,
+                                             const int64_t* labels, float grad_scale,
+                                             int B, int L1, int L2, int L3, int C,
+                                             float* h1, float* h2, float* logits, float* sample_loss, float* loss,
+                                             float* d_x, float* d_w1, float* d_b1, float* d_w2, float* d_b2,
+                                             float* d_w3, float* d_b3,
+                                             void* scratch, int64_t scratch_bytes, int phases,
+                                             const int64_t* labels_b, const float* lam, float eps,
+                                             const nnue_buckets* buckets, nnue_stream_t stream);
+
 /* The table's weight gradient consumed where it is produced (single rank, SGD): clip_grad_norm_ needs the global norm
  * before any parameter moves (train.py:363-366), and
  *     || A^T D ||_F^2 = sum_{b,b'} (A A^T)_{bb'} (D D^T)_{bb'}      (A = the map [B][direct], D = d_out [B][L1])
@@ -629,6 +674,13 @@ int nnue_ftm_backward_bucketed(const uint8_t* bits, const float* sink, const flo
  * row -- the caller validates labels; the kernel only stays in bounds. */
 int nnue_cross_entropy(const float* logits, const int64_t* labels, int B, int C, float grad_scale,
                        float* sample_loss, float* loss, float* d_logits, nnue_stream_t stream);
+
+/* nnue_cross_entropy (compute_loss, train.py:250-254) on soft targets, as defined under "soft targets" above: labels_b and
+ * lam may both be NULL (a2 = a, lam = 1), eps in [0, 1) is F.cross_entropy's label_smoothing.  sample_loss, loss and
+ * d_logits (may be NULL) as nnue_cross_entropy.  NNUE_E_ARG, nothing launched: eps outside [0, 1), labels_b without lam. */
+int nnue_cross_entropy_soft(const float* logits, const int64_t* labels, const int64_t* labels_b, const float* lam, float eps,
+                            int B, int C, float grad_scale, float* sample_loss, float* loss, float* d_logits,
+                            nnue_stream_t stream);
 
 /* Prediction bookkeeping of compute_metrics / evaluate_model (evaluate.py:23-59, :62-87): adds this batch to
  * confusion[truth*K + pred] (uint64, K = C, or 2 when C == 1).  pred = first arg-max of the row (numpy's
@@ -1047,6 +1099,21 @@ int nnue_load_batch_policy(const uint8_t* images_u8, const int64_t* labels_all, 
                            int B, int H, int W, int64_t N, int Ho, int Wo, int policy, uint64_t seed, uint64_t step,
                            float* out, int64_t* labels_out, float* params_out, nnue_stream_t stream);
 int nnue_load_batch_params_count(void);
+
+/* Batch-level mixing (build extension): one stage behind the per-image transform list (data/datasets.py:301-350) and the
+ * collate (data/loaders.py:95-120), in place on images [B,3,H,W] float32.  Sample i is paired with j = B-1-i; one thread
+ * reads an element of both and writes both; for odd B the middle sample keeps itself.  One draw per batch (host
+ * arguments):
+ *   mode 1, mixup:  x_i' = lam x_i + (1-lam) x_j and x_j' = lam x_j + (1-lam) x_i, both from the original values;
+ *                   lam_out = lam (in [0, 1])
+ *   mode 2, CutMix: inside the box [y0, y0+hh) x [x0, x0+hw) (inside the image; hh or hw may be 0) the two samples swap
+ *                   pixels, a bitwise select; lam_out = (float)(H*W - hh*hw) / (float)(H*W)
+ *   mode 0:         the images are left alone, lam_out = 1
+ * In every mode labels_b_out[i] = labels[B-1-i] and lam_out[i] is the value above: what the soft-target entry points take
+ * beside labels.  labels_b_out must not overlap labels.  NNUE_E_ARG, nothing launched: a null pointer, non-positive sizes,
+ * another mode, lam outside [0, 1] (mode 1), a box that leaves the image (mode 2). */
+int nnue_mix_batch(float* images, const int64_t* labels, int B, int H, int W, int mode, float lam, int y0, int x0, int hh,
+                   int hw, int64_t* labels_b_out, float* lam_out, nnue_stream_t stream);
 
 /* clip_grad_norm_ + torch.optim.Adam(lr, weight_decay) on flat buffers -- the optimizer create_optimizer picks
  * when optimizer_type != "sgd" (train.py:363-366, :465-470; torch defaults betas (0.9, 0.999), eps 1e-8, L2

@@ -9,6 +9,7 @@
 // on plain-VALU "simple" kernels otherwise.  The two narrow layers (L2 -> L3 -> C) are a per-sample
 // tail kernel working out of LDS.  Split-K partials are summed in fixed order: reproducible.
 #include <type_traits>
+#include <tuple>
 #include <cstdlib>
 #include <cstring>
 
@@ -637,6 +638,33 @@ __device__ __forceinline__ float ce_dlogit(float z, float mx, float inv, bool is
   return (expf(z - mx) * inv - (is_y ? 1.0f : 0.0f)) * scale_over_b;
 }
 
+// ---- the SOFT arm of the two tail kernels (soft targets, include/nnue_hip.h): the kernels take a trailing pack that is
+// empty (the plain kernels: the arguments and the code they have always had) or one SoftTargets
+
+// the smoothing term's sum_c (mx - z_c) over the C <= 64 logits of N samples: one more 64-lane butterfly beside those of
+// ce_wave_stats (FAST: the exchanges of ce_wave_stats_fast), lanes >= C add 0
+template <int N, bool FAST>
+__device__ __forceinline__ void ce_wave_csum(const float (&v)[N], bool in, const float (&mx)[N], float (&cs)[N]) {
+#pragma unroll
+  for (int n = 0; n < N; ++n) cs[n] = in ? mx[n] - v[n] : 0.0f;
+  if constexpr (FAST) {
+#define NNUE_SUM_STEP(SH) _Pragma("unroll") for (int n = 0; n < N; ++n) cs[n] += lane_xor<SH>(cs[n]);
+    NNUE_SUM_STEP(32) NNUE_SUM_STEP(16) NNUE_SUM_STEP(8) NNUE_SUM_STEP(4) NNUE_SUM_STEP(2) NNUE_SUM_STEP(1)
+#undef NNUE_SUM_STEP
+  } else {
+#pragma unroll
+    for (int sh = 32; sh >= 1; sh >>= 1)
+#pragma unroll
+      for (int n = 0; n < N; ++n) cs[n] += __shfl_xor(cs[n], sh);
+  }
+}
+
+// d loss / d logit z of a sample that counts, against the soft target t.  The explicit fma is the contraction the compiler
+// picks for ce_dlogit's p - onehot: with t = 1 or 0 the two agree bitwise (left to itself it folds t's own sum into p - t)
+__device__ __forceinline__ float ce_dlogit_soft(float z, float mx, float inv, float t, float scale_over_b) {
+  return fmaf(expf(z - mx), inv, -t) * scale_over_b;
+}
+
 // class slice cp (of S) of d_z2[j] = sum_c d_logits[c] w3[c][j]: four chains over c = cp, cp + S, ...  (w3j = w3 + j)
 template <int S>
 __device__ __forceinline__ float dz2_slice(const float* dl, const float* w3j, int cp, int C, int L3) {
@@ -664,7 +692,7 @@ __device__ __forceinline__ float slice_tree(float (&q)[S]) {
 
 // NT threads per sample: 128 for the usual class counts, 512 when C is large (1000 classes at 224x224: the logits,
 // the softmax and the d_z2 sum are then 4x wider per pass).
-template <int NT, bool VEC>
+template <int NT, bool VEC, typename... Soft>
 __global__ __launch_bounds__(NT) void tail_train_kernel(const float* __restrict__ part, int ksplit,
                                                         const float* __restrict__ b1, const float* __restrict__ w2,
                                                         const float* __restrict__ b2, const float* __restrict__ w3,
@@ -675,7 +703,8 @@ __global__ __launch_bounds__(NT) void tail_train_kernel(const float* __restrict_
                                                         float* __restrict__ sample_loss, float* __restrict__ d_logits,
                                                         float* __restrict__ d_z1, float* __restrict__ d_z2, Buckets bk,
                                                         const float* __restrict__ x, int L1, float* __restrict__ x_g,
-                                                        float* __restrict__ d_z1_g) {
+                                                        float* __restrict__ d_z1_g, Soft... soft) {
+  constexpr bool SOFT = sizeof...(Soft) == 1;
   extern __shared__ float lds[];  // h1 [L2] | h2 [L3] | logits / d_logits [C] | d_z2 [L3] | red [8]
   constexpr int S = NT / 32;      // class slices of the d_z2 sum
   __shared__ float part_s[S][32];
@@ -723,6 +752,13 @@ __global__ __launch_bounds__(NT) void tail_train_kernel(const float* __restrict_
   }
   const float b2v = (VEC && og < L3) ? b2[og] : 0.0f, b3v = (VEC && og < C) ? b3[og] : 0.0f;
   const int64_t y = labels[b];
+  int64_t y2 = y;
+  float lam = 1.0f, eps = 0.0f;
+  if constexpr (SOFT) {
+    const SoftTargets st = (soft, ...);
+    eps = st.eps;
+    if (st.labels_b) y2 = st.labels_b[b], lam = st.lam[b];
+  }
   for (int j = tid; j < L2; j += NT) {
     float z = b1[j];
     int s = 0;
@@ -798,7 +834,7 @@ __global__ __launch_bounds__(NT) void tail_train_kernel(const float* __restrict_
   }
   __syncthreads();
   // softmax cross-entropy of this sample and its gradient
-  float mx = -INFINITY, se = 0.f;
+  float mx = -INFINITY, se = 0.f, csum = 0.f;  // csum (SOFT): sum_c (mx - z_c), the smoothing term
   if (C <= 64) {  // every wave forms the same two reductions by itself: no block barriers
     const int lane = tid & 63;
     const float v[1] = {lane < C ? lgs[lane] : -INFINITY};
@@ -806,18 +842,34 @@ __global__ __launch_bounds__(NT) void tail_train_kernel(const float* __restrict_
     ce_wave_stats<1>(v, lane < C, m1, s1);
     mx = m1[0];
     se = s1[0];
+    if constexpr (SOFT) {
+      float c1[1];
+      ce_wave_csum<1, false>(v, lane < C, m1, c1);
+      csum = c1[0];
+    }
   } else {
     for (int c = tid; c < C; c += NT) mx = fmaxf(mx, lgs[c]);
     mx = block_reduce_nt<NT>(mx, true, red);
     for (int c = tid; c < C; c += NT) se += expf(lgs[c] - mx);
     se = block_reduce_nt<NT>(se, false, red);
+    if constexpr (SOFT) {
+      for (int c = tid; c < C; c += NT) csum += mx - lgs[c];
+      csum = block_reduce_nt<NT>(csum, false, red);
+    }
   }
-  const bool ok = y >= 0 && y < C;
-  if (tid == 0) sample_loss[b] = ok ? nnue_ce_sample_loss(mx, lgs[y], se) : 0.0f;
+  const bool ok = SOFT ? nnue_soft_counts(y, y2, lam, C) : y >= 0 && y < C;
+  if constexpr (SOFT) {
+    if (tid == 0)
+      sample_loss[b] = ok ? nnue_ce_soft_sample_loss(mx, lgs[y], lgs[y2 >= 0 && y2 < C ? y2 : y], se, csum, lam, eps, C) : 0.0f;
+  } else {
+    if (tid == 0) sample_loss[b] = ok ? nnue_ce_sample_loss(mx, lgs[y], se) : 0.0f;
+  }
   const float inv = 1.0f / se;
   __syncthreads();  // every thread has read lgs[y] / the logits it needs before they are overwritten
   for (int c = tid; c < C; c += NT) {
-    const float g = ok ? ce_dlogit(lgs[c], mx, inv, c == y, scale_over_b) : 0.0f;
+    float g;
+    if constexpr (SOFT) g = ok ? ce_dlogit_soft(lgs[c], mx, inv, nnue_soft_target(c == y, c == y2, lam, eps, C), scale_over_b) : 0.0f;
+    else g = ok ? ce_dlogit(lgs[c], mx, inv, c == y, scale_over_b) : 0.0f;
     lgs[c] = g;
     d_logits[(size_t)b * C + c] = g;
   }
@@ -939,14 +991,15 @@ __device__ __forceinline__ f32x4 tail_mma4(const float4& a, float b0, float b1, 
 // DX: the d_x tiles follow the tail (phases 123).  !DX: the tail alone, one workgroup per row tile (n_cg = 1; x, w1 and
 // d_x are not read) -- what every other phase combination runs at these shapes, so that all of them form the tail's
 // values with the same arithmetic.
-template <int L2, int L3, bool DX, bool SKIP = false>
+template <int L2, int L3, bool DX, bool SKIP = false, typename... Soft>
 __global__ __launch_bounds__(kTdxThreads) void tail_dx_train_kernel(
     const float* __restrict__ part, int ksplit, const float* __restrict__ b1, const float* __restrict__ w2,
     const float* __restrict__ b2, const float* __restrict__ w3, const float* __restrict__ b3, float clip,
     const int64_t* __restrict__ labels, float scale_over_b, int B, int C, float* __restrict__ h1, float* __restrict__ h2,
     float* __restrict__ logits, float* __restrict__ sample_loss, float* __restrict__ d_logits, float* __restrict__ d_z1,
     float* __restrict__ d_z2, const float* __restrict__ x, const float* __restrict__ w1, int L1, float* __restrict__ d_x,
-    int m_tiles, int n_cg NNUE_TDX_ABL_PARAM) {
+    int m_tiles, int n_cg NNUE_TDX_ABL_PARAM, Soft... soft) {
+  constexpr bool SOFT = sizeof...(Soft) == 1;
   constexpr int T = kTdxRows, NT = kTdxThreads, NWAVE = NT / 64;
   constexpr int NI = T * L2 / 4 / NT;       // float4 slots of the tile's slab rows per thread
   constexpr int NCH = L2 / (16 * kBwxKC);   // K chunks of the d_x product
@@ -959,7 +1012,7 @@ __global__ __launch_bounds__(kTdxThreads) void tail_dx_train_kernel(
   __shared__ __attribute__((aligned(16))) float dz2s[T][L3 + 4];
   __shared__ float ps[T][4][L3];  // partial h2 sums [row][K quarter][unit], then partial d_z2 sums [row][class half][unit]
   __shared__ __attribute__((aligned(16))) float lgs[T][kTdxMaxC + 4];  // logits, then d_logits
-  __shared__ int64_t ys[T];
+  __shared__ int64_t ys[SOFT ? 3 * T : T];  // SOFT: then the second labels, then lam (its bits)
   __shared__ f32x4 xch[DX ? NWAVE : 1][64];  // d_x accumulators swapped between the two waves of a pair
 
   const int blk = blockIdx.x, slot = blk >> 3;
@@ -997,6 +1050,13 @@ __global__ __launch_bounds__(kTdxThreads) void tail_dx_train_kernel(
   tail_load_frags<L2, L3>(fr, w2, w3, b3, C, wave, r, q);
   const float b2v = b2[tid % L3];
   const int64_t yv = labels[min(row0 + (tid % T), B - 1)];
+  int64_t y2v = yv;
+  float lamv = 1.0f, eps = 0.0f;
+  if constexpr (SOFT) {
+    const SoftTargets st = (soft, ...);
+    eps = st.eps;
+    if (st.labels_b) y2v = st.labels_b[min(row0 + (tid % T), B - 1)], lamv = st.lam[min(row0 + (tid % T), B - 1)];  // uniform
+  }
   int srow[NI], scol[NI];
   float4 z4[NI];
   const float* prow[NI];  // this thread's slab row (a padding row of the last tile reads row B - 1: it feeds no output)
@@ -1033,6 +1093,9 @@ __global__ __launch_bounds__(kTdxThreads) void tail_dx_train_kernel(
     float4 v[NI][16];
     load_batch(0, v);
     if (tid < T) ys[tid] = row0 + tid < B ? yv : -1;
+    if constexpr (SOFT) {
+      if (tid < T) ys[T + tid] = y2v, ys[2 * T + tid] = __float_as_int(lamv);
+    }
     sum_batch(0, v);
   }
   for (int s0 = 16; s0 < ksplit; s0 += 16) {
@@ -1114,16 +1177,29 @@ __global__ __launch_bounds__(kTdxThreads) void tail_dx_train_kernel(
 #pragma unroll
     for (int it = 0; it < RW; ++it) v[it] = in ? lgs[wave + NWAVE * it][lane] : -INFINITY;
     ce_wave_stats_fast<RW>(v, in, mx, se);
+    float cs[RW];  // SOFT: sum_c (mx - z_c), the smoothing term
+    if constexpr (SOFT) ce_wave_csum<RW, true>(v, in, mx, cs);
 #pragma unroll
     for (int it = 0; it < RW; ++it) {
       const int rr = wave + NWAVE * it;
       const int64_t y = ys[rr];
-      const bool ok = y >= 0 && y < C;
+      int64_t y2 = y;
+      float lam = 1.0f;
+      if constexpr (SOFT) y2 = ys[T + rr], lam = __int_as_float((int)ys[2 * T + rr]);
+      const bool ok = SOFT ? nnue_soft_counts(y, y2, lam, C) : y >= 0 && y < C;
       const float zy = ok ? lgs[rr][y] : 0.f;  // read by every lane before any lane overwrites its logit
-      if (writer && lane == 0 && row0 + rr < B) sample_loss[row0 + rr] = ok ? nnue_ce_sample_loss(mx[it], zy, se[it]) : 0.0f;
+      if constexpr (SOFT) {
+        const float zy2 = ok ? lgs[rr][y2 >= 0 && y2 < C ? y2 : y] : 0.f;
+        if (writer && lane == 0 && row0 + rr < B)
+          sample_loss[row0 + rr] = ok ? nnue_ce_soft_sample_loss(mx[it], zy, zy2, se[it], cs[it], lam, eps, C) : 0.0f;
+      } else {
+        if (writer && lane == 0 && row0 + rr < B) sample_loss[row0 + rr] = ok ? nnue_ce_sample_loss(mx[it], zy, se[it]) : 0.0f;
+      }
       const float inv = 1.0f / se[it];
       if (in) {
-        const float g = ok ? ce_dlogit(v[it], mx[it], inv, lane == y, scale_over_b) : 0.0f;
+        float g;
+        if constexpr (SOFT) g = ok ? ce_dlogit_soft(v[it], mx[it], inv, nnue_soft_target(lane == y, lane == y2, lam, eps, C), scale_over_b) : 0.0f;
+        else g = ok ? ce_dlogit(v[it], mx[it], inv, lane == y, scale_over_b) : 0.0f;
         lgs[rr][lane] = g;
         if (writer && row0 + rr < B) d_logits[(size_t)(row0 + rr) * C + lane] = g;
       }
@@ -1248,7 +1324,7 @@ int abl_knob(const char* name) { const char* e = getenv(name); return e ? atoi(e
 // the d_x blocks alone -- what the launch would cost if the small gradients rode elsewhere
 bool abl_skip_small() { static const int v = abl_knob("NNUE_CLS_ABL_SKIP_SMALL"); return v != 0; }
 
-template <bool DX, typename... Args> void launch_tail_dx_kernel(int grid, hipStream_t s, Args... args) {
+template <bool DX, typename... Soft, typename... Args> void launch_tail_dx_kernel(int grid, hipStream_t s, std::tuple<Soft...> soft, Args... args) {
   static const int skip = abl_knob("NNUE_CLS_ABL_SKIP_TAIL_PRODUCTS"), clocks = abl_knob("NNUE_CLS_ABL_TAIL_CLOCKS");
   if (clocks && grid > g_tdx_clock_blocks) {  // eager launches only: this allocates
     if (g_tdx_clocks) (void)hipFree(g_tdx_clocks);
@@ -1257,8 +1333,10 @@ template <bool DX, typename... Args> void launch_tail_dx_kernel(int grid, hipStr
   }
   if (clocks && g_tdx_clocks) (void)hipMemsetAsync(g_tdx_clocks, 0, (size_t)g_tdx_clock_blocks * kTdxClocks * sizeof(long long), s);
   const TdxAbl abl{clocks ? g_tdx_clocks : nullptr};
-  if (skip) hipLaunchKernelGGL((tail_dx_train_kernel<128, 32, DX, true>), dim3(grid), dim3(kTdxThreads), 0, s, args..., abl);
-  else hipLaunchKernelGGL((tail_dx_train_kernel<128, 32, DX, false>), dim3(grid), dim3(kTdxThreads), 0, s, args..., abl);
+  std::apply([&](auto... st) {
+    if (skip) hipLaunchKernelGGL((tail_dx_train_kernel<128, 32, DX, true, Soft...>), dim3(grid), dim3(kTdxThreads), 0, s, args..., abl, st...);
+    else hipLaunchKernelGGL((tail_dx_train_kernel<128, 32, DX, false, Soft...>), dim3(grid), dim3(kTdxThreads), 0, s, args..., abl, st...);
+  }, soft);
 }
 }  // namespace
 
@@ -1273,8 +1351,11 @@ extern "C" int nnue_cls_abl_tail_clocks(long long* out, int max_blocks) {
 #else
 namespace {
 constexpr bool abl_skip_small() { return false; }
-template <bool DX, typename... Args> void launch_tail_dx_kernel(int grid, hipStream_t s, Args... args) {
-  hipLaunchKernelGGL((tail_dx_train_kernel<128, 32, DX, false>), dim3(grid), dim3(kTdxThreads), 0, s, args...);
+// soft: empty (the plain kernel) or one SoftTargets, the kernel's trailing argument
+template <bool DX, typename... Soft, typename... Args> void launch_tail_dx_kernel(int grid, hipStream_t s, std::tuple<Soft...> soft, Args... args) {
+  std::apply([&](auto... st) {
+    hipLaunchKernelGGL((tail_dx_train_kernel<128, 32, DX, false, Soft...>), dim3(grid), dim3(kTdxThreads), 0, s, args..., st...);
+  }, soft);
 }
 }  // namespace
 #endif
@@ -1691,23 +1772,14 @@ extern "C" int nnue_classifier_train_rider(int pairwise, int B, int L1, int L2, 
   return NNUE_OK;
 }
 
-extern "C" int nnue_classifier_train_step(const float* x, int pairwise, const float* w1, const float* b1, const float* w2, const float* b2,
-                                          const float* w3, const float* b3, float clip, const int64_t* labels, float grad_scale, int B,
-                                          int L1, int L2, int L3, int C, float* h1, float* h2, float* logits, float* sample_loss,
-                                          float* loss, float* d_x, float* d_w1, float* d_b1, float* d_w2, float* d_b2, float* d_w3,
-                                          float* d_b3, void* scratch, int64_t scratch_bytes, int phases, nnue_stream_t stream) {
-  return nnue_classifier_train_step_bucketed(x, pairwise, w1, b1, w2, b2, w3, b3, clip, labels, grad_scale, B, L1, L2, L3, C, h1, h2, logits,
-                                             sample_loss, loss, d_x, d_w1, d_b1, d_w2, d_b2, d_w3, d_b3, scratch, scratch_bytes, phases,
-                                             nullptr, stream);
-}
-
-// Checks in the order they have always had, then one arm per field of the plan (train_step_plan)
-extern "C" int nnue_classifier_train_step_bucketed(const float* x, int pairwise, const float* w1, const float* b1, const float* w2,
-                                                   const float* b2, const float* w3, const float* b3, float clip, const int64_t* labels,
-                                                   float grad_scale, int B, int L1, int L2, int L3, int C, float* h1, float* h2,
-                                                   float* logits, float* sample_loss, float* loss, float* d_x, float* d_w1, float* d_b1,
-                                                   float* d_w2, float* d_b2, float* d_w3, float* d_b3, void* scratch,
-                                                   int64_t scratch_bytes, int phases, const nnue_buckets* buckets, nnue_stream_t stream) {
+namespace {
+// The one launcher behind the four entry points.  soft NULL: the plain step.  Checks in the order they have always had, then
+// one arm per field of the plan (train_step_plan)
+int train_step(const float* x, int pairwise, const float* w1, const float* b1, const float* w2, const float* b2, const float* w3,
+               const float* b3, float clip, const int64_t* labels, float grad_scale, int B, int L1, int L2, int L3, int C, float* h1,
+               float* h2, float* logits, float* sample_loss, float* loss, float* d_x, float* d_w1, float* d_b1, float* d_w2, float* d_b2,
+               float* d_w3, float* d_b3, void* scratch, int64_t scratch_bytes, int phases, const nnue_buckets* buckets, nnue_stream_t stream,
+               const SoftTargets* soft) {
   Buckets bk;
   const int rc = buckets_from(buckets, B, &bk, "nnue_classifier_train_step_bucketed");
   if (rc != NNUE_OK) return rc;
@@ -1754,22 +1826,33 @@ extern "C" int nnue_classifier_train_step_bucketed(const float* x, int pairwise,
   // one launch: the small weight/bias gradients (per layer stack), the mean loss and (piggy-backed) the d_w1 slab sum
   const SmallWgrad sw = small_wgrad_args(p, B, L2, L3, C, bk, d_logits, d_z2, d_z1, h1, h2, d_b1, d_w2, d_b2, d_w3, d_b3, sample_loss, loss,
                                          SlabSum{slabs, sp.sum_slabs, dw1_floats(K, L1, L2), d_w1});
-  auto tile_tail = [&](auto with_dx) {
-    launch_tail_dx_kernel<decltype(with_dx)::value>(sp.tdx_grid, s, part, sp.tail_slabs, b1, w2, b2, w3, b3, clip, labels, grad_scale / (float)B,
-                                                    B, C, h1, h2, logits, sample_loss, d_logits, d_z1, d_z2, x, w1, L1, d_x,
+  // st: nothing (the plain kernels) or one SoftTargets (their SOFT arm)
+  auto tile_tail = [&](auto with_dx, auto... st) {
+    launch_tail_dx_kernel<decltype(with_dx)::value>(sp.tdx_grid, s, std::make_tuple(st...), part, sp.tail_slabs, b1, w2, b2, w3, b3, clip, labels,
+                                                    grad_scale / (float)B, B, C, h1, h2, logits, sample_loss, d_logits, d_z1, d_z2, x, w1, L1, d_x,
                                                     row_tiles(B, K), sp.tdx_cg);
   };
-#define NNUE_TAIL(NT, V)                                                                                                                  \
+#define NNUE_TAIL(NT, V, ...)                                                                                                             \
   hipLaunchKernelGGL((tail_train_kernel<NT, V>), dim3(sp.tail_grid), dim3(NT), (size_t)sp.tail_lds, s, part, sp.tail_slabs, b1, w2, b2, w3, b3, \
-                     clip, labels, grad_scale / (float)B, B, L2, L3, C, h1, h2, logits, sample_loss, d_logits, d_z1, d_z2, bk, x, L1, x_g, d_z1_g)
+                     clip, labels, grad_scale / (float)B, B, L2, L3, C, h1, h2, logits, sample_loss, d_logits, d_z1, d_z2, bk, x, L1, x_g,     \
+                     d_z1_g, ##__VA_ARGS__)
 
   // A kernel template's instantiations stand in the code object in the order of their first use here: tail_dx_train_kernel
-  // with, then without d_x tiles, tail_train_kernel<512, .>, <128, .>.  A new arm goes behind them, so that no kernel moves.
-  if (sp.dx == DxLaunch::with_tail) tile_tail(std::true_type{});  // the whole call: nothing below is planned with it
+  // with, then without d_x tiles, tail_train_kernel<512, .>, <128, .>.  A new arm goes behind them, so that no kernel moves:
+  // the SOFT arms follow in the same order.
+  const bool plain = soft == nullptr;
+  if (plain && sp.dx == DxLaunch::with_tail) tile_tail(std::true_type{});  // the whole call: nothing below is planned with it
   if (sp.l1_forward) launch_l1_forward(p, l1, w1, part);
-  if (sp.tail == TailLaunch::tile) tile_tail(std::false_type{});
-  else if (sp.tail == TailLaunch::sample512) { if (sp.tail_vec) NNUE_TAIL(512, true); else NNUE_TAIL(512, false); }
-  else if (sp.tail == TailLaunch::sample128) { if (sp.tail_vec) NNUE_TAIL(128, true); else NNUE_TAIL(128, false); }
+  if (plain) {
+    if (sp.tail == TailLaunch::tile) tile_tail(std::false_type{});
+    else if (sp.tail == TailLaunch::sample512) { if (sp.tail_vec) NNUE_TAIL(512, true); else NNUE_TAIL(512, false); }
+    else if (sp.tail == TailLaunch::sample128) { if (sp.tail_vec) NNUE_TAIL(128, true); else NNUE_TAIL(128, false); }
+  } else {  // the same launches with the kernels' SOFT arm
+    if (sp.dx == DxLaunch::with_tail) tile_tail(std::true_type{}, *soft);
+    else if (sp.tail == TailLaunch::tile) tile_tail(std::false_type{}, *soft);
+    else if (sp.tail == TailLaunch::sample512) { if (sp.tail_vec) NNUE_TAIL(512, true, *soft); else NNUE_TAIL(512, false, *soft); }
+    else if (sp.tail == TailLaunch::sample128) { if (sp.tail_vec) NNUE_TAIL(128, true, *soft); else NNUE_TAIL(128, false, *soft); }
+  }
 #undef NNUE_TAIL
   if (sp.dx == DxLaunch::with_dw1) {
     const int w_blocks = bww_blocks(p, l1);
@@ -1783,4 +1866,49 @@ extern "C" int nnue_classifier_train_step_bucketed(const float* x, int pairwise,
   if (sp.dw1_product) launch_l1_backward_w(p, l1, d_z1, slabs, d_w1);
   if (sp.small_wgrad) hipLaunchKernelGGL(small_wgrad_kernel, dim3(sw.wgrad_blocks + sp.slab_blocks), dim3(256), 0, s, sw);
   return nnue_launch_status("nnue_classifier_train_step");
+}
+}  // namespace
+
+extern "C" int nnue_classifier_train_step(const float* x, int pairwise, const float* w1, const float* b1, const float* w2, const float* b2,
+                                          const float* w3, const float* b3, float clip, const int64_t* labels, float grad_scale, int B,
+                                          int L1, int L2, int L3, int C, float* h1, float* h2, float* logits, float* sample_loss,
+                                          float* loss, float* d_x, float* d_w1, float* d_b1, float* d_w2, float* d_b2, float* d_w3,
+                                          float* d_b3, void* scratch, int64_t scratch_bytes, int phases, nnue_stream_t stream) {
+  return train_step(x, pairwise, w1, b1, w2, b2, w3, b3, clip, labels, grad_scale, B, L1, L2, L3, C, h1, h2, logits, sample_loss, loss, d_x,
+                    d_w1, d_b1, d_w2, d_b2, d_w3, d_b3, scratch, scratch_bytes, phases, nullptr, stream, nullptr);
+}
+
+extern "C" int nnue_classifier_train_step_bucketed(const float* x, int pairwise, const float* w1, const float* b1, const float* w2,
+                                                   const float* b2, const float* w3, const float* b3, float clip, const int64_t* labels,
+                                                   float grad_scale, int B, int L1, int L2, int L3, int C, float* h1, float* h2,
+                                                   float* logits, float* sample_loss, float* loss, float* d_x, float* d_w1, float* d_b1,
+                                                   float* d_w2, float* d_b2, float* d_w3, float* d_b3, void* scratch,
+                                                   int64_t scratch_bytes, int phases, const nnue_buckets* buckets, nnue_stream_t stream) {
+  return train_step(x, pairwise, w1, b1, w2, b2, w3, b3, clip, labels, grad_scale, B, L1, L2, L3, C, h1, h2, logits, sample_loss, loss, d_x,
+                    d_w1, d_b1, d_w2, d_b2, d_w3, d_b3, scratch, scratch_bytes, phases, buckets, stream, nullptr);
+}
+
+extern "C" int nnue_classifier_train_step_soft(const float* x, int pairwise, const float* w1, const float* b1, const float* w2,
+                                               const float* b2, const float* w3, const float* b3, float clip, const int64_t* labels,
+                                               float grad_scale, int B, int L1, int L2, int L3, int C, float* h1, float* h2, float* logits,
+                                               float* sample_loss, float* loss, float* d_x, float* d_w1, float* d_b1, float* d_w2,
+                                               float* d_b2, float* d_w3, float* d_b3, void* scratch, int64_t scratch_bytes, int phases,
+                                               const int64_t* labels_b, const float* lam, float eps, nnue_stream_t stream) {
+  return nnue_classifier_train_step_soft_bucketed(x, pairwise, w1, b1, w2, b2, w3, b3, clip, labels, grad_scale, B, L1, L2, L3, C, h1, h2,
+                                                  logits, sample_loss, loss, d_x, d_w1, d_b1, d_w2, d_b2, d_w3, d_b3, scratch, scratch_bytes,
+                                                  phases, labels_b, lam, eps, nullptr, stream);
+}
+
+extern "C" int nnue_classifier_train_step_soft_bucketed(const float* x, int pairwise, const float* w1, const float* b1, const float* w2,
+                                                        const float* b2, const float* w3, const float* b3, float clip,
+                                                        const int64_t* labels, float grad_scale, int B, int L1, int L2, int L3, int C,
+                                                        float* h1, float* h2, float* logits, float* sample_loss, float* loss, float* d_x,
+                                                        float* d_w1, float* d_b1, float* d_w2, float* d_b2, float* d_w3, float* d_b3,
+                                                        void* scratch, int64_t scratch_bytes, int phases, const int64_t* labels_b,
+                                                        const float* lam, float eps, const nnue_buckets* buckets, nnue_stream_t stream) {
+  NNUE_REQUIRE(eps >= 0.0f && eps < 1.0f, NNUE_E_ARG, "nnue_classifier_train_step_soft: eps = %g is outside [0, 1)", (double)eps);
+  NNUE_REQUIRE(lam || !labels_b, NNUE_E_ARG, "nnue_classifier_train_step_soft: labels_b without lam");
+  const SoftTargets soft{labels_b, labels_b ? lam : nullptr, eps};  // lam without labels_b mixes a label with itself: not read
+  return train_step(x, pairwise, w1, b1, w2, b2, w3, b3, clip, labels, grad_scale, B, L1, L2, L3, C, h1, h2, logits, sample_loss, loss, d_x,
+                    d_w1, d_b1, d_w2, d_b2, d_w3, d_b3, scratch, scratch_bytes, phases, buckets, stream, &soft);
 }

@@ -38,6 +38,24 @@ constexpr int kWave = 64;  // CDNA4 wavefront
 // logits.  Shared by the stand-alone loss (optim_kernels.hip) and the fused classifier step (classifier_kernels.hip).
 __device__ __forceinline__ float nnue_ce_sample_loss(float mx, float z_y, float se) { return (mx - z_y) + logf(se); }
 
+// Soft targets (include/nnue_hip.h, "soft targets"): a second label and a mixing weight per sample (NULL, NULL: a2 = a,
+// lam = 1) and one smoothing constant per call.  Shared by the same two places as the plain loss.
+struct SoftTargets { const int64_t* labels_b; const float* lam; float eps; };
+// a sample counts iff a is a class and (lam == 1 or a2 is one); otherwise its loss and its gradient row are 0
+__device__ __forceinline__ bool nnue_soft_counts(int64_t a, int64_t a2, float lam, int C) {
+  return a >= 0 && a < C && (lam == 1.0f || (a2 >= 0 && a2 < C));
+}
+// The plain form with the target spread over two labels and, by eps / C, over every class: csum = sum_c (mx - z_c).  Every
+// term is non-negative and each mx - z is formed before anything is summed; with eps = 0, lam = 1 the products are exact
+// and the value is nnue_ce_sample_loss(mx, z_a, se).  z_a2 of a sample whose a2 is no class (lam == 1): pass z_a.
+__device__ __forceinline__ float nnue_ce_soft_sample_loss(float mx, float z_a, float z_a2, float se, float csum, float lam, float eps, int C) {
+  return ((1.0f - eps) * (lam * (mx - z_a) + (1.0f - lam) * (mx - z_a2)) + logf(se)) + (eps / (float)C) * csum;
+}
+// t_c of the definition
+__device__ __forceinline__ float nnue_soft_target(bool is_a, bool is_a2, float lam, float eps, int C) {
+  return (1.0f - eps) * (lam * (is_a ? 1.0f : 0.0f) + (1.0f - lam) * (is_a2 ? 1.0f : 0.0f)) + eps / (float)C;
+}
+
 namespace {
 __global__ __launch_bounds__(256) void nnue_zero_floats_kernel(float* __restrict__ dst, size_t count) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;

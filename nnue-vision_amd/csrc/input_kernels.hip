@@ -366,3 +366,83 @@ extern "C" int nnue_load_batch_policy(const uint8_t* images_u8, const int64_t* l
                      labels_all, indices, H, W, N, Ho, Wo, tiles_x, policy, seed, step, out, labels_out, params_out);
   return nnue_launch_status("nnue_load_batch_policy");
 }
+
+// ---------------------------------------------------------------- batch-level mixing (mixup / CutMix; include/nnue_hip.h)
+namespace {
+
+struct MixArgs { int B, H, W, mode; float lam; int y0, x0, hh, hw; };
+
+// grid (chunks of an image, pairs): pair p = samples (p, B-1-p); a thread reads V consecutive elements of both images and
+// writes both -- safe in place.  V = 4: float4 runs (W % 4 == 0: a run stays inside one row).  The pair's labels_b_out and
+// lam_out are written by the first thread of its first workgroup; the middle sample of an odd batch keeps its pixels.
+template <int V>
+__global__ __launch_bounds__(256) void mix_batch_kernel(float* __restrict__ images, const int64_t* __restrict__ labels, MixArgs a,
+                                                        float lam_eff, int64_t* __restrict__ labels_b_out, float* __restrict__ lam_out) {
+  const int i = blockIdx.y, j = a.B - 1 - i;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    const int64_t li = labels[i], lj = labels[j];
+    labels_b_out[i] = lj, labels_b_out[j] = li;
+    lam_out[i] = lam_eff, lam_out[j] = lam_eff;
+  }
+  if (a.mode == 0 || i == j) return;
+  const int hw = a.H * a.W, n = 3 * hw;
+  const int e = ((int)blockIdx.x * 256 + (int)threadIdx.x) * V;
+  if (e >= n) return;
+  float* __restrict__ pi = images + (size_t)i * n + e;
+  float* __restrict__ pj = images + (size_t)j * n + e;
+  float xi[V], xj[V];
+  if constexpr (V == 4) {
+    const float4 vi = *reinterpret_cast<const float4*>(pi), vj = *reinterpret_cast<const float4*>(pj);
+    xi[0] = vi.x, xi[1] = vi.y, xi[2] = vi.z, xi[3] = vi.w;
+    xj[0] = vj.x, xj[1] = vj.y, xj[2] = vj.z, xj[3] = vj.w;
+  } else {
+    xi[0] = *pi, xj[0] = *pj;
+  }
+  float oi[V], oj[V];
+  if (a.mode == 1) {
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+      oi[k] = a.lam * xi[k] + (1.0f - a.lam) * xj[k];
+      oj[k] = a.lam * xj[k] + (1.0f - a.lam) * xi[k];
+    }
+  } else {
+    const int pix = e % hw, y = pix / a.W, x = pix - y * a.W;
+    const bool row_in = y >= a.y0 && y < a.y0 + a.hh;
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+      const bool in = row_in && x + k >= a.x0 && x + k < a.x0 + a.hw;
+      oi[k] = in ? xj[k] : xi[k];
+      oj[k] = in ? xi[k] : xj[k];
+    }
+  }
+  if constexpr (V == 4) {
+    *reinterpret_cast<float4*>(pi) = make_float4(oi[0], oi[1], oi[2], oi[3]);
+    *reinterpret_cast<float4*>(pj) = make_float4(oj[0], oj[1], oj[2], oj[3]);
+  } else {
+    *pi = oi[0], *pj = oj[0];
+  }
+}
+
+}  // namespace
+
+extern "C" int nnue_mix_batch(float* images, const int64_t* labels, int B, int H, int W, int mode, float lam, int y0, int x0, int hh,
+                              int hw, int64_t* labels_b_out, float* lam_out, nnue_stream_t stream) {
+  NNUE_REQUIRE(images && labels && labels_b_out && lam_out, NNUE_E_ARG, "nnue_mix_batch: null pointer");
+  NNUE_REQUIRE(B > 0 && H > 0 && W > 0, NNUE_E_ARG, "nnue_mix_batch: B=%d H=%d W=%d must be positive", B, H, W);
+  NNUE_REQUIRE((long long)H * W < (1ll << 24), NNUE_E_SHAPE, "nnue_mix_batch: image too large");
+  NNUE_REQUIRE(mode >= 0 && mode <= 2, NNUE_E_ARG, "nnue_mix_batch: mode %d is none of 0 (none), 1 (mixup), 2 (CutMix)", mode);
+  NNUE_REQUIRE(mode != 1 || (lam >= 0.0f && lam <= 1.0f), NNUE_E_ARG, "nnue_mix_batch: lam = %g is outside [0, 1]", (double)lam);
+  NNUE_REQUIRE(mode != 2 || (y0 >= 0 && x0 >= 0 && hh >= 0 && hw >= 0 && hh <= H - y0 && hw <= W - x0), NNUE_E_ARG,
+               "nnue_mix_batch: the box [%d, %d+%d) x [%d, %d+%d) leaves the %d x %d image", y0, y0, hh, x0, x0, hw, H, W);
+  NNUE_REQUIRE(B <= 2 * 65535, NNUE_E_SHAPE, "nnue_mix_batch: B=%d exceeds one grid dimension of pairs", B);
+  const float lam_eff = mode == 1 ? lam : mode == 2 ? (float)(H * W - hh * hw) / (float)(H * W) : 1.0f;
+  const MixArgs a{B, H, W, mode, lam, y0, x0, hh, hw};
+  const int n = 3 * H * W, pairs = (B + 1) / 2;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (mode != 0 && W % 4 == 0 && nnue_aligned16(images))
+    hipLaunchKernelGGL(mix_batch_kernel<4>, dim3((n / 4 + 255) / 256, pairs), dim3(256), 0, s, images, labels, a, lam_eff, labels_b_out, lam_out);
+  else
+    hipLaunchKernelGGL(mix_batch_kernel<1>, dim3(mode == 0 ? 1 : (n + 255) / 256, pairs), dim3(256), 0, s, images, labels, a, lam_eff,
+                       labels_b_out, lam_out);
+  return nnue_launch_status("nnue_mix_batch");
+}

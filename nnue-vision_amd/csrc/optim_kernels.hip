@@ -966,3 +966,61 @@ extern "C" int nnue_lr_schedule_step(const float* table, int64_t n, int32_t* pos
   hipLaunchKernelGGL(lr_schedule_step_kernel, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), table, (int)n, position, lr_out);
   return nnue_launch_status("nnue_lr_schedule_step");
 }
+
+// ---------------------------------------------------------------- soft targets (behind everything else: no kernel above moves)
+namespace {
+// cross_entropy_kernel on soft targets (include/nnue_hip.h, "soft targets"): one wave per sample, one more wave sum.
+// GRAD: d_logits is wanted.  (A template also for the code object's sake: instantiations follow every plain kernel and the
+// templates used above, so this one stands last.)
+template <bool GRAD>
+__global__ __launch_bounds__(256) void cross_entropy_soft_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
+                                                                 SoftTargets st, int B, int C, float scale_over_b,
+                                                                 float* __restrict__ sample_loss, float* __restrict__ d_logits) {
+  const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (b >= B) return;
+  const float* __restrict__ z = logits + (size_t)b * C;
+  float mx = -INFINITY;
+  for (int c = lane; c < C; c += 64) mx = fmaxf(mx, z[c]);
+  mx = wave_max(mx);
+  float se = 0.f, csum = 0.f;
+  for (int c = lane; c < C; c += 64) {
+    se += expf(z[c] - mx);
+    csum += mx - z[c];
+  }
+  se = wave_sum(se);
+  csum = wave_sum(csum);
+  const int64_t y = labels[b], y2 = st.labels_b ? st.labels_b[b] : y;
+  const float lam = st.labels_b ? st.lam[b] : 1.0f;
+  const bool ok = nnue_soft_counts(y, y2, lam, C);
+  if (lane == 0)
+    sample_loss[b] = ok ? nnue_ce_soft_sample_loss(mx, z[y], z[y2 >= 0 && y2 < C ? y2 : y], se, csum, lam, st.eps, C) : 0.0f;
+  if constexpr (GRAD) {
+    const float inv = 1.0f / se;
+    for (int c = lane; c < C; c += 64) {
+      // the explicit fma is the contraction the compiler picks for cross_entropy_kernel's p - onehot (t = 1, 0: the same bits)
+      const float g = fmaf(expf(z[c] - mx), inv, -nnue_soft_target(c == y, c == y2, lam, st.eps, C));
+      d_logits[(size_t)b * C + c] = ok ? g * scale_over_b : 0.0f;
+    }
+  }
+}
+}  // namespace
+
+extern "C" int nnue_cross_entropy_soft(const float* logits, const int64_t* labels, const int64_t* labels_b, const float* lam, float eps,
+                                       int B, int C, float grad_scale, float* sample_loss, float* loss, float* d_logits,
+                                       nnue_stream_t stream) {
+  NNUE_REQUIRE(logits && labels && sample_loss && loss, NNUE_E_ARG, "nnue_cross_entropy_soft: null pointer");
+  NNUE_REQUIRE(B > 0 && C > 0, NNUE_E_ARG, "nnue_cross_entropy_soft: B=%d C=%d must be positive", B, C);
+  NNUE_REQUIRE(eps >= 0.0f && eps < 1.0f, NNUE_E_ARG, "nnue_cross_entropy_soft: eps = %g is outside [0, 1)", (double)eps);
+  NNUE_REQUIRE(lam || !labels_b, NNUE_E_ARG, "nnue_cross_entropy_soft: labels_b without lam");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const SoftTargets st{labels_b, labels_b ? lam : nullptr, eps};
+  if (d_logits)
+    hipLaunchKernelGGL(cross_entropy_soft_kernel<true>, dim3((B + 3) / 4), dim3(256), 0, s, logits, labels, st, B, C, grad_scale / (float)B,
+                       sample_loss, d_logits);
+  else
+    hipLaunchKernelGGL(cross_entropy_soft_kernel<false>, dim3((B + 3) / 4), dim3(256), 0, s, logits, labels, st, B, C, grad_scale / (float)B,
+                       sample_loss, d_logits);
+  hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(256), 0, s, sample_loss, B, loss);
+  return nnue_launch_status("nnue_cross_entropy_soft");
+}

@@ -15,14 +15,22 @@ values stay float between stages (include/nnue_hip.h defines every stage).  Omit
 p <= .2): RandomShadow, RandomFog, GridDistortion, ElasticTransform, CLAHE, ColorJitter, Posterize, Equalize.
 ``"heavy"`` (medium plus a second pass of stronger stages) is not built and raises ``ValueError``.
 
+``mixup_alpha`` / ``cutmix_alpha`` (build extensions, both 0 by default) add one batch-level stage behind the per-image list
+and the collate (data/loaders.py:95-120): ``mixed_batch`` is ``batch`` followed by one ``lib.mix_batch`` launch that mixes
+sample i with sample B-1-i in place -- mixup with a weight drawn from Beta(alpha, alpha), or CutMix with the usual box --
+and returns the second labels and the weights a trainer built with ``two_labels`` takes.  The draw is a host function of
+(seed, step), ``mix_draw``: no device read, no synchronisation, and a resumed run mixes as the uninterrupted one does.
+
 Datasets themselves (download / decode) are out of scope: construct ``GpuImageDataset`` from any uint8
 ``[N,H,W,3]`` array and integer labels.
 """
 from __future__ import annotations
 
+import math
 import numbers
 from typing import Iterator, Optional, Tuple
 
+import numpy as np
 import torch
 
 from . import lib
@@ -53,10 +61,36 @@ def resolve_out_hw(out_hw) -> Optional[Tuple[int, int]]:
     return int(hw[0]), int(hw[1])
 
 
+def mix_draw(seed: int, step: int, mixup_alpha: float, cutmix_alpha: float, H: int, W: int):
+    """The batch-level draw of step ``step``: (mode, lam, y0, x0, hh, hw), the host arguments of ``lib.mix_batch``.  mode 0 (both
+    alphas 0): nothing is mixed.  With both alphas positive each of mixup (1) and CutMix (2) has probability 0.5.
+    lam ~ Beta(alpha, alpha) of the chosen mode.  CutMix's box is the usual one -- r = sqrt(1 - lam), sides int(H r) and
+    int(W r), centre uniform over the pixels -- clipped to the image (``mix_batch`` then derives the weight from the clipped
+    area).  A function of (seed, step) alone: numpy's PCG64 seeded with the pair."""
+    if mixup_alpha <= 0 and cutmix_alpha <= 0:
+        return 0, 1.0, 0, 0, 0, 0
+    rng = np.random.Generator(np.random.PCG64([int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1)]))
+    coin = rng.random()  # drawn in every case: the stream does not depend on which alphas are set
+    mode = 1 if cutmix_alpha <= 0 else 2 if mixup_alpha <= 0 else (1 if coin < 0.5 else 2)
+    alpha = mixup_alpha if mode == 1 else cutmix_alpha
+    lam = min(1.0, max(0.0, float(rng.beta(alpha, alpha))))
+    cy, cx = int(rng.integers(0, H)), int(rng.integers(0, W))
+    if mode == 1:
+        return 1, lam, 0, 0, 0, 0
+    r = math.sqrt(1.0 - lam)
+    cut_h, cut_w = int(H * r), int(W * r)
+    y0, y1 = min(max(cy - cut_h // 2, 0), H), min(max(cy + cut_h // 2, 0), H)
+    x0, x1 = min(max(cx - cut_w // 2, 0), W), min(max(cx + cut_w // 2, 0), W)
+    return 2, lam, y0, x0, y1 - y0, x1 - x0
+
+
 class GpuImageDataset:
     def __init__(self, images_u8, labels, device=None, augment=False, seed: int = 0,
-                 num_classes: Optional[int] = None, out_hw=None):
+                 num_classes: Optional[int] = None, out_hw=None, mixup_alpha: float = 0.0, cutmix_alpha: float = 0.0):
         resolve_augment(augment)  # refuse "heavy" and unknown strings here, not at the first batch
+        self.mixup_alpha, self.cutmix_alpha = float(mixup_alpha), float(cutmix_alpha)
+        if not (self.mixup_alpha >= 0.0 and self.cutmix_alpha >= 0.0):
+            raise ValueError(f"mixup_alpha = {mixup_alpha} and cutmix_alpha = {cutmix_alpha} must not be negative")
         self.out_hw = resolve_out_hw(out_hw)
         device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         images_u8 = torch.as_tensor(images_u8)
@@ -100,6 +134,21 @@ class GpuImageDataset:
         return lib.load_batch_policy(self.images, self.labels, indices.to(self.images.device), policy, self.seed, self.step,
                                      out_hw=self.output_hw, out=out, labels_out=labels_out, params_out=params_out)
 
+    @property
+    def mixes(self) -> bool:
+        return self.mixup_alpha > 0.0 or self.cutmix_alpha > 0.0
+
+    def mixed_batch(self, indices: torch.Tensor, out: Optional[torch.Tensor] = None, labels_out: Optional[torch.Tensor] = None,
+                    soft_out=None):
+        """``batch`` followed by one ``lib.mix_batch`` launch on the same stream, with ``mix_draw``'s values for this batch's
+        step.  ``soft_out`` = (labels_b int64 [b], lam float32 [b]) receives the second labels and the weights (a trainer's
+        ``soft_inputs[s]``).  Returns (images, labels, labels_b, lam)."""
+        images, labels = self.batch(indices, out=out, labels_out=labels_out)
+        mode, lam, y0, x0, hh, hw = mix_draw(self.seed, self.step, self.mixup_alpha, self.cutmix_alpha, *self.output_hw)
+        labels_b, lam_out = soft_out if soft_out is not None else (None, None)
+        labels_b, lam_out = lib.mix_batch(images, labels, mode, lam, (y0, x0, hh, hw), labels_b_out=labels_b, lam_out=lam_out)
+        return images, labels, labels_b, lam_out
+
     def loader(self, batch_size: int, shuffle: bool = False, drop_last: bool = False,
                generator: Optional[torch.Generator] = None) -> "GpuLoader":
         return GpuLoader(self, batch_size, shuffle, drop_last, generator)
@@ -137,29 +186,40 @@ def train_epoch(trainer, loader: GpuLoader):
     one input slot, whole rounds of full batches go through ``trainer.step_many``: one pipeline kernel per slot, then ONE
     graph replay for the round's steps (no gap between graph launches).  Returns (sum of per-step mean losses as a
     device scalar, number of steps); the short last batch of an epoch goes through ``trainer.step(images, labels)``
-    (padded, see NnueTrainer.step).
+    (padded, see NnueTrainer.step).  A dataset that mixes (mixup_alpha / cutmix_alpha) is fed through ``mixed_batch``: one more
+    launch per batch, the second labels and the weights into ``trainer.soft_inputs[s]``; the trainer must have been built with
+    ``two_labels=True``.
 
     A side-stream double buffer was measured and is slower here (0.218 vs 0.177 ms per C2 step): the 9 us kernel is
     not worth two event waits per step on a host-launch-bound loop."""
     ds, slots = loader.dataset, len(trainer.inputs)
     if ds.label_range[1] >= trainer.C:
         raise ValueError(f"dataset labels reach {ds.label_range[1]} but the model has {trainer.C} classes")
+    mixes = ds.mixes
+    if mixes and not trainer.two_labels:
+        raise ValueError("the dataset mixes batches (mixup_alpha / cutmix_alpha): build the trainer with two_labels=True")
+
+    def fill(idx, s):  # one batch straight into input slot s
+        if mixes:
+            ds.mixed_batch(idx, out=trainer.inputs[s][0], labels_out=trainer.inputs[s][1], soft_out=trainer.soft_inputs[s])
+        else:
+            ds.batch(idx, out=trainer.inputs[s][0], labels_out=trainer.inputs[s][1])
     total = torch.zeros((), dtype=torch.float32, device=trainer.dev)
     batches = loader.index_batches()
     n, i, round_slots = len(batches), 0, tuple(range(slots))
     while i < n:
         if slots > 1 and i + slots <= n and batches[i + slots - 1].numel() == trainer.B:  # only the last batch can be short
             for s in round_slots:
-                ds.batch(batches[i + s], out=trainer.inputs[s][0], labels_out=trainer.inputs[s][1])
+                fill(batches[i + s], s)
             total += trainer.step_many(round_slots).sum()
             i += slots
             continue
         s, idx = i % slots, batches[i]
         if idx.numel() == trainer.B:
-            ds.batch(idx, out=trainer.inputs[s][0], labels_out=trainer.inputs[s][1])
+            fill(idx, s)
             total += trainer.step(slot=s)
         else:
-            images, labels = ds.batch(idx)
+            images, labels, labels_b, lam = ds.mixed_batch(idx) if mixes else (*ds.batch(idx), None, None)
             count = None
             if trainer.dp.world > 1:
                 # short last batch with ranks: the exact mean needs the number of real samples over ALL ranks (every
@@ -168,7 +228,7 @@ def train_epoch(trainer, loader: GpuLoader):
                 cnt = torch.tensor([int(idx.numel())], dtype=torch.int64, device=trainer.dev if trainer.dp.backend == "nccl" else "cpu")
                 dist.all_reduce(cnt, group=trainer.dp.group)
                 count = int(cnt.item())
-            total += trainer.step(images, labels, slot=s, global_count=count)
+            total += trainer.step(images, labels, slot=s, global_count=count, labels_b=labels_b, lam=lam)
         i += 1
     return total, n
 
@@ -190,5 +250,6 @@ def dataset_from_config(config, images_u8, labels, train: bool, device=None, see
     """A GpuImageDataset set up from a training config the way train.py:278-287 sets up the reference's loaders."""
     augment, out_hw = augment_from_config(config, train)
     num_classes = getattr(config, "num_classes", None)
+    mix = {k: float(getattr(config, k, 0.0)) if train else 0.0 for k in ("mixup_alpha", "cutmix_alpha")}  # the training set only
     return GpuImageDataset(images_u8, labels, device=device, augment=augment, seed=seed,
-                           num_classes=int(num_classes) if num_classes is not None else None, out_hw=out_hw)
+                           num_classes=int(num_classes) if num_classes is not None else None, out_hw=out_hw, **mix)

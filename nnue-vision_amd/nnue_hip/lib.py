@@ -138,6 +138,18 @@ SIGNATURES = {
                                                      _c_p, _c_p, _c_p, _c_p, _c_p,
                                                      _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_int, _c_bk, _c_p]),
     "nnue_cross_entropy": (_c_int, [_c_p, _c_p, _c_int, _c_int, _c_f, _c_p, _c_p, _c_p, _c_p]),
+    "nnue_cross_entropy_soft": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_f, _c_int, _c_int, _c_f, _c_p, _c_p, _c_p, _c_p]),
+    "nnue_classifier_train_step_soft": (_c_int, [_c_p, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_f, _c_p, _c_f,
+                                                 _c_int, _c_int, _c_int, _c_int, _c_int,
+                                                 _c_p, _c_p, _c_p, _c_p, _c_p,
+                                                 _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_int,
+                                                 _c_p, _c_p, _c_f, _c_p]),
+    "nnue_classifier_train_step_soft_bucketed": (_c_int, [_c_p, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_f, _c_p, _c_f,
+                                                          _c_int, _c_int, _c_int, _c_int, _c_int,
+                                                          _c_p, _c_p, _c_p, _c_p, _c_p,
+                                                          _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_int,
+                                                          _c_p, _c_p, _c_f, _c_bk, _c_p]),
+    "nnue_mix_batch": (_c_int, [_c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_f, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p]),
     "nnue_confusion_accumulate": (_c_int, [_c_p, _c_p, _c_int, _c_int, _c_p, _c_p]),
     "nnue_load_batch": (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_i64, _c_int, ctypes.c_uint64, ctypes.c_uint64,
                                  _c_p, _c_p, _c_p]),
@@ -274,7 +286,9 @@ class time_calls:
 
 # entry points timed under the name of the call they replace (a caller's timer keys name the plain forms)
 _TIMED_AS = {"nnue_ftm_conv_binarize_planes": "nnue_ftm_conv_binarize", "nnue_ftm_forward_l1_planes": "nnue_ftm_forward_l1",
-             "nnue_ftm_conv_binarize_value_planes": "nnue_ftm_conv_binarize", "nnue_ftm_backward_planes": "nnue_ftm_backward"}
+             "nnue_ftm_conv_binarize_value_planes": "nnue_ftm_conv_binarize", "nnue_ftm_backward_planes": "nnue_ftm_backward",
+             "nnue_classifier_train_step_soft": "nnue_classifier_train_step",
+             "nnue_classifier_train_step_soft_bucketed": "nnue_classifier_train_step_bucketed"}
 
 
 def _call(name: str, *args) -> None:
@@ -1225,8 +1239,10 @@ CLS_TAIL_IN_DX = 64      # the per-sample tail runs inside the d_x launch (only 
 
 def classifier_train_step(x, pairwise: bool, w1, b1, w2, b2, w3, b3, labels, grad_scale: float = 1.0, clip: float = 0.0,
                           want_dx: bool = True, scratch: Optional[torch.Tensor] = None, out=None, loss_out=None,
-                          grads=None, d_x=None, phases: int = 3, buckets: Optional[BucketPlan] = None):
+                          grads=None, d_x=None, phases: int = 3, buckets: Optional[BucketPlan] = None, soft=None):
     """Forward + mean cross-entropy + backward of the classifier block in one C call.
+    soft = (labels_b int64 [B] or None, lam float32 [B] or None, eps): the soft-target entry points (include/nnue_hip.h,
+    "soft targets") -- a second label and a weight per sample, label smoothing eps; None: the plain ones.
     Returns (h1, h2, logits), (sample_loss, loss), d_x, grads."""
     x = _need(x, torch.float32, "classifier input")
     b, l1 = x.shape
@@ -1247,10 +1263,18 @@ def classifier_train_step(x, pairwise: bool, w1, b1, w2, b2, w3, b3, labels, gra
             b2.data_ptr(), w3.data_ptr(), b3.data_ptr(), float(clip), labels.data_ptr(), float(grad_scale), b, l1, l2, l3, c,
             h1.data_ptr(), h2.data_ptr(), logits.data_ptr(), sample_loss.data_ptr(), loss.data_ptr(),
             _ptr(d_x if want_dx else None), *[g.data_ptr() for g in grads], scratch.data_ptr(), scratch.numel(), int(phases))
+    if soft is not None:
+        labels_b, lam, eps = soft
+        if labels_b is not None:
+            labels_b = _need(labels_b, torch.int64, "labels_b", (b,))
+        if lam is not None:
+            lam = _need(lam, torch.float32, "lam", (b,))
+        args += (_ptr(labels_b), _ptr(lam), float(eps))
     if buckets is None:
-        _call("nnue_classifier_train_step", *args, _stream(x))
+        _call("nnue_classifier_train_step_soft" if soft is not None else "nnue_classifier_train_step", *args, _stream(x))
     else:
-        _call("nnue_classifier_train_step_bucketed", *args, buckets.ref, _stream(x))
+        _call("nnue_classifier_train_step_soft_bucketed" if soft is not None else "nnue_classifier_train_step_bucketed", *args,
+              buckets.ref, _stream(x))
     return (h1, h2, logits), (sample_loss, loss), (d_x if want_dx else None), grads
 
 
@@ -1269,6 +1293,29 @@ def cross_entropy(logits: torch.Tensor, labels: torch.Tensor, grad_scale: float 
         sample_loss, loss, d_logits = out
     _call("nnue_cross_entropy", logits.data_ptr(), labels.data_ptr(), b, c, float(grad_scale), sample_loss.data_ptr(),
           loss.data_ptr(), _ptr(d_logits), _stream(logits))
+    return sample_loss, loss, d_logits
+
+
+def cross_entropy_soft(logits: torch.Tensor, labels: torch.Tensor, labels_b: Optional[torch.Tensor] = None,
+                       lam: Optional[torch.Tensor] = None, eps: float = 0.0, grad_scale: float = 1.0, want_grad: bool = True, out=None):
+    """cross_entropy on soft targets (include/nnue_hip.h, "soft targets"): lam CE(z, labels) + (1 - lam) CE(z, labels_b), each with
+    label_smoothing = eps.  labels_b = lam = None: one label per sample."""
+    logits = _need(logits, torch.float32, "logits")
+    b, c = logits.shape
+    labels = _need(labels, torch.int64, "labels", (b,))
+    if labels_b is not None:
+        labels_b = _need(labels_b, torch.int64, "labels_b", (b,))
+    if lam is not None:
+        lam = _need(lam, torch.float32, "lam", (b,))
+    dev = logits.device
+    if out is None:
+        sample_loss = torch.empty((b,), dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        d_logits = torch.empty((b, c), dtype=torch.float32, device=dev) if want_grad else None
+    else:
+        sample_loss, loss, d_logits = out
+    _call("nnue_cross_entropy_soft", logits.data_ptr(), labels.data_ptr(), _ptr(labels_b), _ptr(lam), float(eps), b, c, float(grad_scale),
+          sample_loss.data_ptr(), loss.data_ptr(), _ptr(d_logits), _stream(logits))
     return sample_loss, loss, d_logits
 
 
@@ -1563,3 +1610,32 @@ def load_batch_policy(images_u8: torch.Tensor, labels_all: torch.Tensor, indices
 
 def load_batch_params_count() -> int:
     return int(load().nnue_load_batch_params_count())
+
+
+MIX_MODES = {"none": 0, "mixup": 1, "cutmix": 2}  # nnue_mix_batch's mode argument
+
+
+def mix_batch(images: torch.Tensor, labels: torch.Tensor, mode: int, lam: float = 1.0, box=(0, 0, 0, 0),
+              labels_b_out: Optional[torch.Tensor] = None, lam_out: Optional[torch.Tensor] = None):
+    """Batch-level mixing IN PLACE on float32 [B,3,H,W]: sample i with B-1-i; mode 0 none / 1 mixup (weight lam) / 2 CutMix (the
+    samples swap the pixels of box = (y0, x0, hh, hw)).  Returns (labels_b [B] = labels reversed, lam [B]): the ``soft`` inputs of
+    classifier_train_step beside ``labels``."""
+    images = _need(images, torch.float32, "images")
+    if images.dim() != 4 or images.shape[1] != 3 or not images.is_contiguous():
+        raise ValueError(f"mix_batch: images must be a contiguous float32 [B,3,H,W] tensor, got {tuple(images.shape)}")
+    b, _, h, w = images.shape
+    labels = _need(labels, torch.int64, "labels", (b,))
+    if labels_b_out is None:
+        labels_b_out = torch.empty((b,), dtype=torch.int64, device=images.device)
+    else:
+        labels_b_out = _need(labels_b_out, torch.int64, "labels_b_out", (b,))
+    if lam_out is None:
+        lam_out = torch.empty((b,), dtype=torch.float32, device=images.device)
+    else:
+        lam_out = _need(lam_out, torch.float32, "lam_out", (b,))
+    if labels_b_out.data_ptr() == labels.data_ptr():
+        raise ValueError("mix_batch: labels_b_out must not be labels (a pair reads both labels and writes both)")
+    y0, x0, hh, hw = (int(v) for v in box)
+    _call("nnue_mix_batch", images.data_ptr(), labels.data_ptr(), b, h, w, int(mode), float(lam), y0, x0, hh, hw,
+          labels_b_out.data_ptr(), lam_out.data_ptr(), _stream(images))
+    return labels_b_out, lam_out

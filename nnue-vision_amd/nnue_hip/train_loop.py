@@ -22,6 +22,11 @@ NNUE model, minus the parts that are out of scope here (W&B, RunPod, dataset dow
   None unless the config sets the new attribute ``lr_schedule``) attaches a per-step schedule to the trainer
   (training_utils.py:283-336, which the reference defines and never calls); each history row then gains ``train/lr``, the
   rate of the epoch's last step.
+* ``label_smoothing``, ``mixup_alpha``, ``cutmix_alpha`` (optional config attributes, all 0 by default; build extensions): the
+  training trainer is built with the smoothing constant, and -- when the training ``GpuLoader``'s dataset mixes
+  (``dataset_from_config`` reads the two alphas) -- with ``two_labels``.  Only the training trainer and the training dataset
+  see them: ``evaluate_model`` on the train, validation and test loaders stays plain cross-entropy on unmixed batches, so the
+  reported losses stay comparable across runs.
 * ``save_last`` / ``resume_from`` (arguments, or the config attributes of those names; off by default): after each epoch's
   evaluations ``last.ckpt`` is written beside ``best-model.ckpt`` -- the five reference keys plus ``"run_state"`` (the
   trainer's state, the epoch and step counts, best-so-far values, the history, the GPU dataset's draw counter and the
@@ -125,8 +130,13 @@ def run_training(config, train_loader: Iterable, val_loader: Iterable, test_load
         opt = dict(optimizer="sgd", momentum=float(config.momentum))
     else:
         opt = dict(optimizer="adam")
+    mixes = in_place and train_loader.dataset.mixes
+    if not mixes and (float(getattr(config, "mixup_alpha", 0.0)) > 0 or float(getattr(config, "cutmix_alpha", 0.0)) > 0):
+        raise ValueError("the config sets mixup_alpha / cutmix_alpha but the train loader does not mix: build its dataset with "
+                         "input_pipeline.dataset_from_config (a GpuLoader)")
     trainer = NnueTrainer(model, batch, hw, lr=float(config.learning_rate), weight_decay=float(config.weight_decay),
-                          max_grad_norm=clip, use_graph=use_graph, input_slots=8 if in_place else 1, **opt)
+                          max_grad_norm=clip, use_graph=use_graph, input_slots=8 if in_place else 1,
+                          label_smoothing=float(getattr(config, "label_smoothing", 0.0)), two_labels=mixes, **opt)
     if lr_schedule is None and getattr(config, "lr_schedule", False):
         lr_schedule = LrSchedule.from_config(config, len(train_loader))
     if isinstance(lr_schedule, LrSchedule):

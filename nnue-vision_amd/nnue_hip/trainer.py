@@ -160,8 +160,15 @@ class NnueTrainer:
     def __init__(self, model, batch_size: int, image_hw: Tuple[int, int], lr: float, momentum: float = 0.0,
                  weight_decay: float = 0.0, max_grad_norm: float = 0.0, group=None, use_graph: bool = True,
                  input_slots: int = 1, optimizer: str = "sgd", betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
-                 ft_path: Optional[str] = None):
-        """ft_path: the FeatureTransformer kernel family, as lib.ft_path's ``mode`` (None: NNUE_FT_PATH decides)."""
+                 ft_path: Optional[str] = None, label_smoothing: float = 0.0, two_labels: bool = False):
+        """ft_path: the FeatureTransformer kernel family, as lib.ft_path's ``mode`` (None: NNUE_FT_PATH decides).
+        label_smoothing (F.cross_entropy's, in [0, 1)) and two_labels (a second label and a weight per sample: mixup, CutMix) make
+        the classifier step train on soft targets (include/nnue_hip.h, "soft targets"); with both at their defaults the step is
+        the plain one, launch for launch."""
+        label_smoothing = float(label_smoothing)
+        if not 0.0 <= label_smoothing < 1.0:
+            raise ValueError(f"label_smoothing = {label_smoothing} must lie in [0, 1)")
+        self._label_smoothing, self.two_labels = label_smoothing, bool(two_labels)
         lib.load()
         p0 = next(model.parameters())
         if not p0.is_cuda:
@@ -225,6 +232,13 @@ class NnueTrainer:
         self.inputs = [(torch.empty((B, 3, self.H, self.W), **f32), torch.empty((B,), dtype=torch.int64, device=self.dev))
                        for _ in range(max(1, input_slots))]
         self.images, self.labels = self.inputs[0]
+        # two_labels: per slot the second labels and the weights of the first ones (-1 / 1: one label per sample)
+        self.soft_inputs = None
+        self.labels_b = self.lam = None
+        if self.two_labels:
+            self.soft_inputs = [(torch.full((B,), -1, dtype=torch.int64, device=self.dev), torch.ones((B,), **f32))
+                                for _ in self.inputs]
+            self.labels_b, self.lam = self.soft_inputs[0]
         self.conv_out = torch.empty((B, self.fps, self.gh, self.gw), **f32)
         # the live map of the step, in the mode's kernel family (``fm`` / ``bits`` / ``act`` name it by family)
         self.feats = lib.FT_FAMILIES[self.mode.ft_path].empty(B, self.P, self.F, self.L1, self.dev)
@@ -342,6 +356,20 @@ class NnueTrainer:
     weight_decay = property(lambda self: self._hyper["weight_decay"], lambda self, v: self._set_hyper("weight_decay", float(v)))
     max_grad_norm = property(lambda self: self._hyper["max_grad_norm"], lambda self, v: self._set_hyper("max_grad_norm", float(v)))
 
+    # Label smoothing is a constant of the recorded LOCAL plan (an argument of the classifier step): changing it re-records that
+    # plan and drops every graph of the local step; the update plans are untouched.
+    def _set_label_smoothing(self, value: float) -> None:
+        value = float(value)
+        if not 0.0 <= value < 1.0:
+            raise ValueError(f"label_smoothing = {value} must lie in [0, 1)")
+        if value == self._label_smoothing:
+            return
+        self._label_smoothing = value
+        self._plan_local = self._plan_seg = None
+        self._g_local.clear()
+
+    label_smoothing = property(lambda self: self._label_smoothing, _set_label_smoothing)
+
     def set_lr(self, lr: float) -> None:
         """Learning rate for the following steps (a scheduler's hook)."""
         self.lr = lr
@@ -408,9 +436,10 @@ class NnueTrainer:
     def _cls_step(self, phases: int) -> None:
         g = self.g
         cls_grads = tuple(g[f"classifier.classifier.{i}.{n}"] for i in (0, 2, 4) for n in ("weight", "bias"))
+        soft = (self.labels_b, self.lam, self._label_smoothing) if (self.two_labels or self._label_smoothing != 0.0) else None
         lib.classifier_train_step(self.ft, True, *self._cls_params(), self.labels, 1.0, self.clip, scratch=self.cls_scratch,
                                   out=(self.h1, self.h2, self.logits), loss_out=(self.sample_loss, self.loss),
-                                  grads=cls_grads, d_x=self.d_ft, phases=phases, buckets=self.bucket_plan)
+                                  grads=cls_grads, d_x=self.d_ft, phases=phases, buckets=self.bucket_plan, soft=soft)
 
     def _rider(self, loss: torch.Tensor):
         """The small-gradient tile family's arguments with `loss` as the mean loss's destination (one host struct per
@@ -630,6 +659,8 @@ class NnueTrainer:
             self._plan_seg = {}
             self._plan_slot = slot
             self.images, self.labels = self.inputs[slot]
+            if self.soft_inputs is not None:
+                self.labels_b, self.lam = self.soft_inputs[slot]
             for name in self.SEGMENTS:
                 with lib.record_calls() as calls:
                     self._segment(name)
@@ -667,6 +698,8 @@ class NnueTrainer:
             return plan
         swap = {self.inputs[src][0].data_ptr(): self.inputs[slot][0].data_ptr(),
                 self.inputs[src][1].data_ptr(): self.inputs[slot][1].data_ptr()}
+        if self.soft_inputs is not None:
+            swap.update({a.data_ptr(): b.data_ptr() for a, b in zip(self.soft_inputs[src], self.soft_inputs[slot])})
         if alt:
             swap.update(self._alt_swap())
         rider_swap = None
@@ -686,7 +719,8 @@ class NnueTrainer:
 
     # ------------------------------------------------------------------ public
     def step(self, images: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None, slot: int = 0,
-             timers=None, global_count: Optional[int] = None) -> torch.Tensor:
+             timers=None, global_count: Optional[int] = None, labels_b: Optional[torch.Tensor] = None,
+             lam: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One optimizer step on this rank's slice.  Returns the local mean loss (device scalar, no sync).
 
         A short batch (fewer than the B images the trainer was built for; possibly none on some ranks) is padded; with
@@ -696,9 +730,15 @@ class NnueTrainer:
         ``images``/``labels`` are copied into input slot ``slot`` first; pass None to train on what the slot
         already holds (zero-copy: fill ``trainer.inputs[slot]`` directly).  With ``timers`` ({C entry point:
         list}) the step runs eagerly from the recorded plan and brackets the named calls with HIP events on the
-        launch stream (bench.py's per-kernel durations)."""
+        launch stream (bench.py's per-kernel durations).
+
+        ``labels_b``/``lam`` (a trainer built with two_labels; both or neither, beside ``images``): the second labels and the
+        weights of the first ones, copied into ``soft_inputs[slot]`` and padded with -1 / 1 the way labels are padded.  Without
+        them a copied batch has one label per sample."""
         buf_images, buf_labels = self.inputs[slot]
         ragged = None
+        if (labels_b is None) != (lam is None) or (labels_b is not None and (images is None or not self.two_labels)):
+            raise ValueError("labels_b and lam come together, beside images, on a trainer built with two_labels=True")
         if images is not None:
             if labels is None or images.shape[1:] != buf_images.shape[1:] or labels.shape[0] != images.shape[0] \
                     or not 0 <= images.shape[0] <= self.B or (images.shape[0] == 0 and self.dp.world == 1):
@@ -718,6 +758,15 @@ class NnueTrainer:
                 buf_images[:n].copy_(images, non_blocking=True)
                 buf_labels.fill_(-1)
                 buf_labels[:n].copy_(labels, non_blocking=True)
+            if labels_b is not None and (labels_b.shape != labels.shape or lam.shape != labels.shape):
+                raise ValueError(f"labels_b {tuple(labels_b.shape)} and lam {tuple(lam.shape)} must have labels' shape {tuple(labels.shape)}")
+            if self.soft_inputs is not None:
+                buf_b, buf_lam = self.soft_inputs[slot]
+                buf_b.fill_(-1)
+                buf_lam.fill_(1.0)
+                if labels_b is not None:
+                    buf_b[:n].copy_(labels_b, non_blocking=True)
+                    buf_lam[:n].copy_(lam, non_blocking=True)
         if ragged is None and global_count is not None and self.dp.world > 1 and int(global_count) != self.B * self.dp.world:
             ragged = self.B * self.dp.world / int(global_count)  # this rank's slot is full but others are short: the same global mean
         _, upd_first, upd = self._plans(slot)
@@ -911,7 +960,8 @@ class NnueTrainer:
         parameters become views of the new trainer's buffers)."""
         torch.cuda.synchronize(self.dev)
         new = NnueTrainer(self.model, self.B, (self.H, self.W), group=self.dp.group, use_graph=self.use_graph, input_slots=len(self.inputs),
-                          optimizer=self.optimizer, betas=self.betas, eps=self.eps, ft_path=ft_path, **self._hyper)
+                          optimizer=self.optimizer, betas=self.betas, eps=self.eps, ft_path=ft_path, label_smoothing=self._label_smoothing,
+                          two_labels=self.two_labels, **self._hyper)
         if self.mode.sharded_update and self.flat_momentum is not None and self.dp.world > 1 and self.steps_done > 0:
             self.dp.all_gather(self.flat_momentum, self.dp.shard_of(self.flat_momentum))
         for src, dst in zip(self._optimizer_buffers(), new._optimizer_buffers()):
@@ -930,7 +980,8 @@ class NnueTrainer:
         if self._lr_values is not None:
             schedule = {"values": self._lr_values.clone(), "position": int(self.lr_position)}
         return {"version": 1, "optimizer_type": self.optimizer, "optimizer": self.optimizer_state_dict(),
-                "steps_done": int(self.steps_done), "lr": float(self._hyper["lr"]), "lr_schedule": schedule}
+                "steps_done": int(self.steps_done), "lr": float(self._hyper["lr"]), "lr_schedule": schedule,
+                "label_smoothing": float(self._label_smoothing)}
 
     def _checked_optimizer_state(self, sd: dict, steps_done: int):
         """The flat-buffer sources of a torch optimizer state dict, {buffer name: {parameter name: tensor}}, after checking
@@ -990,7 +1041,8 @@ class NnueTrainer:
 
     def load_state_dict(self, sd: dict) -> None:
         """state_dict()'s counterpart, on a fresh trainer or on a used one between steps.  Validates first (optimizer type,
-        presence of momentum, every tensor's shape against the layout; ValueError, nothing changed), then copies in place: the
+        presence of momentum, every tensor's shape against the layout, the label smoothing the state was trained with -- a state
+        without the key counts as 0; ValueError, nothing changed), then copies in place: the
         momentum or both moments into the flat buffers, Adam's step into adam_step_count, the rate into lr_dev, the schedule's
         values and position into lr_table / lr_pos / lr_position, and steps_done.  No buffer is re-bound -- recorded plans and
         captured graphs hold raw pointers and stay valid; only a schedule of another length than the attached one (or a
@@ -1011,6 +1063,9 @@ class NnueTrainer:
             if values.dim() != 1 or values.numel() < 1 or not 0 <= position <= 2**31 - 1:
                 raise ValueError("lr_schedule: expected 1-D values of at least one entry and a position in 0 .. 2^31 - 1")
         lr = float(sd["lr"])
+        if float(sd.get("label_smoothing", 0.0)) != self._label_smoothing:  # (a state from before the key existed: 0)
+            raise ValueError(f"the state was trained with label_smoothing = {float(sd.get('label_smoothing', 0.0))}, "
+                             f"this trainer's is {self._label_smoothing}")
         # ---- validated: from here on only in-place copies
         self._apply_optimizer_state(sources, steps_done)
         if schedule is None:
