@@ -326,6 +326,23 @@ def run_plan(plan, stream_ptr: int, timers=None) -> None:
             raise NnueHipError(f"{name} failed (code {rc}): {load().nnue_hip_last_error().decode()}")
 
 
+def retarget_plan(plan, pointers, structs=None):
+    """`plan` with other buffers behind its calls: an integer argument that is a key of `pointers` ({address: address}) becomes
+    the value; a ctypes pointer whose target's address is a key of `structs` ({address: ctypes pointer}) becomes the value;
+    everything else passes through.  The plan itself is never modified, and comes back as it is when nothing was replaced."""
+    if not pointers and not structs:
+        return plan
+
+    def sub(a):
+        if isinstance(a, int):
+            return pointers.get(a, a) if pointers else a
+        if structs and isinstance(a, ctypes._Pointer) and a:
+            return structs.get(ctypes.addressof(a.contents), a)
+        return a
+    out = [(name, fn, tuple(sub(a) for a in args)) for name, fn, args in plan]
+    return plan if out == plan else out  # (ctypes pointers and functions compare by identity)
+
+
 def _stream(t: torch.Tensor) -> int:
     return torch.cuda.current_stream(t.device).cuda_stream
 

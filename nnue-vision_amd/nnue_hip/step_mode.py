@@ -4,6 +4,8 @@
 machine (``print(step_mode.resolve(...).describe())``).  NnueTrainer allocates from the mode and its segments read it;
 tests/trainer_modes.py is the table that holds it still.  The knobs are read from ``os.environ`` here because the library reads
 the same ones from the process environment behind its queries.
+
+``step_form`` (at the end) is the second, per-call decision: which run form one call of ``NnueTrainer.step`` takes.
 """
 from __future__ import annotations
 
@@ -185,3 +187,58 @@ def resolve(*, B: int, H: int, W: int, stride: int, fps: int, F: int, L1: int, L
         sq_range=(tbl_lo, tbl_hi) if sq != "none" else None, sq_count=sq_count, ride_ste=ride_ste, ste_chunks=ste_chunks,
         val_planes=val_planes, fuse_next_forward=fuse_next_forward, ride_small=ride_small, fuse_tail_dx=fuse_tail_dx, phases=phases,
         ste_stages=None if ride_ste else (1 if defer_ste else 3), merged_backward_launch=merged_backward_launch)
+
+
+# ---- The run form of ONE call of NnueTrainer.step.  ``StepMode`` is per trainer and fixed at construction; ``StepForm`` is per
+# call: it depends on whether this is the first step, whether the batch is short, whether timers were passed, and on the trainer's
+# run-time copy of ``capture_collectives`` (a failed capture clears it).  Launch-free like ``resolve``.
+#
+# form name -> the kind of the ``_g_local`` key (slot, kind) of the ONE graph that is the whole step -- local kernels, exchange
+# and update -- or None where the call runs its parts, its exchange and its update one after the other:
+#   graph_dp      local kernels + _exchange_and_update(False), captured together (steady state, captured collectives)
+#   graph         local kernels + the ``upd`` plan, captured together (steady state, no collectives)
+#   local         part "all", then the update tail (no collectives: first step, short batch, timers, no graphs)
+#   own_exchange  part "all", then an eager _exchange_and_update, which updates itself (sharded update, factor exchange)
+#   one_message   part "all", one all-reduce of the whole flat gradient buffer (blocking, or async_op + wait()), the update tail
+#   two_buckets   part "a", async all-reduce of the big bucket, part "b", async all-reduce of the tail bucket, both waited, the
+#                 update tail
+# A part is a replay of graph (slot, part) with graphs, else its recorded segments run eagerly.  The update tail is, in order:
+# short batch -> eager _update with the scaled gradient (the loss is scaled too); first step -> the ``upd_first`` plan; graphs ->
+# a replay of ``_g_update``; else the ``upd`` plan run eagerly.
+FORMS = {"graph_dp": "full_dp", "graph": "full", "local": None, "own_exchange": None, "one_message": None, "two_buckets": None}
+# the kinds of ``_g_local`` key whose graph contains an optimizer update (a change of the update plans drops them): the whole-step
+# graphs above and step_many's group graph (slots, "many")
+UPDATE_GRAPH_KINDS = tuple(kind for kind in FORMS.values() if kind is not None) + ("many",)
+
+
+@dataclass(frozen=True)
+class StepForm:
+    name: str                  # a key of FORMS
+    parts: Tuple[str, ...]     # the local parts the call runs, captured ahead of any collective: ("all",) | ("a", "b")
+    async_op: bool = False     # one_message only: async_op + wait() instead of the blocking collective
+
+    graph = property(lambda self: FORMS[self.name])  # the kind of the whole-step graph the call replays, or None
+
+
+def step_form(*, graphs: bool, first: bool, ragged: bool, collectives: bool, buckets: int, capture_collectives: bool,
+              own_exchange: bool, async_op: bool = False) -> StepForm:
+    """graphs: the trainer uses graphs and the call has no timers; first: no step has been taken; ragged: a short-batch factor
+    applies; collectives, buckets: DataParallel's; capture_collectives: the trainer's run-time copy; own_exchange: the mode's
+    sharded_update or factor_exchange; async_op: NNUE_DP_ASYNC_OP=1 at this call.  The trainer reaches only combinations in which
+    capture_collectives implies collectives, graphs on the trainer and one bucket, and own_exchange implies collectives and one
+    bucket; any other combination gets what the same order of questions gives it -- none is special-cased."""
+    parts = ("a", "b") if collectives and buckets == 2 else ("all",)
+    steady = graphs and not first and not ragged
+    if steady and capture_collectives:
+        name = "graph_dp"
+    elif steady and not collectives:
+        name = "graph"
+    elif not collectives:
+        name = "local"
+    elif own_exchange:
+        name = "own_exchange"
+    elif buckets != 2:
+        name = "one_message"
+    else:
+        name = "two_buckets"
+    return StepForm(name, parts, bool(async_op) and name == "one_message")

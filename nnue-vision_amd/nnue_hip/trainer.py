@@ -32,6 +32,7 @@ from dataclasses import dataclass
 from typing import Dict, List, Optional, Tuple
 
 import os
+import warnings
 
 import torch
 import torch.distributed as dist
@@ -39,6 +40,26 @@ import torch.distributed as dist
 from . import lib, step_mode
 
 SKIP = ("nnue2score",)  # no gradient ever reaches it (reference tests/test_model.py:179-182)
+
+
+def _checked_label_smoothing(value) -> float:
+    value = float(value)
+    if not 0.0 <= value < 1.0:
+        raise ValueError(f"label_smoothing = {value} must lie in [0, 1)")
+    return value
+
+
+def _checked_schedule(values, position) -> Tuple[torch.Tensor, int]:
+    """(values as a float32 CPU vector, position) of a per-step schedule, or ValueError."""
+    values = torch.as_tensor(values).detach().to(device="cpu", dtype=torch.float32).contiguous()
+    if values.dim() != 1 or values.numel() < 1:
+        raise ValueError(f"a schedule is a 1-D sequence of at least one value, got shape {tuple(values.shape)}")
+    if values.numel() > 2**31 - 1:
+        raise ValueError("a schedule has at most 2^31 - 1 values")
+    position = int(position)
+    if not 0 <= position <= 2**31 - 1:
+        raise ValueError(f"schedule position {position} must lie in 0 .. 2^31 - 1")
+    return values, position
 
 
 @dataclass
@@ -165,10 +186,7 @@ class NnueTrainer:
         label_smoothing (F.cross_entropy's, in [0, 1)) and two_labels (a second label and a weight per sample: mixup, CutMix) make
         the classifier step train on soft targets (include/nnue_hip.h, "soft targets"); with both at their defaults the step is
         the plain one, launch for launch."""
-        label_smoothing = float(label_smoothing)
-        if not 0.0 <= label_smoothing < 1.0:
-            raise ValueError(f"label_smoothing = {label_smoothing} must lie in [0, 1)")
-        self._label_smoothing, self.two_labels = label_smoothing, bool(two_labels)
+        self._label_smoothing, self.two_labels = _checked_label_smoothing(label_smoothing), bool(two_labels)
         lib.load()
         p0 = next(model.parameters())
         if not p0.is_cuda:
@@ -336,7 +354,7 @@ class NnueTrainer:
         plan and the graphs of the local step alone stay."""
         self._plan_update_first = self._plan_update = None
         self._g_update = None
-        for key_ in [k for k in self._g_local if k[1] in ("full", "full_dp", "many")]:  # every graph that contains an update
+        for key_ in [k for k in self._g_local if k[1] in step_mode.UPDATE_GRAPH_KINDS]:
             del self._g_local[key_]
 
     def _get_lr(self) -> float:
@@ -359,9 +377,7 @@ class NnueTrainer:
     # Label smoothing is a constant of the recorded LOCAL plan (an argument of the classifier step): changing it re-records that
     # plan and drops every graph of the local step; the update plans are untouched.
     def _set_label_smoothing(self, value: float) -> None:
-        value = float(value)
-        if not 0.0 <= value < 1.0:
-            raise ValueError(f"label_smoothing = {value} must lie in [0, 1)")
+        value = _checked_label_smoothing(value)
         if value == self._label_smoothing:
             return
         self._label_smoothing = value
@@ -382,14 +398,7 @@ class NnueTrainer:
     def set_lr_schedule(self, values, position: int = 0) -> None:
         """Optimizer step number t, counted from position 0, uses ``values[min(t, len - 1)]``; the next step is number
         ``position``."""
-        values = torch.as_tensor(values).detach().to(device="cpu", dtype=torch.float32).contiguous()
-        if values.dim() != 1 or values.numel() < 1:
-            raise ValueError(f"a schedule is a 1-D sequence of at least one value, got shape {tuple(values.shape)}")
-        if values.numel() > 2**31 - 1:
-            raise ValueError("a schedule has at most 2^31 - 1 values")
-        position = int(position)
-        if not 0 <= position <= 2**31 - 1:
-            raise ValueError(f"schedule position {position} must lie in 0 .. 2^31 - 1")
+        values, position = _checked_schedule(values, position)
         self._lr_values = values.clone()
         self.lr_table = values.to(self.dev)
         self.lr_pos = torch.full((1,), position, dtype=torch.int32, device=self.dev)
@@ -423,6 +432,9 @@ class NnueTrainer:
         p = self.p
         return [p[f"classifier.classifier.{i}.{n}"] for i in (0, 2, 4) for n in ("weight", "bias")]
 
+    def _cls_grads(self):
+        return tuple(self.g[f"classifier.classifier.{i}.{n}"] for i in (0, 2, 4) for n in ("weight", "bias"))
+
     # The step is cut into segments so that a captured graph can run the ones nothing waits for beside the
     # critical path (conv -> bits -> FT forward -> classifier activations/d_x -> value gradient -> STE):
     #   front      conv, per-sample bit masks + forward tile lists                       main
@@ -434,22 +446,18 @@ class NnueTrainer:
     SEGMENTS = ("front", "transpose", "forward", "ft_wgrad", "cls_wgrad", "tail")
 
     def _cls_step(self, phases: int) -> None:
-        g = self.g
-        cls_grads = tuple(g[f"classifier.classifier.{i}.{n}"] for i in (0, 2, 4) for n in ("weight", "bias"))
         soft = (self.labels_b, self.lam, self._label_smoothing) if (self.two_labels or self._label_smoothing != 0.0) else None
         lib.classifier_train_step(self.ft, True, *self._cls_params(), self.labels, 1.0, self.clip, scratch=self.cls_scratch,
                                   out=(self.h1, self.h2, self.logits), loss_out=(self.sample_loss, self.loss),
-                                  grads=cls_grads, d_x=self.d_ft, phases=phases, buckets=self.bucket_plan, soft=soft)
+                                  grads=self._cls_grads(), d_x=self.d_ft, phases=phases, buckets=self.bucket_plan, soft=soft)
 
     def _rider(self, loss: torch.Tensor):
         """The small-gradient tile family's arguments with `loss` as the mean loss's destination (one host struct per
         destination: step_many gives every step of a group its own)."""
         key = loss.data_ptr()
         if key not in self._riders:
-            g = self.g
-            grads = tuple(g[f"classifier.classifier.{i}.{n}"] for i in (0, 2, 4) for n in ("weight", "bias"))
             self._riders[key] = lib.classifier_train_rider(True, self.B, self.L1, self.L2, self.L3, self.C, self.h1, self.h2,
-                                                           self.sample_loss, loss, grads, self.cls_scratch, self.bucket_plan)
+                                                           self.sample_loss, loss, self._cls_grads(), self.cls_scratch, self.bucket_plan)
         return self._riders[key]
 
     def _segment(self, name: str) -> None:
@@ -615,6 +623,13 @@ class NnueTrainer:
         dist.all_reduce(flag, op=dist.ReduceOp.MIN, group=self.dp.group)
         return bool(int(flag.item()))
 
+    def _gather_momentum_shards(self) -> None:
+        """Under the sharded update with more than one rank every rank owns only its shard of the momentum: all-gathers the
+        shards into every rank's flat buffer once the stream has finished them.  A COLLECTIVE where the condition holds."""
+        if self.mode.sharded_update and self.flat_momentum is not None and self.dp.world > 1 and self.steps_done > 0:
+            torch.cuda.current_stream(self.dev).synchronize()
+            self.dp.all_gather(self.flat_momentum, self.dp.shard_of(self.flat_momentum))
+
     def _optimizer_buffers(self):
         return [t for t in (self.flat_momentum, self.flat_exp_avg, self.flat_exp_avg_sq, self.adam_step_count) if t is not None]
 
@@ -628,6 +643,27 @@ class NnueTrainer:
                 fn(torch.cuda.current_stream(self.dev))
         torch.cuda.current_stream(self.dev).wait_stream(self._side)
         return graph
+
+    def _capture_agreed(self, key, fn, ring: Optional[torch.Tensor] = None) -> bool:
+        """Captures fn(main_stream), a whole step or step group with its exchange inside, into ``_g_local[key]`` (with `ring`, a
+        group's loss ring: as (graph, ring)) -- on every rank or on none.  A stack that cannot capture its collectives keeps them
+        eager from here on: the key is dropped, ``capture_collectives`` cleared and False returned on ALL ranks.  Without
+        collectives there is nobody to agree with and a failed capture raises."""
+        captured = True
+        try:
+            graph = self._capture(fn)
+            self._g_local[key] = graph if ring is None else (graph, ring)
+        except RuntimeError as exc:
+            if not self.dp.collectives:
+                raise
+            warnings.warn(f"collectives could not be captured into the step graph ({exc}); using the eager collective")
+            captured = False
+            torch.cuda.synchronize(self.dev)
+        if self.dp.collectives and not self._ranks_agree(captured):
+            self._g_local.pop(key, None)
+            self.capture_collectives = False
+            return False
+        return True
 
     def _run_local(self, slot: int, part: str, main: torch.cuda.Stream, timers=None, loss=None, alt: bool = False,
                    forward_done: bool = False) -> None:
@@ -692,30 +728,17 @@ class NnueTrainer:
     def _seg_plan(self, slot: int, name: str, loss: Optional[torch.Tensor] = None, alt: bool = False):
         """The recorded calls of one segment with the recorded slot's input pointers swapped for `slot`'s (and the mean
         loss's destination for `loss`; `alt`: the map's buffers for the second map's)."""
-        plan = self._plan_seg[name]
-        src = self._plan_slot
-        if slot == src and loss is None and not alt:
-            return plan
-        swap = {self.inputs[src][0].data_ptr(): self.inputs[slot][0].data_ptr(),
-                self.inputs[src][1].data_ptr(): self.inputs[slot][1].data_ptr()}
-        if self.soft_inputs is not None:
-            swap.update({a.data_ptr(): b.data_ptr() for a, b in zip(self.soft_inputs[src], self.soft_inputs[slot])})
+        src, swap, riders = self._plan_slot, {}, None
+        if slot != src:
+            held = self.inputs if self.soft_inputs is None else [i + s for i, s in zip(self.inputs, self.soft_inputs)]
+            swap.update({a.data_ptr(): b.data_ptr() for a, b in zip(held[src], held[slot])})
         if alt:
             swap.update(self._alt_swap())
-        rider_swap = None
         if loss is not None:
             swap[self.loss.data_ptr()] = loss.data_ptr()
             if self.mode.ride_small:  # the mean loss's destination sits inside the rider's host struct: use the struct made for `loss`
-                rider_swap = (ctypes.addressof(self._rider(self.loss)), ctypes.pointer(self._rider(loss)))
-
-        def sub(a):
-            if isinstance(a, int):
-                return swap.get(a, a)
-            if rider_swap is not None and hasattr(a, "contents") and isinstance(a.contents, lib.NnueClsRider) \
-                    and ctypes.addressof(a.contents) == rider_swap[0]:
-                return rider_swap[1]
-            return a
-        return [(nm, fn, tuple(sub(a) for a in args)) for nm, fn, args in plan]
+                riders = {ctypes.addressof(self._rider(self.loss)): ctypes.pointer(self._rider(loss))}
+        return lib.retarget_plan(self._plan_seg[name], swap, riders)
 
     # ------------------------------------------------------------------ public
     def step(self, images: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None, slot: int = 0,
@@ -735,6 +758,82 @@ class NnueTrainer:
         ``labels_b``/``lam`` (a trainer built with two_labels; both or neither, beside ``images``): the second labels and the
         weights of the first ones, copied into ``soft_inputs[slot]`` and padded with -1 / 1 the way labels are padded.  Without
         them a copied batch has one label per sample."""
+        ragged = self._stage(slot, images, labels, labels_b, lam, global_count)
+        _, upd_first, upd = self._plans(slot)
+        self._last_alt = False
+        first, graphs = self.steps_done == 0, self.use_graph and timers is None
+        main = torch.cuda.current_stream(self.dev)
+        scale = self.dp.grad_scale * ragged if ragged is not None else None  # (None: the plans' own, dp.grad_scale)
+
+        def form_now():  # (asked again after a capture that the ranks agreed to do without)
+            return step_mode.step_form(graphs=graphs, first=first, ragged=ragged is not None, collectives=self.dp.collectives,
+                                       buckets=self.dp.buckets, capture_collectives=self.capture_collectives,
+                                       own_exchange=self.mode.sharded_update or self.mode.factor_exchange,
+                                       async_op=os.environ.get("NNUE_DP_ASYNC_OP") == "1")
+        form = form_now()
+        if graphs:  # capture everything this step replays before any collective is enqueued
+            for part in form.parts:
+                if (slot, part) not in self._g_local:
+                    self._g_local[(slot, part)] = self._capture(lambda st, part=part: self._run_local(slot, part, st))
+            if self._g_update is None and upd:
+                self._g_update = self._capture(lambda st: lib.run_plan(upd, st.cuda_stream))
+        if form.graph is not None and (slot, form.graph) not in self._g_local:
+            def whole_step(st, with_exchange=form.name == "graph_dp"):
+                self._run_local(slot, "all", st)
+                if with_exchange:
+                    self._exchange_and_update(False)
+                else:
+                    lib.run_plan(upd, st.cuda_stream)
+            if not self._capture_agreed((slot, form.graph), whole_step):
+                form = form_now()
+
+        def run(part):
+            if graphs:
+                self._g_local[(slot, part)].replay()
+            else:
+                self._run_local(slot, part, main, timers=timers)
+
+        if form.graph is not None:  # steady state: ONE graph, one replay per step
+            self._g_local[(slot, form.graph)].replay()
+        elif form.name == "own_exchange":
+            run("all")
+            with lib.time_calls(timers):
+                self._exchange_and_update(first, grad_scale=scale)
+        else:
+            if form.name == "two_buckets":
+                # big bucket is complete after part a: its all-reduce runs on the collective's own stream while part b
+                # (STE/conv backward) still computes; the tail bucket follows part b
+                run("a")
+                big = self.dp.allreduce_sum(self.flat_grads[self.bucket_split:], async_op=True)
+                run("b")
+                small = self.dp.allreduce_sum(self.flat_grads[:self.bucket_split], async_op=True)
+                big.wait()
+                small.wait()
+            else:
+                run("all")
+            if form.name == "one_message":
+                # one message: the whole flat gradient buffer, after the local graph; the wait is a stream dependency.
+                # A blocking (for the stream, not the host) collective: measured 25 us/step cheaper than async_op + wait()
+                # in the 1-rank RCCL rehearsal (0.1395 vs 0.1643 ms); NNUE_DP_ASYNC_OP=1 restores the latter
+                work = self.dp.allreduce_sum(self.flat_grads, async_op=form.async_op)
+                if form.async_op:
+                    work.wait()
+            # the update tail of "local", "one_message" and "two_buckets"
+            if ragged is not None:
+                self._update(first, grad_scale=scale)
+            elif first:
+                lib.run_plan(upd_first, main.cuda_stream, timers)
+            elif graphs:
+                self._g_update.replay()
+            else:
+                lib.run_plan(upd, main.cuda_stream, timers)
+        self._advance(1)
+        # a short batch's kernels divided by B: the mean over the real samples (a whole-step graph never runs one)
+        return self.loss * ragged if ragged is not None else self.loss
+
+    def _stage(self, slot: int, images, labels, labels_b, lam, global_count) -> Optional[float]:
+        """Checks step()'s inputs and copies them into input slot `slot`, a short batch padded.  Returns the factor that restores
+        the exact mean over the real samples where the kernels divide by B (gradients and loss are scaled by it), else None."""
         buf_images, buf_labels = self.inputs[slot]
         ragged = None
         if (labels_b is None) != (lam is None) or (labels_b is not None and (images is None or not self.two_labels)):
@@ -769,98 +868,7 @@ class NnueTrainer:
                     buf_lam[:n].copy_(lam, non_blocking=True)
         if ragged is None and global_count is not None and self.dp.world > 1 and int(global_count) != self.B * self.dp.world:
             ragged = self.B * self.dp.world / int(global_count)  # this rank's slot is full but others are short: the same global mean
-        _, upd_first, upd = self._plans(slot)
-        self._last_alt = False
-        first = self.steps_done == 0
-        stream = torch.cuda.current_stream(self.dev).cuda_stream
-        graphs = self.use_graph and timers is None
-
-        two_buckets = self.dp.collectives and self.dp.buckets == 2
-        parts = ("a", "b") if two_buckets else ("all",)
-        main = torch.cuda.current_stream(self.dev)
-        if graphs:  # capture everything this step replays before any collective is enqueued
-            for part in parts:
-                if (slot, part) not in self._g_local:
-                    self._g_local[(slot, part)] = self._capture(
-                        lambda st, part=part: self._run_local(slot, part, st))
-            if self._g_update is None and upd:
-                self._g_update = self._capture(lambda st: lib.run_plan(upd, st.cuda_stream))
-
-        def run(part):
-            if graphs:
-                self._g_local[(slot, part)].replay()
-            else:
-                self._run_local(slot, part, main, timers=timers)
-
-        if graphs and self.capture_collectives and not first and ragged is None:
-            # data parallel, steady state: local kernels + exchange + update are ONE graph
-            if (slot, "full_dp") not in self._g_local:
-                def full_dp(st):
-                    self._run_local(slot, "all", st)
-                    self._exchange_and_update(False)
-                captured = True
-                try:
-                    self._g_local[(slot, "full_dp")] = self._capture(full_dp)
-                except RuntimeError as exc:  # a stack that cannot capture its collectives: keep them eager from here on
-                    import warnings
-                    warnings.warn(f"collectives could not be captured into the step graph ({exc}); using the eager collective")
-                    captured = False
-                    torch.cuda.synchronize(self.dev)
-                if not self._ranks_agree(captured):  # all ranks or none
-                    self._g_local.pop((slot, "full_dp"), None)
-                    self.capture_collectives = False
-            if self.capture_collectives:
-                self._g_local[(slot, "full_dp")].replay()
-                self._advance(1)
-                return self.loss
-        if graphs and not self.dp.collectives and not first and ragged is None:
-            # single rank, steady state: local step + update are ONE graph (one replay per step)
-            if (slot, "full") not in self._g_local:
-                def full(st):
-                    self._run_local(slot, "all", st)
-                    lib.run_plan(upd, st.cuda_stream)
-                self._g_local[(slot, "full")] = self._capture(full)
-            self._g_local[(slot, "full")].replay()
-            self._advance(1)
-            return self.loss
-        if not self.dp.collectives:
-            run("all")
-        elif self.mode.sharded_update or self.mode.factor_exchange:
-            run("all")
-            with lib.time_calls(timers):
-                self._exchange_and_update(first, grad_scale=self.dp.grad_scale * ragged if ragged is not None else None)
-            self._advance(1)
-            return self.loss * ragged if ragged is not None else self.loss
-        elif not two_buckets:
-            # one message: the whole flat gradient buffer, after the local graph; the wait is a stream dependency
-            run("all")
-            # a blocking (for the stream, not the host) collective: measured 25 us/step cheaper than async_op + wait()
-            # in the 1-rank RCCL rehearsal (0.1395 vs 0.1643 ms); NNUE_DP_ASYNC_OP=1 restores the latter
-            if os.environ.get("NNUE_DP_ASYNC_OP") == "1":
-                self.dp.allreduce_sum(self.flat_grads, async_op=True).wait()
-            else:
-                self.dp.allreduce_sum(self.flat_grads, async_op=False)
-        else:
-            # big bucket is complete after part a: its all-reduce runs on the collective's own stream while part b
-            # (STE/conv backward) still computes; the tail bucket follows part b
-            run("a")
-            big = self.dp.allreduce_sum(self.flat_grads[self.bucket_split:], async_op=True)
-            run("b")
-            small = self.dp.allreduce_sum(self.flat_grads[:self.bucket_split], async_op=True)
-            big.wait()
-            small.wait()
-        if ragged is not None:
-            self._update(first, grad_scale=self.dp.grad_scale * ragged)
-            self._advance(1)
-            return self.loss * ragged
-        if first:
-            lib.run_plan(upd_first, stream, timers)
-        elif graphs:
-            self._g_update.replay()
-        else:
-            lib.run_plan(upd, stream, timers)
-        self._advance(1)
-        return self.loss
+        return ragged
 
     def _run_many(self, st: torch.cuda.Stream, slots, ring: torch.Tensor, upd, timers=None) -> None:
         """The launches of ``len(slots)`` consecutive steps on stream `st` (the current stream): what step_many captures, and
@@ -880,12 +888,8 @@ class NnueTrainer:
                     self._small_update(False, self.dp.grad_scale)
                     self._next_map(slots[i + 1], nxt)
                     self._table_update(False, self.dp.grad_scale, self.d_ft, cur, nxt)
-            elif alt:
-                swap = self._alt_swap()
-                lib.run_plan([(nm, fn, tuple(swap.get(a, a) if isinstance(a, int) else a for a in args)) for nm, fn, args in upd],
-                             st.cuda_stream, timers)
             else:
-                lib.run_plan(upd, st.cuda_stream, timers)
+                lib.run_plan(lib.retarget_plan(upd, self._alt_swap() if alt else None), st.cuda_stream, timers)
 
     def _group_fuses(self, slots) -> bool:
         """In a group on `slots` the table update of every step but the last also forms the next step's forward."""
@@ -914,41 +918,26 @@ class NnueTrainer:
         slots = tuple(int(s) for s in slots)
         if not slots or min(slots) < 0 or max(slots) >= len(self.inputs):
             raise ValueError(f"slots must name input slots 0..{len(self.inputs) - 1}")
-        if timers is not None and self.steps_done > 0 and self._plan_local is not None:
+        recorded = self.steps_done > 0 and self._plan_local is not None
+        one_graph = self.use_graph and recorded and (not self.dp.collectives or self.capture_collectives)
+        if timers is not None and recorded:
             # (with ranks: the collectives are issued eagerly, in the same order on every rank)
             _, _, upd = self._plans(slots[0])
             ring = self._ring(len(slots))
             self._run_many(torch.cuda.current_stream(self.dev), slots, ring, upd, timers)
-            self._last_alt = self._ends_on_alt(slots)
-            self._advance(len(slots))
-            return ring[:len(slots)]
-        one_graph = (self.use_graph and self.steps_done > 0 and self._plan_local is not None
-                     and (not self.dp.collectives or self.capture_collectives))
-        if one_graph and (slots, "many") not in self._g_local:
-            _, _, upd = self._plans(slots[0])
-            ring = self._ring(len(slots))
-            captured = True
-            try:
-                self._g_local[(slots, "many")] = (self._capture(lambda st: self._run_many(st, slots, ring, upd)), ring)
-            except RuntimeError as exc:
-                if not self.dp.collectives:
-                    raise
-                import warnings
-                warnings.warn(f"collectives could not be captured into the step graph ({exc}); using the eager collective")
-                captured = False
-                torch.cuda.synchronize(self.dev)
-            if self.dp.collectives and not self._ranks_agree(captured):  # all ranks or none
-                self._g_local.pop((slots, "many"), None)
-                self.capture_collectives = False
-                one_graph = False
-        if not one_graph:
-            ring = self._ring(len(slots))
-            for i, s in enumerate(slots):
-                ring[i].copy_(self.step(slot=s), non_blocking=True)
-            return ring[:len(slots)]
-        graph, ring = self._g_local[(slots, "many")]
-        graph.replay()
-        self._last_alt = self._ends_on_alt(slots)
+        else:
+            if one_graph and (slots, "many") not in self._g_local:
+                _, _, upd = self._plans(slots[0])
+                ring = self._ring(len(slots))
+                one_graph = self._capture_agreed((slots, "many"), lambda st: self._run_many(st, slots, ring, upd), ring)
+            if not one_graph:  # single steps: they advance the counters themselves
+                ring = self._ring(len(slots))
+                for i, s in enumerate(slots):
+                    ring[i].copy_(self.step(slot=s), non_blocking=True)
+                return ring[:len(slots)]
+            graph, ring = self._g_local[(slots, "many")]
+            graph.replay()
+        self._last_alt = self._ends_on_alt(slots)  # (the maps alternate within a fused group)
         self._advance(len(slots))
         return ring[:len(slots)]
 
@@ -962,8 +951,7 @@ class NnueTrainer:
         new = NnueTrainer(self.model, self.B, (self.H, self.W), group=self.dp.group, use_graph=self.use_graph, input_slots=len(self.inputs),
                           optimizer=self.optimizer, betas=self.betas, eps=self.eps, ft_path=ft_path, label_smoothing=self._label_smoothing,
                           two_labels=self.two_labels, **self._hyper)
-        if self.mode.sharded_update and self.flat_momentum is not None and self.dp.world > 1 and self.steps_done > 0:
-            self.dp.all_gather(self.flat_momentum, self.dp.shard_of(self.flat_momentum))
+        self._gather_momentum_shards()
         for src, dst in zip(self._optimizer_buffers(), new._optimizer_buffers()):
             dst.copy_(src)
         new.steps_done = self.steps_done
@@ -1058,10 +1046,7 @@ class NnueTrainer:
         sources = self._checked_optimizer_state(sd["optimizer"], steps_done)
         schedule = sd.get("lr_schedule")
         if schedule is not None:
-            values = torch.as_tensor(schedule["values"]).detach().to(device="cpu", dtype=torch.float32)
-            position = int(schedule["position"])
-            if values.dim() != 1 or values.numel() < 1 or not 0 <= position <= 2**31 - 1:
-                raise ValueError("lr_schedule: expected 1-D values of at least one entry and a position in 0 .. 2^31 - 1")
+            values, position = _checked_schedule(schedule["values"], schedule["position"])
         lr = float(sd["lr"])
         if float(sd.get("label_smoothing", 0.0)) != self._label_smoothing:  # (a state from before the key existed: 0)
             raise ValueError(f"the state was trained with label_smoothing = {float(sd.get('label_smoothing', 0.0))}, "
@@ -1088,9 +1073,7 @@ class NnueTrainer:
         With the sharded update (more than one rank, bandwidth-sized buffers) every rank owns only its shard of the
         momentum, so this call first all-gathers the shards: it is then a COLLECTIVE and every rank must make it (the
         train loop does: all ranks reach the same best-F1 decision)."""
-        if self.mode.sharded_update and self.flat_momentum is not None and self.dp.world > 1 and self.steps_done > 0:
-            torch.cuda.current_stream(self.dev).synchronize()
-            self.dp.all_gather(self.flat_momentum, self.dp.shard_of(self.flat_momentum))
+        self._gather_momentum_shards()
         params = list(self.model.parameters())
         if self.optimizer == "adam":
             opt = torch.optim.Adam(params, lr=self.lr, betas=self.betas, eps=self.eps, weight_decay=self.weight_decay)
