@@ -1147,7 +1147,7 @@ int nnue_adam_step_ext(float* params, float* grads, float* exp_avg, float* exp_a
  *   c = min(1, max_norm/(norm+1e-6)) if max_norm > 0 else 1 ; g <- c*g + wd*p ; m <- first ? g : momentum*m + g ; p <- p - lr*m
  * momentum[i] == 0: momentum_bufs may be NULL or hold NULL there, and nothing is written to it.
  * The arrays are HOST arrays (pointers to device memory, counts and hyperparameters); the call packs them into kernel-argument
- * tables of 50 segments, so a step has no host-to-device copy and launches 2 kernels per 50 segments (1 without a norm).
+ * tables of 45 segments, so a step has no host-to-device copy and launches 2 kernels per 45 segments (1 without a norm).
  * Any sizes, any 4-byte-aligned views: 16-byte accesses where the segment's pointers share their offset within 16 bytes.
  * The norm is summed in fixed-size chunks in list order and re-derived in double: two runs give the same bits whatever the
  * pointers.  scratch >= nnue_multi_optim_scratch(counts, n) bytes (0 on invalid arguments).  norm_out (device float, may be
@@ -1167,6 +1167,96 @@ int nnue_multi_adam_step(float* const* params, float* const* grads, float* const
                          int32_t* const* step_counters, const int64_t* counts, int n, const float* lr, const float* beta1,
                          const float* beta2, const float* eps, const float* weight_decay, float max_norm, float* norm_out,
                          void* scratch, int64_t scratch_bytes, const float* lr_dev, nnue_stream_t stream);
+
+/* ---- weight clip (build extension: the export range held during training) ----------------------------------------------
+ * The reference's export (serialize.py:508-510 -> NNUE.get_quantized_model_data -> NNUE._clip_weights, nnue.py:528-539) clamps
+ * input.weight and the classifier's Linear weights to [-1, 1] before it quantises them; the trainers this model family descends
+ * from call _clip_weights after every optimizer step (the reference's loop, train.py:366, lost the call).  The entry points below
+ * are the optimizer entry points above with that clamp inside the launch that applies the update.  With bound c = weight_clip,
+ * every element w of a clipped tensor that the update leaves becomes
+ *     w > c ? c : (w < -c ? -c : w)
+ * -- torch.clamp_(-c, c) bit for bit: a NaN stays a NaN, -0.0 stays -0.0 -- before it is stored, and, in the fused update +
+ * next-forward pass, before it becomes the operand of the next step's forward.  Momentum and both Adam moments are formed from
+ * the un-clamped arithmetic and are never clamped; nothing else of a step reads the clamped value.  A step with the clamp is
+ * therefore, bit for bit, the plain step followed by clamp_ on the clipped tensors.
+ * weight_clip = 0 is "off": the call then launches exactly what the entry point without the suffix launches (both are one
+ * implementation).  A bound that is negative, infinite or NaN is refused with NNUE_E_ARG.  No entry point here takes more
+ * scratch or adds a launch.
+ * Flat buffers (nnue_sgd_step_clip, nnue_adam_step_clip, nnue_adam_step_ext_clip) name the clipped elements by clip_ranges: a
+ * HOST array of n_clip_ranges <= 4 pairs (lo, hi), half-open element ranges inside [0, count]; elements outside every range are
+ * not clamped.  A range applies to what the call itself updates: with ext_applied_elsewhere the rows left to the producer are
+ * clamped by the producer's own _clip entry point.  The 16-byte kernel is taken only where every boundary is a multiple of 4.
+ * The table forms take the bound alone (every element they update belongs to input.weight); the multi-tensor forms take one
+ * bound per segment (weight_clip[i], a HOST array like lr[]; NULL or 0: that segment is not clamped). */
+
+/* nnue_sgd_step with the weight clip above (_clip_weights, nnue.py:528-539, after optimizer.step(), train.py:366). */
+int nnue_sgd_step_clip(float* params, float* grads, float* momentum_buf, int64_t count, float lr, float momentum,
+                       float weight_decay, float max_norm, float grad_scale, int first_step, float* norm_out, void* scratch,
+                       int64_t scratch_bytes, const float* ste_partial, int ste_chunks, int ste_fps, float* ste_d_thr,
+                       float* ste_d_weight, const float* ext_partial, int ext_count, int64_t ext_lo, int64_t ext_hi, float* coef_out,
+                       int ext_applied_elsewhere, const float* lr_dev, float weight_clip, const int64_t* clip_ranges,
+                       int n_clip_ranges, nnue_stream_t stream);
+
+/* nnue_adam_step with the weight clip above (_clip_weights, nnue.py:528-539, after optimizer.step(), train.py:366). */
+int nnue_adam_step_clip(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int32_t* step_counter, int64_t count,
+                        float lr, float beta1, float beta2, float eps, float weight_decay, float max_norm, float grad_scale,
+                        float* norm_out, void* scratch, int64_t scratch_bytes, const float* lr_dev, float weight_clip,
+                        const int64_t* clip_ranges, int n_clip_ranges, nnue_stream_t stream);
+
+/* nnue_adam_step_ext with the weight clip above (_clip_weights, nnue.py:528-539, after optimizer.step(), train.py:366). */
+int nnue_adam_step_ext_clip(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int32_t* step_counter, int64_t count,
+                            float lr, float beta1, float beta2, float eps, float weight_decay, float max_norm, float grad_scale,
+                            float* norm_out, void* scratch, int64_t scratch_bytes, const float* ext_partial, int ext_count,
+                            int64_t ext_lo, int64_t ext_hi, float* coef_out, int ext_applied_elsewhere, const float* lr_dev,
+                            float weight_clip, const int64_t* clip_ranges, int n_clip_ranges, nnue_stream_t stream);
+
+/* nnue_ftm_backward_weight_update with the weight clip above on the table rows it updates (_clip_weights, nnue.py:528-539,
+ * after optimizer.step(), train.py:366). */
+int nnue_ftm_backward_weight_update_clip(const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight,
+                                         float* momentum_rows, const float* coef, float lr, float momentum, float weight_decay,
+                                         float grad_scale, int first_step, float weight_clip, const float* lr_dev,
+                                         nnue_stream_t stream);
+
+/* nnue_ftm_backward_weight_update_forward with the weight clip above (_clip_weights, nnue.py:528-539, after optimizer.step(),
+ * train.py:366): the next step's forward contracts the clamped tiles, the ones the pass stores. */
+int nnue_ftm_backward_weight_update_forward_clip(const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight,
+                                                 float* momentum_rows, const float* coef, float lr, float momentum,
+                                                 float weight_decay, float grad_scale, int first_step, float weight_clip,
+                                                 const float* lr_dev, const uint8_t* bits_next, const float* sink_next, int B_next,
+                                                 const float* bias, float* out_next, void* scratch, int64_t scratch_bytes,
+                                                 nnue_stream_t stream);
+
+/* nnue_ftm_backward_weight_update_adam with the weight clip above on the table rows it updates (_clip_weights,
+ * nnue.py:528-539, after optimizer.step(), train.py:366). */
+int nnue_ftm_backward_weight_update_adam_clip(const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight,
+                                              float* exp_avg_rows, float* exp_avg_sq_rows, const float* coef,
+                                              const int32_t* step_counter, float lr, float beta1, float beta2, float eps,
+                                              float weight_decay, float grad_scale, float weight_clip, const float* lr_dev,
+                                              nnue_stream_t stream);
+
+/* nnue_ftm_backward_weight_update_forward_adam with the weight clip above (_clip_weights, nnue.py:528-539, after
+ * optimizer.step(), train.py:366): the next step's forward contracts the clamped tiles, the ones the pass stores. */
+int nnue_ftm_backward_weight_update_forward_adam_clip(const uint8_t* bits, const float* d_out, int B, int F, int P, int L1,
+                                                      float* weight, float* exp_avg_rows, float* exp_avg_sq_rows, const float* coef,
+                                                      const int32_t* step_counter, float lr, float beta1, float beta2, float eps,
+                                                      float weight_decay, float grad_scale, float weight_clip, const float* lr_dev,
+                                                      const uint8_t* bits_next, const float* sink_next, int B_next, const float* bias,
+                                                      float* out_next, void* scratch, int64_t scratch_bytes, nnue_stream_t stream);
+
+/* nnue_multi_sgd_step with the weight clip above per segment (_clip_weights, nnue.py:528-539, after optimizer.step(),
+ * train.py:366). */
+int nnue_multi_sgd_step_clip(float* const* params, float* const* grads, float* const* momentum_bufs, const int64_t* counts, int n,
+                             const float* lr, const float* momentum, const float* weight_decay, const int32_t* first_step,
+                             const float* weight_clip, float max_norm, float* norm_out, void* scratch, int64_t scratch_bytes,
+                             const float* lr_dev, nnue_stream_t stream);
+
+/* nnue_multi_adam_step with the weight clip above per segment (_clip_weights, nnue.py:528-539, after optimizer.step(),
+ * train.py:366). */
+int nnue_multi_adam_step_clip(float* const* params, float* const* grads, float* const* exp_avgs, float* const* exp_avg_sqs,
+                              int32_t* const* step_counters, const int64_t* counts, int n, const float* lr, const float* beta1,
+                              const float* beta2, const float* eps, const float* weight_decay, const float* weight_clip,
+                              float max_norm, float* norm_out, void* scratch, int64_t scratch_bytes, const float* lr_dev,
+                              nnue_stream_t stream);
 
 #ifdef __cplusplus
 }

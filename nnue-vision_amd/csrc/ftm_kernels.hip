@@ -153,6 +153,18 @@ struct BwwAdamEpi {
   const float* __restrict__ lr_dev;
 };
 
+// The two in-place epilogues with the weight clip (include/nnue_hip.h, "weight clip"): the new table element is clamped to
+// [-wclip, wclip] before it is stored (optim_update.h, clip_weight); momentum and moments are not.  Types of their own, so the
+// kernels without the clamp are compiled from the text they always had.
+struct BwwSgdClipEpi : BwwSgdEpi {
+  static constexpr bool kClip = true;
+  float wclip;
+};
+struct BwwAdamClipEpi : BwwAdamEpi {
+  static constexpr bool kClip = true;
+  float wclip;
+};
+
 struct ValEpi {  // d_conv_out = acc where the position is active, else 0
   static constexpr bool kAU8 = false;
   static constexpr bool kFusedL1 = false;
@@ -596,6 +608,11 @@ __device__ __forceinline__ void nt_store4(float* p, const float4& v) {
 }
 
 template <class Epi, class = void>
+struct has_clip { static constexpr bool value = false; };
+template <class Epi>
+struct has_clip<Epi, decltype((void)Epi::kClip)> { static constexpr bool value = Epi::kClip; };
+
+template <class Epi, class = void>
 struct is_rmw { static constexpr bool value = false; };
 template <class Epi>
 struct is_rmw<Epi, decltype((void)Epi::kRmw)> { static constexpr bool value = Epi::kRmw; };
@@ -649,7 +666,12 @@ __device__ __forceinline__ void rmw_tile(float* __restrict__ smem, const Epi& ep
         }
         nt_store4(epi.momentum + i, g);
       }
-      nt_store4(epi.weight + i, make_float4(w[u].x - lr * g.x, w[u].y - lr * g.y, w[u].z - lr * g.z, w[u].w - lr * g.w));
+      float4 wn = make_float4(w[u].x - lr * g.x, w[u].y - lr * g.y, w[u].z - lr * g.z, w[u].w - lr * g.w);
+      if constexpr (has_clip<Epi>::value) {
+        wn.x = clip_weight(wn.x, epi.wclip); wn.y = clip_weight(wn.y, epi.wclip);
+        wn.z = clip_weight(wn.z, epi.wclip); wn.w = clip_weight(wn.w, epi.wclip);
+      }
+      nt_store4(epi.weight + i, wn);
     }
   }
 }
@@ -709,7 +731,9 @@ __device__ __forceinline__ void rmw_tile_adam(float* __restrict__ smem, const Ep
 #pragma unroll
     for (int e = 0; e < 4; ++e) {  // the arithmetic of adam_apply_kernel, element by element (fused multiply-adds pinned)
       float mi = __uint_as_float(mo[u][e]), vi = __uint_as_float(vv[u][e]);
-      wn[e] = __float_as_uint(adam_update_fused(__uint_as_float(w[u][e]), gv[e], mi, vi, gs, bc, epi.beta1, epi.beta2, epi.eps, epi.wd));
+      float wf = adam_update_fused(__uint_as_float(w[u][e]), gv[e], mi, vi, gs, bc, epi.beta1, epi.beta2, epi.eps, epi.wd);
+      if constexpr (has_clip<Epi>::value) wf = clip_weight(wf, epi.wclip);
+      wn[e] = __float_as_uint(wf);
       mn[e] = __float_as_uint(mi);
       vn[e] = __float_as_uint(vi);
     }
@@ -3037,7 +3061,7 @@ Args make_upd_fwd(const uint8_t* bits, const float* d_out, int B, int F, int P, 
 
 // The fused pass's launch: the scratch check, the forward's plan (slabs, slab length, column tiles, XCD remap) into `a`, the kernel
 // of the product's K-tile count, ftm_finish_kernel.  first: first step of an SGD momentum buffer (written, not read).
-template <bool kAdam>
+template <bool kAdam, bool kClip>
 int update_forward_launch(const char* who, std::conditional_t<kAdam, UpdFwdAdam, UpdFwd> a, int F, bool first, const NextFwd& nx, nnue_stream_t stream) {
   const Shape s = plan(a.Bn, a.L1, a.direct, true, true, true);
   const int64_t need = (int64_t)s.ksplit * a.Bn * a.L1 * (int64_t)sizeof(float);
@@ -3052,10 +3076,10 @@ int update_forward_launch(const char* who, std::conditional_t<kAdam, UpdFwdAdam,
   const bool mom = a.momentum != nullptr;
   auto go = [&](auto nk) {
     constexpr int NK = decltype(nk)::value;
-    if constexpr (kAdam) hipLaunchKernelGGL((ftm_update_forward_kernel<NK, true, false, true>), grid, dim3(256), 0, st, a);
-    else if (!mom) hipLaunchKernelGGL((ftm_update_forward_kernel<NK, false, false>), grid, dim3(256), 0, st, a);
-    else if (first) hipLaunchKernelGGL((ftm_update_forward_kernel<NK, true, true>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((ftm_update_forward_kernel<NK, true, false>), grid, dim3(256), 0, st, a);
+    if constexpr (kAdam) hipLaunchKernelGGL((ftm_update_forward_kernel<NK, true, false, true, kClip>), grid, dim3(256), 0, st, a);
+    else if (!mom) hipLaunchKernelGGL((ftm_update_forward_kernel<NK, false, false, false, kClip>), grid, dim3(256), 0, st, a);
+    else if (first) hipLaunchKernelGGL((ftm_update_forward_kernel<NK, true, true, false, kClip>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((ftm_update_forward_kernel<NK, true, false, false, kClip>), grid, dim3(256), 0, st, a);
   };
   switch ((a.B + 63) / 64) {  // K tiles of the weight-gradient product (nnue_ftm_update_forward_supported: 1, 2, 4, 8 or 16)
     case 1: go(std::integral_constant<int, 1>{}); break;
@@ -3071,10 +3095,18 @@ int update_forward_launch(const char* who, std::conditional_t<kAdam, UpdFwdAdam,
 }
 }  // namespace
 
-extern "C" int nnue_ftm_backward_weight_update(const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight,
-                                               float* momentum_rows, const float* coef, float lr, float momentum, float weight_decay,
-                                               float grad_scale, int first_step, const float* lr_dev, nnue_stream_t stream) {
-  const char* who = "nnue_ftm_backward_weight_update";
+namespace {
+// The weight clip's bound as the table entry points take it (include/nnue_hip.h, "weight clip"); 0 launches the plain kernels.
+int wclip_ok(const char* who, float weight_clip) {
+  NNUE_REQUIRE(weight_clip >= 0.0f && weight_clip <= 3.4028234e38f, NNUE_E_ARG, "%s: weight_clip = %g must be finite and not negative", who,
+               (double)weight_clip);
+  return NNUE_OK;
+}
+
+int weight_update_sgd(const char* who, const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight,
+                      float* momentum_rows, const float* coef, float lr, float momentum, float weight_decay, float grad_scale, int first_step,
+                      float weight_clip, const float* lr_dev, nnue_stream_t stream) {
+  if (const int rc = wclip_ok(who, weight_clip)) return rc;
   if (const int rc = update_ptrs_nonnull(who, bits, d_out, weight, coef, nullptr)) return rc;
   NNUE_REQUIRE(momentum == 0.0f || momentum_rows, NNUE_E_ARG, "%s: momentum %g needs the momentum rows", who, momentum);
   NNUE_REQUIRE(shape_ok(B, F, P, L1), NNUE_E_ARG, "%s: B=%d F=%d P=%d L1=%d out of range", who, B, F, P, L1);
@@ -3082,9 +3114,25 @@ extern "C" int nnue_ftm_backward_weight_update(const uint8_t* bits, const float*
   if (const int rc = update_ptrs_aligned(who, bits, d_out, weight, nullptr, nullptr)) return rc;
   const int direct = (F - 1 < P) ? F - 1 : P;
   if (direct <= 0) return NNUE_OK;
-  return update_launch(who, bits, d_out, B, P, L1, direct,
-                       BwwSgdEpi{weight, momentum == 0.0f ? nullptr : momentum_rows, coef, L1, lr, momentum, weight_decay, grad_scale, first_step, /*xcd_remap=*/1, lr_dev},
-                       stream);
+  const BwwSgdEpi epi{weight, momentum == 0.0f ? nullptr : momentum_rows, coef, L1, lr, momentum, weight_decay, grad_scale, first_step, /*xcd_remap=*/1, lr_dev};
+  if (weight_clip > 0.0f) return update_launch(who, bits, d_out, B, P, L1, direct, BwwSgdClipEpi{epi, weight_clip}, stream);
+  return update_launch(who, bits, d_out, B, P, L1, direct, epi, stream);
+}
+}  // namespace
+
+extern "C" int nnue_ftm_backward_weight_update(const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight,
+                                               float* momentum_rows, const float* coef, float lr, float momentum, float weight_decay,
+                                               float grad_scale, int first_step, const float* lr_dev, nnue_stream_t stream) {
+  return weight_update_sgd("nnue_ftm_backward_weight_update", bits, d_out, B, F, P, L1, weight, momentum_rows, coef, lr, momentum, weight_decay,
+                           grad_scale, first_step, 0.0f, lr_dev, stream);
+}
+
+extern "C" int nnue_ftm_backward_weight_update_clip(const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight,
+                                                    float* momentum_rows, const float* coef, float lr, float momentum, float weight_decay,
+                                                    float grad_scale, int first_step, float weight_clip, const float* lr_dev,
+                                                    nnue_stream_t stream) {
+  return weight_update_sgd("nnue_ftm_backward_weight_update_clip", bits, d_out, B, F, P, L1, weight, momentum_rows, coef, lr, momentum,
+                           weight_decay, grad_scale, first_step, weight_clip, lr_dev, stream);
 }
 
 // nnue_ftm_backward_weight_update + nnue_ftm_forward of the NEXT step's map in one pass over the table (update_forward.h).
@@ -3100,21 +3148,44 @@ extern "C" int nnue_ftm_update_forward_supported(int B, int B_next, int F, int P
   return s.tile == kBf128 && s.ksplit > 1 && s.klen % 128 == 0 && plan(direct, L1, B, false, false, true).tile == kBf128;
 }
 
-extern "C" int nnue_ftm_backward_weight_update_forward(const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight,
-                                                       float* momentum_rows, const float* coef, float lr, float momentum, float weight_decay,
-                                                       float grad_scale, int first_step, const float* lr_dev, const uint8_t* bits_next,
-                                                       const float* sink_next, int B_next, const float* bias, float* out_next, void* scratch,
-                                                       int64_t scratch_bytes, nnue_stream_t stream) {
-  const char* who = "nnue_ftm_backward_weight_update_forward";
-  const NextFwd nx{bits_next, sink_next, bias, out_next, scratch, scratch_bytes};
+namespace {
+int weight_update_forward_sgd(const char* who, const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight,
+                              float* momentum_rows, const float* coef, float lr, float momentum, float weight_decay, float grad_scale,
+                              int first_step, float weight_clip, const float* lr_dev, const NextFwd& nx, int B_next, nnue_stream_t stream) {
+  const uint8_t* bits_next = nx.bits_next;
+  if (const int rc = wclip_ok(who, weight_clip)) return rc;
   if (const int rc = update_ptrs_nonnull(who, bits, d_out, weight, coef, &nx)) return rc;
   NNUE_REQUIRE(momentum == 0.0f || momentum_rows, NNUE_E_ARG, "%s: momentum %g needs the momentum rows", who, momentum);
   NNUE_REQUIRE(nnue_ftm_update_forward_supported(B, B_next, F, P, L1), NNUE_E_SHAPE,
                "%s: B=%d B_next=%d F=%d P=%d L1=%d is not a split-K forward over a big table (use the two separate calls)", who, B, B_next, F, P, L1);
   if (const int rc = update_ptrs_aligned(who, bits, d_out, weight, momentum_rows, &nx)) return rc;
-  const UpdFwd a = make_upd_fwd<UpdFwd>(bits, d_out, B, F, P, L1, weight, momentum == 0.0f ? nullptr : momentum_rows, coef, lr_dev, lr, momentum,
-                                        weight_decay, grad_scale, bits_next, B_next);
-  return update_forward_launch<false>(who, a, F, a.momentum && first_step, nx, stream);
+  UpdFwd a = make_upd_fwd<UpdFwd>(bits, d_out, B, F, P, L1, weight, momentum == 0.0f ? nullptr : momentum_rows, coef, lr_dev, lr, momentum,
+                                  weight_decay, grad_scale, bits_next, B_next);
+  a.wclip = weight_clip;
+  if (weight_clip > 0.0f) return update_forward_launch<false, true>(who, a, F, a.momentum && first_step, nx, stream);
+  return update_forward_launch<false, false>(who, a, F, a.momentum && first_step, nx, stream);
+}
+}  // namespace
+
+extern "C" int nnue_ftm_backward_weight_update_forward(const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight,
+                                                       float* momentum_rows, const float* coef, float lr, float momentum, float weight_decay,
+                                                       float grad_scale, int first_step, const float* lr_dev, const uint8_t* bits_next,
+                                                       const float* sink_next, int B_next, const float* bias, float* out_next, void* scratch,
+                                                       int64_t scratch_bytes, nnue_stream_t stream) {
+  return weight_update_forward_sgd("nnue_ftm_backward_weight_update_forward", bits, d_out, B, F, P, L1, weight, momentum_rows, coef, lr, momentum,
+                                   weight_decay, grad_scale, first_step, 0.0f, lr_dev,
+                                   NextFwd{bits_next, sink_next, bias, out_next, scratch, scratch_bytes}, B_next, stream);
+}
+
+extern "C" int nnue_ftm_backward_weight_update_forward_clip(const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight,
+                                                            float* momentum_rows, const float* coef, float lr, float momentum,
+                                                            float weight_decay, float grad_scale, int first_step, float weight_clip,
+                                                            const float* lr_dev, const uint8_t* bits_next, const float* sink_next, int B_next,
+                                                            const float* bias, float* out_next, void* scratch, int64_t scratch_bytes,
+                                                            nnue_stream_t stream) {
+  return weight_update_forward_sgd("nnue_ftm_backward_weight_update_forward_clip", bits, d_out, B, F, P, L1, weight, momentum_rows, coef, lr,
+                                   momentum, weight_decay, grad_scale, first_step, weight_clip, lr_dev,
+                                   NextFwd{bits_next, sink_next, bias, out_next, scratch, scratch_bytes}, B_next, stream);
 }
 
 // ---- ... and with Adam (train.py:465-470): BwwAdamEpi / the kAdam form of the fused pass -----------------------------------------
@@ -3133,29 +3204,27 @@ int adam_table_args_ok(const char* who, const void* exp_avg_rows, const void* ex
 }
 }  // namespace
 
-extern "C" int nnue_ftm_backward_weight_update_adam(const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight,
-                                                    float* exp_avg_rows, float* exp_avg_sq_rows, const float* coef,
-                                                    const int32_t* step_counter, float lr, float beta1, float beta2, float eps,
-                                                    float weight_decay, float grad_scale, const float* lr_dev, nnue_stream_t stream) {
-  const char* who = "nnue_ftm_backward_weight_update_adam";
+namespace {
+int weight_update_adam(const char* who, const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight, float* exp_avg_rows,
+                       float* exp_avg_sq_rows, const float* coef, const int32_t* step_counter, float lr, float beta1, float beta2, float eps,
+                       float weight_decay, float grad_scale, float weight_clip, const float* lr_dev, nnue_stream_t stream) {
+  if (const int rc = wclip_ok(who, weight_clip)) return rc;
   if (const int rc = update_ptrs_nonnull(who, bits, d_out, weight, coef, nullptr)) return rc;
   if (const int rc = adam_table_args_ok(who, exp_avg_rows, exp_avg_sq_rows, step_counter, B, F, P, L1, beta1, beta2, eps)) return rc;
   if (const int rc = update_ptrs_aligned(who, bits, d_out, weight, nullptr, nullptr)) return rc;
   const int direct = (F - 1 < P) ? F - 1 : P;
   if (direct <= 0) return NNUE_OK;
-  return update_launch(who, bits, d_out, B, P, L1, direct,
-                       BwwAdamEpi{weight, exp_avg_rows, exp_avg_sq_rows, coef, step_counter, L1, lr, beta1, beta2, eps, weight_decay, grad_scale, /*xcd_remap=*/1, lr_dev},
-                       stream);
+  const BwwAdamEpi epi{weight, exp_avg_rows, exp_avg_sq_rows, coef, step_counter, L1, lr, beta1, beta2, eps, weight_decay, grad_scale, /*xcd_remap=*/1, lr_dev};
+  if (weight_clip > 0.0f) return update_launch(who, bits, d_out, B, P, L1, direct, BwwAdamClipEpi{epi, weight_clip}, stream);
+  return update_launch(who, bits, d_out, B, P, L1, direct, epi, stream);
 }
 
-extern "C" int nnue_ftm_backward_weight_update_forward_adam(const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight,
-                                                            float* exp_avg_rows, float* exp_avg_sq_rows, const float* coef,
-                                                            const int32_t* step_counter, float lr, float beta1, float beta2, float eps,
-                                                            float weight_decay, float grad_scale, const float* lr_dev,
-                                                            const uint8_t* bits_next, const float* sink_next, int B_next, const float* bias,
-                                                            float* out_next, void* scratch, int64_t scratch_bytes, nnue_stream_t stream) {
-  const char* who = "nnue_ftm_backward_weight_update_forward_adam";
-  const NextFwd nx{bits_next, sink_next, bias, out_next, scratch, scratch_bytes};
+int weight_update_forward_adam(const char* who, const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight,
+                               float* exp_avg_rows, float* exp_avg_sq_rows, const float* coef, const int32_t* step_counter, float lr, float beta1,
+                               float beta2, float eps, float weight_decay, float grad_scale, float weight_clip, const float* lr_dev,
+                               const NextFwd& nx, int B_next, nnue_stream_t stream) {
+  const uint8_t* bits_next = nx.bits_next;
+  if (const int rc = wclip_ok(who, weight_clip)) return rc;
   if (const int rc = update_ptrs_nonnull(who, bits, d_out, weight, coef, &nx)) return rc;
   if (const int rc = adam_table_args_ok(who, exp_avg_rows, exp_avg_sq_rows, step_counter, B, F, P, L1, beta1, beta2, eps)) return rc;
   NNUE_REQUIRE(nnue_ftm_update_forward_supported(B, B_next, F, P, L1), NNUE_E_SHAPE,
@@ -3168,7 +3237,50 @@ extern "C" int nnue_ftm_backward_weight_update_forward_adam(const uint8_t* bits,
   a.beta1 = beta1;
   a.beta2 = beta2;
   a.eps = eps;
-  return update_forward_launch<true>(who, a, F, false, nx, stream);
+  a.wclip = weight_clip;
+  if (weight_clip > 0.0f) return update_forward_launch<true, true>(who, a, F, false, nx, stream);
+  return update_forward_launch<true, false>(who, a, F, false, nx, stream);
+}
+}  // namespace
+
+extern "C" int nnue_ftm_backward_weight_update_adam(const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight,
+                                                    float* exp_avg_rows, float* exp_avg_sq_rows, const float* coef,
+                                                    const int32_t* step_counter, float lr, float beta1, float beta2, float eps,
+                                                    float weight_decay, float grad_scale, const float* lr_dev, nnue_stream_t stream) {
+  return weight_update_adam("nnue_ftm_backward_weight_update_adam", bits, d_out, B, F, P, L1, weight, exp_avg_rows, exp_avg_sq_rows, coef,
+                            step_counter, lr, beta1, beta2, eps, weight_decay, grad_scale, 0.0f, lr_dev, stream);
+}
+
+extern "C" int nnue_ftm_backward_weight_update_adam_clip(const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight,
+                                                         float* exp_avg_rows, float* exp_avg_sq_rows, const float* coef,
+                                                         const int32_t* step_counter, float lr, float beta1, float beta2, float eps,
+                                                         float weight_decay, float grad_scale, float weight_clip, const float* lr_dev,
+                                                         nnue_stream_t stream) {
+  return weight_update_adam("nnue_ftm_backward_weight_update_adam_clip", bits, d_out, B, F, P, L1, weight, exp_avg_rows, exp_avg_sq_rows, coef,
+                            step_counter, lr, beta1, beta2, eps, weight_decay, grad_scale, weight_clip, lr_dev, stream);
+}
+
+extern "C" int nnue_ftm_backward_weight_update_forward_adam(const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight,
+                                                            float* exp_avg_rows, float* exp_avg_sq_rows, const float* coef,
+                                                            const int32_t* step_counter, float lr, float beta1, float beta2, float eps,
+                                                            float weight_decay, float grad_scale, const float* lr_dev,
+                                                            const uint8_t* bits_next, const float* sink_next, int B_next, const float* bias,
+                                                            float* out_next, void* scratch, int64_t scratch_bytes, nnue_stream_t stream) {
+  return weight_update_forward_adam("nnue_ftm_backward_weight_update_forward_adam", bits, d_out, B, F, P, L1, weight, exp_avg_rows,
+                                    exp_avg_sq_rows, coef, step_counter, lr, beta1, beta2, eps, weight_decay, grad_scale, 0.0f, lr_dev,
+                                    NextFwd{bits_next, sink_next, bias, out_next, scratch, scratch_bytes}, B_next, stream);
+}
+
+extern "C" int nnue_ftm_backward_weight_update_forward_adam_clip(const uint8_t* bits, const float* d_out, int B, int F, int P, int L1,
+                                                                 float* weight, float* exp_avg_rows, float* exp_avg_sq_rows, const float* coef,
+                                                                 const int32_t* step_counter, float lr, float beta1, float beta2, float eps,
+                                                                 float weight_decay, float grad_scale, float weight_clip, const float* lr_dev,
+                                                                 const uint8_t* bits_next, const float* sink_next, int B_next,
+                                                                 const float* bias, float* out_next, void* scratch, int64_t scratch_bytes,
+                                                                 nnue_stream_t stream) {
+  return weight_update_forward_adam("nnue_ftm_backward_weight_update_forward_adam_clip", bits, d_out, B, F, P, L1, weight, exp_avg_rows,
+                                    exp_avg_sq_rows, coef, step_counter, lr, beta1, beta2, eps, weight_decay, grad_scale, weight_clip, lr_dev,
+                                    NextFwd{bits_next, sink_next, bias, out_next, scratch, scratch_bytes}, B_next, stream);
 }
 
 // Which matrix unit a product of this shape runs on (the launch policy above, for reporting: bench.py prices a kernel

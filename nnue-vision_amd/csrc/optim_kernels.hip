@@ -98,6 +98,19 @@ __device__ __forceinline__ float clip_coefficient(float norm, float max_norm) {
 
 #include "optim_update.h"  // sgd_update, AdamBias, adam_bias_correction, adam_update: shared with the product epilogues
 
+// The weight clip of a flat buffer (include/nnue_hip.h, "weight clip"), by value in the kernel arguments: the bound and up to
+// four half-open element ranges of the buffer (unused ones empty).  The apply kernels take it as their last argument.  The SGD
+// kernels are compiled twice: kClip = false is the kernel without it, instruction for instruction, and what a bound of 0 launches;
+// the Adam kernels branch on the bound (see adam_apply_kernel).
+struct FlatClip {
+  float bound;
+  int64_t lo[4], hi[4];
+  __device__ __forceinline__ bool covers(int64_t i) const {
+    return (i >= lo[0] && i < hi[0]) || (i >= lo[1] && i < hi[1]) || (i >= lo[2] && i < hi[2]) || (i >= lo[3] && i < hi[3]);
+  }
+  __device__ __forceinline__ float apply(int64_t i, float w) const { return covers(i) ? clip_weight(w, bound) : w; }
+};
+
 // Block partial of sum (g * scale)^2: 16-byte loads, four independent chains per thread (the 268 MB gradient of
 // the 224x224 configuration is one streaming read; a dependent scalar chain reached only 1.25 TB/s).
 __device__ __forceinline__ float sqnorm_block_partial(const float* __restrict__ g, int64_t count, float scale, float* red,
@@ -192,13 +205,14 @@ __global__ __launch_bounds__(256) void sqnorm_stage1_ste(const float* __restrict
 
 // Every block re-derives the norm from the kNormBlocks partials (4 KiB, L2-resident) in the same
 // fixed order, then streams its share of the update.
+template <bool kClip>
 __global__ __launch_bounds__(256) void sgd_apply_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                         float* __restrict__ m, int64_t count, float lr, float momentum,
                                                         float wd, float max_norm, float scale, int first_step,
                                                         const float* __restrict__ partial, int nparts,
                                                         float* __restrict__ norm_out, const float* __restrict__ ext_partial,
                                                         int ext_count, float* __restrict__ coef_out, int64_t skip_lo, int64_t skip_hi,
-                                                        const float* __restrict__ lr_dev) {
+                                                        const float* __restrict__ lr_dev, const FlatClip fc) {
   __shared__ double red[4];
   __shared__ float coef_s;
   if (lr_dev) lr = lr_dev[0];  // the learning rate as a device scalar: a scheduler changes it without re-capturing the step
@@ -247,27 +261,33 @@ __global__ __launch_bounds__(256) void sgd_apply_kernel(float* __restrict__ p, c
     if (j < live) {
       const int64_t i = j < skip_lo ? j : j + hole;
       float mn;
-      p[i] = sgd_update(pw[u], pg[u], pm[u], mn, gs, lr, momentum, wd, m != nullptr, first_step);
+      float wn = sgd_update(pw[u], pg[u], pm[u], mn, gs, lr, momentum, wd, m != nullptr, first_step);
+      if constexpr (kClip) wn = fc.apply(i, wn);
+      p[i] = wn;
       if (m) m[i] = mn;
     }
   }
   for (int64_t j = j0 + kPre * stride; j < live; j += stride) {
     const int64_t i = j < skip_lo ? j : j + hole;
     float mn;
-    p[i] = sgd_update(p[i], g[i], (m && !first_step) ? m[i] : 0.0f, mn, gs, lr, momentum, wd, m != nullptr, first_step);
+    float wn = sgd_update(p[i], g[i], (m && !first_step) ? m[i] : 0.0f, mn, gs, lr, momentum, wd, m != nullptr, first_step);
+    if constexpr (kClip) wn = fc.apply(i, wn);
+    p[i] = wn;
     if (m) m[i] = mn;
   }
 }
 
 // The same update with 16-byte accesses for buffers that are launch-sized (count, the hole and the pointers multiples of 4 /
 // 16 bytes): one float4 per thread and pass, the first two passes requested before the norm is re-derived.  (The scalar kernel
-// stays for big buffers: with 16-byte accesses it streamed 1.34 GB slower, 225-257 vs 211 us.)
+// stays for big buffers: with 16-byte accesses it streamed 1.34 GB slower, 225-257 vs 211 us.)  kClip: every boundary of the
+// clip's ranges is a multiple of 4 (the entry point checks it), so a float4 lies inside a range or outside it.
+template <bool kClip>
 __global__ __launch_bounds__(256) void sgd_apply_vec_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                             int64_t count, float lr, float momentum, float wd, float max_norm, float scale,
                                                             int first_step, const float* __restrict__ partial, int nparts,
                                                             float* __restrict__ norm_out, const float* __restrict__ ext_partial, int ext_count,
                                                             float* __restrict__ coef_out, int64_t skip_lo, int64_t skip_hi,
-                                                            const float* __restrict__ lr_dev) {
+                                                            const float* __restrict__ lr_dev, const FlatClip fc) {
   __shared__ double red[4];
   __shared__ float coef_s;
   if (lr_dev) lr = lr_dev[0];
@@ -316,6 +336,12 @@ __global__ __launch_bounds__(256) void sgd_apply_vec_kernel(float* __restrict__ 
     float4 mn, wn;
     wn.x = one(w.x, gv.x, mv.x, mn.x); wn.y = one(w.y, gv.y, mv.y, mn.y);
     wn.z = one(w.z, gv.z, mv.z, mn.z); wn.w = one(w.w, gv.w, mv.w, mn.w);
+    if constexpr (kClip) {
+      if (fc.covers(4 * i)) {
+        wn.x = clip_weight(wn.x, fc.bound); wn.y = clip_weight(wn.y, fc.bound);
+        wn.z = clip_weight(wn.z, fc.bound); wn.w = clip_weight(wn.w, fc.bound);
+      }
+    }
     if (m) reinterpret_cast<float4*>(m)[i] = mn;
     reinterpret_cast<float4*>(p)[i] = wn;
   };
@@ -341,12 +367,17 @@ __global__ __launch_bounds__(256) void sqnorm_stage1_count(const float* __restri
   if (threadIdx.x == 0) partial[blockIdx.x] = v;
 }
 
+// The weight clip here is a uniform branch on the descriptor's bound (0: off), not a second instantiation: adam_update leaves its
+// multiply-adds to the compiler's contraction (optim_update.h), and a clamping instantiation of this kernel was compiled with one
+// of them fused that the plain one keeps apart (one ulp) -- with one text both arms share the arithmetic, and it is the
+// arithmetic the kernel had before the clip existed (compared instruction by instruction).  The same in adam_apply_ext_kernel.
 __global__ __launch_bounds__(256) void adam_apply_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                          float* __restrict__ m, float* __restrict__ v, int64_t count,
                                                          float lr, float beta1, float beta2, float eps, float wd,
                                                          float max_norm, float scale, const int* __restrict__ step_counter,
                                                          const float* __restrict__ partial, int nparts,
-                                                         float* __restrict__ norm_out, const float* __restrict__ lr_dev) {
+                                                         float* __restrict__ norm_out, const float* __restrict__ lr_dev,
+                                                         const FlatClip fc) {
   __shared__ double red[4];
   __shared__ float coef_s;
   if (lr_dev) lr = lr_dev[0];
@@ -367,7 +398,9 @@ __global__ __launch_bounds__(256) void adam_apply_kernel(float* __restrict__ p, 
   const int64_t stride = (int64_t)gridDim.x * 256;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < count; i += stride) {
     float mi = m[i], vi = v[i];
-    p[i] = adam_update(p[i], g[i], mi, vi, gs, bc, beta1, beta2, eps, wd);
+    float wn = adam_update(p[i], g[i], mi, vi, gs, bc, beta1, beta2, eps, wd);
+    if (fc.bound > 0.0f) wn = fc.apply(i, wn);  // (uniform; see the note above adam_apply_kernel)
+    p[i] = wn;
     m[i] = mi;
     v[i] = vi;
   }
@@ -392,7 +425,7 @@ __global__ __launch_bounds__(256) void adam_apply_ext_kernel(float* __restrict__
                                                              int nparts, float* __restrict__ norm_out,
                                                              const float* __restrict__ ext_partial, int ext_count,
                                                              float* __restrict__ coef_out, int64_t skip_lo, int64_t skip_hi,
-                                                             const float* __restrict__ lr_dev) {
+                                                             const float* __restrict__ lr_dev, const FlatClip fc) {
   __shared__ double red[4];
   __shared__ float coef_s;
   if (lr_dev) lr = lr_dev[0];
@@ -420,7 +453,9 @@ __global__ __launch_bounds__(256) void adam_apply_ext_kernel(float* __restrict__
   for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < live; j += stride) {
     const int64_t i = j < skip_lo ? j : j + hole;
     float mi = m[i], vi = v[i];
-    p[i] = adam_update(p[i], g[i], mi, vi, gs, bc, beta1, beta2, eps, wd);
+    float wn = adam_update(p[i], g[i], mi, vi, gs, bc, beta1, beta2, eps, wd);
+    if (fc.bound > 0.0f) wn = fc.apply(i, wn);  // (uniform; see the note above adam_apply_kernel)
+    p[i] = wn;
     m[i] = mi;
     v[i] = vi;
   }
@@ -435,7 +470,7 @@ __global__ __launch_bounds__(256) void adam_apply_ext_kernel(float* __restrict__
 constexpr int kMultiChunk = 16384;       // elements per norm partial (4096 partials for the 268 MB table of the 224x224 model)
 constexpr int kMultiUnit = 4096;         // elements per apply unit: 256 threads x 4 float4
 constexpr int kMultiApplyBlocks = 2048;  // apply grid cap: each workgroup then streams >= 8 units of a big table per re-reduction
-constexpr int kMultiSegs = 50;
+constexpr int kMultiSegs = 45;
 
 struct MultiSeg {
   float* p;
@@ -447,6 +482,7 @@ struct MultiSeg {
   int32_t chunk0, unit0;  // this segment's first norm chunk / apply unit within the launch
   float lr, a, b, wd, eps;  // a: momentum or beta1; b: beta2
   int32_t first;            // SGD: no momentum buffer yet (the update writes it without reading)
+  float clip;               // weight clip of this segment (include/nnue_hip.h, "weight clip"); 0: not clamped
 };
 
 struct MultiArgs {
@@ -617,11 +653,15 @@ __device__ __forceinline__ MultiHyper multi_hyper(const MultiArgs& A, int s) {
 
 template <bool kAdam>
 __device__ __forceinline__ float multi_update(const MultiSeg& S, const MultiHyper& h, float w, float g, float& m, float& v, float gs) {
-  if (kAdam) return adam_update(w, g, m, v, gs, h.bc, S.a, S.b, S.eps, S.wd);
-  float mn;
-  const float out = sgd_update(w, g, m, mn, gs, h.lr, S.a, S.wd, S.m != nullptr, S.first != 0);
-  m = mn;
-  return out;
+  float out;
+  if (kAdam) {
+    out = adam_update(w, g, m, v, gs, h.bc, S.a, S.b, S.eps, S.wd);
+  } else {
+    float mn;
+    out = sgd_update(w, g, m, mn, gs, h.lr, S.a, S.wd, S.m != nullptr, S.first != 0);
+    m = mn;
+  }
+  return S.clip > 0.0f ? clip_weight(out, S.clip) : out;  // (wave-uniform: the segment's)
 }
 
 // Stage 2.  The first unit is requested before the norm is re-derived (both are first touches after the kernel boundary).
@@ -689,23 +729,70 @@ __global__ __launch_bounds__(256) void multi_apply_kernel(const MultiArgs A) {
 
 }  // namespace
 
-extern "C" int nnue_adam_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int32_t* step_counter, int64_t count,
-                              float lr, float beta1, float beta2, float eps, float weight_decay, float max_norm, float grad_scale,
-                              float* norm_out, void* scratch, int64_t scratch_bytes, const float* lr_dev, nnue_stream_t stream) {
-  NNUE_REQUIRE(params && grads && exp_avg && exp_avg_sq && step_counter && scratch, NNUE_E_ARG, "nnue_adam_step: null pointer");
-  NNUE_REQUIRE(count > 0, NNUE_E_ARG, "nnue_adam_step: count must be positive");
+namespace {
+
+// The flat entry points' weight clip, checked and packed for the kernels (include/nnue_hip.h, "weight clip"): `ranges` holds
+// n_ranges pairs (lo, hi) of element indices.  *on: a kernel with the clamp is to be launched (a bound of 0 or no range with
+// an element in it: the plain kernel).  *by4: every boundary is a multiple of 4 (what the float4 kernel needs).
+int flat_clip_of(const char* who, float bound, const int64_t* ranges, int n_ranges, int64_t count, FlatClip* fc, bool* on, bool* by4) {
+  *fc = FlatClip{};
+  *on = false;
+  *by4 = true;
+  NNUE_REQUIRE(bound >= 0.0f && bound <= 3.4028234e38f, NNUE_E_ARG, "%s: weight_clip = %g must be finite and not negative", who, (double)bound);
+  NNUE_REQUIRE(n_ranges >= 0 && n_ranges <= 4 && (n_ranges == 0 || ranges), NNUE_E_ARG, "%s: the weight clip takes 0 .. 4 ranges, got %d", who,
+               n_ranges);
+  fc->bound = bound;
+  for (int r = 0; r < n_ranges; ++r) {
+    const int64_t lo = ranges[2 * r], hi = ranges[2 * r + 1];
+    NNUE_REQUIRE(lo >= 0 && lo <= hi && hi <= count, NNUE_E_ARG, "%s: clip range %d = [%lld, %lld) does not lie in [0, %lld]", who, r,
+                 (long long)lo, (long long)hi, (long long)count);
+    fc->lo[r] = lo;
+    fc->hi[r] = hi;
+    if (lo < hi && bound > 0.0f) *on = true;
+    if (lo < hi && (lo % 4 != 0 || hi % 4 != 0)) *by4 = false;
+  }
+  return NNUE_OK;
+}
+
+int adam_step_impl(const char* who, float* params, float* grads, float* exp_avg, float* exp_avg_sq, int32_t* step_counter, int64_t count,
+                   float lr, float beta1, float beta2, float eps, float weight_decay, float max_norm, float grad_scale, float* norm_out,
+                   void* scratch, int64_t scratch_bytes, const float* lr_dev, float weight_clip, const int64_t* clip_ranges, int n_ranges,
+                   nnue_stream_t stream) {
+  NNUE_REQUIRE(params && grads && exp_avg && exp_avg_sq && step_counter && scratch, NNUE_E_ARG, "%s: null pointer", who);
+  NNUE_REQUIRE(count > 0, NNUE_E_ARG, "%s: count must be positive", who);
   NNUE_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps > 0.f, NNUE_E_ARG,
-               "nnue_adam_step: betas must be in [0,1) and eps > 0");
-  NNUE_REQUIRE(scratch_bytes >= nnue_sgd_scratch(count), NNUE_E_SCRATCH, "nnue_adam_step: scratch %lld < %lld bytes",
+               "%s: betas must be in [0,1) and eps > 0", who);
+  NNUE_REQUIRE(scratch_bytes >= nnue_sgd_scratch(count), NNUE_E_SCRATCH, "%s: scratch %lld < %lld bytes", who,
                (long long)scratch_bytes, (long long)nnue_sgd_scratch(count));
+  FlatClip fc;
+  bool clip_on, by4;
+  if (const int rc = flat_clip_of(who, weight_clip, clip_ranges, n_ranges, count, &fc, &clip_on, &by4)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   float* partial = static_cast<float*>(scratch);
   hipLaunchKernelGGL(sqnorm_stage1_count, dim3(kNormBlocks), dim3(256), 0, s, grads, count, grad_scale, partial, step_counter);
   int blocks = (int)((count + 1023) / 1024);
   if (blocks > 2048) blocks = 2048;
+  if (!clip_on) fc = FlatClip{};  // bound 0: the kernel's plain arm
   hipLaunchKernelGGL(adam_apply_kernel, dim3(blocks), dim3(256), 0, s, params, grads, exp_avg, exp_avg_sq, count, lr, beta1, beta2, eps,
-                     weight_decay, max_norm, grad_scale, step_counter, partial, kNormBlocks, norm_out, lr_dev);
-  return nnue_launch_status("nnue_adam_step");
+                     weight_decay, max_norm, grad_scale, step_counter, partial, kNormBlocks, norm_out, lr_dev, fc);
+  return nnue_launch_status(who);
+}
+
+}  // namespace
+
+extern "C" int nnue_adam_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int32_t* step_counter, int64_t count,
+                              float lr, float beta1, float beta2, float eps, float weight_decay, float max_norm, float grad_scale,
+                              float* norm_out, void* scratch, int64_t scratch_bytes, const float* lr_dev, nnue_stream_t stream) {
+  return adam_step_impl("nnue_adam_step", params, grads, exp_avg, exp_avg_sq, step_counter, count, lr, beta1, beta2, eps, weight_decay, max_norm,
+                        grad_scale, norm_out, scratch, scratch_bytes, lr_dev, 0.0f, nullptr, 0, stream);
+}
+
+extern "C" int nnue_adam_step_clip(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int32_t* step_counter, int64_t count,
+                                   float lr, float beta1, float beta2, float eps, float weight_decay, float max_norm, float grad_scale,
+                                   float* norm_out, void* scratch, int64_t scratch_bytes, const float* lr_dev, float weight_clip,
+                                   const int64_t* clip_ranges, int n_clip_ranges, nnue_stream_t stream) {
+  return adam_step_impl("nnue_adam_step_clip", params, grads, exp_avg, exp_avg_sq, step_counter, count, lr, beta1, beta2, eps, weight_decay,
+                        max_norm, grad_scale, norm_out, scratch, scratch_bytes, lr_dev, weight_clip, clip_ranges, n_clip_ranges, stream);
 }
 
 extern "C" int nnue_cross_entropy(const float* logits, const int64_t* labels, int B, int C, float grad_scale,
@@ -735,16 +822,21 @@ extern "C" int nnue_sqnorm_partials(const float* grads, int64_t count, float* pa
   return nnue_launch_status("nnue_sqnorm_partials");
 }
 
-extern "C" int nnue_sgd_step(float* params, float* grads, float* momentum_buf, int64_t count, float lr, float momentum,
-                             float weight_decay, float max_norm, float grad_scale, int first_step, float* norm_out,
-                             void* scratch, int64_t scratch_bytes, const float* ste_partial, int ste_chunks, int ste_fps,
-                             float* ste_d_thr, float* ste_d_weight, const float* ext_partial, int ext_count, int64_t ext_lo,
-                             int64_t ext_hi, float* coef_out, int ext_applied_elsewhere, const float* lr_dev, nnue_stream_t stream) {
-  NNUE_REQUIRE(params && grads && scratch, NNUE_E_ARG, "nnue_sgd_step: null pointer");
-  NNUE_REQUIRE(count > 0, NNUE_E_ARG, "nnue_sgd_step: count must be positive");
-  NNUE_REQUIRE(momentum == 0.0f || momentum_buf, NNUE_E_ARG, "nnue_sgd_step: momentum %g needs a momentum buffer", momentum);
-  NNUE_REQUIRE(scratch_bytes >= nnue_sgd_scratch(count), NNUE_E_SCRATCH, "nnue_sgd_step: scratch %lld < %lld bytes",
+namespace {
+int sgd_step_impl(const char* who, float* params, float* grads, float* momentum_buf, int64_t count, float lr, float momentum,
+                  float weight_decay, float max_norm, float grad_scale, int first_step, float* norm_out,
+                  void* scratch, int64_t scratch_bytes, const float* ste_partial, int ste_chunks, int ste_fps,
+                  float* ste_d_thr, float* ste_d_weight, const float* ext_partial, int ext_count, int64_t ext_lo,
+                  int64_t ext_hi, float* coef_out, int ext_applied_elsewhere, const float* lr_dev, float weight_clip,
+                  const int64_t* clip_ranges, int n_ranges, nnue_stream_t stream) {
+  NNUE_REQUIRE(params && grads && scratch, NNUE_E_ARG, "%s: null pointer", who);
+  NNUE_REQUIRE(count > 0, NNUE_E_ARG, "%s: count must be positive", who);
+  NNUE_REQUIRE(momentum == 0.0f || momentum_buf, NNUE_E_ARG, "%s: momentum %g needs a momentum buffer", who, momentum);
+  NNUE_REQUIRE(scratch_bytes >= nnue_sgd_scratch(count), NNUE_E_SCRATCH, "%s: scratch %lld < %lld bytes", who,
                (long long)scratch_bytes, (long long)nnue_sgd_scratch(count));
+  FlatClip fc;
+  bool clip_on, by4;
+  if (const int rc = flat_clip_of(who, weight_clip, clip_ranges, n_ranges, count, &fc, &clip_on, &by4)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   float* partial = static_cast<float*>(scratch);
   // norm workgroups: 16 floats per thread while that still leaves fewer than kNormBlocks (a small model's apply kernel
@@ -753,11 +845,11 @@ extern "C" int nnue_sgd_step(float* params, float* grads, float* momentum_buf, i
   nb = nb < 64 ? 64 : (nb > kNormBlocks ? kNormBlocks : nb);
   int nparts = nb;
   NNUE_REQUIRE(!ext_applied_elsewhere || (ext_partial && coef_out), NNUE_E_ARG,
-               "nnue_sgd_step: ext_applied_elsewhere needs the producer's partials and coef_out");
+               "%s: ext_applied_elsewhere needs the producer's partials and coef_out", who);
   if (ext_partial) {
     NNUE_REQUIRE(ext_count > 0 && ext_count <= 65536 && ext_lo >= 0 && ext_lo < ext_hi && ext_hi <= count && ext_lo % 4 == 0 &&
                      (ext_hi % 4 == 0 || ext_hi == count),
-                 NNUE_E_ARG, "nnue_sgd_step: producer partials need 0 < count <= 65536 and a range [lo, hi) of multiples of 4 inside grads");
+                 NNUE_E_ARG, "%s: producer partials need 0 < count <= 65536 and a range [lo, hi) of multiples of 4 inside grads", who);
   } else {
     ext_lo = ext_hi = 0;
     ext_count = 0;
@@ -765,14 +857,14 @@ extern "C" int nnue_sgd_step(float* params, float* grads, float* momentum_buf, i
   if (ste_partial) {
     // the deferred sums own the first `skip` elements of grads: [d_thr | d_weight] in either order, nothing else
     NNUE_REQUIRE(ste_d_thr && ste_d_weight && ste_chunks > 0 && ste_fps > 0 && ste_fps * 28 <= 4 * kSteRideBlocks, NNUE_E_ARG,
-                 "nnue_sgd_step: deferred STE sums need d_thr, d_weight, chunks > 0 and fps * 28 <= %d", 4 * kSteRideBlocks);
+                 "%s: deferred STE sums need d_thr, d_weight, chunks > 0 and fps * 28 <= %d", who, 4 * kSteRideBlocks);
     const float* lo = ste_d_thr < ste_d_weight ? ste_d_thr : ste_d_weight;
     const float* hi_t = ste_d_thr + ste_fps;
     const float* hi_w = ste_d_weight + (size_t)ste_fps * 27;
     const float* hi = hi_t > hi_w ? hi_t : hi_w;
     const int64_t skip = nnue_round_up(hi - grads, 4);
     NNUE_REQUIRE((!ext_partial || ext_lo >= skip) && lo == grads && skip <= count && skip <= nnue_round_up(ste_fps, 4) + nnue_round_up((int64_t)ste_fps * 27, 4) + 8, NNUE_E_ARG,
-                 "nnue_sgd_step: deferred STE outputs must be the first elements of grads");
+                 "%s: deferred STE outputs must be the first elements of grads", who);
     const int s2_blocks = (ste_fps * 28 + 3) / 4;
     // padding between / after the two outputs is never written by the sums: it enters neither the norm nor is it read
     // before the update multiplies it -- keep it zero (the flat gradient buffer's padding is zero-initialised)
@@ -790,40 +882,47 @@ extern "C" int nnue_sgd_step(float* params, float* grads, float* momentum_buf, i
   float* mom = momentum == 0.0f ? nullptr : momentum_buf;
   static const char* novec = std::getenv("NNUE_SGD_SCALAR");
   const bool vec = !(novec && novec[0] == '1') && live <= (16ll << 20) && count % 4 == 0 && skip_lo % 4 == 0 && skip_hi % 4 == 0 &&
-                   nnue_aligned16(params) && nnue_aligned16(grads) && (!mom || nnue_aligned16(mom));
+                   nnue_aligned16(params) && nnue_aligned16(grads) && (!mom || nnue_aligned16(mom)) && (!clip_on || by4);
+  auto go = [&](auto kernel, int grid) {  // (the plain and the clamping kernel of a form take the same arguments)
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, s, params, grads, mom, count, lr, momentum, weight_decay, max_norm, grad_scale,
+                       first_step, partial, nparts, norm_out, ext_partial, ext_count, coef_out, skip_lo, skip_hi, lr_dev, fc);
+  };
   if (vec) {
     int vb = (int)((live / 4 + 511) / 512);  // two float4 passes per thread
     vb = vb < 1 ? 1 : (vb > 2048 ? 2048 : vb);
-    hipLaunchKernelGGL(sgd_apply_vec_kernel, dim3(vb), dim3(256), 0, s, params, grads, mom, count, lr, momentum, weight_decay, max_norm, grad_scale,
-                       first_step, partial, nparts, norm_out, ext_partial, ext_count, coef_out, skip_lo, skip_hi, lr_dev);
-    return nnue_launch_status("nnue_sgd_step");
+    if (clip_on) go(sgd_apply_vec_kernel<true>, vb);
+    else go(sgd_apply_vec_kernel<false>, vb);
+    return nnue_launch_status(who);
   }
-  hipLaunchKernelGGL(sgd_apply_kernel, dim3(blocks), dim3(256), 0, s, params, grads, mom, count, lr, momentum, weight_decay, max_norm, grad_scale,
-                     first_step, partial, nparts, norm_out, ext_partial, ext_count, coef_out, skip_lo, skip_hi, lr_dev);
-  return nnue_launch_status("nnue_sgd_step");
+  if (clip_on) go(sgd_apply_kernel<true>, blocks);
+  else go(sgd_apply_kernel<false>, blocks);
+  return nnue_launch_status(who);
 }
 
-extern "C" int nnue_adam_step_ext(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int32_t* step_counter, int64_t count,
-                                  float lr, float beta1, float beta2, float eps, float weight_decay, float max_norm, float grad_scale,
-                                  float* norm_out, void* scratch, int64_t scratch_bytes, const float* ext_partial, int ext_count,
-                                  int64_t ext_lo, int64_t ext_hi, float* coef_out, int ext_applied_elsewhere, const float* lr_dev,
-                                  nnue_stream_t stream) {
-  NNUE_REQUIRE(params && grads && exp_avg && exp_avg_sq && step_counter && scratch, NNUE_E_ARG, "nnue_adam_step_ext: null pointer");
-  NNUE_REQUIRE(count > 0, NNUE_E_ARG, "nnue_adam_step_ext: count must be positive");
+int adam_step_ext_impl(const char* who, float* params, float* grads, float* exp_avg, float* exp_avg_sq, int32_t* step_counter, int64_t count,
+                       float lr, float beta1, float beta2, float eps, float weight_decay, float max_norm, float grad_scale,
+                       float* norm_out, void* scratch, int64_t scratch_bytes, const float* ext_partial, int ext_count,
+                       int64_t ext_lo, int64_t ext_hi, float* coef_out, int ext_applied_elsewhere, const float* lr_dev,
+                       float weight_clip, const int64_t* clip_ranges, int n_ranges, nnue_stream_t stream) {
+  NNUE_REQUIRE(params && grads && exp_avg && exp_avg_sq && step_counter && scratch, NNUE_E_ARG, "%s: null pointer", who);
+  NNUE_REQUIRE(count > 0, NNUE_E_ARG, "%s: count must be positive", who);
   NNUE_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps > 0.f, NNUE_E_ARG,
-               "nnue_adam_step_ext: betas must be in [0,1) and eps > 0");
-  NNUE_REQUIRE(scratch_bytes >= nnue_sgd_scratch(count), NNUE_E_SCRATCH, "nnue_adam_step_ext: scratch %lld < %lld bytes",
+               "%s: betas must be in [0,1) and eps > 0", who);
+  NNUE_REQUIRE(scratch_bytes >= nnue_sgd_scratch(count), NNUE_E_SCRATCH, "%s: scratch %lld < %lld bytes", who,
                (long long)scratch_bytes, (long long)nnue_sgd_scratch(count));
   NNUE_REQUIRE(!ext_applied_elsewhere || (ext_partial && coef_out), NNUE_E_ARG,
-               "nnue_adam_step_ext: ext_applied_elsewhere needs the producer's partials and coef_out");
+               "%s: ext_applied_elsewhere needs the producer's partials and coef_out", who);
   if (ext_partial) {
     NNUE_REQUIRE(ext_count > 0 && ext_count <= 65536 && ext_lo >= 0 && ext_lo < ext_hi && ext_hi <= count && ext_lo % 4 == 0 &&
                      (ext_hi % 4 == 0 || ext_hi == count),
-                 NNUE_E_ARG, "nnue_adam_step_ext: producer partials need 0 < count <= 65536 and a range [lo, hi) of multiples of 4 inside grads");
+                 NNUE_E_ARG, "%s: producer partials need 0 < count <= 65536 and a range [lo, hi) of multiples of 4 inside grads", who);
   } else {
     ext_lo = ext_hi = 0;
     ext_count = 0;
   }
+  FlatClip fc;
+  bool clip_on, by4;
+  if (const int rc = flat_clip_of(who, weight_clip, clip_ranges, n_ranges, count, &fc, &clip_on, &by4)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   float* partial = static_cast<float*>(scratch);
   int nb = (int)((count + 4095) / 4096);  // as nnue_sgd_step: 16 floats per thread, 64 .. kNormBlocks workgroups
@@ -834,10 +933,53 @@ extern "C" int nnue_adam_step_ext(float* params, float* grads, float* exp_avg, f
   int blocks = (int)((live + 1023) / 1024);
   blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
   const int64_t skip_lo = ext_applied_elsewhere ? ext_lo : 0, skip_hi = ext_applied_elsewhere ? ext_hi : 0;
-  hipLaunchKernelGGL(adam_apply_ext_kernel, dim3(blocks), dim3(256), 0, s, params, grads, exp_avg, exp_avg_sq, count, lr, beta1, beta2, eps,
-                     weight_decay, max_norm, grad_scale, step_counter, partial, nb, norm_out, ext_partial, ext_count, coef_out, skip_lo, skip_hi,
-                     lr_dev);
-  return nnue_launch_status("nnue_adam_step_ext");
+  if (!clip_on) fc = FlatClip{};  // bound 0: the kernel's plain arm
+  hipLaunchKernelGGL(adam_apply_ext_kernel, dim3(blocks), dim3(256), 0, s, params, grads, exp_avg, exp_avg_sq, count, lr, beta1, beta2,
+                     eps, weight_decay, max_norm, grad_scale, step_counter, partial, nb, norm_out, ext_partial, ext_count, coef_out, skip_lo,
+                     skip_hi, lr_dev, fc);
+  return nnue_launch_status(who);
+}
+}  // namespace
+
+extern "C" int nnue_sgd_step(float* params, float* grads, float* momentum_buf, int64_t count, float lr, float momentum,
+                             float weight_decay, float max_norm, float grad_scale, int first_step, float* norm_out,
+                             void* scratch, int64_t scratch_bytes, const float* ste_partial, int ste_chunks, int ste_fps,
+                             float* ste_d_thr, float* ste_d_weight, const float* ext_partial, int ext_count, int64_t ext_lo,
+                             int64_t ext_hi, float* coef_out, int ext_applied_elsewhere, const float* lr_dev, nnue_stream_t stream) {
+  return sgd_step_impl("nnue_sgd_step", params, grads, momentum_buf, count, lr, momentum, weight_decay, max_norm, grad_scale, first_step, norm_out,
+                       scratch, scratch_bytes, ste_partial, ste_chunks, ste_fps, ste_d_thr, ste_d_weight, ext_partial, ext_count, ext_lo, ext_hi,
+                       coef_out, ext_applied_elsewhere, lr_dev, 0.0f, nullptr, 0, stream);
+}
+
+extern "C" int nnue_sgd_step_clip(float* params, float* grads, float* momentum_buf, int64_t count, float lr, float momentum,
+                                  float weight_decay, float max_norm, float grad_scale, int first_step, float* norm_out,
+                                  void* scratch, int64_t scratch_bytes, const float* ste_partial, int ste_chunks, int ste_fps,
+                                  float* ste_d_thr, float* ste_d_weight, const float* ext_partial, int ext_count, int64_t ext_lo,
+                                  int64_t ext_hi, float* coef_out, int ext_applied_elsewhere, const float* lr_dev, float weight_clip,
+                                  const int64_t* clip_ranges, int n_clip_ranges, nnue_stream_t stream) {
+  return sgd_step_impl("nnue_sgd_step_clip", params, grads, momentum_buf, count, lr, momentum, weight_decay, max_norm, grad_scale, first_step,
+                       norm_out, scratch, scratch_bytes, ste_partial, ste_chunks, ste_fps, ste_d_thr, ste_d_weight, ext_partial, ext_count, ext_lo,
+                       ext_hi, coef_out, ext_applied_elsewhere, lr_dev, weight_clip, clip_ranges, n_clip_ranges, stream);
+}
+
+extern "C" int nnue_adam_step_ext(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int32_t* step_counter, int64_t count,
+                                  float lr, float beta1, float beta2, float eps, float weight_decay, float max_norm, float grad_scale,
+                                  float* norm_out, void* scratch, int64_t scratch_bytes, const float* ext_partial, int ext_count,
+                                  int64_t ext_lo, int64_t ext_hi, float* coef_out, int ext_applied_elsewhere, const float* lr_dev,
+                                  nnue_stream_t stream) {
+  return adam_step_ext_impl("nnue_adam_step_ext", params, grads, exp_avg, exp_avg_sq, step_counter, count, lr, beta1, beta2, eps, weight_decay,
+                            max_norm, grad_scale, norm_out, scratch, scratch_bytes, ext_partial, ext_count, ext_lo, ext_hi, coef_out,
+                            ext_applied_elsewhere, lr_dev, 0.0f, nullptr, 0, stream);
+}
+
+extern "C" int nnue_adam_step_ext_clip(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int32_t* step_counter, int64_t count,
+                                       float lr, float beta1, float beta2, float eps, float weight_decay, float max_norm, float grad_scale,
+                                       float* norm_out, void* scratch, int64_t scratch_bytes, const float* ext_partial, int ext_count,
+                                       int64_t ext_lo, int64_t ext_hi, float* coef_out, int ext_applied_elsewhere, const float* lr_dev,
+                                       float weight_clip, const int64_t* clip_ranges, int n_clip_ranges, nnue_stream_t stream) {
+  return adam_step_ext_impl("nnue_adam_step_ext_clip", params, grads, exp_avg, exp_avg_sq, step_counter, count, lr, beta1, beta2, eps,
+                            weight_decay, max_norm, grad_scale, norm_out, scratch, scratch_bytes, ext_partial, ext_count, ext_lo, ext_hi, coef_out,
+                            ext_applied_elsewhere, lr_dev, weight_clip, clip_ranges, n_clip_ranges, stream);
 }
 
 extern "C" int nnue_confusion_accumulate(const float* logits, const int64_t* labels, int B, int C, uint64_t* confusion,
@@ -860,8 +1002,8 @@ int64_t multi_chunks(int64_t count) { return (count + kMultiChunk - 1) / kMultiC
 template <bool kAdam>
 int multi_step(const char* what, float* const* params, float* const* grads, float* const* m, float* const* v, int32_t* const* steps,
                const int64_t* counts, int n, const float* lr, const float* a, const float* b, const float* eps, const float* wd,
-               const int32_t* first, float max_norm, float* norm_out, void* scratch, int64_t scratch_bytes, const float* lr_dev,
-               nnue_stream_t stream) {
+               const int32_t* first, const float* clip, float max_norm, float* norm_out, void* scratch, int64_t scratch_bytes,
+               const float* lr_dev, nnue_stream_t stream) {
   NNUE_REQUIRE(n > 0, NNUE_E_ARG, "%s: n = %d must be positive", what, n);
   NNUE_REQUIRE(params && grads && counts && lr && a && wd && scratch && (kAdam ? (m && v && steps && b && eps) : first != nullptr),
                NNUE_E_ARG, "%s: null pointer", what);
@@ -877,6 +1019,8 @@ int multi_step(const char* what, float* const* params, float* const* grads, floa
     } else {
       NNUE_REQUIRE(a[i] == 0.0f || (m && m[i]), NNUE_E_ARG, "%s: momentum %g needs a momentum buffer (segment %d)", what, a[i], i);
     }
+    NNUE_REQUIRE(!clip || (clip[i] >= 0.0f && clip[i] <= 3.4028234e38f), NNUE_E_ARG, "%s: weight_clip = %g of segment %d must be finite and not negative",
+                 what, clip ? (double)clip[i] : 0.0, i);
     nparts += multi_chunks(counts[i]);
   }
   NNUE_REQUIRE(nparts < ((int64_t)1 << 28), NNUE_E_ARG, "%s: %lld elements in all: too many", what, (long long)nparts * kMultiChunk);
@@ -900,7 +1044,8 @@ int multi_step(const char* what, float* const* params, float* const* grads, floa
       MultiSeg& S = A.seg[i];
       const bool has_m = kAdam || a[j] != 0.0f;
       S = MultiSeg{params[j], grads[j], has_m ? m[j] : nullptr, kAdam ? v[j] : nullptr, kAdam ? steps[j] : nullptr, counts[j],
-                   A.chunks, A.units, lr[j], a[j], kAdam ? b[j] : 0.0f, wd[j], kAdam ? eps[j] : 0.0f, kAdam ? 0 : first[j]};
+                   A.chunks, A.units, lr[j], a[j], kAdam ? b[j] : 0.0f, wd[j], kAdam ? eps[j] : 0.0f, kAdam ? 0 : first[j],
+                   clip ? clip[j] : 0.0f};
       A.chunks += (int32_t)multi_chunks(counts[j]);
       A.units += (int32_t)((counts[j] + kMultiUnit - 1) / kMultiUnit);
     }
@@ -935,7 +1080,15 @@ extern "C" int nnue_multi_sgd_step(float* const* params, float* const* grads, fl
                                    float max_norm, float* norm_out, void* scratch, int64_t scratch_bytes, const float* lr_dev,
                                    nnue_stream_t stream) {
   return multi_step<false>("nnue_multi_sgd_step", params, grads, momentum_bufs, nullptr, nullptr, counts, n, lr, momentum, nullptr,
-                           nullptr, weight_decay, first_step, max_norm, norm_out, scratch, scratch_bytes, lr_dev, stream);
+                           nullptr, weight_decay, first_step, nullptr, max_norm, norm_out, scratch, scratch_bytes, lr_dev, stream);
+}
+
+extern "C" int nnue_multi_sgd_step_clip(float* const* params, float* const* grads, float* const* momentum_bufs, const int64_t* counts, int n,
+                                        const float* lr, const float* momentum, const float* weight_decay, const int32_t* first_step,
+                                        const float* weight_clip, float max_norm, float* norm_out, void* scratch, int64_t scratch_bytes,
+                                        const float* lr_dev, nnue_stream_t stream) {
+  return multi_step<false>("nnue_multi_sgd_step_clip", params, grads, momentum_bufs, nullptr, nullptr, counts, n, lr, momentum, nullptr,
+                           nullptr, weight_decay, first_step, weight_clip, max_norm, norm_out, scratch, scratch_bytes, lr_dev, stream);
 }
 
 extern "C" int nnue_multi_adam_step(float* const* params, float* const* grads, float* const* exp_avgs, float* const* exp_avg_sqs,
@@ -943,7 +1096,16 @@ extern "C" int nnue_multi_adam_step(float* const* params, float* const* grads, f
                                     const float* beta2, const float* eps, const float* weight_decay, float max_norm, float* norm_out,
                                     void* scratch, int64_t scratch_bytes, const float* lr_dev, nnue_stream_t stream) {
   return multi_step<true>("nnue_multi_adam_step", params, grads, exp_avgs, exp_avg_sqs, step_counters, counts, n, lr, beta1, beta2, eps,
-                          weight_decay, nullptr, max_norm, norm_out, scratch, scratch_bytes, lr_dev, stream);
+                          weight_decay, nullptr, nullptr, max_norm, norm_out, scratch, scratch_bytes, lr_dev, stream);
+}
+
+extern "C" int nnue_multi_adam_step_clip(float* const* params, float* const* grads, float* const* exp_avgs, float* const* exp_avg_sqs,
+                                         int32_t* const* step_counters, const int64_t* counts, int n, const float* lr, const float* beta1,
+                                         const float* beta2, const float* eps, const float* weight_decay, const float* weight_clip,
+                                         float max_norm, float* norm_out, void* scratch, int64_t scratch_bytes, const float* lr_dev,
+                                         nnue_stream_t stream) {
+  return multi_step<true>("nnue_multi_adam_step_clip", params, grads, exp_avgs, exp_avg_sqs, step_counters, counts, n, lr, beta1, beta2, eps,
+                          weight_decay, nullptr, weight_clip, max_norm, norm_out, scratch, scratch_bytes, lr_dev, stream);
 }
 
 namespace {

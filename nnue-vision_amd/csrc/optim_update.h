@@ -30,6 +30,12 @@ __device__ __forceinline__ float adam_update(float w, float g, float& m, float& 
   return w - bc.step_size * (m / (sqrtf(v) * bc.inv_sqrt_bc2 + eps));
 }
 
+// The post-update weight clip (nnue.py:528-539, _clip_weights; include/nnue_hip.h, "weight clip"): what torch.clamp_(-c, c)
+// leaves, bit for bit -- a NaN stays a NaN and -0.0 stays -0.0, which fminf / fmaxf would not keep.  Every kernel that applies
+// an update to a clipped tensor calls it on the value sgd_update / adam_update / adam_update_fused returned, before the store;
+// the optimizer's state is formed from the un-clamped arithmetic and never clamped.
+__device__ __forceinline__ float clip_weight(float w, float c) { return w > c ? c : (w < -c ? -c : w); }
+
 // adam_update with every fused multiply-add written out -- the form -ffp-contract=on gives that text (the multiply on the
 // left of a sum is the fused one).  Under the build's default contraction the compiler fuses a * b + c * d wherever the
 // caller's context lets it (measured: v = beta2 v + (1 - beta2) g g came out as one fma in the product's epilogue and as

@@ -33,6 +33,7 @@ struct UpdFwd {
   int B, Bn, P, L1, direct, klen, tiles_n, xcd_remap;  // B rows of the factors (bits, d_out), Bn rows of the next map / out'
   float lr, mom, wd, scale;
   int abl;  // timing-only ablations (NNUE_ABLATIONS builds): 1 no parameter/momentum loads, 2 no stores, 4 no forward phase, 8 no d_W MFMAs
+  float wclip;  // the weight clip's bound (kClip forms of the kernel; include/nnue_hip.h, "weight clip")
 };
 // The Adam form (torch.optim.Adam, train.py:465-470): `momentum` holds the exp_avg rows; the step number is the device counter
 // the optimizer's norm launch has already advanced, so the launch replays from a graph.
@@ -72,7 +73,11 @@ __device__ __forceinline__ int uf_wp_img(int row, int chunk) { return row * 256 
 // from there on, and the final contract1(), the barrier, the accumulators' trip through LDS and stage3() lie between the
 // request and its first use.  Compiled: 226-235 VGPRs over the kNK forms (230 at kNK = 2), no scratch, 64 KB LDS, two workgroups
 // per CU as the SGD forms.  The bias corrections (two double-precision pow) are formed once, at entry.
-template <int kNK, bool kMom, bool kFirst, bool kAdam = false>
+//
+// kClip: the weight clip.  The new tile is clamped to [-wclip, wclip] in phase 2 BEFORE it is stored and before phase 3 splits it
+// into the planes of step t+1's forward -- the forward must contract the table the store leaves, which a clamp launched after this
+// pass could not give it.  Momentum and moments are stored un-clamped.
+template <int kNK, bool kMom, bool kFirst, bool kAdam = false, bool kClip = false>
 __global__ __launch_bounds__(256, 2) void ftm_update_forward_kernel(std::conditional_t<kAdam, UpdFwdAdam, UpdFwd> a) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[kUfLds];
   constexpr int KT = kBf64K, PB = 64 * KT * 2;
@@ -311,6 +316,10 @@ __global__ __launch_bounds__(256, 2) void ftm_update_forward_kernel(std::conditi
         wn.y = adam_update_fused(w[u].y, v.y, mo[u].y, vv[u].y, gs, bc, a.beta1, a.beta2, a.eps, a.wd);
         wn.z = adam_update_fused(w[u].z, v.z, mo[u].z, vv[u].z, gs, bc, a.beta1, a.beta2, a.eps, a.wd);
         wn.w = adam_update_fused(w[u].w, v.w, mo[u].w, vv[u].w, gs, bc, a.beta1, a.beta2, a.eps, a.wd);
+        if constexpr (kClip) {
+          wn.x = clip_weight(wn.x, a.wclip); wn.y = clip_weight(wn.y, a.wclip);
+          wn.z = clip_weight(wn.z, a.wclip); wn.w = clip_weight(wn.w, a.wclip);
+        }
 #ifdef NNUE_ABLATIONS
         if (!(a.abl & 2))
 #endif
@@ -332,7 +341,11 @@ __global__ __launch_bounds__(256, 2) void ftm_update_forward_kernel(std::conditi
         g.x = fmaf(a.mom, mo[u].x, g.x); g.y = fmaf(a.mom, mo[u].y, g.y);
         g.z = fmaf(a.mom, mo[u].z, g.z); g.w = fmaf(a.mom, mo[u].w, g.w);
       }
-      const float4 wn = make_float4(w[u].x - lr * g.x, w[u].y - lr * g.y, w[u].z - lr * g.z, w[u].w - lr * g.w);
+      float4 wn = make_float4(w[u].x - lr * g.x, w[u].y - lr * g.y, w[u].z - lr * g.z, w[u].w - lr * g.w);
+      if constexpr (kClip) {
+        wn.x = clip_weight(wn.x, a.wclip); wn.y = clip_weight(wn.y, a.wclip);
+        wn.z = clip_weight(wn.z, a.wclip); wn.w = clip_weight(wn.w, a.wclip);
+      }
 #ifdef NNUE_ABLATIONS
       if (!(a.abl & 2))
 #endif

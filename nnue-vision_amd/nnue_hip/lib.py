@@ -214,6 +214,26 @@ SIGNATURES = {
     "nnue_ftm_backward_weight_update_forward_adam": (_c_int, [_c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p,
                                                               _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_p,
                                                               _c_p, _c_p, _c_int, _c_p, _c_p, _c_p, _c_i64, _c_p]),
+    # the weight clip (include/nnue_hip.h, "weight clip"): the optimizer entry points with the clamp in their update launch
+    "nnue_sgd_step_clip": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_f, _c_f, _c_f, _c_f, _c_f, _c_int, _c_p, _c_p, _c_i64, _c_p, _c_int,
+                                    _c_int, _c_p, _c_p, _c_p, _c_int, _c_i64, _c_i64, _c_p, _c_int, _c_p, _c_f, _c_p, _c_int, _c_p]),
+    "nnue_adam_step_clip": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f,
+                                     _c_p, _c_p, _c_i64, _c_p, _c_f, _c_p, _c_int, _c_p]),
+    "nnue_adam_step_ext_clip": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f,
+                                         _c_p, _c_p, _c_i64, _c_p, _c_int, _c_i64, _c_i64, _c_p, _c_int, _c_p, _c_f, _c_p, _c_int, _c_p]),
+    "nnue_ftm_backward_weight_update_clip": (_c_int, [_c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p, _c_f, _c_f, _c_f, _c_f,
+                                                      _c_int, _c_f, _c_p, _c_p]),
+    "nnue_ftm_backward_weight_update_forward_clip": (_c_int, [_c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p, _c_f, _c_f, _c_f,
+                                                              _c_f, _c_int, _c_f, _c_p, _c_p, _c_p, _c_int, _c_p, _c_p, _c_p, _c_i64, _c_p]),
+    "nnue_ftm_backward_weight_update_adam_clip": (_c_int, [_c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p,
+                                                           _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_p, _c_p]),
+    "nnue_ftm_backward_weight_update_forward_adam_clip": (_c_int, [_c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p,
+                                                                   _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_p,
+                                                                   _c_p, _c_p, _c_int, _c_p, _c_p, _c_p, _c_i64, _c_p]),
+    "nnue_multi_sgd_step_clip": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p, _c_f, _c_p, _c_p, _c_i64, _c_p,
+                                          _c_p]),
+    "nnue_multi_adam_step_clip": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_f, _c_p,
+                                           _c_p, _c_i64, _c_p, _c_p]),
 }
 
 _lib: Optional[ctypes.CDLL] = None
@@ -285,7 +305,12 @@ class time_calls:
 
 
 # entry points timed under the name of the call they replace (a caller's timer keys name the plain forms)
-_TIMED_AS = {"nnue_ftm_conv_binarize_planes": "nnue_ftm_conv_binarize", "nnue_ftm_forward_l1_planes": "nnue_ftm_forward_l1",
+_TIMED_AS = {"nnue_sgd_step_clip": "nnue_sgd_step", "nnue_adam_step_clip": "nnue_adam_step", "nnue_adam_step_ext_clip": "nnue_adam_step_ext",
+             "nnue_ftm_backward_weight_update_clip": "nnue_ftm_backward_weight_update",
+             "nnue_ftm_backward_weight_update_forward_clip": "nnue_ftm_backward_weight_update_forward",
+             "nnue_ftm_backward_weight_update_adam_clip": "nnue_ftm_backward_weight_update_adam",
+             "nnue_ftm_backward_weight_update_forward_adam_clip": "nnue_ftm_backward_weight_update_forward_adam",
+             "nnue_ftm_conv_binarize_planes": "nnue_ftm_conv_binarize", "nnue_ftm_forward_l1_planes": "nnue_ftm_forward_l1",
              "nnue_ftm_conv_binarize_value_planes": "nnue_ftm_conv_binarize", "nnue_ftm_backward_planes": "nnue_ftm_backward",
              "nnue_classifier_train_step_soft": "nnue_classifier_train_step",
              "nnue_classifier_train_step_soft_bucketed": "nnue_classifier_train_step_bucketed"}
@@ -1393,10 +1418,16 @@ def ftm_backward_tail_rows(d_out: torch.Tensor, fm: "FeatureMatrix", d_weight: t
           d_bias.data_ptr(), _stream(d_out))
 
 
-def _ftm_weight_update(name: str, d_out, fm, weight, coef, lr_dev, scalars, momentum_rows=None, adam=None, nxt=None) -> None:
+def _ftm_weight_update(name: str, d_out, fm, weight, coef, lr_dev, scalars, momentum_rows=None, adam=None, nxt=None,
+                       weight_clip: float = 0.0) -> None:
     """The one body of ftm_backward_weight_update{,_forward}{,_adam}; `name`: the public function, "nnue_" + name its C entry
     point.  scalars: the optimizer's C arguments between the state pointers and lr_dev; adam = (exp_avg_rows, exp_avg_sq_rows,
-    step_counter), else SGD on momentum_rows; nxt = (fm_next, bias, out_next): the pass also forms that map's forward."""
+    step_counter), else SGD on momentum_rows; nxt = (fm_next, bias, out_next): the pass also forms that map's forward.
+    weight_clip > 0: the ``_clip`` sibling of the entry point, which clamps the new table elements (include/nnue_hip.h, "weight
+    clip"); 0 is the plain entry point."""
+    weight_clip = checked_weight_clip(weight_clip)
+    if weight_clip > 0.0:
+        name, scalars = name + "_clip", (*scalars, weight_clip)
     d_out = _need(d_out, torch.float32, "d_out")
     b, l1 = d_out.shape
     weight = _need(weight, torch.float32, "input.weight", (fm.num_rows, l1))
@@ -1425,10 +1456,10 @@ def _ftm_weight_update(name: str, d_out, fm, weight, coef, lr_dev, scalars, mome
 
 def ftm_backward_weight_update(d_out: torch.Tensor, fm: "FeatureMatrix", weight: torch.Tensor, momentum_rows: Optional[torch.Tensor],
                                coef: torch.Tensor, lr: float, momentum: float, weight_decay: float, grad_scale: float,
-                               first_step: bool, lr_dev: Optional[torch.Tensor] = None) -> None:
+                               first_step: bool, lr_dev: Optional[torch.Tensor] = None, weight_clip: float = 0.0) -> None:
     """weight rows [0, direct) <- SGD update with d_W = A^T d_out formed and consumed in the product's epilogue.
-    lr_dev (device float32 scalar): the learning rate is read from it instead of `lr`."""
-    _ftm_weight_update("ftm_backward_weight_update", d_out, fm, weight, coef, lr_dev, momentum_rows=momentum_rows,
+    lr_dev (device float32 scalar): the learning rate is read from it instead of `lr`.  weight_clip: see _ftm_weight_update."""
+    _ftm_weight_update("ftm_backward_weight_update", d_out, fm, weight, coef, lr_dev, momentum_rows=momentum_rows, weight_clip=weight_clip,
                        scalars=(float(lr), float(momentum), float(weight_decay), float(grad_scale), int(bool(first_step))))
 
 
@@ -1441,32 +1472,36 @@ def ftm_update_forward_supported(batch: int, num_rows: int, positions: int, l1: 
 def ftm_backward_weight_update_forward(d_out: torch.Tensor, fm: "FeatureMatrix", weight: torch.Tensor,
                                        momentum_rows: Optional[torch.Tensor], coef: torch.Tensor, lr: float, momentum: float,
                                        weight_decay: float, grad_scale: float, first_step: bool, fm_next: "FeatureMatrix",
-                                       bias: torch.Tensor, out_next: torch.Tensor, lr_dev: Optional[torch.Tensor] = None) -> None:
+                                       bias: torch.Tensor, out_next: torch.Tensor, lr_dev: Optional[torch.Tensor] = None,
+                                       weight_clip: float = 0.0) -> None:
     """ftm_backward_weight_update(d_out, fm, ...) and ftm_forward(weight, bias, fm_next, out=out_next) in one pass over the
-    table (bitwise the two calls).  `bias` and table row F-1 must already be updated (sgd_step)."""
-    _ftm_weight_update("ftm_backward_weight_update_forward", d_out, fm, weight, coef, lr_dev, momentum_rows=momentum_rows,
+    table (bitwise the two calls).  `bias` and table row F-1 must already be updated (sgd_step).  weight_clip: the forward
+    contracts the clamped table (see _ftm_weight_update)."""
+    _ftm_weight_update("ftm_backward_weight_update_forward", d_out, fm, weight, coef, lr_dev, momentum_rows=momentum_rows, weight_clip=weight_clip,
                        nxt=(fm_next, bias, out_next), scalars=(float(lr), float(momentum), float(weight_decay), float(grad_scale), int(bool(first_step))))
 
 
 def ftm_backward_weight_update_adam(d_out: torch.Tensor, fm: "FeatureMatrix", weight: torch.Tensor, exp_avg_rows: torch.Tensor,
                                     exp_avg_sq_rows: torch.Tensor, coef: torch.Tensor, step_counter: torch.Tensor, lr: float,
                                     betas, eps: float, weight_decay: float, grad_scale: float,
-                                    lr_dev: Optional[torch.Tensor] = None) -> None:
+                                    lr_dev: Optional[torch.Tensor] = None, weight_clip: float = 0.0) -> None:
     """weight rows [0, direct) and the matching moment rows <- Adam update with d_W = A^T d_out formed and consumed in the
     product's epilogue.  ``step_counter`` (device int32) is read, not advanced: adam_step(ext_applied_elsewhere=True) of the
     same step advances it and leaves ``coef``."""
     _ftm_weight_update("ftm_backward_weight_update_adam", d_out, fm, weight, coef, lr_dev, adam=(exp_avg_rows, exp_avg_sq_rows, step_counter),
+                       weight_clip=weight_clip,
                        scalars=(float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay), float(grad_scale)))
 
 
 def ftm_backward_weight_update_forward_adam(d_out: torch.Tensor, fm: "FeatureMatrix", weight: torch.Tensor, exp_avg_rows: torch.Tensor,
                                             exp_avg_sq_rows: torch.Tensor, coef: torch.Tensor, step_counter: torch.Tensor, lr: float,
                                             betas, eps: float, weight_decay: float, grad_scale: float, fm_next: "FeatureMatrix",
-                                            bias: torch.Tensor, out_next: torch.Tensor, lr_dev: Optional[torch.Tensor] = None) -> None:
+                                            bias: torch.Tensor, out_next: torch.Tensor, lr_dev: Optional[torch.Tensor] = None,
+                                            weight_clip: float = 0.0) -> None:
     """ftm_backward_weight_update_adam(d_out, fm, ...) and ftm_forward(weight, bias, fm_next, out=out_next) in one pass over the
     table (bitwise the two calls).  `bias` and table row F-1 must already be updated (adam_step)."""
     _ftm_weight_update("ftm_backward_weight_update_forward_adam", d_out, fm, weight, coef, lr_dev,
-                       adam=(exp_avg_rows, exp_avg_sq_rows, step_counter), nxt=(fm_next, bias, out_next),
+                       adam=(exp_avg_rows, exp_avg_sq_rows, step_counter), nxt=(fm_next, bias, out_next), weight_clip=weight_clip,
                        scalars=(float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay), float(grad_scale)))
 
 
@@ -1509,14 +1544,48 @@ class FactorExchange:
               _stream(flat_grads))
 
 
+def checked_weight_clip(value) -> float:
+    """The weight clip's bound as a float: 0 (off) or a finite positive number; ValueError otherwise."""
+    value = float(value)
+    if not 0.0 <= value < float("inf"):  # (NaN fails the comparison)
+        raise ValueError(f"weight_clip = {value} must be finite and not negative")
+    return value
+
+
+class WeightClip:
+    """The weight clip of a flat buffer (include/nnue_hip.h, "weight clip"): the bound and up to four half-open element ranges
+    [(lo, hi), ...] of the buffer, as sgd_step / adam_step take it (``clip=``).  ``array`` is the host array the C call reads;
+    a recorded plan holds this object's array, which keeps it alive."""
+
+    def __init__(self, bound: float, ranges):
+        self.bound = checked_weight_clip(bound)
+        self.ranges = [(int(lo), int(hi)) for lo, hi in ranges if int(lo) < int(hi)]
+        if len(self.ranges) > 4 or any(lo < 0 for lo, _ in self.ranges):
+            raise ValueError(f"a weight clip takes at most four ranges of non-negative indices, got {self.ranges}")
+        self.array = (ctypes.c_int64 * (2 * max(1, len(self.ranges))))(*[x for r in self.ranges for x in r])
+
+    @property
+    def on(self) -> bool:
+        return self.bound > 0.0 and bool(self.ranges)
+
+    def window(self, lo: int, hi: int) -> "WeightClip":
+        """The clip of the slice [lo, hi) of the buffer: the ranges intersected with it, in the slice's own indices (the sharded
+        update's call covers one shard)."""
+        return WeightClip(self.bound, [(max(a, lo) - lo, min(b, hi) - lo) for a, b in self.ranges])
+
+    def args(self):
+        return (self.bound, self.array, len(self.ranges))
+
+
 def sgd_step(params: torch.Tensor, grads: torch.Tensor, momentum_buf: Optional[torch.Tensor], lr: float,
              momentum: float, weight_decay: float, max_norm: float, grad_scale: float, first_step: bool,
              norm_out: Optional[torch.Tensor], scratch: torch.Tensor, ste=None, ext=None,
              coef_out: Optional[torch.Tensor] = None, ext_applied_elsewhere: bool = False,
-             lr_dev: Optional[torch.Tensor] = None) -> None:
+             lr_dev: Optional[torch.Tensor] = None, clip: Optional[WeightClip] = None) -> None:
     """ste = (partial scratch of ste_conv_backward(stages=1), chunks, fps, d_thr, d_weight): the deferred second stage
     runs inside the norm launch; d_thr / d_weight must be the first elements of `grads`.  lr_dev (device float32 scalar): the
-    learning rate is read from it instead of `lr` (changes between steps need no re-recording / re-capture)."""
+    learning rate is read from it instead of `lr` (changes between steps need no re-recording / re-capture).  clip (a
+    WeightClip that is ``on``): nnue_sgd_step_clip, which clamps the updated elements of its ranges; None or off: nnue_sgd_step."""
     params = _need(params, torch.float32, "flat params")
     grads = _need(grads, torch.float32, "flat grads", tuple(params.shape))
     if momentum_buf is not None:
@@ -1528,10 +1597,11 @@ def sgd_step(params: torch.Tensor, grads: torch.Tensor, momentum_buf: Optional[t
         ste_args = (None, 0, 0, None, None)
     # ext = (partials, lo, hi): a producer's sums of squares for grads[lo:hi] (e.g. ftm_backward(sq_partial=...))
     ext_args = (ext[0].data_ptr(), ext[0].numel(), int(ext[1]), int(ext[2])) if ext is not None else (None, 0, 0, 0)
-    _call("nnue_sgd_step", params.data_ptr(), grads.data_ptr(), _ptr(momentum_buf), params.numel(), float(lr),
+    clipped = clip is not None and clip.on
+    _call("nnue_sgd_step_clip" if clipped else "nnue_sgd_step", params.data_ptr(), grads.data_ptr(), _ptr(momentum_buf), params.numel(), float(lr),
           float(momentum), float(weight_decay), float(max_norm), float(grad_scale), int(bool(first_step)),
           _ptr(norm_out), scratch.data_ptr(), scratch.numel(), *ste_args, *ext_args, _ptr(coef_out), int(bool(ext_applied_elsewhere)),
-          _ptr(lr_dev), _stream(params))
+          _ptr(lr_dev), *(clip.args() if clipped else ()), _stream(params))
 
 
 def lr_schedule_step(table: torch.Tensor, position: torch.Tensor, lr_out: torch.Tensor) -> None:
@@ -1549,9 +1619,11 @@ def adam_step(params: torch.Tensor, grads: torch.Tensor, exp_avg: torch.Tensor, 
               step_counter: torch.Tensor, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
               max_norm: float = 0.0, grad_scale: float = 1.0, norm_out: Optional[torch.Tensor] = None,
               scratch: Optional[torch.Tensor] = None, lr_dev: Optional[torch.Tensor] = None, ext=None,
-              coef_out: Optional[torch.Tensor] = None, ext_applied_elsewhere: bool = False) -> None:
+              coef_out: Optional[torch.Tensor] = None, ext_applied_elsewhere: bool = False,
+              clip: Optional[WeightClip] = None) -> None:
     """ext / coef_out / ext_applied_elsewhere as in sgd_step (nnue_adam_step_ext): ext = (partials, lo, hi), a producer's sums of
-    squares for grads[lo:hi]; with ext_applied_elsewhere that range of params and moments is left to the producer."""
+    squares for grads[lo:hi]; with ext_applied_elsewhere that range of params and moments is left to the producer.  clip as in
+    sgd_step: the ``_clip`` sibling of whichever of the two entry points the call takes."""
     params = _need(params, torch.float32, "flat params")
     shape = tuple(params.shape)
     grads = _need(grads, torch.float32, "flat grads", shape)
@@ -1560,16 +1632,18 @@ def adam_step(params: torch.Tensor, grads: torch.Tensor, exp_avg: torch.Tensor, 
     _need(step_counter, torch.int32, "step counter", (1,))
     if scratch is None:
         scratch = torch.empty((sgd_scratch_bytes(params.numel()),), dtype=torch.uint8, device=params.device)
+    clipped = clip is not None and clip.on
+    clip_args = clip.args() if clipped else ()
     if ext is not None or coef_out is not None or ext_applied_elsewhere:
         ext_args = (ext[0].data_ptr(), ext[0].numel(), int(ext[1]), int(ext[2])) if ext is not None else (None, 0, 0, 0)
-        _call("nnue_adam_step_ext", params.data_ptr(), grads.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(),
+        _call("nnue_adam_step_ext_clip" if clipped else "nnue_adam_step_ext", params.data_ptr(), grads.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(),
               step_counter.data_ptr(), params.numel(), float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
               float(max_norm), float(grad_scale), _ptr(norm_out), scratch.data_ptr(), scratch.numel(), *ext_args, _ptr(coef_out),
-              int(bool(ext_applied_elsewhere)), _ptr(lr_dev), _stream(params))
+              int(bool(ext_applied_elsewhere)), _ptr(lr_dev), *clip_args, _stream(params))
         return
-    _call("nnue_adam_step", params.data_ptr(), grads.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(),
+    _call("nnue_adam_step_clip" if clipped else "nnue_adam_step", params.data_ptr(), grads.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(),
           step_counter.data_ptr(), params.numel(), float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
-          float(max_norm), float(grad_scale), _ptr(norm_out), scratch.data_ptr(), scratch.numel(), _ptr(lr_dev), _stream(params))
+          float(max_norm), float(grad_scale), _ptr(norm_out), scratch.data_ptr(), scratch.numel(), _ptr(lr_dev), *clip_args, _stream(params))
 
 
 def load_batch(images_u8: torch.Tensor, labels_all: torch.Tensor, indices: torch.Tensor, augment: bool, seed: int, step: int,

@@ -8,6 +8,10 @@ The reference's inner loop (train.py:359-366) ends in ``clip_grad_norm_`` and ``
     loss.backward()
     optimizer.step()            # clip_grad_norm_ + SGD in two launches; optimizer.grad_norm = the pre-clip norm
 
+``weight_clip`` (a per-group option, 0 = off; the keyword is the groups' default) clamps every parameter of the group to
+[-weight_clip, weight_clip] inside the update launch -- the reference's ``_clip_weights`` (nnue.py:528-539) at 1.0, for a group
+holding ``input.weight`` and the classifier's three weights; the rest goes into a group without it.
+
 They subclass ``torch.optim.SGD`` / ``torch.optim.Adam``: the constructor signature, ``param_groups``, ``zero_grad``,
 hooks, schedulers and the ``state_dict`` format are torch's own, so a checkpoint moves between these and torch's
 optimizers (and ``NnueTrainer.optimizer_state_dict()``) in both directions.  Options the kernels do not implement are
@@ -36,13 +40,13 @@ def _refuse(cond: bool, what: str) -> None:
 class _Table:
     """The host arrays of one segment list, kept between steps and refilled in place (no allocation after the first step)."""
 
-    FIELDS = ("params", "grads", "m", "v", "steps", "counts", "lr", "a", "b", "eps", "wd", "first")
+    FIELDS = ("params", "grads", "m", "v", "steps", "counts", "lr", "a", "b", "eps", "wd", "first", "clip")
 
     def __init__(self, params: List[torch.Tensor]):
         n = self.n = len(params)
         self.params, self.grads, self.m, self.v, self.steps = ((_P * n)() for _ in range(5))
         self.counts = (ctypes.c_int64 * n)(*[p.numel() for p in params])
-        self.lr, self.a, self.b, self.eps, self.wd = ((ctypes.c_float * n)() for _ in range(5))
+        self.lr, self.a, self.b, self.eps, self.wd, self.clip = ((ctypes.c_float * n)() for _ in range(6))
         self.first = (ctypes.c_int32 * n)()
         self.addr = {k: ctypes.addressof(getattr(self, k)) for k in self.FIELDS}
         dev = params[0].device
@@ -61,6 +65,7 @@ class _MultiTensor:
 
     def _setup(self) -> None:
         self.defaults["max_grad_norm"] = self._max_grad_norm
+        self.defaults["weight_clip"] = self._weight_clip
         self.grad_norm: Optional[torch.Tensor] = None  # the pre-clip norm of the last step (a device scalar; None: no clip)
         self._table: Optional[_Table] = None
         self._key = None
@@ -69,6 +74,7 @@ class _MultiTensor:
         param_group.setdefault("max_grad_norm", self._max_grad_norm)
         if param_group["max_grad_norm"] != self._max_grad_norm:
             raise ValueError(_GLOBAL_CLIP)
+        param_group.setdefault("weight_clip", self._weight_clip)
         super().add_param_group(param_group)
         try:
             self._check_group(self.param_groups[-1])
@@ -77,15 +83,18 @@ class _MultiTensor:
             raise
 
     def _check_group(self, g: dict) -> None:
+        g["weight_clip"] = lib.checked_weight_clip(g.get("weight_clip", 0.0))
         _refuse(isinstance(g["lr"], torch.Tensor), "a tensor lr")
         _refuse(isinstance(g["weight_decay"], torch.Tensor), "a tensor weight_decay")
         for k in ("maximize", "fused", "capturable", "differentiable"):
             _refuse(bool(g.get(k)), f"{k}=True")
 
     def load_state_dict(self, state_dict: dict) -> None:
+        own = [g["weight_clip"] for g in self.param_groups]
         super().load_state_dict(state_dict)
-        for g in self.param_groups:  # a torch.optim state_dict has no max_grad_norm: ours stays
+        for g, clip in zip(self.param_groups, own):  # a torch.optim state_dict has no max_grad_norm: ours stays
             g["max_grad_norm"] = self._max_grad_norm
+            g.setdefault("weight_clip", clip)  # (a group option like any other: the dict's value where it has one)
             self._check_group(g)
         self._key = None  # the state tensors were replaced
 
@@ -122,6 +131,9 @@ class _MultiTensor:
         if device.type != "cuda":  # the CPU convenience path: the same formulas in stock torch
             self.grad_norm = torch.nn.utils.clip_grad_norm_([p for p, _ in segs], max_norm, foreach=False) if max_norm > 0 else None
             super().step()
+            for p, g in segs:
+                if g["weight_clip"] > 0:
+                    p.clamp_(-g["weight_clip"], g["weight_clip"])
             return loss
         key = tuple(id(p) for p, _ in segs)
         if key != self._key:  # a new set of parameters with gradients (or new state tensors): new arrays
@@ -133,6 +145,7 @@ class _MultiTensor:
             t.grads[i] = p.grad.data_ptr()
             t.lr[i] = g["lr"]  # read at every step: schedulers work unchanged
             t.wd[i] = g["weight_decay"]
+            t.clip[i] = g["weight_clip"]  # the group's weight clip (0: the segment is not clamped)
         self._fill_state(t, segs)
         norm_out = t.norm.data_ptr() if max_norm > 0 else None
         self._launch(t, max_norm, norm_out, torch.cuda.current_stream(device).cuda_stream)
@@ -154,7 +167,7 @@ class SGD(_MultiTensor, torch.optim.SGD):
 
     def __init__(self, params, lr: float = 1e-3, momentum: float = 0.0, dampening: float = 0.0, weight_decay: float = 0.0,
                  nesterov: bool = False, *, maximize: bool = False, foreach: Optional[bool] = None, differentiable: bool = False,
-                 fused: Optional[bool] = None, max_grad_norm: float = 0.0):
+                 fused: Optional[bool] = None, max_grad_norm: float = 0.0, weight_clip: float = 0.0):
         _refuse(bool(nesterov), "nesterov=True")
         _refuse(dampening != 0, "dampening != 0")
         _refuse(bool(maximize), "maximize=True")
@@ -162,6 +175,7 @@ class SGD(_MultiTensor, torch.optim.SGD):
         _refuse(bool(differentiable), "differentiable=True")
         _refuse(isinstance(lr, torch.Tensor), "a tensor lr")
         self._max_grad_norm = float(max_grad_norm)
+        self._weight_clip = lib.checked_weight_clip(weight_clip)  # the default of a group that does not set its own
         super().__init__(params, lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov,
                          maximize=maximize, foreach=False, differentiable=differentiable, fused=fused)
         self._setup()
@@ -188,6 +202,10 @@ class SGD(_MultiTensor, torch.optim.SGD):
 
     def _launch(self, t: _Table, max_norm: float, norm_out, stream: int) -> None:
         A = t.addr
+        if any(t.clip):
+            lib._call("nnue_multi_sgd_step_clip", A["params"], A["grads"], A["m"], A["counts"], t.n, A["lr"], A["a"], A["wd"], A["first"],
+                      A["clip"], max_norm, norm_out, t.scratch.data_ptr(), t.scratch.numel(), None, stream)
+            return
         lib._call("nnue_multi_sgd_step", A["params"], A["grads"], A["m"], A["counts"], t.n, A["lr"], A["a"], A["wd"], A["first"],
                   max_norm, norm_out, t.scratch.data_ptr(), t.scratch.numel(), None, stream)
 
@@ -201,7 +219,7 @@ class Adam(_MultiTensor, torch.optim.Adam):
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
                  amsgrad: bool = False, *, foreach: Optional[bool] = None, maximize: bool = False, capturable: bool = False,
                  differentiable: bool = False, fused: Optional[bool] = None, decoupled_weight_decay: bool = False,
-                 max_grad_norm: float = 0.0):
+                 max_grad_norm: float = 0.0, weight_clip: float = 0.0):
         _refuse(bool(amsgrad), "amsgrad=True")
         _refuse(bool(decoupled_weight_decay), "decoupled_weight_decay=True")
         _refuse(bool(maximize), "maximize=True")
@@ -211,6 +229,7 @@ class Adam(_MultiTensor, torch.optim.Adam):
         _refuse(isinstance(lr, torch.Tensor), "a tensor lr")
         _refuse(any(isinstance(b, torch.Tensor) for b in betas), "tensor betas")
         self._max_grad_norm = float(max_grad_norm)
+        self._weight_clip = lib.checked_weight_clip(weight_clip)  # the default of a group that does not set its own
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, foreach=False,
                          maximize=maximize, capturable=capturable, differentiable=differentiable, fused=fused,
                          decoupled_weight_decay=decoupled_weight_decay)
@@ -256,6 +275,10 @@ class Adam(_MultiTensor, torch.optim.Adam):
 
     def _launch(self, t: _Table, max_norm: float, norm_out, stream: int) -> None:
         A = t.addr
-        lib._call("nnue_multi_adam_step", A["params"], A["grads"], A["m"], A["v"], A["steps"], A["counts"], t.n, A["lr"], A["a"],
-                  A["b"], A["eps"], A["wd"], max_norm, norm_out, t.scratch.data_ptr(), t.scratch.numel(), None, stream)
+        if any(t.clip):
+            lib._call("nnue_multi_adam_step_clip", A["params"], A["grads"], A["m"], A["v"], A["steps"], A["counts"], t.n, A["lr"], A["a"],
+                      A["b"], A["eps"], A["wd"], A["clip"], max_norm, norm_out, t.scratch.data_ptr(), t.scratch.numel(), None, stream)
+        else:
+            lib._call("nnue_multi_adam_step", A["params"], A["grads"], A["m"], A["v"], A["steps"], A["counts"], t.n, A["lr"], A["a"],
+                      A["b"], A["eps"], A["wd"], max_norm, norm_out, t.scratch.data_ptr(), t.scratch.numel(), None, stream)
         torch._foreach_add_(self._host_steps, 1.0)  # torch's own count, on the host (what state_dict() hands on)

@@ -27,6 +27,9 @@ NNUE model, minus the parts that are out of scope here (W&B, RunPod, dataset dow
   (``dataset_from_config`` reads the two alphas) -- with ``two_labels``.  Only the training trainer and the training dataset
   see them: ``evaluate_model`` on the train, validation and test loaders stays plain cross-entropy on unmixed batches, so the
   reported losses stay comparable across runs.
+* ``weight_clip`` (optional config attribute, 0 by default; a build extension): the trainer clamps the table and the classifier's
+  weights to [-weight_clip, weight_clip] inside every optimizer update.  1.0 is what the export clamps to (``_clip_weights``,
+  nnue.py:528-539): the metrics of a run trained with it describe the network ``serialize_model`` writes.
 * ``save_last`` / ``resume_from`` (arguments, or the config attributes of those names; off by default): after each epoch's
   evaluations ``last.ckpt`` is written beside ``best-model.ckpt`` -- the five reference keys plus ``"run_state"`` (the
   trainer's state, the epoch and step counts, best-so-far values, the history, the GPU dataset's draw counter and the
@@ -98,6 +101,12 @@ def build_model(config, device):
                      clip_activations=getattr(config, "clip_activations", None)).to(device)
 
 
+def config_weight_clip(config) -> float:
+    """The config's ``weight_clip`` (0 where it has none), checked as the trainer checks it: ValueError for a negative, NaN or
+    infinite value."""
+    return lib.checked_weight_clip(getattr(config, "weight_clip", 0.0))
+
+
 def run_training(config, train_loader: Iterable, val_loader: Iterable, test_loader: Optional[Iterable] = None, model=None,
                  checkpoint_dir=None, log: Callable[[str], None] = print, use_graph: bool = True,
                  compiled_eval: Optional[bool] = None, save_last: Optional[bool] = None, resume_from=None,
@@ -108,6 +117,7 @@ def run_training(config, train_loader: Iterable, val_loader: Iterable, test_load
     if resume_from is None:
         resume_from = getattr(config, "resume_from", None)
     optimizer_type = "sgd" if config.optimizer_type == "sgd" else "adam"
+    weight_clip = config_weight_clip(config)
     resumed = _read_resume_file(resume_from, config, optimizer_type) if resume_from else None
     if compiled_eval is None:
         compiled_eval = bool(getattr(config, "compiled_eval", False))
@@ -136,7 +146,8 @@ def run_training(config, train_loader: Iterable, val_loader: Iterable, test_load
                          "input_pipeline.dataset_from_config (a GpuLoader)")
     trainer = NnueTrainer(model, batch, hw, lr=float(config.learning_rate), weight_decay=float(config.weight_decay),
                           max_grad_norm=clip, use_graph=use_graph, input_slots=8 if in_place else 1,
-                          label_smoothing=float(getattr(config, "label_smoothing", 0.0)), two_labels=mixes, **opt)
+                          label_smoothing=float(getattr(config, "label_smoothing", 0.0)), two_labels=mixes, weight_clip=weight_clip,
+                          **opt)
     if lr_schedule is None and getattr(config, "lr_schedule", False):
         lr_schedule = LrSchedule.from_config(config, len(train_loader))
     if isinstance(lr_schedule, LrSchedule):

@@ -49,6 +49,19 @@ def _checked_label_smoothing(value) -> float:
     return value
 
 
+# The tensors NNUE._clip_weights clamps (nnue.py:528-539): the FeatureTransformer's table and the classifier's Linear weights (for
+# num_ls_buckets > 1 the stacked [K, out, in] BucketedLinear weights).  Never the conv weights, the thresholds or a bias.
+CLIPPED = ("input.weight", "classifier.classifier.0.weight", "classifier.classifier.2.weight", "classifier.classifier.4.weight")
+
+
+def clip_ranges(layout: "FlatLayout"):
+    """The clipped tensors as half-open element ranges of the layout's flat buffers, each extended to the next tensor's start
+    (the last one to the buffers' end): the zero padding behind a tensor is clamped with it -- a no-op -- and every boundary is a
+    multiple of the layout's alignment, so the float4 kernels see no ragged case."""
+    ends = list(layout.offsets[1:]) + [layout.count]
+    return [(layout.offsets[i], ends[i]) for i, k in enumerate(layout.names) if k in CLIPPED]
+
+
 def _checked_schedule(values, position) -> Tuple[torch.Tensor, int]:
     """(values as a float32 CPU vector, position) of a per-step schedule, or ValueError."""
     values = torch.as_tensor(values).detach().to(device="cpu", dtype=torch.float32).contiguous()
@@ -181,18 +194,22 @@ class NnueTrainer:
     def __init__(self, model, batch_size: int, image_hw: Tuple[int, int], lr: float, momentum: float = 0.0,
                  weight_decay: float = 0.0, max_grad_norm: float = 0.0, group=None, use_graph: bool = True,
                  input_slots: int = 1, optimizer: str = "sgd", betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
-                 ft_path: Optional[str] = None, label_smoothing: float = 0.0, two_labels: bool = False):
+                 ft_path: Optional[str] = None, label_smoothing: float = 0.0, two_labels: bool = False, weight_clip: float = 0.0):
         """ft_path: the FeatureTransformer kernel family, as lib.ft_path's ``mode`` (None: NNUE_FT_PATH decides).
         label_smoothing (F.cross_entropy's, in [0, 1)) and two_labels (a second label and a weight per sample: mixup, CutMix) make
         the classifier step train on soft targets (include/nnue_hip.h, "soft targets"); with both at their defaults the step is
-        the plain one, launch for launch."""
+        the plain one, launch for launch.
+        weight_clip (0: off; 1.0 is the reference's _clip_weights, nnue.py:528-539): after every optimizer update the table and the
+        classifier's weights are clamped to [-weight_clip, weight_clip] inside the launches that apply the update (include/nnue_hip.h,
+        "weight clip") -- bit for bit the plain step followed by ``clamp_`` on those four tensors, in every step mode."""
         self._label_smoothing, self.two_labels = _checked_label_smoothing(label_smoothing), bool(two_labels)
+        weight_clip = lib.checked_weight_clip(weight_clip)
         lib.load()
         p0 = next(model.parameters())
         if not p0.is_cuda:
             raise lib.NnueHipError("NnueTrainer needs the model on the GPU (no CPU fallback)")
         self.model, self.dev = model, p0.device
-        self._hyper = dict(lr=lr, momentum=momentum, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
+        self._hyper = dict(lr=lr, momentum=momentum, weight_decay=weight_decay, max_grad_norm=max_grad_norm, weight_clip=weight_clip)
         if optimizer not in ("sgd", "adam"):
             raise ValueError(f"optimizer must be 'sgd' or 'adam', got {optimizer!r}")
         self.optimizer, self.betas, self.eps = optimizer, betas, eps
@@ -226,6 +243,7 @@ class NnueTrainer:
         # gradient buckets: [threshold, conv weight] come last out of the backward and lead the flat buffer
         assert self.layout.names[:2] == ["visual_threshold", "conv.weight"]
         self.bucket_split = self.layout.offsets[2]
+        self._clip_ranges = clip_ranges(self.layout)  # (built once; the bound is a constant of the update plans)
         for k, prm in model.named_parameters():
             if k not in SKIP:
                 prm.data = self.p[k]
@@ -334,7 +352,7 @@ class NnueTrainer:
     # ------------------------------------------------------------------ hyper-parameters
     # The learning rate is a device scalar (``lr_dev``) every optimizer kernel reads: changing it costs one fill and keeps
     # every plan and graph -- per-step schedules are fine; with ranks every rank must set the same value.  Momentum, weight
-    # decay and the clip norm are constants of the recorded update plan (and of every graph captured from it): changing one
+    # decay, the clip norm and the weight clip are constants of the recorded update plan (and of every graph captured from it): changing one
     # re-records that plan and drops the graphs that contain it; the local (forward/backward) plan is untouched.
     # ``trainer.lr = x`` and ``trainer.set_lr(x)`` are the same thing.
     def _set_hyper(self, key: str, value: float) -> None:
@@ -344,6 +362,8 @@ class NnueTrainer:
             self._hyper[key] = value
             self.lr_dev.fill_(value)
             return
+        if key == "weight_clip":
+            value = lib.checked_weight_clip(value)
         if key == "momentum" and self.optimizer == "sgd" and bool(value) != (self.flat_momentum is not None):
             raise ValueError("momentum cannot be switched on or off after construction (the buffer layout is fixed)")
         self._hyper[key] = value
@@ -373,6 +393,15 @@ class NnueTrainer:
     momentum = property(lambda self: self._hyper["momentum"], lambda self, v: self._set_hyper("momentum", float(v)))
     weight_decay = property(lambda self: self._hyper["weight_decay"], lambda self, v: self._set_hyper("weight_decay", float(v)))
     max_grad_norm = property(lambda self: self._hyper["max_grad_norm"], lambda self, v: self._set_hyper("max_grad_norm", float(v)))
+    weight_clip = property(lambda self: self._hyper["weight_clip"], lambda self, v: self._set_hyper("weight_clip", float(v)))
+
+    def _flat_clip(self, lo: int = 0, hi: Optional[int] = None) -> Optional[lib.WeightClip]:
+        """The weight clip as the flat optimizer calls take it, or None when it is off; [lo, hi): the slice of the flat buffers
+        the call covers (the sharded update's shard)."""
+        if not self.weight_clip:
+            return None
+        clip = lib.WeightClip(self.weight_clip, self._clip_ranges)
+        return clip if hi is None else clip.window(lo, hi)
 
     # Label smoothing is a constant of the recorded LOCAL plan (an argument of the classifier step): changing it re-records that
     # plan and drops every graph of the local step; the update plans are untouched.
@@ -543,16 +572,17 @@ class NnueTrainer:
         self._lr_tick()
         ext = (self.sq_partial, *self.mode.sq_range) if self.mode.sq != "none" else None
         elsewhere = self.mode.sq == "gram"
+        clip = self._flat_clip()  # (the table rows left to _table_update are clamped there)
         if self.optimizer == "adam":
             lib.adam_step(self.flat_params, self.flat_grads, self.flat_exp_avg, self.flat_exp_avg_sq, self.adam_step_count,
                           self.lr, self.betas, self.eps, self.weight_decay, self.max_grad_norm, scale, self.grad_norm,
-                          self.sgd_scratch, lr_dev=self.lr_dev, ext=ext, coef_out=self.clip_coef, ext_applied_elsewhere=elsewhere)
+                          self.sgd_scratch, lr_dev=self.lr_dev, ext=ext, coef_out=self.clip_coef, ext_applied_elsewhere=elsewhere, clip=clip)
             return
         ste = ((self.ste_scratch, self.mode.ste_chunks, self.fps, self.g["visual_threshold"], self.g["conv.weight"])
                if self.mode.defer_ste else None)
         lib.sgd_step(self.flat_params, self.flat_grads, self.flat_momentum, self.lr, self.momentum, self.weight_decay,
                      self.max_grad_norm, scale, first, self.grad_norm, self.sgd_scratch, ste=ste, ext=ext,
-                     coef_out=self.clip_coef, ext_applied_elsewhere=elsewhere, lr_dev=self.lr_dev)
+                     coef_out=self.clip_coef, ext_applied_elsewhere=elsewhere, lr_dev=self.lr_dev, clip=clip)
 
     def _table_update(self, first: bool, scale: float, d_ft: torch.Tensor, fm, nxt=None) -> None:
         """The product d_W = A^T d_ft (A: map `fm`) with the table's update in its epilogue, after _small_update: SGD on the
@@ -568,7 +598,7 @@ class NnueTrainer:
             fn = lib.ftm_backward_weight_update if nxt is None else lib.ftm_backward_weight_update_forward
             mom = self.flat_momentum[lo:hi] if self.flat_momentum is not None else None
             opt = (mom, self.clip_coef, self.lr, self.momentum, self.weight_decay, scale, first)
-        fn(d_ft, fm, self.p["input.weight"], *opt, *forward, lr_dev=self.lr_dev)
+        fn(d_ft, fm, self.p["input.weight"], *opt, *forward, lr_dev=self.lr_dev, weight_clip=self.weight_clip)
 
     def _next_map(self, slot: int, nxt) -> None:
         """conv + {0,1} map of input slot `slot` into map `nxt`, between the two halves of an update that forms the next step's
@@ -609,8 +639,10 @@ class NnueTrainer:
         dp.all_gather(self.all_partials, self.local_partials)  # rank-major, fixed order: every rank forms the identical norm
         mom = dp.shard_of(self.flat_momentum) if self.flat_momentum is not None else None
         self._lr_tick()
+        per = self.grad_shard.numel()
         lib.sgd_step(dp.shard_of(self.flat_params), self.grad_shard, mom, self.lr, self.momentum, self.weight_decay, self.max_grad_norm,
-                     scale, first, self.grad_norm, self.sgd_scratch, ext=(self.all_partials, 0, self.grad_shard.numel()), lr_dev=self.lr_dev)
+                     scale, first, self.grad_norm, self.sgd_scratch, ext=(self.all_partials, 0, per), lr_dev=self.lr_dev,
+                     clip=self._flat_clip(dp.rank * per, (dp.rank + 1) * per))
         dp.all_gather(self.flat_params, dp.shard_of(self.flat_params))
 
     def _ranks_agree(self, ok: bool) -> bool:
@@ -969,7 +1001,7 @@ class NnueTrainer:
             schedule = {"values": self._lr_values.clone(), "position": int(self.lr_position)}
         return {"version": 1, "optimizer_type": self.optimizer, "optimizer": self.optimizer_state_dict(),
                 "steps_done": int(self.steps_done), "lr": float(self._hyper["lr"]), "lr_schedule": schedule,
-                "label_smoothing": float(self._label_smoothing)}
+                "label_smoothing": float(self._label_smoothing), "weight_clip": float(self.weight_clip)}
 
     def _checked_optimizer_state(self, sd: dict, steps_done: int):
         """The flat-buffer sources of a torch optimizer state dict, {buffer name: {parameter name: tensor}}, after checking
@@ -1029,8 +1061,8 @@ class NnueTrainer:
 
     def load_state_dict(self, sd: dict) -> None:
         """state_dict()'s counterpart, on a fresh trainer or on a used one between steps.  Validates first (optimizer type,
-        presence of momentum, every tensor's shape against the layout, the label smoothing the state was trained with -- a state
-        without the key counts as 0; ValueError, nothing changed), then copies in place: the
+        presence of momentum, every tensor's shape against the layout, the label smoothing and the weight clip the state was trained
+        with -- a state without either key counts as 0; ValueError, nothing changed), then copies in place: the
         momentum or both moments into the flat buffers, Adam's step into adam_step_count, the rate into lr_dev, the schedule's
         values and position into lr_table / lr_pos / lr_position, and steps_done.  No buffer is re-bound -- recorded plans and
         captured graphs hold raw pointers and stay valid; only a schedule of another length than the attached one (or a
@@ -1051,6 +1083,9 @@ class NnueTrainer:
         if float(sd.get("label_smoothing", 0.0)) != self._label_smoothing:  # (a state from before the key existed: 0)
             raise ValueError(f"the state was trained with label_smoothing = {float(sd.get('label_smoothing', 0.0))}, "
                              f"this trainer's is {self._label_smoothing}")
+        if float(sd.get("weight_clip", 0.0)) != self.weight_clip:  # (a state from before the key existed: 0)
+            raise ValueError(f"the state was trained with weight_clip = {float(sd.get('weight_clip', 0.0))}, "
+                             f"this trainer's is {self.weight_clip}")
         # ---- validated: from here on only in-place copies
         self._apply_optimizer_state(sources, steps_done)
         if schedule is None:
