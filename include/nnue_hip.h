@@ -540,7 +540,20 @@ int nnue_classifier_train_step_bucketed(const float* x, int pairwise,
  * loss is non-negative and each mx - z is formed before anything is summed (the form of the plain loss), so it stays
  * accurate with logits near 1e4.  A sample counts iff a is in [0, C) and (lam == 1 or a2 is in [0, C)); otherwise its
  * loss is 0 and its gradient row is 0 (the padding rule of the plain kernels; -1 pads a short batch).  The mean is over
- * B, summed in sample order.  With eps = 0, lam = 1 the values are those of the plain entry points. */
+ * B, summed in sample order.  With eps = 0, lam = 1 the values are those of the plain entry points.
+ *
+ * Distillation (the teacher arm; knowledge distillation in Hinton's form, (1-alpha) CE + alpha T^2 KL(q || pT)): beside
+ * the soft target a row of teacher logits u = teacher[b] (float32 [B][C], row stride C, finite) per sample, and one weight
+ * alpha in [0, 1] and one temperature T > 0 per call.  With mu = max_c u_c, sT = sum_c exp((z_c - mx)/T) and
+ * sU = sum_c exp((u_c - mu)/T):
+ *     q_c       = exp((u_c - mu)/T) / sU           (the teacher at temperature T)
+ *     pT_c      = exp((z_c - mx)/T) / sT           (the student at temperature T; max_c z_c/T = mx/T: no second maximum)
+ *     KL_b      = log sT - log sU + (1/T) sum_c q_c ((mx - z_c) - (mu - u_c))        ( = sum_c q_c (log q_c - log pT_c) )
+ *     loss_b    = (1-alpha) L_soft_b + alpha T^2 KL_b                   (L_soft_b: the loss_b above)
+ *     d_logit_c = ((1-alpha) (exp(z_c - mx)/se - t_c) + alpha T (pT_c - q_c)) grad_scale / B
+ * Every mx - z and mu - u is formed before anything is summed.  A sample counts iff the rule above says so; one that does
+ * not has loss 0 and a zero gradient row exactly, whatever its teacher row holds (NaN included).  alpha == 0: teacher may
+ * be NULL and is not read; the call IS the soft call (the same launches, the same bits). */
 
 /* nnue_classifier_train_step / _bucketed (nnue.py:660-669, :728-734 + compute_loss, train.py:250-254, and their autograd)
  * on the soft targets above: the same phases, plan, scratch layout, refusals and launches, with the SOFT arm of the
@@ -570,6 +583,38 @@ int nnue_classifier_train_step_soft_bucketed(const float* x, int pairwise,
                                              void* scratch, int64_t scratch_bytes, int phases,
                                              const int64_t* labels_b, const float* lam, float eps,
                                              const nnue_buckets* buckets, nnue_stream_t stream);
+
+/* nnue_classifier_train_step_soft (nnue.py:660-669, :728-734 + compute_loss, train.py:250-254, and their autograd) with the
+ * teacher arm defined under "soft targets": the same phases, plan, scratch layout, refusals and launches with the DISTILL arm
+ * of the per-sample tail; it reads B*C*4 bytes more.  h1, h2 and logits are bitwise the plain call's.  Three more refusals,
+ * NNUE_E_ARG with nothing launched: alpha outside [0, 1] (or NaN), temperature not finite or <= 0, teacher == NULL with
+ * alpha > 0.  NNUE_E_SHAPE where the per-sample tail's LDS row of teacher logits does not fit (L2 + 2 L3 + 2 C + 8 floats
+ * over 64 KiB). */
+int nnue_classifier_train_step_distill(const float* x, int pairwise,
+                                       const float* w1, const float* b1, const float* w2, const float* b2,
+                                       const float* w3, const float* b3, float clip,
+                                       const int64_t* labels, float grad_scale,
+                                       int B, int L1, int L2, int L3, int C,
+                                       float* h1, float* h2, float* logits, float* sample_loss, float* loss,
+                                       float* d_x, float* d_w1, float* d_b1, float* d_w2, float* d_b2,
+                                       float* d_w3, float* d_b3,
+                                       void* scratch, int64_t scratch_bytes, int phases,
+                                       const int64_t* labels_b, const float* lam, float eps,
+                                       const float* teacher, float alpha, float temperature, nnue_stream_t stream);
+/* the bucketed form of the call above (train.py:250-254, :360-361 on top of nnue.py:728-734 per stack), grouped mode included;
+ * teacher rows are in sample order, like labels. */
+int nnue_classifier_train_step_distill_bucketed(const float* x, int pairwise,
+                                                const float* w1, const float* b1, const float* w2, const float* b2,
+                                                const float* w3, const float* b3, float clip,
+                                                const int64_t* labels, float grad_scale,
+                                                int B, int L1, int L2, int L3, int C,
+                                                float* h1, float* h2, float* logits, float* sample_loss, float* loss,
+                                                float* d_x, float* d_w1, float* d_b1, float* d_w2, float* d_b2,
+                                                float* d_w3, float* d_b3,
+                                                void* scratch, int64_t scratch_bytes, int phases,
+                                                const int64_t* labels_b, const float* lam, float eps,
+                                                const float* teacher, float alpha, float temperature,
+                                                const nnue_buckets* buckets, nnue_stream_t stream);
 
 /* The table's weight gradient consumed where it is produced (single rank, SGD): clip_grad_norm_ needs the global norm
  * before any parameter moves (train.py:363-366), and
@@ -681,6 +726,14 @@ int nnue_cross_entropy(const float* logits, const int64_t* labels, int B, int C,
 int nnue_cross_entropy_soft(const float* logits, const int64_t* labels, const int64_t* labels_b, const float* lam, float eps,
                             int B, int C, float grad_scale, float* sample_loss, float* loss, float* d_logits,
                             nnue_stream_t stream);
+
+/* nnue_cross_entropy_soft (compute_loss, train.py:250-254) with the teacher arm defined under "soft targets": teacher
+ * float32 [B][C], alpha in [0, 1], temperature > 0.  d_logits may be NULL; the loss values do not depend on it.  alpha == 0
+ * is nnue_cross_entropy_soft (teacher may be NULL).  NNUE_E_ARG, nothing launched: alpha outside [0, 1], temperature not
+ * finite or <= 0, teacher == NULL with alpha > 0, and the soft call's refusals. */
+int nnue_cross_entropy_distill(const float* logits, const int64_t* labels, const int64_t* labels_b, const float* lam, float eps,
+                               int B, int C, float grad_scale, float* sample_loss, float* loss, float* d_logits,
+                               const float* teacher, float alpha, float temperature, nnue_stream_t stream);
 
 /* Prediction bookkeeping of compute_metrics / evaluate_model (evaluate.py:23-59, :62-87): adds this batch to
  * confusion[truth*K + pred] (uint64, K = C, or 2 when C == 1).  pred = first arg-max of the row (numpy's

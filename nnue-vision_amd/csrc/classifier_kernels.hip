@@ -665,6 +665,56 @@ __device__ __forceinline__ float ce_dlogit_soft(float z, float mx, float inv, fl
   return fmaf(expf(z - mx), inv, -t) * scale_over_b;
 }
 
+// ---- the DISTILL arm (the teacher term of include/nnue_hip.h, "soft targets"): the trailing pack is one DistillTargets; it
+// holds the SOFT arm's values too (SOFT is true with it) and adds a teacher row per sample.  Per-element arithmetic: common.h.
+
+// a[n] over the 64 lanes, max or sum, in place: the butterflies of ce_wave_stats (FAST: the exchanges of ce_wave_stats_fast)
+template <int N, bool FAST, bool MAX>
+__device__ __forceinline__ void ce_wave_all(float (&a)[N]) {
+  if constexpr (FAST) {
+#define NNUE_ALL_STEP(SH) _Pragma("unroll") for (int n = 0; n < N; ++n) { const float o = lane_xor<SH>(a[n]); a[n] = MAX ? fmaxf(a[n], o) : a[n] + o; }
+    NNUE_ALL_STEP(32) NNUE_ALL_STEP(16) NNUE_ALL_STEP(8) NNUE_ALL_STEP(4) NNUE_ALL_STEP(2) NNUE_ALL_STEP(1)
+#undef NNUE_ALL_STEP
+  } else {
+#pragma unroll
+    for (int sh = 32; sh >= 1; sh >>= 1)
+#pragma unroll
+      for (int n = 0; n < N; ++n) {
+        const float o = __shfl_xor(a[n], sh);
+        a[n] = MAX ? fmaxf(a[n], o) : a[n] + o;
+      }
+  }
+}
+
+// every statistic of the DISTILL arm for N samples with C <= 64 (lane c holds logit v and teacher logit u of class c), in TWO
+// butterflies' depth -- the plain kernels' -- whatever their number: the exchanges of independent chains are issued together,
+// a chain's values do not depend on what runs beside it.  First the two maxima (mx = max v, mu = max u), then the five sums:
+// se and cs (those of ce_wave_stats and ce_wave_csum, bit for bit), sU = sum eu, sT = sum ez, ks = sum eu ((mx - v) - (mu - u)),
+// with eu = exp((u - mu) / T) and ez = exp((v - mx) / T) of this lane (0 past C).
+template <int N, bool FAST>
+__device__ __forceinline__ void ce_wave_distill(const float (&v)[N], const float (&u)[N], bool in, float T, float (&mx)[N], float (&se)[N],
+                                                float (&cs)[N], float (&mu)[N], float (&eu)[N], float (&ez)[N], float (&sU)[N],
+                                                float (&sT)[N], float (&ks)[N]) {
+  float m[2 * N], a[5 * N];
+#pragma unroll
+  for (int n = 0; n < N; ++n) m[n] = in ? v[n] : -INFINITY, m[N + n] = in ? u[n] : -INFINITY;
+  ce_wave_all<2 * N, FAST, true>(m);
+#pragma unroll
+  for (int n = 0; n < N; ++n) {
+    mx[n] = m[n], mu[n] = m[N + n];
+    eu[n] = in ? nnue_distill_exp(u[n], mu[n], T) : 0.0f;
+    ez[n] = in ? nnue_distill_exp(v[n], mx[n], T) : 0.0f;
+    a[n] = in ? expf(v[n] - mx[n]) : 0.0f;
+    a[N + n] = in ? mx[n] - v[n] : 0.0f;
+    a[2 * N + n] = eu[n];
+    a[3 * N + n] = ez[n];
+    a[4 * N + n] = in ? nnue_distill_kl_acc(0.0f, eu[n], v[n], mx[n], u[n], mu[n]) : 0.0f;
+  }
+  ce_wave_all<5 * N, FAST, false>(a);
+#pragma unroll
+  for (int n = 0; n < N; ++n) se[n] = a[n], cs[n] = a[N + n], sU[n] = a[2 * N + n], sT[n] = a[3 * N + n], ks[n] = a[4 * N + n];
+}
+
 // class slice cp (of S) of d_z2[j] = sum_c d_logits[c] w3[c][j]: four chains over c = cp, cp + S, ...  (w3j = w3 + j)
 template <int S>
 __device__ __forceinline__ float dz2_slice(const float* dl, const float* w3j, int cp, int C, int L3) {
@@ -705,7 +755,8 @@ __global__ __launch_bounds__(NT) void tail_train_kernel(const float* __restrict_
                                                         const float* __restrict__ x, int L1, float* __restrict__ x_g,
                                                         float* __restrict__ d_z1_g, Soft... soft) {
   constexpr bool SOFT = sizeof...(Soft) == 1;
-  extern __shared__ float lds[];  // h1 [L2] | h2 [L3] | logits / d_logits [C] | d_z2 [L3] | red [8]
+  constexpr bool DISTILL = (std::is_same_v<Soft, DistillTargets> || ...);
+  extern __shared__ float lds[];  // h1 [L2] | h2 [L3] | logits / d_logits [C] | d_z2 [L3] | red [8] | DISTILL: teacher row [C]
   constexpr int S = NT / 32;      // class slices of the d_z2 sum
   __shared__ float part_s[S][32];
   float* h1s = lds;
@@ -759,6 +810,19 @@ __global__ __launch_bounds__(NT) void tail_train_kernel(const float* __restrict_
     eps = st.eps;
     if (st.labels_b) y2 = st.labels_b[b], lam = st.lam[b];
   }
+  // DISTILL: the teacher row is read once, strided by thread; the first kPreU values per thread are requested here and
+  // parked in LDS behind the slab sum, whose loads hide their latency (1024 classes at NT = 512), the rest goes straight
+  constexpr int kPreU = 2;
+  float* us = red + 8;
+  float alpha = 0.0f, T = 1.0f, uv[kPreU];
+  if constexpr (DISTILL) {
+    const DistillTargets dt = (soft, ...);
+    alpha = dt.alpha, T = dt.temperature;
+    const float* __restrict__ ur = dt.teacher + (size_t)b * C;
+#pragma unroll
+    for (int i = 0; i < kPreU; ++i) uv[i] = tid + NT * i < C ? ur[tid + NT * i] : 0.0f;
+    for (int c = tid + NT * kPreU; c < C; c += NT) us[c] = ur[c];
+  }
   for (int j = tid; j < L2; j += NT) {
     float z = b1[j];
     int s = 0;
@@ -773,6 +837,11 @@ __global__ __launch_bounds__(NT) void tail_train_kernel(const float* __restrict_
     const float h = act_fn(z, clip);
     h1s[j] = h;
     h1[(size_t)b * L2 + j] = h;
+  }
+  if constexpr (DISTILL) {
+#pragma unroll
+    for (int i = 0; i < kPreU; ++i)
+      if (tid + NT * i < C) us[tid + NT * i] = uv[i];
   }
   __syncthreads();
   for (int j0 = 0; j0 < L3; j0 += NT / 4) {
@@ -835,14 +904,22 @@ __global__ __launch_bounds__(NT) void tail_train_kernel(const float* __restrict_
   __syncthreads();
   // softmax cross-entropy of this sample and its gradient
   float mx = -INFINITY, se = 0.f, csum = 0.f;  // csum (SOFT): sum_c (mx - z_c), the smoothing term
+  float mu = -INFINITY, sU = 0.f, sT = 0.f, ksum = 0.f;  // DISTILL: the teacher's max and the three sums of the definition
   if (C <= 64) {  // every wave forms the same two reductions by itself: no block barriers
     const int lane = tid & 63;
     const float v[1] = {lane < C ? lgs[lane] : -INFINITY};
     float m1[1], s1[1];
-    ce_wave_stats<1>(v, lane < C, m1, s1);
+    if constexpr (DISTILL) {
+      const float u[1] = {lane < C ? us[lane] : 0.0f};
+      float c1[1], mu1[1], eu[1], ez[1], su1[1], st1[1], k1[1];
+      ce_wave_distill<1, false>(v, u, lane < C, T, m1, s1, c1, mu1, eu, ez, su1, st1, k1);
+      csum = c1[0], mu = mu1[0], sU = su1[0], sT = st1[0], ksum = k1[0];
+    } else {
+      ce_wave_stats<1>(v, lane < C, m1, s1);
+    }
     mx = m1[0];
     se = s1[0];
-    if constexpr (SOFT) {
+    if constexpr (SOFT && !DISTILL) {
       float c1[1];
       ce_wave_csum<1, false>(v, lane < C, m1, c1);
       csum = c1[0];
@@ -856,9 +933,27 @@ __global__ __launch_bounds__(NT) void tail_train_kernel(const float* __restrict_
       for (int c = tid; c < C; c += NT) csum += mx - lgs[c];
       csum = block_reduce_nt<NT>(csum, false, red);
     }
+    if constexpr (DISTILL) {
+      for (int c = tid; c < C; c += NT) mu = fmaxf(mu, us[c]);
+      mu = block_reduce_nt<NT>(mu, true, red);
+      for (int c = tid; c < C; c += NT) {
+        const float eu = nnue_distill_exp(us[c], mu, T);
+        sU += eu;
+        sT += nnue_distill_exp(lgs[c], mx, T);
+        ksum = nnue_distill_kl_acc(ksum, eu, lgs[c], mx, us[c], mu);
+      }
+      sU = block_reduce_nt<NT>(sU, false, red);
+      sT = block_reduce_nt<NT>(sT, false, red);
+      ksum = block_reduce_nt<NT>(ksum, false, red);
+    }
   }
   const bool ok = SOFT ? nnue_soft_counts(y, y2, lam, C) : y >= 0 && y < C;
-  if constexpr (SOFT) {
+  if constexpr (DISTILL) {
+    if (tid == 0) {
+      const float ls = ok ? nnue_ce_soft_sample_loss(mx, lgs[y], lgs[y2 >= 0 && y2 < C ? y2 : y], se, csum, lam, eps, C) : 0.0f;
+      sample_loss[b] = ok ? nnue_distill_sample_loss(ls, sT, sU, ksum, alpha, T) : 0.0f;
+    }
+  } else if constexpr (SOFT) {
     if (tid == 0)
       sample_loss[b] = ok ? nnue_ce_soft_sample_loss(mx, lgs[y], lgs[y2 >= 0 && y2 < C ? y2 : y], se, csum, lam, eps, C) : 0.0f;
   } else {
@@ -868,7 +963,12 @@ __global__ __launch_bounds__(NT) void tail_train_kernel(const float* __restrict_
   __syncthreads();  // every thread has read lgs[y] / the logits it needs before they are overwritten
   for (int c = tid; c < C; c += NT) {
     float g;
-    if constexpr (SOFT) g = ok ? ce_dlogit_soft(lgs[c], mx, inv, nnue_soft_target(c == y, c == y2, lam, eps, C), scale_over_b) : 0.0f;
+    if constexpr (DISTILL) {
+      const float soft_g = fmaf(expf(lgs[c] - mx), inv, -nnue_soft_target(c == y, c == y2, lam, eps, C));
+      g = ok ? nnue_distill_dlogit(soft_g, nnue_distill_exp(lgs[c], mx, T), 1.0f / sT, nnue_distill_exp(us[c], mu, T), 1.0f / sU, alpha, T,
+                                   scale_over_b)
+             : 0.0f;
+    } else if constexpr (SOFT) g = ok ? ce_dlogit_soft(lgs[c], mx, inv, nnue_soft_target(c == y, c == y2, lam, eps, C), scale_over_b) : 0.0f;
     else g = ok ? ce_dlogit(lgs[c], mx, inv, c == y, scale_over_b) : 0.0f;
     lgs[c] = g;
     d_logits[(size_t)b * C + c] = g;
@@ -1000,6 +1100,7 @@ __global__ __launch_bounds__(kTdxThreads) void tail_dx_train_kernel(
     float* __restrict__ d_z2, const float* __restrict__ x, const float* __restrict__ w1, int L1, float* __restrict__ d_x,
     int m_tiles, int n_cg NNUE_TDX_ABL_PARAM, Soft... soft) {
   constexpr bool SOFT = sizeof...(Soft) == 1;
+  constexpr bool DISTILL = (std::is_same_v<Soft, DistillTargets> || ...);
   constexpr int T = kTdxRows, NT = kTdxThreads, NWAVE = NT / 64;
   constexpr int NI = T * L2 / 4 / NT;       // float4 slots of the tile's slab rows per thread
   constexpr int NCH = L2 / (16 * kBwxKC);   // K chunks of the d_x product
@@ -1056,6 +1157,16 @@ __global__ __launch_bounds__(kTdxThreads) void tail_dx_train_kernel(
     const SoftTargets st = (soft, ...);
     eps = st.eps;
     if (st.labels_b) y2v = st.labels_b[min(row0 + (tid % T), B - 1)], lamv = st.lam[min(row0 + (tid % T), B - 1)];  // uniform
+  }
+  // DISTILL: the teacher logit of class `lane` of each row this wave takes in the softmax phase below (rows wave,
+  // wave + NWAVE): one coalesced float per lane and row, requested here so that the slab sum hides its latency; a lane
+  // past C and a padding row read a clamped address and feed nothing
+  float alpha = 0.0f, tmp = 1.0f, uv[T / NWAVE];
+  if constexpr (DISTILL) {
+    const DistillTargets dt = (soft, ...);
+    alpha = dt.alpha, tmp = dt.temperature;
+#pragma unroll
+    for (int it = 0; it < T / NWAVE; ++it) uv[it] = dt.teacher[(size_t)min(row0 + wave + NWAVE * it, B - 1) * C + min(lane, C - 1)];
   }
   int srow[NI], scol[NI];
   float4 z4[NI];
@@ -1176,9 +1287,11 @@ __global__ __launch_bounds__(kTdxThreads) void tail_dx_train_kernel(
     float v[RW], mx[RW], se[RW];
 #pragma unroll
     for (int it = 0; it < RW; ++it) v[it] = in ? lgs[wave + NWAVE * it][lane] : -INFINITY;
-    ce_wave_stats_fast<RW>(v, in, mx, se);
     float cs[RW];  // SOFT: sum_c (mx - z_c), the smoothing term
-    if constexpr (SOFT) ce_wave_csum<RW, true>(v, in, mx, cs);
+    float mu[RW], eu[RW], ez[RW], sU[RW], sT[RW], ks[RW];  // DISTILL: the teacher's max, the numerators of q and pT, the three sums
+    if constexpr (DISTILL) ce_wave_distill<RW, true>(v, uv, in, tmp, mx, se, cs, mu, eu, ez, sU, sT, ks);
+    else ce_wave_stats_fast<RW>(v, in, mx, se);
+    if constexpr (SOFT && !DISTILL) ce_wave_csum<RW, true>(v, in, mx, cs);
 #pragma unroll
     for (int it = 0; it < RW; ++it) {
       const int rr = wave + NWAVE * it;
@@ -1190,7 +1303,12 @@ __global__ __launch_bounds__(kTdxThreads) void tail_dx_train_kernel(
       const float zy = ok ? lgs[rr][y] : 0.f;  // read by every lane before any lane overwrites its logit
       if constexpr (SOFT) {
         const float zy2 = ok ? lgs[rr][y2 >= 0 && y2 < C ? y2 : y] : 0.f;
-        if (writer && lane == 0 && row0 + rr < B)
+        if constexpr (DISTILL) {
+          if (writer && lane == 0 && row0 + rr < B) {
+            const float ls = ok ? nnue_ce_soft_sample_loss(mx[it], zy, zy2, se[it], cs[it], lam, eps, C) : 0.0f;
+            sample_loss[row0 + rr] = ok ? nnue_distill_sample_loss(ls, sT[it], sU[it], ks[it], alpha, tmp) : 0.0f;
+          }
+        } else if (writer && lane == 0 && row0 + rr < B)
           sample_loss[row0 + rr] = ok ? nnue_ce_soft_sample_loss(mx[it], zy, zy2, se[it], cs[it], lam, eps, C) : 0.0f;
       } else {
         if (writer && lane == 0 && row0 + rr < B) sample_loss[row0 + rr] = ok ? nnue_ce_sample_loss(mx[it], zy, se[it]) : 0.0f;
@@ -1198,7 +1316,10 @@ __global__ __launch_bounds__(kTdxThreads) void tail_dx_train_kernel(
       const float inv = 1.0f / se[it];
       if (in) {
         float g;
-        if constexpr (SOFT) g = ok ? ce_dlogit_soft(v[it], mx[it], inv, nnue_soft_target(lane == y, lane == y2, lam, eps, C), scale_over_b) : 0.0f;
+        if constexpr (DISTILL) {
+          const float soft_g = fmaf(expf(v[it] - mx[it]), inv, -nnue_soft_target(lane == y, lane == y2, lam, eps, C));
+          g = ok ? nnue_distill_dlogit(soft_g, ez[it], 1.0f / sT[it], eu[it], 1.0f / sU[it], alpha, tmp, scale_over_b) : 0.0f;
+        } else if constexpr (SOFT) g = ok ? ce_dlogit_soft(v[it], mx[it], inv, nnue_soft_target(lane == y, lane == y2, lam, eps, C), scale_over_b) : 0.0f;
         else g = ok ? ce_dlogit(v[it], mx[it], inv, lane == y, scale_over_b) : 0.0f;
         lgs[rr][lane] = g;
         if (writer && row0 + rr < B) d_logits[(size_t)(row0 + rr) * C + lane] = g;
@@ -1773,13 +1894,13 @@ extern "C" int nnue_classifier_train_rider(int pairwise, int B, int L1, int L2, 
 }
 
 namespace {
-// The one launcher behind the four entry points.  soft NULL: the plain step.  Checks in the order they have always had, then
-// one arm per field of the plan (train_step_plan)
+// The one launcher behind the six entry points.  soft NULL: the plain step; distill (with soft = its SoftTargets half): the
+// teacher arm.  Checks in the order they have always had, then one arm per field of the plan (train_step_plan)
 int train_step(const float* x, int pairwise, const float* w1, const float* b1, const float* w2, const float* b2, const float* w3,
                const float* b3, float clip, const int64_t* labels, float grad_scale, int B, int L1, int L2, int L3, int C, float* h1,
                float* h2, float* logits, float* sample_loss, float* loss, float* d_x, float* d_w1, float* d_b1, float* d_w2, float* d_b2,
                float* d_w3, float* d_b3, void* scratch, int64_t scratch_bytes, int phases, const nnue_buckets* buckets, nnue_stream_t stream,
-               const SoftTargets* soft) {
+               const SoftTargets* soft, const DistillTargets* distill = nullptr) {
   Buckets bk;
   const int rc = buckets_from(buckets, B, &bk, "nnue_classifier_train_step_bucketed");
   if (rc != NNUE_OK) return rc;
@@ -1805,6 +1926,9 @@ int train_step(const float* x, int pairwise, const float* w1, const float* b1, c
                L3, C);
   NNUE_REQUIRE(sp.refusal != Refusal::odd_l1, NNUE_E_SHAPE, "nnue_classifier_train_step: pairwise needs an even L1 (got %d)", L1);
   NNUE_REQUIRE(sp.refusal != Refusal::tail_lds, NNUE_E_SHAPE, "nnue_classifier_train_step: L2+2*L3+C too large for the LDS tail");
+  // the DISTILL arm of tail_train_kernel keeps the teacher row in LDS beside the logits
+  const int64_t tail_lds = sp.tail_lds + (distill ? (int64_t)C * 4 : 0);
+  NNUE_REQUIRE(tail_lds <= 64 * 1024, NNUE_E_SHAPE, "nnue_classifier_train_step_distill: L2+2*L3+2*C too large for the LDS tail");
   NNUE_REQUIRE(scratch_bytes >= t.total * (int64_t)sizeof(float), NNUE_E_SCRATCH,
                "nnue_classifier_train_step: scratch %lld < %lld bytes", (long long)scratch_bytes, (long long)(t.total * 4));
   NNUE_REQUIRE(nnue_aligned16(x) && nnue_aligned16(w1) && nnue_aligned16(scratch) && nnue_aligned16(d_w1) && nnue_aligned16(h1) &&
@@ -1833,13 +1957,13 @@ int train_step(const float* x, int pairwise, const float* w1, const float* b1, c
                                                     row_tiles(B, K), sp.tdx_cg);
   };
 #define NNUE_TAIL(NT, V, ...)                                                                                                             \
-  hipLaunchKernelGGL((tail_train_kernel<NT, V>), dim3(sp.tail_grid), dim3(NT), (size_t)sp.tail_lds, s, part, sp.tail_slabs, b1, w2, b2, w3, b3, \
+  hipLaunchKernelGGL((tail_train_kernel<NT, V>), dim3(sp.tail_grid), dim3(NT), (size_t)tail_lds, s, part, sp.tail_slabs, b1, w2, b2, w3, b3, \
                      clip, labels, grad_scale / (float)B, B, L2, L3, C, h1, h2, logits, sample_loss, d_logits, d_z1, d_z2, bk, x, L1, x_g,     \
                      d_z1_g, ##__VA_ARGS__)
 
   // A kernel template's instantiations stand in the code object in the order of their first use here: tail_dx_train_kernel
   // with, then without d_x tiles, tail_train_kernel<512, .>, <128, .>.  A new arm goes behind them, so that no kernel moves:
-  // the SOFT arms follow in the same order.
+  // the SOFT arms follow in the same order, then the DISTILL arms.
   const bool plain = soft == nullptr;
   if (plain && sp.dx == DxLaunch::with_tail) tile_tail(std::true_type{});  // the whole call: nothing below is planned with it
   if (sp.l1_forward) launch_l1_forward(p, l1, w1, part);
@@ -1847,11 +1971,16 @@ int train_step(const float* x, int pairwise, const float* w1, const float* b1, c
     if (sp.tail == TailLaunch::tile) tile_tail(std::false_type{});
     else if (sp.tail == TailLaunch::sample512) { if (sp.tail_vec) NNUE_TAIL(512, true); else NNUE_TAIL(512, false); }
     else if (sp.tail == TailLaunch::sample128) { if (sp.tail_vec) NNUE_TAIL(128, true); else NNUE_TAIL(128, false); }
-  } else {  // the same launches with the kernels' SOFT arm
+  } else if (!distill) {  // the same launches with the kernels' SOFT arm
     if (sp.dx == DxLaunch::with_tail) tile_tail(std::true_type{}, *soft);
     else if (sp.tail == TailLaunch::tile) tile_tail(std::false_type{}, *soft);
     else if (sp.tail == TailLaunch::sample512) { if (sp.tail_vec) NNUE_TAIL(512, true, *soft); else NNUE_TAIL(512, false, *soft); }
     else if (sp.tail == TailLaunch::sample128) { if (sp.tail_vec) NNUE_TAIL(128, true, *soft); else NNUE_TAIL(128, false, *soft); }
+  } else {  // and with their DISTILL arm
+    if (sp.dx == DxLaunch::with_tail) tile_tail(std::true_type{}, *distill);
+    else if (sp.tail == TailLaunch::tile) tile_tail(std::false_type{}, *distill);
+    else if (sp.tail == TailLaunch::sample512) { if (sp.tail_vec) NNUE_TAIL(512, true, *distill); else NNUE_TAIL(512, false, *distill); }
+    else if (sp.tail == TailLaunch::sample128) { if (sp.tail_vec) NNUE_TAIL(128, true, *distill); else NNUE_TAIL(128, false, *distill); }
   }
 #undef NNUE_TAIL
   if (sp.dx == DxLaunch::with_dw1) {
@@ -1911,4 +2040,39 @@ extern "C" int nnue_classifier_train_step_soft_bucketed(const float* x, int pair
   const SoftTargets soft{labels_b, labels_b ? lam : nullptr, eps};  // lam without labels_b mixes a label with itself: not read
   return train_step(x, pairwise, w1, b1, w2, b2, w3, b3, clip, labels, grad_scale, B, L1, L2, L3, C, h1, h2, logits, sample_loss, loss, d_x,
                     d_w1, d_b1, d_w2, d_b2, d_w3, d_b3, scratch, scratch_bytes, phases, buckets, stream, &soft);
+}
+
+extern "C" int nnue_classifier_train_step_distill(const float* x, int pairwise, const float* w1, const float* b1, const float* w2,
+                                                  const float* b2, const float* w3, const float* b3, float clip, const int64_t* labels,
+                                                  float grad_scale, int B, int L1, int L2, int L3, int C, float* h1, float* h2,
+                                                  float* logits, float* sample_loss, float* loss, float* d_x, float* d_w1, float* d_b1,
+                                                  float* d_w2, float* d_b2, float* d_w3, float* d_b3, void* scratch, int64_t scratch_bytes,
+                                                  int phases, const int64_t* labels_b, const float* lam, float eps, const float* teacher,
+                                                  float alpha, float temperature, nnue_stream_t stream) {
+  return nnue_classifier_train_step_distill_bucketed(x, pairwise, w1, b1, w2, b2, w3, b3, clip, labels, grad_scale, B, L1, L2, L3, C, h1, h2,
+                                                     logits, sample_loss, loss, d_x, d_w1, d_b1, d_w2, d_b2, d_w3, d_b3, scratch,
+                                                     scratch_bytes, phases, labels_b, lam, eps, teacher, alpha, temperature, nullptr, stream);
+}
+
+extern "C" int nnue_classifier_train_step_distill_bucketed(const float* x, int pairwise, const float* w1, const float* b1, const float* w2,
+                                                           const float* b2, const float* w3, const float* b3, float clip,
+                                                           const int64_t* labels, float grad_scale, int B, int L1, int L2, int L3, int C,
+                                                           float* h1, float* h2, float* logits, float* sample_loss, float* loss,
+                                                           float* d_x, float* d_w1, float* d_b1, float* d_w2, float* d_b2, float* d_w3,
+                                                           float* d_b3, void* scratch, int64_t scratch_bytes, int phases,
+                                                           const int64_t* labels_b, const float* lam, float eps, const float* teacher,
+                                                           float alpha, float temperature, const nnue_buckets* buckets,
+                                                           nnue_stream_t stream) {
+  NNUE_REQUIRE(alpha >= 0.0f && alpha <= 1.0f, NNUE_E_ARG, "nnue_classifier_train_step_distill: alpha = %g is outside [0, 1]", (double)alpha);
+  NNUE_REQUIRE(temperature > 0.0f && temperature < INFINITY, NNUE_E_ARG,
+               "nnue_classifier_train_step_distill: temperature = %g must be finite and positive", (double)temperature);
+  NNUE_REQUIRE(teacher || alpha == 0.0f, NNUE_E_ARG, "nnue_classifier_train_step_distill: alpha > 0 without teacher logits");
+  NNUE_REQUIRE(eps >= 0.0f && eps < 1.0f, NNUE_E_ARG, "nnue_classifier_train_step_distill: eps = %g is outside [0, 1)", (double)eps);
+  NNUE_REQUIRE(lam || !labels_b, NNUE_E_ARG, "nnue_classifier_train_step_distill: labels_b without lam");
+  DistillTargets dt;
+  dt.labels_b = labels_b, dt.lam = labels_b ? lam : nullptr, dt.eps = eps;
+  dt.teacher = teacher, dt.alpha = alpha, dt.temperature = temperature;
+  // alpha == 0 is the soft call: the same launches, the teacher is not read
+  return train_step(x, pairwise, w1, b1, w2, b2, w3, b3, clip, labels, grad_scale, B, L1, L2, L3, C, h1, h2, logits, sample_loss, loss, d_x,
+                    d_w1, d_b1, d_w2, d_b2, d_w3, d_b3, scratch, scratch_bytes, phases, buckets, stream, &dt, alpha > 0.0f ? &dt : nullptr);
 }

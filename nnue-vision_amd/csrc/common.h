@@ -56,6 +56,31 @@ __device__ __forceinline__ float nnue_soft_target(bool is_a, bool is_a2, float l
   return (1.0f - eps) * (lam * (is_a ? 1.0f : 0.0f) + (1.0f - lam) * (is_a2 ? 1.0f : 0.0f)) + eps / (float)C;
 }
 
+// Distillation (include/nnue_hip.h, "soft targets": the teacher arm): one row of teacher logits per sample beside the soft
+// targets, a weight alpha in (0, 1] and a temperature T > 0 per call (alpha == 0 never reaches a kernel: the launcher runs
+// the soft call).  The per-element arithmetic below is shared by both tail kernels and the stand-alone loss; the fmas are
+// explicit so that every kernel forms the same bits whatever stands around the call.
+struct DistillTargets : SoftTargets { const float* teacher; float alpha, temperature; };
+// exp((v - vmax) / T): the numerator of q (v = u, vmax = mu) and of pT (v = z, vmax = mx); v - vmax is formed first
+__device__ __forceinline__ float nnue_distill_exp(float v, float vmax, float T) { return expf((v - vmax) / T); }
+// acc + one term of sU * sum_c q_c ((mx - z_c) - (mu - u_c)), eu = exp((u - mu) / T): the term is 0 where q underflows,
+// whatever the distances
+__device__ __forceinline__ float nnue_distill_kl_acc(float acc, float eu, float z, float mx, float u, float mu) {
+  return fmaf(eu, (mx - z) - (mu - u), acc);
+}
+// loss_b from the soft loss and the three sums: KL = (log sT - log sU) + (ksum / sU) / T, both logs >= 0
+__device__ __forceinline__ float nnue_distill_sample_loss(float l_soft, float sT, float sU, float ksum, float alpha, float T) {
+  const float kl = (logf(sT) - logf(sU)) + (ksum / sU) / T;
+  return fmaf(alpha * T * T, kl, (1.0f - alpha) * l_soft);
+}
+// d loss / d logit z of a sample that counts: soft = exp(z - mx) / se - t (ce_dlogit_soft's fma), ez and eu the numerators
+// of pT and q, inv_sT = 1 / sT, inv_sU = 1 / sU
+__device__ __forceinline__ float nnue_distill_dlogit(float soft, float ez, float inv_sT, float eu, float inv_sU, float alpha, float T,
+                                                     float scale_over_b) {
+  const float d = fmaf(ez, inv_sT, -(eu * inv_sU));
+  return fmaf(alpha * T, d, (1.0f - alpha) * soft) * scale_over_b;
+}
+
 namespace {
 __global__ __launch_bounds__(256) void nnue_zero_floats_kernel(float* __restrict__ dst, size_t count) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;

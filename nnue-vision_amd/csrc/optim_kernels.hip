@@ -1186,3 +1186,84 @@ extern "C" int nnue_cross_entropy_soft(const float* logits, const int64_t* label
   hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(256), 0, s, sample_loss, B, loss);
   return nnue_launch_status("nnue_cross_entropy_soft");
 }
+
+// ---------------------------------------------------------------- distillation (behind the soft loss: no kernel above moves)
+namespace {
+// cross_entropy_soft_kernel with the teacher term (include/nnue_hip.h, "soft targets"): one wave per sample, the per-element
+// arithmetic of common.h.  GRAD: d_logits is wanted; the loss does not depend on it.
+template <bool GRAD>
+__global__ __launch_bounds__(256) void cross_entropy_distill_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
+                                                                    DistillTargets dt, int B, int C, float scale_over_b,
+                                                                    float* __restrict__ sample_loss, float* __restrict__ d_logits) {
+  const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (b >= B) return;
+  const float* __restrict__ z = logits + (size_t)b * C;
+  const float* __restrict__ u = dt.teacher + (size_t)b * C;
+  const float T = dt.temperature;
+  float mx = -INFINITY, mu = -INFINITY;
+  for (int c = lane; c < C; c += 64) {
+    mx = fmaxf(mx, z[c]);
+    mu = fmaxf(mu, u[c]);
+  }
+  mx = wave_max(mx);
+  mu = wave_max(mu);
+  float se = 0.f, csum = 0.f, sU = 0.f, sT = 0.f, ksum = 0.f;
+  for (int c = lane; c < C; c += 64) {
+    se += expf(z[c] - mx);
+    csum += mx - z[c];
+    const float eu = nnue_distill_exp(u[c], mu, T);
+    sU += eu;
+    sT += nnue_distill_exp(z[c], mx, T);
+    ksum = nnue_distill_kl_acc(ksum, eu, z[c], mx, u[c], mu);
+  }
+  se = wave_sum(se);
+  csum = wave_sum(csum);
+  sU = wave_sum(sU);
+  sT = wave_sum(sT);
+  ksum = wave_sum(ksum);
+  const int64_t y = labels[b], y2 = dt.labels_b ? dt.labels_b[b] : y;
+  const float lam = dt.labels_b ? dt.lam[b] : 1.0f;
+  const bool ok = nnue_soft_counts(y, y2, lam, C);
+  if (lane == 0) {
+    const float ls = ok ? nnue_ce_soft_sample_loss(mx, z[y], z[y2 >= 0 && y2 < C ? y2 : y], se, csum, lam, dt.eps, C) : 0.0f;
+    sample_loss[b] = ok ? nnue_distill_sample_loss(ls, sT, sU, ksum, dt.alpha, T) : 0.0f;
+  }
+  if constexpr (GRAD) {
+    const float inv = 1.0f / se, inv_sT = 1.0f / sT, inv_sU = 1.0f / sU;
+    for (int c = lane; c < C; c += 64) {
+      const float soft = fmaf(expf(z[c] - mx), inv, -nnue_soft_target(c == y, c == y2, lam, dt.eps, C));
+      const float g = nnue_distill_dlogit(soft, nnue_distill_exp(z[c], mx, T), inv_sT, nnue_distill_exp(u[c], mu, T), inv_sU, dt.alpha, T,
+                                          scale_over_b);
+      d_logits[(size_t)b * C + c] = ok ? g : 0.0f;
+    }
+  }
+}
+}  // namespace
+
+extern "C" int nnue_cross_entropy_distill(const float* logits, const int64_t* labels, const int64_t* labels_b, const float* lam, float eps,
+                                          int B, int C, float grad_scale, float* sample_loss, float* loss, float* d_logits,
+                                          const float* teacher, float alpha, float temperature, nnue_stream_t stream) {
+  NNUE_REQUIRE(alpha >= 0.0f && alpha <= 1.0f, NNUE_E_ARG, "nnue_cross_entropy_distill: alpha = %g is outside [0, 1]", (double)alpha);
+  NNUE_REQUIRE(temperature > 0.0f && temperature < INFINITY, NNUE_E_ARG,
+               "nnue_cross_entropy_distill: temperature = %g must be finite and positive", (double)temperature);
+  NNUE_REQUIRE(teacher || alpha == 0.0f, NNUE_E_ARG, "nnue_cross_entropy_distill: alpha > 0 without teacher logits");
+  // alpha == 0 is the soft call: the same launches, the teacher is not read
+  if (alpha == 0.0f) return nnue_cross_entropy_soft(logits, labels, labels_b, lam, eps, B, C, grad_scale, sample_loss, loss, d_logits, stream);
+  NNUE_REQUIRE(logits && labels && sample_loss && loss, NNUE_E_ARG, "nnue_cross_entropy_distill: null pointer");
+  NNUE_REQUIRE(B > 0 && C > 0, NNUE_E_ARG, "nnue_cross_entropy_distill: B=%d C=%d must be positive", B, C);
+  NNUE_REQUIRE(eps >= 0.0f && eps < 1.0f, NNUE_E_ARG, "nnue_cross_entropy_distill: eps = %g is outside [0, 1)", (double)eps);
+  NNUE_REQUIRE(lam || !labels_b, NNUE_E_ARG, "nnue_cross_entropy_distill: labels_b without lam");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  DistillTargets dt;
+  dt.labels_b = labels_b, dt.lam = labels_b ? lam : nullptr, dt.eps = eps;
+  dt.teacher = teacher, dt.alpha = alpha, dt.temperature = temperature;
+  if (d_logits)
+    hipLaunchKernelGGL(cross_entropy_distill_kernel<true>, dim3((B + 3) / 4), dim3(256), 0, s, logits, labels, dt, B, C, grad_scale / (float)B,
+                       sample_loss, d_logits);
+  else
+    hipLaunchKernelGGL(cross_entropy_distill_kernel<false>, dim3((B + 3) / 4), dim3(256), 0, s, logits, labels, dt, B, C,
+                       grad_scale / (float)B, sample_loss, d_logits);
+  hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(256), 0, s, sample_loss, B, loss);
+  return nnue_launch_status("nnue_cross_entropy_distill");
+}

@@ -149,6 +149,17 @@ SIGNATURES = {
                                                           _c_p, _c_p, _c_p, _c_p, _c_p,
                                                           _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_int,
                                                           _c_p, _c_p, _c_f, _c_bk, _c_p]),
+    "nnue_cross_entropy_distill": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_f, _c_int, _c_int, _c_f, _c_p, _c_p, _c_p, _c_p, _c_f, _c_f, _c_p]),
+    "nnue_classifier_train_step_distill": (_c_int, [_c_p, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_f, _c_p, _c_f,
+                                                    _c_int, _c_int, _c_int, _c_int, _c_int,
+                                                    _c_p, _c_p, _c_p, _c_p, _c_p,
+                                                    _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_int,
+                                                    _c_p, _c_p, _c_f, _c_p, _c_f, _c_f, _c_p]),
+    "nnue_classifier_train_step_distill_bucketed": (_c_int, [_c_p, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_f, _c_p, _c_f,
+                                                             _c_int, _c_int, _c_int, _c_int, _c_int,
+                                                             _c_p, _c_p, _c_p, _c_p, _c_p,
+                                                             _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_int,
+                                                             _c_p, _c_p, _c_f, _c_p, _c_f, _c_f, _c_bk, _c_p]),
     "nnue_mix_batch": (_c_int, [_c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_f, _c_int, _c_int, _c_int, _c_int, _c_p, _c_p, _c_p]),
     "nnue_confusion_accumulate": (_c_int, [_c_p, _c_p, _c_int, _c_int, _c_p, _c_p]),
     "nnue_load_batch": (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_i64, _c_int, ctypes.c_uint64, ctypes.c_uint64,
@@ -313,7 +324,9 @@ _TIMED_AS = {"nnue_sgd_step_clip": "nnue_sgd_step", "nnue_adam_step_clip": "nnue
              "nnue_ftm_conv_binarize_planes": "nnue_ftm_conv_binarize", "nnue_ftm_forward_l1_planes": "nnue_ftm_forward_l1",
              "nnue_ftm_conv_binarize_value_planes": "nnue_ftm_conv_binarize", "nnue_ftm_backward_planes": "nnue_ftm_backward",
              "nnue_classifier_train_step_soft": "nnue_classifier_train_step",
-             "nnue_classifier_train_step_soft_bucketed": "nnue_classifier_train_step_bucketed"}
+             "nnue_classifier_train_step_soft_bucketed": "nnue_classifier_train_step_bucketed",
+             "nnue_classifier_train_step_distill": "nnue_classifier_train_step",
+             "nnue_classifier_train_step_distill_bucketed": "nnue_classifier_train_step_bucketed"}
 
 
 def _call(name: str, *args) -> None:
@@ -1281,11 +1294,17 @@ CLS_TAIL_IN_DX = 64      # the per-sample tail runs inside the d_x launch (only 
 
 def classifier_train_step(x, pairwise: bool, w1, b1, w2, b2, w3, b3, labels, grad_scale: float = 1.0, clip: float = 0.0,
                           want_dx: bool = True, scratch: Optional[torch.Tensor] = None, out=None, loss_out=None,
-                          grads=None, d_x=None, phases: int = 3, buckets: Optional[BucketPlan] = None, soft=None):
+                          grads=None, d_x=None, phases: int = 3, buckets: Optional[BucketPlan] = None, soft=None,
+                          distill=None):
     """Forward + mean cross-entropy + backward of the classifier block in one C call.
     soft = (labels_b int64 [B] or None, lam float32 [B] or None, eps): the soft-target entry points (include/nnue_hip.h,
     "soft targets") -- a second label and a weight per sample, label smoothing eps; None: the plain ones.
+    distill = (teacher float32 [B, C] or None, alpha, T): the distillation entry points -- (1 - alpha) times the soft loss plus
+    alpha T^2 KL(teacher at T || student at T); beside ``soft`` or alone (one label per sample, eps 0).  teacher may be None
+    only with alpha == 0, which is the soft call.  ValueError before any call for alpha outside [0, 1] or T not finite and > 0.
     Returns (h1, h2, logits), (sample_loss, loss), d_x, grads."""
+    if distill is not None:
+        distill = (distill[0], *check_distill(distill[1], distill[2]))
     x = _need(x, torch.float32, "classifier input")
     b, l1 = x.shape
     w1, b1, w2, b2, w3, b3, l2, l3, c, k = _cls_shapes(w1, b1, w2, b2, w3, b3, l1, buckets)
@@ -1305,6 +1324,8 @@ def classifier_train_step(x, pairwise: bool, w1, b1, w2, b2, w3, b3, labels, gra
             b2.data_ptr(), w3.data_ptr(), b3.data_ptr(), float(clip), labels.data_ptr(), float(grad_scale), b, l1, l2, l3, c,
             h1.data_ptr(), h2.data_ptr(), logits.data_ptr(), sample_loss.data_ptr(), loss.data_ptr(),
             _ptr(d_x if want_dx else None), *[g.data_ptr() for g in grads], scratch.data_ptr(), scratch.numel(), int(phases))
+    if distill is not None and soft is None:
+        soft = (None, None, 0.0)
     if soft is not None:
         labels_b, lam, eps = soft
         if labels_b is not None:
@@ -1312,11 +1333,18 @@ def classifier_train_step(x, pairwise: bool, w1, b1, w2, b2, w3, b3, labels, gra
         if lam is not None:
             lam = _need(lam, torch.float32, "lam", (b,))
         args += (_ptr(labels_b), _ptr(lam), float(eps))
+    if distill is not None:
+        teacher, alpha, temperature = distill
+        if teacher is not None:
+            teacher = _need(teacher, torch.float32, "teacher logits", (b, c))
+        elif alpha > 0.0:
+            raise ValueError("distill: alpha > 0 needs teacher logits")
+        args += (_ptr(teacher), alpha, temperature)
+    form = "_distill" if distill is not None else "_soft" if soft is not None else ""
     if buckets is None:
-        _call("nnue_classifier_train_step_soft" if soft is not None else "nnue_classifier_train_step", *args, _stream(x))
+        _call(f"nnue_classifier_train_step{form}", *args, _stream(x))
     else:
-        _call("nnue_classifier_train_step_soft_bucketed" if soft is not None else "nnue_classifier_train_step_bucketed", *args,
-              buckets.ref, _stream(x))
+        _call(f"nnue_classifier_train_step{form}_bucketed", *args, buckets.ref, _stream(x))
     return (h1, h2, logits), (sample_loss, loss), (d_x if want_dx else None), grads
 
 
@@ -1358,6 +1386,46 @@ def cross_entropy_soft(logits: torch.Tensor, labels: torch.Tensor, labels_b: Opt
         sample_loss, loss, d_logits = out
     _call("nnue_cross_entropy_soft", logits.data_ptr(), labels.data_ptr(), _ptr(labels_b), _ptr(lam), float(eps), b, c, float(grad_scale),
           sample_loss.data_ptr(), loss.data_ptr(), _ptr(d_logits), _stream(logits))
+    return sample_loss, loss, d_logits
+
+
+def check_distill(alpha, temperature):
+    """(alpha, T) of a distillation call as floats; ValueError unless alpha lies in [0, 1] and T is finite and positive (what
+    the C entry points refuse with NNUE_E_ARG)."""
+    alpha, temperature = float(alpha), float(temperature)
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError(f"distill alpha = {alpha} must lie in [0, 1]")
+    if not (0.0 < temperature < float("inf")):
+        raise ValueError(f"distill temperature = {temperature} must be finite and positive")
+    return alpha, temperature
+
+
+def cross_entropy_distill(logits: torch.Tensor, labels: torch.Tensor, teacher: Optional[torch.Tensor], alpha: float,
+                          temperature: float = 1.0, labels_b: Optional[torch.Tensor] = None, lam: Optional[torch.Tensor] = None,
+                          eps: float = 0.0, grad_scale: float = 1.0, want_grad: bool = True, out=None):
+    """cross_entropy_soft with a teacher (include/nnue_hip.h, "soft targets"): (1 - alpha) times the soft loss plus
+    alpha T^2 KL(softmax(teacher / T) || softmax(logits / T)).  teacher float32 [B, C]; None only with alpha == 0."""
+    alpha, temperature = check_distill(alpha, temperature)
+    logits = _need(logits, torch.float32, "logits")
+    b, c = logits.shape
+    labels = _need(labels, torch.int64, "labels", (b,))
+    if labels_b is not None:
+        labels_b = _need(labels_b, torch.int64, "labels_b", (b,))
+    if lam is not None:
+        lam = _need(lam, torch.float32, "lam", (b,))
+    if teacher is not None:
+        teacher = _need(teacher, torch.float32, "teacher logits", (b, c))
+    elif alpha > 0.0:
+        raise ValueError("cross_entropy_distill: alpha > 0 needs teacher logits")
+    dev = logits.device
+    if out is None:
+        sample_loss = torch.empty((b,), dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        d_logits = torch.empty((b, c), dtype=torch.float32, device=dev) if want_grad else None
+    else:
+        sample_loss, loss, d_logits = out
+    _call("nnue_cross_entropy_distill", logits.data_ptr(), labels.data_ptr(), _ptr(labels_b), _ptr(lam), float(eps), b, c, float(grad_scale),
+          sample_loss.data_ptr(), loss.data_ptr(), _ptr(d_logits), _ptr(teacher), alpha, temperature, _stream(logits))
     return sample_loss, loss, d_logits
 
 

@@ -27,6 +27,12 @@ NNUE model, minus the parts that are out of scope here (W&B, RunPod, dataset dow
   (``dataset_from_config`` reads the two alphas) -- with ``two_labels``.  Only the training trainer and the training dataset
   see them: ``evaluate_model`` on the train, validation and test loaders stays plain cross-entropy on unmixed batches, so the
   reported losses stay comparable across runs.
+* ``distill_alpha``, ``distill_temperature`` (optional config attributes, 0 and 1 by default; build extensions) and the argument
+  ``teacher``: with ``distill_alpha > 0`` the training trainer adds alpha T^2 KL(teacher at T || student at T) to (1 - alpha) times
+  its loss (include/nnue_hip.h, "soft targets"), on the logits ``teacher`` -- any callable images [b,3,H,W] -> logits [b,C] on
+  the device, such as a drop-in ``nnue.NNUE`` in eval mode -- returns for each training batch under ``torch.no_grad()``.
+  ``distill_alpha > 0`` without a teacher is a ValueError; with alpha 0 a teacher is never called.  Evaluation stays plain
+  cross-entropy.
 * ``weight_clip`` (optional config attribute, 0 by default; a build extension): the trainer clamps the table and the classifier's
   weights to [-weight_clip, weight_clip] inside every optimizer update.  1.0 is what the export clamps to (``_clip_weights``,
   nnue.py:528-539): the metrics of a run trained with it describe the network ``serialize_model`` writes.
@@ -110,8 +116,13 @@ def config_weight_clip(config) -> float:
 def run_training(config, train_loader: Iterable, val_loader: Iterable, test_loader: Optional[Iterable] = None, model=None,
                  checkpoint_dir=None, log: Callable[[str], None] = print, use_graph: bool = True,
                  compiled_eval: Optional[bool] = None, save_last: Optional[bool] = None, resume_from=None,
-                 lr_schedule=None) -> TrainResult:
+                 lr_schedule=None, teacher=None) -> TrainResult:
     import evaluate
+    distill_alpha, distill_temperature = lib.check_distill(getattr(config, "distill_alpha", 0.0), getattr(config, "distill_temperature", 1.0))
+    if distill_alpha > 0.0 and teacher is None:
+        raise ValueError(f"the config sets distill_alpha = {distill_alpha}: run_training needs a teacher")
+    if distill_alpha == 0.0:
+        teacher = None  # never called
     if save_last is None:
         save_last = bool(getattr(config, "save_last", False))
     if resume_from is None:
@@ -147,7 +158,7 @@ def run_training(config, train_loader: Iterable, val_loader: Iterable, test_load
     trainer = NnueTrainer(model, batch, hw, lr=float(config.learning_rate), weight_decay=float(config.weight_decay),
                           max_grad_norm=clip, use_graph=use_graph, input_slots=8 if in_place else 1,
                           label_smoothing=float(getattr(config, "label_smoothing", 0.0)), two_labels=mixes, weight_clip=weight_clip,
-                          **opt)
+                          distill_alpha=distill_alpha, distill_temperature=distill_temperature, **opt)
     if lr_schedule is None and getattr(config, "lr_schedule", False):
         lr_schedule = LrSchedule.from_config(config, len(train_loader))
     if isinstance(lr_schedule, LrSchedule):
@@ -177,10 +188,15 @@ def run_training(config, train_loader: Iterable, val_loader: Iterable, test_load
     for epoch in range(first_epoch, int(config.max_epochs)):
         model.train()
         if in_place:
-            result.steps += train_epoch(trainer, train_loader)[1]
+            result.steps += train_epoch(trainer, train_loader, teacher=teacher)[1]
         else:
             for images, labels in train_loader:
-                trainer.step(images.to(device, non_blocking=True), labels.to(device, non_blocking=True).long())
+                images = images.to(device, non_blocking=True)
+                teacher_logits = None
+                if teacher is not None:
+                    with torch.no_grad():
+                        teacher_logits = teacher(images).detach().to(torch.float32)
+                trainer.step(images, labels.to(device, non_blocking=True).long(), teacher_logits=teacher_logits)
                 result.steps += 1
         trainer = _density_check(trainer, log)
         model.eval()

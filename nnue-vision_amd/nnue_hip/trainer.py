@@ -194,15 +194,21 @@ class NnueTrainer:
     def __init__(self, model, batch_size: int, image_hw: Tuple[int, int], lr: float, momentum: float = 0.0,
                  weight_decay: float = 0.0, max_grad_norm: float = 0.0, group=None, use_graph: bool = True,
                  input_slots: int = 1, optimizer: str = "sgd", betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
-                 ft_path: Optional[str] = None, label_smoothing: float = 0.0, two_labels: bool = False, weight_clip: float = 0.0):
+                 ft_path: Optional[str] = None, label_smoothing: float = 0.0, two_labels: bool = False, weight_clip: float = 0.0,
+                 distill_alpha: float = 0.0, distill_temperature: float = 1.0):
         """ft_path: the FeatureTransformer kernel family, as lib.ft_path's ``mode`` (None: NNUE_FT_PATH decides).
         label_smoothing (F.cross_entropy's, in [0, 1)) and two_labels (a second label and a weight per sample: mixup, CutMix) make
         the classifier step train on soft targets (include/nnue_hip.h, "soft targets"); with both at their defaults the step is
         the plain one, launch for launch.
         weight_clip (0: off; 1.0 is the reference's _clip_weights, nnue.py:528-539): after every optimizer update the table and the
         classifier's weights are clamped to [-weight_clip, weight_clip] inside the launches that apply the update (include/nnue_hip.h,
-        "weight clip") -- bit for bit the plain step followed by ``clamp_`` on those four tensors, in every step mode."""
+        "weight clip") -- bit for bit the plain step followed by ``clamp_`` on those four tensors, in every step mode.
+        distill_alpha (in [0, 1]) and distill_temperature (> 0): with alpha > 0 the loss is (1 - alpha) times the (soft) cross-entropy
+        plus alpha T^2 KL(teacher at T || student at T) (include/nnue_hip.h, "soft targets": the teacher arm) on the teacher logits
+        of ``teacher_inputs[s]`` (float32 [B, C] per input slot; ``step(..., teacher_logits=)`` or a loader's teacher fills them).
+        With alpha == 0 nothing is allocated and no call changes."""
         self._label_smoothing, self.two_labels = _checked_label_smoothing(label_smoothing), bool(two_labels)
+        self.distill_alpha, self.distill_temperature = lib.check_distill(distill_alpha, distill_temperature)
         weight_clip = lib.checked_weight_clip(weight_clip)
         lib.load()
         p0 = next(model.parameters())
@@ -275,6 +281,11 @@ class NnueTrainer:
             self.soft_inputs = [(torch.full((B,), -1, dtype=torch.int64, device=self.dev), torch.ones((B,), **f32))
                                 for _ in self.inputs]
             self.labels_b, self.lam = self.soft_inputs[0]
+        # distill_alpha > 0: per slot the teacher's logits (a padding row is never read into a result: its label is -1)
+        self.teacher_inputs = self.teacher = None
+        if self.distill_alpha > 0.0:
+            self.teacher_inputs = [torch.zeros((B, self.C), **f32) for _ in self.inputs]
+            self.teacher = self.teacher_inputs[0]
         self.conv_out = torch.empty((B, self.fps, self.gh, self.gw), **f32)
         # the live map of the step, in the mode's kernel family (``fm`` / ``bits`` / ``act`` name it by family)
         self.feats = lib.FT_FAMILIES[self.mode.ft_path].empty(B, self.P, self.F, self.L1, self.dev)
@@ -476,9 +487,11 @@ class NnueTrainer:
 
     def _cls_step(self, phases: int) -> None:
         soft = (self.labels_b, self.lam, self._label_smoothing) if (self.two_labels or self._label_smoothing != 0.0) else None
+        distill = (self.teacher, self.distill_alpha, self.distill_temperature) if self.distill_alpha > 0.0 else None
         lib.classifier_train_step(self.ft, True, *self._cls_params(), self.labels, 1.0, self.clip, scratch=self.cls_scratch,
                                   out=(self.h1, self.h2, self.logits), loss_out=(self.sample_loss, self.loss),
-                                  grads=self._cls_grads(), d_x=self.d_ft, phases=phases, buckets=self.bucket_plan, soft=soft)
+                                  grads=self._cls_grads(), d_x=self.d_ft, phases=phases, buckets=self.bucket_plan, soft=soft,
+                                  distill=distill)
 
     def _rider(self, loss: torch.Tensor):
         """The small-gradient tile family's arguments with `loss` as the mean loss's destination (one host struct per
@@ -729,6 +742,8 @@ class NnueTrainer:
             self.images, self.labels = self.inputs[slot]
             if self.soft_inputs is not None:
                 self.labels_b, self.lam = self.soft_inputs[slot]
+            if self.teacher_inputs is not None:
+                self.teacher = self.teacher_inputs[slot]
             for name in self.SEGMENTS:
                 with lib.record_calls() as calls:
                     self._segment(name)
@@ -763,6 +778,8 @@ class NnueTrainer:
         src, swap, riders = self._plan_slot, {}, None
         if slot != src:
             held = self.inputs if self.soft_inputs is None else [i + s for i, s in zip(self.inputs, self.soft_inputs)]
+            if self.teacher_inputs is not None:
+                held = [h + (t,) for h, t in zip(held, self.teacher_inputs)]
             swap.update({a.data_ptr(): b.data_ptr() for a, b in zip(held[src], held[slot])})
         if alt:
             swap.update(self._alt_swap())
@@ -775,7 +792,7 @@ class NnueTrainer:
     # ------------------------------------------------------------------ public
     def step(self, images: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None, slot: int = 0,
              timers=None, global_count: Optional[int] = None, labels_b: Optional[torch.Tensor] = None,
-             lam: Optional[torch.Tensor] = None) -> torch.Tensor:
+             lam: Optional[torch.Tensor] = None, teacher_logits: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One optimizer step on this rank's slice.  Returns the local mean loss (device scalar, no sync).
 
         A short batch (fewer than the B images the trainer was built for; possibly none on some ranks) is padded; with
@@ -789,8 +806,12 @@ class NnueTrainer:
 
         ``labels_b``/``lam`` (a trainer built with two_labels; both or neither, beside ``images``): the second labels and the
         weights of the first ones, copied into ``soft_inputs[slot]`` and padded with -1 / 1 the way labels are padded.  Without
-        them a copied batch has one label per sample."""
-        ragged = self._stage(slot, images, labels, labels_b, lam, global_count)
+        them a copied batch has one label per sample.
+
+        ``teacher_logits`` (a trainer built with distill_alpha > 0, which needs them beside every copied batch; float32 [n, C]):
+        the teacher's logits for ``images``, copied into ``teacher_inputs[slot]``; the rows behind a short batch are zeroed and,
+        their labels being -1, do not count."""
+        ragged = self._stage(slot, images, labels, labels_b, lam, global_count, teacher_logits)
         _, upd_first, upd = self._plans(slot)
         self._last_alt = False
         first, graphs = self.steps_done == 0, self.use_graph and timers is None
@@ -863,13 +884,17 @@ class NnueTrainer:
         # a short batch's kernels divided by B: the mean over the real samples (a whole-step graph never runs one)
         return self.loss * ragged if ragged is not None else self.loss
 
-    def _stage(self, slot: int, images, labels, labels_b, lam, global_count) -> Optional[float]:
+    def _stage(self, slot: int, images, labels, labels_b, lam, global_count, teacher_logits=None) -> Optional[float]:
         """Checks step()'s inputs and copies them into input slot `slot`, a short batch padded.  Returns the factor that restores
         the exact mean over the real samples where the kernels divide by B (gradients and loss are scaled by it), else None."""
         buf_images, buf_labels = self.inputs[slot]
         ragged = None
         if (labels_b is None) != (lam is None) or (labels_b is not None and (images is None or not self.two_labels)):
             raise ValueError("labels_b and lam come together, beside images, on a trainer built with two_labels=True")
+        if teacher_logits is not None and (images is None or self.teacher_inputs is None):
+            raise ValueError("teacher_logits come beside images, on a trainer built with distill_alpha > 0")
+        if teacher_logits is None and images is not None and self.teacher_inputs is not None:
+            raise ValueError("a trainer built with distill_alpha > 0 needs teacher_logits beside images")
         if images is not None:
             if labels is None or images.shape[1:] != buf_images.shape[1:] or labels.shape[0] != images.shape[0] \
                     or not 0 <= images.shape[0] <= self.B or (images.shape[0] == 0 and self.dp.world == 1):
@@ -898,6 +923,13 @@ class NnueTrainer:
                 if labels_b is not None:
                     buf_b[:n].copy_(labels_b, non_blocking=True)
                     buf_lam[:n].copy_(lam, non_blocking=True)
+            if teacher_logits is not None:
+                if tuple(teacher_logits.shape) != (n, self.C) or teacher_logits.dtype != torch.float32:
+                    raise ValueError(f"teacher_logits must be float32 {(n, self.C)}, got {teacher_logits.dtype} {tuple(teacher_logits.shape)}")
+                buf_t = self.teacher_inputs[slot]
+                if n < self.B:
+                    buf_t.zero_()
+                buf_t[:n].copy_(teacher_logits, non_blocking=True)
         if ragged is None and global_count is not None and self.dp.world > 1 and int(global_count) != self.B * self.dp.world:
             ragged = self.B * self.dp.world / int(global_count)  # this rank's slot is full but others are short: the same global mean
         return ragged
@@ -982,7 +1014,8 @@ class NnueTrainer:
         torch.cuda.synchronize(self.dev)
         new = NnueTrainer(self.model, self.B, (self.H, self.W), group=self.dp.group, use_graph=self.use_graph, input_slots=len(self.inputs),
                           optimizer=self.optimizer, betas=self.betas, eps=self.eps, ft_path=ft_path, label_smoothing=self._label_smoothing,
-                          two_labels=self.two_labels, **self._hyper)
+                          two_labels=self.two_labels, distill_alpha=self.distill_alpha, distill_temperature=self.distill_temperature,
+                          **self._hyper)
         self._gather_momentum_shards()
         for src, dst in zip(self._optimizer_buffers(), new._optimizer_buffers()):
             dst.copy_(src)
@@ -1001,7 +1034,8 @@ class NnueTrainer:
             schedule = {"values": self._lr_values.clone(), "position": int(self.lr_position)}
         return {"version": 1, "optimizer_type": self.optimizer, "optimizer": self.optimizer_state_dict(),
                 "steps_done": int(self.steps_done), "lr": float(self._hyper["lr"]), "lr_schedule": schedule,
-                "label_smoothing": float(self._label_smoothing), "weight_clip": float(self.weight_clip)}
+                "label_smoothing": float(self._label_smoothing), "weight_clip": float(self.weight_clip),
+                "distill_alpha": float(self.distill_alpha), "distill_temperature": float(self.distill_temperature)}
 
     def _checked_optimizer_state(self, sd: dict, steps_done: int):
         """The flat-buffer sources of a torch optimizer state dict, {buffer name: {parameter name: tensor}}, after checking
@@ -1062,7 +1096,8 @@ class NnueTrainer:
     def load_state_dict(self, sd: dict) -> None:
         """state_dict()'s counterpart, on a fresh trainer or on a used one between steps.  Validates first (optimizer type,
         presence of momentum, every tensor's shape against the layout, the label smoothing and the weight clip the state was trained
-        with -- a state without either key counts as 0; ValueError, nothing changed), then copies in place: the
+        with -- a state without either key counts as 0 -- and its distill_alpha / distill_temperature -- 0 and 1 without the keys;
+        ValueError, nothing changed), then copies in place: the
         momentum or both moments into the flat buffers, Adam's step into adam_step_count, the rate into lr_dev, the schedule's
         values and position into lr_table / lr_pos / lr_position, and steps_done.  No buffer is re-bound -- recorded plans and
         captured graphs hold raw pointers and stay valid; only a schedule of another length than the attached one (or a
@@ -1086,6 +1121,10 @@ class NnueTrainer:
         if float(sd.get("weight_clip", 0.0)) != self.weight_clip:  # (a state from before the key existed: 0)
             raise ValueError(f"the state was trained with weight_clip = {float(sd.get('weight_clip', 0.0))}, "
                              f"this trainer's is {self.weight_clip}")
+        held = (float(sd.get("distill_alpha", 0.0)), float(sd.get("distill_temperature", 1.0)))  # (before the keys existed: 0, 1)
+        if held != (self.distill_alpha, self.distill_temperature):
+            raise ValueError(f"the state was trained with distill_alpha = {held[0]}, distill_temperature = {held[1]}, "
+                             f"this trainer's are {self.distill_alpha}, {self.distill_temperature}")
         # ---- validated: from here on only in-place copies
         self._apply_optimizer_state(sources, steps_done)
         if schedule is None:
