@@ -1311,6 +1311,105 @@ int nnue_multi_adam_step_clip(float* const* params, float* const* grads, float* 
                               float max_norm, float* norm_out, void* scratch, int64_t scratch_bytes, const float* lr_dev,
                               nnue_stream_t stream);
 
+/* ---- weight average (build extension: a moving average of the weights kept by the launches that store them) --------------
+ * Training recipes with mixup, label smoothing and a cosine schedule evaluate and export an exponential moving average of the
+ * weights; the reference's loop (train.py:359-366) has none.  The entry points below are the optimizer entry points above with
+ * that average inside the launch that applies the update.  With omd = float32(1 - float64(decay)), every element e of the average
+ * whose weight the launch stores as w_new becomes
+ *     ema_update(e, w_new, omd) = fmaf(omd, w_new - e, e)
+ * -- one rounding of the difference, one of the fused multiply-add.  w_new is the value the launch stores: after the update, and
+ * after the clamp where the weight clip is on (a convex combination of clamped weights stays inside the bound, so with
+ * weight_clip = 1 the average is already the network the export writes).  Momentum and both Adam moments never see the average,
+ * and nothing else of a step reads it: a step with the average is, bit for bit, the plain step on parameters and optimizer
+ * state plus one ema_update per element -- nnue_ema_update, the stand-alone pass, applied to the old average and the new weights.
+ * The rate reaches the kernels as one float by value (ema_omd) or, where ema_omd_dev is not NULL, through that device float,
+ * which then replaces it exactly as lr_dev replaces lr (a warm-up changes it without re-recording or re-capturing anything).
+ * ema == NULL is "off": the call launches exactly what its _clip sibling launches (one implementation), whatever the rate.
+ * With ema != NULL and ema_omd_dev == NULL, ema_omd outside (0, 1] or NaN is refused with NNUE_E_ARG; nothing is launched.
+ * Flat buffers: ema is laid out like params (count floats).  Under ext_applied_elsewhere the rows left to the producer are
+ * averaged by the producer's own _ema entry point, as with the clip.  Table forms: ema holds the rows that match `weight`
+ * (16-byte aligned).  Multi-tensor forms: one pointer and one rate per segment (HOST arrays like lr[]; ema == NULL or ema[i] ==
+ * NULL: that segment is off; a list with an average packs 38 segments per launch, one without keeps its 45).
+ * The fused update + next-forward pass carries the average too (the kEma forms of its kernel): the new tile is
+ * averaged after the clamp and stored behind the parameters; the next step's forward never reads the average, so out_next stays
+ * bitwise what the _clip form gives. */
+
+/* The stand-alone pass of the average (after optimizer.step(), train.py:366): ema[i] <- ema_update(ema[i], params[i], omd) for i
+ * in [0, count).  Any 4-byte-aligned pointers: 16-byte accesses where both are 16-byte aligned, 4-byte ones otherwise.
+ * ema_omd_dev (device float, may be NULL) replaces omd.  NNUE_E_ARG, nothing launched: a NULL ema or params, count <= 0, omd
+ * outside (0, 1] or NaN without ema_omd_dev. */
+int nnue_ema_update(float* ema, const float* params, int64_t count, float omd, const float* ema_omd_dev, nnue_stream_t stream);
+
+/* nnue_sgd_step_clip with the weight average above (after optimizer.step(), train.py:366). */
+int nnue_sgd_step_ema(float* params, float* grads, float* momentum_buf, int64_t count, float lr, float momentum,
+                      float weight_decay, float max_norm, float grad_scale, int first_step, float* norm_out, void* scratch,
+                      int64_t scratch_bytes, const float* ste_partial, int ste_chunks, int ste_fps, float* ste_d_thr,
+                      float* ste_d_weight, const float* ext_partial, int ext_count, int64_t ext_lo, int64_t ext_hi, float* coef_out,
+                      int ext_applied_elsewhere, const float* lr_dev, float weight_clip, const int64_t* clip_ranges,
+                      int n_clip_ranges, float* ema, float ema_omd, const float* ema_omd_dev, nnue_stream_t stream);
+
+/* nnue_adam_step_clip with the weight average above (after optimizer.step(), train.py:366). */
+int nnue_adam_step_ema(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int32_t* step_counter, int64_t count,
+                       float lr, float beta1, float beta2, float eps, float weight_decay, float max_norm, float grad_scale,
+                       float* norm_out, void* scratch, int64_t scratch_bytes, const float* lr_dev, float weight_clip,
+                       const int64_t* clip_ranges, int n_clip_ranges, float* ema, float ema_omd, const float* ema_omd_dev,
+                       nnue_stream_t stream);
+
+/* nnue_adam_step_ext_clip with the weight average above (after optimizer.step(), train.py:366). */
+int nnue_adam_step_ext_ema(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int32_t* step_counter, int64_t count,
+                           float lr, float beta1, float beta2, float eps, float weight_decay, float max_norm, float grad_scale,
+                           float* norm_out, void* scratch, int64_t scratch_bytes, const float* ext_partial, int ext_count,
+                           int64_t ext_lo, int64_t ext_hi, float* coef_out, int ext_applied_elsewhere, const float* lr_dev,
+                           float weight_clip, const int64_t* clip_ranges, int n_clip_ranges, float* ema, float ema_omd,
+                           const float* ema_omd_dev, nnue_stream_t stream);
+
+/* nnue_ftm_backward_weight_update_clip with the weight average above on the table rows it updates (after optimizer.step(),
+ * train.py:366): ema = the average's rows that match `weight`. */
+int nnue_ftm_backward_weight_update_ema(const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight,
+                                        float* momentum_rows, const float* coef, float lr, float momentum, float weight_decay,
+                                        float grad_scale, int first_step, float weight_clip, const float* lr_dev, float* ema,
+                                        float ema_omd, const float* ema_omd_dev, nnue_stream_t stream);
+
+/* nnue_ftm_backward_weight_update_forward_clip with the weight average above on the table rows it updates (after
+ * optimizer.step(), train.py:366): ema = the average's rows that match `weight`. */
+int nnue_ftm_backward_weight_update_forward_ema(const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight,
+                                                float* momentum_rows, const float* coef, float lr, float momentum,
+                                                float weight_decay, float grad_scale, int first_step, float weight_clip,
+                                                const float* lr_dev, const uint8_t* bits_next, const float* sink_next, int B_next,
+                                                const float* bias, float* out_next, void* scratch, int64_t scratch_bytes,
+                                                float* ema, float ema_omd, const float* ema_omd_dev, nnue_stream_t stream);
+
+/* nnue_ftm_backward_weight_update_adam_clip with the weight average above on the table rows it updates (after
+ * optimizer.step(), train.py:366): ema = the average's rows that match `weight`. */
+int nnue_ftm_backward_weight_update_adam_ema(const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight,
+                                             float* exp_avg_rows, float* exp_avg_sq_rows, const float* coef,
+                                             const int32_t* step_counter, float lr, float beta1, float beta2, float eps,
+                                             float weight_decay, float grad_scale, float weight_clip, const float* lr_dev,
+                                             float* ema, float ema_omd, const float* ema_omd_dev, nnue_stream_t stream);
+
+/* nnue_ftm_backward_weight_update_forward_adam_clip with the weight average above on the table rows it updates (after
+ * optimizer.step(), train.py:366): ema = the average's rows that match `weight`. */
+int nnue_ftm_backward_weight_update_forward_adam_ema(const uint8_t* bits, const float* d_out, int B, int F, int P, int L1,
+                                                     float* weight, float* exp_avg_rows, float* exp_avg_sq_rows, const float* coef,
+                                                     const int32_t* step_counter, float lr, float beta1, float beta2, float eps,
+                                                     float weight_decay, float grad_scale, float weight_clip, const float* lr_dev,
+                                                     const uint8_t* bits_next, const float* sink_next, int B_next, const float* bias,
+                                                     float* out_next, void* scratch, int64_t scratch_bytes, float* ema,
+                                                     float ema_omd, const float* ema_omd_dev, nnue_stream_t stream);
+
+/* nnue_multi_sgd_step_clip with the weight average above per segment (after optimizer.step(), train.py:366). */
+int nnue_multi_sgd_step_ema(float* const* params, float* const* grads, float* const* momentum_bufs, const int64_t* counts, int n,
+                            const float* lr, const float* momentum, const float* weight_decay, const int32_t* first_step,
+                            const float* weight_clip, float max_norm, float* norm_out, void* scratch, int64_t scratch_bytes,
+                            const float* lr_dev, float* const* ema, const float* ema_omd, nnue_stream_t stream);
+
+/* nnue_multi_adam_step_clip with the weight average above per segment (after optimizer.step(), train.py:366). */
+int nnue_multi_adam_step_ema(float* const* params, float* const* grads, float* const* exp_avgs, float* const* exp_avg_sqs,
+                             int32_t* const* step_counters, const int64_t* counts, int n, const float* lr, const float* beta1,
+                             const float* beta2, const float* eps, const float* weight_decay, const float* weight_clip,
+                             float max_norm, float* norm_out, void* scratch, int64_t scratch_bytes, const float* lr_dev,
+                             float* const* ema, const float* ema_omd, nnue_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

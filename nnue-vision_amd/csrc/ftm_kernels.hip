@@ -165,6 +165,17 @@ struct BwwAdamClipEpi : BwwAdamEpi {
   float wclip;
 };
 
+// Any of the four in-place epilogues with the weight average (include/nnue_hip.h, "weight average"): `ema` holds the rows that
+// match `weight`; the element the epilogue stores -- clamped where the clip is on -- also moves its average (optim_update.h,
+// ema_update).  omd_dev replaces omd as lr_dev replaces lr.  Types of their own again: the kernels without it keep their text.
+template <class Base>
+struct WithEma : Base {
+  static constexpr bool kEma = true;
+  float* __restrict__ ema;
+  float omd;
+  const float* __restrict__ omd_dev;
+};
+
 struct ValEpi {  // d_conv_out = acc where the position is active, else 0
   static constexpr bool kAU8 = false;
   static constexpr bool kFusedL1 = false;
@@ -613,6 +624,11 @@ template <class Epi>
 struct has_clip<Epi, decltype((void)Epi::kClip)> { static constexpr bool value = Epi::kClip; };
 
 template <class Epi, class = void>
+struct has_ema { static constexpr bool value = false; };
+template <class Epi>
+struct has_ema<Epi, decltype((void)Epi::kEma)> { static constexpr bool value = Epi::kEma; };
+
+template <class Epi, class = void>
 struct is_rmw { static constexpr bool value = false; };
 template <class Epi>
 struct is_rmw<Epi, decltype((void)Epi::kRmw)> { static constexpr bool value = Epi::kRmw; };
@@ -632,7 +648,10 @@ __device__ __forceinline__ void rmw_tile(float* __restrict__ smem, const Epi& ep
   const int r = lane & 15, q = lane >> 4;
   const float gs = epi.coef[0] * epi.scale;
   const float lr = epi.lr_dev ? epi.lr_dev[0] : epi.lr;
-  float4 w[PER], mo[PER];
+  constexpr bool kEma = has_ema<Epi>::value;
+  float omd = 0.0f;
+  if constexpr (kEma) omd = epi.omd_dev ? epi.omd_dev[0] : epi.omd;
+  float4 w[PER], mo[PER], ev[kEma ? PER : 1];
 #pragma unroll
   for (int u = 0; u < PER; ++u) {
     const int idx = tid + 256 * u, row = idx / (BN / 4), c4 = idx % (BN / 4);
@@ -641,6 +660,7 @@ __device__ __forceinline__ void rmw_tile(float* __restrict__ smem, const Epi& ep
     const size_t i = (size_t)m * epi.L1 + n;
     w[u] = ok ? nt_load4(epi.weight + i) : make_float4(0.f, 0.f, 0.f, 0.f);
     mo[u] = (ok && epi.momentum && !epi.first_step) ? nt_load4(epi.momentum + i) : make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (kEma) ev[u] = ok ? nt_load4(epi.ema + i) : make_float4(0.f, 0.f, 0.f, 0.f);  // requested with the parameters
   }
 #pragma unroll
   for (int i = 0; i < TM; ++i)
@@ -672,6 +692,9 @@ __device__ __forceinline__ void rmw_tile(float* __restrict__ smem, const Epi& ep
         wn.z = clip_weight(wn.z, epi.wclip); wn.w = clip_weight(wn.w, epi.wclip);
       }
       nt_store4(epi.weight + i, wn);
+      if constexpr (kEma)
+        nt_store4(epi.ema + i, make_float4(ema_update(ev[u].x, wn.x, omd), ema_update(ev[u].y, wn.y, omd), ema_update(ev[u].z, wn.z, omd),
+                                           ema_update(ev[u].w, wn.w, omd)));
     }
   }
 }
@@ -682,8 +705,9 @@ template <class Epi>
 struct is_adam<Epi, decltype((void)Epi::kAdam)> { static constexpr bool value = Epi::kAdam; };
 
 // rmw_tile for BwwAdamEpi: three streams read and three written per tile (parameters, exp_avg, exp_avg_sq), 96 KB in flight
-// per workgroup at 128 x 64.  As there: every load of the tile is requested after the K loop and before the first result is
-// combined; here they go through buffer descriptors whose window ends at table row M, so no load or store sits behind a
+// per workgroup at 128 x 64 -- with the weight average (WithEma) four streams and 128 KB: that form compiles to 212 registers
+// (178 + 32 AGPRs, no scratch) and two workgroups per CU where the plain one holds three at 168.  As there: every load of the
+// tile is requested after the K loop and before the first result is combined; here they go through buffer descriptors whose window ends at table row M, so no load or store sits behind a
 // branch (an element past the tile's rows or columns gets an offset outside the window: it reads zero and its stores are
 // dropped) and one s_waitcnt covers them; non-temporal, touched once per step.  The bias corrections (two double-precision
 // pow) are formed once per workgroup -- a workgroup owns one tile -- BEFORE the loads are requested: formed while the 96
@@ -700,6 +724,14 @@ __device__ __forceinline__ void rmw_tile_adam(float* __restrict__ smem, const Ep
   const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc(epi.weight, 0, bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rsm = __builtin_amdgcn_make_buffer_rsrc(epi.exp_avg, 0, bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rsv = __builtin_amdgcn_make_buffer_rsrc(epi.exp_avg_sq, 0, bytes, 0x00020000);
+  constexpr bool kEma = has_ema<Epi>::value;
+  float* ema_rows = nullptr;
+  float omd = 0.0f;
+  if constexpr (kEma) {
+    ema_rows = epi.ema;
+    omd = epi.omd_dev ? epi.omd_dev[0] : epi.omd;
+  }
+  const __amdgpu_buffer_rsrc_t rse = __builtin_amdgcn_make_buffer_rsrc(kEma ? ema_rows : epi.weight, 0, bytes, 0x00020000);
   auto off_of = [&](int u) {
     const int idx = tid + 256 * u, row = idx / (BN / 4), c4 = idx % (BN / 4);
     const int m = m_base + row, n = n_base + 4 * c4;
@@ -708,9 +740,13 @@ __device__ __forceinline__ void rmw_tile_adam(float* __restrict__ smem, const Ep
   const float gs = epi.coef[0] * epi.scale;
   const float lr = epi.lr_dev ? epi.lr_dev[0] : epi.lr;
   const AdamBias bc = adam_bias_correction(lr, epi.beta1, epi.beta2, epi.step_counter[0]);
-  u32x4 w[PER], mo[PER], vv[PER];
+  u32x4 w[PER], mo[PER], vv[PER], ev[kEma ? PER : 1];
 #pragma unroll
   for (int u = 0; u < PER; ++u) w[u] = __builtin_amdgcn_raw_buffer_load_b128(rsw, off_of(u), 0, 2);
+  if constexpr (kEma) {  // the fourth stream, requested with the parameters
+#pragma unroll
+    for (int u = 0; u < PER; ++u) ev[u] = __builtin_amdgcn_raw_buffer_load_b128(rse, off_of(u), 0, 2);
+  }
 #pragma unroll
   for (int u = 0; u < PER; ++u) mo[u] = __builtin_amdgcn_raw_buffer_load_b128(rsm, off_of(u), 0, 2);
 #pragma unroll
@@ -727,7 +763,7 @@ __device__ __forceinline__ void rmw_tile_adam(float* __restrict__ smem, const Ep
     const int idx = tid + 256 * u, row = idx / (BN / 4), c4 = idx % (BN / 4);
     const float4 g = *reinterpret_cast<const float4*>(smem + row * LD + 4 * c4);
     const float gv[4] = {g.x, g.y, g.z, g.w};
-    u32x4 wn, mn, vn;
+    u32x4 wn, mn, vn, en;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {  // the arithmetic of adam_apply_kernel, element by element (fused multiply-adds pinned)
       float mi = __uint_as_float(mo[u][e]), vi = __uint_as_float(vv[u][e]);
@@ -736,8 +772,10 @@ __device__ __forceinline__ void rmw_tile_adam(float* __restrict__ smem, const Ep
       wn[e] = __float_as_uint(wf);
       mn[e] = __float_as_uint(mi);
       vn[e] = __float_as_uint(vi);
+      if constexpr (kEma) en[e] = __float_as_uint(ema_update(__uint_as_float(ev[u][e]), wf, omd));
     }
     const int off = off_of(u);
+    if constexpr (kEma) __builtin_amdgcn_raw_buffer_store_b128(en, rse, off, 0, 2);
     __builtin_amdgcn_raw_buffer_store_b128(mn, rsm, off, 0, 2);
     __builtin_amdgcn_raw_buffer_store_b128(vn, rsv, off, 0, 2);
     __builtin_amdgcn_raw_buffer_store_b128(wn, rsw, off, 0, 2);
@@ -3061,7 +3099,7 @@ Args make_upd_fwd(const uint8_t* bits, const float* d_out, int B, int F, int P, 
 
 // The fused pass's launch: the scratch check, the forward's plan (slabs, slab length, column tiles, XCD remap) into `a`, the kernel
 // of the product's K-tile count, ftm_finish_kernel.  first: first step of an SGD momentum buffer (written, not read).
-template <bool kAdam, bool kClip>
+template <bool kAdam, bool kClip, bool kEma = false>
 int update_forward_launch(const char* who, std::conditional_t<kAdam, UpdFwdAdam, UpdFwd> a, int F, bool first, const NextFwd& nx, nnue_stream_t stream) {
   const Shape s = plan(a.Bn, a.L1, a.direct, true, true, true);
   const int64_t need = (int64_t)s.ksplit * a.Bn * a.L1 * (int64_t)sizeof(float);
@@ -3076,10 +3114,10 @@ int update_forward_launch(const char* who, std::conditional_t<kAdam, UpdFwdAdam,
   const bool mom = a.momentum != nullptr;
   auto go = [&](auto nk) {
     constexpr int NK = decltype(nk)::value;
-    if constexpr (kAdam) hipLaunchKernelGGL((ftm_update_forward_kernel<NK, true, false, true, kClip>), grid, dim3(256), 0, st, a);
-    else if (!mom) hipLaunchKernelGGL((ftm_update_forward_kernel<NK, false, false, false, kClip>), grid, dim3(256), 0, st, a);
-    else if (first) hipLaunchKernelGGL((ftm_update_forward_kernel<NK, true, true, false, kClip>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((ftm_update_forward_kernel<NK, true, false, false, kClip>), grid, dim3(256), 0, st, a);
+    if constexpr (kAdam) hipLaunchKernelGGL((ftm_update_forward_kernel<NK, true, false, true, kClip, kEma>), grid, dim3(256), 0, st, a);
+    else if (!mom) hipLaunchKernelGGL((ftm_update_forward_kernel<NK, false, false, false, kClip, kEma>), grid, dim3(256), 0, st, a);
+    else if (first) hipLaunchKernelGGL((ftm_update_forward_kernel<NK, true, true, false, kClip, kEma>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((ftm_update_forward_kernel<NK, true, false, false, kClip, kEma>), grid, dim3(256), 0, st, a);
   };
   switch ((a.B + 63) / 64) {  // K tiles of the weight-gradient product (nnue_ftm_update_forward_supported: 1, 2, 4, 8 or 16)
     case 1: go(std::integral_constant<int, 1>{}); break;
@@ -3103,10 +3141,28 @@ int wclip_ok(const char* who, float weight_clip) {
   return NNUE_OK;
 }
 
+// The weight average as the table entry points take it (include/nnue_hip.h, "weight average"): ema == NULL is off and launches
+// what the _clip form launches; otherwise the rows must be 16-byte aligned and a rate given by value must lie in (0, 1].
+int table_ema_ok(const char* who, const float* ema, float omd, const float* omd_dev) {
+  if (!ema) return NNUE_OK;
+  NNUE_REQUIRE(omd_dev || (omd > 0.0f && omd <= 1.0f), NNUE_E_ARG, "%s: ema_omd = %g must lie in (0, 1]", who, (double)omd);
+  NNUE_REQUIRE(nnue_aligned16(ema), NNUE_E_ARG, "%s: the average's rows must be 16-byte aligned", who);
+  return NNUE_OK;
+}
+
+// update_launch with the epilogue `epi`, or -- with an average -- with its WithEma form
+template <class Epi>
+int update_launch_ema(const char* who, const uint8_t* bits, const float* d_out, int B, int P, int L1, int direct, const Epi& epi, float* ema,
+                      float omd, const float* omd_dev, nnue_stream_t stream) {
+  if (ema) return update_launch(who, bits, d_out, B, P, L1, direct, WithEma<Epi>{epi, ema, omd, omd_dev}, stream);
+  return update_launch(who, bits, d_out, B, P, L1, direct, epi, stream);
+}
+
 int weight_update_sgd(const char* who, const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight,
                       float* momentum_rows, const float* coef, float lr, float momentum, float weight_decay, float grad_scale, int first_step,
-                      float weight_clip, const float* lr_dev, nnue_stream_t stream) {
+                      float weight_clip, const float* lr_dev, float* ema, float omd, const float* omd_dev, nnue_stream_t stream) {
   if (const int rc = wclip_ok(who, weight_clip)) return rc;
+  if (const int rc = table_ema_ok(who, ema, omd, omd_dev)) return rc;
   if (const int rc = update_ptrs_nonnull(who, bits, d_out, weight, coef, nullptr)) return rc;
   NNUE_REQUIRE(momentum == 0.0f || momentum_rows, NNUE_E_ARG, "%s: momentum %g needs the momentum rows", who, momentum);
   NNUE_REQUIRE(shape_ok(B, F, P, L1), NNUE_E_ARG, "%s: B=%d F=%d P=%d L1=%d out of range", who, B, F, P, L1);
@@ -3115,16 +3171,24 @@ int weight_update_sgd(const char* who, const uint8_t* bits, const float* d_out, 
   const int direct = (F - 1 < P) ? F - 1 : P;
   if (direct <= 0) return NNUE_OK;
   const BwwSgdEpi epi{weight, momentum == 0.0f ? nullptr : momentum_rows, coef, L1, lr, momentum, weight_decay, grad_scale, first_step, /*xcd_remap=*/1, lr_dev};
-  if (weight_clip > 0.0f) return update_launch(who, bits, d_out, B, P, L1, direct, BwwSgdClipEpi{epi, weight_clip}, stream);
-  return update_launch(who, bits, d_out, B, P, L1, direct, epi, stream);
+  if (weight_clip > 0.0f) return update_launch_ema(who, bits, d_out, B, P, L1, direct, BwwSgdClipEpi{epi, weight_clip}, ema, omd, omd_dev, stream);
+  return update_launch_ema(who, bits, d_out, B, P, L1, direct, epi, ema, omd, omd_dev, stream);
 }
 }  // namespace
+
+extern "C" int nnue_ftm_backward_weight_update_ema(const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight,
+                                                   float* momentum_rows, const float* coef, float lr, float momentum, float weight_decay,
+                                                   float grad_scale, int first_step, float weight_clip, const float* lr_dev, float* ema,
+                                                   float ema_omd, const float* ema_omd_dev, nnue_stream_t stream) {
+  return weight_update_sgd("nnue_ftm_backward_weight_update_ema", bits, d_out, B, F, P, L1, weight, momentum_rows, coef, lr, momentum,
+                           weight_decay, grad_scale, first_step, weight_clip, lr_dev, ema, ema_omd, ema_omd_dev, stream);
+}
 
 extern "C" int nnue_ftm_backward_weight_update(const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight,
                                                float* momentum_rows, const float* coef, float lr, float momentum, float weight_decay,
                                                float grad_scale, int first_step, const float* lr_dev, nnue_stream_t stream) {
   return weight_update_sgd("nnue_ftm_backward_weight_update", bits, d_out, B, F, P, L1, weight, momentum_rows, coef, lr, momentum, weight_decay,
-                           grad_scale, first_step, 0.0f, lr_dev, stream);
+                           grad_scale, first_step, 0.0f, lr_dev, nullptr, 0.0f, nullptr, stream);
 }
 
 extern "C" int nnue_ftm_backward_weight_update_clip(const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight,
@@ -3132,7 +3196,7 @@ extern "C" int nnue_ftm_backward_weight_update_clip(const uint8_t* bits, const f
                                                     float grad_scale, int first_step, float weight_clip, const float* lr_dev,
                                                     nnue_stream_t stream) {
   return weight_update_sgd("nnue_ftm_backward_weight_update_clip", bits, d_out, B, F, P, L1, weight, momentum_rows, coef, lr, momentum,
-                           weight_decay, grad_scale, first_step, weight_clip, lr_dev, stream);
+                           weight_decay, grad_scale, first_step, weight_clip, lr_dev, nullptr, 0.0f, nullptr, stream);
 }
 
 // nnue_ftm_backward_weight_update + nnue_ftm_forward of the NEXT step's map in one pass over the table (update_forward.h).
@@ -3151,9 +3215,11 @@ extern "C" int nnue_ftm_update_forward_supported(int B, int B_next, int F, int P
 namespace {
 int weight_update_forward_sgd(const char* who, const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight,
                               float* momentum_rows, const float* coef, float lr, float momentum, float weight_decay, float grad_scale,
-                              int first_step, float weight_clip, const float* lr_dev, const NextFwd& nx, int B_next, nnue_stream_t stream) {
+                              int first_step, float weight_clip, const float* lr_dev, const NextFwd& nx, int B_next, float* ema, float omd,
+                              const float* omd_dev, nnue_stream_t stream) {
   const uint8_t* bits_next = nx.bits_next;
   if (const int rc = wclip_ok(who, weight_clip)) return rc;
+  if (const int rc = table_ema_ok(who, ema, omd, omd_dev)) return rc;
   if (const int rc = update_ptrs_nonnull(who, bits, d_out, weight, coef, &nx)) return rc;
   NNUE_REQUIRE(momentum == 0.0f || momentum_rows, NNUE_E_ARG, "%s: momentum %g needs the momentum rows", who, momentum);
   NNUE_REQUIRE(nnue_ftm_update_forward_supported(B, B_next, F, P, L1), NNUE_E_SHAPE,
@@ -3162,8 +3228,14 @@ int weight_update_forward_sgd(const char* who, const uint8_t* bits, const float*
   UpdFwd a = make_upd_fwd<UpdFwd>(bits, d_out, B, F, P, L1, weight, momentum == 0.0f ? nullptr : momentum_rows, coef, lr_dev, lr, momentum,
                                   weight_decay, grad_scale, bits_next, B_next);
   a.wclip = weight_clip;
-  if (weight_clip > 0.0f) return update_forward_launch<false, true>(who, a, F, a.momentum && first_step, nx, stream);
-  return update_forward_launch<false, false>(who, a, F, a.momentum && first_step, nx, stream);
+  a.ema = ema;
+  a.omd = omd;
+  a.omd_dev = omd_dev;
+  const bool first = a.momentum && first_step;
+  if (ema) return weight_clip > 0.0f ? update_forward_launch<false, true, true>(who, a, F, first, nx, stream)
+                                     : update_forward_launch<false, false, true>(who, a, F, first, nx, stream);
+  if (weight_clip > 0.0f) return update_forward_launch<false, true>(who, a, F, first, nx, stream);
+  return update_forward_launch<false, false>(who, a, F, first, nx, stream);
 }
 }  // namespace
 
@@ -3174,7 +3246,7 @@ extern "C" int nnue_ftm_backward_weight_update_forward(const uint8_t* bits, cons
                                                        int64_t scratch_bytes, nnue_stream_t stream) {
   return weight_update_forward_sgd("nnue_ftm_backward_weight_update_forward", bits, d_out, B, F, P, L1, weight, momentum_rows, coef, lr, momentum,
                                    weight_decay, grad_scale, first_step, 0.0f, lr_dev,
-                                   NextFwd{bits_next, sink_next, bias, out_next, scratch, scratch_bytes}, B_next, stream);
+                                   NextFwd{bits_next, sink_next, bias, out_next, scratch, scratch_bytes}, B_next, nullptr, 0.0f, nullptr, stream);
 }
 
 extern "C" int nnue_ftm_backward_weight_update_forward_clip(const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight,
@@ -3185,7 +3257,18 @@ extern "C" int nnue_ftm_backward_weight_update_forward_clip(const uint8_t* bits,
                                                             nnue_stream_t stream) {
   return weight_update_forward_sgd("nnue_ftm_backward_weight_update_forward_clip", bits, d_out, B, F, P, L1, weight, momentum_rows, coef, lr,
                                    momentum, weight_decay, grad_scale, first_step, weight_clip, lr_dev,
-                                   NextFwd{bits_next, sink_next, bias, out_next, scratch, scratch_bytes}, B_next, stream);
+                                   NextFwd{bits_next, sink_next, bias, out_next, scratch, scratch_bytes}, B_next, nullptr, 0.0f, nullptr, stream);
+}
+
+extern "C" int nnue_ftm_backward_weight_update_forward_ema(const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight,
+                                                           float* momentum_rows, const float* coef, float lr, float momentum,
+                                                           float weight_decay, float grad_scale, int first_step, float weight_clip,
+                                                           const float* lr_dev, const uint8_t* bits_next, const float* sink_next, int B_next,
+                                                           const float* bias, float* out_next, void* scratch, int64_t scratch_bytes,
+                                                           float* ema, float ema_omd, const float* ema_omd_dev, nnue_stream_t stream) {
+  return weight_update_forward_sgd("nnue_ftm_backward_weight_update_forward_ema", bits, d_out, B, F, P, L1, weight, momentum_rows, coef, lr,
+                                   momentum, weight_decay, grad_scale, first_step, weight_clip, lr_dev,
+                                   NextFwd{bits_next, sink_next, bias, out_next, scratch, scratch_bytes}, B_next, ema, ema_omd, ema_omd_dev, stream);
 }
 
 // ---- ... and with Adam (train.py:465-470): BwwAdamEpi / the kAdam form of the fused pass -----------------------------------------
@@ -3207,24 +3290,27 @@ int adam_table_args_ok(const char* who, const void* exp_avg_rows, const void* ex
 namespace {
 int weight_update_adam(const char* who, const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight, float* exp_avg_rows,
                        float* exp_avg_sq_rows, const float* coef, const int32_t* step_counter, float lr, float beta1, float beta2, float eps,
-                       float weight_decay, float grad_scale, float weight_clip, const float* lr_dev, nnue_stream_t stream) {
+                       float weight_decay, float grad_scale, float weight_clip, const float* lr_dev, float* ema, float omd, const float* omd_dev,
+                       nnue_stream_t stream) {
   if (const int rc = wclip_ok(who, weight_clip)) return rc;
+  if (const int rc = table_ema_ok(who, ema, omd, omd_dev)) return rc;
   if (const int rc = update_ptrs_nonnull(who, bits, d_out, weight, coef, nullptr)) return rc;
   if (const int rc = adam_table_args_ok(who, exp_avg_rows, exp_avg_sq_rows, step_counter, B, F, P, L1, beta1, beta2, eps)) return rc;
   if (const int rc = update_ptrs_aligned(who, bits, d_out, weight, nullptr, nullptr)) return rc;
   const int direct = (F - 1 < P) ? F - 1 : P;
   if (direct <= 0) return NNUE_OK;
   const BwwAdamEpi epi{weight, exp_avg_rows, exp_avg_sq_rows, coef, step_counter, L1, lr, beta1, beta2, eps, weight_decay, grad_scale, /*xcd_remap=*/1, lr_dev};
-  if (weight_clip > 0.0f) return update_launch(who, bits, d_out, B, P, L1, direct, BwwAdamClipEpi{epi, weight_clip}, stream);
-  return update_launch(who, bits, d_out, B, P, L1, direct, epi, stream);
+  if (weight_clip > 0.0f) return update_launch_ema(who, bits, d_out, B, P, L1, direct, BwwAdamClipEpi{epi, weight_clip}, ema, omd, omd_dev, stream);
+  return update_launch_ema(who, bits, d_out, B, P, L1, direct, epi, ema, omd, omd_dev, stream);
 }
 
 int weight_update_forward_adam(const char* who, const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight,
                                float* exp_avg_rows, float* exp_avg_sq_rows, const float* coef, const int32_t* step_counter, float lr, float beta1,
                                float beta2, float eps, float weight_decay, float grad_scale, float weight_clip, const float* lr_dev,
-                               const NextFwd& nx, int B_next, nnue_stream_t stream) {
+                               const NextFwd& nx, int B_next, float* ema, float omd, const float* omd_dev, nnue_stream_t stream) {
   const uint8_t* bits_next = nx.bits_next;
   if (const int rc = wclip_ok(who, weight_clip)) return rc;
+  if (const int rc = table_ema_ok(who, ema, omd, omd_dev)) return rc;
   if (const int rc = update_ptrs_nonnull(who, bits, d_out, weight, coef, &nx)) return rc;
   if (const int rc = adam_table_args_ok(who, exp_avg_rows, exp_avg_sq_rows, step_counter, B, F, P, L1, beta1, beta2, eps)) return rc;
   NNUE_REQUIRE(nnue_ftm_update_forward_supported(B, B_next, F, P, L1), NNUE_E_SHAPE,
@@ -3238,6 +3324,11 @@ int weight_update_forward_adam(const char* who, const uint8_t* bits, const float
   a.beta2 = beta2;
   a.eps = eps;
   a.wclip = weight_clip;
+  a.ema = ema;
+  a.omd = omd;
+  a.omd_dev = omd_dev;
+  if (ema) return weight_clip > 0.0f ? update_forward_launch<true, true, true>(who, a, F, false, nx, stream)
+                                     : update_forward_launch<true, false, true>(who, a, F, false, nx, stream);
   if (weight_clip > 0.0f) return update_forward_launch<true, true>(who, a, F, false, nx, stream);
   return update_forward_launch<true, false>(who, a, F, false, nx, stream);
 }
@@ -3248,7 +3339,7 @@ extern "C" int nnue_ftm_backward_weight_update_adam(const uint8_t* bits, const f
                                                     const int32_t* step_counter, float lr, float beta1, float beta2, float eps,
                                                     float weight_decay, float grad_scale, const float* lr_dev, nnue_stream_t stream) {
   return weight_update_adam("nnue_ftm_backward_weight_update_adam", bits, d_out, B, F, P, L1, weight, exp_avg_rows, exp_avg_sq_rows, coef,
-                            step_counter, lr, beta1, beta2, eps, weight_decay, grad_scale, 0.0f, lr_dev, stream);
+                            step_counter, lr, beta1, beta2, eps, weight_decay, grad_scale, 0.0f, lr_dev, nullptr, 0.0f, nullptr, stream);
 }
 
 extern "C" int nnue_ftm_backward_weight_update_adam_clip(const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight,
@@ -3257,7 +3348,28 @@ extern "C" int nnue_ftm_backward_weight_update_adam_clip(const uint8_t* bits, co
                                                          float weight_decay, float grad_scale, float weight_clip, const float* lr_dev,
                                                          nnue_stream_t stream) {
   return weight_update_adam("nnue_ftm_backward_weight_update_adam_clip", bits, d_out, B, F, P, L1, weight, exp_avg_rows, exp_avg_sq_rows, coef,
-                            step_counter, lr, beta1, beta2, eps, weight_decay, grad_scale, weight_clip, lr_dev, stream);
+                            step_counter, lr, beta1, beta2, eps, weight_decay, grad_scale, weight_clip, lr_dev, nullptr, 0.0f, nullptr, stream);
+}
+
+extern "C" int nnue_ftm_backward_weight_update_adam_ema(const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight,
+                                                        float* exp_avg_rows, float* exp_avg_sq_rows, const float* coef,
+                                                        const int32_t* step_counter, float lr, float beta1, float beta2, float eps,
+                                                        float weight_decay, float grad_scale, float weight_clip, const float* lr_dev,
+                                                        float* ema, float ema_omd, const float* ema_omd_dev, nnue_stream_t stream) {
+  return weight_update_adam("nnue_ftm_backward_weight_update_adam_ema", bits, d_out, B, F, P, L1, weight, exp_avg_rows, exp_avg_sq_rows, coef,
+                            step_counter, lr, beta1, beta2, eps, weight_decay, grad_scale, weight_clip, lr_dev, ema, ema_omd, ema_omd_dev, stream);
+}
+
+extern "C" int nnue_ftm_backward_weight_update_forward_adam_ema(const uint8_t* bits, const float* d_out, int B, int F, int P, int L1,
+                                                                float* weight, float* exp_avg_rows, float* exp_avg_sq_rows, const float* coef,
+                                                                const int32_t* step_counter, float lr, float beta1, float beta2, float eps,
+                                                                float weight_decay, float grad_scale, float weight_clip, const float* lr_dev,
+                                                                const uint8_t* bits_next, const float* sink_next, int B_next,
+                                                                const float* bias, float* out_next, void* scratch, int64_t scratch_bytes,
+                                                                float* ema, float ema_omd, const float* ema_omd_dev, nnue_stream_t stream) {
+  return weight_update_forward_adam("nnue_ftm_backward_weight_update_forward_adam_ema", bits, d_out, B, F, P, L1, weight, exp_avg_rows,
+                                    exp_avg_sq_rows, coef, step_counter, lr, beta1, beta2, eps, weight_decay, grad_scale, weight_clip, lr_dev,
+                                    NextFwd{bits_next, sink_next, bias, out_next, scratch, scratch_bytes}, B_next, ema, ema_omd, ema_omd_dev, stream);
 }
 
 extern "C" int nnue_ftm_backward_weight_update_forward_adam(const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight,
@@ -3268,7 +3380,7 @@ extern "C" int nnue_ftm_backward_weight_update_forward_adam(const uint8_t* bits,
                                                             float* out_next, void* scratch, int64_t scratch_bytes, nnue_stream_t stream) {
   return weight_update_forward_adam("nnue_ftm_backward_weight_update_forward_adam", bits, d_out, B, F, P, L1, weight, exp_avg_rows,
                                     exp_avg_sq_rows, coef, step_counter, lr, beta1, beta2, eps, weight_decay, grad_scale, 0.0f, lr_dev,
-                                    NextFwd{bits_next, sink_next, bias, out_next, scratch, scratch_bytes}, B_next, stream);
+                                    NextFwd{bits_next, sink_next, bias, out_next, scratch, scratch_bytes}, B_next, nullptr, 0.0f, nullptr, stream);
 }
 
 extern "C" int nnue_ftm_backward_weight_update_forward_adam_clip(const uint8_t* bits, const float* d_out, int B, int F, int P, int L1,
@@ -3280,7 +3392,7 @@ extern "C" int nnue_ftm_backward_weight_update_forward_adam_clip(const uint8_t* 
                                                                  nnue_stream_t stream) {
   return weight_update_forward_adam("nnue_ftm_backward_weight_update_forward_adam_clip", bits, d_out, B, F, P, L1, weight, exp_avg_rows,
                                     exp_avg_sq_rows, coef, step_counter, lr, beta1, beta2, eps, weight_decay, grad_scale, weight_clip, lr_dev,
-                                    NextFwd{bits_next, sink_next, bias, out_next, scratch, scratch_bytes}, B_next, stream);
+                                    NextFwd{bits_next, sink_next, bias, out_next, scratch, scratch_bytes}, B_next, nullptr, 0.0f, nullptr, stream);
 }
 
 // Which matrix unit a product of this shape runs on (the launch policy above, for reporting: bench.py prices a kernel

@@ -111,6 +111,17 @@ struct FlatClip {
   __device__ __forceinline__ float apply(int64_t i, float w) const { return covers(i) ? clip_weight(w, bound) : w; }
 };
 
+// The weight average of a flat buffer (include/nnue_hip.h, "weight average"), by value in the kernel arguments behind the clip:
+// the average's buffer, laid out like the parameters (NULL: off), and its rate 1 - decay as a float or -- where omd_dev is not
+// NULL -- as the device scalar that replaces it, as lr_dev replaces lr.  The SGD kernels are compiled once more with kEma (the
+// kernels without it keep their text); the Adam kernels branch on the pointer, as they do on the clip's bound.
+struct FlatEma {
+  float* __restrict__ e;
+  float omd;
+  const float* __restrict__ omd_dev;
+  __device__ __forceinline__ float rate() const { return omd_dev ? omd_dev[0] : omd; }
+};
+
 // Block partial of sum (g * scale)^2: 16-byte loads, four independent chains per thread (the 268 MB gradient of
 // the 224x224 configuration is one streaming read; a dependent scalar chain reached only 1.25 TB/s).
 __device__ __forceinline__ float sqnorm_block_partial(const float* __restrict__ g, int64_t count, float scale, float* red,
@@ -205,17 +216,19 @@ __global__ __launch_bounds__(256) void sqnorm_stage1_ste(const float* __restrict
 
 // Every block re-derives the norm from the kNormBlocks partials (4 KiB, L2-resident) in the same
 // fixed order, then streams its share of the update.
-template <bool kClip>
+template <bool kClip, bool kEma>
 __global__ __launch_bounds__(256) void sgd_apply_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                         float* __restrict__ m, int64_t count, float lr, float momentum,
                                                         float wd, float max_norm, float scale, int first_step,
                                                         const float* __restrict__ partial, int nparts,
                                                         float* __restrict__ norm_out, const float* __restrict__ ext_partial,
                                                         int ext_count, float* __restrict__ coef_out, int64_t skip_lo, int64_t skip_hi,
-                                                        const float* __restrict__ lr_dev, const FlatClip fc) {
+                                                        const float* __restrict__ lr_dev, const FlatClip fc, const FlatEma fe) {
   __shared__ double red[4];
   __shared__ float coef_s;
   if (lr_dev) lr = lr_dev[0];  // the learning rate as a device scalar: a scheduler changes it without re-capturing the step
+  float omd = 0.0f;
+  if constexpr (kEma) omd = fe.rate();
   // The first kPre passes of this thread's share are requested BEFORE the norm is re-derived: after a kernel boundary
   // both the partials and the parameters are first touches (~2 us each from a cold L2), and the two waits would
   // otherwise run one after the other.  Unconditional loads from clamped indices; results used only where valid.  (live == 0,
@@ -224,7 +237,7 @@ __global__ __launch_bounds__(256) void sgd_apply_kernel(float* __restrict__ p, c
   const int64_t stride = (int64_t)gridDim.x * 256;
   const int64_t hole = skip_hi - skip_lo;  // 0: everything is updated here
   const int64_t live = count - hole, j0 = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  float pw[kPre] = {}, pg[kPre] = {}, pm[kPre] = {};
+  float pw[kPre] = {}, pg[kPre] = {}, pm[kPre] = {}, pe[kPre] = {};
 #pragma unroll
   for (int u = 0; u < kPre && live > 0; ++u) {
     const int64_t j = j0 + u * stride < live ? j0 + u * stride : 0;
@@ -232,6 +245,7 @@ __global__ __launch_bounds__(256) void sgd_apply_kernel(float* __restrict__ p, c
     pw[u] = p[i];
     pg[u] = g[i];
     pm[u] = (m && !first_step) ? m[i] : 0.0f;
+    if constexpr (kEma) pe[u] = fe.e[i];  // the average is requested together with the parameters
   }
   float clip = 1.0f;
   if (max_norm > 0.0f || norm_out || coef_out) {
@@ -265,6 +279,7 @@ __global__ __launch_bounds__(256) void sgd_apply_kernel(float* __restrict__ p, c
       if constexpr (kClip) wn = fc.apply(i, wn);
       p[i] = wn;
       if (m) m[i] = mn;
+      if constexpr (kEma) fe.e[i] = ema_update(pe[u], wn, omd);
     }
   }
   for (int64_t j = j0 + kPre * stride; j < live; j += stride) {
@@ -274,6 +289,7 @@ __global__ __launch_bounds__(256) void sgd_apply_kernel(float* __restrict__ p, c
     if constexpr (kClip) wn = fc.apply(i, wn);
     p[i] = wn;
     if (m) m[i] = mn;
+    if constexpr (kEma) fe.e[i] = ema_update(fe.e[i], wn, omd);
   }
 }
 
@@ -281,16 +297,18 @@ __global__ __launch_bounds__(256) void sgd_apply_kernel(float* __restrict__ p, c
 // 16 bytes): one float4 per thread and pass, the first two passes requested before the norm is re-derived.  (The scalar kernel
 // stays for big buffers: with 16-byte accesses it streamed 1.34 GB slower, 225-257 vs 211 us.)  kClip: every boundary of the
 // clip's ranges is a multiple of 4 (the entry point checks it), so a float4 lies inside a range or outside it.
-template <bool kClip>
+template <bool kClip, bool kEma>
 __global__ __launch_bounds__(256) void sgd_apply_vec_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                             int64_t count, float lr, float momentum, float wd, float max_norm, float scale,
                                                             int first_step, const float* __restrict__ partial, int nparts,
                                                             float* __restrict__ norm_out, const float* __restrict__ ext_partial, int ext_count,
                                                             float* __restrict__ coef_out, int64_t skip_lo, int64_t skip_hi,
-                                                            const float* __restrict__ lr_dev, const FlatClip fc) {
+                                                            const float* __restrict__ lr_dev, const FlatClip fc, const FlatEma fe) {
   __shared__ double red[4];
   __shared__ float coef_s;
   if (lr_dev) lr = lr_dev[0];
+  float omd = 0.0f;
+  if constexpr (kEma) omd = fe.rate();
   constexpr int kPre = 2;
   const int64_t stride = (int64_t)gridDim.x * 256;
   const int64_t hole4 = (skip_hi - skip_lo) >> 2, lo4 = skip_lo >> 2, live4 = (count >> 2) - hole4;
@@ -298,7 +316,8 @@ __global__ __launch_bounds__(256) void sgd_apply_vec_kernel(float* __restrict__ 
   const float4* __restrict__ p4 = reinterpret_cast<const float4*>(p);
   const float4* __restrict__ g4 = reinterpret_cast<const float4*>(g);
   const float4* __restrict__ m4 = reinterpret_cast<const float4*>(m);
-  float4 pw[kPre] = {}, pg[kPre] = {}, pm[kPre] = {};
+  float4* __restrict__ e4 = reinterpret_cast<float4*>(fe.e);
+  float4 pw[kPre] = {}, pg[kPre] = {}, pm[kPre] = {}, pe[kPre] = {};
 #pragma unroll
   for (int u = 0; u < kPre && live4 > 0; ++u) {  // live4 == 0: nothing to read (see sgd_apply_kernel)
     const int64_t j = j0 + u * stride < live4 ? j0 + u * stride : 0;
@@ -306,6 +325,7 @@ __global__ __launch_bounds__(256) void sgd_apply_vec_kernel(float* __restrict__ 
     pw[u] = p4[i];
     pg[u] = g4[i];
     pm[u] = (m && !first_step) ? m4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (kEma) pe[u] = e4[i];  // the average is requested together with the parameters
   }
   float clip = 1.0f;
   if (max_norm > 0.0f || norm_out || coef_out) {
@@ -332,7 +352,7 @@ __global__ __launch_bounds__(256) void sgd_apply_vec_kernel(float* __restrict__ 
   auto one = [&](float w, float gv, float mv, float& m_new) {
     return sgd_update(w, gv, mv, m_new, gs, lr, momentum, wd, m != nullptr, first_step);
   };
-  auto apply = [&](int64_t i, const float4& w, const float4& gv, const float4& mv) {
+  auto apply = [&](int64_t i, const float4& w, const float4& gv, const float4& mv, const float4& ev) {
     float4 mn, wn;
     wn.x = one(w.x, gv.x, mv.x, mn.x); wn.y = one(w.y, gv.y, mv.y, mn.y);
     wn.z = one(w.z, gv.z, mv.z, mn.z); wn.w = one(w.w, gv.w, mv.w, mn.w);
@@ -344,15 +364,19 @@ __global__ __launch_bounds__(256) void sgd_apply_vec_kernel(float* __restrict__ 
     }
     if (m) reinterpret_cast<float4*>(m)[i] = mn;
     reinterpret_cast<float4*>(p)[i] = wn;
+    if constexpr (kEma)
+      e4[i] = make_float4(ema_update(ev.x, wn.x, omd), ema_update(ev.y, wn.y, omd), ema_update(ev.z, wn.z, omd), ema_update(ev.w, wn.w, omd));
   };
 #pragma unroll
   for (int u = 0; u < kPre; ++u) {
     const int64_t j = j0 + u * stride;
-    if (j < live4) apply(j < lo4 ? j : j + hole4, pw[u], pg[u], pm[u]);
+    if (j < live4) apply(j < lo4 ? j : j + hole4, pw[u], pg[u], pm[u], pe[u]);
   }
   for (int64_t j = j0 + kPre * stride; j < live4; j += stride) {
     const int64_t i = j < lo4 ? j : j + hole4;
-    apply(i, p4[i], g4[i], (m && !first_step) ? m4[i] : make_float4(0.f, 0.f, 0.f, 0.f));
+    float4 ev = make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (kEma) ev = e4[i];
+    apply(i, p4[i], g4[i], (m && !first_step) ? m4[i] : make_float4(0.f, 0.f, 0.f, 0.f), ev);
   }
 }
 
@@ -377,7 +401,7 @@ __global__ __launch_bounds__(256) void adam_apply_kernel(float* __restrict__ p, 
                                                          float max_norm, float scale, const int* __restrict__ step_counter,
                                                          const float* __restrict__ partial, int nparts,
                                                          float* __restrict__ norm_out, const float* __restrict__ lr_dev,
-                                                         const FlatClip fc) {
+                                                         const FlatClip fc, const FlatEma fe) {
   __shared__ double red[4];
   __shared__ float coef_s;
   if (lr_dev) lr = lr_dev[0];
@@ -395,6 +419,7 @@ __global__ __launch_bounds__(256) void adam_apply_kernel(float* __restrict__ p, 
   __syncthreads();
   const float gs = coef_s * scale;
   const AdamBias bc = adam_bias_correction(lr, beta1, beta2, step_counter[0]);
+  const float omd = fe.e ? fe.rate() : 0.0f;
   const int64_t stride = (int64_t)gridDim.x * 256;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < count; i += stride) {
     float mi = m[i], vi = v[i];
@@ -403,6 +428,7 @@ __global__ __launch_bounds__(256) void adam_apply_kernel(float* __restrict__ p, 
     p[i] = wn;
     m[i] = mi;
     v[i] = vi;
+    if (fe.e) fe.e[i] = ema_update(fe.e[i], wn, omd);  // (uniform, like the clip: one text, the plain arm's arithmetic unchanged)
   }
 }
 
@@ -425,7 +451,7 @@ __global__ __launch_bounds__(256) void adam_apply_ext_kernel(float* __restrict__
                                                              int nparts, float* __restrict__ norm_out,
                                                              const float* __restrict__ ext_partial, int ext_count,
                                                              float* __restrict__ coef_out, int64_t skip_lo, int64_t skip_hi,
-                                                             const float* __restrict__ lr_dev, const FlatClip fc) {
+                                                             const float* __restrict__ lr_dev, const FlatClip fc, const FlatEma fe) {
   __shared__ double red[4];
   __shared__ float coef_s;
   if (lr_dev) lr = lr_dev[0];
@@ -448,6 +474,7 @@ __global__ __launch_bounds__(256) void adam_apply_ext_kernel(float* __restrict__
   __syncthreads();
   const float gs = coef_s * scale;
   const AdamBias bc = adam_bias_correction(lr, beta1, beta2, step_counter[0]);
+  const float omd = fe.e ? fe.rate() : 0.0f;
   const int64_t stride = (int64_t)gridDim.x * 256;
   const int64_t hole = skip_hi - skip_lo, live = count - hole;  // hole 0: everything is updated here
   for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < live; j += stride) {
@@ -458,9 +485,32 @@ __global__ __launch_bounds__(256) void adam_apply_ext_kernel(float* __restrict__
     p[i] = wn;
     m[i] = mi;
     v[i] = vi;
+    if (fe.e) fe.e[i] = ema_update(fe.e[i], wn, omd);  // (uniform, like the clip: one text, the plain arm's arithmetic unchanged)
   }
 }
 
+
+// The stand-alone pass of the weight average: e <- ema_update(e, w, omd).  kVec: both pointers 16-byte aligned -- float4 q covers
+// elements [4q, 4q + 4), and the count % 4 elements behind the last whole one are taken one per thread by the first workgroup.
+template <bool kVec>
+__global__ __launch_bounds__(256) void ema_update_kernel(float* __restrict__ e, const float* __restrict__ w, int64_t count, float omd,
+                                                         const float* __restrict__ omd_dev) {
+  if (omd_dev) omd = omd_dev[0];
+  const int64_t stride = (int64_t)gridDim.x * 256, t0 = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if constexpr (kVec) {
+    const int64_t n4 = count >> 2;
+    float4* __restrict__ e4 = reinterpret_cast<float4*>(e);
+    const float4* __restrict__ w4 = reinterpret_cast<const float4*>(w);
+    for (int64_t i = t0; i < n4; i += stride) {
+      const float4 ev = e4[i], wv = w4[i];
+      e4[i] = make_float4(ema_update(ev.x, wv.x, omd), ema_update(ev.y, wv.y, omd), ema_update(ev.z, wv.z, omd), ema_update(ev.w, wv.w, omd));
+    }
+    const int64_t i = 4 * n4 + t0;
+    if (t0 < 4 && i < count) e[i] = ema_update(e[i], w[i], omd);
+  } else {
+    for (int64_t i = t0; i < count; i += stride) e[i] = ema_update(e[i], w[i], omd);
+  }
+}
 
 // ---- the multi-tensor form: torch.optim's list of separate parameters (one segment per tensor, any sizes, any views) ----
 // Stage 1 writes one sum-of-squares partial per kMultiChunk elements of each segment, segments in list order; stage 2's
@@ -485,18 +535,34 @@ struct MultiSeg {
   float clip;               // weight clip of this segment (include/nnue_hip.h, "weight clip"); 0: not clamped
 };
 
-struct MultiArgs {
+template <int kSegs>
+struct MultiArgsT {
+  static constexpr int kCap = kSegs;
+  static constexpr bool kEma = false;
   float* partial;      // all partials of the list (the apply reads [0, nparts))
   float* norm_out;     // pre-clip norm (first apply launch only), may be NULL
   const float* lr_dev; // n device floats replacing lr, indexed by seg_base + segment; may be NULL
   int32_t nparts, part_base, seg_base, n, chunks, units, need_norm;
   float max_norm;
-  MultiSeg seg[kMultiSegs];
+  MultiSeg seg[kSegs];
 };
+using MultiArgs = MultiArgsT<kMultiSegs>;
 static_assert(sizeof(MultiArgs) <= 4096, "the segment table must fit the 4 KiB kernel-argument budget");
 
+// The table of a list that keeps a weight average (include/nnue_hip.h, "weight average"): per segment the average's buffer (NULL:
+// that segment is off) and its rate.  A table of its own with fewer segments, so the lists without an average keep their
+// 45-segment launches.
+constexpr int kMultiSegsEma = 38;
+struct MultiArgsEma : MultiArgsT<kMultiSegsEma> {
+  static constexpr bool kEma = true;
+  float* e[kMultiSegsEma];
+  float omd[kMultiSegsEma];
+};
+static_assert(sizeof(MultiArgsEma) <= 4096, "the segment table must fit the 4 KiB kernel-argument budget");
+
 // the last segment whose first chunk (by_unit: unit) is <= x; x is wave-uniform, so these are scalar loads of the arguments
-__device__ __forceinline__ int multi_find(const MultiArgs& A, int x, bool by_unit) {
+template <class Args>
+__device__ __forceinline__ int multi_find(const Args& A, int x, bool by_unit) {
   int lo = 0, hi = A.n - 1;
   while (lo < hi) {
     const int mid = (lo + hi + 1) >> 1;
@@ -512,7 +578,8 @@ __device__ __forceinline__ float sq4(float4 x, float a) { return fmaf(x.w, x.w, 
 // arrives in a 16-byte load (g aligned, whole chunk in range) or in guarded scalar loads (a misaligned view, the ragged
 // last chunk): the partial does not depend on where the gradient happens to lie.  Adam: the first workgroup also
 // advances the segments' step counters (as sqnorm_stage1_count does).
-__global__ __launch_bounds__(256) void multi_sqnorm_kernel(const MultiArgs A) {
+template <class Args>
+__global__ __launch_bounds__(256) void multi_sqnorm_kernel(const Args A) {
   __shared__ float red[4];
   if (blockIdx.x == 0 && (int)threadIdx.x < A.n && A.seg[threadIdx.x].step) A.seg[threadIdx.x].step[0] += 1;
   if (!A.need_norm) return;
@@ -634,6 +701,33 @@ struct MultiUnit {
       }
     }
   }
+
+  // the unit's new weights (w, after the update) into the segment's average: 16-byte accesses where the unit is in its vector
+  // form and the average shares the parameters' offset within 16 bytes, else one element at a time
+  __device__ __forceinline__ void average(const MultiSeg& S, float* __restrict__ ema, float omd) const {
+    float* __restrict__ E = ema + base;
+    const bool evec = vec && ((reinterpret_cast<uintptr_t>(ema) ^ reinterpret_cast<uintptr_t>(S.p)) & 15) == 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (evec) {
+        const int o = offset(j, 0);
+        if (o + 4 > lim) continue;
+        const float4 ev = *reinterpret_cast<const float4*>(E + o);
+        *reinterpret_cast<float4*>(E + o) = make_float4(ema_update(ev.x, w[j].x, omd), ema_update(ev.y, w[j].y, omd),
+                                                        ema_update(ev.z, w[j].z, omd), ema_update(ev.w, w[j].w, omd));
+      } else {
+        auto one = [&](int c, float wc) {
+          const int o = vec ? offset(j, 0) + c : offset(j, c);
+          if (vec ? offset(j, 0) + 4 > lim : o >= lim) return;
+          E[o] = ema_update(E[o], wc, omd);
+        };
+        one(0, w[j].x);
+        one(1, w[j].y);
+        one(2, w[j].z);
+        one(3, w[j].w);
+      }
+    }
+  }
 };
 
 // the per-segment constants of the update: learning rate (lr_dev wins) and, for Adam, the bias corrections of the step
@@ -642,8 +736,8 @@ struct MultiHyper {
   float lr;
   AdamBias bc;
 };
-template <bool kAdam>
-__device__ __forceinline__ MultiHyper multi_hyper(const MultiArgs& A, int s) {
+template <bool kAdam, class Args>
+__device__ __forceinline__ MultiHyper multi_hyper(const Args& A, int s) {
   const MultiSeg& S = A.seg[s];
   MultiHyper h;
   h.lr = A.lr_dev ? A.lr_dev[A.seg_base + s] : S.lr;
@@ -665,8 +759,8 @@ __device__ __forceinline__ float multi_update(const MultiSeg& S, const MultiHype
 }
 
 // Stage 2.  The first unit is requested before the norm is re-derived (both are first touches after the kernel boundary).
-template <bool kAdam>
-__global__ __launch_bounds__(256) void multi_apply_kernel(const MultiArgs A) {
+template <bool kAdam, class Args>
+__global__ __launch_bounds__(256) void multi_apply_kernel(const Args A) {
   __shared__ double red[4];
   __shared__ float coef_s;
   int u = blockIdx.x;
@@ -705,6 +799,9 @@ __global__ __launch_bounds__(256) void multi_apply_kernel(const MultiArgs A) {
       U.w[j].w = multi_update<kAdam>(S, h, U.w[j].w, U.g[j].w, U.m[j].w, U.v[j].w, clip);
     }
     U.store(S);
+    if constexpr (Args::kEma) {
+      if (A.e[s]) U.average(S, A.e[s], A.omd[s]);  // (wave-uniform: the segment's)
+    }
     // vector form: the head (unit 0) and the tail (last unit) elements, one per thread (tiny segments have both)
     const int k = u - S.unit0;
     if (U.vec) {
@@ -715,7 +812,11 @@ __global__ __launch_bounds__(256) void multi_apply_kernel(const MultiArgs A) {
         const int64_t e = pass == 0 ? (k == 0 && t < head && t < S.count ? t : -1) : (last && tail0 + t < S.count ? tail0 + t : -1);
         if (e < 0) continue;
         float mv = (S.m && (kAdam || !S.first)) ? S.m[e] : 0.0f, vv = kAdam ? S.v[e] : 0.0f;
-        S.p[e] = multi_update<kAdam>(S, h, S.p[e], S.g[e], mv, vv, clip);
+        const float wn = multi_update<kAdam>(S, h, S.p[e], S.g[e], mv, vv, clip);
+        S.p[e] = wn;
+        if constexpr (Args::kEma) {
+          if (A.e[s]) A.e[s][e] = ema_update(A.e[s][e], wn, A.omd[s]);
+        }
         if (S.m) S.m[e] = mv;
         if (kAdam) S.v[e] = vv;
       }
@@ -754,10 +855,21 @@ int flat_clip_of(const char* who, float bound, const int64_t* ranges, int n_rang
   return NNUE_OK;
 }
 
+// The flat entry points' weight average, checked and packed (include/nnue_hip.h, "weight average").  ema == NULL is "off": the
+// kernel's plain arm / instantiation, whatever the rate says.  Otherwise the rate given by value must lie in (0, 1]; a device
+// scalar replaces it unseen, as lr_dev replaces lr.
+int flat_ema_of(const char* who, float* ema, float omd, const float* omd_dev, FlatEma* fe) {
+  *fe = FlatEma{nullptr, 0.0f, nullptr};
+  if (!ema) return NNUE_OK;
+  NNUE_REQUIRE(omd_dev || (omd > 0.0f && omd <= 1.0f), NNUE_E_ARG, "%s: ema_omd = %g must lie in (0, 1]", who, (double)omd);
+  *fe = FlatEma{ema, omd, omd_dev};
+  return NNUE_OK;
+}
+
 int adam_step_impl(const char* who, float* params, float* grads, float* exp_avg, float* exp_avg_sq, int32_t* step_counter, int64_t count,
                    float lr, float beta1, float beta2, float eps, float weight_decay, float max_norm, float grad_scale, float* norm_out,
                    void* scratch, int64_t scratch_bytes, const float* lr_dev, float weight_clip, const int64_t* clip_ranges, int n_ranges,
-                   nnue_stream_t stream) {
+                   float* ema, float ema_omd, const float* ema_omd_dev, nnue_stream_t stream) {
   NNUE_REQUIRE(params && grads && exp_avg && exp_avg_sq && step_counter && scratch, NNUE_E_ARG, "%s: null pointer", who);
   NNUE_REQUIRE(count > 0, NNUE_E_ARG, "%s: count must be positive", who);
   NNUE_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps > 0.f, NNUE_E_ARG,
@@ -767,6 +879,8 @@ int adam_step_impl(const char* who, float* params, float* grads, float* exp_avg,
   FlatClip fc;
   bool clip_on, by4;
   if (const int rc = flat_clip_of(who, weight_clip, clip_ranges, n_ranges, count, &fc, &clip_on, &by4)) return rc;
+  FlatEma fe;
+  if (const int rc = flat_ema_of(who, ema, ema_omd, ema_omd_dev, &fe)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   float* partial = static_cast<float*>(scratch);
   hipLaunchKernelGGL(sqnorm_stage1_count, dim3(kNormBlocks), dim3(256), 0, s, grads, count, grad_scale, partial, step_counter);
@@ -774,7 +888,7 @@ int adam_step_impl(const char* who, float* params, float* grads, float* exp_avg,
   if (blocks > 2048) blocks = 2048;
   if (!clip_on) fc = FlatClip{};  // bound 0: the kernel's plain arm
   hipLaunchKernelGGL(adam_apply_kernel, dim3(blocks), dim3(256), 0, s, params, grads, exp_avg, exp_avg_sq, count, lr, beta1, beta2, eps,
-                     weight_decay, max_norm, grad_scale, step_counter, partial, kNormBlocks, norm_out, lr_dev, fc);
+                     weight_decay, max_norm, grad_scale, step_counter, partial, kNormBlocks, norm_out, lr_dev, fc, fe);
   return nnue_launch_status(who);
 }
 
@@ -784,7 +898,7 @@ extern "C" int nnue_adam_step(float* params, float* grads, float* exp_avg, float
                               float lr, float beta1, float beta2, float eps, float weight_decay, float max_norm, float grad_scale,
                               float* norm_out, void* scratch, int64_t scratch_bytes, const float* lr_dev, nnue_stream_t stream) {
   return adam_step_impl("nnue_adam_step", params, grads, exp_avg, exp_avg_sq, step_counter, count, lr, beta1, beta2, eps, weight_decay, max_norm,
-                        grad_scale, norm_out, scratch, scratch_bytes, lr_dev, 0.0f, nullptr, 0, stream);
+                        grad_scale, norm_out, scratch, scratch_bytes, lr_dev, 0.0f, nullptr, 0, nullptr, 0.0f, nullptr, stream);
 }
 
 extern "C" int nnue_adam_step_clip(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int32_t* step_counter, int64_t count,
@@ -792,7 +906,18 @@ extern "C" int nnue_adam_step_clip(float* params, float* grads, float* exp_avg, 
                                    float* norm_out, void* scratch, int64_t scratch_bytes, const float* lr_dev, float weight_clip,
                                    const int64_t* clip_ranges, int n_clip_ranges, nnue_stream_t stream) {
   return adam_step_impl("nnue_adam_step_clip", params, grads, exp_avg, exp_avg_sq, step_counter, count, lr, beta1, beta2, eps, weight_decay,
-                        max_norm, grad_scale, norm_out, scratch, scratch_bytes, lr_dev, weight_clip, clip_ranges, n_clip_ranges, stream);
+                        max_norm, grad_scale, norm_out, scratch, scratch_bytes, lr_dev, weight_clip, clip_ranges, n_clip_ranges, nullptr, 0.0f,
+                        nullptr, stream);
+}
+
+extern "C" int nnue_adam_step_ema(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int32_t* step_counter, int64_t count,
+                                  float lr, float beta1, float beta2, float eps, float weight_decay, float max_norm, float grad_scale,
+                                  float* norm_out, void* scratch, int64_t scratch_bytes, const float* lr_dev, float weight_clip,
+                                  const int64_t* clip_ranges, int n_clip_ranges, float* ema, float ema_omd, const float* ema_omd_dev,
+                                  nnue_stream_t stream) {
+  return adam_step_impl("nnue_adam_step_ema", params, grads, exp_avg, exp_avg_sq, step_counter, count, lr, beta1, beta2, eps, weight_decay,
+                        max_norm, grad_scale, norm_out, scratch, scratch_bytes, lr_dev, weight_clip, clip_ranges, n_clip_ranges, ema, ema_omd,
+                        ema_omd_dev, stream);
 }
 
 extern "C" int nnue_cross_entropy(const float* logits, const int64_t* labels, int B, int C, float grad_scale,
@@ -828,7 +953,7 @@ int sgd_step_impl(const char* who, float* params, float* grads, float* momentum_
                   void* scratch, int64_t scratch_bytes, const float* ste_partial, int ste_chunks, int ste_fps,
                   float* ste_d_thr, float* ste_d_weight, const float* ext_partial, int ext_count, int64_t ext_lo,
                   int64_t ext_hi, float* coef_out, int ext_applied_elsewhere, const float* lr_dev, float weight_clip,
-                  const int64_t* clip_ranges, int n_ranges, nnue_stream_t stream) {
+                  const int64_t* clip_ranges, int n_ranges, float* ema, float ema_omd, const float* ema_omd_dev, nnue_stream_t stream) {
   NNUE_REQUIRE(params && grads && scratch, NNUE_E_ARG, "%s: null pointer", who);
   NNUE_REQUIRE(count > 0, NNUE_E_ARG, "%s: count must be positive", who);
   NNUE_REQUIRE(momentum == 0.0f || momentum_buf, NNUE_E_ARG, "%s: momentum %g needs a momentum buffer", who, momentum);
@@ -837,6 +962,8 @@ int sgd_step_impl(const char* who, float* params, float* grads, float* momentum_
   FlatClip fc;
   bool clip_on, by4;
   if (const int rc = flat_clip_of(who, weight_clip, clip_ranges, n_ranges, count, &fc, &clip_on, &by4)) return rc;
+  FlatEma fe;
+  if (const int rc = flat_ema_of(who, ema, ema_omd, ema_omd_dev, &fe)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   float* partial = static_cast<float*>(scratch);
   // norm workgroups: 16 floats per thread while that still leaves fewer than kNormBlocks (a small model's apply kernel
@@ -882,20 +1009,23 @@ int sgd_step_impl(const char* who, float* params, float* grads, float* momentum_
   float* mom = momentum == 0.0f ? nullptr : momentum_buf;
   static const char* novec = std::getenv("NNUE_SGD_SCALAR");
   const bool vec = !(novec && novec[0] == '1') && live <= (16ll << 20) && count % 4 == 0 && skip_lo % 4 == 0 && skip_hi % 4 == 0 &&
-                   nnue_aligned16(params) && nnue_aligned16(grads) && (!mom || nnue_aligned16(mom)) && (!clip_on || by4);
+                   nnue_aligned16(params) && nnue_aligned16(grads) && (!mom || nnue_aligned16(mom)) && (!clip_on || by4) &&
+                   (!fe.e || nnue_aligned16(fe.e));
   auto go = [&](auto kernel, int grid) {  // (the plain and the clamping kernel of a form take the same arguments)
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, s, params, grads, mom, count, lr, momentum, weight_decay, max_norm, grad_scale,
-                       first_step, partial, nparts, norm_out, ext_partial, ext_count, coef_out, skip_lo, skip_hi, lr_dev, fc);
+                       first_step, partial, nparts, norm_out, ext_partial, ext_count, coef_out, skip_lo, skip_hi, lr_dev, fc, fe);
   };
   if (vec) {
     int vb = (int)((live / 4 + 511) / 512);  // two float4 passes per thread
     vb = vb < 1 ? 1 : (vb > 2048 ? 2048 : vb);
-    if (clip_on) go(sgd_apply_vec_kernel<true>, vb);
-    else go(sgd_apply_vec_kernel<false>, vb);
+    if (fe.e) clip_on ? go(sgd_apply_vec_kernel<true, true>, vb) : go(sgd_apply_vec_kernel<false, true>, vb);
+    else if (clip_on) go(sgd_apply_vec_kernel<true, false>, vb);
+    else go(sgd_apply_vec_kernel<false, false>, vb);
     return nnue_launch_status(who);
   }
-  if (clip_on) go(sgd_apply_kernel<true>, blocks);
-  else go(sgd_apply_kernel<false>, blocks);
+  if (fe.e) clip_on ? go(sgd_apply_kernel<true, true>, blocks) : go(sgd_apply_kernel<false, true>, blocks);
+  else if (clip_on) go(sgd_apply_kernel<true, false>, blocks);
+  else go(sgd_apply_kernel<false, false>, blocks);
   return nnue_launch_status(who);
 }
 
@@ -903,7 +1033,8 @@ int adam_step_ext_impl(const char* who, float* params, float* grads, float* exp_
                        float lr, float beta1, float beta2, float eps, float weight_decay, float max_norm, float grad_scale,
                        float* norm_out, void* scratch, int64_t scratch_bytes, const float* ext_partial, int ext_count,
                        int64_t ext_lo, int64_t ext_hi, float* coef_out, int ext_applied_elsewhere, const float* lr_dev,
-                       float weight_clip, const int64_t* clip_ranges, int n_ranges, nnue_stream_t stream) {
+                       float weight_clip, const int64_t* clip_ranges, int n_ranges, float* ema, float ema_omd, const float* ema_omd_dev,
+                       nnue_stream_t stream) {
   NNUE_REQUIRE(params && grads && exp_avg && exp_avg_sq && step_counter && scratch, NNUE_E_ARG, "%s: null pointer", who);
   NNUE_REQUIRE(count > 0, NNUE_E_ARG, "%s: count must be positive", who);
   NNUE_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps > 0.f, NNUE_E_ARG,
@@ -923,6 +1054,8 @@ int adam_step_ext_impl(const char* who, float* params, float* grads, float* exp_
   FlatClip fc;
   bool clip_on, by4;
   if (const int rc = flat_clip_of(who, weight_clip, clip_ranges, n_ranges, count, &fc, &clip_on, &by4)) return rc;
+  FlatEma fe;
+  if (const int rc = flat_ema_of(who, ema, ema_omd, ema_omd_dev, &fe)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   float* partial = static_cast<float*>(scratch);
   int nb = (int)((count + 4095) / 4096);  // as nnue_sgd_step: 16 floats per thread, 64 .. kNormBlocks workgroups
@@ -936,7 +1069,7 @@ int adam_step_ext_impl(const char* who, float* params, float* grads, float* exp_
   if (!clip_on) fc = FlatClip{};  // bound 0: the kernel's plain arm
   hipLaunchKernelGGL(adam_apply_ext_kernel, dim3(blocks), dim3(256), 0, s, params, grads, exp_avg, exp_avg_sq, count, lr, beta1, beta2,
                      eps, weight_decay, max_norm, grad_scale, step_counter, partial, nb, norm_out, ext_partial, ext_count, coef_out, skip_lo,
-                     skip_hi, lr_dev, fc);
+                     skip_hi, lr_dev, fc, fe);
   return nnue_launch_status(who);
 }
 }  // namespace
@@ -948,7 +1081,7 @@ extern "C" int nnue_sgd_step(float* params, float* grads, float* momentum_buf, i
                              int64_t ext_hi, float* coef_out, int ext_applied_elsewhere, const float* lr_dev, nnue_stream_t stream) {
   return sgd_step_impl("nnue_sgd_step", params, grads, momentum_buf, count, lr, momentum, weight_decay, max_norm, grad_scale, first_step, norm_out,
                        scratch, scratch_bytes, ste_partial, ste_chunks, ste_fps, ste_d_thr, ste_d_weight, ext_partial, ext_count, ext_lo, ext_hi,
-                       coef_out, ext_applied_elsewhere, lr_dev, 0.0f, nullptr, 0, stream);
+                       coef_out, ext_applied_elsewhere, lr_dev, 0.0f, nullptr, 0, nullptr, 0.0f, nullptr, stream);
 }
 
 extern "C" int nnue_sgd_step_clip(float* params, float* grads, float* momentum_buf, int64_t count, float lr, float momentum,
@@ -959,7 +1092,19 @@ extern "C" int nnue_sgd_step_clip(float* params, float* grads, float* momentum_b
                                   const int64_t* clip_ranges, int n_clip_ranges, nnue_stream_t stream) {
   return sgd_step_impl("nnue_sgd_step_clip", params, grads, momentum_buf, count, lr, momentum, weight_decay, max_norm, grad_scale, first_step,
                        norm_out, scratch, scratch_bytes, ste_partial, ste_chunks, ste_fps, ste_d_thr, ste_d_weight, ext_partial, ext_count, ext_lo,
-                       ext_hi, coef_out, ext_applied_elsewhere, lr_dev, weight_clip, clip_ranges, n_clip_ranges, stream);
+                       ext_hi, coef_out, ext_applied_elsewhere, lr_dev, weight_clip, clip_ranges, n_clip_ranges, nullptr, 0.0f, nullptr, stream);
+}
+
+extern "C" int nnue_sgd_step_ema(float* params, float* grads, float* momentum_buf, int64_t count, float lr, float momentum,
+                                 float weight_decay, float max_norm, float grad_scale, int first_step, float* norm_out,
+                                 void* scratch, int64_t scratch_bytes, const float* ste_partial, int ste_chunks, int ste_fps,
+                                 float* ste_d_thr, float* ste_d_weight, const float* ext_partial, int ext_count, int64_t ext_lo,
+                                 int64_t ext_hi, float* coef_out, int ext_applied_elsewhere, const float* lr_dev, float weight_clip,
+                                 const int64_t* clip_ranges, int n_clip_ranges, float* ema, float ema_omd, const float* ema_omd_dev,
+                                 nnue_stream_t stream) {
+  return sgd_step_impl("nnue_sgd_step_ema", params, grads, momentum_buf, count, lr, momentum, weight_decay, max_norm, grad_scale, first_step,
+                       norm_out, scratch, scratch_bytes, ste_partial, ste_chunks, ste_fps, ste_d_thr, ste_d_weight, ext_partial, ext_count, ext_lo,
+                       ext_hi, coef_out, ext_applied_elsewhere, lr_dev, weight_clip, clip_ranges, n_clip_ranges, ema, ema_omd, ema_omd_dev, stream);
 }
 
 extern "C" int nnue_adam_step_ext(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int32_t* step_counter, int64_t count,
@@ -969,7 +1114,7 @@ extern "C" int nnue_adam_step_ext(float* params, float* grads, float* exp_avg, f
                                   nnue_stream_t stream) {
   return adam_step_ext_impl("nnue_adam_step_ext", params, grads, exp_avg, exp_avg_sq, step_counter, count, lr, beta1, beta2, eps, weight_decay,
                             max_norm, grad_scale, norm_out, scratch, scratch_bytes, ext_partial, ext_count, ext_lo, ext_hi, coef_out,
-                            ext_applied_elsewhere, lr_dev, 0.0f, nullptr, 0, stream);
+                            ext_applied_elsewhere, lr_dev, 0.0f, nullptr, 0, nullptr, 0.0f, nullptr, stream);
 }
 
 extern "C" int nnue_adam_step_ext_clip(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int32_t* step_counter, int64_t count,
@@ -979,7 +1124,35 @@ extern "C" int nnue_adam_step_ext_clip(float* params, float* grads, float* exp_a
                                        float weight_clip, const int64_t* clip_ranges, int n_clip_ranges, nnue_stream_t stream) {
   return adam_step_ext_impl("nnue_adam_step_ext_clip", params, grads, exp_avg, exp_avg_sq, step_counter, count, lr, beta1, beta2, eps,
                             weight_decay, max_norm, grad_scale, norm_out, scratch, scratch_bytes, ext_partial, ext_count, ext_lo, ext_hi, coef_out,
-                            ext_applied_elsewhere, lr_dev, weight_clip, clip_ranges, n_clip_ranges, stream);
+                            ext_applied_elsewhere, lr_dev, weight_clip, clip_ranges, n_clip_ranges, nullptr, 0.0f, nullptr, stream);
+}
+
+extern "C" int nnue_adam_step_ext_ema(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int32_t* step_counter, int64_t count,
+                                      float lr, float beta1, float beta2, float eps, float weight_decay, float max_norm, float grad_scale,
+                                      float* norm_out, void* scratch, int64_t scratch_bytes, const float* ext_partial, int ext_count,
+                                      int64_t ext_lo, int64_t ext_hi, float* coef_out, int ext_applied_elsewhere, const float* lr_dev,
+                                      float weight_clip, const int64_t* clip_ranges, int n_clip_ranges, float* ema, float ema_omd,
+                                      const float* ema_omd_dev, nnue_stream_t stream) {
+  return adam_step_ext_impl("nnue_adam_step_ext_ema", params, grads, exp_avg, exp_avg_sq, step_counter, count, lr, beta1, beta2, eps,
+                            weight_decay, max_norm, grad_scale, norm_out, scratch, scratch_bytes, ext_partial, ext_count, ext_lo, ext_hi, coef_out,
+                            ext_applied_elsewhere, lr_dev, weight_clip, clip_ranges, n_clip_ranges, ema, ema_omd, ema_omd_dev, stream);
+}
+
+// The stand-alone pass of the weight average (include/nnue_hip.h, "weight average"): ema <- ema_update(ema, params, omd) over
+// count elements.  16-byte accesses where both pointers are 16-byte aligned (the < 4 elements behind the last whole float4 go
+// one per thread), 4-byte accesses otherwise.
+extern "C" int nnue_ema_update(float* ema, const float* params, int64_t count, float omd, const float* ema_omd_dev, nnue_stream_t stream) {
+  NNUE_REQUIRE(ema && params, NNUE_E_ARG, "nnue_ema_update: null pointer");
+  NNUE_REQUIRE(count > 0, NNUE_E_ARG, "nnue_ema_update: count must be positive");
+  NNUE_REQUIRE(ema_omd_dev || (omd > 0.0f && omd <= 1.0f), NNUE_E_ARG, "nnue_ema_update: omd = %g must lie in (0, 1]", (double)omd);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const bool vec = nnue_aligned16(ema) && nnue_aligned16(params) && count >= 4;
+  const int64_t work = vec ? count / 4 + 3 : count;  // threads' worth of work: float4s and up to three tail elements
+  int64_t blocks = (work + 1023) / 1024;             // (up to four passes per thread before the grid is capped)
+  blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
+  if (vec) hipLaunchKernelGGL(ema_update_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, ema, params, count, omd, ema_omd_dev);
+  else hipLaunchKernelGGL(ema_update_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, ema, params, count, omd, ema_omd_dev);
+  return nnue_launch_status("nnue_ema_update");
 }
 
 extern "C" int nnue_confusion_accumulate(const float* logits, const int64_t* labels, int B, int C, uint64_t* confusion,
@@ -999,11 +1172,13 @@ int64_t multi_chunks(int64_t count) { return (count + kMultiChunk - 1) / kMultiC
 
 // Validates every segment, then packs the tables (kMultiSegs segments per launch) and launches all norm launches before
 // all apply launches on `stream`.  m / v / steps / first / a / b / eps may be NULL where the form does not use them.
-template <bool kAdam>
+// Args: MultiArgs, or MultiArgsEma for a list that keeps a weight average (ema[i] / omd[i] per segment; ema[i] NULL: off there).
+template <bool kAdam, class Args = MultiArgs>
 int multi_step(const char* what, float* const* params, float* const* grads, float* const* m, float* const* v, int32_t* const* steps,
                const int64_t* counts, int n, const float* lr, const float* a, const float* b, const float* eps, const float* wd,
                const int32_t* first, const float* clip, float max_norm, float* norm_out, void* scratch, int64_t scratch_bytes,
-               const float* lr_dev, nnue_stream_t stream) {
+               const float* lr_dev, nnue_stream_t stream, float* const* ema = nullptr, const float* omd = nullptr) {
+  constexpr int kCap = Args::kCap;
   NNUE_REQUIRE(n > 0, NNUE_E_ARG, "%s: n = %d must be positive", what, n);
   NNUE_REQUIRE(params && grads && counts && lr && a && wd && scratch && (kAdam ? (m && v && steps && b && eps) : first != nullptr),
                NNUE_E_ARG, "%s: null pointer", what);
@@ -1021,6 +1196,9 @@ int multi_step(const char* what, float* const* params, float* const* grads, floa
     }
     NNUE_REQUIRE(!clip || (clip[i] >= 0.0f && clip[i] <= 3.4028234e38f), NNUE_E_ARG, "%s: weight_clip = %g of segment %d must be finite and not negative",
                  what, clip ? (double)clip[i] : 0.0, i);
+    if constexpr (Args::kEma)
+      NNUE_REQUIRE(!ema[i] || (omd && omd[i] > 0.0f && omd[i] <= 1.0f), NNUE_E_ARG, "%s: ema_omd = %g of segment %d must lie in (0, 1]", what,
+                   omd ? (double)omd[i] : 0.0, i);
     nparts += multi_chunks(counts[i]);
   }
   NNUE_REQUIRE(nparts < ((int64_t)1 << 28), NNUE_E_ARG, "%s: %lld elements in all: too many", what, (long long)nparts * kMultiChunk);
@@ -1028,16 +1206,16 @@ int multi_step(const char* what, float* const* params, float* const* grads, floa
                (long long)scratch_bytes, (long long)nnue_multi_optim_scratch(counts, n));
   hipStream_t s = static_cast<hipStream_t>(stream);
   const bool need_norm = max_norm > 0.0f || norm_out;
-  MultiArgs A{};
+  Args A{};
   A.partial = static_cast<float*>(scratch);
   A.lr_dev = lr_dev;
   A.nparts = (int32_t)nparts;
   A.need_norm = need_norm;
   A.max_norm = max_norm;
-  auto pack = [&](int base, int part_base) {  // segments [base, base + kMultiSegs) into A
+  auto pack = [&](int base, int part_base) {  // segments [base, base + kCap) into A
     A.seg_base = base;
     A.part_base = part_base;
-    A.n = n - base < kMultiSegs ? n - base : kMultiSegs;
+    A.n = n - base < kCap ? n - base : kCap;
     A.chunks = A.units = 0;
     for (int i = 0; i < A.n; ++i) {
       const int j = base + i;
@@ -1046,22 +1224,26 @@ int multi_step(const char* what, float* const* params, float* const* grads, floa
       S = MultiSeg{params[j], grads[j], has_m ? m[j] : nullptr, kAdam ? v[j] : nullptr, kAdam ? steps[j] : nullptr, counts[j],
                    A.chunks, A.units, lr[j], a[j], kAdam ? b[j] : 0.0f, wd[j], kAdam ? eps[j] : 0.0f, kAdam ? 0 : first[j],
                    clip ? clip[j] : 0.0f};
+      if constexpr (Args::kEma) {
+        A.e[i] = ema[j];
+        A.omd[i] = ema[j] ? omd[j] : 0.0f;
+      }
       A.chunks += (int32_t)multi_chunks(counts[j]);
       A.units += (int32_t)((counts[j] + kMultiUnit - 1) / kMultiUnit);
     }
   };
   if (need_norm || kAdam) {
-    for (int base = 0, part = 0; base < n; base += kMultiSegs) {
+    for (int base = 0, part = 0; base < n; base += kCap) {
       pack(base, part);
       part += A.chunks;
       A.norm_out = nullptr;
-      hipLaunchKernelGGL(multi_sqnorm_kernel, dim3(need_norm ? A.chunks : 1), dim3(256), 0, s, A);
+      hipLaunchKernelGGL(multi_sqnorm_kernel<Args>, dim3(need_norm ? A.chunks : 1), dim3(256), 0, s, A);
     }
   }
-  for (int base = 0; base < n; base += kMultiSegs) {
+  for (int base = 0; base < n; base += kCap) {
     pack(base, 0);
     A.norm_out = base == 0 ? norm_out : nullptr;
-    hipLaunchKernelGGL(multi_apply_kernel<kAdam>, dim3(A.units < kMultiApplyBlocks ? A.units : kMultiApplyBlocks), dim3(256), 0, s, A);
+    hipLaunchKernelGGL((multi_apply_kernel<kAdam, Args>), dim3(A.units < kMultiApplyBlocks ? A.units : kMultiApplyBlocks), dim3(256), 0, s, A);
   }
   return nnue_launch_status(what);
 }
@@ -1105,6 +1287,41 @@ extern "C" int nnue_multi_adam_step_clip(float* const* params, float* const* gra
                                          float max_norm, float* norm_out, void* scratch, int64_t scratch_bytes, const float* lr_dev,
                                          nnue_stream_t stream) {
   return multi_step<true>("nnue_multi_adam_step_clip", params, grads, exp_avgs, exp_avg_sqs, step_counters, counts, n, lr, beta1, beta2, eps,
+                          weight_decay, nullptr, weight_clip, max_norm, norm_out, scratch, scratch_bytes, lr_dev, stream);
+}
+
+// The multi-tensor forms with a weight average per segment (include/nnue_hip.h, "weight average").  A list without one (ema NULL,
+// or NULL in every segment) is the _clip form's call, launch for launch.
+namespace {
+bool multi_has_ema(float* const* ema, int n) {
+  for (int i = 0; ema && i < n; ++i)
+    if (ema[i]) return true;
+  return false;
+}
+}  // namespace
+
+extern "C" int nnue_multi_sgd_step_ema(float* const* params, float* const* grads, float* const* momentum_bufs, const int64_t* counts, int n,
+                                       const float* lr, const float* momentum, const float* weight_decay, const int32_t* first_step,
+                                       const float* weight_clip, float max_norm, float* norm_out, void* scratch, int64_t scratch_bytes,
+                                       const float* lr_dev, float* const* ema, const float* ema_omd, nnue_stream_t stream) {
+  if (n > 0 && multi_has_ema(ema, n))
+    return multi_step<false, MultiArgsEma>("nnue_multi_sgd_step_ema", params, grads, momentum_bufs, nullptr, nullptr, counts, n, lr, momentum,
+                                           nullptr, nullptr, weight_decay, first_step, weight_clip, max_norm, norm_out, scratch, scratch_bytes,
+                                           lr_dev, stream, ema, ema_omd);
+  return multi_step<false>("nnue_multi_sgd_step_ema", params, grads, momentum_bufs, nullptr, nullptr, counts, n, lr, momentum, nullptr,
+                           nullptr, weight_decay, first_step, weight_clip, max_norm, norm_out, scratch, scratch_bytes, lr_dev, stream);
+}
+
+extern "C" int nnue_multi_adam_step_ema(float* const* params, float* const* grads, float* const* exp_avgs, float* const* exp_avg_sqs,
+                                        int32_t* const* step_counters, const int64_t* counts, int n, const float* lr, const float* beta1,
+                                        const float* beta2, const float* eps, const float* weight_decay, const float* weight_clip,
+                                        float max_norm, float* norm_out, void* scratch, int64_t scratch_bytes, const float* lr_dev,
+                                        float* const* ema, const float* ema_omd, nnue_stream_t stream) {
+  if (n > 0 && multi_has_ema(ema, n))
+    return multi_step<true, MultiArgsEma>("nnue_multi_adam_step_ema", params, grads, exp_avgs, exp_avg_sqs, step_counters, counts, n, lr, beta1,
+                                          beta2, eps, weight_decay, nullptr, weight_clip, max_norm, norm_out, scratch, scratch_bytes, lr_dev,
+                                          stream, ema, ema_omd);
+  return multi_step<true>("nnue_multi_adam_step_ema", params, grads, exp_avgs, exp_avg_sqs, step_counters, counts, n, lr, beta1, beta2, eps,
                           weight_decay, nullptr, weight_clip, max_norm, norm_out, scratch, scratch_bytes, lr_dev, stream);
 }
 

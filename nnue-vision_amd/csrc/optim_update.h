@@ -36,6 +36,13 @@ __device__ __forceinline__ float adam_update(float w, float g, float& m, float& 
 // the optimizer's state is formed from the un-clamped arithmetic and never clamped.
 __device__ __forceinline__ float clip_weight(float w, float c) { return w > c ? c : (w < -c ? -c : w); }
 
+// The moving average of the weights (include/nnue_hip.h, "weight average"): e <- e + omd (w_new - e), one rounding of the
+// difference and one of the fused multiply-add, omd = float32(1 - float64(decay)).  w_new is the value the launch stores -- after
+// the update and after clip_weight where the clip is on -- so a convex combination of clamped weights stays inside the bound.
+// Every kernel that applies an update calls it last; nothing of a step reads the average, and the optimizer's state never
+// sees it.  Nothing here is left to the compiler's contraction: the stand-alone pass and every fused form give the same bits.
+__device__ __forceinline__ float ema_update(float e, float w_new, float omd) { return fmaf(omd, w_new - e, e); }
+
 // adam_update with every fused multiply-add written out -- the form -ffp-contract=on gives that text (the multiply on the
 // left of a sum is the fused one).  Under the build's default contraction the compiler fuses a * b + c * d wherever the
 // caller's context lets it (measured: v = beta2 v + (1 - beta2) g g came out as one fma in the product's epilogue and as

@@ -34,6 +34,10 @@ struct UpdFwd {
   float lr, mom, wd, scale;
   int abl;  // timing-only ablations (NNUE_ABLATIONS builds): 1 no parameter/momentum loads, 2 no stores, 4 no forward phase, 8 no d_W MFMAs
   float wclip;  // the weight clip's bound (kClip forms of the kernel; include/nnue_hip.h, "weight clip")
+  // the weight average (kEma forms; include/nnue_hip.h, "weight average"): the rows matching `weight`, the rate, its device scalar
+  float* __restrict__ ema;
+  const float* __restrict__ omd_dev;
+  float omd;
 };
 // The Adam form (torch.optim.Adam, train.py:465-470): `momentum` holds the exp_avg rows; the step number is the device counter
 // the optimizer's norm launch has already advanced, so the launch replays from a graph.
@@ -77,7 +81,14 @@ __device__ __forceinline__ int uf_wp_img(int row, int chunk) { return row * 256 
 // kClip: the weight clip.  The new tile is clamped to [-wclip, wclip] in phase 2 BEFORE it is stored and before phase 3 splits it
 // into the planes of step t+1's forward -- the forward must contract the table the store leaves, which a clamp launched after this
 // pass could not give it.  Momentum and moments are stored un-clamped.
-template <int kNK, bool kMom, bool kFirst, bool kAdam = false, bool kClip = false>
+//
+// kEma: the weight average, a further table-sized stream read and written.  The SGD forms have no second moment, so the average's
+// tile takes exactly the place the Adam form gives exp_avg_sq: requested after the LAST stage1() of phase 1 (fetch2e), 32 registers
+// that are free from there on.  The Adam form has no such place left -- parameters, both moments and the forward's accumulators
+// fill the wave -- so there the average is requested per row group INSIDE phase 2: two row groups ahead of the loop, and row group
+// u + 2 as soon as row group u has stored its moments (whose registers it takes over).  The new element is averaged after the
+// clamp and stored behind the parameters; nothing of phase 3 reads it.  Figures of every instantiation: DESIGN section 7.
+template <int kNK, bool kMom, bool kFirst, bool kAdam = false, bool kClip = false, bool kEma = false>
 __global__ __launch_bounds__(256, 2) void ftm_update_forward_kernel(std::conditional_t<kAdam, UpdFwdAdam, UpdFwd> a) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[kUfLds];
   constexpr int KT = kBf64K, PB = 64 * KT * 2;
@@ -115,6 +126,8 @@ __global__ __launch_bounds__(256, 2) void ftm_update_forward_kernel(std::conditi
                                                                        0x00020000);
   __amdgpu_buffer_rsrc_t rsv = rsm;  // second moment (Adam only)
   if constexpr (kAdam) rsv = __builtin_amdgcn_make_buffer_rsrc(a.exp_avg_sq, 0, (unsigned)((size_t)a.direct * L1 * 4), 0x00020000);
+  __amdgpu_buffer_rsrc_t rse = rsm;  // the weight average (kEma only)
+  if constexpr (kEma) rse = __builtin_amdgcn_make_buffer_rsrc(a.ema, 0, (unsigned)((size_t)a.direct * L1 * 4), 0x00020000);
   const int m0 = (wave >> 1) * 64, n0 = (wave & 1) * 32;
   // Per-thread coordinates behind global offsets.  They are re-derived from an opaque copy of the thread index at the top of
   // every tile: loop-invariant offsets (about forty of them) would otherwise be held -- and spilled -- across the loop beside the
@@ -261,6 +274,23 @@ __global__ __launch_bounds__(256, 2) void ftm_update_forward_kernel(std::conditi
       vv[u] = make_float4(__uint_as_float(x[0]), __uint_as_float(x[1]), __uint_as_float(x[2]), __uint_as_float(x[3]));
     }
   };
+  // the average of the tile whose parameters fetch2 requested: the whole tile (SGD forms, after the last stage1()) or one row group
+  float4 ev[8];
+  auto fetch2e_row = [&](int u) {
+    const u32x4 x = __builtin_amdgcn_raw_buffer_load_b128(rse, wm_off(u), 0, 2);
+    ev[u] = make_float4(__uint_as_float(x[0]), __uint_as_float(x[1]), __uint_as_float(x[2]), __uint_as_float(x[3]));
+  };
+  auto fetch2e = [&]() {
+#pragma unroll
+    for (int u = 0; u < 8; ++u) fetch2e_row(u);
+  };
+  float omd = 0.0f;
+  if constexpr (kEma) omd = a.omd_dev ? a.omd_dev[0] : a.omd;
+  auto store_e = [&](int u, const float4& wn) {
+    __builtin_amdgcn_raw_buffer_store_b128((u32x4){__float_as_uint(ema_update(ev[u].x, wn.x, omd)), __float_as_uint(ema_update(ev[u].y, wn.y, omd)),
+                                                   __float_as_uint(ema_update(ev[u].z, wn.z, omd)), __float_as_uint(ema_update(ev[u].w, wn.w, omd))},
+                                           rse, wm_off(u), 0, 2);
+  };
   const float gs = a.coef[0] * a.scale;
   const float lr = a.lr_dev ? a.lr_dev[0] : a.lr;
   AdamBias bc{0.f, 0.f};
@@ -292,6 +322,7 @@ __global__ __launch_bounds__(256, 2) void ftm_update_forward_kernel(std::conditi
       __syncthreads();
     }
     if constexpr (kAdam) fetch2v();  // after the last stage1(): see above
+    if constexpr (kEma && !kAdam) fetch2e();  // (the SGD forms: the same place)
 #ifdef NNUE_ABLATIONS
     if (!(a.abl & 8))
 #endif
@@ -306,6 +337,10 @@ __global__ __launch_bounds__(256, 2) void ftm_update_forward_kernel(std::conditi
         for (int e = 0; e < 4; ++e) Ct[(m0 + 16 * i + 4 * q + e) * 68 + n0 + 16 * t + r] = accw[i][t][e];
     stage3();  // An does not overlap Ct
     fetch3(m_base, 1);
+    if constexpr (kEma && kAdam) {  // the first two row groups of the average; the others follow inside the loop
+      fetch2e_row(0);
+      fetch2e_row(1);
+    }
     __syncthreads();
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
@@ -330,6 +365,10 @@ __global__ __launch_bounds__(256, 2) void ftm_update_forward_kernel(std::conditi
                                                  rsv, wm_off(u), 0, 2);
           __builtin_amdgcn_raw_buffer_store_b128((u32x4){__float_as_uint(wn.x), __float_as_uint(wn.y), __float_as_uint(wn.z), __float_as_uint(wn.w)}, rsw,
                                                  wm_off(u), 0, 2);
+          if constexpr (kEma) {
+            if (u + 2 < 8) fetch2e_row(u + 2);  // (into the registers this row group's moments have just left)
+            store_e(u, wn);
+          }
         }
         w[u] = m_base + 8 * g8 + u < a.direct ? wn : make_float4(0.f, 0.f, 0.f, 0.f);
         continue;
@@ -355,6 +394,7 @@ __global__ __launch_bounds__(256, 2) void ftm_update_forward_kernel(std::conditi
                                                  wm_off(u), 0, 2);
         __builtin_amdgcn_raw_buffer_store_b128((u32x4){__float_as_uint(wn.x), __float_as_uint(wn.y), __float_as_uint(wn.z), __float_as_uint(wn.w)}, rsw,
                                                wm_off(u), 0, 2);
+        if constexpr (kEma) store_e(u, wn);
       }
       // rows past the product's table rows (their stores were dropped) contribute nothing to the forward
       w[u] = m_base + 8 * g8 + u < a.direct ? wn : make_float4(0.f, 0.f, 0.f, 0.f);

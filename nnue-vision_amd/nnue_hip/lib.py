@@ -245,7 +245,17 @@ SIGNATURES = {
                                           _c_p]),
     "nnue_multi_adam_step_clip": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_int, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_f, _c_p,
                                            _c_p, _c_i64, _c_p, _c_p]),
+    # the weight average (include/nnue_hip.h, "weight average"): the stand-alone pass, and the _clip entry points with the average
+    # (ema, ema_omd, ema_omd_dev -- the multi-tensor forms: ema[], ema_omd[]) in front of the stream
+    "nnue_ema_update": (_c_int, [_c_p, _c_p, _c_i64, _c_f, _c_p, _c_p]),
 }
+for _name in ("nnue_sgd_step", "nnue_adam_step", "nnue_adam_step_ext", "nnue_ftm_backward_weight_update", "nnue_ftm_backward_weight_update_forward",
+              "nnue_ftm_backward_weight_update_adam", "nnue_ftm_backward_weight_update_forward_adam"):
+    _res, _args = SIGNATURES[_name + "_clip"]
+    SIGNATURES[_name + "_ema"] = (_res, _args[:-1] + [_c_p, _c_f, _c_p, _c_p])
+for _name in ("nnue_multi_sgd_step", "nnue_multi_adam_step"):
+    _res, _args = SIGNATURES[_name + "_clip"]
+    SIGNATURES[_name + "_ema"] = (_res, _args[:-1] + [_c_p, _c_p, _c_p])
 
 _lib: Optional[ctypes.CDLL] = None
 
@@ -316,7 +326,12 @@ class time_calls:
 
 
 # entry points timed under the name of the call they replace (a caller's timer keys name the plain forms)
-_TIMED_AS = {"nnue_sgd_step_clip": "nnue_sgd_step", "nnue_adam_step_clip": "nnue_adam_step", "nnue_adam_step_ext_clip": "nnue_adam_step_ext",
+_TIMED_AS = {"nnue_sgd_step_ema": "nnue_sgd_step", "nnue_adam_step_ema": "nnue_adam_step", "nnue_adam_step_ext_ema": "nnue_adam_step_ext",
+             "nnue_ftm_backward_weight_update_ema": "nnue_ftm_backward_weight_update",
+             "nnue_ftm_backward_weight_update_forward_ema": "nnue_ftm_backward_weight_update_forward",
+             "nnue_ftm_backward_weight_update_adam_ema": "nnue_ftm_backward_weight_update_adam",
+             "nnue_ftm_backward_weight_update_forward_adam_ema": "nnue_ftm_backward_weight_update_forward_adam",
+             "nnue_sgd_step_clip": "nnue_sgd_step", "nnue_adam_step_clip": "nnue_adam_step", "nnue_adam_step_ext_clip": "nnue_adam_step_ext",
              "nnue_ftm_backward_weight_update_clip": "nnue_ftm_backward_weight_update",
              "nnue_ftm_backward_weight_update_forward_clip": "nnue_ftm_backward_weight_update_forward",
              "nnue_ftm_backward_weight_update_adam_clip": "nnue_ftm_backward_weight_update_adam",
@@ -1487,14 +1502,21 @@ def ftm_backward_tail_rows(d_out: torch.Tensor, fm: "FeatureMatrix", d_weight: t
 
 
 def _ftm_weight_update(name: str, d_out, fm, weight, coef, lr_dev, scalars, momentum_rows=None, adam=None, nxt=None,
-                       weight_clip: float = 0.0) -> None:
+                       weight_clip: float = 0.0, ema: Optional["WeightAverage"] = None) -> None:
     """The one body of ftm_backward_weight_update{,_forward}{,_adam}; `name`: the public function, "nnue_" + name its C entry
     point.  scalars: the optimizer's C arguments between the state pointers and lr_dev; adam = (exp_avg_rows, exp_avg_sq_rows,
     step_counter), else SGD on momentum_rows; nxt = (fm_next, bias, out_next): the pass also forms that map's forward.
     weight_clip > 0: the ``_clip`` sibling of the entry point, which clamps the new table elements (include/nnue_hip.h, "weight
-    clip"); 0 is the plain entry point."""
+    clip"); 0 is the plain entry point.
+    ema (a WeightAverage over the rows that match `weight`): the ``_ema`` sibling, which also moves the average of every table
+    element it stores (include/nnue_hip.h, "weight average"), in the fused pass (nxt) as in the product's epilogue."""
     weight_clip = checked_weight_clip(weight_clip)
-    if weight_clip > 0.0:
+    ema_args = ()
+    if ema is not None:
+        _need(ema.ema, torch.float32, "average's rows", tuple(weight.shape))
+        name, scalars = name + "_ema", (*scalars, weight_clip)
+        ema_args = ema.args()
+    elif weight_clip > 0.0:
         name, scalars = name + "_clip", (*scalars, weight_clip)
     d_out = _need(d_out, torch.float32, "d_out")
     b, l1 = d_out.shape
@@ -1519,15 +1541,16 @@ def _ftm_weight_update(name: str, d_out, fm, weight, coef, lr_dev, scalars, mome
         forward = (fm_next.bits.data_ptr(), fm_next.sink.data_ptr(), fm_next.batch, bias.data_ptr(), out_next.data_ptr(),
                    fm_next.scratch.data_ptr(), fm_next.scratch.numel())
     _call("nnue_" + name, fm.bits.data_ptr(), d_out.data_ptr(), b, fm.num_rows, fm.positions, l1, weight.data_ptr(), *state, *scalars,
-          _ptr(lr_dev), *forward, _stream(d_out))
+          _ptr(lr_dev), *forward, *ema_args, _stream(d_out))
 
 
 def ftm_backward_weight_update(d_out: torch.Tensor, fm: "FeatureMatrix", weight: torch.Tensor, momentum_rows: Optional[torch.Tensor],
                                coef: torch.Tensor, lr: float, momentum: float, weight_decay: float, grad_scale: float,
-                               first_step: bool, lr_dev: Optional[torch.Tensor] = None, weight_clip: float = 0.0) -> None:
+                               first_step: bool, lr_dev: Optional[torch.Tensor] = None, weight_clip: float = 0.0,
+                               ema: Optional["WeightAverage"] = None) -> None:
     """weight rows [0, direct) <- SGD update with d_W = A^T d_out formed and consumed in the product's epilogue.
-    lr_dev (device float32 scalar): the learning rate is read from it instead of `lr`.  weight_clip: see _ftm_weight_update."""
-    _ftm_weight_update("ftm_backward_weight_update", d_out, fm, weight, coef, lr_dev, momentum_rows=momentum_rows, weight_clip=weight_clip,
+    lr_dev (device float32 scalar): the learning rate is read from it instead of `lr`.  weight_clip, ema: see _ftm_weight_update."""
+    _ftm_weight_update("ftm_backward_weight_update", d_out, fm, weight, coef, lr_dev, momentum_rows=momentum_rows, weight_clip=weight_clip, ema=ema,
                        scalars=(float(lr), float(momentum), float(weight_decay), float(grad_scale), int(bool(first_step))))
 
 
@@ -1541,23 +1564,24 @@ def ftm_backward_weight_update_forward(d_out: torch.Tensor, fm: "FeatureMatrix",
                                        momentum_rows: Optional[torch.Tensor], coef: torch.Tensor, lr: float, momentum: float,
                                        weight_decay: float, grad_scale: float, first_step: bool, fm_next: "FeatureMatrix",
                                        bias: torch.Tensor, out_next: torch.Tensor, lr_dev: Optional[torch.Tensor] = None,
-                                       weight_clip: float = 0.0) -> None:
+                                       weight_clip: float = 0.0, ema: Optional["WeightAverage"] = None) -> None:
     """ftm_backward_weight_update(d_out, fm, ...) and ftm_forward(weight, bias, fm_next, out=out_next) in one pass over the
     table (bitwise the two calls).  `bias` and table row F-1 must already be updated (sgd_step).  weight_clip: the forward
     contracts the clamped table (see _ftm_weight_update)."""
-    _ftm_weight_update("ftm_backward_weight_update_forward", d_out, fm, weight, coef, lr_dev, momentum_rows=momentum_rows, weight_clip=weight_clip,
+    _ftm_weight_update("ftm_backward_weight_update_forward", d_out, fm, weight, coef, lr_dev, momentum_rows=momentum_rows, weight_clip=weight_clip, ema=ema,
                        nxt=(fm_next, bias, out_next), scalars=(float(lr), float(momentum), float(weight_decay), float(grad_scale), int(bool(first_step))))
 
 
 def ftm_backward_weight_update_adam(d_out: torch.Tensor, fm: "FeatureMatrix", weight: torch.Tensor, exp_avg_rows: torch.Tensor,
                                     exp_avg_sq_rows: torch.Tensor, coef: torch.Tensor, step_counter: torch.Tensor, lr: float,
                                     betas, eps: float, weight_decay: float, grad_scale: float,
-                                    lr_dev: Optional[torch.Tensor] = None, weight_clip: float = 0.0) -> None:
+                                    lr_dev: Optional[torch.Tensor] = None, weight_clip: float = 0.0,
+                                    ema: Optional["WeightAverage"] = None) -> None:
     """weight rows [0, direct) and the matching moment rows <- Adam update with d_W = A^T d_out formed and consumed in the
     product's epilogue.  ``step_counter`` (device int32) is read, not advanced: adam_step(ext_applied_elsewhere=True) of the
     same step advances it and leaves ``coef``."""
     _ftm_weight_update("ftm_backward_weight_update_adam", d_out, fm, weight, coef, lr_dev, adam=(exp_avg_rows, exp_avg_sq_rows, step_counter),
-                       weight_clip=weight_clip,
+                       weight_clip=weight_clip, ema=ema,
                        scalars=(float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay), float(grad_scale)))
 
 
@@ -1565,11 +1589,11 @@ def ftm_backward_weight_update_forward_adam(d_out: torch.Tensor, fm: "FeatureMat
                                             exp_avg_sq_rows: torch.Tensor, coef: torch.Tensor, step_counter: torch.Tensor, lr: float,
                                             betas, eps: float, weight_decay: float, grad_scale: float, fm_next: "FeatureMatrix",
                                             bias: torch.Tensor, out_next: torch.Tensor, lr_dev: Optional[torch.Tensor] = None,
-                                            weight_clip: float = 0.0) -> None:
+                                            weight_clip: float = 0.0, ema: Optional["WeightAverage"] = None) -> None:
     """ftm_backward_weight_update_adam(d_out, fm, ...) and ftm_forward(weight, bias, fm_next, out=out_next) in one pass over the
     table (bitwise the two calls).  `bias` and table row F-1 must already be updated (adam_step)."""
     _ftm_weight_update("ftm_backward_weight_update_forward_adam", d_out, fm, weight, coef, lr_dev,
-                       adam=(exp_avg_rows, exp_avg_sq_rows, step_counter), nxt=(fm_next, bias, out_next), weight_clip=weight_clip,
+                       adam=(exp_avg_rows, exp_avg_sq_rows, step_counter), nxt=(fm_next, bias, out_next), weight_clip=weight_clip, ema=ema,
                        scalars=(float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay), float(grad_scale)))
 
 
@@ -1645,15 +1669,93 @@ class WeightClip:
         return (self.bound, self.array, len(self.ranges))
 
 
+def checked_ema_decay(value) -> float:
+    """The weight average's decay as a float: 0 (off) or a number in (0, 1); ValueError otherwise."""
+    value = float(value)
+    if not 0.0 <= value < 1.0:  # (NaN fails the comparison)
+        raise ValueError(f"ema_decay = {value} must be 0 (off) or lie in (0, 1)")
+    return value
+
+
+def ema_omd(decay: float) -> float:
+    """The rate the kernels take for `decay` (include/nnue_hip.h, "weight average"): float32(1 - float64(decay))."""
+    return float(torch.tensor(1.0 - float(decay), dtype=torch.float64).to(torch.float32))
+
+
+EMA_WARMUP_MAX = 1 << 24  # entries of a warm-up table (64 MB): decays up to 1 - 5.4e-7
+
+
+def ema_warmup_table(decay: float) -> torch.Tensor:
+    """The rates of a warmed-up average as a per-step table (float32, CPU) for nnue_lr_schedule_step: step t, counted from 0,
+    uses omd_t = float32(1 - decay_t) with decay_t = min(decay, (1 + t) / (10 + t)) in float64; the table ends at the first t
+    at which the decay itself is reached, which every later step then uses (the schedule launch clamps its position)."""
+    decay = checked_ema_decay(decay)
+    if decay == 0.0:
+        raise ValueError("a warm-up needs ema_decay > 0")
+    n = 1
+    if decay > 0.1:  # (1 + t) / (10 + t) >= decay  <=>  t >= (10 decay - 1) / (1 - decay)
+        n = int((10.0 * decay - 1.0) / (1.0 - decay)) + 2
+    if n > EMA_WARMUP_MAX:
+        raise ValueError(f"ema_warmup with ema_decay = {decay} needs a table of {n} steps (at most {EMA_WARMUP_MAX})")
+    t = torch.arange(n, dtype=torch.float64)
+    decay_t = torch.clamp((1.0 + t) / (10.0 + t), max=decay)
+    return (1.0 - decay_t).to(torch.float32)
+
+
+class WeightAverage:
+    """The weight average as the optimizer calls take it (``ema=``; include/nnue_hip.h, "weight average"): the average's
+    buffer, laid out like the parameters the call updates, its rate omd = float32(1 - decay), and optionally the device float32
+    scalar that replaces the rate (as lr_dev replaces lr)."""
+
+    def __init__(self, ema: torch.Tensor, omd: float, omd_dev: Optional[torch.Tensor] = None):
+        self.ema = _need(ema, torch.float32, "weight average")
+        self.omd = float(omd)
+        if omd_dev is None and not 0.0 < self.omd <= 1.0:
+            raise ValueError(f"the weight average's rate omd = {self.omd} must lie in (0, 1]")
+        if omd_dev is not None:
+            _need(omd_dev, torch.float32, "weight average's rate", (1,))
+        self.omd_dev = omd_dev
+
+    def window(self, lo: int, hi: int) -> "WeightAverage":
+        """The average of the slice [lo, hi) of the buffer (the sharded update's shard)."""
+        return WeightAverage(self.ema[lo:hi], self.omd, self.omd_dev)
+
+    def args(self):
+        return (self.ema.data_ptr(), self.omd, _ptr(self.omd_dev))
+
+
+def ema_update(ema: torch.Tensor, params: torch.Tensor, omd: float, omd_dev: Optional[torch.Tensor] = None) -> None:
+    """ema <- fmaf(omd, params - ema, ema), element by element: the stand-alone pass of the weight average (nnue_ema_update).
+    Contiguous float32 tensors of one shape, any 4-byte-aligned views; omd_dev (device float32 scalar) replaces omd."""
+    _need(ema, torch.float32, "weight average")
+    _need(params, torch.float32, "params", tuple(ema.shape))
+    if not ema.is_contiguous() or not params.is_contiguous():
+        raise ValueError("ema_update: both tensors must be contiguous (the average is written in place)")
+    if omd_dev is not None:
+        _need(omd_dev, torch.float32, "weight average's rate", (1,))
+    _call("nnue_ema_update", ema.data_ptr(), params.data_ptr(), ema.numel(), float(omd), _ptr(omd_dev), _stream(ema))
+
+
+def _clip_ema_args(clip: Optional[WeightClip], ema: Optional[WeightAverage], shape):
+    """(entry-point suffix, arguments between lr_dev and the stream) of a flat optimizer call."""
+    clipped = clip is not None and clip.on
+    if ema is not None:
+        _need(ema.ema, torch.float32, "weight average", shape)
+        return "_ema", (*(clip.args() if clipped else (0.0, None, 0)), *ema.args())
+    return ("_clip", clip.args()) if clipped else ("", ())
+
+
 def sgd_step(params: torch.Tensor, grads: torch.Tensor, momentum_buf: Optional[torch.Tensor], lr: float,
              momentum: float, weight_decay: float, max_norm: float, grad_scale: float, first_step: bool,
              norm_out: Optional[torch.Tensor], scratch: torch.Tensor, ste=None, ext=None,
              coef_out: Optional[torch.Tensor] = None, ext_applied_elsewhere: bool = False,
-             lr_dev: Optional[torch.Tensor] = None, clip: Optional[WeightClip] = None) -> None:
+             lr_dev: Optional[torch.Tensor] = None, clip: Optional[WeightClip] = None,
+             ema: Optional[WeightAverage] = None) -> None:
     """ste = (partial scratch of ste_conv_backward(stages=1), chunks, fps, d_thr, d_weight): the deferred second stage
     runs inside the norm launch; d_thr / d_weight must be the first elements of `grads`.  lr_dev (device float32 scalar): the
     learning rate is read from it instead of `lr` (changes between steps need no re-recording / re-capture).  clip (a
-    WeightClip that is ``on``): nnue_sgd_step_clip, which clamps the updated elements of its ranges; None or off: nnue_sgd_step."""
+    WeightClip that is ``on``): nnue_sgd_step_clip, which clamps the updated elements of its ranges; None or off: nnue_sgd_step.
+    ema (a WeightAverage laid out like params): nnue_sgd_step_ema, which also moves the average of every element it stores."""
     params = _need(params, torch.float32, "flat params")
     grads = _need(grads, torch.float32, "flat grads", tuple(params.shape))
     if momentum_buf is not None:
@@ -1665,11 +1767,11 @@ def sgd_step(params: torch.Tensor, grads: torch.Tensor, momentum_buf: Optional[t
         ste_args = (None, 0, 0, None, None)
     # ext = (partials, lo, hi): a producer's sums of squares for grads[lo:hi] (e.g. ftm_backward(sq_partial=...))
     ext_args = (ext[0].data_ptr(), ext[0].numel(), int(ext[1]), int(ext[2])) if ext is not None else (None, 0, 0, 0)
-    clipped = clip is not None and clip.on
-    _call("nnue_sgd_step_clip" if clipped else "nnue_sgd_step", params.data_ptr(), grads.data_ptr(), _ptr(momentum_buf), params.numel(), float(lr),
+    suffix, tail = _clip_ema_args(clip, ema, tuple(params.shape))
+    _call("nnue_sgd_step" + suffix, params.data_ptr(), grads.data_ptr(), _ptr(momentum_buf), params.numel(), float(lr),
           float(momentum), float(weight_decay), float(max_norm), float(grad_scale), int(bool(first_step)),
           _ptr(norm_out), scratch.data_ptr(), scratch.numel(), *ste_args, *ext_args, _ptr(coef_out), int(bool(ext_applied_elsewhere)),
-          _ptr(lr_dev), *(clip.args() if clipped else ()), _stream(params))
+          _ptr(lr_dev), *tail, _stream(params))
 
 
 def lr_schedule_step(table: torch.Tensor, position: torch.Tensor, lr_out: torch.Tensor) -> None:
@@ -1688,10 +1790,10 @@ def adam_step(params: torch.Tensor, grads: torch.Tensor, exp_avg: torch.Tensor, 
               max_norm: float = 0.0, grad_scale: float = 1.0, norm_out: Optional[torch.Tensor] = None,
               scratch: Optional[torch.Tensor] = None, lr_dev: Optional[torch.Tensor] = None, ext=None,
               coef_out: Optional[torch.Tensor] = None, ext_applied_elsewhere: bool = False,
-              clip: Optional[WeightClip] = None) -> None:
+              clip: Optional[WeightClip] = None, ema: Optional[WeightAverage] = None) -> None:
     """ext / coef_out / ext_applied_elsewhere as in sgd_step (nnue_adam_step_ext): ext = (partials, lo, hi), a producer's sums of
     squares for grads[lo:hi]; with ext_applied_elsewhere that range of params and moments is left to the producer.  clip as in
-    sgd_step: the ``_clip`` sibling of whichever of the two entry points the call takes."""
+    sgd_step: the ``_clip`` sibling of whichever of the two entry points the call takes; ema as in sgd_step: its ``_ema`` sibling."""
     params = _need(params, torch.float32, "flat params")
     shape = tuple(params.shape)
     grads = _need(grads, torch.float32, "flat grads", shape)
@@ -1700,16 +1802,15 @@ def adam_step(params: torch.Tensor, grads: torch.Tensor, exp_avg: torch.Tensor, 
     _need(step_counter, torch.int32, "step counter", (1,))
     if scratch is None:
         scratch = torch.empty((sgd_scratch_bytes(params.numel()),), dtype=torch.uint8, device=params.device)
-    clipped = clip is not None and clip.on
-    clip_args = clip.args() if clipped else ()
+    suffix, clip_args = _clip_ema_args(clip, ema, shape)
     if ext is not None or coef_out is not None or ext_applied_elsewhere:
         ext_args = (ext[0].data_ptr(), ext[0].numel(), int(ext[1]), int(ext[2])) if ext is not None else (None, 0, 0, 0)
-        _call("nnue_adam_step_ext_clip" if clipped else "nnue_adam_step_ext", params.data_ptr(), grads.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(),
+        _call("nnue_adam_step_ext" + suffix, params.data_ptr(), grads.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(),
               step_counter.data_ptr(), params.numel(), float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
               float(max_norm), float(grad_scale), _ptr(norm_out), scratch.data_ptr(), scratch.numel(), *ext_args, _ptr(coef_out),
               int(bool(ext_applied_elsewhere)), _ptr(lr_dev), *clip_args, _stream(params))
         return
-    _call("nnue_adam_step_clip" if clipped else "nnue_adam_step", params.data_ptr(), grads.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(),
+    _call("nnue_adam_step" + suffix, params.data_ptr(), grads.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(),
           step_counter.data_ptr(), params.numel(), float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
           float(max_norm), float(grad_scale), _ptr(norm_out), scratch.data_ptr(), scratch.numel(), _ptr(lr_dev), *clip_args, _stream(params))
 

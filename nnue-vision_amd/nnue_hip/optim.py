@@ -12,6 +12,11 @@ The reference's inner loop (train.py:359-366) ends in ``clip_grad_norm_`` and ``
 [-weight_clip, weight_clip] inside the update launch -- the reference's ``_clip_weights`` (nnue.py:528-539) at 1.0, for a group
 holding ``input.weight`` and the classifier's three weights; the rest goes into a group without it.
 
+``ema_decay`` (a per-group option, 0 = off, else in (0, 1); the keyword is the groups' default) keeps a moving average of every
+parameter of the group in ``state[p]["ema"]`` -- a clone of the parameter made at its first step, then moved by the update launch
+itself: ``e <- fmaf(omd, p_new - e, e)`` with omd = float32(1 - ema_decay) (include/nnue_hip.h, "weight average").
+``optimizer.ema_state()`` returns {parameter: its average}.
+
 They subclass ``torch.optim.SGD`` / ``torch.optim.Adam``: the constructor signature, ``param_groups``, ``zero_grad``,
 hooks, schedulers and the ``state_dict`` format are torch's own, so a checkpoint moves between these and torch's
 optimizers (and ``NnueTrainer.optimizer_state_dict()``) in both directions.  Options the kernels do not implement are
@@ -40,13 +45,13 @@ def _refuse(cond: bool, what: str) -> None:
 class _Table:
     """The host arrays of one segment list, kept between steps and refilled in place (no allocation after the first step)."""
 
-    FIELDS = ("params", "grads", "m", "v", "steps", "counts", "lr", "a", "b", "eps", "wd", "first", "clip")
+    FIELDS = ("params", "grads", "m", "v", "steps", "counts", "lr", "a", "b", "eps", "wd", "first", "clip", "ema", "omd")
 
     def __init__(self, params: List[torch.Tensor]):
         n = self.n = len(params)
-        self.params, self.grads, self.m, self.v, self.steps = ((_P * n)() for _ in range(5))
+        self.params, self.grads, self.m, self.v, self.steps, self.ema = ((_P * n)() for _ in range(6))
         self.counts = (ctypes.c_int64 * n)(*[p.numel() for p in params])
-        self.lr, self.a, self.b, self.eps, self.wd, self.clip = ((ctypes.c_float * n)() for _ in range(6))
+        self.lr, self.a, self.b, self.eps, self.wd, self.clip, self.omd = ((ctypes.c_float * n)() for _ in range(7))
         self.first = (ctypes.c_int32 * n)()
         self.addr = {k: ctypes.addressof(getattr(self, k)) for k in self.FIELDS}
         dev = params[0].device
@@ -66,6 +71,7 @@ class _MultiTensor:
     def _setup(self) -> None:
         self.defaults["max_grad_norm"] = self._max_grad_norm
         self.defaults["weight_clip"] = self._weight_clip
+        self.defaults["ema_decay"] = self._ema_decay
         self.grad_norm: Optional[torch.Tensor] = None  # the pre-clip norm of the last step (a device scalar; None: no clip)
         self._table: Optional[_Table] = None
         self._key = None
@@ -75,6 +81,7 @@ class _MultiTensor:
         if param_group["max_grad_norm"] != self._max_grad_norm:
             raise ValueError(_GLOBAL_CLIP)
         param_group.setdefault("weight_clip", self._weight_clip)
+        param_group.setdefault("ema_decay", self._ema_decay)
         super().add_param_group(param_group)
         try:
             self._check_group(self.param_groups[-1])
@@ -84,17 +91,19 @@ class _MultiTensor:
 
     def _check_group(self, g: dict) -> None:
         g["weight_clip"] = lib.checked_weight_clip(g.get("weight_clip", 0.0))
+        g["ema_decay"] = lib.checked_ema_decay(g.get("ema_decay", 0.0))
         _refuse(isinstance(g["lr"], torch.Tensor), "a tensor lr")
         _refuse(isinstance(g["weight_decay"], torch.Tensor), "a tensor weight_decay")
         for k in ("maximize", "fused", "capturable", "differentiable"):
             _refuse(bool(g.get(k)), f"{k}=True")
 
     def load_state_dict(self, state_dict: dict) -> None:
-        own = [g["weight_clip"] for g in self.param_groups]
+        own = [(g["weight_clip"], g["ema_decay"]) for g in self.param_groups]
         super().load_state_dict(state_dict)
-        for g, clip in zip(self.param_groups, own):  # a torch.optim state_dict has no max_grad_norm: ours stays
+        for g, (clip, decay) in zip(self.param_groups, own):  # a torch.optim state_dict has no max_grad_norm: ours stays
             g["max_grad_norm"] = self._max_grad_norm
             g.setdefault("weight_clip", clip)  # (a group option like any other: the dict's value where it has one)
+            g.setdefault("ema_decay", decay)
             self._check_group(g)
         self._key = None  # the state tensors were replaced
 
@@ -130,10 +139,18 @@ class _MultiTensor:
         max_norm = self._max_grad_norm
         if device.type != "cuda":  # the CPU convenience path: the same formulas in stock torch
             self.grad_norm = torch.nn.utils.clip_grad_norm_([p for p, _ in segs], max_norm, foreach=False) if max_norm > 0 else None
+            # a new average starts as the parameter it follows: cloned before the update, entered into the state after it (torch's
+            # Adam creates its own state only in an empty dict)
+            new = {p: p.detach().clone(memory_format=torch.contiguous_format) for p, g in segs
+                   if g["ema_decay"] and self.state.get(p, {}).get("ema") is None}
             super().step()
-            for p, g in segs:
+            for p, e in new.items():
+                self.state[p]["ema"] = e
+            for (p, g), before in zip(segs, self._averages(segs)):
                 if g["weight_clip"] > 0:
                     p.clamp_(-g["weight_clip"], g["weight_clip"])
+                if before is not None:
+                    before.lerp_(p, lib.ema_omd(g["ema_decay"]))
             return loss
         key = tuple(id(p) for p, _ in segs)
         if key != self._key:  # a new set of parameters with gradients (or new state tensors): new arrays
@@ -147,10 +164,32 @@ class _MultiTensor:
             t.wd[i] = g["weight_decay"]
             t.clip[i] = g["weight_clip"]  # the group's weight clip (0: the segment is not clamped)
         self._fill_state(t, segs)
+        for i, ((p, g), e) in enumerate(zip(segs, self._averages(segs))):  # (after _fill_state: Adam's lazy state asks for an empty dict)
+            t.ema[i] = None if e is None else _state_buffer(self.state[p], "ema", p).data_ptr()
+            t.omd[i] = 0.0 if e is None else lib.ema_omd(g["ema_decay"])
         norm_out = t.norm.data_ptr() if max_norm > 0 else None
         self._launch(t, max_norm, norm_out, torch.cuda.current_stream(device).cuda_stream)
         self.grad_norm = t.norm if max_norm > 0 else None
         return loss
+
+
+    def _averages(self, segs):
+        """Per segment the parameter's average (``state[p]["ema"]``, a clone of the parameter where the group asks for one and
+        there is none yet) or None."""
+        out = []
+        for p, g in segs:
+            if not g["ema_decay"]:
+                out.append(None)
+                continue
+            st = self.state[p]
+            if st.get("ema") is None:
+                st["ema"] = p.detach().clone(memory_format=torch.contiguous_format)
+            out.append(st["ema"])
+        return out
+
+    def ema_state(self) -> dict:
+        """{parameter: its moving average} for every parameter that has one (a group with ema_decay > 0, after its first step)."""
+        return {p: self.state[p]["ema"] for g in self.param_groups for p in g["params"] if self.state.get(p, {}).get("ema") is not None}
 
 
 def _state_buffer(state: dict, key: str, p: torch.Tensor) -> torch.Tensor:
@@ -167,7 +206,7 @@ class SGD(_MultiTensor, torch.optim.SGD):
 
     def __init__(self, params, lr: float = 1e-3, momentum: float = 0.0, dampening: float = 0.0, weight_decay: float = 0.0,
                  nesterov: bool = False, *, maximize: bool = False, foreach: Optional[bool] = None, differentiable: bool = False,
-                 fused: Optional[bool] = None, max_grad_norm: float = 0.0, weight_clip: float = 0.0):
+                 fused: Optional[bool] = None, max_grad_norm: float = 0.0, weight_clip: float = 0.0, ema_decay: float = 0.0):
         _refuse(bool(nesterov), "nesterov=True")
         _refuse(dampening != 0, "dampening != 0")
         _refuse(bool(maximize), "maximize=True")
@@ -176,6 +215,7 @@ class SGD(_MultiTensor, torch.optim.SGD):
         _refuse(isinstance(lr, torch.Tensor), "a tensor lr")
         self._max_grad_norm = float(max_grad_norm)
         self._weight_clip = lib.checked_weight_clip(weight_clip)  # the default of a group that does not set its own
+        self._ema_decay = lib.checked_ema_decay(ema_decay)        # likewise
         super().__init__(params, lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov,
                          maximize=maximize, foreach=False, differentiable=differentiable, fused=fused)
         self._setup()
@@ -202,6 +242,10 @@ class SGD(_MultiTensor, torch.optim.SGD):
 
     def _launch(self, t: _Table, max_norm: float, norm_out, stream: int) -> None:
         A = t.addr
+        if any(t.ema):
+            lib._call("nnue_multi_sgd_step_ema", A["params"], A["grads"], A["m"], A["counts"], t.n, A["lr"], A["a"], A["wd"], A["first"],
+                      A["clip"], max_norm, norm_out, t.scratch.data_ptr(), t.scratch.numel(), None, A["ema"], A["omd"], stream)
+            return
         if any(t.clip):
             lib._call("nnue_multi_sgd_step_clip", A["params"], A["grads"], A["m"], A["counts"], t.n, A["lr"], A["a"], A["wd"], A["first"],
                       A["clip"], max_norm, norm_out, t.scratch.data_ptr(), t.scratch.numel(), None, stream)
@@ -219,7 +263,7 @@ class Adam(_MultiTensor, torch.optim.Adam):
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
                  amsgrad: bool = False, *, foreach: Optional[bool] = None, maximize: bool = False, capturable: bool = False,
                  differentiable: bool = False, fused: Optional[bool] = None, decoupled_weight_decay: bool = False,
-                 max_grad_norm: float = 0.0, weight_clip: float = 0.0):
+                 max_grad_norm: float = 0.0, weight_clip: float = 0.0, ema_decay: float = 0.0):
         _refuse(bool(amsgrad), "amsgrad=True")
         _refuse(bool(decoupled_weight_decay), "decoupled_weight_decay=True")
         _refuse(bool(maximize), "maximize=True")
@@ -230,6 +274,7 @@ class Adam(_MultiTensor, torch.optim.Adam):
         _refuse(any(isinstance(b, torch.Tensor) for b in betas), "tensor betas")
         self._max_grad_norm = float(max_grad_norm)
         self._weight_clip = lib.checked_weight_clip(weight_clip)  # the default of a group that does not set its own
+        self._ema_decay = lib.checked_ema_decay(ema_decay)        # likewise
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, foreach=False,
                          maximize=maximize, capturable=capturable, differentiable=differentiable, fused=fused,
                          decoupled_weight_decay=decoupled_weight_decay)
@@ -257,7 +302,7 @@ class Adam(_MultiTensor, torch.optim.Adam):
         steps = []
         for i, (p, g) in enumerate(segs):
             st = self.state[p]
-            if len(st) == 0:  # torch's lazy state
+            if "step" not in st:  # torch's lazy state (the dict may already hold a caller's "ema")
                 st["step"] = torch.tensor(0.0, dtype=torch.float32)
                 st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
                 st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
@@ -275,7 +320,11 @@ class Adam(_MultiTensor, torch.optim.Adam):
 
     def _launch(self, t: _Table, max_norm: float, norm_out, stream: int) -> None:
         A = t.addr
-        if any(t.clip):
+        if any(t.ema):
+            lib._call("nnue_multi_adam_step_ema", A["params"], A["grads"], A["m"], A["v"], A["steps"], A["counts"], t.n, A["lr"], A["a"],
+                      A["b"], A["eps"], A["wd"], A["clip"], max_norm, norm_out, t.scratch.data_ptr(), t.scratch.numel(), None, A["ema"],
+                      A["omd"], stream)
+        elif any(t.clip):
             lib._call("nnue_multi_adam_step_clip", A["params"], A["grads"], A["m"], A["v"], A["steps"], A["counts"], t.n, A["lr"], A["a"],
                       A["b"], A["eps"], A["wd"], A["clip"], max_norm, norm_out, t.scratch.data_ptr(), t.scratch.numel(), None, stream)
         else:

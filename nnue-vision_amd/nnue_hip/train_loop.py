@@ -33,6 +33,11 @@ NNUE model, minus the parts that are out of scope here (W&B, RunPod, dataset dow
   the device, such as a drop-in ``nnue.NNUE`` in eval mode -- returns for each training batch under ``torch.no_grad()``.
   ``distill_alpha > 0`` without a teacher is a ValueError; with alpha 0 a teacher is never called.  Evaluation stays plain
   cross-entropy.
+* ``ema_decay`` / ``ema_warmup`` (optional config attributes, 0 / False by default; a build extension): the trainer keeps a moving
+  average of the weights inside its update launches (``NnueTrainer(ema_decay=, ema_warmup=)``).  With the average on every
+  epoch's row gains ``val_ema/loss``, ``val_ema/f1`` and ``val_ema/accuracy`` -- and ``compiled_ema/*`` beside ``compiled/*`` --
+  all measured through ``trainer.ema_weights()``, and the checkpoints gain ``ema_state_dict`` (the averaged parameters under the
+  model's state-dict keys).  The best model is selected on ``val/f1`` as before.
 * ``weight_clip`` (optional config attribute, 0 by default; a build extension): the trainer clamps the table and the classifier's
   weights to [-weight_clip, weight_clip] inside every optimizer update.  1.0 is what the export clamps to (``_clip_weights``,
   nnue.py:528-539): the metrics of a run trained with it describe the network ``serialize_model`` writes.
@@ -113,6 +118,15 @@ def config_weight_clip(config) -> float:
     return lib.checked_weight_clip(getattr(config, "weight_clip", 0.0))
 
 
+def config_ema(config):
+    """(ema_decay, ema_warmup) of the config (0, False where it has none), checked as the trainer checks them: ValueError for a
+    decay outside [0, 1) or NaN, and for a warm-up without a decay."""
+    decay, warmup = lib.checked_ema_decay(getattr(config, "ema_decay", 0.0)), bool(getattr(config, "ema_warmup", False))
+    if warmup and not decay:
+        raise ValueError("the config sets ema_warmup without ema_decay > 0")
+    return decay, warmup
+
+
 def run_training(config, train_loader: Iterable, val_loader: Iterable, test_loader: Optional[Iterable] = None, model=None,
                  checkpoint_dir=None, log: Callable[[str], None] = print, use_graph: bool = True,
                  compiled_eval: Optional[bool] = None, save_last: Optional[bool] = None, resume_from=None,
@@ -129,6 +143,7 @@ def run_training(config, train_loader: Iterable, val_loader: Iterable, test_load
         resume_from = getattr(config, "resume_from", None)
     optimizer_type = "sgd" if config.optimizer_type == "sgd" else "adam"
     weight_clip = config_weight_clip(config)
+    ema_decay, ema_warmup = config_ema(config)
     resumed = _read_resume_file(resume_from, config, optimizer_type) if resume_from else None
     if compiled_eval is None:
         compiled_eval = bool(getattr(config, "compiled_eval", False))
@@ -158,7 +173,8 @@ def run_training(config, train_loader: Iterable, val_loader: Iterable, test_load
     trainer = NnueTrainer(model, batch, hw, lr=float(config.learning_rate), weight_decay=float(config.weight_decay),
                           max_grad_norm=clip, use_graph=use_graph, input_slots=8 if in_place else 1,
                           label_smoothing=float(getattr(config, "label_smoothing", 0.0)), two_labels=mixes, weight_clip=weight_clip,
-                          distill_alpha=distill_alpha, distill_temperature=distill_temperature, **opt)
+                          distill_alpha=distill_alpha, distill_temperature=distill_temperature, ema_decay=ema_decay,
+                          ema_warmup=ema_warmup, **opt)
     if lr_schedule is None and getattr(config, "lr_schedule", False):
         lr_schedule = LrSchedule.from_config(config, len(train_loader))
     if isinstance(lr_schedule, LrSchedule):
@@ -218,6 +234,21 @@ def run_training(config, train_loader: Iterable, val_loader: Iterable, test_load
                         "compiled/ms_per_sample": compiled["ms_per_sample"], "compiled/latent_density": compiled["latent_density"]})
             line += (f" | Compiled F1: {compiled['f1']:.4f}, Compiled Acc: {compiled['acc']:.4f}, "
                      f"Speed: {compiled['ms_per_sample']:.2f}ms/sample, Density: {compiled['latent_density']:.4f}")
+        ema_state = None
+        if trainer.flat_ema is not None:  # the averaged network, through the live parameters (every rank: a collective when sharded)
+            with trainer.ema_weights():
+                model.eval()
+                ema_loss, ema_metrics = evaluate.evaluate_model(model, val_loader, None, device)
+                model.train()
+                row.update({"val_ema/loss": ema_loss, "val_ema/f1": ema_metrics["f1"], "val_ema/accuracy": ema_metrics["acc"]})
+                line += f" | EMA Val Loss: {ema_loss:.4f}, EMA Val F1: {ema_metrics['f1']:.4f}, EMA Val Acc: {ema_metrics['acc']:.4f}"
+                if engine is not None:
+                    engine.requantize(model)
+                    compiled = evaluate.evaluate_engine(engine, val_loader, source=compiled_eval_source)
+                    row.update({"compiled_ema/f1": compiled["f1"], "compiled_ema/accuracy": compiled["acc"],
+                                "compiled_ema/ms_per_sample": compiled["ms_per_sample"],
+                                "compiled_ema/latent_density": compiled["latent_density"]})
+                ema_state = {k: v.detach().cpu().clone() for k, v in trainer.ema_state().items()}
         result.history.append(row)
         log(line)
         # with save_last EVERY rank takes the trainer's state once per epoch, whatever its own best-F1 decision (under the
@@ -226,11 +257,14 @@ def run_training(config, train_loader: Iterable, val_loader: Iterable, test_load
         writes = ckpt_dir is not None and (not save_last or trainer.dp.rank == 0)
 
         def five_keys():
-            return {"epoch": epoch,
+            keys = {"epoch": epoch,
                     "model_state_dict": {k: v.detach().cpu().clone() for k, v in model.state_dict().items()},
                     "optimizer_state_dict": state["optimizer"] if save_last else _to_cpu(trainer.optimizer_state_dict()),
                     "metrics": {"val_f1": val_metrics["f1"], "val_loss": val_loss},
                     "config_name": config.name}
+            if ema_state is not None:  # (only with the average on: a run without it writes the five keys it always wrote)
+                keys["ema_state_dict"] = ema_state
+            return keys
         if val_metrics["f1"] > result.best_val_f1:
             result.best_val_f1, result.best_epoch = val_metrics["f1"], epoch
             if ckpt_dir is not None:

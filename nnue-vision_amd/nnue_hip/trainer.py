@@ -27,6 +27,7 @@ SGD step) is one fixed sequence of HIP kernels here, working on preallocated buf
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Tuple
@@ -195,7 +196,7 @@ class NnueTrainer:
                  weight_decay: float = 0.0, max_grad_norm: float = 0.0, group=None, use_graph: bool = True,
                  input_slots: int = 1, optimizer: str = "sgd", betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
                  ft_path: Optional[str] = None, label_smoothing: float = 0.0, two_labels: bool = False, weight_clip: float = 0.0,
-                 distill_alpha: float = 0.0, distill_temperature: float = 1.0):
+                 distill_alpha: float = 0.0, distill_temperature: float = 1.0, ema_decay: float = 0.0, ema_warmup: bool = False):
         """ft_path: the FeatureTransformer kernel family, as lib.ft_path's ``mode`` (None: NNUE_FT_PATH decides).
         label_smoothing (F.cross_entropy's, in [0, 1)) and two_labels (a second label and a weight per sample: mixup, CutMix) make
         the classifier step train on soft targets (include/nnue_hip.h, "soft targets"); with both at their defaults the step is
@@ -206,7 +207,15 @@ class NnueTrainer:
         distill_alpha (in [0, 1]) and distill_temperature (> 0): with alpha > 0 the loss is (1 - alpha) times the (soft) cross-entropy
         plus alpha T^2 KL(teacher at T || student at T) (include/nnue_hip.h, "soft targets": the teacher arm) on the teacher logits
         of ``teacher_inputs[s]`` (float32 [B, C] per input slot; ``step(..., teacher_logits=)`` or a loader's teacher fills them).
-        With alpha == 0 nothing is allocated and no call changes."""
+        With alpha == 0 nothing is allocated and no call changes.
+        ema_decay (0: off, nothing is allocated and no call changes; else in (0, 1)): a moving average of every trainable parameter,
+        ``flat_ema``, kept by the launches that apply the update (include/nnue_hip.h, "weight average") -- bit for bit the plain step
+        plus ``e <- fmaf(omd, w_new - e, e)`` per element with omd = float32(1 - decay); read it through ``ema_state()`` and
+        ``ema_weights()``.  ema_warmup: step t (from 0) averages with decay_t = min(ema_decay, (1 + t) / (10 + t))."""
+        self._ema_decay = lib.checked_ema_decay(ema_decay)
+        self.ema_warmup = bool(ema_warmup)
+        if self.ema_warmup and not self._ema_decay:
+            raise ValueError("ema_warmup needs ema_decay > 0")
         self._label_smoothing, self.two_labels = _checked_label_smoothing(label_smoothing), bool(two_labels)
         self.distill_alpha, self.distill_temperature = lib.check_distill(distill_alpha, distill_temperature)
         weight_clip = lib.checked_weight_clip(weight_clip)
@@ -244,6 +253,21 @@ class NnueTrainer:
         self.flat_exp_avg_sq = torch.zeros(self.layout.count, **f32) if optimizer == "adam" else None
         self.adam_step_count = torch.zeros(1, dtype=torch.int32, device=self.dev) if optimizer == "adam" else None
         self.dp.broadcast(self.flat_params)  # identical replicas even if ranks were seeded differently
+        # the weight average: a clone of the (broadcast) parameters; its rate lives in a device scalar the kernels read, so
+        # ``trainer.ema_decay = x`` is one fill and a warm-up moves it per step -- plans and graphs stay valid either way
+        self.flat_ema = self.ema_omd_dev = self._ema = self._ema_table = self._ema_spare = None
+        self.ema_table = self.ema_pos = None
+        self.ema_position = 0
+        self._ema_swapped = False  # inside ``ema_weights()``: the live parameters hold the average
+        if self._ema_decay:
+            self.flat_ema = self.flat_params.clone()
+            self.ema_omd_dev = torch.full((1,), lib.ema_omd(self._ema_decay), **f32)
+            self._ema = lib.WeightAverage(self.flat_ema, lib.ema_omd(self._ema_decay), self.ema_omd_dev)
+            # (the table's own rows of it, for _table_update; the two share the device rate, and _set_ema_decay keeps their omd alike)
+            self._ema_table = lib.WeightAverage(self.layout.views(self.flat_ema)["input.weight"], self._ema.omd, self.ema_omd_dev)
+            if self.ema_warmup:
+                self.ema_table = lib.ema_warmup_table(self._ema_decay).to(self.dev)
+                self.ema_pos = torch.zeros((1,), dtype=torch.int32, device=self.dev)
         self.p = self.layout.views(self.flat_params)
         self.g = self.layout.views(self.flat_grads)
         # gradient buckets: [threshold, conv weight] come last out of the backward and lead the flat buffer
@@ -406,6 +430,38 @@ class NnueTrainer:
     max_grad_norm = property(lambda self: self._hyper["max_grad_norm"], lambda self, v: self._set_hyper("max_grad_norm", float(v)))
     weight_clip = property(lambda self: self._hyper["weight_clip"], lambda self, v: self._set_hyper("weight_clip", float(v)))
 
+    # The weight average's decay: its rate omd = float32(1 - decay) is a device scalar (``ema_omd_dev``) like the learning rate, so
+    # a change costs one fill and keeps every plan and graph.  Under a warm-up the rate comes from a per-step table instead: a new
+    # decay makes a new table and re-records the update plans, as a new learning-rate schedule does.  The average cannot be
+    # switched on or off after construction (its buffer is an argument of the recorded calls).
+    def _set_ema_decay(self, value: float) -> None:
+        value = lib.checked_ema_decay(value)
+        if bool(value) != (self.flat_ema is not None):
+            raise ValueError("the weight average cannot be switched on or off after construction")
+        if value == self._ema_decay:
+            return
+        self._ema_decay = value
+        self._ema.omd = self._ema_table.omd = lib.ema_omd(value)
+        if self.ema_table is None:
+            self.ema_omd_dev.fill_(self._ema.omd)
+        else:  # (ema_omd_dev keeps the last step's rate; the next step's comes out of the new table at the same position)
+            self.ema_table = lib.ema_warmup_table(value).to(self.dev)
+            self._drop_update_plans()
+
+    ema_decay = property(lambda self: self._ema_decay, _set_ema_decay)
+
+    def _flat_ema(self, lo: int = 0, hi: Optional[int] = None) -> Optional[lib.WeightAverage]:
+        """The weight average as the flat optimizer calls take it, or None when it is off; [lo, hi): the slice of the flat
+        buffers the call covers (the sharded update's shard)."""
+        if self._ema is None:
+            return None
+        return self._ema if hi is None else self._ema.window(lo, hi)
+
+    def _ema_tick(self) -> None:
+        """The warm-up's launch of one optimizer step, beside _lr_tick: this step's rate out of the table into ema_omd_dev."""
+        if self.ema_table is not None:
+            lib.lr_schedule_step(self.ema_table, self.ema_pos, self.ema_omd_dev)
+
     def _flat_clip(self, lo: int = 0, hi: Optional[int] = None) -> Optional[lib.WeightClip]:
         """The weight clip as the flat optimizer calls take it, or None when it is off; [lo, hi): the slice of the flat buffers
         the call covers (the sharded update's shard)."""
@@ -463,6 +519,8 @@ class NnueTrainer:
         """The host's count of optimizer steps, and the schedule's mirrors with it (lr_position; _hyper['lr'] = what lr_dev
         now holds)."""
         self.steps_done += steps
+        if self.ema_table is not None:
+            self.ema_position = min(self.ema_position + steps, 2**31 - 1)
         if self._lr_values is not None:
             self.lr_position = min(self.lr_position + steps, 2**31 - 1)
             self._hyper["lr"] = float(self._lr_values[min(self.lr_position - 1, self._lr_values.numel() - 1)])
@@ -583,19 +641,22 @@ class NnueTrainer:
         the table's rows alone and the clip coefficient in ``clip_coef`` for _table_update.  It is the first launch of a step that
         reads lr_dev, so the schedule's launch goes ahead of it."""
         self._lr_tick()
+        self._ema_tick()
         ext = (self.sq_partial, *self.mode.sq_range) if self.mode.sq != "none" else None
         elsewhere = self.mode.sq == "gram"
         clip = self._flat_clip()  # (the table rows left to _table_update are clamped there)
+        ema = self._flat_ema()  # (... and averaged there)
         if self.optimizer == "adam":
             lib.adam_step(self.flat_params, self.flat_grads, self.flat_exp_avg, self.flat_exp_avg_sq, self.adam_step_count,
                           self.lr, self.betas, self.eps, self.weight_decay, self.max_grad_norm, scale, self.grad_norm,
-                          self.sgd_scratch, lr_dev=self.lr_dev, ext=ext, coef_out=self.clip_coef, ext_applied_elsewhere=elsewhere, clip=clip)
+                          self.sgd_scratch, lr_dev=self.lr_dev, ext=ext, coef_out=self.clip_coef, ext_applied_elsewhere=elsewhere, clip=clip,
+                          ema=ema)
             return
         ste = ((self.ste_scratch, self.mode.ste_chunks, self.fps, self.g["visual_threshold"], self.g["conv.weight"])
                if self.mode.defer_ste else None)
         lib.sgd_step(self.flat_params, self.flat_grads, self.flat_momentum, self.lr, self.momentum, self.weight_decay,
                      self.max_grad_norm, scale, first, self.grad_norm, self.sgd_scratch, ste=ste, ext=ext,
-                     coef_out=self.clip_coef, ext_applied_elsewhere=elsewhere, lr_dev=self.lr_dev, clip=clip)
+                     coef_out=self.clip_coef, ext_applied_elsewhere=elsewhere, lr_dev=self.lr_dev, clip=clip, ema=ema)
 
     def _table_update(self, first: bool, scale: float, d_ft: torch.Tensor, fm, nxt=None) -> None:
         """The product d_W = A^T d_ft (A: map `fm`) with the table's update in its epilogue, after _small_update: SGD on the
@@ -611,7 +672,7 @@ class NnueTrainer:
             fn = lib.ftm_backward_weight_update if nxt is None else lib.ftm_backward_weight_update_forward
             mom = self.flat_momentum[lo:hi] if self.flat_momentum is not None else None
             opt = (mom, self.clip_coef, self.lr, self.momentum, self.weight_decay, scale, first)
-        fn(d_ft, fm, self.p["input.weight"], *opt, *forward, lr_dev=self.lr_dev, weight_clip=self.weight_clip)
+        fn(d_ft, fm, self.p["input.weight"], *opt, *forward, lr_dev=self.lr_dev, weight_clip=self.weight_clip, ema=self._ema_table)
 
     def _next_map(self, slot: int, nxt) -> None:
         """conv + {0,1} map of input slot `slot` into map `nxt`, between the two halves of an update that forms the next step's
@@ -652,10 +713,11 @@ class NnueTrainer:
         dp.all_gather(self.all_partials, self.local_partials)  # rank-major, fixed order: every rank forms the identical norm
         mom = dp.shard_of(self.flat_momentum) if self.flat_momentum is not None else None
         self._lr_tick()
+        self._ema_tick()
         per = self.grad_shard.numel()
         lib.sgd_step(dp.shard_of(self.flat_params), self.grad_shard, mom, self.lr, self.momentum, self.weight_decay, self.max_grad_norm,
                      scale, first, self.grad_norm, self.sgd_scratch, ext=(self.all_partials, 0, per), lr_dev=self.lr_dev,
-                     clip=self._flat_clip(dp.rank * per, (dp.rank + 1) * per))
+                     clip=self._flat_clip(dp.rank * per, (dp.rank + 1) * per), ema=self._flat_ema(dp.rank * per, (dp.rank + 1) * per))
         dp.all_gather(self.flat_params, dp.shard_of(self.flat_params))
 
     def _ranks_agree(self, ok: bool) -> bool:
@@ -674,6 +736,14 @@ class NnueTrainer:
         if self.mode.sharded_update and self.flat_momentum is not None and self.dp.world > 1 and self.steps_done > 0:
             torch.cuda.current_stream(self.dev).synchronize()
             self.dp.all_gather(self.flat_momentum, self.dp.shard_of(self.flat_momentum))
+
+    def _gather_ema_shards(self) -> None:
+        """The same for the weight average: under the sharded update every rank averages its own shard of the parameters, and
+        the shards meet only when somebody asks (ema_state, ema_weights, state_dict, rebuilt).  A COLLECTIVE where the condition
+        holds."""
+        if self.mode.sharded_update and self.flat_ema is not None and self.dp.world > 1 and self.steps_done > 0:
+            torch.cuda.current_stream(self.dev).synchronize()
+            self.dp.all_gather(self.flat_ema, self.dp.shard_of(self.flat_ema))
 
     def _optimizer_buffers(self):
         return [t for t in (self.flat_momentum, self.flat_exp_avg, self.flat_exp_avg_sq, self.adam_step_count) if t is not None]
@@ -755,6 +825,8 @@ class NnueTrainer:
             live = [self.flat_params, self.flat_grads, self.grad_norm] + self._optimizer_buffers()
             if self.lr_table is not None:  # (recording would otherwise move the schedule two steps)
                 live += [self.lr_pos, self.lr_dev]
+            if self.flat_ema is not None:
+                live += [self.flat_ema, self.ema_omd_dev] + ([self.ema_pos] if self.ema_pos is not None else [])
             keep = [t.clone() for t in live]  # recording executes the updates: put everything back afterwards
             with lib.record_calls() as calls:
                 self._update(True)
@@ -811,6 +883,7 @@ class NnueTrainer:
         ``teacher_logits`` (a trainer built with distill_alpha > 0, which needs them beside every copied batch; float32 [n, C]):
         the teacher's logits for ``images``, copied into ``teacher_inputs[slot]``; the rows behind a short batch are zeroed and,
         their labels being -1, do not count."""
+        self._not_swapped()
         ragged = self._stage(slot, images, labels, labels_b, lam, global_count, teacher_logits)
         _, upd_first, upd = self._plans(slot)
         self._last_alt = False
@@ -979,6 +1052,7 @@ class NnueTrainer:
         the next call overwrites); ``self.loss`` is not written.  Falls back to single steps while the plans are not recorded yet, without graphs, or with an eager
         collective.  ``timers`` ({C entry point: list}): the same launches issued eagerly with HIP events around the named
         calls (bench.py's per-kernel durations of the group form)."""
+        self._not_swapped()
         slots = tuple(int(s) for s in slots)
         if not slots or min(slots) < 0 or max(slots) >= len(self.inputs):
             raise ValueError(f"slots must name input slots 0..{len(self.inputs) - 1}")
@@ -1005,6 +1079,41 @@ class NnueTrainer:
         self._advance(len(slots))
         return ring[:len(slots)]
 
+    # ------------------------------------------------------------------ the weight average's surface
+    def _not_swapped(self) -> None:
+        if self._ema_swapped:
+            raise RuntimeError("a step inside ema_weights(): the live parameters hold the average; leave the context first")
+
+    def ema_state(self) -> Dict[str, torch.Tensor]:
+        """The averaged parameters, name -> view of ``flat_ema``, under the keys ``model.state_dict()`` has for them (nnue2score,
+        which never trains, is not averaged).  A COLLECTIVE under the sharded update with more than one rank: the shards are
+        gathered first."""
+        if self.flat_ema is None:
+            raise ValueError("this trainer keeps no weight average (ema_decay = 0)")
+        self._gather_ema_shards()
+        return self.layout.views(self.flat_ema)
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the context the model's live parameters hold the averaged values -- ``evaluate``, ``model(images)``,
+        ``serialize_model``, ``EngineModel.from_model`` and ``requantize`` see the averaged network unchanged; on exit the exact
+        bits of the trained parameters are back (a spare buffer, allocated on first use, keeps them).  No step may be taken
+        inside.  A COLLECTIVE where ema_state() is one."""
+        if self.flat_ema is None:
+            raise ValueError("this trainer keeps no weight average (ema_decay = 0)")
+        self._not_swapped()
+        self._gather_ema_shards()
+        if self._ema_spare is None:
+            self._ema_spare = torch.empty_like(self.flat_params)
+        self._ema_spare.copy_(self.flat_params)
+        self.flat_params.copy_(self.flat_ema)
+        self._ema_swapped = True
+        try:
+            yield self
+        finally:
+            self.flat_params.copy_(self._ema_spare)
+            self._ema_swapped = False
+
     def rebuilt(self, ft_path: str) -> "NnueTrainer":
         """A trainer for the same model, shapes, hyper-parameters and optimizer state that uses another FeatureTransformer
         kernel family (``"mfma"`` | ``"bits"`` | ``"list"`` | ``"auto"``: the constructor's ``ft_path``) -- the train loop's density check
@@ -1015,8 +1124,15 @@ class NnueTrainer:
         new = NnueTrainer(self.model, self.B, (self.H, self.W), group=self.dp.group, use_graph=self.use_graph, input_slots=len(self.inputs),
                           optimizer=self.optimizer, betas=self.betas, eps=self.eps, ft_path=ft_path, label_smoothing=self._label_smoothing,
                           two_labels=self.two_labels, distill_alpha=self.distill_alpha, distill_temperature=self.distill_temperature,
-                          **self._hyper)
+                          ema_decay=self._ema_decay, ema_warmup=self.ema_warmup, **self._hyper)
         self._gather_momentum_shards()
+        if self.flat_ema is not None:  # the average, its rate (a warm-up's last one) and the warm-up's position carry over
+            self._gather_ema_shards()
+            new.flat_ema.copy_(self.flat_ema)
+            new.ema_omd_dev.copy_(self.ema_omd_dev)
+            if self.ema_pos is not None:
+                new.ema_pos.copy_(self.ema_pos)
+                new.ema_position = self.ema_position
         for src, dst in zip(self._optimizer_buffers(), new._optimizer_buffers()):
             dst.copy_(src)
         new.steps_done = self.steps_done
@@ -1032,7 +1148,11 @@ class NnueTrainer:
         schedule = None
         if self._lr_values is not None:
             schedule = {"values": self._lr_values.clone(), "position": int(self.lr_position)}
-        return {"version": 1, "optimizer_type": self.optimizer, "optimizer": self.optimizer_state_dict(),
+        ema = None
+        if self.flat_ema is not None:
+            ema = {"decay": float(self._ema_decay), "warmup": bool(self.ema_warmup), "position": int(self.ema_position),
+                   "omd": self.ema_omd_dev.detach().clone(), "state": {k: v.clone() for k, v in self.ema_state().items()}}
+        return {"version": 1, "ema": ema, "optimizer_type": self.optimizer, "optimizer": self.optimizer_state_dict(),
                 "steps_done": int(self.steps_done), "lr": float(self._hyper["lr"]), "lr_schedule": schedule,
                 "label_smoothing": float(self._label_smoothing), "weight_clip": float(self.weight_clip),
                 "distill_alpha": float(self.distill_alpha), "distill_temperature": float(self.distill_temperature)}
@@ -1125,8 +1245,31 @@ class NnueTrainer:
         if held != (self.distill_alpha, self.distill_temperature):
             raise ValueError(f"the state was trained with distill_alpha = {held[0]}, distill_temperature = {held[1]}, "
                              f"this trainer's are {self.distill_alpha}, {self.distill_temperature}")
+        ema = sd.get("ema")  # (a state from before the key existed, or of a trainer without the average: None)
+        if (ema is None) != (self.flat_ema is None):
+            raise ValueError("the state " + ("has no" if ema is None else "carries a") + " weight average, this trainer "
+                             + ("keeps one" if ema is None else "keeps none") + f" (ema_decay = {self._ema_decay})")
+        if ema is not None:
+            if float(ema["decay"]) != self._ema_decay or bool(ema["warmup"]) != self.ema_warmup:
+                raise ValueError(f"the state's weight average has ema_decay = {float(ema['decay'])}, ema_warmup = {bool(ema['warmup'])}, "
+                                 f"this trainer's are {self._ema_decay}, {self.ema_warmup}")
+            if not 0 <= int(ema["position"]) <= 2**31 - 1:
+                raise ValueError(f"the weight average's warm-up position {int(ema['position'])} must lie in 0 .. 2^31 - 1")
+            for k, shape in zip(self.layout.names, self.layout.shapes):
+                t = ema["state"].get(k)
+                if not torch.is_tensor(t) or tuple(t.shape) != tuple(shape):
+                    raise ValueError(f"the state's weight average has no tensor of shape {tuple(shape)} for {k!r}")
+            if tuple(torch.as_tensor(ema["omd"]).shape) != (1,):
+                raise ValueError("the state's weight average has no rate ('omd': one float32)")
         # ---- validated: from here on only in-place copies
         self._apply_optimizer_state(sources, steps_done)
+        if ema is not None:
+            for k, v in self.layout.views(self.flat_ema).items():
+                v.copy_(ema["state"][k])
+            self.ema_omd_dev.copy_(torch.as_tensor(ema["omd"], dtype=torch.float32))
+            if self.ema_pos is not None:
+                self.ema_position = int(ema["position"])
+                self.ema_pos.fill_(self.ema_position)
         if schedule is None:
             self.clear_lr_schedule()
         elif self._lr_values is None or self._lr_values.numel() != values.numel():
