@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "nnue_hip.h"
 
 // Records a printf-style message retrievable through nnue_hip_last_error().
@@ -28,6 +29,14 @@ static inline bool nnue_aligned16(const void* p) { return (reinterpret_cast<uint
 static inline int64_t nnue_round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 
 constexpr int kWave = 64;  // CDNA4 wavefront
+
+// The optimizer updates' {weight clip} x {weight average} choice of a kernel instantiation, made in one place: calls
+// f(std::bool_constant<kClip>{}, std::bool_constant<kEma>{}) for the two run-time flags and returns what it returns.
+template <class F>
+static inline auto with_clip_ema(bool clip_on, bool ema_on, F&& f) {
+  if (ema_on) return clip_on ? f(std::true_type{}, std::true_type{}) : f(std::false_type{}, std::true_type{});
+  return clip_on ? f(std::true_type{}, std::false_type{}) : f(std::false_type{}, std::false_type{});
+}
 
 // Zero fills as ordinary kernels.  hipMemsetAsync captured into a hipGraph ahead of a kernel that scatters or
 // accumulates into the same buffer was observed not to be ordered reliably before that kernel on this stack (ROCm 7.0:

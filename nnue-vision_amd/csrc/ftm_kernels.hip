@@ -133,7 +133,7 @@ struct BwwSgdEpi {
 };
 
 // The same for the reference's other optimizer: clip_grad_norm_ + torch.optim.Adam (train.py:363-366, :465-470) applied to
-// the table rows and their two moments in place, element by element adam_apply_kernel's arithmetic with its fused multiply-adds
+// the table rows and their two moments in place, element by element adam_apply_ext_kernel's arithmetic with its fused multiply-adds
 // pinned (adam_update_fused: bitwise the fused update + forward pass, within a rounding per term of adam_update).  The
 // step number is the device counter the optimizer's norm launch has already advanced (nnue_adam_step_ext), so nothing in
 // the launch changes from step to step.  Only the bf16-split tiles take it (rmw_tile_adam).
@@ -765,7 +765,7 @@ __device__ __forceinline__ void rmw_tile_adam(float* __restrict__ smem, const Ep
     const float gv[4] = {g.x, g.y, g.z, g.w};
     u32x4 wn, mn, vn, en;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {  // the arithmetic of adam_apply_kernel, element by element (fused multiply-adds pinned)
+    for (int e = 0; e < 4; ++e) {  // the arithmetic of adam_apply_ext_kernel, element by element (fused multiply-adds pinned)
       float mi = __uint_as_float(mo[u][e]), vi = __uint_as_float(vv[u][e]);
       float wf = adam_update_fused(__uint_as_float(w[u][e]), gv[e], mi, vi, gs, bc, epi.beta1, epi.beta2, epi.eps, epi.wd);
       if constexpr (has_clip<Epi>::value) wf = clip_weight(wf, epi.wclip);
@@ -2371,7 +2371,7 @@ Shape plan(int M, int N, int K, bool prefer_m, bool allow_split, bool bf_ok = fa
 }
 
 // One product by the kernel of its Shape.  Only what an epilogue's callers can plan is instantiated: the in-place update
-// epilogues (update_product_shape) never see an f32 tile, and their 128-row tiles are always the 64-deep ones.
+// epilogues (update_launch) never see an f32 tile, and their 128-row tiles are always the 64-deep ones.
 template <bool AKC, bool BKC, class Epi>
 void launch(hipStream_t st, const Shape& s, Mat ma, Mat mb, Epi epi, int M, int N, int K, GroupArgs ga = GroupArgs{}) {
   const dim3 grid((unsigned)(s.tiles_m * s.tiles_n) + (ga.n ? 1u : 0u), (unsigned)s.ksplit);
@@ -3035,15 +3035,41 @@ struct NextFwd {
   float* out_next;
   void* scratch;
   int64_t scratch_bytes;
+  int B_next;
 };
 
-// pointer checks of the four update entry points (nx: the fused pass's further arguments, or NULL)
-int update_ptrs_nonnull(const char* who, const void* bits, const void* d_out, const void* weight, const void* coef, const NextFwd* nx) {
+// The weight clip and the weight average as the table entry points take them (include/nnue_hip.h, "weight clip", "weight
+// average").  {} is "off", what the plain entry points pass and what launches the plain kernels: a bound of 0, and ema == NULL --
+// which launches what the _clip form launches, whatever the rate says.
+struct TableOptions {
+  float weight_clip = 0.0f;
+  float* ema = nullptr;
+  float omd = 0.0f;
+  const float* omd_dev = nullptr;
+};
+
+// The checks the update entry points share, in one order (nx: the fused pass's further arguments, or NULL; momentum_rows: the
+// fused SGD pass's, or NULL).  own(): the optimizer's own checks, which stand behind the pointer checks.
+template <class Own>
+int table_update_args_ok(const char* who, const uint8_t* bits, const float* d_out, const float* weight, const float* coef, int B, int F, int P,
+                         int L1, const void* momentum_rows, const TableOptions& o, const NextFwd* nx, Own own) {
+  NNUE_REQUIRE(o.weight_clip >= 0.0f && o.weight_clip <= 3.4028234e38f, NNUE_E_ARG, "%s: weight_clip = %g must be finite and not negative", who,
+               (double)o.weight_clip);
+  if (o.ema) {  // otherwise the rows must be 16-byte aligned and a rate given by value must lie in (0, 1]
+    NNUE_REQUIRE(o.omd_dev || (o.omd > 0.0f && o.omd <= 1.0f), NNUE_E_ARG, "%s: ema_omd = %g must lie in (0, 1]", who, (double)o.omd);
+    NNUE_REQUIRE(nnue_aligned16(o.ema), NNUE_E_ARG, "%s: the average's rows must be 16-byte aligned", who);
+  }
   NNUE_REQUIRE(bits && d_out && weight && coef && (!nx || (nx->bits_next && nx->sink_next && nx->bias && nx->out_next && nx->scratch)), NNUE_E_ARG,
                "%s: null pointer", who);
-  return NNUE_OK;
-}
-int update_ptrs_aligned(const char* who, const void* bits, const void* d_out, const void* weight, const void* momentum_rows, const NextFwd* nx) {
+  if (const int rc = own()) return rc;
+  if (nx) {
+    NNUE_REQUIRE(nnue_ftm_update_forward_supported(B, nx->B_next, F, P, L1), NNUE_E_SHAPE,
+                 "%s: B=%d B_next=%d F=%d P=%d L1=%d is not a split-K forward over a big table (use the two separate calls)", who, B, nx->B_next, F, P,
+                 L1);
+  } else {  // (Adam's own checks have run these two already, ahead of its table limits: here they are SGD's, and pass again for Adam)
+    NNUE_REQUIRE(shape_ok(B, F, P, L1), NNUE_E_ARG, "%s: B=%d F=%d P=%d L1=%d out of range", who, B, F, P, L1);
+    NNUE_REQUIRE(nnue_ftm_supported(F, P, L1), NNUE_E_SHAPE, "%s: P=%d and L1=%d must be multiples of 4", who, P, L1);
+  }
   NNUE_REQUIRE(nnue_aligned16(bits) && nnue_aligned16(d_out) && nnue_aligned16(weight) &&
                    (!nx || (nnue_aligned16(nx->bits_next) && nnue_aligned16(nx->bias) && nnue_aligned16(nx->out_next) && nnue_aligned16(nx->scratch) &&
                             (!momentum_rows || nnue_aligned16(momentum_rows)))),
@@ -3052,41 +3078,45 @@ int update_ptrs_aligned(const char* who, const void* bits, const void* d_out, co
   return NNUE_OK;
 }
 
-// Shape of the product d_W = A^T d_out whose epilogue applies the update (BwwSgdEpi / BwwAdamEpi): always a bf16-split tile --
-// the in-place epilogues live there -- and never split along K
-int update_product_shape(const char* who, int direct, int L1, int B, Shape* out) {
+// The stand-alone update's launch with the epilogue the options select: `epi`, or ClipEpi{epi, bound} where the clip is on, and
+// WithEma<> around either where there is an average.  The product d_W = A^T d_out whose epilogue applies the update is always a
+// bf16-split tile -- the in-place epilogues live there -- and never split along K.
+template <class ClipEpi, class Epi>
+int update_launch(const char* who, const uint8_t* bits, const float* d_out, int B, int P, int L1, int direct, const Epi& epi, const TableOptions& o,
+                  nnue_stream_t stream) {
   Shape s = plan(direct, L1, B, false, false, true);
   if (!s.bf) s = shape_of(kBf64, direct, L1, B);  // launch-sized product: a 64-row bf16 tile
   NNUE_REQUIRE(s.ksplit == 1, NNUE_E_SHAPE, "%s: the product must not be split along K", who);
-  *out = s;
-  return NNUE_OK;
-}
-
-template <class Epi>
-int update_launch(const char* who, const uint8_t* bits, const float* d_out, int B, int P, int L1, int direct, const Epi& epi, nnue_stream_t stream) {
-  Shape s;
-  if (const int rc = update_product_shape(who, direct, L1, B, &s)) return rc;
-  launch<false, false>(static_cast<hipStream_t>(stream), s, Mat{bits, (unsigned)((size_t)B * P), P, kIntMax, kIntMax},
-                       Mat{d_out, (unsigned)((size_t)B * L1 * 4), L1, kIntMax, kIntMax}, epi, direct, L1, B);
+  auto go = [&](const auto& e) {
+    launch<false, false>(static_cast<hipStream_t>(stream), s, Mat{bits, (unsigned)((size_t)B * P), P, kIntMax, kIntMax},
+                         Mat{d_out, (unsigned)((size_t)B * L1 * 4), L1, kIntMax, kIntMax}, e, direct, L1, B);
+  };
+  with_clip_ema(o.weight_clip > 0.0f, o.ema != nullptr, [&](auto clip, auto ema) {
+    using E = std::conditional_t<decltype(clip)::value, ClipEpi, Epi>;
+    E e{epi};
+    if constexpr (decltype(clip)::value) e.wclip = o.weight_clip;
+    if constexpr (decltype(ema)::value) go(WithEma<E>{e, o.ema, o.omd, o.omd_dev});
+    else go(e);
+  });
   return nnue_launch_status(who);
 }
 
-// What an entry point of the fused pass fills of its arguments: the operands, shapes and the hyper-parameters both optimizers
-// have (Adam: `state_rows` = exp_avg, mom = 0, and its own three fields on top).  slabs, klen, tiles_n, xcd_remap and abl stay
-// zero: update_forward_launch fills them from the forward's plan.
+// What an entry point of the fused pass fills of its arguments: the operands, shapes, the hyper-parameters both optimizers have
+// (Adam: `state_rows` = exp_avg, mom = 0, and its own three fields on top) and the options.  slabs, klen, tiles_n, xcd_remap and
+// abl stay zero: update_forward_launch fills them from the forward's plan.
 template <class Args>
 Args make_upd_fwd(const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight, float* state_rows, const float* coef,
-                  const float* lr_dev, float lr, float mom, float wd, float scale, const uint8_t* bits_next, int B_next) {
+                  const float* lr_dev, float lr, float mom, float wd, float scale, const TableOptions& o, const NextFwd& nx) {
   Args a{};
   a.bits = bits;
-  a.bits_next = bits_next;
+  a.bits_next = nx.bits_next;
   a.d_out = d_out;
   a.weight = weight;
   a.momentum = state_rows;
   a.coef = coef;
   a.lr_dev = lr_dev;
   a.B = B;
-  a.Bn = B_next;
+  a.Bn = nx.B_next;
   a.P = P;
   a.L1 = L1;
   a.direct = (F - 1 < P) ? F - 1 : P;
@@ -3094,12 +3124,17 @@ Args make_upd_fwd(const uint8_t* bits, const float* d_out, int B, int F, int P, 
   a.mom = mom;
   a.wd = wd;
   a.scale = scale;
+  a.wclip = o.weight_clip;
+  a.ema = o.ema;
+  a.omd = o.omd;
+  a.omd_dev = o.omd_dev;
   return a;
 }
 
 // The fused pass's launch: the scratch check, the forward's plan (slabs, slab length, column tiles, XCD remap) into `a`, the kernel
-// of the product's K-tile count, ftm_finish_kernel.  first: first step of an SGD momentum buffer (written, not read).
-template <bool kAdam, bool kClip, bool kEma = false>
+// of the product's K-tile count and of the options in `a`, ftm_finish_kernel.  first: first step of an SGD momentum buffer
+// (written, not read).
+template <bool kAdam>
 int update_forward_launch(const char* who, std::conditional_t<kAdam, UpdFwdAdam, UpdFwd> a, int F, bool first, const NextFwd& nx, nnue_stream_t stream) {
   const Shape s = plan(a.Bn, a.L1, a.direct, true, true, true);
   const int64_t need = (int64_t)s.ksplit * a.Bn * a.L1 * (int64_t)sizeof(float);
@@ -3113,11 +3148,14 @@ int update_forward_launch(const char* who, std::conditional_t<kAdam, UpdFwdAdam,
   const dim3 grid((unsigned)(s.tiles_n * s.ksplit));
   const bool mom = a.momentum != nullptr;
   auto go = [&](auto nk) {
-    constexpr int NK = decltype(nk)::value;
-    if constexpr (kAdam) hipLaunchKernelGGL((ftm_update_forward_kernel<NK, true, false, true, kClip, kEma>), grid, dim3(256), 0, st, a);
-    else if (!mom) hipLaunchKernelGGL((ftm_update_forward_kernel<NK, false, false, false, kClip, kEma>), grid, dim3(256), 0, st, a);
-    else if (first) hipLaunchKernelGGL((ftm_update_forward_kernel<NK, true, true, false, kClip, kEma>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((ftm_update_forward_kernel<NK, true, false, false, kClip, kEma>), grid, dim3(256), 0, st, a);
+    with_clip_ema(a.wclip > 0.0f, a.ema != nullptr, [&](auto clip, auto ema) {
+      constexpr int NK = decltype(nk)::value;
+      constexpr bool kClip = decltype(clip)::value, kEma = decltype(ema)::value;
+      if constexpr (kAdam) hipLaunchKernelGGL((ftm_update_forward_kernel<NK, true, false, true, kClip, kEma>), grid, dim3(256), 0, st, a);
+      else if (!mom) hipLaunchKernelGGL((ftm_update_forward_kernel<NK, false, false, false, kClip, kEma>), grid, dim3(256), 0, st, a);
+      else if (first) hipLaunchKernelGGL((ftm_update_forward_kernel<NK, true, true, false, kClip, kEma>), grid, dim3(256), 0, st, a);
+      else hipLaunchKernelGGL((ftm_update_forward_kernel<NK, true, false, false, kClip, kEma>), grid, dim3(256), 0, st, a);
+    });
   };
   switch ((a.B + 63) / 64) {  // K tiles of the weight-gradient product (nnue_ftm_update_forward_supported: 1, 2, 4, 8 or 16)
     case 1: go(std::integral_constant<int, 1>{}); break;
@@ -3131,64 +3169,33 @@ int update_forward_launch(const char* who, std::conditional_t<kAdam, UpdFwdAdam,
                      nx.bias, a.weight + (size_t)(F - 1) * a.L1, nx.sink_next, a.L1, nx.out_next);
   return nnue_launch_status(who);
 }
-}  // namespace
 
-namespace {
-// The weight clip's bound as the table entry points take it (include/nnue_hip.h, "weight clip"); 0 launches the plain kernels.
-int wclip_ok(const char* who, float weight_clip) {
-  NNUE_REQUIRE(weight_clip >= 0.0f && weight_clip <= 3.4028234e38f, NNUE_E_ARG, "%s: weight_clip = %g must be finite and not negative", who,
-               (double)weight_clip);
-  return NNUE_OK;
-}
-
-// The weight average as the table entry points take it (include/nnue_hip.h, "weight average"): ema == NULL is off and launches
-// what the _clip form launches; otherwise the rows must be 16-byte aligned and a rate given by value must lie in (0, 1].
-int table_ema_ok(const char* who, const float* ema, float omd, const float* omd_dev) {
-  if (!ema) return NNUE_OK;
-  NNUE_REQUIRE(omd_dev || (omd > 0.0f && omd <= 1.0f), NNUE_E_ARG, "%s: ema_omd = %g must lie in (0, 1]", who, (double)omd);
-  NNUE_REQUIRE(nnue_aligned16(ema), NNUE_E_ARG, "%s: the average's rows must be 16-byte aligned", who);
-  return NNUE_OK;
-}
-
-// update_launch with the epilogue `epi`, or -- with an average -- with its WithEma form
-template <class Epi>
-int update_launch_ema(const char* who, const uint8_t* bits, const float* d_out, int B, int P, int L1, int direct, const Epi& epi, float* ema,
-                      float omd, const float* omd_dev, nnue_stream_t stream) {
-  if (ema) return update_launch(who, bits, d_out, B, P, L1, direct, WithEma<Epi>{epi, ema, omd, omd_dev}, stream);
-  return update_launch(who, bits, d_out, B, P, L1, direct, epi, stream);
-}
-
+// nnue_ftm_backward_weight_update (nx == NULL) and nnue_ftm_backward_weight_update_forward, with their _clip and _ema siblings
 int weight_update_sgd(const char* who, const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight,
                       float* momentum_rows, const float* coef, float lr, float momentum, float weight_decay, float grad_scale, int first_step,
-                      float weight_clip, const float* lr_dev, float* ema, float omd, const float* omd_dev, nnue_stream_t stream) {
-  if (const int rc = wclip_ok(who, weight_clip)) return rc;
-  if (const int rc = table_ema_ok(who, ema, omd, omd_dev)) return rc;
-  if (const int rc = update_ptrs_nonnull(who, bits, d_out, weight, coef, nullptr)) return rc;
-  NNUE_REQUIRE(momentum == 0.0f || momentum_rows, NNUE_E_ARG, "%s: momentum %g needs the momentum rows", who, momentum);
-  NNUE_REQUIRE(shape_ok(B, F, P, L1), NNUE_E_ARG, "%s: B=%d F=%d P=%d L1=%d out of range", who, B, F, P, L1);
-  NNUE_REQUIRE(nnue_ftm_supported(F, P, L1), NNUE_E_SHAPE, "%s: P=%d and L1=%d must be multiples of 4", who, P, L1);
-  if (const int rc = update_ptrs_aligned(who, bits, d_out, weight, nullptr, nullptr)) return rc;
+                      const float* lr_dev, const TableOptions& o, const NextFwd* nx, nnue_stream_t stream) {
+  if (const int rc = table_update_args_ok(who, bits, d_out, weight, coef, B, F, P, L1, momentum_rows, o, nx, [&]() -> int {
+        NNUE_REQUIRE(momentum == 0.0f || momentum_rows, NNUE_E_ARG, "%s: momentum %g needs the momentum rows", who, momentum);
+        return NNUE_OK;
+      }))
+    return rc;
+  float* rows = momentum == 0.0f ? nullptr : momentum_rows;
+  if (nx) {
+    const UpdFwd a = make_upd_fwd<UpdFwd>(bits, d_out, B, F, P, L1, weight, rows, coef, lr_dev, lr, momentum, weight_decay, grad_scale, o, *nx);
+    return update_forward_launch<false>(who, a, F, rows && first_step, *nx, stream);
+  }
   const int direct = (F - 1 < P) ? F - 1 : P;
   if (direct <= 0) return NNUE_OK;
-  const BwwSgdEpi epi{weight, momentum == 0.0f ? nullptr : momentum_rows, coef, L1, lr, momentum, weight_decay, grad_scale, first_step, /*xcd_remap=*/1, lr_dev};
-  if (weight_clip > 0.0f) return update_launch_ema(who, bits, d_out, B, P, L1, direct, BwwSgdClipEpi{epi, weight_clip}, ema, omd, omd_dev, stream);
-  return update_launch_ema(who, bits, d_out, B, P, L1, direct, epi, ema, omd, omd_dev, stream);
+  const BwwSgdEpi epi{weight, rows, coef, L1, lr, momentum, weight_decay, grad_scale, first_step, /*xcd_remap=*/1, lr_dev};
+  return update_launch<BwwSgdClipEpi>(who, bits, d_out, B, P, L1, direct, epi, o, stream);
 }
 }  // namespace
-
-extern "C" int nnue_ftm_backward_weight_update_ema(const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight,
-                                                   float* momentum_rows, const float* coef, float lr, float momentum, float weight_decay,
-                                                   float grad_scale, int first_step, float weight_clip, const float* lr_dev, float* ema,
-                                                   float ema_omd, const float* ema_omd_dev, nnue_stream_t stream) {
-  return weight_update_sgd("nnue_ftm_backward_weight_update_ema", bits, d_out, B, F, P, L1, weight, momentum_rows, coef, lr, momentum,
-                           weight_decay, grad_scale, first_step, weight_clip, lr_dev, ema, ema_omd, ema_omd_dev, stream);
-}
 
 extern "C" int nnue_ftm_backward_weight_update(const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight,
                                                float* momentum_rows, const float* coef, float lr, float momentum, float weight_decay,
                                                float grad_scale, int first_step, const float* lr_dev, nnue_stream_t stream) {
   return weight_update_sgd("nnue_ftm_backward_weight_update", bits, d_out, B, F, P, L1, weight, momentum_rows, coef, lr, momentum, weight_decay,
-                           grad_scale, first_step, 0.0f, lr_dev, nullptr, 0.0f, nullptr, stream);
+                           grad_scale, first_step, lr_dev, {}, nullptr, stream);
 }
 
 extern "C" int nnue_ftm_backward_weight_update_clip(const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight,
@@ -3196,7 +3203,15 @@ extern "C" int nnue_ftm_backward_weight_update_clip(const uint8_t* bits, const f
                                                     float grad_scale, int first_step, float weight_clip, const float* lr_dev,
                                                     nnue_stream_t stream) {
   return weight_update_sgd("nnue_ftm_backward_weight_update_clip", bits, d_out, B, F, P, L1, weight, momentum_rows, coef, lr, momentum,
-                           weight_decay, grad_scale, first_step, weight_clip, lr_dev, nullptr, 0.0f, nullptr, stream);
+                           weight_decay, grad_scale, first_step, lr_dev, {weight_clip}, nullptr, stream);
+}
+
+extern "C" int nnue_ftm_backward_weight_update_ema(const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight,
+                                                   float* momentum_rows, const float* coef, float lr, float momentum, float weight_decay,
+                                                   float grad_scale, int first_step, float weight_clip, const float* lr_dev, float* ema,
+                                                   float ema_omd, const float* ema_omd_dev, nnue_stream_t stream) {
+  return weight_update_sgd("nnue_ftm_backward_weight_update_ema", bits, d_out, B, F, P, L1, weight, momentum_rows, coef, lr, momentum,
+                           weight_decay, grad_scale, first_step, lr_dev, {weight_clip, ema, ema_omd, ema_omd_dev}, nullptr, stream);
 }
 
 // nnue_ftm_backward_weight_update + nnue_ftm_forward of the NEXT step's map in one pass over the table (update_forward.h).
@@ -3212,41 +3227,14 @@ extern "C" int nnue_ftm_update_forward_supported(int B, int B_next, int F, int P
   return s.tile == kBf128 && s.ksplit > 1 && s.klen % 128 == 0 && plan(direct, L1, B, false, false, true).tile == kBf128;
 }
 
-namespace {
-int weight_update_forward_sgd(const char* who, const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight,
-                              float* momentum_rows, const float* coef, float lr, float momentum, float weight_decay, float grad_scale,
-                              int first_step, float weight_clip, const float* lr_dev, const NextFwd& nx, int B_next, float* ema, float omd,
-                              const float* omd_dev, nnue_stream_t stream) {
-  const uint8_t* bits_next = nx.bits_next;
-  if (const int rc = wclip_ok(who, weight_clip)) return rc;
-  if (const int rc = table_ema_ok(who, ema, omd, omd_dev)) return rc;
-  if (const int rc = update_ptrs_nonnull(who, bits, d_out, weight, coef, &nx)) return rc;
-  NNUE_REQUIRE(momentum == 0.0f || momentum_rows, NNUE_E_ARG, "%s: momentum %g needs the momentum rows", who, momentum);
-  NNUE_REQUIRE(nnue_ftm_update_forward_supported(B, B_next, F, P, L1), NNUE_E_SHAPE,
-               "%s: B=%d B_next=%d F=%d P=%d L1=%d is not a split-K forward over a big table (use the two separate calls)", who, B, B_next, F, P, L1);
-  if (const int rc = update_ptrs_aligned(who, bits, d_out, weight, momentum_rows, &nx)) return rc;
-  UpdFwd a = make_upd_fwd<UpdFwd>(bits, d_out, B, F, P, L1, weight, momentum == 0.0f ? nullptr : momentum_rows, coef, lr_dev, lr, momentum,
-                                  weight_decay, grad_scale, bits_next, B_next);
-  a.wclip = weight_clip;
-  a.ema = ema;
-  a.omd = omd;
-  a.omd_dev = omd_dev;
-  const bool first = a.momentum && first_step;
-  if (ema) return weight_clip > 0.0f ? update_forward_launch<false, true, true>(who, a, F, first, nx, stream)
-                                     : update_forward_launch<false, false, true>(who, a, F, first, nx, stream);
-  if (weight_clip > 0.0f) return update_forward_launch<false, true>(who, a, F, first, nx, stream);
-  return update_forward_launch<false, false>(who, a, F, first, nx, stream);
-}
-}  // namespace
-
 extern "C" int nnue_ftm_backward_weight_update_forward(const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight,
                                                        float* momentum_rows, const float* coef, float lr, float momentum, float weight_decay,
                                                        float grad_scale, int first_step, const float* lr_dev, const uint8_t* bits_next,
                                                        const float* sink_next, int B_next, const float* bias, float* out_next, void* scratch,
                                                        int64_t scratch_bytes, nnue_stream_t stream) {
-  return weight_update_forward_sgd("nnue_ftm_backward_weight_update_forward", bits, d_out, B, F, P, L1, weight, momentum_rows, coef, lr, momentum,
-                                   weight_decay, grad_scale, first_step, 0.0f, lr_dev,
-                                   NextFwd{bits_next, sink_next, bias, out_next, scratch, scratch_bytes}, B_next, nullptr, 0.0f, nullptr, stream);
+  const NextFwd nx{bits_next, sink_next, bias, out_next, scratch, scratch_bytes, B_next};
+  return weight_update_sgd("nnue_ftm_backward_weight_update_forward", bits, d_out, B, F, P, L1, weight, momentum_rows, coef, lr, momentum,
+                           weight_decay, grad_scale, first_step, lr_dev, {}, &nx, stream);
 }
 
 extern "C" int nnue_ftm_backward_weight_update_forward_clip(const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight,
@@ -3255,9 +3243,9 @@ extern "C" int nnue_ftm_backward_weight_update_forward_clip(const uint8_t* bits,
                                                             const float* lr_dev, const uint8_t* bits_next, const float* sink_next, int B_next,
                                                             const float* bias, float* out_next, void* scratch, int64_t scratch_bytes,
                                                             nnue_stream_t stream) {
-  return weight_update_forward_sgd("nnue_ftm_backward_weight_update_forward_clip", bits, d_out, B, F, P, L1, weight, momentum_rows, coef, lr,
-                                   momentum, weight_decay, grad_scale, first_step, weight_clip, lr_dev,
-                                   NextFwd{bits_next, sink_next, bias, out_next, scratch, scratch_bytes}, B_next, nullptr, 0.0f, nullptr, stream);
+  const NextFwd nx{bits_next, sink_next, bias, out_next, scratch, scratch_bytes, B_next};
+  return weight_update_sgd("nnue_ftm_backward_weight_update_forward_clip", bits, d_out, B, F, P, L1, weight, momentum_rows, coef, lr, momentum,
+                           weight_decay, grad_scale, first_step, lr_dev, {weight_clip}, &nx, stream);
 }
 
 extern "C" int nnue_ftm_backward_weight_update_forward_ema(const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight,
@@ -3266,9 +3254,9 @@ extern "C" int nnue_ftm_backward_weight_update_forward_ema(const uint8_t* bits, 
                                                            const float* lr_dev, const uint8_t* bits_next, const float* sink_next, int B_next,
                                                            const float* bias, float* out_next, void* scratch, int64_t scratch_bytes,
                                                            float* ema, float ema_omd, const float* ema_omd_dev, nnue_stream_t stream) {
-  return weight_update_forward_sgd("nnue_ftm_backward_weight_update_forward_ema", bits, d_out, B, F, P, L1, weight, momentum_rows, coef, lr,
-                                   momentum, weight_decay, grad_scale, first_step, weight_clip, lr_dev,
-                                   NextFwd{bits_next, sink_next, bias, out_next, scratch, scratch_bytes}, B_next, ema, ema_omd, ema_omd_dev, stream);
+  const NextFwd nx{bits_next, sink_next, bias, out_next, scratch, scratch_bytes, B_next};
+  return weight_update_sgd("nnue_ftm_backward_weight_update_forward_ema", bits, d_out, B, F, P, L1, weight, momentum_rows, coef, lr, momentum,
+                           weight_decay, grad_scale, first_step, lr_dev, {weight_clip, ema, ema_omd, ema_omd_dev}, &nx, stream);
 }
 
 // ---- ... and with Adam (train.py:465-470): BwwAdamEpi / the kAdam form of the fused pass -----------------------------------------
@@ -3285,52 +3273,28 @@ int adam_table_args_ok(const char* who, const void* exp_avg_rows, const void* ex
   NNUE_REQUIRE((int64_t)F * L1 * 4 <= 0x7ff00000ll, NNUE_E_SHAPE, "%s: table of %d x %d floats is too large", who, F, L1);
   return NNUE_OK;
 }
-}  // namespace
 
-namespace {
+// nnue_ftm_backward_weight_update_adam (nx == NULL) and nnue_ftm_backward_weight_update_forward_adam, with their siblings
 int weight_update_adam(const char* who, const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight, float* exp_avg_rows,
                        float* exp_avg_sq_rows, const float* coef, const int32_t* step_counter, float lr, float beta1, float beta2, float eps,
-                       float weight_decay, float grad_scale, float weight_clip, const float* lr_dev, float* ema, float omd, const float* omd_dev,
-                       nnue_stream_t stream) {
-  if (const int rc = wclip_ok(who, weight_clip)) return rc;
-  if (const int rc = table_ema_ok(who, ema, omd, omd_dev)) return rc;
-  if (const int rc = update_ptrs_nonnull(who, bits, d_out, weight, coef, nullptr)) return rc;
-  if (const int rc = adam_table_args_ok(who, exp_avg_rows, exp_avg_sq_rows, step_counter, B, F, P, L1, beta1, beta2, eps)) return rc;
-  if (const int rc = update_ptrs_aligned(who, bits, d_out, weight, nullptr, nullptr)) return rc;
+                       float weight_decay, float grad_scale, const float* lr_dev, const TableOptions& o, const NextFwd* nx, nnue_stream_t stream) {
+  if (const int rc = table_update_args_ok(who, bits, d_out, weight, coef, B, F, P, L1, nullptr, o, nx, [&] {
+        return adam_table_args_ok(who, exp_avg_rows, exp_avg_sq_rows, step_counter, B, F, P, L1, beta1, beta2, eps);
+      }))
+    return rc;
+  if (nx) {
+    UpdFwdAdam a = make_upd_fwd<UpdFwdAdam>(bits, d_out, B, F, P, L1, weight, exp_avg_rows, coef, lr_dev, lr, 0.0f, weight_decay, grad_scale, o, *nx);
+    a.exp_avg_sq = exp_avg_sq_rows;
+    a.step_counter = step_counter;
+    a.beta1 = beta1;
+    a.beta2 = beta2;
+    a.eps = eps;
+    return update_forward_launch<true>(who, a, F, false, *nx, stream);
+  }
   const int direct = (F - 1 < P) ? F - 1 : P;
   if (direct <= 0) return NNUE_OK;
   const BwwAdamEpi epi{weight, exp_avg_rows, exp_avg_sq_rows, coef, step_counter, L1, lr, beta1, beta2, eps, weight_decay, grad_scale, /*xcd_remap=*/1, lr_dev};
-  if (weight_clip > 0.0f) return update_launch_ema(who, bits, d_out, B, P, L1, direct, BwwAdamClipEpi{epi, weight_clip}, ema, omd, omd_dev, stream);
-  return update_launch_ema(who, bits, d_out, B, P, L1, direct, epi, ema, omd, omd_dev, stream);
-}
-
-int weight_update_forward_adam(const char* who, const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight,
-                               float* exp_avg_rows, float* exp_avg_sq_rows, const float* coef, const int32_t* step_counter, float lr, float beta1,
-                               float beta2, float eps, float weight_decay, float grad_scale, float weight_clip, const float* lr_dev,
-                               const NextFwd& nx, int B_next, float* ema, float omd, const float* omd_dev, nnue_stream_t stream) {
-  const uint8_t* bits_next = nx.bits_next;
-  if (const int rc = wclip_ok(who, weight_clip)) return rc;
-  if (const int rc = table_ema_ok(who, ema, omd, omd_dev)) return rc;
-  if (const int rc = update_ptrs_nonnull(who, bits, d_out, weight, coef, &nx)) return rc;
-  if (const int rc = adam_table_args_ok(who, exp_avg_rows, exp_avg_sq_rows, step_counter, B, F, P, L1, beta1, beta2, eps)) return rc;
-  NNUE_REQUIRE(nnue_ftm_update_forward_supported(B, B_next, F, P, L1), NNUE_E_SHAPE,
-               "%s: B=%d B_next=%d F=%d P=%d L1=%d is not a split-K forward over a big table (use the two separate calls)", who, B, B_next, F, P, L1);
-  if (const int rc = update_ptrs_aligned(who, bits, d_out, weight, nullptr, &nx)) return rc;
-  UpdFwdAdam a = make_upd_fwd<UpdFwdAdam>(bits, d_out, B, F, P, L1, weight, exp_avg_rows, coef, lr_dev, lr, 0.0f, weight_decay, grad_scale,
-                                          bits_next, B_next);
-  a.exp_avg_sq = exp_avg_sq_rows;
-  a.step_counter = step_counter;
-  a.beta1 = beta1;
-  a.beta2 = beta2;
-  a.eps = eps;
-  a.wclip = weight_clip;
-  a.ema = ema;
-  a.omd = omd;
-  a.omd_dev = omd_dev;
-  if (ema) return weight_clip > 0.0f ? update_forward_launch<true, true, true>(who, a, F, false, nx, stream)
-                                     : update_forward_launch<true, false, true>(who, a, F, false, nx, stream);
-  if (weight_clip > 0.0f) return update_forward_launch<true, true>(who, a, F, false, nx, stream);
-  return update_forward_launch<true, false>(who, a, F, false, nx, stream);
+  return update_launch<BwwAdamClipEpi>(who, bits, d_out, B, P, L1, direct, epi, o, stream);
 }
 }  // namespace
 
@@ -3339,7 +3303,7 @@ extern "C" int nnue_ftm_backward_weight_update_adam(const uint8_t* bits, const f
                                                     const int32_t* step_counter, float lr, float beta1, float beta2, float eps,
                                                     float weight_decay, float grad_scale, const float* lr_dev, nnue_stream_t stream) {
   return weight_update_adam("nnue_ftm_backward_weight_update_adam", bits, d_out, B, F, P, L1, weight, exp_avg_rows, exp_avg_sq_rows, coef,
-                            step_counter, lr, beta1, beta2, eps, weight_decay, grad_scale, 0.0f, lr_dev, nullptr, 0.0f, nullptr, stream);
+                            step_counter, lr, beta1, beta2, eps, weight_decay, grad_scale, lr_dev, {}, nullptr, stream);
 }
 
 extern "C" int nnue_ftm_backward_weight_update_adam_clip(const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight,
@@ -3348,7 +3312,7 @@ extern "C" int nnue_ftm_backward_weight_update_adam_clip(const uint8_t* bits, co
                                                          float weight_decay, float grad_scale, float weight_clip, const float* lr_dev,
                                                          nnue_stream_t stream) {
   return weight_update_adam("nnue_ftm_backward_weight_update_adam_clip", bits, d_out, B, F, P, L1, weight, exp_avg_rows, exp_avg_sq_rows, coef,
-                            step_counter, lr, beta1, beta2, eps, weight_decay, grad_scale, weight_clip, lr_dev, nullptr, 0.0f, nullptr, stream);
+                            step_counter, lr, beta1, beta2, eps, weight_decay, grad_scale, lr_dev, {weight_clip}, nullptr, stream);
 }
 
 extern "C" int nnue_ftm_backward_weight_update_adam_ema(const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight,
@@ -3357,19 +3321,8 @@ extern "C" int nnue_ftm_backward_weight_update_adam_ema(const uint8_t* bits, con
                                                         float weight_decay, float grad_scale, float weight_clip, const float* lr_dev,
                                                         float* ema, float ema_omd, const float* ema_omd_dev, nnue_stream_t stream) {
   return weight_update_adam("nnue_ftm_backward_weight_update_adam_ema", bits, d_out, B, F, P, L1, weight, exp_avg_rows, exp_avg_sq_rows, coef,
-                            step_counter, lr, beta1, beta2, eps, weight_decay, grad_scale, weight_clip, lr_dev, ema, ema_omd, ema_omd_dev, stream);
-}
-
-extern "C" int nnue_ftm_backward_weight_update_forward_adam_ema(const uint8_t* bits, const float* d_out, int B, int F, int P, int L1,
-                                                                float* weight, float* exp_avg_rows, float* exp_avg_sq_rows, const float* coef,
-                                                                const int32_t* step_counter, float lr, float beta1, float beta2, float eps,
-                                                                float weight_decay, float grad_scale, float weight_clip, const float* lr_dev,
-                                                                const uint8_t* bits_next, const float* sink_next, int B_next,
-                                                                const float* bias, float* out_next, void* scratch, int64_t scratch_bytes,
-                                                                float* ema, float ema_omd, const float* ema_omd_dev, nnue_stream_t stream) {
-  return weight_update_forward_adam("nnue_ftm_backward_weight_update_forward_adam_ema", bits, d_out, B, F, P, L1, weight, exp_avg_rows,
-                                    exp_avg_sq_rows, coef, step_counter, lr, beta1, beta2, eps, weight_decay, grad_scale, weight_clip, lr_dev,
-                                    NextFwd{bits_next, sink_next, bias, out_next, scratch, scratch_bytes}, B_next, ema, ema_omd, ema_omd_dev, stream);
+                            step_counter, lr, beta1, beta2, eps, weight_decay, grad_scale, lr_dev, {weight_clip, ema, ema_omd, ema_omd_dev}, nullptr,
+                            stream);
 }
 
 extern "C" int nnue_ftm_backward_weight_update_forward_adam(const uint8_t* bits, const float* d_out, int B, int F, int P, int L1, float* weight,
@@ -3378,9 +3331,9 @@ extern "C" int nnue_ftm_backward_weight_update_forward_adam(const uint8_t* bits,
                                                             float weight_decay, float grad_scale, const float* lr_dev,
                                                             const uint8_t* bits_next, const float* sink_next, int B_next, const float* bias,
                                                             float* out_next, void* scratch, int64_t scratch_bytes, nnue_stream_t stream) {
-  return weight_update_forward_adam("nnue_ftm_backward_weight_update_forward_adam", bits, d_out, B, F, P, L1, weight, exp_avg_rows,
-                                    exp_avg_sq_rows, coef, step_counter, lr, beta1, beta2, eps, weight_decay, grad_scale, 0.0f, lr_dev,
-                                    NextFwd{bits_next, sink_next, bias, out_next, scratch, scratch_bytes}, B_next, nullptr, 0.0f, nullptr, stream);
+  const NextFwd nx{bits_next, sink_next, bias, out_next, scratch, scratch_bytes, B_next};
+  return weight_update_adam("nnue_ftm_backward_weight_update_forward_adam", bits, d_out, B, F, P, L1, weight, exp_avg_rows, exp_avg_sq_rows, coef,
+                            step_counter, lr, beta1, beta2, eps, weight_decay, grad_scale, lr_dev, {}, &nx, stream);
 }
 
 extern "C" int nnue_ftm_backward_weight_update_forward_adam_clip(const uint8_t* bits, const float* d_out, int B, int F, int P, int L1,
@@ -3390,9 +3343,22 @@ extern "C" int nnue_ftm_backward_weight_update_forward_adam_clip(const uint8_t* 
                                                                  const uint8_t* bits_next, const float* sink_next, int B_next,
                                                                  const float* bias, float* out_next, void* scratch, int64_t scratch_bytes,
                                                                  nnue_stream_t stream) {
-  return weight_update_forward_adam("nnue_ftm_backward_weight_update_forward_adam_clip", bits, d_out, B, F, P, L1, weight, exp_avg_rows,
-                                    exp_avg_sq_rows, coef, step_counter, lr, beta1, beta2, eps, weight_decay, grad_scale, weight_clip, lr_dev,
-                                    NextFwd{bits_next, sink_next, bias, out_next, scratch, scratch_bytes}, B_next, nullptr, 0.0f, nullptr, stream);
+  const NextFwd nx{bits_next, sink_next, bias, out_next, scratch, scratch_bytes, B_next};
+  return weight_update_adam("nnue_ftm_backward_weight_update_forward_adam_clip", bits, d_out, B, F, P, L1, weight, exp_avg_rows, exp_avg_sq_rows,
+                            coef, step_counter, lr, beta1, beta2, eps, weight_decay, grad_scale, lr_dev, {weight_clip}, &nx, stream);
+}
+
+extern "C" int nnue_ftm_backward_weight_update_forward_adam_ema(const uint8_t* bits, const float* d_out, int B, int F, int P, int L1,
+                                                                float* weight, float* exp_avg_rows, float* exp_avg_sq_rows, const float* coef,
+                                                                const int32_t* step_counter, float lr, float beta1, float beta2, float eps,
+                                                                float weight_decay, float grad_scale, float weight_clip, const float* lr_dev,
+                                                                const uint8_t* bits_next, const float* sink_next, int B_next,
+                                                                const float* bias, float* out_next, void* scratch, int64_t scratch_bytes,
+                                                                float* ema, float ema_omd, const float* ema_omd_dev, nnue_stream_t stream) {
+  const NextFwd nx{bits_next, sink_next, bias, out_next, scratch, scratch_bytes, B_next};
+  return weight_update_adam("nnue_ftm_backward_weight_update_forward_adam_ema", bits, d_out, B, F, P, L1, weight, exp_avg_rows, exp_avg_sq_rows,
+                            coef, step_counter, lr, beta1, beta2, eps, weight_decay, grad_scale, lr_dev, {weight_clip, ema, ema_omd, ema_omd_dev}, &nx,
+                            stream);
 }
 
 // Which matrix unit a product of this shape runs on (the launch policy above, for reporting: bench.py prices a kernel

@@ -101,7 +101,7 @@ __device__ __forceinline__ float clip_coefficient(float norm, float max_norm) {
 // The weight clip of a flat buffer (include/nnue_hip.h, "weight clip"), by value in the kernel arguments: the bound and up to
 // four half-open element ranges of the buffer (unused ones empty).  The apply kernels take it as their last argument.  The SGD
 // kernels are compiled twice: kClip = false is the kernel without it, instruction for instruction, and what a bound of 0 launches;
-// the Adam kernels branch on the bound (see adam_apply_kernel).
+// the Adam kernel branches on the bound (see adam_apply_ext_kernel).
 struct FlatClip {
   float bound;
   int64_t lo[4], hi[4];
@@ -214,8 +214,35 @@ __global__ __launch_bounds__(256) void sqnorm_stage1_ste(const float* __restrict
   if (threadIdx.x == 0) partial[nb + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-// Every block re-derives the norm from the kNormBlocks partials (4 KiB, L2-resident) in the same
-// fixed order, then streams its share of the update.
+// The norm step of every apply kernel.  Every block re-derives the norm from the norm launch's partials (at most 4 KiB,
+// L2-resident) in the same fixed order -- plus, where given, a producer's sums of squares (unscaled) of the range the norm launch
+// skipped -- before it streams its share of the update.  Returns clip_grad_norm_'s coefficient; the first workgroup leaves the
+// norm in norm_out and the coefficient in coef_out (for the producer that applies [skip_lo, skip_hi) itself) where they are given.
+__device__ __forceinline__ float clip_from_partials(const float* __restrict__ partial, int nparts, const float* __restrict__ ext_partial,
+                                                    int ext_count, float scale, float max_norm, float* __restrict__ norm_out,
+                                                    float* __restrict__ coef_out) {
+  __shared__ double red[4];
+  __shared__ float coef_s;
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < nparts; i += 256) acc += (double)partial[i];
+  if (ext_partial) {
+    const double s2 = (double)scale * (double)scale;
+    for (int i = threadIdx.x; i < ext_count; i += 256) acc += (double)ext_partial[i] * s2;
+  }
+#pragma unroll
+  for (int s = 32; s >= 1; s >>= 1) acc += __shfl_xor(acc, s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const float norm = (float)sqrt((red[0] + red[1]) + (red[2] + red[3]));
+    if (norm_out && blockIdx.x == 0) *norm_out = norm;
+    coef_s = clip_coefficient(norm, max_norm);
+    if (coef_out && blockIdx.x == 0) *coef_out = coef_s;
+  }
+  __syncthreads();
+  return coef_s;
+}
+
 template <bool kClip, bool kEma>
 __global__ __launch_bounds__(256) void sgd_apply_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                         float* __restrict__ m, int64_t count, float lr, float momentum,
@@ -224,8 +251,6 @@ __global__ __launch_bounds__(256) void sgd_apply_kernel(float* __restrict__ p, c
                                                         float* __restrict__ norm_out, const float* __restrict__ ext_partial,
                                                         int ext_count, float* __restrict__ coef_out, int64_t skip_lo, int64_t skip_hi,
                                                         const float* __restrict__ lr_dev, const FlatClip fc, const FlatEma fe) {
-  __shared__ double red[4];
-  __shared__ float coef_s;
   if (lr_dev) lr = lr_dev[0];  // the learning rate as a device scalar: a scheduler changes it without re-capturing the step
   float omd = 0.0f;
   if constexpr (kEma) omd = fe.rate();
@@ -249,24 +274,7 @@ __global__ __launch_bounds__(256) void sgd_apply_kernel(float* __restrict__ p, c
   }
   float clip = 1.0f;
   if (max_norm > 0.0f || norm_out || coef_out) {
-    double acc = 0.0;
-    for (int i = threadIdx.x; i < nparts; i += 256) acc += (double)partial[i];
-    if (ext_partial) {  // a producer's sums of squares (unscaled) of the range the norm launch skipped
-      const double s2 = (double)scale * (double)scale;
-      for (int i = threadIdx.x; i < ext_count; i += 256) acc += (double)ext_partial[i] * s2;
-    }
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) acc += __shfl_xor(acc, s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      const float norm = (float)sqrt((red[0] + red[1]) + (red[2] + red[3]));
-      if (norm_out && blockIdx.x == 0) *norm_out = norm;
-      coef_s = clip_coefficient(norm, max_norm);
-      if (coef_out && blockIdx.x == 0) *coef_out = coef_s;  // for the producer that applies [skip_lo, skip_hi) itself
-    }
-    __syncthreads();
-    clip = coef_s;
+    clip = clip_from_partials(partial, nparts, ext_partial, ext_count, scale, max_norm, norm_out, coef_out);
   }
   const float gs = clip * scale;
 #pragma unroll
@@ -304,8 +312,6 @@ __global__ __launch_bounds__(256) void sgd_apply_vec_kernel(float* __restrict__ 
                                                             float* __restrict__ norm_out, const float* __restrict__ ext_partial, int ext_count,
                                                             float* __restrict__ coef_out, int64_t skip_lo, int64_t skip_hi,
                                                             const float* __restrict__ lr_dev, const FlatClip fc, const FlatEma fe) {
-  __shared__ double red[4];
-  __shared__ float coef_s;
   if (lr_dev) lr = lr_dev[0];
   float omd = 0.0f;
   if constexpr (kEma) omd = fe.rate();
@@ -329,24 +335,7 @@ __global__ __launch_bounds__(256) void sgd_apply_vec_kernel(float* __restrict__ 
   }
   float clip = 1.0f;
   if (max_norm > 0.0f || norm_out || coef_out) {
-    double acc = 0.0;
-    for (int i = threadIdx.x; i < nparts; i += 256) acc += (double)partial[i];
-    if (ext_partial) {
-      const double s2 = (double)scale * (double)scale;
-      for (int i = threadIdx.x; i < ext_count; i += 256) acc += (double)ext_partial[i] * s2;
-    }
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) acc += __shfl_xor(acc, s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      const float norm = (float)sqrt((red[0] + red[1]) + (red[2] + red[3]));
-      if (norm_out && blockIdx.x == 0) *norm_out = norm;
-      coef_s = clip_coefficient(norm, max_norm);
-      if (coef_out && blockIdx.x == 0) *coef_out = coef_s;
-    }
-    __syncthreads();
-    clip = coef_s;
+    clip = clip_from_partials(partial, nparts, ext_partial, ext_count, scale, max_norm, norm_out, coef_out);
   }
   const float gs = clip * scale;
   auto one = [&](float w, float gv, float mv, float& m_new) {
@@ -383,67 +372,27 @@ __global__ __launch_bounds__(256) void sgd_apply_vec_kernel(float* __restrict__ 
 // Adam (torch.optim.Adam defaults: L2 weight decay folded into the gradient, bias-corrected moments, no
 // amsgrad).  The step number lives in device memory (step_counter[0], incremented here by the norm kernel's
 // first thread) so that the launch has no changing host argument and can be replayed from a hipGraph.
+// kSkip (nnue_adam_step_ext): the norm launch skips [lo, hi) of the gradient -- a producer left that range's sums of squares.
+template <bool kSkip>
 __global__ __launch_bounds__(256) void sqnorm_stage1_count(const float* __restrict__ g, int64_t count, float scale,
-                                                           float* __restrict__ partial, int* __restrict__ step_counter) {
+                                                           float* __restrict__ partial, int* __restrict__ step_counter, int64_t lo,
+                                                           int64_t hi) {
   __shared__ float red[4];
   if (blockIdx.x == 0 && threadIdx.x == 0) step_counter[0] += 1;
-  const float v = sqnorm_block_partial(g, count, scale, red, blockIdx.x, gridDim.x);
+  const float v = kSkip ? sqnorm_block_partial_skip(g, count, scale, red, blockIdx.x, gridDim.x, lo, hi)
+                        : sqnorm_block_partial(g, count, scale, red, blockIdx.x, gridDim.x);
   if (threadIdx.x == 0) partial[blockIdx.x] = v;
 }
 
+// The apply launch of nnue_adam_step (kExt = false) and of nnue_adam_step_ext (kExt = true: it adds the producer's partials to the
+// norm, leaves the clip coefficient in coef_out and -- with skip_lo < skip_hi -- does not touch that range, whose producer applies
+// the update itself; without kExt those arguments are not read).
 // The weight clip here is a uniform branch on the descriptor's bound (0: off), not a second instantiation: adam_update leaves its
 // multiply-adds to the compiler's contraction (optim_update.h), and a clamping instantiation of this kernel was compiled with one
 // of them fused that the plain one keeps apart (one ulp) -- with one text both arms share the arithmetic, and it is the
-// arithmetic the kernel had before the clip existed (compared instruction by instruction).  The same in adam_apply_ext_kernel.
-__global__ __launch_bounds__(256) void adam_apply_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                         float* __restrict__ m, float* __restrict__ v, int64_t count,
-                                                         float lr, float beta1, float beta2, float eps, float wd,
-                                                         float max_norm, float scale, const int* __restrict__ step_counter,
-                                                         const float* __restrict__ partial, int nparts,
-                                                         float* __restrict__ norm_out, const float* __restrict__ lr_dev,
-                                                         const FlatClip fc, const FlatEma fe) {
-  __shared__ double red[4];
-  __shared__ float coef_s;
-  if (lr_dev) lr = lr_dev[0];
-  double acc = 0.0;
-  for (int i = threadIdx.x; i < nparts; i += 256) acc += (double)partial[i];
-#pragma unroll
-  for (int s = 32; s >= 1; s >>= 1) acc += __shfl_xor(acc, s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const float norm = (float)sqrt((red[0] + red[1]) + (red[2] + red[3]));
-    if (norm_out && blockIdx.x == 0) *norm_out = norm;
-    coef_s = clip_coefficient(norm, max_norm);
-  }
-  __syncthreads();
-  const float gs = coef_s * scale;
-  const AdamBias bc = adam_bias_correction(lr, beta1, beta2, step_counter[0]);
-  const float omd = fe.e ? fe.rate() : 0.0f;
-  const int64_t stride = (int64_t)gridDim.x * 256;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < count; i += stride) {
-    float mi = m[i], vi = v[i];
-    float wn = adam_update(p[i], g[i], mi, vi, gs, bc, beta1, beta2, eps, wd);
-    if (fc.bound > 0.0f) wn = fc.apply(i, wn);  // (uniform; see the note above adam_apply_kernel)
-    p[i] = wn;
-    m[i] = mi;
-    v[i] = vi;
-    if (fe.e) fe.e[i] = ema_update(fe.e[i], wn, omd);  // (uniform, like the clip: one text, the plain arm's arithmetic unchanged)
-  }
-}
-
-// The two launches of nnue_adam_step_ext: the norm launch skips [lo, hi) of the gradient (a producer left that range's sums of
-// squares), the apply pass adds the producer's partials to the norm, leaves the clip coefficient in coef_out and -- with
-// skip_lo < skip_hi -- does not touch that range (its producer applies the update itself).  Otherwise adam_apply_kernel.
-__global__ __launch_bounds__(256) void sqnorm_stage1_count_skip(const float* __restrict__ g, int64_t count, float scale,
-                                                                float* __restrict__ partial, int* __restrict__ step_counter, int64_t lo,
-                                                                int64_t hi) {
-  __shared__ float red[4];
-  if (blockIdx.x == 0 && threadIdx.x == 0) step_counter[0] += 1;
-  const float v = sqnorm_block_partial_skip(g, count, scale, red, blockIdx.x, gridDim.x, lo, hi);
-  if (threadIdx.x == 0) partial[blockIdx.x] = v;
-}
-
+// arithmetic the kernel had before the clip existed (compared instruction by instruction).  The average is a uniform branch on
+// its pointer for the same reason.
+template <bool kExt>
 __global__ __launch_bounds__(256) void adam_apply_ext_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                              float* __restrict__ v, int64_t count, float lr, float beta1, float beta2,
                                                              float eps, float wd, float max_norm, float scale,
@@ -452,36 +401,18 @@ __global__ __launch_bounds__(256) void adam_apply_ext_kernel(float* __restrict__
                                                              const float* __restrict__ ext_partial, int ext_count,
                                                              float* __restrict__ coef_out, int64_t skip_lo, int64_t skip_hi,
                                                              const float* __restrict__ lr_dev, const FlatClip fc, const FlatEma fe) {
-  __shared__ double red[4];
-  __shared__ float coef_s;
   if (lr_dev) lr = lr_dev[0];
-  double acc = 0.0;
-  for (int i = threadIdx.x; i < nparts; i += 256) acc += (double)partial[i];
-  if (ext_partial) {  // a producer's sums of squares (unscaled) of the range the norm launch skipped
-    const double s2 = (double)scale * (double)scale;
-    for (int i = threadIdx.x; i < ext_count; i += 256) acc += (double)ext_partial[i] * s2;
-  }
-#pragma unroll
-  for (int s = 32; s >= 1; s >>= 1) acc += __shfl_xor(acc, s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const float norm = (float)sqrt((red[0] + red[1]) + (red[2] + red[3]));
-    if (norm_out && blockIdx.x == 0) *norm_out = norm;
-    coef_s = clip_coefficient(norm, max_norm);
-    if (coef_out && blockIdx.x == 0) *coef_out = coef_s;  // for the producer that applies [skip_lo, skip_hi) itself
-  }
-  __syncthreads();
-  const float gs = coef_s * scale;
+  const float gs = clip_from_partials(partial, nparts, kExt ? ext_partial : nullptr, kExt ? ext_count : 0, scale, max_norm, norm_out,
+                                      kExt ? coef_out : nullptr) * scale;
   const AdamBias bc = adam_bias_correction(lr, beta1, beta2, step_counter[0]);
   const float omd = fe.e ? fe.rate() : 0.0f;
   const int64_t stride = (int64_t)gridDim.x * 256;
-  const int64_t hole = skip_hi - skip_lo, live = count - hole;  // hole 0: everything is updated here
+  const int64_t hole = kExt ? skip_hi - skip_lo : 0, live = count - hole;  // hole 0: everything is updated here
   for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < live; j += stride) {
-    const int64_t i = j < skip_lo ? j : j + hole;
+    const int64_t i = (!kExt || j < skip_lo) ? j : j + hole;
     float mi = m[i], vi = v[i];
     float wn = adam_update(p[i], g[i], mi, vi, gs, bc, beta1, beta2, eps, wd);
-    if (fc.bound > 0.0f) wn = fc.apply(i, wn);  // (uniform; see the note above adam_apply_kernel)
+    if (fc.bound > 0.0f) wn = fc.apply(i, wn);  // (uniform; see the note above)
     p[i] = wn;
     m[i] = mi;
     v[i] = vi;
@@ -761,28 +692,12 @@ __device__ __forceinline__ float multi_update(const MultiSeg& S, const MultiHype
 // Stage 2.  The first unit is requested before the norm is re-derived (both are first touches after the kernel boundary).
 template <bool kAdam, class Args>
 __global__ __launch_bounds__(256) void multi_apply_kernel(const Args A) {
-  __shared__ double red[4];
-  __shared__ float coef_s;
   int u = blockIdx.x;
   int s = multi_find(A, u, true);
   MultiUnit<kAdam> U;
   U.load(A.seg[s], u - A.seg[s].unit0, A.seg[s].m && (kAdam || !A.seg[s].first));
   float clip = 1.0f;
-  if (A.need_norm) {
-    double acc = 0.0;
-    for (int i = threadIdx.x; i < A.nparts; i += 256) acc += (double)A.partial[i];
-#pragma unroll
-    for (int k = 32; k >= 1; k >>= 1) acc += __shfl_xor(acc, k);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      const float norm = (float)sqrt((red[0] + red[1]) + (red[2] + red[3]));
-      if (A.norm_out && blockIdx.x == 0) *A.norm_out = norm;
-      coef_s = clip_coefficient(norm, A.max_norm);
-    }
-    __syncthreads();
-    clip = coef_s;
-  }
+  if (A.need_norm) clip = clip_from_partials(A.partial, A.nparts, nullptr, 0, 1.0f, A.max_norm, A.norm_out, nullptr);
   int hs = s;
   MultiHyper h = multi_hyper<kAdam>(A, s);
   while (true) {
@@ -830,96 +745,6 @@ __global__ __launch_bounds__(256) void multi_apply_kernel(const Args A) {
 
 }  // namespace
 
-namespace {
-
-// The flat entry points' weight clip, checked and packed for the kernels (include/nnue_hip.h, "weight clip"): `ranges` holds
-// n_ranges pairs (lo, hi) of element indices.  *on: a kernel with the clamp is to be launched (a bound of 0 or no range with
-// an element in it: the plain kernel).  *by4: every boundary is a multiple of 4 (what the float4 kernel needs).
-int flat_clip_of(const char* who, float bound, const int64_t* ranges, int n_ranges, int64_t count, FlatClip* fc, bool* on, bool* by4) {
-  *fc = FlatClip{};
-  *on = false;
-  *by4 = true;
-  NNUE_REQUIRE(bound >= 0.0f && bound <= 3.4028234e38f, NNUE_E_ARG, "%s: weight_clip = %g must be finite and not negative", who, (double)bound);
-  NNUE_REQUIRE(n_ranges >= 0 && n_ranges <= 4 && (n_ranges == 0 || ranges), NNUE_E_ARG, "%s: the weight clip takes 0 .. 4 ranges, got %d", who,
-               n_ranges);
-  fc->bound = bound;
-  for (int r = 0; r < n_ranges; ++r) {
-    const int64_t lo = ranges[2 * r], hi = ranges[2 * r + 1];
-    NNUE_REQUIRE(lo >= 0 && lo <= hi && hi <= count, NNUE_E_ARG, "%s: clip range %d = [%lld, %lld) does not lie in [0, %lld]", who, r,
-                 (long long)lo, (long long)hi, (long long)count);
-    fc->lo[r] = lo;
-    fc->hi[r] = hi;
-    if (lo < hi && bound > 0.0f) *on = true;
-    if (lo < hi && (lo % 4 != 0 || hi % 4 != 0)) *by4 = false;
-  }
-  return NNUE_OK;
-}
-
-// The flat entry points' weight average, checked and packed (include/nnue_hip.h, "weight average").  ema == NULL is "off": the
-// kernel's plain arm / instantiation, whatever the rate says.  Otherwise the rate given by value must lie in (0, 1]; a device
-// scalar replaces it unseen, as lr_dev replaces lr.
-int flat_ema_of(const char* who, float* ema, float omd, const float* omd_dev, FlatEma* fe) {
-  *fe = FlatEma{nullptr, 0.0f, nullptr};
-  if (!ema) return NNUE_OK;
-  NNUE_REQUIRE(omd_dev || (omd > 0.0f && omd <= 1.0f), NNUE_E_ARG, "%s: ema_omd = %g must lie in (0, 1]", who, (double)omd);
-  *fe = FlatEma{ema, omd, omd_dev};
-  return NNUE_OK;
-}
-
-int adam_step_impl(const char* who, float* params, float* grads, float* exp_avg, float* exp_avg_sq, int32_t* step_counter, int64_t count,
-                   float lr, float beta1, float beta2, float eps, float weight_decay, float max_norm, float grad_scale, float* norm_out,
-                   void* scratch, int64_t scratch_bytes, const float* lr_dev, float weight_clip, const int64_t* clip_ranges, int n_ranges,
-                   float* ema, float ema_omd, const float* ema_omd_dev, nnue_stream_t stream) {
-  NNUE_REQUIRE(params && grads && exp_avg && exp_avg_sq && step_counter && scratch, NNUE_E_ARG, "%s: null pointer", who);
-  NNUE_REQUIRE(count > 0, NNUE_E_ARG, "%s: count must be positive", who);
-  NNUE_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps > 0.f, NNUE_E_ARG,
-               "%s: betas must be in [0,1) and eps > 0", who);
-  NNUE_REQUIRE(scratch_bytes >= nnue_sgd_scratch(count), NNUE_E_SCRATCH, "%s: scratch %lld < %lld bytes", who,
-               (long long)scratch_bytes, (long long)nnue_sgd_scratch(count));
-  FlatClip fc;
-  bool clip_on, by4;
-  if (const int rc = flat_clip_of(who, weight_clip, clip_ranges, n_ranges, count, &fc, &clip_on, &by4)) return rc;
-  FlatEma fe;
-  if (const int rc = flat_ema_of(who, ema, ema_omd, ema_omd_dev, &fe)) return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  float* partial = static_cast<float*>(scratch);
-  hipLaunchKernelGGL(sqnorm_stage1_count, dim3(kNormBlocks), dim3(256), 0, s, grads, count, grad_scale, partial, step_counter);
-  int blocks = (int)((count + 1023) / 1024);
-  if (blocks > 2048) blocks = 2048;
-  if (!clip_on) fc = FlatClip{};  // bound 0: the kernel's plain arm
-  hipLaunchKernelGGL(adam_apply_kernel, dim3(blocks), dim3(256), 0, s, params, grads, exp_avg, exp_avg_sq, count, lr, beta1, beta2, eps,
-                     weight_decay, max_norm, grad_scale, step_counter, partial, kNormBlocks, norm_out, lr_dev, fc, fe);
-  return nnue_launch_status(who);
-}
-
-}  // namespace
-
-extern "C" int nnue_adam_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int32_t* step_counter, int64_t count,
-                              float lr, float beta1, float beta2, float eps, float weight_decay, float max_norm, float grad_scale,
-                              float* norm_out, void* scratch, int64_t scratch_bytes, const float* lr_dev, nnue_stream_t stream) {
-  return adam_step_impl("nnue_adam_step", params, grads, exp_avg, exp_avg_sq, step_counter, count, lr, beta1, beta2, eps, weight_decay, max_norm,
-                        grad_scale, norm_out, scratch, scratch_bytes, lr_dev, 0.0f, nullptr, 0, nullptr, 0.0f, nullptr, stream);
-}
-
-extern "C" int nnue_adam_step_clip(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int32_t* step_counter, int64_t count,
-                                   float lr, float beta1, float beta2, float eps, float weight_decay, float max_norm, float grad_scale,
-                                   float* norm_out, void* scratch, int64_t scratch_bytes, const float* lr_dev, float weight_clip,
-                                   const int64_t* clip_ranges, int n_clip_ranges, nnue_stream_t stream) {
-  return adam_step_impl("nnue_adam_step_clip", params, grads, exp_avg, exp_avg_sq, step_counter, count, lr, beta1, beta2, eps, weight_decay,
-                        max_norm, grad_scale, norm_out, scratch, scratch_bytes, lr_dev, weight_clip, clip_ranges, n_clip_ranges, nullptr, 0.0f,
-                        nullptr, stream);
-}
-
-extern "C" int nnue_adam_step_ema(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int32_t* step_counter, int64_t count,
-                                  float lr, float beta1, float beta2, float eps, float weight_decay, float max_norm, float grad_scale,
-                                  float* norm_out, void* scratch, int64_t scratch_bytes, const float* lr_dev, float weight_clip,
-                                  const int64_t* clip_ranges, int n_clip_ranges, float* ema, float ema_omd, const float* ema_omd_dev,
-                                  nnue_stream_t stream) {
-  return adam_step_impl("nnue_adam_step_ema", params, grads, exp_avg, exp_avg_sq, step_counter, count, lr, beta1, beta2, eps, weight_decay,
-                        max_norm, grad_scale, norm_out, scratch, scratch_bytes, lr_dev, weight_clip, clip_ranges, n_clip_ranges, ema, ema_omd,
-                        ema_omd_dev, stream);
-}
-
 extern "C" int nnue_cross_entropy(const float* logits, const int64_t* labels, int B, int C, float grad_scale,
                                   float* sample_loss, float* loss, float* d_logits, nnue_stream_t stream) {
   NNUE_REQUIRE(logits && labels && sample_loss && loss, NNUE_E_ARG, "nnue_cross_entropy: null pointer");
@@ -947,40 +772,115 @@ extern "C" int nnue_sqnorm_partials(const float* grads, int64_t count, float* pa
   return nnue_launch_status("nnue_sqnorm_partials");
 }
 
+// ---- the flat entry points: nnue_sgd_step, nnue_adam_step, nnue_adam_step_ext and their _clip and _ema siblings ----
 namespace {
+
+// The weight clip and the weight average as the caller of a flat entry point gave them (include/nnue_hip.h, "weight clip",
+// "weight average"): clip_ranges holds n_ranges pairs (lo, hi) of element indices.  {} is "off", what the plain entry points pass;
+// the _clip ones fill the first three fields, the _ema ones all six.
+struct FlatOptions {
+  float weight_clip = 0.0f;
+  const int64_t* clip_ranges = nullptr;
+  int n_ranges = 0;
+  float* ema = nullptr;
+  float ema_omd = 0.0f;
+  const float* ema_omd_dev = nullptr;
+};
+
+// ... and as the kernels take them.  clip_on: a kernel with the clamp is to be launched (a bound of 0 or no range with an element
+// in it: the plain kernel, and fc stays empty -- the Adam kernel's plain arm).  by4: every boundary is a multiple of 4 (what the
+// float4 kernel needs).  ema == NULL is "off", whatever the rate says: fe.e is NULL, the kernel's plain arm / instantiation;
+// otherwise the rate given by value must lie in (0, 1], and a device scalar replaces it unseen, as lr_dev replaces lr.
+struct FlatPacked {
+  FlatClip fc;
+  FlatEma fe;
+  bool clip_on, by4;
+};
+
+int flat_options_of(const char* who, const FlatOptions& o, int64_t count, FlatPacked* out) {
+  *out = FlatPacked{FlatClip{}, FlatEma{nullptr, 0.0f, nullptr}, false, true};
+  NNUE_REQUIRE(o.weight_clip >= 0.0f && o.weight_clip <= 3.4028234e38f, NNUE_E_ARG, "%s: weight_clip = %g must be finite and not negative", who,
+               (double)o.weight_clip);
+  NNUE_REQUIRE(o.n_ranges >= 0 && o.n_ranges <= 4 && (o.n_ranges == 0 || o.clip_ranges), NNUE_E_ARG,
+               "%s: the weight clip takes 0 .. 4 ranges, got %d", who, o.n_ranges);
+  FlatClip fc{};
+  fc.bound = o.weight_clip;
+  for (int r = 0; r < o.n_ranges; ++r) {
+    const int64_t lo = o.clip_ranges[2 * r], hi = o.clip_ranges[2 * r + 1];
+    NNUE_REQUIRE(lo >= 0 && lo <= hi && hi <= count, NNUE_E_ARG, "%s: clip range %d = [%lld, %lld) does not lie in [0, %lld]", who, r,
+                 (long long)lo, (long long)hi, (long long)count);
+    fc.lo[r] = lo;
+    fc.hi[r] = hi;
+    if (lo < hi && o.weight_clip > 0.0f) out->clip_on = true;
+    if (lo < hi && (lo % 4 != 0 || hi % 4 != 0)) out->by4 = false;
+  }
+  if (out->clip_on) out->fc = fc;
+  if (o.ema) {
+    NNUE_REQUIRE(o.ema_omd_dev || (o.ema_omd > 0.0f && o.ema_omd <= 1.0f), NNUE_E_ARG, "%s: ema_omd = %g must lie in (0, 1]", who,
+                 (double)o.ema_omd);
+    out->fe = FlatEma{o.ema, o.ema_omd, o.ema_omd_dev};
+  }
+  return NNUE_OK;
+}
+
+// A producer's share of a flat step: its sums of squares `partial` of grads[lo, hi), which the norm launch then skips, and --
+// with applied_elsewhere -- the update of that range, for which the apply launch leaves the clip coefficient in coef_out.  The
+// first six fields are the entry point's arguments ({}: no producer); ext_range_of checks them, empties the range where there
+// are no partials and fills the rest: the hole [skip_lo, skip_hi) of the apply launch and the elements it updates.
+struct ExtRange {
+  const float* partial;
+  int count;
+  int64_t lo, hi;
+  float* coef_out;
+  int applied_elsewhere;
+  int64_t skip_lo, skip_hi, live;
+};
+
+int ext_range_of(const char* who, int64_t count, ExtRange* x) {
+  NNUE_REQUIRE(!x->applied_elsewhere || (x->partial && x->coef_out), NNUE_E_ARG,
+               "%s: ext_applied_elsewhere needs the producer's partials and coef_out", who);
+  if (x->partial) {
+    NNUE_REQUIRE(x->count > 0 && x->count <= 65536 && x->lo >= 0 && x->lo < x->hi && x->hi <= count && x->lo % 4 == 0 &&
+                     (x->hi % 4 == 0 || x->hi == count),
+                 NNUE_E_ARG, "%s: producer partials need 0 < count <= 65536 and a range [lo, hi) of multiples of 4 inside grads", who);
+  } else {
+    x->lo = x->hi = 0;
+    x->count = 0;
+  }
+  x->skip_lo = x->applied_elsewhere ? x->lo : 0;
+  x->skip_hi = x->applied_elsewhere ? x->hi : 0;
+  x->live = count - (x->skip_hi - x->skip_lo);
+  return NNUE_OK;
+}
+
+// norm workgroups: 16 floats per thread while that still leaves fewer than kNormBlocks (a small model's apply kernel
+// then re-derives the norm from a few hundred partials instead of 1024)
+int norm_blocks(int64_t count) {
+  const int64_t nb = (count + 4095) / 4096;
+  return nb < 64 ? 64 : (nb > kNormBlocks ? kNormBlocks : (int)nb);
+}
+// apply workgroups: up to four elements per thread before the grid is capped
+int apply_blocks(int64_t live) {
+  const int64_t blocks = (live + 1023) / 1024;
+  return blocks < 1 ? 1 : (blocks > 2048 ? 2048 : (int)blocks);
+}
+
 int sgd_step_impl(const char* who, float* params, float* grads, float* momentum_buf, int64_t count, float lr, float momentum,
-                  float weight_decay, float max_norm, float grad_scale, int first_step, float* norm_out,
-                  void* scratch, int64_t scratch_bytes, const float* ste_partial, int ste_chunks, int ste_fps,
-                  float* ste_d_thr, float* ste_d_weight, const float* ext_partial, int ext_count, int64_t ext_lo,
-                  int64_t ext_hi, float* coef_out, int ext_applied_elsewhere, const float* lr_dev, float weight_clip,
-                  const int64_t* clip_ranges, int n_ranges, float* ema, float ema_omd, const float* ema_omd_dev, nnue_stream_t stream) {
+                  float weight_decay, float max_norm, float grad_scale, int first_step, float* norm_out, void* scratch,
+                  int64_t scratch_bytes, const float* ste_partial, int ste_chunks, int ste_fps, float* ste_d_thr, float* ste_d_weight,
+                  ExtRange x, const float* lr_dev, const FlatOptions& opts, nnue_stream_t stream) {
   NNUE_REQUIRE(params && grads && scratch, NNUE_E_ARG, "%s: null pointer", who);
   NNUE_REQUIRE(count > 0, NNUE_E_ARG, "%s: count must be positive", who);
   NNUE_REQUIRE(momentum == 0.0f || momentum_buf, NNUE_E_ARG, "%s: momentum %g needs a momentum buffer", who, momentum);
   NNUE_REQUIRE(scratch_bytes >= nnue_sgd_scratch(count), NNUE_E_SCRATCH, "%s: scratch %lld < %lld bytes", who,
                (long long)scratch_bytes, (long long)nnue_sgd_scratch(count));
-  FlatClip fc;
-  bool clip_on, by4;
-  if (const int rc = flat_clip_of(who, weight_clip, clip_ranges, n_ranges, count, &fc, &clip_on, &by4)) return rc;
-  FlatEma fe;
-  if (const int rc = flat_ema_of(who, ema, ema_omd, ema_omd_dev, &fe)) return rc;
+  FlatPacked f;
+  if (const int rc = flat_options_of(who, opts, count, &f)) return rc;
+  if (const int rc = ext_range_of(who, count, &x)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   float* partial = static_cast<float*>(scratch);
-  // norm workgroups: 16 floats per thread while that still leaves fewer than kNormBlocks (a small model's apply kernel
-  // then re-derives the norm from a few hundred partials instead of 1024)
-  int nb = (int)((count + 4095) / 4096);
-  nb = nb < 64 ? 64 : (nb > kNormBlocks ? kNormBlocks : nb);
+  const int nb = norm_blocks(count);
   int nparts = nb;
-  NNUE_REQUIRE(!ext_applied_elsewhere || (ext_partial && coef_out), NNUE_E_ARG,
-               "%s: ext_applied_elsewhere needs the producer's partials and coef_out", who);
-  if (ext_partial) {
-    NNUE_REQUIRE(ext_count > 0 && ext_count <= 65536 && ext_lo >= 0 && ext_lo < ext_hi && ext_hi <= count && ext_lo % 4 == 0 &&
-                     (ext_hi % 4 == 0 || ext_hi == count),
-                 NNUE_E_ARG, "%s: producer partials need 0 < count <= 65536 and a range [lo, hi) of multiples of 4 inside grads", who);
-  } else {
-    ext_lo = ext_hi = 0;
-    ext_count = 0;
-  }
   if (ste_partial) {
     // the deferred sums own the first `skip` elements of grads: [d_thr | d_weight] in either order, nothing else
     NNUE_REQUIRE(ste_d_thr && ste_d_weight && ste_chunks > 0 && ste_fps > 0 && ste_fps * 28 <= 4 * kSteRideBlocks, NNUE_E_ARG,
@@ -990,86 +890,58 @@ int sgd_step_impl(const char* who, float* params, float* grads, float* momentum_
     const float* hi_w = ste_d_weight + (size_t)ste_fps * 27;
     const float* hi = hi_t > hi_w ? hi_t : hi_w;
     const int64_t skip = nnue_round_up(hi - grads, 4);
-    NNUE_REQUIRE((!ext_partial || ext_lo >= skip) && lo == grads && skip <= count && skip <= nnue_round_up(ste_fps, 4) + nnue_round_up((int64_t)ste_fps * 27, 4) + 8, NNUE_E_ARG,
+    NNUE_REQUIRE((!x.partial || x.lo >= skip) && lo == grads && skip <= count && skip <= nnue_round_up(ste_fps, 4) + nnue_round_up((int64_t)ste_fps * 27, 4) + 8, NNUE_E_ARG,
                  "%s: deferred STE outputs must be the first elements of grads", who);
     const int s2_blocks = (ste_fps * 28 + 3) / 4;
     // padding between / after the two outputs is never written by the sums: it enters neither the norm nor is it read
     // before the update multiplies it -- keep it zero (the flat gradient buffer's padding is zero-initialised)
     hipLaunchKernelGGL(sqnorm_stage1_ste, dim3(nb + s2_blocks), dim3(256), 0, s, grads, count, grad_scale, partial, ste_partial,
-                       ste_chunks, ste_fps, ste_d_thr, ste_d_weight, s2_blocks, skip, ext_lo, ext_hi, nb);
+                       ste_chunks, ste_fps, ste_d_thr, ste_d_weight, s2_blocks, skip, x.lo, x.hi, nb);
     nparts = nb + s2_blocks;
-  } else if (max_norm > 0.0f || norm_out || coef_out) {
-    hipLaunchKernelGGL(sqnorm_stage1, dim3(nb), dim3(256), 0, s, grads, count, grad_scale, partial, ext_lo, ext_hi);
+  } else if (max_norm > 0.0f || norm_out || x.coef_out) {
+    hipLaunchKernelGGL(sqnorm_stage1, dim3(nb), dim3(256), 0, s, grads, count, grad_scale, partial, x.lo, x.hi);
   }
-  const int64_t live = ext_applied_elsewhere ? count - (ext_hi - ext_lo) : count;
-  int blocks = (int)((live + 1023) / 1024);
-  blocks = blocks < 1 ? 1 : blocks;
-  if (blocks > 2048) blocks = 2048;
-  const int64_t skip_lo = ext_applied_elsewhere ? ext_lo : 0, skip_hi = ext_applied_elsewhere ? ext_hi : 0;
   float* mom = momentum == 0.0f ? nullptr : momentum_buf;
   static const char* novec = std::getenv("NNUE_SGD_SCALAR");
-  const bool vec = !(novec && novec[0] == '1') && live <= (16ll << 20) && count % 4 == 0 && skip_lo % 4 == 0 && skip_hi % 4 == 0 &&
-                   nnue_aligned16(params) && nnue_aligned16(grads) && (!mom || nnue_aligned16(mom)) && (!clip_on || by4) &&
-                   (!fe.e || nnue_aligned16(fe.e));
-  auto go = [&](auto kernel, int grid) {  // (the plain and the clamping kernel of a form take the same arguments)
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, s, params, grads, mom, count, lr, momentum, weight_decay, max_norm, grad_scale,
-                       first_step, partial, nparts, norm_out, ext_partial, ext_count, coef_out, skip_lo, skip_hi, lr_dev, fc, fe);
-  };
-  if (vec) {
-    int vb = (int)((live / 4 + 511) / 512);  // two float4 passes per thread
-    vb = vb < 1 ? 1 : (vb > 2048 ? 2048 : vb);
-    if (fe.e) clip_on ? go(sgd_apply_vec_kernel<true, true>, vb) : go(sgd_apply_vec_kernel<false, true>, vb);
-    else if (clip_on) go(sgd_apply_vec_kernel<true, false>, vb);
-    else go(sgd_apply_vec_kernel<false, false>, vb);
+  const bool vec = !(novec && novec[0] == '1') && x.live <= (16ll << 20) && count % 4 == 0 && x.skip_lo % 4 == 0 && x.skip_hi % 4 == 0 &&
+                   nnue_aligned16(params) && nnue_aligned16(grads) && (!mom || nnue_aligned16(mom)) && (!f.clip_on || f.by4) &&
+                   (!f.fe.e || nnue_aligned16(f.fe.e));
+  const int64_t vb = (x.live / 4 + 511) / 512;  // the float4 kernel: two passes per thread
+  const int vec_blocks = vb < 1 ? 1 : (vb > 2048 ? 2048 : (int)vb);
+  return with_clip_ema(f.clip_on, f.fe.e != nullptr, [&](auto clip, auto ema) {
+    constexpr bool kClip = decltype(clip)::value, kEma = decltype(ema)::value;
+    auto go = [&](auto kernel, int grid) {  // (the two forms take the same arguments)
+      hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, s, params, grads, mom, count, lr, momentum, weight_decay, max_norm, grad_scale,
+                         first_step, partial, nparts, norm_out, x.partial, x.count, x.coef_out, x.skip_lo, x.skip_hi, lr_dev, f.fc, f.fe);
+    };
+    if (vec) go(sgd_apply_vec_kernel<kClip, kEma>, vec_blocks);
+    else go(sgd_apply_kernel<kClip, kEma>, apply_blocks(x.live));
     return nnue_launch_status(who);
-  }
-  if (fe.e) clip_on ? go(sgd_apply_kernel<true, true>, blocks) : go(sgd_apply_kernel<false, true>, blocks);
-  else if (clip_on) go(sgd_apply_kernel<true, false>, blocks);
-  else go(sgd_apply_kernel<false, false>, blocks);
-  return nnue_launch_status(who);
+  });
 }
 
-int adam_step_ext_impl(const char* who, float* params, float* grads, float* exp_avg, float* exp_avg_sq, int32_t* step_counter, int64_t count,
-                       float lr, float beta1, float beta2, float eps, float weight_decay, float max_norm, float grad_scale,
-                       float* norm_out, void* scratch, int64_t scratch_bytes, const float* ext_partial, int ext_count,
-                       int64_t ext_lo, int64_t ext_hi, float* coef_out, int ext_applied_elsewhere, const float* lr_dev,
-                       float weight_clip, const int64_t* clip_ranges, int n_ranges, float* ema, float ema_omd, const float* ema_omd_dev,
-                       nnue_stream_t stream) {
+// nnue_adam_step (kExt = false: x is {}, and the norm launch keeps the kNormBlocks workgroups it always had) and nnue_adam_step_ext.
+template <bool kExt>
+int adam_step_impl(const char* who, float* params, float* grads, float* exp_avg, float* exp_avg_sq, int32_t* step_counter, int64_t count,
+                   float lr, float beta1, float beta2, float eps, float weight_decay, float max_norm, float grad_scale, float* norm_out,
+                   void* scratch, int64_t scratch_bytes, ExtRange x, const float* lr_dev, const FlatOptions& opts, nnue_stream_t stream) {
   NNUE_REQUIRE(params && grads && exp_avg && exp_avg_sq && step_counter && scratch, NNUE_E_ARG, "%s: null pointer", who);
   NNUE_REQUIRE(count > 0, NNUE_E_ARG, "%s: count must be positive", who);
   NNUE_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps > 0.f, NNUE_E_ARG,
                "%s: betas must be in [0,1) and eps > 0", who);
   NNUE_REQUIRE(scratch_bytes >= nnue_sgd_scratch(count), NNUE_E_SCRATCH, "%s: scratch %lld < %lld bytes", who,
                (long long)scratch_bytes, (long long)nnue_sgd_scratch(count));
-  NNUE_REQUIRE(!ext_applied_elsewhere || (ext_partial && coef_out), NNUE_E_ARG,
-               "%s: ext_applied_elsewhere needs the producer's partials and coef_out", who);
-  if (ext_partial) {
-    NNUE_REQUIRE(ext_count > 0 && ext_count <= 65536 && ext_lo >= 0 && ext_lo < ext_hi && ext_hi <= count && ext_lo % 4 == 0 &&
-                     (ext_hi % 4 == 0 || ext_hi == count),
-                 NNUE_E_ARG, "%s: producer partials need 0 < count <= 65536 and a range [lo, hi) of multiples of 4 inside grads", who);
-  } else {
-    ext_lo = ext_hi = 0;
-    ext_count = 0;
-  }
-  FlatClip fc;
-  bool clip_on, by4;
-  if (const int rc = flat_clip_of(who, weight_clip, clip_ranges, n_ranges, count, &fc, &clip_on, &by4)) return rc;
-  FlatEma fe;
-  if (const int rc = flat_ema_of(who, ema, ema_omd, ema_omd_dev, &fe)) return rc;
+  if (const int rc = ext_range_of(who, count, &x)) return rc;
+  FlatPacked f;
+  if (const int rc = flat_options_of(who, opts, count, &f)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   float* partial = static_cast<float*>(scratch);
-  int nb = (int)((count + 4095) / 4096);  // as nnue_sgd_step: 16 floats per thread, 64 .. kNormBlocks workgroups
-  nb = nb < 64 ? 64 : (nb > kNormBlocks ? kNormBlocks : nb);
+  const int nb = kExt ? norm_blocks(count) : kNormBlocks;
   // (always launched: it also advances the step counter)
-  hipLaunchKernelGGL(sqnorm_stage1_count_skip, dim3(nb), dim3(256), 0, s, grads, count, grad_scale, partial, step_counter, ext_lo, ext_hi);
-  const int64_t live = ext_applied_elsewhere ? count - (ext_hi - ext_lo) : count;
-  int blocks = (int)((live + 1023) / 1024);
-  blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
-  const int64_t skip_lo = ext_applied_elsewhere ? ext_lo : 0, skip_hi = ext_applied_elsewhere ? ext_hi : 0;
-  if (!clip_on) fc = FlatClip{};  // bound 0: the kernel's plain arm
-  hipLaunchKernelGGL(adam_apply_ext_kernel, dim3(blocks), dim3(256), 0, s, params, grads, exp_avg, exp_avg_sq, count, lr, beta1, beta2,
-                     eps, weight_decay, max_norm, grad_scale, step_counter, partial, nb, norm_out, ext_partial, ext_count, coef_out, skip_lo,
-                     skip_hi, lr_dev, fc, fe);
+  hipLaunchKernelGGL(sqnorm_stage1_count<kExt>, dim3(nb), dim3(256), 0, s, grads, count, grad_scale, partial, step_counter, x.lo, x.hi);
+  hipLaunchKernelGGL(adam_apply_ext_kernel<kExt>, dim3(apply_blocks(x.live)), dim3(256), 0, s, params, grads, exp_avg, exp_avg_sq, count, lr,
+                     beta1, beta2, eps, weight_decay, max_norm, grad_scale, step_counter, partial, nb, norm_out, x.partial, x.count, x.coef_out,
+                     x.skip_lo, x.skip_hi, lr_dev, f.fc, f.fe);
   return nnue_launch_status(who);
 }
 }  // namespace
@@ -1080,8 +952,8 @@ extern "C" int nnue_sgd_step(float* params, float* grads, float* momentum_buf, i
                              float* ste_d_thr, float* ste_d_weight, const float* ext_partial, int ext_count, int64_t ext_lo,
                              int64_t ext_hi, float* coef_out, int ext_applied_elsewhere, const float* lr_dev, nnue_stream_t stream) {
   return sgd_step_impl("nnue_sgd_step", params, grads, momentum_buf, count, lr, momentum, weight_decay, max_norm, grad_scale, first_step, norm_out,
-                       scratch, scratch_bytes, ste_partial, ste_chunks, ste_fps, ste_d_thr, ste_d_weight, ext_partial, ext_count, ext_lo, ext_hi,
-                       coef_out, ext_applied_elsewhere, lr_dev, 0.0f, nullptr, 0, nullptr, 0.0f, nullptr, stream);
+                       scratch, scratch_bytes, ste_partial, ste_chunks, ste_fps, ste_d_thr, ste_d_weight,
+                       ExtRange{ext_partial, ext_count, ext_lo, ext_hi, coef_out, ext_applied_elsewhere}, lr_dev, {}, stream);
 }
 
 extern "C" int nnue_sgd_step_clip(float* params, float* grads, float* momentum_buf, int64_t count, float lr, float momentum,
@@ -1091,8 +963,9 @@ extern "C" int nnue_sgd_step_clip(float* params, float* grads, float* momentum_b
                                   int64_t ext_hi, float* coef_out, int ext_applied_elsewhere, const float* lr_dev, float weight_clip,
                                   const int64_t* clip_ranges, int n_clip_ranges, nnue_stream_t stream) {
   return sgd_step_impl("nnue_sgd_step_clip", params, grads, momentum_buf, count, lr, momentum, weight_decay, max_norm, grad_scale, first_step,
-                       norm_out, scratch, scratch_bytes, ste_partial, ste_chunks, ste_fps, ste_d_thr, ste_d_weight, ext_partial, ext_count, ext_lo,
-                       ext_hi, coef_out, ext_applied_elsewhere, lr_dev, weight_clip, clip_ranges, n_clip_ranges, nullptr, 0.0f, nullptr, stream);
+                       norm_out, scratch, scratch_bytes, ste_partial, ste_chunks, ste_fps, ste_d_thr, ste_d_weight,
+                       ExtRange{ext_partial, ext_count, ext_lo, ext_hi, coef_out, ext_applied_elsewhere}, lr_dev,
+                       {weight_clip, clip_ranges, n_clip_ranges}, stream);
 }
 
 extern "C" int nnue_sgd_step_ema(float* params, float* grads, float* momentum_buf, int64_t count, float lr, float momentum,
@@ -1103,8 +976,35 @@ extern "C" int nnue_sgd_step_ema(float* params, float* grads, float* momentum_bu
                                  const int64_t* clip_ranges, int n_clip_ranges, float* ema, float ema_omd, const float* ema_omd_dev,
                                  nnue_stream_t stream) {
   return sgd_step_impl("nnue_sgd_step_ema", params, grads, momentum_buf, count, lr, momentum, weight_decay, max_norm, grad_scale, first_step,
-                       norm_out, scratch, scratch_bytes, ste_partial, ste_chunks, ste_fps, ste_d_thr, ste_d_weight, ext_partial, ext_count, ext_lo,
-                       ext_hi, coef_out, ext_applied_elsewhere, lr_dev, weight_clip, clip_ranges, n_clip_ranges, ema, ema_omd, ema_omd_dev, stream);
+                       norm_out, scratch, scratch_bytes, ste_partial, ste_chunks, ste_fps, ste_d_thr, ste_d_weight,
+                       ExtRange{ext_partial, ext_count, ext_lo, ext_hi, coef_out, ext_applied_elsewhere}, lr_dev,
+                       {weight_clip, clip_ranges, n_clip_ranges, ema, ema_omd, ema_omd_dev}, stream);
+}
+
+extern "C" int nnue_adam_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int32_t* step_counter, int64_t count,
+                              float lr, float beta1, float beta2, float eps, float weight_decay, float max_norm, float grad_scale,
+                              float* norm_out, void* scratch, int64_t scratch_bytes, const float* lr_dev, nnue_stream_t stream) {
+  return adam_step_impl<false>("nnue_adam_step", params, grads, exp_avg, exp_avg_sq, step_counter, count, lr, beta1, beta2, eps, weight_decay,
+                               max_norm, grad_scale, norm_out, scratch, scratch_bytes, ExtRange{}, lr_dev, {}, stream);
+}
+
+extern "C" int nnue_adam_step_clip(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int32_t* step_counter, int64_t count,
+                                   float lr, float beta1, float beta2, float eps, float weight_decay, float max_norm, float grad_scale,
+                                   float* norm_out, void* scratch, int64_t scratch_bytes, const float* lr_dev, float weight_clip,
+                                   const int64_t* clip_ranges, int n_clip_ranges, nnue_stream_t stream) {
+  return adam_step_impl<false>("nnue_adam_step_clip", params, grads, exp_avg, exp_avg_sq, step_counter, count, lr, beta1, beta2, eps, weight_decay,
+                               max_norm, grad_scale, norm_out, scratch, scratch_bytes, ExtRange{}, lr_dev,
+                               {weight_clip, clip_ranges, n_clip_ranges}, stream);
+}
+
+extern "C" int nnue_adam_step_ema(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int32_t* step_counter, int64_t count,
+                                  float lr, float beta1, float beta2, float eps, float weight_decay, float max_norm, float grad_scale,
+                                  float* norm_out, void* scratch, int64_t scratch_bytes, const float* lr_dev, float weight_clip,
+                                  const int64_t* clip_ranges, int n_clip_ranges, float* ema, float ema_omd, const float* ema_omd_dev,
+                                  nnue_stream_t stream) {
+  return adam_step_impl<false>("nnue_adam_step_ema", params, grads, exp_avg, exp_avg_sq, step_counter, count, lr, beta1, beta2, eps, weight_decay,
+                               max_norm, grad_scale, norm_out, scratch, scratch_bytes, ExtRange{}, lr_dev,
+                               {weight_clip, clip_ranges, n_clip_ranges, ema, ema_omd, ema_omd_dev}, stream);
 }
 
 extern "C" int nnue_adam_step_ext(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int32_t* step_counter, int64_t count,
@@ -1112,9 +1012,9 @@ extern "C" int nnue_adam_step_ext(float* params, float* grads, float* exp_avg, f
                                   float* norm_out, void* scratch, int64_t scratch_bytes, const float* ext_partial, int ext_count,
                                   int64_t ext_lo, int64_t ext_hi, float* coef_out, int ext_applied_elsewhere, const float* lr_dev,
                                   nnue_stream_t stream) {
-  return adam_step_ext_impl("nnue_adam_step_ext", params, grads, exp_avg, exp_avg_sq, step_counter, count, lr, beta1, beta2, eps, weight_decay,
-                            max_norm, grad_scale, norm_out, scratch, scratch_bytes, ext_partial, ext_count, ext_lo, ext_hi, coef_out,
-                            ext_applied_elsewhere, lr_dev, 0.0f, nullptr, 0, nullptr, 0.0f, nullptr, stream);
+  return adam_step_impl<true>("nnue_adam_step_ext", params, grads, exp_avg, exp_avg_sq, step_counter, count, lr, beta1, beta2, eps, weight_decay,
+                              max_norm, grad_scale, norm_out, scratch, scratch_bytes,
+                              ExtRange{ext_partial, ext_count, ext_lo, ext_hi, coef_out, ext_applied_elsewhere}, lr_dev, {}, stream);
 }
 
 extern "C" int nnue_adam_step_ext_clip(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int32_t* step_counter, int64_t count,
@@ -1122,9 +1022,10 @@ extern "C" int nnue_adam_step_ext_clip(float* params, float* grads, float* exp_a
                                        float* norm_out, void* scratch, int64_t scratch_bytes, const float* ext_partial, int ext_count,
                                        int64_t ext_lo, int64_t ext_hi, float* coef_out, int ext_applied_elsewhere, const float* lr_dev,
                                        float weight_clip, const int64_t* clip_ranges, int n_clip_ranges, nnue_stream_t stream) {
-  return adam_step_ext_impl("nnue_adam_step_ext_clip", params, grads, exp_avg, exp_avg_sq, step_counter, count, lr, beta1, beta2, eps,
-                            weight_decay, max_norm, grad_scale, norm_out, scratch, scratch_bytes, ext_partial, ext_count, ext_lo, ext_hi, coef_out,
-                            ext_applied_elsewhere, lr_dev, weight_clip, clip_ranges, n_clip_ranges, nullptr, 0.0f, nullptr, stream);
+  return adam_step_impl<true>("nnue_adam_step_ext_clip", params, grads, exp_avg, exp_avg_sq, step_counter, count, lr, beta1, beta2, eps,
+                              weight_decay, max_norm, grad_scale, norm_out, scratch, scratch_bytes,
+                              ExtRange{ext_partial, ext_count, ext_lo, ext_hi, coef_out, ext_applied_elsewhere}, lr_dev,
+                              {weight_clip, clip_ranges, n_clip_ranges}, stream);
 }
 
 extern "C" int nnue_adam_step_ext_ema(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int32_t* step_counter, int64_t count,
@@ -1133,9 +1034,10 @@ extern "C" int nnue_adam_step_ext_ema(float* params, float* grads, float* exp_av
                                       int64_t ext_lo, int64_t ext_hi, float* coef_out, int ext_applied_elsewhere, const float* lr_dev,
                                       float weight_clip, const int64_t* clip_ranges, int n_clip_ranges, float* ema, float ema_omd,
                                       const float* ema_omd_dev, nnue_stream_t stream) {
-  return adam_step_ext_impl("nnue_adam_step_ext_ema", params, grads, exp_avg, exp_avg_sq, step_counter, count, lr, beta1, beta2, eps,
-                            weight_decay, max_norm, grad_scale, norm_out, scratch, scratch_bytes, ext_partial, ext_count, ext_lo, ext_hi, coef_out,
-                            ext_applied_elsewhere, lr_dev, weight_clip, clip_ranges, n_clip_ranges, ema, ema_omd, ema_omd_dev, stream);
+  return adam_step_impl<true>("nnue_adam_step_ext_ema", params, grads, exp_avg, exp_avg_sq, step_counter, count, lr, beta1, beta2, eps,
+                              weight_decay, max_norm, grad_scale, norm_out, scratch, scratch_bytes,
+                              ExtRange{ext_partial, ext_count, ext_lo, ext_hi, coef_out, ext_applied_elsewhere}, lr_dev,
+                              {weight_clip, clip_ranges, n_clip_ranges, ema, ema_omd, ema_omd_dev}, stream);
 }
 
 // The stand-alone pass of the weight average (include/nnue_hip.h, "weight average"): ema <- ema_update(ema, params, omd) over

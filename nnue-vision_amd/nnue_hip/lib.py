@@ -249,11 +249,15 @@ SIGNATURES = {
     # (ema, ema_omd, ema_omd_dev -- the multi-tensor forms: ema[], ema_omd[]) in front of the stream
     "nnue_ema_update": (_c_int, [_c_p, _c_p, _c_i64, _c_f, _c_p, _c_p]),
 }
-for _name in ("nnue_sgd_step", "nnue_adam_step", "nnue_adam_step_ext", "nnue_ftm_backward_weight_update", "nnue_ftm_backward_weight_update_forward",
-              "nnue_ftm_backward_weight_update_adam", "nnue_ftm_backward_weight_update_forward_adam"):
+# the optimizer updates that have a _clip and an _ema sibling with one bound and one average (the multi-tensor forms take lists)
+_UPDATE_ENTRY_POINTS = ("nnue_sgd_step", "nnue_adam_step", "nnue_adam_step_ext", "nnue_ftm_backward_weight_update",
+                        "nnue_ftm_backward_weight_update_forward", "nnue_ftm_backward_weight_update_adam",
+                        "nnue_ftm_backward_weight_update_forward_adam")
+_MULTI_UPDATE_ENTRY_POINTS = ("nnue_multi_sgd_step", "nnue_multi_adam_step")  # (timed under their own names: not in _TIMED_AS)
+for _name in _UPDATE_ENTRY_POINTS:
     _res, _args = SIGNATURES[_name + "_clip"]
     SIGNATURES[_name + "_ema"] = (_res, _args[:-1] + [_c_p, _c_f, _c_p, _c_p])
-for _name in ("nnue_multi_sgd_step", "nnue_multi_adam_step"):
+for _name in _MULTI_UPDATE_ENTRY_POINTS:
     _res, _args = SIGNATURES[_name + "_clip"]
     SIGNATURES[_name + "_ema"] = (_res, _args[:-1] + [_c_p, _c_p, _c_p])
 
@@ -326,16 +330,7 @@ class time_calls:
 
 
 # entry points timed under the name of the call they replace (a caller's timer keys name the plain forms)
-_TIMED_AS = {"nnue_sgd_step_ema": "nnue_sgd_step", "nnue_adam_step_ema": "nnue_adam_step", "nnue_adam_step_ext_ema": "nnue_adam_step_ext",
-             "nnue_ftm_backward_weight_update_ema": "nnue_ftm_backward_weight_update",
-             "nnue_ftm_backward_weight_update_forward_ema": "nnue_ftm_backward_weight_update_forward",
-             "nnue_ftm_backward_weight_update_adam_ema": "nnue_ftm_backward_weight_update_adam",
-             "nnue_ftm_backward_weight_update_forward_adam_ema": "nnue_ftm_backward_weight_update_forward_adam",
-             "nnue_sgd_step_clip": "nnue_sgd_step", "nnue_adam_step_clip": "nnue_adam_step", "nnue_adam_step_ext_clip": "nnue_adam_step_ext",
-             "nnue_ftm_backward_weight_update_clip": "nnue_ftm_backward_weight_update",
-             "nnue_ftm_backward_weight_update_forward_clip": "nnue_ftm_backward_weight_update_forward",
-             "nnue_ftm_backward_weight_update_adam_clip": "nnue_ftm_backward_weight_update_adam",
-             "nnue_ftm_backward_weight_update_forward_adam_clip": "nnue_ftm_backward_weight_update_forward_adam",
+_TIMED_AS = {**{_name + _suffix: _name for _suffix in ("_ema", "_clip") for _name in _UPDATE_ENTRY_POINTS},
              "nnue_ftm_conv_binarize_planes": "nnue_ftm_conv_binarize", "nnue_ftm_forward_l1_planes": "nnue_ftm_forward_l1",
              "nnue_ftm_conv_binarize_value_planes": "nnue_ftm_conv_binarize", "nnue_ftm_backward_planes": "nnue_ftm_backward",
              "nnue_classifier_train_step_soft": "nnue_classifier_train_step",

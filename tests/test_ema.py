@@ -41,6 +41,18 @@ def test_the_exports_exist_with_the_documented_signatures():
         tail = "float* const* ema, const float* ema_omd" if multi else "float* ema, float ema_omd, const float* ema_omd_dev"
         assert ema == f"{head}, {tail}, nnue_stream_t stream", name  # the _clip sibling's arguments plus the average's
         assert len(lib.SIGNATURES[name + "_ema"][1]) == len(lib.SIGNATURES[name + "_clip"][1]) + (2 if multi else 3)
+    # the siblings are timed under the plain form's name (bench.py's timer keys name the plain forms): the 14 rows, spelled out
+    assert {k: v for k, v in lib._TIMED_AS.items() if k.endswith(("_clip", "_ema"))} == {
+        "nnue_sgd_step_ema": "nnue_sgd_step", "nnue_adam_step_ema": "nnue_adam_step", "nnue_adam_step_ext_ema": "nnue_adam_step_ext",
+        "nnue_ftm_backward_weight_update_ema": "nnue_ftm_backward_weight_update",
+        "nnue_ftm_backward_weight_update_forward_ema": "nnue_ftm_backward_weight_update_forward",
+        "nnue_ftm_backward_weight_update_adam_ema": "nnue_ftm_backward_weight_update_adam",
+        "nnue_ftm_backward_weight_update_forward_adam_ema": "nnue_ftm_backward_weight_update_forward_adam",
+        "nnue_sgd_step_clip": "nnue_sgd_step", "nnue_adam_step_clip": "nnue_adam_step", "nnue_adam_step_ext_clip": "nnue_adam_step_ext",
+        "nnue_ftm_backward_weight_update_clip": "nnue_ftm_backward_weight_update",
+        "nnue_ftm_backward_weight_update_forward_clip": "nnue_ftm_backward_weight_update_forward",
+        "nnue_ftm_backward_weight_update_adam_clip": "nnue_ftm_backward_weight_update_adam",
+        "nnue_ftm_backward_weight_update_forward_adam_clip": "nnue_ftm_backward_weight_update_forward_adam"}
 
 
 def test_the_entry_points_refuse_bad_arguments_without_launching():
